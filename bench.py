@@ -18,6 +18,10 @@ Prints ONE JSON line (rank 0) with the driver's contract keys plus
                 attached to the launches of the TIMED region, its share, bound and recomputable fraction)
   cpu_baseline: the CPU oracle (a restatement of MonteCarlo.jl's algorithm, NOT the Julia package itself) timed on all
                 host cores of this box on a bounded sample, plus the same with its dense products routed to OpenBLAS
+
+--steps K sets the number of timed steps; `ms_per_step` is the wall time of one of them.  --dump-outputs DIR writes the
+state the last timed step left (HS fields, Green's functions, acceptance counters, measurement sums) as DIR/*.npy, see
+dump_outputs(); the inputs are seeded (BASE_SEED), so two builds can be compared array for array.
 """
 import argparse
 import json
@@ -127,6 +131,39 @@ def cpu_baseline(cfg, n_threads, sweeps_each, use_blas, partial_updates=None):
     return rate, dt, what
 
 
+DUMP_LIMIT_BYTES = 60 * 10 ** 6  # --dump-outputs stays under 64 MB, .npy headers included
+
+
+def dump_outputs(mc, first_walker, out_dir):
+    """--dump-outputs: what the timed sweeps hand a caller, read back right after the last timed step (before the kernel
+    pass moves the chains on) and written as out_dir/<name>.npy:
+      walker_ids   [k]             global ids of the walkers below
+      conf         [k, N, slices]  HS field (+-1) of each walker
+      greens_eff   [k, nb, N, N]   mc.s.greens of each walker (the Green's function the sweep carries)
+      acceptance   [k, 2]          (proposed, accepted) local updates of each walker so far
+      accumulators [size]          measurement sums of this rank (include/dqmc_hip.h layout; zero before the first
+                                   measurement, its last entry is the sample count)
+    All walkers when they fit in DUMP_LIMIT_BYTES, else a fixed sample of k of them drawn with BASE_SEED."""
+    import numpy as np
+    W, n, nb, M = mc.n_walkers, mc.N, mc.nb, mc.p.slices
+    acc = mc.accumulators()
+    per_walker = nb * n * n * 8 + n * M * 4 + 3 * 8
+    k = max(1, min(W, (DUMP_LIMIT_BYTES - acc.nbytes) // per_walker))
+    idx = np.arange(W) if k == W else np.sort(np.random.default_rng(BASE_SEED).choice(W, k, replace=False))
+    stats = [mc.analysis(int(w)) for w in idx]
+    out = {
+        "walker_ids": (first_walker + idx).astype(np.float64),
+        "conf": np.stack([mc.conf(int(w)) for w in idx]).astype(np.float32),
+        "greens_eff": np.stack([np.stack(mc.greens_eff(int(w))) for w in idx]),
+        "acceptance": np.array([[s.prop_local, s.acc_local] for s in stats], dtype=np.float64),
+        "accumulators": acc,
+    }
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    return {"dir": out_dir, "walkers": int(k), "of": int(W), "bytes": int(sum(a.nbytes for a in out.values()))}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -137,6 +174,8 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sweeps", type=int, default=5)
     ap.add_argument("--no-kernel-timing", action="store_true", help="no HIP events on the launches of the timed region")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the state the last timed step left (rank 0) as DIR/<name>.npy, see dump_outputs()")
     ap.add_argument("--cpu-leg", choices=("port", "blas"), default=None,
                     help="internal: run only this CPU baseline leg (child process, never touches the GPU)")
     ap.add_argument("--cpu-threads", type=int, default=0)
@@ -148,6 +187,8 @@ def main():
         return
     steps = args.steps if args.steps is not None else cfg["steps"]
     warmup = args.warmup if args.warmup is not None else cfg["warmup"]
+    if steps < 1 or warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # bare `bench.py --gpus N` (no launcher): start N fresh ranks, one per GPU, BEFORE anything in this process
@@ -256,6 +297,7 @@ def main():
         tmax = torch.tensor([dt], dtype=torch.float64, device="cpu" if one_dev else "cuda:%d" % dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
+    dumped = dump_outputs(mc, first, args.dump_outputs) if args.dump_outputs and rank == 0 else None
     # Kernel pass: the same K steps once more with HIP events attached to every launch (drained after its own timer
     # stops).  Kept apart from the region `value` is taken from, because the events themselves cost ~4 us per launch
     # (about 2900 launches per sweep); the family times add up to less than THIS pass's time per step.
@@ -428,6 +470,8 @@ def main():
                          "frac_of_fp64_peak", "algorithmic_GBps", "frac_of_hbm_peak", "pmc_GBps",
                          "pmc_frac_of_hbm_peak")}},
     }
+    if dumped is not None:
+        out["dump_outputs"] = dumped
     if rank == 0 and n_gpus == 1 and not args.no_cpu_baseline:
         import subprocess
         cores, visible = effective_cores()
