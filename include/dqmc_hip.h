@@ -221,12 +221,26 @@ int dqmc_combined_iterator_next(dqmc_handle *h, int32_t *l);
  * packed kernels :76-92,158-192,215-219; HubbardModelAttractive.jl:226-249): the sum over l = 1..slices
  * of kernel(G00, G0l, Gl0, Gll), times delta_tau / n_sites as finish! does.  Needs current_slice == 1
  * and dqmc_set_pair_directions.  Accumulator layout:
- *   [cds n_dirs][sds_x n_dirs][sds_y n_dirs][sds_z n_dirs][ps n_dirs x K x K][samples]
+ *   [cds n_dirs][sds_x n_dirs][sds_y n_dirs][sds_z n_dirs][ps n_dirs x K x K][ccs, see below][samples]
  * dqmc_reset_accumulators clears these sums too. */
 int dqmc_accumulate_susceptibilities(dqmc_handle *h, int32_t recalculate);
 int dqmc_susceptibilities_size(dqmc_handle *h, size_t *n_doubles);
 int dqmc_get_susceptibilities(dqmc_handle *h, double *host_out);
 int dqmc_export_susceptibilities(dqmc_handle *h, void *device_out);
+
+/* current_current_susceptibility (measurements.jl:257-317; attractive override HubbardModelAttractive.jl:250-266)
+ * over EachLocalQuadBySyncedDistance{K} (lattice_iterators.jl:360-467): trg_of[src + n*k] = 0-based target of src
+ * in direction k < K (-1 if none), as for dqmc_set_local_targets; T = mc.s.hopping_matrix, model_kind's number of
+ * n x n column-major blocks (copied).  Needs dqmc_set_pair_directions first.  Once set, every
+ * dqmc_accumulate_susceptibilities also sums cc_kernel(G00, G0l, Gl0, Gll) in the same CombinedGreensIterator pass,
+ * times delta_tau / n_sites (generic.jl:291-294), and the susceptibility layout above gains a section in front of
+ * the sample count:
+ *   [cds][sds_x][sds_y][sds_z][ps n_dirs x K_pc x K_pc if local targets][ccs n_dirs x K_cc][samples]
+ * ccs in Julia's column-major order of output[dir12, dir_ii].  The reference's identity terms stay out as in
+ * measurements.jl:295-309.  dqmc_current_targets_fast_path reports whether the lattice took the LDS kernel
+ * (n_dirs == n_sites, one direction per (src1, src2) for each src1, K <= 8) or the general one. */
+int dqmc_set_current_targets(dqmc_handle *h, const int32_t *trg_of, int32_t K, const double *T);
+int dqmc_current_targets_fast_path(dqmc_handle *h, int32_t *fast);
 
 /* ---- measurement reduction over ranks -------------------
  * One process (or thread) per GPU; walkers never interact, the only collective is the reduction of the measurement

@@ -8,8 +8,8 @@ from ._lib import DQMCError, lib  # noqa: F401
 from .configurations import (CompressedConf, ConfigRecorder, Discarder, compress,  # noqa: F401
                              decompress)
 from . import lattices  # noqa: F401
-from .lattices import (Chain, EachLocalQuadByDistance, EachSitePairByDistance, SquareLattice,  # noqa: F401
-                       build_checkerboard)
+from .lattices import (Chain, EachLocalQuadByDistance, EachLocalQuadBySyncedDistance, EachSitePairByDistance,  # noqa: F401
+                       SquareLattice, build_checkerboard)
 from .models import (HubbardModel, HubbardModelAttractive, HubbardModelRepulsive,  # noqa: F401
                      rand_conf)
 from .sharding import (Communicator, reduce_accumulators, walker_block, walker_range,  # noqa: F401

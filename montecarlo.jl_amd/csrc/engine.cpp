@@ -7,6 +7,7 @@
 // walkers is processed by every launch (grid = units x tiles).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -77,6 +78,10 @@ struct dqmc_handle {
     int *trg_of = nullptr;          // [K][n]
     size_t pc_n = 0;
     double *pc_per_walker = nullptr, *pc_acc = nullptr;
+    int K_cc = 0;                   // EachLocalQuadBySyncedDistance{K} (current_current_susceptibility)
+    std::vector<int> cc_trg_h;      // [K][n]
+    std::vector<double> cc_T;       // mc.s.hopping_matrix, nb blocks n x n
+    CCPlan cc;
     size_t corr_n = 0;
     int current_slice = 0, direction = 0;
     bool prepared = false;
@@ -1365,6 +1370,7 @@ int dqmc_accumulate_greens(dqmc_handle *h)
     }
     return DQMC_OK;
 }
+static int cc_setup(dqmc_handle *h);
 // EachSitePairByDistance(lattice) (lattice_iterators.jl:157-190) as a direction table
 int dqmc_set_pair_directions(dqmc_handle *h, const int32_t *dir_of, int32_t n_dirs)
 {
@@ -1402,6 +1408,7 @@ int dqmc_set_pair_directions(dqmc_handle *h, const int32_t *dir_of, int32_t n_di
     HIPCHK(hipMemcpy(h->pair_src, src.data(), sizeof(int) * n * n, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(h->pair_trg, trg.data(), sizeof(int) * n * n, hipMemcpyHostToDevice));
     HIPCHK(hipStreamSynchronize(h->stream));
+    if (h->K_cc) CHK(cc_setup(h));  // the current-current tables follow the directions
     return DQMC_OK;
 }
 int dqmc_accumulate_correlations(dqmc_handle *h)

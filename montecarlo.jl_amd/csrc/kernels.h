@@ -316,6 +316,29 @@ hipError_t launch_sus_slice(int n, int nb, int model, int n_walkers, const doubl
                             double *per_walker, long per_stride, hipStream_t s);
 hipError_t launch_sus_reduce(int n_walkers, long total, double factor, const double *per_walker, double *acc,
                              hipStream_t s);
+// current_current_susceptibility (cc.hip): target table trg[k][s] (-1 if none) and, per block b, the hopping
+// entries tst[b][k][s] = T_b[s, trg] and tts[b][k][s] = T_b[trg, s].  bsum [walkers][K][n] holds the G00 factor of
+// the pass.  The fast path (fast = true; chosen by the host) needs n_dirs == n and, for every s1, a different dir12
+// for every s2 (dsel[s1][s2] = dir12); the chunk tables describe the LDS panels (see cc.hip).
+constexpr int CC_KMAX = 8;  // largest K of the fast path
+struct CCPlan {
+    int K = 0;
+    const int *trg = nullptr;
+    const double *tst = nullptr, *tts = nullptr;
+    double *bsum = nullptr;
+    bool fast = false;
+    int C = 0, umax = 0, nchunks = 0, chunks_per_wg = 0, n_wg = 0, threads = 0;
+    size_t lds_bytes = 0;
+    const int *dsel = nullptr, *rows = nullptr, *ucnt = nullptr, *slot = nullptr;
+    double *partial = nullptr;  // [walkers][n_wg][K][n] (fast path), [walkers][K][n_dirs] (general kernel)
+};
+hipError_t launch_cc_b(int n, int nb, int n_walkers, int K, double afac, const double *G00, long stride_unit,
+                       const int *trg, const double *tst, const double *tts, double *bsum, hipStream_t s);
+// one time slice added to per_walker[w][offset + dir12 + n_dirs*k] (already divided by n)
+hipError_t launch_cc_slice(const CCPlan &p, int n, int nb, int n_walkers, double afac, double xfac,
+                           const double *G0l, const double *Gl0, const double *Gll, long stride_unit,
+                           const int *dir_ptr, const int *pair_src, const int *pair_trg, int n_dirs,
+                           double *per_walker, long per_stride, long offset, hipStream_t s);
 // HS field <-> Julia BitArray chunks (compress / decompress, HubbardModel.jl:56-59)
 hipError_t launch_conf_pack(const int8_t *conf, size_t n_elem, unsigned long long *chunks, hipStream_t s);
 hipError_t launch_conf_unpack(const unsigned long long *chunks, size_t n_elem, int8_t *conf, hipStream_t s);

@@ -569,10 +569,140 @@ int dqmc_combined_iterator_next(dqmc_handle *h, int32_t *l)
 // ---- susceptibilities: apply!(::CombinedGreensIterator, ...) (generic.jl:226-243) on the device -------------
 // charge_density_susceptibility, spin_density_susceptibility(:x/:y/:z), pairing_susceptibility
 // (measurements.jl:57-58,142-144,207): sum over l of kernel(G00, G0l, Gl0, Gll), finish! * delta_tau / N
+// current_current_susceptibility (measurements.jl:257-317) over EachLocalQuadBySyncedDistance{K}: device tables of
+// cc.hip from the target table, the hopping matrix and the direction tables; picks the LDS path when the lattice
+// allows it (n_dirs == n and, for every s1, a different direction for every s2) and its LDS budget is met.
+static int cc_setup(dqmc_handle *h)
+{
+    const int n = h->n, nb = h->nb, nd = h->n_dirs;
+    if (h->K_cc > nd) {  // directions replaced by a table with fewer of them: the targets no longer apply
+        h->K_cc = 0;
+        h->red_valid = false;
+        return 0;
+    }
+    const int K = h->K_cc;
+    const size_t nK = (size_t)n * K;
+    std::vector<double> tst((size_t)nb * nK, 0.0), tts((size_t)nb * nK, 0.0);
+    for (int b = 0; b < nb; ++b)
+        for (size_t e = 0; e < nK; ++e) {
+            const int s = (int)(e % n), t = h->cc_trg_h[e];
+            if (t < 0) continue;
+            const double *T = h->cc_T.data() + (size_t)b * n * n;
+            tst[b * nK + e] = T[s + (size_t)n * t];
+            tts[b * nK + e] = T[t + (size_t)n * s];
+        }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    CCPlan &p = h->cc;
+    p = CCPlan();
+    p.K = K;
+    int *trg = nullptr;
+    double *dtst = nullptr, *dtts = nullptr;
+    CHK(dalloc(h, &trg, nK));
+    CHK(dalloc(h, &dtst, nb * nK));
+    CHK(dalloc(h, &dtts, nb * nK));
+    CHK(dalloc(h, &p.bsum, (size_t)h->W * nK));
+    HIPCHK(hipMemcpy(trg, h->cc_trg_h.data(), sizeof(int) * nK, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dtst, tst.data(), sizeof(double) * nb * nK, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dtts, tts.data(), sizeof(double) * nb * nK, hipMemcpyHostToDevice));
+    p.trg = trg; p.tst = dtst; p.tts = dtts;
+    h->red_valid = false;
+    CHK(dalloc(h, &p.partial, (size_t)h->W * nd * K));  // (the general kernel's per-slice sums)
+    // fast-path precondition, checked on the direction tables themselves
+    if (K > CC_KMAX || n > 1024 || nd != n) return 0;
+    std::vector<int> ptr(nd + 1), src((size_t)n * n), dst((size_t)n * n);
+    HIPCHK(hipMemcpy(ptr.data(), h->dir_ptr, sizeof(int) * (nd + 1), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(src.data(), h->pair_src, sizeof(int) * n * n, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(dst.data(), h->pair_trg, sizeof(int) * n * n, hipMemcpyDeviceToHost));
+    std::vector<int> dsel((size_t)n * n, -1);
+    std::vector<char> seen((size_t)n * nd, 0);
+    for (int d = 0; d < nd; ++d)
+        for (int q = ptr[d]; q < ptr[d + 1]; ++q) {
+            const int s1 = src[q], s2 = dst[q];
+            if (seen[(size_t)s1 * nd + d]) return 0;  // two s2 of one s1 share a direction
+            seen[(size_t)s1 * nd + d] = 1;
+            dsel[(size_t)s1 * n + s2] = d;
+        }
+    // chunk size: the largest C whose panels fit 80 KiB of LDS (two workgroups per CU)
+    for (int C = 16; C >= 1; C /= 2) {
+        const int nchunks = (n + C - 1) / C;
+        std::vector<std::vector<int>> U(nchunks);
+        std::vector<int> slot((size_t)nchunks * C * (K + 1), -1);
+        int umax = 0;
+        for (int c = 0; c < nchunks; ++c) {
+            std::vector<int> &u = U[c];
+            for (int s = c * C; s < std::min(n, (c + 1) * C); ++s) {
+                u.push_back(s);
+                for (int k = 0; k < K; ++k)
+                    if (h->cc_trg_h[s + (size_t)n * k] >= 0) u.push_back(h->cc_trg_h[s + (size_t)n * k]);
+            }
+            std::sort(u.begin(), u.end());
+            u.erase(std::unique(u.begin(), u.end()), u.end());
+            umax = std::max(umax, (int)u.size());
+            for (int i = 0; i < C && c * C + i < n; ++i) {
+                const int s = c * C + i;
+                int *sl = slot.data() + ((size_t)c * C + i) * (K + 1);
+                sl[0] = (int)(std::lower_bound(u.begin(), u.end(), s) - u.begin());
+                for (int k = 0; k < K; ++k) {
+                    const int t = h->cc_trg_h[s + (size_t)n * k];
+                    sl[k + 1] = t < 0 ? -1 : (int)(std::lower_bound(u.begin(), u.end(), t) - u.begin());
+                }
+            }
+        }
+        const size_t lds = sizeof(double) * (2 * (size_t)umax * n + nK) + sizeof(int) * (size_t)C * n;
+        if (lds > 80 * 1024) continue;
+        std::vector<int> rows((size_t)nchunks * umax, 0), ucnt(nchunks);
+        for (int c = 0; c < nchunks; ++c) {
+            ucnt[c] = (int)U[c].size();
+            std::copy(U[c].begin(), U[c].end(), rows.begin() + (size_t)c * umax);
+        }
+        // about two workgroups per CU over all walkers; each takes a run of chunks
+        const int groups = std::max(1, std::min(nchunks, (512 + h->W - 1) / h->W));
+        p.chunks_per_wg = (nchunks + groups - 1) / groups;
+        p.n_wg = (nchunks + p.chunks_per_wg - 1) / p.chunks_per_wg;
+        p.C = C; p.umax = umax; p.nchunks = nchunks; p.lds_bytes = lds;
+        p.threads = std::min(1024, (n + 63) / 64 * 64);
+        int *ddsel = nullptr, *drows = nullptr, *ducnt = nullptr, *dslot = nullptr;
+        CHK(dalloc(h, &ddsel, (size_t)n * n));
+        CHK(dalloc(h, &drows, rows.size()));
+        CHK(dalloc(h, &ducnt, ucnt.size()));
+        CHK(dalloc(h, &dslot, slot.size()));
+        CHK(dalloc(h, &p.partial, (size_t)h->W * p.n_wg * nK));
+        HIPCHK(hipMemcpy(ddsel, dsel.data(), sizeof(int) * n * n, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(drows, rows.data(), sizeof(int) * rows.size(), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(ducnt, ucnt.data(), sizeof(int) * ucnt.size(), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(dslot, slot.data(), sizeof(int) * slot.size(), hipMemcpyHostToDevice));
+        p.dsel = ddsel; p.rows = drows; p.ucnt = ducnt; p.slot = dslot;
+        p.fast = true;
+        HIPCHK(hipStreamSynchronize(h->stream));
+        return 0;
+    }
+    return 0;
+}
+int dqmc_set_current_targets(dqmc_handle *h, const int32_t *trg_of, int32_t K, const double *T)
+{
+    ENTER(h);
+    const int n = h->n;
+    if (!h->n_dirs) return fail(h, DQMC_ERR_STATE, "call dqmc_set_pair_directions first");
+    if (!trg_of || !T || K < 1 || K > h->n_dirs) return fail(h, DQMC_ERR_INVALID, "bad target table or hopping matrix");
+    for (size_t i = 0; i < (size_t)n * K; ++i)
+        if (trg_of[i] < -1 || trg_of[i] >= n) return fail(h, DQMC_ERR_INVALID, "target index out of range");
+    h->cc_trg_h.assign(trg_of, trg_of + (size_t)n * K);
+    h->cc_T.assign(T, T + (size_t)h->nb * n * n);
+    h->K_cc = K;
+    return cc_setup(h);
+}
+int dqmc_current_targets_fast_path(dqmc_handle *h, int32_t *fast)
+{
+    if (!h || !fast) return DQMC_ERR_INVALID;
+    *fast = h->K_cc && h->cc.fast ? 1 : 0;
+    return DQMC_OK;
+}
+static long ut_cc_offset(dqmc_handle *h) { return 4L * h->n_dirs + (long)h->n_dirs * h->K_loc * h->K_loc; }
 static int ut_sus_layout(dqmc_handle *h)
 {
     UTStack *u = h->ut;
-    const size_t want = 4 * (size_t)h->n_dirs + (size_t)h->n_dirs * h->K_loc * h->K_loc + 1;
+    const size_t want = 4 * (size_t)h->n_dirs + (size_t)h->n_dirs * h->K_loc * h->K_loc
+                        + (size_t)h->n_dirs * h->K_cc + 1;
     if (u->sus_n == want) return 0;
     u->sus_n = want;
     h->red_valid = false;  // (re)sized: the last reduction is void
@@ -591,6 +721,13 @@ int dqmc_accumulate_susceptibilities(dqmc_handle *h, int32_t recalculate)
     CHK(true_greens(h, h->greens));                                 // G00 = greens!(mc)
     CHK(copy_mat(h, u->g00, h->tmp2));
     HIPCHK(hipMemsetAsync(u->sus_per_walker, 0, sizeof(double) * h->W * total, h->stream));  // prepare!
+    // cc_kernel: 4 a b + 2 cross on the attractive model's single block (HubbardModelAttractive.jl:250-266)
+    const double cc_fac = h->p.model_kind == DQMC_ATTRACTIVE ? 2.0 : 1.0;
+    if (h->K_cc) {
+        Timed t(h, DQMC_K_MISC);
+        HIPCHK(launch_cc_b(h->n, h->nb, h->W, h->K_cc, cc_fac, u->g00, h->nn, h->cc.trg, h->cc.tst, h->cc.tts,
+                           h->cc.bsum, h->stream));
+    }
     CHK(ut_cgi_begin(h, recalculate));
     for (;;) {
         int l = -1;
@@ -600,6 +737,10 @@ int dqmc_accumulate_susceptibilities(dqmc_handle *h, int32_t recalculate)
         HIPCHK(launch_sus_slice(h->n, h->nb, h->p.model_kind, h->W, u->g00, u->out[0], u->out[1], u->out[2], h->nn,
                                 h->dir_ptr, h->pair_src, h->pair_trg, h->n_dirs, h->K_loc, h->trg_of, u->sus_per_walker,
                                 total, h->stream));
+        if (h->K_cc)
+            HIPCHK(launch_cc_slice(h->cc, h->n, h->nb, h->W, cc_fac, cc_fac, u->out[0], u->out[1], u->out[2], h->nn,
+                                   h->dir_ptr, h->pair_src, h->pair_trg, h->n_dirs, u->sus_per_walker, total,
+                                   ut_cc_offset(h), h->stream));
     }
     {
         Timed t(h, DQMC_K_MISC);

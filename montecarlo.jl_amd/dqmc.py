@@ -624,7 +624,7 @@ class DQMC:
 
     def susceptibilities(self):
         """-> dict of means: CDS, SDSx, SDSy, SDSz per direction, PS[dir12, dir1, dir2] if local targets
-        are set, count"""
+        are set, CCS[dir12, dir_ii] if current targets are set, count"""
         n = C.c_size_t()
         self._c(lib().dqmc_susceptibilities_size(self._h, C.byref(n)))
         out = np.zeros(n.value)
@@ -634,8 +634,36 @@ class DQMC:
         K = getattr(self, "_K", 0)
         if K:
             res["PS"] = out[4 * nd:4 * nd + nd * K * K].reshape((nd, K, K), order="F") / cnt
+        Kcc = getattr(self, "_Kcc", 0)
+        if Kcc:
+            off = 4 * nd + nd * K * K
+            res["CCS"] = out[off:off + nd * Kcc].reshape((nd, Kcc), order="F") / cnt
         res["count"] = cnt
         return res
+
+    # ---- current_current_susceptibility (measurements.jl:257-317) over EachLocalQuadBySyncedDistance{K}
+    def set_current_targets(self, iterator, hopping=None):
+        """hand the targets of EachLocalQuadBySyncedDistance{K} and mc.s.hopping_matrix (default: the model's
+        hopping_matrix(), one n x n matrix per block) to the device; the pair directions of the same lattice are
+        set with it.  From then on accumulate_susceptibilities also sums CCS[dir12, dir_ii]."""
+        self.set_pair_directions(iterator.pairs_by_dir)
+        blocks = self.model.hopping_matrix() if hopping is None else hopping
+        if isinstance(blocks, np.ndarray) and blocks.ndim == 2:
+            blocks = [blocks]
+        if len(blocks) != self.nb or any(np.shape(b) != (self.N, self.N) for b in blocks):
+            raise ValueError("hopping must be %d matrices of %d x %d" % (self.nb, self.N, self.N))
+        self._cc_T = np.ascontiguousarray(np.concatenate([np.asarray(b, dtype=np.float64).reshape(-1, order="F")
+                                                          for b in blocks]))
+        tab = np.asfortranarray(iterator.trg_of.astype(np.int32))  # [src, k] -> trg_of[src + n*k]
+        self._c(lib().dqmc_set_current_targets(self._h, tab.ctypes.data_as(C.POINTER(C.c_int32)), iterator.K,
+                                               dptr(self._cc_T)))
+        self._Kcc = iterator.K
+
+    def current_targets_fast_path(self):
+        """True when the lattice took the LDS kernel for the current-current sums (see include/dqmc_hip.h)"""
+        f = C.c_int32()
+        self._c(lib().dqmc_current_targets_fast_path(self._h, C.byref(f)))
+        return bool(f.value)
 
     # ---- instrumentation
     def qr_fallbacks(self):

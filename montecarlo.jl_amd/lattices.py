@@ -196,3 +196,66 @@ class EachLocalQuadByDistance:
                             for dir2, trg2 in self.trg_from_src[src2 - 1]:
                                 if dir2 == d2 + 1:
                                     yield lin, src1, trg1, src2, trg2
+
+
+class EachLocalQuadBySyncedDistance:
+    """EachLocalQuadBySyncedDistance{K}(lattice) (src/lattices/lattice_iterators.jl:360-467): quadruples
+    (src1, trg1, src2, trg2) whose two targets are reached in the same direction dir_ii, one of the K
+    shortest, grouped by (dir12, dir_ii) with dir12 the direction index of the pair (src1, src2).
+    `trg_from_src` and `trg_of` as in EachLocalQuadByDistance; `implied[d12][k]` lists the 1-based quads
+    of one cell in the order the reference's `while` loop pushes them (built on first use)."""
+
+    def __init__(self, lattice, K=None, pairs=None):
+        self.pairs_by_dir = pairs if pairs is not None else EachSitePairByDistance(lattice)
+        n = len(lattice)
+        if K is None:  # current_current_susceptibility(): K = 1 + length(neighbors(lattice, 1)) (measurements.jl:257-263)
+            K = 1 + lattice.neighs.shape[0]
+        if K > self.pairs_by_dir.ndirections():
+            raise ValueError("K exceeds the number of directions of the lattice")
+        self.K = K
+        self.trg_from_src = [[] for _ in range(n)]
+        for d in range(K):
+            for src, trg in self.pairs_by_dir.pairs[d]:
+                self.trg_from_src[src - 1].append((d + 1, trg))
+        self.trg_of = -np.ones((n, K), dtype=np.int32)
+        for src, lst in enumerate(self.trg_from_src):
+            for d, trg in lst:
+                if self.trg_of[src, d - 1] >= 0:
+                    raise ValueError("more than one target per direction: lattice with a basis is not supported")
+                self.trg_of[src, d - 1] = trg - 1
+        # every pair (src1, src2) contributes one quad per direction both sources have a target in
+        have = (self.trg_of >= 0).sum(axis=0)
+        self.N = int((have.astype(np.int64) ** 2).sum())
+        self._implied = None
+
+    @property
+    def implied(self):
+        """implied[dir12][dir_ii] (0-based indices into lists of 1-based (src1, trg1, src2, trg2)), as the
+        reference's `while` loop fills it: pair index, then the target i of src1, then the target j of src2"""
+        if self._implied is None:
+            nd = self.pairs_by_dir.ndirections()
+            implied = [[[] for _ in range(self.K)] for _ in range(nd)]
+            for d12, prs in enumerate(self.pairs_by_dir.pairs):
+                cell = implied[d12]
+                for src1, src2 in prs:
+                    for dir1, trg1 in self.trg_from_src[src1 - 1]:
+                        for dir2, trg2 in self.trg_from_src[src2 - 1]:
+                            if dir1 == dir2:
+                                cell[dir1 - 1].append((src1, trg1, src2, trg2))
+            self._implied = implied
+        return self._implied
+
+    def __len__(self):
+        return self.N
+
+    def ndirections(self):
+        return (self.pairs_by_dir.ndirections(), self.K)
+
+    def __iter__(self):
+        """(lin, src1, trg1, src2, trg2), lin the 1-based column-major linear index of (dir12, dir_ii)"""
+        nd, implied = self.pairs_by_dir.ndirections(), self.implied
+        for k in range(self.K):
+            for d12 in range(nd):
+                lin = 1 + d12 + nd * k
+                for quad in implied[d12][k]:
+                    yield (lin,) + quad
