@@ -32,11 +32,12 @@ struct UTStack;  // unequal-time stack (unequal_time.inl)
 
 struct dqmc_handle {
     dqmc_params p{};
-    int n = 0, nb = 1, N = 0, M = 0, s = 0, K = 0, W = 0, units = 0, kd = 32;
+    int n = 0, nb = 1, N = 0, M = 0, s = 0, K = 0, W = 0, units = 0;
     long nn = 0;
     double lambda = 0, epl = 0, eml = 0;
     SweepConsts sc{};
     hipStream_t stream = nullptr;
+    KernelSwitches sw;  // read once, when the handle is set up (read_kernel_switches)
     // constants (nb x n x n)
     double *eT = nullptr, *eTinv = nullptr, *eT2 = nullptr, *eTinv2 = nullptr;
     double *eT2T = nullptr;  // transposed copy of eT2: A operand of the daggered slice products in slab.hip
@@ -61,9 +62,8 @@ struct dqmc_handle {
     int *&pivot = qs[0].pivot;
     double *Dl = nullptr, *Dr = nullptr;
     hipStream_t cur = nullptr;  // the stream the launch helpers use (= stream)
-    double *sU = nullptr, *sVT = nullptr;
     double *greens_alt = nullptr, *lu_img = nullptr;  // decide / apply sweep (sweep_lu.hip)
-    bool sweep_lu = true, sweep_fused = true;
+    bool sweep_fused = true;
     WalkerRng *rng = nullptr;
     DevStats *stats = nullptr;
     unsigned long long *pc_scratch = nullptr;  // prop_check_kernel: partial maximum + arrival counter per walker
@@ -303,12 +303,36 @@ static int set_ones(dqmc_handle *h, double *d)
     return 0;
 }
 
+// The kernel-selection and test switches, read from the environment once per handle / stand-alone
+// primitive call: nothing else reads them (the launchers get them from the handle)
+static void read_kernel_switches(dqmc_handle *h)
+{
+    KernelSwitches &k = h->sw;
+    k.qr_noblocked = getenv("DQMC_QR_NOBLOCKED") != nullptr;
+    if (const char *e = getenv("DQMC_QRB_SITES")) k.qrb_sites = atoi(e) & 7;
+    if (const char *e = getenv("DQMC_QR_TAIL")) k.qr_tail = atoi(e) != 0;
+    k.qr_sc1 = getenv("DQMC_QR_SC1") != nullptr;
+    k.qr_nocoop = getenv("DQMC_QR_NOCOOP") != nullptr;
+    if (const char *e = getenv("DQMC_QR_FORCE_TIMEOUT"))
+        k.qr_force_timeout = strncmp(e, "step:", 5) == 0 ? 2 + atoi(e + 5) : (strncmp(e, "extra:", 6) == 0 ? 1000 + atoi(e + 6) : 1);
+    k.qr_nopanel = getenv("DQMC_QR_NOPANEL") != nullptr;
+    k.trsm_simple = getenv("DQMC_TRSM_SIMPLE") != nullptr;
+    k.sweep_split = getenv("DQMC_SWEEP_SPLIT") != nullptr;
+    k.flush_ncp2 = getenv("DQMC_FLUSH_NCP2") != nullptr;
+    k.no_slab = getenv("DQMC_NO_SLAB") != nullptr;
+}
+
 static int alloc_qr_workspace(dqmc_handle *h)
 {
     // device-side error word (bit 1: a hand-off inside the sweep elimination kernel timed out; bit 0 is no longer set by
     // anything: a cooperative-QR time-out is not an error since round 2, the guarded kernel behind the launch redoes
     // the factorisation and dqmc_qr_fallbacks counts it)
     CHK(dalloc(h, &h->qr_ws.errflag, (size_t)1));
+    h->qr_ws.tail = h->sw.qr_tail;
+    h->qr_ws.force_sc1 = h->sw.qr_sc1;
+    h->qr_ws.no_coop = h->sw.qr_nocoop;
+    h->qr_ws.no_panel = h->sw.qr_nopanel;
+    h->qr_ws.force_timeout = h->sw.qr_force_timeout;
     if (h->n > 256) return 0;
     hipDeviceProp_t prop;
     HIPCHK(hipGetDeviceProperties(&prop, h->p.device_id));
@@ -318,22 +342,16 @@ static int alloc_qr_workspace(dqmc_handle *h)
     // co-residency: what the occupancy API reports for the kernel on this device (its ~200 VGPRs admit 2 per CU)
     h->qr_ws.max_blocks = prop.multiProcessorCount * qr_coop_blocks_per_cu();
     h->qr_ws.epoch = 0;
-    if (const char *e = getenv("DQMC_QR_TAIL")) h->qr_ws.tail_j0 = atoi(e);  // A/B switches, read per handle
-    h->qr_ws.force_sc1 = getenv("DQMC_QR_SC1") != nullptr;
-    h->qr_ws.no_coop = getenv("DQMC_QR_NOCOOP") != nullptr;
-    if (const char *e = getenv("DQMC_QR_FORCE_TIMEOUT"))
-        h->qr_ws.force_timeout = strncmp(e, "step:", 5) == 0 ? 2 + atoi(e + 5) : (strncmp(e, "extra:", 6) == 0 ? 1000 + atoi(e + 6) : 1);
     // pre-pivoted blocked UDT in one launch (qrb.hip): n == 256, all eight workgroups of every unit co-resident.
     // DQMC_QR_NOBLOCKED: off; DQMC_QRB_SITES: bit mask of the call sites that use it (1 = slice-sequence builds and every other
     // caller, 2 = first, 4 = second factorisation of calculate_greens_AVX!)
     h->qrb_sites = 0;
-    if (h->n == 256 && getenv("DQMC_QR_NOBLOCKED") == nullptr) {
+    if (h->n == 256 && !h->sw.qr_noblocked) {
         const int per_cu = qrb_blocks_per_cu();
         if (per_cu >= 1 && ((h->units + 7) / 8) * 64 <= prop.multiProcessorCount * per_cu) {
             CHK(dalloc(h, (char **)&h->qr_ws.mailbox2, qrb_mailbox_bytes(h->units)));
             h->qr_ws.blk_max_blocks = prop.multiProcessorCount * per_cu;
-            h->qrb_sites = 7;
-            if (const char *e = getenv("DQMC_QRB_SITES")) h->qrb_sites = atoi(e) & 7;
+            h->qrb_sites = h->sw.qrb_sites;
         }
     }
     return 0;
@@ -386,7 +404,7 @@ static int udt_formq(dqmc_handle *h, double *Uout, QrSet &q, double *winv, doubl
     CHK(run_gemm(h, g));
     {
         Timed t(h, DQMC_K_TRSM);
-        HIPCHK(launch_trsm_right_upper(n, h->units, q.V, h->nn, q.S, h->nn, nullptr, q.tau, n, q.W, h->nn, winv, h->cur, ts));
+        HIPCHK(launch_trsm_right_upper(n, h->units, q.V, h->nn, q.S, h->nn, nullptr, q.tau, n, q.W, h->nn, winv, h->sw, h->cur, ts));
     }
     g = gemm_base(h, U_(h, q.W), 0, U_(h, q.V), 1, Uout);
     g.alpha = -1.0;
@@ -416,7 +434,7 @@ static int udt(dqmc_handle *h, double *A, double *Uout, double *Dout, double *To
 static int rdivp_set(dqmc_handle *h, const double *A, const double *T, double *Out, const QrSet &q, double *winv, double *ts)
 {
     Timed t(h, DQMC_K_TRSM);
-    HIPCHK(launch_trsm_right_upper(h->n, h->units, A, h->nn, T, h->nn, q.pivot, nullptr, 0, Out, h->nn, winv, h->cur, ts));
+    HIPCHK(launch_trsm_right_upper(h->n, h->units, A, h->nn, T, h->nn, q.pivot, nullptr, 0, Out, h->nn, winv, h->sw, h->cur, ts));
     return 0;
 }
 static int rdivp(dqmc_handle *h, double *A, const double *T)
@@ -791,81 +809,46 @@ static int sweep_spatial_launches(dqmc_handle *h)
     const int l = h->current_slice;
     int8_t *cslice = h->conf + (long)(l - 1) * h->N;
     h->conf_version++;
-    if (h->sweep_lu) {
-        // decide on the 64 x 64 block (four waves per walker), apply the chunk out of place with MFMA
-        double *cur = h->greens, *alt = h->greens_alt;
-        const size_t istr = (size_t)h->units * sweep_lu_image_doubles();
-        const long cstr = (long)h->N * h->M;
-        hipEvent_t a, b;
-        if (h->sweep_fused && h->n % 64 == 0 && h->N >= 128) {
-            // the elimination of chunk c runs beside the flush of chunk c - 1 (one launch per chunk boundary)
-            const int nc = h->N / 64;
+    // decide on the 64 x 64 block (four waves per walker), apply the chunk out of place with MFMA
+    double *cur = h->greens, *alt = h->greens_alt;
+    const size_t istr = (size_t)h->units * sweep_lu_image_doubles();
+    const long cstr = (long)h->N * h->M;
+    hipEvent_t a, b;
+    if (h->sweep_fused && h->n % 64 == 0 && h->N >= 128) {
+        // the elimination of chunk c runs beside the flush of chunk c - 1 (one launch per chunk boundary)
+        const int nc = h->N / 64;
+        timing_events(h, &a, &b);
+        HIPCHK(launch_sweep_lu(h->n, h->nb, h->W, cur, h->nn, cslice, cstr, 0, 64, h->lu_img, h->sc, h->rng, h->stats,
+                               h->p.check_sign_problem, h->qr_ws.errflag, h->cur, a, b));
+        CHK(timing_push(h, a, b, DQMC_K_SWEEP));
+        for (int c = 1; c < nc; ++c) {
             timing_events(h, &a, &b);
-            HIPCHK(launch_sweep_lu(h->n, h->nb, h->W, cur, h->nn, cslice, cstr, 0, 64, h->lu_img, h->sc, h->rng, h->stats,
-                                   h->p.check_sign_problem, h->qr_ws.errflag, h->cur, a, b));
+            HIPCHK(launch_sweep_fused(h->n, h->nb, h->W, cur, alt, h->nn, cslice, cstr, 64 * c, 64 * (c - 1),
+                                      h->lu_img + (size_t)(c & 1) * istr, h->lu_img + (size_t)((c - 1) & 1) * istr, h->sc,
+                                      h->rng, h->stats, h->p.check_sign_problem, h->qr_ws.errflag, h->cur, a, b));
             CHK(timing_push(h, a, b, DQMC_K_SWEEP));
-            for (int c = 1; c < nc; ++c) {
-                timing_events(h, &a, &b);
-                HIPCHK(launch_sweep_fused(h->n, h->nb, h->W, cur, alt, h->nn, cslice, cstr, 64 * c, 64 * (c - 1),
-                                          h->lu_img + (size_t)(c & 1) * istr, h->lu_img + (size_t)((c - 1) & 1) * istr, h->sc,
-                                          h->rng, h->stats, h->p.check_sign_problem, h->qr_ws.errflag, h->cur, a, b));
-                CHK(timing_push(h, a, b, DQMC_K_SWEEP));
-                std::swap(cur, alt);
-            }
-            timing_events(h, &a, &b);
-            HIPCHK(launch_sweep_flush_lu(h->n, h->units, cur, alt, h->nn, 64 * (nc - 1), 64,
-                                         h->lu_img + (size_t)((nc - 1) & 1) * istr, h->cur, a, b));
-            CHK(timing_push(h, a, b, DQMC_K_FLUSH));
-            std::swap(cur, alt);
-            if (cur != h->greens) std::swap(h->greens, h->greens_alt);
-            return 0;
-        }
-        for (int site0 = 0; site0 < h->N; site0 += 64) {
-            const int ns = std::min(64, h->N - site0);
-            timing_events(h, &a, &b);
-            HIPCHK(launch_sweep_lu(h->n, h->nb, h->W, cur, h->nn, cslice, cstr, site0, ns, h->lu_img, h->sc,
-                                   h->rng, h->stats, h->p.check_sign_problem, h->qr_ws.errflag, h->cur, a, b));
-            CHK(timing_push(h, a, b, DQMC_K_SWEEP));
-            timing_events(h, &a, &b);
-            HIPCHK(launch_sweep_flush_lu(h->n, h->units, cur, alt, h->nn, site0, ns, h->lu_img, h->cur, a, b));
-            CHK(timing_push(h, a, b, DQMC_K_FLUSH));
             std::swap(cur, alt);
         }
+        timing_events(h, &a, &b);
+        HIPCHK(launch_sweep_flush_lu(h->n, h->units, cur, alt, h->nn, 64 * (nc - 1), 64,
+                                     h->lu_img + (size_t)((nc - 1) & 1) * istr, h->sw, h->cur, a, b));
+        CHK(timing_push(h, a, b, DQMC_K_FLUSH));
+        std::swap(cur, alt);
         if (cur != h->greens) std::swap(h->greens, h->greens_alt);
         return 0;
     }
-    for (int site0 = 0; site0 < h->N; site0 += h->kd) {
-        const int ns = std::min(h->kd, h->N - site0);
-        {
-            Timed t(h, DQMC_K_SWEEP);
-            HIPCHK(launch_sweep_chunk(h->n, h->nb, h->W, h->p.model_kind, h->greens, h->nn, cslice, (long)h->N * h->M,
-                                      site0, ns, h->sU, h->sVT, (long)h->n * h->kd, h->sc, h->rng, h->stats,
-                                      h->p.check_sign_problem, h->cur));
-        }
-        if (h->n % 64 == 0 && h->kd == 64) {  // dedicated flush kernel (whole K in LDS, C requested first)
-            hipEvent_t a = nullptr, b = nullptr;
-            if (h->timing) {
-                auto get = [&]() {
-                    hipEvent_t ev;
-                    if (!h->pool.empty()) { ev = h->pool.back(); h->pool.pop_back(); }
-                    else (void)hipEventCreate(&ev);
-                    return ev;
-                };
-                a = get(); b = get();
-            }
-            HIPCHK(launch_gemm_flush(h->n, h->units, h->sU, h->sVT, (long)h->n * h->kd, h->greens, h->nn, h->cur, a, b));
-            if (h->timing) {
-                h->pending.push_back({a, b, DQMC_K_GEMM});
-                if (h->pending.size() >= 2048) CHK(timing_drain(h));
-            }
-            continue;
-        }
-        GemmArgs g = gemm_base(h, mat(h->sU, (long)h->n * h->kd, h->n), 0, mat(h->sVT, (long)h->n * h->kd, h->n), 1,
-                               h->greens);
-        g.K = h->kd;
-        g.beta = 1;
-        CHK(run_gemm(h, g));
+    for (int site0 = 0; site0 < h->N; site0 += 64) {
+        const int ns = std::min(64, h->N - site0);
+        timing_events(h, &a, &b);
+        HIPCHK(launch_sweep_lu(h->n, h->nb, h->W, cur, h->nn, cslice, cstr, site0, ns, h->lu_img, h->sc,
+                               h->rng, h->stats, h->p.check_sign_problem, h->qr_ws.errflag, h->cur, a, b));
+        CHK(timing_push(h, a, b, DQMC_K_SWEEP));
+        timing_events(h, &a, &b);
+        HIPCHK(launch_sweep_flush_lu(h->n, h->units, cur, alt, h->nn, site0, ns, h->lu_img, h->sw, h->cur, a, b));
+        CHK(timing_push(h, a, b, DQMC_K_FLUSH));
+        std::swap(cur, alt);
     }
+    if (cur != h->greens) std::swap(h->greens, h->greens_alt);
     return 0;
 }
 
@@ -887,7 +870,6 @@ int dqmc_create(const dqmc_params *p, dqmc_handle **out)
 {
     if (!p || !out) return fail(nullptr, DQMC_ERR_INVALID, "dqmc_create: null argument");
     *out = nullptr;
-    refresh_kernel_switches();  // (the launchers' A/B switches: read here, never inside a launch)
     if (p->n_sites < 1 || p->slices < 1 || p->safe_mult < 1 || p->n_walkers < 1)
         return fail(nullptr, DQMC_ERR_INVALID, "dqmc_create: n_sites, slices, safe_mult, n_walkers must be >= 1");
     if (p->slices % p->safe_mult != 0)  // stack.jl:115: convert(Int, slices / safe_mult) throws InexactError
@@ -898,10 +880,7 @@ int dqmc_create(const dqmc_params *p, dqmc_handle **out)
         return fail(nullptr, DQMC_ERR_INVALID, "dqmc_create: hopping exponentials missing");
     if (!(p->U >= 0.0)) return fail(nullptr, DQMC_ERR_INVALID, "dqmc_create: U must be positive");
     const int nb = p->model_kind == DQMC_REPULSIVE ? 2 : 1;
-    const bool sweep_old = getenv("DQMC_SWEEP_OLD") != nullptr;  // one-workgroup-per-walker chunk kernel (A/B only)
     if (p->n_sites > 1024) return fail(nullptr, DQMC_ERR_INVALID, "dqmc_create: n_sites exceeds 1024 (unsupported)");
-    if (sweep_old && nb * ((p->n_sites + 63) & ~63) > 1024)
-        return fail(nullptr, DQMC_ERR_INVALID, "dqmc_create: DQMC_SWEEP_OLD needs n_blocks * n_sites <= 1024");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
         return fail(nullptr, DQMC_ERR_NO_DEVICE, "dqmc_create: no HIP device visible");
@@ -909,6 +888,7 @@ int dqmc_create(const dqmc_params *p, dqmc_handle **out)
         return fail(nullptr, DQMC_ERR_INVALID, "dqmc_create: device_id out of range");
 
     dqmc_handle *h = new dqmc_handle();
+    read_kernel_switches(h);
     h->p = *p;
     h->p.eT = h->p.eTinv = h->p.eT2 = h->p.eTinv2 = nullptr;
     h->N = h->n = p->n_sites;
@@ -919,8 +899,6 @@ int dqmc_create(const dqmc_params *p, dqmc_handle **out)
     h->W = p->n_walkers;
     h->units = h->W * h->nb;
     h->nn = (long)h->n * h->n;
-    h->kd = sweep_kd(h->n, h->nb);
-    h->sweep_lu = !sweep_old;
     // elimination of chunk c beside the flush of chunk c - 1 in one launch (the elimination first applies the previous
     // chunk to its own 64 x 64 block; the flush workgroups take two column passes each, so that at 32 units the whole
     // launch is co-resident, one workgroup per CU): 36 us per chunk against 24 + 17 for the two separate launches.
@@ -928,7 +906,7 @@ int dqmc_create(const dqmc_params *p, dqmc_handle **out)
     // With more units than that the phase is throughput-bound and the separate launches win (config 4 on one GPU,
     // 512 units: 688 vs 715 ms per sweep), so the fused form is used only when its grid fits the CUs.
     h->sweep_fused = false;
-    if (getenv("DQMC_SWEEP_SPLIT") == nullptr && h->n % 64 == 0) {
+    if (!h->sw.sweep_split && h->n % 64 == 0) {
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, p->device_id) == hipSuccess) {
             const int ncp = (h->n % 256 == 0) ? 2 : 1, nt = (h->n % 128 == 0) ? 8 : 4;
@@ -976,7 +954,7 @@ int dqmc_create(const dqmc_params *p, dqmc_handle **out)
     CHIP(hipMemcpy(h->eTinv, p->eTinv, cn * sizeof(double), hipMemcpyHostToDevice));
     CHIP(hipMemcpy(h->eT2, p->eT2, cn * sizeof(double), hipMemcpyHostToDevice));
     CHIP(hipMemcpy(h->eTinv2, p->eTinv2, cn * sizeof(double), hipMemcpyHostToDevice));
-    if (h->n == 256 && !getenv("DQMC_NO_SLAB")) {
+    if (h->n == 256 && !h->sw.no_slab) {
         std::vector<double> tr(cn);
         for (int b = 0; b < nb; ++b)
             for (int j = 0; j < h->n; ++j)
@@ -1007,8 +985,6 @@ int dqmc_create(const dqmc_params *p, dqmc_handle **out)
     if (h->n > 256) CCHK(dalloc(h, &h->trsm_s, un));
     CCHK(dalloc(h, &h->pivot, uv));
     CCHK(alloc_qr_workspace(h));
-    CCHK(dalloc(h, &h->sU, (size_t)h->units * h->n * h->kd));
-    CCHK(dalloc(h, &h->sVT, (size_t)h->units * h->n * h->kd));
     CCHK(dalloc(h, &h->greens_alt, un));
     CCHK(dalloc(h, &h->lu_img, 2 * (size_t)h->units * sweep_lu_image_doubles()));
     CCHK(dalloc(h, &h->rng, (size_t)h->W));
@@ -1808,7 +1784,7 @@ static int scratch_init(dqmc_handle *h, int device_id, int n, int batch)
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(nullptr, DQMC_ERR_NO_DEVICE, "no HIP device visible");
     if (device_id < 0 || device_id >= ndev) return fail(nullptr, DQMC_ERR_INVALID, "device_id out of range");
     if (n < 1 || n > 1024 || batch < 1) return fail(nullptr, DQMC_ERR_INVALID, "n must be 1..1024 and batch >= 1");
-    refresh_kernel_switches();
+    read_kernel_switches(h);
     h->p.device_id = device_id;
     h->n = h->N = n;
     h->nb = 1;

@@ -95,32 +95,29 @@ struct SlabArgs {
 };
 hipError_t launch_slab_chain(const SlabArgs &a, hipStream_t s, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
 
-// C += U V' for the delayed-update flush: U[t + n m], VT[t + n m], m < 64 slots; n % 64 == 0
-hipError_t launch_gemm_flush(int n, int n_units, const double *U, const double *VT, long sUV, double *C, long sC,
-                             hipStream_t s, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
-
 // Column-pivoted Householder QR, in place (udt_AVX_pivot! "QR decomposition" loop,
 // src/linalg/UDT.jl:212-246).  On exit A holds R on/above the diagonal and the
 // Householder vectors below it (unit diagonal implied), tau[n], pivot[n] (0-based:
 // column j of the factored matrix is original column pivot[j]).
 // Workspace of the cooperative (8 workgroups per matrix) QR: mailbox of n_units x 2 x 8 slots of
 // QR_COOP_SLOT doubles (tagged packets), an error flag (bounded spins), a launch counter.
-// A/B and fallback switches of the launchers (environment).  They are read ONCE per handle / primitive call
-// (refresh_kernel_switches(), called when a handle is set up), never inside a launch: no environ scan per stabilisation step,
-// no change of kernels or numerics in the middle of a run, no race with a host thread that edits the environment.
+// Kernel-selection and test switches (environment).  Each handle, and each stand-alone primitive call, reads them once
+// when it is set up (read_kernel_switches(), engine.cpp) and keeps its own copy; the launchers get them as arguments
+// (or through the QR workspace) and never read the environment.  So a handle's kernels cannot change during its life,
+// whatever another handle or thread does.
 struct KernelSwitches {
-    bool qr_stream = false;       // DQMC_QR_STREAM: streaming single-workgroup QR instead of the tile kernel
-    bool qr_tile_bounds = false;  // DQMC_QR_TILE_BOUNDS: tile QR with run-time bounds at n == 256
+    bool qr_noblocked = false;    // DQMC_QR_NOBLOCKED: no one-launch pre-pivoted UDT (qrb.hip)
+    int qrb_sites = 7;            // DQMC_QRB_SITES: call sites that take it (bit mask, see alloc_qr_workspace)
+    bool qr_tail = true;          // DQMC_QR_TAIL=0: no hand-over to qr_tail_kernel at n == 256
+    bool qr_sc1 = false;          // DQMC_QR_SC1: write-through (agent-scope) packet stores regardless of placement
+    bool qr_nocoop = false;       // DQMC_QR_NOCOOP: single-workgroup QR kernels only
+    int qr_force_timeout = 0;     // DQMC_QR_FORCE_TIMEOUT (QrCoopWorkspace::force_timeout)
     bool qr_nopanel = false;      // DQMC_QR_NOPANEL: streaming QR instead of the panel kernel for n > 256
-    double qp_thr = 1e-4;         // DQMC_QP_THR: recompute threshold of the panel kernel's down-dated norms
-    bool trsm_simple = false;     // DQMC_TRSM_SIMPLE: substitution kernel (the fallback of the MFMA solves)
-    bool trsm_ll = false;         // DQMC_TRSM_LL: left-looking slab-in-LDS solve (n > 256 panels)
-    bool trsm_bounds = false;     // DQMC_TRSM_BOUNDS: right-looking solve with run-time bounds at n == 256
-    bool flush_ncp2 = false;      // DQMC_FLUSH_NCP2: two column passes per flush workgroup
-    int gemm_stagger = 0;         // DQMC_GEMM_STAGGER
+    bool trsm_simple = false;     // DQMC_TRSM_SIMPLE: substitution kernel instead of the MFMA solves
+    bool sweep_split = false;     // DQMC_SWEEP_SPLIT: elimination and flush as separate launches
+    bool flush_ncp2 = false;      // DQMC_FLUSH_NCP2: the separate flush always in its multi-pass form
+    bool no_slab = false;         // DQMC_NO_SLAB: no slab-resident product chains (slab.hip)
 };
-const KernelSwitches &kernel_switches();
-void refresh_kernel_switches();
 
 constexpr int QR_COOP_SLOT = 528;  // 264 packets of 16 bytes
 constexpr int QR_COOP_SLOTS_PER_UNIT = 16;  // 2 parities x 8 parts (qr_coop_kernel)
@@ -130,11 +127,12 @@ struct QrCoopWorkspace {
     int *fb = nullptr;    // [0] launch epoch of the last cooperative launch that timed out, [1] fallbacks taken
     unsigned long long epoch = 0;
     int max_blocks = 0;   // launch the cooperative kernel only if its grid fits (co-residency)
-    int tail_j0 = 128;    // n == 256: hand-over step to qr_tail_kernel (0 = cooperative kernel only; 64, 96, 128)
-    // A/B and test switches, read from the environment when the workspace is set up (per handle / per primitive call):
-    int force_sc1 = 0;      // DQMC_QR_SC1: write-through (agent-scope) packet stores regardless of placement
-    int no_coop = 0;        // DQMC_QR_NOCOOP: single-workgroup kernels only
-    int force_timeout = 0;  // DQMC_QR_FORCE_TIMEOUT: 1 = every cooperative launch gives up at once;
+    // switches, copied from the handle's KernelSwitches when the workspace is set up:
+    bool tail = true;       // n == 256: steps 128.. on one CU per matrix (qr_tail_kernel)
+    int force_sc1 = 0;      // write-through (agent-scope) packet stores regardless of placement
+    int no_coop = 0;        // single-workgroup kernels only
+    bool no_panel = false;  // streaming kernel instead of the panel kernel for n > 256
+    int force_timeout = 0;  // test hook: 1 = every cooperative launch gives up at once;
                             // "step:<j>" -> 2 + j: part 3 of every matrix stops publishing at step j (bounded spins run out)
     // pre-pivoted blocked UDT (qrb.hip, n == 256): its own mailbox; blk_max_blocks = co-resident workgroups (0 = off)
     double *mailbox2 = nullptr;
@@ -175,15 +173,13 @@ hipError_t launch_udt_finish(int n, int n_units, double *A, long strideA, const 
 // compact-WY triangle, whose inverse diagonal is tau).
 hipError_t launch_trsm_right_upper(int n, int n_units, const double *A, long strideA, const double *T,
                                    long strideT, const int *pivot, const double *dmul, long strideV,
-                                   double *Out, long strideOut, double *winv, hipStream_t s,
-                                   double *scratch = nullptr);
+                                   double *Out, long strideOut, double *winv, const KernelSwitches &sw,
+                                   hipStream_t s, double *scratch = nullptr);
 // winv: n_units * ceil(n/16) * 256 doubles of scratch for the inverted diagonal blocks (n <= 256 path);
 // nullptr selects the substitution kernel; scratch: n_units x strideOut doubles for the panelled MFMA solve of n > 256
-// (without it the substitution kernel is used there)
+// (without it the substitution kernel is used there); sw.trsm_simple: the substitution kernel everywhere
 
-// One chunk of sweep_spatial (DQMC.jl:546-582): sites [site0, site0+nsites) of the
-// current slice with delayed rank-1 updates; writes the accepted update vectors
-// (Uout: n x KD, VTout: n x KD, zero padded) for the flush GEMM G += Uout*VTout'.
+// sweep_spatial (DQMC.jl:546-582): the constants of the local updates, the walkers' random streams and counters
 struct SweepConsts {
     // per conf value index ci = (conf>0): attractive gamma (Attractive.jl:121) and
     // exp(-dE_boson); repulsive Delta_up, Delta_dn (Repulsive.jl:139-141)
@@ -231,16 +227,10 @@ __device__ __forceinline__ void magstats_push(DevMagStats &s, double value)
     s.count += 1;
 }
 #endif
-int sweep_kd(int n, int nb);  // chunk length (update slots per flush) for this problem size
-hipError_t launch_sweep_chunk(int n, int nb, int n_walkers, int model, double *G, long strideG,
-                              int8_t *conf_slice, long conf_stride, int site0, int nsites,
-                              double *Uout, double *VTout, long strideUV, SweepConsts sc,
-                              WalkerRng *rng, DevStats *stats, int check_sign, hipStream_t s);
-
-// The same chunk as a decide / apply pair (sweep_lu.hip): sweep_lu_kernel eliminates the 64 x 64 block G[c, c]
-// with one wave per walker (decisions, HS field, counters) and leaves register images of the triangular factors
-// (sweep_lu_image_doubles() doubles per unit); sweep_flush_lu_kernel applies the chunk to G out of place
-// (Gout = Gin + T R0).  No limit on n_blocks * n_sites.
+// One chunk of 64 sites of the current slice as a decide / apply pair (sweep_lu.hip): sweep_lu_kernel eliminates the
+// 64 x 64 block G[c, c] with one wave per walker (decisions, HS field, counters) and leaves register images of the
+// triangular factors (sweep_lu_image_doubles() doubles per unit); sweep_flush_lu_kernel applies the chunk to G out of
+// place (Gout = Gin + T R0).  No limit on n_blocks * n_sites.
 size_t sweep_lu_image_doubles();
 hipError_t launch_sweep_lu(int n, int nb, int n_walkers, const double *G, long strideG, int8_t *conf_slice,
                            long conf_stride, int site0, int nsites, double *img, SweepConsts sc, WalkerRng *rng,
@@ -252,9 +242,10 @@ hipError_t launch_sweep_fused(int n, int nb, int n_walkers, const double *Gin, d
                               const double *imgp, SweepConsts sc, WalkerRng *rng, DevStats *stats, int check_sign,
                               int *errflag, hipStream_t s, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
 
+// sw.flush_ncp2: the multi-pass form that more units than CUs take anyway
 hipError_t launch_sweep_flush_lu(int n, int n_units, const double *Gin, double *Gout, long strideG, int site0,
-                                 int nsites, const double *img, hipStream_t s, hipEvent_t start = nullptr,
-                                 hipEvent_t stop = nullptr);
+                                 int nsites, const double *img, const KernelSwitches &sw, hipStream_t s,
+                                 hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
 
 // Checkerboard products with sparse bond-group factors (cb.hip): O = post . F_last ... F_first . pre . X on the rows
 // (side 0) or columns (side 1) of X; factor m in ELL form vals / cols [m][n][kmax]; the diagonal scalings are the

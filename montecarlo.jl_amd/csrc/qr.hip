@@ -207,6 +207,8 @@ constexpr int QP_UC2 = 4;  // columns per group in the rank-QP_NB update
 constexpr int QP_THREADS = 512, QP_WAVES = QP_THREADS / 64;  // 2 waves per SIMD: 256 VGPRs per lane (at 1024 threads the
                                                              // 128-register budget spilled and the kernel ran 2.4 x slower)
 constexpr int QP_RPT = 2;  // rows per thread in the one-element-per-row phases (n <= 1024)
+// a down-dated column norm is recomputed from scratch once it has fallen below this fraction of its last exact value
+constexpr double QP_RECOMPUTE_THR = 1e-4;
 // barrier that hands over LDS data only (the global stores of the step stay in flight; the one full barrier of a step
 // sits behind the row update, before the next step touches what this one stored)
 #define QP_LDS_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
@@ -1280,7 +1282,7 @@ __device__ long long *qb_stamp_ptr = nullptr;  // [wave 8][step 192][point 8] of
 // Geometry of a tail kernel that takes over after J0 steps with NW waves: M = 256 - J0 trailing rows and columns,
 // 8 NW thread groups of 8 lanes, CPT = M / (8 NW) columns per group, KR = M / 8 rows per lane.
 //   <128, 4>: 128 x 128 on ONE wave per SIMD (the step is bound by VALU issue: two waves per SIMD halve each other's rate
-//             in the replicated selection / scalar work) - the default;  <64, 8>: 192 x 192 on two waves per SIMD
+//             in the replicated selection / scalar work) - the form that is launched
 template <int J0, int NW>
 struct QbGeo {
     static constexpr int M = 256 - J0, KR = M / 8, CPT = M / (8 * NW), VS = KR + 2, THREADS = 64 * NW, REGIONS = M / 32;
@@ -1720,11 +1722,10 @@ int qr_coop_blocks_per_cu()
 }
 
 static hipError_t launch_qr_single(int n, int n_units, double *A, long strideA, double *tau, int *pivot,
-                                   const double *src, long strideSrc, int *guard, int guard_val, hipStream_t s,
-                                   double *X = nullptr, long strideX = 0, const int *never = nullptr)
+                                   const double *src, long strideSrc, int *guard, int guard_val, bool no_panel,
+                                   hipStream_t s, double *X = nullptr, long strideX = 0, const int *never = nullptr)
 {
-    const bool no_tile = kernel_switches().qr_stream;
-    if (n > 128 && n <= 256 && !no_tile) {
+    if (n > 128 && n <= 256) {
         const size_t lds_t = (64 * QT_LSTRIDE + 3 * 256 + 8 * QT_VS + 8 * 256) * sizeof(double) + 256 * sizeof(int);
         int dev = 0;
         (void)hipGetDevice(&dev);
@@ -1740,7 +1741,7 @@ static hipError_t launch_qr_single(int n, int n_units, double *A, long strideA, 
         // the first 128 steps, qr_tail_kernel the rest; `never` is a word that never equals -1 (the tail's exit test)
         const bool two_phase = X && never && n == 256 && !guard;
         const int nsteps = two_phase ? 128 : n;
-        if (n == 256 && !kernel_switches().qr_tile_bounds)
+        if (n == 256)
             hipLaunchKernelGGL(qr_tile256_kernel<true>, dim3(n_units), dim3(QT_THREADS), lds_t, s, n, nsteps, A, strideA, tau,
                                pivot, src, strideSrc, guard, guard_val, two_phase ? X : nullptr, strideX);
         else
@@ -1753,7 +1754,7 @@ static hipError_t launch_qr_single(int n, int n_units, double *A, long strideA, 
         return hipGetLastError();
     }
     // n > 256: the panel (dlaqps-style) kernel, unless it is switched off or its LDS does not fit
-    if (n > 256 && n <= 768 && !no_tile && !guard && !src && !kernel_switches().qr_nopanel) {
+    if (n > 256 && n <= 768 && !guard && !src && !no_panel) {
         const size_t lds_p = ((size_t)(QP_NB + 4) * n + 2 * QP_NB + QP_WAVES + 2) * sizeof(double) + (size_t)(n + 2 + QP_WAVES) * sizeof(int);
         int dev = 0;
         (void)hipGetDevice(&dev);
@@ -1763,9 +1764,12 @@ static hipError_t launch_qr_single(int n, int n_units, double *A, long strideA, 
             (void)hipFuncSetAttribute((const void *)qr_panel_kernel<12>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
             pmask |= 1u << dev;
         }
-        const double thr = kernel_switches().qp_thr;  // recompute threshold (A/B)
-        if (n <= 576) hipLaunchKernelGGL((qr_panel_kernel<9>), dim3(n_units), dim3(QP_THREADS), lds_p, s, n, A, strideA, tau, pivot, thr);
-        else hipLaunchKernelGGL((qr_panel_kernel<12>), dim3(n_units), dim3(QP_THREADS), lds_p, s, n, A, strideA, tau, pivot, thr);
+        if (n <= 576)
+            hipLaunchKernelGGL((qr_panel_kernel<9>), dim3(n_units), dim3(QP_THREADS), lds_p, s, n, A, strideA, tau, pivot,
+                               QP_RECOMPUTE_THR);
+        else
+            hipLaunchKernelGGL((qr_panel_kernel<12>), dim3(n_units), dim3(QP_THREADS), lds_p, s, n, A, strideA, tau, pivot,
+                               QP_RECOMPUTE_THR);
         return hipGetLastError();
     }
     const size_t lds = 2 * 1024 * sizeof(double);
@@ -1796,36 +1800,28 @@ hipError_t launch_qr_pivot(int n, int n_units, double *A, long strideA, double *
         if (blocks <= ws->max_blocks) {
             ws->epoch += 1;
             const int force_sc1 = ws->force_sc1, force_to = ws->force_timeout;
-            // n == 256: the first steps cooperatively, the rest on one CU per matrix (qr_tail_kernel)
-            const int tail_j0 = ws->tail_j0;  // DQMC_QR_TAIL at handle creation; default 128 x 128 tail
-            const bool two_phase = n == 256 && X && (tail_j0 == 64 || tail_j0 == 96 || tail_j0 == 128);
+            // n == 256: the first 128 steps cooperatively, the rest on one CU per matrix (qr_tail_kernel)
+            const bool two_phase = n == 256 && X && ws->tail;
             hipLaunchKernelGGL(qr_coop_kernel, dim3(blocks), dim3(256), 0, s, n, n_units, A, strideA, tau, pivot,
-                               ws->mailbox, ws->epoch, ws->fb, force_sc1, W, strideW, force_to, two_phase ? tail_j0 : n,
+                               ws->mailbox, ws->epoch, ws->fb, force_sc1, W, strideW, force_to, two_phase ? 128 : n,
                                X, strideX);
             hipError_t e = hipGetLastError();
             if (e != hipSuccess) return e;
             if (two_phase) {
                 const int ep = (int)(ws->epoch & 0x7fffffffull);
-                if (tail_j0 == 64)
-                    hipLaunchKernelGGL((qr_tail_kernel<64, 8>), dim3(n_units), dim3(512), 0, s, n_units, X, strideX, W, strideW,
-                                       tau, pivot, ws->fb, ep);
-                else if (tail_j0 == 96)
-                    hipLaunchKernelGGL((qr_tail_kernel<96, 5>), dim3(n_units), dim3(320), 0, s, n_units, X, strideX, W, strideW,
-                                       tau, pivot, ws->fb, ep);
-                else
-                    hipLaunchKernelGGL((qr_tail_kernel<128, 4>), dim3(n_units), dim3(256), 0, s, n_units, X, strideX, W, strideW,
-                                       tau, pivot, ws->fb, ep);
+                hipLaunchKernelGGL((qr_tail_kernel<128, 4>), dim3(n_units), dim3(256), 0, s, n_units, X, strideX, W, strideW,
+                                   tau, pivot, ws->fb, ep);
                 e = hipGetLastError();
                 if (e != hipSuccess) return e;
             }
             *factored = W;
             return launch_qr_single(n, n_units, W, strideW, tau, pivot, A, strideA, ws->fb,
-                                    (int)(ws->epoch & 0x7fffffffull), s);
+                                    (int)(ws->epoch & 0x7fffffffull), ws->no_panel, s);
         }
     }
-    const bool tail_ok = ws && ws->fb && ws->tail_j0 == 128;  // (fb[0] holds launch epochs >= 0, never -1)
-    return launch_qr_single(n, n_units, A, strideA, tau, pivot, nullptr, 0, nullptr, 0, s, tail_ok ? X : nullptr, strideX,
-                            tail_ok ? ws->fb : nullptr);
+    const bool tail_ok = ws && ws->fb && ws->tail;  // (fb[0] holds launch epochs >= 0, never -1)
+    return launch_qr_single(n, n_units, A, strideA, tau, pivot, nullptr, 0, nullptr, 0, ws && ws->no_panel, s,
+                            tail_ok ? X : nullptr, strideX, tail_ok ? ws->fb : nullptr);
 }
 
 // D = |diag R| (UDT.jl:268-272) for every unit
@@ -1956,19 +1952,10 @@ __global__ __launch_bounds__(256) void trsm_kernel(int n, const double *__restri
 }
 
 // ---------------------------------------------------------------------------
-// MFMA-blocked variant for n <= 256.  X T = O with T upper triangular is solved by column blocks
-// of 16: the contribution of all previous blocks is one 32 x 16 x j0 product on
-// v_mfma_f64_16x16x4_f64 (X slab from LDS, the T panel staged to LDS), followed by a 16-step
-// substitution inside the block (one lane per row, the block's solved values in registers).
-// One workgroup (2 waves) owns a 32-row slab; 8 slabs x units fill the chip.
-typedef double d4_t __attribute__((ext_vector_type(4)));
-constexpr int TM_XS = 40;    // LDS stride of an X column (32 rows + pad: conflict-free MFMA operand reads)
-constexpr int TM_TS = 258;   // LDS stride of a T panel column (2*TS = 4 mod 64 dwords: conflict-free)
-
 // Inverses of the 16 x 16 diagonal blocks of T (upper triangular; reciprocal diagonal either 1/T[c,c] or
 // dmul[c]), one workgroup of 16 threads per (block, unit): thread j builds column j of W = B^-1 by back
-// substitution.  With them the in-block solve of the main kernel is one small MFMA product instead of a
-// 16-step substitution on 16 lanes.  Rows/columns beyond n are the identity.
+// substitution.  With them the in-block solve of trsm_rl_kernel (trsm_rl.hip) is one small MFMA product instead of
+// a 16-step substitution on 16 lanes.  Rows/columns beyond n are the identity.
 __global__ __launch_bounds__(16) void trsm_diag_inv_kernel(int n, const double *__restrict__ Tall, long sT,
                                                           const double *__restrict__ dmulall, long sV,
                                                           double *__restrict__ Wall, int nblk)
@@ -2004,120 +1991,6 @@ __global__ __launch_bounds__(16) void trsm_diag_inv_kernel(int n, const double *
     for (int i = 0; i < 16; ++i) W[i + 16 * j] = wcol[i];  // column-major 16 x 16
 }
 
-// Panel form: solves the nc columns c0 .. c0 + nc - 1 (nc <= 256) of an nr-row problem against the diagonal block
-// T[c0 : c0 + nc, c0 : c0 + nc] of an ld x ld triangle; the contribution of the columns before c0 must already have
-// been subtracted (launch_trsm_right_upper does that with a GEMM for n > 256).  nr = nc = ld = n, c0 = 0 is the
-// whole n <= 256 problem.
-__global__ __launch_bounds__(128) void trsm_mfma_kernel(int nr, int n, int c0, int ld, int nblk_all,
-                                                       const double *__restrict__ Aall, long sA,
-                                                       const double *__restrict__ Tall, long sT,
-                                                       const int *__restrict__ pivall,
-                                                       const double *__restrict__ dmulall, long sV,
-                                                       double *__restrict__ Oall, long sO, int slabs,
-                                                       const double *__restrict__ Wall)
-{
-    extern __shared__ __attribute__((aligned(16))) double sm[];
-    double *Xs = sm;                   // [256][TM_XS]
-    double *Tp = Xs + 256 * TM_XS;     // [16][TM_TS]  panel T[0 : j0+16, j0 : j0+16], column c at Tp + c*TM_TS
-    double *Wl = Tp + 16 * TM_TS;      // [16][18] inverse of the current diagonal block, W[k][c] at Wl + c*18 + k
-    const int unit = blockIdx.x / slabs, row0 = (blockIdx.x % slabs) * 32;
-    const double *__restrict__ A = Aall + (long)unit * sA;
-    const double *__restrict__ T = Tall + (long)unit * sT + (long)ld * c0 + c0;  // the panel's diagonal block
-    const int *__restrict__ piv = pivall ? pivall + (long)unit * ld : nullptr;
-    (void)dmulall; (void)sV;  // the diagonal enters through the inverted blocks
-    double *__restrict__ O = Oall + (long)unit * sO;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int li = lane & 15, lq = lane >> 4;
-
-    for (int idx = tid; idx < n * 32; idx += 128) {
-        const int j = idx >> 5, r = idx & 31, row = row0 + r;
-        const int pj = piv ? piv[c0 + j] : c0 + j;
-        Xs[j * TM_XS + r] = row < nr ? A[row + (long)ld * pj] : 0.0;
-    }
-    const int nblk = (n + 15) >> 4;
-    for (int idx = n * 32 + tid; idx < nblk * 16 * 32; idx += 128) Xs[(idx >> 5) * TM_XS + (idx & 31)] = 0.0;  // columns >= n
-    const double *__restrict__ Wu = Wall + ((long)unit * nblk_all + (c0 >> 4)) * 256;
-    // the T panel of block J+1 is requested from global memory (L2) while block J computes:
-    // thread (c = tid >> 3) holds k = (tid & 7) + 8 i of column j0 + c in registers until the LDS panel is free
-    double pre[32], pre_w[2] = {0.0, 0.0};
-    auto fetch_panel = [&](int J) {
-        // no per-lane predicates: entries below the diagonal are never used (the product reads rows
-        // k < j0 <= col, the substitution rows j0 + c2 < col), indices are clamped into the matrix, and
-        // the number of 8-row steps is wave-uniform
-        const int j0 = J << 4, c = tid >> 3, col = min(j0 + c, n - 1);
-        const int steps = J < nblk ? ((min(j0 + 16, n) + 15) >> 4) << 1 : 0;  // 8-row steps, rounded up to a pair
-        const double *__restrict__ tc = T + (long)ld * col;
-#pragma unroll
-        for (int i = 0; i < 32; i += 2) {
-            if (i < steps) {  // one wave-uniform guard per pair
-                pre[i] = tc[min((tid & 7) + 8 * i, n - 1)];
-                pre[i + 1] = tc[min((tid & 7) + 8 * (i + 1), n - 1)];
-            }
-        }
-        if (J < nblk) {
-            pre_w[0] = Wu[(long)J * 256 + tid];
-            pre_w[1] = Wu[(long)J * 256 + 128 + tid];
-        }
-    };
-    fetch_panel(0);
-    for (int J = 0; J < nblk; ++J) {
-        const int j0 = J << 4;
-        __syncthreads();  // previous block's panel no longer read; first pass: Xs complete
-        {
-            const int c = tid >> 3, steps = ((min(j0 + 16, n) + 15) >> 4) << 1;  // as fetched: wave-uniform
-#pragma unroll
-            for (int i = 0; i < 32; i += 2) {
-                if (i < steps) {
-                    Tp[c * TM_TS + (tid & 7) + 8 * i] = pre[i];
-                    Tp[c * TM_TS + (tid & 7) + 8 * (i + 1)] = pre[i + 1];
-                }
-            }
-            Wl[(tid >> 4) * 18 + (tid & 15)] = pre_w[0];
-            Wl[((tid + 128) >> 4) * 18 + (tid & 15)] = pre_w[1];
-        }
-        __syncthreads();
-        fetch_panel(J + 1);
-        // acc[i = lq + 4 r][c = li] = sum_{k < j0} X[16 w + i, k] T[k, j0 + c]; two independent
-        // accumulators (a dependent MFMA chain would expose the 64+ cycle MFMA latency per k-step)
-        d4_t acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
-        // j0 is a multiple of 16: steps of 16 k with all eight operand reads issued before the MFMAs
-        const double *xa = Xs + lq * TM_XS + 16 * w + li, *tb = Tp + li * TM_TS + lq;
-        for (int kk = 0; kk < j0; kk += 16) {
-            double a[4], b[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                a[u] = xa[(kk + 4 * u) * TM_XS];
-                b[u] = tb[kk + 4 * u];
-            }
-            acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a[0], b[0], acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a[1], b[1], acc1, 0, 0, 0);
-            acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a[2], b[2], acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a[3], b[3], acc1, 0, 0, 0);
-        }
-        const d4_t acc = acc0 + acc1;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) Xs[(j0 + li) * TM_XS + 16 * w + lq + 4 * r] -= acc[r];
-        // in-block solve X_J = R_J W_J with the precomputed inverse of the diagonal block: four k-steps on the
-        // wave's own 16 rows (LDS ops of one wave are ordered: the subtraction above is visible)
-        {
-            d4_t xacc = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const double a = Xs[(j0 + 4 * u + lq) * TM_XS + 16 * w + li];
-                const double b = Wl[li * 18 + 4 * u + lq];
-                xacc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, xacc, 0, 0, 0);
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) Xs[(j0 + li) * TM_XS + 16 * w + lq + 4 * r] = xacc[r];
-        }
-    }
-    __syncthreads();
-    for (int idx = tid; idx < n * 32; idx += 128) {
-        const int j = idx >> 5, r = idx & 31, row = row0 + r;
-        if (row < nr) O[row + (long)ld * (c0 + j)] = Xs[j * TM_XS + r];
-    }
-}
-
 // W[:, j] = A[:, pivot[j]] (the gather of rdivp!, general.jl:143-148) for the panelled solve
 __global__ void trsm_gather_kernel(int n, const double *__restrict__ Aall, long sA, const int *__restrict__ pivall,
                                    double *__restrict__ Wall, long sW)
@@ -2140,37 +2013,19 @@ hipError_t launch_trsm_rl(int nr, int nc, int c0, int ld, int nblk_all, int n_un
 
 hipError_t launch_trsm_right_upper(int n, int n_units, const double *A, long sA, const double *T, long sT,
                                    const int *pivot, const double *dmul, long sV, double *Out, long sO,
-                                   double *winv, hipStream_t s, double *scratch)
+                                   double *winv, const KernelSwitches &sw, hipStream_t s, double *scratch)
 {
-    const bool no_mfma = kernel_switches().trsm_simple;
-    const size_t lds_m = (256 * TM_XS + 16 * TM_TS + 16 * 18) * sizeof(double);
-    auto set_attr = [&]() {
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        static unsigned attr_mask = 0;  // per device
-        if (!(attr_mask & (1u << dev))) {
-            (void)hipFuncSetAttribute((const void *)trsm_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)lds_m);
-            attr_mask |= 1u << dev;
-        }
-    };
+    const bool no_mfma = sw.trsm_simple;
     if (n <= 256 && winv && !no_mfma) {
-        const int slabs = (n + 31) / 32, nblk = (n + 15) / 16;
+        const int nblk = (n + 15) / 16;
         hipLaunchKernelGGL(trsm_diag_inv_kernel, dim3(nblk, n_units), dim3(16), 0, s, n, T, sT, dmul, sV, winv, nblk);
-        set_attr();
-        // (in place is fine for both kernels: a workgroup reads all entries of its own 32 rows before it writes any)
-        const bool left_looking = kernel_switches().trsm_ll;  // the slab-in-LDS kernel (A/B measurements)
-        if (left_looking)
-            hipLaunchKernelGGL(trsm_mfma_kernel, dim3(n_units * slabs), dim3(128), lds_m, s, n, n, 0, n, nblk, A, sA, T, sT,
-                               pivot, dmul, sV, Out, sO, slabs, winv);
-        else
-            return launch_trsm_rl(n, n, 0, n, nblk, n_units, A, sA, T, sT, pivot, Out, sO, winv, s);
-        return hipGetLastError();
+        // (in place is fine: a workgroup reads all entries of its own 32 rows before it writes any)
+        return launch_trsm_rl(n, n, 0, n, nblk, n_units, A, sA, T, sT, pivot, Out, sO, winv, s);
     }
     if (n > 256 && winv && scratch && sA == sO && !no_mfma) {
         // Panels of up to 256 columns: gather (pivot) into scratch, then per panel  X_P = (A_P - X_<P T_<P,P) inv(T_PP):
-        // the bracket with the MFMA GEMM, the triangle with the panel form of the kernel above.
-        const int nblk = (n + 15) / 16, slabs = (n + 31) / 32;
+        // the bracket with the MFMA GEMM, the triangle with the panel form of the right-looking solve.
+        const int nblk = (n + 15) / 16;
         int pw = 256;
         for (int cand = 256; cand >= 128; cand -= 16)  // equal panels when a width between 128 and 256 divides n
             if (n % cand == 0) { pw = cand; break; }
@@ -2178,7 +2033,6 @@ hipError_t launch_trsm_right_upper(int n, int n_units, const double *A, long sA,
         int bx = (int)(((long)n * n + 255) / 256);
         if (bx > 128) bx = 128;
         hipLaunchKernelGGL(trsm_gather_kernel, dim3(bx, n_units), dim3(256), 0, s, n, A, sA, pivot, scratch, sO);
-        set_attr();
         for (int c0 = 0; c0 < n; c0 += pw) {
             const int nc = n - c0 < pw ? n - c0 : pw;
             if (c0 > 0) {
@@ -2219,23 +2073,6 @@ hipError_t launch_trsm_right_upper(int n, int n_units, const double *A, long sA,
     else TR_LAUNCH(16);
 #undef TR_LAUNCH
     return hipGetLastError();
-}
-
-static KernelSwitches g_switches;
-const KernelSwitches &kernel_switches() { return g_switches; }
-void refresh_kernel_switches()
-{
-    KernelSwitches k;
-    k.qr_stream = getenv("DQMC_QR_STREAM") != nullptr;
-    k.qr_tile_bounds = getenv("DQMC_QR_TILE_BOUNDS") != nullptr;
-    k.qr_nopanel = getenv("DQMC_QR_NOPANEL") != nullptr;
-    if (const char *e = getenv("DQMC_QP_THR")) k.qp_thr = atof(e);
-    k.trsm_simple = getenv("DQMC_TRSM_SIMPLE") != nullptr;
-    k.trsm_ll = getenv("DQMC_TRSM_LL") != nullptr;
-    k.trsm_bounds = getenv("DQMC_TRSM_BOUNDS") != nullptr;
-    k.flush_ncp2 = getenv("DQMC_FLUSH_NCP2") != nullptr;
-    if (const char *e = getenv("DQMC_GEMM_STAGGER")) k.gemm_stagger = atoi(e);
-    g_switches = k;
 }
 
 }  // namespace dqmc

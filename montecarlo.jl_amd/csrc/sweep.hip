@@ -1,329 +1,10 @@
-// sweep.hip — sweep_spatial (src/flavors/DQMC/DQMC.jl:546-582) with propose_local /
-// accept_local! of HubbardModelAttractive.jl:113-155 and HubbardModelRepulsive.jl:128-232,
-// plus the small bookkeeping kernels (propagation-error check, measurement sums).
-//
-// The site loop is strictly sequential, so one workgroup owns one walker.  Accepted
-// rank-1 Sherman–Morrison updates are DELAYED inside a chunk of KD sites: thread t keeps
-// its row of U' (n x cnt) and its column of V (cnt x n) in registers,
-//     G = G0 + U' V,   U'[:,j] = -(e_i - G[:,i]) * x,   V[j,:] = G[i,:],
-// so a proposal only needs the current diagonal (kept in LDS) and an accept costs 2*cnt
-// FMAs per thread instead of a 2 n^2 pass over G.  The chunk's U', V^T are written out
-// zero padded and the host flushes them with one MFMA GEMM (G0 += U' V) for all walkers.
-// This is a re-association of the reference's arithmetic only.
+// sweep.hip — the small helper and measurement kernels of the engine: identity / diagonal / elementwise helpers, the
+// propagation-error check (stack.jl:538-549), the measurement sums over walkers, the equal-time correlations and the
+// time-displaced susceptibilities, the HS-field packing.  The site sweep itself is in sweep_lu.hip.
 #include "kernels.h"
-#include <cstdlib>
 
 namespace dqmc {
 
-constexpr int SW_GROUP = 8;   // sites per group (static register indices inside a group)
-constexpr int SW_KD = 64;     // sites per chunk = update slots per flush
-
-// Two-level delayed updates.  Within a chunk of KD sites the accepted Sherman-Morrison updates
-// are kept as G = G0 + U'V (slot j = j-th accept of the chunk):
-//   * the slot history U'[t][m], V[m][t] of thread t lives in the global arrays that the flush
-//     GEMM reads anyway (own-lane coalesced stores at accept, own-lane loads at group starts);
-//   * LDS keeps only what other threads need: UiT[m][s] = U'[site0+s][m], ViT[m][s] = V[m][site0+s]
-//     for the chunk's own sites, the current diagonal dg[s], the uniforms of the chunk;
-//   * the rows/columns of G at the 8 sites of the current GROUP are held current in registers:
-//     corrected once at the group start from all older slots (batched: one history load feeds 16
-//     FMAs), then updated eagerly at every accept inside the group (<= 14 FMAs).
-// An accept therefore costs O(1) per thread on the critical path instead of a 2*cnt loop.
-// Layout of the dynamic LDS region (doubles unless noted):
-//   UiT[nb][KD][KD], ViT[nb][KD][KD], dg[2][KD], ul[KD], negv[KD], cs[KD] (int), flip[KD] (int)
-// MODEL (0 attractive, 1 repulsive) and FULL are compile-time: FULL = no padding lanes (n % 64 == 0) and the
-// chunk is one aligned block of 64 sites, i.e. exactly one wave per block owns the chunk's rows.  PMC counters
-// show the per-site instruction stream (a third of it scalar: exec-mask branches) to be the limiter; the
-// specialisation removes the per-lane predicates and the other model's code from that stream.
-template <int MAXT, int MODEL, bool FULL>
-__global__ __launch_bounds__(MAXT) void sweep_chunk_kernel(int n, int nb, int model_rt, double *__restrict__ Gall,
-                                                          long strideG, int8_t *__restrict__ conf_slice,
-                                                          long conf_stride, int site0, int nsites,
-                                                          double *__restrict__ Uall, double *__restrict__ VTall,
-                                                          long strideUV, SweepConsts sc, WalkerRng *rngs,
-                                                          DevStats *stats, int check_sign)
-{
-    constexpr int KD = SW_KD;
-    extern __shared__ __attribute__((aligned(16))) double sm[];
-    const int npad = (n + 63) & ~63;
-    double *UiT = sm;
-    double *ViT = UiT + (size_t)nb * KD * KD;
-    double *dg = ViT + (size_t)nb * KD * KD;  // [2][KD]
-    double *ul = dg + 2 * KD;
-    double *negv = ul + KD;
-    int *cs = (int *)(negv + KD);
-    int *flip = cs + KD;
-
-    const int w = blockIdx.x;
-    const int tid = threadIdx.x;
-    const int b = tid / npad, t = tid - b * npad;  // wave-uniform block index
-    (void)model_rt;
-    constexpr int model = MODEL;
-    const bool active = FULL ? true : t < n;
-    const int unit = w * nb + b;
-    const double *__restrict__ G = Gall + (long)unit * strideG;
-    double *Uo = Uall + (long)unit * strideUV;   // slot m of thread t at Uo[t + n*m]
-    double *VTo = VTall + (long)unit * strideUV;
-    int8_t *__restrict__ cw = conf_slice + (long)w * conf_stride;
-    double *uit = UiT + (size_t)b * KD * KD, *vit = ViT + (size_t)b * KD * KD;
-
-    const int sl = t - site0;  // my index inside the chunk, if any
-    // FULL: wave-uniform (the wave whose first row is site0), decided on a scalar
-    const bool in_chunk = FULL ? (__builtin_amdgcn_readfirstlane(t) == site0) : (active && sl >= 0 && sl < nsites);
-    // the diagonal entry of my row (if it is one of the chunk's sites) is kept in a register: I am its only
-    // writer, the LDS copy is what the proposals of all threads read
-    double dgv = 0.0;
-    if (in_chunk) { dgv = G[t + (long)n * t]; dg[b * KD + sl] = dgv; }
-    const WalkerRng rs = rngs[w];
-    if (tid < KD) flip[tid] = 0;
-    if (tid < nsites) {
-        cs[tid] = cw[site0 + tid];
-        // the k-th uniform consumed by this chunk, whichever site consumes it (DQMC.jl:573)
-        const unsigned long long d = rs.draw + (unsigned long long)tid;
-        ul[tid] = rs.uniforms ? (d < rs.n_uniforms ? rs.uniforms[d] : 2.0) : philox_uniform(rs.seed, d);
-    }
-    int ndraw = 0, nneg = 0, exhausted = 0, cnt = 0;
-    double u_next = 0.0;  // ul[ndraw], requested as soon as its predecessor has been consumed
-    const double g0 = sc.gamma[0], g1 = sc.gamma[1], e0 = sc.ebos[0], e1 = sc.ebos[1];
-    const double du0 = sc.dup[0], du1 = sc.dup[1], dd0 = sc.ddn[0], dd1 = sc.ddn[1];
-
-    // G0[:, site] and G0[site, :] for one group of sites, requested one group ahead
-    double colr[SW_GROUP], rowr[SW_GROUP], coln[SW_GROUP], rown[SW_GROUP];
-    // no per-lane predicates: padding lanes read row/column n-1, sites past the chunk re-read the last one
-    // (their values are never used); a group that lies entirely past the chunk is skipped by a uniform branch
-    const int tq = FULL ? t : (active ? t : n - 1);
-    auto fetch = [&](int s0, double (&cc)[SW_GROUP], double (&rr)[SW_GROUP]) {
-        if (s0 >= nsites) return;
-        if (FULL) {
-            // the 8 row entries G[site0+s0 .. +7, t] are contiguous and 16-byte aligned: four wide loads instead of
-            // eight narrow ones (each such instruction touches 64 different lines per wave)
-            const double2 *rp = reinterpret_cast<const double2 *>(G + site0 + s0 + (long)n * tq);
-#pragma unroll
-            for (int x = 0; x < SW_GROUP / 2; ++x) {
-                const double2 v = rp[x];
-                rr[2 * x] = v.x;
-                rr[2 * x + 1] = v.y;
-            }
-#pragma unroll
-            for (int q = 0; q < SW_GROUP; ++q) cc[q] = G[tq + (long)n * (site0 + s0 + q)];
-            return;
-        }
-#pragma unroll
-        for (int q = 0; q < SW_GROUP; ++q) {
-            const int site = site0 + min(s0 + q, nsites - 1);
-            cc[q] = G[tq + (long)n * site];
-            rr[q] = G[site + (long)n * tq];
-        }
-    };
-    fetch(0, colr, rowr);
-    __syncthreads();
-    u_next = ul[0];
-
-    for (int s0 = 0; s0 < nsites; s0 += SW_GROUP) {
-        fetch(s0 + SW_GROUP, coln, rown);
-        // ---- group start: bring the group's rows/columns up to date with all slots of the chunk
-        {
-            const int cnt0 = __builtin_amdgcn_readfirstlane(cnt);
-            constexpr int HB = 8;  // slots per batch; the next batch is in flight while this one is consumed
-            // padding lanes (t >= n) read row n-1 and slots past the end re-read slot cnt0-1: the loads carry
-            // no predicates; only the arithmetic of the last, partial batch sits behind wave-uniform branches
-            const double *__restrict__ hU = Uo + (active ? t : n - 1);
-            const double *__restrict__ hV = VTo + (active ? t : n - 1);
-            double hu[HB], hv[HB], hun[HB], hvn[HB];
-            auto load_batch = [&](int m0, double (&au)[HB], double (&av)[HB]) {
-#pragma unroll
-                for (int k = 0; k < HB; ++k) {
-                    const int m = min(m0 + k, cnt0 - 1);
-                    au[k] = hU[(long)n * m];
-                    av[k] = hV[(long)n * m];
-                }
-            };
-            if (cnt0 > 0) load_batch(0, hu, hv);
-            int mb = 0;
-            for (; mb + HB <= cnt0; mb += HB) {  // full batches: no per-slot tests
-                if (mb + HB < cnt0) load_batch(mb + HB, hun, hvn);
-                // LDS operands buffered three slots ahead: their reads are in flight during the current slot's FMAs
-                double2 opu[4][SW_GROUP / 2], opv[4][SW_GROUP / 2];
-                auto load_ops = [&](int m, double2 (&ou)[SW_GROUP / 2], double2 (&ov)[SW_GROUP / 2]) {
-                    const double2 *ub = reinterpret_cast<const double2 *>(uit + m * KD + s0);
-                    const double2 *vb = reinterpret_cast<const double2 *>(vit + m * KD + s0);
-#pragma unroll
-                    for (int x = 0; x < SW_GROUP / 2; ++x) { ou[x] = ub[x]; ov[x] = vb[x]; }
-                };
-                load_ops(mb, opu[0], opv[0]);
-                load_ops(mb + 1, opu[1], opv[1]);
-                load_ops(mb + 2, opu[2], opv[2]);
-#pragma unroll
-                for (int k = 0; k < HB; ++k) {
-                    if (k + 3 < HB) load_ops(mb + k + 3, opu[(k + 3) & 3], opv[(k + 3) & 3]);
-#pragma unroll
-                    for (int x = 0; x < SW_GROUP / 2; ++x) {
-                        colr[2 * x] += hu[k] * opv[k & 3][x].x;       // G[t, site_q] += U'[t][m] V[m][site_q]
-                        colr[2 * x + 1] += hu[k] * opv[k & 3][x].y;
-                        rowr[2 * x] += opu[k & 3][x].x * hv[k];       // G[site_q, t] += U'[site_q][m] V[m][t]
-                        rowr[2 * x + 1] += opu[k & 3][x].y * hv[k];
-                    }
-                }
-#pragma unroll
-                for (int k = 0; k < HB; ++k) { hu[k] = hun[k]; hv[k] = hvn[k]; }
-            }
-            if (mb < cnt0) {  // last, partial batch (already loaded; slots past the end are clamped copies)
-#pragma unroll
-                for (int k = 0; k < HB - 1; ++k) {
-                    if (mb + k < cnt0) {
-                        const double *ub = uit + (mb + k) * KD + s0, *vb = vit + (mb + k) * KD + s0;
-#pragma unroll
-                        for (int q = 0; q < SW_GROUP; ++q) {
-                            colr[q] += hu[k] * vb[q];
-                            rowr[q] += ub[q] * hv[k];
-                        }
-                    }
-                }
-            }
-        }
-        // the next site's spin and diagonal entries are requested one site ahead: after the barrier of an
-        // accept (they are final then: an accept only touches entries of later sites) or right away on a reject
-        int c_in = cs[s0];
-        double d0_in = dg[s0], d1_in = MODEL != 0 ? dg[KD + s0] : 0.0;
-#pragma unroll
-        for (int q = 0; q < SW_GROUP; ++q) {
-            const int s = s0 + q;
-            if (FULL || s < nsites) {
-                const int i = site0 + s;
-                const int c = c_in;
-                const int ci = c > 0 ? 1 : 0;
-                const double d0 = d0_in;
-                double detratio, p, x0, x1 = 0.0, r0s = 0.0, r1s = 0.0, d0s = 0.0, d1s = 0.0;
-                if (model == 0) {  // HubbardModelAttractive.jl:113-127
-                    const double gamma = ci ? g1 : g0;
-                    const double r = 1.0 + gamma * (1.0 - d0);
-                    detratio = r * r;
-                    p = (ci ? e1 : e0) * detratio;
-                    x0 = gamma;  // numerator; the division by r is off the decision path (done on accept)
-                    x1 = r;
-                } else {           // HubbardModelRepulsive.jl:128-156,174-191
-                    const double d1 = d1_in;
-                    const double D0 = ci ? du1 : du0, D1 = ci ? dd1 : dd0;
-                    const double R0 = 1.0 + D0 * (1.0 - d0), R1 = 1.0 + D1 * (1.0 - d1);
-                    detratio = R0 * R1;
-                    p = detratio;
-                    r0s = R0; r1s = R1; d0s = D0; d1s = D1;
-                }
-                if (MODEL != 0 && check_sign && detratio < 0.0) {  // attractive: detratio = r^2 >= 0
-                    if (tid == 0) negv[nneg] = detratio;
-                    ++nneg;
-                }
-                bool acc;
-                if (p > 1.0) acc = true;  // DQMC.jl:573: rand() is consumed only when p <= 1
-                else {
-                    const double u = u_next;
-                    ++ndraw;
-                    u_next = ul[ndraw];  // (one past the chunk's last uniform at most: inside the LDS block, never used)
-                    if (u == 2.0) exhausted = 1;
-                    acc = u < p;
-                }
-                if (acc) {
-                    const int j = __builtin_amdgcn_readfirstlane(cnt);
-                    double xb;
-                    if (model == 0) xb = x0 / x1;  // Attractive.jl:149: x = gamma / (1 + gamma*IG[i])
-                    else {                          // Repulsive.jl:174-191: (R_other * inv_div) * Delta_b
-                        const double inv_div = 1.0 / detratio;
-                        xb = (b == 0) ? (r1s * inv_div) * d0s : (r0s * inv_div) * d1s;
-                    }
-                    const double ut = ((t == i) ? 1.0 : 0.0) - colr[q];  // IG = e_i - G[:,i]
-                    double newU = -(ut * xb), newV = rowr[q];
-                    if (!active) { newU = 0.0; newV = 0.0; }
-                    if (active) {  // slot history of this thread (also the flush GEMM's operands)
-                        Uo[t + (long)n * j] = newU;
-                        VTo[t + (long)n * j] = newV;
-                    }
-                    if (in_chunk) {
-                        uit[j * KD + sl] = newU;
-                        vit[j * KD + sl] = newV;
-                        if (sl > s) { dgv += newU * newV; dg[b * KD + sl] = dgv; }  // sites <= s are done
-                    }
-                    // cs[s] itself must stay intact: waves drift apart between barriers (a rejected
-                    // site has none) and a slower wave may not have read it yet for ITS proposal
-                    if (FULL) { if (__builtin_amdgcn_readfirstlane(tid) == 0) flip[s] = 1; }  // wave 0, same value from every lane
-                    else if (tid == 0) flip[s] = 1;
-                    ++cnt;
-                    // LDS-only barrier: __syncthreads() would drain the history stores as well
-                    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-                    if (q + 1 < SW_GROUP) {  // (reads one entry past the chunk at most: inside the LDS block, unused)
-                        c_in = cs[s + 1];
-                        d0_in = dg[s + 1];
-                        if (MODEL != 0) d1_in = dg[KD + s + 1];
-                    }
-                    // eager update of the rest of the group (static q' > q)
-                    {
-                        const double *ub = uit + j * KD + s0, *vb = vit + j * KD + s0;
-#pragma unroll
-                        for (int q2 = q + 1; q2 < SW_GROUP; ++q2) {
-                            colr[q2] += newU * vb[q2];
-                            rowr[q2] += ub[q2] * newV;
-                        }
-                    }
-                } else if (q + 1 < SW_GROUP) {
-                    c_in = cs[s + 1];
-                    d0_in = dg[s + 1];
-                    if (MODEL != 0) d1_in = dg[KD + s + 1];
-                }
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < SW_GROUP; ++q) { colr[q] = coln[q]; rowr[q] = rown[q]; }
-    }
-    // unused slots are zero padded so that the flush GEMM G0 += U' V always runs with K = KD
-    if (active) {
-        for (int m = cnt; m < KD; ++m) {
-            Uo[t + (long)n * m] = 0.0;
-            VTo[t + (long)n * m] = 0.0;
-        }
-    }
-    if (tid < nsites) cw[site0 + tid] = (int8_t)(flip[tid] ? -cs[tid] : cs[tid]);
-    if (tid == 0) {
-        for (int k = 0; k < nneg; ++k) magstats_push(stats[w].negative_probability, negv[k]);
-        rngs[w].draw = rs.draw + (unsigned long long)ndraw;
-        if (exhausted) rngs[w].exhausted = 1;
-        stats[w].prop_local += nsites;
-        stats[w].acc_local += cnt;
-    }
-}
-
-// chunk length = update slots per flush (the history lives in global memory, LDS holds KD x KD tables)
-int sweep_kd(int n, int nb) { (void)n; (void)nb; return SW_KD; }
-
-hipError_t launch_sweep_chunk(int n, int nb, int n_walkers, int model, double *G, long strideG, int8_t *conf_slice,
-                              long conf_stride, int site0, int nsites, double *Uout, double *VTout, long strideUV,
-                              SweepConsts sc, WalkerRng *rng, DevStats *stats, int check_sign, hipStream_t s)
-{
-    const int npad = (n + 63) & ~63;
-    const int threads = nb * npad;
-    if (threads > 1024 || nsites > SW_KD) return hipErrorInvalidValue;
-    dim3 grid(n_walkers), block(threads);
-    const size_t lds = ((size_t)nb * 2 * SW_KD * SW_KD + 6 * SW_KD) * sizeof(double) + 64;
-    const bool full = (n % 64 == 0) && (site0 % 64 == 0) && nsites == 64;
-#define SW_LAUNCH3(MT, MD, FL)                                                                                   \
-    do {                                                                                                         \
-        (void)hipFuncSetAttribute((const void *)sweep_chunk_kernel<MT, MD, FL>,                                  \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); /* per device: every launch */ \
-        hipLaunchKernelGGL((sweep_chunk_kernel<MT, MD, FL>), grid, block, lds, s, n, nb, model, G, strideG,      \
-                           conf_slice, conf_stride, site0, nsites, Uout, VTout, strideUV, sc, rng, stats,        \
-                           check_sign);                                                                          \
-    } while (0)
-#define SW_LAUNCH(MT)                                                                                            \
-    do {                                                                                                         \
-        if (model == 0) { if (full) SW_LAUNCH3(MT, 0, true); else SW_LAUNCH3(MT, 0, false); }                    \
-        else { if (full) SW_LAUNCH3(MT, 1, true); else SW_LAUNCH3(MT, 1, false); }                               \
-    } while (0)
-    if (threads <= 256) SW_LAUNCH(256);
-    else if (threads <= 512) SW_LAUNCH(512);
-    else SW_LAUNCH(1024);
-#undef SW_LAUNCH
-#undef SW_LAUNCH3
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------
 __global__ void set_identity_kernel(int n, double *A, long stride)
 {
     double *a = A + (long)blockIdx.y * stride;

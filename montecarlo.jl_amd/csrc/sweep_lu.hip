@@ -1039,7 +1039,8 @@ __global__ __launch_bounds__(256) void sweep_fused_kernel(SweepFusedArgs a)
 
 
 hipError_t launch_sweep_flush_lu(int n, int n_units, const double *Gin, double *Gout, long strideG, int site0,
-                                 int nsites, const double *img, hipStream_t s, hipEvent_t start, hipEvent_t stop)
+                                 int nsites, const double *img, const KernelSwitches &sw, hipStream_t s, hipEvent_t start,
+                                 hipEvent_t stop)
 {
     const bool wide = n % 128 == 0;
     const int nt = wide ? 8 : 4;
@@ -1064,32 +1065,20 @@ hipError_t launch_sweep_flush_lu(int n, int n_units, const double *Gin, double *
     // two column passes per workgroup (one pair of triangular solves per 64-row tile instead of two) when the grid is
     // more than one round of workgroups anyway: 512 units (config 4 on one GPU) 293 -> 230 us; a single round
     // (32 units: 256 workgroups) is faster with one pass each (16.7 vs 24 us).  DQMC_FLUSH_NCP2 forces it.
-    const bool ncp2_env = kernel_switches().flush_ncp2;
     static int n_cus[32] = {0};
     if (dev >= 0 && dev < 32 && n_cus[dev] == 0) {
         hipDeviceProp_t prop;
         n_cus[dev] = hipGetDeviceProperties(&prop, dev) == hipSuccess ? prop.multiProcessorCount : 256;
     }
-    const bool ncp2 = ncp2_env || (dev >= 0 && dev < 32 && groups * 8 * tm * tn > n_cus[dev]);
+    const bool ncp2 = sw.flush_ncp2 || (dev >= 0 && dev < 32 && groups * 8 * tm * tn > n_cus[dev]);
     // (n % 256 == 0 used to take 128-column passes here: 109 KB of LDS, one workgroup per CU, 230 us per launch of 512 units;
     // 64-column passes - 75 KB, two workgroups per CU - 190 us, software-pipelined 187.  A third workgroup per CU (R0 tile
     // aliased onto the solves' operands, 41 KB): 193 us; a late start of every other workgroup: slower by the delay.
     // In-kernel stamps (tools/fl_stamps.py): 38 k cycles until the operands of a workgroup are there, 8 - 10 k of solves,
     // 12 - 16 k per pass of 4 k cycles of MFMA - all resident workgroups fetch at ~17 B/cycle/CU, which is what the part
     // delivers to every CU at once; PMC: HBM traffic = algorithmic (profiles/r03_pmc_flush_512units.txt))
-    if (ncp2 && wide && full && n % 256 == 0 && ncp2_env) {  // (the former form: DQMC_FLUSH_NCP2, for A/B and under test)
-        static unsigned m2 = 0;
-        if (!(m2 & (1u << dev))) {
-            (void)hipFuncSetAttribute((const void *)sweep_flush_lu_kernel<true, 8, 2>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)(((size_t)LU_STRIDE + 128 * FL_LDR) * sizeof(double)));
-            m2 |= 1u << dev;
-        }
-        hipExtLaunchKernelGGL((sweep_flush_lu_kernel<true, 8, 2>), dim3(groups * 8 * tm * (tn / 2)), dim3(256), lds, s, start, stop,
-                              0, n, n_units, Gin, Gout, strideG, site0, nsites, img, tm, tn / 2, 2);
-        return hipGetLastError();
-    }
-    // n not a multiple of 128 (64-column tiles, e.g. n = 576: 9 x 9 tiles per unit, every row tile's solves done 9
-    // times over) and more than one round of workgroups: ONE workgroup per 64-row tile, all column tiles in passes
+    // more than one round of workgroups: ONE workgroup per 64-row tile, all 64-column tiles in passes (at n = 576 the
+    // one-pass form does every row tile's solves 9 times over)
     if (ncp2 && full && (n + 63) / 64 > 1) {
         const int tn4 = (n + 63) / 64;
         const size_t lds4 = ((size_t)LU_STRIDE + 64 * FL_LDR) * sizeof(double);

@@ -8,12 +8,17 @@ namespace dqmc {
 
 typedef double d4_t __attribute__((ext_vector_type(4)));
 
-// Right-looking form of the same solve, register resident: a workgroup owns 32 rows of X; wave (rt, par) keeps the
-// TRANSPOSED 16 x 16 tiles X'[block L][rows of row tile rt] of the column blocks L = par (mod 2) in MFMA accumulator
-// layout for the whole solve.  Step J: the two owners of block J finish it, X_J' = W_J' R_J' (four MFMAs on their own
-// registers), and leave it in LDS as a register image; after ONE barrier every wave subtracts T[J, L]' X_J' from its
+// X T = O with T upper triangular, solved by column blocks of 16, right-looking and register resident: a workgroup owns
+// 32 rows of X; wave (rt, par) keeps the TRANSPOSED 16 x 16 tiles X'[block L][rows of row tile rt] of the column blocks
+// L = par (mod 2) in MFMA accumulator layout for the whole solve.  Step J: the two owners of block J finish it,
+// X_J' = W_J' R_J' (four MFMAs on their own registers; W_J = inverse of the diagonal block J, trsm_diag_inv_kernel in
+// qr.hip), and leave it in LDS as a register image; after ONE barrier every wave subtracts T[J, L]' X_J' from its
 // later tiles (four MFMAs each, B operand = that image, A operand = the T row panel staged in LDS one step ahead).
-// The owners of block J + 1 update that tile first, so consecutive steps overlap.  Panel parameters as above.
+// The owners of block J + 1 update that tile first, so consecutive steps overlap.
+// Panel form: the nc columns c0 .. c0 + nc - 1 (nc <= 256) of an nr-row problem are solved against the diagonal block
+// T[c0 : c0 + nc, c0 : c0 + nc] of an ld x ld triangle; the contribution of the columns before c0 must already have been
+// subtracted (launch_trsm_right_upper does that with a GEMM for n > 256).  nr = nc = ld = n, c0 = 0 is the whole
+// n <= 256 problem.
 #ifdef TR_STAMPS  // diagnostic build only (tools/tr_stamps.py): cycle stamps of workgroup 0
 __device__ long long *tr_stamp_ptr = nullptr;
 #define TR_STAMP(idx)                                                                                        \
@@ -235,7 +240,7 @@ hipError_t launch_trsm_rl(int nr, int nc, int c0, int ld, int nblk_all, int n_un
     }
     const int slabs = (nr + 31) / 32;
     const int groups = (n_units + 7) / 8;
-    if (nc == 256 && nr % 32 == 0 && !kernel_switches().trsm_bounds)
+    if (nc == 256 && nr % 32 == 0)
         hipLaunchKernelGGL(trsm_rl_kernel<true>, dim3(groups * 8 * slabs), dim3(256), lds_r, s, nr, nc, c0, ld, nblk_all, A, sA, T,
                            sT, pivot, Out, sO, slabs, winv, n_units);
     else

@@ -303,23 +303,20 @@ def test_cooperative_qr_timeout_falls_back(gpu, O):
                                    {"DQMC_QR_NOBLOCKED": "1", "DQMC_QR_TAIL": "0"},
                                    {"DQMC_QR_NOBLOCKED": "1", "DQMC_QR_NOCOOP": "1"},
                                    {"DQMC_QR_NOBLOCKED": "1", "DQMC_QR_NOCOOP": "1", "DQMC_QR_TAIL": "0"},
-                                   {"DQMC_QRB_SITES": "1"},
-                                   {"DQMC_TRSM_LL": "1"}, {"DQMC_TRSM_SIMPLE": "1"}, {"DQMC_SWEEP_OLD": "1"},
-                                   {"DQMC_TRSM_BOUNDS": "1"},
-                                   {"DQMC_QR_NOBLOCKED": "1", "DQMC_QR_NOCOOP": "1", "DQMC_QR_TILE_BOUNDS": "1"}],
+                                   {"DQMC_QRB_SITES": "1"}, {"DQMC_TRSM_SIMPLE": "1"}],
                          ids=["slab_chains", "fused_sweep", "two_pass_flush", "blocked_udt_sc1_mailbox",
                               "udt_pivoted_cooperative", "udt_pivoted_cooperative_sc1", "udt_pivoted_cooperative_only",
                               "udt_pivoted_tile_plus_tail", "udt_pivoted_tile_only", "blocked_udt_slice_sequences_only",
-                              "trsm_left_looking", "trsm_substitution",
-                              "sweep_round1", "trsm_with_bounds", "udt_pivoted_tile_with_bounds"])
+                              "trsm_substitution"])
 def test_fast_paths_against_their_plain_forms(gpu, plain):
     """The default launch forms at n = 256 (slab-resident product chains, elimination fused with the previous chunk's
-    flush, the one-launch pre-pivoted UDT; the two-pass flush of the throughput regime against the one-pass one) against
-    the forms they replace, selected per handle through the environment: same seeds, HS field identical, G within the
-    parity tolerance.  The udt_pivoted_* entries run the reference's own pivot rule (UDT.jl:212-246: the cooperative
-    two-phase QR, the tile kernels) in place of the pre-pivoted blocked factorisation - a different column order, the same
-    G; *_sc1_* are the forms whose hand-off stores are agent-scope (write-through), i.e. inside the HIP memory model;
-    the remaining entries are the fallbacks that ship behind switches (round-1 TRSM and sweep kernels)."""
+    flush, the one-launch pre-pivoted UDT) against the forms that other shapes or switches select, per handle through
+    the environment: same seeds, HS field identical, G within the parity tolerance.  two_pass_flush runs the separate
+    flush in the multi-pass form that more units than CUs take (config 4) at 2 walkers.  The udt_pivoted_* entries run
+    the reference's own pivot rule (UDT.jl:212-246: the cooperative two-phase QR, the tile kernels) in place of the
+    pre-pivoted blocked factorisation - a different column order, the same G; *_sc1_* are the forms whose hand-off
+    stores are agent-scope (write-through), i.e. inside the HIP memory model; trsm_substitution is the substitution
+    solve (the stand-alone primitives' solve at n > 256) in place of the MFMA solves."""
     def run(env):
         old = {k: os.environ.get(k) for k in env}
         os.environ.update(env)

@@ -35,7 +35,7 @@ BUDGET = {
     "sweep_lu4_kernel<1, true>": (1, 1),
     "sweep_lu4_kernel<2, true>": (1, 1),
     "sweep_flush_lu_kernel<true, 8, 1>": (1, 0),
-    "sweep_flush_lu_kernel<true, 8, 2>": (1, 0),
+    "sweep_flush_lu_kernel<true, 4, 0>": (1, 0),  # more units than CUs (config 4)
     "qrb_udt_kernel": (1, 0),                    # one-launch UDT (a hand-off poll is one load -> wait by nature)
     "qr_coop_kernel": (1, 0),
     "qr_tail_kernel<128, 4>": (3, 0),

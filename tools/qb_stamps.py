@@ -15,8 +15,8 @@ X = rng.standard_normal((32, 256, 256))
 for rep in range(2):
     gpu.udt_AVX_pivot(X, True)
 torch.cuda.synchronize()
-j0 = int(os.environ.get("DQMC_QR_TAIL", "128"))
-nsteps, nw = 256 - j0, (8 if j0 == 64 else 4)
+j0 = 128  # hand-over step of the cooperative kernel to qr_tail_kernel<128, 4>
+nsteps, nw = 256 - j0, 4
 t = buf.cpu().numpy().astype(np.int64).reshape(8, 192, 8)[:nw, :nsteps]
 names = ["start->wave candidate", "candidate->extracted+published", "wait at barrier", "8-candidate select", "LDS column + scalars",
          "u + dots", "sum8 + update + norms"]
