@@ -63,6 +63,12 @@ typedef struct {
     const double *eTinv;             /* hopping_matrix_exp_inv         = exp(+dtau/2 T) */
     const double *eT2;               /* hopping_matrix_exp_squared     */
     const double *eTinv2;            /* hopping_matrix_exp_inv_squared */
+    /* At n_sites == 256 (dense slab path, no checkerboard, DQMC_NO_KRON unset) dqmc_create tests each block of eT2 and
+     * eTinv2 for the Kronecker form E = Ey (x) Ex of the periodic 16 x 16 square lattice (site x + 16 y):
+     * Ex = E[0:16, 0:16], Ey = E[0::16, 0::16] / E[0,0], accepted when E[0,0] > 0 and
+     * max|E - Ey (x) Ex| <= 256 DBL_EPSILON max|E|.  Then slice products and wraps apply the two 16 x 16 factors instead of
+     * the dense matrix (dqmc_kron_hopping reports it); the difference is rounding of the exponential, far inside the
+     * 1e-10 tolerance on G.  Any other hopping keeps the dense products. */
 } dqmc_params;
 
 /* MagnitudeStats (DQMC.jl:4-31): log10 magnitudes */
@@ -308,6 +314,8 @@ int dqmc_set_checkerboard(dqmc_handle *h, int32_t kmax, int32_t n_mats, const do
  * the guarded single-workgroup kernel launched behind it redoes the factorisation, so results stay valid.  This counter reports
  * how often that happened.  (The one-launch UDT has no second path: its time-outs fail the call, see dqmc_device_errors.) */
 int dqmc_qr_fallbacks(dqmc_handle *h, int64_t *count);
+/* 1 when slice products and wraps apply eT2 / eTinv2 as Kronecker products of 16 x 16 factors (see dqmc_params), else 0 */
+int dqmc_kron_hopping(dqmc_handle *h, int32_t *on);
 /* which call sites of udt_AVX_pivot! (UDT.jl:192-306) this handle serves with the one-launch pre-pivoted factorisation:
  * bit 0 add_slice_sequence_left/right (stack.jl:272-311) and other callers, bit 1 / bit 2 the two factorisations of
  * calculate_greens_AVX! (stack.jl:349, :376); 0 = the reference's pivot rule everywhere (n != 256, > 32 units, DQMC_QR_NOBLOCKED) */

@@ -120,6 +120,7 @@ SIGNATURES = {
     "dqmc_set_checkerboard": (C.c_int, [_H, C.c_int32, C.c_int32, _dp, C.POINTER(C.c_int32), _dp, _dp,
                               C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "dqmc_qr_fallbacks": (C.c_int, [_H, C.POINTER(C.c_int64)]),
+    "dqmc_kron_hopping": (C.c_int, [_H, C.POINTER(C.c_int32)]),
     "dqmc_device_errors": (C.c_int, [_H, C.POINTER(C.c_int32)]),
     "dqmc_udt_one_launch_sites": (C.c_int, [_H, C.POINTER(C.c_int32)]),
     "dqmc_build_commit": (C.c_char_p, []),

@@ -42,6 +42,10 @@ struct dqmc_handle {
     double *eT = nullptr, *eTinv = nullptr, *eT2 = nullptr, *eTinv2 = nullptr;
     double *eT2T = nullptr;  // transposed copy of eT2: A operand of the daggered slice products in slab.hip
     bool slab = false;       // n == 256 dense path: slice chains and wraps as slab-resident launches
+    // n == 256 hopping exponentials that are Kronecker products Ey (x) Ex of 16 x 16 factors (kron_factor): slice chains
+    // and wraps take kron.hip instead of slab.hip.  kron_f: [eT2, eTinv2, eT2', eTinv2'] x [x, y] x nb x 16 x 16
+    bool kron = false;
+    double *kron_f = nullptr;
     int8_t *conf = nullptr;  // W x (N x M)
     // stack (slot-major): u/t: (K+1) x units x n^2 ; d: (K+1) x units x n
     double *u_stack = nullptr, *t_stack = nullptr, *d_stack = nullptr;
@@ -303,6 +307,31 @@ static int set_ones(dqmc_handle *h, double *d)
     return 0;
 }
 
+// eT2 / eTinv2 of the 16 x 16 periodic square lattice (n = 256, site x + 16 y) as Ey (x) Ex: Ex = E[0:16, 0:16] (the
+// y = y' = 0 block), Ey = E[0::16, 0::16] / E[0, 0].  Accepted when max|E - Ey (x) Ex| <= 256 eps max|E| (the exponentials
+// of the lattice's Kronecker-sum hopping matrix measure 16-28 ulp); any other hopping keeps the dense slab path.
+static bool kron_factor(const double *E, double *fx, double *fy)
+{
+    const int n = 256;
+    const double e00 = E[0];
+    if (!(e00 > 0.0)) return false;
+    for (int j = 0; j < 16; ++j)
+        for (int i = 0; i < 16; ++i) {
+            fx[i + 16 * j] = E[i + (size_t)n * j];
+            fy[i + 16 * j] = E[16 * i + (size_t)n * 16 * j] / e00;
+        }
+    double emax = 0.0, rmax = 0.0;
+    for (int y2 = 0; y2 < 16; ++y2)
+        for (int x2 = 0; x2 < 16; ++x2)
+            for (int y = 0; y < 16; ++y)
+                for (int x = 0; x < 16; ++x) {
+                    const double e = E[(x + 16 * y) + (size_t)n * (x2 + 16 * y2)];
+                    emax = std::max(emax, std::fabs(e));
+                    rmax = std::max(rmax, std::fabs(e - fy[y + 16 * y2] * fx[x + 16 * x2]));
+                }
+    return std::isfinite(emax) && rmax <= 256.0 * 2.220446049250313e-16 * emax;
+}
+
 // The kernel-selection and test switches, read from the environment once per handle / stand-alone
 // primitive call: nothing else reads them (the launchers get them from the handle)
 static void read_kernel_switches(dqmc_handle *h)
@@ -320,6 +349,7 @@ static void read_kernel_switches(dqmc_handle *h)
     k.sweep_split = getenv("DQMC_SWEEP_SPLIT") != nullptr;
     k.flush_ncp2 = getenv("DQMC_FLUSH_NCP2") != nullptr;
     k.no_slab = getenv("DQMC_NO_SLAB") != nullptr;
+    k.no_kron = getenv("DQMC_NO_KRON") != nullptr;
 }
 
 static int alloc_qr_workspace(dqmc_handle *h)
@@ -552,6 +582,35 @@ static int run_slab(dqmc_handle *h, const SlabArgs &a)
     return timing_push(h, ea, eb, DQMC_K_GEMM);
 }
 
+// ---- the same with Kronecker-factored hopping exponentials (kron.hip) -------------
+enum { KF_ET2 = 0, KF_ETINV2 = 1, KF_ET2T = 2, KF_ETINV2T = 3 };
+static bool use_kron(const dqmc_handle *h) { return h->kron && !h->cb.on; }
+static KronArgs kron_base(dqmc_handle *h, const double *X0, double *out)
+{
+    KronArgs a{};
+    a.n_units = h->units; a.nb = h->nb; a.nsteps = 0;
+    a.X0 = X0; a.x_su = h->nn;
+    a.out = out; a.out_su = h->nn;
+    a.conf_stride = (long)h->N * h->M;
+    a.epl = h->epl; a.eml = h->eml;
+    return a;
+}
+static KronStep &kron_step(dqmc_handle *h, KronArgs &a, int which)
+{
+    KronStep &st = a.st[a.nsteps++];
+    st = KronStep{};
+    st.ax = h->kron_f + (size_t)which * 2 * h->nb * 256;
+    st.ay = st.ax + (size_t)h->nb * 256;
+    return st;
+}
+static int run_kron(dqmc_handle *h, const KronArgs &a)
+{
+    hipEvent_t ea, eb;
+    timing_events(h, &ea, &eb);
+    HIPCHK(launch_kron_chain(a, h->cur, ea, eb));
+    return timing_push(h, ea, eb, DQMC_K_GEMM);
+}
+
 // ---- slice sequences (stack.jl:272-311, slice_matrices.jl:42-76) -------------------
 // The s products of a stack interval only need the HS field of slices that sweep_spatial has already left behind, in
 // the order the sweep visits them (up pass: B_l X for l = (idx-1)s+1 .. idx s; down pass: B_l' X for l = idx s ..
@@ -585,7 +644,24 @@ static int add_slice_sequence(dqmc_handle *h, int dir, int idx, bool wrap_temp)
         if (h->slab && !h->cb.on) CHK(wrap_greens_slab(h, h->greens, h->greens_temp, h->current_slice - 1, 1));
     }
     double *out = nullptr;
-    if (h->slab && !h->cb.on && h->s <= SLAB_MAX_STEPS) {  // the (remaining) products in one launch
+    if (use_kron(h) && h->s <= SLAB_MAX_STEPS) {  // the same launch with the factored eT2 (kron.hip)
+        out = h->bufA;
+        KronArgs a = kron_base(h, X, out);
+        for (int t = 0; t < h->s; ++t) {
+            if (dir == 1) {
+                KronStep &st = kron_step(h, a, KF_ET2);
+                st.pre_conf = conf_slice(h, (idx - 1) * h->s + 1 + t);
+                st.pre_sign = +1;
+            } else {  // B_l' X = eV (eT2' X)
+                KronStep &st = kron_step(h, a, KF_ET2T);
+                st.post_conf = conf_slice(h, idx * h->s - t);
+                st.post_sign = +1;
+            }
+        }
+        a.col_d = dslot(h, src); a.col_stride = h->n;  // stack.jl:281 / :305
+        CHK(run_kron(h, a));
+    }
+    else if (h->slab && !h->cb.on && h->s <= SLAB_MAX_STEPS) {  // the (remaining) products in one launch
         out = h->bufA;
         SlabArgs a = slab_base(h, X, h->nn, 0, out);
         chain_steps(h, a, dir, idx, t0, h->s);
@@ -624,8 +700,29 @@ static int add_slice_sequence_right(dqmc_handle *h, int idx) { return add_slice_
 
 // wrap_greens! (stack.jl:491-500), out of place, one launch: column slab c of the result is
 //   +1:  eT2 (eV (G (eV^-1 eTinv2[:, c])))          -1:  eV^-1 (eTinv2 (G eT2[:, c])) eV[c]
+// Factored form (kron.hip): two one-step launches through bufB, each storing its result transposed, so that the right
+// product becomes a left product with the transposed factors:
+//   +1:  P = eT2 (eV G)           -> bufB = P'        dst = (eTinv2' (eV^-1 P'))'  = P eV^-1 eTinv2
+//   -1:  P = eV^-1 (eTinv2 G)     -> bufB = P'        dst = (eV (eT2' P'))'        = P eT2 eV
+static int wrap_greens_kron(dqmc_handle *h, const double *src, double *dst, int curr_slice, int direction)
+{
+    const int8_t *c = conf_slice(h, direction == -1 ? curr_slice - 1 : curr_slice);
+    KronArgs a = kron_base(h, src, h->bufB);
+    a.transpose_out = 1;
+    KronStep &s1 = kron_step(h, a, direction == -1 ? KF_ETINV2 : KF_ET2);
+    if (direction == -1) { s1.post_conf = c; s1.post_sign = -1; }
+    else { s1.pre_conf = c; s1.pre_sign = +1; }
+    CHK(run_kron(h, a));
+    KronArgs b = kron_base(h, h->bufB, dst);
+    b.transpose_out = 1;
+    KronStep &s2 = kron_step(h, b, direction == -1 ? KF_ET2T : KF_ETINV2T);
+    if (direction == -1) { s2.post_conf = c; s2.post_sign = +1; }
+    else { s2.pre_conf = c; s2.pre_sign = -1; }
+    return run_kron(h, b);
+}
 static int wrap_greens_slab(dqmc_handle *h, const double *src, double *dst, int curr_slice, int direction)
 {
+    if (use_kron(h)) return wrap_greens_kron(h, src, dst, curr_slice, direction);
     if (direction == -1) {
         const int8_t *c = conf_slice(h, curr_slice - 1);
         SlabArgs a = slab_base(h, h->eT2, 0, h->nn, dst);
@@ -962,6 +1059,27 @@ int dqmc_create(const dqmc_params *p, dqmc_handle **out)
         CCHK(dalloc(h, &h->eT2T, cn));
         CHIP(hipMemcpy(h->eT2T, tr.data(), cn * sizeof(double), hipMemcpyHostToDevice));
         h->slab = true;
+    }
+    if (h->slab && !h->sw.no_kron) {
+        // factors of eT2, eTinv2 and their transposes ((Ey (x) Ex)' = Ey' (x) Ex': same residual, no second check)
+        std::vector<double> f((size_t)4 * 2 * nb * 256);
+        bool ok = true;
+        for (int m = 0; m < 2 && ok; ++m)
+            for (int b = 0; b < nb && ok; ++b) {
+                double *fx = f.data() + ((size_t)m * 2 * nb + b) * 256, *fy = fx + (size_t)nb * 256;
+                double *tx = f.data() + ((size_t)(m + 2) * 2 * nb + b) * 256, *ty = tx + (size_t)nb * 256;
+                ok = kron_factor((m ? p->eTinv2 : p->eT2) + (size_t)b * h->nn, fx, fy);
+                for (int j = 0; j < 16; ++j)
+                    for (int i = 0; i < 16; ++i) {
+                        tx[i + 16 * j] = fx[j + 16 * i];
+                        ty[i + 16 * j] = fy[j + 16 * i];
+                    }
+            }
+        if (ok) {
+            CCHK(dalloc(h, &h->kron_f, f.size()));
+            CHIP(hipMemcpy(h->kron_f, f.data(), f.size() * sizeof(double), hipMemcpyHostToDevice));
+            h->kron = true;
+        }
     }
     CCHK(dalloc(h, &h->conf, (size_t)h->W * h->N * h->M));
     {
@@ -1738,6 +1856,14 @@ int dqmc_udt_one_launch_sites(dqmc_handle *h, int32_t *mask)
 }
 
 // diagnostics: cooperative-QR launches whose hand-offs timed out and were redone by the single-workgroup kernel
+int dqmc_kron_hopping(dqmc_handle *h, int32_t *on)
+{
+    ENTER(h);
+    if (!on) return DQMC_ERR_INVALID;
+    *on = use_kron(h) ? 1 : 0;
+    return DQMC_OK;
+}
+
 int dqmc_qr_fallbacks(dqmc_handle *h, int64_t *count)
 {
     ENTER(h);

@@ -94,6 +94,23 @@ struct SlabArgs {
     double epl, eml;
 };
 hipError_t launch_slab_chain(const SlabArgs &a, hipStream_t s, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
+// The same chains with Kronecker-factored A_s = ay (x) ax (kron.hip, n = 256 = 16 x 16 sites)
+struct KronStep {
+    const double *ax, *ay;               // 16 x 16 factors, column-major, block b at + 256 b
+    const int8_t *pre_conf; int pre_sign;    // conf pointers already offset to the slice; null = no scaling
+    const int8_t *post_conf; int post_sign;
+};
+struct KronArgs {
+    int n_units, nb, nsteps;
+    KronStep st[SLAB_MAX_STEPS];
+    const double *X0; long x_su;         // X_0 per unit
+    double *out; long out_su;            // must not alias X0
+    const double *col_d; long col_stride;  // final column scaling by an array (per unit), or none
+    int transpose_out;                   // store the result transposed
+    long conf_stride;                    // per walker
+    double epl, eml;
+};
+hipError_t launch_kron_chain(const KronArgs &a, hipStream_t s, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
 
 // Column-pivoted Householder QR, in place (udt_AVX_pivot! "QR decomposition" loop,
 // src/linalg/UDT.jl:212-246).  On exit A holds R on/above the diagonal and the
@@ -117,6 +134,7 @@ struct KernelSwitches {
     bool sweep_split = false;     // DQMC_SWEEP_SPLIT: elimination and flush as separate launches
     bool flush_ncp2 = false;      // DQMC_FLUSH_NCP2: the separate flush always in its multi-pass form
     bool no_slab = false;         // DQMC_NO_SLAB: no slab-resident product chains (slab.hip)
+    bool no_kron = false;         // DQMC_NO_KRON: dense slab chains even where the hopping factorises (kron.hip)
 };
 
 constexpr int QR_COOP_SLOT = 528;  // 264 packets of 16 bytes

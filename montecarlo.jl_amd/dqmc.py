@@ -672,6 +672,12 @@ class DQMC:
         self._c(lib().dqmc_qr_fallbacks(self._h, C.byref(n)))
         return n.value
 
+    def kron_hopping(self):
+        """True when slice products and wraps apply the hopping exponentials as Kronecker products of 16 x 16 factors"""
+        f = C.c_int32(0)
+        self._c(lib().dqmc_kron_hopping(self._h, C.byref(f)))
+        return bool(f.value)
+
     def udt_one_launch_sites(self):
         """bit mask of the udt_AVX_pivot! call sites served by the one-launch pre-pivoted factorisation (0: none)"""
         w = C.c_int32(0)

@@ -1,0 +1,33 @@
+"""ISA budget of the Kronecker-factored chain kernel (kron.hip), in the style of test_isa_guard.py: no flat memory
+operations, at most one load -> s_waitcnt vmcnt(0) pair in a row, no MFMA source-C write-after-read."""
+import os
+import sys
+
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from test_isa_guard import _load_shipped, _runs_and_flat  # noqa: E402
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+
+@pytest.fixture(scope="module")
+def kron_kernels():
+    hits = {n: v for n, v in _load_shipped().items() if "kron_chain_kernel" in n and "(" in n}
+    assert hits, "kron_chain_kernel is not in the shipped library"
+    return hits
+
+
+def test_kron_chain_kernel_budget(kron_kernels):
+    for name, ins in kron_kernels.items():
+        run, flat = _runs_and_flat(ins)
+        assert run <= 1, (name, "consecutive load -> s_waitcnt vmcnt(0) pairs", run)
+        assert flat == 0, (name, "flat memory operations", flat)
+        assert sum(t.startswith("v_mfma_f64_16x16x4") for t in ins) >= 8
+
+
+def test_kron_chain_kernel_has_no_mfma_source_c_hazard(kron_kernels):
+    import scan_mfma_war as W
+    for name, ins in kron_kernels.items():
+        assert not W.hazards(["\t" + t for t in ins]), name
