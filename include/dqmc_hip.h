@@ -63,12 +63,15 @@ typedef struct {
     const double *eTinv;             /* hopping_matrix_exp_inv         = exp(+dtau/2 T) */
     const double *eT2;               /* hopping_matrix_exp_squared     */
     const double *eTinv2;            /* hopping_matrix_exp_inv_squared */
-    /* At n_sites == 256 (dense slab path, no checkerboard, DQMC_NO_KRON unset) dqmc_create tests each block of eT2 and
-     * eTinv2 for the Kronecker form E = Ey (x) Ex of the periodic 16 x 16 square lattice (site x + 16 y):
-     * Ex = E[0:16, 0:16], Ey = E[0::16, 0::16] / E[0,0], accepted when E[0,0] > 0 and
-     * max|E - Ey (x) Ex| <= 256 DBL_EPSILON max|E|.  Then slice products and wraps apply the two 16 x 16 factors instead of
-     * the dense matrix (dqmc_kron_hopping reports it); the difference is rounding of the exponential, far inside the
-     * 1e-10 tolerance on G.  Any other hopping keeps the dense products. */
+    /* dqmc_create tests each block of eT2 and eTinv2 for a Kronecker form when no checkerboard is set and DQMC_NO_KRON
+     * is unset; the test is max|E - product of the factors| <= 256 DBL_EPSILON max|E| with E[0,0] > 0.
+     *  - n_sites == 256 (dense slab path): E = Ey (x) Ex, the periodic 16 x 16 square lattice (site x + 16 y), with
+     *    Ex = E[0:16, 0:16], Ey = E[0::16, 0::16] / E[0,0].
+     *  - n_sites == 512: E = Ez (x) Ey (x) Ex, the periodic 8 x 8 x 8 cubic lattice (site x + 8 y + 64 z), with
+     *    Ex = E[0:8, 0:8], Ey = E[0::8, 0::8][0:8, 0:8] / E[0,0], Ez = E[0::64, 0::64] / E[0,0].
+     * When every block passes, slice products and wraps apply the factors instead of the dense matrix
+     * (dqmc_kron_hopping reports it); the difference is rounding of the exponential, far inside the 1e-10 tolerance on G.
+     * Any other size or hopping keeps the dense products. */
 } dqmc_params;
 
 /* MagnitudeStats (DQMC.jl:4-31): log10 magnitudes */
@@ -314,7 +317,8 @@ int dqmc_set_checkerboard(dqmc_handle *h, int32_t kmax, int32_t n_mats, const do
  * the guarded single-workgroup kernel launched behind it redoes the factorisation, so results stay valid.  This counter reports
  * how often that happened.  (The one-launch UDT has no second path: its time-outs fail the call, see dqmc_device_errors.) */
 int dqmc_qr_fallbacks(dqmc_handle *h, int64_t *count);
-/* 1 when slice products and wraps apply eT2 / eTinv2 as Kronecker products of 16 x 16 factors (see dqmc_params), else 0 */
+/* 1 when slice products and wraps apply eT2 / eTinv2 as Kronecker products (16 x 16 factors at n = 256, 8 x 8 factors at
+ * n = 512; see dqmc_params), else 0 */
 int dqmc_kron_hopping(dqmc_handle *h, int32_t *on);
 /* which call sites of udt_AVX_pivot! (UDT.jl:192-306) this handle serves with the one-launch pre-pivoted factorisation:
  * bit 0 add_slice_sequence_left/right (stack.jl:272-311) and other callers, bit 1 / bit 2 the two factorisations of

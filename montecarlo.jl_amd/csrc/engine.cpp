@@ -43,9 +43,13 @@ struct dqmc_handle {
     double *eT2T = nullptr;  // transposed copy of eT2: A operand of the daggered slice products in slab.hip
     bool slab = false;       // n == 256 dense path: slice chains and wraps as slab-resident launches
     // n == 256 hopping exponentials that are Kronecker products Ey (x) Ex of 16 x 16 factors (kron_factor): slice chains
-    // and wraps take kron.hip instead of slab.hip.  kron_f: [eT2, eTinv2, eT2', eTinv2'] x [x, y] x nb x 16 x 16
+    // and wraps take kron.hip instead of slab.hip.  kron_f: [eT2, eTinv2, eT2', eTinv2'] x [x, y] x nb x 16 x 16.
+    // n == 512 ones that are Ez (x) Ey (x) Ex of 8 x 8 factors (kron3_factor): kron3.hip instead of the dense GEMMs.
+    // kron_f: [eT2, eTinv2, eT2', eTinv2'] x ([Exy image] x nb x 4096, [Ez image] x nb x 256).
+    // kron_fa / kron_fb: doubles per block of the two operand sets (ax / ay of a KronStep)
     bool kron = false;
     double *kron_f = nullptr;
+    int kron_fa = 0, kron_fb = 0;
     int8_t *conf = nullptr;  // W x (N x M)
     // stack (slot-major): u/t: (K+1) x units x n^2 ; d: (K+1) x units x n
     double *u_stack = nullptr, *t_stack = nullptr, *d_stack = nullptr;
@@ -332,6 +336,50 @@ static bool kron_factor(const double *E, double *fx, double *fy)
     return std::isfinite(emax) && rmax <= 256.0 * 2.220446049250313e-16 * emax;
 }
 
+// eT2 / eTinv2 of the 8 x 8 x 8 periodic cubic lattice (n = 512, site x + 8 y + 64 z) as Ez (x) Ey (x) Ex:
+// Ex = E[0:8, 0:8], Ey = E[0::8, 0::8][0:8, 0:8] / E[0, 0], Ez = E[0::64, 0::64] / E[0, 0].  The same acceptance as
+// kron_factor (the cubic lattice's exponentials measure 18-39 ulp); any other hopping keeps the dense path.
+static bool kron3_factor(const double *E, double *fx, double *fy, double *fz)
+{
+    const int n = 512;
+    const double e00 = E[0];
+    if (!(e00 > 0.0)) return false;
+    for (int j = 0; j < 8; ++j)
+        for (int i = 0; i < 8; ++i) {
+            fx[i + 8 * j] = E[i + (size_t)n * j];
+            fy[i + 8 * j] = E[8 * i + (size_t)n * 8 * j] / e00;
+            fz[i + 8 * j] = E[64 * i + (size_t)n * 64 * j] / e00;
+        }
+    double emax = 0.0, rmax = 0.0;
+    for (int c = 0; c < n; ++c)
+        for (int r = 0; r < n; ++r) {
+            const double e = E[r + (size_t)n * c];
+            const double f = fz[(r >> 6) + 8 * (c >> 6)] * fy[((r >> 3) & 7) + 8 * ((c >> 3) & 7)] * fx[(r & 7) + 8 * (c & 7)];
+            emax = std::max(emax, std::fabs(e));
+            rmax = std::max(rmax, std::fabs(e - f));
+        }
+    return std::isfinite(emax) && rmax <= 256.0 * 2.220446049250313e-16 * emax;
+}
+// The operand images kron3.hip reads (see there) of A = Ez (x) Exy, Exy = Ey (x) Ex; tr: of A' = Ez' (x) Exy'
+static void kron3_images(const double *fx, const double *fy, const double *fz, bool tr, double *img_xy, double *img_z)
+{
+    auto exy = [&](int r, int c) {
+        if (tr) std::swap(r, c);
+        return fy[(r >> 3) + 8 * (c >> 3)] * fx[(r & 7) + 8 * (c & 7)];
+    };
+    auto ez = [&](int r, int c) { return tr ? fz[c + 8 * r] : fz[r + 8 * c]; };
+    for (int mp = 0; mp < 4; ++mp)
+        for (int m = 0; m < 4; ++m)
+            for (int r = 0; r < 4; ++r)
+                for (int lane = 0; lane < 64; ++lane)
+                    img_xy[((mp * 4 + m) * 4 + r) * 64 + lane] = exy(16 * mp + (lane & 15), 16 * m + 4 * r + (lane >> 4));
+    for (int q = 0; q < 4; ++q)
+        for (int lane = 0; lane < 64; ++lane) {
+            const int row = lane & 15, k = 4 * q + (lane >> 4);
+            img_z[q * 64 + lane] = (row >> 3) == (k >> 3) ? ez(row & 7, k & 7) : 0.0;
+        }
+}
+
 // The kernel-selection and test switches, read from the environment once per handle / stand-alone
 // primitive call: nothing else reads them (the launchers get them from the handle)
 static void read_kernel_switches(dqmc_handle *h)
@@ -585,6 +633,8 @@ static int run_slab(dqmc_handle *h, const SlabArgs &a)
 // ---- the same with Kronecker-factored hopping exponentials (kron.hip) -------------
 enum { KF_ET2 = 0, KF_ETINV2 = 1, KF_ET2T = 2, KF_ETINV2T = 3 };
 static bool use_kron(const dqmc_handle *h) { return h->kron && !h->cb.on; }
+// wraps out of place (wrap_greens_slab): the n = 256 slab path and every factored path
+static bool oop_wrap(const dqmc_handle *h) { return (h->slab || h->kron) && !h->cb.on; }
 static KronArgs kron_base(dqmc_handle *h, const double *X0, double *out)
 {
     KronArgs a{};
@@ -599,15 +649,16 @@ static KronStep &kron_step(dqmc_handle *h, KronArgs &a, int which)
 {
     KronStep &st = a.st[a.nsteps++];
     st = KronStep{};
-    st.ax = h->kron_f + (size_t)which * 2 * h->nb * 256;
-    st.ay = st.ax + (size_t)h->nb * 256;
+    st.ax = h->kron_f + (size_t)which * h->nb * (h->kron_fa + h->kron_fb);
+    st.ay = st.ax + (size_t)h->nb * h->kron_fa;
     return st;
 }
 static int run_kron(dqmc_handle *h, const KronArgs &a)
 {
     hipEvent_t ea, eb;
     timing_events(h, &ea, &eb);
-    HIPCHK(launch_kron_chain(a, h->cur, ea, eb));
+    if (h->n == 512) HIPCHK(launch_kron3_chain(a, h->cur, ea, eb));
+    else HIPCHK(launch_kron_chain(a, h->cur, ea, eb));
     return timing_push(h, ea, eb, DQMC_K_GEMM);
 }
 
@@ -641,7 +692,7 @@ static int add_slice_sequence(dqmc_handle *h, int dir, int idx, bool wrap_temp)
     const int t0 = 0;
     const double *X = uslot(h, src);
     if (wrap_temp) {
-        if (h->slab && !h->cb.on) CHK(wrap_greens_slab(h, h->greens, h->greens_temp, h->current_slice - 1, 1));
+        if (oop_wrap(h)) CHK(wrap_greens_slab(h, h->greens, h->greens_temp, h->current_slice - 1, 1));
     }
     double *out = nullptr;
     if (use_kron(h) && h->s <= SLAB_MAX_STEPS) {  // the same launch with the factored eT2 (kron.hip)
@@ -744,7 +795,7 @@ static int wrap_greens_inplace(dqmc_handle *h, double *gf, int curr_slice, int d
 // *gf <- wrapped *gf (the slab path writes into tmp1 and exchanges the two pointers)
 static int wrap_greens(dqmc_handle *h, double **gf, int curr_slice, int direction)
 {
-    if (h->slab && !h->cb.on) {
+    if (oop_wrap(h)) {
         CHK(wrap_greens_slab(h, *gf, h->tmp1, curr_slice, direction));
         std::swap(*gf, h->tmp1);
         return 0;
@@ -833,7 +884,7 @@ static int propagate(dqmc_handle *h)
                 // stack.jl:534-536 wraps greens_temp unconditionally; its result is only observable through the
                 // check, so the wrap is skipped when the check is off.  (Slab form: out of place, in front of the
                 // slice sequence.)
-                const bool wt = h->p.check_propagation_error != 0, wt_slab = wt && h->slab && !h->cb.on;
+                const bool wt = h->p.check_propagation_error != 0, wt_slab = wt && oop_wrap(h);
                 CHK(add_slice_sequence_left(h, idx, wt_slab));
                 const Udt L = slot_ref(h, idx);
                 if (wt && !wt_slab) {
@@ -1079,6 +1130,29 @@ int dqmc_create(const dqmc_params *p, dqmc_handle **out)
             CCHK(dalloc(h, &h->kron_f, f.size()));
             CHIP(hipMemcpy(h->kron_f, f.data(), f.size() * sizeof(double), hipMemcpyHostToDevice));
             h->kron = true;
+            h->kron_fa = h->kron_fb = 256;
+        }
+    }
+    if (h->n == 512 && !h->sw.no_kron) {
+        // operand images of eT2, eTinv2 and their transposes (Ez' (x) Ey' (x) Ex': same residual, no second check)
+        const size_t per = (size_t)nb * (4096 + 256);
+        std::vector<double> f(4 * per);
+        double fx[64], fy[64], fz[64];
+        bool ok = true;
+        for (int m = 0; m < 2 && ok; ++m)
+            for (int b = 0; b < nb && ok; ++b) {
+                ok = kron3_factor((m ? p->eTinv2 : p->eT2) + (size_t)b * h->nn, fx, fy, fz);
+                for (int t = 0; t < 2; ++t) {
+                    double *xy = f.data() + (size_t)(m + 2 * t) * per + (size_t)b * 4096;
+                    kron3_images(fx, fy, fz, t == 1, xy, f.data() + (size_t)(m + 2 * t) * per + (size_t)nb * 4096 + (size_t)b * 256);
+                }
+            }
+        if (ok) {
+            CCHK(dalloc(h, &h->kron_f, f.size()));
+            CHIP(hipMemcpy(h->kron_f, f.data(), f.size() * sizeof(double), hipMemcpyHostToDevice));
+            h->kron = true;
+            h->kron_fa = 4096;
+            h->kron_fb = 256;
         }
     }
     CCHK(dalloc(h, &h->conf, (size_t)h->W * h->N * h->M));

@@ -94,7 +94,7 @@ struct SlabArgs {
     double epl, eml;
 };
 hipError_t launch_slab_chain(const SlabArgs &a, hipStream_t s, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
-// The same chains with Kronecker-factored A_s = ay (x) ax (kron.hip, n = 256 = 16 x 16 sites)
+// The same chains with Kronecker-factored A_s = ay (x) ax (kron.hip, n = 256 = 16 x 16 sites; kron3.hip, n = 512)
 struct KronStep {
     const double *ax, *ay;               // 16 x 16 factors, column-major, block b at + 256 b
     const int8_t *pre_conf; int pre_sign;    // conf pointers already offset to the slice; null = no scaling
@@ -111,6 +111,9 @@ struct KronArgs {
     double epl, eml;
 };
 hipError_t launch_kron_chain(const KronArgs &a, hipStream_t s, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
+// The same chains at n = 512 = 8 x 8 x 8 sites with A_s = Ez (x) Exy (kron3.hip): ax / ay are the operand images of
+// Exy (64 x 64, block b at + 4096 b) and of I2 (x) Ez (block b at + 256 b) described there
+hipError_t launch_kron3_chain(const KronArgs &a, hipStream_t s, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
 
 // Column-pivoted Householder QR, in place (udt_AVX_pivot! "QR decomposition" loop,
 // src/linalg/UDT.jl:212-246).  On exit A holds R on/above the diagonal and the

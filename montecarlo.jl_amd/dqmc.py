@@ -673,7 +673,8 @@ class DQMC:
         return n.value
 
     def kron_hopping(self):
-        """True when slice products and wraps apply the hopping exponentials as Kronecker products of 16 x 16 factors"""
+        """True when slice products and wraps apply the hopping exponentials as Kronecker products (16 x 16 factors at
+        n = 256, 8 x 8 at n = 512; include/dqmc_hip.h)"""
         f = C.c_int32(0)
         self._c(lib().dqmc_kron_hopping(self._h, C.byref(f)))
         return bool(f.value)

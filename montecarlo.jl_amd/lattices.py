@@ -1,4 +1,4 @@
-"""Host-side lattices (src/lattices/square.jl:25-60, chain.jl:19-41, abstract.jl:99-115).
+"""Host-side lattices (src/lattices/square.jl:25-60, chain.jl:19-41, cubic.jl:19-70, abstract.jl:99-115).
 
 Integer tables are 1-based like the reference's so that they compare verbatim with
 its fixtures (test/flavortests_DQMC.jl:22-24)."""
@@ -49,6 +49,27 @@ class Chain(AbstractLattice):
         self.bonds = np.array([(s, self.neighs[0, s - 1], 0) for s in c], dtype=np.int64)
 
 
+class CubicLattice(AbstractLattice):
+    """CubicLattice(D, L) (cubic.jl:23-56): site x_1 + L x_2 + L^2 x_3 + ... (column-major reshape of 1:L^D); neighs rows
+    1..D are the "uprights" (circshift by -1 along dimension d), rows D+1..2D the "downlefts"."""
+
+    def __init__(self, D, L):
+        self.L, self.dim = L, D
+        self.sites = L ** D
+        lat = np.arange(1, self.sites + 1).reshape((L,) * D, order="F")
+        self.lattice = lat
+        ups = [np.roll(lat, -1, axis=d).reshape(-1, order="F") for d in range(D)]
+        downs = [np.roll(lat, 1, axis=d).reshape(-1, order="F") for d in range(D)]
+        self.neighs = np.vstack(ups + downs).astype(np.int64)
+        self.n_bonds = D * self.sites
+        bonds = np.zeros((self.n_bonds, 3), dtype=np.int64)
+        b = 0
+        for src in lat.reshape(-1, order="F"):
+            for trg in self.neighs[:D, src - 1]:
+                bonds[b] = (src, trg, 0); b += 1
+        self.bonds = bonds
+
+
 def build_checkerboard(l):
     """src/flavors/DQMC/abstract.jl:23-54 (used here only to pin the bond tables)."""
     bonds = l.neighbors(False)
@@ -72,16 +93,27 @@ def build_checkerboard(l):
 
 # ---------------------------------------------------------------------------
 # EachSitePairByDistance (src/lattices/lattice_iterators.jl:131-190)
+def _check_cubic(l):
+    if l.dim != 3:  # cubic.jl:69-70 define positions and lattice_vectors for D = 3 only
+        raise NotImplementedError("positions / lattice_vectors of CubicLattice are defined for D = 3 only (D = %d)" % l.dim)
+
+
 def _positions(l):
-    """positions(l) (square.jl:72, chain.jl:52): 1-based cartesian coordinates"""
+    """positions(l) (square.jl:72, chain.jl:52, cubic.jl:69): 1-based cartesian coordinates"""
     if isinstance(l, SquareLattice):
         return [np.array([i + 1.0, j + 1.0]) for j in range(l.L) for i in range(l.L)]
+    if isinstance(l, CubicLattice):
+        _check_cubic(l)
+        return [np.array([i + 1.0, j + 1.0, k + 1.0]) for k in range(l.L) for j in range(l.L) for i in range(l.L)]
     return [np.array([i + 1.0]) for i in range(l.sites)]
 
 
 def _lattice_vectors(l):
     if isinstance(l, SquareLattice):
         return [np.array([float(l.L), 0.0]), np.array([0.0, float(l.L)])]
+    if isinstance(l, CubicLattice):
+        _check_cubic(l)
+        return [np.array([float(l.L), 0.0, 0.0]), np.array([0.0, float(l.L), 0.0]), np.array([0.0, 0.0, float(l.L)])]
     return [np.array([float(l.sites)])]
 
 

@@ -5,16 +5,16 @@ performance-critical methods (interaction_matrix_exp!, propose_local,
 accept_local!) live on the device behind dqmc_sweep_spatial / dqmc_propagate."""
 import numpy as np
 
-from .lattices import Chain, SquareLattice
+from .lattices import Chain, CubicLattice, SquareLattice
 
 
 def choose_lattice(dims, L):
-    """HubbardModel.jl:23-31 (CubicLattice is outside the hot-path scope)."""
+    """HubbardModel.jl:23-31"""
     if dims == 1:
         return Chain(L)
     if dims == 2:
         return SquareLattice(L)
-    raise NotImplementedError("only Chain and SquareLattice are provided")
+    return CubicLattice(dims, L)
 
 
 class HubbardModelAttractive:
