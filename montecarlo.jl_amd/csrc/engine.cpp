@@ -72,6 +72,13 @@ struct dqmc_handle {
     hipStream_t cur = nullptr;  // the stream the launch helpers use (= stream)
     double *greens_alt = nullptr, *lu_img = nullptr;  // decide / apply sweep (sweep_lu.hip)
     bool sweep_fused = true;
+    // the last chunk of the latest sweep_spatial, eliminated but not applied to greens (fold_wrap_flush): the next factored
+    // wrap of greens applies it, materialize_pending_flush() everywhere else
+    struct PendingFlush {
+        const double *G = nullptr;  // = greens while pending
+        const double *img = nullptr;
+        int site0 = 0;
+    } pf;
     WalkerRng *rng = nullptr;
     DevStats *stats = nullptr;
     unsigned long long *pc_scratch = nullptr;  // prop_check_kernel: partial maximum + arrival counter per walker
@@ -398,6 +405,7 @@ static void read_kernel_switches(dqmc_handle *h)
     k.flush_ncp2 = getenv("DQMC_FLUSH_NCP2") != nullptr;
     k.no_slab = getenv("DQMC_NO_SLAB") != nullptr;
     k.no_kron = getenv("DQMC_NO_KRON") != nullptr;
+    k.no_wrap_flush = getenv("DQMC_NO_WRAP_FLUSH") != nullptr;
 }
 
 static int alloc_qr_workspace(dqmc_handle *h)
@@ -635,6 +643,32 @@ enum { KF_ET2 = 0, KF_ETINV2 = 1, KF_ET2T = 2, KF_ETINV2T = 3 };
 static bool use_kron(const dqmc_handle *h) { return h->kron && !h->cb.on; }
 // wraps out of place (wrap_greens_slab): the n = 256 slab path and every factored path
 static bool oop_wrap(const dqmc_handle *h) { return (h->slab || h->kron) && !h->cb.on; }
+// the last chunk of sweep_spatial goes into the first launch of the next wrap (kron.hip) instead of a flush of its own.
+// Only with the fused chunk loop (few units: one round of workgroups): every one of the 16 workgroups of a unit reads all of
+// C (128 KB) and the image, so the folded launch grows with the units, and at 512 units (config 4) the multi-pass flush it
+// replaces is cheaper
+static bool fold_wrap_flush(const dqmc_handle *h)
+{
+    return use_kron(h) && h->n == 256 && h->sweep_fused && !h->sw.no_wrap_flush;
+}
+// greens as the reference has it: a pending last chunk is applied by the stand-alone flush (out of place through
+// greens_alt, which is free between two sweep_spatial calls)
+static int materialize_pending_flush(dqmc_handle *h)
+{
+    if (!h->pf.G) return 0;
+    const dqmc_handle::PendingFlush p = h->pf;
+    h->pf = dqmc_handle::PendingFlush{};
+    if (p.G != h->greens) return fail(h, DQMC_ERR_STATE, "pending sweep update does not belong to greens");
+    hipEvent_t a, b;
+    timing_events(h, &a, &b);
+    HIPCHK(launch_sweep_flush_lu(h->n, h->units, h->greens, h->greens_alt, h->nn, p.site0, 64, p.img, h->sw, h->cur, a, b));
+    CHK(timing_push(h, a, b, DQMC_K_FLUSH));
+    std::swap(h->greens, h->greens_alt);
+    return 0;
+}
+// greens is about to be recomputed from the UDT stack: a pending chunk need not be applied to it (its HS-field flips are
+// in conf already, and the stack is built from conf alone)
+static void discard_pending_flush(dqmc_handle *h) { h->pf = dqmc_handle::PendingFlush{}; }
 static KronArgs kron_base(dqmc_handle *h, const double *X0, double *out)
 {
     KronArgs a{};
@@ -760,6 +794,11 @@ static int wrap_greens_kron(dqmc_handle *h, const double *src, double *dst, int 
     const int8_t *c = conf_slice(h, direction == -1 ? curr_slice - 1 : curr_slice);
     KronArgs a = kron_base(h, src, h->bufB);
     a.transpose_out = 1;
+    if (h->pf.G) {  // the sweep's last chunk is applied to the columns of src as the first launch loads them
+        if (h->pf.G != src || h->n != 256) return fail(h, DQMC_ERR_STATE, "wrap of another matrix with a sweep update pending");
+        a.pf_img = h->pf.img; a.pf_img_su = (long)sweep_lu_image_doubles(); a.pf_site0 = h->pf.site0;
+        h->pf = dqmc_handle::PendingFlush{};
+    }
     KronStep &s1 = kron_step(h, a, direction == -1 ? KF_ETINV2 : KF_ET2);
     if (direction == -1) { s1.post_conf = c; s1.post_sign = -1; }
     else { s1.pre_conf = c; s1.pre_sign = +1; }
@@ -868,6 +907,9 @@ static int build_stack(dqmc_handle *h)
 }
 
 // stack.jl:502-631
+// A sweep update pending on greens (fold_wrap_flush) is taken by the wraps of greens: the plain steps and, at the up
+// pass's interval boundaries with the propagation check on, the wrap into greens_temp.  Where greens is recomputed from
+// the stack it is dropped (discard_pending_flush), where the old greens is compared it is applied first.
 static int propagate(dqmc_handle *h)
 {
     const int M = h->M, s = h->s;
@@ -877,6 +919,7 @@ static int propagate(dqmc_handle *h)
             if (h->current_slice == 1) {
                 const Udt R = slot_ref(h, 0);   // copyto!(s.Ur, s.u_stack[1]) ... (stack.jl:512-520) without the copies
                 CHK(reset_slot(h, 0));
+                discard_pending_flush(h);
                 CHK(calculate_greens_src(h, h->greens, slot_ref(h, 0), R));
             } else if (1 < h->current_slice && h->current_slice <= M) {
                 const int idx = (h->current_slice - 1) / s;
@@ -885,9 +928,10 @@ static int propagate(dqmc_handle *h)
                 // check, so the wrap is skipped when the check is off.  (Slab form: out of place, in front of the
                 // slice sequence.)
                 const bool wt = h->p.check_propagation_error != 0, wt_slab = wt && oop_wrap(h);
-                CHK(add_slice_sequence_left(h, idx, wt_slab));
+                CHK(add_slice_sequence_left(h, idx, wt_slab));  // (wt_slab: its wrap takes a pending update)
                 const Udt L = slot_ref(h, idx);
                 if (wt && !wt_slab) {
+                    CHK(materialize_pending_flush(h));
                     CHK(copy_mat(h, h->greens_temp, h->greens));
                     CHK(wrap_greens(h, &h->greens_temp, h->current_slice - 1, 1));
                 }
@@ -899,6 +943,7 @@ static int propagate(dqmc_handle *h)
                     CHK(prop_check(h));
                     return 0;
                 }
+                discard_pending_flush(h);
                 CHK(calculate_greens_src(h, h->greens, L, R));
                 if (h->p.check_propagation_error) CHK(prop_check(h));
             } else {
@@ -917,6 +962,7 @@ static int propagate(dqmc_handle *h)
             if (h->current_slice == M) {
                 const Udt L = slot_ref(h, h->K);
                 CHK(reset_slot(h, h->K));
+                discard_pending_flush(h);
                 CHK(calculate_greens_src(h, h->greens, L, slot_ref(h, h->K)));
                 CHK(wrap_greens(h, &h->greens, h->current_slice + 1, -1));
             } else if (0 < h->current_slice && h->current_slice < M) {
@@ -925,7 +971,11 @@ static int propagate(dqmc_handle *h)
                 CHK(add_slice_sequence_right(h, idx));
                 const Udt R = slot_ref(h, idx - 1);
                 // greens_temp = old Green's function (stack.jl:596-600): exchange the buffers instead of copying
-                if (h->p.check_propagation_error) std::swap(h->greens_temp, h->greens);
+                if (h->p.check_propagation_error) {
+                    CHK(materialize_pending_flush(h));
+                    std::swap(h->greens_temp, h->greens);
+                }
+                discard_pending_flush(h);
                 CHK(calculate_greens_src(h, h->greens, L, R));
                 if (h->p.check_propagation_error) CHK(prop_check(h));
                 CHK(wrap_greens(h, &h->greens, h->current_slice + 1, -1));
@@ -958,8 +1008,10 @@ static int sweep_spatial_launches(dqmc_handle *h)
     int8_t *cslice = h->conf + (long)(l - 1) * h->N;
     h->conf_version++;
     // decide on the 64 x 64 block (four waves per walker), apply the chunk out of place with MFMA
+    CHK(materialize_pending_flush(h));  // (normally consumed by the wrap in between)
     double *cur = h->greens, *alt = h->greens_alt;
     const size_t istr = (size_t)h->units * sweep_lu_image_doubles();
+
     const long cstr = (long)h->N * h->M;
     hipEvent_t a, b;
     if (h->sweep_fused && h->n % 64 == 0 && h->N >= 128) {
@@ -977,11 +1029,16 @@ static int sweep_spatial_launches(dqmc_handle *h)
             CHK(timing_push(h, a, b, DQMC_K_SWEEP));
             std::swap(cur, alt);
         }
-        timing_events(h, &a, &b);
-        HIPCHK(launch_sweep_flush_lu(h->n, h->units, cur, alt, h->nn, 64 * (nc - 1), 64,
-                                     h->lu_img + (size_t)((nc - 1) & 1) * istr, h->sw, h->cur, a, b));
-        CHK(timing_push(h, a, b, DQMC_K_FLUSH));
-        std::swap(cur, alt);
+        // the last chunk: left pending for the next wrap (its image slot is not written before the next sweep), or applied
+        const double *img_last = h->lu_img + (size_t)((nc - 1) & 1) * istr;
+        if (fold_wrap_flush(h)) {
+            h->pf = dqmc_handle::PendingFlush{cur, img_last, 64 * (nc - 1)};
+        } else {
+            timing_events(h, &a, &b);
+            HIPCHK(launch_sweep_flush_lu(h->n, h->units, cur, alt, h->nn, 64 * (nc - 1), 64, img_last, h->sw, h->cur, a, b));
+            CHK(timing_push(h, a, b, DQMC_K_FLUSH));
+            std::swap(cur, alt);
+        }
         if (cur != h->greens) std::swap(h->greens, h->greens_alt);
         return 0;
     }
@@ -1328,6 +1385,7 @@ int dqmc_sweep_spatial(dqmc_handle *h)
 {
     ENTER(h); NEED_PREPARED(h);
     CHK(sweep_spatial(h));
+    CHK(materialize_pending_flush(h));  // (the API boundary: greens as the reference has it)
     return dqmc_synchronize(h);
 }
 int dqmc_update(dqmc_handle *h)
@@ -1335,6 +1393,7 @@ int dqmc_update(dqmc_handle *h)
     ENTER(h); NEED_PREPARED(h);
     CHK(propagate(h));
     CHK(sweep_spatial(h));
+    CHK(materialize_pending_flush(h));  // (the API boundary: greens as the reference has it)
     return dqmc_synchronize(h);
 }
 int dqmc_sweep(dqmc_handle *h, int32_t n_sweeps)
@@ -1345,6 +1404,7 @@ int dqmc_sweep(dqmc_handle *h, int32_t n_sweeps)
             CHK(propagate(h));
             CHK(sweep_spatial(h));
         }
+    CHK(materialize_pending_flush(h));  // (the API boundary: greens as the reference has it)
     return dqmc_synchronize(h);
 }
 int dqmc_update_until_measure(dqmc_handle *h, int32_t *n_updates)
@@ -1357,6 +1417,7 @@ int dqmc_update_until_measure(dqmc_handle *h, int32_t *n_updates)
         ++cnt;
     } while (!(h->current_slice == 1 && h->direction == 1));
     if (n_updates) *n_updates = cnt;
+    CHK(materialize_pending_flush(h));  // (the API boundary: greens as the reference has it)
     return dqmc_synchronize(h);
 }
 

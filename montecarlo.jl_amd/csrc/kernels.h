@@ -109,6 +109,11 @@ struct KronArgs {
     int transpose_out;                   // store the result transposed
     long conf_stride;                    // per walker
     double epl, eml;
+    // pending rank-64 update of X_0 (n = 256 only): the last chunk of a sweep, eliminated but not yet applied to G.  When
+    // pf_img is set, X_0 is first replaced by X_0 + (X_0[:, c] - E) X Y X_0[c, :] (c = pf_site0 .. + 63, the chunk's image
+    // at pf_img + unit * pf_img_su): what sweep_flush_lu_kernel would have written (kron.hip).  Null: no update.
+    const double *pf_img; long pf_img_su;
+    int pf_site0;
 };
 hipError_t launch_kron_chain(const KronArgs &a, hipStream_t s, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
 // The same chains at n = 512 = 8 x 8 x 8 sites with A_s = Ez (x) Exy (kron3.hip): ax / ay are the operand images of
@@ -138,6 +143,7 @@ struct KernelSwitches {
     bool flush_ncp2 = false;      // DQMC_FLUSH_NCP2: the separate flush always in its multi-pass form
     bool no_slab = false;         // DQMC_NO_SLAB: no slab-resident product chains (slab.hip)
     bool no_kron = false;         // DQMC_NO_KRON: dense slab chains even where the hopping factorises (kron.hip)
+    bool no_wrap_flush = false;   // DQMC_NO_WRAP_FLUSH: the last chunk of a sweep as a stand-alone flush, not in the wrap
 };
 
 constexpr int QR_COOP_SLOT = 528;  // 264 packets of 16 bytes
@@ -253,6 +259,19 @@ __device__ __forceinline__ void magstats_push(DevMagStats &s, double value)
 // triangular factors (sweep_lu_image_doubles() doubles per unit); sweep_flush_lu_kernel applies the chunk to G out of
 // place (Gout = Gin + T R0).  No limit on n_blocks * n_sites.
 size_t sweep_lu_image_doubles();
+// Layout of that image (doubles per unit): [U pair tiles 6][L pair tiles 6][PT 4][Q 4], each a 16 x 16 tile as 4 accumulator
+// registers x 64 lanes of v_mfma_f64_16x16x4_f64 (register r of lane (g, ci) = element [4 r + g][ci]), then x[64].  U pair
+// (K, J), K < J: block Uu_KJ of the eliminated strict upper triangle; L pair (K, J): block L_JK of the strict lower one;
+// PT_J: (I - X_J Uu_JJ)^-1; Q_J: (I - L_JJ X_J)^-1 (X = diag(x); tools/proto/lu_sweep_proto.py: PT_J is the transpose of its
+// PT[J], Q_J its Q[J]).  Taken as the A operand, register q of a tile is the B-side transpose (A[ci][4 q + g] = [4 q + g][ci]).
+constexpr int LU_TILE = 256;
+constexpr int LU_OFF_U = 0, LU_OFF_L = 6 * LU_TILE, LU_OFF_PT = 12 * LU_TILE, LU_OFF_Q = 16 * LU_TILE;
+constexpr int LU_IMG = 20 * LU_TILE;
+constexpr int LU_STRIDE = LU_IMG + 64;
+__host__ __device__ constexpr int lu_pair(int K, int J)  // K < J: (0,1) (0,2) (0,3) (1,2) (1,3) (2,3)
+{
+    return K == 0 ? J - 1 : (K == 1 ? J + 1 : 5);
+}
 hipError_t launch_sweep_lu(int n, int nb, int n_walkers, const double *G, long strideG, int8_t *conf_slice,
                            long conf_stride, int site0, int nsites, double *img, SweepConsts sc, WalkerRng *rng,
                            DevStats *stats, int check_sign, int *errflag, hipStream_t s,

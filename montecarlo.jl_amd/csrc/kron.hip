@@ -18,6 +18,14 @@
 // transpose, and the parity alternates: (y, x) at the start, where a load of one register is 64 consecutive doubles.
 // Columns are independent: a workgroup (4 waves x KR_NC columns) owns 16 consecutive columns through all steps, and
 // nothing crosses workgroups.  The result is staged in LDS and stored as whole 128-byte lines, as is or transposed.
+//
+// Pending chunk (KronArgs::pf_img, the first launch of a wrap behind a sweep).  The sweep leaves its last chunk c of 64
+// sites eliminated but not applied: G' = G + T R0 with T = C X Y, C = G[:, c] - E, Y = (I - Uu X)^-1 (I - L X)^-1,
+// R0 = G[c, :] (sweep_lu.hip).  A workgroup owns whole columns j, so it forms G'[:, j] = G[:, j] + C R^[:, j] with
+// R^ = X Y R0 re-associated onto the rows (the stand-alone flush solves on the columns of C instead):
+//   XV_J = X_J Q_J (R0_J + sum_{K<J} L_JK XV_K),   R^_J = PT_J (XV_J + X_J sum_{K>J} Uu_JK R^_K)
+// (blocks of 16 sites, image tiles as in kernels.h, each taken as the A operand of its own matrix), then 256 x 64 x 16 of
+// MFMA with C read from G.  R0 is register (site0 / 64) of the X_0 tiles already loaded.
 #include "kernels.h"
 #include <hip/hip_ext.h>
 
@@ -34,6 +42,18 @@ constexpr int KR_SLD = 18;               // row stride of the transposed staging
 constexpr int KR_LDS_T = 4 * KR_NC * 16 * KR_TLD;  // transpose tiles of the four waves
 constexpr int KR_LDS_S = KR_N * KR_SLD;            // staging image of the result (>= KR_COLS * KR_N)
 constexpr int KR_LDS = KR_LDS_T > KR_LDS_S ? KR_LDS_T : KR_LDS_S;
+// pending chunk (kr_apply_pending): the 20 image tiles as row-major 16 x 17 matrices, x, R0 [column][site] (stride 65);
+// behind the transpose tiles, the update [column][entry] (stride 257), written once the image is no longer read
+constexpr int KR_PF_TS = 16 * 17;
+constexpr int KR_PF_IMG = 0, KR_PF_X = 20 * KR_PF_TS, KR_PF_R0 = KR_PF_X + 64, KR_PF_RLD = 65;
+constexpr int KR_PF_D = KR_LDS_T, KR_PF_DLD = 257;
+constexpr int KR_LDS_PF = KR_PF_D + KR_COLS * KR_PF_DLD;  // 67 712 bytes: two workgroups per CU
+static_assert(KR_PF_R0 + KR_COLS * KR_PF_RLD <= KR_LDS_PF && KR_LDS <= KR_LDS_PF, "pending-chunk LDS layout");
+
+#define KR_GLOBAL __attribute__((address_space(1)))
+typedef const KR_GLOBAL double *kr_gcdp;
+typedef double kr_d2 __attribute__((ext_vector_type(2)));
+typedef const KR_GLOBAL kr_d2 *kr_gcd2p;
 
 // exp(sign lambda conf[i]) of block blk (vs_conf() of engine.cpp, slab_conf_val() of slab.hip)
 __device__ __forceinline__ double kr_conf(int8_t c, int sign, bool bn, double epl, double eml)
@@ -41,11 +61,159 @@ __device__ __forceinline__ double kr_conf(int8_t c, int sign, bool bn, double ep
     return (((c > 0) == (sign > 0)) != bn) ? epl : eml;
 }
 
+#ifdef KR_STAMPS  // diagnostic build only (tools/kr_stamps.py): per workgroup of the pending-chunk launch, cycle stamps of wave 0
+__device__ long long *kr_stamp_ptr = nullptr;
+#define KR_STAMP(k)                                                                                   \
+    do {                                                                                              \
+        if (PF && threadIdx.x == 0 && kr_stamp_ptr)                                                   \
+            kr_stamp_ptr[16 * blockIdx.x + (k)] = (long long)__builtin_amdgcn_s_memtime();            \
+    } while (0)
+#define KR_STAMP_RT(k)                                                                                \
+    do {                                                                                              \
+        if (PF && threadIdx.x == 0 && kr_stamp_ptr)                                                   \
+            kr_stamp_ptr[16 * blockIdx.x + (k)] = (long long)__builtin_amdgcn_s_memrealtime();        \
+    } while (0)
+extern "C" int dqmc_debug_kr_stamps(void *devptr)
+{
+    return (int)hipMemcpyToSymbol(HIP_SYMBOL(kr_stamp_ptr), &devptr, sizeof(void *));
+}
+#else
+#define KR_STAMP(k) do { } while (0)
+#define KR_STAMP_RT(k) do { } while (0)
+#endif
+// X_0 (the column tiles v of this workgroup's 16 columns) += C R^ for the pending chunk (file header)
+template <bool PF>
+__device__ __forceinline__ void kr_apply_pending(const KronArgs &a, int unit, int c0, d4k (&v)[KR_NC], double *lds)
+{
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 4, ci = lane & 15;
+    const int site0 = a.pf_site0;
+    const kr_gcdp img = (kr_gcdp)(a.pf_img + (long)unit * a.pf_img_su);
+    const kr_gcdp G = (kr_gcdp)(a.X0 + (long)unit * a.x_su);
+    double *limg = lds + KR_PF_IMG, *lx = lds + KR_PF_X, *lr = lds + KR_PF_R0, *ld = lds + KR_PF_D;
+    // requests first: image (2 doubles per request) and x
+    constexpr int NI = LU_IMG / 2 / 256;
+    static_assert(NI * 512 == LU_IMG, "image staging");
+    kr_d2 iv[NI];
+#pragma unroll
+    for (int i = 0; i < NI; ++i) iv[i] = reinterpret_cast<kr_gcd2p>(img)[tid + 256 * i];
+    const double xin = img[LU_IMG + (tid & 63)];
+    // image -> LDS, every tile as its matrix N row-major: N[ci][4 q + g] is then the A operand of N itself
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+        const int p = 2 * (tid + 256 * i), tl = p >> 8, r = (p >> 6) & 3, ln = p & 63;
+        double *d = limg + tl * KR_PF_TS + (4 * r + (ln >> 4)) * 17 + (ln & 15);
+        d[0] = iv[i].x;
+        d[1] = iv[i].y;
+    }
+    if (tid < 64) lx[tid] = xin;
+    // R0[s][j] = G[site0 + s][j]: register site0 / 64 of the (y, x) tiles, s = ci + 16 g
+    {
+        const int rr = site0 >> 6;
+#pragma unroll
+        for (int t = 0; t < KR_NC; ++t) {
+            const double r0 = rr == 0 ? v[t][0] : (rr == 1 ? v[t][1] : (rr == 2 ? v[t][2] : v[t][3]));
+            lr[(KR_NC * w + t) * KR_PF_RLD + ci + 16 * g] = r0;
+        }
+    }
+    __syncthreads();
+    KR_STAMP(2);
+    auto A = [&](int tl, int q) { return limg[tl * KR_PF_TS + ci * 17 + 4 * q + g]; };
+    auto xr = [&](int J, int r) { return lx[16 * J + 4 * r + g]; };
+    constexpr int TU = LU_OFF_U / LU_TILE, TL = LU_OFF_L / LU_TILE, TP = LU_OFF_PT / LU_TILE, TQ = LU_OFF_Q / LU_TILE;
+    // D = C R^ (below) on this wave's rows 64 w .. 64 w + 63.  Its A operands, C[16 (4 w + mm) + ci][16 J + 4 q + g], come
+    // one block J ahead of its 16 MFMAs, the first during the solves (the four row tiles of a request share one address;
+    // all 64 in flight were 128 more VGPRs: one workgroup per CU)
+    const kr_gcdp gc = G + 64 * w + ci + (long)KR_N * (site0 + g);
+    double ca[2][4][4];  // [J & 1][mm][q]
+    auto fetch = [&](int J, double (&c)[4][4]) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+            for (int mm = 0; mm < 4; ++mm) c[mm][q] = gc[16 * mm + (long)KR_N * (16 * J + 4 * q)];
+    };
+    fetch(0, ca[0]);
+    // (the four waves solve the same 64 x 16 block: each needs all of R^ as B operands)
+    d4k xv[4], rh[4];
+#pragma unroll
+    for (int J = 0; J < 4; ++J) {
+        d4k acc;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[r] = lr[ci * KR_PF_RLD + 16 * J + 4 * r + g];
+#pragma unroll
+        for (int K = 0; K < J; ++K)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) acc = KR_MFMA(A(TL + lu_pair(K, J), q), xv[K][q], acc);
+        d4k z = (d4k){0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int q = 0; q < 4; ++q) z = KR_MFMA(A(TQ + J, q), acc[q], z);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) xv[J][r] = z[r] * xr(J, r);
+    }
+#pragma unroll
+    for (int J = 3; J >= 0; --J) {
+        d4k acc = (d4k){0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int K = J + 1; K < 4; ++K)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) acc = KR_MFMA(A(TU + lu_pair(J, K), q), rh[K][q], acc);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[r] = xv[J][r] + xr(J, r) * acc[r];
+        d4k o = (d4k){0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int q = 0; q < 4; ++q) o = KR_MFMA(A(TP + J, q), acc[q], o);
+        rh[J] = o;
+    }
+    KR_STAMP(3);
+    // tile mm of D holds D[16 (4 w + mm) + 4 r + g][j = ci]
+    d4k dm[4];
+#pragma unroll
+    for (int mm = 0; mm < 4; ++mm) dm[mm] = (d4k){0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int J = 0; J < 4; ++J) {
+        if (J < 3) fetch(J + 1, ca[(J + 1) & 1]);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+            for (int mm = 0; mm < 4; ++mm) {
+                const int i = 16 * (4 * w + mm) + ci, s = 16 * J + 4 * q + g;
+                const double c = ca[J & 1][mm][q] - (i == site0 + s ? 1.0 : 0.0);
+                dm[mm] = KR_MFMA(c, rh[J][q], dm[mm]);
+            }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    KR_STAMP(4);
+    __syncthreads();  // every wave is done with the image (the update goes over it)
+#pragma unroll
+    for (int mm = 0; mm < 4; ++mm)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) ld[ci * KR_PF_DLD + 16 * (4 * w + mm) + 4 * r + g] = dm[mm][r];
+    __syncthreads();
+#pragma unroll
+    for (int t = 0; t < KR_NC; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[t][r] += ld[(KR_NC * w + t) * KR_PF_DLD + ci + 16 * (g + 4 * r)];
+    // (the update region lies behind the transpose tiles: the first step's tile stores need no barrier; the staging image
+    // at the end that overlaps it is behind the steps' barriers)
+}
+
+template <bool PF>
 __global__ __launch_bounds__(256) void kron_chain_kernel(KronArgs a)
 {
-    __shared__ __attribute__((aligned(16))) double lds[KR_LDS];
-    const int unit = blockIdx.x / (KR_N / KR_COLS), c0 = KR_COLS * (blockIdx.x % (KR_N / KR_COLS));
+    __shared__ __attribute__((aligned(16))) double lds[PF ? KR_LDS_PF : KR_LDS];
+    // PF: the 16 workgroups of a unit share an XCD (blockIdx.x % 8, as the flush kernels place units): each of them reads
+    // all of C and the image, which then come into one L2 once instead of into eight
+#ifndef KR_NO_XCD_GROUPS
+    constexpr bool XG = PF;
+#else
+    constexpr bool XG = false;
+#endif
+    const unsigned bq = XG ? blockIdx.x >> 3 : blockIdx.x;
+    const int unit = XG ? (bq / (KR_N / KR_COLS)) * 8 + (blockIdx.x & 7) : bq / (KR_N / KR_COLS);
+    const int c0 = KR_COLS * (bq % (KR_N / KR_COLS));
     if (unit >= a.n_units) return;
+    KR_STAMP(0);
+    KR_STAMP_RT(1);
     const int wk = a.nb == 2 ? unit >> 1 : unit, blk = a.nb == 2 ? unit & 1 : 0;
     const bool bn = blk != 0;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 4, ci = lane & 15;
@@ -97,6 +265,8 @@ __global__ __launch_bounds__(256) void kron_chain_kernel(KronArgs a)
 #pragma unroll
         for (int t = 0; t < KR_NC; ++t) cs[t] = cd[t];
     }
+    if constexpr (PF) kr_apply_pending<PF>(a, unit, c0, v, lds);
+    KR_STAMP(5);
 
     for (int s = 0; s < a.nsteps; ++s) {
         const KronStep &st = a.st[s];
@@ -138,6 +308,7 @@ __global__ __launch_bounds__(256) void kron_chain_kernel(KronArgs a)
         }
         cur = nxt;
     }
+    KR_STAMP(6);
     // ---- staging image: transposed [entry][column] (row stride KR_SLD), else [column][entry] (the global image)
     const int par = a.nsteps & 1;
 #pragma unroll
@@ -164,14 +335,24 @@ __global__ __launch_bounds__(256) void kron_chain_kernel(KronArgs a)
             *reinterpret_cast<double2 *>(o + (long)KR_N * c0 + e) = *reinterpret_cast<const double2 *>(lds + e);
         }
     }
+    KR_STAMP(7);
+    KR_STAMP_RT(8);
 }
 
 hipError_t launch_kron_chain(const KronArgs &a, hipStream_t s, hipEvent_t start, hipEvent_t stop)
 {
     if (a.nsteps < 1 || a.nsteps > SLAB_MAX_STEPS || a.nb < 1 || a.nb > 2) return hipErrorInvalidValue;
+    if (a.pf_img && (a.pf_site0 < 0 || a.pf_site0 % 64 != 0 || a.pf_site0 + 64 > KR_N || a.pf_img_su < LU_STRIDE))
+        return hipErrorInvalidValue;
     const dim3 grid(a.n_units * (KR_N / KR_COLS)), block(256);
-    if (start) hipExtLaunchKernelGGL(kron_chain_kernel, grid, block, 0, s, start, stop, 0, a);
-    else hipLaunchKernelGGL(kron_chain_kernel, grid, block, 0, s, a);
+    if (a.pf_img) {
+        const dim3 gridx((a.n_units + 7) / 8 * 8 * (KR_N / KR_COLS));  // whole groups of eight units (XCD placement)
+        if (start) hipExtLaunchKernelGGL(kron_chain_kernel<true>, gridx, block, 0, s, start, stop, 0, a);
+        else hipLaunchKernelGGL(kron_chain_kernel<true>, gridx, block, 0, s, a);
+    } else {
+        if (start) hipExtLaunchKernelGGL(kron_chain_kernel<false>, grid, block, 0, s, start, stop, 0, a);
+        else hipLaunchKernelGGL(kron_chain_kernel<false>, grid, block, 0, s, a);
+    }
     return hipGetLastError();
 }
 

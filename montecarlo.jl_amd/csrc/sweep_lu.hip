@@ -30,16 +30,8 @@ namespace dqmc {
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 
-// per-unit image written by sweep_lu_kernel, read by sweep_flush_lu_kernel (doubles):
-//   [U pair tiles 6][L pair tiles 6][PT 4][Q 4] each 4 regs x 64 lanes, then x[64]
-constexpr int LU_TILE = 256;
-constexpr int LU_OFF_U = 0, LU_OFF_L = 6 * LU_TILE, LU_OFF_PT = 12 * LU_TILE, LU_OFF_Q = 16 * LU_TILE;
-constexpr int LU_IMG = 20 * LU_TILE;
-constexpr int LU_STRIDE = LU_IMG + 64;
-__host__ __device__ constexpr int lu_pair(int K, int J)  // K < J: (0,1) (0,2) (0,3) (1,2) (1,3) (2,3)
-{
-    return K == 0 ? J - 1 : (K == 1 ? J + 1 : 5);
-}
+// per-unit image written by sweep_lu_kernel, read by sweep_flush_lu_kernel and by the first launch of a factored wrap
+// (kron.hip): layout in kernels.h (LU_TILE .. lu_pair)
 size_t sweep_lu_image_doubles() { return LU_STRIDE; }
 
 __device__ __forceinline__ double readlane_d(double v, int lane)
