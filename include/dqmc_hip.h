@@ -71,7 +71,8 @@ typedef struct {
      *    Ex = E[0:8, 0:8], Ey = E[0::8, 0::8][0:8, 0:8] / E[0,0], Ez = E[0::64, 0::64] / E[0,0].
      * When every block passes, slice products and wraps apply the factors instead of the dense matrix
      * (dqmc_kron_hopping reports it); the difference is rounding of the exponential, far inside the 1e-10 tolerance on G.
-     * Any other size or hopping keeps the dense products. */
+     * Any other size or hopping keeps the dense products.  The triangular 16 x 16 lattice, which is no Kronecker product,
+     * takes its factors through dqmc_set_triangular_factors. */
 } dqmc_params;
 
 /* MagnitudeStats (DQMC.jl:4-31): log10 magnitudes */
@@ -317,9 +318,23 @@ int dqmc_set_checkerboard(dqmc_handle *h, int32_t kmax, int32_t n_mats, const do
  * the guarded single-workgroup kernel launched behind it redoes the factorisation, so results stay valid.  This counter reports
  * how often that happened.  (The one-launch UDT has no second path: its time-outs fail the call, see dqmc_device_errors.) */
 int dqmc_qr_fallbacks(dqmc_handle *h, int64_t *count);
-/* 1 when slice products and wraps apply eT2 / eTinv2 as Kronecker products (16 x 16 factors at n = 256, 8 x 8 factors at
- * n = 512; see dqmc_params), else 0 */
+/* 1 when slice products and wraps apply eT2 / eTinv2 in factored form (Kronecker products of 16 x 16 factors at n = 256,
+ * 8 x 8 factors at n = 512, see dqmc_params; the triangular 16 x 16 lattice's three factors, see
+ * dqmc_set_triangular_factors), else 0 */
 int dqmc_kron_hopping(dqmc_handle *h, int32_t *on);
+/* The periodic 16 x 16 TriangularLattice (n_sites = 256, site x + 16 y; hopping along X = x + 1, Y = y + 1 and D = XY,
+ * triangular.jl:60-78) in three-factor form.  X, Y and D commute, so exp(-a T) = e^{a mu} f(X) f(Y) f(XY) with
+ * f = exp(a t (S + S')) on a 16-ring, and each of eT2 and eTinv2 is E = (Fy (x) Fx) Ed, where Ed applies Fd along each
+ * diagonal x - y = u: (Ed v)(x, y) = sum_y' Fd[y, y'] v(x - y + y', y').  f holds, per block, [eT2: Fx Fy Fd][eTinv2: Fx
+ * Fy Fd], each a 16 x 16 column-major matrix (1536 doubles per block).
+ * The handle checks them against its own eT2 / eTinv2: E[0,0] > 0 and max|E - P| <= 256 DBL_EPSILON max|E| for
+ * P = (Fy (x) Fx) Ed and for the two orders the kernel applies, Fx Ed Fy and Fy Ed Fx.  When every block passes, slice
+ * products and wraps apply the three factors (tri.hip; dqmc_kron_hopping reports 1) and the sweep's last chunk is applied
+ * by the stand-alone flush.  Returns DQMC_ERR_INVALID for factors that fail the check or n_sites != 256, DQMC_ERR_STATE
+ * after dqmc_prepare / dqmc_build_stack / dqmc_replay_greens; in both cases the handle keeps its path and stays usable.
+ * A handle on a path that does not take them (DQMC_NO_KRON or DQMC_NO_SLAB set, a checkerboard, or a square lattice's
+ * Kronecker factors already taken) returns DQMC_OK and keeps its path. */
+int dqmc_set_triangular_factors(dqmc_handle *h, const double *f);
 /* which call sites of udt_AVX_pivot! (UDT.jl:192-306) this handle serves with the one-launch pre-pivoted factorisation:
  * bit 0 add_slice_sequence_left/right (stack.jl:272-311) and other callers, bit 1 / bit 2 the two factorisations of
  * calculate_greens_AVX! (stack.jl:349, :376); 0 = the reference's pivot rule everywhere (n != 256, > 32 units, DQMC_QR_NOBLOCKED) */

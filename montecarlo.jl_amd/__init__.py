@@ -9,12 +9,14 @@ from .configurations import (CompressedConf, ConfigRecorder, Discarder, compress
                              decompress)
 from . import lattices  # noqa: F401
 from .lattices import (Chain, EachLocalQuadByDistance, EachLocalQuadBySyncedDistance, EachSitePairByDistance,  # noqa: F401
-                       CubicLattice, SquareLattice, build_checkerboard)
+                       CubicLattice, SquareLattice, TriangularLattice, build_checkerboard)
 from .models import (HubbardModel, HubbardModelAttractive, HubbardModelRepulsive,  # noqa: F401
                      rand_conf)
 from .sharding import (Communicator, reduce_accumulators, walker_block, walker_range,  # noqa: F401
                        walker_seeds)
 from .dqmc import (DQMC, DQMCParameters, calculate_greens_AVX, device_count,  # noqa: F401
-                   checkerboard_exponentials, checkerboard_tables, hopping_exponentials, mfma_f64_peak, rdivp, udt_AVX_pivot, vmul)
+                   checkerboard_exponentials, checkerboard_seqs, checkerboard_tables,
+                   hopping_exponentials, mfma_f64_peak, rdivp, triangular_factors,
+                   udt_AVX_pivot, vmul)
 
 lib()  # fail loudly at import time if the HIP library has not been built

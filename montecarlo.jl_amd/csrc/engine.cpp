@@ -46,8 +46,10 @@ struct dqmc_handle {
     // and wraps take kron.hip instead of slab.hip.  kron_f: [eT2, eTinv2, eT2', eTinv2'] x [x, y] x nb x 16 x 16.
     // n == 512 ones that are Ez (x) Ey (x) Ex of 8 x 8 factors (kron3_factor): kron3.hip instead of the dense GEMMs.
     // kron_f: [eT2, eTinv2, eT2', eTinv2'] x ([Exy image] x nb x 4096, [Ez image] x nb x 256).
+    // n == 256 triangular 16 x 16 lattice (dqmc_set_triangular_factors): (Fy (x) Fx) Ed, tri.hip instead of slab.hip.
+    // kron_f: [eT2, eTinv2, eT2', eTinv2'] x [x, y, d] x nb x 16 x 16 (ax = Fx, ay = Fy, Fd behind Fy).
     // kron_fa / kron_fb: doubles per block of the two operand sets (ax / ay of a KronStep)
-    bool kron = false;
+    bool kron = false, tri = false;
     double *kron_f = nullptr;
     int kron_fa = 0, kron_fb = 0;
     int8_t *conf = nullptr;  // W x (N x M)
@@ -387,6 +389,36 @@ static void kron3_images(const double *fx, const double *fy, const double *fz, b
         }
 }
 
+// eT2 / eTinv2 of the 16 x 16 periodic triangular lattice (n = 256, site x + 16 y; hopping along X = (1, 0), Y = (0, 1) and
+// D = XY) as (Fy (x) Fx) Ed, where Ed applies Fd along the diagonals x - y = const:
+//   (Ed v)(x, y) = sum_y' Fd[y, y'] v(x - y + y', y')
+// The factors come from the host (dqmc_set_triangular_factors).  X, Y and D commute, so every order of the three products is
+// E up to rounding; the gate bounds the claimed form and the two orders the kernel applies (tri.hip: Fx Ed Fy from a step
+// that starts with y in the registers, Fy Ed Fx from one that starts with x), each by 256 eps max|E|.  Their transposes
+// (the daggered products and the wraps' right products) have the same residuals.
+static bool tri_factor_ok(const double *E, const double *fx, const double *fy, const double *fd)
+{
+    const int n = 256;
+    if (!(E[0] > 0.0)) return false;
+    auto F = [](const double *f, int r, int c) { return f[(r & 15) + 16 * (c & 15)]; };
+    double emax = 0.0, rmax = 0.0;
+    for (int y2 = 0; y2 < 16; ++y2)
+        for (int x2 = 0; x2 < 16; ++x2)
+            for (int y = 0; y < 16; ++y)
+                for (int x = 0; x < 16; ++x) {
+                    const double e = E[(x + 16 * y) + (size_t)n * (x2 + 16 * y2)];
+                    double claim = 0.0, xdy = 0.0, ydx = 0.0;
+                    for (int k = 0; k < 16; ++k) {
+                        claim += F(fy, y, k) * F(fx, x, x2 - y2 + k) * F(fd, k, y2);   // (Fy (x) Fx) Ed
+                        xdy += F(fx, x, x2 + y - k) * F(fd, y, k) * F(fy, k, y2);      // Fx Ed Fy
+                        ydx += F(fy, y, k) * F(fd, k, y2) * F(fx, x - k + y2, x2);     // Fy Ed Fx
+                    }
+                    emax = std::max(emax, std::fabs(e));
+                    rmax = std::max(rmax, std::max(std::fabs(e - claim), std::max(std::fabs(e - xdy), std::fabs(e - ydx))));
+                }
+    return std::isfinite(emax) && std::isfinite(rmax) && rmax <= 256.0 * 2.220446049250313e-16 * emax;
+}
+
 // The kernel-selection and test switches, read from the environment once per handle / stand-alone
 // primitive call: nothing else reads them (the launchers get them from the handle)
 static void read_kernel_switches(dqmc_handle *h)
@@ -649,7 +681,8 @@ static bool oop_wrap(const dqmc_handle *h) { return (h->slab || h->kron) && !h->
 // replaces is cheaper
 static bool fold_wrap_flush(const dqmc_handle *h)
 {
-    return use_kron(h) && h->n == 256 && h->sweep_fused && !h->sw.no_wrap_flush;
+    // (not on the triangular path: tri.hip has no pending-chunk form; the stand-alone flush applies the last chunk)
+    return use_kron(h) && h->n == 256 && !h->tri && h->sweep_fused && !h->sw.no_wrap_flush;
 }
 // greens as the reference has it: a pending last chunk is applied by the stand-alone flush (out of place through
 // greens_alt, which is free between two sweep_spatial calls)
@@ -692,6 +725,7 @@ static int run_kron(dqmc_handle *h, const KronArgs &a)
     hipEvent_t ea, eb;
     timing_events(h, &ea, &eb);
     if (h->n == 512) HIPCHK(launch_kron3_chain(a, h->cur, ea, eb));
+    else if (h->tri) HIPCHK(launch_tri_chain(a, h->cur, ea, eb));
     else HIPCHK(launch_kron_chain(a, h->cur, ea, eb));
     return timing_push(h, ea, eb, DQMC_K_GEMM);
 }
@@ -795,7 +829,7 @@ static int wrap_greens_kron(dqmc_handle *h, const double *src, double *dst, int 
     KronArgs a = kron_base(h, src, h->bufB);
     a.transpose_out = 1;
     if (h->pf.G) {  // the sweep's last chunk is applied to the columns of src as the first launch loads them
-        if (h->pf.G != src || h->n != 256) return fail(h, DQMC_ERR_STATE, "wrap of another matrix with a sweep update pending");
+        if (h->pf.G != src || h->n != 256 || h->tri) return fail(h, DQMC_ERR_STATE, "wrap of another matrix with a sweep update pending");
         a.pf_img = h->pf.img; a.pf_img_su = (long)sweep_lu_image_doubles(); a.pf_site0 = h->pf.site0;
         h->pf = dqmc_handle::PendingFlush{};
     }
@@ -1931,6 +1965,45 @@ int dqmc_get_reduced_stats(dqmc_handle *h, dqmc_stats *out)
     return DQMC_OK;
 }
 
+
+// The triangular 16 x 16 lattice's hopping exponentials as three 16 x 16 factors per matrix (include/dqmc_hip.h): checked
+// against the handle's own eT2 / eTinv2 (tri_factor_ok) before the handle takes them; a failed check leaves it as it was.
+int dqmc_set_triangular_factors(dqmc_handle *h, const double *f)
+{
+    ENTER(h);
+    if (!f) return fail(h, DQMC_ERR_INVALID, "dqmc_set_triangular_factors: null factors");
+    if (h->n != 256) return fail(h, DQMC_ERR_INVALID, "dqmc_set_triangular_factors: n_sites must be 256");
+    if (h->prepared) return fail(h, DQMC_ERR_STATE, "dqmc_set_triangular_factors: call before dqmc_prepare");
+    if (!h->slab || h->cb.on || h->sw.no_kron || h->kron) return DQMC_OK;  // a path that does not take them: kept
+    const int nb = h->nb;
+    std::vector<double> E((size_t)2 * nb * h->nn);
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(E.data(), h->eT2, sizeof(double) * nb * h->nn, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(E.data() + (size_t)nb * h->nn, h->eTinv2, sizeof(double) * nb * h->nn, hipMemcpyDeviceToHost));
+    // [eT2, eTinv2, eT2', eTinv2'] x [x, y, d] x nb x 256
+    std::vector<double> img((size_t)4 * 3 * nb * 256);
+    for (int b = 0; b < nb; ++b)
+        for (int m = 0; m < 2; ++m) {
+            const double *fb = f + (size_t)b * 1536 + (size_t)m * 768;
+            if (!tri_factor_ok(E.data() + ((size_t)m * nb + b) * h->nn, fb, fb + 256, fb + 512))
+                return fail(h, DQMC_ERR_INVALID, "dqmc_set_triangular_factors: the factors do not reproduce eT2 / eTinv2 of block " +
+                                                     std::to_string(b) + " within 256 ulp");
+            for (int k = 0; k < 3; ++k) {
+                double *o = img.data() + (((size_t)m * 3 + k) * nb + b) * 256, *ot = o + (size_t)2 * 3 * nb * 256;
+                for (int j = 0; j < 16; ++j)
+                    for (int i = 0; i < 16; ++i) {
+                        o[i + 16 * j] = fb[256 * k + i + 16 * j];
+                        ot[i + 16 * j] = fb[256 * k + j + 16 * i];
+                    }
+            }
+        }
+    CHK(dalloc(h, &h->kron_f, img.size()));
+    HIPCHK(hipMemcpy(h->kron_f, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice));
+    h->kron_fa = 256;
+    h->kron_fb = 512;  // Fy, then Fd
+    h->tri = h->kron = true;
+    return DQMC_OK;
+}
 
 // CheckerboardTrue with the bond-group factors kept sparse on the device (stack.jl:185-235): `n_mats` factors in ELL
 // form (vals / cols [n_mats][n][kmax], 0-based columns, padding val 0), the diagonal exp(-+dtau mu) per block and

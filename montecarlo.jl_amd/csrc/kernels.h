@@ -119,6 +119,9 @@ hipError_t launch_kron_chain(const KronArgs &a, hipStream_t s, hipEvent_t start 
 // The same chains at n = 512 = 8 x 8 x 8 sites with A_s = Ez (x) Exy (kron3.hip): ax / ay are the operand images of
 // Exy (64 x 64, block b at + 4096 b) and of I2 (x) Ez (block b at + 256 b) described there
 hipError_t launch_kron3_chain(const KronArgs &a, hipStream_t s, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
+// The same chains on the triangular 16 x 16 lattice (n = 256) with A_s = (Fy (x) Fx) Ed (tri.hip): ax = Fx and ay = Fy of
+// block b at + 256 b, and Fd (applied along the diagonals x - y = const) at ay + 256 (nb + b)
+hipError_t launch_tri_chain(const KronArgs &a, hipStream_t s, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
 
 // Column-pivoted Householder QR, in place (udt_AVX_pivot! "QR decomposition" loop,
 // src/linalg/UDT.jl:212-246).  On exit A holds R on/above the diagonal and the

@@ -62,6 +62,34 @@ def hopping_exponentials(T, delta_tau):
     return eT, eTinv, eT @ eT, eTinv @ eTinv
 
 
+_ERR_INVALID = -1  # DQMC_ERR_INVALID (include/dqmc_hip.h)
+
+
+def _ring_exponentials(h, delta_tau):
+    """exp(-dtau h) and exp(+dtau h) of a 16 x 16 one-dimensional hopping h with the recipe of hopping_exponentials:
+    the half-step exponential from eigh, squared"""
+    w, V = np.linalg.eigh(-0.5 * delta_tau * h)
+    e = (V * np.exp(w)) @ V.T
+    w, V = np.linalg.eigh(0.5 * delta_tau * h)
+    ei = (V * np.exp(w)) @ V.T
+    return e @ e, ei @ ei
+
+
+def triangular_factors(model, delta_tau):
+    """The factors dqmc_set_triangular_factors takes for a model on TriangularLattice(16): per block
+    [eT2: Fx Fy Fd][eTinv2: Fx Fy Fd], each 16 x 16 column-major, such that eT2 = (Fy (x) Fx) Ed(Fd) (and eTinv2 alike)
+    in the site order x + 16 y, where Ed applies Fd along the diagonals x - y = const.  T = -mu - t (X + X' + Y + Y' + D + D')
+    with X, Y and D = XY commuting shifts, so exp(-dtau T) = e^{dtau mu} f(X) f(Y) f(D), f = exp(dtau t (S + S')) on a
+    16-ring; mu is folded into Fx.  The engine checks them against the dense exponentials."""
+    L = 16
+    S = np.roll(np.eye(L), 1, axis=0)
+    ring = -model.t * (S + S.T)
+    ex, exi = _ring_exponentials(ring - model.mu * np.eye(L), delta_tau)
+    e1, e1i = _ring_exponentials(ring, delta_tau)
+    per_block = np.concatenate([m.reshape(-1, order="F") for m in (ex, e1, e1, exi, e1i, e1i)])
+    return np.ascontiguousarray(np.tile(per_block, model.flv))
+
+
 def checkerboard_exponentials(T, lattice, delta_tau, return_factors=False):
     """CheckerboardTrue (init_checkerboard_matrices, stack.jl:185-235; slice_matrices.jl:79-222;
     _greens! DQMC.jl:731-750) as the four constant matrices of the dense code path.  The reference
@@ -152,6 +180,20 @@ def checkerboard_tables(T, lattice, delta_tau):
     return dict(kmax=kmax, vals=vals, cols=cols, mu=mu, mu_inv=mu_inv, seqs=seqs)
 
 
+def checkerboard_seqs(tables):
+    """The seven factor sequences of checkerboard_tables as the [7][32] array and the lengths dqmc_set_checkerboard takes;
+    a lattice with more than 16 bond groups has longer sequences and cannot use the sparse form"""
+    seqs = np.zeros((7, 32), dtype=np.int32)
+    lens = np.zeros(7, dtype=np.int32)
+    for q, sq in enumerate(tables["seqs"]):
+        if len(sq) > 32:
+            raise ValueError("sparse checkerboard: a factor sequence of %d entries exceeds the 32 the engine takes (%d bond "
+                             "groups); use checkerboard=\"dense\"" % (len(sq), (len(sq) + 1) // 2))
+        lens[q] = len(sq)
+        seqs[q, :len(sq)] = sq
+    return seqs, lens
+
+
 class DQMCAnalysis:
     """DQMC.jl:36-47 for one walker"""
 
@@ -206,11 +248,7 @@ class DQMC:
         if self.checkerboard and sparse:
             tb = [checkerboard_tables(T, model.l, self.p.delta_tau) for T in Ts]
             t0 = tb[0]  # both spin blocks of the repulsive model share T (HubbardModelRepulsive.jl:87-100)
-            seqs = np.zeros((7, 32), dtype=np.int32)
-            lens = np.zeros(7, dtype=np.int32)
-            for q, sq in enumerate(t0["seqs"]):
-                lens[q] = len(sq)
-                seqs[q, :len(sq)] = sq
+            seqs, lens = checkerboard_seqs(t0)
             mu = np.ascontiguousarray(np.concatenate([t["mu"] for t in tb]))
             mui = np.ascontiguousarray(np.concatenate([t["mu_inv"] for t in tb]))
             vals, cols = np.ascontiguousarray(t0["vals"]), np.ascontiguousarray(t0["cols"])
@@ -218,6 +256,16 @@ class DQMC:
                                               cols.ctypes.data_as(C.POINTER(C.c_int32)), dptr(mu), dptr(mui),
                                               seqs.ctypes.data_as(C.POINTER(C.c_int32)),
                                               lens.ctypes.data_as(C.POINTER(C.c_int32))), self._h)
+        # the triangular 16 x 16 lattice: its exponentials in three-factor form (tri.hip).  The engine tests the factors
+        # against its own eT2 / eTinv2 and refuses ones that do not reproduce them (a hopping other than the model's
+        # t and mu): the handle then keeps the dense path.
+        from .lattices import TriangularLattice
+        l = model.l
+        if isinstance(l, TriangularLattice) and l.Lx == l.Ly == 16 and not self.checkerboard:
+            f = triangular_factors(model, self.p.delta_tau)
+            rc = lib().dqmc_set_triangular_factors(self._h, dptr(f))
+            if rc != _ERR_INVALID:
+                self._c(rc)
         # rand(DQMC, m, slices) per walker (DQMC.jl:273), then the Metropolis stream
         self.seeds = [seed + first_walker + w for w in range(n_walkers)]
         for w, s in enumerate(self.seeds):
@@ -673,8 +721,8 @@ class DQMC:
         return n.value
 
     def kron_hopping(self):
-        """True when slice products and wraps apply the hopping exponentials as Kronecker products (16 x 16 factors at
-        n = 256, 8 x 8 at n = 512; include/dqmc_hip.h)"""
+        """True when slice products and wraps apply the hopping exponentials in factored form (16 x 16 Kronecker factors
+        at n = 256, 8 x 8 at n = 512, the triangular 16 x 16 lattice's three factors; include/dqmc_hip.h)"""
         f = C.c_int32(0)
         self._c(lib().dqmc_kron_hopping(self._h, C.byref(f)))
         return bool(f.value)

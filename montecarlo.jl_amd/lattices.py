@@ -1,4 +1,5 @@
-"""Host-side lattices (src/lattices/square.jl:25-60, chain.jl:19-41, cubic.jl:19-70, abstract.jl:99-115).
+"""Host-side lattices (src/lattices/square.jl:25-60, chain.jl:19-41, cubic.jl:19-70, triangular.jl:1-119,
+abstract.jl:99-115).
 
 Integer tables are 1-based like the reference's so that they compare verbatim with
 its fixtures (test/flavortests_DQMC.jl:22-24)."""
@@ -70,6 +71,38 @@ class CubicLattice(AbstractLattice):
         self.bonds = bonds
 
 
+class TriangularLattice(AbstractLattice):
+    """TriangularLattice(L; Lx=L, Ly=L) (triangular.jl:24-57): site i + Lx (j - 1) (column-major reshape of 1:Lx*Ly);
+    neighs rows = up (i+1), upright (i+1, j+1), right (j+1), down, downleft, left (Julia circshift semantics, :60-78);
+    ext_neighs the same rows two steps away (R + 2a, :81-99).  The bonds table lists neighs[1:3] then ext_neighs[1:3] for
+    each source; the hopping matrix takes neighs only, so the ext bonds carry no hopping.  Kept as the reference has them:
+    positions() puts upright at distance sqrt(3), and the geometric nearest neighbour (i+1, j-1) is no hopping neighbour
+    (DESIGN 4.7)."""
+
+    def __init__(self, L, Lx=None, Ly=None):
+        Lx = L if Lx is None else Lx
+        Ly = L if Ly is None else Ly
+        self.L, self.Lx, self.Ly = L, Lx, Ly
+        self.sites = Lx * Ly
+        lat = np.arange(1, self.sites + 1).reshape((Lx, Ly), order="F")
+        self.lattice = lat
+
+        def table(k):  # circshift(lattice, (-k, 0)), (-k, -k), (0, -k), (k, 0), (k, k), (0, k)
+            shifts = ((-k, 0), (-k, -k), (0, -k), (k, 0), (k, k), (0, k))
+            cart = np.stack([np.roll(lat, s, axis=(0, 1)) for s in shifts])
+            return np.vstack([c.reshape(-1, order="F") for c in cart]).astype(np.int64), cart
+        self.neighs, self.neighs_cartesian = table(1)
+        self.ext_neighs, self.ext_neighs_cartesian = table(2)
+        self.isAsite = np.array([(i + 1) % 2 == 0 for j in range(Ly) for i in range(Lx)])
+        self.n_bonds = 6 * self.sites
+        bonds = np.zeros((self.n_bonds, 3), dtype=np.int64)
+        b = 0
+        for src in lat.reshape(-1, order="F"):
+            for trg in list(self.neighs[:3, src - 1]) + list(self.ext_neighs[:3, src - 1]):
+                bonds[b] = (src, trg, 0); b += 1
+        self.bonds = bonds
+
+
 def build_checkerboard(l):
     """src/flavors/DQMC/abstract.jl:23-54 (used here only to pin the bond tables)."""
     bonds = l.neighbors(False)
@@ -99,7 +132,10 @@ def _check_cubic(l):
 
 
 def _positions(l):
-    """positions(l) (square.jl:72, chain.jl:52, cubic.jl:69): 1-based cartesian coordinates"""
+    """positions(l) (square.jl:72, chain.jl:52, cubic.jl:69, triangular.jl:113-116): cartesian coordinates"""
+    if isinstance(l, TriangularLattice):  # a1 = (0.5, sqrt(3) / 2) along i, a2 = (1, 0) along j, 1-based (i, j)
+        a1, a2 = np.array([0.5, 0.8660254037844386]), np.array([1.0, 0.0])
+        return [a1 * (i + 1) + a2 * (j + 1) for j in range(l.Ly) for i in range(l.Lx)]
     if isinstance(l, SquareLattice):
         return [np.array([i + 1.0, j + 1.0]) for j in range(l.L) for i in range(l.L)]
     if isinstance(l, CubicLattice):
@@ -109,6 +145,8 @@ def _positions(l):
 
 
 def _lattice_vectors(l):
+    if isinstance(l, TriangularLattice):  # triangular.jl:118
+        return [np.array([0.5, 0.8660254037844386]) * l.Lx, np.array([float(l.Ly), 0.0])]
     if isinstance(l, SquareLattice):
         return [np.array([float(l.L), 0.0]), np.array([0.0, float(l.L)])]
     if isinstance(l, CubicLattice):
