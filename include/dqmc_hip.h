@@ -348,6 +348,70 @@ const char *dqmc_build_commit(void);
  * leave it alone - this is what decides whether a committed profile still describes the library */
 const char *dqmc_build_source_hash(void);
 
+/* ---- the classical MC flavor with the IsingModel ---------------------------------------------------------------
+ * MC(model; ...) (src/flavors/MC/MC.jl:16-80) with IsingModel (src/models/Ising/IsingModel.jl) for n_walkers
+ * independent Markov chains on one device, one lane per walker (csrc/ising.hip).  A walker's stream is the Philox4x32-10
+ * counter stream of dqmc_seed: key = seed, counter = draw index.  sweep(mc) (MC.jl:316-333) visits sites 1..N in order,
+ * dE = 2 s_i sum_{j in neighs[:, i]} s_j (IsingModel.jl:85-101), and accepts iff dE <= 0 || u < exp(-beta dE), with a
+ * uniform drawn only when dE > 0; exp(-beta dE) is a per-walker table computed on the host (dqmc_mc_set_beta).
+ * Limits: n_sites <= 16384, 1 <= z <= 8.  Errors come from dqmc_mc_last_error. */
+typedef struct dqmc_mc_handle dqmc_mc_handle;
+
+typedef struct {
+    int32_t n_sites;         /* length(lattice(m)) */
+    int32_t z;               /* neighbours per site: size(l.neighs, 1) */
+    int32_t n_walkers;       /* independent chains batched on this device */
+    int32_t device_id;
+    int32_t n_bonds;         /* size(l.bonds, 1) */
+    int32_t series_capacity; /* per-walker measurements recorded as a time series (0 = none) */
+    const int64_t *neighs;   /* l.neighs as is: z x n_sites, column-major, 1-based (lattices/abstract.jl:56-66) */
+    const int64_t *bonds;    /* l.bonds[:, 1:2]: n_bonds x 2, column-major, 1-based (abstract.jl:33-38, neighbors(l)) */
+} dqmc_mc_params;
+
+/* MCAnalysis (MC.jl:1-11) and the sums behind IsingEnergyMeasurement / IsingMagnetizationMeasurement
+ * (models/Ising/measurements.jl:13-94) for one walker; the sums are exact integers held in fp64 */
+typedef struct {
+    int64_t energy;        /* model.energy[] */
+    int64_t magnetization; /* sum(mc.conf) */
+    double sum_E, sum_E2, sum_absM, sum_M2;
+    int64_t n_meas;        /* measurements summed since the last dqmc_mc_reset_accumulators */
+    int64_t prop_local, acc_local;
+    uint64_t uniforms_used; /* draws consumed from the walker's stream */
+    int64_t n_series;       /* measurements recorded in the series, <= series_capacity */
+} dqmc_mc_stats;
+
+/* MC(m; ...) + init! (MC.jl:50-80): validates the arguments, then the device (no device: DQMC_ERR_NO_DEVICE) */
+int dqmc_mc_create(const dqmc_mc_params *p, dqmc_mc_handle **out);
+int dqmc_mc_destroy(dqmc_mc_handle *h);
+/* message of the last failing call on this handle (h may be NULL: create errors) */
+const char *dqmc_mc_last_error(const dqmc_mc_handle *h);
+/* mc.p.beta (MCParameters, MC.jl:24) of one walker: the threshold table exp(-beta 2k), k = 1..8, computed on the host;
+ * beta finite and >= 0 */
+int dqmc_mc_set_beta(dqmc_mc_handle *h, int32_t walker, double beta);
+/* the walker's stream: key = seed, cursor at draw 0 */
+int dqmc_mc_seed(dqmc_mc_handle *h, int32_t walker, uint64_t seed);
+/* mc.conf = rand(MC, m) (IsingModel.jl:83): site i takes the walker's next uniform, u < 0.5 -> -1; then init!
+ * (energy(mc, m, conf), IsingModel.jl:24).  walker < 0: every walker */
+int dqmc_mc_rand_conf(dqmc_mc_handle *h, int32_t walker);
+/* mc.conf as Int8 +-1 in site order; set_conf recomputes energy and magnetization and leaves the cursor alone */
+int dqmc_mc_set_conf(dqmc_mc_handle *h, int32_t walker, const int8_t *conf);
+int dqmc_mc_get_conf(dqmc_mc_handle *h, int32_t walker, int8_t *conf);
+/* BitArray(conf .== 1) chunks as dqmc_get_conf_bits: ceil(n_sites / 64) uint64 */
+int dqmc_mc_get_conf_bits(dqmc_mc_handle *h, int32_t walker, uint64_t *chunks);
+/* n_sweeps x sweep(mc) with the measurement rule of run! (MC.jl:262-283): after global sweep index
+ * i = first_sweep_index, first_sweep_index + 1, ... measure iff i > thermalization && i % measure_rate == 0.
+ * Split into launches of bounded work; complete on return. */
+int dqmc_mc_sweep(dqmc_mc_handle *h, int32_t n_sweeps, int64_t first_sweep_index, int64_t thermalization,
+                  int32_t measure_rate);
+int dqmc_mc_get_stats(dqmc_mc_handle *h, int32_t walker, dqmc_mc_stats *out);
+/* per-measurement E and |M| (the Observable series of measure!, measurements.jl:30-37,75-81), n_series entries each;
+ * either buffer may be NULL */
+int dqmc_mc_get_series(dqmc_mc_handle *h, int32_t walker, int32_t *energy, int32_t *abs_magnetization,
+                       int64_t *n_recorded);
+/* clear the measurement sums and series of every walker (MCAnalysis counters stay) */
+int dqmc_mc_reset_accumulators(dqmc_mc_handle *h);
+int dqmc_mc_synchronize(dqmc_mc_handle *h);
+
 /* ---- instrumentation ------------------------------------------------------ */
 /* Per-kernel-family device time accumulated with HIP events on the handle's
  * stream when enabled (off by default; used by bench.py's roofline leg). */

@@ -19,4 +19,6 @@ from .dqmc import (DQMC, DQMCParameters, calculate_greens_AVX, device_count,  # 
                    hopping_exponentials, mfma_f64_peak, rdivp, triangular_factors,
                    udt_AVX_pivot, vmul)
 
+from .mc import MC, IsingModel, IsingTc  # noqa: F401
+
 lib()  # fail loudly at import time if the HIP library has not been built

@@ -41,6 +41,18 @@ class Stats(C.Structure):
                 ("negative_probability", MagStats), ("propagation_error", MagStats)]
 
 
+class McParams(C.Structure):
+    _fields_ = [("n_sites", C.c_int32), ("z", C.c_int32), ("n_walkers", C.c_int32), ("device_id", C.c_int32),
+                ("n_bonds", C.c_int32), ("series_capacity", C.c_int32), ("neighs", C.POINTER(C.c_int64)),
+                ("bonds", C.POINTER(C.c_int64))]
+
+
+class McStats(C.Structure):
+    _fields_ = [("energy", C.c_int64), ("magnetization", C.c_int64), ("sum_E", C.c_double), ("sum_E2", C.c_double),
+                ("sum_absM", C.c_double), ("sum_M2", C.c_double), ("n_meas", C.c_int64), ("prop_local", C.c_int64),
+                ("acc_local", C.c_int64), ("uniforms_used", C.c_uint64), ("n_series", C.c_int64)]
+
+
 _dp = C.POINTER(C.c_double)
 _i64p = C.POINTER(C.c_int64)
 _H = C.c_void_p
@@ -126,6 +138,21 @@ SIGNATURES = {
     "dqmc_udt_one_launch_sites": (C.c_int, [_H, C.POINTER(C.c_int32)]),
     "dqmc_build_commit": (C.c_char_p, []),
     "dqmc_build_source_hash": (C.c_char_p, []),
+    "dqmc_mc_create": (C.c_int, [C.POINTER(McParams), C.POINTER(_H)]),
+    "dqmc_mc_destroy": (C.c_int, [_H]),
+    "dqmc_mc_last_error": (C.c_char_p, [_H]),
+    "dqmc_mc_set_beta": (C.c_int, [_H, C.c_int32, C.c_double]),
+    "dqmc_mc_seed": (C.c_int, [_H, C.c_int32, C.c_uint64]),
+    "dqmc_mc_rand_conf": (C.c_int, [_H, C.c_int32]),
+    "dqmc_mc_set_conf": (C.c_int, [_H, C.c_int32, C.c_void_p]),
+    "dqmc_mc_get_conf": (C.c_int, [_H, C.c_int32, C.c_void_p]),
+    "dqmc_mc_get_conf_bits": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_uint64)]),
+    "dqmc_mc_sweep": (C.c_int, [_H, C.c_int32, C.c_int64, C.c_int64, C.c_int32]),
+    "dqmc_mc_get_stats": (C.c_int, [_H, C.c_int32, C.POINTER(McStats)]),
+    "dqmc_mc_get_series": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                           C.POINTER(C.c_int64)]),
+    "dqmc_mc_reset_accumulators": (C.c_int, [_H]),
+    "dqmc_mc_synchronize": (C.c_int, [_H]),
     "dqmc_timing_enable": (C.c_int, [_H, C.c_int32]),
     "dqmc_timing_get": (C.c_int, [_H, _dp, _i64p]),
     "dqmc_mfma_f64_peak": (C.c_int, [C.c_int32, C.c_int32, _dp]),

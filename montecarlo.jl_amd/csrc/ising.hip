@@ -1,0 +1,555 @@
+// ising.hip — the classical MC flavor (src/flavors/MC/MC.jl) with the IsingModel (src/models/Ising/IsingModel.jl),
+// batched over independent Markov chains: kernels and the dqmc_mc_* C ABI (include/dqmc_hip.h).
+//
+// A chain is strictly sequential (sites 1..N in order, MC.jl:316-333), so the only parallelism is across walkers:
+// one lane per walker, one wave per workgroup.  All lanes visit the same site at the same time, so the site index and
+// its row of the neighbour table are wave-uniform (scalar loads).  A walker's spins stay in LDS for the whole launch,
+// bit-packed as [word][lane] (bit i & 31 of word i >> 5, 1 = spin +1): a per-lane read of a uniform word index touches
+// 64 consecutive dwords, one per bank.  The word that holds the current site lives in a register, so the dependency
+// through the previous site's spin (the "down" neighbour i - 1 is almost always in the same word) is a register
+// forward, not an LDS round trip.
+//
+// Metropolis: dE = 2 s_i sum_j s_j = 2k with k in -z..z.  k <= 0 accepts without a draw; k > 0 draws the walker's next
+// Philox4x32-10 uniform (key = seed, counter = draw index, as orc_ising_run) and accepts iff u < thr[k], where
+// thr[k] = exp(-beta 2k) comes from the host's libm: no exp on the device, so every decision is bit-identical to the
+// oracle's.  E and M are tracked incrementally; a measurement adds E, E^2, |M|, M^2 to fp64 sums (exact integers).
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/dqmc_hip.h"
+#include "kernels.h"
+
+namespace dqmc_mc {
+
+constexpr int MAX_SITES = 16384;  // 512 words x 64 lanes x 4 B = 128 KiB of LDS per workgroup
+constexpr int MAX_Z = 8;
+constexpr int WAVE = 64;
+// one launch runs at most this many site visits summed over its walkers (sites x sweeps x walkers), a handle with
+// fewer than BUDGET_WALKERS walkers counted as that many (their waves run side by side, so a launch takes as long as
+// one walker's chain); dqmc_mc_sweep splits its sweeps into launches of at least one sweep each, so that no single
+// kernel holds the GPU for long
+constexpr double LAUNCH_BUDGET = 268435456.0;
+constexpr double BUDGET_WALKERS = 16384.0;
+
+struct DevState {
+    int N, W, nw, cap;
+    const int *nbr;                 // [N + 1][8] 0-based, rows padded to 8 (row N: read ahead, unused)
+    const int *__restrict__ bonds;  // [n_bonds][2] 0-based
+    int n_bonds;
+    unsigned int *conf;             // [nw][W]
+    unsigned long long *key, *draw;
+    int *E, *M;
+    double *thr;                    // [8][W], thr[k - 1] = exp(-beta 2k)
+    double *sE, *sE2, *sM, *sM2;
+    long long *n_meas, *prop, *acc, *n_series;
+    int *serE, *serM;               // [cap][W]
+};
+
+// flat index of lane `w` in the [row][W] arrays
+__device__ __forceinline__ size_t at(int row, int W, int w) { return (size_t)row * W + w; }
+
+// the neighbour table is a kernel argument of its own, read-only and not aliased: that is what lets the compiler read
+// a row with one scalar load (a member of DevState would be an ordinary pointer the kernel's stores might alias)
+template <int Z>
+__global__ __launch_bounds__(WAVE) void ising_sweep_kernel(DevState s, const int4 *__restrict__ nbr, int n_sweeps,
+                                                           long long first_sweep, long long thermalization,
+                                                           int measure_rate)
+{
+    extern __shared__ unsigned int sp[];
+    const int lane = threadIdx.x;
+    const int w = blockIdx.x * WAVE + lane;
+    if (w >= s.W) return;
+    const int N = s.N, nw = s.nw, W = s.W;
+    for (int j = 0; j < nw; ++j) sp[j * WAVE + lane] = s.conf[at(j, W, w)];
+    const unsigned long long key = s.key[w];
+    unsigned long long draw = s.draw[w];
+    int E = s.E[w], M = s.M[w];
+    double thr[Z];
+#pragma unroll
+    for (int k = 0; k < Z; ++k) thr[k] = s.thr[at(k, W, w)];
+    double sE = s.sE[w], sE2 = s.sE2[w], sM = s.sM[w], sM2 = s.sM2[w];
+    long long n_meas = s.n_meas[w], n_series = s.n_series[w], acc = 0;
+
+    for (int sw = 0; sw < n_sweeps; ++sw) {
+        int cw = 0;
+        unsigned int cur = sp[lane];
+        int4 r0 = nbr[0], r1 = nbr[1];  // row of site 0; the row of site i + 1 is requested while site i runs
+        for (int i = 0; i < N; ++i) {
+            const int iw = i >> 5, ib = i & 31;
+            if (iw != cw) {  // uniform: the previous word is complete
+                sp[cw * WAVE + lane] = cur;
+                cw = iw;
+                cur = sp[cw * WAVE + lane];
+            }
+            const int row[8] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w};
+            r0 = nbr[2 * i + 2];  // (the table holds N + 1 rows)
+            r1 = nbr[2 * i + 3];
+            int up = 0;
+#pragma unroll
+            for (int k = 0; k < Z; ++k) {
+                const int j = row[k], jw = j >> 5;
+                const unsigned int v = jw == iw ? cur : sp[jw * WAVE + lane];
+                up += (v >> (j & 31)) & 1u;
+            }
+            const int si = (cur >> ib) & 1u;
+            const int sum = 2 * up - Z;         // sum of the neighbours' spins
+            const int k = si ? sum : -sum;      // dE / 2
+            bool accept = k <= 0;
+            if (k > 0) {
+                const double u = dqmc::philox_uniform(key, draw);
+                ++draw;
+                double t = thr[0];
+#pragma unroll
+                for (int q = 1; q < Z; ++q) t = k == q + 1 ? thr[q] : t;
+                accept = u < t;
+            }
+            if (accept) {
+                cur ^= 1u << ib;
+                E += 2 * k;
+                M += si ? -2 : 2;
+                ++acc;
+            }
+        }
+        sp[cw * WAVE + lane] = cur;
+        const long long g = first_sweep + sw;  // global 1-based sweep index (MC.jl:262-283)
+        if (g > thermalization && g % measure_rate == 0) {
+            const double e = (double)E, m = (double)(M < 0 ? -M : M);
+            sE += e;
+            sE2 += e * e;
+            sM += m;
+            sM2 += m * m;
+            if (n_series < s.cap) {
+                s.serE[at((int)n_series, W, w)] = E;
+                s.serM[at((int)n_series, W, w)] = M < 0 ? -M : M;
+                ++n_series;
+            }
+            ++n_meas;
+        }
+    }
+    for (int j = 0; j < nw; ++j) s.conf[at(j, W, w)] = sp[j * WAVE + lane];
+    s.draw[w] = draw;
+    s.E[w] = E;
+    s.M[w] = M;
+    s.sE[w] = sE;
+    s.sE2[w] = sE2;
+    s.sM[w] = sM;
+    s.sM2[w] = sM2;
+    s.n_meas[w] = n_meas;
+    s.n_series[w] = n_series;
+    s.prop[w] += (long long)n_sweeps * N;
+    s.acc[w] += acc;
+}
+
+// rand(MC, m) (IsingModel.jl:83): site i (column-major) takes the walker's next uniform, u < 0.5 -> -1.
+// walker < 0: every walker.
+__global__ __launch_bounds__(WAVE) void ising_rand_conf_kernel(DevState s, int walker)
+{
+    const int w = walker >= 0 ? walker : blockIdx.x * WAVE + threadIdx.x;
+    if (w >= s.W || (walker >= 0 && threadIdx.x != 0)) return;
+    const unsigned long long key = s.key[w];
+    unsigned long long draw = s.draw[w];
+    for (int j = 0; j < s.nw; ++j) {
+        unsigned int word = 0;
+        const int n = min(32, s.N - 32 * j);
+        for (int b = 0; b < n; ++b) word |= (dqmc::philox_uniform(key, draw++) < 0.5 ? 0u : 1u) << b;
+        s.conf[at(j, s.W, w)] = word;
+    }
+    s.draw[w] = draw;
+}
+
+// energy(mc, m, conf) over the bonds table (IsingModel.jl:149-186) and M = sum(conf); walker < 0: every walker
+__global__ __launch_bounds__(WAVE) void ising_observables_kernel(DevState s, int walker)
+{
+    extern __shared__ unsigned int sp[];
+    const int lane = threadIdx.x;
+    const int w = walker >= 0 ? walker : blockIdx.x * WAVE + lane;
+    if (w >= s.W || (walker >= 0 && lane != 0)) return;
+    int M = 0;
+    for (int j = 0; j < s.nw; ++j) {
+        const unsigned int v = s.conf[at(j, s.W, w)];
+        sp[j * WAVE + lane] = v;
+        M += 2 * __popc(v);
+    }
+    M -= s.N;
+    int E = 0;
+    for (int b = 0; b < s.n_bonds; ++b) {
+        const int a = s.bonds[2 * b], c = s.bonds[2 * b + 1];
+        const int sa = (sp[(a >> 5) * WAVE + lane] >> (a & 31)) & 1u, sc = (sp[(c >> 5) * WAVE + lane] >> (c & 31)) & 1u;
+        E -= sa == sc ? 1 : -1;
+    }
+    s.E[w] = E;
+    s.M[w] = M;
+}
+
+}  // namespace dqmc_mc
+
+using namespace dqmc_mc;
+
+struct dqmc_mc_handle {
+    int N = 0, z = 0, W = 0, nw = 0, cap = 0, n_bonds = 0, device = 0;
+    std::vector<int> nbr_h;    // [N][z] 0-based
+    std::vector<int> bonds_h;  // [n_bonds][2] 0-based
+    hipStream_t stream = nullptr;
+    DevState d{};
+    std::vector<void *> allocs;
+    std::string err;
+};
+
+static thread_local std::string g_mc_create_error;
+
+static int mc_fail(dqmc_mc_handle *h, int code, const std::string &msg)
+{
+    if (h) h->err = msg;
+    else g_mc_create_error = msg;
+    return code;
+}
+
+#define MCHK(expr)                                                                          \
+    do {                                                                                    \
+        hipError_t e_ = (expr);                                                             \
+        if (e_ != hipSuccess) return mc_fail(h, DQMC_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
+template <typename T>
+static int mc_alloc(dqmc_mc_handle *h, T **p, size_t count)
+{
+    void *q = nullptr;
+    MCHK(hipMalloc(&q, (count ? count : 1) * sizeof(T)));
+    h->allocs.push_back(q);
+    MCHK(hipMemsetAsync(q, 0, (count ? count : 1) * sizeof(T), h->stream));
+    *p = (T *)q;
+    return 0;
+}
+
+static int mc_walker(dqmc_mc_handle *h, int32_t w, const char *fn)
+{
+    if (!h) return mc_fail(nullptr, DQMC_ERR_INVALID, std::string(fn) + ": null handle");
+    if (w < 0 || w >= h->W) return mc_fail(h, DQMC_ERR_INVALID, std::string(fn) + ": walker out of range");
+    return 0;
+}
+
+// one element of a [row][W] device array
+template <typename T>
+static int mc_put(dqmc_mc_handle *h, T *base, int row, int w, T v)
+{
+    MCHK(hipMemcpyAsync(base + (size_t)row * h->W + w, &v, sizeof(T), hipMemcpyHostToDevice, h->stream));
+    MCHK(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+template <typename T>
+static int mc_get(dqmc_mc_handle *h, const T *base, int row, int w, T *v)
+{
+    MCHK(hipMemcpyAsync(v, base + (size_t)row * h->W + w, sizeof(T), hipMemcpyDeviceToHost, h->stream));
+    MCHK(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+static int mc_launch_observables(dqmc_mc_handle *h, int walker)
+{
+    const int grid = walker >= 0 ? 1 : (h->W + WAVE - 1) / WAVE;
+    hipLaunchKernelGGL(ising_observables_kernel, dim3(grid), dim3(WAVE), (size_t)h->nw * WAVE * 4, h->stream, h->d,
+                       walker);
+    MCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" {
+
+const char *dqmc_mc_last_error(const dqmc_mc_handle *h) { return h ? h->err.c_str() : g_mc_create_error.c_str(); }
+
+int dqmc_mc_create(const dqmc_mc_params *p, dqmc_mc_handle **out)
+{
+    if (!p || !out) return mc_fail(nullptr, DQMC_ERR_INVALID, "dqmc_mc_create: null argument");
+    *out = nullptr;
+    if (p->n_sites < 1 || p->n_walkers < 1)
+        return mc_fail(nullptr, DQMC_ERR_INVALID, "dqmc_mc_create: n_sites and n_walkers must be >= 1");
+    if (p->n_sites > MAX_SITES)
+        return mc_fail(nullptr, DQMC_ERR_INVALID,
+                       "dqmc_mc_create: n_sites exceeds 16384 (the walker's spins must fit in LDS)");
+    if (p->z < 1 || p->z > MAX_Z)
+        return mc_fail(nullptr, DQMC_ERR_INVALID, "dqmc_mc_create: z must be in 1..8 (neighbours per site)");
+    if (p->n_bonds < 0 || p->series_capacity < 0)
+        return mc_fail(nullptr, DQMC_ERR_INVALID, "dqmc_mc_create: n_bonds and series_capacity must be >= 0");
+    if (!p->neighs || (p->n_bonds > 0 && !p->bonds))
+        return mc_fail(nullptr, DQMC_ERR_INVALID, "dqmc_mc_create: neighbour or bonds table missing");
+    const int N = p->n_sites, z = p->z, nb = p->n_bonds;
+    for (long i = 0; i < (long)z * N; ++i)
+        if (p->neighs[i] < 1 || p->neighs[i] > N)
+            return mc_fail(nullptr, DQMC_ERR_INVALID, "dqmc_mc_create: neighbour index out of range 1..n_sites");
+    for (long i = 0; i < 2L * nb; ++i)
+        if (p->bonds[i] < 1 || p->bonds[i] > N)
+            return mc_fail(nullptr, DQMC_ERR_INVALID, "dqmc_mc_create: bond index out of range 1..n_sites");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+        return mc_fail(nullptr, DQMC_ERR_NO_DEVICE, "dqmc_mc_create: no HIP device visible");
+    if (p->device_id < 0 || p->device_id >= ndev)
+        return mc_fail(nullptr, DQMC_ERR_INVALID, "dqmc_mc_create: device_id out of range");
+
+    dqmc_mc_handle *h = new dqmc_mc_handle();
+    h->N = N;
+    h->z = z;
+    h->W = p->n_walkers;
+    h->nw = (N + 31) / 32;
+    h->cap = p->series_capacity;
+    h->n_bonds = nb;
+    h->device = p->device_id;
+    h->nbr_h.resize((size_t)N * z);
+    for (int i = 0; i < N; ++i)
+        for (int k = 0; k < z; ++k) h->nbr_h[(size_t)i * z + k] = (int)p->neighs[(size_t)i * z + k] - 1;
+    h->bonds_h.resize((size_t)2 * nb);
+    for (int b = 0; b < nb; ++b) {  // Julia's n_bonds x 2 column-major -> pairs
+        h->bonds_h[2 * b] = (int)p->bonds[b] - 1;
+        h->bonds_h[2 * b + 1] = (int)p->bonds[nb + b] - 1;
+    }
+    auto bail = [&](int rc) {
+        g_mc_create_error = h->err;
+        dqmc_mc_destroy(h);
+        return rc;
+    };
+    if (hipSetDevice(h->device) != hipSuccess || hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess)
+        return bail(mc_fail(h, DQMC_ERR_HIP, "dqmc_mc_create: cannot open the device"));
+    std::vector<int> nbr_pad((size_t)(N + 1) * MAX_Z, 0);
+    for (int i = 0; i < N; ++i)
+        for (int k = 0; k < z; ++k) nbr_pad[(size_t)i * MAX_Z + k] = h->nbr_h[(size_t)i * z + k];
+    DevState &d = h->d;
+    d.N = N;
+    d.W = h->W;
+    d.nw = h->nw;
+    d.cap = h->cap;
+    d.n_bonds = nb;
+    const size_t W = h->W;
+    int *nbr = nullptr, *bonds = nullptr;
+    int rc = 0;
+    if ((rc = mc_alloc(h, &nbr, nbr_pad.size())) || (rc = mc_alloc(h, &bonds, h->bonds_h.size())) ||
+        (rc = mc_alloc(h, &d.conf, (size_t)h->nw * W)) || (rc = mc_alloc(h, &d.key, W)) ||
+        (rc = mc_alloc(h, &d.draw, W)) || (rc = mc_alloc(h, &d.E, W)) || (rc = mc_alloc(h, &d.M, W)) ||
+        (rc = mc_alloc(h, &d.thr, (size_t)MAX_Z * W)) || (rc = mc_alloc(h, &d.sE, W)) ||
+        (rc = mc_alloc(h, &d.sE2, W)) || (rc = mc_alloc(h, &d.sM, W)) || (rc = mc_alloc(h, &d.sM2, W)) ||
+        (rc = mc_alloc(h, &d.n_meas, W)) || (rc = mc_alloc(h, &d.prop, W)) || (rc = mc_alloc(h, &d.acc, W)) ||
+        (rc = mc_alloc(h, &d.n_series, W)) || (rc = mc_alloc(h, &d.serE, (size_t)h->cap * W)) ||
+        (rc = mc_alloc(h, &d.serM, (size_t)h->cap * W)))
+        return bail(rc);
+    d.nbr = nbr;
+    d.bonds = bonds;
+    if (hipMemcpyAsync(nbr, nbr_pad.data(), nbr_pad.size() * 4, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
+        (nb && hipMemcpyAsync(bonds, h->bonds_h.data(), h->bonds_h.size() * 4, hipMemcpyHostToDevice, h->stream) !=
+                   hipSuccess))
+        return bail(mc_fail(h, DQMC_ERR_HIP, "dqmc_mc_create: table upload failed"));
+    // the whole spin array of a workgroup in LDS above the 64 KiB default
+    const size_t lds = (size_t)h->nw * WAVE * 4;
+    const void *kernels[] = {(const void *)ising_sweep_kernel<1>, (const void *)ising_sweep_kernel<2>,
+                             (const void *)ising_sweep_kernel<3>, (const void *)ising_sweep_kernel<4>,
+                             (const void *)ising_sweep_kernel<5>, (const void *)ising_sweep_kernel<6>,
+                             (const void *)ising_sweep_kernel<7>, (const void *)ising_sweep_kernel<8>,
+                             (const void *)ising_observables_kernel};
+    for (const void *k : kernels)
+        if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+            return bail(mc_fail(h, DQMC_ERR_HIP, "dqmc_mc_create: cannot reserve LDS for the spins"));
+    if (hipStreamSynchronize(h->stream) != hipSuccess)
+        return bail(mc_fail(h, DQMC_ERR_HIP, "dqmc_mc_create: device initialisation failed"));
+    *out = h;
+    return DQMC_OK;
+}
+
+int dqmc_mc_destroy(dqmc_mc_handle *h)
+{
+    if (!h) return DQMC_OK;
+    if (h->stream) {
+        (void)hipSetDevice(h->device);
+        (void)hipStreamSynchronize(h->stream);
+    }
+    for (void *p : h->allocs) (void)hipFree(p);
+    if (h->stream) (void)hipStreamDestroy(h->stream);
+    delete h;
+    return DQMC_OK;
+}
+
+int dqmc_mc_set_beta(dqmc_mc_handle *h, int32_t walker, double beta)
+{
+    if (int rc = mc_walker(h, walker, "dqmc_mc_set_beta")) return rc;
+    if (!std::isfinite(beta) || beta < 0.0)
+        return mc_fail(h, DQMC_ERR_INVALID, "dqmc_mc_set_beta: beta must be finite and >= 0");
+    MCHK(hipSetDevice(h->device));
+    double thr[MAX_Z];
+    for (int k = 1; k <= MAX_Z; ++k) thr[k - 1] = exp(-beta * (2.0 * k));  // exp(-beta dE), MC.jl:327
+    MCHK(hipMemcpy2DAsync(h->d.thr + walker, (size_t)h->W * sizeof(double), thr, sizeof(double), sizeof(double), MAX_Z,
+                          hipMemcpyHostToDevice, h->stream));
+    MCHK(hipStreamSynchronize(h->stream));
+    return DQMC_OK;
+}
+
+int dqmc_mc_seed(dqmc_mc_handle *h, int32_t walker, uint64_t seed)
+{
+    if (int rc = mc_walker(h, walker, "dqmc_mc_seed")) return rc;
+    MCHK(hipSetDevice(h->device));
+    if (int rc = mc_put<unsigned long long>(h, h->d.key, 0, walker, seed)) return rc;
+    return mc_put<unsigned long long>(h, h->d.draw, 0, walker, 0ull);
+}
+
+int dqmc_mc_rand_conf(dqmc_mc_handle *h, int32_t walker)
+{
+    if (!h) return mc_fail(nullptr, DQMC_ERR_INVALID, "dqmc_mc_rand_conf: null handle");
+    if (walker >= h->W) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_mc_rand_conf: walker out of range");
+    MCHK(hipSetDevice(h->device));
+    const int grid = walker >= 0 ? 1 : (h->W + WAVE - 1) / WAVE;
+    hipLaunchKernelGGL(ising_rand_conf_kernel, dim3(grid), dim3(WAVE), 0, h->stream, h->d, walker);
+    MCHK(hipGetLastError());
+    if (int rc = mc_launch_observables(h, walker)) return rc;
+    MCHK(hipStreamSynchronize(h->stream));
+    return DQMC_OK;
+}
+
+int dqmc_mc_set_conf(dqmc_mc_handle *h, int32_t walker, const int8_t *conf)
+{
+    if (int rc = mc_walker(h, walker, "dqmc_mc_set_conf")) return rc;
+    if (!conf) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_mc_set_conf: null conf");
+    std::vector<unsigned int> words(h->nw, 0u);
+    for (int i = 0; i < h->N; ++i) {
+        if (conf[i] != 1 && conf[i] != -1) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_mc_set_conf: spins must be +-1");
+        if (conf[i] == 1) words[i >> 5] |= 1u << (i & 31);
+    }
+    MCHK(hipSetDevice(h->device));
+    MCHK(hipMemcpy2DAsync(h->d.conf + walker, (size_t)h->W * 4, words.data(), 4, 4, h->nw, hipMemcpyHostToDevice,
+                          h->stream));
+    if (int rc = mc_launch_observables(h, walker)) return rc;
+    MCHK(hipStreamSynchronize(h->stream));
+    return DQMC_OK;
+}
+
+static int mc_words(dqmc_mc_handle *h, int32_t walker, std::vector<unsigned int> &words)
+{
+    words.assign(h->nw, 0u);
+    MCHK(hipSetDevice(h->device));
+    MCHK(hipMemcpy2DAsync(words.data(), 4, h->d.conf + walker, (size_t)h->W * 4, 4, h->nw, hipMemcpyDeviceToHost,
+                          h->stream));
+    MCHK(hipStreamSynchronize(h->stream));
+    return DQMC_OK;
+}
+
+int dqmc_mc_get_conf(dqmc_mc_handle *h, int32_t walker, int8_t *conf)
+{
+    if (int rc = mc_walker(h, walker, "dqmc_mc_get_conf")) return rc;
+    if (!conf) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_mc_get_conf: null conf");
+    std::vector<unsigned int> words;
+    if (int rc = mc_words(h, walker, words)) return rc;
+    for (int i = 0; i < h->N; ++i) conf[i] = (words[i >> 5] >> (i & 31)) & 1u ? 1 : -1;
+    return DQMC_OK;
+}
+
+int dqmc_mc_get_conf_bits(dqmc_mc_handle *h, int32_t walker, uint64_t *chunks)
+{
+    if (int rc = mc_walker(h, walker, "dqmc_mc_get_conf_bits")) return rc;
+    if (!chunks) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_mc_get_conf_bits: null chunks");
+    std::vector<unsigned int> words;
+    if (int rc = mc_words(h, walker, words)) return rc;
+    const int nc = (h->N + 63) / 64;
+    for (int c = 0; c < nc; ++c)
+        chunks[c] = (uint64_t)words[2 * c] | (2 * c + 1 < h->nw ? (uint64_t)words[2 * c + 1] << 32 : 0ull);
+    return DQMC_OK;
+}
+
+int dqmc_mc_sweep(dqmc_mc_handle *h, int32_t n_sweeps, int64_t first_sweep_index, int64_t thermalization,
+                  int32_t measure_rate)
+{
+    if (!h) return mc_fail(nullptr, DQMC_ERR_INVALID, "dqmc_mc_sweep: null handle");
+    if (n_sweeps < 0 || measure_rate < 1 || first_sweep_index < 1)
+        return mc_fail(h, DQMC_ERR_INVALID, "dqmc_mc_sweep: n_sweeps >= 0, first_sweep_index >= 1, measure_rate >= 1");
+    MCHK(hipSetDevice(h->device));
+    const size_t lds = (size_t)h->nw * WAVE * 4;
+    const int grid = (h->W + WAVE - 1) / WAVE;
+    const double per_sweep = (double)h->N * std::max((double)h->W, BUDGET_WALKERS);
+    const int chunk = (int)std::max(1.0, std::min((double)n_sweeps, std::floor(LAUNCH_BUDGET / per_sweep)));
+    for (int done = 0; done < n_sweeps;) {
+        const int n = std::min(chunk, n_sweeps - done);
+        const long long first = first_sweep_index + done;
+        switch (h->z) {
+#define MC_CASE(Z)                                                                                                  \
+    case Z:                                                                                                         \
+        hipLaunchKernelGGL(ising_sweep_kernel<Z>, dim3(grid), dim3(WAVE), lds, h->stream, h->d,                    \
+                           (const int4 *)h->d.nbr, n, first,                                                       \
+                           (long long)thermalization, (int)measure_rate);                                          \
+        break;
+            MC_CASE(1) MC_CASE(2) MC_CASE(3) MC_CASE(4) MC_CASE(5) MC_CASE(6) MC_CASE(7) MC_CASE(8)
+#undef MC_CASE
+        }
+        MCHK(hipGetLastError());
+        done += n;
+    }
+    MCHK(hipStreamSynchronize(h->stream));
+    return DQMC_OK;
+}
+
+int dqmc_mc_get_stats(dqmc_mc_handle *h, int32_t walker, dqmc_mc_stats *out)
+{
+    if (int rc = mc_walker(h, walker, "dqmc_mc_get_stats")) return rc;
+    if (!out) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_mc_get_stats: null out");
+    MCHK(hipSetDevice(h->device));
+    const DevState &d = h->d;
+    int E = 0, M = 0;
+    unsigned long long draw = 0;
+    long long n_meas = 0, prop = 0, acc = 0, n_series = 0;
+    int rc = 0;
+    if ((rc = mc_get(h, d.E, 0, walker, &E)) || (rc = mc_get(h, d.M, 0, walker, &M)) ||
+        (rc = mc_get(h, d.draw, 0, walker, &draw)) || (rc = mc_get(h, d.sE, 0, walker, &out->sum_E)) ||
+        (rc = mc_get(h, d.sE2, 0, walker, &out->sum_E2)) || (rc = mc_get(h, d.sM, 0, walker, &out->sum_absM)) ||
+        (rc = mc_get(h, d.sM2, 0, walker, &out->sum_M2)) || (rc = mc_get(h, d.n_meas, 0, walker, &n_meas)) ||
+        (rc = mc_get(h, d.prop, 0, walker, &prop)) || (rc = mc_get(h, d.acc, 0, walker, &acc)) ||
+        (rc = mc_get(h, d.n_series, 0, walker, &n_series)))
+        return rc;
+    out->energy = E;
+    out->magnetization = M;
+    out->n_meas = n_meas;
+    out->prop_local = prop;
+    out->acc_local = acc;
+    out->uniforms_used = draw;
+    out->n_series = n_series;
+    return DQMC_OK;
+}
+
+int dqmc_mc_get_series(dqmc_mc_handle *h, int32_t walker, int32_t *energy, int32_t *abs_magnetization,
+                       int64_t *n_recorded)
+{
+    if (int rc = mc_walker(h, walker, "dqmc_mc_get_series")) return rc;
+    if (!n_recorded) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_mc_get_series: null n_recorded");
+    MCHK(hipSetDevice(h->device));
+    long long n = 0;
+    if (int rc = mc_get(h, h->d.n_series, 0, walker, &n)) return rc;
+    *n_recorded = n;
+    if (n > 0 && energy)
+        MCHK(hipMemcpy2DAsync(energy, 4, h->d.serE + walker, (size_t)h->W * 4, 4, n, hipMemcpyDeviceToHost, h->stream));
+    if (n > 0 && abs_magnetization)
+        MCHK(hipMemcpy2DAsync(abs_magnetization, 4, h->d.serM + walker, (size_t)h->W * 4, 4, n, hipMemcpyDeviceToHost,
+                              h->stream));
+    MCHK(hipStreamSynchronize(h->stream));
+    return DQMC_OK;
+}
+
+int dqmc_mc_reset_accumulators(dqmc_mc_handle *h)
+{
+    if (!h) return mc_fail(nullptr, DQMC_ERR_INVALID, "dqmc_mc_reset_accumulators: null handle");
+    MCHK(hipSetDevice(h->device));
+    const size_t W = h->W;
+    MCHK(hipMemsetAsync(h->d.sE, 0, W * 8, h->stream));
+    MCHK(hipMemsetAsync(h->d.sE2, 0, W * 8, h->stream));
+    MCHK(hipMemsetAsync(h->d.sM, 0, W * 8, h->stream));
+    MCHK(hipMemsetAsync(h->d.sM2, 0, W * 8, h->stream));
+    MCHK(hipMemsetAsync(h->d.n_meas, 0, W * 8, h->stream));
+    MCHK(hipMemsetAsync(h->d.n_series, 0, W * 8, h->stream));
+    MCHK(hipStreamSynchronize(h->stream));
+    return DQMC_OK;
+}
+
+int dqmc_mc_synchronize(dqmc_mc_handle *h)
+{
+    if (!h) return mc_fail(nullptr, DQMC_ERR_INVALID, "dqmc_mc_synchronize: null handle");
+    MCHK(hipSetDevice(h->device));
+    MCHK(hipStreamSynchronize(h->stream));
+    return DQMC_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,231 @@
+"""The classical MC flavor (src/flavors/MC/MC.jl) with the IsingModel (src/models/Ising/IsingModel.jl,
+measurements.jl), `n_walkers` independent Markov chains batched on one device (csrc/ising.hip).
+
+Walker w draws from the Philox4x32-10 stream keyed by `seed + first_walker + w`: draws 0..N-1 give the initial
+configuration (rand(MC, m)), the Metropolis uniforms follow.  The host holds the model, the loop control and
+finish!; every site update runs on the device."""
+import ctypes as C
+import math
+import time
+
+import numpy as np
+
+from ._lib import DQMCError, ERR_INVALID, McParams, McStats, lib
+from .configurations import CompressedConf
+from .lattices import Chain, CubicLattice, SquareLattice
+
+IsingTc = 1.0 / (0.5 * math.log(1.0 + math.sqrt(2.0)))  # IsingModel.jl:7
+
+
+def _choose_lattice(dims, L):
+    """choose_lattice(IsingModel, dims, L) (IsingModel.jl:26-35)"""
+    if dims == 1:
+        return Chain(L)
+    if dims == 2:
+        return SquareLattice(L)
+    return CubicLattice(dims, L)
+
+
+class IsingModel:
+    """IsingModel(; dims, L) (IsingModel.jl:17-22); any project lattice may be given as `l`."""
+
+    def __init__(self, dims=None, L=None, l=None):
+        if l is None:
+            if dims is None or L is None:
+                raise ValueError("IsingModel needs dims and L, or a lattice l")
+            l = _choose_lattice(dims, L)
+        self.l = l
+        self.L = L if L is not None else getattr(l, "L", len(l))
+        self.dims = dims if dims is not None else getattr(l, "dim", 2 if hasattr(l, "lattice") else 1)
+
+    def __len__(self):
+        return len(self.l)
+
+    def energy(self, conf):
+        """energy(mc, m, conf) (IsingModel.jl:149-186): -sum over the undirected bonds table, for any integer spins"""
+        c = np.asarray(conf).reshape(-1, order="F").astype(np.int64)
+        b = np.asarray(self.l.bonds, dtype=np.int64)[:, :2] - 1
+        return float(-np.sum(c[b[:, 0]] * c[b[:, 1]]))
+
+    def propose_local(self, i, conf):
+        """propose_local(mc, m, i, conf) (IsingModel.jl:85-101): delta_E = 2 conf[i] sum_{j in neighs[:, i]} conf[j],
+        i 1-based"""
+        c = np.asarray(conf).reshape(-1, order="F").astype(np.int64)
+        return 2.0 * float(c[i - 1]) * float(np.sum(c[np.asarray(self.l.neighs)[:, i - 1] - 1]))
+
+
+class MC:
+    """MC(model; beta | T, ...) (MC.jl:16-80) for `n_walkers` chains.  `beta` may be a sequence of n_walkers values
+    (one temperature per walker).  Global (Wolff) moves are refused: the reference's global_move cannot run
+    (IsingModel.jl:137 assigns to an undefined `model`) and its rand(1:N) draws have no place in the walker streams."""
+
+    def __init__(self, model, beta=None, T=None, n_walkers=1, seed=123, first_walker=0, thermalization=0, sweeps=1000,
+                 measure_rate=1, print_rate=1000, global_moves=False, global_rate=5, device_id=0, series_capacity=0):
+        if global_moves:
+            raise NotImplementedError(
+                "MC(global_moves=True): the reference's Wolff global_move cannot run (IsingModel.jl:137 uses the "
+                "undefined `model`) and its rand(1:N) draws have no defined place in the walkers' Philox streams")
+        if (beta is None) == (T is None):
+            raise ValueError("MC needs exactly one of beta and T")
+        if T is not None:
+            beta = (1.0 / np.asarray(T, dtype=float)) if np.ndim(T) else 1.0 / float(T)
+        betas = np.broadcast_to(np.asarray(beta, dtype=float), (n_walkers,)).copy()
+        if not np.all(np.isfinite(betas)) or np.any(betas < 0):
+            raise ValueError("beta must be finite and >= 0")
+        if measure_rate < 1:
+            raise ValueError("measure_rate must be >= 1")
+        self.model = model
+        self.N = len(model.l)
+        self.n_walkers = n_walkers
+        self.betas = betas
+        self.beta = float(betas[0]) if np.all(betas == betas[0]) else betas
+        self.seeds = [seed + first_walker + w for w in range(n_walkers)]
+        self.thermalization, self.sweeps, self.measure_rate = thermalization, sweeps, measure_rate
+        self.print_rate, self.global_moves, self.global_rate = print_rate, global_moves, global_rate
+        self.last_sweep = 0
+        self.series_capacity = series_capacity
+        self._neighs = np.asfortranarray(np.asarray(model.l.neighs, dtype=np.int64))
+        self._bonds = np.asfortranarray(np.asarray(model.l.bonds, dtype=np.int64)[:, :2])
+        p = McParams(n_sites=self.N, z=self._neighs.shape[0], n_walkers=n_walkers, device_id=device_id,
+                     n_bonds=self._bonds.shape[0], series_capacity=series_capacity,
+                     neighs=self._neighs.ctypes.data_as(C.POINTER(C.c_int64)),
+                     bonds=self._bonds.ctypes.data_as(C.POINTER(C.c_int64)))
+        h = C.c_void_p()
+        rc = lib().dqmc_mc_create(C.byref(p), C.byref(h))
+        if rc != 0:
+            msg = lib().dqmc_mc_last_error(None)
+            raise DQMCError(rc, msg.decode() if msg else "")
+        self._h = h
+        for w in range(n_walkers):
+            self._c(lib().dqmc_mc_seed(self._h, w, self.seeds[w]))
+            self._c(lib().dqmc_mc_set_beta(self._h, w, float(betas[w])))
+        self._c(lib().dqmc_mc_rand_conf(self._h, -1))  # mc.conf = rand(MC, m); init! (MC.jl:61,74)
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            lib().dqmc_mc_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _c(self, rc):
+        if rc != 0:
+            msg = lib().dqmc_mc_last_error(self._h)
+            raise DQMCError(rc, msg.decode() if msg else "")
+
+    # ---- state
+    def seed(self, walker, seed):
+        """key the walker's stream with `seed`, cursor at draw 0 (the configuration stays)"""
+        self._c(lib().dqmc_mc_seed(self._h, walker, seed))
+        self.seeds[walker] = seed
+
+    def set_beta(self, walker, beta):
+        self._c(lib().dqmc_mc_set_beta(self._h, walker, float(beta)))
+        self.betas[walker] = float(beta)
+
+    def rand_conf(self, walker=-1):
+        self._c(lib().dqmc_mc_rand_conf(self._h, walker))
+
+    def conf(self, walker=0):
+        out = np.zeros(self.N, dtype=np.int8)
+        self._c(lib().dqmc_mc_get_conf(self._h, walker, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def set_conf(self, walker, conf):
+        c = np.ascontiguousarray(np.asarray(conf).reshape(-1, order="F"), dtype=np.int8)
+        if c.size != self.N:
+            raise DQMCError(ERR_INVALID, "set_conf: expected %d spins" % self.N)
+        self._c(lib().dqmc_mc_set_conf(self._h, walker, c.ctypes.data_as(C.c_void_p)))
+
+    def conf_bits(self, walker=0):
+        """compress(mc, m, conf) = BitArray(conf .== 1) as CompressedConf (shape (N, 1), decompress gives conf(w))"""
+        out = np.zeros((self.N + 63) // 64, dtype=np.uint64)
+        self._c(lib().dqmc_mc_get_conf_bits(self._h, walker, out.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return CompressedConf(out, (self.N, 1))
+
+    def stats(self, walker=0):
+        st = McStats()
+        self._c(lib().dqmc_mc_get_stats(self._h, walker, C.byref(st)))
+        return st
+
+    def energy(self, walker=0):
+        """model.energy[] of the walker, tracked on the device"""
+        return float(self.stats(walker).energy)
+
+    def uniforms_used(self, walker=0):
+        return int(self.stats(walker).uniforms_used)
+
+    # ---- the loop
+    def sweep(self, n=1):
+        """n x sweep(mc) with run!'s measurement rule, continuing from last_sweep"""
+        if n > 0:
+            self._c(lib().dqmc_mc_sweep(self._h, n, self.last_sweep + 1, self.thermalization, self.measure_rate))
+            self.last_sweep += n
+
+    def run(self, verbose=False, recorder=None, sweeps=None, thermalization=None):
+        """run!(mc) (MC.jl:190-315) for every walker, resuming after last_sweep; a recorder gets
+        push(mc, i) after each sweep i > thermalization (of walker 0, ConfigRecorder keeps every rate-th)"""
+        if sweeps is not None:
+            self.sweeps = sweeps
+        if thermalization is not None:
+            self.thermalization = thermalization
+        total = self.thermalization + self.sweeps
+        t0 = time.time()
+        while self.last_sweep < total:
+            stop = total
+            if recorder is not None and getattr(recorder, "rate", None):
+                nxt = max(self.last_sweep + 1, self.thermalization + 1)
+                r = recorder.rate
+                stop = min(total, ((nxt + r - 1) // r) * r)
+            elif verbose and self.print_rate:
+                stop = min(total, (self.last_sweep // self.print_rate + 1) * self.print_rate)
+            self.sweep(stop - self.last_sweep)
+            i = self.last_sweep
+            if recorder is not None and i > self.thermalization:
+                recorder.push(self, i)
+            if verbose and self.print_rate and i % self.print_rate == 0:
+                st = self.stats(0)
+                print("\t%d\n\t\tsweep dur: %.3fs\n\t\tacc rate (local) : %.1f%%" %
+                      (i, (time.time() - t0) / self.print_rate, 100.0 * st.acc_local / max(st.prop_local, 1)))
+                t0 = time.time()
+        return True
+
+    def reset_accumulators(self):
+        self._c(lib().dqmc_mc_reset_accumulators(self._h))
+
+    def synchronize(self):
+        self._c(lib().dqmc_mc_synchronize(self._h))
+
+    # ---- results
+    def analysis(self, walker=0):
+        """MCAnalysis (MC.jl:1-11) of one walker"""
+        st = self.stats(walker)
+        return {"acc_rate": st.acc_local / st.prop_local if st.prop_local else 0.0, "prop_local": int(st.prop_local),
+                "acc_local": int(st.acc_local), "acc_rate_global": 0.0, "prop_global": 0, "acc_global": 0}
+
+    def measurements(self, walker=0):
+        """finish! of IsingMagnetizationMeasurement and IsingEnergyMeasurement (measurements.jl:13-94) on the sums:
+        {"Magn": {M, M2, m, chi}, "Energy": {E, E2, e, C}} (means over the walker's measurements)"""
+        st = self.stats(walker)
+        n = st.n_meas
+        if n == 0:
+            raise DQMCError(ERR_INVALID, "measurements: no measurement has been taken")
+        beta, invN = float(self.betas[walker]), 1.0 / self.N
+        E, E2, M, M2 = st.sum_E / n, st.sum_E2 / n, st.sum_absM / n, st.sum_M2 / n
+        return {"Magn": {"M": M, "M2": M2, "m": M * invN, "chi": beta * invN * (M2 - M * M)},
+                "Energy": {"E": E, "E2": E2, "e": E * invN, "C": beta * beta * invN * (E2 - E * E)},
+                "n_meas": int(n)}
+
+    def series(self, walker=0):
+        """per-measurement (E, |M|) of the walker as recorded (at most series_capacity entries)"""
+        cap = self.series_capacity
+        e = np.zeros(max(cap, 1), dtype=np.int32)
+        m = np.zeros(max(cap, 1), dtype=np.int32)
+        n = C.c_int64()
+        self._c(lib().dqmc_mc_get_series(self._h, walker, e.ctypes.data_as(C.POINTER(C.c_int32)),
+                                         m.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(n)))
+        return e[:n.value].copy(), m[:n.value].copy()
