@@ -155,7 +155,7 @@ def test_cfg4_repulsive_shape(gpu, O):
 
 def test_cfg5_shape_n576(gpu, O):
     """BASELINE config 5 lattice (24x24, n=576, dtau=0.05) at a short beta: exercises the n > 256
-    kernel paths (streaming QR, LDS-slab TRSM, 8-site sweep chunks)"""
+    kernel paths (streaming QR, LDS-slab TRSM, 64-site sweep chunks)"""
     model = gpu.HubbardModelAttractive(24, 2)
     mc = gpu.DQMC(model, beta=1.0, delta_tau=0.05, n_walkers=1, seed=7)
     o = O.OracleDQMC(24, "attractive", beta=1.0, delta_tau=0.05)

@@ -231,3 +231,103 @@ def test_interface_consistency(gpu):
     st = mc.stats(0)
     assert st.n_meas == 0 and st.n_series == 0 and st.sum_E == 0.0 and st.prop_local == 110 * 256
     mc.close()
+
+
+# ---- the kernel's limits: the N ceiling (512 LDS spin words per lane), every z = 1..8, the threshold edges
+def _check_against_restatement(O, mc, l, betas, seed, therm, sweeps, rate=1, walkers=None):
+    for w in (range(len(betas)) if walkers is None else walkers):
+        ref, c = restate(O, l, float(betas[w]), seed + w, therm, sweeps, rate)
+        assert _stats(mc, w) == ref, w
+        assert np.array_equal(mc.conf(w), c), w
+
+
+@pytest.mark.parametrize("name,make", [
+    ("square128_N16384_z4", lambda g: g.SquareLattice(128)),
+    ("cubic4d_11_N14641_z8", lambda g: g.CubicLattice(4, 11)),   # 14641 = 457 words of 32 spins + 17
+])
+def test_the_site_ceiling_matches_the_restatement(gpu, O, name, make):
+    """N = 16384 (the most the LDS holds) and a 4D lattice just below it whose last spin word is partial, three walkers
+    at different betas, the run split over two sweep calls"""
+    l = make(gpu)
+    assert len(l) <= 16384
+    therm, sweeps, seed = 2, 3, 4711
+    betas = [0.2, 0.44, 0.7]
+    mc = gpu.MC(gpu.IsingModel(l=l), beta=betas, n_walkers=3, seed=seed, thermalization=therm, sweeps=sweeps)
+    mc.sweep(2)
+    mc.sweep(therm + sweeps - 2)
+    _check_against_restatement(O, mc, l, betas, seed, therm, sweeps)
+    mc.close()
+
+
+class _RingTable:
+    """N sites (0-based i) with the neighbours i ^ 1 (z = 1) or i +- 1..(z - 1)/2 and i + N/2 (odd z), 1-based as the
+    project's lattices; the bonds are the undirected edges of that table"""
+
+    def __init__(self, N, z):
+        assert N % 2 == 0 and (z == 1 or (z % 2 == 1 and N // 2 > (z - 1) // 2))
+        i = np.arange(N)
+        if z == 1:
+            rows = [i ^ 1]
+        else:
+            rows = [(i + s * d) % N for d in range(1, (z - 1) // 2 + 1) for s in (1, -1)] + [(i + N // 2) % N]
+        self.sites = N
+        self.neighs = np.vstack(rows).astype(np.int64) + 1
+        edges = sorted({(min(a, b), max(a, b)) for r in rows for a, b in zip(i, r)})
+        assert len(edges) * 2 == N * z  # every neighbour distinct: each edge seen once from each end
+        self.bonds = np.array(edges, dtype=np.int64) + 1
+
+    def __len__(self):
+        return self.sites
+
+
+@pytest.mark.parametrize("N,z", [(50, 1), (70, 3), (94, 5), (1000, 7)])
+def test_odd_z_tables_match_the_restatement(gpu, O, N, z):
+    """z = 1, 3, 5, 7 (the instantiations of ising_sweep_kernel<Z> no project lattice selects), N even and not a
+    multiple of 32 (a partial last spin word)"""
+    l = _RingTable(N, z)
+    model = gpu.IsingModel(l=l)
+    therm, sweeps, rate, seed = 4, 21, 2, 606
+    betas = [0.15, 0.4, 0.9]
+    mc = gpu.MC(model, beta=betas, n_walkers=3, seed=seed, thermalization=therm, sweeps=sweeps, measure_rate=rate)
+    mc.sweep(9)
+    mc.sweep(therm + sweeps - 9)
+    _check_against_restatement(O, mc, l, betas, seed, therm, sweeps, rate)
+    for w in range(3):
+        assert mc.stats(w).energy == model.energy(mc.conf(w))
+    mc.close()
+
+
+def test_z8_many_walkers_matches_the_restatement(gpu, O):
+    """CubicLattice(4, 4): z = 8, every entry of a padded neighbour row and all eight thresholds, 300 walkers"""
+    l = gpu.CubicLattice(4, 4)
+    assert l.neighs.shape == (8, 256)
+    W, therm, sweeps, rate, seed = 300, 5, 20, 2, 8080
+    betas = np.linspace(0.02, 0.4, W)
+    mc = gpu.MC(gpu.IsingModel(l=l), beta=betas, n_walkers=W, seed=seed, thermalization=therm, sweeps=sweeps,
+                measure_rate=rate)
+    mc.sweep(7)
+    mc.sweep(therm + sweeps - 7)
+    _check_against_restatement(O, mc, l, betas, seed, therm, sweeps, rate, walkers=(0, 1, 63, 64, 150, 255, 299))
+    mc.close()
+
+
+@pytest.mark.parametrize("name,make", [
+    ("ring70_z3", lambda g: _RingTable(70, 3)),
+    ("square8_z4", lambda g: g.SquareLattice(8)),
+    ("cubic4d_4_z8", lambda g: g.CubicLattice(4, 4)),
+])
+def test_threshold_edges_match_the_restatement(gpu, O, name, make):
+    """beta = 0: every proposal accepted, a uniform still drawn for every dE > 0.  beta = 185: exp(-2 beta k) is normal
+    for k = 1, subnormal for k = 2 (exp(-740)) and 0 from k = 3 on; beta = 1000: every threshold is 0, so only dE <= 0 is
+    accepted, and the draws for dE > 0 are still counted"""
+    l = make(gpu)
+    therm, sweeps, seed = 3, 8, 99
+    betas = [0.0, 185.0, 1000.0]
+    mc = gpu.MC(gpu.IsingModel(l=l), beta=betas, n_walkers=3, seed=seed, thermalization=therm, sweeps=sweeps)
+    mc.sweep(5)
+    mc.sweep(therm + sweeps - 5)
+    _check_against_restatement(O, mc, l, betas, seed, therm, sweeps)
+    st = mc.stats(0)
+    assert st.acc_local == st.prop_local == (therm + sweeps) * len(l)
+    assert st.uniforms_used > len(l)
+    mc.close()

@@ -22,6 +22,23 @@ def test_vmul_variants(gpu, n, batch, ta, tb):
         assert relerr(C[i], ref) < 1e-13
 
 
+@pytest.mark.parametrize("n,batch", [(257, 2), (300, 1), (600, 2), (1024, 1)])
+@pytest.mark.parametrize("ta,tb", [(0, 0), (0, 1), (1, 0), (1, 1)])
+def test_vmul_variants_n_above_256(gpu, n, batch, ta, tb):
+    """n > 256, off and on the tile grid up to the ceiling: every entry within the dot product's error bound
+    |C - ref| <= 2 n eps (|op(A)| |op(B)|), which a dropped or doubled k-term in any entry breaks (a max-norm relative
+    error lets a wrong small entry through)"""
+    rng = np.random.default_rng(n + 2 * ta + tb)
+    A = rng.standard_normal((batch, n, n))
+    B = rng.standard_normal((batch, n, n))
+    C = gpu.vmul(A, B, bool(ta), bool(tb))
+    eps = np.finfo(np.float64).eps
+    for i in range(batch):
+        opA, opB = (A[i].T if ta else A[i]), (B[i].T if tb else B[i])
+        bound = 2 * n * eps * (np.abs(opA) @ np.abs(opB))
+        assert np.all(np.abs(C[i] - opA @ opB) <= bound), (i, (np.abs(C[i] - opA @ opB) / bound).max())
+
+
 def test_vmul_layout_asymmetric(gpu):
     """A = I against an asymmetric B catches a transposed accumulator map"""
     n = 32
@@ -69,7 +86,7 @@ def test_udt_contracts(gpu, O, n, apply_pivot):
             assert relerr(U[i], Uo) < 1e-9
 
 
-@pytest.mark.parametrize("n,batch", [(320, 3), (576, 2), (600, 1)])
+@pytest.mark.parametrize("n,batch", [(257, 2), (320, 3), (576, 2), (600, 1), (1024, 1)])
 def test_udt_panel_kernel_n_above_256(gpu, O, n, batch):
     """n > 256: the panel (dlaqps-style) QR - one read of the trailing matrix per step, norms down-dated with the row of R
     and recomputed on cancellation - against the contracts of test/slice_matrices.jl:202-234, against the oracle's
@@ -177,7 +194,28 @@ def test_rdivp(gpu, O, n):
         assert relerr(out[i], ref) < 1e-10
 
 
-@pytest.mark.parametrize("n", [16, 64, 256])
+@pytest.mark.parametrize("n", [257, 291, 292, 574, 575, 1024])
+def test_rdivp_n_above_256(gpu, O, n):
+    """n > 256: the substitution on an LDS row slab (trsm_kernel<RS>) on both sides of each switch of its height
+    (64 rows up to 291, 32 up to 574, 16 up to 1024), with the non-identity pivots of a pivoted UDT: against the oracle,
+    and the residual Out triu(T) = A[:, pivot] in every entry, scaled by the column norms"""
+    rng = np.random.default_rng(n + 1)
+    X = rng.standard_normal((n, n))
+    _, _, T, piv = O.udt_pivot(X, False)
+    assert not np.array_equal(piv, np.arange(1, n + 1))
+    A = rng.standard_normal((2, n, n))
+    A[1] *= np.exp(rng.uniform(-10, 10, size=n))[:, None]   # graded rows
+    out = gpu.rdivp(A, np.stack([T] * 2), np.stack([piv] * 2))
+    Tu = np.triu(T)
+    for i in range(2):
+        ref = O.rdivp(A[i], T, piv)
+        assert relerr(out[i], ref) < 1e-10
+        Ap = A[i][:, piv - 1]
+        res = np.abs(out[i] @ Tu - Ap) / np.linalg.norm(Ap, axis=0)[None, :]
+        assert res.max() < 1e-12, res.max()
+
+
+@pytest.mark.parametrize("n", [16, 64, 256, 257, 324, 600, 1024])
 def test_calculate_greens_AVX(gpu, O, n):
     """G = [I + Ul Dl Tl (Ur Dr Tr)']^-1 (stack.jl:337-393) against the oracle and a direct inverse"""
     rng = np.random.default_rng(n + 2)
@@ -193,12 +231,15 @@ def test_calculate_greens_AVX(gpu, O, n):
         args.append((Ul, Dl, Tl, Ur, Dr, Tr))
     stack = lambda k: np.stack([a[k] for a in args])
     G = gpu.calculate_greens_AVX(stack(0), stack(1), stack(2), stack(3), stack(4), stack(5))
+    worst = 0.0
     for i, a in enumerate(args):
         Go = O.calculate_greens(*a)
+        worst = max(worst, relerr(G[i], Go))
         assert relerr(G[i], Go) < TOL
         Ul, Dl, Tl, Ur, Dr, Tr = a
         direct = np.linalg.inv(np.eye(n) + (Ul * Dl) @ Tl @ ((Ur * Dr) @ Tr).T)
         assert relerr(G[i], direct) < 1e-8
+    print("n = %d: worst rel |G - G_oracle| = %.3g" % (n, worst))
 
 
 def test_mfma_peak_probe(gpu):
