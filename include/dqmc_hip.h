@@ -410,6 +410,26 @@ int dqmc_mc_get_series(dqmc_mc_handle *h, int32_t walker, int32_t *energy, int32
                        int64_t *n_recorded);
 /* clear the measurement sums and series of every walker (MCAnalysis counters stay) */
 int dqmc_mc_reset_accumulators(dqmc_mc_handle *h);
+/* Wolff cluster move, global_move(mc, m::IsingModel, conf) (IsingModel.jl:104-140) with m.energy[] = energy(mc, m,
+ * conf).  Seed site min(N - 1, floor(u(m, 0) N)); the directed slot (i, k) (0-based site i, k < z) joins
+ * neighs[k, i] iff the two spins are equal and u(m, 1 + 8 i + k) < 1 - exp(-2 beta) (computed on the host by
+ * dqmc_mc_set_beta); the cluster (the sites reachable from the seed through such slots, one site at least) is flipped,
+ * accepted = cluster size > 1, then energy and magnetization are recomputed.  u(m, t) is Philox4x32-10 with key = the
+ * walker's seed and counter words (t, low32(m), 1, high32(m)); m counts the walker's cluster moves since
+ * dqmc_mc_seed.  The local stream (counter words 2 and 3 zero) is not touched. */
+/* mc.p.global_rate with mc.p.global_moves (MC.jl:22-23, 233-236): from now on dqmc_mc_sweep runs one global_move per
+ * walker after every sweep whose global index is a multiple of rate, before that sweep's measurement.  0 = off (the
+ * default); rate >= 0 */
+int dqmc_mc_set_global_rate(dqmc_mc_handle *h, int32_t rate);
+/* one global_move (IsingModel.jl:104-140) of one walker, or of every walker when walker < 0; it takes no measurement */
+int dqmc_mc_global_move(dqmc_mc_handle *h, int32_t walker);
+/* MCAnalysis prop_global / acc_global (MC.jl:1-11, 234-235) of one walker, with the sum of the cluster sizes and the
+ * move cursor m */
+typedef struct {
+    int64_t prop_global, acc_global, sum_cluster_size;
+    uint64_t moves_drawn;
+} dqmc_mc_global_stats;
+int dqmc_mc_get_global_stats(dqmc_mc_handle *h, int32_t walker, dqmc_mc_global_stats *out);
 int dqmc_mc_synchronize(dqmc_mc_handle *h);
 
 /* ---- instrumentation ------------------------------------------------------ */

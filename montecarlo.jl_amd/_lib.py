@@ -53,6 +53,11 @@ class McStats(C.Structure):
                 ("acc_local", C.c_int64), ("uniforms_used", C.c_uint64), ("n_series", C.c_int64)]
 
 
+class McGlobalStats(C.Structure):
+    _fields_ = [("prop_global", C.c_int64), ("acc_global", C.c_int64), ("sum_cluster_size", C.c_int64),
+                ("moves_drawn", C.c_uint64)]
+
+
 _dp = C.POINTER(C.c_double)
 _i64p = C.POINTER(C.c_int64)
 _H = C.c_void_p
@@ -152,6 +157,9 @@ SIGNATURES = {
     "dqmc_mc_get_series": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                            C.POINTER(C.c_int64)]),
     "dqmc_mc_reset_accumulators": (C.c_int, [_H]),
+    "dqmc_mc_set_global_rate": (C.c_int, [_H, C.c_int32]),
+    "dqmc_mc_global_move": (C.c_int, [_H, C.c_int32]),
+    "dqmc_mc_get_global_stats": (C.c_int, [_H, C.c_int32, C.POINTER(McGlobalStats)]),
     "dqmc_mc_synchronize": (C.c_int, [_H]),
     "dqmc_timing_enable": (C.c_int, [_H, C.c_int32]),
     "dqmc_timing_get": (C.c_int, [_H, _dp, _i64p]),

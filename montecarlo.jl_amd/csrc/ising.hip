@@ -13,6 +13,23 @@
 // Philox4x32-10 uniform (key = seed, counter = draw index, as orc_ising_run) and accepts iff u < thr[k], where
 // thr[k] = exp(-beta 2k) comes from the host's libm: no exp on the device, so every decision is bit-identical to the
 // oracle's.  E and M are tracked incrementally; a measurement adds E, E^2, |M|, M^2 to fp64 sums (exact integers).
+//
+// Wolff cluster move: global_move(mc, m::IsingModel, conf) (IsingModel.jl:104-140) with its evident intent
+// (m.energy[] = energy(mc, m, conf) where the reference writes the undefined `model`), defined on a stream of its own so
+// that it does not depend on the traversal order or on how the device parallelises the growth:
+//   u(m, t) = Philox4x32-10, key = the walker's seed, counter words (t, low32(m), 1, high32(m)), made into a uniform as
+//             philox_uniform does; m = the walker's move cursor (Wolff moves since dqmc_mc_seed).  Local draws have
+//             c2 = c3 = 0, so the two domains never overlap.
+//   seed site       min(N - 1, floor(u(m, 0) N))
+//   slot (i, k)     0-based site i, k < z: active iff s_i == s_{neighs[k, i]} and u(m, 1 + 8 i + k) < p_w
+//   cluster C       the sites reachable from the seed through active slots; every site of C is flipped (a one-site
+//                   cluster too), accepted = |C| > 1, then E is recomputed over the bonds table and M by popcount
+//   p_w             1 - exp(-2 beta) from the host's libm (dqmc_mc_set_beta), compared in fp64
+// Only the slots leaving C decide its boundary, (1 - p)^(aligned boundary bonds); the internal factor is the same before
+// and after the flip, so detailed balance holds.  Where neighs repeats a site (SquareLattice(2), short chains) the double
+// bond counts twice in the Metropolis dE, and two independent slot tests, 1 - (1 - p)^2, are its Fortuin-Kasteleyn
+// probability.  In run! order (MC.jl:230-242) the move of sweep i follows that sweep's local sweep and precedes its
+// measurement.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -44,6 +61,9 @@ struct DevState {
     unsigned long long *key, *draw;
     int *E, *M;
     double *thr;                    // [8][W], thr[k - 1] = exp(-beta 2k)
+    double *pw;                     // [W], 1 - exp(-2 beta): the cluster move's bond probability
+    unsigned long long *moves;      // [W], the cluster move cursor
+    long long *gprop, *gacc, *gsum; // [W], moves, moves with |C| > 1, sum of |C|
     double *sE, *sE2, *sM, *sM2;
     long long *n_meas, *prop, *acc, *n_series;
     int *serE, *serM;               // [cap][W]
@@ -57,7 +77,7 @@ __device__ __forceinline__ size_t at(int row, int W, int w) { return (size_t)row
 template <int Z>
 __global__ __launch_bounds__(WAVE) void ising_sweep_kernel(DevState s, const int4 *__restrict__ nbr, int n_sweeps,
                                                            long long first_sweep, long long thermalization,
-                                                           int measure_rate)
+                                                           int measure_rate, long long deferred_sweep)
 {
     extern __shared__ unsigned int sp[];
     const int lane = threadIdx.x;
@@ -116,7 +136,8 @@ __global__ __launch_bounds__(WAVE) void ising_sweep_kernel(DevState s, const int
         }
         sp[cw * WAVE + lane] = cur;
         const long long g = first_sweep + sw;  // global 1-based sweep index (MC.jl:262-283)
-        if (g > thermalization && g % measure_rate == 0) {
+        // the measurement of deferred_sweep (-1: none) follows that sweep's cluster move (ising_wolff_kernel)
+        if (g > thermalization && g % measure_rate == 0 && g != deferred_sweep) {
             const double e = (double)E, m = (double)(M < 0 ? -M : M);
             sE += e;
             sE2 += e * e;
@@ -185,12 +206,109 @@ __global__ __launch_bounds__(WAVE) void ising_observables_kernel(DevState s, int
     s.M[w] = M;
 }
 
+// LDS of the cluster move: spin words [nw], cluster bitset [nw], 8 counters, two frontier queues of N 16-bit site
+// indices (at N = 16384: 4 KiB + 64 KiB)
+constexpr int WOLFF_THREADS = 256;
+static inline size_t wolff_lds_bytes(int N, int nw) { return (size_t)(2 * nw + 8) * 4 + (size_t)4 * N; }
+
+// global_move (IsingModel.jl:104-140), as defined at the top of this file, one workgroup per walker (walker < 0:
+// workgroup b is walker b).  The cluster grows level by level: the frontier's slots are spread over the workgroup, a
+// slot draws only when its neighbour is aligned and not yet in the cluster, and the old value of an LDS atomicOr enqueues
+// every site exactly once, so the cluster is the same set whatever order the slots run in.  One barrier per level; the
+// level counters rotate over three words (level l reads ctr[l % 3], appends to ctr[(l + 1) % 3] and clears
+// ctr[(l + 2) % 3], which level l - 1 read before the barrier).  Then the cluster is flipped (XOR of the words), E is
+// recomputed over the bonds table as ising_observables_kernel does and M by popcount.  measure != 0: the measurement
+// of run! (MC.jl:262-283) for the sweep this move follows, as the sweep kernel takes it.
+__global__ __launch_bounds__(WOLFF_THREADS) void ising_wolff_kernel(DevState s, const int *__restrict__ nbr, int z,
+                                                                    int walker, int measure)
+{
+    extern __shared__ unsigned int sm[];
+    const int tid = threadIdx.x;
+    const int w = walker >= 0 ? walker : blockIdx.x;
+    const int N = s.N, nw = s.nw, W = s.W;
+    unsigned int *sp = sm, *cl = sm + nw, *ctr = sm + 2 * nw;  // ctr[0..2] level sizes, [3] |C|, [4] E, [5] up spins
+    unsigned short *q = (unsigned short *)(sm + 2 * nw + 8);   // q[0..N) and q[N..2N): frontiers of even / odd levels
+    const unsigned long long key = s.key[w], m = s.moves[w];
+    const unsigned int c1 = (unsigned int)m, c3 = (unsigned int)(m >> 32);
+    const double p = s.pw[w];
+    const int seed = min(N - 1, (int)(dqmc::philox4_uniform(key, 0u, c1, 1u, c3) * N));
+    for (int j = tid; j < nw; j += WOLFF_THREADS) {
+        sp[j] = s.conf[at(j, W, w)];
+        cl[j] = j == seed >> 5 ? 1u << (seed & 31) : 0u;
+    }
+    if (tid < 8) ctr[tid] = tid == 0 ? 1u : 0u;
+    if (tid == 0) q[0] = (unsigned short)seed;
+    __syncthreads();
+    const unsigned int s0 = (sp[seed >> 5] >> (seed & 31)) & 1u;  // every site of the cluster has the seed's spin
+
+    for (int lev = 0;; ++lev) {
+        const int n = (int)ctr[lev % 3];
+        if (n == 0) break;
+        const unsigned short *qc = q + (lev & 1) * N;
+        unsigned short *qn = q + ((lev & 1) ^ 1) * N;
+        if (tid == 0) ctr[(lev + 2) % 3] = 0u;
+        for (int t = tid; t < n * z; t += WOLFF_THREADS) {
+            const int e = t / z, k = t - e * z;
+            const int i = qc[e];
+            const int j = nbr[i * MAX_Z + k];
+            const unsigned int bit = 1u << (j & 31);
+            if (((sp[j >> 5] >> (j & 31)) & 1u) != s0 || (cl[j >> 5] & bit)) continue;
+            if (!(dqmc::philox4_uniform(key, 1u + 8u * (unsigned int)i + (unsigned int)k, c1, 1u, c3) < p)) continue;
+            if (atomicOr(&cl[j >> 5], bit) & bit) continue;  // another slot reached j first
+            qn[atomicAdd(&ctr[(lev + 1) % 3], 1u)] = (unsigned short)j;
+        }
+        __syncthreads();
+    }
+
+    unsigned int size = 0, up = 0;
+    for (int j = tid; j < nw; j += WOLFF_THREADS) {
+        const unsigned int c = cl[j], v = sp[j] ^ c;
+        sp[j] = v;
+        s.conf[at(j, W, w)] = v;
+        size += __popc(c);
+        up += __popc(v);
+    }
+    if (size) atomicAdd(&ctr[3], size);
+    if (up) atomicAdd(&ctr[5], up);
+    __syncthreads();
+    int e = 0;
+    for (int b = tid; b < s.n_bonds; b += WOLFF_THREADS) {
+        const int a = s.bonds[2 * b], c = s.bonds[2 * b + 1];
+        e -= ((sp[a >> 5] >> (a & 31)) & 1u) == ((sp[c >> 5] >> (c & 31)) & 1u) ? 1 : -1;
+    }
+    if (e) atomicAdd(&ctr[4], (unsigned int)e);
+    __syncthreads();
+    if (tid != 0) return;
+    const int E = (int)ctr[4], M = 2 * (int)ctr[5] - N, C = (int)ctr[3];
+    s.E[w] = E;
+    s.M[w] = M;
+    s.moves[w] = m + 1;
+    s.gprop[w] += 1;
+    s.gacc[w] += C > 1 ? 1 : 0;
+    s.gsum[w] += C;
+    if (measure) {
+        const double ed = (double)E, md = (double)(M < 0 ? -M : M);
+        s.sE[w] += ed;
+        s.sE2[w] += ed * ed;
+        s.sM[w] += md;
+        s.sM2[w] += md * md;
+        const long long ns = s.n_series[w];
+        if (ns < s.cap) {
+            s.serE[at((int)ns, W, w)] = E;
+            s.serM[at((int)ns, W, w)] = M < 0 ? -M : M;
+            s.n_series[w] = ns + 1;
+        }
+        s.n_meas[w] += 1;
+    }
+}
+
 }  // namespace dqmc_mc
 
 using namespace dqmc_mc;
 
 struct dqmc_mc_handle {
     int N = 0, z = 0, W = 0, nw = 0, cap = 0, n_bonds = 0, device = 0;
+    int global_rate = 0;       // mc.p.global_rate when global moves are on, 0 = off
     std::vector<int> nbr_h;    // [N][z] 0-based
     std::vector<int> bonds_h;  // [n_bonds][2] 0-based
     hipStream_t stream = nullptr;
@@ -254,6 +372,15 @@ static int mc_launch_observables(dqmc_mc_handle *h, int walker)
     const int grid = walker >= 0 ? 1 : (h->W + WAVE - 1) / WAVE;
     hipLaunchKernelGGL(ising_observables_kernel, dim3(grid), dim3(WAVE), (size_t)h->nw * WAVE * 4, h->stream, h->d,
                        walker);
+    MCHK(hipGetLastError());
+    return 0;
+}
+
+static int mc_launch_wolff(dqmc_mc_handle *h, int walker, int measure)
+{
+    const int grid = walker >= 0 ? 1 : h->W;
+    hipLaunchKernelGGL(ising_wolff_kernel, dim3(grid), dim3(WOLFF_THREADS), wolff_lds_bytes(h->N, h->nw), h->stream,
+                       h->d, (const int *)h->d.nbr, h->z, walker, measure);
     MCHK(hipGetLastError());
     return 0;
 }
@@ -332,7 +459,9 @@ int dqmc_mc_create(const dqmc_mc_params *p, dqmc_mc_handle **out)
         (rc = mc_alloc(h, &d.sE2, W)) || (rc = mc_alloc(h, &d.sM, W)) || (rc = mc_alloc(h, &d.sM2, W)) ||
         (rc = mc_alloc(h, &d.n_meas, W)) || (rc = mc_alloc(h, &d.prop, W)) || (rc = mc_alloc(h, &d.acc, W)) ||
         (rc = mc_alloc(h, &d.n_series, W)) || (rc = mc_alloc(h, &d.serE, (size_t)h->cap * W)) ||
-        (rc = mc_alloc(h, &d.serM, (size_t)h->cap * W)))
+        (rc = mc_alloc(h, &d.serM, (size_t)h->cap * W)) || (rc = mc_alloc(h, &d.pw, W)) ||
+        (rc = mc_alloc(h, &d.moves, W)) || (rc = mc_alloc(h, &d.gprop, W)) || (rc = mc_alloc(h, &d.gacc, W)) ||
+        (rc = mc_alloc(h, &d.gsum, W)))
         return bail(rc);
     d.nbr = nbr;
     d.bonds = bonds;
@@ -350,6 +479,9 @@ int dqmc_mc_create(const dqmc_mc_params *p, dqmc_mc_handle **out)
     for (const void *k : kernels)
         if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
             return bail(mc_fail(h, DQMC_ERR_HIP, "dqmc_mc_create: cannot reserve LDS for the spins"));
+    if (hipFuncSetAttribute((const void *)ising_wolff_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)wolff_lds_bytes(N, h->nw)) != hipSuccess)
+        return bail(mc_fail(h, DQMC_ERR_HIP, "dqmc_mc_create: cannot reserve LDS for the cluster move"));
     if (hipStreamSynchronize(h->stream) != hipSuccess)
         return bail(mc_fail(h, DQMC_ERR_HIP, "dqmc_mc_create: device initialisation failed"));
     *out = h;
@@ -379,8 +511,7 @@ int dqmc_mc_set_beta(dqmc_mc_handle *h, int32_t walker, double beta)
     for (int k = 1; k <= MAX_Z; ++k) thr[k - 1] = exp(-beta * (2.0 * k));  // exp(-beta dE), MC.jl:327
     MCHK(hipMemcpy2DAsync(h->d.thr + walker, (size_t)h->W * sizeof(double), thr, sizeof(double), sizeof(double), MAX_Z,
                           hipMemcpyHostToDevice, h->stream));
-    MCHK(hipStreamSynchronize(h->stream));
-    return DQMC_OK;
+    return mc_put<double>(h, h->d.pw, 0, walker, 1.0 - exp(-2.0 * beta));  // 1 - exp(-2 beta), IsingModel.jl:126
 }
 
 int dqmc_mc_seed(dqmc_mc_handle *h, int32_t walker, uint64_t seed)
@@ -388,6 +519,7 @@ int dqmc_mc_seed(dqmc_mc_handle *h, int32_t walker, uint64_t seed)
     if (int rc = mc_walker(h, walker, "dqmc_mc_seed")) return rc;
     MCHK(hipSetDevice(h->device));
     if (int rc = mc_put<unsigned long long>(h, h->d.key, 0, walker, seed)) return rc;
+    if (int rc = mc_put<unsigned long long>(h, h->d.moves, 0, walker, 0ull)) return rc;
     return mc_put<unsigned long long>(h, h->d.draw, 0, walker, 0ull);
 }
 
@@ -464,20 +596,26 @@ int dqmc_mc_sweep(dqmc_mc_handle *h, int32_t n_sweeps, int64_t first_sweep_index
     const int grid = (h->W + WAVE - 1) / WAVE;
     const double per_sweep = (double)h->N * std::max((double)h->W, BUDGET_WALKERS);
     const int chunk = (int)std::max(1.0, std::min((double)n_sweeps, std::floor(LAUNCH_BUDGET / per_sweep)));
+    const int r = h->global_rate;
     for (int done = 0; done < n_sweeps;) {
-        const int n = std::min(chunk, n_sweeps - done);
+        int n = std::min(chunk, n_sweeps - done);
         const long long first = first_sweep_index + done;
+        if (r > 0) n = (int)std::min<long long>(n, r - (first - 1) % r);  // a launch ends at the next multiple of r
+        const long long last = first + n - 1;
+        const bool move = r > 0 && last % r == 0;  // global_move after sweep `last` (MC.jl:233-236)
         switch (h->z) {
 #define MC_CASE(Z)                                                                                                  \
     case Z:                                                                                                         \
         hipLaunchKernelGGL(ising_sweep_kernel<Z>, dim3(grid), dim3(WAVE), lds, h->stream, h->d,                    \
                            (const int4 *)h->d.nbr, n, first,                                                       \
-                           (long long)thermalization, (int)measure_rate);                                          \
+                           (long long)thermalization, (int)measure_rate, move ? last : -1LL);                      \
         break;
             MC_CASE(1) MC_CASE(2) MC_CASE(3) MC_CASE(4) MC_CASE(5) MC_CASE(6) MC_CASE(7) MC_CASE(8)
 #undef MC_CASE
         }
         MCHK(hipGetLastError());
+        if (move)
+            if (int rc = mc_launch_wolff(h, -1, last > thermalization && last % measure_rate == 0)) return rc;
         done += n;
     }
     MCHK(hipStreamSynchronize(h->stream));
@@ -508,6 +646,43 @@ int dqmc_mc_get_stats(dqmc_mc_handle *h, int32_t walker, dqmc_mc_stats *out)
     out->acc_local = acc;
     out->uniforms_used = draw;
     out->n_series = n_series;
+    return DQMC_OK;
+}
+
+int dqmc_mc_set_global_rate(dqmc_mc_handle *h, int32_t rate)
+{
+    if (!h) return mc_fail(nullptr, DQMC_ERR_INVALID, "dqmc_mc_set_global_rate: null handle");
+    if (rate < 0) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_mc_set_global_rate: rate must be >= 0 (0 = off)");
+    h->global_rate = rate;
+    return DQMC_OK;
+}
+
+int dqmc_mc_global_move(dqmc_mc_handle *h, int32_t walker)
+{
+    if (!h) return mc_fail(nullptr, DQMC_ERR_INVALID, "dqmc_mc_global_move: null handle");
+    if (walker >= h->W) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_mc_global_move: walker out of range");
+    MCHK(hipSetDevice(h->device));
+    if (int rc = mc_launch_wolff(h, walker < 0 ? -1 : walker, 0)) return rc;
+    MCHK(hipStreamSynchronize(h->stream));
+    return DQMC_OK;
+}
+
+int dqmc_mc_get_global_stats(dqmc_mc_handle *h, int32_t walker, dqmc_mc_global_stats *out)
+{
+    if (int rc = mc_walker(h, walker, "dqmc_mc_get_global_stats")) return rc;
+    if (!out) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_mc_get_global_stats: null out");
+    MCHK(hipSetDevice(h->device));
+    const DevState &d = h->d;
+    long long prop = 0, acc = 0, sum = 0;
+    unsigned long long moves = 0;
+    int rc = 0;
+    if ((rc = mc_get(h, d.gprop, 0, walker, &prop)) || (rc = mc_get(h, d.gacc, 0, walker, &acc)) ||
+        (rc = mc_get(h, d.gsum, 0, walker, &sum)) || (rc = mc_get(h, d.moves, 0, walker, &moves)))
+        return rc;
+    out->prop_global = prop;
+    out->acc_global = acc;
+    out->sum_cluster_size = sum;
+    out->moves_drawn = moves;
     return DQMC_OK;
 }
 

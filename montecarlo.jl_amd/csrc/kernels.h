@@ -248,6 +248,28 @@ __device__ __forceinline__ double philox_uniform(unsigned long long seed, unsign
     return (double)((hi << 26) | lo) * (1.0 / 9007199254740992.0);
 }
 
+// the same generator and uniform with all four counter words given: philox4_uniform(seed, low32(i), high32(i), 0, 0)
+// equals philox_uniform(seed, i); the Ising cluster move draws from c2 = 1 (ising.hip)
+__device__ __forceinline__ double philox4_uniform(unsigned long long seed, unsigned int c0, unsigned int c1,
+                                                  unsigned int c2, unsigned int c3)
+{
+    unsigned int k0 = (unsigned int)seed, k1 = (unsigned int)(seed >> 32);
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0;
+        const unsigned long long p1 = (unsigned long long)0xCD9E8D57u * c2;
+        const unsigned int n0 = (unsigned int)(p1 >> 32) ^ c1 ^ k0;
+        const unsigned int n1 = (unsigned int)p1;
+        const unsigned int n2 = (unsigned int)(p0 >> 32) ^ c3 ^ k1;
+        const unsigned int n3 = (unsigned int)p0;
+        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    const unsigned long long hi = c0 >> 5, lo = c1 >> 6;
+    return (double)((hi << 26) | lo) * (1.0 / 9007199254740992.0);
+}
+
 __device__ __forceinline__ void magstats_push(DevMagStats &s, double value)
 {
     const double v = log10(fabs(value));

@@ -2,15 +2,16 @@
 measurements.jl), `n_walkers` independent Markov chains batched on one device (csrc/ising.hip).
 
 Walker w draws from the Philox4x32-10 stream keyed by `seed + first_walker + w`: draws 0..N-1 give the initial
-configuration (rand(MC, m)), the Metropolis uniforms follow.  The host holds the model, the loop control and
-finish!; every site update runs on the device."""
+configuration (rand(MC, m)), the Metropolis uniforms follow.  The Wolff cluster move (`cluster_moves=True`) draws from a
+domain of its own of the same key (include/dqmc_hip.h, dqmc_mc_global_move).  The host holds the model, the loop control
+and finish!; every site update runs on the device."""
 import ctypes as C
 import math
 import time
 
 import numpy as np
 
-from ._lib import DQMCError, ERR_INVALID, McParams, McStats, lib
+from ._lib import DQMCError, ERR_INVALID, McGlobalStats, McParams, McStats, lib
 from .configurations import CompressedConf
 from .lattices import Chain, CubicLattice, SquareLattice
 
@@ -56,15 +57,24 @@ class IsingModel:
 
 class MC:
     """MC(model; beta | T, ...) (MC.jl:16-80) for `n_walkers` chains.  `beta` may be a sequence of n_walkers values
-    (one temperature per walker).  Global (Wolff) moves are refused: the reference's global_move cannot run
-    (IsingModel.jl:137 assigns to an undefined `model`) and its rand(1:N) draws have no place in the walker streams."""
+    (one temperature per walker).
+
+    `cluster_moves=True` runs a Wolff cluster move per walker after every sweep whose index is a multiple of
+    `global_rate`, as run! does with global_moves (MC.jl:233-236), on a stream of its own (dqmc_mc_global_move).
+    `global_moves=True` is refused: the reference's global_move cannot run as written (IsingModel.jl:137 assigns to an
+    undefined `model`) and its rand(1:N) draws have no place in the walker streams; `cluster_moves` is its defined
+    counterpart."""
 
     def __init__(self, model, beta=None, T=None, n_walkers=1, seed=123, first_walker=0, thermalization=0, sweeps=1000,
-                 measure_rate=1, print_rate=1000, global_moves=False, global_rate=5, device_id=0, series_capacity=0):
+                 measure_rate=1, print_rate=1000, global_moves=False, global_rate=5, device_id=0, series_capacity=0,
+                 cluster_moves=False):
         if global_moves:
             raise NotImplementedError(
                 "MC(global_moves=True): the reference's Wolff global_move cannot run (IsingModel.jl:137 uses the "
-                "undefined `model`) and its rand(1:N) draws have no defined place in the walkers' Philox streams")
+                "undefined `model`) and its rand(1:N) draws have no defined place in the walkers' Philox streams; "
+                "MC(cluster_moves=True, global_rate=...) runs the cluster move on a stream of its own")
+        if cluster_moves and (int(global_rate) != global_rate or global_rate < 1):
+            raise ValueError("MC(cluster_moves=True): global_rate must be an integer >= 1")
         if (beta is None) == (T is None):
             raise ValueError("MC needs exactly one of beta and T")
         if T is not None:
@@ -82,6 +92,7 @@ class MC:
         self.seeds = [seed + first_walker + w for w in range(n_walkers)]
         self.thermalization, self.sweeps, self.measure_rate = thermalization, sweeps, measure_rate
         self.print_rate, self.global_moves, self.global_rate = print_rate, global_moves, global_rate
+        self.cluster_moves = bool(cluster_moves)
         self.last_sweep = 0
         self.series_capacity = series_capacity
         self._neighs = np.asfortranarray(np.asarray(model.l.neighs, dtype=np.int64))
@@ -100,6 +111,8 @@ class MC:
             self._c(lib().dqmc_mc_seed(self._h, w, self.seeds[w]))
             self._c(lib().dqmc_mc_set_beta(self._h, w, float(betas[w])))
         self._c(lib().dqmc_mc_rand_conf(self._h, -1))  # mc.conf = rand(MC, m); init! (MC.jl:61,74)
+        if self.cluster_moves:
+            self._c(lib().dqmc_mc_set_global_rate(self._h, int(global_rate)))
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
@@ -175,6 +188,9 @@ class MC:
             self.thermalization = thermalization
         total = self.thermalization + self.sweeps
         t0 = time.time()
+        if verbose and self.cluster_moves:
+            g = self.global_stats(0)
+            g0 = (g.acc_global, g.prop_global)
         while self.last_sweep < total:
             stop = total
             if recorder is not None and getattr(recorder, "rate", None):
@@ -192,7 +208,24 @@ class MC:
                 print("\t%d\n\t\tsweep dur: %.3fs\n\t\tacc rate (local) : %.1f%%" %
                       (i, (time.time() - t0) / self.print_rate, 100.0 * st.acc_local / max(st.prop_local, 1)))
                 t0 = time.time()
+                if self.cluster_moves:  # MC.jl:265-271: this print window, then overall
+                    g = self.global_stats(0)
+                    print("\t\tacc rate (global): %.1f%%\n\t\tacc rate (global, overall): %.1f%%" %
+                          (100.0 * (g.acc_global - g0[0]) / max(g.prop_global - g0[1], 1),
+                           100.0 * g.acc_global / max(g.prop_global, 1)))
+                    g0 = (g.acc_global, g.prop_global)
         return True
+
+    def global_move(self, walker=-1):
+        """global_move(mc, m, conf) (IsingModel.jl:104-140): one Wolff cluster move of one walker (walker < 0: every
+        walker), counted in the global stats, no measurement"""
+        self._c(lib().dqmc_mc_global_move(self._h, walker))
+
+    def global_stats(self, walker=0):
+        """prop_global, acc_global, sum_cluster_size and moves_drawn (the move cursor) of one walker"""
+        st = McGlobalStats()
+        self._c(lib().dqmc_mc_get_global_stats(self._h, walker, C.byref(st)))
+        return st
 
     def reset_accumulators(self):
         self._c(lib().dqmc_mc_reset_accumulators(self._h))
@@ -204,8 +237,11 @@ class MC:
     def analysis(self, walker=0):
         """MCAnalysis (MC.jl:1-11) of one walker"""
         st = self.stats(walker)
+        g = self.global_stats(walker)
         return {"acc_rate": st.acc_local / st.prop_local if st.prop_local else 0.0, "prop_local": int(st.prop_local),
-                "acc_local": int(st.acc_local), "acc_rate_global": 0.0, "prop_global": 0, "acc_global": 0}
+                "acc_local": int(st.acc_local),
+                "acc_rate_global": g.acc_global / g.prop_global if g.prop_global else 0.0,
+                "prop_global": int(g.prop_global), "acc_global": int(g.acc_global)}
 
     def measurements(self, walker=0):
         """finish! of IsingMagnetizationMeasurement and IsingEnergyMeasurement (measurements.jl:13-94) on the sums:
