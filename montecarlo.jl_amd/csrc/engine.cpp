@@ -81,6 +81,11 @@ struct dqmc_handle {
         const double *img = nullptr;
         int site0 = 0;
     } pf;
+    // the factored wrap in one launch (kron.hip: kron_wrap_kernel): arrival words per unit, never cleared (wrap_launches
+    // counts the launches on them); wrap_blocks[pending]: co-resident workgroups of the two forms, 0 = two launches
+    unsigned *wrap_cnt = nullptr;
+    unsigned wrap_launches = 0;
+    int wrap_blocks[2] = {0, 0};
     WalkerRng *rng = nullptr;
     DevStats *stats = nullptr;
     unsigned long long *pc_scratch = nullptr;  // prop_check_kernel: partial maximum + arrival counter per walker
@@ -438,6 +443,7 @@ static void read_kernel_switches(dqmc_handle *h)
     k.no_slab = getenv("DQMC_NO_SLAB") != nullptr;
     k.no_kron = getenv("DQMC_NO_KRON") != nullptr;
     k.no_wrap_flush = getenv("DQMC_NO_WRAP_FLUSH") != nullptr;
+    k.wrap_two_launch = getenv("DQMC_WRAP_TWO_LAUNCH") != nullptr;
 }
 
 static int alloc_qr_workspace(dqmc_handle *h)
@@ -474,6 +480,21 @@ static int alloc_qr_workspace(dqmc_handle *h)
     }
     return 0;
 }
+// The factored wrap in one launch (kron.hip: kron_wrap_kernel): its workgroups wait for each other, so a handle takes it
+// only where the occupancy API says that the whole grid is resident at once on this device, for the form with the pending
+// chunk (two workgroups per CU by its LDS) and the one without separately.  DQMC_WRAP_TWO_LAUNCH: never.
+// The words are allocated if either form fits and wrap_greens_kron asks again per form, so a handle whose grid fits only
+// without the chunk mixes one- and two-launch wraps (the same bits either way).  The occupancy figure knows nothing of
+// another handle, stream or process on the device: that case is what the bounded poll and the error bit are for.
+static int alloc_wrap_handoff(dqmc_handle *h)
+{
+    if (!h->kron || h->n != 256 || h->sw.wrap_two_launch) return 0;
+    hipDeviceProp_t prop;
+    HIPCHK(hipGetDeviceProperties(&prop, h->p.device_id));
+    for (int pf = 0; pf < 2; ++pf) h->wrap_blocks[pf] = prop.multiProcessorCount * kron_wrap_blocks_per_cu(pf != 0);
+    if (kron_wrap_grid(h->units) > std::max(h->wrap_blocks[0], h->wrap_blocks[1])) return 0;
+    return dalloc(h, &h->wrap_cnt, (size_t)kron_wrap_grid(h->units) / 16 * KR_CNT_STRIDE);
+}
 static int check_qr_workspace(dqmc_handle *h)
 {
     if (!h->qr_ws.errflag) return 0;
@@ -481,6 +502,10 @@ static int check_qr_workspace(dqmc_handle *h)
     HIPCHK(hipMemcpy(&e, h->qr_ws.errflag, sizeof(int), hipMemcpyDeviceToHost));
     if (e) {  // reported once: the flag is cleared, the data of the failed call is not trustworthy
         HIPCHK(hipMemset(h->qr_ws.errflag, 0, sizeof(int)));
+        if (e & 32)
+            return fail(h, DQMC_ERR_HIP, "factored wrap (one launch): the hand-off between the workgroups of a unit timed out (is the "
+                                         "grid co-resident?  results of this call are invalid; DQMC_WRAP_TWO_LAUNCH=1 selects the "
+                                         "two-launch form, which has no hand-off)");
         if (e & 16)
             return fail(h, DQMC_ERR_HIP, "blocked UDT: a hand-off between the workgroups of a matrix timed out (results of this call "
                                          "are invalid; DQMC_QR_NOBLOCKED=1 selects the kernels without that requirement)");
@@ -819,10 +844,12 @@ static int add_slice_sequence_right(dqmc_handle *h, int idx) { return add_slice_
 
 // wrap_greens! (stack.jl:491-500), out of place, one launch: column slab c of the result is
 //   +1:  eT2 (eV (G (eV^-1 eTinv2[:, c])))          -1:  eV^-1 (eTinv2 (G eT2[:, c])) eV[c]
-// Factored form (kron.hip): two one-step launches through bufB, each storing its result transposed, so that the right
+// Factored form (kron.hip): two one-step chains through bufB, each storing its result transposed, so that the right
 // product becomes a left product with the transposed factors:
 //   +1:  P = eT2 (eV G)           -> bufB = P'        dst = (eTinv2' (eV^-1 P'))'  = P eV^-1 eTinv2
 //   -1:  P = eV^-1 (eTinv2 G)     -> bufB = P'        dst = (eV (eT2' P'))'        = P eT2 eV
+// At n = 256 on the square lattice both run in one launch with a hand-off per unit (kron_wrap_kernel) when its whole grid is
+// co-resident by the occupancy API (alloc_wrap_handoff); otherwise, and under DQMC_WRAP_TWO_LAUNCH, as two launches.
 static int wrap_greens_kron(dqmc_handle *h, const double *src, double *dst, int curr_slice, int direction)
 {
     const int8_t *c = conf_slice(h, direction == -1 ? curr_slice - 1 : curr_slice);
@@ -836,6 +863,20 @@ static int wrap_greens_kron(dqmc_handle *h, const double *src, double *dst, int 
     KronStep &s1 = kron_step(h, a, direction == -1 ? KF_ETINV2 : KF_ET2);
     if (direction == -1) { s1.post_conf = c; s1.post_sign = -1; }
     else { s1.pre_conf = c; s1.pre_sign = +1; }
+    if (h->wrap_cnt && h->n == 256 && !h->tri && kron_wrap_grid(h->units) <= h->wrap_blocks[a.pf_img ? 1 : 0]) {
+        KronStep &s2 = kron_step(h, a, direction == -1 ? KF_ET2T : KF_ETINV2T);
+        if (direction == -1) { s2.post_conf = c; s2.post_sign = +1; }
+        else { s2.pre_conf = c; s2.pre_sign = -1; }
+        a.wrap_out = dst;
+        a.wrap_cnt = h->wrap_cnt;
+        a.wrap_target = 16u * (h->wrap_launches + 1);
+        a.errflag = h->qr_ws.errflag;
+        hipEvent_t ea, eb;
+        timing_events(h, &ea, &eb);
+        HIPCHK(launch_kron_wrap(a, h->cur, ea, eb));
+        ++h->wrap_launches;  // (only a launch that went out adds to the arrival words)
+        return timing_push(h, ea, eb, DQMC_K_GEMM);
+    }
     CHK(run_kron(h, a));
     KronArgs b = kron_base(h, h->bufB, dst);
     b.transpose_out = 1;
@@ -1268,6 +1309,7 @@ int dqmc_create(const dqmc_params *p, dqmc_handle **out)
     if (h->n > 256) CCHK(dalloc(h, &h->trsm_s, un));
     CCHK(dalloc(h, &h->pivot, uv));
     CCHK(alloc_qr_workspace(h));
+    CCHK(alloc_wrap_handoff(h));
     CCHK(dalloc(h, &h->greens_alt, un));
     CCHK(dalloc(h, &h->lu_img, 2 * (size_t)h->units * sweep_lu_image_doubles()));
     CCHK(dalloc(h, &h->rng, (size_t)h->W));
@@ -2043,7 +2085,7 @@ int dqmc_set_checkerboard(dqmc_handle *h, int32_t kmax, int32_t n_mats, const do
 }
 
 // the device error word as it stands (not cleared): 0 unless a bounded wait inside a kernel ran out since the last call that
-// reported it (bit 1: sweep elimination hand-off, bit 4: one-launch UDT hand-off)
+// reported it (bit 1: sweep elimination hand-off, bit 4: one-launch UDT hand-off, bit 5: one-launch wrap hand-off)
 int dqmc_device_errors(dqmc_handle *h, int32_t *word)
 {
     ENTER(h);

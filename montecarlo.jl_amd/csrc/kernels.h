@@ -114,8 +114,21 @@ struct KronArgs {
     // at pf_img + unit * pf_img_su): what sweep_flush_lu_kernel would have written (kron.hip).  Null: no update.
     const double *pf_img; long pf_img_su;
     int pf_site0;
+    // launch_kron_wrap only: st[1] goes from out into wrap_out; arrival word of unit u at wrap_cnt[KR_CNT_STRIDE u], which
+    // reaches wrap_target (16 x the one-launch wraps on these words so far, this one included) when the unit's first step
+    // is stored; errflag: the device error word (bit 5: that wait ran out)
+    double *wrap_out;
+    unsigned *wrap_cnt; unsigned wrap_target;
+    int *errflag;
 };
 hipError_t launch_kron_chain(const KronArgs &a, hipStream_t s, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
+// wrap_greens! at n = 256 in one launch (kron.hip: kron_wrap_kernel): nsteps = 2, both results stored transposed.  Every
+// workgroup waits for the 15 others of its unit, so the caller launches it only when kron_wrap_grid(n_units) workgroups are
+// co-resident: kron_wrap_blocks_per_cu (the occupancy API, with / without the pending chunk) x compute units.
+constexpr int KR_CNT_STRIDE = 32;  // arrival words on 128-byte lines of their own
+inline int kron_wrap_grid(int n_units) { return (n_units + 7) / 8 * 8 * 16; }  // whole groups of eight units (XCD placement)
+int kron_wrap_blocks_per_cu(bool pending);
+hipError_t launch_kron_wrap(const KronArgs &a, hipStream_t s, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
 // The same chains at n = 512 = 8 x 8 x 8 sites with A_s = Ez (x) Exy (kron3.hip): ax / ay are the operand images of
 // Exy (64 x 64, block b at + 4096 b) and of I2 (x) Ez (block b at + 256 b) described there
 hipError_t launch_kron3_chain(const KronArgs &a, hipStream_t s, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
@@ -147,6 +160,7 @@ struct KernelSwitches {
     bool no_slab = false;         // DQMC_NO_SLAB: no slab-resident product chains (slab.hip)
     bool no_kron = false;         // DQMC_NO_KRON: dense slab chains even where the hopping factorises (kron.hip)
     bool no_wrap_flush = false;   // DQMC_NO_WRAP_FLUSH: the last chunk of a sweep as a stand-alone flush, not in the wrap
+    bool wrap_two_launch = false; // DQMC_WRAP_TWO_LAUNCH: the factored wrap at n = 256 as two one-step launches
 };
 
 constexpr int QR_COOP_SLOT = 528;  // 264 packets of 16 bytes

@@ -9,7 +9,8 @@
 //
 // with the argument conventions and scaling placement of slab.hip.  Used for
 //   * add_slice_sequence_left/right (stack.jl:272-311): the safe_mult products B_l X / B_l' X;
-//   * wrap_greens! (stack.jl:491-500) as two one-step launches with transposed stores (engine.cpp: wrap_greens_kron).
+//   * wrap_greens! (stack.jl:491-500) as two one-step chains with transposed stores (engine.cpp: wrap_greens_kron): in one
+//     launch with a hand-off per unit where the grid is co-resident (kron_wrap_kernel), else as two launches.
 //
 // Layout.  A wave holds a column as one MFMA accumulator tile (4 doubles per lane): register r of lane (g = lane >> 4,
 // c = lane & 15) is V[a = g + 4 r][b = c], where (a, b) = (y, x) or (x, y) by step parity.  Register q of that tile is
@@ -19,7 +20,7 @@
 // Columns are independent: a workgroup (4 waves x KR_NC columns) owns 16 consecutive columns through all steps, and
 // nothing crosses workgroups.  The result is staged in LDS and stored as whole 128-byte lines, as is or transposed.
 //
-// Pending chunk (KronArgs::pf_img, the first launch of a wrap behind a sweep).  The sweep leaves its last chunk c of 64
+// Pending chunk (KronArgs::pf_img, the first chain of a wrap behind a sweep).  The sweep leaves its last chunk c of 64
 // sites eliminated but not applied: G' = G + T R0 with T = C X Y, C = G[:, c] - E, Y = (I - Uu X)^-1 (I - L X)^-1,
 // R0 = G[c, :] (sweep_lu.hip).  A workgroup owns whole columns j, so it forms G'[:, j] = G[:, j] + C R^[:, j] with
 // R^ = X Y R0 re-associated onto the rows (the stand-alone flush solves on the columns of C instead):
@@ -54,6 +55,7 @@ static_assert(KR_PF_R0 + KR_COLS * KR_PF_RLD <= KR_LDS_PF && KR_LDS <= KR_LDS_PF
 typedef const KR_GLOBAL double *kr_gcdp;
 typedef double kr_d2 __attribute__((ext_vector_type(2)));
 typedef const KR_GLOBAL kr_d2 *kr_gcd2p;
+typedef unsigned kr_u4 __attribute__((ext_vector_type(4)));
 
 // exp(sign lambda conf[i]) of block blk (vs_conf() of engine.cpp, slab_conf_val() of slab.hip)
 __device__ __forceinline__ double kr_conf(int8_t c, int sign, bool bn, double epl, double eml)
@@ -62,6 +64,7 @@ __device__ __forceinline__ double kr_conf(int8_t c, int sign, bool bn, double ep
 }
 
 #ifdef KR_STAMPS  // diagnostic build only (tools/kr_stamps.py): per workgroup of the pending-chunk launch, cycle stamps of wave 0
+                  // (inside kr_chain only of the chain that applies the chunk: the second chain of kron_wrap_kernel stamps nothing)
 __device__ long long *kr_stamp_ptr = nullptr;
 #define KR_STAMP(k)                                                                                   \
     do {                                                                                              \
@@ -133,6 +136,42 @@ __device__ __forceinline__ void kr_apply_pending(const KronArgs &a, int unit, in
     };
     fetch(0, ca[0]);
     // (the four waves solve the same 64 x 16 block: each needs all of R^ as B operands)
+#ifdef KR_PROBE_PRODUCTS
+    // TIMING PROBE, WRONG VALUES (diagnostic build with KR_STAMPS only): what the solves would cost as two
+    // block-triangular products on prebuilt inverse blocks, with image tiles standing in for the blocks nothing builds yet.
+    // Wave w forms block row w of each product (independent accumulators), the intermediate and R^ go through LDS.
+    d4k rh[4];
+    {
+        double *lw = lr + KR_COLS * KR_PF_RLD, *lh = lr;  // behind R0 (free up to KR_LDS_PF); over R0, dead after the first product
+        static_assert(KR_PF_R0 + 2 * KR_COLS * KR_PF_RLD <= KR_LDS_PF, "probe LDS");
+        d4k pa[4];
+#pragma unroll
+        for (int J = 0; J < 4; ++J) {
+            pa[J] = (d4k){0.0, 0.0, 0.0, 0.0};
+            if (J <= w)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) pa[J] = KR_MFMA(A(TL + J, q), lr[ci * KR_PF_RLD + 16 * J + 4 * q + g], pa[J]);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            lw[ci * KR_PF_RLD + 16 * w + 4 * r + g] = (pa[0][r] + pa[1][r] + pa[2][r] + pa[3][r]) * xr(w, r);
+        __syncthreads();
+#pragma unroll
+        for (int J = 0; J < 4; ++J) {
+            pa[J] = (d4k){0.0, 0.0, 0.0, 0.0};
+            if (J >= w)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) pa[J] = KR_MFMA(A(TU + J, q), lw[ci * KR_PF_RLD + 16 * J + 4 * q + g], pa[J]);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) lh[ci * KR_PF_RLD + 16 * w + 4 * r + g] = pa[0][r] + pa[1][r] + pa[2][r] + pa[3][r];
+        __syncthreads();
+#pragma unroll
+        for (int J = 0; J < 4; ++J)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) rh[J][q] = lh[ci * KR_PF_RLD + 16 * J + 4 * q + g];
+    }
+#else
     d4k xv[4], rh[4];
 #pragma unroll
     for (int J = 0; J < 4; ++J) {
@@ -163,6 +202,7 @@ __device__ __forceinline__ void kr_apply_pending(const KronArgs &a, int unit, in
         for (int q = 0; q < 4; ++q) o = KR_MFMA(A(TP + J, q), acc[q], o);
         rh[J] = o;
     }
+#endif
     KR_STAMP(3);
     // tile mm of D holds D[16 (4 w + mm) + 4 r + g][j = ci]
     d4k dm[4];
@@ -197,23 +237,13 @@ __device__ __forceinline__ void kr_apply_pending(const KronArgs &a, int unit, in
     // at the end that overlaps it is behind the steps' barriers)
 }
 
-template <bool PF>
-__global__ __launch_bounds__(256) void kron_chain_kernel(KronArgs a)
+// One chain of a workgroup: columns c0 .. c0 + KR_COLS - 1 of X_0 (x0u, this unit's matrix) through the steps st[0 .. nsteps),
+// result to ou.  PF: the pending chunk is applied to X_0 first.  WT: the result is stored write-through (the hand-off of
+// kron_wrap_kernel).
+template <bool PF, bool WT>
+__device__ __forceinline__ void kr_chain(const KronArgs &a, const KronStep *steps, int nsteps, const double *x0u, double *ou,
+                                         int unit, int c0, double *lds)
 {
-    __shared__ __attribute__((aligned(16))) double lds[PF ? KR_LDS_PF : KR_LDS];
-    // PF: the 16 workgroups of a unit share an XCD (blockIdx.x % 8, as the flush kernels place units): each of them reads
-    // all of C and the image, which then come into one L2 once instead of into eight
-#ifndef KR_NO_XCD_GROUPS
-    constexpr bool XG = PF;
-#else
-    constexpr bool XG = false;
-#endif
-    const unsigned bq = XG ? blockIdx.x >> 3 : blockIdx.x;
-    const int unit = XG ? (bq / (KR_N / KR_COLS)) * 8 + (blockIdx.x & 7) : bq / (KR_N / KR_COLS);
-    const int c0 = KR_COLS * (bq % (KR_N / KR_COLS));
-    if (unit >= a.n_units) return;
-    KR_STAMP(0);
-    KR_STAMP_RT(1);
     const int wk = a.nb == 2 ? unit >> 1 : unit, blk = a.nb == 2 ? unit & 1 : 0;
     const bool bn = blk != 0;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 4, ci = lane & 15;
@@ -223,7 +253,7 @@ __global__ __launch_bounds__(256) void kron_chain_kernel(KronArgs a)
     // X_0: column c0 + KR_NC w + t, parity (y, x): register r = entries ci + 16 (g + 4 r), 64 consecutive doubles
     d4k v[KR_NC];
     {
-        const double *x0 = a.X0 + (long)unit * a.x_su + (long)KR_N * (c0 + KR_NC * w) + ci + 16 * g;
+        const double *x0 = x0u + (long)KR_N * (c0 + KR_NC * w) + ci + 16 * g;
 #pragma unroll
         for (int t = 0; t < KR_NC; ++t)
 #pragma unroll
@@ -240,7 +270,7 @@ __global__ __launch_bounds__(256) void kron_chain_kernel(KronArgs a)
         int8_t cpre[4], cpost[4];
     };
     auto request = [&](int s, Ops &o) {
-        const KronStep &st = a.st[s];
+        const KronStep &st = steps[s];
         const int par = s & 1;
         const double *fx = st.ax + KR_N * blk, *fy = st.ay + KR_N * blk;
         const double *fa = par ? fx : fy, *fb = par ? fy : fx;
@@ -249,7 +279,7 @@ __global__ __launch_bounds__(256) void kron_chain_kernel(KronArgs a)
             o.av[q] = fa[ci + 16 * (4 * q + g)];
             o.bv[q] = fb[ci + 16 * (4 * q + g)];
         }
-        const int8_t *dummy = reinterpret_cast<const int8_t *>(a.X0);
+        const int8_t *dummy = reinterpret_cast<const int8_t *>(x0u);
         const int8_t *pre = st.pre_conf ? st.pre_conf + conf_off : dummy, *post = st.post_conf ? st.post_conf + conf_off : dummy;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -261,15 +291,15 @@ __global__ __launch_bounds__(256) void kron_chain_kernel(KronArgs a)
     request(0, cur);
     double cs[KR_NC];  // final column scale (read from X_0 and not applied when there is none)
     {
-        const double *cd = a.col_d ? a.col_d + (long)unit * a.col_stride + c0 + KR_NC * w : a.X0;
+        const double *cd = a.col_d ? a.col_d + (long)unit * a.col_stride + c0 + KR_NC * w : x0u;
 #pragma unroll
         for (int t = 0; t < KR_NC; ++t) cs[t] = cd[t];
     }
     if constexpr (PF) kr_apply_pending<PF>(a, unit, c0, v, lds);
     KR_STAMP(5);
 
-    for (int s = 0; s < a.nsteps; ++s) {
-        const KronStep &st = a.st[s];
+    for (int s = 0; s < nsteps; ++s) {
+        const KronStep &st = steps[s];
         if (st.pre_conf) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -287,7 +317,7 @@ __global__ __launch_bounds__(256) void kron_chain_kernel(KronArgs a)
 #pragma unroll
             for (int r = 0; r < 4; ++r) tile[t * 16 * KR_TLD + (g + 4 * r) * KR_TLD + ci] = p[r];
         }
-        request(min(s + 1, a.nsteps - 1), nxt);
+        request(min(s + 1, nsteps - 1), nxt);
         __syncthreads();
         // Q = Fb P^T: B operand of k-block q is P[a = ci][b = 4 q + g]; the result has b in the registers, a on the lanes
 #pragma unroll
@@ -310,7 +340,7 @@ __global__ __launch_bounds__(256) void kron_chain_kernel(KronArgs a)
     }
     KR_STAMP(6);
     // ---- staging image: transposed [entry][column] (row stride KR_SLD), else [column][entry] (the global image)
-    const int par = a.nsteps & 1;
+    const int par = nsteps & 1;
 #pragma unroll
     for (int t = 0; t < KR_NC; ++t) {
         const int cl = KR_NC * w + t;
@@ -321,8 +351,16 @@ __global__ __launch_bounds__(256) void kron_chain_kernel(KronArgs a)
         }
     }
     __syncthreads();
-    double *o = a.out + (long)unit * a.out_su;
-    if (a.transpose_out) {  // out[c][i] = X[i][c]: row i of the image is 16 consecutive doubles at c0 + 256 i
+    double *o = ou;
+    if constexpr (WT) {  // transposed, as below, each 16 bytes with one write-through store
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(o, 0, KR_N * KR_N * (int)sizeof(double), 0x00020000);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const int e = 2 * (tid + 256 * k), i = e >> 4, cl = e & 15;
+            __builtin_amdgcn_raw_buffer_store_b128(*reinterpret_cast<const kr_u4 *>(lds + i * KR_SLD + cl), rs,
+                                                   (c0 + KR_N * i + cl) * (int)sizeof(double), 0, 16 /* sc1 */);
+        }
+    } else if (a.transpose_out) {  // out[c][i] = X[i][c]: row i of the image is 16 consecutive doubles at c0 + 256 i
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             const int e = 2 * (tid + 256 * k), i = e >> 4, cl = e & 15;
@@ -335,8 +373,107 @@ __global__ __launch_bounds__(256) void kron_chain_kernel(KronArgs a)
             *reinterpret_cast<double2 *>(o + (long)KR_N * c0 + e) = *reinterpret_cast<const double2 *>(lds + e);
         }
     }
+}
+
+// unit and first column of a workgroup.  XG: the 16 workgroups of a unit share an XCD (blockIdx.x % 8, as the flush kernels
+// place units): each of them reads all of C and the image, which then come into one L2 once instead of into eight
+template <bool XG>
+__device__ __forceinline__ void kr_place(int &unit, int &c0)
+{
+    const unsigned bq = XG ? blockIdx.x >> 3 : blockIdx.x;
+    unit = XG ? (bq / (KR_N / KR_COLS)) * 8 + (blockIdx.x & 7) : bq / (KR_N / KR_COLS);
+    c0 = KR_COLS * (bq % (KR_N / KR_COLS));
+}
+
+template <bool PF>
+__global__ __launch_bounds__(256) void kron_chain_kernel(KronArgs a)
+{
+    __shared__ __attribute__((aligned(16))) double lds[PF ? KR_LDS_PF : KR_LDS];
+#ifndef KR_NO_XCD_GROUPS
+    constexpr bool XG = PF;
+#else
+    constexpr bool XG = false;
+#endif
+    int unit, c0;
+    kr_place<XG>(unit, c0);
+    if (unit >= a.n_units) return;
+    KR_STAMP(0);
+    KR_STAMP_RT(1);
+    kr_chain<PF, false>(a, a.st, a.nsteps, a.X0 + (long)unit * a.x_su, a.out + (long)unit * a.out_su, unit, c0, lds);
     KR_STAMP(7);
     KR_STAMP_RT(8);
+}
+
+// wrap_greens! in one launch (engine.cpp: wrap_greens_kron): both one-step chains, st[0] from X0 into out (= P', stored
+// transposed) and st[1] from out into wrap_out (transposed again).  A unit's second step reads columns of out that all 16
+// workgroups of the unit wrote, and nothing of any other unit, so the hand-off is per unit: write-through (sc1) stores of
+// P', every wave drains them, then one lane per workgroup adds to the unit's arrival word (agent scope, relaxed), polls it
+// until the unit's 16 workgroups of this launch are in (the words are never cleared: wrap_target counts all launches so
+// far), and takes one agent-scope acquire for the workgroup's plain loads of P'.  The grid must be co-resident
+// (launch_kron_wrap checks it); the poll is bounded all the same: a time-out sets bit 5 of the error word and runs through.
+constexpr unsigned KR_SPIN = 1000000u;  // ~1 s of polling; the wait is a few microseconds
+template <bool PF>
+__global__ __launch_bounds__(256) void kron_wrap_kernel(KronArgs a)
+{
+    __shared__ __attribute__((aligned(16))) double lds[PF ? KR_LDS_PF : KR_LDS];
+#ifndef KR_NO_XCD_GROUPS
+    constexpr bool XG = true;
+#else
+    constexpr bool XG = false;
+#endif
+    int unit, c0;
+    kr_place<XG>(unit, c0);
+    if (unit >= a.n_units) return;
+    KR_STAMP(0);
+    KR_STAMP_RT(1);
+    double *mid = a.out + (long)unit * a.out_su;
+    kr_chain<PF, true>(a, a.st, 1, a.X0 + (long)unit * a.x_su, mid, unit, c0, lds);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave, before the arrival below
+    KR_STAMP(7);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned *cnt = a.wrap_cnt + KR_CNT_STRIDE * unit;
+        __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        bool in = false;
+        for (unsigned s = 0; s < KR_SPIN && !in; ++s) {
+            in = (int)(__hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - a.wrap_target) >= 0;
+            if (!in) __builtin_amdgcn_s_sleep(2);
+        }
+        if (!in) atomicOr(a.errflag, 32);
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    __syncthreads();
+    KR_STAMP(9);
+    kr_chain<false, false>(a, a.st + 1, 1, mid, a.wrap_out + (long)unit * a.out_su, unit, c0, lds);
+    KR_STAMP(10);
+    KR_STAMP_RT(8);
+}
+
+int kron_wrap_blocks_per_cu(bool pf)
+{
+    int nb = 0;
+    const hipError_t e = pf ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kron_wrap_kernel<true>, 256, 0)
+                            : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kron_wrap_kernel<false>, 256, 0);
+    return e == hipSuccess ? nb : 0;
+}
+
+hipError_t launch_kron_wrap(const KronArgs &a, hipStream_t s, hipEvent_t start, hipEvent_t stop)
+{
+    if (a.nsteps != 2 || a.nb < 1 || a.nb > 2 || !a.transpose_out || a.col_d || !a.wrap_out || !a.wrap_cnt || !a.errflag)
+        return hipErrorInvalidValue;
+    if (a.x_su < KR_N * KR_N || a.out_su < KR_N * KR_N) return hipErrorInvalidValue;
+    if (a.pf_img && (a.pf_site0 < 0 || a.pf_site0 % 64 != 0 || a.pf_site0 + 64 > KR_N || a.pf_img_su < LU_STRIDE))
+        return hipErrorInvalidValue;
+    const dim3 gridx(kron_wrap_grid(a.n_units)), block(256);
+    if (a.pf_img) {
+        if (start) hipExtLaunchKernelGGL(kron_wrap_kernel<true>, gridx, block, 0, s, start, stop, 0, a);
+        else hipLaunchKernelGGL(kron_wrap_kernel<true>, gridx, block, 0, s, a);
+    } else {
+        if (start) hipExtLaunchKernelGGL(kron_wrap_kernel<false>, gridx, block, 0, s, start, stop, 0, a);
+        else hipLaunchKernelGGL(kron_wrap_kernel<false>, gridx, block, 0, s, a);
+    }
+    return hipGetLastError();
 }
 
 hipError_t launch_kron_chain(const KronArgs &a, hipStream_t s, hipEvent_t start, hipEvent_t stop)
