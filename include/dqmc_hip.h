@@ -252,6 +252,58 @@ int dqmc_export_susceptibilities(dqmc_handle *h, void *device_out);
 int dqmc_set_current_targets(dqmc_handle *h, const int32_t *trg_of, int32_t K, const double *T);
 int dqmc_current_targets_fast_path(dqmc_handle *h, int32_t *fast);
 
+/* ---- error bars: logarithmic binning per walker on the device ------------------------------------------------
+ * The observable of a DQMCMeasurement is a BinningAnalysis LogBinner (measurements/generic.jl:35-39, default capacity
+ * _default_capacity :68-88), and mean / var / std_error / tau are answered from it (generic.jl:58-61,
+ * Measurements.jl:85-88).  Here there is one binner per (walker, scalar element) of a section, L = ceil(log2(capacity +
+ * 1)) levels, state on the device as [level][walker][element] for each of x_sum, x2_sum and the one-value compressor:
+ * (3 L - 1) * n_walkers * n_elements doubles per section (the top level has no compressor).  push(x), with t pushes
+ * before it: for l = 0, 1, ...: x_sum[l] += x, x2_sum[l] += x^2; if bit l of t is 0, keep x in the compressor and stop,
+ * else x = (compressor[l] + x) / 2 and go on.  count[l] = floor(T / 2^l) after T pushes, the same for every element:
+ * kept on the host.  Per level, n = count[l]: var = x2_sum/(n-1) - x_sum^2/(n(n-1)), varN = var/n, std_error =
+ * sqrt(max(varN, 0)), tau = (varN(l)/varN(0) - 1)/2, mean = x_sum[0]/count[0]; NaN errors below two samples.  The
+ * reliable level is the last one with count >= 32 (level 0 if there is none).
+ * The W walkers of a handle are independent chains: mean = sum_w mean_w / W, std_error = sqrt(sum_w varN_w(l)) / W,
+ * tau = (sum_w varN_w(l) / sum_w varN_w(0) - 1)/2, and a second estimate that needs no binning, std_error_walkers =
+ * sqrt(sum_w (mean_w - mean)^2 / (W (W - 1))) (NaN for W = 1).
+ * Sections and their element order (the accumulator layouts above without the trailing sample count):
+ *   DQMC_BIN_GREENS            [G: B*n*n][1 - G_ii: B*n]   (no G.^2 block: the binner supersedes it)
+ *   DQMC_BIN_CORRELATIONS      [cdc][sdc_x][sdc_y][sdc_z][mx][my][mz]
+ *   DQMC_BIN_PAIRING           [n_dirs x K x K]
+ *   DQMC_BIN_SUSCEPTIBILITIES  [cds][sds_x][sds_y][sds_z][ps if local targets][ccs if current targets]
+ *   DQMC_BIN_USER              n_elements samples per walker supplied by the caller
+ * Once a section is enabled, its dqmc_accumulate_* call also pushes every walker's sample, read in place from the
+ * buffers the measurement kernels leave behind, after those kernels and on the same stream; the accumulators receive
+ * exactly what they receive without a binner.  A push beyond the capacity fails with DQMC_ERR_STATE before anything is
+ * accumulated (the reference: OverflowError).  dqmc_reset_accumulators clears the binners too.  With no binner enabled
+ * nothing is allocated or launched. */
+enum { DQMC_BIN_GREENS = 0, DQMC_BIN_CORRELATIONS = 1, DQMC_BIN_PAIRING = 2, DQMC_BIN_SUSCEPTIBILITIES = 3,
+       DQMC_BIN_USER = 4 };
+/* LogBinner(zero, capacity = capacity) for every walker and element of a measurement section (generic.jl:39);
+ * capacity 0 = 100000.  The section's measurement must be configured (pair directions, local / current targets; the
+ * susceptibilities also need dqmc_prepare); if its layout changes afterwards, enable again.  Enabling again starts anew. */
+int dqmc_binner_enable(dqmc_handle *h, int32_t which, int64_t capacity);
+/* elements per walker, levels and pushes so far (length(obs), BinningAnalysis' count at level 0) */
+int dqmc_binner_size(dqmc_handle *h, int32_t which, size_t *n_elements, int32_t *n_levels, int64_t *n_pushed);
+/* the level std_error(obs) and tau(obs) use (generic.jl:60-61): the last one with at least 32 entries */
+int dqmc_binner_reliable_level(dqmc_handle *h, int32_t which, int32_t *level);
+/* x_sum and x2_sum (n_elements doubles each, either may be NULL) and the count of one level of one walker */
+int dqmc_binner_get_level(dqmc_handle *h, int32_t which, int32_t walker, int32_t level,
+                          double *x_sum, double *x2_sum, int64_t *count);
+/* mean(m), std_error(m), tau(m) (generic.jl:58-61) over the walkers of the handle at `level` (< 0: the reliable one),
+ * plus the cross-walker error; host buffers of n_elements doubles, any may be NULL */
+int dqmc_binner_finish(dqmc_handle *h, int32_t which, int32_t level,
+                       double *mean, double *std_error, double *std_error_walkers, double *tau);
+/* the additive moments behind dqmc_binner_finish into a caller-owned device buffer of 4 * n_elements + 1 doubles:
+ * [sum_w mean_w][sum_w mean_w^2][sum_w varN_w(level)][sum_w varN_w(0)][W].  A multi-rank host sums the whole buffer over
+ * its ranks (same level everywhere) and applies the formulas above with W = the last entry. */
+int dqmc_binner_export_moments(dqmc_handle *h, int32_t which, int32_t level, void *device_out);
+/* a binner over samples the caller computes on the device (an observable of its own): create, then push a device
+ * buffer [n_walkers][n_elements] per sample.  The buffer must be complete when the call is made; the call returns when
+ * it has been read. */
+int dqmc_binner_user_create(dqmc_handle *h, int64_t n_elements, int64_t capacity);
+int dqmc_binner_user_push(dqmc_handle *h, const double *device_samples);
+
 /* ---- measurement reduction over ranks -------------------
  * One process (or thread) per GPU; walkers never interact, the only collective is the reduction of the measurement
  * sums every `measure_rate` sweeps (DQMC.jl:429-436).  dqmc_reduce packs EVERY accumulator of the handle (Green's

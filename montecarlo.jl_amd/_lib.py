@@ -13,6 +13,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "dqmc_hip.h")
 
 OK, ERR_INVALID, ERR_HIP, ERR_NO_DEVICE, ERR_STATE, ERR_RNG = 0, -1, -2, -3, -4, -5
 ATTRACTIVE, REPULSIVE = 0, 1
+BIN_SECTIONS = ("greens", "correlations", "pairing", "susceptibilities", "user")  # DQMC_BIN_*
 K_FAMILIES = ("gemm", "qr", "trsm", "sweep", "misc", "flush")
 
 
@@ -121,6 +122,14 @@ SIGNATURES = {
     "dqmc_susceptibilities_size": (C.c_int, [_H, C.POINTER(C.c_size_t)]),
     "dqmc_get_susceptibilities": (C.c_int, [_H, _dp]),
     "dqmc_export_susceptibilities": (C.c_int, [_H, C.c_void_p]),
+    "dqmc_binner_enable": (C.c_int, [_H, C.c_int32, C.c_int64]),
+    "dqmc_binner_size": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_size_t), C.POINTER(C.c_int32), _i64p]),
+    "dqmc_binner_reliable_level": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_int32)]),
+    "dqmc_binner_get_level": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _i64p]),
+    "dqmc_binner_finish": (C.c_int, [_H, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp]),
+    "dqmc_binner_export_moments": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_void_p]),
+    "dqmc_binner_user_create": (C.c_int, [_H, C.c_int64, C.c_int64]),
+    "dqmc_binner_user_push": (C.c_int, [_H, C.c_void_p]),
     "dqmc_comm_unique_id": (C.c_int, [C.c_void_p]),
     "dqmc_comm_init": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_H)]),
     "dqmc_comm_destroy": (C.c_int, [_H]),

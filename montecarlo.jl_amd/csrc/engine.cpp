@@ -135,6 +135,13 @@ struct dqmc_handle {
     dqmc_stats red_stats{};
     bool red_valid = false;
     size_t red_sizes[4] = {0, 0, 0, 0};  // section sizes of the LAST reduction (dqmc_get_reduced checks against these)
+    // logarithmic binners (binner.inl), one per DQMC_BIN_* section: xs, x2 [L][W][E], c [L - 1][W][E], out = finish scratch
+    struct Binner {
+        bool on = false;
+        int E = 0, L = 0;
+        int64_t cap = 0, T = 0;  // capacity and pushes so far: count[level] = T >> level for every element
+        double *xs = nullptr, *x2 = nullptr, *c = nullptr, *out = nullptr;
+    } bin[5];
 };
 
 // ---------------------------------------------------------------------------
@@ -1340,6 +1347,7 @@ int dqmc_create(const dqmc_params *p, dqmc_handle **out)
 
 static void ut_free(dqmc_handle *h);
 static int ut_reset_accumulators(dqmc_handle *h);
+static int binner_reset(dqmc_handle *h);
 int dqmc_destroy(dqmc_handle *h)
 {
     if (!h) return DQMC_OK;
@@ -1665,14 +1673,20 @@ int dqmc_get_stats(dqmc_handle *h, int32_t w, dqmc_stats *out)
     return DQMC_OK;
 }
 
+// binner.inl: binner_room refuses the call (before anything is accumulated) when the section's binner is full or its
+// layout has changed; binner_push_section pushes the samples the measurement kernels have just left on the device
+static int binner_room(dqmc_handle *h, int which);
+static int binner_push_section(dqmc_handle *h, int which);
 int dqmc_accumulate_greens(dqmc_handle *h)
 {
     ENTER(h); NEED_PREPARED(h);
+    CHK(binner_room(h, DQMC_BIN_GREENS));
     CHK(true_greens(h, h->greens));
     {
         Timed t(h, DQMC_K_MISC);
         HIPCHK(launch_accumulate(h->n, h->nb, h->W, h->tmp2, h->nn, h->acc, h->stream));
     }
+    if (h->bin[DQMC_BIN_GREENS].on) CHK(binner_push_section(h, DQMC_BIN_GREENS));
     return DQMC_OK;
 }
 static int cc_setup(dqmc_handle *h);
@@ -1720,12 +1734,14 @@ int dqmc_accumulate_correlations(dqmc_handle *h)
 {
     ENTER(h); NEED_PREPARED(h);
     if (!h->n_dirs) return fail(h, DQMC_ERR_STATE, "call dqmc_set_pair_directions first");
+    CHK(binner_room(h, DQMC_BIN_CORRELATIONS));
     CHK(true_greens(h, h->greens));
     {
         Timed t(h, DQMC_K_MISC);
         HIPCHK(launch_correlations(h->n, h->nb, h->p.model_kind, h->W, h->tmp2, h->nn, h->dir_ptr, h->pair_src,
                                    h->pair_trg, h->n_dirs, h->corr_per_walker, h->corr_acc, h->stream));
     }
+    if (h->bin[DQMC_BIN_CORRELATIONS].on) CHK(binner_push_section(h, DQMC_BIN_CORRELATIONS));
     return DQMC_OK;
 }
 int dqmc_correlations_size(dqmc_handle *h, size_t *n)
@@ -1774,12 +1790,14 @@ int dqmc_accumulate_pairing(dqmc_handle *h)
 {
     ENTER(h); NEED_PREPARED(h);
     if (!h->K_loc) return fail(h, DQMC_ERR_STATE, "call dqmc_set_local_targets first");
+    CHK(binner_room(h, DQMC_BIN_PAIRING));
     CHK(true_greens(h, h->greens));
     {
         Timed t(h, DQMC_K_MISC);
         HIPCHK(launch_pairing(h->n, h->nb, h->W, h->tmp2, h->nn, h->dir_ptr, h->pair_src, h->pair_trg, h->n_dirs,
                               h->K_loc, h->trg_of, h->pc_per_walker, h->pc_acc, h->stream));
     }
+    if (h->bin[DQMC_BIN_PAIRING].on) CHK(binner_push_section(h, DQMC_BIN_PAIRING));
     return DQMC_OK;
 }
 int dqmc_pairing_size(dqmc_handle *h, size_t *n)
@@ -1818,6 +1836,7 @@ int dqmc_reset_accumulators(dqmc_handle *h)
     if (h->corr_acc) HIPCHK(hipMemsetAsync(h->corr_acc, 0, h->corr_n * sizeof(double), h->stream));
     if (h->pc_acc) HIPCHK(hipMemsetAsync(h->pc_acc, 0, h->pc_n * sizeof(double), h->stream));
     CHK(ut_reset_accumulators(h));
+    CHK(binner_reset(h));
     return DQMC_OK;
 }
 int dqmc_get_accumulators(dqmc_handle *h, double *host_out)
@@ -1836,6 +1855,7 @@ int dqmc_export_accumulators(dqmc_handle *h, void *device_out)
 }
 
 #include "unequal_time.inl"
+#include "binner.inl"
 
 // ---------------------------------------------------------------------------
 // Measurement reduction over ranks: every accumulator the handle keeps and the DQMCAnalysis

@@ -409,6 +409,22 @@ hipError_t launch_cc_slice(const CCPlan &p, int n, int nb, int n_walkers, double
                            const double *G0l, const double *Gl0, const double *Gll, long stride_unit,
                            const int *dir_ptr, const int *pair_src, const int *pair_trg, int n_dirs,
                            double *per_walker, long per_stride, long offset, hipStream_t s);
+// logarithmic binning (binner.hip).  Where a push reads its W x E samples: PLAIN = scale * src[w][e]; GREENS = the true
+// G of every unit and the occupation 1 - G_ii; CORR = src [w][4 n_dirs] followed by mx, my (zero) and mz from G.
+// State: xs, x2 [L][W][E], c [L - 1][W][E]; lmax = trailing 1-bits of the number of pushes so far (< L).
+enum { BIN_SRC_PLAIN = 0, BIN_SRC_GREENS = 1, BIN_SRC_CORR = 2 };
+struct BinPush {
+    int mode = BIN_SRC_PLAIN;
+    const double *src = nullptr, *G = nullptr;
+    long stride_unit = 0;
+    int n = 0, nb = 1, model = 0, n_dirs = 0;
+    double scale = 1.0;
+};
+hipError_t launch_binner_push(const BinPush &p, int W, int E, int L, int lmax, double *xs, double *x2, double *c,
+                              hipStream_t s);
+// out [8 E + 1]: mean, std_error, std_error_walkers, tau, sum mean_w, sum mean_w^2, sum varN_w(level), sum varN_w(0), W
+hipError_t launch_binner_finish(int W, int E, long T, int level, const double *xs, const double *x2, double *out,
+                                hipStream_t s);
 // HS field <-> Julia BitArray chunks (compress / decompress, HubbardModel.jl:56-59)
 hipError_t launch_conf_pack(const int8_t *conf, size_t n_elem, unsigned long long *chunks, hipStream_t s);
 hipError_t launch_conf_unpack(const unsigned long long *chunks, size_t n_elem, int8_t *conf, hipStream_t s);

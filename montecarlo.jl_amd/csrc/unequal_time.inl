@@ -717,6 +717,7 @@ int dqmc_accumulate_susceptibilities(dqmc_handle *h, int32_t recalculate)
     if (recalculate < 1) return fail(h, DQMC_ERR_INVALID, "recalculate must be positive");
     UTStack *u = h->ut;
     CHK(ut_sus_layout(h));
+    CHK(binner_room(h, DQMC_BIN_SUSCEPTIBILITIES));
     const long total = (long)u->sus_n - 1;
     CHK(true_greens(h, h->greens));                                 // G00 = greens!(mc)
     CHK(copy_mat(h, u->g00, h->tmp2));
@@ -746,6 +747,7 @@ int dqmc_accumulate_susceptibilities(dqmc_handle *h, int32_t recalculate)
         Timed t(h, DQMC_K_MISC);
         HIPCHK(launch_sus_reduce(h->W, total, h->p.delta_tau, u->sus_per_walker, u->sus_acc, h->stream));
     }
+    if (h->bin[DQMC_BIN_SUSCEPTIBILITIES].on) CHK(binner_push_section(h, DQMC_BIN_SUSCEPTIBILITIES));
     return dqmc_synchronize(h);
 }
 int dqmc_susceptibilities_size(dqmc_handle *h, size_t *n)

@@ -221,6 +221,7 @@ class DQMC:
                                         measure_rate=measure_rate, check_sign_problem=check_sign_problem,
                                         check_propagation_error=check_propagation_error, **kw)
         self.n_walkers = n_walkers
+        self._device_id = device_id
         self.N = len(model.l)
         self.nb = model.flv
         self.last_sweep = 0
@@ -398,19 +399,22 @@ class DQMC:
                     tail[-1] += 1
         return self.accumulators() + tail
 
-    def run(self, verbose=False, on_measure=None, recorder=None, measurements=("greens",)):
+    def run(self, verbose=False, on_measure=None, recorder=None, measurements=("greens",), binning=False):
         """run!(mc) (DQMC.jl:369-515) without the host-side measurement framework: the selected
         measurements are accumulated on the device every `measure_rate`-th sweep after thermalization,
         at current_slice == 1 && direction == +1 (DQMC.jl:425-436).  `measurements` may contain
         "greens" (greens_measurement, occupation), "correlations" (charge/spin density correlations,
         magnetization; needs set_pair_directions), "pairing" (needs set_local_targets) and
-        "susceptibilities" (the CombinedGreensIterator measurements)."""
+        "susceptibilities" (the CombinedGreensIterator measurements).  `binning=True` enables the device-side
+        LogBinner of every selected measurement before the first sweep (enable_binning; read with binned())."""
         known = {"greens": lib().dqmc_accumulate_greens, "correlations": lib().dqmc_accumulate_correlations,
                  "pairing": lib().dqmc_accumulate_pairing}
         for m in measurements:
             if m not in known and m != "susceptibilities":
                 raise ValueError("unknown measurement %r" % (m,))
         self.prepare()
+        if binning:  # a resumed run! keeps the binners it has (DQMC.jl:395-411)
+            self.enable_binning([m for m in measurements if not self._binning_enabled(m)])
         if self.last_sweep == 0:  # a resumed run! keeps the measurement state (DQMC.jl:395-411)
             self.reset_accumulators()
         total = self.p.thermalization + self.p.sweeps
@@ -558,6 +562,161 @@ class DQMC:
         G2 = [acc[(B + b) * n * n:(B + b + 1) * n * n].reshape((n, n), order="F") / cnt for b in range(B)]
         occ = [acc[2 * B * n * n + b * n:2 * B * n * n + (b + 1) * n] / cnt for b in range(B)]
         return dict(G=G, G2=G2, occupation=occ, count=cnt)
+
+    # ---- error bars: per-walker logarithmic binning on the device (include/dqmc_hip.h "error bars")
+    @staticmethod
+    def _bin(which):
+        if which not in _lib.BIN_SECTIONS:
+            raise ValueError("unknown binner section %r" % (which,))
+        return _lib.BIN_SECTIONS.index(which)
+
+    @staticmethod
+    def _capacity(capacity):
+        if capacity is None:
+            return 0  # the library's default, 100000
+        if int(capacity) < 1:
+            raise _lib.DQMCError(_lib.ERR_INVALID, "binner capacity must be at least 1")
+        return int(capacity)
+
+    def enable_binning(self, which=("greens",), capacity=None):
+        """a LogBinner (capacity: default 100000) per walker and element of the given measurement sections; from then
+        on every accumulate_* of such a section also pushes each walker's sample.  Costs
+        (3 L - 1) * n_walkers * n_elements doubles of device memory per section, L = ceil(log2(capacity + 1))."""
+        cap = self._capacity(capacity)
+        for m in ((which,) if isinstance(which, str) else which):
+            if m == "user":
+                raise ValueError("the user binner is made by user_binner(n_elements)")
+            self._c(lib().dqmc_binner_enable(self._h, self._bin(m), cap))
+            self._binned = getattr(self, "_binned", set()) | {m}
+
+    def _binning_enabled(self, which):
+        return which in getattr(self, "_binned", ())
+
+    def user_binner(self, n_elements, capacity=None):
+        """a binner over `n_elements` samples per walker that the caller computes on the device"""
+        self._c(lib().dqmc_binner_user_create(self._h, int(n_elements), self._capacity(capacity)))
+
+    def user_push(self, samples):
+        """push one sample [n_walkers, n_elements]: a contiguous float64 device tensor (torch) or a device address"""
+        if hasattr(samples, "data_ptr"):
+            E = self.binner_size("user")[0]
+            if str(samples.dtype) != "torch.float64" or not samples.is_contiguous() or not samples.is_cuda \
+                    or samples.numel() != self.n_walkers * E:
+                raise ValueError("samples must be a contiguous float64 device tensor of n_walkers x %d" % E)
+            import torch
+            torch.cuda.current_stream(samples.device).synchronize()  # the engine reads it on its own stream
+            samples = samples.data_ptr()
+        self._c(lib().dqmc_binner_user_push(self._h, C.c_void_p(samples)))
+
+    def binner_size(self, which="greens"):
+        """-> (elements per walker, levels, pushes so far)"""
+        n, L, T = C.c_size_t(), C.c_int32(), C.c_int64()
+        self._c(lib().dqmc_binner_size(self._h, self._bin(which), C.byref(n), C.byref(L), C.byref(T)))
+        return n.value, L.value, T.value
+
+    def binner_reliable_level(self, which="greens"):
+        lv = C.c_int32()
+        self._c(lib().dqmc_binner_reliable_level(self._h, self._bin(which), C.byref(lv)))
+        return lv.value
+
+    def binner_level(self, which, walker, level):
+        """-> (x_sum, x2_sum, count) of one level of one walker's binners (inspection)"""
+        E = self.binner_size(which)[0]
+        xs, x2, cnt = np.zeros(E), np.zeros(E), C.c_int64()
+        self._c(lib().dqmc_binner_get_level(self._h, self._bin(which), walker, level, dptr(xs), dptr(x2), C.byref(cnt)))
+        return xs, x2, cnt.value
+
+    def binned_raw(self, which="greens", level=None):
+        """-> dict of flat arrays in the section's element order: mean, std_error (binning, at `level` or the reliable
+        one), std_error_walkers (cross-walker), tau; count (pushes per walker) and reliable_level"""
+        E, _, T = self.binner_size(which)
+        out = {k: np.zeros(E) for k in ("mean", "std_error", "std_error_walkers", "tau")}
+        self._c(lib().dqmc_binner_finish(self._h, self._bin(which), -1 if level is None else level,
+                                         *[dptr(out[k]) for k in ("mean", "std_error", "std_error_walkers", "tau")]))
+        out["count"] = T
+        out["reliable_level"] = self.binner_reliable_level(which)
+        return out
+
+    def _bin_fields(self, which):
+        """[(name, offset, size, shape or None)] of a section, in the layouts of include/dqmc_hip.h"""
+        n, B = self.N, self.nb
+        nd, K, Kcc = getattr(self, "_ndirs", 0), getattr(self, "_K", 0), getattr(self, "_Kcc", 0)
+        if which == "greens":
+            sizes = [("G", B * n * n, None), ("occupation", B * n, None)]
+        elif which == "correlations":
+            sizes = [(k, nd, None) for k in ("CDC", "SDCx", "SDCy", "SDCz")] + [(k, n, None) for k in ("Mx", "My", "Mz")]
+        elif which == "pairing":
+            sizes = [("PC", nd * K * K, (nd, K, K))]
+        elif which == "susceptibilities":
+            sizes = [(k, nd, None) for k in ("CDS", "SDSx", "SDSy", "SDSz")]
+            if K:
+                sizes.append(("PS", nd * K * K, (nd, K, K)))
+            if Kcc:
+                sizes.append(("CCS", nd * Kcc, (nd, Kcc)))
+        else:
+            sizes = [("x", self.binner_size("user")[0], None)]
+        out, off = [], 0
+        for name, size, shape in sizes:
+            out.append((name, off, size, shape))
+            off += size
+        return out
+
+    def _bin_shape(self, which, flat):
+        """one flat section vector -> {field: array shaped like the existing getters}"""
+        n, B, res = self.N, self.nb, {}
+        for name, off, size, shape in self._bin_fields(which):
+            v = flat[off:off + size]
+            if name == "G":
+                v = self._blocks(v)
+            elif name == "occupation":
+                v = [v[b * n:(b + 1) * n] for b in range(B)]
+            elif shape is not None:
+                v = v.reshape(shape, order="F")
+            res[name] = v
+        return res
+
+    def _bin_dict(self, which, raw):
+        res = {}
+        for key, suffix in (("mean", ""), ("std_error", "_std_error"), ("std_error_walkers", "_std_error_walkers"),
+                            ("tau", "_tau")):
+            for name, v in self._bin_shape(which, raw[key]).items():
+                res[name + suffix] = v
+        return res
+
+    def binned(self, which="greens", level=None):
+        """mean(m), std_error(m), tau(m) of a binned section over the walkers of this handle, shaped like the existing
+        getters: greens -> G, occupation (lists of blocks); correlations -> CDC, SDCx, SDCy, SDCz, Mx, My, Mz; pairing
+        -> PC[dir12, dir1, dir2]; susceptibilities -> CDS, SDSx, SDSy, SDSz, PS, CCS; user -> x.  Every field X comes with
+        X_std_error (binning error at `level`, default the reliable level), X_std_error_walkers (the cross-walker
+        error, independent of the binning) and X_tau; plus count (samples per walker) and reliable_level."""
+        raw = self.binned_raw(which, level)
+        res = self._bin_dict(which, raw)
+        res["count"] = raw["count"]
+        res["reliable_level"] = raw["reliable_level"]
+        return res
+
+    def binner_moments(self, which="greens", level=None, out=None):
+        """dqmc_binner_export_moments: the additive moments [sum mean_w][sum mean_w^2][sum varN_w(level)][sum varN_w(0)]
+        [W] as a float64 device tensor of 4 E + 1 entries (`out`, or a new torch tensor on this handle's device).  A
+        multi-rank host all-reduces (sum) the whole tensor and hands it to finish_moments."""
+        E = self.binner_size(which)[0]
+        if out is None:
+            import torch
+            out = torch.empty(4 * E + 1, dtype=torch.float64, device="cuda:%d" % self._device_id)
+        if out.numel() != 4 * E + 1 or not out.is_contiguous() or str(out.dtype) != "torch.float64":
+            raise ValueError("out must be a contiguous float64 device tensor of %d entries" % (4 * E + 1))
+        self._c(lib().dqmc_binner_export_moments(self._h, self._bin(which), -1 if level is None else level,
+                                                 C.c_void_p(out.data_ptr())))
+        return out
+
+    def finish_moments(self, buf, which=None):
+        """finish_moments(buf), and with `which` the result shaped like binned(which)"""
+        raw = finish_moments(buf)
+        if which is None:
+            return raw
+        res = self._bin_dict(which, raw)
+        res["n_walkers"] = raw["n_walkers"]
+        return res
 
     # ---- equal-time correlations (charge_density_correlation, spin_density_correlation, magnetization)
     def set_pair_directions(self, iterator):
@@ -747,6 +906,24 @@ class DQMC:
         n = np.zeros(len(_lib.K_FAMILIES), dtype=np.int64)
         self._c(lib().dqmc_timing_get(self._h, dptr(ms), i64ptr(n)))
         return {k: (float(ms[i]), int(n[i])) for i, k in enumerate(_lib.K_FAMILIES)}
+
+
+def finish_moments(buf):
+    """Reduced binner moments (DQMC.binner_moments summed over ranks: [sum mean_w][sum mean_w^2][sum varN_w(level)]
+    [sum varN_w(0)][W]) -> dict of flat arrays mean, std_error, std_error_walkers, tau and n_walkers, with the formulas of
+    include/dqmc_hip.h: mean = S1/W, std_error = sqrt(Vl)/W, tau = (Vl/V0 - 1)/2, std_error_walkers =
+    sqrt((S2 - S1^2/W) / (W (W - 1)))."""
+    if hasattr(buf, "detach"):
+        buf = buf.detach().cpu().numpy()
+    buf = np.asarray(buf, dtype=np.float64)
+    E, W = (buf.size - 1) // 4, buf[-1]
+    if buf.ndim != 1 or buf.size != 4 * E + 1 or W < 1:
+        raise ValueError("not a binner moment buffer")
+    s1, s2, vl, v0 = (buf[i * E:(i + 1) * E] for i in range(4))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        between = np.maximum(s2 - s1 * s1 / W, 0.0) / (W * (W - 1)) if W >= 2 else np.full(E, np.nan)
+        return dict(mean=s1 / W, std_error=np.sqrt(np.where(vl < 0, 0.0, vl)) / W, std_error_walkers=np.sqrt(between),
+                    tau=0.5 * (vl / v0 - 1.0), n_walkers=int(W))
 
 
 # ---------------------------------------------------------------------------
