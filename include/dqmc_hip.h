@@ -484,6 +484,48 @@ typedef struct {
 int dqmc_mc_get_global_stats(dqmc_mc_handle *h, int32_t walker, dqmc_mc_global_stats *out);
 int dqmc_mc_synchronize(dqmc_mc_handle *h);
 
+/* ---- error bars of the MC flavor: one logarithmic binner per walker, pushed inside the sweep --------------------
+ * measure! of IsingEnergyMeasurement / IsingMagnetizationMeasurement pushes E, E^2, |M| and M^2 into Observables
+ * (models/Ising/measurements.jl:30-35,72-78), and finish! takes their means (:37-42,80-85).  Here
+ * every walker has one binner over the four elements [E, E2, M, M2] (M = |M|) under the contract of "error bars" above:
+ * L = ceil(log2(capacity + 1)) levels; per level and walker x_sum[4], x2_sum[4], a one-value compressor [4] (none on the
+ * top level) and the cross sums xy_sum[2] of the pairs (E, E2) and (M, M2), which take the product of the pair's two
+ * level-l values wherever x2_sum[l] takes the squares.  Device layout [level][element][walker].  All walkers measure at
+ * the same sweeps, so the push count T and count[l] = floor(T / 2^l) are host integers.  Per level, n = count[l]:
+ * varN as above, covN = (xy_sum/(n-1) - x_sum y_sum/(n(n-1)))/n, NaN below two samples; this is what the error of
+ * C = beta^2/N (<E2> - <E>^2) and chi = beta/N (<M2> - <M>^2) (measurements.jl:40,83) needs:
+ * var(C) = (beta^2/N)^2 (varN(E2) - 4 <E> covN(E, E2) + 4 <E>^2 varN(E)).
+ * Once enabled, dqmc_mc_sweep pushes every measurement it takes, in the sweep kernel itself (and right after the
+ * cluster move for a measurement that follows one); the sums, series and chains are exactly those of a handle without
+ * a binner.  dqmc_mc_sweep counts the measurements of a call beforehand: if they would pass the capacity it returns
+ * DQMC_ERR_STATE and nothing has run (the reference: OverflowError of push!).  dqmc_mc_reset_accumulators clears the
+ * binner and its count; dqmc_mc_global_move takes no measurement and pushes nothing.  With the binner off nothing is
+ * allocated and the launches are those of a handle that never had one. */
+/* LogBinner(zero, capacity = capacity) behind each Observable (measurements/generic.jl:39; capacity 0 = 100000,
+ * generic.jl:68-88).  Enabling again starts anew. */
+int dqmc_mc_binner_enable(dqmc_mc_handle *h, int64_t capacity);
+/* levels and pushes so far (length of the Observables measure! pushes into, measurements.jl:30-35); either may be NULL */
+int dqmc_mc_binner_size(dqmc_mc_handle *h, int32_t *n_levels, int64_t *n_pushed);
+/* the level std_error and tau use (generic.jl:60-61): the last one with count >= 32, else 0 */
+int dqmc_mc_binner_reliable_level(dqmc_mc_handle *h, int32_t *level);
+/* the sums of one level of one walker in element order [E, E2, M, M2] / pair order [(E, E2), (M, M2)] and the level's
+ * count; any output may be NULL */
+int dqmc_mc_binner_get_level(dqmc_mc_handle *h, int32_t walker, int32_t level,
+                             double x_sum[4], double x2_sum[4], double xy_sum[2], int64_t *count);
+/* mean, std_error^2 and tau of the Observables of one walker (generic.jl:58-61; mean(m.E), mean(m.E2) of finish!,
+ * measurements.jl:38-39,81-82) and the covariances behind the errors of C and chi (measurements.jl:40,83) */
+typedef struct {
+    double mean[4];   /* x_sum[0] / count[0] */
+    double varN[4];   /* at `level`; std_error = sqrt(max(varN, 0)) */
+    double varN0[4];  /* at level 0 */
+    double tau[4];    /* (varN / varN0 - 1) / 2 */
+    double covN[2];   /* at `level`, pairs (E, E2) and (M, M2) */
+    int64_t count;    /* count[level] */
+    int32_t level;    /* the level used */
+} dqmc_mc_binned;
+/* level < 0: the reliable level */
+int dqmc_mc_binner_finish(dqmc_mc_handle *h, int32_t walker, int32_t level, dqmc_mc_binned *out);
+
 /* ---- instrumentation ------------------------------------------------------ */
 /* Per-kernel-family device time accumulated with HIP events on the handle's
  * stream when enabled (off by default; used by bench.py's roofline leg). */

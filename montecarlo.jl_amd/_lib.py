@@ -59,6 +59,11 @@ class McGlobalStats(C.Structure):
                 ("moves_drawn", C.c_uint64)]
 
 
+class McBinned(C.Structure):
+    _fields_ = [("mean", C.c_double * 4), ("varN", C.c_double * 4), ("varN0", C.c_double * 4), ("tau", C.c_double * 4),
+                ("covN", C.c_double * 2), ("count", C.c_int64), ("level", C.c_int32)]
+
+
 _dp = C.POINTER(C.c_double)
 _i64p = C.POINTER(C.c_int64)
 _H = C.c_void_p
@@ -170,6 +175,11 @@ SIGNATURES = {
     "dqmc_mc_global_move": (C.c_int, [_H, C.c_int32]),
     "dqmc_mc_get_global_stats": (C.c_int, [_H, C.c_int32, C.POINTER(McGlobalStats)]),
     "dqmc_mc_synchronize": (C.c_int, [_H]),
+    "dqmc_mc_binner_enable": (C.c_int, [_H, C.c_int64]),
+    "dqmc_mc_binner_size": (C.c_int, [_H, C.POINTER(C.c_int32), _i64p]),
+    "dqmc_mc_binner_reliable_level": (C.c_int, [_H, C.POINTER(C.c_int32)]),
+    "dqmc_mc_binner_get_level": (C.c_int, [_H, C.c_int32, C.c_int32, _dp, _dp, _dp, _i64p]),
+    "dqmc_mc_binner_finish": (C.c_int, [_H, C.c_int32, C.c_int32, C.POINTER(McBinned)]),
     "dqmc_timing_enable": (C.c_int, [_H, C.c_int32]),
     "dqmc_timing_get": (C.c_int, [_H, _dp, _i64p]),
     "dqmc_mfma_f64_peak": (C.c_int, [C.c_int32, C.c_int32, _dp]),

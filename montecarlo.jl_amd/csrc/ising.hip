@@ -72,6 +72,55 @@ struct DevState {
 // flat index of lane `w` in the [row][W] arrays
 __device__ __forceinline__ size_t at(int row, int W, int w) { return (size_t)row * W + w; }
 
+// push!(observable, value) of IsingEnergyMeasurement / IsingMagnetizationMeasurement (measurements.jl:30-35,72-78) into
+// the walker's logarithmic binner (include/dqmc_hip.h, "error bars of the MC flavor"): elements [E, E2, M, M2] with
+// M = |M|, state [level][element][walker] for x_sum, x2_sum and the compressor, [level][pair][walker] for the cross
+// sums of (E, E2) and (M, M2).  lmax = trailing 1-bits of the push count, the same in every lane: levels below it
+// complete a pair with their compressor and carry the average upwards, level lmax keeps the value (top = the last
+// level, which has no compressor).  A level's values are requested together; levels above lmax are not touched.
+__device__ __forceinline__ void ising_bin_push(double *__restrict__ xs, double *__restrict__ x2,
+                                               double *__restrict__ xy, double *__restrict__ c, int W, int w, int lmax,
+                                               int top, double e, double m)
+{
+    double x[4] = {e, e * e, m, m * m};
+    const size_t sW = (size_t)W;
+    size_t a4 = (size_t)w, a2 = (size_t)w;
+    for (int l = 0; l < lmax; ++l, a4 += 4 * sW, a2 += 2 * sW) {
+        double s1[4], s2[4], cc[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            s1[k] = xs[a4 + k * sW];
+            s2[k] = x2[a4 + k * sW];
+            cc[k] = c[a4 + k * sW];
+        }
+        const double p0 = xy[a2], p1 = xy[a2 + sW];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            xs[a4 + k * sW] = s1[k] + x[k];
+            x2[a4 + k * sW] = s2[k] + x[k] * x[k];
+        }
+        xy[a2] = p0 + x[0] * x[1];
+        xy[a2 + sW] = p1 + x[2] * x[3];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) x[k] = 0.5 * (cc[k] + x[k]);
+    }
+    double s1[4], s2[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        s1[k] = xs[a4 + k * sW];
+        s2[k] = x2[a4 + k * sW];
+    }
+    const double p0 = xy[a2], p1 = xy[a2 + sW];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        xs[a4 + k * sW] = s1[k] + x[k];
+        x2[a4 + k * sW] = s2[k] + x[k] * x[k];
+        if (lmax < top) c[a4 + k * sW] = x[k];
+    }
+    xy[a2] = p0 + x[0] * x[1];
+    xy[a2 + sW] = p1 + x[2] * x[3];
+}
+
 // the neighbour table is a kernel argument of its own, read-only and not aliased: that is what lets the compiler read
 // a row with one scalar load (a member of DevState would be an ordinary pointer the kernel's stores might alias)
 template <int Z>
@@ -163,6 +212,119 @@ __global__ __launch_bounds__(WAVE) void ising_sweep_kernel(DevState s, const int
     s.n_series[w] = n_series;
     s.prop[w] += (long long)n_sweeps * N;
     s.acc[w] += acc;
+}
+
+// ising_sweep_kernel with the binner on: the same chain, and every measurement is pushed where it is taken.  T = pushes
+// before this launch (all walkers of a handle measure at the same sweeps, so one count serves them all and the cascade
+// length of a push is the same in every lane).  The site loop is a copy, not a shared helper: routed through one, the
+// eight forms above come out with other registers and another instruction order.
+template <int Z>
+__global__ __launch_bounds__(WAVE) void ising_sweep_binned_kernel(DevState s, const int4 *__restrict__ nbr,
+                                                                  int n_sweeps, long long first_sweep,
+                                                                  long long thermalization, int measure_rate,
+                                                                  long long deferred_sweep, double *__restrict__ bxs,
+                                                                  double *__restrict__ bx2, double *__restrict__ bxy,
+                                                                  double *__restrict__ bc, int top, long long T)
+{
+    extern __shared__ unsigned int sp[];
+    const int lane = threadIdx.x;
+    const int w = blockIdx.x * WAVE + lane;
+    if (w >= s.W) return;
+    const int N = s.N, nw = s.nw, W = s.W;
+    for (int j = 0; j < nw; ++j) sp[j * WAVE + lane] = s.conf[at(j, W, w)];
+    const unsigned long long key = s.key[w];
+    unsigned long long draw = s.draw[w];
+    int E = s.E[w], M = s.M[w];
+    double thr[Z];
+#pragma unroll
+    for (int k = 0; k < Z; ++k) thr[k] = s.thr[at(k, W, w)];
+    double sE = s.sE[w], sE2 = s.sE2[w], sM = s.sM[w], sM2 = s.sM2[w];
+    long long n_meas = s.n_meas[w], n_series = s.n_series[w], acc = 0;
+
+    for (int sw = 0; sw < n_sweeps; ++sw) {
+        int cw = 0;
+        unsigned int cur = sp[lane];
+        int4 r0 = nbr[0], r1 = nbr[1];  // row of site 0; the row of site i + 1 is requested while site i runs
+        for (int i = 0; i < N; ++i) {
+            const int iw = i >> 5, ib = i & 31;
+            if (iw != cw) {  // uniform: the previous word is complete
+                sp[cw * WAVE + lane] = cur;
+                cw = iw;
+                cur = sp[cw * WAVE + lane];
+            }
+            const int row[8] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w};
+            r0 = nbr[2 * i + 2];  // (the table holds N + 1 rows)
+            r1 = nbr[2 * i + 3];
+            int up = 0;
+#pragma unroll
+            for (int k = 0; k < Z; ++k) {
+                const int j = row[k], jw = j >> 5;
+                const unsigned int v = jw == iw ? cur : sp[jw * WAVE + lane];
+                up += (v >> (j & 31)) & 1u;
+            }
+            const int si = (cur >> ib) & 1u;
+            const int sum = 2 * up - Z;         // sum of the neighbours' spins
+            const int k = si ? sum : -sum;      // dE / 2
+            bool accept = k <= 0;
+            if (k > 0) {
+                const double u = dqmc::philox_uniform(key, draw);
+                ++draw;
+                double t = thr[0];
+#pragma unroll
+                for (int q = 1; q < Z; ++q) t = k == q + 1 ? thr[q] : t;
+                accept = u < t;
+            }
+            if (accept) {
+                cur ^= 1u << ib;
+                E += 2 * k;
+                M += si ? -2 : 2;
+                ++acc;
+            }
+        }
+        sp[cw * WAVE + lane] = cur;
+        const long long g = first_sweep + sw;  // global 1-based sweep index (MC.jl:262-283)
+        // the measurement of deferred_sweep (-1: none) follows that sweep's cluster move (ising_wolff_kernel)
+        if (g > thermalization && g % measure_rate == 0 && g != deferred_sweep) {
+            const double e = (double)E, m = (double)(M < 0 ? -M : M);
+            sE += e;
+            sE2 += e * e;
+            sM += m;
+            sM2 += m * m;
+            if (n_series < s.cap) {
+                s.serE[at((int)n_series, W, w)] = E;
+                s.serM[at((int)n_series, W, w)] = M < 0 ? -M : M;
+                ++n_series;
+            }
+            ++n_meas;
+            ising_bin_push(bxs, bx2, bxy, bc, W, w, min(top, __builtin_ctzll(~(unsigned long long)T)), top, e, m);
+            ++T;
+        }
+    }
+    for (int j = 0; j < nw; ++j) s.conf[at(j, W, w)] = sp[j * WAVE + lane];
+    s.draw[w] = draw;
+    s.E[w] = E;
+    s.M[w] = M;
+    s.sE[w] = sE;
+    s.sE2[w] = sE2;
+    s.sM[w] = sM;
+    s.sM2[w] = sM2;
+    s.n_meas[w] = n_meas;
+    s.n_series[w] = n_series;
+    s.prop[w] += (long long)n_sweeps * N;
+    s.acc[w] += acc;
+}
+
+// the push of a measurement that ising_wolff_kernel took (the deferred measurement of the sweep its move follows): E
+// and M as that kernel left them, one lane per walker
+__global__ __launch_bounds__(WAVE) void ising_bin_push_kernel(const int *__restrict__ E, const int *__restrict__ M, int W,
+                                                              int lmax, int top, double *__restrict__ bxs,
+                                                              double *__restrict__ bx2, double *__restrict__ bxy,
+                                                              double *__restrict__ bc)
+{
+    const int w = blockIdx.x * WAVE + threadIdx.x;
+    if (w >= W) return;
+    const int m = M[w];
+    ising_bin_push(bxs, bx2, bxy, bc, W, w, lmax, top, (double)E[w], (double)(m < 0 ? -m : m));
 }
 
 // rand(MC, m) (IsingModel.jl:83): site i (column-major) takes the walker's next uniform, u < 0.5 -> -1.
@@ -315,6 +477,12 @@ struct dqmc_mc_handle {
     DevState d{};
     std::vector<void *> allocs;
     std::string err;
+    struct Binner {  // ising_bin_push: count[level] = T >> level for every walker, so no count lives on the device
+        bool on = false;
+        int L = 0;
+        int64_t cap = 0, T = 0;
+        double *xs = nullptr, *x2 = nullptr, *xy = nullptr, *c = nullptr;  // [L][4][W], [L][4][W], [L][2][W], [L - 1][4][W]
+    } bin;
 };
 
 static thread_local std::string g_mc_create_error;
@@ -383,6 +551,72 @@ static int mc_launch_wolff(dqmc_mc_handle *h, int walker, int measure)
                        h->d, (const int *)h->d.nbr, h->z, walker, measure);
     MCHK(hipGetLastError());
     return 0;
+}
+
+static const int64_t MC_BIN_DEFAULT_CAPACITY = 100000;  // BinningAnalysis' _default_capacity
+
+static void mc_bin_free(dqmc_mc_handle *h)
+{
+    dqmc_mc_handle::Binner &b = h->bin;
+    for (double **p : {&b.xs, &b.x2, &b.xy, &b.c}) {
+        if (!*p) continue;
+        for (size_t i = 0; i < h->allocs.size(); ++i)
+            if (h->allocs[i] == (void *)*p) {
+                h->allocs.erase(h->allocs.begin() + i);
+                break;
+            }
+        (void)hipFree(*p);
+    }
+    b = dqmc_mc_handle::Binner{};
+}
+
+// the push of the measurement ising_wolff_kernel has just taken
+static int mc_launch_bin_push(dqmc_mc_handle *h)
+{
+    dqmc_mc_handle::Binner &b = h->bin;
+    int lmax = 0;
+    while ((b.T >> lmax) & 1) ++lmax;
+    if (lmax >= b.L) return mc_fail(h, DQMC_ERR_STATE, "dqmc_mc_sweep: binner capacity exhausted");
+    hipLaunchKernelGGL(ising_bin_push_kernel, dim3((h->W + WAVE - 1) / WAVE), dim3(WAVE), 0, h->stream,
+                       (const int *)h->d.E, (const int *)h->d.M, h->W, lmax, b.L - 1, b.xs, b.x2, b.xy, b.c);
+    MCHK(hipGetLastError());
+    b.T += 1;
+    return 0;
+}
+
+// measurements of run! (MC.jl:262-283) among the sweeps first..last: i > thermalization && i % rate == 0
+static int64_t mc_measurements_in(int64_t first, int64_t last, int64_t thermalization, int64_t rate)
+{
+    const int64_t lo = std::max<int64_t>(first - 1, thermalization);  // (first >= 1)
+    return last > lo ? last / rate - lo / rate : 0;
+}
+
+#define MC_BIN_OK(h, fn)                                                                              \
+    if (!(h)) return mc_fail(nullptr, DQMC_ERR_INVALID, std::string(fn) + ": null handle");          \
+    if (!(h)->bin.on) return mc_fail((h), DQMC_ERR_STATE, std::string(fn) + ": the binner is not enabled")
+
+// x_sum, x2_sum (4 each) and xy_sum (2) of one level of one walker
+static int mc_bin_level(dqmc_mc_handle *h, int walker, int level, double *xs, double *x2, double *xy)
+{
+    const dqmc_mc_handle::Binner &b = h->bin;
+    const size_t W = h->W, pitch = W * sizeof(double);
+    MCHK(hipSetDevice(h->device));
+    if (xs)
+        MCHK(hipMemcpy2DAsync(xs, 8, b.xs + (size_t)level * 4 * W + walker, pitch, 8, 4, hipMemcpyDeviceToHost, h->stream));
+    if (x2)
+        MCHK(hipMemcpy2DAsync(x2, 8, b.x2 + (size_t)level * 4 * W + walker, pitch, 8, 4, hipMemcpyDeviceToHost, h->stream));
+    if (xy)
+        MCHK(hipMemcpy2DAsync(xy, 8, b.xy + (size_t)level * 2 * W + walker, pitch, 8, 2, hipMemcpyDeviceToHost, h->stream));
+    MCHK(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+static int mc_bin_reliable(const dqmc_mc_handle::Binner &b)  // the last level with count >= 32, else 0
+{
+    int lv = 0;
+    for (int l = 0; l < b.L; ++l)
+        if ((b.T >> l) >= 32) lv = l;
+    return lv;
 }
 
 extern "C" {
@@ -591,6 +825,10 @@ int dqmc_mc_sweep(dqmc_mc_handle *h, int32_t n_sweeps, int64_t first_sweep_index
     if (!h) return mc_fail(nullptr, DQMC_ERR_INVALID, "dqmc_mc_sweep: null handle");
     if (n_sweeps < 0 || measure_rate < 1 || first_sweep_index < 1)
         return mc_fail(h, DQMC_ERR_INVALID, "dqmc_mc_sweep: n_sweeps >= 0, first_sweep_index >= 1, measure_rate >= 1");
+    dqmc_mc_handle::Binner &b = h->bin;
+    if (b.on && b.T + mc_measurements_in(first_sweep_index, first_sweep_index + n_sweeps - 1, thermalization,
+                                          measure_rate) > b.cap)  // the reference: OverflowError of push!
+        return mc_fail(h, DQMC_ERR_STATE, "dqmc_mc_sweep: the measurements of this call would pass the binner's capacity");
     MCHK(hipSetDevice(h->device));
     const size_t lds = (size_t)h->nw * WAVE * 4;
     const int grid = (h->W + WAVE - 1) / WAVE;
@@ -603,19 +841,28 @@ int dqmc_mc_sweep(dqmc_mc_handle *h, int32_t n_sweeps, int64_t first_sweep_index
         if (r > 0) n = (int)std::min<long long>(n, r - (first - 1) % r);  // a launch ends at the next multiple of r
         const long long last = first + n - 1;
         const bool move = r > 0 && last % r == 0;  // global_move after sweep `last` (MC.jl:233-236)
-        switch (h->z) {
+        const bool deferred = move && last > thermalization && last % measure_rate == 0;
+        switch (h->z) {  // binner on: the forms that push every measurement they take
 #define MC_CASE(Z)                                                                                                  \
     case Z:                                                                                                         \
-        hipLaunchKernelGGL(ising_sweep_kernel<Z>, dim3(grid), dim3(WAVE), lds, h->stream, h->d,                    \
-                           (const int4 *)h->d.nbr, n, first,                                                       \
-                           (long long)thermalization, (int)measure_rate, move ? last : -1LL);                      \
+        if (b.on)                                                                                                   \
+            hipLaunchKernelGGL(ising_sweep_binned_kernel<Z>, dim3(grid), dim3(WAVE), lds, h->stream, h->d,         \
+                               (const int4 *)h->d.nbr, n, first, (long long)thermalization, (int)measure_rate,     \
+                               move ? last : -1LL, b.xs, b.x2, b.xy, b.c, b.L - 1, (long long)b.T);                \
+        else                                                                                                        \
+            hipLaunchKernelGGL(ising_sweep_kernel<Z>, dim3(grid), dim3(WAVE), lds, h->stream, h->d,                \
+                               (const int4 *)h->d.nbr, n, first,                                                   \
+                               (long long)thermalization, (int)measure_rate, move ? last : -1LL);                  \
         break;
             MC_CASE(1) MC_CASE(2) MC_CASE(3) MC_CASE(4) MC_CASE(5) MC_CASE(6) MC_CASE(7) MC_CASE(8)
 #undef MC_CASE
         }
+        if (b.on) b.T += mc_measurements_in(first, last, thermalization, measure_rate) - (deferred ? 1 : 0);
         MCHK(hipGetLastError());
         if (move)
-            if (int rc = mc_launch_wolff(h, -1, last > thermalization && last % measure_rate == 0)) return rc;
+            if (int rc = mc_launch_wolff(h, -1, deferred)) return rc;
+        if (deferred && b.on)
+            if (int rc = mc_launch_bin_push(h)) return rc;
         done += n;
     }
     MCHK(hipStreamSynchronize(h->stream));
@@ -715,7 +962,112 @@ int dqmc_mc_reset_accumulators(dqmc_mc_handle *h)
     MCHK(hipMemsetAsync(h->d.sM2, 0, W * 8, h->stream));
     MCHK(hipMemsetAsync(h->d.n_meas, 0, W * 8, h->stream));
     MCHK(hipMemsetAsync(h->d.n_series, 0, W * 8, h->stream));
+    dqmc_mc_handle::Binner &b = h->bin;
+    if (b.on) {
+        MCHK(hipMemsetAsync(b.xs, 0, (size_t)b.L * 4 * W * 8, h->stream));
+        MCHK(hipMemsetAsync(b.x2, 0, (size_t)b.L * 4 * W * 8, h->stream));
+        MCHK(hipMemsetAsync(b.xy, 0, (size_t)b.L * 2 * W * 8, h->stream));
+        if (b.L > 1) MCHK(hipMemsetAsync(b.c, 0, (size_t)(b.L - 1) * 4 * W * 8, h->stream));
+        b.T = 0;
+    }
     MCHK(hipStreamSynchronize(h->stream));
+    return DQMC_OK;
+}
+
+int dqmc_mc_binner_enable(dqmc_mc_handle *h, int64_t capacity)
+{
+    if (!h) return mc_fail(nullptr, DQMC_ERR_INVALID, "dqmc_mc_binner_enable: null handle");
+    if (capacity < 0) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_mc_binner_enable: capacity must be positive (0 selects 100000)");
+    if (capacity == 0) capacity = MC_BIN_DEFAULT_CAPACITY;
+    if (capacity > ((int64_t)1 << 40)) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_mc_binner_enable: capacity above 2^40");
+    MCHK(hipSetDevice(h->device));
+    MCHK(hipStreamSynchronize(h->stream));
+    mc_bin_free(h);
+    dqmc_mc_handle::Binner &b = h->bin;
+    int L = 1;  // ceil(log2(capacity + 1))
+    while (((int64_t)1 << L) < capacity + 1) ++L;
+    const size_t W = h->W;
+    int rc = 0;
+    if ((rc = mc_alloc(h, &b.xs, (size_t)L * 4 * W)) || (rc = mc_alloc(h, &b.x2, (size_t)L * 4 * W)) ||
+        (rc = mc_alloc(h, &b.xy, (size_t)L * 2 * W)) || (rc = mc_alloc(h, &b.c, (size_t)(L - 1) * 4 * W))) {
+        const std::string msg = h->err;
+        mc_bin_free(h);
+        h->err = msg;
+        return rc;
+    }
+    const void *kernels[] = {(const void *)ising_sweep_binned_kernel<1>, (const void *)ising_sweep_binned_kernel<2>,
+                             (const void *)ising_sweep_binned_kernel<3>, (const void *)ising_sweep_binned_kernel<4>,
+                             (const void *)ising_sweep_binned_kernel<5>, (const void *)ising_sweep_binned_kernel<6>,
+                             (const void *)ising_sweep_binned_kernel<7>, (const void *)ising_sweep_binned_kernel<8>};
+    for (const void *k : kernels)
+        if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)h->nw * WAVE * 4)) !=
+            hipSuccess) {
+            mc_bin_free(h);
+            return mc_fail(h, DQMC_ERR_HIP, "dqmc_mc_binner_enable: cannot reserve LDS for the spins");
+        }
+    MCHK(hipStreamSynchronize(h->stream));
+    b.on = true;
+    b.L = L;
+    b.cap = capacity;
+    b.T = 0;
+    return DQMC_OK;
+}
+
+int dqmc_mc_binner_size(dqmc_mc_handle *h, int32_t *n_levels, int64_t *n_pushed)
+{
+    MC_BIN_OK(h, "dqmc_mc_binner_size");
+    if (n_levels) *n_levels = h->bin.L;
+    if (n_pushed) *n_pushed = h->bin.T;
+    return DQMC_OK;
+}
+
+int dqmc_mc_binner_reliable_level(dqmc_mc_handle *h, int32_t *level)
+{
+    MC_BIN_OK(h, "dqmc_mc_binner_reliable_level");
+    if (!level) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_mc_binner_reliable_level: null level");
+    *level = mc_bin_reliable(h->bin);
+    return DQMC_OK;
+}
+
+int dqmc_mc_binner_get_level(dqmc_mc_handle *h, int32_t walker, int32_t level, double x_sum[4], double x2_sum[4],
+                             double xy_sum[2], int64_t *count)
+{
+    MC_BIN_OK(h, "dqmc_mc_binner_get_level");
+    if (int rc = mc_walker(h, walker, "dqmc_mc_binner_get_level")) return rc;
+    if (level < 0 || level >= h->bin.L) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_mc_binner_get_level: level out of range");
+    if (int rc = mc_bin_level(h, walker, level, x_sum, x2_sum, xy_sum)) return rc;
+    if (count) *count = h->bin.T >> level;
+    return DQMC_OK;
+}
+
+// varN and covN of the header: (q/(n - 1) - a b/(n (n - 1)))/n, NaN below two samples (varN: a = b, q = x2_sum)
+static double mc_bin_covN(double a, double b, double q, double n)
+{
+    if (n < 2.0) return std::nan("");
+    return (q / (n - 1.0) - a * b / (n * (n - 1.0))) / n;
+}
+
+int dqmc_mc_binner_finish(dqmc_mc_handle *h, int32_t walker, int32_t level, dqmc_mc_binned *out)
+{
+    MC_BIN_OK(h, "dqmc_mc_binner_finish");
+    if (int rc = mc_walker(h, walker, "dqmc_mc_binner_finish")) return rc;
+    if (!out) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_mc_binner_finish: null out");
+    const dqmc_mc_handle::Binner &b = h->bin;
+    if (level >= b.L) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_mc_binner_finish: level out of range");
+    if (level < 0) level = mc_bin_reliable(b);
+    double xs0[4], x20[4], xs[4], x2[4], xy[2];
+    if (int rc = mc_bin_level(h, walker, 0, xs0, x20, nullptr)) return rc;
+    if (int rc = mc_bin_level(h, walker, level, xs, x2, xy)) return rc;
+    const double n0 = (double)b.T, nl = (double)(b.T >> level);
+    for (int k = 0; k < 4; ++k) {
+        out->mean[k] = xs0[k] / n0;
+        out->varN[k] = mc_bin_covN(xs[k], xs[k], x2[k], nl);
+        out->varN0[k] = mc_bin_covN(xs0[k], xs0[k], x20[k], n0);
+        out->tau[k] = 0.5 * (out->varN[k] / out->varN0[k] - 1.0);
+    }
+    for (int q = 0; q < 2; ++q) out->covN[q] = mc_bin_covN(xs[2 * q], xs[2 * q + 1], xy[q], nl);
+    out->count = b.T >> level;
+    out->level = level;
     return DQMC_OK;
 }
 

@@ -11,7 +11,7 @@ import time
 
 import numpy as np
 
-from ._lib import DQMCError, ERR_INVALID, McGlobalStats, McParams, McStats, lib
+from ._lib import DQMCError, ERR_INVALID, McBinned, McGlobalStats, McParams, McStats, lib
 from .configurations import CompressedConf
 from .lattices import Chain, CubicLattice, SquareLattice
 
@@ -63,11 +63,15 @@ class MC:
     `global_rate`, as run! does with global_moves (MC.jl:233-236), on a stream of its own (dqmc_mc_global_move).
     `global_moves=True` is refused: the reference's global_move cannot run as written (IsingModel.jl:137 assigns to an
     undefined `model`) and its rand(1:N) draws have no place in the walker streams; `cluster_moves` is its defined
-    counterpart."""
+    counterpart.
+
+    `binning=True` gives every walker a logarithmic binner over E, E2, |M| and M2, pushed on the device where the
+    measurement is taken (enable_binning); `binned()` then answers mean, std_error and tau, and the errors of C and
+    chi."""
 
     def __init__(self, model, beta=None, T=None, n_walkers=1, seed=123, first_walker=0, thermalization=0, sweeps=1000,
                  measure_rate=1, print_rate=1000, global_moves=False, global_rate=5, device_id=0, series_capacity=0,
-                 cluster_moves=False):
+                 cluster_moves=False, binning=False, binning_capacity=None):
         if global_moves:
             raise NotImplementedError(
                 "MC(global_moves=True): the reference's Wolff global_move cannot run (IsingModel.jl:137 uses the "
@@ -113,6 +117,8 @@ class MC:
         self._c(lib().dqmc_mc_rand_conf(self._h, -1))  # mc.conf = rand(MC, m); init! (MC.jl:61,74)
         if self.cluster_moves:
             self._c(lib().dqmc_mc_set_global_rate(self._h, int(global_rate)))
+        if binning:
+            self.enable_binning(binning_capacity)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
@@ -255,6 +261,92 @@ class MC:
         return {"Magn": {"M": M, "M2": M2, "m": M * invN, "chi": beta * invN * (M2 - M * M)},
                 "Energy": {"E": E, "E2": E2, "e": E * invN, "C": beta * beta * invN * (E2 - E * E)},
                 "n_meas": int(n)}
+
+    # ---- error bars
+    def enable_binning(self, capacity=None):
+        """a LogBinner per walker over [E, E2, |M|, M2] (capacity None: 100000 measurements); enabling again starts
+        anew.  A sweep() whose measurements would pass the capacity raises before anything runs."""
+        self._c(lib().dqmc_mc_binner_enable(self._h, 0 if capacity is None else int(capacity)))
+
+    def binner_size(self):
+        """(levels, pushes so far)"""
+        L, T = C.c_int32(), C.c_int64()
+        self._c(lib().dqmc_mc_binner_size(self._h, C.byref(L), C.byref(T)))
+        return L.value, T.value
+
+    def binner_reliable_level(self):
+        lv = C.c_int32()
+        self._c(lib().dqmc_mc_binner_reliable_level(self._h, C.byref(lv)))
+        return lv.value
+
+    def binner_level(self, walker, level):
+        """(x_sum[4], x2_sum[4], xy_sum[2], count) of one level of one walker: elements [E, E2, |M|, M2], pairs
+        (E, E2) and (|M|, M2)"""
+        xs, x2, xy, n = np.zeros(4), np.zeros(4), np.zeros(2), C.c_int64()
+        dp = C.POINTER(C.c_double)
+        self._c(lib().dqmc_mc_binner_get_level(self._h, walker, level, xs.ctypes.data_as(dp), x2.ctypes.data_as(dp),
+                                               xy.ctypes.data_as(dp), C.byref(n)))
+        return xs, x2, xy, n.value
+
+    def binner_finish(self, walker=0, level=None):
+        """dqmc_mc_binned of one walker at `level` (None: the reliable level)"""
+        out = McBinned()
+        self._c(lib().dqmc_mc_binner_finish(self._h, walker, -1 if level is None else int(level), C.byref(out)))
+        return out
+
+    def _binned_walker(self, walker, level):
+        """per observable (mean, variance of the mean at `level`, the same at level 0 or None) of one walker"""
+        b = self.binner_finish(walker, level)
+        beta, invN = float(self.betas[walker]), 1.0 / self.N
+        E, E2, M, M2 = b.mean
+        vE, vE2, vM, vM2 = b.varN
+
+        def fluct(scale, x, x2, vx, vx2, cov):  # scale (<x2> - <x>^2) and the delta method on the binned covariance
+            var = scale * scale * (vx2 - 4.0 * x * cov + 4.0 * x * x * vx)
+            return scale * (x2 - x * x), (max(var, 0.0) if var == var else var), None
+
+        obs = {"E": (E, vE, b.varN0[0]), "E2": (E2, vE2, b.varN0[1]),
+               "e": (E * invN, vE * invN * invN, b.varN0[0] * invN * invN),
+               "C": fluct(beta * beta * invN, E, E2, vE, vE2, b.covN[0]),
+               "M": (M, vM, b.varN0[2]), "M2": (M2, vM2, b.varN0[3]),
+               "m": (M * invN, vM * invN * invN, b.varN0[2] * invN * invN),
+               "chi": fluct(beta * invN, M, M2, vM, vM2, b.covN[1])}
+        return obs, int(b.count), int(b.level)
+
+    def binned(self, walker=0, level=None, walkers=None):
+        """mean(obs), std_error(obs) and tau(obs) of the Observables of IsingEnergyMeasurement /
+        IsingMagnetizationMeasurement (measurements.jl:13-94) from the device binner at `level` (None: the reliable
+        one): {"Energy": {E, E2, e, C}, "Magn": {M, M2, m, chi}, "count", "level"}, each observable {mean, std_error,
+        tau}.  C and chi get their error by the delta method on the binned covariance of (E, E2) and (|M|, M2) and
+        have no tau.  `walkers=[...]` pools chains of equal beta: mean = sum_w mean_w / W, std_error =
+        sqrt(sum_w var_w) / W (C and chi formed per walker first), tau from the summed variances, plus
+        std_error_walkers = sqrt(sum_w (mean_w - mean)^2 / (W (W - 1))), which needs no binning."""
+        pooled = walkers is not None
+        ws = [int(w) for w in walkers] if pooled else [walker]
+        if not ws:
+            raise ValueError("binned: no walker given")
+        if any(self.betas[w] != self.betas[ws[0]] for w in ws):
+            raise ValueError("binned: the pooled walkers must share one beta")
+        per = [self._binned_walker(w, level) for w in ws]
+        count, lv = per[0][1], per[0][2]
+        W = float(len(ws))
+        out = {"Energy": {}, "Magn": {}, "count": count, "level": lv}
+        for group, names in (("Energy", ("E", "E2", "e", "C")), ("Magn", ("M", "M2", "m", "chi"))):
+            for k in names:
+                means = np.array([p[0][k][0] for p in per])
+                vl = float(np.sum([p[0][k][1] for p in per]))
+                mean = float(means.sum() / W)
+                o = {"mean": mean, "std_error": (math.sqrt(max(vl, 0.0)) if vl == vl else vl) / W}
+                if per[0][0][k][2] is not None:
+                    with np.errstate(invalid="ignore", divide="ignore"):
+                        o["tau"] = float(0.5 * (np.float64(vl) / np.sum([p[0][k][2] for p in per]) - 1.0))
+                if pooled:
+                    o["std_error_walkers"] = (math.sqrt(float(((means - mean) ** 2).sum()) / (W * (W - 1.0)))
+                                              if W >= 2 else float("nan"))
+                out[group][k] = o
+        if pooled:
+            out["n_walkers"] = len(ws)
+        return out
 
     def series(self, walker=0):
         """per-measurement (E, |M|) of the walker as recorded (at most series_capacity entries)"""

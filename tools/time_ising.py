@@ -6,7 +6,12 @@ time is the wall time of MC.sweep (one synchronising C call that runs the sweeps
 The CPU comparison is orc_ising_run (the oracle's sequential restatement, one host core) on one chain of the same
 shape in the same process; `cpu_16_cores_extrapolated` is that rate times 16, not a measurement.
 
-    python tools/time_ising.py [--sweeps N] [--out FILE]"""
+`--binning` times the per-walker binner instead (include/dqmc_hip.h, "error bars of the MC flavor"): L = 8, 16, 64 with
+256 chains at T_c, every sweep measured, with and without a cluster move per sweep; handles with the binner off and on
+take turns in one process (two turns each, the spread is in the line), and the binner's pooled tau of |M| gives the
+effective samples per second.
+
+    python tools/time_ising.py [--sweeps N] [--binning] [--out FILE]"""
 import argparse
 import hashlib
 import json
@@ -20,15 +25,61 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
+def time_binning(mc_amd, args, src_hash):
+    """binner off against on, alternated: sweeps/s per walker of both and what a measured sweep costs more"""
+    lines = []
+    for L in (8, 16, 64):
+        for cluster in (False, True):
+            N, W = L * L, 256
+            warm = max(2, int(2e5 / N))
+            sweeps = args.sweeps or max(10, int(1.5e6 / N))
+            kw = dict(T=mc_amd.IsingTc, n_walkers=W, seed=1, thermalization=warm, cluster_moves=cluster, global_rate=1)
+            mcs = {"off": mc_amd.MC(mc_amd.IsingModel(dims=2, L=L), **kw),
+                   "on": mc_amd.MC(mc_amd.IsingModel(dims=2, L=L), binning=True, binning_capacity=2 * sweeps, **kw)}
+            for mc in mcs.values():
+                mc.sweep(warm)
+            dt = {"off": [], "on": []}
+            for _ in range(2):
+                for k, mc in mcs.items():
+                    t0 = time.perf_counter()
+                    mc.sweep(sweeps)
+                    dt[k].append(time.perf_counter() - t0)
+            b = mcs["on"].binned(walkers=range(W))
+            assert mcs["on"].stats(0).sum_E == mcs["off"].stats(0).sum_E and b["count"] == (2 * sweeps) >> b["level"]
+            for mc in mcs.values():
+                mc.close()
+            off, on = min(dt["off"]), min(dt["on"])
+            tau = b["Magn"]["M"]["tau"]
+            line = {"shape": "square L=%d" % L, "n_sites": N, "n_walkers": W, "cluster_moves": cluster,
+                    "sweeps_timed": sweeps, "seconds_off": [round(t, 4) for t in dt["off"]],
+                    "seconds_on": [round(t, 4) for t in dt["on"]], "sweeps_per_s_per_walker_off": sweeps / off,
+                    "sweeps_per_s_per_walker_on": sweeps / on, "binner_cost_per_measured_sweep_us": (on - off) / sweeps * 1e6,
+                    "binner_cost_percent": 100.0 * (on / off - 1.0), "level": b["level"], "tau_absM": tau,
+                    "tau_E": b["Energy"]["E"]["tau"], "absM": b["Magn"]["M"],
+                    "effective_absM_samples_per_s_per_walker": sweeps / on / (2.0 * max(tau, 0.0) + 1.0),
+                    "source_hash": src_hash}
+            print(json.dumps(line), flush=True)
+            lines.append(line)
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sweeps", type=int, default=0, help="timed sweeps per shape (0: sized per shape)")
+    ap.add_argument("--binning", action="store_true", help="time the binner on against off instead of the shapes")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import __graft_entry__ as g
     mc_amd = g.load_package()
-    O = g.load_oracle()
     src_hash = mc_amd.lib().dqmc_build_source_hash().decode()
+    if args.binning:
+        lines = time_binning(mc_amd, args, src_hash)
+        if args.out:
+            with open(args.out, "w") as f:
+                for line in lines:
+                    f.write(json.dumps(line) + "\n")
+        return
+    O = g.load_oracle()
     shapes = [(8, 256), (16, 256), (32, 256), (64, 256), (8, 16384)]
     lines = []
     for L, W in shapes:
