@@ -421,6 +421,15 @@ __device__ __noinline__ void lu4_wave(int n, const double *__restrict__ Gall, lo
         // block 0 on wave 2 that wave entered block 2 about 4000 cycles behind)
         const bool PIV = (I0 == J), HLP = (J > I0), PTQ = (J == (I0 == 0 ? 3 : (I0 == 3 ? 1 : 0)));
         if (!PIV && !HLP && !PTQ) continue;
+        if (PRO && NB == 1 && J >= 2 && I0 == 1 && sizeof(Lu4Smem<NB>) + LU_STRIDE * sizeof(double) <= 150 * 1024) {
+            // EARLY prologue: the R0 block lies on ring slots 31..63 until waves 1..3 are done with it.  The pivot of
+            // block 1 writes slots 16..30 only (site 15 of a block has no payload), so the later pivots look for the
+            // three flags here, a block ahead of their first slot and off the hand-over
+            int *pflag = reinterpret_cast<int *>(lu4_lds + (sizeof(Lu4Smem<NB>) + 15) / 16 * 2 + LU_STRIDE + 1536 + 1024);
+            (void)lu4_wait(&pflag[5], &sm.abort);
+            (void)lu4_wait(&pflag[6], &sm.abort);
+            (void)lu4_wait(&pflag[7], &sm.abort);
+        }
         d4 PT[NB], Q[NB];
         if (PTQ) {
 #pragma unroll
@@ -443,13 +452,6 @@ __device__ __noinline__ void lu4_wave(int n, const double *__restrict__ Gall, lo
         for (int b = 0; b < NB; ++b) { pf_pay[b] = make_double2(0.0, 0.0); pf_xh[b] = 0.0; }
         double dcur[NB];
         if (PIV) {
-            if (PRO && NB == 1 && I0 >= 1 && sizeof(Lu4Smem<NB>) + LU_STRIDE * sizeof(double) <= 150 * 1024) {
-                // EARLY prologue: the R0 block lies on ring slots 31..63 until waves 1..3 are done with it
-                int *pflag = reinterpret_cast<int *>(lu4_lds + (sizeof(Lu4Smem<NB>) + 15) / 16 * 2 + LU_STRIDE + 1536 + 1024);
-                (void)lu4_wait(&pflag[5], &sm.abort);
-                (void)lu4_wait(&pflag[6], &sm.abort);
-                (void)lu4_wait(&pflag[7], &sm.abort);
-            }
 #pragma unroll
             for (int b = 0; b < NB; ++b) dcur[b] = readlane_d(S[b][J][0], 0);
         }
@@ -459,6 +461,7 @@ __device__ __noinline__ void lu4_wave(int n, const double *__restrict__ Gall, lo
 #pragma unroll
             for (int b = 0; b < NB; ++b) xv4[b] = 0.0;
             unsigned panel_acc = 0;
+            bool stored = false;  // strip rows of this panel already published (before site 15's flag)
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) {
                 const int c = 4 * r0 + ks, s = 16 * I0 + c;
@@ -519,7 +522,7 @@ __device__ __noinline__ void lu4_wave(int n, const double *__restrict__ Gall, lo
                                 dcur[b] = __builtin_fma(x, qs, readlane_d(S[b][J][c1 >> 2], l1));
                             }
                             S[b][J] = MFMA(aS, mS, S[b][J]);
-                            sm.aST[b][s][lane] = make_double2(aS, aT);
+                            if (c < 15) sm.aST[b][s][lane] = make_double2(aS, aT);  // (c == 15: both are zero, nobody reads)
                             sm.xs[b][s] = x;
                             ST[b][J] = MFMA(aT, mT, ST[b][J]);
                         }
@@ -528,6 +531,19 @@ __device__ __noinline__ void lu4_wave(int n, const double *__restrict__ Gall, lo
                     }
                     lastflag = word;
                 } else {
+                    // Site 15 of a block changes no row of the block (rows k > s only): its operands are zero, its strip
+                    // and PT / Q MFMAs would add nothing and nobody reads its payload; a helper only needs its x
+                    if (!HLP && c == 15) continue;
+                    if (HLP && J < 3 && c == 15) {  // the strip rows are final after site 14: out before the last flag
+#pragma unroll
+                        for (int b = 0; b < NB; ++b) {
+                            sm.strip[lu4_strip_idx(I0, r0, J)][b][0][lane] = S[b][I0][r0];
+                            sm.strip[lu4_strip_idx(I0, r0, J)][b][1][lane] = ST[b][I0][r0];
+                        }
+                        LU4_ORDER();
+                        __hip_atomic_store(&sm.sflag[lu4_strip_idx(I0, r0, J)], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        stored = true;
+                    }
                     // flag and payload are requested together (in this order); the payload is only valid if the
                     // flag was already set
                     int v = c > 0 ? __builtin_amdgcn_readfirstlane(pf_v) : 0;
@@ -540,7 +556,7 @@ __device__ __noinline__ void lu4_wave(int n, const double *__restrict__ Gall, lo
                         LU4_ORDER();
 #pragma unroll
                         for (int b = 0; b < NB; ++b) {
-                            pay[b] = sm.aST[b][s][lane];
+                            if (c < 15) pay[b] = sm.aST[b][s][lane];
                             xh[b] = sm.xs[b][s];
                         }
                         v = __builtin_amdgcn_readfirstlane(vr);
@@ -562,7 +578,7 @@ __device__ __noinline__ void lu4_wave(int n, const double *__restrict__ Gall, lo
                         LU4_ORDER();
 #pragma unroll
                         for (int b = 0; b < NB; ++b) {
-                            pf_pay[b] = sm.aST[b][s + 1][lane];
+                            if (c + 1 < 15) pf_pay[b] = sm.aST[b][s + 1][lane];
                             pf_xh[b] = sm.xs[b][s + 1];
                         }
                     }
@@ -572,12 +588,12 @@ __device__ __noinline__ void lu4_wave(int n, const double *__restrict__ Gall, lo
 #pragma unroll
                         for (int b = 0; b < NB; ++b) {
                             const double aS = pay[b].x, aT = pay[b].y;
-                            if (HLP) {
-                                xv4[b] = g == ks ? xh[b] : xv4[b];
+                            if (HLP) xv4[b] = g == ks ? xh[b] : xv4[b];
+                            if (HLP && c < 15) {
                                 S[b][I0] = MFMA(aS, S[b][I0][r0], S[b][I0]);
                                 ST[b][I0] = MFMA(aT, ST[b][I0][r0], ST[b][I0]);
                             }
-                            if (PTQ) {
+                            if (PTQ && c < 15) {
                                 PT[b] = MFMA(aT, PT[b][r0], PT[b]);  // PT[j][:] += x G[s, j] PT[s][:]
                                 Q[b] = MFMA(aS, Q[b][r0], Q[b]);     // Q[k][:]  += x G[k, s] Q[s][:]
                             }
@@ -587,7 +603,7 @@ __device__ __noinline__ void lu4_wave(int n, const double *__restrict__ Gall, lo
             }
             // panel end: the four sites applied to the later tiles of my block column with k = 4 MFMAs
             if (HLP && panel_acc != 0) {
-                if (J < 3) {  // my finished strip rows for the waves to my right
+                if (J < 3 && !stored) {  // my finished strip rows for the waves to my right
 #pragma unroll
                     for (int b = 0; b < NB; ++b) {
                         sm.strip[lu4_strip_idx(I0, r0, J)][b][0][lane] = S[b][I0][r0];
