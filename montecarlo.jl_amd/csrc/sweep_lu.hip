@@ -207,19 +207,21 @@ __device__ __noinline__ void lu4_wave(int n, const double *__restrict__ Gall, lo
             for (int Jb = 0; Jb < 4; ++Jb)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) az[Jb][r] = Gin[t + (long)n * (site0p + 16 * Jb + 4 * r + g)];
-            // R0 block: thread -> column t' = tid / 4 of this chunk, 16 consecutive sites of the previous one
+            constexpr bool STAGE = sizeof(Lu4Smem<NB>) + LU_STRIDE * sizeof(double) <= 150 * 1024;
+            // R0 block [64 t'][66], 16 bytes per thread and request.  STAGE: a wave's request covers 2 columns x 512
+            // contiguous bytes = 8 cache lines (the map of the flush workgroups); with one column t' = tid / 4 per four
+            // lanes and 16 consecutive sites per thread - the map NB == 2 keeps - a request touches 64 lines, and the
+            // four waves' 32 requests were most of what the CU's vector cache had to look up in this round trip
+            auto r0_col = [&](int i) { return STAGE ? (i * 256 + tid) >> 5 : tid >> 2; };
+            auto r0_row = [&](int i) { return STAGE ? 2 * ((i * 256 + tid) & 31) : (tid & 3) * 16 + 2 * i; };
             d2v r0v[8];
-            {
-                const int tl = tid >> 2, s0 = (tid & 3) * 16;
-                const gcd2p q = reinterpret_cast<gcd2p>(Gin + (long)n * (site0 + tl) + site0p + s0);
 #pragma unroll
-                for (int i = 0; i < 8; ++i) r0v[i] = q[i];
-            }
+            for (int i = 0; i < 8; ++i)
+                r0v[i] = *reinterpret_cast<gcd2p>(Gin + (long)n * (site0 + r0_col(i)) + site0p + r0_row(i));
             // the images of the previous chunk (the 80 operands of the two triangles, x): NB == 1 stages them in LDS
             // behind the shared structure, all four waves copying together, so that the whole prologue needs ONE memory
             // round trip (G columns, R0 block and images in flight together) and no operand lives in a register
             // before its MFMA; NB == 2 has no LDS left for that and requests the operands into registers
-            constexpr bool STAGE = sizeof(Lu4Smem<NB>) + LU_STRIDE * sizeof(double) <= 150 * 1024;
             double *imgl = lu4_lds + (sizeof(Lu4Smem<NB>) + 15) / 16 * 2;
             double opU[STAGE ? 1 : 6][4], opL[STAGE ? 1 : 6][4], opP[STAGE ? 1 : 4][4], opQ[STAGE ? 1 : 4][4], xr[4][4];
             if (STAGE) {
@@ -229,9 +231,13 @@ __device__ __noinline__ void lu4_wave(int n, const double *__restrict__ Gall, lo
                 d2v iv[NI];
 #pragma unroll
                 for (int i = 0; i < NI; ++i) iv[i] = src[min(tid + 256 * i, LU_STRIDE / 2 - 1)];
+                // (no bound check around the store: past the end a thread re-writes the last element with the value it
+                // loaded from there.  Behind a condition the compiler sinks the load into the branch and drains every
+                // request in front of it - a second round trip in the middle of the staging.  Without the scheduling
+                // barrier it moves half of the requests behind the first LDS stores instead.)
+                __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                for (int i = 0; i < NI; ++i)
-                    if (tid + 256 * i < LU_STRIDE / 2) dst[tid + 256 * i] = iv[i];
+                for (int i = 0; i < NI; ++i) dst[min(tid + 256 * i, LU_STRIDE / 2 - 1)] = iv[i];
             } else {
 #pragma unroll
                 for (int pr = 0; pr < (STAGE ? 0 : 6); ++pr)
@@ -248,12 +254,9 @@ __device__ __noinline__ void lu4_wave(int n, const double *__restrict__ Gall, lo
                         opQ[Jb][q] = imgp[LU_OFF_Q + Jb * LU_TILE + q * 64 + lane];
                     }
             }
-            {   // (all loads of the prologue are in flight by now: one round trip)
-                const int tl = tid >> 2, s0 = (tid & 3) * 16;
-                d2v *d = reinterpret_cast<d2v *>(Rl + tl * 66 + s0);
+            // (all loads of the prologue are in flight by now: one round trip)
 #pragma unroll
-                for (int i = 0; i < 8; ++i) d[i] = r0v[i];
-            }
+            for (int i = 0; i < 8; ++i) *reinterpret_cast<d2v *>(Rl + r0_col(i) * 66 + r0_row(i)) = r0v[i];
             if (STAGE) __syncthreads();  // images (and the R0 block) are in LDS
 #pragma unroll
             for (int Jb = 0; Jb < 4; ++Jb)
