@@ -157,6 +157,54 @@ int dqmc_wrap_greens(dqmc_handle *h, int32_t slice, int32_t direction);
 /* ---- analysis ----------------------------------------------------------- */
 int dqmc_get_stats(dqmc_handle *h, int32_t walker, dqmc_stats *out);
 
+/* ---- global moves ----------------------------------------------------------------------------------------------
+ * The reference reserves them and leaves them unsupported: DQMCParameters has global_moves and global_rate
+ * (DQMC.jl:53-54, 72-73), DQMCAnalysis has prop_global and acc_global (DQMC.jl:40-42), and update(mc, i) carries the
+ * hook, commented out (DQMC.jl:526-532).  Here a move changes the whole HS field or one site's time line and is
+ * accepted with the ratio of the fermion determinants, from log|det(I + B_M ... B_1)| and its sign per block.
+ *
+ * calculate_greens_AVX! (stack.jl:337-393) forms G^-1 = (Ul U1) A2 (T1 Ur'), A2 being the matrix of its second
+ * udt_AVX_pivot! (:368-376).  With D = |diag R|, T = D^-1 R P' (UDT.jl:270-277) every U is orthogonal and every T has
+ * a triangular diagonal of +-1, so log|det G^-1| = sum_i log D2_i (D2 the D of that second UDT), and sign det G^-1 =
+ * sign det A2: the chains Ul Dl Tl and Ur Dr Tr are products of B_l = eT2 eV(l) (slice_matrices.jl:23-39), each of
+ * positive determinant.  The sign of det A2 comes from an LU with partial pivoting of a copy of A2 (csrc/logdet.hip). */
+/* logabsdet[w * n_blocks + b] and sign[...] (+1 / -1; 0: A2 singular or not finite) of I + B_M ... B_1 for the current
+ * field of every walker, from scratch: the slice chain of calculate_greens(mc, 0) (stack.jl:422-480).  Overwrites
+ * Ul..Tr, curr_U, tmp1/2 like dqmc_calculate_greens_at; does not touch mc.s.greens, the stack slots or current_slice.
+ * A unit's values do not depend on the other units of the handle. */
+int dqmc_logdet(dqmc_handle *h, double *logabsdet, int32_t *sign);
+enum { DQMC_GLOBAL_FLIP_ALL = 0,    /* conf -> -conf */
+       DQMC_GLOBAL_FLIP_SITE = 1 }; /* conf[i, :] -> -conf[i, :], i = min(N - 1, floor(u(m, 0) N)) (0-based) */
+/* One global move of `walker`, or of every walker when walker < 0 (the place of global_move(mc, mc.model, mc.conf),
+ * DQMC.jl:530).  Weight ratio p, from propose_local's conventions: attractive (HubbardModelAttractive.jl:113-127, bosonic
+ * weight exp(-lambda sum conf), determinant squared) p = exp(lambda (sum conf - sum conf') + 2 (logabsdet' - logabsdet));
+ * repulsive (HubbardModelRepulsive.jl:128-156) p = sign_up' sign_dn' sign_up sign_dn exp(sum_b (logabsdet'_b -
+ * logabsdet_b)).  Accepted iff p > 1 || u(m, 1) < p, the uniform drawn only when p <= 1 (DQMC.jl:573); p < 0 is rejected
+ * and, with check_sign_problem, pushed to negative_probability (DQMC.jl:562-563).  u(m, t) is Philox4x32-10 with key =
+ * the walker's seed and counter words (t, low32(m), 1, high32(m)), m = the walker's moves since dqmc_seed (as
+ * dqmc_mc_global_move); the local stream (words 2 and 3 zero) and dqmc_uniforms_used are not touched.  In
+ * dqmc_set_uniforms mode the move consumes the host stream instead, in this order: the site uniform (FLIP_SITE only),
+ * then the acceptance uniform if p <= 1; these do count in dqmc_uniforms_used.
+ * Proposal, decision, the field of each walker and the counters stay on the device.  On return every walker of the
+ * handle is in the state dqmc_prepare leaves for its field (accepted: the new one, rejected: the old one): the stack
+ * rebuilt, mc.s.greens at current_slice = slices, direction = -1.  The logabsdet of the current field is kept between
+ * moves and recomputed when the field has changed in between.  Cost: two slice chains (one if the cache holds) plus
+ * dqmc_prepare's stack build.  DQMC_ERR_STATE before dqmc_prepare, DQMC_ERR_INVALID for an unknown kind. */
+int dqmc_global_move(dqmc_handle *h, int32_t kind, int32_t walker);
+/* mc.p.global_rate with mc.p.global_moves (DQMC.jl:53-54): from now on dqmc_update, dqmc_sweep and
+ * dqmc_update_until_measure run one move of `kind` per walker where the reference's hook stands (DQMC.jl:526-532): behind
+ * the propagate that reaches current_slice == slices && direction == -1, in front of that slice's sweep_spatial, in
+ * every sweep whose index is a multiple of rate.  The sweep index of an update is 1 + (updates since dqmc_prepare) /
+ * (2 slices).  rate 0 = off (the default): the sweep is then exactly the one of a handle without global moves.
+ * DQMC_ERR_INVALID for rate < 0 or an unknown kind. */
+int dqmc_set_global_rate(dqmc_handle *h, int32_t rate, int32_t kind);
+/* DQMCAnalysis prop_global / acc_global (DQMC.jl:40-42) of one walker and its move counter m */
+typedef struct {
+    int64_t prop_global, acc_global;
+    uint64_t moves_drawn;
+} dqmc_global_stats;
+int dqmc_get_global_stats(dqmc_handle *h, int32_t walker, dqmc_global_stats *out);
+
 /* ---- measurement accumulators (stand-in for push!(LogBinner, greens(mc)),
  * measurements/generic.jl:207-215,260-263).  dqmc_accumulate_greens adds, for
  * every walker of this handle, the true G, G.^2 and the occupation 1-G_ii into

@@ -42,6 +42,13 @@ class Stats(C.Structure):
                 ("negative_probability", MagStats), ("propagation_error", MagStats)]
 
 
+class GlobalStats(C.Structure):
+    _fields_ = [("prop_global", C.c_int64), ("acc_global", C.c_int64), ("moves_drawn", C.c_uint64)]
+
+
+GLOBAL_KINDS = ("all", "site")  # DQMC_GLOBAL_FLIP_ALL, DQMC_GLOBAL_FLIP_SITE
+
+
 class McParams(C.Structure):
     _fields_ = [("n_sites", C.c_int32), ("z", C.c_int32), ("n_walkers", C.c_int32), ("device_id", C.c_int32),
                 ("n_bonds", C.c_int32), ("series_capacity", C.c_int32), ("neighs", C.POINTER(C.c_int64)),
@@ -97,6 +104,10 @@ SIGNATURES = {
     "dqmc_replay_greens": (C.c_int, [_H, C.c_int32]),
     "dqmc_wrap_greens": (C.c_int, [_H, C.c_int32, C.c_int32]),
     "dqmc_get_stats": (C.c_int, [_H, C.c_int32, C.POINTER(Stats)]),
+    "dqmc_logdet": (C.c_int, [_H, _dp, C.POINTER(C.c_int32)]),
+    "dqmc_global_move": (C.c_int, [_H, C.c_int32, C.c_int32]),
+    "dqmc_set_global_rate": (C.c_int, [_H, C.c_int32, C.c_int32]),
+    "dqmc_get_global_stats": (C.c_int, [_H, C.c_int32, C.POINTER(GlobalStats)]),
     "dqmc_accumulate_greens": (C.c_int, [_H]),
     "dqmc_accumulator_size": (C.c_int, [_H, C.POINTER(C.c_size_t)]),
     "dqmc_reset_accumulators": (C.c_int, [_H]),

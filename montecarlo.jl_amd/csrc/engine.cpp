@@ -142,6 +142,14 @@ struct dqmc_handle {
         int64_t cap = 0, T = 0;  // capacity and pushes so far: count[level] = T >> level for every element
         double *xs = nullptr, *x2 = nullptr, *c = nullptr, *out = nullptr;
     } bin[5];
+    // global moves (global_move.inl): per-walker device state, logabsdet / sign per unit of the current field [0] (valid
+    // while gm_cache_version == conf_version) and of a proposal [1]; rate / kind of the hook in the update (0 = off)
+    GlobalMoveState *gm = nullptr;
+    double *gm_lad[2] = {nullptr, nullptr};
+    int *gm_sg[2] = {nullptr, nullptr};
+    long long gm_cache_version = -1;
+    int gm_rate = 0, gm_kind = DQMC_GLOBAL_FLIP_SITE;
+    long long gm_updates = 0;  // updates since dqmc_prepare: update u belongs to sweep 1 + u / (2 slices)
 };
 
 // ---------------------------------------------------------------------------
@@ -596,7 +604,9 @@ static int rdivp(dqmc_handle *h, double *A, const double *T)
 // L = (Ul, Dl, Tl), R = (Ur, Dr, Tr) are only read (they may be stack slots); h->Ul .. h->Tr are the work matrices
 // the reference overwrites its six inputs with.  L / R may also BE those work matrices (each is consumed before the
 // step that overwrites it).
-static int calculate_greens_src(dqmc_handle *h, double *out, Udt L, Udt R)
+// a2_copy (optional): receives the matrix handed to the second UDT (:368-376), whose determinant is that of G^-1 up to
+// a sign (logdet.hip); the D of that UDT is what the function leaves in h->Dr.
+static int calculate_greens_src(dqmc_handle *h, double *out, Udt L, Udt R, double *a2_copy = nullptr)
 {
     const int n = h->n;
     QrSet &qa = h->qs[0], &qb = h->qs[0];
@@ -619,6 +629,7 @@ static int calculate_greens_src(dqmc_handle *h, double *out, Udt L, Udt R)
     g = gemm_base(h, U_(h, h->Tl), 1, U_(h, h->Ur), 0, h->Tr);         // :362 + :368
     g.adddiag = vs_arr(h->Dr, n);
     CHK(run_gemm(h, g));
+    if (a2_copy) CHK(copy_mat(h, a2_copy, h->Tr));
     const double *tlul = h->Tr;  // where Tl Ul of :378 ends up
     if (udt_is_fused(h, 2)) {
         // :376 and :378 in one launch: "U" = Tl Q goes to Ul (free: the reference's Ul = Q is only used in :378)
@@ -636,9 +647,9 @@ static int calculate_greens_src(dqmc_handle *h, double *out, Udt L, Udt R)
     CHK(run_gemm(h, g));
     return 0;
 }
-static int calculate_greens(dqmc_handle *h, double *out)
+static int calculate_greens(dqmc_handle *h, double *out, double *a2_copy = nullptr)
 {
-    return calculate_greens_src(h, out, Udt{h->Ul, h->Dl, h->Tl}, Udt{h->Ur, h->Dr, h->Tr});
+    return calculate_greens_src(h, out, Udt{h->Ul, h->Dl, h->Tl}, Udt{h->Ur, h->Dr, h->Tr}, a2_copy);
 }
 
 // ---- checkerboard products with sparse factors (slice_matrices.jl:104-222, DQMC.jl:731-750) --------------------
@@ -1322,6 +1333,11 @@ int dqmc_create(const dqmc_params *p, dqmc_handle **out)
     CCHK(dalloc(h, &h->rng, (size_t)h->W));
     CCHK(dalloc(h, &h->stats, (size_t)h->W));
     CCHK(dalloc(h, &h->pc_scratch, 2 * (size_t)h->W));
+    CCHK(dalloc(h, &h->gm, (size_t)h->W));
+    for (int i = 0; i < 2; ++i) {
+        CCHK(dalloc(h, &h->gm_lad[i], (size_t)h->units));
+        CCHK(dalloc(h, &h->gm_sg[i], (size_t)h->units));
+    }
     {
         std::vector<DevStats> st(h->W);
         for (auto &x : st) {
@@ -1406,6 +1422,8 @@ int dqmc_seed(dqmc_handle *h, int32_t w, uint64_t seed)
     HIPCHK(hipStreamSynchronize(h->stream));
     WalkerRng r = {(unsigned long long)seed, 0ull, nullptr, 0ull, 0};
     HIPCHK(hipMemcpy(h->rng + w, &r, sizeof(r), hipMemcpyHostToDevice));
+    const unsigned long long m0 = 0;  // the move counter of the global-move stream starts anew with the seed
+    HIPCHK(hipMemcpy(&h->gm[w].moves_drawn, &m0, sizeof(m0), hipMemcpyHostToDevice));
     return DQMC_OK;
 }
 int dqmc_uniforms_used(dqmc_handle *h, int32_t w, uint64_t *used)
@@ -1455,8 +1473,10 @@ int dqmc_prepare(dqmc_handle *h)
     CHK(build_stack(h));
     CHK(propagate(h));
     h->prepared = true;
+    h->gm_updates = 0;
     return dqmc_synchronize(h);
 }
+static int update_hooked(dqmc_handle *h);  // global_move.inl: propagate, the global-move hook (off by default), sweep_spatial
 #define NEED_PREPARED(h) \
     if (!(h)->prepared) return fail((h), DQMC_ERR_STATE, "call dqmc_prepare or dqmc_build_stack first")
 int dqmc_propagate(dqmc_handle *h)
@@ -1475,8 +1495,7 @@ int dqmc_sweep_spatial(dqmc_handle *h)
 int dqmc_update(dqmc_handle *h)
 {
     ENTER(h); NEED_PREPARED(h);
-    CHK(propagate(h));
-    CHK(sweep_spatial(h));
+    CHK(update_hooked(h));
     CHK(materialize_pending_flush(h));  // (the API boundary: greens as the reference has it)
     return dqmc_synchronize(h);
 }
@@ -1484,10 +1503,7 @@ int dqmc_sweep(dqmc_handle *h, int32_t n_sweeps)
 {
     ENTER(h); NEED_PREPARED(h);
     for (int i = 0; i < n_sweeps; ++i)
-        for (int u = 0; u < 2 * h->M; ++u) {
-            CHK(propagate(h));
-            CHK(sweep_spatial(h));
-        }
+        for (int u = 0; u < 2 * h->M; ++u) CHK(update_hooked(h));
     CHK(materialize_pending_flush(h));  // (the API boundary: greens as the reference has it)
     return dqmc_synchronize(h);
 }
@@ -1496,8 +1512,7 @@ int dqmc_update_until_measure(dqmc_handle *h, int32_t *n_updates)
     ENTER(h); NEED_PREPARED(h);
     int cnt = 0;
     do {
-        CHK(propagate(h));
-        CHK(sweep_spatial(h));
+        CHK(update_hooked(h));
         ++cnt;
     } while (!(h->current_slice == 1 && h->direction == 1));
     if (n_updates) *n_updates = cnt;
@@ -1541,7 +1556,7 @@ int dqmc_get_greens(dqmc_handle *h, int32_t w, double *out)
 }
 
 // calculate_greens(mc, slice, output) (stack.jl:422-480) for every walker of the handle
-static int calculate_greens_from_scratch(dqmc_handle *h, int slice, double *output)
+static int calculate_greens_from_scratch(dqmc_handle *h, int slice, double *output, double *a2_copy = nullptr)
 {
     const int n = h->n, M = h->M, s = h->s;
     // right factor: Ur,Dr,Tr = B(slice+1)' ... B(M)'
@@ -1593,7 +1608,7 @@ static int calculate_greens_from_scratch(dqmc_handle *h, int slice, double *outp
         CHK(copy_mat(h, h->tmp1, h->Tl));
         CHK(run_gemm(h, gemm_base(h, U_(h, h->tmp2), 0, U_(h, h->tmp1), 0, h->Tl)));
     }
-    CHK(calculate_greens(h, output));
+    CHK(calculate_greens(h, output, a2_copy));
     return 0;
 }
 int dqmc_calculate_greens_at(dqmc_handle *h, int32_t w, int32_t slice, double *out)
@@ -1856,6 +1871,7 @@ int dqmc_export_accumulators(dqmc_handle *h, void *device_out)
 
 #include "unequal_time.inl"
 #include "binner.inl"
+#include "global_move.inl"
 
 // ---------------------------------------------------------------------------
 // Measurement reduction over ranks: every accumulator the handle keeps and the DQMCAnalysis

@@ -1,0 +1,105 @@
+// global_move.inl — global moves of the DQMC flavor (include/dqmc_hip.h "global moves"; part of engine.cpp).
+//
+// The reference reserves the hook (DQMC.jl:526-532) and the parameters (DQMC.jl:53-54, 72-73) but has no move.  Here a
+// move flips the whole HS field or one site's time line and is accepted with the ratio of the fermion determinants,
+// which needs log|det(I + B_M ... B_1)| and its sign per unit: logdet_from_scratch.  Everything a move decides stays on
+// the device (csrc/logdet.hip); the host only queues launches.
+
+// logabsdet / sign of every unit for the current field into lad / sg (device, `units` entries): the from-scratch chain
+// of calculate_greens(mc, 0) with the matrix handed to its second UDT copied aside (bufA), then logdet_kernel on that
+// copy and on the D the UDT left in Dr.  Overwrites Ul .. Tr, tmp1 / tmp2, bufA / bufB and greens_temp.
+static int logdet_from_scratch(dqmc_handle *h, double *lad, int *sg)
+{
+    CHK(calculate_greens_from_scratch(h, 0, h->greens_temp, h->bufA));
+    Timed t(h, DQMC_K_MISC);
+    HIPCHK(launch_logdet(h->n, h->units, h->bufA, h->nn, h->Dr, h->n, lad, sg, h->cur));
+    return 0;
+}
+// the cache of the current field's values (invalid once conf_version has moved on)
+static int logdet_current(dqmc_handle *h)
+{
+    if (h->gm_cache_version == h->conf_version) return 0;
+    CHK(logdet_from_scratch(h, h->gm_lad[0], h->gm_sg[0]));
+    h->gm_cache_version = h->conf_version;
+    return 0;
+}
+// one move of `walker` (< 0: every walker); leaves the handle as dqmc_prepare would for the resulting fields
+static int global_move(dqmc_handle *h, int kind, int walker)
+{
+    CHK(logdet_current(h));
+    {
+        Timed t(h, DQMC_K_MISC);
+        HIPCHK(launch_gm_propose(h->N, h->M, h->W, kind, walker, h->conf, h->rng, h->gm, h->cur));
+    }
+    h->conf_version++;
+    CHK(logdet_from_scratch(h, h->gm_lad[1], h->gm_sg[1]));
+    {
+        Timed t(h, DQMC_K_MISC);
+        HIPCHK(launch_gm_decide(h->N, h->M, h->nb, h->W, kind, h->lambda, h->p.check_sign_problem, h->conf, h->rng, h->gm,
+                                h->stats, h->gm_lad[0], h->gm_sg[0], h->gm_lad[1], h->gm_sg[1], h->cur));
+    }
+    // the field is the old or the new one per walker, and the cache holds the values of whichever it is
+    h->conf_version++;
+    h->gm_cache_version = h->conf_version;
+    discard_pending_flush(h);
+    CHK(init_stack(h));
+    CHK(build_stack(h));
+    CHK(propagate(h));
+    return 0;
+}
+// update(mc, i) (DQMC.jl:523-538) with the reference's hook filled in: i = 1 + (updates since dqmc_prepare) / (2 slices)
+static int update_hooked(dqmc_handle *h)
+{
+    CHK(propagate(h));
+    if (h->gm_rate > 0) {
+        const long long i = 1 + h->gm_updates / (2LL * h->M);
+        if (h->current_slice == h->M && h->direction == -1 && i % h->gm_rate == 0) CHK(global_move(h, h->gm_kind, -1));
+    }
+    h->gm_updates++;
+    return sweep_spatial(h);
+}
+
+int dqmc_logdet(dqmc_handle *h, double *logabsdet, int32_t *sign)
+{
+    ENTER(h);
+    if (!logabsdet || !sign) return fail(h, DQMC_ERR_INVALID, "dqmc_logdet: null output");
+    h->gm_cache_version = -1;  // from scratch, as documented
+    CHK(logdet_current(h));
+    CHK(dqmc_synchronize(h));
+    HIPCHK(hipMemcpy(logabsdet, h->gm_lad[0], sizeof(double) * h->units, hipMemcpyDeviceToHost));
+    static_assert(sizeof(int) == sizeof(int32_t), "sign buffer");
+    HIPCHK(hipMemcpy(sign, h->gm_sg[0], sizeof(int) * h->units, hipMemcpyDeviceToHost));
+    return DQMC_OK;
+}
+int dqmc_global_move(dqmc_handle *h, int32_t kind, int32_t walker)
+{
+    ENTER(h);
+    if (!h->prepared) return fail(h, DQMC_ERR_STATE, "dqmc_global_move: call dqmc_prepare first");
+    if (kind != DQMC_GLOBAL_FLIP_ALL && kind != DQMC_GLOBAL_FLIP_SITE)
+        return fail(h, DQMC_ERR_INVALID, "dqmc_global_move: unknown kind (DQMC_GLOBAL_FLIP_ALL or DQMC_GLOBAL_FLIP_SITE)");
+    if (walker >= h->W) return fail(h, DQMC_ERR_INVALID, "walker index out of range");
+    CHK(global_move(h, kind, walker < 0 ? -1 : walker));
+    return dqmc_synchronize(h);
+}
+int dqmc_set_global_rate(dqmc_handle *h, int32_t rate, int32_t kind)
+{
+    ENTER(h);
+    if (rate < 0) return fail(h, DQMC_ERR_INVALID, "dqmc_set_global_rate: rate must be >= 0");
+    if (kind != DQMC_GLOBAL_FLIP_ALL && kind != DQMC_GLOBAL_FLIP_SITE)
+        return fail(h, DQMC_ERR_INVALID, "dqmc_set_global_rate: unknown kind (DQMC_GLOBAL_FLIP_ALL or DQMC_GLOBAL_FLIP_SITE)");
+    h->gm_rate = rate;
+    h->gm_kind = kind;
+    return DQMC_OK;
+}
+int dqmc_get_global_stats(dqmc_handle *h, int32_t w, dqmc_global_stats *out)
+{
+    ENTER(h); WALKER_OK(h, w);
+    if (!out) return fail(h, DQMC_ERR_INVALID, "dqmc_get_global_stats: null output");
+    HIPCHK(hipStreamSynchronize(h->stream));
+    GlobalMoveState g;
+    HIPCHK(hipMemcpy(&g, h->gm + w, sizeof(g), hipMemcpyDeviceToHost));
+    out->prop_global = g.prop_global;
+    out->acc_global = g.acc_global;
+    out->moves_drawn = g.moves_drawn;
+    return DQMC_OK;
+}

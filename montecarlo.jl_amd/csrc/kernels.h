@@ -425,6 +425,28 @@ hipError_t launch_binner_push(const BinPush &p, int W, int E, int L, int lmax, d
 // out [8 E + 1]: mean, std_error, std_error_walkers, tau, sum mean_w, sum mean_w^2, sum varN_w(level), sum varN_w(0), W
 hipError_t launch_binner_finish(int W, int E, long T, int level, const double *xs, const double *x2, double *out,
                                 hipStream_t s);
+// log|det| and sign of I + B_M ... B_1 per unit (logdet.hip): logabsdet = sum_i log D2[i] with D2 the D of the second
+// udt_AVX_pivot! of calculate_greens_AVX! (stack.jl:376), sign = sign det A2 of the matrix that UDT factors, from an LU
+// with partial pivoting of the copy in A2 (n_units x strideA, destroyed).  One workgroup per unit, fixed summation order.
+hipError_t launch_logdet(int n, int n_units, double *A2, long strideA, const double *D2, long strideD, double *logabsdet,
+                         int *sign, hipStream_t s);
+// DQMC global moves (logdet.hip): per walker, device-resident.  m = moves_drawn is the walker's move counter, the Philox
+// counter words of u(m, t) are (t, low32(m), 1, high32(m)).
+struct GlobalMoveState {
+    unsigned long long moves_drawn;
+    long long prop_global, acc_global;
+    long long dS;        // sum(conf) - sum(conf') of the pending proposal
+    double last_p;       // weight ratio of the latest move
+    int active, site, last_accepted, pad_;
+};
+// kind 0: conf -> -conf, 1: conf[site, :] -> -conf[site, :] with site = min(N - 1, floor(u(m, 0) N)).  walker < 0: all.
+hipError_t launch_gm_propose(int N, int M, int n_walkers, int kind, int walker, int8_t *conf, WalkerRng *rng,
+                             GlobalMoveState *gm, hipStream_t s);
+// accept iff p > 1 || u(m, 1) < p (the uniform drawn only when p <= 1); accepted walkers copy (lad_prop, sg_prop) into
+// (lad_cur, sg_cur), rejected ones get their field back
+hipError_t launch_gm_decide(int N, int M, int nb, int n_walkers, int kind, double lambda, int check_sign, int8_t *conf,
+                            WalkerRng *rng, GlobalMoveState *gm, DevStats *stats, double *lad_cur, int *sg_cur,
+                            const double *lad_prop, const int *sg_prop, hipStream_t s);
 // HS field <-> Julia BitArray chunks (compress / decompress, HubbardModel.jl:56-59)
 hipError_t launch_conf_pack(const int8_t *conf, size_t n_elem, unsigned long long *chunks, hipStream_t s);
 hipError_t launch_conf_unpack(const unsigned long long *chunks, size_t n_elem, int8_t *conf, hipStream_t s);

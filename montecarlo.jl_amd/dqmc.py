@@ -28,6 +28,8 @@ class DQMCParameters:
     beta: float = 1.0
     slices: int = 10
     measure_rate: int = 10
+    global_moves: bool = False
+    global_rate: int = 5
 
     @staticmethod
     def resolve(**kw):
@@ -197,7 +199,10 @@ def checkerboard_seqs(tables):
 class DQMCAnalysis:
     """DQMC.jl:36-47 for one walker"""
 
-    def __init__(self, st):
+    def __init__(self, st, gst=None):
+        self.prop_global = gst.prop_global if gst is not None else 0
+        self.acc_global = gst.acc_global if gst is not None else 0
+        self.acc_rate_global = self.acc_global / self.prop_global if self.prop_global else 0.0
         self.prop_local = st.prop_local
         self.acc_local = st.acc_local
         self.acc_rate = st.acc_local / st.prop_local if st.prop_local else 0.0
@@ -210,16 +215,22 @@ class DQMC:
     """DQMC(model; beta, delta_tau=0.1, safe_mult=10, ...) (DQMC.jl:250-289) for
     `n_walkers` chains on device `device_id`.  `seed` keys the initial HS fields and the
     Metropolis streams of walker w as `seed + first_walker + w`, so results do not depend
-    on how walkers are distributed over devices."""
+    on how walkers are distributed over devices.  `global_moves=True` runs one global move of `global_kind` ("site": one
+    site's whole time line is flipped, "all": the whole field) per walker in every `global_rate`-th sweep, where the
+    reference keeps its hook (DQMC.jl:526-532); see global_move()."""
 
     def __init__(self, model, n_walkers=1, device_id=0, seed=123, first_walker=0, thermalization=100, sweeps=100,
                  safe_mult=10, measure_rate=10, check_sign_problem=True, check_propagation_error=True,
-                 checkerboard=False, **kw):
+                 checkerboard=False, global_moves=False, global_rate=5, global_kind="site", **kw):
         self.model = model
         self.checkerboard = bool(checkerboard)
+        if int(global_rate) < 1:
+            raise ValueError("global_rate must be at least 1")
+        self.global_kind = self._global_kind(global_kind)
         self.p = DQMCParameters.resolve(thermalization=thermalization, sweeps=sweeps, safe_mult=safe_mult,
                                         measure_rate=measure_rate, check_sign_problem=check_sign_problem,
-                                        check_propagation_error=check_propagation_error, **kw)
+                                        check_propagation_error=check_propagation_error,
+                                        global_moves=bool(global_moves), global_rate=int(global_rate), **kw)
         self.n_walkers = n_walkers
         self._device_id = device_id
         self.N = len(model.l)
@@ -273,6 +284,8 @@ class DQMC:
             rng = np.random.Generator(np.random.Philox(key=s))
             self.set_conf(w, rand_conf(rng, self.N, self.p.slices))
             self.seed(w, s)
+        if self.p.global_moves:
+            self.set_global_rate(self.p.global_rate, self.global_kind)
 
     # ---- lifetime
     def close(self):
@@ -470,11 +483,43 @@ class DQMC:
     def wrap_greens(self, slice_, direction):
         self._c(lib().dqmc_wrap_greens(self._h, slice_, direction))
 
+    # ---- global moves (include/dqmc_hip.h "global moves")
+    @staticmethod
+    def _global_kind(kind):
+        if kind in _lib.GLOBAL_KINDS:
+            return _lib.GLOBAL_KINDS.index(kind)
+        return int(kind)  # the engine refuses a number it does not know
+
+    def logdet(self):
+        """-> (logabsdet, sign), arrays [n_walkers, n_blocks]: log|det(I + B_M ... B_1)| and its sign per block for the
+        current field of every walker, computed from scratch on the device"""
+        lad = np.zeros(self.n_walkers * self.nb)
+        sg = np.zeros(self.n_walkers * self.nb, dtype=np.int32)
+        self._c(lib().dqmc_logdet(self._h, dptr(lad), sg.ctypes.data_as(C.POINTER(C.c_int32))))
+        return lad.reshape(self.n_walkers, self.nb), sg.reshape(self.n_walkers, self.nb)
+
+    def global_move(self, kind="site", walker=-1):
+        """one global move ("all": conf -> -conf, "site": one site's time line) of `walker` (-1: every walker), accepted
+        with the determinant ratio; afterwards the handle is in the state prepare() leaves for the resulting fields"""
+        self._c(lib().dqmc_global_move(self._h, self._global_kind(kind), walker))
+
+    def set_global_rate(self, rate, kind="site"):
+        """one global move per walker in every sweep whose index is a multiple of `rate` (0: off)"""
+        self._c(lib().dqmc_set_global_rate(self._h, rate, self._global_kind(kind)))
+
+    def global_stats(self, walker=0):
+        """-> dict(prop_global, acc_global, moves_drawn) of one walker"""
+        g = _lib.GlobalStats()
+        self._c(lib().dqmc_get_global_stats(self._h, walker, C.byref(g)))
+        return dict(prop_global=g.prop_global, acc_global=g.acc_global, moves_drawn=g.moves_drawn)
+
     # ---- analysis / measurement sums
     def analysis(self, walker=0):
         st = _lib.Stats()
         self._c(lib().dqmc_get_stats(self._h, walker, C.byref(st)))
-        return DQMCAnalysis(st)
+        g = _lib.GlobalStats()
+        self._c(lib().dqmc_get_global_stats(self._h, walker, C.byref(g)))
+        return DQMCAnalysis(st, g)
 
     def analysis_sum(self):
         """(prop_local, acc_local) summed over the walkers of this handle"""
