@@ -296,9 +296,14 @@ int dqmc_export_susceptibilities(dqmc_handle *h, void *device_out);
  *   [cds][sds_x][sds_y][sds_z][ps n_dirs x K_pc x K_pc if local targets][ccs n_dirs x K_cc][samples]
  * ccs in Julia's column-major order of output[dir12, dir_ii].  The reference's identity terms stay out as in
  * measurements.jl:295-309.  dqmc_current_targets_fast_path reports whether the lattice took the LDS kernel
- * (n_dirs == n_sites, one direction per (src1, src2) for each src1, K <= 8) or the general one. */
+ * (n_dirs == n_sites, one direction per (src1, src2) for each src1, K <= 8) or the general one.
+ * dqmc_current_targets_plan reports the launch plan of the LDS kernel (host code only, for tests and tools):
+ *   out = [fast, C sources per chunk, umax panel rows, chunks, chunks per workgroup, workgroups per walker,
+ *          threads per workgroup, dynamic LDS bytes];
+ * all zero when no targets are set or the general kernel is taken. */
 int dqmc_set_current_targets(dqmc_handle *h, const int32_t *trg_of, int32_t K, const double *T);
 int dqmc_current_targets_fast_path(dqmc_handle *h, int32_t *fast);
+int dqmc_current_targets_plan(dqmc_handle *h, int32_t out[8]);
 
 /* ---- error bars: logarithmic binning per walker on the device ------------------------------------------------
  * The observable of a DQMCMeasurement is a BinningAnalysis LogBinner (measurements/generic.jl:35-39, default capacity

@@ -135,6 +135,7 @@ SIGNATURES = {
     "dqmc_accumulate_susceptibilities": (C.c_int, [_H, C.c_int32]),
     "dqmc_set_current_targets": (C.c_int, [_H, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_double)]),
     "dqmc_current_targets_fast_path": (C.c_int, [_H, C.POINTER(C.c_int32)]),
+    "dqmc_current_targets_plan": (C.c_int, [_H, C.POINTER(C.c_int32)]),
     "dqmc_susceptibilities_size": (C.c_int, [_H, C.POINTER(C.c_size_t)]),
     "dqmc_get_susceptibilities": (C.c_int, [_H, _dp]),
     "dqmc_export_susceptibilities": (C.c_int, [_H, C.c_void_p]),

@@ -697,6 +697,16 @@ int dqmc_current_targets_fast_path(dqmc_handle *h, int32_t *fast)
     *fast = h->K_cc && h->cc.fast ? 1 : 0;
     return DQMC_OK;
 }
+int dqmc_current_targets_plan(dqmc_handle *h, int32_t out[8])
+{
+    if (!h || !out) return DQMC_ERR_INVALID;
+    for (int i = 0; i < 8; ++i) out[i] = 0;
+    if (!h->K_cc || !h->cc.fast) return DQMC_OK;
+    const CCPlan &p = h->cc;
+    out[0] = 1; out[1] = p.C; out[2] = p.umax; out[3] = p.nchunks; out[4] = p.chunks_per_wg; out[5] = p.n_wg;
+    out[6] = p.threads; out[7] = (int32_t)p.lds_bytes;
+    return DQMC_OK;
+}
 static long ut_cc_offset(dqmc_handle *h) { return 4L * h->n_dirs + (long)h->n_dirs * h->K_loc * h->K_loc; }
 static int ut_sus_layout(dqmc_handle *h)
 {

@@ -917,6 +917,14 @@ class DQMC:
         self._c(lib().dqmc_current_targets_fast_path(self._h, C.byref(f)))
         return bool(f.value)
 
+    def current_targets_plan(self):
+        """-> dict(fast, C, umax, nchunks, chunks_per_wg, n_wg, threads, lds_bytes): the launch plan of the LDS kernel
+        (all zero when no targets are set or the general kernel is taken; see include/dqmc_hip.h)"""
+        out = (C.c_int32 * 8)()
+        self._c(lib().dqmc_current_targets_plan(self._h, out))
+        names = ("fast", "C", "umax", "nchunks", "chunks_per_wg", "n_wg", "threads", "lds_bytes")
+        return dict(zip(names, (int(v) for v in out)))
+
     # ---- instrumentation
     def qr_fallbacks(self):
         """cooperative-QR launches that timed out and were redone by the single-workgroup kernel"""
