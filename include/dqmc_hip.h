@@ -535,6 +535,44 @@ typedef struct {
     uint64_t moves_drawn;
 } dqmc_mc_global_stats;
 int dqmc_mc_get_global_stats(dqmc_mc_handle *h, int32_t walker, dqmc_mc_global_stats *out);
+/* Replica exchange (parallel tempering) between the walkers of one handle.  The reference has no such move; like the
+ * cluster move this is a defined extension.  The walkers form n_walkers / R ladders of R consecutive slots.  Slot w keeps
+ * what belongs to its temperature: beta and its tables, the Philox key and both cursors, the sums, series and binner,
+ * and every counter.  An accepted exchange swaps the configurations of two neighbouring slots of a ladder: the spins,
+ * energy, magnetization and the replica label (at first the slot's index within its ladder).  So dqmc_mc_get_stats(w)
+ * and the binner of w stay "at beta_w"; a replica wanders over the slots.  The handle keeps an exchange cursor x, the
+ * number of rounds since dqmc_mc_set_exchange.  Round x tries the pairs (i, i + 1) of every ladder with ladder-local
+ * i = x (mod 2) and i + 1 < R.  For the slots (a, b = a + 1) of a pair: d = (E_a - E_b) / 2 (an integer, E = n_bonds mod 2
+ * for every configuration) and db = beta_a - beta_b in fp64 on the host; the betas need not be monotone.  The pair
+ * swaps if db == 0, d == 0, or db and d have the same sign.  Otherwise p = 1.0, then p = p * q[j] for every set bit j of
+ * |d| in ascending order, with q[j] = exp(-2 |db| 2^j) a per-pair table of J entries (2^J > n_bonds, J <= 17) from the
+ * host's libm, rebuilt by dqmc_mc_set_beta for the two pairs a slot belongs to; the pair swaps iff u < p, where
+ * u = Philox4x32-10 with the key of slot a and counter words (low32(x), high32(x), 2, 0), formed only when it decides.
+ * This is a third domain: the local stream has words 2 and 3 zero, the cluster move has word 2 = 1.  Neither of their
+ * cursors moves.  There is no exp on the device and a product of doubles is exactly rounded, so every decision can be
+ * reproduced bit for bit.  p differs from exp(2 db d) by the rounding of at most 17 factors and 16 products, about
+ * 20 ulp: that relative error of the acceptance probability is the size of the deviation from exact detailed balance
+ * (a chain that used p for both directions of every pair would be exact; the rule is symmetric in a and b).  Per slot a,
+ * prop_exchange / acc_exchange count the tries and swaps of the pair (a, a + 1); the last slot of a ladder stays 0. */
+/* n_replicas = R >= 2 defines the ladders (n_walkers % R != 0: DQMC_ERR_INVALID); 0 or 1: none.  rate = k > 0: from now
+ * on dqmc_mc_sweep runs one round after every sweep whose global index is a multiple of k, after that sweep's cluster
+ * move if it has one and before its measurement; rate 0 (or no ladders): dqmc_mc_sweep runs none and behaves as on a
+ * handle that never had exchange (with R >= 2 dqmc_mc_exchange still works).  Resets the cursor, the labels and the
+ * exchange counters.  The results do not depend on how a run is split into calls of dqmc_mc_sweep. */
+int dqmc_mc_set_exchange(dqmc_mc_handle *h, int32_t n_replicas, int32_t rate);
+/* one round at the cursor by hand (a launch of its own); it takes no measurement.  Without ladders: DQMC_ERR_STATE */
+int dqmc_mc_exchange(dqmc_mc_handle *h);
+/* the exchange counters of the pair (walker, walker + 1), the label of the replica now in the slot, and the cursor */
+typedef struct {
+    int64_t prop_exchange, acc_exchange;
+    int64_t replica;
+    uint64_t rounds;
+} dqmc_mc_exchange_stats;
+int dqmc_mc_get_exchange_stats(dqmc_mc_handle *h, int32_t walker, dqmc_mc_exchange_stats *out);
+/* 1: dqmc_mc_sweep runs its rounds inside the sweep kernel (64 % R == 0: a ladder never straddles a wave; the spins
+ * change columns in LDS), except a round that follows a cluster move; 0: every round is a launch of its own on the state
+ * in device memory (any other R), or dqmc_mc_sweep runs no rounds */
+int dqmc_mc_exchange_fused(dqmc_mc_handle *h, int32_t *fused);
 int dqmc_mc_synchronize(dqmc_mc_handle *h);
 
 /* ---- error bars of the MC flavor: one logarithmic binner per walker, pushed inside the sweep --------------------

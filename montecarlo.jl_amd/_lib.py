@@ -66,6 +66,11 @@ class McGlobalStats(C.Structure):
                 ("moves_drawn", C.c_uint64)]
 
 
+class McExchangeStats(C.Structure):
+    _fields_ = [("prop_exchange", C.c_int64), ("acc_exchange", C.c_int64), ("replica", C.c_int64),
+                ("rounds", C.c_uint64)]
+
+
 class McBinned(C.Structure):
     _fields_ = [("mean", C.c_double * 4), ("varN", C.c_double * 4), ("varN0", C.c_double * 4), ("tau", C.c_double * 4),
                 ("covN", C.c_double * 2), ("count", C.c_int64), ("level", C.c_int32)]
@@ -186,6 +191,10 @@ SIGNATURES = {
     "dqmc_mc_set_global_rate": (C.c_int, [_H, C.c_int32]),
     "dqmc_mc_global_move": (C.c_int, [_H, C.c_int32]),
     "dqmc_mc_get_global_stats": (C.c_int, [_H, C.c_int32, C.POINTER(McGlobalStats)]),
+    "dqmc_mc_set_exchange": (C.c_int, [_H, C.c_int32, C.c_int32]),
+    "dqmc_mc_exchange": (C.c_int, [_H]),
+    "dqmc_mc_get_exchange_stats": (C.c_int, [_H, C.c_int32, C.POINTER(McExchangeStats)]),
+    "dqmc_mc_exchange_fused": (C.c_int, [_H, C.POINTER(C.c_int32)]),
     "dqmc_mc_synchronize": (C.c_int, [_H]),
     "dqmc_mc_binner_enable": (C.c_int, [_H, C.c_int64]),
     "dqmc_mc_binner_size": (C.c_int, [_H, C.POINTER(C.c_int32), _i64p]),

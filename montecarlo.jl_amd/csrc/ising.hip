@@ -30,6 +30,18 @@
 // bond counts twice in the Metropolis dE, and two independent slot tests, 1 - (1 - p)^2, are its Fortuin-Kasteleyn
 // probability.  In run! order (MC.jl:230-242) the move of sweep i follows that sweep's local sweep and precedes its
 // measurement.
+//
+// Replica exchange (parallel tempering; the reference has no such move, this is a defined extension like the cluster
+// move): the handle's walkers form n_walkers / R ladders of R consecutive slots.  A slot keeps what belongs to its
+// temperature (beta and tables, key and cursors, sums, series, binner, counters); an accepted exchange swaps the
+// configurations of two neighbouring slots: the spin words, E, M and the replica label.  Round x (the handle's exchange
+// cursor, 0 after dqmc_mc_set_exchange, + 1 per round) tries the pairs (i, i + 1), i = x mod 2, i + 1 < R, ladder-local.
+// For slots (a, b = a + 1): d = (E_a - E_b) / 2 (an integer: E = n_bonds mod 2), db = beta_a - beta_b (host, fp64).  The
+// pair swaps if db == 0, d == 0 or db and d have the same sign; otherwise iff u < p with p = the product, in ascending
+// j, of q[j] = exp(-2 |db| 2^j) (host libm, a table per pair) over the set bits j of |d|, and
+// u = philox4_uniform(key_a, low32(x), high32(x), 2, 0): a third domain, c2 = 2.  No exp on the device, and products
+// of doubles are exactly rounded, so a host restatement reproduces every decision bit for bit.  In a sweep the order
+// is local sweep, cluster move, exchange round, measurement.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -45,6 +57,7 @@ namespace dqmc_mc {
 constexpr int MAX_SITES = 16384;  // 512 words x 64 lanes x 4 B = 128 KiB of LDS per workgroup
 constexpr int MAX_Z = 8;
 constexpr int WAVE = 64;
+constexpr int MAX_XJ = 17;  // entries of an exchange pair's table: 2^J > n_bonds, n_bonds <= MAX_Z MAX_SITES / 2 = 2^16
 // one launch runs at most this many site visits summed over its walkers (sites x sweeps x walkers), a handle with
 // fewer than BUDGET_WALKERS walkers counted as that many (their waves run side by side, so a launch takes as long as
 // one walker's chain); dqmc_mc_sweep splits its sweeps into launches of at least one sweep each, so that no single
@@ -71,6 +84,71 @@ struct DevState {
 
 // flat index of lane `w` in the [row][W] arrays
 __device__ __forceinline__ size_t at(int row, int W, int w) { return (size_t)row * W + w; }
+
+// replica exchange: a kernel argument of its own, so that DevState keeps its layout
+struct Exchange {
+    int R, rate, J;               // ladder length, a round after every rate-th sweep (0: by hand only), entries of q per pair
+    unsigned long long x;         // the exchange cursor at the start of the launch
+    const double *__restrict__ q; // [J][W], column a: q[j] = exp(-2 |beta_a - beta_{a+1}| 2^j) of the pair (a, a + 1)
+    const int *__restrict__ sgn;  // [W], sign of beta_a - beta_{a+1}
+    int *replica;                 // [W], the label of the configuration in the slot
+    long long *prop, *acc;        // [W], tries and swaps of the pair (a, a + 1)
+};
+
+// does the pair (a, a + 1) swap in round xc?  (the rule at the top of this file; a draw only when it decides)
+__device__ __forceinline__ bool ising_exchange_decide(const Exchange &x, unsigned long long xc, int W, int a,
+                                                      unsigned long long key_a, int sgn, int Ea, int Eb)
+{
+    const int d = (Ea - Eb) / 2;
+    if (sgn == 0 || d == 0 || (d > 0) == (sgn > 0)) return true;
+    const unsigned int ad = (unsigned int)(d < 0 ? -d : d);
+    double q[MAX_XJ];  // the pair's whole table as one batch of requests, not a round trip per set bit
+#pragma unroll
+    for (int j = 0; j < MAX_XJ; ++j) q[j] = j < x.J ? x.q[at(j, W, a)] : 1.0;
+    double p = 1.0;
+#pragma unroll
+    for (int j = 0; j < MAX_XJ; ++j)
+        if ((ad >> j) & 1u) p = p * q[j];  // (|d| < 2^J: no bit at or above J is set)
+    return dqmc::philox4_uniform(key_a, (unsigned int)xc, (unsigned int)(xc >> 32), 2u, 0u) < p;
+}
+
+// one exchange round inside the sweep kernels (64 % R == 0: a ladder never straddles a wave).  il = the slot's index in
+// its ladder.  The lower lane of a pair decides; the upper one reads the decision, and both take the partner's E, M and
+// label, by cross-lane reads.  Then the nw spin words change columns: every lane reads sp[j * 64 + src] and writes
+// sp[j * 64 + lane], src = the partner where the pair swaps.  The write of a word waits for the data of its read, the
+// workgroup is one wave, and a wave's LDS instructions execute in order for all its lanes at once: every lane has read
+// word j before any lane overwrites it, so no barrier is needed (words j and j' never share an address).  Lanes past
+// W have left the kernel; n_walkers % R == 0 keeps every partner below W.
+__device__ __forceinline__ void ising_exchange_round(unsigned int *sp, const Exchange &x, unsigned long long xc, int lane,
+                                                     int w, int W, int nw, int il, unsigned long long key, int sgn, int &E,
+                                                     int &M, int &rep, long long &xprop, long long &xacc)
+{
+    const bool lo = ((il ^ (int)xc) & 1) == 0;
+    const bool active = lo ? il + 1 < x.R : il > 0;
+    const int partner = active ? (lo ? lane + 1 : lane - 1) : lane;
+    const int Ep = __shfl(E, partner), Mp = __shfl(M, partner), rp = __shfl(rep, partner);
+    int swap = 0;
+    if (active && lo) {
+        swap = ising_exchange_decide(x, xc, W, w, key, sgn, E, Ep) ? 1 : 0;
+        ++xprop;
+        xacc += swap;
+    }
+    swap = __shfl(swap, lo ? lane : partner);
+    if (!__any(swap)) return;  // uniform: no pair of this wave swaps
+    if (swap) {
+        E = Ep;
+        M = Mp;
+        rep = rp;
+    }
+    const int src = swap ? partner : lane;
+    __builtin_amdgcn_wave_barrier();
+    for (int j = 0; j < nw; ++j) {
+        const unsigned int v = sp[j * WAVE + src];
+        __builtin_amdgcn_wave_barrier();  // (no instruction: keeps the compiler from moving LDS accesses across)
+        sp[j * WAVE + lane] = v;
+        __builtin_amdgcn_wave_barrier();
+    }
+}
 
 // push!(observable, value) of IsingEnergyMeasurement / IsingMagnetizationMeasurement (measurements.jl:30-35,72-78) into
 // the walker's logarithmic binner (include/dqmc_hip.h, "error bars of the MC flavor"): elements [E, E2, M, M2] with
@@ -121,198 +199,13 @@ __device__ __forceinline__ void ising_bin_push(double *__restrict__ xs, double *
     xy[a2 + sW] = p1 + x[2] * x[3];
 }
 
-// the neighbour table is a kernel argument of its own, read-only and not aliased: that is what lets the compiler read
-// a row with one scalar load (a member of DevState would be an ordinary pointer the kernel's stores might alias)
-template <int Z>
-__global__ __launch_bounds__(WAVE) void ising_sweep_kernel(DevState s, const int4 *__restrict__ nbr, int n_sweeps,
-                                                           long long first_sweep, long long thermalization,
-                                                           int measure_rate, long long deferred_sweep)
-{
-    extern __shared__ unsigned int sp[];
-    const int lane = threadIdx.x;
-    const int w = blockIdx.x * WAVE + lane;
-    if (w >= s.W) return;
-    const int N = s.N, nw = s.nw, W = s.W;
-    for (int j = 0; j < nw; ++j) sp[j * WAVE + lane] = s.conf[at(j, W, w)];
-    const unsigned long long key = s.key[w];
-    unsigned long long draw = s.draw[w];
-    int E = s.E[w], M = s.M[w];
-    double thr[Z];
-#pragma unroll
-    for (int k = 0; k < Z; ++k) thr[k] = s.thr[at(k, W, w)];
-    double sE = s.sE[w], sE2 = s.sE2[w], sM = s.sM[w], sM2 = s.sM2[w];
-    long long n_meas = s.n_meas[w], n_series = s.n_series[w], acc = 0;
-
-    for (int sw = 0; sw < n_sweeps; ++sw) {
-        int cw = 0;
-        unsigned int cur = sp[lane];
-        int4 r0 = nbr[0], r1 = nbr[1];  // row of site 0; the row of site i + 1 is requested while site i runs
-        for (int i = 0; i < N; ++i) {
-            const int iw = i >> 5, ib = i & 31;
-            if (iw != cw) {  // uniform: the previous word is complete
-                sp[cw * WAVE + lane] = cur;
-                cw = iw;
-                cur = sp[cw * WAVE + lane];
-            }
-            const int row[8] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w};
-            r0 = nbr[2 * i + 2];  // (the table holds N + 1 rows)
-            r1 = nbr[2 * i + 3];
-            int up = 0;
-#pragma unroll
-            for (int k = 0; k < Z; ++k) {
-                const int j = row[k], jw = j >> 5;
-                const unsigned int v = jw == iw ? cur : sp[jw * WAVE + lane];
-                up += (v >> (j & 31)) & 1u;
-            }
-            const int si = (cur >> ib) & 1u;
-            const int sum = 2 * up - Z;         // sum of the neighbours' spins
-            const int k = si ? sum : -sum;      // dE / 2
-            bool accept = k <= 0;
-            if (k > 0) {
-                const double u = dqmc::philox_uniform(key, draw);
-                ++draw;
-                double t = thr[0];
-#pragma unroll
-                for (int q = 1; q < Z; ++q) t = k == q + 1 ? thr[q] : t;
-                accept = u < t;
-            }
-            if (accept) {
-                cur ^= 1u << ib;
-                E += 2 * k;
-                M += si ? -2 : 2;
-                ++acc;
-            }
-        }
-        sp[cw * WAVE + lane] = cur;
-        const long long g = first_sweep + sw;  // global 1-based sweep index (MC.jl:262-283)
-        // the measurement of deferred_sweep (-1: none) follows that sweep's cluster move (ising_wolff_kernel)
-        if (g > thermalization && g % measure_rate == 0 && g != deferred_sweep) {
-            const double e = (double)E, m = (double)(M < 0 ? -M : M);
-            sE += e;
-            sE2 += e * e;
-            sM += m;
-            sM2 += m * m;
-            if (n_series < s.cap) {
-                s.serE[at((int)n_series, W, w)] = E;
-                s.serM[at((int)n_series, W, w)] = M < 0 ? -M : M;
-                ++n_series;
-            }
-            ++n_meas;
-        }
-    }
-    for (int j = 0; j < nw; ++j) s.conf[at(j, W, w)] = sp[j * WAVE + lane];
-    s.draw[w] = draw;
-    s.E[w] = E;
-    s.M[w] = M;
-    s.sE[w] = sE;
-    s.sE2[w] = sE2;
-    s.sM[w] = sM;
-    s.sM2[w] = sM2;
-    s.n_meas[w] = n_meas;
-    s.n_series[w] = n_series;
-    s.prop[w] += (long long)n_sweeps * N;
-    s.acc[w] += acc;
-}
-
-// ising_sweep_kernel with the binner on: the same chain, and every measurement is pushed where it is taken.  T = pushes
-// before this launch (all walkers of a handle measure at the same sweeps, so one count serves them all and the cascade
-// length of a push is the same in every lane).  The site loop is a copy, not a shared helper: routed through one, the
-// eight forms above come out with other registers and another instruction order.
-template <int Z>
-__global__ __launch_bounds__(WAVE) void ising_sweep_binned_kernel(DevState s, const int4 *__restrict__ nbr,
-                                                                  int n_sweeps, long long first_sweep,
-                                                                  long long thermalization, int measure_rate,
-                                                                  long long deferred_sweep, double *__restrict__ bxs,
-                                                                  double *__restrict__ bx2, double *__restrict__ bxy,
-                                                                  double *__restrict__ bc, int top, long long T)
-{
-    extern __shared__ unsigned int sp[];
-    const int lane = threadIdx.x;
-    const int w = blockIdx.x * WAVE + lane;
-    if (w >= s.W) return;
-    const int N = s.N, nw = s.nw, W = s.W;
-    for (int j = 0; j < nw; ++j) sp[j * WAVE + lane] = s.conf[at(j, W, w)];
-    const unsigned long long key = s.key[w];
-    unsigned long long draw = s.draw[w];
-    int E = s.E[w], M = s.M[w];
-    double thr[Z];
-#pragma unroll
-    for (int k = 0; k < Z; ++k) thr[k] = s.thr[at(k, W, w)];
-    double sE = s.sE[w], sE2 = s.sE2[w], sM = s.sM[w], sM2 = s.sM2[w];
-    long long n_meas = s.n_meas[w], n_series = s.n_series[w], acc = 0;
-
-    for (int sw = 0; sw < n_sweeps; ++sw) {
-        int cw = 0;
-        unsigned int cur = sp[lane];
-        int4 r0 = nbr[0], r1 = nbr[1];  // row of site 0; the row of site i + 1 is requested while site i runs
-        for (int i = 0; i < N; ++i) {
-            const int iw = i >> 5, ib = i & 31;
-            if (iw != cw) {  // uniform: the previous word is complete
-                sp[cw * WAVE + lane] = cur;
-                cw = iw;
-                cur = sp[cw * WAVE + lane];
-            }
-            const int row[8] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w};
-            r0 = nbr[2 * i + 2];  // (the table holds N + 1 rows)
-            r1 = nbr[2 * i + 3];
-            int up = 0;
-#pragma unroll
-            for (int k = 0; k < Z; ++k) {
-                const int j = row[k], jw = j >> 5;
-                const unsigned int v = jw == iw ? cur : sp[jw * WAVE + lane];
-                up += (v >> (j & 31)) & 1u;
-            }
-            const int si = (cur >> ib) & 1u;
-            const int sum = 2 * up - Z;         // sum of the neighbours' spins
-            const int k = si ? sum : -sum;      // dE / 2
-            bool accept = k <= 0;
-            if (k > 0) {
-                const double u = dqmc::philox_uniform(key, draw);
-                ++draw;
-                double t = thr[0];
-#pragma unroll
-                for (int q = 1; q < Z; ++q) t = k == q + 1 ? thr[q] : t;
-                accept = u < t;
-            }
-            if (accept) {
-                cur ^= 1u << ib;
-                E += 2 * k;
-                M += si ? -2 : 2;
-                ++acc;
-            }
-        }
-        sp[cw * WAVE + lane] = cur;
-        const long long g = first_sweep + sw;  // global 1-based sweep index (MC.jl:262-283)
-        // the measurement of deferred_sweep (-1: none) follows that sweep's cluster move (ising_wolff_kernel)
-        if (g > thermalization && g % measure_rate == 0 && g != deferred_sweep) {
-            const double e = (double)E, m = (double)(M < 0 ? -M : M);
-            sE += e;
-            sE2 += e * e;
-            sM += m;
-            sM2 += m * m;
-            if (n_series < s.cap) {
-                s.serE[at((int)n_series, W, w)] = E;
-                s.serM[at((int)n_series, W, w)] = M < 0 ? -M : M;
-                ++n_series;
-            }
-            ++n_meas;
-            ising_bin_push(bxs, bx2, bxy, bc, W, w, min(top, __builtin_ctzll(~(unsigned long long)T)), top, e, m);
-            ++T;
-        }
-    }
-    for (int j = 0; j < nw; ++j) s.conf[at(j, W, w)] = sp[j * WAVE + lane];
-    s.draw[w] = draw;
-    s.E[w] = E;
-    s.M[w] = M;
-    s.sE[w] = sE;
-    s.sE2[w] = sE2;
-    s.sM[w] = sM;
-    s.sM2[w] = sM2;
-    s.n_meas[w] = n_meas;
-    s.n_series[w] = n_series;
-    s.prop[w] += (long long)n_sweeps * N;
-    s.acc[w] += acc;
-}
+// the sweep kernels, without and with the exchange round (ising_sweep.inl)
+#define ISING_EXCHANGE 0
+#include "ising_sweep.inl"
+#undef ISING_EXCHANGE
+#define ISING_EXCHANGE 1
+#include "ising_sweep.inl"
+#undef ISING_EXCHANGE
 
 // the push of a measurement that ising_wolff_kernel took (the deferred measurement of the sweep its move follows): E
 // and M as that kernel left them, one lane per walker
@@ -464,6 +357,70 @@ __global__ __launch_bounds__(WOLFF_THREADS) void ising_wolff_kernel(DevState s, 
     }
 }
 
+// the measurement of run! (MC.jl:262-283) of slot w, as ising_wolff_kernel takes it
+__device__ __forceinline__ void ising_measure_slot(const DevState &s, int w, int E, int M)
+{
+    const double ed = (double)E, md = (double)(M < 0 ? -M : M);
+    const double sE = s.sE[w], sE2 = s.sE2[w], sM = s.sM[w], sM2 = s.sM2[w];  // requested together
+    const long long ns = s.n_series[w], nm = s.n_meas[w];
+    s.sE[w] = sE + ed;
+    s.sE2[w] = sE2 + ed * ed;
+    s.sM[w] = sM + md;
+    s.sM2[w] = sM2 + md * md;
+    if (ns < s.cap) {
+        s.serE[at((int)ns, s.W, w)] = E;
+        s.serM[at((int)ns, s.W, w)] = M < 0 ? -M : M;
+        s.n_series[w] = ns + 1;
+    }
+    s.n_meas[w] = nm + 1;
+}
+
+// one exchange round (x.x) on the state in global memory: any R, ladders that cross waves, a round that follows a
+// cluster move, dqmc_mc_exchange.  One lane per slot; the lower lane of a pair decides and swaps E, M, the label and the
+// nw words of the two columns, which no other lane touches in this round; upper lanes have nothing to do.  measure != 0:
+// the measurement of the sweep this round ends, taken for both slots of a pair by its lower lane and for a slot
+// without a pair by its own.
+__global__ __launch_bounds__(WAVE) void ising_exchange_kernel(DevState s, Exchange x, int measure)
+{
+    const int w = blockIdx.x * WAVE + threadIdx.x;
+    if (w >= s.W) return;
+    const int il = w % x.R;
+    const bool lo = ((il ^ (int)x.x) & 1) == 0;
+    const bool active = lo ? il + 1 < x.R : il > 0;
+    if (active && !lo) return;
+    int E = s.E[w], M = s.M[w];
+    if (active) {  // (il + 1 < R and W % R == 0: w + 1 < W)
+        const int b = w + 1;
+        int Eb = s.E[b], Mb = s.M[b];
+        const int ra = x.replica[w], rb = x.replica[b], sgn = x.sgn[w];  // everything the round reads, requested together
+        const unsigned long long key = s.key[w];
+        const long long prop = x.prop[w], acc = x.acc[w];
+        const bool swap = ising_exchange_decide(x, x.x, s.W, w, key, sgn, E, Eb);
+        x.prop[w] = prop + 1;
+        if (swap) {
+            x.acc[w] = acc + 1;
+            const int t = E, u = M;
+            E = Eb;
+            M = Mb;
+            Eb = t;
+            Mb = u;
+            s.E[w] = E;
+            s.M[w] = M;
+            s.E[b] = Eb;
+            s.M[b] = Mb;
+            x.replica[w] = rb;
+            x.replica[b] = ra;
+            for (int j = 0; j < s.nw; ++j) {
+                const unsigned int va = s.conf[at(j, s.W, w)], vb = s.conf[at(j, s.W, b)];
+                s.conf[at(j, s.W, w)] = vb;
+                s.conf[at(j, s.W, b)] = va;
+            }
+        }
+        if (measure) ising_measure_slot(s, b, Eb, Mb);
+    }
+    if (measure) ising_measure_slot(s, w, E, M);
+}
+
 }  // namespace dqmc_mc
 
 using namespace dqmc_mc;
@@ -471,6 +428,15 @@ using namespace dqmc_mc;
 struct dqmc_mc_handle {
     int N = 0, z = 0, W = 0, nw = 0, cap = 0, n_bonds = 0, device = 0;
     int global_rate = 0;       // mc.p.global_rate when global moves are on, 0 = off
+    struct Tempering {         // replica exchange (dqmc_mc_set_exchange); R = 0: no ladders
+        int R = 0, rate = 0, J = 0;
+        uint64_t cursor = 0;   // rounds since dqmc_mc_set_exchange
+        double *q = nullptr;   // [MAX_XJ][W]
+        int *sgn = nullptr, *replica = nullptr;
+        long long *prop = nullptr, *acc = nullptr;
+        bool fused() const { return R >= 2 && rate > 0 && WAVE % R == 0; }
+    } xch;
+    std::vector<double> beta_h;  // [W], as dqmc_mc_set_beta got them
     std::vector<int> nbr_h;    // [N][z] 0-based
     std::vector<int> bonds_h;  // [n_bonds][2] 0-based
     hipStream_t stream = nullptr;
@@ -551,6 +517,40 @@ static int mc_launch_wolff(dqmc_mc_handle *h, int walker, int measure)
                        h->d, (const int *)h->d.nbr, h->z, walker, measure);
     MCHK(hipGetLastError());
     return 0;
+}
+
+static Exchange mc_exchange_arg(const dqmc_mc_handle *h)
+{
+    const dqmc_mc_handle::Tempering &t = h->xch;
+    return Exchange{t.R, t.rate, t.J, (unsigned long long)t.cursor, t.q, t.sgn, t.replica, t.prop, t.acc};
+}
+
+// one round at the handle's cursor, which it advances
+static int mc_launch_exchange(dqmc_mc_handle *h, int measure)
+{
+    hipLaunchKernelGGL(ising_exchange_kernel, dim3((h->W + WAVE - 1) / WAVE), dim3(WAVE), 0, h->stream, h->d,
+                       mc_exchange_arg(h), measure);
+    MCHK(hipGetLastError());
+    h->xch.cursor += 1;
+    return 0;
+}
+
+// the table of the pair (a, a + 1) into column a: q[j] = exp(-2 |beta_a - beta_{a+1}| 2^j) and the sign of the difference
+static void mc_pair_table(const dqmc_mc_handle *h, int a, double q[MAX_XJ], int *sgn)
+{
+    const double db = h->beta_h[a] - h->beta_h[a + 1];
+    *sgn = db > 0.0 ? 1 : (db < 0.0 ? -1 : 0);
+    for (int j = 0; j < MAX_XJ; ++j) q[j] = exp(-2.0 * fabs(db) * (double)(1 << j));
+}
+
+static int mc_put_pair_table(dqmc_mc_handle *h, int a)
+{
+    double q[MAX_XJ];
+    int sgn = 0;
+    mc_pair_table(h, a, q, &sgn);
+    MCHK(hipMemcpy2DAsync(h->xch.q + a, (size_t)h->W * sizeof(double), q, sizeof(double), sizeof(double), MAX_XJ,
+                          hipMemcpyHostToDevice, h->stream));
+    return mc_put<int>(h, h->xch.sgn, 0, a, sgn);
 }
 
 static const int64_t MC_BIN_DEFAULT_CAPACITY = 100000;  // BinningAnalysis' _default_capacity
@@ -659,6 +659,7 @@ int dqmc_mc_create(const dqmc_mc_params *p, dqmc_mc_handle **out)
     h->cap = p->series_capacity;
     h->n_bonds = nb;
     h->device = p->device_id;
+    h->beta_h.assign((size_t)p->n_walkers, 0.0);
     h->nbr_h.resize((size_t)N * z);
     for (int i = 0; i < N; ++i)
         for (int k = 0; k < z; ++k) h->nbr_h[(size_t)i * z + k] = (int)p->neighs[(size_t)i * z + k] - 1;
@@ -745,7 +746,14 @@ int dqmc_mc_set_beta(dqmc_mc_handle *h, int32_t walker, double beta)
     for (int k = 1; k <= MAX_Z; ++k) thr[k - 1] = exp(-beta * (2.0 * k));  // exp(-beta dE), MC.jl:327
     MCHK(hipMemcpy2DAsync(h->d.thr + walker, (size_t)h->W * sizeof(double), thr, sizeof(double), sizeof(double), MAX_Z,
                           hipMemcpyHostToDevice, h->stream));
-    return mc_put<double>(h, h->d.pw, 0, walker, 1.0 - exp(-2.0 * beta));  // 1 - exp(-2 beta), IsingModel.jl:126
+    if (int rc = mc_put<double>(h, h->d.pw, 0, walker, 1.0 - exp(-2.0 * beta))) return rc;  // 1 - exp(-2 beta), IsingModel.jl:126
+    h->beta_h[walker] = beta;
+    const int R = h->xch.R;  // the exchange tables of the two pairs this slot belongs to
+    if (R >= 2 && walker % R > 0)
+        if (int rc = mc_put_pair_table(h, walker - 1)) return rc;
+    if (R >= 2 && walker % R + 1 < R)
+        if (int rc = mc_put_pair_table(h, walker)) return rc;
+    return DQMC_OK;
 }
 
 int dqmc_mc_seed(dqmc_mc_handle *h, int32_t walker, uint64_t seed)
@@ -835,32 +843,51 @@ int dqmc_mc_sweep(dqmc_mc_handle *h, int32_t n_sweeps, int64_t first_sweep_index
     const double per_sweep = (double)h->N * std::max((double)h->W, BUDGET_WALKERS);
     const int chunk = (int)std::max(1.0, std::min((double)n_sweeps, std::floor(LAUNCH_BUDGET / per_sweep)));
     const int r = h->global_rate;
+    dqmc_mc_handle::Tempering &t = h->xch;
+    const int k = t.R >= 2 ? t.rate : 0;  // an exchange round after every k-th sweep
+    const bool fused = t.fused();
     for (int done = 0; done < n_sweeps;) {
         int n = std::min(chunk, n_sweeps - done);
         const long long first = first_sweep_index + done;
         if (r > 0) n = (int)std::min<long long>(n, r - (first - 1) % r);  // a launch ends at the next multiple of r
+        // and at the next multiple of k where the round is a launch of its own (fused: only behind a cluster move)
+        if (k > 0 && !fused) n = (int)std::min<long long>(n, k - (first - 1) % k);
         const long long last = first + n - 1;
         const bool move = r > 0 && last % r == 0;  // global_move after sweep `last` (MC.jl:233-236)
-        const bool deferred = move && last > thermalization && last % measure_rate == 0;
-        switch (h->z) {  // binner on: the forms that push every measurement they take
+        const bool round = k > 0 && last % k == 0 && (!fused || move);  // ising_exchange_kernel after sweep `last`
+        const bool deferred = (move || round) && last > thermalization && last % measure_rate == 0;
+        const long long defer = move || round ? last : -1LL;
+        const Exchange xa = mc_exchange_arg(h);
+        switch (h->z) {  // binner on: the forms that push every measurement they take; fused: with the exchange round
 #define MC_CASE(Z)                                                                                                  \
     case Z:                                                                                                         \
-        if (b.on)                                                                                                   \
+        if (b.on && fused)                                                                                          \
+            hipLaunchKernelGGL(ising_sweep_binned_exchange_kernel<Z>, dim3(grid), dim3(WAVE), lds, h->stream, h->d, \
+                               (const int4 *)h->d.nbr, n, first, (long long)thermalization, (int)measure_rate,     \
+                               defer, b.xs, b.x2, b.xy, b.c, b.L - 1, (long long)b.T, xa);                          \
+        else if (b.on)                                                                                              \
             hipLaunchKernelGGL(ising_sweep_binned_kernel<Z>, dim3(grid), dim3(WAVE), lds, h->stream, h->d,         \
                                (const int4 *)h->d.nbr, n, first, (long long)thermalization, (int)measure_rate,     \
-                               move ? last : -1LL, b.xs, b.x2, b.xy, b.c, b.L - 1, (long long)b.T);                \
+                               defer, b.xs, b.x2, b.xy, b.c, b.L - 1, (long long)b.T);                              \
+        else if (fused)                                                                                             \
+            hipLaunchKernelGGL(ising_sweep_exchange_kernel<Z>, dim3(grid), dim3(WAVE), lds, h->stream, h->d,       \
+                               (const int4 *)h->d.nbr, n, first, (long long)thermalization, (int)measure_rate,     \
+                               defer, xa);                                                                          \
         else                                                                                                        \
             hipLaunchKernelGGL(ising_sweep_kernel<Z>, dim3(grid), dim3(WAVE), lds, h->stream, h->d,                \
-                               (const int4 *)h->d.nbr, n, first,                                                   \
-                               (long long)thermalization, (int)measure_rate, move ? last : -1LL);                  \
+                               (const int4 *)h->d.nbr, n, first, (long long)thermalization, (int)measure_rate,     \
+                               defer);                                                                              \
         break;
             MC_CASE(1) MC_CASE(2) MC_CASE(3) MC_CASE(4) MC_CASE(5) MC_CASE(6) MC_CASE(7) MC_CASE(8)
 #undef MC_CASE
         }
         if (b.on) b.T += mc_measurements_in(first, last, thermalization, measure_rate) - (deferred ? 1 : 0);
         MCHK(hipGetLastError());
+        if (fused) t.cursor += (uint64_t)(last / k - (first - 1) / k - (round ? 1 : 0));  // the rounds the launch ran
         if (move)
-            if (int rc = mc_launch_wolff(h, -1, deferred)) return rc;
+            if (int rc = mc_launch_wolff(h, -1, deferred && !round)) return rc;  // the last kernel of a sweep measures
+        if (round)
+            if (int rc = mc_launch_exchange(h, deferred)) return rc;
         if (deferred && b.on)
             if (int rc = mc_launch_bin_push(h)) return rc;
         done += n;
@@ -930,6 +957,101 @@ int dqmc_mc_get_global_stats(dqmc_mc_handle *h, int32_t walker, dqmc_mc_global_s
     out->acc_global = acc;
     out->sum_cluster_size = sum;
     out->moves_drawn = moves;
+    return DQMC_OK;
+}
+
+int dqmc_mc_set_exchange(dqmc_mc_handle *h, int32_t n_replicas, int32_t rate)
+{
+    if (!h) return mc_fail(nullptr, DQMC_ERR_INVALID, "dqmc_mc_set_exchange: null handle");
+    if (n_replicas < 0 || rate < 0)
+        return mc_fail(h, DQMC_ERR_INVALID, "dqmc_mc_set_exchange: n_replicas and rate must be >= 0 (0 = off)");
+    const int R = n_replicas >= 2 ? n_replicas : 0;
+    if (R && h->W % R != 0)
+        return mc_fail(h, DQMC_ERR_INVALID, "dqmc_mc_set_exchange: n_walkers must be a multiple of n_replicas");
+    MCHK(hipSetDevice(h->device));
+    dqmc_mc_handle::Tempering &t = h->xch;
+    const size_t W = h->W;
+    if (R && !t.q) {
+        int rc = 0;
+        if ((rc = mc_alloc(h, &t.q, (size_t)MAX_XJ * W)) || (rc = mc_alloc(h, &t.sgn, W)) ||
+            (rc = mc_alloc(h, &t.replica, W)) || (rc = mc_alloc(h, &t.prop, W)) || (rc = mc_alloc(h, &t.acc, W)))
+            return rc;
+    }
+    if (R && WAVE % R == 0) {  // the whole spin array of a workgroup in LDS above the 64 KiB default, as dqmc_mc_create
+        const void *kernels[] = {
+            (const void *)ising_sweep_exchange_kernel<1>,        (const void *)ising_sweep_exchange_kernel<2>,
+            (const void *)ising_sweep_exchange_kernel<3>,        (const void *)ising_sweep_exchange_kernel<4>,
+            (const void *)ising_sweep_exchange_kernel<5>,        (const void *)ising_sweep_exchange_kernel<6>,
+            (const void *)ising_sweep_exchange_kernel<7>,        (const void *)ising_sweep_exchange_kernel<8>,
+            (const void *)ising_sweep_binned_exchange_kernel<1>, (const void *)ising_sweep_binned_exchange_kernel<2>,
+            (const void *)ising_sweep_binned_exchange_kernel<3>, (const void *)ising_sweep_binned_exchange_kernel<4>,
+            (const void *)ising_sweep_binned_exchange_kernel<5>, (const void *)ising_sweep_binned_exchange_kernel<6>,
+            (const void *)ising_sweep_binned_exchange_kernel<7>, (const void *)ising_sweep_binned_exchange_kernel<8>};
+        for (const void *k : kernels)
+            if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)h->nw * WAVE * 4)) !=
+                hipSuccess)
+                return mc_fail(h, DQMC_ERR_HIP, "dqmc_mc_set_exchange: cannot reserve LDS for the spins");
+    }
+    t.R = R;
+    t.rate = rate;
+    t.cursor = 0;
+    t.J = 0;
+    while ((1L << t.J) <= (long)h->n_bonds) ++t.J;  // 2^J > n_bonds >= |d|
+    if (t.q) {
+        MCHK(hipMemsetAsync(t.prop, 0, W * 8, h->stream));
+        MCHK(hipMemsetAsync(t.acc, 0, W * 8, h->stream));
+        std::vector<int> label(W, 0), sgn(W, 0);
+        std::vector<double> q((size_t)MAX_XJ * W, 0.0);
+        for (size_t w = 0; R && w < W; ++w) {
+            label[w] = (int)(w % R);
+            if (w % R + 1 == (size_t)R) continue;  // the last slot of a ladder has no pair of its own
+            double col[MAX_XJ];
+            mc_pair_table(h, (int)w, col, &sgn[w]);
+            for (int j = 0; j < MAX_XJ; ++j) q[(size_t)j * W + w] = col[j];
+        }
+        MCHK(hipMemcpyAsync(t.replica, label.data(), W * 4, hipMemcpyHostToDevice, h->stream));
+        MCHK(hipMemcpyAsync(t.sgn, sgn.data(), W * 4, hipMemcpyHostToDevice, h->stream));
+        MCHK(hipMemcpyAsync(t.q, q.data(), q.size() * 8, hipMemcpyHostToDevice, h->stream));
+    }
+    MCHK(hipStreamSynchronize(h->stream));
+    return DQMC_OK;
+}
+
+int dqmc_mc_exchange(dqmc_mc_handle *h)
+{
+    if (!h) return mc_fail(nullptr, DQMC_ERR_INVALID, "dqmc_mc_exchange: null handle");
+    if (h->xch.R < 2)
+        return mc_fail(h, DQMC_ERR_STATE, "dqmc_mc_exchange: no ladders (dqmc_mc_set_exchange with n_replicas >= 2 first)");
+    MCHK(hipSetDevice(h->device));
+    if (int rc = mc_launch_exchange(h, 0)) return rc;
+    MCHK(hipStreamSynchronize(h->stream));
+    return DQMC_OK;
+}
+
+int dqmc_mc_get_exchange_stats(dqmc_mc_handle *h, int32_t walker, dqmc_mc_exchange_stats *out)
+{
+    if (int rc = mc_walker(h, walker, "dqmc_mc_get_exchange_stats")) return rc;
+    if (!out) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_mc_get_exchange_stats: null out");
+    MCHK(hipSetDevice(h->device));
+    const dqmc_mc_handle::Tempering &t = h->xch;
+    long long prop = 0, acc = 0;
+    int label = 0;
+    int rc = 0;
+    if (t.q && ((rc = mc_get(h, t.prop, 0, walker, &prop)) || (rc = mc_get(h, t.acc, 0, walker, &acc)) ||
+                (rc = mc_get(h, t.replica, 0, walker, &label))))
+        return rc;
+    out->prop_exchange = prop;
+    out->acc_exchange = acc;
+    out->replica = label;
+    out->rounds = t.cursor;
+    return DQMC_OK;
+}
+
+int dqmc_mc_exchange_fused(dqmc_mc_handle *h, int32_t *fused)
+{
+    if (!h) return mc_fail(nullptr, DQMC_ERR_INVALID, "dqmc_mc_exchange_fused: null handle");
+    if (!fused) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_mc_exchange_fused: null fused");
+    *fused = h->xch.fused() ? 1 : 0;
     return DQMC_OK;
 }
 

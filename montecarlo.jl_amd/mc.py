@@ -3,7 +3,8 @@ measurements.jl), `n_walkers` independent Markov chains batched on one device (c
 
 Walker w draws from the Philox4x32-10 stream keyed by `seed + first_walker + w`: draws 0..N-1 give the initial
 configuration (rand(MC, m)), the Metropolis uniforms follow.  The Wolff cluster move (`cluster_moves=True`) draws from a
-domain of its own of the same key (include/dqmc_hip.h, dqmc_mc_global_move).  The host holds the model, the loop control
+domain of its own of the same key (include/dqmc_hip.h, dqmc_mc_global_move), and so does replica exchange
+(`n_replicas`, `exchange_rate`; dqmc_mc_set_exchange).  The host holds the model, the loop control
 and finish!; every site update runs on the device."""
 import ctypes as C
 import math
@@ -11,7 +12,7 @@ import time
 
 import numpy as np
 
-from ._lib import DQMCError, ERR_INVALID, McBinned, McGlobalStats, McParams, McStats, lib
+from ._lib import DQMCError, ERR_INVALID, McBinned, McExchangeStats, McGlobalStats, McParams, McStats, lib
 from .configurations import CompressedConf
 from .lattices import Chain, CubicLattice, SquareLattice
 
@@ -67,11 +68,19 @@ class MC:
 
     `binning=True` gives every walker a logarithmic binner over E, E2, |M| and M2, pushed on the device where the
     measurement is taken (enable_binning); `binned()` then answers mean, std_error and tau, and the errors of C and
-    chi."""
+    chi.
+
+    `n_replicas=R` (R >= 2, n_walkers a multiple of it) makes every R consecutive walkers a ladder for replica exchange
+    (parallel tempering, an extension the reference does not have; dqmc_mc_set_exchange defines it), and
+    `exchange_rate=k` runs one exchange round after every k-th sweep: after that sweep's cluster move, before its
+    measurement.  A `beta` or `T` sequence of length R is tiled over the ladders.  Walker w stays at beta_w with its
+    stream, sums, series and binner; an accepted exchange swaps the configurations (spins, E, M and the replica label)
+    of two neighbouring walkers, so measurements(w) and binned(w) remain "at beta_w".  `exchange_rate=0` leaves the
+    sweeps as they are without exchange; `exchange()` then still runs a round by hand."""
 
     def __init__(self, model, beta=None, T=None, n_walkers=1, seed=123, first_walker=0, thermalization=0, sweeps=1000,
                  measure_rate=1, print_rate=1000, global_moves=False, global_rate=5, device_id=0, series_capacity=0,
-                 cluster_moves=False, binning=False, binning_capacity=None):
+                 cluster_moves=False, binning=False, binning_capacity=None, n_replicas=0, exchange_rate=0):
         if global_moves:
             raise NotImplementedError(
                 "MC(global_moves=True): the reference's Wolff global_move cannot run (IsingModel.jl:137 uses the "
@@ -83,7 +92,12 @@ class MC:
             raise ValueError("MC needs exactly one of beta and T")
         if T is not None:
             beta = (1.0 / np.asarray(T, dtype=float)) if np.ndim(T) else 1.0 / float(T)
-        betas = np.broadcast_to(np.asarray(beta, dtype=float), (n_walkers,)).copy()
+        if int(n_replicas) != n_replicas or int(exchange_rate) != exchange_rate:
+            raise ValueError("MC: n_replicas and exchange_rate must be integers")
+        beta = np.asarray(beta, dtype=float)
+        if n_replicas >= 2 and beta.ndim == 1 and len(beta) == n_replicas and n_walkers % n_replicas == 0:
+            beta = np.tile(beta, n_walkers // n_replicas)  # one ladder's temperatures, the same in every ladder
+        betas = np.broadcast_to(beta, (n_walkers,)).copy()
         if not np.all(np.isfinite(betas)) or np.any(betas < 0):
             raise ValueError("beta must be finite and >= 0")
         if measure_rate < 1:
@@ -97,6 +111,7 @@ class MC:
         self.thermalization, self.sweeps, self.measure_rate = thermalization, sweeps, measure_rate
         self.print_rate, self.global_moves, self.global_rate = print_rate, global_moves, global_rate
         self.cluster_moves = bool(cluster_moves)
+        self.n_replicas, self.exchange_rate = int(n_replicas), int(exchange_rate)
         self.last_sweep = 0
         self.series_capacity = series_capacity
         self._neighs = np.asfortranarray(np.asarray(model.l.neighs, dtype=np.int64))
@@ -117,6 +132,8 @@ class MC:
         self._c(lib().dqmc_mc_rand_conf(self._h, -1))  # mc.conf = rand(MC, m); init! (MC.jl:61,74)
         if self.cluster_moves:
             self._c(lib().dqmc_mc_set_global_rate(self._h, int(global_rate)))
+        if self.n_replicas or self.exchange_rate:
+            self.set_exchange(self.n_replicas, self.exchange_rate)
         if binning:
             self.enable_binning(binning_capacity)
 
@@ -233,6 +250,35 @@ class MC:
         self._c(lib().dqmc_mc_get_global_stats(self._h, walker, C.byref(st)))
         return st
 
+    # ---- replica exchange
+    def set_exchange(self, n_replicas, rate):
+        """dqmc_mc_set_exchange: ladders of n_replicas consecutive walkers (0 or 1: none), a round after every rate-th
+        sweep (0: none); resets the exchange cursor, the replica labels and the exchange counters"""
+        self._c(lib().dqmc_mc_set_exchange(self._h, int(n_replicas), int(rate)))
+        self.n_replicas, self.exchange_rate = int(n_replicas), int(rate)
+
+    def exchange(self):
+        """one exchange round by hand (dqmc_mc_exchange), counted in the exchange stats, no measurement"""
+        self._c(lib().dqmc_mc_exchange(self._h))
+
+    def exchange_stats(self, walker=0):
+        """prop_exchange and acc_exchange of the pair (walker, walker + 1), the label `replica` of the configuration
+        now in the slot, and `rounds` (the exchange cursor)"""
+        st = McExchangeStats()
+        self._c(lib().dqmc_mc_get_exchange_stats(self._h, walker, C.byref(st)))
+        return st
+
+    def exchange_fused(self):
+        """True: sweep() runs its exchange rounds inside the sweep kernel (64 % n_replicas == 0)"""
+        f = C.c_int32()
+        self._c(lib().dqmc_mc_exchange_fused(self._h, C.byref(f)))
+        return bool(f.value)
+
+    def replicas(self):
+        """the replica labels of all slots: replicas()[w] is the ladder-local index of the slot in which the
+        configuration now in slot w started"""
+        return np.array([self.exchange_stats(w).replica for w in range(self.n_walkers)], dtype=np.int64)
+
     def reset_accumulators(self):
         self._c(lib().dqmc_mc_reset_accumulators(self._h))
 
@@ -244,7 +290,10 @@ class MC:
         """MCAnalysis (MC.jl:1-11) of one walker"""
         st = self.stats(walker)
         g = self.global_stats(walker)
+        x = self.exchange_stats(walker)
         return {"acc_rate": st.acc_local / st.prop_local if st.prop_local else 0.0, "prop_local": int(st.prop_local),
+                "acc_rate_exchange": x.acc_exchange / x.prop_exchange if x.prop_exchange else 0.0,
+                "prop_exchange": int(x.prop_exchange), "acc_exchange": int(x.acc_exchange),
                 "acc_local": int(st.acc_local),
                 "acc_rate_global": g.acc_global / g.prop_global if g.prop_global else 0.0,
                 "prop_global": int(g.prop_global), "acc_global": int(g.acc_global)}

@@ -35,6 +35,9 @@ def functions(src, extra):
             funcs[cur] = []
         elif cur and line.startswith("\t") and line.strip() != "...":  # ("...": padding between functions)
             funcs[cur].append(line.split("//")[0].strip())
+    for code in funcs.values():  # the s_nop fill behind a function's last instruction depends on what follows it
+        while code and code[-1] == "s_nop 0":
+            code.pop()
     return funcs
 
 
