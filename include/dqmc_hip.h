@@ -305,6 +305,44 @@ int dqmc_set_current_targets(dqmc_handle *h, const int32_t *trg_of, int32_t K, c
 int dqmc_current_targets_fast_path(dqmc_handle *h, int32_t *fast);
 int dqmc_current_targets_plan(dqmc_handle *h, int32_t out[8]);
 
+/* ---- time-displaced recording: G(r, tau) and the tau-resolved charge / spin correlations ---------------------------
+ * The reference has no such measurement: GreensAt{k,l} gives one (k, l) matrix and its susceptibilities integrate over l
+ * (generic.jl:226-243).  Like the global moves this is a defined extension.  Recording is a setting of the handle, as
+ * dqmc_set_current_targets is: once set, every dqmc_accumulate_susceptibilities pass also keeps, in the same pass, rows
+ * of what its packed kernels see at the slices l = 0, every, 2 every, ..., slices.
+ * dqmc_set_time_displaced(h, every, what): every == 0 turns recording off (the default; `what` is then ignored and
+ * nothing stays allocated).  Otherwise every >= 1 with slices % every == 0 (so that the row l = slices, tau = beta,
+ * exists) and `what` a non-empty mask of DQMC_TD_GREENS | DQMC_TD_DENSITY; anything else returns DQMC_ERR_INVALID and
+ * the handle keeps its setting.  Needs dqmc_set_pair_directions (DQMC_ERR_STATE without it); a later
+ * dqmc_set_pair_directions rebuilds the layout for the new table.  Every successful call starts the sums at zero.
+ * Rows r = 0 .. R-1, R = 1 + slices / every; row r belongs to l = r every, tau = l delta_tau.  Row 0 takes the packed
+ * tuple (G00, G0l, Gl0, Gll) = (G00, G00 - I, G00, G00) with G00 = greens!(mc): the -I is the tau -> 0+ limit of
+ * G(0, tau) = -<c^dagger(tau) c(0)>, and with it the packed charge and spin kernels are the equal-time kernels term by
+ * term (measurements.jl:60-73 against :75-92).  Rows r >= 1 take the tuple the CombinedGreensIterator yields at l.
+ * Per-walker sample = element order of the binner section (d fastest, then r, then the block b; N = n_sites):
+ *   [if GREENS : Gl0[b][r][d] = (1/N) sum over the pairs (i, j) of direction d of Gl0_b[i, j]    n_blocks R n_dirs
+ *                G0l[b][r][d] = (1/N) sum over the pairs (i, j) of direction d of G0l_b[i, j]    n_blocks R n_dirs]
+ *   [if DENSITY: CDC[r][d] SDCx[r][d] SDCy[r][d] SDCz[r][d]                                      4 R n_dirs]
+ * The DENSITY entries are the per-slice values whose sum over l, times delta_tau, is the cds / sds of the
+ * susceptibility layout: divided by N, no delta_tau.  The accumulator has the same layout, holds the sum of the samples
+ * over walkers and calls, and ends with [samples]; dqmc_reset_accumulators clears it.
+ * Every value is stored from a sum in a fixed order (no atomics): two passes on the same state give the same bits and a
+ * walker's sample does not depend on the other walkers.  The Green's rows take one of two kernels (csrc/tdm.hip):
+ * where n_dirs == n_sites and every source and every target meets each direction exactly once (translation-invariant
+ * tables) a lane owns a direction and walks the columns through a table src_of[d + n_dirs j] built here from dir_of, so
+ * that a wave reads within one column; every other table, or any table under DQMC_TDM_GENERAL=1 (read at dqmc_create),
+ * takes the pair lists.  dqmc_time_displaced_plan: out = [rows R, every, what, fast (1 / 0)], all zero when off.
+ * With recording off nothing is allocated or launched and every result is bit for bit that of a handle without it; with
+ * recording on the pass leaves the susceptibility accumulators, mc.s.greens, the stacks, the HS field and the RNG
+ * cursors bit for bit as without. */
+enum { DQMC_TD_GREENS = 1, DQMC_TD_DENSITY = 2 };
+int dqmc_set_time_displaced(dqmc_handle *h, int32_t every, int32_t what);
+/* doubles of the accumulator, sample count included (0 when recording is off) */
+int dqmc_time_displaced_size(dqmc_handle *h, size_t *n_doubles);
+int dqmc_get_time_displaced(dqmc_handle *h, double *host_out);
+int dqmc_export_time_displaced(dqmc_handle *h, void *device_out);
+int dqmc_time_displaced_plan(dqmc_handle *h, int32_t out[4]);   /* [rows R, every, what, fast] */
+
 /* ---- error bars: logarithmic binning per walker on the device ------------------------------------------------
  * The observable of a DQMCMeasurement is a BinningAnalysis LogBinner (measurements/generic.jl:35-39, default capacity
  * _default_capacity :68-88), and mean / var / std_error / tau are answered from it (generic.jl:58-61,
@@ -325,6 +363,8 @@ int dqmc_current_targets_plan(dqmc_handle *h, int32_t out[8]);
  *   DQMC_BIN_PAIRING           [n_dirs x K x K]
  *   DQMC_BIN_SUSCEPTIBILITIES  [cds][sds_x][sds_y][sds_z][ps if local targets][ccs if current targets]
  *   DQMC_BIN_USER              n_elements samples per walker supplied by the caller
+ *   DQMC_BIN_TIME_DISPLACED    the per-walker sample of "time-displaced recording" above (pushed by
+ *                              dqmc_accumulate_susceptibilities, which checks the room of both of its sections first)
  * Once a section is enabled, its dqmc_accumulate_* call also pushes every walker's sample, read in place from the
  * buffers the measurement kernels leave behind, after those kernels and on the same stream; the accumulators receive
  * exactly what they receive without a binner.  A push beyond the capacity fails with DQMC_ERR_STATE before anything is
@@ -332,6 +372,10 @@ int dqmc_current_targets_plan(dqmc_handle *h, int32_t out[8]);
  * nothing is allocated or launched. */
 enum { DQMC_BIN_GREENS = 0, DQMC_BIN_CORRELATIONS = 1, DQMC_BIN_PAIRING = 2, DQMC_BIN_SUSCEPTIBILITIES = 3,
        DQMC_BIN_USER = 4 };
+/* (an enum of its own: the five sections above are a closed list for hosts that enumerate them).  Enabling it needs
+ * dqmc_set_time_displaced and dqmc_prepare.  Memory: (3 L - 1) n_walkers E doubles, E = (2 n_blocks + 4) R n_dirs with
+ * both parts - choose `every` and the capacity with that in mind. */
+enum { DQMC_BIN_TIME_DISPLACED = 5 };
 /* LogBinner(zero, capacity = capacity) for every walker and element of a measurement section (generic.jl:39);
  * capacity 0 = 100000.  The section's measurement must be configured (pair directions, local / current targets; the
  * susceptibilities also need dqmc_prepare); if its layout changes afterwards, enable again.  Enabling again starts anew. */
@@ -381,6 +425,13 @@ int dqmc_reduce_size(dqmc_handle *h, size_t *n_doubles /* sums + 4 */);
 int dqmc_reduce_export(dqmc_handle *h, double *host_out);
 int dqmc_reduce_import(dqmc_handle *h, const double *host_in);
 enum { DQMC_RED_GREENS = 0, DQMC_RED_CORRELATIONS = 1, DQMC_RED_PAIRING = 2, DQMC_RED_SUSCEPTIBILITIES = 3 };
+/* With recording on (dqmc_set_time_displaced) the E = dqmc_time_displaced_size - 1 sums are packed behind the
+ * susceptibilities, in front of the counters: dqmc_reduce_size grows by exactly E; with recording off the buffer is byte
+ * for byte the one above.  The sample count is not packed a second time: the passes that record are the passes that feed
+ * the susceptibilities, so dqmc_get_reduced(DQMC_RED_TIME_DISPLACED) returns [E reduced sums][reduced susceptibility
+ * samples], dqmc_time_displaced_size doubles.  It returns DQMC_ERR_STATE when the two local counts differed at the
+ * reduction, i.e. recording was (re)set after susceptibility passes with no dqmc_reset_accumulators since. */
+enum { DQMC_RED_TIME_DISPLACED = 4 };
 int dqmc_get_reduced(dqmc_handle *h, int32_t which, double *host_out);
 int dqmc_get_reduced_stats(dqmc_handle *h, dqmc_stats *out);
 

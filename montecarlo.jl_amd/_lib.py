@@ -14,6 +14,8 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "dqmc_hip.h")
 OK, ERR_INVALID, ERR_HIP, ERR_NO_DEVICE, ERR_STATE, ERR_RNG = 0, -1, -2, -3, -4, -5
 ATTRACTIVE, REPULSIVE = 0, 1
 BIN_SECTIONS = ("greens", "correlations", "pairing", "susceptibilities", "user")  # DQMC_BIN_*
+BIN_TIME_DISPLACED, RED_TIME_DISPLACED = 5, 4  # DQMC_BIN_TIME_DISPLACED, DQMC_RED_TIME_DISPLACED (enums of their own)
+TD_GREENS, TD_DENSITY = 1, 2                   # DQMC_TD_*
 K_FAMILIES = ("gemm", "qr", "trsm", "sweep", "misc", "flush")
 
 
@@ -141,6 +143,11 @@ SIGNATURES = {
     "dqmc_set_current_targets": (C.c_int, [_H, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_double)]),
     "dqmc_current_targets_fast_path": (C.c_int, [_H, C.POINTER(C.c_int32)]),
     "dqmc_current_targets_plan": (C.c_int, [_H, C.POINTER(C.c_int32)]),
+    "dqmc_set_time_displaced": (C.c_int, [_H, C.c_int32, C.c_int32]),
+    "dqmc_time_displaced_size": (C.c_int, [_H, C.POINTER(C.c_size_t)]),
+    "dqmc_get_time_displaced": (C.c_int, [_H, _dp]),
+    "dqmc_export_time_displaced": (C.c_int, [_H, C.c_void_p]),
+    "dqmc_time_displaced_plan": (C.c_int, [_H, C.POINTER(C.c_int32)]),
     "dqmc_susceptibilities_size": (C.c_int, [_H, C.POINTER(C.c_size_t)]),
     "dqmc_get_susceptibilities": (C.c_int, [_H, _dp]),
     "dqmc_export_susceptibilities": (C.c_int, [_H, C.c_void_p]),

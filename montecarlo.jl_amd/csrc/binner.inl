@@ -5,7 +5,7 @@
 static const int64_t BIN_DEFAULT_CAPACITY = 100000;  // BinningAnalysis' _default_capacity
 
 #define BIN_OK(h, which)                                                                        \
-    if ((which) < DQMC_BIN_GREENS || (which) > DQMC_BIN_USER)                                   \
+    if ((which) < DQMC_BIN_GREENS || (which) > DQMC_BIN_TIME_DISPLACED)                         \
         return fail((h), DQMC_ERR_INVALID, "binner section out of range");                      \
     if (!(h)->bin[(which)].on) return fail((h), DQMC_ERR_STATE, "this section's binner is not enabled")
 
@@ -17,6 +17,7 @@ static long binner_section_elements(dqmc_handle *h, int which)
     case DQMC_BIN_CORRELATIONS: return h->n_dirs ? (long)h->corr_n - 1 : 0;
     case DQMC_BIN_PAIRING: return h->K_loc ? (long)h->pc_n - 1 : 0;
     case DQMC_BIN_SUSCEPTIBILITIES: return h->ut && h->ut->sus_n ? (long)h->ut->sus_n - 1 : 0;
+    case DQMC_BIN_TIME_DISPLACED: return h->td.every ? (long)h->td.E : 0;
     default: return h->bin[DQMC_BIN_USER].E;
     }
 }
@@ -96,6 +97,7 @@ static int binner_push_section(dqmc_handle *h, int which)
     case DQMC_BIN_GREENS: p.mode = BIN_SRC_GREENS; break;
     case DQMC_BIN_CORRELATIONS: p.mode = BIN_SRC_CORR; p.src = h->corr_per_walker; break;
     case DQMC_BIN_PAIRING: p.src = h->pc_per_walker; break;
+    case DQMC_BIN_TIME_DISPLACED: p.src = h->td.per_walker; break;  // rows as tdm.hip stored them: no delta_tau
     default: p.src = h->ut->sus_per_walker; p.scale = h->p.delta_tau; break;  // finish!: * delta_tau as sus_reduce_kernel
     }
     return binner_push(h, which, p);
@@ -133,8 +135,12 @@ static int binner_finish_device(dqmc_handle *h, int which, int32_t level)
 int dqmc_binner_enable(dqmc_handle *h, int32_t which, int64_t capacity)
 {
     ENTER(h);
-    if (which < DQMC_BIN_GREENS || which > DQMC_BIN_SUSCEPTIBILITIES)
+    if (which < DQMC_BIN_GREENS || which == DQMC_BIN_USER || which > DQMC_BIN_TIME_DISPLACED)
         return fail(h, DQMC_ERR_INVALID, "dqmc_binner_enable takes a measurement section (dqmc_binner_user_create makes the user binner)");
+    if (which == DQMC_BIN_TIME_DISPLACED) {
+        NEED_PREPARED(h);
+        if (!h->td.every) return fail(h, DQMC_ERR_STATE, "call dqmc_set_time_displaced first");
+    }
     if (which == DQMC_BIN_SUSCEPTIBILITIES) {  // its layout needs the unequal-time stack
         NEED_UT(h);
         if (!h->n_dirs) return fail(h, DQMC_ERR_STATE, "call dqmc_set_pair_directions first");

@@ -134,14 +134,24 @@ struct dqmc_handle {
     size_t red_cap = 0;
     dqmc_stats red_stats{};
     bool red_valid = false;
-    size_t red_sizes[4] = {0, 0, 0, 0};  // section sizes of the LAST reduction (dqmc_get_reduced checks against these)
+    size_t red_sizes[5] = {0, 0, 0, 0, 0};  // section sizes of the LAST reduction (dqmc_get_reduced checks against these)
+    bool red_td_ok = false;  // the time-displaced and susceptibility sample counts agreed when that reduction was packed
     // logarithmic binners (binner.inl), one per DQMC_BIN_* section: xs, x2 [L][W][E], c [L - 1][W][E], out = finish scratch
     struct Binner {
         bool on = false;
         int E = 0, L = 0;
         int64_t cap = 0, T = 0;  // capacity and pushes so far: count[level] = T >> level for every element
         double *xs = nullptr, *x2 = nullptr, *c = nullptr, *out = nullptr;
-    } bin[5];
+    } bin[6];
+    // time-displaced recording (unequal_time.inl, tdm.hip): every == 0: off, nothing allocated.  E doubles per walker
+    // sample in the layout of include/dqmc_hip.h, acc [E + 1]; src_of [n_dirs][n] only with the fast form
+    struct TimeDisplaced {
+        int every = 0, what = 0, R = 0;
+        bool fast = false;
+        size_t E = 0;
+        double *per_walker = nullptr, *acc = nullptr;
+        int *src_of = nullptr;
+    } td;
     // global moves (global_move.inl): per-walker device state, logabsdet / sign per unit of the current field [0] (valid
     // while gm_cache_version == conf_version) and of a proposal [1]; rate / kind of the hook in the update (0 = off)
     GlobalMoveState *gm = nullptr;
@@ -459,6 +469,7 @@ static void read_kernel_switches(dqmc_handle *h)
     k.no_kron = getenv("DQMC_NO_KRON") != nullptr;
     k.no_wrap_flush = getenv("DQMC_NO_WRAP_FLUSH") != nullptr;
     k.wrap_two_launch = getenv("DQMC_WRAP_TWO_LAUNCH") != nullptr;
+    k.tdm_general = getenv("DQMC_TDM_GENERAL") != nullptr;
 }
 
 static int alloc_qr_workspace(dqmc_handle *h)
@@ -1705,6 +1716,7 @@ int dqmc_accumulate_greens(dqmc_handle *h)
     return DQMC_OK;
 }
 static int cc_setup(dqmc_handle *h);
+static int td_setup(dqmc_handle *h, int every, int what);
 // EachSitePairByDistance(lattice) (lattice_iterators.jl:157-190) as a direction table
 int dqmc_set_pair_directions(dqmc_handle *h, const int32_t *dir_of, int32_t n_dirs)
 {
@@ -1743,6 +1755,7 @@ int dqmc_set_pair_directions(dqmc_handle *h, const int32_t *dir_of, int32_t n_di
     HIPCHK(hipMemcpy(h->pair_trg, trg.data(), sizeof(int) * n * n, hipMemcpyHostToDevice));
     HIPCHK(hipStreamSynchronize(h->stream));
     if (h->K_cc) CHK(cc_setup(h));  // the current-current tables follow the directions
+    if (h->td.every) CHK(td_setup(h, h->td.every, h->td.what));  // and so do the time-displaced rows
     return DQMC_OK;
 }
 int dqmc_accumulate_correlations(dqmc_handle *h)
@@ -1851,6 +1864,7 @@ int dqmc_reset_accumulators(dqmc_handle *h)
     if (h->corr_acc) HIPCHK(hipMemsetAsync(h->corr_acc, 0, h->corr_n * sizeof(double), h->stream));
     if (h->pc_acc) HIPCHK(hipMemsetAsync(h->pc_acc, 0, h->pc_n * sizeof(double), h->stream));
     CHK(ut_reset_accumulators(h));
+    if (h->td.every) HIPCHK(hipMemsetAsync(h->td.acc, 0, (h->td.E + 1) * sizeof(double), h->stream));
     CHK(binner_reset(h));
     return DQMC_OK;
 }
@@ -1884,7 +1898,7 @@ int dqmc_export_accumulators(dqmc_handle *h, void *device_out)
 static const size_t RED_STAT_SUMS = 6;
 static size_t red_nsum(dqmc_handle *h)
 {
-    return h->acc_n + h->corr_n + h->pc_n + (h->ut ? h->ut->sus_n : 0) + RED_STAT_SUMS;
+    return h->acc_n + h->corr_n + h->pc_n + (h->ut ? h->ut->sus_n : 0) + (h->td.every ? h->td.E : 0) + RED_STAT_SUMS;
 }
 static int red_pack(dqmc_handle *h)
 {
@@ -1903,7 +1917,20 @@ static int red_pack(dqmc_handle *h)
     CHK(put(h->corr_acc, h->corr_n));
     CHK(put(h->pc_acc, h->pc_n));
     if (h->ut) CHK(put(h->ut->sus_acc, h->ut->sus_n));
+    // the time-displaced sums without their sample count: the passes that feed them feed the susceptibilities, whose
+    // count stands for both (dqmc_get_reduced hands it out with the section) - if the two local counts agree
+    h->red_td_ok = false;
+    if (h->td.every) {
+        CHK(put(h->td.acc, h->td.E));
+        double c_td = 0.0, c_sus = 0.0;
+        HIPCHK(hipStreamSynchronize(h->stream));
+        HIPCHK(hipMemcpy(&c_td, h->td.acc + h->td.E, sizeof(double), hipMemcpyDeviceToHost));
+        if (h->ut && h->ut->sus_n)
+            HIPCHK(hipMemcpy(&c_sus, h->ut->sus_acc + h->ut->sus_n - 1, sizeof(double), hipMemcpyDeviceToHost));
+        h->red_td_ok = c_td == c_sus;
+    }
     h->red_sizes[0] = h->acc_n; h->red_sizes[1] = h->corr_n; h->red_sizes[2] = h->pc_n; h->red_sizes[3] = h->ut ? h->ut->sus_n : 0;
+    h->red_sizes[4] = h->td.every ? h->td.E : 0;
     // counters of the local walkers, reduced on the host in walker order
     std::vector<DevStats> st(h->W);
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -2017,22 +2044,31 @@ int dqmc_reduce_import(dqmc_handle *h, const double *host_in)
     return DQMC_OK;
 }
 // section `which` of the last reduction: 0 Green's-function sums (dqmc_accumulator_size doubles), 1 correlations,
-// 2 pairing, 3 susceptibilities (sizes as the local getters report)
+// 2 pairing, 3 susceptibilities (sizes as the local getters report), 4 the time-displaced rows: the E packed sums, then
+// the reduced sample count of the susceptibilities (dqmc_time_displaced_size doubles)
 int dqmc_get_reduced(dqmc_handle *h, int32_t which, double *host_out)
 {
     ENTER(h);
-    if (!host_out || which < 0 || which > 3) return fail(h, DQMC_ERR_INVALID, "dqmc_get_reduced: bad arguments");
+    if (!host_out || which < 0 || which > DQMC_RED_TIME_DISPLACED) return fail(h, DQMC_ERR_INVALID, "dqmc_get_reduced: bad arguments");
     if (!h->red_valid) return fail(h, DQMC_ERR_STATE, "call dqmc_reduce first");
-    const size_t sizes[4] = {h->acc_n, h->corr_n, h->pc_n, h->ut ? h->ut->sus_n : 0};
+    const size_t sizes[5] = {h->acc_n, h->corr_n, h->pc_n, h->ut ? h->ut->sus_n : 0, h->td.every ? h->td.E : 0};
     size_t off = 0;
     for (int i = 0; i < which; ++i) off += sizes[i];
     if (sizes[which] == 0) return fail(h, DQMC_ERR_STATE, "dqmc_get_reduced: this accumulator is not configured");
-    for (int i = 0; i < 4; ++i)  // (sizes as they are NOW against the sizes that were packed)
+    for (int i = 0; i < 5; ++i)  // (sizes as they are NOW against the sizes that were packed)
         if (sizes[i] != h->red_sizes[i])
             return fail(h, DQMC_ERR_STATE, "accumulators were reconfigured after the last reduction: call dqmc_reduce again");
     if (h->red_cap < red_nsum(h) + 4) return fail(h, DQMC_ERR_STATE, "call dqmc_reduce first");
+    if (which == DQMC_RED_TIME_DISPLACED && !h->red_td_ok)
+        return fail(h, DQMC_ERR_STATE, "time-displaced and susceptibility sample counts differed at the last reduction: "
+                                       "call dqmc_reset_accumulators after dqmc_set_time_displaced");
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipMemcpy(host_out, h->red_buf + off, sizes[which] * sizeof(double), hipMemcpyDeviceToHost));
+    if (which == DQMC_RED_TIME_DISPLACED) {
+        host_out[sizes[4]] = 0.0;
+        if (sizes[3])
+            HIPCHK(hipMemcpy(host_out + sizes[4], h->red_buf + off - 1, sizeof(double), hipMemcpyDeviceToHost));
+    }
     return DQMC_OK;
 }
 int dqmc_get_reduced_stats(dqmc_handle *h, dqmc_stats *out)

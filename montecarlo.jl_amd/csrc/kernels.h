@@ -161,6 +161,7 @@ struct KernelSwitches {
     bool no_kron = false;         // DQMC_NO_KRON: dense slab chains even where the hopping factorises (kron.hip)
     bool no_wrap_flush = false;   // DQMC_NO_WRAP_FLUSH: the last chunk of a sweep as a stand-alone flush, not in the wrap
     bool wrap_two_launch = false; // DQMC_WRAP_TWO_LAUNCH: the factored wrap at n = 256 as two one-step launches
+    bool tdm_general = false;     // DQMC_TDM_GENERAL: the pair-list kernel for the Green's rows of every table (tdm.hip)
 };
 
 constexpr int QR_COOP_SLOT = 528;  // 264 packets of 16 bytes
@@ -409,6 +410,19 @@ hipError_t launch_cc_slice(const CCPlan &p, int n, int nb, int n_walkers, double
                            const double *G0l, const double *Gl0, const double *Gll, long stride_unit,
                            const int *dir_ptr, const int *pair_src, const int *pair_trg, int n_dirs,
                            double *per_walker, long per_stride, long offset, hipStream_t s);
+// time-displaced recording (tdm.hip): row `row` of every walker's sample per_walker[w][per_stride], written, not added.
+// Green's rows: Gl0[b][row][d] at ((0 nb + b) R + row) n_dirs + d and G0l[b][row][d] at ((1 nb + b) R + row) n_dirs + d,
+// each (1/n) sum over the pairs of direction d; fast = one lane per direction over src_of[d + n j] (needs n_dirs == n and
+// a complete table), else the pair lists.  minus_identity: G0l - I in the place of G0l (row 0).
+hipError_t launch_tdm_greens(bool fast, int n, int nb, int n_walkers, int R, int row, int minus_identity,
+                             const double *Gl0, const double *G0l, long stride_unit, const int *src_of,
+                             const int *dir_ptr, const int *pair_src, const int *pair_trg, int n_dirs,
+                             double *per_walker, long per_stride, hipStream_t s);
+// density rows: the per-slice values of sus_pairs_kernel at offset + (q R + row) n_dirs + d, q = CDC, SDCx, SDCy, SDCz
+hipError_t launch_tdm_density(int n, int nb, int model, int n_walkers, int R, int row, int minus_identity,
+                              const double *G00, const double *G0l, const double *Gl0, const double *Gll,
+                              long stride_unit, const int *dir_ptr, const int *pair_src, const int *pair_trg, int n_dirs,
+                              double *per_walker, long per_stride, long offset, hipStream_t s);
 // logarithmic binning (binner.hip).  Where a push reads its W x E samples: PLAIN = scale * src[w][e]; GREENS = the true
 // G of every unit and the occupation 1 - G_ii; CORR = src [w][4 n_dirs] followed by mx, my (zero) and mz from G.
 // State: xs, x2 [L][W][E], c [L - 1][W][E]; lmax = trailing 1-bits of the number of pushes so far (< L).

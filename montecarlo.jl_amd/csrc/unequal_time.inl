@@ -720,6 +720,119 @@ static int ut_sus_layout(dqmc_handle *h)
     CHK(dalloc(h, &u->sus_acc, want));
     return 0;
 }
+// ---- time-displaced recording (include/dqmc_hip.h; kernels in tdm.hip) ---------------------------------------------
+static void td_free(dqmc_handle *h)
+{
+    dqmc_handle::TimeDisplaced &t = h->td;
+    for (void *p : {(void *)t.per_walker, (void *)t.acc, (void *)t.src_of}) {
+        if (!p) continue;
+        auto it = std::find(h->allocs.begin(), h->allocs.end(), p);
+        if (it != h->allocs.end()) h->allocs.erase(it);
+        (void)hipFree(p);
+    }
+    t = dqmc_handle::TimeDisplaced{};
+}
+// (re)builds the layout, the buffers and, where the direction table allows it, src_of; the accumulator starts at zero
+static int td_setup(dqmc_handle *h, int every, int what)
+{
+    const int n = h->n, nd = h->n_dirs, nb = h->nb;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    td_free(h);
+    h->red_valid = false;  // (re)sized: the last reduction is void
+    dqmc_handle::TimeDisplaced &t = h->td;
+    const int R = 1 + h->M / every;
+    const size_t E = ((what & DQMC_TD_GREENS) ? 2 * (size_t)nb : 0) * R * nd + ((what & DQMC_TD_DENSITY) ? 4 : 0) * (size_t)R * nd;
+    CHK(dalloc(h, &t.per_walker, (size_t)h->W * E));
+    CHK(dalloc(h, &t.acc, E + 1));
+    // fast form of the Green's rows: n_dirs == n and a Latin square - every source meets each direction once (the
+    // first two conditions of cc_setup's LDS plan) and so does every target, which is what makes src_of complete
+    bool fast = (what & DQMC_TD_GREENS) && !h->sw.tdm_general && nd == n;
+    if (fast) {
+        std::vector<int> ptr(nd + 1), src((size_t)n * n), dst((size_t)n * n);
+        HIPCHK(hipMemcpy(ptr.data(), h->dir_ptr, sizeof(int) * (nd + 1), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(src.data(), h->pair_src, sizeof(int) * n * n, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(dst.data(), h->pair_trg, sizeof(int) * n * n, hipMemcpyDeviceToHost));
+        std::vector<int> src_of((size_t)nd * n, -1);
+        std::vector<char> seen((size_t)n * nd, 0);
+        for (int d = 0; d < nd && fast; ++d)
+            for (int q = ptr[d]; q < ptr[d + 1]; ++q) {
+                const int i = src[q], j = dst[q];
+                if (seen[(size_t)i * nd + d] || src_of[d + (size_t)nd * j] >= 0) { fast = false; break; }
+                seen[(size_t)i * nd + d] = 1;
+                src_of[d + (size_t)nd * j] = i;
+            }
+        // (n^2 pairs into n^2 slots without a collision: every slot is filled)
+        if (fast) {
+            CHK(dalloc(h, &t.src_of, (size_t)nd * n));
+            HIPCHK(hipMemcpy(t.src_of, src_of.data(), sizeof(int) * nd * n, hipMemcpyHostToDevice));
+        }
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    t.every = every; t.what = what; t.R = R; t.E = E; t.fast = fast;
+    return 0;
+}
+int dqmc_set_time_displaced(dqmc_handle *h, int32_t every, int32_t what)
+{
+    ENTER(h);
+    if (every == 0) {  // off: as a handle that never recorded
+        HIPCHK(hipStreamSynchronize(h->stream));
+        if (h->td.every) h->red_valid = false;
+        td_free(h);
+        return DQMC_OK;
+    }
+    if (!h->n_dirs) return fail(h, DQMC_ERR_STATE, "call dqmc_set_pair_directions first");
+    if (every < 1 || h->M % every != 0) return fail(h, DQMC_ERR_INVALID, "every must be 0 or a positive divisor of slices");
+    if (what < 1 || what > (DQMC_TD_GREENS | DQMC_TD_DENSITY))
+        return fail(h, DQMC_ERR_INVALID, "what must be a non-empty mask of DQMC_TD_GREENS | DQMC_TD_DENSITY");
+    return td_setup(h, every, what);
+}
+int dqmc_time_displaced_size(dqmc_handle *h, size_t *n_doubles)
+{
+    if (!h || !n_doubles) return DQMC_ERR_INVALID;
+    *n_doubles = h->td.every ? h->td.E + 1 : 0;
+    return DQMC_OK;
+}
+int dqmc_get_time_displaced(dqmc_handle *h, double *host_out)
+{
+    ENTER(h);
+    if (!host_out) return fail(h, DQMC_ERR_INVALID, "host_out is NULL");
+    if (!h->td.every) return fail(h, DQMC_ERR_STATE, "call dqmc_set_time_displaced first");
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(host_out, h->td.acc, (h->td.E + 1) * sizeof(double), hipMemcpyDeviceToHost));
+    return DQMC_OK;
+}
+int dqmc_export_time_displaced(dqmc_handle *h, void *device_out)
+{
+    ENTER(h);
+    if (!device_out) return fail(h, DQMC_ERR_INVALID, "device_out is NULL");
+    if (!h->td.every) return fail(h, DQMC_ERR_STATE, "call dqmc_set_time_displaced first");
+    HIPCHK(hipMemcpyAsync(device_out, h->td.acc, (h->td.E + 1) * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return DQMC_OK;
+}
+int dqmc_time_displaced_plan(dqmc_handle *h, int32_t out[4])
+{
+    if (!h || !out) return DQMC_ERR_INVALID;
+    const dqmc_handle::TimeDisplaced &t = h->td;
+    out[0] = t.R; out[1] = t.every; out[2] = t.what; out[3] = t.every && t.fast ? 1 : 0;
+    return DQMC_OK;
+}
+// row `row` of every walker's sample from one packed tuple (Timed by the caller)
+static int td_record(dqmc_handle *h, int row, int minus_identity, const double *g00, const double *g0l,
+                     const double *gl0, const double *gll)
+{
+    const dqmc_handle::TimeDisplaced &t = h->td;
+    const long off_density = (t.what & DQMC_TD_GREENS) ? 2L * h->nb * t.R * h->n_dirs : 0;
+    if (t.what & DQMC_TD_GREENS)
+        HIPCHK(launch_tdm_greens(t.fast, h->n, h->nb, h->W, t.R, row, minus_identity, gl0, g0l, h->nn, t.src_of,
+                                 h->dir_ptr, h->pair_src, h->pair_trg, h->n_dirs, t.per_walker, (long)t.E, h->stream));
+    if (t.what & DQMC_TD_DENSITY)
+        HIPCHK(launch_tdm_density(h->n, h->nb, h->p.model_kind, h->W, t.R, row, minus_identity, g00, g0l, gl0, gll,
+                                  h->nn, h->dir_ptr, h->pair_src, h->pair_trg, h->n_dirs, t.per_walker, (long)t.E,
+                                  off_density, h->stream));
+    return 0;
+}
+
 int dqmc_accumulate_susceptibilities(dqmc_handle *h, int32_t recalculate)
 {
     ENTER(h); NEED_UT(h);
@@ -728,6 +841,8 @@ int dqmc_accumulate_susceptibilities(dqmc_handle *h, int32_t recalculate)
     UTStack *u = h->ut;
     CHK(ut_sus_layout(h));
     CHK(binner_room(h, DQMC_BIN_SUSCEPTIBILITIES));
+    const bool record = h->td.every != 0;
+    if (record) CHK(binner_room(h, DQMC_BIN_TIME_DISPLACED));
     const long total = (long)u->sus_n - 1;
     CHK(true_greens(h, h->greens));                                 // G00 = greens!(mc)
     CHK(copy_mat(h, u->g00, h->tmp2));
@@ -739,12 +854,18 @@ int dqmc_accumulate_susceptibilities(dqmc_handle *h, int32_t recalculate)
         HIPCHK(launch_cc_b(h->n, h->nb, h->W, h->K_cc, cc_fac, u->g00, h->nn, h->cc.trg, h->cc.tst, h->cc.tts,
                            h->cc.bsum, h->stream));
     }
+    if (record) {  // row 0: (G00, G00 - I, G00, G00), no iterator step
+        Timed t(h, DQMC_K_MISC);
+        CHK(td_record(h, 0, 1, u->g00, u->g00, u->g00, u->g00));
+    }
     CHK(ut_cgi_begin(h, recalculate));
     for (;;) {
         int l = -1;
         CHK(ut_cgi_next(h, &l));
         if (l < 0) break;
         Timed t(h, DQMC_K_MISC);
+        if (record && l % h->td.every == 0)  // a launch of its own: sus_pairs_kernel and its sums stay as they are
+            CHK(td_record(h, l / h->td.every, 0, u->g00, u->out[0], u->out[1], u->out[2]));
         HIPCHK(launch_sus_slice(h->n, h->nb, h->p.model_kind, h->W, u->g00, u->out[0], u->out[1], u->out[2], h->nn,
                                 h->dir_ptr, h->pair_src, h->pair_trg, h->n_dirs, h->K_loc, h->trg_of, u->sus_per_walker,
                                 total, h->stream));
@@ -757,7 +878,12 @@ int dqmc_accumulate_susceptibilities(dqmc_handle *h, int32_t recalculate)
         Timed t(h, DQMC_K_MISC);
         HIPCHK(launch_sus_reduce(h->W, total, h->p.delta_tau, u->sus_per_walker, u->sus_acc, h->stream));
     }
+    if (record) {  // the accumulator takes the samples, walkers in order
+        Timed t(h, DQMC_K_MISC);
+        HIPCHK(launch_sus_reduce(h->W, (long)h->td.E, 1.0, h->td.per_walker, h->td.acc, h->stream));
+    }
     if (h->bin[DQMC_BIN_SUSCEPTIBILITIES].on) CHK(binner_push_section(h, DQMC_BIN_SUSCEPTIBILITIES));
+    if (record && h->bin[DQMC_BIN_TIME_DISPLACED].on) CHK(binner_push_section(h, DQMC_BIN_TIME_DISPLACED));
     return dqmc_synchronize(h);
 }
 int dqmc_susceptibilities_size(dqmc_handle *h, size_t *n)

@@ -418,13 +418,16 @@ class DQMC:
         at current_slice == 1 && direction == +1 (DQMC.jl:425-436).  `measurements` may contain
         "greens" (greens_measurement, occupation), "correlations" (charge/spin density correlations,
         magnetization; needs set_pair_directions), "pairing" (needs set_local_targets) and
-        "susceptibilities" (the CombinedGreensIterator measurements).  `binning=True` enables the device-side
+        "susceptibilities" (the CombinedGreensIterator measurements) and "time_displaced" (the tau-resolved rows; needs
+        set_time_displaced; shares the one iterator pass with "susceptibilities").  `binning=True` enables the device-side
         LogBinner of every selected measurement before the first sweep (enable_binning; read with binned())."""
         known = {"greens": lib().dqmc_accumulate_greens, "correlations": lib().dqmc_accumulate_correlations,
                  "pairing": lib().dqmc_accumulate_pairing}
         for m in measurements:
-            if m not in known and m != "susceptibilities":
+            if m not in known and m not in ("susceptibilities", "time_displaced"):
                 raise ValueError("unknown measurement %r" % (m,))
+        if "time_displaced" in measurements and not self.time_displaced_plan()["every"]:
+            raise _lib.DQMCError(_lib.ERR_STATE, "call set_time_displaced before run(measurements=(..., 'time_displaced'))")
         self.prepare()
         if binning:  # a resumed run! keeps the binners it has (DQMC.jl:395-411)
             self.enable_binning([m for m in measurements if not self._binning_enabled(m)])
@@ -439,11 +442,13 @@ class DQMC:
                 if cs == 1 and d == 1 and i > self.p.thermalization and recorder is not None:
                     recorder.push(self, i)  # push!(mc.configs, mc, mc.model, i) (DQMC.jl:430)
                 if cs == 1 and d == 1 and i > self.p.thermalization and i % self.p.measure_rate == 0:
+                    ut_pass = False  # one CombinedGreensIterator pass serves both of its measurements
                     for m in measurements:
-                        if m == "susceptibilities":
-                            self.accumulate_susceptibilities()
-                        else:
+                        if m in known:
                             self._c(known[m](self._h))
+                        elif not ut_pass:
+                            self.accumulate_susceptibilities()
+                            ut_pass = True
                     if on_measure is not None:
                         on_measure(self, i)
             self.last_sweep = i
@@ -541,11 +546,12 @@ class DQMC:
 
     def reduced(self, which="greens"):
         """dqmc_get_reduced: the global sums of the last reduction (the handle's own accumulators keep the local sums);
-        `which` = greens | correlations | pairing | susceptibilities, layouts as the local getters"""
-        idx = {"greens": 0, "correlations": 1, "pairing": 2, "susceptibilities": 3}[which]
+        `which` = greens | correlations | pairing | susceptibilities | time_displaced, layouts as the local getters"""
+        idx = {"greens": 0, "correlations": 1, "pairing": 2, "susceptibilities": 3,
+               "time_displaced": _lib.RED_TIME_DISPLACED}[which]
         n = C.c_size_t()
         size_fn = (lib().dqmc_accumulator_size, lib().dqmc_correlations_size, lib().dqmc_pairing_size,
-                   lib().dqmc_susceptibilities_size)[idx]
+                   lib().dqmc_susceptibilities_size, lib().dqmc_time_displaced_size)[idx]
         self._c(size_fn(self._h, C.byref(n)))
         out = np.zeros(n.value)
         self._c(lib().dqmc_get_reduced(self._h, idx, dptr(out)))
@@ -611,6 +617,8 @@ class DQMC:
     # ---- error bars: per-walker logarithmic binning on the device (include/dqmc_hip.h "error bars")
     @staticmethod
     def _bin(which):
+        if which == "time_displaced":  # DQMC_BIN_TIME_DISPLACED, an enum of its own
+            return _lib.BIN_TIME_DISPLACED
         if which not in _lib.BIN_SECTIONS:
             raise ValueError("unknown binner section %r" % (which,))
         return _lib.BIN_SECTIONS.index(which)
@@ -698,6 +706,13 @@ class DQMC:
                 sizes.append(("PS", nd * K * K, (nd, K, K)))
             if Kcc:
                 sizes.append(("CCS", nd * Kcc, (nd, Kcc)))
+        elif which == "time_displaced":  # [b][r][d] / [r][d], d fastest: C order
+            p = self.time_displaced_plan()
+            sizes = []
+            if p["what"] & _lib.TD_GREENS:
+                sizes += [(k, B * p["rows"] * nd, (B, p["rows"], nd)) for k in ("Gl0", "G0l")]
+            if p["what"] & _lib.TD_DENSITY:
+                sizes += [(k, p["rows"] * nd, (p["rows"], nd)) for k in ("CDC", "SDCx", "SDCy", "SDCz")]
         else:
             sizes = [("x", self.binner_size("user")[0], None)]
         out, off = [], 0
@@ -715,6 +730,8 @@ class DQMC:
                 v = self._blocks(v)
             elif name == "occupation":
                 v = [v[b * n:(b + 1) * n] for b in range(B)]
+            elif which == "time_displaced":
+                v = v.reshape(shape)
             elif shape is not None:
                 v = v.reshape(shape, order="F")
             res[name] = v
@@ -736,6 +753,8 @@ class DQMC:
         error, independent of the binning) and X_tau; plus count (samples per walker) and reliable_level."""
         raw = self.binned_raw(which, level)
         res = self._bin_dict(which, raw)
+        if which == "time_displaced":
+            res["tau"] = self._td_tau()
         res["count"] = raw["count"]
         res["reliable_level"] = raw["reliable_level"]
         return res
@@ -890,6 +909,54 @@ class DQMC:
         if Kcc:
             off = 4 * nd + nd * K * K
             res["CCS"] = out[off:off + nd * Kcc].reshape((nd, Kcc), order="F") / cnt
+        res["count"] = cnt
+        return res
+
+    # ---- time-displaced recording (include/dqmc_hip.h): G(r, tau) and the tau-resolved charge / spin correlations
+    def set_time_displaced(self, every=1, what=("greens", "density")):
+        """from now on every accumulate_susceptibilities pass also records rows at l = 0, every, ..., slices (every = 0:
+        off).  `what`: "greens" (Gl0, G0l summed per direction) and / or "density" (CDC, SDCx, SDCy, SDCz), or the
+        DQMC_TD_* mask itself.  Needs set_pair_directions; starts the recorded sums at zero."""
+        if isinstance(what, str):
+            what = (what,)
+        if not isinstance(what, int):
+            bits = {"greens": _lib.TD_GREENS, "density": _lib.TD_DENSITY}
+            for k in what:
+                if k not in bits:
+                    raise ValueError("unknown time-displaced part %r" % (k,))
+            what = sum(bits[k] for k in set(what))
+        self._c(lib().dqmc_set_time_displaced(self._h, int(every), int(what)))
+
+    def time_displaced_plan(self):
+        """-> dict(rows, every, what, fast): fast = the Green's rows take the one-lane-per-direction kernel (all zero
+        when recording is off)"""
+        out = (C.c_int32 * 4)()
+        self._c(lib().dqmc_time_displaced_plan(self._h, out))
+        return dict(zip(("rows", "every", "what", "fast"), (int(v) for v in out)))
+
+    def time_displaced_size(self):
+        n = C.c_size_t()
+        self._c(lib().dqmc_time_displaced_size(self._h, C.byref(n)))
+        return n.value
+
+    def time_displaced_raw(self):
+        """the accumulator as the device holds it: the sums in the layout of include/dqmc_hip.h, then the sample count"""
+        out = np.zeros(self.time_displaced_size())
+        self._c(lib().dqmc_get_time_displaced(self._h, dptr(out)))
+        return out
+
+    def _td_tau(self):
+        p = self.time_displaced_plan()
+        return np.arange(p["rows"]) * p["every"] * self.p.delta_tau
+
+    def time_displaced(self):
+        """-> dict of means over the samples: tau [R]; Gl0, G0l [n_blocks, R, n_dirs]; CDC, SDCx, SDCy, SDCz [R, n_dirs]
+        (whichever are recorded); count"""
+        raw = self.time_displaced_raw()
+        cnt = raw[-1]
+        res = {"tau": self._td_tau()}
+        for name, v in self._bin_shape("time_displaced", raw[:-1]).items():
+            res[name] = v / cnt
         res["count"] = cnt
         return res
 
