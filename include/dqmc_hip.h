@@ -668,6 +668,62 @@ typedef struct {
 /* level < 0: the reliable level */
 int dqmc_mc_binner_finish(dqmc_mc_handle *h, int32_t walker, int32_t level, dqmc_mc_binned *out);
 
+/* ---- finite-size-scaling observables of the MC flavor: M^4 and the structure factor S(k) ------------------------
+ * The reference measures E and M only (models/Ising/measurements.jl); this is a defined extension, like the cluster
+ * move and replica exchange.  The Binder cumulant U4 = 1 - <M^4>/(3 <M^2>^2) and the second-moment correlation length
+ * xi = sqrt(S(0)/S(k) - 1)/(2 sin(|k|/2)), S(0) = <M^2>/N, need two functions of the configuration at the moment of
+ * measurement, which is never kept:
+ *   phase tables  the host passes n_k wave vectors (0 <= n_k <= 8) as fixed-point tables int32 [n_k][N], site order as
+ *                 dqmc_mc_get_conf: cos_q30[k][i] = llround(cos(k . r_i) 2^30) and sin_q30[k][i] likewise.  n_k = 0
+ *                 measures M^4 only.
+ *   per measurement and walker
+ *                 Fc_k = sum_i s_i cos_q30[k][i], Fs_k = sum_i s_i sin_q30[k][i] in 64-bit integers (|F| <= 2^14 2^30 =
+ *                 2^44: exact, whatever the order of the additions; a numpy int64 sum reproduces them),
+ *                 S_k = ((double)Fc (double)Fc + (double)Fs (double)Fs) * inv, inv = 1.0 / ((double)N * 2^60) (the
+ *                 conversions are exact, the rest is three or four fp64 roundings depending on contraction: device and
+ *                 host agree to a few ulp, not to the bit),
+ *                 M4 = m2 * m2 with m2 = (double)(M M) (exact), one rounding: M4 and its running sum are bit-exact.
+ *                 The entries are off by at most 2^-31 relative to the unit phase, which puts the quantisation bias of
+ *                 S_k below 2^-29 relative to N (the largest value S_k takes), far under any statistical error.
+ *   when          exactly where and when E and |M| of that measurement are taken: the same configuration, after that
+ *                 sweep's cluster move and exchange round.  Under replica exchange the values belong to the slot ("at
+ *                 beta_w"), like the other sums.
+ * Per walker: sum_M4, sum_S[8] and an n_meas of their own (FSS may be switched on mid-run).  With the binner enabled a
+ * second section "FSS" of its own arrays, under the same level / compressor scheme as the section above: elements
+ * [M2, M4, S_0 .. S_{n_k - 1}] (M2 = M M), cross sums of the pairs (M2, M4) and (M2, S_k), device layout
+ * [level][element][walker].  The four-element section, its getters and its pushes are as they are without FSS, and
+ * so are the chains, the sums and the draws: with FSS on, dqmc_mc_sweep ends a launch at every measured sweep and
+ * launches one measurement kernel behind it, on the state the sweep's last kernel left in device memory. */
+/* n_k >= 0: FSS on with these tables (copied; either may be NULL when n_k == 0); n_k = -1: off (the default).  Resets
+ * the FSS sums; if the binner is enabled it starts anew with every section empty and its capacity kept.
+ * DQMC_ERR_INVALID for n_k > 8, n_k < -1, a NULL table with n_k > 0 (these two are checked before the handle), or an
+ * entry above 2^30 in magnitude. */
+int dqmc_mc_set_fss(dqmc_mc_handle *h, int32_t n_k, const int32_t *cos_q30, const int32_t *sin_q30);
+typedef struct {
+    int64_t n_meas;    /* FSS measurements summed since dqmc_mc_set_fss / dqmc_mc_reset_accumulators */
+    int32_t n_k;       /* -1: FSS is off (then everything else is 0) */
+    double sum_M4;
+    double sum_S[8];   /* entries at and above n_k are 0 */
+} dqmc_mc_fss;
+int dqmc_mc_get_fss(dqmc_mc_handle *h, int32_t walker, dqmc_mc_fss *out);
+/* the sums of one level of one walker of the FSS section: x_sum and x2_sum hold 2 + n_k elements [M2, M4, S_0 ..],
+ * xy_sum 1 + n_k pairs [(M2, M4), (M2, S_0) ..]; any output may be NULL.  DQMC_ERR_STATE without binner or FSS. */
+int dqmc_mc_fss_binner_get_level(dqmc_mc_handle *h, int32_t walker, int32_t level, double *x_sum, double *x2_sum,
+                                 double *xy_sum, int64_t *count);
+/* as dqmc_mc_binned, for the FSS section: entries at and above 2 + n_k (covN: 1 + n_k) are 0 */
+typedef struct {
+    double mean[10];   /* [M2, M4, S_0 ..] */
+    double varN[10];   /* at `level` */
+    double varN0[10];  /* at level 0 */
+    double tau[10];
+    double covN[9];    /* at `level`, pairs (M2, M4), (M2, S_0) .. */
+    int64_t count;
+    int32_t level;
+    int32_t n_k;
+} dqmc_mc_fss_binned;
+/* level < 0: the reliable level (the last one with count >= 32, else 0) */
+int dqmc_mc_fss_binner_finish(dqmc_mc_handle *h, int32_t walker, int32_t level, dqmc_mc_fss_binned *out);
+
 /* ---- instrumentation ------------------------------------------------------ */
 /* Per-kernel-family device time accumulated with HIP events on the handle's
  * stream when enabled (off by default; used by bench.py's roofline leg). */

@@ -78,6 +78,16 @@ class McBinned(C.Structure):
                 ("covN", C.c_double * 2), ("count", C.c_int64), ("level", C.c_int32)]
 
 
+class McFss(C.Structure):
+    _fields_ = [("n_meas", C.c_int64), ("n_k", C.c_int32), ("sum_M4", C.c_double), ("sum_S", C.c_double * 8)]
+
+
+class McFssBinned(C.Structure):
+    _fields_ = [("mean", C.c_double * 10), ("varN", C.c_double * 10), ("varN0", C.c_double * 10),
+                ("tau", C.c_double * 10), ("covN", C.c_double * 9), ("count", C.c_int64), ("level", C.c_int32),
+                ("n_k", C.c_int32)]
+
+
 _dp = C.POINTER(C.c_double)
 _i64p = C.POINTER(C.c_int64)
 _H = C.c_void_p
@@ -208,6 +218,10 @@ SIGNATURES = {
     "dqmc_mc_binner_reliable_level": (C.c_int, [_H, C.POINTER(C.c_int32)]),
     "dqmc_mc_binner_get_level": (C.c_int, [_H, C.c_int32, C.c_int32, _dp, _dp, _dp, _i64p]),
     "dqmc_mc_binner_finish": (C.c_int, [_H, C.c_int32, C.c_int32, C.POINTER(McBinned)]),
+    "dqmc_mc_set_fss": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "dqmc_mc_get_fss": (C.c_int, [_H, C.c_int32, C.POINTER(McFss)]),
+    "dqmc_mc_fss_binner_get_level": (C.c_int, [_H, C.c_int32, C.c_int32, _dp, _dp, _dp, _i64p]),
+    "dqmc_mc_fss_binner_finish": (C.c_int, [_H, C.c_int32, C.c_int32, C.POINTER(McFssBinned)]),
     "dqmc_timing_enable": (C.c_int, [_H, C.c_int32]),
     "dqmc_timing_get": (C.c_int, [_H, _dp, _i64p]),
     "dqmc_mfma_f64_peak": (C.c_int, [C.c_int32, C.c_int32, _dp]),

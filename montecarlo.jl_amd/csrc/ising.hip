@@ -42,9 +42,20 @@
 // u = philox4_uniform(key_a, low32(x), high32(x), 2, 0): a third domain, c2 = 2.  No exp on the device, and products
 // of doubles are exactly rounded, so a host restatement reproduces every decision bit for bit.  In a sweep the order
 // is local sweep, cluster move, exchange round, measurement.
+//
+// Finite-size-scaling observables (the reference measures E and M only; a defined extension, include/dqmc_hip.h): with
+// FSS on every measurement also takes M4 = m2 m2, m2 = (double)(M M), and for each of the n_k <= 8 wave vectors the host
+// passed as fixed-point tables cos_q30[k][i] = llround(cos(k . r_i) 2^30), sin_q30 likewise (int32 [n_k][N]):
+//   Fc_k = sum_i s_i cos_q30[k][i], Fs_k = sum_i s_i sin_q30[k][i]   in 64-bit integers, |F| <= 2^44: exact, order-free
+//   S_k  = ((double)Fc (double)Fc + (double)Fs (double)Fs) * (1 / (N 2^60))
+// on the configuration E and |M| of that measurement are taken on (after the sweep's cluster move and exchange round; the
+// values belong to the slot).  Per walker sum_M4, sum_S[8] and an n_meas of their own; with the binner on a second section
+// over [M2, M4, S_0 ..] with the cross sums (M2, M4) and (M2, S_k).  A stand-alone kernel (ising_fss.inl) that
+// dqmc_mc_sweep launches behind every measured sweep: the kernels above it in this file are the same with FSS on or off.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -421,6 +432,9 @@ __global__ __launch_bounds__(WAVE) void ising_exchange_kernel(DevState s, Exchan
     if (measure) ising_measure_slot(s, w, E, M);
 }
 
+// the finite-size-scaling measurement: FssArg, ising_fss_bin_push, ising_fss_kernel
+#include "ising_fss.inl"
+
 }  // namespace dqmc_mc
 
 using namespace dqmc_mc;
@@ -449,6 +463,16 @@ struct dqmc_mc_handle {
         int64_t cap = 0, T = 0;
         double *xs = nullptr, *x2 = nullptr, *xy = nullptr, *c = nullptr;  // [L][4][W], [L][4][W], [L][2][W], [L - 1][4][W]
     } bin;
+    struct Fss {  // dqmc_mc_set_fss; n_k = -1: off
+        int n_k = -1;
+        int *cq = nullptr, *sq = nullptr;         // [n_k][32 nw]: rows padded with zeros to whole spin words
+        double *sM4 = nullptr, *sS = nullptr;     // [W], [8][W] (allocated when FSS is first switched on)
+        long long *n_meas = nullptr;              // [W]
+        // the FSS section of the binner (there iff bin.on && n_k >= 0; L and cap are bin's): [L][2 + n_k][W] twice,
+        // [L][1 + n_k][W], [L - 1][1 + n_k][2][W]; T = its pushes
+        double *xs = nullptr, *x2 = nullptr, *xy = nullptr, *c = nullptr;
+        int64_t T = 0;
+    } fss;
 };
 
 static thread_local std::string g_mc_create_error;
@@ -617,6 +641,121 @@ static int mc_bin_reliable(const dqmc_mc_handle::Binner &b)  // the last level w
     for (int l = 0; l < b.L; ++l)
         if ((b.T >> l) >= 32) lv = l;
     return lv;
+}
+
+// ---- finite-size-scaling observables
+constexpr int MAX_K = 8;
+
+static void mc_release(dqmc_mc_handle *h, void *p)  // hipFree of one of the handle's allocations
+{
+    if (!p) return;
+    for (size_t i = 0; i < h->allocs.size(); ++i)
+        if (h->allocs[i] == p) {
+            h->allocs.erase(h->allocs.begin() + i);
+            break;
+        }
+    (void)hipFree(p);
+}
+
+static void mc_fss_bin_free(dqmc_mc_handle *h)
+{
+    dqmc_mc_handle::Fss &f = h->fss;
+    for (double **p : {&f.xs, &f.x2, &f.xy, &f.c}) {
+        mc_release(h, *p);
+        *p = nullptr;
+    }
+    f.T = 0;
+}
+
+// the FSS section for the binner as it stands (nothing unless both are on)
+static int mc_fss_bin_alloc(dqmc_mc_handle *h)
+{
+    dqmc_mc_handle::Fss &f = h->fss;
+    mc_fss_bin_free(h);
+    if (!h->bin.on || f.n_k < 0) return 0;
+    const size_t W = h->W, L = h->bin.L, ne = 2 + f.n_k, np = 1 + f.n_k;
+    int rc = 0;
+    if ((rc = mc_alloc(h, &f.xs, L * ne * W)) || (rc = mc_alloc(h, &f.x2, L * ne * W)) ||
+        (rc = mc_alloc(h, &f.xy, L * np * W)) || (rc = mc_alloc(h, &f.c, (L - 1) * np * 2 * W))) {
+        const std::string msg = h->err;
+        mc_fss_bin_free(h);
+        h->err = msg;
+    }
+    return rc;
+}
+
+static int mc_fss_clear(dqmc_mc_handle *h)  // the sums and the section's state
+{
+    dqmc_mc_handle::Fss &f = h->fss;
+    const size_t W = h->W;
+    if (f.sM4) {
+        MCHK(hipMemsetAsync(f.sM4, 0, W * 8, h->stream));
+        MCHK(hipMemsetAsync(f.sS, 0, (size_t)MAX_K * W * 8, h->stream));
+        MCHK(hipMemsetAsync(f.n_meas, 0, W * 8, h->stream));
+    }
+    if (f.xs) {
+        const size_t L = h->bin.L, ne = 2 + f.n_k, np = 1 + f.n_k;
+        MCHK(hipMemsetAsync(f.xs, 0, L * ne * W * 8, h->stream));
+        MCHK(hipMemsetAsync(f.x2, 0, L * ne * W * 8, h->stream));
+        MCHK(hipMemsetAsync(f.xy, 0, L * np * W * 8, h->stream));
+        if (L > 1) MCHK(hipMemsetAsync(f.c, 0, (L - 1) * np * 2 * W * 8, h->stream));
+    }
+    f.T = 0;
+    return 0;
+}
+
+// the FSS measurement of the sweep whose last kernel has just been launched (and its push).  The 1 + n_k pairs run side
+// by side, N table visits each; where they would pass the launch budget together the pairs are spread over launches.
+static int mc_launch_fss(dqmc_mc_handle *h)
+{
+    dqmc_mc_handle::Fss &f = h->fss;
+    FssArg a{};
+    a.n_k = f.n_k;
+    a.inv = 1.0 / ((double)h->N * 1152921504606846976.0);  // N 2^60 is exact, one rounding
+    a.sM4 = f.sM4;
+    a.sS = f.sS;
+    a.n_meas = f.n_meas;
+    if (f.xs) {
+        int lmax = 0;
+        while ((f.T >> lmax) & 1) ++lmax;
+        if (lmax >= h->bin.L) return mc_fail(h, DQMC_ERR_STATE, "dqmc_mc_sweep: binner capacity exhausted");
+        a.bxs = f.xs;
+        a.bx2 = f.x2;
+        a.bxy = f.xy;
+        a.bc = f.c;
+        a.lmax = lmax;
+        a.top = h->bin.L - 1;
+    }
+    const int pairs = 1 + f.n_k;
+    const double per_pair = (double)h->N * std::max((double)h->W, BUDGET_WALKERS);
+    const int chunk = (int)std::max(1.0, std::min((double)pairs, std::floor(LAUNCH_BUDGET / per_pair)));
+    for (int y0 = 0; y0 < pairs; y0 += chunk) {
+        hipLaunchKernelGGL(ising_fss_kernel, dim3((h->W + WAVE - 1) / WAVE, std::min(chunk, pairs - y0)), dim3(WAVE), 0,
+                           h->stream, h->d, a, (const int4 *)f.cq, (const int4 *)f.sq, y0);
+        MCHK(hipGetLastError());
+    }
+    if (f.xs) f.T += 1;
+    return 0;
+}
+
+#define MC_FSS_BIN_OK(h, fn)                                                                          \
+    MC_BIN_OK(h, fn);                                                                                 \
+    if (!(h)->fss.xs) return mc_fail((h), DQMC_ERR_STATE, std::string(fn) + ": FSS is off (dqmc_mc_set_fss first)")
+
+// x_sum, x2_sum (2 + n_k each) and xy_sum (1 + n_k) of one level of one walker of the FSS section
+static int mc_fss_bin_level(dqmc_mc_handle *h, int walker, int level, double *xs, double *x2, double *xy)
+{
+    const dqmc_mc_handle::Fss &f = h->fss;
+    const size_t W = h->W, pitch = W * sizeof(double), ne = 2 + f.n_k, np = 1 + f.n_k;
+    MCHK(hipSetDevice(h->device));
+    if (xs)
+        MCHK(hipMemcpy2DAsync(xs, 8, f.xs + (size_t)level * ne * W + walker, pitch, 8, ne, hipMemcpyDeviceToHost, h->stream));
+    if (x2)
+        MCHK(hipMemcpy2DAsync(x2, 8, f.x2 + (size_t)level * ne * W + walker, pitch, 8, ne, hipMemcpyDeviceToHost, h->stream));
+    if (xy)
+        MCHK(hipMemcpy2DAsync(xy, 8, f.xy + (size_t)level * np * W + walker, pitch, 8, np, hipMemcpyDeviceToHost, h->stream));
+    MCHK(hipStreamSynchronize(h->stream));
+    return 0;
 }
 
 extern "C" {
@@ -837,6 +976,11 @@ int dqmc_mc_sweep(dqmc_mc_handle *h, int32_t n_sweeps, int64_t first_sweep_index
     if (b.on && b.T + mc_measurements_in(first_sweep_index, first_sweep_index + n_sweeps - 1, thermalization,
                                           measure_rate) > b.cap)  // the reference: OverflowError of push!
         return mc_fail(h, DQMC_ERR_STATE, "dqmc_mc_sweep: the measurements of this call would pass the binner's capacity");
+    dqmc_mc_handle::Fss &fs = h->fss;
+    if (fs.xs && fs.T + mc_measurements_in(first_sweep_index, first_sweep_index + n_sweeps - 1, thermalization,
+                                            measure_rate) > b.cap)
+        return mc_fail(h, DQMC_ERR_STATE,
+                       "dqmc_mc_sweep: the measurements of this call would pass the capacity of the binner's FSS section");
     MCHK(hipSetDevice(h->device));
     const size_t lds = (size_t)h->nw * WAVE * 4;
     const int grid = (h->W + WAVE - 1) / WAVE;
@@ -852,6 +996,11 @@ int dqmc_mc_sweep(dqmc_mc_handle *h, int32_t n_sweeps, int64_t first_sweep_index
         if (r > 0) n = (int)std::min<long long>(n, r - (first - 1) % r);  // a launch ends at the next multiple of r
         // and at the next multiple of k where the round is a launch of its own (fused: only behind a cluster move)
         if (k > 0 && !fused) n = (int)std::min<long long>(n, k - (first - 1) % k);
+        if (fs.n_k >= 0) {  // and at the next measured sweep: its FSS measurement is a launch of its own
+            const long long g0 = std::max<long long>(first, (long long)thermalization + 1);
+            const long long gm = (g0 + measure_rate - 1) / measure_rate * measure_rate;
+            n = (int)std::min<long long>(n, gm - first + 1);
+        }
         const long long last = first + n - 1;
         const bool move = r > 0 && last % r == 0;  // global_move after sweep `last` (MC.jl:233-236)
         const bool round = k > 0 && last % k == 0 && (!fused || move);  // ising_exchange_kernel after sweep `last`
@@ -890,6 +1039,8 @@ int dqmc_mc_sweep(dqmc_mc_handle *h, int32_t n_sweeps, int64_t first_sweep_index
             if (int rc = mc_launch_exchange(h, deferred)) return rc;
         if (deferred && b.on)
             if (int rc = mc_launch_bin_push(h)) return rc;
+        if (fs.n_k >= 0 && last > thermalization && last % measure_rate == 0)
+            if (int rc = mc_launch_fss(h)) return rc;
         done += n;
     }
     MCHK(hipStreamSynchronize(h->stream));
@@ -1092,6 +1243,7 @@ int dqmc_mc_reset_accumulators(dqmc_mc_handle *h)
         if (b.L > 1) MCHK(hipMemsetAsync(b.c, 0, (size_t)(b.L - 1) * 4 * W * 8, h->stream));
         b.T = 0;
     }
+    if (int rc = mc_fss_clear(h)) return rc;
     MCHK(hipStreamSynchronize(h->stream));
     return DQMC_OK;
 }
@@ -1132,6 +1284,13 @@ int dqmc_mc_binner_enable(dqmc_mc_handle *h, int64_t capacity)
     b.L = L;
     b.cap = capacity;
     b.T = 0;
+    if (int rc = mc_fss_bin_alloc(h)) {  // the FSS section, when FSS is on
+        const std::string msg = h->err;
+        mc_bin_free(h);
+        h->err = msg;
+        return rc;
+    }
+    MCHK(hipStreamSynchronize(h->stream));
     return DQMC_OK;
 }
 
@@ -1190,6 +1349,106 @@ int dqmc_mc_binner_finish(dqmc_mc_handle *h, int32_t walker, int32_t level, dqmc
     for (int q = 0; q < 2; ++q) out->covN[q] = mc_bin_covN(xs[2 * q], xs[2 * q + 1], xy[q], nl);
     out->count = b.T >> level;
     out->level = level;
+    return DQMC_OK;
+}
+
+int dqmc_mc_set_fss(dqmc_mc_handle *h, int32_t n_k, const int32_t *cos_q30, const int32_t *sin_q30)
+{
+    if (n_k < -1 || n_k > MAX_K)
+        return mc_fail(h, DQMC_ERR_INVALID, "dqmc_mc_set_fss: n_k must be in 0..8 (-1 = off)");
+    if (n_k > 0 && (!cos_q30 || !sin_q30)) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_mc_set_fss: null phase table");
+    if (!h) return mc_fail(nullptr, DQMC_ERR_INVALID, "dqmc_mc_set_fss: null handle");
+    for (long i = 0; i < (long)std::max(n_k, 0) * h->N; ++i)
+        if (std::abs((long)cos_q30[i]) > (1L << 30) || std::abs((long)sin_q30[i]) > (1L << 30))
+            return mc_fail(h, DQMC_ERR_INVALID, "dqmc_mc_set_fss: table entry above 2^30 in magnitude");
+    MCHK(hipSetDevice(h->device));
+    MCHK(hipStreamSynchronize(h->stream));
+    dqmc_mc_handle::Fss &f = h->fss;
+    mc_fss_bin_free(h);
+    mc_release(h, f.cq);
+    mc_release(h, f.sq);
+    f.cq = f.sq = nullptr;
+    f.n_k = -1;
+    if (n_k >= 0) {
+        const size_t W = h->W, pitch = (size_t)32 * h->nw, n = (size_t)n_k * pitch;
+        int rc = 0;
+        if (!f.sM4 && ((rc = mc_alloc(h, &f.sM4, W)) || (rc = mc_alloc(h, &f.sS, (size_t)MAX_K * W)) ||
+                       (rc = mc_alloc(h, &f.n_meas, W))))
+            return rc;
+        if ((rc = mc_alloc(h, &f.cq, n)) || (rc = mc_alloc(h, &f.sq, n))) return rc;
+        if (n) {  // (mc_alloc zeroed the padding)
+            MCHK(hipMemcpy2DAsync(f.cq, pitch * 4, cos_q30, (size_t)h->N * 4, (size_t)h->N * 4, n_k, hipMemcpyHostToDevice,
+                                  h->stream));
+            MCHK(hipMemcpy2DAsync(f.sq, pitch * 4, sin_q30, (size_t)h->N * 4, (size_t)h->N * 4, n_k, hipMemcpyHostToDevice,
+                                  h->stream));
+        }
+        MCHK(hipStreamSynchronize(h->stream));  // (the tables are the caller's: copied before this returns)
+        f.n_k = n_k;
+    }
+    if (int rc = mc_fss_clear(h)) return rc;
+    MCHK(hipStreamSynchronize(h->stream));
+    if (h->bin.on) return dqmc_mc_binner_enable(h, h->bin.cap);  // every section empty, the capacity kept
+    return DQMC_OK;
+}
+
+int dqmc_mc_get_fss(dqmc_mc_handle *h, int32_t walker, dqmc_mc_fss *out)
+{
+    if (int rc = mc_walker(h, walker, "dqmc_mc_get_fss")) return rc;
+    if (!out) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_mc_get_fss: null out");
+    const dqmc_mc_handle::Fss &f = h->fss;
+    *out = dqmc_mc_fss{};
+    out->n_k = f.n_k;
+    if (f.n_k < 0) return DQMC_OK;
+    MCHK(hipSetDevice(h->device));
+    long long n = 0;
+    int rc = 0;
+    if ((rc = mc_get(h, f.n_meas, 0, walker, &n)) || (rc = mc_get(h, f.sM4, 0, walker, &out->sum_M4))) return rc;
+    for (int k = 0; k < f.n_k; ++k)
+        if ((rc = mc_get(h, f.sS, k, walker, &out->sum_S[k]))) return rc;
+    out->n_meas = n;
+    return DQMC_OK;
+}
+
+int dqmc_mc_fss_binner_get_level(dqmc_mc_handle *h, int32_t walker, int32_t level, double *x_sum, double *x2_sum,
+                                 double *xy_sum, int64_t *count)
+{
+    MC_FSS_BIN_OK(h, "dqmc_mc_fss_binner_get_level");
+    if (int rc = mc_walker(h, walker, "dqmc_mc_fss_binner_get_level")) return rc;
+    if (level < 0 || level >= h->bin.L)
+        return mc_fail(h, DQMC_ERR_INVALID, "dqmc_mc_fss_binner_get_level: level out of range");
+    if (int rc = mc_fss_bin_level(h, walker, level, x_sum, x2_sum, xy_sum)) return rc;
+    if (count) *count = h->fss.T >> level;
+    return DQMC_OK;
+}
+
+int dqmc_mc_fss_binner_finish(dqmc_mc_handle *h, int32_t walker, int32_t level, dqmc_mc_fss_binned *out)
+{
+    MC_FSS_BIN_OK(h, "dqmc_mc_fss_binner_finish");
+    if (int rc = mc_walker(h, walker, "dqmc_mc_fss_binner_finish")) return rc;
+    if (!out) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_mc_fss_binner_finish: null out");
+    const dqmc_mc_handle::Fss &f = h->fss;
+    const int L = h->bin.L, ne = 2 + f.n_k;
+    if (level >= L) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_mc_fss_binner_finish: level out of range");
+    if (level < 0) {  // the existing rule: the last level with count >= 32, else 0
+        level = 0;
+        for (int l = 0; l < L; ++l)
+            if ((f.T >> l) >= 32) level = l;
+    }
+    double xs0[2 + MAX_K], x20[2 + MAX_K], xs[2 + MAX_K], x2[2 + MAX_K], xy[1 + MAX_K];
+    if (int rc = mc_fss_bin_level(h, walker, 0, xs0, x20, nullptr)) return rc;
+    if (int rc = mc_fss_bin_level(h, walker, level, xs, x2, xy)) return rc;
+    *out = dqmc_mc_fss_binned{};
+    const double n0 = (double)f.T, nl = (double)(f.T >> level);
+    for (int k = 0; k < ne; ++k) {
+        out->mean[k] = xs0[k] / n0;
+        out->varN[k] = mc_bin_covN(xs[k], xs[k], x2[k], nl);
+        out->varN0[k] = mc_bin_covN(xs0[k], xs0[k], x20[k], n0);
+        out->tau[k] = 0.5 * (out->varN[k] / out->varN0[k] - 1.0);
+    }
+    for (int q = 0; q + 1 < ne; ++q) out->covN[q] = mc_bin_covN(xs[0], xs[1 + q], xy[q], nl);
+    out->count = f.T >> level;
+    out->level = level;
+    out->n_k = f.n_k;
     return DQMC_OK;
 }
 

@@ -12,9 +12,10 @@ import time
 
 import numpy as np
 
-from ._lib import DQMCError, ERR_INVALID, McBinned, McExchangeStats, McGlobalStats, McParams, McStats, lib
+from ._lib import (DQMCError, ERR_INVALID, ERR_STATE, McBinned, McExchangeStats, McFss, McFssBinned, McGlobalStats,
+                   McParams, McStats, lib)
 from .configurations import CompressedConf
-from .lattices import Chain, CubicLattice, SquareLattice
+from .lattices import Chain, CubicLattice, SquareLattice, _lattice_vectors, _positions
 
 IsingTc = 1.0 / (0.5 * math.log(1.0 + math.sqrt(2.0)))  # IsingModel.jl:7
 
@@ -56,6 +57,49 @@ class IsingModel:
         return 2.0 * float(c[i - 1]) * float(np.sum(c[np.asarray(self.l.neighs)[:, i - 1] - 1]))
 
 
+def reciprocal_vectors(l):
+    """the smallest wave vectors of the lattice, one per lattice dimension: the columns b_j of B with A^T B = 2 pi I,
+    A's columns the lattice vectors (a_i . b_j = 2 pi delta_ij), returned as rows"""
+    A = np.array(_lattice_vectors(l), dtype=float).T
+    return (2.0 * np.pi * np.linalg.inv(A.T)).T.copy()
+
+
+def q30_tables(l, k_vectors):
+    """(cos_q30, sin_q30, k): int32 [n_k][N] with llround(cos(k . r_i) 2^30) and the sine likewise, r_i =
+    lattices._positions(l) in the site order of mc.conf (include/dqmc_hip.h, "finite-size-scaling observables")"""
+    r = np.array(_positions(l), dtype=float)
+    k = np.array(k_vectors, dtype=float).reshape(-1, r.shape[1]) if len(k_vectors) else np.zeros((0, r.shape[1]))
+    if len(k) > 8:
+        raise ValueError("FSS: at most 8 wave vectors")
+    ph = k @ r.T
+
+    def llround(x):  # half away from zero, as C's llround
+        return (np.sign(x) * np.floor(np.abs(x) + 0.5)).astype(np.int64).astype(np.int32)
+    return (np.ascontiguousarray(llround(np.cos(ph) * 2.0 ** 30)),
+            np.ascontiguousarray(llround(np.sin(ph) * 2.0 ** 30)), k)
+
+
+def _binder(M2, M4):
+    """U4 = 1 - <M4> / (3 <M2>^2) and its gradient with respect to (M2, M4)"""
+    return 1.0 - M4 / (3.0 * M2 * M2), (2.0 * M4 / (3.0 * M2 ** 3), -1.0 / (3.0 * M2 * M2))
+
+
+def _xi(M2, S, N, knorm):
+    """xi = sqrt(S(0) / S(k) - 1) / (2 sin(|k| / 2)) with S(0) = <M2> / N and its gradient with respect to (M2, S);
+    NaN where S(0) < S(k)"""
+    c = 1.0 / (2.0 * math.sin(0.5 * knorm))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        root = float(np.sqrt(np.float64(M2) / (N * np.float64(S)) - 1.0))
+        g = np.float64(c) / (2.0 * np.float64(root))
+        return c * root, (float(g / (N * S)), float(-g * M2 / (N * S * S)))
+
+
+def _delta_var(grad, vx, vy, cov):
+    """first-order variance of f(x, y) from the variances of the means and their covariance"""
+    var = grad[0] * grad[0] * vx + grad[1] * grad[1] * vy + 2.0 * grad[0] * grad[1] * cov
+    return max(var, 0.0) if var == var else var
+
+
 class MC:
     """MC(model; beta | T, ...) (MC.jl:16-80) for `n_walkers` chains.  `beta` may be a sequence of n_walkers values
     (one temperature per walker).
@@ -76,11 +120,16 @@ class MC:
     measurement.  A `beta` or `T` sequence of length R is tiled over the ladders.  Walker w stays at beta_w with its
     stream, sums, series and binner; an accepted exchange swaps the configurations (spins, E, M and the replica label)
     of two neighbouring walkers, so measurements(w) and binned(w) remain "at beta_w".  `exchange_rate=0` leaves the
-    sweeps as they are without exchange; `exchange()` then still runs a round by hand."""
+    sweeps as they are without exchange; `exchange()` then still runs a round by hand.
+
+    `fss=True` (or a list of at most 8 wave vectors) also measures M^4 and the structure factor S(k) wherever E and |M|
+    are measured (set_fss): `fss()` gives the Binder cumulant U4 and the second-moment correlation length xi, and with
+    `binning=True` `binned_fss()` gives their error bars."""
 
     def __init__(self, model, beta=None, T=None, n_walkers=1, seed=123, first_walker=0, thermalization=0, sweeps=1000,
                  measure_rate=1, print_rate=1000, global_moves=False, global_rate=5, device_id=0, series_capacity=0,
-                 cluster_moves=False, binning=False, binning_capacity=None, n_replicas=0, exchange_rate=0):
+                 cluster_moves=False, binning=False, binning_capacity=None, n_replicas=0, exchange_rate=0,
+                 fss=False):
         if global_moves:
             raise NotImplementedError(
                 "MC(global_moves=True): the reference's Wolff global_move cannot run (IsingModel.jl:137 uses the "
@@ -134,6 +183,9 @@ class MC:
             self._c(lib().dqmc_mc_set_global_rate(self._h, int(global_rate)))
         if self.n_replicas or self.exchange_rate:
             self.set_exchange(self.n_replicas, self.exchange_rate)
+        self.k_vectors = None
+        if fss is not False and fss is not None:
+            self.set_fss(fss)
         if binning:
             self.enable_binning(binning_capacity)
 
@@ -393,6 +445,127 @@ class MC:
                     o["std_error_walkers"] = (math.sqrt(float(((means - mean) ** 2).sum()) / (W * (W - 1.0)))
                                               if W >= 2 else float("nan"))
                 out[group][k] = o
+        if pooled:
+            out["n_walkers"] = len(ws)
+        return out
+
+    # ---- finite-size scaling
+    def set_fss(self, k_vectors=True):
+        """dqmc_mc_set_fss: from now on every measurement also takes M^4 and S(k) = |sum_i s_i e^{i k . r_i}|^2 / N at
+        the given wave vectors (True: reciprocal_vectors(lattice), the smallest ones, one per lattice dimension; a
+        list of at most 8 vectors of the lattice's dimension, possibly empty: M^4 only; None or False: off).  Resets
+        the FSS sums and, if binning is on, restarts the binner with every section empty."""
+        if k_vectors is None or k_vectors is False:
+            self._c(lib().dqmc_mc_set_fss(self._h, -1, None, None))
+            self.k_vectors = None
+            return
+        ks = reciprocal_vectors(self.model.l) if k_vectors is True else k_vectors
+        cq, sq, k = q30_tables(self.model.l, ks)
+        i32 = C.POINTER(C.c_int32)
+        self._c(lib().dqmc_mc_set_fss(self._h, len(k), cq.ctypes.data_as(i32), sq.ctypes.data_as(i32)))
+        self.k_vectors = k
+
+    def fss_sums(self, walker=0):
+        """dqmc_mc_fss of one walker: n_meas, n_k, sum_M4, sum_S[8]"""
+        out = McFss()
+        self._c(lib().dqmc_mc_get_fss(self._h, walker, C.byref(out)))
+        return out
+
+    def _fss_derived(self, M2, M4, S):
+        U4, _ = _binder(M2, M4)
+        xi = np.array([_xi(M2, S[k], self.N, float(np.linalg.norm(self.k_vectors[k])))[0] for k in range(len(S))])
+        out = {"M2": M2, "M4": M4, "S": np.array(S, dtype=float), "U4": U4, "xi": xi}
+        L = getattr(self.model.l, "L", None)
+        if L is not None:
+            out["xi_over_L"] = xi / float(L)
+        return out
+
+    def fss(self, walker=0):
+        """the plain means of one walker: M4, S (one per wave vector), the Binder cumulant U4 = 1 - <M4>/(3 <M2>^2)
+        and the second-moment correlation length xi_k = sqrt(S(0)/S_k - 1) / (2 sin(|k|/2)) with S(0) = <M2>/N (the
+        usual definition for unit lattice spacing; NaN where S(0) < S_k), xi_over_L where the lattice has an L.
+        <M2> is the one of measurements(): the two counts must agree (after switching FSS on mid-run,
+        reset_accumulators() first)."""
+        f, st = self.fss_sums(walker), self.stats(walker)
+        if f.n_k < 0:
+            raise DQMCError(ERR_STATE, "fss: FSS is off (MC(fss=True) or set_fss)")
+        if f.n_meas == 0:
+            raise DQMCError(ERR_INVALID, "fss: no measurement has been taken")
+        if f.n_meas != st.n_meas:
+            raise DQMCError(ERR_STATE, "fss: %d FSS measurements but %d of M2 (FSS was switched on mid-run: "
+                                       "reset_accumulators() first)" % (f.n_meas, st.n_meas))
+        n = float(f.n_meas)
+        out = self._fss_derived(st.sum_M2 / n, f.sum_M4 / n, [f.sum_S[k] / n for k in range(f.n_k)])
+        out["n_meas"] = int(f.n_meas)
+        return out
+
+    def fss_binner_level(self, walker, level):
+        """(x_sum[2 + n_k], x2_sum[2 + n_k], xy_sum[1 + n_k], count) of one level of one walker of the binner's FSS
+        section: elements [M2, M4, S_0 ..], pairs (M2, M4), (M2, S_0) .."""
+        nk = 0 if self.k_vectors is None else len(self.k_vectors)
+        xs, x2, xy, n = np.zeros(2 + nk), np.zeros(2 + nk), np.zeros(1 + nk), C.c_int64()
+        dp = C.POINTER(C.c_double)
+        self._c(lib().dqmc_mc_fss_binner_get_level(self._h, walker, level, xs.ctypes.data_as(dp), x2.ctypes.data_as(dp),
+                                                   xy.ctypes.data_as(dp), C.byref(n)))
+        return xs, x2, xy, n.value
+
+    def fss_binner_finish(self, walker=0, level=None):
+        """dqmc_mc_fss_binned of one walker at `level` (None: the reliable level)"""
+        out = McFssBinned()
+        self._c(lib().dqmc_mc_fss_binner_finish(self._h, walker, -1 if level is None else int(level), C.byref(out)))
+        return out
+
+    def _binned_fss_walker(self, walker, level):
+        """{name: (mean, variance of the mean at `level`, the same at level 0 or None)} of one walker; S, xi as lists"""
+        b = self.fss_binner_finish(walker, level)
+        nk = b.n_k
+        M2, M4 = b.mean[0], b.mean[1]
+        U4, gU = _binder(M2, M4)
+        obs = {"M2": (M2, b.varN[0], b.varN0[0]), "M4": (M4, b.varN[1], b.varN0[1]),
+               "U4": (U4, _delta_var(gU, b.varN[0], b.varN[1], b.covN[0]), None), "S": [], "xi": []}
+        for k in range(nk):
+            S = b.mean[2 + k]
+            xi, g = _xi(M2, S, self.N, float(np.linalg.norm(self.k_vectors[k])))
+            obs["S"].append((S, b.varN[2 + k], b.varN0[2 + k]))
+            obs["xi"].append((xi, _delta_var(g, b.varN[0], b.varN[2 + k], b.covN[1 + k]), None))
+        return obs, int(b.count), int(b.level)
+
+    def binned_fss(self, walker=0, level=None, walkers=None):
+        """mean, std_error and tau of M2, M4 and each S_k from the binner's FSS section at `level` (None: the reliable
+        one), and mean and std_error of U4 and each xi_k (xi_over_L where the lattice has an L) by the delta method on
+        the binned covariances of (M2, M4) and (M2, S_k): {"M2", "M4", "U4": {...}, "S", "xi": [{...} per k], "count",
+        "level"}.  `walkers=[...]` pools chains of equal beta under the rules of binned(): U4 and xi are formed per
+        walker first, std_error = sqrt(sum_w var_w) / W, plus std_error_walkers."""
+        pooled = walkers is not None
+        ws = [int(w) for w in walkers] if pooled else [walker]
+        if not ws:
+            raise ValueError("binned_fss: no walker given")
+        if any(self.betas[w] != self.betas[ws[0]] for w in ws):
+            raise ValueError("binned_fss: the pooled walkers must share one beta")
+        per = [self._binned_fss_walker(w, level) for w in ws]
+        W = float(len(ws))
+
+        def pool(entries):
+            means = np.array([e[0] for e in entries])
+            vl = float(np.sum([e[1] for e in entries]))
+            mean = float(means.sum() / W)
+            o = {"mean": mean, "std_error": (math.sqrt(max(vl, 0.0)) if vl == vl else vl) / W}
+            if entries[0][2] is not None:
+                with np.errstate(invalid="ignore", divide="ignore"):
+                    o["tau"] = float(0.5 * (np.float64(vl) / np.sum([e[2] for e in entries]) - 1.0))
+            if pooled:
+                o["std_error_walkers"] = (math.sqrt(float(((means - mean) ** 2).sum()) / (W * (W - 1.0)))
+                                          if W >= 2 else float("nan"))
+            return o
+
+        out = {"count": per[0][1], "level": per[0][2]}
+        for name in ("M2", "M4", "U4"):
+            out[name] = pool([p[0][name] for p in per])
+        for name in ("S", "xi"):
+            out[name] = [pool([p[0][name][k] for p in per]) for k in range(len(per[0][0][name]))]
+        L = getattr(self.model.l, "L", None)
+        if L is not None:
+            out["xi_over_L"] = [{key: v / float(L) for key, v in o.items()} for o in out["xi"]]
         if pooled:
             out["n_walkers"] = len(ws)
         return out
