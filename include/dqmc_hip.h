@@ -624,6 +624,38 @@ int dqmc_mc_get_exchange_stats(dqmc_mc_handle *h, int32_t walker, dqmc_mc_exchan
  * change columns in LDS), except a round that follows a cluster move; 0: every round is a launch of its own on the state
  * in device memory (any other R), or dqmc_mc_sweep runs no rounds */
 int dqmc_mc_exchange_fused(dqmc_mc_handle *h, int32_t *fused);
+/* Checkerboard sweeps: the local update of one walker spread over a whole workgroup.  sweep(mc) of the reference is
+ * sequential, so this is another Markov chain: like the cluster move and replica exchange a defined extension, opt-in,
+ * on a Philox domain of its own.  A colouring gives every site a colour c_i in [0, C), C <= 16, such that no site shares
+ * its colour with any entry of its neighs column (a repeated neighbour is fine and counts twice in dE, as on
+ * SquareLattice(2); a site that lists itself as a neighbour cannot be coloured: DQMC_ERR_INVALID).  A checkerboard sweep
+ * of a walker visits the colours 0 .. C - 1 in order; within a colour every site i (0-based) is decided from the
+ * configuration as it stood when the colour began: dE = 2 s_i sum_k s_{neighs[k, i]}, accepted iff dE <= 0 ||
+ * u_cb(s, i) < thr[dE / 2 - 1] with the per-walker table exp(-beta 2k) of dqmc_mc_set_beta, compared in fp64 (no exp on
+ * the device).  u_cb(s, i) is Philox4x32-10 with the slot's key and counter words (i, low32(s), 3, high32(s)), where s
+ * counts the checkerboard sweeps the slot has run since dqmc_mc_seed: a fourth domain (word 2 is 0 for the local stream,
+ * 1 for the cluster move, 2 for exchange).  It matters only where dE > 0 and is formed only there; uniforms_used, the
+ * move cursor and the exchange cursor do not move.  The sites of a colour share no bond, so the outcome is one
+ * configuration whatever order the device takes them in, dE is additive within a colour, and E and M stay exact
+ * integers: a host restatement reproduces every sweep bit for bit.  prop_local += n_sites per sweep, acc_local counts
+ * the accepted sites.  Everything else keeps its place: sweep i is followed by its cluster move, its exchange round
+ * (always a launch of its own in this mode: dqmc_mc_exchange_fused answers 0), its measurement and its FSS measurement;
+ * an exchange leaves s with the slot, like every other cursor.  Each colour pass is a product of commuting single-site
+ * Metropolis kernels, each of which satisfies detailed balance, so the sweep leaves the Boltzmann weight invariant. */
+#define DQMC_MC_UPDATE_SEQUENTIAL   0
+#define DQMC_MC_UPDATE_CHECKERBOARD 1
+/* kind 0 (the default): the sequential sweep, exactly as on a handle that never heard of this call (colour is ignored).
+ * kind 1: checkerboard sweeps with the caller's colouring, colour[i] in [0, n_colours), 1 <= n_colours <= 16 (copied).
+ * It is validated on the host before the device is touched: DQMC_ERR_INVALID names the offending pair of sites, and the
+ * handle stays as it was.  May be called at any time between sweeps; it touches neither the configurations, the sums
+ * nor any cursor (only dqmc_mc_seed zeroes sweeps_drawn). */
+int dqmc_mc_set_update(dqmc_mc_handle *h, int32_t kind, const int32_t *colour /* n_sites, NULL for kind 0 */,
+                       int32_t n_colours);
+typedef struct {
+    int32_t kind, n_colours; /* n_colours = 0 in sequential mode */
+    uint64_t sweeps_drawn;   /* the slot's checkerboard sweep cursor s */
+} dqmc_mc_update_stats;
+int dqmc_mc_get_update(dqmc_mc_handle *h, int32_t walker, dqmc_mc_update_stats *out);
 int dqmc_mc_synchronize(dqmc_mc_handle *h);
 
 /* ---- error bars of the MC flavor: one logarithmic binner per walker, pushed inside the sweep --------------------

@@ -19,6 +19,6 @@ from .dqmc import (DQMC, DQMCParameters, calculate_greens_AVX, device_count,  # 
                    finish_moments, hopping_exponentials, mfma_f64_peak, rdivp, triangular_factors,
                    udt_AVX_pivot, vmul)
 
-from .mc import MC, IsingModel, IsingTc, reciprocal_vectors  # noqa: F401
+from .mc import MC, IsingModel, IsingTc, greedy_colouring, reciprocal_vectors  # noqa: F401
 
 lib()  # fail loudly at import time if the HIP library has not been built

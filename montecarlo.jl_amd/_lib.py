@@ -73,6 +73,13 @@ class McExchangeStats(C.Structure):
                 ("rounds", C.c_uint64)]
 
 
+class McUpdateStats(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("n_colours", C.c_int32), ("sweeps_drawn", C.c_uint64)]
+
+
+MC_UPDATE_KINDS = ("sequential", "checkerboard")  # DQMC_MC_UPDATE_*
+
+
 class McBinned(C.Structure):
     _fields_ = [("mean", C.c_double * 4), ("varN", C.c_double * 4), ("varN0", C.c_double * 4), ("tau", C.c_double * 4),
                 ("covN", C.c_double * 2), ("count", C.c_int64), ("level", C.c_int32)]
@@ -212,6 +219,8 @@ SIGNATURES = {
     "dqmc_mc_exchange": (C.c_int, [_H]),
     "dqmc_mc_get_exchange_stats": (C.c_int, [_H, C.c_int32, C.POINTER(McExchangeStats)]),
     "dqmc_mc_exchange_fused": (C.c_int, [_H, C.POINTER(C.c_int32)]),
+    "dqmc_mc_set_update": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_int32), C.c_int32]),
+    "dqmc_mc_get_update": (C.c_int, [_H, C.c_int32, C.POINTER(McUpdateStats)]),
     "dqmc_mc_synchronize": (C.c_int, [_H]),
     "dqmc_mc_binner_enable": (C.c_int, [_H, C.c_int64]),
     "dqmc_mc_binner_size": (C.c_int, [_H, C.POINTER(C.c_int32), _i64p]),

@@ -52,6 +52,13 @@
 // values belong to the slot).  Per walker sum_M4, sum_S[8] and an n_meas of their own; with the binner on a second section
 // over [M2, M4, S_0 ..] with the cross sums (M2, M4) and (M2, S_k).  A stand-alone kernel (ising_fss.inl) that
 // dqmc_mc_sweep launches behind every measured sweep: the kernels above it in this file are the same with FSS on or off.
+//
+// Checkerboard sweep (dqmc_mc_set_update; the reference's sweep(mc) is sequential, so this is another defined extension,
+// opt-in): a colouring c_i in [0, C), C <= 16, no site sharing its colour with a neighbour; a sweep visits the colours in
+// order, and within a colour every site is decided from the configuration as it stood when the colour began, with the
+// Metropolis rule and threshold table above and u_cb(s, i) = philox4_uniform(key, i, low32(s), 3, high32(s)), s = the
+// slot's checkerboard sweeps since dqmc_mc_seed: a fourth domain, c2 = 3.  One workgroup per walker (ising_cb.inl);
+// the sequential kernels, their launches and their results are untouched while the mode is off.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -435,6 +442,19 @@ __global__ __launch_bounds__(WAVE) void ising_exchange_kernel(DevState s, Exchan
 // the finite-size-scaling measurement: FssArg, ising_fss_bin_push, ising_fss_kernel
 #include "ising_fss.inl"
 
+// the checkerboard sweep, one workgroup per walker: CbArg, ising_cb_kernel
+#include "ising_cb.inl"
+
+// The work bound of the checkerboard sweep, from its measured cost on the MI355X: with the walkers' workgroups
+// all resident a sweep takes about 0.6 us + 2.45 ns per site (L = 8 .. 128: 1.3, 3.0, 10.6, 40 us), i.e. N + 512 "site
+// visits" of 2.5 ns with the barriers counted as CB_SWEEP_OVERHEAD sites; about 680 workgroups of 256 lanes run side by side
+// (4096 walkers take 6 times as long as 16 .. 256), counted as CB_RESIDENT_WALKERS = 512.  A launch runs at most
+// CB_LAUNCH_BUDGET / ((N + 512) max(1, W / 512)) sweeps, one at least: 2^20 visits are 2.6 ms, near the 3 ms the
+// sequential path aims at.
+constexpr double CB_LAUNCH_BUDGET = 1048576.0;
+constexpr double CB_SWEEP_OVERHEAD = 512.0;
+constexpr double CB_RESIDENT_WALKERS = 512.0;
+
 }  // namespace dqmc_mc
 
 using namespace dqmc_mc;
@@ -473,6 +493,11 @@ struct dqmc_mc_handle {
         double *xs = nullptr, *x2 = nullptr, *xy = nullptr, *c = nullptr;
         int64_t T = 0;
     } fss;
+    struct Update {  // dqmc_mc_set_update
+        int kind = DQMC_MC_UPDATE_SEQUENTIAL, C = 0, threads = CB_THREADS;
+        int *site = nullptr, *rows = nullptr, *off = nullptr;  // [N], [N][8], [C + 1]: the colour-sorted tables
+        unsigned long long *cursor = nullptr;                  // [W], allocated with the handle (dqmc_mc_seed zeroes it)
+    } upd;
 };
 
 static thread_local std::string g_mc_create_error;
@@ -835,7 +860,7 @@ int dqmc_mc_create(const dqmc_mc_params *p, dqmc_mc_handle **out)
         (rc = mc_alloc(h, &d.n_series, W)) || (rc = mc_alloc(h, &d.serE, (size_t)h->cap * W)) ||
         (rc = mc_alloc(h, &d.serM, (size_t)h->cap * W)) || (rc = mc_alloc(h, &d.pw, W)) ||
         (rc = mc_alloc(h, &d.moves, W)) || (rc = mc_alloc(h, &d.gprop, W)) || (rc = mc_alloc(h, &d.gacc, W)) ||
-        (rc = mc_alloc(h, &d.gsum, W)))
+        (rc = mc_alloc(h, &d.gsum, W)) || (rc = mc_alloc(h, &h->upd.cursor, W)))
         return bail(rc);
     d.nbr = nbr;
     d.bonds = bonds;
@@ -901,6 +926,7 @@ int dqmc_mc_seed(dqmc_mc_handle *h, int32_t walker, uint64_t seed)
     MCHK(hipSetDevice(h->device));
     if (int rc = mc_put<unsigned long long>(h, h->d.key, 0, walker, seed)) return rc;
     if (int rc = mc_put<unsigned long long>(h, h->d.moves, 0, walker, 0ull)) return rc;
+    if (int rc = mc_put<unsigned long long>(h, h->upd.cursor, 0, walker, 0ull)) return rc;
     return mc_put<unsigned long long>(h, h->d.draw, 0, walker, 0ull);
 }
 
@@ -985,11 +1011,15 @@ int dqmc_mc_sweep(dqmc_mc_handle *h, int32_t n_sweeps, int64_t first_sweep_index
     const size_t lds = (size_t)h->nw * WAVE * 4;
     const int grid = (h->W + WAVE - 1) / WAVE;
     const double per_sweep = (double)h->N * std::max((double)h->W, BUDGET_WALKERS);
-    const int chunk = (int)std::max(1.0, std::min((double)n_sweeps, std::floor(LAUNCH_BUDGET / per_sweep)));
+    const dqmc_mc_handle::Update &u = h->upd;
+    const bool cb = u.kind == DQMC_MC_UPDATE_CHECKERBOARD;
+    const double cb_per_sweep = ((double)h->N + CB_SWEEP_OVERHEAD) * std::max(1.0, (double)h->W / CB_RESIDENT_WALKERS);
+    const int chunk = (int)std::max(
+        1.0, std::min((double)n_sweeps, std::floor(cb ? CB_LAUNCH_BUDGET / cb_per_sweep : LAUNCH_BUDGET / per_sweep)));
     const int r = h->global_rate;
     dqmc_mc_handle::Tempering &t = h->xch;
     const int k = t.R >= 2 ? t.rate : 0;  // an exchange round after every k-th sweep
-    const bool fused = t.fused();
+    const bool fused = t.fused() && !cb;  // the checkerboard kernel runs no rounds: each is a launch of its own
     for (int done = 0; done < n_sweeps;) {
         int n = std::min(chunk, n_sweeps - done);
         const long long first = first_sweep_index + done;
@@ -1007,6 +1037,12 @@ int dqmc_mc_sweep(dqmc_mc_handle *h, int32_t n_sweeps, int64_t first_sweep_index
         const bool deferred = (move || round) && last > thermalization && last % measure_rate == 0;
         const long long defer = move || round ? last : -1LL;
         const Exchange xa = mc_exchange_arg(h);
+        if (cb) {
+            const CbArg ca{u.C, h->z, u.cursor, b.on ? b.xs : nullptr, b.x2, b.xy, b.c, b.L - 1, (long long)b.T};
+            hipLaunchKernelGGL(ising_cb_kernel, dim3(h->W), dim3(u.threads), 0, h->stream, h->d, ca, (const int *)u.site,
+                               (const int4 *)u.rows, (const int *)u.off, n, first, (long long)thermalization,
+                               (int)measure_rate, defer);
+        } else
         switch (h->z) {  // binner on: the forms that push every measurement they take; fused: with the exchange round
 #define MC_CASE(Z)                                                                                                  \
     case Z:                                                                                                         \
@@ -1202,7 +1238,7 @@ int dqmc_mc_exchange_fused(dqmc_mc_handle *h, int32_t *fused)
 {
     if (!h) return mc_fail(nullptr, DQMC_ERR_INVALID, "dqmc_mc_exchange_fused: null handle");
     if (!fused) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_mc_exchange_fused: null fused");
-    *fused = h->xch.fused() ? 1 : 0;
+    *fused = h->xch.fused() && h->upd.kind == DQMC_MC_UPDATE_SEQUENTIAL ? 1 : 0;
     return DQMC_OK;
 }
 
@@ -1449,6 +1485,83 @@ int dqmc_mc_fss_binner_finish(dqmc_mc_handle *h, int32_t walker, int32_t level, 
     out->count = f.T >> level;
     out->level = level;
     out->n_k = f.n_k;
+    return DQMC_OK;
+}
+
+int dqmc_mc_set_update(dqmc_mc_handle *h, int32_t kind, const int32_t *colour, int32_t n_colours)
+{
+    if (!h) return mc_fail(nullptr, DQMC_ERR_INVALID, "dqmc_mc_set_update: null handle");
+    if (kind == DQMC_MC_UPDATE_SEQUENTIAL) {
+        h->upd.kind = kind;
+        return DQMC_OK;
+    }
+    if (kind != DQMC_MC_UPDATE_CHECKERBOARD)
+        return mc_fail(h, DQMC_ERR_INVALID, "dqmc_mc_set_update: kind must be 0 (sequential) or 1 (checkerboard)");
+    if (!colour) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_mc_set_update: null colouring");
+    if (n_colours < 1 || n_colours > CB_MAX_COLOURS)
+        return mc_fail(h, DQMC_ERR_INVALID, "dqmc_mc_set_update: n_colours must be in 1..16");
+    const int N = h->N, z = h->z, nc = n_colours;
+    for (int i = 0; i < N; ++i)
+        if (colour[i] < 0 || colour[i] >= nc)
+            return mc_fail(h, DQMC_ERR_INVALID,
+                           "dqmc_mc_set_update: the colour of site " + std::to_string(i) + " is out of range 0..n_colours-1");
+    for (int i = 0; i < N; ++i)
+        for (int k = 0; k < z; ++k) {
+            const int j = h->nbr_h[(size_t)i * z + k];
+            if (j == i)
+                return mc_fail(h, DQMC_ERR_INVALID, "dqmc_mc_set_update: site " + std::to_string(i) +
+                                                        " lists itself as a neighbour (0-based): no checkerboard sweep");
+            if (colour[j] == colour[i])
+                return mc_fail(h, DQMC_ERR_INVALID, "dqmc_mc_set_update: the neighbours " + std::to_string(i) + " and " +
+                                                        std::to_string(j) + " (0-based sites) share colour " +
+                                                        std::to_string(colour[i]));
+        }
+    // the sites sorted by colour (site order within a class), the class offsets, and the padded rows in that order
+    std::vector<int> off((size_t)nc + 1, 0), site((size_t)N), rows((size_t)N * MAX_Z, 0);
+    for (int i = 0; i < N; ++i) off[(size_t)colour[i] + 1] += 1;
+    int largest = 0;
+    for (int c = 0; c < nc; ++c) {
+        largest = std::max(largest, off[(size_t)c + 1]);
+        off[(size_t)c + 1] += off[c];
+    }
+    std::vector<int> fill(off.begin(), off.end() - 1);
+    for (int i = 0; i < N; ++i) {
+        const int e = fill[colour[i]]++;
+        site[e] = i;
+        for (int k = 0; k < z; ++k) rows[(size_t)e * MAX_Z + k] = h->nbr_h[(size_t)i * z + k];
+    }
+    MCHK(hipSetDevice(h->device));
+    MCHK(hipStreamSynchronize(h->stream));
+    dqmc_mc_handle::Update &u = h->upd;
+    for (int **p : {&u.site, &u.rows, &u.off}) {
+        mc_release(h, *p);
+        *p = nullptr;
+    }
+    u.kind = DQMC_MC_UPDATE_SEQUENTIAL;  // (until the new tables are in place)
+    int rc = 0;
+    if ((rc = mc_alloc(h, &u.site, site.size())) || (rc = mc_alloc(h, &u.rows, rows.size())) ||
+        (rc = mc_alloc(h, &u.off, off.size())))
+        return rc;
+    MCHK(hipMemcpyAsync(u.site, site.data(), site.size() * 4, hipMemcpyHostToDevice, h->stream));
+    MCHK(hipMemcpyAsync(u.rows, rows.data(), rows.size() * 4, hipMemcpyHostToDevice, h->stream));
+    MCHK(hipMemcpyAsync(u.off, off.data(), off.size() * 4, hipMemcpyHostToDevice, h->stream));
+    MCHK(hipStreamSynchronize(h->stream));  // (the vectors are this call's: copied before it returns)
+    u.C = nc;
+    u.threads = std::min(CB_THREADS, std::max(WAVE, (largest + WAVE - 1) / WAVE * WAVE));
+    u.kind = DQMC_MC_UPDATE_CHECKERBOARD;
+    return DQMC_OK;
+}
+
+int dqmc_mc_get_update(dqmc_mc_handle *h, int32_t walker, dqmc_mc_update_stats *out)
+{
+    if (int rc = mc_walker(h, walker, "dqmc_mc_get_update")) return rc;
+    if (!out) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_mc_get_update: null out");
+    MCHK(hipSetDevice(h->device));
+    unsigned long long s = 0;
+    if (int rc = mc_get(h, h->upd.cursor, 0, walker, &s)) return rc;
+    out->kind = h->upd.kind;
+    out->n_colours = h->upd.kind == DQMC_MC_UPDATE_CHECKERBOARD ? h->upd.C : 0;
+    out->sweeps_drawn = s;
     return DQMC_OK;
 }
 

@@ -12,8 +12,8 @@ import time
 
 import numpy as np
 
-from ._lib import (DQMCError, ERR_INVALID, ERR_STATE, McBinned, McExchangeStats, McFss, McFssBinned, McGlobalStats,
-                   McParams, McStats, lib)
+from ._lib import (DQMCError, ERR_INVALID, ERR_STATE, MC_UPDATE_KINDS, McBinned, McExchangeStats, McFss, McFssBinned,
+                   McGlobalStats, McParams, McStats, McUpdateStats, lib)
 from .configurations import CompressedConf
 from .lattices import Chain, CubicLattice, SquareLattice, _lattice_vectors, _positions
 
@@ -79,6 +79,25 @@ def q30_tables(l, k_vectors):
             np.ascontiguousarray(llround(np.sin(ph) * 2.0 ** 30)), k)
 
 
+def greedy_colouring(l):
+    """the default colouring of update="checkerboard" (dqmc_mc_set_update): in site order, the smallest colour not used
+    by an already-coloured neighbour j < i; int32 [N].  Two colours on the bipartite lattices (even chains, even square
+    and cubic lattices), three or four on odd ones and on the triangular lattice.  A site that lists itself as a
+    neighbour (the 1-site chain) cannot be coloured: ValueError."""
+    nb = np.asarray(l.neighs, dtype=np.int64) - 1
+    N = nb.shape[1]
+    colour = np.full(N, -1, dtype=np.int32)
+    for i in range(N):
+        if np.any(nb[:, i] == i):
+            raise ValueError("greedy_colouring: site %d lists itself as a neighbour" % i)
+        used = {int(colour[j]) for j in nb[:, i] if j < i}
+        c = 0
+        while c in used:
+            c += 1
+        colour[i] = c
+    return colour
+
+
 def _binder(M2, M4):
     """U4 = 1 - <M4> / (3 <M2>^2) and its gradient with respect to (M2, M4)"""
     return 1.0 - M4 / (3.0 * M2 * M2), (2.0 * M4 / (3.0 * M2 ** 3), -1.0 / (3.0 * M2 * M2))
@@ -124,12 +143,17 @@ class MC:
 
     `fss=True` (or a list of at most 8 wave vectors) also measures M^4 and the structure factor S(k) wherever E and |M|
     are measured (set_fss): `fss()` gives the Binder cumulant U4 and the second-moment correlation length xi, and with
-    `binning=True` `binned_fss()` gives their error bars."""
+    `binning=True` `binned_fss()` gives their error bars.
+
+    `update="checkerboard"` sweeps every walker with a whole workgroup, colour class by colour class (set_update;
+    `colouring=None`: greedy_colouring(lattice)): another Markov chain than the reference's sequential sweep(mc), with
+    the same stationary distribution, on a Philox domain of its own, and much faster per sweep where the walkers are
+    few and the lattice is large.  `update="sequential"` (the default) is the reference's sweep."""
 
     def __init__(self, model, beta=None, T=None, n_walkers=1, seed=123, first_walker=0, thermalization=0, sweeps=1000,
                  measure_rate=1, print_rate=1000, global_moves=False, global_rate=5, device_id=0, series_capacity=0,
                  cluster_moves=False, binning=False, binning_capacity=None, n_replicas=0, exchange_rate=0,
-                 fss=False):
+                 fss=False, update="sequential", colouring=None):
         if global_moves:
             raise NotImplementedError(
                 "MC(global_moves=True): the reference's Wolff global_move cannot run (IsingModel.jl:137 uses the "
@@ -183,6 +207,9 @@ class MC:
             self._c(lib().dqmc_mc_set_global_rate(self._h, int(global_rate)))
         if self.n_replicas or self.exchange_rate:
             self.set_exchange(self.n_replicas, self.exchange_rate)
+        self.update = "sequential"
+        if update != "sequential" or colouring is not None:
+            self.set_update(update, colouring)
         self.k_vectors = None
         if fss is not False and fss is not None:
             self.set_fss(fss)
@@ -330,6 +357,30 @@ class MC:
         """the replica labels of all slots: replicas()[w] is the ladder-local index of the slot in which the
         configuration now in slot w started"""
         return np.array([self.exchange_stats(w).replica for w in range(self.n_walkers)], dtype=np.int64)
+
+    # ---- the local update
+    def set_update(self, kind, colouring=None):
+        """dqmc_mc_set_update: "sequential" (the reference's sweep(mc), the default) or "checkerboard" with `colouring`
+        (an integer per site, at most 16 colours, no two neighbours alike; None: greedy_colouring(lattice)).  Between
+        sweeps at any time; configurations, sums and cursors stay."""
+        if kind not in MC_UPDATE_KINDS:
+            raise ValueError("set_update: kind must be one of %s" % (MC_UPDATE_KINDS,))
+        if kind == "sequential":
+            self._c(lib().dqmc_mc_set_update(self._h, 0, None, 0))
+        else:
+            col = greedy_colouring(self.model.l) if colouring is None else colouring
+            col = np.ascontiguousarray(np.asarray(col).reshape(-1), dtype=np.int32)
+            if col.size != self.N:
+                raise DQMCError(ERR_INVALID, "set_update: expected %d colours" % self.N)
+            n = int(col.max()) + 1 if col.size else 0
+            self._c(lib().dqmc_mc_set_update(self._h, 1, col.ctypes.data_as(C.POINTER(C.c_int32)), n))
+        self.update = kind
+
+    def update_stats(self, walker=0):
+        """kind, n_colours and sweeps_drawn (the walker's checkerboard sweep cursor)"""
+        st = McUpdateStats()
+        self._c(lib().dqmc_mc_get_update(self._h, walker, C.byref(st)))
+        return st
 
     def reset_accumulators(self):
         self._c(lib().dqmc_mc_reset_accumulators(self._h))
