@@ -204,6 +204,10 @@ typedef struct {
     uint64_t moves_drawn;
 } dqmc_global_stats;
 int dqmc_get_global_stats(dqmc_handle *h, int32_t walker, dqmc_global_stats *out);
+/* The latest move the walker took part in: its weight ratio p as the device computed it (NaN: a singular or non-finite
+ * A2), the decision (1 accepted, 0 rejected) and the site of a FLIP_SITE move (0 for FLIP_ALL).  Before the walker's
+ * first move: p = 0, accepted = 0, site = 0. */
+int dqmc_get_global_last(dqmc_handle *h, int32_t walker, double *p, int32_t *accepted, int32_t *site);
 
 /* ---- measurement accumulators (stand-in for push!(LogBinner, greens(mc)),
  * measurements/generic.jl:207-215,260-263).  dqmc_accumulate_greens adds, for
@@ -447,6 +451,13 @@ int dqmc_vmul(int32_t device_id, int32_t n, int32_t batch, int32_t transa, int32
  * step-by-step search of UDT.jl:212-246: D is then not sorted; DQMC_QR_NOBLOCKED=1 selects the reference's rule. */
 int dqmc_udt_pivot(int32_t device_id, int32_t n, int32_t batch, double *U, double *D, double *T,
                    int64_t *pivot, int32_t apply_pivot);
+/* The kernel behind dqmc_logdet on matrices of the caller's: unit u has its n x n column-major matrix at A + u * strideA
+ * (strideA >= n * n) and n positive numbers at D + u * strideD (strideD >= n); logabsdet[u] = sum_i log D[u][i] in the
+ * kernel's fixed order, sign[u] = the sign of det A[u] from an LU with partial pivoting (the largest magnitude on or
+ * below the diagonal, the lowest row among equals), 0 for a zero or non-finite pivot.  A and D come back as the device
+ * left them: the matrices overwritten by the elimination at n > 64, everything between the units untouched. */
+int dqmc_logdet_matrices(int32_t device_id, int32_t n, int32_t batch, double *A, int64_t strideA, double *D,
+                         int64_t strideD, double *logabsdet, int32_t *sign);
 /* rdivp!(A, T, O, pivot) (src/linalg/general.jl:138-166) */
 int dqmc_rdivp(int32_t device_id, int32_t n, int32_t batch, double *A, const double *T,
                const int64_t *pivot);

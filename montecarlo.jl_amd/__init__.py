@@ -16,7 +16,7 @@ from .sharding import (Communicator, reduce_accumulators, walker_block, walker_r
                        walker_seeds)
 from .dqmc import (DQMC, DQMCParameters, calculate_greens_AVX, device_count,  # noqa: F401
                    checkerboard_exponentials, checkerboard_seqs, checkerboard_tables,
-                   finish_moments, hopping_exponentials, mfma_f64_peak, rdivp, triangular_factors,
+                   finish_moments, hopping_exponentials, logdet_matrices, mfma_f64_peak, rdivp, triangular_factors,
                    udt_AVX_pivot, vmul)
 
 from .mc import MC, IsingModel, IsingTc, greedy_colouring, reciprocal_vectors  # noqa: F401

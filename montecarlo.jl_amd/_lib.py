@@ -187,6 +187,8 @@ SIGNATURES = {
     "dqmc_get_reduced_stats": (C.c_int, [_H, C.POINTER(Stats)]),
     "dqmc_vmul": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp]),
     "dqmc_udt_pivot": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp, _i64p, C.c_int32]),
+    "dqmc_logdet_matrices": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _dp, C.c_int64, _dp, C.c_int64, _dp,
+                             C.POINTER(C.c_int32)]),
     "dqmc_rdivp": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _i64p]),
     "dqmc_calculate_greens": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "dqmc_set_checkerboard": (C.c_int, [_H, C.c_int32, C.c_int32, _dp, C.POINTER(C.c_int32), _dp, _dp,
@@ -198,6 +200,7 @@ SIGNATURES = {
     "dqmc_udt_one_launch_sites": (C.c_int, [_H, C.POINTER(C.c_int32)]),
     "dqmc_build_commit": (C.c_char_p, []),
     "dqmc_build_source_hash": (C.c_char_p, []),
+    "dqmc_get_global_last": (C.c_int, [_H, C.c_int32, _dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "dqmc_mc_create": (C.c_int, [C.POINTER(McParams), C.POINTER(_H)]),
     "dqmc_mc_destroy": (C.c_int, [_H]),
     "dqmc_mc_last_error": (C.c_char_p, [_H]),

@@ -2323,6 +2323,32 @@ int dqmc_udt_pivot(int32_t device_id, int32_t n, int32_t batch, double *U, doubl
     return DQMC_OK;
 }
 
+int dqmc_logdet_matrices(int32_t device_id, int32_t n, int32_t batch, double *A, int64_t strideA, double *D,
+                         int64_t strideD, double *logabsdet, int32_t *sign)
+{
+    dqmc_handle hh; dqmc_handle *h = &hh;
+    SCHK(scratch_init(h, device_id, n, batch));
+    if (!A || !D || !logabsdet || !sign || strideA < h->nn || strideD < n) {
+        scratch_free(h);
+        return fail(nullptr, DQMC_ERR_INVALID, "dqmc_logdet_matrices: null array, strideA < n * n or strideD < n");
+    }
+    const size_t ua = (size_t)batch * strideA, ud = (size_t)batch * strideD;
+    double *dA, *dD, *dL;
+    int *dS;
+    SCHK(dalloc(h, &dA, ua, false)); SCHK(dalloc(h, &dD, ud, false)); SCHK(dalloc(h, &dL, batch)); SCHK(dalloc(h, &dS, batch));
+    SHIP(hipMemcpy(dA, A, ua * sizeof(double), hipMemcpyHostToDevice));
+    SHIP(hipMemcpy(dD, D, ud * sizeof(double), hipMemcpyHostToDevice));
+    SHIP(launch_logdet(n, batch, dA, strideA, dD, strideD, dL, dS, h->stream));
+    SHIP(hipStreamSynchronize(h->stream));
+    SHIP(hipMemcpy(A, dA, ua * sizeof(double), hipMemcpyDeviceToHost));
+    SHIP(hipMemcpy(D, dD, ud * sizeof(double), hipMemcpyDeviceToHost));
+    SHIP(hipMemcpy(logabsdet, dL, batch * sizeof(double), hipMemcpyDeviceToHost));
+    static_assert(sizeof(int) == sizeof(int32_t), "sign buffer");
+    SHIP(hipMemcpy(sign, dS, batch * sizeof(int), hipMemcpyDeviceToHost));
+    scratch_free(h);
+    return DQMC_OK;
+}
+
 int dqmc_rdivp(int32_t device_id, int32_t n, int32_t batch, double *A, const double *T, const int64_t *pivot)
 {
     dqmc_handle hh; dqmc_handle *h = &hh;

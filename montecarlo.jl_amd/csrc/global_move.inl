@@ -103,3 +103,15 @@ int dqmc_get_global_stats(dqmc_handle *h, int32_t w, dqmc_global_stats *out)
     out->moves_drawn = g.moves_drawn;
     return DQMC_OK;
 }
+int dqmc_get_global_last(dqmc_handle *h, int32_t w, double *p, int32_t *accepted, int32_t *site)
+{
+    ENTER(h); WALKER_OK(h, w);
+    if (!p || !accepted || !site) return fail(h, DQMC_ERR_INVALID, "dqmc_get_global_last: null output");
+    HIPCHK(hipStreamSynchronize(h->stream));
+    GlobalMoveState g;
+    HIPCHK(hipMemcpy(&g, h->gm + w, sizeof(g), hipMemcpyDeviceToHost));
+    *p = g.last_p;
+    *accepted = g.last_accepted;
+    *site = g.site;
+    return DQMC_OK;
+}

@@ -518,6 +518,12 @@ class DQMC:
         self._c(lib().dqmc_get_global_stats(self._h, walker, C.byref(g)))
         return dict(prop_global=g.prop_global, acc_global=g.acc_global, moves_drawn=g.moves_drawn)
 
+    def global_last(self, walker=0):
+        """-> dict(p, accepted, site) of the latest global move the walker took part in"""
+        p, acc, site = C.c_double(), C.c_int32(), C.c_int32()
+        self._c(lib().dqmc_get_global_last(self._h, walker, C.byref(p), C.byref(acc), C.byref(site)))
+        return dict(p=p.value, accepted=bool(acc.value), site=site.value)
+
     # ---- analysis / measurement sums
     def analysis(self, walker=0):
         st = _lib.Stats()
@@ -1083,6 +1089,23 @@ def udt_AVX_pivot(X, apply_pivot=True, device_id=0):
     piv = np.zeros(batch * n, dtype=np.int64)
     check(lib().dqmc_udt_pivot(device_id, n, batch, dptr(u), dptr(d), dptr(t), i64ptr(piv), int(apply_pivot)))
     return _unpack(u, batch, n), d.reshape(batch, n), _unpack(t, batch, n), piv.reshape(batch, n)
+
+
+def logdet_matrices(A, D, n, strideA=None, strideD=None, device_id=0):
+    """logdet_kernel (csrc/logdet.hip) on the caller's matrices: A flat, unit u column-major at u * strideA, D flat at
+    u * strideD -> logabsdet [batch], sign [batch], and A and D as the device left them"""
+    strideA = n * n if strideA is None else int(strideA)
+    strideD = n if strideD is None else int(strideD)
+    a = np.array(A, dtype=np.float64).reshape(-1)
+    d = np.array(D, dtype=np.float64).reshape(-1)
+    batch = a.size // strideA
+    if batch < 1 or a.size != batch * strideA or d.size != batch * strideD:
+        raise ValueError("A and D must hold batch * strideA and batch * strideD numbers")
+    lad = np.zeros(batch)
+    sg = np.zeros(batch, dtype=np.int32)
+    check(lib().dqmc_logdet_matrices(device_id, n, batch, dptr(a), strideA, dptr(d), strideD, dptr(lad),
+                                     sg.ctypes.data_as(C.POINTER(C.c_int32))))
+    return lad, sg, a, d
 
 
 def rdivp(A, T, pivot, device_id=0):

@@ -11,7 +11,9 @@
   the sign of det A2.  Its distance from slogdet_mp is what the tolerances of test_gpu_global_move.py are derived from.
 * philox4_uniform / move_uniform, weight_ratio, decide, apply_flip: the move as the header defines it.
 Shared by test_global_move_reference.py (CPU) and test_gpu_global_move.py."""
+import json
 import math
+import os
 
 import mpmath as mp
 import numpy as np
@@ -20,6 +22,30 @@ from ising_wolff_ref import philox4_uniform
 
 DPS = 60
 FLIP_ALL, FLIP_SITE = 0, 1
+GOLDEN_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "logdet_sizes.json")
+
+
+def field(seed, n, M):
+    """the seeded HS field of the logdet and global-move tests"""
+    rng = np.random.Generator(np.random.Philox(key=seed))
+    return np.asfortranarray((2 * rng.integers(0, 2, size=(n, M)) - 1).astype(np.int8))
+
+
+def golden_model(pkg, case):
+    """the model of one entry of tests/golden/logdet_sizes.json (written by tools/make_logdet_golden.py)"""
+    kind, L = case["lattice"]
+    if kind == "cubic":
+        lat = pkg.CubicLattice(3, L)
+    else:
+        lat = {"square": pkg.SquareLattice, "triangular": pkg.TriangularLattice}[kind](L)
+    if case["model"] == "attractive":
+        return pkg.HubbardModelAttractive(l=lat, U=case["U"], mu=case["mu"])
+    return pkg.HubbardModelRepulsive(l=lat, U=case["U"])
+
+
+def load_golden():
+    with open(GOLDEN_PATH) as f:
+        return json.load(f)
 
 
 def hs_lambda(U, delta_tau):
@@ -106,6 +132,31 @@ def oracle_logdet(O, model, delta_tau, safe_mult, conf):
         sg.append(int(np.linalg.slogdet(A2)[0]))
         A2s.append(A2)
     return lad, sg, A2s
+
+
+def second_route_logdet(O, model, delta_tau, safe_mult, conf):
+    """float64 by another stabilisation: B_M ... B_1 = U D T accumulated from the right-hand end with a pivoted QR every
+    safe_mult slices (the forward chain, where oracle_logdet factors the daggered one), then, with Db = max(D, 1) and
+    Ds = min(D, 1),  I + U Db Ds T = U Db (Db^-1 U' + Ds T):  logabsdet = sum log Db + log|det(Db^-1 U' + Ds T)|, the sign
+    that of det U det(Db^-1 U' + Ds T), both determinants by LAPACK's LU -> (logabsdet [nb], sign [nb])"""
+    n, M = conf.shape
+    lam = hs_lambda(model.U, delta_tau)
+    epl, eml = math.exp(lam), math.exp(-lam)
+    lad, sg = [], []
+    for b, eT2 in enumerate(_eT2_float(model, delta_tau)):
+        cur, D, T = np.eye(n), np.ones(n), np.eye(n)
+        for l in range(M):  # B_l X = eT2 (eV X)
+            ev = np.where((conf[:, l] > 0) == (b == 0), epl, eml)
+            cur = eT2 @ (ev[:, None] * cur)
+            if (l + 1) % safe_mult == 0 or l == M - 1:
+                cur, D, T1, _ = O.udt_pivot(cur * D[None, :], True)
+                T = T1 @ T
+        Db, Ds = np.maximum(D, 1.0), np.minimum(D, 1.0)
+        s1, l1 = np.linalg.slogdet(cur.T / Db[:, None] + Ds[:, None] * T)
+        s2, _ = np.linalg.slogdet(cur)
+        lad.append(float(np.sum(np.log(Db)) + l1))
+        sg.append(int(round(s1 * s2)))
+    return lad, sg
 
 
 # ---- the move ------------------------------------------------------------------------------------------------------

@@ -12,9 +12,20 @@ and 1.45e-13; ten times the larger: LOGDET_TOL_256 = 1.45e-12.
 The triangular case.  Negative determinants are rare among random fields at U = 8, beta = 4 on TriangularLattice(4): the
 stabilised float64 oracle finds 162 among the fields of seeds 0 .. 59999 (a plain float64 product of the slices gives
 about one half, which is rounding noise, not physics).  Seeds 58187 (signs -1, +1) and 59290 (+1, -1) are two of them,
-confirmed with mpmath; seeds 100 and 101 have both signs +1.  The test asserts that mix so that it cannot pass vacuously."""
-import ctypes as C
+confirmed with mpmath; seeds 100 and 101 have both signs +1.  The test asserts that mix so that it cannot pass vacuously.
 
+Away from 4 x 4 (sections 9 to 11) the expected log-determinants of the current and the proposed fields come from
+tests/golden/logdet_sizes.json (tools/make_logdet_golden.py, checked on the CPU by test_logdet_golden.py).  The
+tolerance on logabsdet is ten times the oracle's largest distance from them on these very fields: TriangularLattice(8),
+beta = 4: 4.7e-10 -> LOGDET_TOL_T8 = 4.7e-9; 4 x 4 attractive with 300 slices of dtau = 0.01: 1.5e-14 -> LOGDET_TOL_300 =
+1.5e-13.  A weight ratio carries four log-determinant errors (two blocks, or one block squared, before and after), and
+the rounding of exp's argument: |p / p_ref - 1| <= expm1(4 tol) + 2^-52 (|log|p_ref|| + 1).  FLIP_ALL of the repulsive
+model at mu = 0 exchanges the two blocks' matrices, so p = 1 up to rounding on every lattice: negative weights are found
+among the FLIP_SITE proposals only (17 of walker 0's 64 sites; the golden sites give p < 0 for three of the four walkers)."""
+import ctypes as C
+import math
+
+import mpmath as mp
 import numpy as np
 import pytest
 
@@ -25,6 +36,8 @@ pytestmark = pytest.mark.gpu
 
 LOGDET_TOL = 6.2e-11
 LOGDET_TOL_256 = 1.45e-12
+LOGDET_TOL_T8 = 4.7e-9
+LOGDET_TOL_300 = 1.5e-13
 TOL_G = 1e-10  # the project's bound on Green's functions
 
 
@@ -163,6 +176,39 @@ def test_decisions_match_the_reference(gpu, parity_ref, kind):
 
 
 # ---- 4. state after a move -------------------------------------------------------------------------------------------
+def _state_after_a_move(mc, fresh, kind):
+    W = mc.n_walkers
+    try:
+        before = confs(mc)
+        mc.prepare()
+        mc.global_move(kind)
+        M = mc.p.slices
+        assert (mc.current_slice, mc.direction) == (M, -1)
+        after = confs(mc)
+        acc = [mc.global_stats(w)["acc_global"] for w in range(W)]
+        for w in range(W):
+            assert np.array_equal(after[w], before[w]) == (acc[w] == 0)
+            assert mc.uniforms_used(w) == 0
+            fresh.set_conf(w, after[w])
+        fresh.prepare()
+        for w in range(W):
+            g = mc.greens_eff(w)
+            for b in range(mc.nb):
+                assert relerr(g[b], mc.calculate_greens(M - 1, w)[b]) < TOL_G
+                assert relerr(g[b], fresh.greens_eff(w)[b]) < TOL_G
+        mc.sweep(1)
+        fresh.sweep(1)
+        for w in range(W):
+            assert np.array_equal(mc.conf(w), fresh.conf(w))
+            assert mc.uniforms_used(w) == fresh.uniforms_used(w) > 0
+            for b in range(mc.nb):
+                assert relerr(mc.greens_eff(w)[b], fresh.greens_eff(w)[b]) < TOL_G
+        return acc
+    finally:
+        mc.close()
+        fresh.close()
+
+
 @pytest.mark.parametrize("kind", ["all", "site"])
 def test_state_after_a_move_is_the_prepared_state(gpu, kind):
     """after a move the handle stands where dqmc_prepare leaves it: (current_slice, direction) = (slices, -1), and
@@ -171,36 +217,7 @@ def test_state_after_a_move_is_the_prepared_state(gpu, kind):
     calculate_greens(mc, slices - 1), which is what prepare() gives as well; both are asserted, within the project's
     1e-10.  A following sweep(1) equals that of a fresh handle given the fields by set_conf + prepare, with the same
     local stream (the move does not draw from it)."""
-    mc = make(gpu, "repulsive", 4, seed=77)
-    fresh = make(gpu, "repulsive", 4, seed=77)
-    try:
-        before = confs(mc)
-        mc.prepare()
-        mc.global_move(kind)
-        M = mc.p.slices
-        assert (mc.current_slice, mc.direction) == (M, -1)
-        after = confs(mc)
-        acc = [mc.global_stats(w)["acc_global"] for w in range(4)]
-        for w in range(4):
-            assert np.array_equal(after[w], before[w]) == (acc[w] == 0)
-            assert mc.uniforms_used(w) == 0
-            fresh.set_conf(w, after[w])
-        fresh.prepare()
-        for w in range(4):
-            g = mc.greens_eff(w)
-            for b in range(2):
-                assert relerr(g[b], mc.calculate_greens(M - 1, w)[b]) < TOL_G
-                assert relerr(g[b], fresh.greens_eff(w)[b]) < TOL_G
-        mc.sweep(1)
-        fresh.sweep(1)
-        for w in range(4):
-            assert np.array_equal(mc.conf(w), fresh.conf(w))
-            assert mc.uniforms_used(w) == fresh.uniforms_used(w) > 0
-            for b in range(2):
-                assert relerr(mc.greens_eff(w)[b], fresh.greens_eff(w)[b]) < TOL_G
-    finally:
-        mc.close()
-        fresh.close()
+    _state_after_a_move(make(gpu, "repulsive", 4, seed=77), make(gpu, "repulsive", 4, seed=77), kind)
 
 
 # ---- 5. independence -------------------------------------------------------------------------------------------------
@@ -343,5 +360,135 @@ def test_refusals(gpu):
         st = _lib.GlobalStats()
         assert _lib.lib().dqmc_get_global_stats(mc._h, 4, C.byref(st)) == _lib.ERR_INVALID
         assert mc.global_stats(0) == dict(prop_global=0, acc_global=0, moves_drawn=0)
+    finally:
+        mc.close()
+
+
+# ---- 9. decisions at TriangularLattice(8), with negative weights ----------------------------------------------------------
+@pytest.fixture(scope="module")
+def golden():
+    return ref.load_golden()
+
+
+def _p_ref(model, dtau, conf, new, cur, prop, w):
+    """weight_ratio's formulas on the golden log-determinants -> mpf"""
+    with mp.workdps(ref.DPS):
+        l0, l1 = [mp.mpf(x) for x in cur["logabsdet"][w]], [mp.mpf(x) for x in prop["logabsdet"][w]]
+        if model.flv == 1:
+            dS = int(conf.astype(np.int64).sum() - new.astype(np.int64).sum())
+            return mp.exp(mp.mpf(ref.hs_lambda(model.U, dtau)) * dS + 2 * (l1[0] - l0[0]))
+        sp = cur["sign"][w][0] * cur["sign"][w][1] * prop["sign"][w][0] * prop["sign"][w][1]
+        return sp * mp.exp((l1[0] - l0[0]) + (l1[1] - l0[1]))
+
+
+def _p_tol(p, tol):
+    return math.expm1(4 * tol) + 2.0 ** -52 * (abs(float(mp.log(abs(p)))) + 1)
+
+
+def _seed_for_site(site, n, start):
+    """the first walker seed from `start` on whose site uniform u(0, 0) lands on `site`"""
+    s = start
+    while ref.pick_site(ref.move_uniform(s, 0, 0), n) != site:
+        s += 1
+    return s
+
+
+@pytest.mark.parametrize("kind", ["all", "site"])
+def test_decisions_at_64_sites_with_negative_weights(gpu, golden, kind):
+    """TriangularLattice(8), U = 8, beta = 4, the four golden fields, the device's own Philox uniforms: the walkers are
+    seeded so that u(0, 0) picks the golden site.  last_p within the bound of the module docstring, the decision that of
+    ref.decide with u(0, 1), the counters, the fields, and one negative_probability entry per negative p."""
+    mv = golden["moves"]["triangular8"]
+    case = golden["logdet"][mv["case"]]
+    model = ref.golden_model(gpu, case)
+    n, M = case["n"], case["slices"]
+    mc = gpu.DQMC(model, n_walkers=4, beta=case["beta"], delta_tau=golden["delta_tau"], safe_mult=golden["safe_mult"])
+    try:
+        expect = []
+        for w, s in enumerate(mv["seeds"]):
+            c = ref.field(s, n, M)
+            new = ref.apply_flip(c, ref.FLIP_ALL if kind == "all" else ref.FLIP_SITE, mv["sites"][w])
+            p = _p_ref(model, golden["delta_tau"], c, new, case, mv[kind], w)
+            seed = _seed_for_site(mv["sites"][w], n, 1000 * (w + 1)) if kind == "site" else 1000 * (w + 1)
+            u = ref.move_uniform(seed, 0, 1)
+            acc, _ = ref.decide(p, lambda: u)
+            tol = _p_tol(p, LOGDET_TOL_T8)
+            assert p > 1 + tol or abs(u - float(p)) > 2 * tol * abs(float(p)), "the decision hangs on rounding"
+            mc.set_conf(w, c)
+            mc.seed(w, seed)
+            expect.append(dict(p=p, acc=acc, conf=new if acc else c, tol=tol))
+        negative = sum(e["p"] < 0 for e in expect)
+        print("moves triangular8 %s: %d negative p of 4" % (kind, negative))
+        if kind == "site":
+            assert negative >= 1
+        mc.prepare()
+        mc.global_move(kind)
+        for w, e in enumerate(expect):
+            last, st = mc.global_last(w), mc.global_stats(w)
+            err = abs(float(mp.mpf(last["p"]) / e["p"] - 1))
+            print("  walker %d: p = %.6e, |p / p_ref - 1| = %.3e, bound %.3e" % (w, last["p"], err, e["tol"]))
+            assert err <= e["tol"]
+            if kind == "site":
+                assert last["site"] == mv["sites"][w]
+            assert last["accepted"] == e["acc"]
+            assert (st["prop_global"], st["acc_global"], st["moves_drawn"]) == (1, int(e["acc"]), 1)
+            assert np.array_equal(mc.conf(w), e["conf"]), w
+            a = mc.analysis(w)
+            assert (a.prop_global, a.acc_global) == (1, int(e["acc"]))
+            assert a.negative_probability.count == int(e["p"] < 0)
+    finally:
+        mc.close()
+
+
+# ---- 10. state after a move at 64 and 256 sites ------------------------------------------------------------------------------
+@pytest.mark.parametrize("kind", ["all", "site"])
+@pytest.mark.parametrize("where", ["triangular8", "square16_attractive"])
+def test_state_after_a_move_is_the_prepared_state_at_larger_sizes(gpu, golden, where, kind):
+    """test_state_after_a_move_is_the_prepared_state at TriangularLattice(8), U = 8, beta = 4 (n = 64) and at 16 x 16
+    attractive, beta = 1 (n = 256: the one-launch UDT and the slab kernels rebuild the stack), same bound TOL_G"""
+    case = golden["logdet"][where]
+    model = ref.golden_model(gpu, case)
+    kw = dict(n_walkers=4, beta=case["beta"], delta_tau=golden["delta_tau"], safe_mult=golden["safe_mult"], seed=77)
+    _state_after_a_move(gpu.DQMC(model, **kw), gpu.DQMC(model, **kw), kind)
+
+
+# ---- 11. FLIP_SITE over more than 256 slices ---------------------------------------------------------------------------------
+def test_flip_site_over_300_slices(gpu, golden):
+    """4 x 4 attractive, dtau = 0.01, beta = 3: gm_flip walks the 300 slices of a site in two turns of its 256 threads.
+    Host streams [site uniform][acceptance uniform]; walkers with p <= 1 alternate between u = (1 + p) / 2 (rejected)
+    and p / 2 (accepted).  The field afterwards is apply_flip's or the original, entry for entry; dS - twice the sum
+    over all 300 entries of the line - is in last_p, which is held to weight_ratio's value on the golden
+    log-determinants."""
+    mv = golden["moves"]["slices300"]
+    model = ref.golden_model(gpu, mv)
+    n, M, dtau = mv["n"], mv["slices"], mv["delta_tau"]
+    assert M > 256
+    mc = gpu.DQMC(model, n_walkers=4, beta=mv["beta"], delta_tau=dtau, safe_mult=golden["safe_mult"])
+    try:
+        assert mc.p.slices == M
+        expect, toggle = [], 0
+        for w, s in enumerate(mv["seeds"]):
+            c = ref.field(s, n, M)
+            new = ref.apply_flip(c, ref.FLIP_SITE, mv["sites"][w])
+            p = _p_ref(model, dtau, c, new, mv["cur"], mv["site"], w)
+            u = 0.25
+            if p <= 1:
+                u = (1 + float(p)) / 2 if toggle % 2 == 0 else float(p) / 2
+                toggle += 1
+            acc, drawn = ref.decide(p, lambda: u)
+            mc.set_conf(w, c)
+            mc.set_uniforms(w, np.array([(mv["sites"][w] + 0.5) / n, u, 0.5, 0.5]))
+            expect.append(dict(p=p, acc=acc, used=1 + int(drawn), conf=new if acc else c))
+        assert {e["acc"] for e in expect} == {True, False}
+        mc.prepare()
+        mc.global_move("site")
+        for w, e in enumerate(expect):
+            last = mc.global_last(w)
+            err, tol = abs(float(mp.mpf(last["p"]) / e["p"] - 1)), _p_tol(e["p"], LOGDET_TOL_300)
+            print("300 slices walker %d: p = %.6e, |p / p_ref - 1| = %.3e, bound %.3e" % (w, last["p"], err, tol))
+            assert err <= tol
+            assert (last["site"], last["accepted"]) == (mv["sites"][w], e["acc"])
+            assert np.array_equal(mc.conf(w), e["conf"]), w
+            assert mc.uniforms_used(w) == e["used"]
     finally:
         mc.close()
