@@ -476,9 +476,24 @@ int dqmc_calculate_greens(int32_t device_id, int32_t n, int32_t batch, const dou
  *   2 B' X  (multiply_daggered_slice_matrix_left!, :197-222)              5 X eT, 6 eTinv X (greens(), DQMC.jl:731-750)
  * Right products take the factors' transposes (rows of H' = columns of H).  After this call the propagation path
  * applies these sequences slab by slab in LDS instead of dense GEMMs with the multiplied-out constants (which
- * dqmc_create still needs: the unequal-time path uses them). */
+ * dqmc_create still needs: the unequal-time path uses them).
+ * The slab is 32 values of the index that is not mixed up to n_sites = 256, 16 up to 568 and 8 above: two images of
+ * n_sites x (width + 1) doubles and two scaling vectors must fit the 160 KiB of LDS of a compute unit, which 8 columns
+ * (160 n_sites bytes) do up to n_sites = 1024, the ceiling of dqmc_create.  A size that no width fits is refused with
+ * DQMC_ERR_INVALID before anything is allocated: the handle keeps the dense constants and stays usable. */
 int dqmc_set_checkerboard(dqmc_handle *h, int32_t kmax, int32_t n_mats, const double *vals, const int32_t *cols,
                           const double *mu, const double *mu_inv, const int32_t *seqs, const int32_t *lens);
+/* out = [1, kmax, slab width (32, 16 or 8), dynamic LDS bytes of a product] with a sparse checkerboard, else zeros */
+int dqmc_checkerboard_plan(dqmc_handle *h, int32_t out[4]);
+/* Diagnostic (like dqmc_vmul): exactly the launch the propagation path issues for sequence `which` (0..6, the order
+ * above) at HS slice `slice` (1..slices; ignored by sequences 5 and 6), for every unit of the handle, on device buffers
+ * of its own.  X and out are host arrays [n_walkers * n_blocks][n_sites][n_sites], column-major per unit.  qscale
+ * (NULL: none) is [n_walkers * n_blocks][n_sites] and multiplies the result along the index that is not mixed: columns
+ * for the left products (the D of a stabilisation step), rows for the right ones.  in_place != 0 hands the kernel one
+ * buffer as source and destination, as the wrap does.  No Monte-Carlo state is written.  DQMC_ERR_STATE without a
+ * sparse checkerboard, DQMC_ERR_INVALID for another `which` or a slice outside 1..slices for sequences 0..4. */
+int dqmc_checkerboard_apply(dqmc_handle *h, int32_t which, int32_t slice, const double *X, const double *qscale,
+                            int32_t in_place, double *out);
 
 /* The cooperative QR with the reference's pivot rule (n < 256, or 33..64 units at n = 256; 8 workgroups per matrix, bounded
  * hand-off spins) leaves its input intact; if a launch times out (CUs held by another stream for longer than the spins allow),

@@ -193,6 +193,8 @@ SIGNATURES = {
     "dqmc_calculate_greens": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "dqmc_set_checkerboard": (C.c_int, [_H, C.c_int32, C.c_int32, _dp, C.POINTER(C.c_int32), _dp, _dp,
                               C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "dqmc_checkerboard_plan": (C.c_int, [_H, C.POINTER(C.c_int32)]),
+    "dqmc_checkerboard_apply": (C.c_int, [_H, C.c_int32, C.c_int32, _dp, _dp, C.c_int32, _dp]),
     "dqmc_qr_fallbacks": (C.c_int, [_H, C.POINTER(C.c_int64)]),
     "dqmc_kron_hopping": (C.c_int, [_H, C.POINTER(C.c_int32)]),
     "dqmc_set_triangular_factors": (C.c_int, [_H, _dp]),

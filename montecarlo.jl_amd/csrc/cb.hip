@@ -4,8 +4,8 @@
 //
 // Every product is a short sequence of sparse factors (chkr_hop_half[g], chkr_hop[1], their inverses / adjoints,
 // stack.jl:185-235) plus diagonal scalings, all acting on ONE index k of X (rows for a left product, columns for a
-// right product).  A workgroup keeps a slab of 32 (n <= 256) or 16 values of the other index in LDS, applies the
-// whole sequence there (ping-pong between two images, one barrier per factor) and writes the slab back: X moves
+// right product).  A workgroup keeps a slab of 32 (n <= 256), 16 (n <= 568) or 8 values of the other index in LDS (the
+// widest of the three whose two images fit 160 KiB, cb_slab_width), applies the whole sequence there (ping-pong between two images, one barrier per factor) and writes the slab back: X moves
 // through HBM once per product instead of once per factor, and no n^3 work is done.
 #include "kernels.h"
 #include <hip/hip_ext.h>
@@ -22,8 +22,10 @@ __global__ __launch_bounds__(256) void cb_apply_kernel(CbArgs a)
     const int slabs = (n + QW - 1) / QW;
     const int unit = blockIdx.x / slabs, q0 = (blockIdx.x % slabs) * QW;
     const int w = unit / a.nb, blk = unit - w * a.nb;
-    const double *__restrict__ X = a.X + (long)unit * a.strideX;
-    double *__restrict__ O = a.O + (long)unit * a.strideX;
+    // (X and O may be the same buffer: the wrap multiplies in place.  A workgroup reads only the slab it writes, and
+    // all of it before the first store)
+    const double *X = a.X + (long)unit * a.strideX;
+    double *O = a.O + (long)unit * a.strideX;
     const int tid = threadIdx.x;
     // scale of the mixed index k: conf-derived exp(+-lambda s) and / or a stored vector (mu)
     auto kscale = [&](int conf_sign, const double *vec, int k) -> double {
@@ -122,22 +124,34 @@ __global__ __launch_bounds__(256) void cb_apply_kernel(CbArgs a)
     }
 }
 
+// two slab images of n x (qw + 1) doubles and the two scaling vectors: 544 n bytes at 32 columns, 288 n at 16 (n <= 568),
+// 160 n at 8 (n <= 1024, all of the CU's LDS); 0 when none fits
+int cb_slab_width(int n, size_t *lds_bytes)
+{
+    const int qw = n <= 256 ? 32 : n <= 568 ? 16 : 8;
+    const size_t lds = (2 * (size_t)n * (qw + 1) + 2 * (size_t)n) * sizeof(double);
+    if (lds_bytes) *lds_bytes = lds;
+    return n >= 1 && lds <= CB_LDS_MAX ? qw : 0;
+}
+
 hipError_t launch_cb_apply(const CbArgs &a, int n_units, hipStream_t s, hipEvent_t start, hipEvent_t stop)
 {
-    const int qw = a.n <= 256 ? 32 : 16;
-    const size_t lds = (2 * (size_t)a.n * (qw + 1) + 2 * (size_t)a.n) * sizeof(double);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    size_t lds = 0;
+    const int qw = cb_slab_width(a.n, &lds);
+    if (!qw) return hipErrorInvalidValue;  // (dqmc_set_checkerboard refuses such a size)
     int dev = 0;
     (void)hipGetDevice(&dev);
     static unsigned attr_mask = 0;
     if (!(attr_mask & (1u << dev))) {
         (void)hipFuncSetAttribute((const void *)cb_apply_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         (void)hipFuncSetAttribute((const void *)cb_apply_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute((const void *)cb_apply_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         attr_mask |= 1u << dev;
     }
     const int slabs = (a.n + qw - 1) / qw;
     if (qw == 32) hipExtLaunchKernelGGL(cb_apply_kernel<32>, dim3(n_units * slabs), dim3(256), lds, s, start, stop, 0, a);
-    else hipExtLaunchKernelGGL(cb_apply_kernel<16>, dim3(n_units * slabs), dim3(256), lds, s, start, stop, 0, a);
+    else if (qw == 16) hipExtLaunchKernelGGL(cb_apply_kernel<16>, dim3(n_units * slabs), dim3(256), lds, s, start, stop, 0, a);
+    else hipExtLaunchKernelGGL(cb_apply_kernel<8>, dim3(n_units * slabs), dim3(256), lds, s, start, stop, 0, a);
     return hipGetLastError();
 }
 

@@ -2138,6 +2138,11 @@ int dqmc_set_checkerboard(dqmc_handle *h, int32_t kmax, int32_t n_mats, const do
             if (seqs[q * 32 + i] < 0 || seqs[q * 32 + i] >= n_mats)
                 return fail(h, DQMC_ERR_INVALID, "dqmc_set_checkerboard: factor index out of range");
     }
+    // the slab kernel keeps two images of n x (width + 1) doubles in LDS; refused before anything is allocated or changed
+    if (!cb_slab_width(h->n, nullptr))
+        return fail(h, DQMC_ERR_INVALID, "dqmc_set_checkerboard: n_sites = " + std::to_string(h->n) + " is beyond the sparse form: its "
+                                         "narrowest slab (8 columns) needs 160 n bytes of the 163840 B of LDS, i.e. n_sites <= 1024; "
+                                         "the handle keeps the dense constants");
     HIPCHK(hipStreamSynchronize(h->stream));
     CHK(dalloc(h, &h->cb.vals, cnt));
     CHK(dalloc(h, &h->cb.cols, cnt));
@@ -2153,6 +2158,49 @@ int dqmc_set_checkerboard(dqmc_handle *h, int32_t kmax, int32_t n_mats, const do
         for (int i = 0; i < lens[q]; ++i) h->cb.seq[q][i] = seqs[q * 32 + i];
     }
     h->cb.on = true;
+    return DQMC_OK;
+}
+
+// [sparse on, kmax, slab width, dynamic LDS bytes] of the checkerboard products; zeros on the dense constants
+int dqmc_checkerboard_plan(dqmc_handle *h, int32_t out[4])
+{
+    if (!h || !out) return DQMC_ERR_INVALID;
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (!h->cb.on) return DQMC_OK;
+    size_t lds = 0;
+    out[0] = 1;
+    out[1] = h->cb.kmax;
+    out[2] = cb_slab_width(h->n, &lds);
+    out[3] = (int32_t)lds;
+    return DQMC_OK;
+}
+// diagnostic: one cb_mult of every unit on buffers of its own (no Monte-Carlo state is read but the HS field, none written)
+int dqmc_checkerboard_apply(dqmc_handle *h, int32_t which, int32_t slice, const double *X, const double *qscale,
+                            int32_t in_place, double *out)
+{
+    ENTER(h);
+    if (!h->cb.on) return fail(h, DQMC_ERR_STATE, "dqmc_checkerboard_apply: the handle has no sparse checkerboard");
+    if (!X || !out) return fail(h, DQMC_ERR_INVALID, "dqmc_checkerboard_apply: null matrix");
+    if (which < CB_LEFT_B || which > CB_LEFT_ETINV) return fail(h, DQMC_ERR_INVALID, "dqmc_checkerboard_apply: which must be 0..6");
+    const bool conf_scaled = which <= CB_RIGHT_BINV;  // (the two greens() sandwiches take no slice)
+    if (conf_scaled && (slice < 1 || slice > h->M)) return fail(h, DQMC_ERR_INVALID, "dqmc_checkerboard_apply: slice out of range");
+    const size_t cnt = (size_t)h->units * h->nn, qcnt = (size_t)h->units * h->n;
+    struct Bufs {
+        double *x = nullptr, *o = nullptr, *q = nullptr;
+        ~Bufs() { (void)hipFree(x); (void)hipFree(o); (void)hipFree(q); }
+    } b;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMalloc((void **)&b.x, cnt * sizeof(double)));
+    if (!in_place) HIPCHK(hipMalloc((void **)&b.o, cnt * sizeof(double)));
+    HIPCHK(hipMemcpy(b.x, X, cnt * sizeof(double), hipMemcpyHostToDevice));
+    if (qscale) {
+        HIPCHK(hipMalloc((void **)&b.q, qcnt * sizeof(double)));
+        HIPCHK(hipMemcpy(b.q, qscale, qcnt * sizeof(double), hipMemcpyHostToDevice));
+    }
+    double *dst = in_place ? b.x : b.o;
+    CHK(cb_mult(h, which, conf_scaled ? slice : 0, b.x, dst, b.q));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(out, dst, cnt * sizeof(double), hipMemcpyDeviceToHost));
     return DQMC_OK;
 }
 

@@ -349,6 +349,10 @@ struct CbArgs {
 };
 hipError_t launch_cb_apply(const CbArgs &a, int n_units, hipStream_t s, hipEvent_t start = nullptr,
                            hipEvent_t stop = nullptr);
+// slab width (32, 16 or 8 values of the index that is not mixed) cb_apply_kernel takes at n, and its dynamic LDS bytes;
+// 0 when not even 8 columns fit CB_LDS_MAX
+constexpr size_t CB_LDS_MAX = 160 * 1024;
+int cb_slab_width(int n, size_t *lds_bytes);
 
 // small helpers
 hipError_t launch_set_identity(int n, int count, double *A, long stride, hipStream_t s);

@@ -196,6 +196,18 @@ def checkerboard_seqs(tables):
     return seqs, lens
 
 
+def checkerboard_slab(n):
+    """(slab width, dynamic LDS bytes) of the sparse-factor kernel at n sites, as dqmc_checkerboard_plan reports them: two
+    images of n x (width + 1) doubles and two scaling vectors in the 160 KiB of LDS; 32 columns up to n = 256, 16 up to
+    568, 8 up to 1024.  Beyond that no width fits and dqmc_set_checkerboard refuses the tables."""
+    qw = 32 if n <= 256 else 16 if n <= 568 else 8
+    lds = (2 * n * (qw + 1) + 2 * n) * 8
+    if n < 1 or lds > 160 * 1024:
+        raise ValueError("sparse checkerboard: %d sites are beyond the slab kernel (8 columns need 160 n bytes of 163840 B of "
+                         "LDS: n <= 1024); use checkerboard=\"dense\"" % n)
+    return qw, lds
+
+
 class DQMCAnalysis:
     """DQMC.jl:36-47 for one walker"""
 
@@ -255,9 +267,10 @@ class DQMC:
         # checkerboard=True picks the faster execution of the same decomposition: measured on MI355X (config 3 shape,
         # tools/time_parts.py checkerboard) the sparse-factor kernel takes 32.5 us per product against 31.2 us for the dense
         # MFMA GEMM with the multiplied-out constants at n = 256, so dense up to n = 256 and sparse (O(n^2) work per
-        # product) above; checkerboard="sparse" / "dense" force one
+        # product) above; checkerboard="sparse" / "dense" force one.  The cross-over was measured at n = 256 only.
         sparse = checkerboard == "sparse" or (checkerboard is True and self.N > 256)
         if self.checkerboard and sparse:
+            checkerboard_slab(self.N)  # ValueError where no slab width fits (the engine refuses such tables as well)
             tb = [checkerboard_tables(T, model.l, self.p.delta_tau) for T in Ts]
             t0 = tb[0]  # both spin blocks of the repulsive model share T (HubbardModelRepulsive.jl:87-100)
             seqs, lens = checkerboard_seqs(t0)
@@ -487,6 +500,32 @@ class DQMC:
 
     def wrap_greens(self, slice_, direction):
         self._c(lib().dqmc_wrap_greens(self._h, slice_, direction))
+
+    # ---- sparse checkerboard products (diagnostics)
+    def checkerboard_plan(self):
+        """dqmc_checkerboard_plan: dict(sparse, kmax, slab_width, lds_bytes); zeros on the dense constants"""
+        out = (C.c_int32 * 4)()
+        self._c(lib().dqmc_checkerboard_plan(self._h, out))
+        return dict(sparse=int(out[0]), kmax=int(out[1]), slab_width=int(out[2]), lds_bytes=int(out[3]))
+
+    def checkerboard_apply(self, which, slice_, X, qscale=None, in_place=False):
+        """dqmc_checkerboard_apply: sequence `which` (0 B X, 1 B^-1 X, 2 B' X, 3 X B, 4 X B^-1, 5 X eT, 6 eTinv X) at HS
+        slice `slice_` on X [n_walkers * n_blocks, n, n] (unit = walker * n_blocks + block), with the launch the
+        propagation issues; qscale [units, n] scales the index that is not mixed; in_place: source = destination"""
+        units, n = self.n_walkers * self.nb, self.N
+        X = np.asarray(X, dtype=np.float64)
+        if X.shape != (units, n, n):
+            raise ValueError("X must have shape (n_walkers * n_blocks, n_sites, n_sites)")
+        x = _pack(X)
+        q = None
+        if qscale is not None:
+            q = np.ascontiguousarray(qscale, dtype=np.float64)
+            if q.shape != (units, n):
+                raise ValueError("qscale must have shape (n_walkers * n_blocks, n_sites)")
+        out = np.zeros_like(x)
+        self._c(lib().dqmc_checkerboard_apply(self._h, int(which), int(slice_), dptr(x), dptr(q) if q is not None else None,
+                                              int(bool(in_place)), dptr(out)))
+        return _unpack(out, units, n)
 
     # ---- global moves (include/dqmc_hip.h "global moves")
     @staticmethod
