@@ -521,6 +521,18 @@ int dqmc_set_triangular_factors(dqmc_handle *h, const double *f);
  * bit 0 add_slice_sequence_left/right (stack.jl:272-311) and other callers, bit 1 / bit 2 the two factorisations of
  * calculate_greens_AVX! (stack.jl:349, :376); 0 = the reference's pivot rule everywhere (n != 256, > 32 units, DQMC_QR_NOBLOCKED) */
 int dqmc_udt_one_launch_sites(dqmc_handle *h, int32_t *mask);
+/* Read-only diagnostic: which of the launch forms that need co-resident workgroups this handle took when it was set up,
+ * from the variables the launchers themselves read; nothing is launched.  A unit is one walker x one block; the block maps
+ * launch whole groups of eight units.
+ *   out[0]  units                                   out[1]  units in whole groups of eight
+ *   out[2]  compute units of the device             out[3]  dqmc_udt_one_launch_sites
+ *   out[4]  workgroups the one-launch UDT may use (compute units x occupancy; 0: not admitted, or n_sites != 256)
+ *   out[5]  workgroups the cooperative QR may use   out[6]  1: the cooperative QR is admitted for out[0] units
+ *           (n_sites <= 256; it runs at the call sites out[3] leaves to it), 0: single-workgroup QR kernels
+ *   out[7]  1: site sweep with the fused chunk loop (elimination beside the previous chunk's flush), 0: launch per chunk
+ *   out[8], out[9]    workgroups the one-launch factored wrap may use without / with a pending sweep chunk
+ *   out[10], out[11]  1: the factored wrap is one launch without / with a pending chunk, 0: two launches (or no factored wrap) */
+int dqmc_launch_plan(dqmc_handle *h, int32_t out[12]);
 /* device error word as it stands (0 = no bounded wait inside a kernel has run out); no reference counterpart: the reference
  * has no concurrent workgroups (diagnostic next to DQMCAnalysis, src/flavors/DQMC/DQMC.jl:35-47) */
 int dqmc_device_errors(dqmc_handle *h, int32_t *word);

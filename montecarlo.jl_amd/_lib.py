@@ -200,6 +200,7 @@ SIGNATURES = {
     "dqmc_set_triangular_factors": (C.c_int, [_H, _dp]),
     "dqmc_device_errors": (C.c_int, [_H, C.POINTER(C.c_int32)]),
     "dqmc_udt_one_launch_sites": (C.c_int, [_H, C.POINTER(C.c_int32)]),
+    "dqmc_launch_plan": (C.c_int, [_H, C.POINTER(C.c_int32)]),
     "dqmc_build_commit": (C.c_char_p, []),
     "dqmc_build_source_hash": (C.c_char_p, []),
     "dqmc_get_global_last": (C.c_int, [_H, C.c_int32, _dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),

@@ -74,6 +74,7 @@ struct dqmc_handle {
     hipStream_t cur = nullptr;  // the stream the launch helpers use (= stream)
     double *greens_alt = nullptr, *lu_img = nullptr;  // decide / apply sweep (sweep_lu.hip)
     bool sweep_fused = true;
+    int cus = 0;  // compute units of the device: what the admission rules of the co-resident launch forms count against
     // the last chunk of the latest sweep_spatial, eliminated but not applied to greens (fold_wrap_flush): the next factored
     // wrap of greens applies it, materialize_pending_flush() everywhere else
     struct PendingFlush {
@@ -472,6 +473,18 @@ static void read_kernel_switches(dqmc_handle *h)
     k.tdm_general = getenv("DQMC_TDM_GENERAL") != nullptr;
 }
 
+// units in whole groups of eight: the XCD block maps launch workgroups for the padded units too, and they take CUs
+static int padded_units(const dqmc_handle *h) { return (h->units + 7) / 8 * 8; }
+// the one-launch UDT (qrb.hip): eight workgroups per unit, all of them co-resident
+static bool udt_blocked_fits(const dqmc_handle *h, int per_cu) { return per_cu >= 1 && padded_units(h) * 8 <= h->cus * per_cu; }
+// the fused chunk loop of the site sweep: one elimination workgroup per walker beside the flush workgroups, one per CU
+static bool sweep_fused_fits(const dqmc_handle *h)
+{
+    const int ncp = (h->n % 256 == 0) ? 2 : 1, nt = (h->n % 128 == 0) ? 8 : 4;
+    const int flush_blocks = padded_units(h) * (h->n / 64) * (h->n / (16 * nt * ncp));
+    return h->W + flush_blocks <= h->cus;
+}
+
 static int alloc_qr_workspace(dqmc_handle *h)
 {
     // device-side error word (bit 1: a hand-off inside the sweep elimination kernel timed out; bit 0 is no longer set by
@@ -486,11 +499,12 @@ static int alloc_qr_workspace(dqmc_handle *h)
     if (h->n > 256) return 0;
     hipDeviceProp_t prop;
     HIPCHK(hipGetDeviceProperties(&prop, h->p.device_id));
+    h->cus = prop.multiProcessorCount;
     const size_t slots = (size_t)((h->units + 7) / 8) * 8 * QR_COOP_SLOTS_PER_UNIT;
     CHK(dalloc(h, &h->qr_ws.mailbox, slots * QR_COOP_SLOT));
     CHK(dalloc(h, &h->qr_ws.fb, (size_t)2));
     // co-residency: what the occupancy API reports for the kernel on this device (its ~200 VGPRs admit 2 per CU)
-    h->qr_ws.max_blocks = prop.multiProcessorCount * qr_coop_blocks_per_cu();
+    h->qr_ws.max_blocks = h->cus * qr_coop_blocks_per_cu();
     h->qr_ws.epoch = 0;
     // pre-pivoted blocked UDT in one launch (qrb.hip): n == 256, all eight workgroups of every unit co-resident.
     // DQMC_QR_NOBLOCKED: off; DQMC_QRB_SITES: bit mask of the call sites that use it (1 = slice-sequence builds and every other
@@ -498,9 +512,9 @@ static int alloc_qr_workspace(dqmc_handle *h)
     h->qrb_sites = 0;
     if (h->n == 256 && !h->sw.qr_noblocked) {
         const int per_cu = qrb_blocks_per_cu();
-        if (per_cu >= 1 && ((h->units + 7) / 8) * 64 <= prop.multiProcessorCount * per_cu) {
+        if (udt_blocked_fits(h, per_cu)) {
             CHK(dalloc(h, (char **)&h->qr_ws.mailbox2, qrb_mailbox_bytes(h->units)));
-            h->qr_ws.blk_max_blocks = prop.multiProcessorCount * per_cu;
+            h->qr_ws.blk_max_blocks = h->cus * per_cu;
             h->qrb_sites = h->sw.qrb_sites;
         }
     }
@@ -517,9 +531,15 @@ static int alloc_wrap_handoff(dqmc_handle *h)
     if (!h->kron || h->n != 256 || h->sw.wrap_two_launch) return 0;
     hipDeviceProp_t prop;
     HIPCHK(hipGetDeviceProperties(&prop, h->p.device_id));
-    for (int pf = 0; pf < 2; ++pf) h->wrap_blocks[pf] = prop.multiProcessorCount * kron_wrap_blocks_per_cu(pf != 0);
+    h->cus = prop.multiProcessorCount;
+    for (int pf = 0; pf < 2; ++pf) h->wrap_blocks[pf] = h->cus * kron_wrap_blocks_per_cu(pf != 0);
     if (kron_wrap_grid(h->units) > std::max(h->wrap_blocks[0], h->wrap_blocks[1])) return 0;
     return dalloc(h, &h->wrap_cnt, (size_t)kron_wrap_grid(h->units) / 16 * KR_CNT_STRIDE);
+}
+// whether wrap_greens_kron takes the one-launch form, with / without a pending chunk
+static bool wrap_one_launch(const dqmc_handle *h, bool pending)
+{
+    return h->wrap_cnt && h->n == 256 && !h->tri && kron_wrap_grid(h->units) <= h->wrap_blocks[pending ? 1 : 0];
 }
 static int check_qr_workspace(dqmc_handle *h)
 {
@@ -892,7 +912,7 @@ static int wrap_greens_kron(dqmc_handle *h, const double *src, double *dst, int 
     KronStep &s1 = kron_step(h, a, direction == -1 ? KF_ETINV2 : KF_ET2);
     if (direction == -1) { s1.post_conf = c; s1.post_sign = -1; }
     else { s1.pre_conf = c; s1.pre_sign = +1; }
-    if (h->wrap_cnt && h->n == 256 && !h->tri && kron_wrap_grid(h->units) <= h->wrap_blocks[a.pf_img ? 1 : 0]) {
+    if (wrap_one_launch(h, a.pf_img != nullptr)) {
         KronStep &s2 = kron_step(h, a, direction == -1 ? KF_ET2T : KF_ETINV2T);
         if (direction == -1) { s2.post_conf = c; s2.post_sign = +1; }
         else { s2.pre_conf = c; s2.pre_sign = -1; }
@@ -1099,6 +1119,8 @@ static int propagate(dqmc_handle *h)
 
 // DQMC.jl:546-582
 static int sweep_spatial_launches(dqmc_handle *h);
+// the fused chunk loop runs where the handle admitted it (dqmc_create) and the chunks are whole
+static bool sweep_takes_fused(const dqmc_handle *h) { return h->sweep_fused && h->n % 64 == 0 && h->N >= 128; }
 static int sweep_spatial(dqmc_handle *h)
 {
     const int l = h->current_slice;
@@ -1118,7 +1140,7 @@ static int sweep_spatial_launches(dqmc_handle *h)
 
     const long cstr = (long)h->N * h->M;
     hipEvent_t a, b;
-    if (h->sweep_fused && h->n % 64 == 0 && h->N >= 128) {
+    if (sweep_takes_fused(h)) {
         // the elimination of chunk c runs beside the flush of chunk c - 1 (one launch per chunk boundary)
         const int nc = h->N / 64;
         timing_events(h, &a, &b);
@@ -1215,14 +1237,11 @@ int dqmc_create(const dqmc_params *p, dqmc_handle **out)
     // With more units than that the phase is throughput-bound and the separate launches win (config 4 on one GPU,
     // 512 units: 688 vs 715 ms per sweep), so the fused form is used only when its grid fits the CUs.
     h->sweep_fused = false;
-    if (!h->sw.sweep_split && h->n % 64 == 0) {
+    {
         hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, p->device_id) == hipSuccess) {
-            const int ncp = (h->n % 256 == 0) ? 2 : 1, nt = (h->n % 128 == 0) ? 8 : 4;
-            const int flush_blocks = ((h->units + 7) / 8) * 8 * (h->n / 64) * (h->n / (16 * nt * ncp));
-            h->sweep_fused = h->W + flush_blocks <= prop.multiProcessorCount;
-        }
+        if (hipGetDeviceProperties(&prop, p->device_id) == hipSuccess) h->cus = prop.multiProcessorCount;
     }
+    if (!h->sw.sweep_split && h->n % 64 == 0 && h->cus) h->sweep_fused = sweep_fused_fits(h);
     // lambda = acosh(exp(U*dtau/2)) (Attractive.jl:103,118; Repulsive.jl:116,138)
     h->lambda = std::acosh(std::exp(0.5 * p->U * p->delta_tau));
     h->epl = std::exp(h->lambda);
@@ -2214,6 +2233,27 @@ int dqmc_device_errors(dqmc_handle *h, int32_t *word)
     if (!h->qr_ws.errflag) return DQMC_OK;
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipMemcpy(word, h->qr_ws.errflag, sizeof(int), hipMemcpyDeviceToHost));
+    return DQMC_OK;
+}
+// what the handle decided about its co-resident launch forms when it was set up (nothing is launched): [units, units in
+// whole groups of eight, CUs, one-launch UDT call sites, workgroups the one-launch UDT may use (0: not admitted), workgroups
+// the cooperative QR may use, cooperative QR admitted for these units, fused chunk loop, workgroups the one-launch wrap may
+// use without / with a pending chunk, one-launch wrap admitted without / with a pending chunk]
+int dqmc_launch_plan(dqmc_handle *h, int32_t out[12])
+{
+    if (!h || !out) return DQMC_ERR_INVALID;
+    out[0] = h->units;
+    out[1] = padded_units(h);
+    out[2] = h->cus;
+    out[3] = h->qrb_sites;
+    out[4] = h->qr_ws.blk_max_blocks;
+    out[5] = h->qr_ws.max_blocks;
+    out[6] = qr_coop_grid(h->n, h->units, &h->qr_ws) != 0;
+    out[7] = sweep_takes_fused(h);
+    for (int pf = 0; pf < 2; ++pf) {
+        out[8 + pf] = h->wrap_blocks[pf];
+        out[10 + pf] = wrap_one_launch(h, pf != 0);
+    }
     return DQMC_OK;
 }
 // which call sites of udt_AVX_pivot! take the one-launch pre-pivoted form (bit 0: slice-sequence builds and every other caller,

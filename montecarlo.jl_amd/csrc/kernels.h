@@ -202,6 +202,8 @@ hipError_t launch_qr_pivot(int n, int n_units, double *A, long strideA, double *
                            QrCoopWorkspace *ws, double *W, long strideW, const double **factored, hipStream_t s,
                            double *X = nullptr, long strideX = 0);
 int qr_coop_blocks_per_cu();
+// grid of the cooperative kernel for n_units matrices, 0 where launch_qr_pivot takes a single-workgroup kernel instead
+int qr_coop_grid(int n, int n_units, const QrCoopWorkspace *ws);
 
 // After launch_qr_pivot: D = |diag R| (UDT.jl:268-272); V = unit-lower Householder
 // vectors (n x n, explicit zeros/ones); T = D^-1 R:

@@ -1785,19 +1785,28 @@ static hipError_t launch_qr_single(int n, int n_units, double *A, long strideA, 
     return hipGetLastError();
 }
 
+// Workgroups of the cooperative kernel for n_units matrices (8 per matrix, units in whole groups of eight), or 0 where
+// launch_qr_pivot does not take it: all 8 workgroups of every unit must be co-resident (they wait for each other), so the
+// grid is admitted only if it fits the occupancy the runtime reports for this kernel (ws->max_blocks)
+int qr_coop_grid(int n, int n_units, const QrCoopWorkspace *ws)
+{
+    if (!ws || !ws->mailbox || n > 256 || ws->no_coop) return 0;
+    const int groups = (n_units + 7) / 8;
+    const int blocks = groups * 8 * QC_PARTS;
+    return blocks <= ws->max_blocks ? blocks : 0;
+}
+
 // *factored: where the factored matrix is (W for the cooperative kernel, which leaves A untouched; else A, in place)
 hipError_t launch_qr_pivot(int n, int n_units, double *A, long strideA, double *tau, int *pivot, QrCoopWorkspace *ws,
                            double *W, long strideW, const double **factored, hipStream_t s, double *X, long strideX)
 {
     if (n > 1024) return hipErrorInvalidValue;
     *factored = A;
-    // cooperative kernel: all 8 workgroups of every unit must be co-resident (they wait for each other); the grid is
-    // admitted only if it fits the occupancy the runtime reports for this kernel.  Should another stream hold CUs
-    // for longer than the bounded spins allow, the launch gives up and the guarded kernel behind it takes over.
-    if (ws && ws->mailbox && W && n <= 256 && !ws->no_coop) {
-        const int groups = (n_units + 7) / 8;
-        const int blocks = groups * 8 * QC_PARTS;
-        if (blocks <= ws->max_blocks) {
+    // cooperative kernel where its grid is admitted (qr_coop_grid).  Should another stream hold CUs for longer than the
+    // bounded spins allow, the launch gives up and the guarded kernel behind it takes over.
+    if (W) {
+        const int blocks = qr_coop_grid(n, n_units, ws);
+        if (blocks) {
             ws->epoch += 1;
             const int force_sc1 = ws->force_sc1, force_to = ws->force_timeout;
             // n == 256: the first 128 steps cooperatively, the rest on one CU per matrix (qr_tail_kernel)

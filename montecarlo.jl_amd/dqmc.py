@@ -1057,6 +1057,19 @@ class DQMC:
         self._c(lib().dqmc_udt_one_launch_sites(self._h, C.byref(w)))
         return int(w.value)
 
+    def launch_plan(self):
+        """dqmc_launch_plan: what the handle decided about its co-resident launch forms at creation, as a dict: units,
+        units_padded, cus, udt_sites, udt_blocks (0: one-launch UDT not admitted), qr_coop_blocks, qr_coop (1 / 0),
+        sweep_fused (1 / 0), wrap_blocks and wrap_one_launch (each a pair: without / with a pending sweep chunk)"""
+        out = (C.c_int32 * 12)()
+        self._c(lib().dqmc_launch_plan(self._h, out))
+        v = [int(x) for x in out]
+        names = ("units", "units_padded", "cus", "udt_sites", "udt_blocks", "qr_coop_blocks", "qr_coop", "sweep_fused")
+        plan = dict(zip(names, v))
+        plan["wrap_blocks"] = (v[8], v[9])
+        plan["wrap_one_launch"] = (v[10], v[11])
+        return plan
+
     def device_errors(self):
         """device error word (0 unless a bounded wait inside a kernel ran out)"""
         w = C.c_int32(0)

@@ -242,6 +242,102 @@ def test_calculate_greens_AVX(gpu, O, n):
     print("n = %d: worst rel |G - G_oracle| = %.3g" % (n, worst))
 
 
+@pytest.mark.parametrize("batch", [9, 33])
+def test_rdivp_partial_later_group(gpu, O, batch):
+    """n = 256 with units that end inside a later group of eight (trsm_rl_kernel's block map pads them to whole groups):
+    every unit against the oracle, and the residual Out triu(T) = A[:, pivot] in every entry, scaled by the column norms,
+    within the bound of test_rdivp_n_above_256.  Every unit has its own T and pivot, so a unit served another unit's
+    operands fails."""
+    n = 256
+    rng = np.random.default_rng(1000 + batch)
+    Ts, pivs = [], []
+    for i in range(batch):
+        _, _, T, piv = O.udt_pivot(rng.standard_normal((n, n)), False)
+        assert not np.array_equal(piv, np.arange(1, n + 1))
+        Ts.append(T)
+        pivs.append(piv)
+    A = rng.standard_normal((batch, n, n))
+    A[batch - 1] *= np.exp(rng.uniform(-10, 10, size=n))[:, None]   # graded rows in the last unit
+    out = gpu.rdivp(A, np.stack(Ts), np.stack(pivs))
+    worst = 0.0
+    for i in range(batch):
+        assert relerr(out[i], O.rdivp(A[i], Ts[i], pivs[i])) < 1e-10, i
+        Ap = A[i][:, pivs[i] - 1]
+        res = np.abs(out[i] @ np.triu(Ts[i]) - Ap) / np.linalg.norm(Ap, axis=0)[None, :]
+        worst = max(worst, res.max())
+        assert res.max() < 1e-12, (i, res.max())
+    print("rdivp, n = 256, batch %d: worst scaled residual %.3g" % (batch, worst))
+
+
+@pytest.mark.parametrize("batch", [9, 33])
+def test_calculate_greens_AVX_partial_later_group(gpu, O, batch):
+    """n = 256 with a partial later group of eight units: every unit against the oracle (1e-10) and a direct inverse (1e-8),
+    as test_calculate_greens_AVX"""
+    n = 256
+    rng = np.random.default_rng(2000 + batch)
+    args = []
+    for _ in range(batch):
+        Ul, _ = np.linalg.qr(rng.standard_normal((n, n)))
+        Ur, _ = np.linalg.qr(rng.standard_normal((n, n)))
+        Dl = np.sort(np.exp(rng.uniform(-3, 3, n)))[::-1]
+        Dr = np.sort(np.exp(rng.uniform(-3, 3, n)))[::-1]
+        Tl = np.eye(n) + 0.1 * rng.standard_normal((n, n))
+        Tr = np.eye(n) + 0.1 * rng.standard_normal((n, n))
+        args.append((Ul, Dl, Tl, Ur, Dr, Tr))
+    stack = lambda k: np.stack([a[k] for a in args])
+    G = gpu.calculate_greens_AVX(stack(0), stack(1), stack(2), stack(3), stack(4), stack(5))
+    worst = 0.0
+    for i, a in enumerate(args):
+        e = relerr(G[i], O.calculate_greens(*a))
+        worst = max(worst, e)
+        assert e < TOL, (i, e)
+        Ul, Dl, Tl, Ur, Dr, Tr = a
+        direct = np.linalg.inv(np.eye(n) + (Ul * Dl) @ Tl @ ((Ur * Dr) @ Tr).T)
+        assert relerr(G[i], direct) < 1e-8, i
+    print("n = 256, batch %d: worst rel |G - G_oracle| = %.3g" % (batch, worst))
+
+
+@pytest.mark.parametrize("batch", [33, 64, 65])
+@pytest.mark.parametrize("apply_pivot", [True, False])
+def test_udt_natural_dispatch_at_the_qr_edges(gpu, O, batch, apply_pivot):
+    """n = 256 with no switch set, either side of the two limits of the pivoted factorisation (on 256 CUs: 33 units are the
+    first past the one-launch UDT, 64 the last the cooperative QR admits, 65 take the tile kernel and qr_tail_kernel): the
+    contracts of test_udt_contracts for every unit, and units 0, the first of the last group of eight and the last against
+    the oracle run under the pivot rule of the form that the admission rules select.  The last unit has graded columns."""
+    import launch_rules as R
+    n = 256
+    caps = R.capacities(gpu)
+    presorted = R.udt_one_launch(n, batch, caps)
+    print("batch %d: %s" % (batch, "one-launch UDT" if presorted else
+                            ("cooperative QR" if R.qr_coop(n, batch, caps) else "tile QR + tail")))
+    rng = np.random.default_rng(3000 + batch)
+    X = rng.standard_normal((batch, n, n))
+    X[batch - 1] *= np.exp(rng.uniform(-20, 20, size=n))[None, :]
+    U, D, T, piv = gpu.udt_AVX_pivot(X, apply_pivot)
+    for i in range(batch):
+        assert relerr(U[i].T @ U[i], np.eye(n)) < 1e-12, i
+        assert np.all(D[i] > 0)
+        if not presorted:
+            assert np.all(np.diff(D[i]) <= 1e-12 * D[i][:-1])
+        assert sorted(piv[i]) == list(range(1, n + 1))
+        if apply_pivot:
+            rec = (U[i] * D[i]) @ T[i]
+        else:
+            P = np.zeros((n, n)); P[np.arange(n), piv[i] - 1] = 1
+            rec = (U[i] * D[i]) @ np.triu(T[i]) @ P
+        scale = np.abs(X[i]).max(axis=0)
+        assert (np.abs(rec - X[i]) / scale[None, :]).max() < 1e-12, i
+    O.lib().orc_set_udt_presort(1 if presorted else 0)
+    try:
+        for i in sorted({0, 8 * ((batch - 1) // 8), batch - 1}):
+            Uo, Do, To, po = O.udt_pivot(X[i], apply_pivot)
+            assert np.array_equal(po, piv[i]), "unit %d: pivots differ from the oracle's" % i
+            assert relerr(D[i], Do) < 1e-10
+            assert relerr(U[i], Uo) < 1e-9
+    finally:
+        O.lib().orc_set_udt_presort(0)
+
+
 def test_mfma_peak_probe(gpu):
     tf = gpu.mfma_f64_peak(20000)
     print("fp64 MFMA probe: %.1f TFLOP/s" % tf)
