@@ -9,17 +9,16 @@ static const int64_t BIN_DEFAULT_CAPACITY = 100000;  // BinningAnalysis' _defaul
         return fail((h), DQMC_ERR_INVALID, "binner section out of range");                      \
     if (!(h)->bin[(which)].on) return fail((h), DQMC_ERR_STATE, "this section's binner is not enabled")
 
+// DQMC_BIN_* numbers the measurement sections as DQMC_RED_* does (dqmc_handle::sec), except that DQMC_BIN_USER = 4, which
+// has no accumulator, sits in front of DQMC_BIN_TIME_DISPLACED = 5 (DQMC_RED_TIME_DISPLACED = 4)
+static const dqmc_handle::Section &binner_section(dqmc_handle *h, int which)
+{
+    return h->sec[which == DQMC_BIN_TIME_DISPLACED ? DQMC_RED_TIME_DISPLACED : which];
+}
 // elements of a section as its measurement is configured now (0: not configured)
 static long binner_section_elements(dqmc_handle *h, int which)
 {
-    switch (which) {
-    case DQMC_BIN_GREENS: return (long)h->nb * h->nn + (long)h->nb * h->n;
-    case DQMC_BIN_CORRELATIONS: return h->n_dirs ? (long)h->corr_n - 1 : 0;
-    case DQMC_BIN_PAIRING: return h->K_loc ? (long)h->pc_n - 1 : 0;
-    case DQMC_BIN_SUSCEPTIBILITIES: return h->ut && h->ut->sus_n ? (long)h->ut->sus_n - 1 : 0;
-    case DQMC_BIN_TIME_DISPLACED: return h->td.every ? (long)h->td.E : 0;
-    default: return h->bin[DQMC_BIN_USER].E;
-    }
+    return which == DQMC_BIN_USER ? h->bin[DQMC_BIN_USER].E : binner_section(h, which).bin_E;
 }
 static int binner_levels(int64_t capacity)  // ceil(log2(capacity + 1))
 {
@@ -29,13 +28,7 @@ static int binner_levels(int64_t capacity)  // ceil(log2(capacity + 1))
 }
 static void binner_free(dqmc_handle *h, dqmc_handle::Binner &b)
 {
-    for (double **p : {&b.xs, &b.x2, &b.c, &b.out}) {
-        if (!*p) continue;
-        auto it = std::find(h->allocs.begin(), h->allocs.end(), (void *)*p);
-        if (it != h->allocs.end()) h->allocs.erase(it);
-        (void)hipFree(*p);
-        *p = nullptr;
-    }
+    for (double **p : {&b.xs, &b.x2, &b.c, &b.out}) dfree(h, p);
     b = dqmc_handle::Binner{};
 }
 static int binner_alloc(dqmc_handle *h, int which, long E, int64_t capacity)
@@ -93,13 +86,10 @@ static int binner_push_section(dqmc_handle *h, int which)
     p.nb = h->nb;
     p.model = h->p.model_kind;
     p.n_dirs = h->n_dirs;
-    switch (which) {
-    case DQMC_BIN_GREENS: p.mode = BIN_SRC_GREENS; break;
-    case DQMC_BIN_CORRELATIONS: p.mode = BIN_SRC_CORR; p.src = h->corr_per_walker; break;
-    case DQMC_BIN_PAIRING: p.src = h->pc_per_walker; break;
-    case DQMC_BIN_TIME_DISPLACED: p.src = h->td.per_walker; break;  // rows as tdm.hip stored them: no delta_tau
-    default: p.src = h->ut->sus_per_walker; p.scale = h->p.delta_tau; break;  // finish!: * delta_tau as sus_reduce_kernel
-    }
+    p.mode = binner_section(h, which).bin_mode;
+    p.src = binner_section(h, which).per_walker;
+    // finish!: * delta_tau as sus_reduce_kernel (the time-displaced rows go as tdm.hip stored them)
+    if (which == DQMC_BIN_SUSCEPTIBILITIES) p.scale = h->p.delta_tau;
     return binner_push(h, which, p);
 }
 static int binner_reset(dqmc_handle *h)

@@ -67,11 +67,8 @@ struct dqmc_handle {
     struct QrSet {
         double *V = nullptr, *W = nullptr, *S = nullptr, *tau = nullptr, *winv = nullptr, *ts = nullptr;
         int *pivot = nullptr;
-    } qs[1];
-    double *&qrV = qs[0].V, *&qrW = qs[0].W, *&qrS = qs[0].S, *&trsm_w = qs[0].winv, *&trsm_s = qs[0].ts, *&tau = qs[0].tau;
-    int *&pivot = qs[0].pivot;
+    } qs;
     double *Dl = nullptr, *Dr = nullptr;
-    hipStream_t cur = nullptr;  // the stream the launch helpers use (= stream)
     double *greens_alt = nullptr, *lu_img = nullptr;  // decide / apply sweep (sweep_lu.hip)
     bool sweep_fused = true;
     int cus = 0;  // compute units of the device: what the admission rules of the co-resident launch forms count against
@@ -91,21 +88,31 @@ struct dqmc_handle {
     DevStats *stats = nullptr;
     unsigned long long *pc_scratch = nullptr;  // prop_check_kernel: partial maximum + arrival counter per walker
     std::vector<double *> uniforms;  // per walker device arrays
-    double *acc = nullptr;
-    size_t acc_n = 0;
+    // The accumulators, one entry per DQMC_RED_* section: the only list of them.  An entry is filled where the section's
+    // layout is (re)built (sec_layout: dqmc_create, dqmc_set_pair_directions, dqmc_set_local_targets, ut_sus_layout,
+    // td_setup / td_free); the reset, the packed reduction, the binners and the size / get / export entry points read it.
+    // A regular entry: acc = [n - 1 sums][sample count], all of it packed (n_red = n), and the binner sees the n - 1
+    // sums of one walker's sample (bin_E), which the measurement kernels leave in per_walker.  The irregular ones:
+    //   Green's          acc = [G][G.^2][occupation][count]; the binner takes [G][occupation] (bin_E = nb n^2 + nb n)
+    //                    from the true G of every unit itself (BIN_SRC_GREENS): no per_walker
+    //   correlations     per_walker holds the 4 n_dirs pair sums only, the binner takes the magnetisations from G (BIN_SRC_CORR)
+    //   time-displaced   n = E + 1, but the count is not packed (n_red = E): the passes that feed it feed the
+    //                    susceptibilities, whose reduced count dqmc_get_reduced hands out with the section
+    struct Section {
+        double *acc = nullptr, *per_walker = nullptr;
+        size_t n = 0, n_red = 0;  // doubles the local getter reports (0: not configured) / that go into the reduction
+        long bin_E = 0;
+        int bin_mode = BIN_SRC_PLAIN;
+    } sec[DQMC_RED_TIME_DISPLACED + 1];
     // correlation measurements (EachSitePairByDistance tables set by the host)
     int n_dirs = 0;
     int *dir_ptr = nullptr, *pair_src = nullptr, *pair_trg = nullptr;
-    double *corr_per_walker = nullptr, *corr_acc = nullptr;
     int K_loc = 0;                  // EachLocalQuadByDistance{K}
     int *trg_of = nullptr;          // [K][n]
-    size_t pc_n = 0;
-    double *pc_per_walker = nullptr, *pc_acc = nullptr;
     int K_cc = 0;                   // EachLocalQuadBySyncedDistance{K} (current_current_susceptibility)
     std::vector<int> cc_trg_h;      // [K][n]
     std::vector<double> cc_T;       // mc.s.hopping_matrix, nb blocks n x n
     CCPlan cc;
-    size_t corr_n = 0;
     int current_slice = 0, direction = 0;
     bool prepared = false;
     long long conf_version = 0;     // bumped whenever the HS field changes (mc.last_sweep's role for the UT stack)
@@ -135,7 +142,7 @@ struct dqmc_handle {
     size_t red_cap = 0;
     dqmc_stats red_stats{};
     bool red_valid = false;
-    size_t red_sizes[5] = {0, 0, 0, 0, 0};  // section sizes of the LAST reduction (dqmc_get_reduced checks against these)
+    size_t red_sizes[DQMC_RED_TIME_DISPLACED + 1] = {0, 0, 0, 0, 0};  // packed section sizes of the LAST reduction (dqmc_get_reduced checks against these)
     bool red_td_ok = false;  // the time-displaced and susceptibility sample counts agreed when that reduction was packed
     // logarithmic binners (binner.inl), one per DQMC_BIN_* section: xs, x2 [L][W][E], c [L - 1][W][E], out = finish scratch
     struct Binner {
@@ -144,13 +151,12 @@ struct dqmc_handle {
         int64_t cap = 0, T = 0;  // capacity and pushes so far: count[level] = T >> level for every element
         double *xs = nullptr, *x2 = nullptr, *c = nullptr, *out = nullptr;
     } bin[6];
-    // time-displaced recording (unequal_time.inl, tdm.hip): every == 0: off, nothing allocated.  E doubles per walker
-    // sample in the layout of include/dqmc_hip.h, acc [E + 1]; src_of [n_dirs][n] only with the fast form
+    // time-displaced recording (unequal_time.inl, tdm.hip): every == 0: off, nothing allocated.  The sample (bin_E doubles
+    // per walker in the layout of include/dqmc_hip.h) and the sums are sec[DQMC_RED_TIME_DISPLACED]; src_of [n_dirs][n]
+    // only with the fast form
     struct TimeDisplaced {
         int every = 0, what = 0, R = 0;
         bool fast = false;
-        size_t E = 0;
-        double *per_walker = nullptr, *acc = nullptr;
         int *src_of = nullptr;
     } td;
     // global moves (global_move.inl): per-walker device state, logabsdet / sign per unit of the current field [0] (valid
@@ -195,6 +201,30 @@ static int dalloc(dqmc_handle *h, T **p, size_t count, bool zero = true)
     *p = (T *)q;
     return 0;
 }
+// gives a block of dalloc back ahead of dqmc_destroy and nulls the pointer; the stream must be idle
+template <typename T>
+static void dfree(dqmc_handle *h, T **p)
+{
+    if (!*p) return;
+    auto it = std::find(h->allocs.begin(), h->allocs.end(), (void *)*p);
+    if (it != h->allocs.end()) h->allocs.erase(it);
+    (void)hipFree((void *)*p);
+    *p = nullptr;
+}
+// (re)builds the layout of section `which` (dqmc_handle::Section; n == 0: not configured): the old buffers go back, the
+// new ones start at zero.  `samples`: doubles per walker of per_walker.  The stream must be idle.
+static int sec_layout(dqmc_handle *h, int which, size_t n, size_t n_red, long bin_E, size_t samples, int bin_mode = BIN_SRC_PLAIN)
+{
+    dqmc_handle::Section &s = h->sec[which];
+    dfree(h, &s.acc);
+    dfree(h, &s.per_walker);
+    s = dqmc_handle::Section{};
+    if (!n) return 0;
+    CHK(dalloc(h, &s.acc, n));
+    if (samples) CHK(dalloc(h, &s.per_walker, (size_t)h->W * samples));
+    s.n = n; s.n_red = n_red; s.bin_E = bin_E; s.bin_mode = bin_mode;
+    return 0;
+}
 
 // ---- timing scopes ---------------------------------------------------------
 static int timing_drain(dqmc_handle *h)
@@ -212,6 +242,13 @@ static int timing_drain(dqmc_handle *h)
     h->pending.clear();
     return 0;
 }
+static hipEvent_t event_get(dqmc_handle *h)  // from the pool of drained events, or a new one
+{
+    hipEvent_t e;
+    if (!h->pool.empty()) { e = h->pool.back(); h->pool.pop_back(); }
+    else (void)hipEventCreate(&e);
+    return e;
+}
 struct Timed {
     dqmc_handle *h;
     int fam;
@@ -219,20 +256,14 @@ struct Timed {
     Timed(dqmc_handle *h_, int fam_) : h(h_), fam(fam_)
     {
         if (!h->timing) return;
-        auto get = [&]() {
-            hipEvent_t e;
-            if (!h->pool.empty()) { e = h->pool.back(); h->pool.pop_back(); }
-            else (void)hipEventCreate(&e);
-            return e;
-        };
-        a = get();
-        b = get();
-        (void)hipEventRecord(a, h->cur);
+        a = event_get(h);
+        b = event_get(h);
+        (void)hipEventRecord(a, h->stream);
     }
     ~Timed()
     {
         if (!h->timing) return;
-        (void)hipEventRecord(b, h->cur);
+        (void)hipEventRecord(b, h->stream);
         h->pending.push_back({a, b, fam});
         if (h->pending.size() >= 2048) (void)timing_drain(h);
     }
@@ -267,14 +298,8 @@ static void timing_events(dqmc_handle *h, hipEvent_t *a, hipEvent_t *b)
 {
     *a = *b = nullptr;
     if (!h->timing) return;
-    auto get = [&]() {
-        hipEvent_t e;
-        if (!h->pool.empty()) { e = h->pool.back(); h->pool.pop_back(); }
-        else (void)hipEventCreate(&e);
-        return e;
-    };
-    *a = get();
-    *b = get();
+    *a = event_get(h);
+    *b = event_get(h);
 }
 static int timing_push(dqmc_handle *h, hipEvent_t a, hipEvent_t b, int fam)
 {
@@ -285,22 +310,11 @@ static int timing_push(dqmc_handle *h, hipEvent_t a, hipEvent_t b, int fam)
 }
 static int run_gemm(dqmc_handle *h, const GemmArgs &g)
 {
-    if (!h->timing) {
-        HIPCHK(launch_gemm(g, h->cur));
-        return 0;
-    }
     // kernel-only duration: the events are attached to the dispatch itself (no launch gap inside)
-    auto get = [&]() {
-        hipEvent_t e;
-        if (!h->pool.empty()) { e = h->pool.back(); h->pool.pop_back(); }
-        else (void)hipEventCreate(&e);
-        return e;
-    };
-    hipEvent_t a = get(), b = get();
-    HIPCHK(launch_gemm(g, h->cur, a, b));
-    h->pending.push_back({a, b, DQMC_K_GEMM});
-    if (h->pending.size() >= 2048) CHK(timing_drain(h));
-    return 0;
+    hipEvent_t a, b;
+    timing_events(h, &a, &b);
+    HIPCHK(launch_gemm(g, h->stream, a, b));
+    return timing_push(h, a, b, DQMC_K_GEMM);
 }
 // exp(sign*lambda*conf[:,slice]) for block 0, exp(-sign*lambda*conf) for block 1
 // (HubbardModelAttractive.jl:100-110, HubbardModelRepulsive.jl:113-126); slice 1-based
@@ -329,25 +343,25 @@ static void slot_swap_spare(dqmc_handle *h, int i)
 static int copy_mat(dqmc_handle *h, double *dst, const double *src)
 {
     Timed t(h, DQMC_K_MISC);
-    HIPCHK(hipMemcpyAsync(dst, src, sizeof(double) * h->units * h->nn, hipMemcpyDeviceToDevice, h->cur));
+    HIPCHK(hipMemcpyAsync(dst, src, sizeof(double) * h->units * h->nn, hipMemcpyDeviceToDevice, h->stream));
     return 0;
 }
 static int copy_vec(dqmc_handle *h, double *dst, const double *src)
 {
     Timed t(h, DQMC_K_MISC);
-    HIPCHK(hipMemcpyAsync(dst, src, sizeof(double) * h->units * h->n, hipMemcpyDeviceToDevice, h->cur));
+    HIPCHK(hipMemcpyAsync(dst, src, sizeof(double) * h->units * h->n, hipMemcpyDeviceToDevice, h->stream));
     return 0;
 }
 static int set_identity(dqmc_handle *h, double *A)
 {
     Timed t(h, DQMC_K_MISC);
-    HIPCHK(launch_set_identity(h->n, h->units, A, h->nn, h->cur));
+    HIPCHK(launch_set_identity(h->n, h->units, A, h->nn, h->stream));
     return 0;
 }
 static int set_ones(dqmc_handle *h, double *d)
 {
     Timed t(h, DQMC_K_MISC);
-    HIPCHK(launch_fill(d, (size_t)h->units * h->n, 1.0, h->cur));
+    HIPCHK(launch_fill(d, (size_t)h->units * h->n, 1.0, h->stream));
     return 0;
 }
 
@@ -576,16 +590,16 @@ static int udt_factor(dqmc_handle *h, double *A, double *Dout, double *Tout, int
     {
         Timed t(h, DQMC_K_QR);
         // q.V is free until udt_finish writes V: it serves as the hand-over buffer of the two-phase QR
-        HIPCHK(launch_qr_pivot(n, h->units, A, h->nn, q.tau, q.pivot, &h->qr_ws, q.W, h->nn, &F, h->cur, q.V, h->nn));
+        HIPCHK(launch_qr_pivot(n, h->units, A, h->nn, q.tau, q.pivot, &h->qr_ws, q.W, h->nn, &F, h->stream, q.V, h->nn));
     }
     {
         Timed t(h, DQMC_K_MISC);
         HIPCHK(launch_udt_finish(n, h->units, A, h->nn, F, h->nn, q.pivot, Dout, n, q.V, h->nn, Tout, h->nn, apply,
-                                 h->cur));
+                                 h->stream));
     }
     return 0;
 }
-static int udt_formq(dqmc_handle *h, double *Uout, QrSet &q, double *winv, double *ts)
+static int udt_formq(dqmc_handle *h, double *Uout, QrSet &q)
 {
     const int n = h->n;
     GemmArgs g = gemm_base(h, U_(h, q.V), 1, U_(h, q.V), 0, q.S);
@@ -593,7 +607,7 @@ static int udt_formq(dqmc_handle *h, double *Uout, QrSet &q, double *winv, doubl
     CHK(run_gemm(h, g));
     {
         Timed t(h, DQMC_K_TRSM);
-        HIPCHK(launch_trsm_right_upper(n, h->units, q.V, h->nn, q.S, h->nn, nullptr, q.tau, n, q.W, h->nn, winv, h->sw, h->cur, ts));
+        HIPCHK(launch_trsm_right_upper(n, h->units, q.V, h->nn, q.S, h->nn, nullptr, q.tau, n, q.W, h->nn, q.winv, h->sw, h->stream, q.ts));
     }
     g = gemm_base(h, U_(h, q.W), 0, U_(h, q.V), 1, Uout);
     g.alpha = -1.0;
@@ -609,26 +623,26 @@ static int udt_fused(dqmc_handle *h, const double *A, double *Uout, double *Dout
                      const double *B = nullptr)
 {
     Timed t(h, DQMC_K_QR);
-    HIPCHK(launch_udt_blocked(h->units, A, h->nn, Uout, h->nn, Dout, h->n, Tout, h->nn, q.pivot, &h->qr_ws, apply, h->cur, B,
+    HIPCHK(launch_udt_blocked(h->units, A, h->nn, Uout, h->nn, Dout, h->n, Tout, h->nn, q.pivot, &h->qr_ws, apply, h->stream, B,
                               h->nn));
     return 0;
 }
 static int udt(dqmc_handle *h, double *A, double *Uout, double *Dout, double *Tout, int apply)
 {
-    if (udt_is_fused(h, 0) && Tout && Tout != A) return udt_fused(h, A, Uout, Dout, Tout, apply, h->qs[0]);
-    CHK(udt_factor(h, A, Dout, Tout, apply, h->qs[0]));
-    return udt_formq(h, Uout, h->qs[0], h->qs[0].winv, h->qs[0].ts);
+    if (udt_is_fused(h, 0) && Tout && Tout != A) return udt_fused(h, A, Uout, Dout, Tout, apply, h->qs);
+    CHK(udt_factor(h, A, Dout, Tout, apply, h->qs));
+    return udt_formq(h, Uout, h->qs);
 }
 // Out = A[:, pivot of set q] / triu(T) (rdivp!, general.jl:138-166)
-static int rdivp_set(dqmc_handle *h, const double *A, const double *T, double *Out, const QrSet &q, double *winv, double *ts)
+static int rdivp_set(dqmc_handle *h, const double *A, const double *T, double *Out, const QrSet &q)
 {
     Timed t(h, DQMC_K_TRSM);
-    HIPCHK(launch_trsm_right_upper(h->n, h->units, A, h->nn, T, h->nn, q.pivot, nullptr, 0, Out, h->nn, winv, h->sw, h->cur, ts));
+    HIPCHK(launch_trsm_right_upper(h->n, h->units, A, h->nn, T, h->nn, q.pivot, nullptr, 0, Out, h->nn, q.winv, h->sw, h->stream, q.ts));
     return 0;
 }
 static int rdivp(dqmc_handle *h, double *A, const double *T)
 {
-    return rdivp_set(h, A, T, A, h->qs[0], h->qs[0].winv, h->qs[0].ts);
+    return rdivp_set(h, A, T, A, h->qs);
 }
 
 // ---- calculate_greens_AVX! (stack.jl:337-393) -----------------------------------
@@ -640,21 +654,21 @@ static int rdivp(dqmc_handle *h, double *A, const double *T)
 static int calculate_greens_src(dqmc_handle *h, double *out, Udt L, Udt R, double *a2_copy = nullptr)
 {
     const int n = h->n;
-    QrSet &qa = h->qs[0], &qb = h->qs[0];
+    QrSet &q = h->qs;
     GemmArgs g = gemm_base(h, U_(h, L.t), 0, U_(h, R.t), 1, out);  // :346-348
     g.colscale = vs_arr(R.d, n);
     g.rowscale = vs_arr(L.d, n);
     CHK(run_gemm(h, g));
     if (udt_is_fused(h, 1)) {
-        // :349 and :360 in one launch: T out of place (qa.W), and the kernel carries Ul' through the reflectors instead of the
+        // :349 and :360 in one launch: T out of place (q.W), and the kernel carries Ul' through the reflectors instead of the
         // identity, so that its "U" is Tl = Ul Q already (Q itself is not used again: :362 overwrites Tr)
         if (L.u == h->Tl) return fail(h, DQMC_ERR_STATE, "calculate_greens: Ul aliases Tl");
-        CHK(udt_fused(h, out, h->Tl, h->Dr, qa.W, 0, qa, L.u));
-        CHK(rdivp_set(h, R.u, qa.W, h->Ur, qa, qa.winv, qa.ts));       // :361
+        CHK(udt_fused(h, out, h->Tl, h->Dr, q.W, 0, q, L.u));
+        CHK(rdivp_set(h, R.u, q.W, h->Ur, q));                             // :361
     } else {
-        CHK(udt_factor(h, out, h->Dr, nullptr, 0, qa));                    // :349, first half
-        CHK(rdivp_set(h, R.u, out, h->Ur, qa, qa.winv, qa.ts));            // :361 (out of place: Ur = R.u[:, p] / T)
-        CHK(udt_formq(h, h->Tr, qa, qa.winv, qa.ts));                      // :349, second half
+        CHK(udt_factor(h, out, h->Dr, nullptr, 0, q));                     // :349, first half
+        CHK(rdivp_set(h, R.u, out, h->Ur, q));                             // :361 (out of place: Ur = R.u[:, p] / T)
+        CHK(udt_formq(h, h->Tr, q));                                       // :349, second half
         CHK(run_gemm(h, gemm_base(h, U_(h, L.u), 0, U_(h, h->Tr), 0, h->Tl)));    // :360
     }
     g = gemm_base(h, U_(h, h->Tl), 1, U_(h, h->Ur), 0, h->Tr);         // :362 + :368
@@ -664,13 +678,13 @@ static int calculate_greens_src(dqmc_handle *h, double *out, Udt L, Udt R, doubl
     const double *tlul = h->Tr;  // where Tl Ul of :378 ends up
     if (udt_is_fused(h, 2)) {
         // :376 and :378 in one launch: "U" = Tl Q goes to Ul (free: the reference's Ul = Q is only used in :378)
-        CHK(udt_fused(h, h->Tr, h->Ul, h->Dr, qb.W, 0, qb, h->Tl));
-        CHK(rdivp_set(h, h->Ur, qb.W, h->Ur, qb, qb.winv, qb.ts));     // :377
+        CHK(udt_fused(h, h->Tr, h->Ul, h->Dr, q.W, 0, q, h->Tl));
+        CHK(rdivp_set(h, h->Ur, q.W, h->Ur, q));                           // :377
         tlul = h->Ul;
     } else {
-        CHK(udt_factor(h, h->Tr, h->Dr, nullptr, 0, qb));                  // :376
-        CHK(rdivp_set(h, h->Ur, h->Tr, h->Ur, qb, qb.winv, qb.ts));        // :377
-        CHK(udt_formq(h, h->Ul, qb, qb.winv, qb.ts));
+        CHK(udt_factor(h, h->Tr, h->Dr, nullptr, 0, q));                   // :376
+        CHK(rdivp_set(h, h->Ur, h->Tr, h->Ur, q));                         // :377
+        CHK(udt_formq(h, h->Ul, q));
         CHK(run_gemm(h, gemm_base(h, U_(h, h->Tl), 0, U_(h, h->Ul), 0, h->Tr)));  // :378
     }
     g = gemm_base(h, U_(h, h->Ur), 0, U_(h, tlul), 1, out);            // :382-391
@@ -709,7 +723,7 @@ static int cb_mult(dqmc_handle *h, int which, int slice, const double *X, double
     a.qscale = qscale; a.qstride = h->n;
     hipEvent_t ea, eb;
     timing_events(h, &ea, &eb);
-    HIPCHK(launch_cb_apply(a, h->units, h->cur, ea, eb));
+    HIPCHK(launch_cb_apply(a, h->units, h->stream, ea, eb));
     return timing_push(h, ea, eb, DQMC_K_GEMM);
 }
 
@@ -740,7 +754,7 @@ static int run_slab(dqmc_handle *h, const SlabArgs &a)
 {
     hipEvent_t ea, eb;
     timing_events(h, &ea, &eb);
-    HIPCHK(launch_slab_chain(a, h->cur, ea, eb));
+    HIPCHK(launch_slab_chain(a, h->stream, ea, eb));
     return timing_push(h, ea, eb, DQMC_K_GEMM);
 }
 
@@ -768,7 +782,7 @@ static int materialize_pending_flush(dqmc_handle *h)
     if (p.G != h->greens) return fail(h, DQMC_ERR_STATE, "pending sweep update does not belong to greens");
     hipEvent_t a, b;
     timing_events(h, &a, &b);
-    HIPCHK(launch_sweep_flush_lu(h->n, h->units, h->greens, h->greens_alt, h->nn, p.site0, 64, p.img, h->sw, h->cur, a, b));
+    HIPCHK(launch_sweep_flush_lu(h->n, h->units, h->greens, h->greens_alt, h->nn, p.site0, 64, p.img, h->sw, h->stream, a, b));
     CHK(timing_push(h, a, b, DQMC_K_FLUSH));
     std::swap(h->greens, h->greens_alt);
     return 0;
@@ -798,9 +812,9 @@ static int run_kron(dqmc_handle *h, const KronArgs &a)
 {
     hipEvent_t ea, eb;
     timing_events(h, &ea, &eb);
-    if (h->n == 512) HIPCHK(launch_kron3_chain(a, h->cur, ea, eb));
-    else if (h->tri) HIPCHK(launch_tri_chain(a, h->cur, ea, eb));
-    else HIPCHK(launch_kron_chain(a, h->cur, ea, eb));
+    if (h->n == 512) HIPCHK(launch_kron3_chain(a, h->stream, ea, eb));
+    else if (h->tri) HIPCHK(launch_tri_chain(a, h->stream, ea, eb));
+    else HIPCHK(launch_kron_chain(a, h->stream, ea, eb));
     return timing_push(h, ea, eb, DQMC_K_GEMM);
 }
 
@@ -879,10 +893,10 @@ static int add_slice_sequence(dqmc_handle *h, int dir, int idx, bool wrap_temp)
     // new factors into the spare, then slot dst <-> spare: the old slot dst stays readable
     const int sp = h->K + 1;
     if (udt_is_fused(h, 0)) {
-        CHK(udt_fused(h, out, uslot(h, sp), dslot(h, sp), h->tmp2, 1, h->qs[0]));
+        CHK(udt_fused(h, out, uslot(h, sp), dslot(h, sp), h->tmp2, 1, h->qs));
     } else {
-        CHK(udt_factor(h, out, dslot(h, sp), h->tmp2, 1, h->qs[0]));
-        CHK(udt_formq(h, uslot(h, sp), h->qs[0], h->qs[0].winv, h->qs[0].ts));
+        CHK(udt_factor(h, out, dslot(h, sp), h->tmp2, 1, h->qs));
+        CHK(udt_formq(h, uslot(h, sp), h->qs));
     }
     CHK(run_gemm(h, gemm_base(h, U_(h, h->tmp2), 0, U_(h, tslot(h, src)), 0, tslot(h, sp))));
     slot_swap_spare(h, dst);
@@ -922,7 +936,7 @@ static int wrap_greens_kron(dqmc_handle *h, const double *src, double *dst, int 
         a.errflag = h->qr_ws.errflag;
         hipEvent_t ea, eb;
         timing_events(h, &ea, &eb);
-        HIPCHK(launch_kron_wrap(a, h->cur, ea, eb));
+        HIPCHK(launch_kron_wrap(a, h->stream, ea, eb));
         ++h->wrap_launches;  // (only a launch that went out adds to the arrival words)
         return timing_push(h, ea, eb, DQMC_K_GEMM);
     }
@@ -1006,7 +1020,7 @@ static int reset_slot(dqmc_handle *h, int slot)
 static int prop_check(dqmc_handle *h)
 {
     Timed t(h, DQMC_K_MISC);
-    HIPCHK(launch_prop_check(h->n, h->nb, h->W, h->greens_temp, h->greens, h->nn, h->stats, h->pc_scratch, h->cur));
+    HIPCHK(launch_prop_check(h->n, h->nb, h->W, h->greens_temp, h->greens, h->nn, h->stats, h->pc_scratch, h->stream));
     return 0;
 }
 
@@ -1145,13 +1159,13 @@ static int sweep_spatial_launches(dqmc_handle *h)
         const int nc = h->N / 64;
         timing_events(h, &a, &b);
         HIPCHK(launch_sweep_lu(h->n, h->nb, h->W, cur, h->nn, cslice, cstr, 0, 64, h->lu_img, h->sc, h->rng, h->stats,
-                               h->p.check_sign_problem, h->qr_ws.errflag, h->cur, a, b));
+                               h->p.check_sign_problem, h->qr_ws.errflag, h->stream, a, b));
         CHK(timing_push(h, a, b, DQMC_K_SWEEP));
         for (int c = 1; c < nc; ++c) {
             timing_events(h, &a, &b);
             HIPCHK(launch_sweep_fused(h->n, h->nb, h->W, cur, alt, h->nn, cslice, cstr, 64 * c, 64 * (c - 1),
                                       h->lu_img + (size_t)(c & 1) * istr, h->lu_img + (size_t)((c - 1) & 1) * istr, h->sc,
-                                      h->rng, h->stats, h->p.check_sign_problem, h->qr_ws.errflag, h->cur, a, b));
+                                      h->rng, h->stats, h->p.check_sign_problem, h->qr_ws.errflag, h->stream, a, b));
             CHK(timing_push(h, a, b, DQMC_K_SWEEP));
             std::swap(cur, alt);
         }
@@ -1161,7 +1175,7 @@ static int sweep_spatial_launches(dqmc_handle *h)
             h->pf = dqmc_handle::PendingFlush{cur, img_last, 64 * (nc - 1)};
         } else {
             timing_events(h, &a, &b);
-            HIPCHK(launch_sweep_flush_lu(h->n, h->units, cur, alt, h->nn, 64 * (nc - 1), 64, img_last, h->sw, h->cur, a, b));
+            HIPCHK(launch_sweep_flush_lu(h->n, h->units, cur, alt, h->nn, 64 * (nc - 1), 64, img_last, h->sw, h->stream, a, b));
             CHK(timing_push(h, a, b, DQMC_K_FLUSH));
             std::swap(cur, alt);
         }
@@ -1172,10 +1186,10 @@ static int sweep_spatial_launches(dqmc_handle *h)
         const int ns = std::min(64, h->N - site0);
         timing_events(h, &a, &b);
         HIPCHK(launch_sweep_lu(h->n, h->nb, h->W, cur, h->nn, cslice, cstr, site0, ns, h->lu_img, h->sc,
-                               h->rng, h->stats, h->p.check_sign_problem, h->qr_ws.errflag, h->cur, a, b));
+                               h->rng, h->stats, h->p.check_sign_problem, h->qr_ws.errflag, h->stream, a, b));
         CHK(timing_push(h, a, b, DQMC_K_SWEEP));
         timing_events(h, &a, &b);
-        HIPCHK(launch_sweep_flush_lu(h->n, h->units, cur, alt, h->nn, site0, ns, h->lu_img, h->sw, h->cur, a, b));
+        HIPCHK(launch_sweep_flush_lu(h->n, h->units, cur, alt, h->nn, site0, ns, h->lu_img, h->sw, h->stream, a, b));
         CHK(timing_push(h, a, b, DQMC_K_FLUSH));
         std::swap(cur, alt);
     }
@@ -1274,7 +1288,6 @@ int dqmc_create(const dqmc_params *p, dqmc_handle **out)
     } while (0)
     CHIP(hipSetDevice(p->device_id));
     CHIP(hipStreamCreate(&h->stream));
-    h->cur = h->stream;
     const size_t cn = (size_t)nb * h->nn, un = (size_t)h->units * h->nn, uv = (size_t)h->units * h->n;
     CCHK(dalloc(h, &h->eT, cn)); CCHK(dalloc(h, &h->eTinv, cn));
     CCHK(dalloc(h, &h->eT2, cn)); CCHK(dalloc(h, &h->eTinv2, cn));
@@ -1349,13 +1362,13 @@ int dqmc_create(const dqmc_params *p, dqmc_handle **out)
         h->sd.push_back(h->d_stack + (size_t)i * uv);
     }
     double **mats[] = {&h->Ul, &h->Ur, &h->Tl, &h->Tr, &h->greens, &h->greens_temp, &h->tmp1,
-                       &h->tmp2, &h->bufA, &h->bufB, &h->qrV, &h->qrW, &h->qrS};
+                       &h->tmp2, &h->bufA, &h->bufB, &h->qs.V, &h->qs.W, &h->qs.S};
     for (auto m : mats) CCHK(dalloc(h, m, un));
-    CCHK(dalloc(h, &h->Dl, uv)); CCHK(dalloc(h, &h->Dr, uv)); CCHK(dalloc(h, &h->tau, uv));
+    CCHK(dalloc(h, &h->Dl, uv)); CCHK(dalloc(h, &h->Dr, uv)); CCHK(dalloc(h, &h->qs.tau, uv));
     const size_t wn = (size_t)h->units * ((h->n + 15) / 16) * 256;
-    CCHK(dalloc(h, &h->trsm_w, wn));
-    if (h->n > 256) CCHK(dalloc(h, &h->trsm_s, un));
-    CCHK(dalloc(h, &h->pivot, uv));
+    CCHK(dalloc(h, &h->qs.winv, wn));
+    if (h->n > 256) CCHK(dalloc(h, &h->qs.ts, un));
+    CCHK(dalloc(h, &h->qs.pivot, uv));
     CCHK(alloc_qr_workspace(h));
     CCHK(alloc_wrap_handoff(h));
     CCHK(dalloc(h, &h->greens_alt, un));
@@ -1381,8 +1394,10 @@ int dqmc_create(const dqmc_params *p, dqmc_handle **out)
         CHIP(hipMemcpy(h->rng, rg.data(), sizeof(WalkerRng) * h->W, hipMemcpyHostToDevice));
     }
     h->uniforms.assign(h->W, nullptr);
-    h->acc_n = 2 * cn + (size_t)nb * h->n + 1;
-    CCHK(dalloc(h, &h->acc, h->acc_n));
+    {
+        const size_t acc_n = 2 * cn + (size_t)nb * h->n + 1;
+        CCHK(sec_layout(h, DQMC_RED_GREENS, acc_n, acc_n, (long)(cn + (size_t)nb * h->n), 0, BIN_SRC_GREENS));
+    }
     CCHK(init_stack(h));
     CHIP(hipStreamSynchronize(h->stream));
 #undef CCHK
@@ -1392,7 +1407,6 @@ int dqmc_create(const dqmc_params *p, dqmc_handle **out)
 }
 
 static void ut_free(dqmc_handle *h);
-static int ut_reset_accumulators(dqmc_handle *h);
 static int binner_reset(dqmc_handle *h);
 int dqmc_destroy(dqmc_handle *h)
 {
@@ -1615,8 +1629,8 @@ static int calculate_greens_from_scratch(dqmc_handle *h, int slice, double *outp
     if (slice + 1 <= M) {
         for (int k = M; k >= slice + 1; --k) CHK(chain_step(k, true, k % s == 0, h->Dr, h->Tr, nullptr));
         // final: tmp1 = curr_U*Diagonal(Dr); udt(Ur, Dr, tmp1); Tr = tmp1*Tr
-        GemmArgs g = gemm_base(h, U_(h, cur), 0, U_(h, h->qrS), 0, oth);
-        CHK(set_identity(h, h->qrS));
+        GemmArgs g = gemm_base(h, U_(h, cur), 0, U_(h, h->qs.S), 0, oth);
+        CHK(set_identity(h, h->qs.S));
         g.colscale = vs_arr(h->Dr, n);
         CHK(run_gemm(h, g));
         std::swap(cur, oth);
@@ -1629,8 +1643,8 @@ static int calculate_greens_from_scratch(dqmc_handle *h, int slice, double *outp
     cur = h->bufA; oth = h->bufB;
     if (slice >= 1) {
         for (int k = 1; k <= slice; ++k) CHK(chain_step(k, false, k % s == 0, h->Dl, h->Tl, nullptr));
-        GemmArgs g = gemm_base(h, U_(h, cur), 0, U_(h, h->qrS), 0, oth);
-        CHK(set_identity(h, h->qrS));
+        GemmArgs g = gemm_base(h, U_(h, cur), 0, U_(h, h->qs.S), 0, oth);
+        CHK(set_identity(h, h->qs.S));
         g.colscale = vs_arr(h->Dl, n);
         CHK(run_gemm(h, g));
         std::swap(cur, oth);
@@ -1729,7 +1743,7 @@ int dqmc_accumulate_greens(dqmc_handle *h)
     CHK(true_greens(h, h->greens));
     {
         Timed t(h, DQMC_K_MISC);
-        HIPCHK(launch_accumulate(h->n, h->nb, h->W, h->tmp2, h->nn, h->acc, h->stream));
+        HIPCHK(launch_accumulate(h->n, h->nb, h->W, h->tmp2, h->nn, h->sec[DQMC_RED_GREENS].acc, h->stream));
     }
     if (h->bin[DQMC_BIN_GREENS].on) CHK(binner_push_section(h, DQMC_BIN_GREENS));
     return DQMC_OK;
@@ -1763,12 +1777,12 @@ int dqmc_set_pair_directions(dqmc_handle *h, const int32_t *dir_of, int32_t n_di
         CHK(dalloc(h, &h->pair_src, (size_t)n * n));
         CHK(dalloc(h, &h->pair_trg, (size_t)n * n));
     }
+    dfree(h, &h->dir_ptr);
     CHK(dalloc(h, &h->dir_ptr, (size_t)n_dirs + 1));
     h->n_dirs = n_dirs;
-    h->corr_n = 4 * (size_t)n_dirs + 3 * (size_t)n + 1;
     h->red_valid = false;  // (re)sized: the last reduction is void
-    CHK(dalloc(h, &h->corr_per_walker, (size_t)h->W * 4 * n_dirs));
-    CHK(dalloc(h, &h->corr_acc, h->corr_n));
+    const size_t corr_n = 4 * (size_t)n_dirs + 3 * (size_t)n + 1;
+    CHK(sec_layout(h, DQMC_RED_CORRELATIONS, corr_n, corr_n, (long)corr_n - 1, 4 * (size_t)n_dirs, BIN_SRC_CORR));
     HIPCHK(hipMemcpy(h->dir_ptr, ptr.data(), sizeof(int) * (n_dirs + 1), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(h->pair_src, src.data(), sizeof(int) * n * n, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(h->pair_trg, trg.data(), sizeof(int) * n * n, hipMemcpyHostToDevice));
@@ -1786,31 +1800,10 @@ int dqmc_accumulate_correlations(dqmc_handle *h)
     {
         Timed t(h, DQMC_K_MISC);
         HIPCHK(launch_correlations(h->n, h->nb, h->p.model_kind, h->W, h->tmp2, h->nn, h->dir_ptr, h->pair_src,
-                                   h->pair_trg, h->n_dirs, h->corr_per_walker, h->corr_acc, h->stream));
+                                   h->pair_trg, h->n_dirs, h->sec[DQMC_RED_CORRELATIONS].per_walker,
+                                   h->sec[DQMC_RED_CORRELATIONS].acc, h->stream));
     }
     if (h->bin[DQMC_BIN_CORRELATIONS].on) CHK(binner_push_section(h, DQMC_BIN_CORRELATIONS));
-    return DQMC_OK;
-}
-int dqmc_correlations_size(dqmc_handle *h, size_t *n)
-{
-    if (!h || !n) return DQMC_ERR_INVALID;
-    *n = h->corr_n;
-    return DQMC_OK;
-}
-int dqmc_get_correlations(dqmc_handle *h, double *host_out)
-{
-    ENTER(h);
-    if (!h->n_dirs) return fail(h, DQMC_ERR_STATE, "call dqmc_set_pair_directions first");
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(host_out, h->corr_acc, h->corr_n * sizeof(double), hipMemcpyDeviceToHost));
-    return DQMC_OK;
-}
-int dqmc_export_correlations(dqmc_handle *h, void *device_out)
-{
-    ENTER(h);
-    if (!h->n_dirs) return fail(h, DQMC_ERR_STATE, "call dqmc_set_pair_directions first");
-    HIPCHK(hipMemcpyAsync(device_out, h->corr_acc, h->corr_n * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
     return DQMC_OK;
 }
 // EachLocalQuadByDistance{K}(lattice) (lattice_iterators.jl:264-318) as a target table
@@ -1824,11 +1817,11 @@ int dqmc_set_local_targets(dqmc_handle *h, const int32_t *trg_of, int32_t K)
         if (trg_of[i] < -1 || trg_of[i] >= n) return fail(h, DQMC_ERR_INVALID, "target index out of range");
     HIPCHK(hipStreamSynchronize(h->stream));
     h->K_loc = K;
-    h->pc_n = (size_t)h->n_dirs * K * K + 1;
     h->red_valid = false;
+    dfree(h, &h->trg_of);
     CHK(dalloc(h, &h->trg_of, (size_t)n * K));
-    CHK(dalloc(h, &h->pc_per_walker, (size_t)h->W * (h->pc_n - 1)));
-    CHK(dalloc(h, &h->pc_acc, h->pc_n));
+    const size_t pc_n = (size_t)h->n_dirs * K * K + 1;
+    CHK(sec_layout(h, DQMC_RED_PAIRING, pc_n, pc_n, (long)pc_n - 1, pc_n - 1));
     HIPCHK(hipMemcpy(h->trg_of, trg_of, sizeof(int) * n * K, hipMemcpyHostToDevice));
     HIPCHK(hipStreamSynchronize(h->stream));
     return DQMC_OK;
@@ -1842,65 +1835,56 @@ int dqmc_accumulate_pairing(dqmc_handle *h)
     {
         Timed t(h, DQMC_K_MISC);
         HIPCHK(launch_pairing(h->n, h->nb, h->W, h->tmp2, h->nn, h->dir_ptr, h->pair_src, h->pair_trg, h->n_dirs,
-                              h->K_loc, h->trg_of, h->pc_per_walker, h->pc_acc, h->stream));
+                              h->K_loc, h->trg_of, h->sec[DQMC_RED_PAIRING].per_walker, h->sec[DQMC_RED_PAIRING].acc,
+                              h->stream));
     }
     if (h->bin[DQMC_BIN_PAIRING].on) CHK(binner_push_section(h, DQMC_BIN_PAIRING));
-    return DQMC_OK;
-}
-int dqmc_pairing_size(dqmc_handle *h, size_t *n)
-{
-    if (!h || !n) return DQMC_ERR_INVALID;
-    *n = h->pc_n;
-    return DQMC_OK;
-}
-int dqmc_get_pairing(dqmc_handle *h, double *host_out)
-{
-    ENTER(h);
-    if (!h->K_loc) return fail(h, DQMC_ERR_STATE, "call dqmc_set_local_targets first");
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(host_out, h->pc_acc, h->pc_n * sizeof(double), hipMemcpyDeviceToHost));
-    return DQMC_OK;
-}
-int dqmc_export_pairing(dqmc_handle *h, void *device_out)
-{
-    ENTER(h);
-    if (!h->K_loc) return fail(h, DQMC_ERR_STATE, "call dqmc_set_local_targets first");
-    HIPCHK(hipMemcpyAsync(device_out, h->pc_acc, h->pc_n * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return DQMC_OK;
-}
-int dqmc_accumulator_size(dqmc_handle *h, size_t *n)
-{
-    if (!h || !n) return DQMC_ERR_INVALID;
-    *n = h->acc_n;
     return DQMC_OK;
 }
 int dqmc_reset_accumulators(dqmc_handle *h)
 {
     ENTER(h);
     h->red_valid = false;  // (the last reduction no longer describes the accumulators)
-    HIPCHK(hipMemsetAsync(h->acc, 0, h->acc_n * sizeof(double), h->stream));
-    if (h->corr_acc) HIPCHK(hipMemsetAsync(h->corr_acc, 0, h->corr_n * sizeof(double), h->stream));
-    if (h->pc_acc) HIPCHK(hipMemsetAsync(h->pc_acc, 0, h->pc_n * sizeof(double), h->stream));
-    CHK(ut_reset_accumulators(h));
-    if (h->td.every) HIPCHK(hipMemsetAsync(h->td.acc, 0, (h->td.E + 1) * sizeof(double), h->stream));
+    for (const auto &s : h->sec)
+        if (s.n) HIPCHK(hipMemsetAsync(s.acc, 0, s.n * sizeof(double), h->stream));
     CHK(binner_reset(h));
     return DQMC_OK;
 }
-int dqmc_get_accumulators(dqmc_handle *h, double *host_out)
+
+// ---- size / host get / device export of a section's sums (dqmc_handle::Section) --------------------------------------
+static const char *const SEC_NEED[] = {nullptr, "call dqmc_set_pair_directions first", "call dqmc_set_local_targets first",
+                                       "nothing accumulated", "call dqmc_set_time_displaced first"};
+static int sec_size(dqmc_handle *h, int which, size_t *n)
 {
-    ENTER(h);
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(host_out, h->acc, h->acc_n * sizeof(double), hipMemcpyDeviceToHost));
+    if (!h || !n) return DQMC_ERR_INVALID;
+    *n = h->sec[which].n;
     return DQMC_OK;
 }
-int dqmc_export_accumulators(dqmc_handle *h, void *device_out)
+static int sec_get(dqmc_handle *h, int which, double *host_out)
 {
-    ENTER(h);
-    HIPCHK(hipMemcpyAsync(device_out, h->acc, h->acc_n * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    const dqmc_handle::Section &s = h->sec[which];
+    if (!s.n) return fail(h, DQMC_ERR_STATE, SEC_NEED[which]);
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(host_out, s.acc, s.n * sizeof(double), hipMemcpyDeviceToHost));
+    return DQMC_OK;
+}
+static int sec_export(dqmc_handle *h, int which, void *device_out)
+{
+    const dqmc_handle::Section &s = h->sec[which];
+    if (!s.n) return fail(h, DQMC_ERR_STATE, SEC_NEED[which]);
+    HIPCHK(hipMemcpyAsync(device_out, s.acc, s.n * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return DQMC_OK;
 }
+int dqmc_accumulator_size(dqmc_handle *h, size_t *n) { return sec_size(h, DQMC_RED_GREENS, n); }
+int dqmc_get_accumulators(dqmc_handle *h, double *host_out) { ENTER(h); return sec_get(h, DQMC_RED_GREENS, host_out); }
+int dqmc_export_accumulators(dqmc_handle *h, void *device_out) { ENTER(h); return sec_export(h, DQMC_RED_GREENS, device_out); }
+int dqmc_correlations_size(dqmc_handle *h, size_t *n) { return sec_size(h, DQMC_RED_CORRELATIONS, n); }
+int dqmc_get_correlations(dqmc_handle *h, double *host_out) { ENTER(h); return sec_get(h, DQMC_RED_CORRELATIONS, host_out); }
+int dqmc_export_correlations(dqmc_handle *h, void *device_out) { ENTER(h); return sec_export(h, DQMC_RED_CORRELATIONS, device_out); }
+int dqmc_pairing_size(dqmc_handle *h, size_t *n) { return sec_size(h, DQMC_RED_PAIRING, n); }
+int dqmc_get_pairing(dqmc_handle *h, double *host_out) { ENTER(h); return sec_get(h, DQMC_RED_PAIRING, host_out); }
+int dqmc_export_pairing(dqmc_handle *h, void *device_out) { ENTER(h); return sec_export(h, DQMC_RED_PAIRING, device_out); }
 
 #include "unequal_time.inl"
 #include "binner.inl"
@@ -1917,39 +1901,39 @@ int dqmc_export_accumulators(dqmc_handle *h, void *device_out)
 static const size_t RED_STAT_SUMS = 6;
 static size_t red_nsum(dqmc_handle *h)
 {
-    return h->acc_n + h->corr_n + h->pc_n + (h->ut ? h->ut->sus_n : 0) + (h->td.every ? h->td.E : 0) + RED_STAT_SUMS;
+    size_t n = RED_STAT_SUMS;
+    for (const auto &s : h->sec) n += s.n_red;
+    return n;
 }
 static int red_pack(dqmc_handle *h)
 {
     const size_t nsum = red_nsum(h), tot = nsum + 4;
     if (h->red_cap < tot) {
+        HIPCHK(hipStreamSynchronize(h->stream));  // (the old buffer goes back)
+        dfree(h, &h->red_buf);
+        h->red_cap = 0;
         CHK(dalloc(h, &h->red_buf, tot));
         h->red_cap = tot;
     }
     size_t off = 0;
-    auto put = [&](const double *src, size_t cnt) -> int {
-        if (cnt) HIPCHK(hipMemcpyAsync(h->red_buf + off, src, cnt * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-        off += cnt;
-        return 0;
-    };
-    CHK(put(h->acc, h->acc_n));
-    CHK(put(h->corr_acc, h->corr_n));
-    CHK(put(h->pc_acc, h->pc_n));
-    if (h->ut) CHK(put(h->ut->sus_acc, h->ut->sus_n));
-    // the time-displaced sums without their sample count: the passes that feed them feed the susceptibilities, whose
+    for (int i = 0; i <= DQMC_RED_TIME_DISPLACED; ++i) {
+        const dqmc_handle::Section &s = h->sec[i];
+        if (s.n_red)
+            HIPCHK(hipMemcpyAsync(h->red_buf + off, s.acc, s.n_red * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+        off += s.n_red;
+        h->red_sizes[i] = s.n_red;
+    }
+    // the time-displaced sums went without their sample count: the passes that feed them feed the susceptibilities, whose
     // count stands for both (dqmc_get_reduced hands it out with the section) - if the two local counts agree
     h->red_td_ok = false;
-    if (h->td.every) {
-        CHK(put(h->td.acc, h->td.E));
+    const dqmc_handle::Section &td = h->sec[DQMC_RED_TIME_DISPLACED], &sus = h->sec[DQMC_RED_SUSCEPTIBILITIES];
+    if (td.n) {
         double c_td = 0.0, c_sus = 0.0;
         HIPCHK(hipStreamSynchronize(h->stream));
-        HIPCHK(hipMemcpy(&c_td, h->td.acc + h->td.E, sizeof(double), hipMemcpyDeviceToHost));
-        if (h->ut && h->ut->sus_n)
-            HIPCHK(hipMemcpy(&c_sus, h->ut->sus_acc + h->ut->sus_n - 1, sizeof(double), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(&c_td, td.acc + td.n - 1, sizeof(double), hipMemcpyDeviceToHost));
+        if (sus.n) HIPCHK(hipMemcpy(&c_sus, sus.acc + sus.n - 1, sizeof(double), hipMemcpyDeviceToHost));
         h->red_td_ok = c_td == c_sus;
     }
-    h->red_sizes[0] = h->acc_n; h->red_sizes[1] = h->corr_n; h->red_sizes[2] = h->pc_n; h->red_sizes[3] = h->ut ? h->ut->sus_n : 0;
-    h->red_sizes[4] = h->td.every ? h->td.E : 0;
     // counters of the local walkers, reduced on the host in walker order
     std::vector<DevStats> st(h->W);
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -2070,23 +2054,23 @@ int dqmc_get_reduced(dqmc_handle *h, int32_t which, double *host_out)
     ENTER(h);
     if (!host_out || which < 0 || which > DQMC_RED_TIME_DISPLACED) return fail(h, DQMC_ERR_INVALID, "dqmc_get_reduced: bad arguments");
     if (!h->red_valid) return fail(h, DQMC_ERR_STATE, "call dqmc_reduce first");
-    const size_t sizes[5] = {h->acc_n, h->corr_n, h->pc_n, h->ut ? h->ut->sus_n : 0, h->td.every ? h->td.E : 0};
     size_t off = 0;
-    for (int i = 0; i < which; ++i) off += sizes[i];
-    if (sizes[which] == 0) return fail(h, DQMC_ERR_STATE, "dqmc_get_reduced: this accumulator is not configured");
-    for (int i = 0; i < 5; ++i)  // (sizes as they are NOW against the sizes that were packed)
-        if (sizes[i] != h->red_sizes[i])
+    for (int i = 0; i < which; ++i) off += h->sec[i].n_red;
+    const size_t cnt = h->sec[which].n_red;
+    if (cnt == 0) return fail(h, DQMC_ERR_STATE, "dqmc_get_reduced: this accumulator is not configured");
+    for (int i = 0; i <= DQMC_RED_TIME_DISPLACED; ++i)  // (sizes as they are NOW against the sizes that were packed)
+        if (h->sec[i].n_red != h->red_sizes[i])
             return fail(h, DQMC_ERR_STATE, "accumulators were reconfigured after the last reduction: call dqmc_reduce again");
     if (h->red_cap < red_nsum(h) + 4) return fail(h, DQMC_ERR_STATE, "call dqmc_reduce first");
     if (which == DQMC_RED_TIME_DISPLACED && !h->red_td_ok)
         return fail(h, DQMC_ERR_STATE, "time-displaced and susceptibility sample counts differed at the last reduction: "
                                        "call dqmc_reset_accumulators after dqmc_set_time_displaced");
     HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(host_out, h->red_buf + off, sizes[which] * sizeof(double), hipMemcpyDeviceToHost));
-    if (which == DQMC_RED_TIME_DISPLACED) {
-        host_out[sizes[4]] = 0.0;
-        if (sizes[3])
-            HIPCHK(hipMemcpy(host_out + sizes[4], h->red_buf + off - 1, sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(host_out, h->red_buf + off, cnt * sizeof(double), hipMemcpyDeviceToHost));
+    if (which == DQMC_RED_TIME_DISPLACED) {  // the susceptibilities are packed right in front: their last double is the count
+        host_out[cnt] = 0.0;
+        if (h->sec[DQMC_RED_SUSCEPTIBILITIES].n_red)
+            HIPCHK(hipMemcpy(host_out + cnt, h->red_buf + off - 1, sizeof(double), hipMemcpyDeviceToHost));
     }
     return DQMC_OK;
 }
@@ -2310,10 +2294,7 @@ int dqmc_timing_get(dqmc_handle *h, double *ms, int64_t *launches)
 // stand-alone batched primitives (host in / host out)
 // ---------------------------------------------------------------------------
 namespace {
-struct Scratch {  // a throw-away handle-like context for the primitive entry points
-    dqmc_handle h;
-    int ok = 0;
-};
+// the primitive entry points run on a throw-away handle of their own (dqmc_handle hh)
 static int scratch_init(dqmc_handle *h, int device_id, int n, int batch)
 {
     int ndev = 0;
@@ -2328,7 +2309,6 @@ static int scratch_init(dqmc_handle *h, int device_id, int n, int batch)
     h->nn = (long)n * n;
     HIPCHK(hipSetDevice(device_id));
     HIPCHK(hipStreamCreate(&h->stream));
-    h->cur = h->stream;
     return 0;
 }
 static void scratch_free(dqmc_handle *h)
@@ -2380,9 +2360,9 @@ int dqmc_vmul(int32_t device_id, int32_t n, int32_t batch, int32_t ta, int32_t t
 static int scratch_udt_bufs(dqmc_handle *h)
 {
     const size_t un = (size_t)h->units * h->nn, uv = (size_t)h->units * h->n;
-    CHK(dalloc(h, &h->qrV, un)); CHK(dalloc(h, &h->qrW, un)); CHK(dalloc(h, &h->qrS, un));
-    CHK(dalloc(h, &h->tau, uv)); CHK(dalloc(h, &h->pivot, uv));
-    CHK(dalloc(h, &h->trsm_w, (size_t)h->units * ((h->n + 15) / 16) * 256));
+    CHK(dalloc(h, &h->qs.V, un)); CHK(dalloc(h, &h->qs.W, un)); CHK(dalloc(h, &h->qs.S, un));
+    CHK(dalloc(h, &h->qs.tau, uv)); CHK(dalloc(h, &h->qs.pivot, uv));
+    CHK(dalloc(h, &h->qs.winv, (size_t)h->units * ((h->n + 15) / 16) * 256));
     CHK(alloc_qr_workspace(h));
     return 0;
 }
@@ -2405,7 +2385,7 @@ int dqmc_udt_pivot(int32_t device_id, int32_t n, int32_t batch, double *U, doubl
     // (the one-launch form writes T out of place also for Val(false))
     SHIP(hipMemcpy(T, (apply || udt_is_fused(h, 0)) ? dTo : dT, un * sizeof(double), hipMemcpyDeviceToHost));
     std::vector<int> piv(uv);
-    SHIP(hipMemcpy(piv.data(), h->pivot, uv * sizeof(int), hipMemcpyDeviceToHost));
+    SHIP(hipMemcpy(piv.data(), h->qs.pivot, uv * sizeof(int), hipMemcpyDeviceToHost));
     for (size_t i = 0; i < uv; ++i) pivot[i] = (int64_t)piv[i] + 1;
     scratch_free(h);
     return DQMC_OK;
@@ -2443,8 +2423,8 @@ int dqmc_rdivp(int32_t device_id, int32_t n, int32_t batch, double *A, const dou
     SCHK(scratch_init(h, device_id, n, batch));
     const size_t un = (size_t)batch * h->nn, uv = (size_t)batch * n;
     double *dA, *dT;
-    SCHK(dalloc(h, &dA, un, false)); SCHK(dalloc(h, &dT, un, false)); SCHK(dalloc(h, &h->pivot, uv));
-    SCHK(dalloc(h, &h->trsm_w, (size_t)h->units * ((h->n + 15) / 16) * 256));
+    SCHK(dalloc(h, &dA, un, false)); SCHK(dalloc(h, &dT, un, false)); SCHK(dalloc(h, &h->qs.pivot, uv));
+    SCHK(dalloc(h, &h->qs.winv, (size_t)h->units * ((h->n + 15) / 16) * 256));
     std::vector<int> piv(uv);
     for (size_t i = 0; i < uv; ++i) {
         if (pivot[i] < 1 || pivot[i] > n) { scratch_free(h); return fail(nullptr, DQMC_ERR_INVALID, "pivot entry out of range"); }
@@ -2452,7 +2432,7 @@ int dqmc_rdivp(int32_t device_id, int32_t n, int32_t batch, double *A, const dou
     }
     SHIP(hipMemcpy(dA, A, un * sizeof(double), hipMemcpyHostToDevice));
     SHIP(hipMemcpy(dT, T, un * sizeof(double), hipMemcpyHostToDevice));
-    SHIP(hipMemcpy(h->pivot, piv.data(), uv * sizeof(int), hipMemcpyHostToDevice));
+    SHIP(hipMemcpy(h->qs.pivot, piv.data(), uv * sizeof(int), hipMemcpyHostToDevice));
     SCHK(rdivp(h, dA, dT));
     SHIP(hipStreamSynchronize(h->stream));
     SHIP(hipMemcpy(A, dA, un * sizeof(double), hipMemcpyDeviceToHost));

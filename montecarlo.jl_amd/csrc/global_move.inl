@@ -12,7 +12,7 @@ static int logdet_from_scratch(dqmc_handle *h, double *lad, int *sg)
 {
     CHK(calculate_greens_from_scratch(h, 0, h->greens_temp, h->bufA));
     Timed t(h, DQMC_K_MISC);
-    HIPCHK(launch_logdet(h->n, h->units, h->bufA, h->nn, h->Dr, h->n, lad, sg, h->cur));
+    HIPCHK(launch_logdet(h->n, h->units, h->bufA, h->nn, h->Dr, h->n, lad, sg, h->stream));
     return 0;
 }
 // the cache of the current field's values (invalid once conf_version has moved on)
@@ -29,14 +29,14 @@ static int global_move(dqmc_handle *h, int kind, int walker)
     CHK(logdet_current(h));
     {
         Timed t(h, DQMC_K_MISC);
-        HIPCHK(launch_gm_propose(h->N, h->M, h->W, kind, walker, h->conf, h->rng, h->gm, h->cur));
+        HIPCHK(launch_gm_propose(h->N, h->M, h->W, kind, walker, h->conf, h->rng, h->gm, h->stream));
     }
     h->conf_version++;
     CHK(logdet_from_scratch(h, h->gm_lad[1], h->gm_sg[1]));
     {
         Timed t(h, DQMC_K_MISC);
         HIPCHK(launch_gm_decide(h->N, h->M, h->nb, h->W, kind, h->lambda, h->p.check_sign_problem, h->conf, h->rng, h->gm,
-                                h->stats, h->gm_lad[0], h->gm_sg[0], h->gm_lad[1], h->gm_sg[1], h->cur));
+                                h->stats, h->gm_lad[0], h->gm_sg[0], h->gm_lad[1], h->gm_sg[1], h->stream));
     }
     // the field is the old or the new one per walker, and the cache holds the values of whichever it is
     h->conf_version++;

@@ -22,8 +22,6 @@ struct UTStack {
     double *s1 = nullptr, *s2 = nullptr, *curr = nullptr;
     double *out[3] = {nullptr, nullptr, nullptr};  // results handed out: G(k,l) in out[0]; (G0l, Gl0, Gll)
     double *g00 = nullptr;                            // greens!(mc) kept for the packed kernels
-    double *sus_per_walker = nullptr, *sus_acc = nullptr;
-    size_t sus_n = 0;                                 // doubles in sus_acc (last = sample count)
     int it_kind = 0;  // 0 none, 1 GreensIterator, 2 CombinedGreensIterator
     int it_pos = 0, it_l = 0, it_recalc = 0;
 };
@@ -32,11 +30,6 @@ static void ut_free(dqmc_handle *h)
 {
     delete h->ut;  // device buffers are owned by h->allocs
     h->ut = nullptr;
-}
-static int ut_reset_accumulators(dqmc_handle *h)
-{
-    if (h->ut && h->ut->sus_acc) HIPCHK(hipMemsetAsync(h->ut->sus_acc, 0, h->ut->sus_n * sizeof(double), h->stream));
-    return 0;
 }
 static double *ut_slot(dqmc_handle *h, double *base, int idx) { return base + (long)idx * h->units * h->nn; }
 static double *ut_dslot(dqmc_handle *h, double *base, int idx) { return base + (long)idx * h->units * h->n; }
@@ -575,6 +568,11 @@ int dqmc_combined_iterator_next(dqmc_handle *h, int32_t *l)
 static int cc_setup(dqmc_handle *h)
 {
     const int n = h->n, nb = h->nb, nd = h->n_dirs;
+    CCPlan &p = h->cc;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    dfree(h, &p.trg); dfree(h, &p.tst); dfree(h, &p.tts); dfree(h, &p.bsum); dfree(h, &p.partial);
+    dfree(h, &p.dsel); dfree(h, &p.rows); dfree(h, &p.ucnt); dfree(h, &p.slot);
+    p = CCPlan();
     if (h->K_cc > nd) {  // directions replaced by a table with fewer of them: the targets no longer apply
         h->K_cc = 0;
         h->red_valid = false;
@@ -591,9 +589,6 @@ static int cc_setup(dqmc_handle *h)
             tst[b * nK + e] = T[s + (size_t)n * t];
             tts[b * nK + e] = T[t + (size_t)n * s];
         }
-    HIPCHK(hipStreamSynchronize(h->stream));
-    CCPlan &p = h->cc;
-    p = CCPlan();
     p.K = K;
     int *trg = nullptr;
     double *dtst = nullptr, *dtts = nullptr;
@@ -666,6 +661,8 @@ static int cc_setup(dqmc_handle *h)
         CHK(dalloc(h, &drows, rows.size()));
         CHK(dalloc(h, &ducnt, ucnt.size()));
         CHK(dalloc(h, &dslot, slot.size()));
+        HIPCHK(hipStreamSynchronize(h->stream));  // (the general kernel's sums: their zeroing is in flight)
+        dfree(h, &p.partial);
         CHK(dalloc(h, &p.partial, (size_t)h->W * p.n_wg * nK));
         HIPCHK(hipMemcpy(ddsel, dsel.data(), sizeof(int) * n * n, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(drows, rows.data(), sizeof(int) * rows.size(), hipMemcpyHostToDevice));
@@ -710,27 +707,19 @@ int dqmc_current_targets_plan(dqmc_handle *h, int32_t out[8])
 static long ut_cc_offset(dqmc_handle *h) { return 4L * h->n_dirs + (long)h->n_dirs * h->K_loc * h->K_loc; }
 static int ut_sus_layout(dqmc_handle *h)
 {
-    UTStack *u = h->ut;
     const size_t want = 4 * (size_t)h->n_dirs + (size_t)h->n_dirs * h->K_loc * h->K_loc
                         + (size_t)h->n_dirs * h->K_cc + 1;
-    if (u->sus_n == want) return 0;
-    u->sus_n = want;
+    if (h->sec[DQMC_RED_SUSCEPTIBILITIES].n == want) return 0;
     h->red_valid = false;  // (re)sized: the last reduction is void
-    CHK(dalloc(h, &u->sus_per_walker, (size_t)h->W * (want - 1)));
-    CHK(dalloc(h, &u->sus_acc, want));
-    return 0;
+    HIPCHK(hipStreamSynchronize(h->stream));  // (the old buffers go back)
+    return sec_layout(h, DQMC_RED_SUSCEPTIBILITIES, want, want, (long)want - 1, want - 1);
 }
 // ---- time-displaced recording (include/dqmc_hip.h; kernels in tdm.hip) ---------------------------------------------
 static void td_free(dqmc_handle *h)
 {
-    dqmc_handle::TimeDisplaced &t = h->td;
-    for (void *p : {(void *)t.per_walker, (void *)t.acc, (void *)t.src_of}) {
-        if (!p) continue;
-        auto it = std::find(h->allocs.begin(), h->allocs.end(), p);
-        if (it != h->allocs.end()) h->allocs.erase(it);
-        (void)hipFree(p);
-    }
-    t = dqmc_handle::TimeDisplaced{};
+    (void)sec_layout(h, DQMC_RED_TIME_DISPLACED, 0, 0, 0, 0);
+    dfree(h, &h->td.src_of);
+    h->td = dqmc_handle::TimeDisplaced{};
 }
 // (re)builds the layout, the buffers and, where the direction table allows it, src_of; the accumulator starts at zero
 static int td_setup(dqmc_handle *h, int every, int what)
@@ -742,8 +731,7 @@ static int td_setup(dqmc_handle *h, int every, int what)
     dqmc_handle::TimeDisplaced &t = h->td;
     const int R = 1 + h->M / every;
     const size_t E = ((what & DQMC_TD_GREENS) ? 2 * (size_t)nb : 0) * R * nd + ((what & DQMC_TD_DENSITY) ? 4 : 0) * (size_t)R * nd;
-    CHK(dalloc(h, &t.per_walker, (size_t)h->W * E));
-    CHK(dalloc(h, &t.acc, E + 1));
+    CHK(sec_layout(h, DQMC_RED_TIME_DISPLACED, E + 1, E, (long)E, E));
     // fast form of the Green's rows: n_dirs == n and a Latin square - every source meets each direction once (the
     // first two conditions of cc_setup's LDS plan) and so does every target, which is what makes src_of complete
     bool fast = (what & DQMC_TD_GREENS) && !h->sw.tdm_general && nd == n;
@@ -768,7 +756,7 @@ static int td_setup(dqmc_handle *h, int every, int what)
         }
     }
     HIPCHK(hipStreamSynchronize(h->stream));
-    t.every = every; t.what = what; t.R = R; t.E = E; t.fast = fast;
+    t.every = every; t.what = what; t.R = R; t.fast = fast;
     return 0;
 }
 int dqmc_set_time_displaced(dqmc_handle *h, int32_t every, int32_t what)
@@ -786,29 +774,18 @@ int dqmc_set_time_displaced(dqmc_handle *h, int32_t every, int32_t what)
         return fail(h, DQMC_ERR_INVALID, "what must be a non-empty mask of DQMC_TD_GREENS | DQMC_TD_DENSITY");
     return td_setup(h, every, what);
 }
-int dqmc_time_displaced_size(dqmc_handle *h, size_t *n_doubles)
-{
-    if (!h || !n_doubles) return DQMC_ERR_INVALID;
-    *n_doubles = h->td.every ? h->td.E + 1 : 0;
-    return DQMC_OK;
-}
+int dqmc_time_displaced_size(dqmc_handle *h, size_t *n_doubles) { return sec_size(h, DQMC_RED_TIME_DISPLACED, n_doubles); }
 int dqmc_get_time_displaced(dqmc_handle *h, double *host_out)
 {
     ENTER(h);
     if (!host_out) return fail(h, DQMC_ERR_INVALID, "host_out is NULL");
-    if (!h->td.every) return fail(h, DQMC_ERR_STATE, "call dqmc_set_time_displaced first");
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(host_out, h->td.acc, (h->td.E + 1) * sizeof(double), hipMemcpyDeviceToHost));
-    return DQMC_OK;
+    return sec_get(h, DQMC_RED_TIME_DISPLACED, host_out);
 }
 int dqmc_export_time_displaced(dqmc_handle *h, void *device_out)
 {
     ENTER(h);
     if (!device_out) return fail(h, DQMC_ERR_INVALID, "device_out is NULL");
-    if (!h->td.every) return fail(h, DQMC_ERR_STATE, "call dqmc_set_time_displaced first");
-    HIPCHK(hipMemcpyAsync(device_out, h->td.acc, (h->td.E + 1) * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return DQMC_OK;
+    return sec_export(h, DQMC_RED_TIME_DISPLACED, device_out);
 }
 int dqmc_time_displaced_plan(dqmc_handle *h, int32_t out[4])
 {
@@ -822,13 +799,14 @@ static int td_record(dqmc_handle *h, int row, int minus_identity, const double *
                      const double *gl0, const double *gll)
 {
     const dqmc_handle::TimeDisplaced &t = h->td;
+    const dqmc_handle::Section &sc = h->sec[DQMC_RED_TIME_DISPLACED];
     const long off_density = (t.what & DQMC_TD_GREENS) ? 2L * h->nb * t.R * h->n_dirs : 0;
     if (t.what & DQMC_TD_GREENS)
         HIPCHK(launch_tdm_greens(t.fast, h->n, h->nb, h->W, t.R, row, minus_identity, gl0, g0l, h->nn, t.src_of,
-                                 h->dir_ptr, h->pair_src, h->pair_trg, h->n_dirs, t.per_walker, (long)t.E, h->stream));
+                                 h->dir_ptr, h->pair_src, h->pair_trg, h->n_dirs, sc.per_walker, sc.bin_E, h->stream));
     if (t.what & DQMC_TD_DENSITY)
         HIPCHK(launch_tdm_density(h->n, h->nb, h->p.model_kind, h->W, t.R, row, minus_identity, g00, g0l, gl0, gll,
-                                  h->nn, h->dir_ptr, h->pair_src, h->pair_trg, h->n_dirs, t.per_walker, (long)t.E,
+                                  h->nn, h->dir_ptr, h->pair_src, h->pair_trg, h->n_dirs, sc.per_walker, sc.bin_E,
                                   off_density, h->stream));
     return 0;
 }
@@ -843,10 +821,11 @@ int dqmc_accumulate_susceptibilities(dqmc_handle *h, int32_t recalculate)
     CHK(binner_room(h, DQMC_BIN_SUSCEPTIBILITIES));
     const bool record = h->td.every != 0;
     if (record) CHK(binner_room(h, DQMC_BIN_TIME_DISPLACED));
-    const long total = (long)u->sus_n - 1;
+    const dqmc_handle::Section &sus = h->sec[DQMC_RED_SUSCEPTIBILITIES], &td = h->sec[DQMC_RED_TIME_DISPLACED];
+    const long total = sus.bin_E;
     CHK(true_greens(h, h->greens));                                 // G00 = greens!(mc)
     CHK(copy_mat(h, u->g00, h->tmp2));
-    HIPCHK(hipMemsetAsync(u->sus_per_walker, 0, sizeof(double) * h->W * total, h->stream));  // prepare!
+    HIPCHK(hipMemsetAsync(sus.per_walker, 0, sizeof(double) * h->W * total, h->stream));  // prepare!
     // cc_kernel: 4 a b + 2 cross on the attractive model's single block (HubbardModelAttractive.jl:250-266)
     const double cc_fac = h->p.model_kind == DQMC_ATTRACTIVE ? 2.0 : 1.0;
     if (h->K_cc) {
@@ -867,20 +846,20 @@ int dqmc_accumulate_susceptibilities(dqmc_handle *h, int32_t recalculate)
         if (record && l % h->td.every == 0)  // a launch of its own: sus_pairs_kernel and its sums stay as they are
             CHK(td_record(h, l / h->td.every, 0, u->g00, u->out[0], u->out[1], u->out[2]));
         HIPCHK(launch_sus_slice(h->n, h->nb, h->p.model_kind, h->W, u->g00, u->out[0], u->out[1], u->out[2], h->nn,
-                                h->dir_ptr, h->pair_src, h->pair_trg, h->n_dirs, h->K_loc, h->trg_of, u->sus_per_walker,
+                                h->dir_ptr, h->pair_src, h->pair_trg, h->n_dirs, h->K_loc, h->trg_of, sus.per_walker,
                                 total, h->stream));
         if (h->K_cc)
             HIPCHK(launch_cc_slice(h->cc, h->n, h->nb, h->W, cc_fac, cc_fac, u->out[0], u->out[1], u->out[2], h->nn,
-                                   h->dir_ptr, h->pair_src, h->pair_trg, h->n_dirs, u->sus_per_walker, total,
+                                   h->dir_ptr, h->pair_src, h->pair_trg, h->n_dirs, sus.per_walker, total,
                                    ut_cc_offset(h), h->stream));
     }
     {
         Timed t(h, DQMC_K_MISC);
-        HIPCHK(launch_sus_reduce(h->W, total, h->p.delta_tau, u->sus_per_walker, u->sus_acc, h->stream));
+        HIPCHK(launch_sus_reduce(h->W, total, h->p.delta_tau, sus.per_walker, sus.acc, h->stream));
     }
     if (record) {  // the accumulator takes the samples, walkers in order
         Timed t(h, DQMC_K_MISC);
-        HIPCHK(launch_sus_reduce(h->W, (long)h->td.E, 1.0, h->td.per_walker, h->td.acc, h->stream));
+        HIPCHK(launch_sus_reduce(h->W, td.bin_E, 1.0, td.per_walker, td.acc, h->stream));
     }
     if (h->bin[DQMC_BIN_SUSCEPTIBILITIES].on) CHK(binner_push_section(h, DQMC_BIN_SUSCEPTIBILITIES));
     if (record && h->bin[DQMC_BIN_TIME_DISPLACED].on) CHK(binner_push_section(h, DQMC_BIN_TIME_DISPLACED));
@@ -892,22 +871,15 @@ int dqmc_susceptibilities_size(dqmc_handle *h, size_t *n)
     if (!n) return DQMC_ERR_INVALID;
     if (!h->n_dirs) return fail(h, DQMC_ERR_STATE, "call dqmc_set_pair_directions first");
     CHK(ut_sus_layout(h));
-    *n = h->ut->sus_n;
-    return DQMC_OK;
+    return sec_size(h, DQMC_RED_SUSCEPTIBILITIES, n);
 }
 int dqmc_get_susceptibilities(dqmc_handle *h, double *host_out)
 {
     ENTER(h); NEED_UT(h);
-    if (!h->ut->sus_acc) return fail(h, DQMC_ERR_STATE, "nothing accumulated");
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(host_out, h->ut->sus_acc, h->ut->sus_n * sizeof(double), hipMemcpyDeviceToHost));
-    return DQMC_OK;
+    return sec_get(h, DQMC_RED_SUSCEPTIBILITIES, host_out);
 }
 int dqmc_export_susceptibilities(dqmc_handle *h, void *device_out)
 {
     ENTER(h); NEED_UT(h);
-    if (!h->ut->sus_acc) return fail(h, DQMC_ERR_STATE, "nothing accumulated");
-    HIPCHK(hipMemcpyAsync(device_out, h->ut->sus_acc, h->ut->sus_n * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return DQMC_OK;
+    return sec_export(h, DQMC_RED_SUSCEPTIBILITIES, device_out);
 }

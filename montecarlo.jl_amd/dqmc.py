@@ -592,15 +592,7 @@ class DQMC:
     def reduced(self, which="greens"):
         """dqmc_get_reduced: the global sums of the last reduction (the handle's own accumulators keep the local sums);
         `which` = greens | correlations | pairing | susceptibilities | time_displaced, layouts as the local getters"""
-        idx = {"greens": 0, "correlations": 1, "pairing": 2, "susceptibilities": 3,
-               "time_displaced": _lib.RED_TIME_DISPLACED}[which]
-        n = C.c_size_t()
-        size_fn = (lib().dqmc_accumulator_size, lib().dqmc_correlations_size, lib().dqmc_pairing_size,
-                   lib().dqmc_susceptibilities_size, lib().dqmc_time_displaced_size)[idx]
-        self._c(size_fn(self._h, C.byref(n)))
-        out = np.zeros(n.value)
-        self._c(lib().dqmc_get_reduced(self._h, idx, dptr(out)))
-        return out
+        return self._section(which, reduced=True)
 
     def reduced_analysis(self):
         st = _lib.Stats()
@@ -637,15 +629,33 @@ class DQMC:
     def reset_accumulators(self):
         self._c(lib().dqmc_reset_accumulators(self._h))
 
-    def accumulator_size(self):
+    # the accumulator sections: name -> (DQMC_RED_* index, size function, local getter)
+    _SECTIONS = {"greens": (0, "dqmc_accumulator_size", "dqmc_get_accumulators"),
+                 "correlations": (1, "dqmc_correlations_size", "dqmc_get_correlations"),
+                 "pairing": (2, "dqmc_pairing_size", "dqmc_get_pairing"),
+                 "susceptibilities": (3, "dqmc_susceptibilities_size", "dqmc_get_susceptibilities"),
+                 "time_displaced": (_lib.RED_TIME_DISPLACED, "dqmc_time_displaced_size", "dqmc_get_time_displaced")}
+
+    def _section_size(self, which):
         n = C.c_size_t()
-        self._c(lib().dqmc_accumulator_size(self._h, C.byref(n)))
+        self._c(getattr(lib(), self._SECTIONS[which][1])(self._h, C.byref(n)))
         return n.value
 
-    def accumulators(self):
-        out = np.zeros(self.accumulator_size())
-        self._c(lib().dqmc_get_accumulators(self._h, dptr(out)))
+    def _section(self, which, reduced=False):
+        """the raw sums of a section: ask its size, allocate, fetch the local sums or those of the last reduction"""
+        idx, _, getter = self._SECTIONS[which]
+        out = np.zeros(self._section_size(which))
+        if reduced:
+            self._c(lib().dqmc_get_reduced(self._h, idx, dptr(out)))
+        else:
+            self._c(getattr(lib(), getter)(self._h, dptr(out)))
         return out
+
+    def accumulator_size(self):
+        return self._section_size("greens")
+
+    def accumulators(self):
+        return self._section("greens")
 
     def export_accumulators(self, device_ptr):
         self._c(lib().dqmc_export_accumulators(self._h, C.c_void_p(device_ptr)))
@@ -839,18 +849,11 @@ class DQMC:
 
     def correlations_raw(self):
         """the raw sums [cdc][sdc_x][sdc_y][sdc_z][mx][my][mz][count] (layout of include/dqmc_hip.h)"""
-        n = C.c_size_t()
-        self._c(lib().dqmc_correlations_size(self._h, C.byref(n)))
-        out = np.zeros(n.value)
-        self._c(lib().dqmc_get_correlations(self._h, dptr(out)))
-        return out
+        return self._section("correlations")
 
     def correlations(self):
         """-> dict of means: CDC, SDCx, SDCy, SDCz per direction; Mx, My, Mz per site; count"""
-        n = C.c_size_t()
-        self._c(lib().dqmc_correlations_size(self._h, C.byref(n)))
-        out = np.zeros(n.value)
-        self._c(lib().dqmc_get_correlations(self._h, dptr(out)))
+        out = self._section("correlations")
         nd, N, cnt = self._ndirs, self.N, out[-1]
         names = ["CDC", "SDCx", "SDCy", "SDCz"]
         res = {k: out[i * nd:(i + 1) * nd] / cnt for i, k in enumerate(names)}
@@ -873,10 +876,7 @@ class DQMC:
 
     def pairing(self):
         """-> (mean of output[dir12, dir1, dir2] as pushed by finish!, sample count)"""
-        n = C.c_size_t()
-        self._c(lib().dqmc_pairing_size(self._h, C.byref(n)))
-        out = np.zeros(n.value)
-        self._c(lib().dqmc_get_pairing(self._h, dptr(out)))
+        out = self._section("pairing")
         cnt = out[-1]
         return out[:-1].reshape((self._ndirs, self._K, self._K), order="F") / cnt, cnt
 
@@ -941,10 +941,7 @@ class DQMC:
     def susceptibilities(self):
         """-> dict of means: CDS, SDSx, SDSy, SDSz per direction, PS[dir12, dir1, dir2] if local targets
         are set, CCS[dir12, dir_ii] if current targets are set, count"""
-        n = C.c_size_t()
-        self._c(lib().dqmc_susceptibilities_size(self._h, C.byref(n)))
-        out = np.zeros(n.value)
-        self._c(lib().dqmc_get_susceptibilities(self._h, dptr(out)))
+        out = self._section("susceptibilities")
         nd, cnt = self._ndirs, out[-1]
         res = {k: out[i * nd:(i + 1) * nd] / cnt for i, k in enumerate(["CDS", "SDSx", "SDSy", "SDSz"])}
         K = getattr(self, "_K", 0)
@@ -980,15 +977,11 @@ class DQMC:
         return dict(zip(("rows", "every", "what", "fast"), (int(v) for v in out)))
 
     def time_displaced_size(self):
-        n = C.c_size_t()
-        self._c(lib().dqmc_time_displaced_size(self._h, C.byref(n)))
-        return n.value
+        return self._section_size("time_displaced")
 
     def time_displaced_raw(self):
         """the accumulator as the device holds it: the sums in the layout of include/dqmc_hip.h, then the sample count"""
-        out = np.zeros(self.time_displaced_size())
-        self._c(lib().dqmc_get_time_displaced(self._h, dptr(out)))
-        return out
+        return self._section("time_displaced")
 
     def _td_tau(self):
         p = self.time_displaced_plan()
