@@ -209,6 +209,43 @@ int dqmc_get_global_stats(dqmc_handle *h, int32_t walker, dqmc_global_stats *out
  * first move: p = 0, accepted = 0, site = 0. */
 int dqmc_get_global_last(dqmc_handle *h, int32_t walker, double *p, int32_t *accepted, int32_t *site);
 
+/* ---- sign reweighting -------------------------------------------------------------------------------------------
+ * The reference only reports the sign problem: a negative ratio is pushed to negative_probability (DQMC.jl:562-563) and
+ * the measurements go on adding the bare sample (generic.jl:207-215).  Where the weight w of a field is not positive -
+ * the repulsive model away from half filling or on a frustrated lattice - that is the average under |w|, not under w.
+ * Like the global moves this is a defined extension, off by default: with it on, every accumulator and every binner
+ * takes s O in the place of O, s = the sign of the field, next to the sum of s, and <O> = <O s> / <s>.
+ * s_w = prod_b sign_b of walker w, sign_b as dqmc_logdet returns it.  The determinant does not change under a cyclic
+ * rotation of the slices, so s_w belongs to the field, not to current_slice.  It is taken from the values kept for the
+ * global moves (one slice chain when the field has changed since, none otherwise: the dqmc_accumulate_* calls of one
+ * measurement point share it).  The attractive model's weight is a square: s_w = +1, no chain is run.  The evaluation
+ * leaves the Markov chain alone, as dqmc_logdet does: mc.s.greens, the stack slots, current_slice, the RNG cursors.
+ * A unit whose sign comes out 0 (A2 singular or not finite): the walker's sample is left out of every section fed by
+ * that call - it is not read, not added with weight 0 to a count - and the walker's counter of dqmc_get_sign_failures
+ * goes up by one.  (Its binners, which advance in step for all walkers, take 0 for s x and for s: a pair that changes
+ * neither sum of the ratio.)
+ * With weighting on: [sum G] becomes [sum s G], [sum G.^2] [sum s G.^2], the occupation [sum s (1 - G_ii)], and so on
+ * for every section of "measurement accumulators" ... "time-displaced recording" below; each section's last double stays
+ * the plain number of samples (walkers kept).  Walkers are added in the order of the unsigned sums, so that with every
+ * s_w = +1 all sums and all binner levels are bit for bit those of a handle with weighting off.  With weighting off
+ * nothing is evaluated or launched, and every size, layout and result is that of a handle without it. */
+/* on != 0 / 0.  DQMC_ERR_STATE if any section or binner holds samples (dqmc_reset_accumulators first): signed and
+ * unsigned sums never mix.  The sums of signs start at zero. */
+int dqmc_set_sign_weighting(dqmc_handle *h, int32_t on);
+int dqmc_get_sign_weighting(dqmc_handle *h, int32_t *on);
+/* s_w (+1 / -1; 0: see above) of every walker's current field, n_walkers entries; works with weighting off too */
+int dqmc_get_sign(dqmc_handle *h, int32_t *sign /* n_walkers */);
+/* samples left out per walker since dqmc_create (n_walkers entries; dqmc_reset_accumulators does not clear them) */
+int dqmc_get_sign_failures(dqmc_handle *h, int64_t *count /* n_walkers */);
+/* The section DQMC_RED_SIGN: one sum of s per DQMC_RED_* section in front of it, in enum order (the sections are fed at
+ * different times, so each has its own denominator): DQMC_RED_SIGN doubles, no trailing count - a section's own last
+ * double is that.  Entry k grows by sum_w s_w with every call that feeds section k (dqmc_accumulate_susceptibilities
+ * feeds DQMC_RED_SUSCEPTIBILITIES and, with recording on, DQMC_RED_TIME_DISPLACED); it returns to zero with
+ * dqmc_reset_accumulators and when section k is laid out anew.  All zero while weighting is off. */
+int dqmc_sign_sums_size(dqmc_handle *h, size_t *n_doubles);
+int dqmc_get_sign_sums(dqmc_handle *h, double *host_out);
+int dqmc_export_sign_sums(dqmc_handle *h, void *device_out);
+
 /* ---- measurement accumulators (stand-in for push!(LogBinner, greens(mc)),
  * measurements/generic.jl:207-215,260-263).  dqmc_accumulate_greens adds, for
  * every walker of this handle, the true G, G.^2 and the occupation 1-G_ii into
@@ -383,6 +420,12 @@ enum { DQMC_BIN_TIME_DISPLACED = 5 };
 /* LogBinner(zero, capacity = capacity) for every walker and element of a measurement section (generic.jl:39);
  * capacity 0 = 100000.  The section's measurement must be configured (pair directions, local / current targets; the
  * susceptibilities also need dqmc_prepare); if its layout changes afterwards, enable again.  Enabling again starts anew. */
+/* With sign weighting on, every section pushes s_w x, and s_w itself goes into a one-element binner of its own per
+ * section, DQMC_BIN_SIGN + k for the section with DQMC_RED_* index k (sections are pushed at different times, so each has
+ * its own push count).  It is made with the section's binner (dqmc_binner_enable, or dqmc_set_sign_weighting for the
+ * binners enabled before it), has its capacity and push count, and is read like any other binner; it cannot be enabled
+ * on its own.  The error of a ratio <O s> / <s> is the host's to form, from level 0 of both (dqmc.py: signed()). */
+enum { DQMC_BIN_SIGN = 6 };
 int dqmc_binner_enable(dqmc_handle *h, int32_t which, int64_t capacity);
 /* elements per walker, levels and pushes so far (length(obs), BinningAnalysis' count at level 0) */
 int dqmc_binner_size(dqmc_handle *h, int32_t which, size_t *n_elements, int32_t *n_levels, int64_t *n_pushed);
@@ -436,6 +479,10 @@ enum { DQMC_RED_GREENS = 0, DQMC_RED_CORRELATIONS = 1, DQMC_RED_PAIRING = 2, DQM
  * samples], dqmc_time_displaced_size doubles.  It returns DQMC_ERR_STATE when the two local counts differed at the
  * reduction, i.e. recording was (re)set after susceptibility passes with no dqmc_reset_accumulators since. */
 enum { DQMC_RED_TIME_DISPLACED = 4 };
+/* With sign weighting on (dqmc_set_sign_weighting) the DQMC_RED_SIGN sums of signs are packed behind the time-displaced
+ * rows, in front of the counters: dqmc_reduce_size grows by exactly DQMC_RED_SIGN; with weighting off the buffer is byte
+ * for byte the one above and dqmc_get_reduced(DQMC_RED_SIGN) returns DQMC_ERR_STATE. */
+enum { DQMC_RED_SIGN = 5 };
 int dqmc_get_reduced(dqmc_handle *h, int32_t which, double *host_out);
 int dqmc_get_reduced_stats(dqmc_handle *h, dqmc_stats *out);
 

@@ -16,6 +16,7 @@ ATTRACTIVE, REPULSIVE = 0, 1
 BIN_SECTIONS = ("greens", "correlations", "pairing", "susceptibilities", "user")  # DQMC_BIN_*
 BIN_TIME_DISPLACED, RED_TIME_DISPLACED = 5, 4  # DQMC_BIN_TIME_DISPLACED, DQMC_RED_TIME_DISPLACED (enums of their own)
 TD_GREENS, TD_DENSITY = 1, 2                   # DQMC_TD_*
+BIN_SIGN, RED_SIGN = 6, 5                      # DQMC_BIN_SIGN (+ a section's DQMC_RED_* index), DQMC_RED_SIGN
 K_FAMILIES = ("gemm", "qr", "trsm", "sweep", "misc", "flush")
 
 
@@ -132,6 +133,13 @@ SIGNATURES = {
     "dqmc_global_move": (C.c_int, [_H, C.c_int32, C.c_int32]),
     "dqmc_set_global_rate": (C.c_int, [_H, C.c_int32, C.c_int32]),
     "dqmc_get_global_stats": (C.c_int, [_H, C.c_int32, C.POINTER(GlobalStats)]),
+    "dqmc_set_sign_weighting": (C.c_int, [_H, C.c_int32]),
+    "dqmc_get_sign_weighting": (C.c_int, [_H, C.POINTER(C.c_int32)]),
+    "dqmc_get_sign": (C.c_int, [_H, C.POINTER(C.c_int32)]),
+    "dqmc_get_sign_failures": (C.c_int, [_H, _i64p]),
+    "dqmc_sign_sums_size": (C.c_int, [_H, C.POINTER(C.c_size_t)]),
+    "dqmc_get_sign_sums": (C.c_int, [_H, _dp]),
+    "dqmc_export_sign_sums": (C.c_int, [_H, C.c_void_p]),
     "dqmc_accumulate_greens": (C.c_int, [_H]),
     "dqmc_accumulator_size": (C.c_int, [_H, C.POINTER(C.c_size_t)]),
     "dqmc_reset_accumulators": (C.c_int, [_H]),

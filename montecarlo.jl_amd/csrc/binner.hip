@@ -61,6 +61,35 @@ __global__ __launch_bounds__(256) void binner_push_kernel(int E, int lmax, int t
     }
 }
 
+// binner_push_kernel for the sources that read G themselves, with the sign (sign.hip): pushes s_w x, 0 for a walker
+// left out.  The pair sums of the CORR source arrive signed already (corr_reduce_signed_kernel).
+template <int MODE>
+__global__ __launch_bounds__(256) void binner_push_signed_kernel(int E, int lmax, int top, long WE,
+                                                                 const double *__restrict__ src,
+                                                                 const double *__restrict__ G, long stride_unit, int n,
+                                                                 int nb, int model, int n_dirs,
+                                                                 const double *__restrict__ sw, double *__restrict__ xs,
+                                                                 double *__restrict__ x2, double *__restrict__ c)
+{
+    const int w = blockIdx.y;
+    const double sg = sw[w];
+    for (long el = blockIdx.x * 256L + threadIdx.x; el < E; el += gridDim.x * 256L) {
+        const int e = (int)el;
+        double x = 0.0;
+        if (MODE == BIN_SRC_CORR && e < 4 * n_dirs) x = src[(long)w * 4 * n_dirs + e];
+        else if (sg != 0.0) x = sg * bin_sample<MODE>(w, e, src, G, stride_unit, n, nb, model, n_dirs, E, 1.0);
+        long at = (long)w * E + e;
+        for (int l = 0; l < lmax; ++l, at += WE) {
+            xs[at] += x;
+            x2[at] += x * x;
+            x = 0.5 * (c[at] + x);
+        }
+        xs[at] += x;
+        x2[at] += x * x;
+        if (lmax < top) c[at] = x;
+    }
+}
+
 hipError_t launch_binner_push(const BinPush &p, int W, int E, int L, int lmax, double *xs, double *x2, double *c,
                               hipStream_t s)
 {
@@ -73,10 +102,16 @@ hipError_t launch_binner_push(const BinPush &p, int W, int E, int L, int lmax, d
 #define BIN_LAUNCH(MODE)                                                                                               \
     hipLaunchKernelGGL(binner_push_kernel<MODE>, grid, block, 0, s, E, lmax, L - 1, WE, p.src, p.G, p.stride_unit,  \
                        p.n, p.nb, p.model, p.n_dirs, p.scale, xs, x2, c)
-    if (p.mode == BIN_SRC_GREENS) BIN_LAUNCH(BIN_SRC_GREENS);
+#define BIN_LAUNCH_SIGNED(MODE)                                                                                        \
+    hipLaunchKernelGGL(binner_push_signed_kernel<MODE>, grid, block, 0, s, E, lmax, L - 1, WE, p.src, p.G,            \
+                       p.stride_unit, p.n, p.nb, p.model, p.n_dirs, p.sw, xs, x2, c)
+    if (p.sw && p.mode == BIN_SRC_GREENS) BIN_LAUNCH_SIGNED(BIN_SRC_GREENS);
+    else if (p.sw && p.mode == BIN_SRC_CORR) BIN_LAUNCH_SIGNED(BIN_SRC_CORR);
+    else if (p.mode == BIN_SRC_GREENS) BIN_LAUNCH(BIN_SRC_GREENS);
     else if (p.mode == BIN_SRC_CORR) BIN_LAUNCH(BIN_SRC_CORR);
     else BIN_LAUNCH(BIN_SRC_PLAIN);
 #undef BIN_LAUNCH
+#undef BIN_LAUNCH_SIGNED
     return hipGetLastError();
 }
 

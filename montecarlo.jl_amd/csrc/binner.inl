@@ -5,7 +5,7 @@
 static const int64_t BIN_DEFAULT_CAPACITY = 100000;  // BinningAnalysis' _default_capacity
 
 #define BIN_OK(h, which)                                                                        \
-    if ((which) < DQMC_BIN_GREENS || (which) > DQMC_BIN_TIME_DISPLACED)                         \
+    if ((which) < DQMC_BIN_GREENS || (which) >= DQMC_BIN_SIGN + DQMC_RED_SIGN)                  \
         return fail((h), DQMC_ERR_INVALID, "binner section out of range");                      \
     if (!(h)->bin[(which)].on) return fail((h), DQMC_ERR_STATE, "this section's binner is not enabled")
 
@@ -18,8 +18,10 @@ static const dqmc_handle::Section &binner_section(dqmc_handle *h, int which)
 // elements of a section as its measurement is configured now (0: not configured)
 static long binner_section_elements(dqmc_handle *h, int which)
 {
-    return which == DQMC_BIN_USER ? h->bin[DQMC_BIN_USER].E : binner_section(h, which).bin_E;
+    return which == DQMC_BIN_USER || which >= DQMC_BIN_SIGN ? h->bin[which].E : binner_section(h, which).bin_E;
 }
+// the binner of the signs that go with a measurement section's pushes: DQMC_BIN_SIGN + the section's DQMC_RED_* index
+static int binner_sign_of(int which) { return DQMC_BIN_SIGN + (which == DQMC_BIN_TIME_DISPLACED ? DQMC_RED_TIME_DISPLACED : which); }
 static int binner_levels(int64_t capacity)  // ceil(log2(capacity + 1))
 {
     int L = 1;
@@ -90,7 +92,14 @@ static int binner_push_section(dqmc_handle *h, int which)
     p.src = binner_section(h, which).per_walker;
     // finish!: * delta_tau as sus_reduce_kernel (the time-displaced rows go as tdm.hip stored them)
     if (which == DQMC_BIN_SUSCEPTIBILITIES) p.scale = h->p.delta_tau;
-    return binner_push(h, which, p);
+    if (!h->sign_on) return binner_push(h, which, p);
+    // sign weighting: s_w x for the sources that read G (the per_walker ones are signed already), and s_w itself into
+    // the section's sign binner, which has the section's capacity and push count
+    p.sw = h->sign_sw;
+    CHK(binner_push(h, which, p));
+    BinPush q;
+    q.src = h->sign_sw;
+    return binner_push(h, binner_sign_of(which), q);
 }
 static int binner_reset(dqmc_handle *h)
 {
@@ -126,7 +135,8 @@ int dqmc_binner_enable(dqmc_handle *h, int32_t which, int64_t capacity)
 {
     ENTER(h);
     if (which < DQMC_BIN_GREENS || which == DQMC_BIN_USER || which > DQMC_BIN_TIME_DISPLACED)
-        return fail(h, DQMC_ERR_INVALID, "dqmc_binner_enable takes a measurement section (dqmc_binner_user_create makes the user binner)");
+        return fail(h, DQMC_ERR_INVALID, "dqmc_binner_enable takes a measurement section (dqmc_binner_user_create makes the user "
+                                         "binner, the sign binners come with their sections)");
     if (which == DQMC_BIN_TIME_DISPLACED) {
         NEED_PREPARED(h);
         if (!h->td.every) return fail(h, DQMC_ERR_STATE, "call dqmc_set_time_displaced first");
@@ -138,7 +148,9 @@ int dqmc_binner_enable(dqmc_handle *h, int32_t which, int64_t capacity)
     }
     const long E = binner_section_elements(h, which);
     if (!E) return fail(h, DQMC_ERR_STATE, "configure the section's measurement (pair directions / local targets) first");
-    return binner_alloc(h, which, E, capacity);
+    CHK(binner_alloc(h, which, E, capacity));
+    if (h->sign_on) CHK(binner_alloc(h, binner_sign_of(which), 1, h->bin[which].cap));
+    return DQMC_OK;
 }
 int dqmc_binner_user_create(dqmc_handle *h, int64_t n_elements, int64_t capacity)
 {

@@ -103,7 +103,8 @@ struct dqmc_handle {
         size_t n = 0, n_red = 0;  // doubles the local getter reports (0: not configured) / that go into the reduction
         long bin_E = 0;
         int bin_mode = BIN_SRC_PLAIN;
-    } sec[DQMC_RED_TIME_DISPLACED + 1];
+    //   sign             [sum of s per DQMC_RED_* section above], no count; packed only while sign weighting is on
+    } sec[DQMC_RED_SIGN + 1];
     // correlation measurements (EachSitePairByDistance tables set by the host)
     int n_dirs = 0;
     int *dir_ptr = nullptr, *pair_src = nullptr, *pair_trg = nullptr;
@@ -142,7 +143,7 @@ struct dqmc_handle {
     size_t red_cap = 0;
     dqmc_stats red_stats{};
     bool red_valid = false;
-    size_t red_sizes[DQMC_RED_TIME_DISPLACED + 1] = {0, 0, 0, 0, 0};  // packed section sizes of the LAST reduction (dqmc_get_reduced checks against these)
+    size_t red_sizes[DQMC_RED_SIGN + 1] = {0, 0, 0, 0, 0, 0};  // packed section sizes of the LAST reduction (dqmc_get_reduced checks against these)
     bool red_td_ok = false;  // the time-displaced and susceptibility sample counts agreed when that reduction was packed
     // logarithmic binners (binner.inl), one per DQMC_BIN_* section: xs, x2 [L][W][E], c [L - 1][W][E], out = finish scratch
     struct Binner {
@@ -150,7 +151,7 @@ struct dqmc_handle {
         int E = 0, L = 0;
         int64_t cap = 0, T = 0;  // capacity and pushes so far: count[level] = T >> level for every element
         double *xs = nullptr, *x2 = nullptr, *c = nullptr, *out = nullptr;
-    } bin[6];
+    } bin[DQMC_BIN_SIGN + DQMC_RED_SIGN];  // (DQMC_BIN_SIGN + k: the signs pushed with section k = a DQMC_RED_* index)
     // time-displaced recording (unequal_time.inl, tdm.hip): every == 0: off, nothing allocated.  The sample (bin_E doubles
     // per walker in the layout of include/dqmc_hip.h) and the sums are sec[DQMC_RED_TIME_DISPLACED]; src_of [n_dirs][n]
     // only with the fast form
@@ -167,6 +168,12 @@ struct dqmc_handle {
     long long gm_cache_version = -1;
     int gm_rate = 0, gm_kind = DQMC_GLOBAL_FLIP_SITE;
     long long gm_updates = 0;  // updates since dqmc_prepare: update u belongs to sweep 1 + u / (2 slices)
+    // sign reweighting (global_move.inl, sign.hip): off by default.  sign_sw [W + 2]: s_w of the measurement point in
+    // hand as doubles, their sum, the walkers kept (sign_begin writes it in front of every signed sum); sign_fail [W]:
+    // samples left out per walker because a unit's sign came out 0
+    bool sign_on = false;
+    double *sign_sw = nullptr;
+    long long *sign_fail = nullptr;
 };
 
 // ---------------------------------------------------------------------------
@@ -219,6 +226,9 @@ static int sec_layout(dqmc_handle *h, int which, size_t n, size_t n_red, long bi
     dfree(h, &s.acc);
     dfree(h, &s.per_walker);
     s = dqmc_handle::Section{};
+    // the sum of signs that went with the old sums goes with them
+    if (which < DQMC_RED_SIGN && h->sec[DQMC_RED_SIGN].acc)
+        HIPCHK(hipMemsetAsync(h->sec[DQMC_RED_SIGN].acc + which, 0, sizeof(double), h->stream));
     if (!n) return 0;
     CHK(dalloc(h, &s.acc, n));
     if (samples) CHK(dalloc(h, &s.per_walker, (size_t)h->W * samples));
@@ -1397,6 +1407,9 @@ int dqmc_create(const dqmc_params *p, dqmc_handle **out)
     {
         const size_t acc_n = 2 * cn + (size_t)nb * h->n + 1;
         CCHK(sec_layout(h, DQMC_RED_GREENS, acc_n, acc_n, (long)(cn + (size_t)nb * h->n), 0, BIN_SRC_GREENS));
+        CCHK(sec_layout(h, DQMC_RED_SIGN, DQMC_RED_SIGN, 0, 0, 0));
+        CCHK(dalloc(h, &h->sign_sw, (size_t)h->W + 2));
+        CCHK(dalloc(h, &h->sign_fail, (size_t)h->W));
     }
     CCHK(init_stack(h));
     CHIP(hipStreamSynchronize(h->stream));
@@ -1736,14 +1749,22 @@ int dqmc_get_stats(dqmc_handle *h, int32_t w, dqmc_stats *out)
 // layout has changed; binner_push_section pushes the samples the measurement kernels have just left on the device
 static int binner_room(dqmc_handle *h, int which);
 static int binner_push_section(dqmc_handle *h, int which);
+// global_move.inl: with sign weighting on, s_w of the current fields into sign_sw and their sum into the sign sums of the
+// sections about to be fed (DQMC_RED_* indices; sec_b < 0: one section); nothing with it off.  Runs a slice chain unless
+// the cache of the current field holds, so it comes in front of true_greens (the chain overwrites tmp1 / tmp2).
+static int sign_begin(dqmc_handle *h, int sec_a, int sec_b = -1);
 int dqmc_accumulate_greens(dqmc_handle *h)
 {
     ENTER(h); NEED_PREPARED(h);
     CHK(binner_room(h, DQMC_BIN_GREENS));
+    CHK(sign_begin(h, DQMC_RED_GREENS));
     CHK(true_greens(h, h->greens));
     {
         Timed t(h, DQMC_K_MISC);
-        HIPCHK(launch_accumulate(h->n, h->nb, h->W, h->tmp2, h->nn, h->sec[DQMC_RED_GREENS].acc, h->stream));
+        if (h->sign_on)
+            HIPCHK(launch_accumulate_signed(h->n, h->nb, h->W, h->tmp2, h->nn, h->sign_sw, h->sec[DQMC_RED_GREENS].acc, h->stream));
+        else
+            HIPCHK(launch_accumulate(h->n, h->nb, h->W, h->tmp2, h->nn, h->sec[DQMC_RED_GREENS].acc, h->stream));
     }
     if (h->bin[DQMC_BIN_GREENS].on) CHK(binner_push_section(h, DQMC_BIN_GREENS));
     return DQMC_OK;
@@ -1796,8 +1817,16 @@ int dqmc_accumulate_correlations(dqmc_handle *h)
     ENTER(h); NEED_PREPARED(h);
     if (!h->n_dirs) return fail(h, DQMC_ERR_STATE, "call dqmc_set_pair_directions first");
     CHK(binner_room(h, DQMC_BIN_CORRELATIONS));
+    CHK(sign_begin(h, DQMC_RED_CORRELATIONS));
     CHK(true_greens(h, h->greens));
-    {
+    if (h->sign_on) {
+        Timed t(h, DQMC_K_MISC);
+        const dqmc_handle::Section &sc = h->sec[DQMC_RED_CORRELATIONS];
+        HIPCHK(launch_correlation_pairs(h->n, h->nb, h->p.model_kind, h->W, h->tmp2, h->nn, h->dir_ptr, h->pair_src,
+                                        h->pair_trg, h->n_dirs, sc.per_walker, h->stream));
+        HIPCHK(launch_corr_reduce_signed(h->n, h->nb, h->p.model_kind, h->W, h->tmp2, h->nn, h->n_dirs, sc.per_walker,
+                                         h->sign_sw, sc.acc, h->stream));
+    } else {
         Timed t(h, DQMC_K_MISC);
         HIPCHK(launch_correlations(h->n, h->nb, h->p.model_kind, h->W, h->tmp2, h->nn, h->dir_ptr, h->pair_src,
                                    h->pair_trg, h->n_dirs, h->sec[DQMC_RED_CORRELATIONS].per_walker,
@@ -1831,8 +1860,15 @@ int dqmc_accumulate_pairing(dqmc_handle *h)
     ENTER(h); NEED_PREPARED(h);
     if (!h->K_loc) return fail(h, DQMC_ERR_STATE, "call dqmc_set_local_targets first");
     CHK(binner_room(h, DQMC_BIN_PAIRING));
+    CHK(sign_begin(h, DQMC_RED_PAIRING));
     CHK(true_greens(h, h->greens));
-    {
+    if (h->sign_on) {
+        Timed t(h, DQMC_K_MISC);
+        const dqmc_handle::Section &sc = h->sec[DQMC_RED_PAIRING];
+        HIPCHK(launch_pairing_pairs(h->n, h->nb, h->W, h->tmp2, h->nn, h->dir_ptr, h->pair_src, h->pair_trg, h->n_dirs,
+                                    h->K_loc, h->trg_of, sc.per_walker, h->stream));
+        HIPCHK(launch_reduce_signed(h->W, sc.bin_E, 1.0, sc.per_walker, h->sign_sw, sc.acc, h->stream));
+    } else {
         Timed t(h, DQMC_K_MISC);
         HIPCHK(launch_pairing(h->n, h->nb, h->W, h->tmp2, h->nn, h->dir_ptr, h->pair_src, h->pair_trg, h->n_dirs,
                               h->K_loc, h->trg_of, h->sec[DQMC_RED_PAIRING].per_walker, h->sec[DQMC_RED_PAIRING].acc,
@@ -1853,7 +1889,7 @@ int dqmc_reset_accumulators(dqmc_handle *h)
 
 // ---- size / host get / device export of a section's sums (dqmc_handle::Section) --------------------------------------
 static const char *const SEC_NEED[] = {nullptr, "call dqmc_set_pair_directions first", "call dqmc_set_local_targets first",
-                                       "nothing accumulated", "call dqmc_set_time_displaced first"};
+                                       "nothing accumulated", "call dqmc_set_time_displaced first", nullptr};
 static int sec_size(dqmc_handle *h, int which, size_t *n)
 {
     if (!h || !n) return DQMC_ERR_INVALID;
@@ -1893,8 +1929,8 @@ int dqmc_export_pairing(dqmc_handle *h, void *device_out) { ENTER(h); return sec
 // ---------------------------------------------------------------------------
 // Measurement reduction over ranks: every accumulator the handle keeps and the DQMCAnalysis
 // counters, as ONE packed device buffer of doubles [sums | maxima | minima]:
-//   sums   = acc (G, G.^2, occupation, count), correlations, pairing, susceptibilities (each if configured),
-//            then prop_local, acc_local, negative_probability {sum, count}, propagation_error {sum, count}
+//   sums   = acc (G, G.^2, occupation, count), correlations, pairing, susceptibilities, time-displaced rows (each if
+//            configured), the sums of signs (with sign weighting on), then prop_local, acc_local, negative_probability {sum, count}, propagation_error {sum, count}
 //   maxima = negative_probability.max, propagation_error.max      minima = the two .min
 // (MagnitudeStats, DQMC.jl:4-47).  dqmc_reduce runs three ncclAllReduce (sum / max / min) on the handle's stream;
 // a host-side collective (MPI from Julia, gloo in the tests) can do the same through export / import.
@@ -1916,7 +1952,7 @@ static int red_pack(dqmc_handle *h)
         h->red_cap = tot;
     }
     size_t off = 0;
-    for (int i = 0; i <= DQMC_RED_TIME_DISPLACED; ++i) {
+    for (int i = 0; i <= DQMC_RED_SIGN; ++i) {
         const dqmc_handle::Section &s = h->sec[i];
         if (s.n_red)
             HIPCHK(hipMemcpyAsync(h->red_buf + off, s.acc, s.n_red * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
@@ -2052,13 +2088,13 @@ int dqmc_reduce_import(dqmc_handle *h, const double *host_in)
 int dqmc_get_reduced(dqmc_handle *h, int32_t which, double *host_out)
 {
     ENTER(h);
-    if (!host_out || which < 0 || which > DQMC_RED_TIME_DISPLACED) return fail(h, DQMC_ERR_INVALID, "dqmc_get_reduced: bad arguments");
+    if (!host_out || which < 0 || which > DQMC_RED_SIGN) return fail(h, DQMC_ERR_INVALID, "dqmc_get_reduced: bad arguments");
     if (!h->red_valid) return fail(h, DQMC_ERR_STATE, "call dqmc_reduce first");
     size_t off = 0;
     for (int i = 0; i < which; ++i) off += h->sec[i].n_red;
     const size_t cnt = h->sec[which].n_red;
     if (cnt == 0) return fail(h, DQMC_ERR_STATE, "dqmc_get_reduced: this accumulator is not configured");
-    for (int i = 0; i <= DQMC_RED_TIME_DISPLACED; ++i)  // (sizes as they are NOW against the sizes that were packed)
+    for (int i = 0; i <= DQMC_RED_SIGN; ++i)  // (sizes as they are NOW against the sizes that were packed)
         if (h->sec[i].n_red != h->red_sizes[i])
             return fail(h, DQMC_ERR_STATE, "accumulators were reconfigured after the last reduction: call dqmc_reduce again");
     if (h->red_cap < red_nsum(h) + 4) return fail(h, DQMC_ERR_STATE, "call dqmc_reduce first");

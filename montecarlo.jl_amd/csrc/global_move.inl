@@ -23,6 +23,24 @@ static int logdet_current(dqmc_handle *h)
     h->gm_cache_version = h->conf_version;
     return 0;
 }
+// ---- sign reweighting (include/dqmc_hip.h "sign reweighting"; kernels in sign.hip) ---------------------------------
+// s_w = prod_b sign_b is a property of the field (the determinant does not change under a cyclic rotation of the slices),
+// so it comes from the cache above at any current_slice, and the accumulate calls of one measurement point share one
+// chain.  The attractive model's weight is a square: +1 by construction, no chain.
+static int sign_begin(dqmc_handle *h, int sec_a, int sec_b)
+{
+    if (!h->sign_on) return 0;
+    const int *sg = nullptr;
+    if (h->p.model_kind == DQMC_REPULSIVE) {
+        CHK(logdet_current(h));
+        sg = h->gm_sg[0];
+    }
+    double *sums = h->sec[DQMC_RED_SIGN].acc;
+    Timed t(h, DQMC_K_MISC);
+    HIPCHK(launch_sign_prepare(h->nb, h->W, sg, h->sign_sw, h->sign_fail, sums + sec_a, sec_b >= 0 ? sums + sec_b : nullptr,
+                               h->stream));
+    return 0;
+}
 // one move of `walker` (< 0: every walker); leaves the handle as dqmc_prepare would for the resulting fields
 static int global_move(dqmc_handle *h, int kind, int walker)
 {
@@ -70,6 +88,81 @@ int dqmc_logdet(dqmc_handle *h, double *logabsdet, int32_t *sign)
     static_assert(sizeof(int) == sizeof(int32_t), "sign buffer");
     HIPCHK(hipMemcpy(sign, h->gm_sg[0], sizeof(int) * h->units, hipMemcpyDeviceToHost));
     return DQMC_OK;
+}
+int dqmc_get_sign(dqmc_handle *h, int32_t *sign)
+{
+    ENTER(h);
+    if (!sign) return fail(h, DQMC_ERR_INVALID, "dqmc_get_sign: null output");
+    if (h->p.model_kind != DQMC_REPULSIVE) {  // a square: nothing to launch
+        for (int w = 0; w < h->W; ++w) sign[w] = 1;
+        return DQMC_OK;
+    }
+    CHK(logdet_current(h));
+    CHK(dqmc_synchronize(h));
+    std::vector<int> sg(h->units);
+    HIPCHK(hipMemcpy(sg.data(), h->gm_sg[0], sizeof(int) * h->units, hipMemcpyDeviceToHost));
+    for (int w = 0; w < h->W; ++w) {
+        int s = 1;
+        for (int b = 0; b < h->nb; ++b) s *= sg[(size_t)w * h->nb + b];
+        sign[w] = s;
+    }
+    return DQMC_OK;
+}
+int dqmc_set_sign_weighting(dqmc_handle *h, int32_t on)
+{
+    ENTER(h);
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (int i = 0; i < DQMC_RED_SIGN; ++i) {  // signed and unsigned sums never mix
+        const dqmc_handle::Section &sc = h->sec[i];
+        if (!sc.n) continue;
+        double cnt = 0.0;
+        HIPCHK(hipMemcpy(&cnt, sc.acc + sc.n - 1, sizeof(double), hipMemcpyDeviceToHost));
+        if (cnt != 0.0)
+            return fail(h, DQMC_ERR_STATE, "dqmc_set_sign_weighting: a section has samples: call dqmc_reset_accumulators first");
+    }
+    for (int which = DQMC_BIN_GREENS; which <= DQMC_BIN_TIME_DISPLACED; ++which)
+        if (which != DQMC_BIN_USER && h->bin[which].on && h->bin[which].T)
+            return fail(h, DQMC_ERR_STATE, "dqmc_set_sign_weighting: a binner has samples: call dqmc_reset_accumulators first");
+    h->sign_on = on != 0;
+    h->red_valid = false;  // (re)sized: the last reduction is void
+    dqmc_handle::Section &sg = h->sec[DQMC_RED_SIGN];
+    sg.n_red = h->sign_on ? sg.n : 0;
+    HIPCHK(hipMemsetAsync(sg.acc, 0, sg.n * sizeof(double), h->stream));
+    for (int which = DQMC_BIN_GREENS; which <= DQMC_BIN_TIME_DISPLACED; ++which) {
+        if (which == DQMC_BIN_USER) continue;
+        dqmc_handle::Binner &sb = h->bin[binner_sign_of(which)];
+        if (h->sign_on && h->bin[which].on) CHK(binner_alloc(h, binner_sign_of(which), 1, h->bin[which].cap));
+        else if (sb.on) binner_free(h, sb);
+    }
+    return dqmc_synchronize(h);
+}
+int dqmc_get_sign_weighting(dqmc_handle *h, int32_t *on)
+{
+    if (!h || !on) return DQMC_ERR_INVALID;
+    *on = h->sign_on ? 1 : 0;
+    return DQMC_OK;
+}
+int dqmc_get_sign_failures(dqmc_handle *h, int64_t *count)
+{
+    ENTER(h);
+    if (!count) return fail(h, DQMC_ERR_INVALID, "dqmc_get_sign_failures: null output");
+    static_assert(sizeof(long long) == sizeof(int64_t), "counter buffer");
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(count, h->sign_fail, sizeof(int64_t) * h->W, hipMemcpyDeviceToHost));
+    return DQMC_OK;
+}
+int dqmc_sign_sums_size(dqmc_handle *h, size_t *n) { return sec_size(h, DQMC_RED_SIGN, n); }
+int dqmc_get_sign_sums(dqmc_handle *h, double *host_out)
+{
+    ENTER(h);
+    if (!host_out) return fail(h, DQMC_ERR_INVALID, "host_out is NULL");
+    return sec_get(h, DQMC_RED_SIGN, host_out);
+}
+int dqmc_export_sign_sums(dqmc_handle *h, void *device_out)
+{
+    ENTER(h);
+    if (!device_out) return fail(h, DQMC_ERR_INVALID, "device_out is NULL");
+    return sec_export(h, DQMC_RED_SIGN, device_out);
 }
 int dqmc_global_move(dqmc_handle *h, int32_t kind, int32_t walker)
 {

@@ -439,6 +439,9 @@ struct BinPush {
     long stride_unit = 0;
     int n = 0, nb = 1, model = 0, n_dirs = 0;
     double scale = 1.0;
+    // sign reweighting: s_w per walker (sign.hip).  The GREENS and CORR sources, which read G themselves, then take the
+    // signed kernel and push s_w x (0 for s_w = 0); a PLAIN source has been signed where it was written.
+    const double *sw = nullptr;
 };
 hipError_t launch_binner_push(const BinPush &p, int W, int E, int L, int lmax, double *xs, double *x2, double *c,
                               hipStream_t s);
@@ -467,6 +470,26 @@ hipError_t launch_gm_propose(int N, int M, int n_walkers, int kind, int walker, 
 hipError_t launch_gm_decide(int N, int M, int nb, int n_walkers, int kind, double lambda, int check_sign, int8_t *conf,
                             WalkerRng *rng, GlobalMoveState *gm, DevStats *stats, double *lad_cur, int *sg_cur,
                             const double *lad_prop, const int *sg_prop, hipStream_t s);
+// sign reweighting (sign.hip).  sw [n_walkers + 2]: s_w as a double (+1, -1, 0: left out), sum_w s_w, walkers kept.
+// launch_sign_prepare builds it from the per-unit signs sg [n_walkers][nb] (nullptr: all +1), counts the walkers left
+// out in failures [n_walkers] and adds sum_w s_w to *sum_a and, if given, *sum_b.  The signed sums add s_w x_w in the
+// order of their unsigned counterparts (launch_accumulate; the reduce steps of launch_correlations, launch_pairing and
+// launch_sus_reduce, whose per_walker input they rewrite in place as s_w x_w) and count the walkers kept.
+hipError_t launch_sign_prepare(int nb, int n_walkers, const int *sg, double *sw, long long *failures, double *sum_a,
+                               double *sum_b, hipStream_t s);
+hipError_t launch_accumulate_signed(int n, int nb, int n_walkers, const double *G, long stride_unit, const double *sw,
+                                    double *acc, hipStream_t s);
+hipError_t launch_corr_reduce_signed(int n, int nb, int model, int n_walkers, const double *G, long stride_unit,
+                                     int n_dirs, double *per_walker, const double *sw, double *acc, hipStream_t s);
+hipError_t launch_reduce_signed(int n_walkers, long total, double factor, double *per_walker, const double *sw,
+                                double *acc, hipStream_t s);
+// the pair sums of launch_correlations / launch_pairing alone (per_walker written, acc untouched)
+hipError_t launch_correlation_pairs(int n, int nb, int model, int n_walkers, const double *G, long stride_unit,
+                                    const int *dir_ptr, const int *pair_src, const int *pair_trg, int n_dirs,
+                                    double *per_walker, hipStream_t s);
+hipError_t launch_pairing_pairs(int n, int nb, int n_walkers, const double *G, long stride_unit, const int *dir_ptr,
+                                const int *pair_src, const int *pair_trg, int n_dirs, int K, const int *trg_of,
+                                double *per_walker, hipStream_t s);
 // HS field <-> Julia BitArray chunks (compress / decompress, HubbardModel.jl:56-59)
 hipError_t launch_conf_pack(const int8_t *conf, size_t n_elem, unsigned long long *chunks, hipStream_t s);
 hipError_t launch_conf_unpack(const unsigned long long *chunks, size_t n_elem, int8_t *conf, hipStream_t s);

@@ -295,6 +295,16 @@ hipError_t launch_correlations(int n, int nb, int model, int n_walkers, const do
     return hipGetLastError();
 }
 
+// the pair sums alone: the signed reduce (sign.hip) follows
+hipError_t launch_correlation_pairs(int n, int nb, int model, int n_walkers, const double *G, long stride_unit,
+                                    const int *dir_ptr, const int *pair_src, const int *pair_trg, int n_dirs,
+                                    double *per_walker, hipStream_t s)
+{
+    hipLaunchKernelGGL(corr_pairs_kernel, dim3(n_dirs, n_walkers), dim3(256), 0, s, n, nb, model, G, stride_unit,
+                       dir_ptr, pair_src, pair_trg, n_dirs, per_walker, 4L * n_dirs);
+    return hipGetLastError();
+}
+
 // pc_kernel over EachLocalQuadByDistance{K} (measurements.jl:208-214, generic.jl:341-349,
 // lattice_iterators.jl:264-318; attractive override HubbardModelAttractive.jl:243-245):
 //   out[dir12, dir1, dir2] += G[src1, src2] * G[trg1+N, trg2+N] - G[src1, trg2+N] * G[trg1+N, src2]
@@ -351,6 +361,15 @@ hipError_t launch_pairing(int n, int nb, int n_walkers, const double *G, long st
                        pair_src, pair_trg, n_dirs, K, trg_of, per_walker, total);
     hipLaunchKernelGGL(pairing_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, n_walkers, total,
                        per_walker, acc);
+    return hipGetLastError();
+}
+
+hipError_t launch_pairing_pairs(int n, int nb, int n_walkers, const double *G, long stride_unit, const int *dir_ptr,
+                                const int *pair_src, const int *pair_trg, int n_dirs, int K, const int *trg_of,
+                                double *per_walker, hipStream_t s)
+{
+    hipLaunchKernelGGL(pairing_kernel, dim3(n_dirs, n_walkers), dim3(256), 0, s, n, nb, G, stride_unit, dir_ptr,
+                       pair_src, pair_trg, n_dirs, K, trg_of, per_walker, (long)n_dirs * K * K);
     return hipGetLastError();
 }
 

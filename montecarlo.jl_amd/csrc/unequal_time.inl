@@ -823,6 +823,7 @@ int dqmc_accumulate_susceptibilities(dqmc_handle *h, int32_t recalculate)
     if (record) CHK(binner_room(h, DQMC_BIN_TIME_DISPLACED));
     const dqmc_handle::Section &sus = h->sec[DQMC_RED_SUSCEPTIBILITIES], &td = h->sec[DQMC_RED_TIME_DISPLACED];
     const long total = sus.bin_E;
+    CHK(sign_begin(h, DQMC_RED_SUSCEPTIBILITIES, record ? DQMC_RED_TIME_DISPLACED : -1));
     CHK(true_greens(h, h->greens));                                 // G00 = greens!(mc)
     CHK(copy_mat(h, u->g00, h->tmp2));
     HIPCHK(hipMemsetAsync(sus.per_walker, 0, sizeof(double) * h->W * total, h->stream));  // prepare!
@@ -853,13 +854,19 @@ int dqmc_accumulate_susceptibilities(dqmc_handle *h, int32_t recalculate)
                                    h->dir_ptr, h->pair_src, h->pair_trg, h->n_dirs, sus.per_walker, total,
                                    ut_cc_offset(h), h->stream));
     }
-    {
+    if (h->sign_on) {  // the samples become s_w x in place: the binners below read them
         Timed t(h, DQMC_K_MISC);
-        HIPCHK(launch_sus_reduce(h->W, total, h->p.delta_tau, sus.per_walker, sus.acc, h->stream));
-    }
-    if (record) {  // the accumulator takes the samples, walkers in order
-        Timed t(h, DQMC_K_MISC);
-        HIPCHK(launch_sus_reduce(h->W, td.bin_E, 1.0, td.per_walker, td.acc, h->stream));
+        HIPCHK(launch_reduce_signed(h->W, total, h->p.delta_tau, sus.per_walker, h->sign_sw, sus.acc, h->stream));
+        if (record) HIPCHK(launch_reduce_signed(h->W, td.bin_E, 1.0, td.per_walker, h->sign_sw, td.acc, h->stream));
+    } else {
+        {
+            Timed t(h, DQMC_K_MISC);
+            HIPCHK(launch_sus_reduce(h->W, total, h->p.delta_tau, sus.per_walker, sus.acc, h->stream));
+        }
+        if (record) {  // the accumulator takes the samples, walkers in order
+            Timed t(h, DQMC_K_MISC);
+            HIPCHK(launch_sus_reduce(h->W, td.bin_E, 1.0, td.per_walker, td.acc, h->stream));
+        }
     }
     if (h->bin[DQMC_BIN_SUSCEPTIBILITIES].on) CHK(binner_push_section(h, DQMC_BIN_SUSCEPTIBILITIES));
     if (record && h->bin[DQMC_BIN_TIME_DISPLACED].on) CHK(binner_push_section(h, DQMC_BIN_TIME_DISPLACED));

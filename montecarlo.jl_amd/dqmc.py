@@ -229,11 +229,14 @@ class DQMC:
     Metropolis streams of walker w as `seed + first_walker + w`, so results do not depend
     on how walkers are distributed over devices.  `global_moves=True` runs one global move of `global_kind` ("site": one
     site's whole time line is flipped, "all": the whole field) per walker in every `global_rate`-th sweep, where the
-    reference keeps its hook (DQMC.jl:526-532); see global_move()."""
+    reference keeps its hook (DQMC.jl:526-532); see global_move().  `sign_weighting=True` makes every measurement sum
+    and binner take s O in the place of O, s = the sign of the walker's field, next to the sum of s (see
+    set_sign_weighting(), signed()): the averages of a model whose weight is not positive."""
 
     def __init__(self, model, n_walkers=1, device_id=0, seed=123, first_walker=0, thermalization=100, sweeps=100,
                  safe_mult=10, measure_rate=10, check_sign_problem=True, check_propagation_error=True,
-                 checkerboard=False, global_moves=False, global_rate=5, global_kind="site", **kw):
+                 checkerboard=False, global_moves=False, global_rate=5, global_kind="site", sign_weighting=False,
+                 **kw):
         self.model = model
         self.checkerboard = bool(checkerboard)
         if int(global_rate) < 1:
@@ -299,6 +302,8 @@ class DQMC:
             self.seed(w, s)
         if self.p.global_moves:
             self.set_global_rate(self.p.global_rate, self.global_kind)
+        if sign_weighting:
+            self.set_sign_weighting(True)
 
     # ---- lifetime
     def close(self):
@@ -563,6 +568,89 @@ class DQMC:
         self._c(lib().dqmc_get_global_last(self._h, walker, C.byref(p), C.byref(acc), C.byref(site)))
         return dict(p=p.value, accepted=bool(acc.value), site=site.value)
 
+    # ---- sign reweighting (include/dqmc_hip.h "sign reweighting")
+    def set_sign_weighting(self, on=True):
+        """from now on every accumulate_* adds s_w O_w, s_w = the sign of walker w's field, and the section's sum of s_w
+        (off: the bare samples, the default).  Refused (ERR_STATE) while a section or a binner holds samples:
+        reset_accumulators() first.  Read the results with signed(), mean_sign(), sign_sums()."""
+        self._c(lib().dqmc_set_sign_weighting(self._h, int(bool(on))))
+
+    def sign_weighting(self):
+        on = C.c_int32()
+        self._c(lib().dqmc_get_sign_weighting(self._h, C.byref(on)))
+        return bool(on.value)
+
+    def sign(self):
+        """-> int array [n_walkers]: the sign of every walker's current field, the product of logdet()'s signs over the
+        blocks (+1 for the attractive model without a launch; 0: a singular or non-finite block)"""
+        sg = np.zeros(self.n_walkers, dtype=np.int32)
+        self._c(lib().dqmc_get_sign(self._h, sg.ctypes.data_as(C.POINTER(C.c_int32))))
+        return sg
+
+    def sign_failures(self):
+        """-> int array [n_walkers]: samples left out of the signed sums because the walker's sign came out 0"""
+        out = np.zeros(self.n_walkers, dtype=np.int64)
+        self._c(lib().dqmc_get_sign_failures(self._h, i64ptr(out)))
+        return out
+
+    _SIGN_ORDER = ("greens", "correlations", "pairing", "susceptibilities", "time_displaced")  # DQMC_RED_* order
+
+    def sign_sums(self, reduced=False):
+        """-> {section: sum of s over its samples} (the DQMC_RED_SIGN section; `reduced`: of the last reduction)"""
+        return dict(zip(self._SIGN_ORDER, self._section("sign", reduced=reduced)))
+
+    def mean_sign(self, which="greens"):
+        """<s> of the samples of one section: its sum of signs over its sample count"""
+        if which not in self._SIGN_ORDER:
+            raise ValueError("unknown section %r" % (which,))
+        return self.sign_sums()[which] / self._section(which)[-1]
+
+    def signed(self, which="greens"):
+        """<O s> / <s> of a section measured with sign weighting on: the section's usual dict (greens -> G, G2,
+        occupation; correlations; pairing -> PC; susceptibilities; time_displaced), every sum divided by the section's
+        sum of signs instead of its sample count; plus count, sign_sum and mean_sign.  With the section's binner on every
+        field X also comes with X_std_error: the jackknife over the walkers of the ratio (jackknife_ratio), from each
+        walker's level-0 sums of s x and of s; that needs at least two walkers.  ValueError when the sum of signs is 0."""
+        if which not in self._SIGN_ORDER:
+            raise ValueError("unknown section %r" % (which,))
+        if not self.sign_weighting():
+            raise _lib.DQMCError(_lib.ERR_STATE, "signed(): sign weighting is off (set_sign_weighting)")
+        raw = self._section(which)
+        cnt, S = raw[-1], self.sign_sums()[which]
+        if S == 0:
+            raise ValueError("signed(%r): the sum of signs is 0 over %d samples: <O s> / <s> is undefined" % (which, cnt))
+        raw = raw.copy()
+        raw[-1] = S
+        if which == "greens":
+            res = self.unpack_accumulators(raw)
+        elif which == "correlations":
+            res = self.correlations(_raw=raw)
+        elif which == "pairing":
+            res = dict(PC=self.pairing(_raw=raw)[0])
+        elif which == "susceptibilities":
+            res = self.susceptibilities(_raw=raw)
+        else:
+            res = self.time_displaced(_raw=raw)
+        res.update(count=cnt, sign_sum=S, mean_sign=S / cnt)
+        if self._binning_enabled(which):
+            sx, sg = self.signed_walker_sums(which)
+            _, err = jackknife_ratio(sx, sg)
+            for name, v in self._bin_shape(which, err).items():
+                res[name + "_std_error"] = v
+        return res
+
+    def signed_walker_sums(self, which):
+        """-> (sx [n_walkers, E], s [n_walkers]): level 0 of every walker's binners of a section, the sums of s x in the
+        section's element order, and of its sign binner, the sums of s"""
+        bid = _lib.BIN_SIGN + self._SIGN_ORDER.index(which)
+        sx = np.stack([self.binner_level(which, w, 0)[0] for w in range(self.n_walkers)])
+        sg = np.zeros(self.n_walkers)
+        for w in range(self.n_walkers):
+            x = np.zeros(1)
+            self._c(lib().dqmc_binner_get_level(self._h, bid, w, 0, dptr(x), None, None))
+            sg[w] = x[0]
+        return sx, sg
+
     # ---- analysis / measurement sums
     def analysis(self, walker=0):
         st = _lib.Stats()
@@ -591,7 +679,8 @@ class DQMC:
 
     def reduced(self, which="greens"):
         """dqmc_get_reduced: the global sums of the last reduction (the handle's own accumulators keep the local sums);
-        `which` = greens | correlations | pairing | susceptibilities | time_displaced, layouts as the local getters"""
+        `which` = greens | correlations | pairing | susceptibilities | time_displaced | sign (the sums of signs, packed
+        only with sign weighting on), layouts as the local getters"""
         return self._section(which, reduced=True)
 
     def reduced_analysis(self):
@@ -634,7 +723,8 @@ class DQMC:
                  "correlations": (1, "dqmc_correlations_size", "dqmc_get_correlations"),
                  "pairing": (2, "dqmc_pairing_size", "dqmc_get_pairing"),
                  "susceptibilities": (3, "dqmc_susceptibilities_size", "dqmc_get_susceptibilities"),
-                 "time_displaced": (_lib.RED_TIME_DISPLACED, "dqmc_time_displaced_size", "dqmc_get_time_displaced")}
+                 "time_displaced": (_lib.RED_TIME_DISPLACED, "dqmc_time_displaced_size", "dqmc_get_time_displaced"),
+                 "sign": (_lib.RED_SIGN, "dqmc_sign_sums_size", "dqmc_get_sign_sums")}
 
     def _section_size(self, which):
         n = C.c_size_t()
@@ -851,9 +941,9 @@ class DQMC:
         """the raw sums [cdc][sdc_x][sdc_y][sdc_z][mx][my][mz][count] (layout of include/dqmc_hip.h)"""
         return self._section("correlations")
 
-    def correlations(self):
+    def correlations(self, _raw=None):
         """-> dict of means: CDC, SDCx, SDCy, SDCz per direction; Mx, My, Mz per site; count"""
-        out = self._section("correlations")
+        out = self._section("correlations") if _raw is None else _raw
         nd, N, cnt = self._ndirs, self.N, out[-1]
         names = ["CDC", "SDCx", "SDCy", "SDCz"]
         res = {k: out[i * nd:(i + 1) * nd] / cnt for i, k in enumerate(names)}
@@ -874,9 +964,9 @@ class DQMC:
     def accumulate_pairing(self):
         self._c(lib().dqmc_accumulate_pairing(self._h))
 
-    def pairing(self):
+    def pairing(self, _raw=None):
         """-> (mean of output[dir12, dir1, dir2] as pushed by finish!, sample count)"""
-        out = self._section("pairing")
+        out = self._section("pairing") if _raw is None else _raw
         cnt = out[-1]
         return out[:-1].reshape((self._ndirs, self._K, self._K), order="F") / cnt, cnt
 
@@ -938,10 +1028,10 @@ class DQMC:
         recalculate = 4 * self.p.safe_mult if recalculate is None else recalculate
         self._c(lib().dqmc_accumulate_susceptibilities(self._h, recalculate))
 
-    def susceptibilities(self):
+    def susceptibilities(self, _raw=None):
         """-> dict of means: CDS, SDSx, SDSy, SDSz per direction, PS[dir12, dir1, dir2] if local targets
         are set, CCS[dir12, dir_ii] if current targets are set, count"""
-        out = self._section("susceptibilities")
+        out = self._section("susceptibilities") if _raw is None else _raw
         nd, cnt = self._ndirs, out[-1]
         res = {k: out[i * nd:(i + 1) * nd] / cnt for i, k in enumerate(["CDS", "SDSx", "SDSy", "SDSz"])}
         K = getattr(self, "_K", 0)
@@ -987,10 +1077,10 @@ class DQMC:
         p = self.time_displaced_plan()
         return np.arange(p["rows"]) * p["every"] * self.p.delta_tau
 
-    def time_displaced(self):
+    def time_displaced(self, _raw=None):
         """-> dict of means over the samples: tau [R]; Gl0, G0l [n_blocks, R, n_dirs]; CDC, SDCx, SDCy, SDCz [R, n_dirs]
         (whichever are recorded); count"""
-        raw = self.time_displaced_raw()
+        raw = self.time_displaced_raw() if _raw is None else _raw
         cnt = raw[-1]
         res = {"tau": self._td_tau()}
         for name, v in self._bin_shape("time_displaced", raw[:-1]).items():
@@ -1077,6 +1167,23 @@ class DQMC:
         n = np.zeros(len(_lib.K_FAMILIES), dtype=np.int64)
         self._c(lib().dqmc_timing_get(self._h, dptr(ms), i64ptr(n)))
         return {k: (float(ms[i]), int(n[i])) for i, k in enumerate(_lib.K_FAMILIES)}
+
+
+def jackknife_ratio(sx, s):
+    """The ratio estimate <O s> / <s> and its jackknife error over W independent walkers.  sx [W, E]: each walker's sum
+    of s x, s [W]: its sum of s.  ratio = sum_w sx_w / sum_w s_w; leaving walker w out gives r_w = (sum sx - sx_w) /
+    (sum s - s_w), and std_error = sqrt((W - 1) / W sum_w (r_w - mean r)^2).  ValueError below two walkers and when the
+    sum of signs, or one with a walker left out, is 0."""
+    sx, s = np.asarray(sx, dtype=np.float64), np.asarray(s, dtype=np.float64)
+    W = s.shape[0]
+    if W < 2:
+        raise ValueError("the jackknife over walkers needs at least two walkers")
+    S = s.sum()
+    if S == 0 or np.any(S - s == 0):
+        raise ValueError("the sum of signs is 0 (over all walkers, or with one left out): the ratio is undefined")
+    tot = sx.sum(axis=0)
+    r = (tot[None, :] - sx) / (S - s)[:, None]
+    return tot / S, np.sqrt((W - 1) / W * ((r - r.mean(axis=0)) ** 2).sum(axis=0))
 
 
 def finish_moments(buf):
