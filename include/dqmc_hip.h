@@ -486,6 +486,61 @@ enum { DQMC_RED_SIGN = 5 };
 int dqmc_get_reduced(dqmc_handle *h, int32_t which, double *host_out);
 int dqmc_get_reduced_stats(dqmc_handle *h, dqmc_stats *out);
 
+/* ---- checkpoint and resume ---------------------------------------------------------------------------------------
+ * save / load / resume! (FileIO.jl:38-156, DQMC.jl:463-477, 797-924) for the state that lives on the device.  Like the
+ * global moves this is a defined extension of the ABI: the reference writes a JLD file from host objects; here the engine
+ * hands out and takes back one blob, and the file around it is the host's (dqmc.py: save / load).
+ * Saved is what cannot be recomputed: the HS field, the RNG cursors, the counters and every measurement sum.  Not saved:
+ * mc.s.greens, the UDT stack, Ul .. Tr, a pending sweep update, the logabsdet / sign cache, the unequal-time stack (all
+ * follow from the field: resume! rebuilds them through run!'s init!, build_stack, propagate, DQMC.jl:412-414), reduced
+ * buffers (dqmc_reduce), timing counters and host-supplied uniform streams.
+ * The blob is little-endian with fixed-width fields; doubles are IEEE bit patterns.
+ *   header (560 bytes)
+ *     u64 magic "DQMCSTA1"   u32 format version (1)   u32 header bytes
+ *     char[16] dqmc_build_source_hash of the exporting library, zero padded (informational, never checked)
+ *     i32 n_sites, model_kind, slices, safe_mult, n_walkers, n_blocks      f64 delta_tau, U
+ *     u64 n[6]      doubles of the accumulator of each DQMC_RED_* section, 0 = not configured
+ *     u64 n_red[6]  doubles of its part of the reduction buffer
+ *     11 binners (DQMC_BIN_GREENS .. DQMC_BIN_TIME_DISPLACED, then DQMC_BIN_SIGN + k): i32 on, E, L, pad   i64 capacity, T
+ *     i32 time-displaced every, what, R     i32 sign weighting on     i32 global rate, global kind
+ *     i64 updates since dqmc_prepare (the global-move schedule)     u64 FNV-1a 64 of the header bytes in front of it
+ *   payload, in this order, nothing between the parts
+ *     the HS field: per walker the ceil(n_sites slices / 64) u64 chunks of dqmc_get_conf_bits
+ *     per walker (u64 seed, u64 draw): the Philox key and cursor of dqmc_seed / dqmc_uniforms_used
+ *     per walker i64 prop_local, acc_local, then negative_probability and propagation_error as (f64 max, min, sum, i64 count)
+ *     per walker u64 moves_drawn, i64 prop_global, acc_global, i64 pending dS, f64 last p, i32 active, site, accepted, pad
+ *     per walker i64 dqmc_get_sign_failures
+ *     the accumulator of every configured section in DQMC_RED_* order, the sums of signs included (n doubles each)
+ *     x_sum [L][W][E], x2_sum [L][W][E], compressor [L - 1][W][E] of every enabled binner in the order of the header
+ * The binner's T and the update count are state and come back with the payload; every other header field describes how
+ * the handle is configured and must be the same on both sides. */
+/* bytes of the blob of this handle as it is configured now */
+int dqmc_state_size(dqmc_handle *h, size_t *n_bytes);
+/* The blob into host_out (n_bytes = dqmc_state_size).  Only at the measurement point, current_slice == 1 && direction ==
+ * +1, where dqmc_update_until_measure returns (and dqmc_sweep when it started there); DQMC_ERR_STATE anywhere else, and
+ * when a walker runs on a dqmc_set_uniforms stream (a test device the blob does not carry).  Only copies are made: no
+ * kernel is launched and no buffer of the handle is written, so the chain's future is bit for bit that of a handle that
+ * was never exported. */
+int dqmc_state_export(dqmc_handle *h, void *host_out, size_t n_bytes);
+/* Takes a blob into a handle created with the same dqmc_params and configured the same way (pair directions, local and
+ * current targets, time-displaced setting, binners with the same capacities, sign weighting, global rate and kind; the
+ * susceptibility section laid out if it was, e.g. by dqmc_susceptibilities_size).  A bad magic, an unknown version, a
+ * damaged header, any configuration field that differs and a buffer shorter or longer than the header describes return
+ * DQMC_ERR_INVALID with dqmc_last_error naming the first offending field; everything is checked before the first write,
+ * so a refused call leaves the handle as it was.
+ * On success the payload is restored, the stack and mc.s.greens are rebuilt from the field (init_stack, build_stack, then
+ * the propagates of a down pass with no sweep in between) and the handle stands at the measurement point, prepared.  The
+ * last reduction is void, the logabsdet / sign cache invalid, the unequal-time stack rebuilt on its next use.  Every walker
+ * is on the Philox stream of its saved (seed, draw) afterwards: a walker of the importing handle that ran on a
+ * dqmc_set_uniforms stream leaves it (the handle keeps the buffer until dqmc_destroy or the next dqmc_set_uniforms).
+ * The checksum protects the header only: the payload is taken as it comes, as dqmc_set_conf_bits and the other setters
+ * take their arguments (its one index, the site of a walker's latest global move, is checked against n_sites), and a
+ * payload damaged in transit with its sizes intact is not noticed.  The rebuilt
+ * G differs from the propagated one it replaces by rounding: a resumed chain agrees with the uninterrupted one as device
+ * and oracle agree, not to the bit.  Exact are: the payload through export and import, the exporting chain's future,
+ * and the futures of two imports of one blob. */
+int dqmc_state_import(dqmc_handle *h, const void *host_in, size_t n_bytes);
+
 /* ---- batched linalg primitives (unit parity with test/slice_matrices.jl) --
  * host in / host out, `batch` independent n x n problems, run on device_id.  */
 /* vmul! family (src/linalg/general.jl:7-56): C = op(A)*op(B); transa/transb 0|1 */

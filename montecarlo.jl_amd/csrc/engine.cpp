@@ -17,6 +17,7 @@
 
 #include "../../include/dqmc_hip.h"
 #include "kernels.h"
+#include "state_blob.h"
 #include <rccl/rccl.h>
 
 using namespace dqmc;
@@ -1925,6 +1926,7 @@ int dqmc_export_pairing(dqmc_handle *h, void *device_out) { ENTER(h); return sec
 #include "unequal_time.inl"
 #include "binner.inl"
 #include "global_move.inl"
+#include "checkpoint.inl"
 
 // ---------------------------------------------------------------------------
 // Measurement reduction over ranks: every accumulator the handle keeps and the DQMCAnalysis

@@ -1,0 +1,225 @@
+// state_blob.cpp — see state_blob.h.  No HIP, no engine types: bytes in, bytes out.
+#include "state_blob.h"
+
+#include <cstring>
+
+namespace dqmc_blob {
+namespace {
+
+// bin_name(k): the section names the error messages use
+const char *const SEC_NAME[N_SEC] = {"greens", "correlations", "pairing", "susceptibilities", "time_displaced", "sign"};
+const char *const BIN_NAME[N_BIN] = {"greens", "correlations", "pairing", "susceptibilities", "user", "time_displaced",
+                                     "sign:greens", "sign:correlations", "sign:pairing", "sign:susceptibilities",
+                                     "sign:time_displaced"};
+
+void put(uint8_t *&p, uint64_t v, int bytes)
+{
+    for (int i = 0; i < bytes; ++i) *p++ = (uint8_t)(v >> (8 * i));
+}
+uint64_t get(const uint8_t *&p, int bytes)
+{
+    uint64_t v = 0;
+    for (int i = 0; i < bytes; ++i) v |= (uint64_t)*p++ << (8 * i);
+    return v;
+}
+uint64_t bits_of(double d)
+{
+    uint64_t u;
+    std::memcpy(&u, &d, sizeof(u));
+    return u;
+}
+double double_of(uint64_t u)
+{
+    double d;
+    std::memcpy(&d, &u, sizeof(d));
+    return d;
+}
+uint64_t fnv1a(const uint8_t *p, size_t n)
+{
+    uint64_t h = 0xcbf29ce484222325ull;
+    for (size_t i = 0; i < n; ++i) h = (h ^ p[i]) * 0x100000001b3ull;
+    return h;
+}
+
+enum { HEADER_BYTES = 8 + 4 + 4 + HASH_BYTES + 6 * 4 + 2 * 8 + 2 * N_SEC * 8 + N_BIN * 32 + 6 * 4 + 8 + 8 };
+
+bool mul(size_t a, size_t b, size_t *out) { return !__builtin_mul_overflow(a, b, out); }
+bool add(size_t a, size_t b, size_t *out) { return !__builtin_add_overflow(a, b, out); }
+// *off += count * bytes, the old *off into *at
+bool take(size_t *off, size_t *at, size_t count, size_t bytes)
+{
+    size_t sz;
+    *at = *off;
+    return mul(count, bytes, &sz) && add(*off, sz, off);
+}
+int refuse(std::string *why, const std::string &msg)
+{
+    if (why) *why = msg;
+    return -1;
+}
+
+}  // namespace
+
+size_t header_bytes() { return HEADER_BYTES; }
+
+size_t conf_chunks(int32_t n_sites, int32_t slices) { return ((size_t)n_sites * (size_t)slices + 63) / 64; }
+
+bool layout(const Shape &s, Layout *out, std::string *why)
+{
+    auto bad = [&](const char *what) {
+        if (why) *why = what;
+        return false;
+    };
+    if (s.n_sites < 1 || s.slices < 1 || s.n_walkers < 1 || s.nb < 1 || s.nb > 2) return bad("n_sites, slices, n_walkers, nb");
+    const size_t W = (size_t)s.n_walkers;
+    Layout l{};
+    size_t off = HEADER_BYTES;
+    bool ok = take(&off, &l.conf, W * conf_chunks(s.n_sites, s.slices), 8);
+    ok = ok && take(&off, &l.rng, W, RNG_BYTES);
+    ok = ok && take(&off, &l.stats, W, STATS_BYTES);
+    ok = ok && take(&off, &l.gm, W, GM_BYTES);
+    ok = ok && take(&off, &l.sign_fail, W, 8);
+    for (int i = 0; i < N_SEC && ok; ++i) {
+        if (s.sec_n[i] > (uint64_t)SIZE_MAX / 8) return bad("section size");
+        ok = take(&off, &l.sec[i], (size_t)s.sec_n[i], 8);
+    }
+    for (int k = 0; k < N_BIN && ok; ++k) {
+        const Shape::Bin &b = s.bin[k];
+        l.bin_xs[k] = l.bin_x2[k] = l.bin_c[k] = off;
+        if (!b.on) continue;
+        if (b.E < 1 || b.L < 1 || b.L > 41) return bad("binner elements / levels");
+        size_t we;
+        ok = mul(W, (size_t)b.E, &we) && mul(we, 8, &we);
+        ok = ok && take(&off, &l.bin_xs[k], (size_t)b.L, we);
+        ok = ok && take(&off, &l.bin_x2[k], (size_t)b.L, we);
+        ok = ok && take(&off, &l.bin_c[k], (size_t)b.L - 1, we);
+    }
+    if (!ok) return bad("blob size overflows");
+    l.total = off;
+    if (out) *out = l;
+    return true;
+}
+
+void write_header(const Shape &s, uint8_t *out)
+{
+    uint8_t *p = out;
+    put(p, MAGIC, 8);
+    put(p, VERSION, 4);
+    put(p, HEADER_BYTES, 4);
+    std::memcpy(p, s.source_hash, HASH_BYTES);
+    p += HASH_BYTES;
+    for (int32_t v : {s.n_sites, s.model_kind, s.slices, s.safe_mult, s.n_walkers, s.nb}) put(p, (uint32_t)v, 4);
+    put(p, bits_of(s.delta_tau), 8);
+    put(p, bits_of(s.U), 8);
+    for (int i = 0; i < N_SEC; ++i) put(p, s.sec_n[i], 8);
+    for (int i = 0; i < N_SEC; ++i) put(p, s.sec_n_red[i], 8);
+    for (int k = 0; k < N_BIN; ++k) {
+        const Shape::Bin &b = s.bin[k];
+        put(p, (uint32_t)b.on, 4);
+        put(p, (uint32_t)b.E, 4);
+        put(p, (uint32_t)b.L, 4);
+        put(p, 0, 4);
+        put(p, (uint64_t)b.cap, 8);
+        put(p, (uint64_t)b.T, 8);
+    }
+    for (int32_t v : {s.td_every, s.td_what, s.td_R, s.sign_on, s.gm_rate, s.gm_kind}) put(p, (uint32_t)v, 4);
+    put(p, (uint64_t)s.gm_updates, 8);
+    put(p, fnv1a(out, (size_t)(p - out)), 8);
+}
+
+int validate(const uint8_t *buf, size_t n_bytes, const Shape &h, Shape *blob, std::string *why)
+{
+    if (!buf) return refuse(why, "buffer: NULL");
+    if (n_bytes < HEADER_BYTES)
+        return refuse(why, "n_bytes: " + std::to_string(n_bytes) + " bytes do not hold the " + std::to_string((int)HEADER_BYTES) +
+                               "-byte header");
+    const uint8_t *p = buf;
+    if (get(p, 8) != MAGIC) return refuse(why, "magic: not a dqmc_state_export blob");
+    const uint32_t version = (uint32_t)get(p, 4);
+    if (version != VERSION)
+        return refuse(why, "version: format version " + std::to_string(version) + ", this library reads version " +
+                               std::to_string(VERSION));
+    if (get(p, 4) != HEADER_BYTES) return refuse(why, "header_bytes: not the header size of format version 1");
+    const uint8_t *sum_at = buf + HEADER_BYTES - 8;
+    if (get(sum_at, 8) != fnv1a(buf, HEADER_BYTES - 8)) return refuse(why, "checksum: the header is damaged");
+
+    Shape s{};
+    std::memcpy(s.source_hash, p, HASH_BYTES);
+    p += HASH_BYTES;
+    for (int32_t *v : {&s.n_sites, &s.model_kind, &s.slices, &s.safe_mult, &s.n_walkers, &s.nb}) *v = (int32_t)(uint32_t)get(p, 4);
+    s.delta_tau = double_of(get(p, 8));
+    s.U = double_of(get(p, 8));
+    for (int i = 0; i < N_SEC; ++i) s.sec_n[i] = get(p, 8);
+    for (int i = 0; i < N_SEC; ++i) s.sec_n_red[i] = get(p, 8);
+    for (int k = 0; k < N_BIN; ++k) {
+        Shape::Bin &b = s.bin[k];
+        b.on = (int32_t)(uint32_t)get(p, 4);
+        b.E = (int32_t)(uint32_t)get(p, 4);
+        b.L = (int32_t)(uint32_t)get(p, 4);
+        (void)get(p, 4);
+        b.cap = (int64_t)get(p, 8);
+        b.T = (int64_t)get(p, 8);
+    }
+    for (int32_t *v : {&s.td_every, &s.td_what, &s.td_R, &s.sign_on, &s.gm_rate, &s.gm_kind}) *v = (int32_t)(uint32_t)get(p, 4);
+    s.gm_updates = (int64_t)get(p, 8);
+
+    // configuration: the first field that differs from the importing handle
+#define SAME(field, name)                                                                                             \
+    if (!(s.field == h.field))                                                                                        \
+        return refuse(why, std::string(name) + ": the blob has " + std::to_string(s.field) + ", the handle " +        \
+                               std::to_string(h.field))
+    SAME(n_sites, "n_sites");
+    SAME(model_kind, "model_kind");
+    SAME(slices, "slices");
+    SAME(safe_mult, "safe_mult");
+    SAME(n_walkers, "n_walkers");
+    SAME(nb, "nb");
+    if (bits_of(s.delta_tau) != bits_of(h.delta_tau)) return refuse(why, "delta_tau: differs from the handle's");
+    if (bits_of(s.U) != bits_of(h.U)) return refuse(why, "U: differs from the handle's");
+    SAME(sign_on, "sign_on");
+    for (int i = 0; i < N_SEC; ++i) {
+        SAME(sec_n[i], std::string("section ") + SEC_NAME[i] + " n");
+        SAME(sec_n_red[i], std::string("section ") + SEC_NAME[i] + " n_red");
+    }
+    SAME(td_every, "time_displaced every");
+    SAME(td_what, "time_displaced what");
+    SAME(td_R, "time_displaced R");
+    for (int k = 0; k < N_BIN; ++k) {
+        SAME(bin[k].on, std::string("binner ") + BIN_NAME[k] + " on");
+        SAME(bin[k].E, std::string("binner ") + BIN_NAME[k] + " E");
+        SAME(bin[k].L, std::string("binner ") + BIN_NAME[k] + " L");
+        SAME(bin[k].cap, std::string("binner ") + BIN_NAME[k] + " cap");
+    }
+    SAME(gm_rate, "gm_rate");
+    SAME(gm_kind, "gm_kind");
+#undef SAME
+    // state: ranges only
+    for (int k = 0; k < N_BIN; ++k) {
+        const Shape::Bin &b = s.bin[k];
+        if (b.T < 0 || b.T > (b.on ? b.cap : 0))
+            return refuse(why, std::string("binner ") + BIN_NAME[k] + " T: " + std::to_string(b.T) + " pushes outside 0 .. capacity");
+    }
+    if (s.gm_updates < 0) return refuse(why, "gm_updates: negative");
+    Layout l;
+    std::string lw;
+    if (!layout(s, &l, &lw)) return refuse(why, lw + ": not a shape a handle can have");
+    if (n_bytes != l.total)
+        return refuse(why, "n_bytes: the buffer has " + std::to_string(n_bytes) + " bytes, the header describes " +
+                               std::to_string(l.total));
+    if (blob) *blob = s;
+    return 0;
+}
+
+void pack_conf(const int8_t *conf, size_t n, uint8_t *chunks_le)
+{
+    const size_t bytes = (n + 63) / 64 * 8;
+    std::memset(chunks_le, 0, bytes);
+    for (size_t i = 0; i < n; ++i)
+        if (conf[i] == 1) chunks_le[i >> 3] |= (uint8_t)(1u << (i & 7));
+}
+void unpack_conf(const uint8_t *chunks_le, size_t n, int8_t *conf)
+{
+    for (size_t i = 0; i < n; ++i) conf[i] = (chunks_le[i >> 3] >> (i & 7)) & 1 ? 1 : -1;
+}
+
+}  // namespace dqmc_blob

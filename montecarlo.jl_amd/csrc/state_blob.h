@@ -1,0 +1,71 @@
+// state_blob.h — the checkpoint blob of dqmc_state_export / dqmc_state_import (include/dqmc_hip.h "checkpoint and
+// resume"): its header, the validation of a header against the handle that is to take it, and the offsets of the payload.
+// Plain C++ with no HIP in it: engine.cpp fills a Shape from the handle and does the copies; the code here sees bytes only,
+// so that it can be built and run under the host sanitizers on its own (tests/test_checkpoint_blob.py).
+//
+// Every field is little-endian and of fixed width; doubles travel as their IEEE bit pattern.
+#ifndef DQMC_STATE_BLOB_H
+#define DQMC_STATE_BLOB_H
+#include <cstddef>
+#include <cstdint>
+#include <string>
+
+namespace dqmc_blob {
+
+enum { N_SEC = 6,    // DQMC_RED_GREENS .. DQMC_RED_SIGN
+       N_BIN = 11 }; // DQMC_BIN_GREENS .. DQMC_BIN_TIME_DISPLACED, then DQMC_BIN_SIGN + k for the five measurement sections
+static const uint64_t MAGIC = 0x31415453434d5144ull;  // the bytes "DQMCSTA1", read as one little-endian word
+static const uint32_t VERSION = 1;
+enum { HASH_BYTES = 16 };
+
+// What the payload depends on, as the header carries it.  `T` of a binner and `gm_updates` are state (restored by the
+// import); every other field is configuration and must agree with the importing handle.
+struct Shape {
+    char source_hash[HASH_BYTES];  // dqmc_build_source_hash of the exporting library, zero-padded; never checked
+    int32_t n_sites, model_kind, slices, safe_mult, n_walkers, nb;
+    double delta_tau, U;
+    uint64_t sec_n[N_SEC], sec_n_red[N_SEC];  // doubles of a section's accumulator / of its part in the reduction (0: not configured)
+    struct Bin {
+        int32_t on, E, L;
+        int64_t cap, T;
+    } bin[N_BIN];
+    int32_t td_every, td_what, td_R;
+    int32_t sign_on;
+    int32_t gm_rate, gm_kind;
+    int64_t gm_updates;
+};
+
+// bytes per walker of the fixed-size records of the payload
+enum { RNG_BYTES = 16,     // seed, draw
+       STATS_BYTES = 80,   // prop_local, acc_local, 2 x {max, min, sum, count}
+       GM_BYTES = 56 };    // moves_drawn, prop_global, acc_global, dS, last_p, active, site, last_accepted, pad
+
+// byte offsets of the payload from the start of the blob, in blob order
+struct Layout {
+    size_t conf;       // n_walkers x conf_chunks(n_sites, slices) x uint64: dqmc_get_conf_bits per walker
+    size_t rng;        // n_walkers x RNG_BYTES
+    size_t stats;      // n_walkers x STATS_BYTES
+    size_t gm;         // n_walkers x GM_BYTES
+    size_t sign_fail;  // n_walkers x int64
+    size_t sec[N_SEC];                                // sec_n doubles each (configured sections only)
+    size_t bin_xs[N_BIN], bin_x2[N_BIN], bin_c[N_BIN];  // L W E, L W E, (L - 1) W E doubles (enabled binners only)
+    size_t total;      // size of the whole blob
+};
+
+size_t header_bytes();
+size_t conf_chunks(int32_t n_sites, int32_t slices);
+// false if the shape is not one a handle can have (a count below its minimum) or the sizes overflow size_t
+bool layout(const Shape &s, Layout *out, std::string *why = nullptr);
+// header_bytes() bytes into `out`
+void write_header(const Shape &s, uint8_t *out);
+// Everything dqmc_state_import checks before its first write, in this order: the buffer holds a header; magic; format
+// version; the header's checksum; every configuration field against `handle` (the first one that differs is named); the
+// state fields' ranges; n_bytes against the size the header implies.  0 and *blob filled, or -1 and *why set.
+int validate(const uint8_t *buf, size_t n_bytes, const Shape &handle, Shape *blob, std::string *why);
+
+// compress / decompress of one walker's field (HubbardModel.jl:56-59): element i of conf (+1 / -1) in bit i % 64 of chunk i / 64
+void pack_conf(const int8_t *conf, size_t n, uint8_t *chunks_le);
+void unpack_conf(const uint8_t *chunks_le, size_t n, int8_t *conf);
+
+}  // namespace dqmc_blob
+#endif

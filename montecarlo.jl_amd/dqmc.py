@@ -10,7 +10,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from . import _lib
+from . import _lib, checkpoint as _ckpt
 from ._lib import check, dptr, i64ptr, lib
 from .configurations import CompressedConf, ConfigRecorder
 from .models import rand_conf
@@ -239,6 +239,14 @@ class DQMC:
                  **kw):
         self.model = model
         self.checkerboard = bool(checkerboard)
+        # what save() writes down so that load() can construct and configure the object again
+        self._ctor = dict(n_walkers=int(n_walkers), seed=int(seed), first_walker=int(first_walker),
+                          checkerboard=checkerboard if isinstance(checkerboard, str) else bool(checkerboard),
+                          global_kind=global_kind)
+        self._tables, self._td_args, self._bin_caps, self._user_bin = {}, None, {}, None
+        self._gm_set = None       # (rate, kind) of the last set_global_rate
+        self._sus_layout = False  # the susceptibility section is laid out (by its first use)
+        self._mid_sweep = False  # set by load(): run() finishes the sweep the checkpoint was taken in
         if int(global_rate) < 1:
             raise ValueError("global_rate must be at least 1")
         self.global_kind = self._global_kind(global_kind)
@@ -430,7 +438,8 @@ class DQMC:
                     tail[-1] += 1
         return self.accumulators() + tail
 
-    def run(self, verbose=False, on_measure=None, recorder=None, measurements=("greens",), binning=False):
+    def run(self, verbose=False, on_measure=None, recorder=None, measurements=("greens",), binning=False,
+            checkpoint=None, checkpoint_every=None):
         """run!(mc) (DQMC.jl:369-515) without the host-side measurement framework: the selected
         measurements are accumulated on the device every `measure_rate`-th sweep after thermalization,
         at current_slice == 1 && direction == +1 (DQMC.jl:425-436).  `measurements` may contain
@@ -438,7 +447,14 @@ class DQMC:
         magnetization; needs set_pair_directions), "pairing" (needs set_local_targets) and
         "susceptibilities" (the CombinedGreensIterator measurements) and "time_displaced" (the tau-resolved rows; needs
         set_time_displaced; shares the one iterator pass with "susceptibilities").  `binning=True` enables the device-side
-        LogBinner of every selected measurement before the first sweep (enable_binning; read with binned())."""
+        LogBinner of every selected measurement before the first sweep (enable_binning; read with binned()).
+        `checkpoint=path` saves the run (save()) in every `checkpoint_every`-th sweep and in the last one, thermalization
+        included, at the sweep's measurement point behind its measurements: the one place of a sweep where the chain stands
+        where the engine exports its state.  On an object that load() returned from such a file, run() first finishes that
+        sweep (the up pass behind the measurement point) and goes on with the next one up to thermalization + sweeps, as
+        resume! does (DQMC.jl:463-477)."""
+        if checkpoint is not None and (checkpoint_every is None or int(checkpoint_every) < 1):
+            raise ValueError("run(checkpoint=path) needs checkpoint_every >= 1")
         known = {"greens": lib().dqmc_accumulate_greens, "correlations": lib().dqmc_accumulate_correlations,
                  "pairing": lib().dqmc_accumulate_pairing}
         for m in measurements:
@@ -446,13 +462,17 @@ class DQMC:
                 raise ValueError("unknown measurement %r" % (m,))
         if "time_displaced" in measurements and not self.time_displaced_plan()["every"]:
             raise _lib.DQMCError(_lib.ERR_STATE, "call set_time_displaced before run(measurements=(..., 'time_displaced'))")
-        self.prepare()
+        resumed, self._mid_sweep = self._mid_sweep, False
+        if not resumed:  # (a loaded object stands at its measurement point, the stack rebuilt by the import)
+            self.prepare()
         if binning:  # a resumed run! keeps the binners it has (DQMC.jl:395-411)
             self.enable_binning([m for m in measurements if not self._binning_enabled(m)])
         if self.last_sweep == 0:  # a resumed run! keeps the measurement state (DQMC.jl:395-411)
             self.reset_accumulators()
         total = self.p.thermalization + self.p.sweeps
         t0 = time.time()
+        while resumed and self._state() != (self.p.slices, -1):  # the rest of sweep last_sweep: no measurement point in it
+            self._c(lib().dqmc_update(self._h))
         for i in range(self.last_sweep + 1, total + 1):
             for _ in range(2 * self.p.slices):
                 self._c(lib().dqmc_update(self._h))
@@ -469,12 +489,132 @@ class DQMC:
                             ut_pass = True
                     if on_measure is not None:
                         on_measure(self, i)
+                if cs == 1 and d == 1 and checkpoint is not None and (i % int(checkpoint_every) == 0 or i == total):
+                    self.save(checkpoint, _sweep=i)
             self.last_sweep = i
             if verbose and i % 10 == 0:
                 print("\t%d\n\t\tsweep dur: %.3fs" % (i, (time.time() - t0) / 10))
                 t0 = time.time()
         self.synchronize()
         return True
+
+    # ---- checkpoint and resume (include/dqmc_hip.h "checkpoint and resume"; the file: checkpoint.py)
+    def state_size(self):
+        n = C.c_size_t()
+        self._c(lib().dqmc_state_size(self._h, C.byref(n)))
+        return n.value
+
+    def state(self):
+        """dqmc_state_export: the engine's state as a numpy.uint8 array - the HS fields, RNG cursors, counters, every
+        accumulator and binner level.  Only at the measurement point (current_slice == 1, direction == +1: where
+        update_until_measure() returns, and sweep() when it started there); the chain is left exactly as it was."""
+        buf = np.empty(self.state_size(), dtype=np.uint8)
+        self._c(lib().dqmc_state_export(self._h, buf.ctypes.data, buf.size))
+        return buf
+
+    def set_state(self, buf):
+        """dqmc_state_import into this object, which must be configured as the exporting one was (the same constructor
+        arguments, tables, time-displaced setting, binners, sign weighting, global moves): ERR_INVALID naming the first
+        field that differs otherwise, and the object stays as it was.  Afterwards the chains stand at the measurement
+        point with the stack and G rebuilt from the fields."""
+        buf = np.ascontiguousarray(buf, dtype=np.uint8).reshape(-1)
+        self._c(lib().dqmc_state_import(self._h, buf.ctypes.data, buf.size))
+
+    _MODELS = ("HubbardModelAttractive", "HubbardModelRepulsive")
+    _LATTICES = {"SquareLattice": ("L",), "Chain": ("sites",), "CubicLattice": ("dim", "L"),
+                 "TriangularLattice": ("L", "Lx", "Ly")}  # class -> the attributes its constructor takes, in order
+
+    def _preamble(self, sweep, mid_sweep):
+        m, l, p = self.model, self.model.l, self.p
+        if type(m).__name__ not in self._MODELS or type(l).__name__ not in self._LATTICES:
+            raise ValueError("save(): %s on %s is not a model / lattice a checkpoint can name"
+                             % (type(m).__name__, type(l).__name__))
+        model = {"class": type(m).__name__, "U": m.U, "t": m.t}
+        if m.kind == _lib.ATTRACTIVE:
+            model["mu"] = m.mu
+        tables = {}
+        for name, entry in self._tables.items():
+            tables[name] = {"table": _ckpt.pack_table(entry[0]), "count": entry[1]}
+            if name == "current_targets":
+                tables[name]["hopping"] = entry[2]
+        return {
+            "format": 1,
+            "model": model,
+            "lattice": {"class": type(l).__name__, "args": [int(getattr(l, a)) for a in self._LATTICES[type(l).__name__]]},
+            "dqmc": dict(self._ctor, beta=p.beta, delta_tau=p.delta_tau, slices=p.slices, safe_mult=p.safe_mult,
+                         thermalization=p.thermalization, sweeps=p.sweeps, measure_rate=p.measure_rate,
+                         check_sign_problem=bool(p.check_sign_problem),
+                         check_propagation_error=bool(p.check_propagation_error), global_moves=bool(p.global_moves),
+                         global_rate=p.global_rate, sign_weighting=self.sign_weighting()),
+            "tables": tables,
+            "time_displaced": list(self._td_args) if self._td_args else None,
+            "binning": {"sections": dict(self._bin_caps), "user": list(self._user_bin) if self._user_bin else None},
+            "global": list(self._gm_set) if self._gm_set else None,  # the last set_global_rate: (rate, DQMC_GLOBAL_* kind)
+            "susceptibilities_layout": bool(self._sus_layout),
+            "last_sweep": int(sweep),
+            "mid_sweep": bool(mid_sweep),  # saved by run() inside sweep last_sweep: its up pass is still to come
+        }
+
+    def save(self, path, _sweep=None):
+        """save(filename, mc) (FileIO.jl:38-79) for what lives on the device: one file (checkpoint.py) with a JSON
+        preamble - model, lattice, the constructor's arguments, the integer tables handed to set_pair_directions /
+        set_local_targets / set_current_targets, the time-displaced, binning, sign and global-move settings and the run
+        loop's last sweep - and the blob of state().  Written to a temporary file in the same directory and moved into
+        place, so `path` always holds a whole checkpoint.  Only at the measurement point (see state()): run(checkpoint=...)
+        calls it there, and so may the caller on an object that load() returned or that went there with
+        update_until_measure(); an object whose run() has returned stands at current_slice == slices, direction == -1 and
+        is refused (ERR_STATE).  A ConfigRecorder's configurations are the caller's and are not part of the file."""
+        blob = self.state()
+        # (a loaded object saved again before its run() is still inside the sweep its file was taken in)
+        mid = self._mid_sweep if _sweep is None else True
+        _ckpt.write(path, self._preamble(self.last_sweep if _sweep is None else _sweep, mid), blob)
+
+    @classmethod
+    def load(cls, path, device_id=0):
+        """load(filename) (FileIO.jl:95-156): an object constructed and configured as the saved one, with its state
+        imported (set_state) on device `device_id`.  seed and first_walker are the saved ones, so the files of the ranks of
+        a sharded run give back distinct walkers.  last_sweep is the saved one; run() continues behind it."""
+        from . import lattices as _lat, models as _mod
+        pre, blob = _ckpt.read(path)
+        if pre.get("format") != 1:
+            raise _ckpt.CheckpointError("checkpoint preamble format %r, this package reads format 1" % (pre.get("format"),))
+        lat, mdl = pre["lattice"], dict(pre["model"])
+        if lat["class"] not in cls._LATTICES or mdl["class"] not in cls._MODELS:
+            raise _ckpt.CheckpointError("the checkpoint names an unknown model or lattice")
+        l = getattr(_lat, lat["class"])(*lat["args"])
+        model = getattr(_mod, mdl.pop("class"))(l=l, **mdl)
+        kw = dict(pre["dqmc"])
+        mc = cls(model, device_id=device_id, **kw)
+        try:
+            t = pre["tables"]
+            if "pair_directions" in t:
+                mc._set_pair_directions(_ckpt.unpack_table(t["pair_directions"]["table"]), t["pair_directions"]["count"])
+            if "local_targets" in t:
+                mc._set_local_targets(_ckpt.unpack_table(t["local_targets"]["table"]), t["local_targets"]["count"])
+            if "current_targets" in t:
+                hop = t["current_targets"]["hopping"]
+                if hop is not None:
+                    hop = [np.asarray(hop[b * mc.N * mc.N:(b + 1) * mc.N * mc.N]).reshape((mc.N, mc.N), order="F")
+                           for b in range(mc.nb)]
+                mc._set_current_targets(_ckpt.unpack_table(t["current_targets"]["table"]), t["current_targets"]["count"], hop)
+            if pre["time_displaced"]:
+                mc.set_time_displaced(*pre["time_displaced"])
+            if pre["global"]:
+                mc.set_global_rate(*pre["global"])
+            mc.prepare()  # (the susceptibility layout and two of the binners need a prepared handle)
+            if pre["susceptibilities_layout"]:
+                mc._section_size("susceptibilities")
+            for m, cap in pre["binning"]["sections"].items():
+                mc.enable_binning(m, capacity=cap or None)
+            if pre["binning"]["user"]:
+                mc.user_binner(pre["binning"]["user"][0], pre["binning"]["user"][1] or None)
+            mc.set_state(blob)
+        except BaseException:
+            mc.close()
+            raise
+        mc.last_sweep = int(pre["last_sweep"])
+        mc._mid_sweep = bool(pre["mid_sweep"])
+        return mc
 
     # ---- Green's functions
     def _blocks(self, flat):
@@ -555,6 +695,7 @@ class DQMC:
     def set_global_rate(self, rate, kind="site"):
         """one global move per walker in every sweep whose index is a multiple of `rate` (0: off)"""
         self._c(lib().dqmc_set_global_rate(self._h, rate, self._global_kind(kind)))
+        self._gm_set = (int(rate), self._global_kind(kind))
 
     def global_stats(self, walker=0):
         """-> dict(prop_global, acc_global, moves_drawn) of one walker"""
@@ -729,6 +870,8 @@ class DQMC:
     def _section_size(self, which):
         n = C.c_size_t()
         self._c(getattr(lib(), self._SECTIONS[which][1])(self._h, C.byref(n)))
+        if which == "susceptibilities":  # (dqmc_susceptibilities_size lays the section out)
+            self._sus_layout = True
         return n.value
 
     def _section(self, which, reduced=False):
@@ -786,6 +929,9 @@ class DQMC:
                 raise ValueError("the user binner is made by user_binner(n_elements)")
             self._c(lib().dqmc_binner_enable(self._h, self._bin(m), cap))
             self._binned = getattr(self, "_binned", set()) | {m}
+            self._bin_caps[m] = cap
+            if m == "susceptibilities":  # (its binner lays the section out)
+                self._sus_layout = True
 
     def _binning_enabled(self, which):
         return which in getattr(self, "_binned", ())
@@ -793,6 +939,7 @@ class DQMC:
     def user_binner(self, n_elements, capacity=None):
         """a binner over `n_elements` samples per walker that the caller computes on the device"""
         self._c(lib().dqmc_binner_user_create(self._h, int(n_elements), self._capacity(capacity)))
+        self._user_bin = (int(n_elements), self._capacity(capacity))
 
     def user_push(self, samples):
         """push one sample [n_walkers, n_elements]: a contiguous float64 device tensor (torch) or a device address"""
@@ -930,9 +1077,13 @@ class DQMC:
     # ---- equal-time correlations (charge_density_correlation, spin_density_correlation, magnetization)
     def set_pair_directions(self, iterator):
         """hand the EachSitePairByDistance table of the lattice to the device"""
-        tab = np.asfortranarray(iterator.dir_of.astype(np.int32))  # [src, trg] -> dir_of[src + n*trg]
-        self._ndirs = iterator.ndirections()
+        self._set_pair_directions(iterator.dir_of, iterator.ndirections())
+
+    def _set_pair_directions(self, dir_of, n_dirs):
+        tab = np.asfortranarray(np.asarray(dir_of).astype(np.int32))  # [src, trg] -> dir_of[src + n*trg]
+        self._ndirs = int(n_dirs)
         self._c(lib().dqmc_set_pair_directions(self._h, tab.ctypes.data_as(C.POINTER(C.c_int32)), self._ndirs))
+        self._tables["pair_directions"] = (np.array(tab, dtype=np.int32), self._ndirs)
 
     def accumulate_correlations(self):
         self._c(lib().dqmc_accumulate_correlations(self._h))
@@ -957,9 +1108,13 @@ class DQMC:
         """hand the (dir, trg) lists of EachLocalQuadByDistance{K} to the device; the pair
         directions of the same lattice are set with it"""
         self.set_pair_directions(iterator.pairs_by_dir)
-        tab = np.asfortranarray(iterator.trg_of.astype(np.int32))  # [src, k] -> trg_of[src + n*k]
-        self._K = iterator.K
+        self._set_local_targets(iterator.trg_of, iterator.K)
+
+    def _set_local_targets(self, trg_of, K):
+        tab = np.asfortranarray(np.asarray(trg_of).astype(np.int32))  # [src, k] -> trg_of[src + n*k]
+        self._K = int(K)
         self._c(lib().dqmc_set_local_targets(self._h, tab.ctypes.data_as(C.POINTER(C.c_int32)), self._K))
+        self._tables["local_targets"] = (np.array(tab, dtype=np.int32), self._K)
 
     def accumulate_pairing(self):
         self._c(lib().dqmc_accumulate_pairing(self._h))
@@ -1027,6 +1182,7 @@ class DQMC:
         with the packed kernels summed on the device"""
         recalculate = 4 * self.p.safe_mult if recalculate is None else recalculate
         self._c(lib().dqmc_accumulate_susceptibilities(self._h, recalculate))
+        self._sus_layout = True
 
     def susceptibilities(self, _raw=None):
         """-> dict of means: CDS, SDSx, SDSy, SDSz per direction, PS[dir12, dir1, dir2] if local targets
@@ -1058,6 +1214,7 @@ class DQMC:
                     raise ValueError("unknown time-displaced part %r" % (k,))
             what = sum(bits[k] for k in set(what))
         self._c(lib().dqmc_set_time_displaced(self._h, int(every), int(what)))
+        self._td_args = (int(every), int(what)) if int(every) else None
 
     def time_displaced_plan(self):
         """-> dict(rows, every, what, fast): fast = the Green's rows take the one-lane-per-direction kernel (all zero
@@ -1094,6 +1251,9 @@ class DQMC:
         hopping_matrix(), one n x n matrix per block) to the device; the pair directions of the same lattice are
         set with it.  From then on accumulate_susceptibilities also sums CCS[dir12, dir_ii]."""
         self.set_pair_directions(iterator.pairs_by_dir)
+        self._set_current_targets(iterator.trg_of, iterator.K, hopping)
+
+    def _set_current_targets(self, trg_of, K, hopping):
         blocks = self.model.hopping_matrix() if hopping is None else hopping
         if isinstance(blocks, np.ndarray) and blocks.ndim == 2:
             blocks = [blocks]
@@ -1101,10 +1261,12 @@ class DQMC:
             raise ValueError("hopping must be %d matrices of %d x %d" % (self.nb, self.N, self.N))
         self._cc_T = np.ascontiguousarray(np.concatenate([np.asarray(b, dtype=np.float64).reshape(-1, order="F")
                                                           for b in blocks]))
-        tab = np.asfortranarray(iterator.trg_of.astype(np.int32))  # [src, k] -> trg_of[src + n*k]
-        self._c(lib().dqmc_set_current_targets(self._h, tab.ctypes.data_as(C.POINTER(C.c_int32)), iterator.K,
-                                               dptr(self._cc_T)))
-        self._Kcc = iterator.K
+        tab = np.asfortranarray(np.asarray(trg_of).astype(np.int32))  # [src, k] -> trg_of[src + n*k]
+        self._c(lib().dqmc_set_current_targets(self._h, tab.ctypes.data_as(C.POINTER(C.c_int32)), int(K), dptr(self._cc_T)))
+        self._Kcc = int(K)
+        # (the hopping goes into a checkpoint only where it is not the model's own)
+        self._tables["current_targets"] = (np.array(tab, dtype=np.int32), self._Kcc,
+                                           None if hopping is None else [float(x) for x in self._cc_T])
 
     def current_targets_fast_path(self):
         """True when the lattice took the LDS kernel for the current-current sums (see include/dqmc_hip.h)"""
