@@ -448,6 +448,58 @@ int dqmc_binner_export_moments(dqmc_handle *h, int32_t which, int32_t level, voi
 int dqmc_binner_user_create(dqmc_handle *h, int64_t n_elements, int64_t capacity);
 int dqmc_binner_user_push(dqmc_handle *h, const double *device_samples);
 
+/* ---- momentum-space observables: S(q), chi(q), G(k, tau) with error bars ----------------------------------------
+ * The reference measures per direction only; users of a Hubbard DQMC report the lattice Fourier transforms.  Like the
+ * time-displaced recording this is a defined extension.  The transform is linear, so the momentum-space MEANS are the
+ * host's to form from the existing accumulators and a phase table (dqmc.py: structure_factors, static_susceptibilities,
+ * momentum_time_displaced) and need nothing here.  Their ERROR BARS need the covariances between directions, which no
+ * binner keeps: so the transform is applied to every walker's sample on the device and the result is binned.
+ * dqmc_set_momenta(h, n_q, cos_tab, sin_tab): the tables are [n_dirs x n_q] doubles, d fastest (element d + n_dirs q),
+ * and are copied to the device.  n_q == 0 turns the feature off and frees everything (the default; the tables are then
+ * ignored); otherwise 1 <= n_q <= n_dirs and both tables non-NULL, anything else returns DQMC_ERR_INVALID and the
+ * handle keeps its setting.  Needs dqmc_set_pair_directions (DQMC_ERR_STATE without it); a later
+ * dqmc_set_pair_directions turns momenta off, because the tables no longer fit.  Every successful call frees the three
+ * binners below; the caller enables them again.
+ * The engine attaches no meaning to the tables.  The convention of this header and of dqmc.py: C[d, q] = cos(q . r_d),
+ * S[d, q] = sin(q . r_d) with r_d the displacement of direction d, pos[src] - pos[trg] under the minimum image
+ * (EachSitePairByDistance.directions), so that sum_d e^{-i q . r_d} X[d] = Cpart[q] - i Spart[q] with
+ *   Cpart[q] = sum_d X[d] C[d, q],  Spart[q] = sum_d X[d] S[d, q],  d in ascending order (csrc/momentum.hip).
+ * The three binner sections, enabled with dqmc_binner_enable(h, which, capacity) and read with dqmc_binner_size,
+ * _reliable_level, _get_level, _finish and _export_moments like any other; per-walker sample, q fastest:
+ *   DQMC_BIN_MOMENTUM_CORRELATIONS      fed by dqmc_accumulate_correlations: [Sc][Sx][Sy][Sz], n_q each: Cpart of cdc,
+ *                                       sdc_x, sdc_y, sdc_z.  E = 4 n_q
+ *   DQMC_BIN_MOMENTUM_SUSCEPTIBILITIES  fed by dqmc_accumulate_susceptibilities: [chi_c][chi_x][chi_y][chi_z], n_q each:
+ *                                       Cpart of cds, sds_x, sds_y, sds_z, times delta_tau as that section's binner
+ *                                       takes them.  E = 4 n_q.  Needs dqmc_prepare, as its source does
+ *   DQMC_BIN_MOMENTUM_TIME_DISPLACED    fed by dqmc_accumulate_susceptibilities while recording is on; needs
+ *                                       dqmc_set_time_displaced.  If GREENS: [Gl0 C][Gl0 S][G0l C][G0l S], each
+ *                                       n_blocks R n_q (q fastest, then r, then the block): Cpart and Spart of the rows
+ *                                       Gl0[b][r][.] and G0l[b][r][.]; if DENSITY: [CDC][SDCx][SDCy][SDCz], each R n_q,
+ *                                       Cpart only.  E = (4 n_blocks + 4) R n_q with both parts
+ * The density-type rows take the cosine only: their Wick expressions are symmetric under i <-> j, so X[d] = X[-d] in
+ * every sample and the sine part is rounding noise.  The pairing and current-current sums (ps, ccs) are not transformed.
+ * Memory per binner: (3 L - 1) n_walkers E doubles, as for every section: a momentum binner over n_q momenta is n_q /
+ * n_dirs (Green's rows: 2 n_q / n_dirs) of the real-space one.
+ * A momentum binner is pushed on the handle's stream behind the source section's kernels, whether or not the source
+ * section's own binner is enabled; the room of every binner of a call is checked before anything is accumulated
+ * (DQMC_ERR_STATE when a capacity would be passed); dqmc_reset_accumulators clears them.  The sample is the transform of
+ * exactly what the source section's binner receives.  Enabling one before dqmc_set_momenta (the time-displaced one:
+ * before dqmc_set_time_displaced) returns DQMC_ERR_STATE; dqmc_set_momenta or, for the time-displaced one,
+ * dqmc_set_time_displaced called afterwards disables it.
+ * Sign weighting: the sources are s_w x already where the transform reads them, and the momentum sample has one more
+ * element at its end, s_w itself (E grows by 1: dqmc_binner_size reports it), so that the host forms <s O~> / <s> and
+ * its jackknife over the walkers from level 0 of this one binner; there is no DQMC_BIN_SIGN + k for these sections.
+ * dqmc_set_sign_weighting re-creates the momentum binners that were enabled before it, empty, with their capacities.
+ * Every output element is one dot product summed in a fixed order with no atomics: a second pass on the same state gives
+ * the same bits, and a walker's sample depends neither on n_walkers nor on the other rows.  There is no DQMC_RED_*
+ * section for momenta: with no momentum binner enabled nothing is allocated beyond the two tables, nothing is launched,
+ * and every result, reduction buffer and state blob is byte for byte that of a handle that never called
+ * dqmc_set_momenta.  dqmc_momenta_plan: out = [n_q, n_dirs, tile rows, tile columns of the kernel], zeros when off. */
+enum { DQMC_BIN_MOMENTUM_CORRELATIONS = 11, DQMC_BIN_MOMENTUM_SUSCEPTIBILITIES = 12, DQMC_BIN_MOMENTUM_TIME_DISPLACED = 13,
+       DQMC_BIN_MOMENTUM_END = 14 };
+int dqmc_set_momenta(dqmc_handle *h, int32_t n_q, const double *cos_tab, const double *sin_tab);
+int dqmc_momenta_plan(dqmc_handle *h, int32_t out[4]);   /* [n_q, n_dirs, tile rows, tile cols], zeros when off */
+
 /* ---- measurement reduction over ranks -------------------
  * One process (or thread) per GPU; walkers never interact, the only collective is the reduction of the measurement
  * sums every `measure_rate` sweeps (DQMC.jl:429-436).  dqmc_reduce packs EVERY accumulator of the handle (Green's
@@ -513,7 +565,19 @@ int dqmc_get_reduced_stats(dqmc_handle *h, dqmc_stats *out);
  *     the accumulator of every configured section in DQMC_RED_* order, the sums of signs included (n doubles each)
  *     x_sum [L][W][E], x2_sum [L][W][E], compressor [L - 1][W][E] of every enabled binner in the order of the header
  * The binner's T and the update count are state and come back with the payload; every other header field describes how
- * the handle is configured and must be the same on both sides. */
+ * the handle is configured and must be the same on both sides.
+ * Format version 2: the header has room for exactly the eleven binners above, so a handle with a momentum binner enabled
+ * (DQMC_BIN_MOMENTUM_*) writes version 2: the version-1 header (its version field reads 2) and payload, followed by an
+ * extension; a handle with none enabled writes the version-1 blob unchanged, whether or not momenta are set.
+ *   extension
+ *     i32 n_q, n_dirs     3 binners (DQMC_BIN_MOMENTUM_CORRELATIONS ..): i32 on, E, L, pad   i64 capacity, T
+ *     cos_tab, sin_tab: n_dirs n_q doubles each
+ *     x_sum, x2_sum, compressor of every enabled momentum binner, as above
+ *     u64 FNV-1a 64 of all extension bytes in front of it
+ * dqmc_state_import takes both versions.  The extension is validated like the header, before the first write: its size,
+ * its checksum (which covers the binner arrays too), then n_q, n_dirs and the binner shapes against the importing
+ * handle's, then the tables byte for byte against the handle's own; a version-1 blob is refused by a handle with a
+ * momentum binner enabled. */
 /* bytes of the blob of this handle as it is configured now */
 int dqmc_state_size(dqmc_handle *h, size_t *n_bytes);
 /* The blob into host_out (n_bytes = dqmc_state_size).  Only at the measurement point, current_slice == 1 && direction ==

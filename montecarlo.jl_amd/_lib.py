@@ -17,6 +17,8 @@ BIN_SECTIONS = ("greens", "correlations", "pairing", "susceptibilities", "user")
 BIN_TIME_DISPLACED, RED_TIME_DISPLACED = 5, 4  # DQMC_BIN_TIME_DISPLACED, DQMC_RED_TIME_DISPLACED (enums of their own)
 TD_GREENS, TD_DENSITY = 1, 2                   # DQMC_TD_*
 BIN_SIGN, RED_SIGN = 6, 5                      # DQMC_BIN_SIGN (+ a section's DQMC_RED_* index), DQMC_RED_SIGN
+# DQMC_BIN_MOMENTUM_*: the momentum-space binners, above every other DQMC_BIN_* value
+BIN_MOMENTUM = {"momentum_correlations": 11, "momentum_susceptibilities": 12, "momentum_time_displaced": 13}
 K_FAMILIES = ("gemm", "qr", "trsm", "sweep", "misc", "flush")
 
 
@@ -184,6 +186,8 @@ SIGNATURES = {
     "dqmc_binner_export_moments": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_void_p]),
     "dqmc_binner_user_create": (C.c_int, [_H, C.c_int64, C.c_int64]),
     "dqmc_binner_user_push": (C.c_int, [_H, C.c_void_p]),
+    "dqmc_set_momenta": (C.c_int, [_H, C.c_int32, _dp, _dp]),
+    "dqmc_momenta_plan": (C.c_int, [_H, C.POINTER(C.c_int32)]),
     "dqmc_comm_unique_id": (C.c_int, [C.c_void_p]),
     "dqmc_comm_init": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_H)]),
     "dqmc_comm_destroy": (C.c_int, [_H]),

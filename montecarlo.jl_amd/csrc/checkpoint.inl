@@ -9,6 +9,8 @@
 static_assert(sizeof(DevStats) == dqmc_blob::STATS_BYTES, "DevStats is stored as it lies in memory");
 static_assert(sizeof(GlobalMoveState) == dqmc_blob::GM_BYTES, "GlobalMoveState is stored as it lies in memory");
 static_assert(DQMC_RED_SIGN + 1 == dqmc_blob::N_SEC && DQMC_BIN_SIGN + DQMC_RED_SIGN == dqmc_blob::N_BIN, "section tables");
+static_assert(DQMC_BIN_MOMENTUM_CORRELATIONS == dqmc_blob::N_BIN && DQMC_BIN_MOMENTUM_END - DQMC_BIN_MOMENTUM_CORRELATIONS == dqmc_blob::N_MOM,
+              "the momentum binners follow the header's binners: the extension of format version 2");
 
 static void state_shape(const dqmc_handle *h, dqmc_blob::Shape *s)
 {
@@ -25,6 +27,20 @@ static void state_shape(const dqmc_handle *h, dqmc_blob::Shape *s)
     s->td_every = h->td.every; s->td_what = h->td.what; s->td_R = h->td.R;
     s->sign_on = h->sign_on ? 1 : 0;
     s->gm_rate = h->gm_rate; s->gm_kind = h->gm_kind; s->gm_updates = h->gm_updates;
+}
+
+// the momentum binners and the tables they were made for: what the extension of a version-2 blob carries.  With no
+// momentum binner enabled it is empty (m->any() false) and the blob is version 1, momenta set or not.
+static void state_momenta(const dqmc_handle *h, dqmc_blob::Momenta *m)
+{
+    *m = dqmc_blob::Momenta{};
+    for (int k = 0; k < dqmc_blob::N_MOM; ++k) {
+        const dqmc_handle::Binner &b = h->bin[DQMC_BIN_MOMENTUM_CORRELATIONS + k];
+        if (b.on) m->bin[k] = {1, b.E, b.L, b.cap, b.T};
+    }
+    if (!m->any()) return;
+    m->n_q = h->mom.n_q; m->n_dirs = h->n_dirs;
+    m->cos_tab = h->mom.cos_h.data(); m->sin_tab = h->mom.sin_h.data();
 }
 
 // The state dqmc_update_until_measure returns in (and dqmc_sweep when it started there), rebuilt from the HS field alone: dqmc_prepare's init_stack,
@@ -46,10 +62,12 @@ int dqmc_state_size(dqmc_handle *h, size_t *n_bytes)
 {
     if (!h || !n_bytes) return DQMC_ERR_INVALID;
     dqmc_blob::Shape s;
-    dqmc_blob::Layout l;
+    dqmc_blob::Momenta m;
+    dqmc_blob::ExtLayout e;
     state_shape(h, &s);
-    if (!dqmc_blob::layout(s, &l)) return fail(h, DQMC_ERR_INVALID, "dqmc_state_size: the state does not fit a size_t");
-    *n_bytes = l.total;
+    state_momenta(h, &m);
+    if (!dqmc_blob::ext_layout(s, m, &e)) return fail(h, DQMC_ERR_INVALID, "dqmc_state_size: the state does not fit a size_t");
+    *n_bytes = e.total;
     return DQMC_OK;
 }
 
@@ -63,11 +81,15 @@ int dqmc_state_export(dqmc_handle *h, void *host_out, size_t n_bytes)
     if (h->pf.G) return fail(h, DQMC_ERR_STATE, "dqmc_state_export: a sweep update is pending on greens");
     dqmc_blob::Shape s;
     dqmc_blob::Layout l;
+    dqmc_blob::Momenta m;
+    dqmc_blob::ExtLayout e;
     state_shape(h, &s);
-    if (!dqmc_blob::layout(s, &l)) return fail(h, DQMC_ERR_INVALID, "dqmc_state_export: the state does not fit a size_t");
-    if (n_bytes != l.total)
+    state_momenta(h, &m);
+    if (!dqmc_blob::layout(s, &l) || !dqmc_blob::ext_layout(s, m, &e))
+        return fail(h, DQMC_ERR_INVALID, "dqmc_state_export: the state does not fit a size_t");
+    if (n_bytes != e.total)
         return fail(h, DQMC_ERR_INVALID, "dqmc_state_export: n_bytes is " + std::to_string(n_bytes) + ", dqmc_state_size reports " +
-                                             std::to_string(l.total));
+                                             std::to_string(e.total));
     HIPCHK(hipStreamSynchronize(h->stream));
     std::vector<WalkerRng> rg(h->W);
     HIPCHK(hipMemcpy(rg.data(), h->rng, sizeof(WalkerRng) * h->W, hipMemcpyDeviceToHost));
@@ -76,7 +98,7 @@ int dqmc_state_export(dqmc_handle *h, void *host_out, size_t n_bytes)
             return fail(h, DQMC_ERR_STATE, "dqmc_state_export: walker " + std::to_string(w) + " runs on a host-supplied uniform "
                                            "stream (dqmc_set_uniforms), which the blob does not carry");
     uint8_t *out = (uint8_t *)host_out;
-    dqmc_blob::write_header(s, out);
+    dqmc_blob::write_header(s, m, out);
     {   // only copies from here on: nothing is launched, no buffer of the handle is written
         const size_t sz = (size_t)h->N * h->M, chunk_bytes = dqmc_blob::conf_chunks(h->N, h->M) * 8;
         std::vector<int8_t> conf((size_t)h->W * sz);
@@ -100,6 +122,18 @@ int dqmc_state_export(dqmc_handle *h, void *host_out, size_t n_bytes)
         HIPCHK(hipMemcpy(out + l.bin_x2[k], b.x2, b.L * we, hipMemcpyDeviceToHost));
         if (b.L > 1) HIPCHK(hipMemcpy(out + l.bin_c[k], b.c, (b.L - 1) * we, hipMemcpyDeviceToHost));
     }
+    if (m.any()) {  // format version 2: the extension
+        dqmc_blob::write_ext(m, e, out);
+        for (int k = 0; k < dqmc_blob::N_MOM; ++k) {
+            const dqmc_handle::Binner &b = h->bin[DQMC_BIN_MOMENTUM_CORRELATIONS + k];
+            if (!b.on) continue;
+            const size_t we = (size_t)h->W * (size_t)b.E * sizeof(double);
+            HIPCHK(hipMemcpy(out + e.bin_xs[k], b.xs, b.L * we, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(out + e.bin_x2[k], b.x2, b.L * we, hipMemcpyDeviceToHost));
+            if (b.L > 1) HIPCHK(hipMemcpy(out + e.bin_c[k], b.c, (b.L - 1) * we, hipMemcpyDeviceToHost));
+        }
+        dqmc_blob::seal_ext(e, out);
+    }
     return DQMC_OK;
 }
 
@@ -107,10 +141,14 @@ int dqmc_state_import(dqmc_handle *h, const void *host_in, size_t n_bytes)
 {
     ENTER(h);
     dqmc_blob::Shape mine, s;
+    dqmc_blob::Momenta mine_m, m;
     dqmc_blob::Layout l;
+    dqmc_blob::ExtLayout e;
     std::string why;
     state_shape(h, &mine);
-    if (dqmc_blob::validate((const uint8_t *)host_in, n_bytes, mine, &s, &why) != 0 || !dqmc_blob::layout(s, &l, &why))
+    state_momenta(h, &mine_m);
+    if (dqmc_blob::validate_any((const uint8_t *)host_in, n_bytes, mine, mine_m, &s, &m, &why) != 0 || !dqmc_blob::layout(s, &l, &why) ||
+        !dqmc_blob::ext_layout(s, m, &e, &why))
         return fail(h, DQMC_ERR_INVALID, "dqmc_state_import: " + why);
     const uint8_t *in = (const uint8_t *)host_in;
     // the one index the payload carries: the site of a walker's latest global move (the next proposal overwrites it before
@@ -156,6 +194,15 @@ int dqmc_state_import(dqmc_handle *h, const void *host_in, size_t n_bytes)
         HIPCHK(hipMemcpy(b.x2, in + l.bin_x2[k], b.L * we, hipMemcpyHostToDevice));
         if (b.L > 1) HIPCHK(hipMemcpy(b.c, in + l.bin_c[k], (b.L - 1) * we, hipMemcpyHostToDevice));
         b.T = s.bin[k].T;
+    }
+    for (int k = 0; k < dqmc_blob::N_MOM; ++k) {  // (format version 2; a version-1 blob has none and the handle neither)
+        dqmc_handle::Binner &b = h->bin[DQMC_BIN_MOMENTUM_CORRELATIONS + k];
+        if (!b.on) continue;
+        const size_t we = (size_t)h->W * (size_t)b.E * sizeof(double);
+        HIPCHK(hipMemcpy(b.xs, in + e.bin_xs[k], b.L * we, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(b.x2, in + e.bin_x2[k], b.L * we, hipMemcpyHostToDevice));
+        if (b.L > 1) HIPCHK(hipMemcpy(b.c, in + e.bin_c[k], (b.L - 1) * we, hipMemcpyHostToDevice));
+        b.T = m.bin[k].T;
     }
     h->gm_updates = s.gm_updates;
     return dqmc_synchronize(h);

@@ -152,7 +152,16 @@ struct dqmc_handle {
         int E = 0, L = 0;
         int64_t cap = 0, T = 0;  // capacity and pushes so far: count[level] = T >> level for every element
         double *xs = nullptr, *x2 = nullptr, *c = nullptr, *out = nullptr;
-    } bin[DQMC_BIN_SIGN + DQMC_RED_SIGN];  // (DQMC_BIN_SIGN + k: the signs pushed with section k = a DQMC_RED_* index)
+    } bin[DQMC_BIN_MOMENTUM_END];  // (DQMC_BIN_SIGN + k: the signs pushed with section k = a DQMC_RED_* index; then the momentum binners)
+    // momentum-space observables (momentum.inl, momentum.hip): n_q == 0: off, nothing allocated.  cos_d / sin_d
+    // [n_dirs x n_q] on the device, the host copies for the checkpoint; sample[k]: the per-walker momentum sample
+    // [W][E] of binner DQMC_BIN_MOMENTUM_CORRELATIONS + k, allocated with the binner
+    struct Momenta {
+        int n_q = 0;
+        double *cos_d = nullptr, *sin_d = nullptr;
+        std::vector<double> cos_h, sin_h;
+        double *sample[DQMC_BIN_MOMENTUM_END - DQMC_BIN_MOMENTUM_CORRELATIONS] = {nullptr, nullptr, nullptr};
+    } mom;
     // time-displaced recording (unequal_time.inl, tdm.hip): every == 0: off, nothing allocated.  The sample (bin_E doubles
     // per walker in the layout of include/dqmc_hip.h) and the sums are sec[DQMC_RED_TIME_DISPLACED]; src_of [n_dirs][n]
     // only with the fast form
@@ -1750,6 +1759,11 @@ int dqmc_get_stats(dqmc_handle *h, int32_t w, dqmc_stats *out)
 // layout has changed; binner_push_section pushes the samples the measurement kernels have just left on the device
 static int binner_room(dqmc_handle *h, int which);
 static int binner_push_section(dqmc_handle *h, int which);
+// momentum.inl: the transform of the source section's per-walker sample, then its push; mom_off drops the tables and the
+// three binners, mom_disable one binner
+static int mom_push(dqmc_handle *h, int which);
+static void mom_disable(dqmc_handle *h, int which);
+static void mom_off(dqmc_handle *h);
 // global_move.inl: with sign weighting on, s_w of the current fields into sign_sw and their sum into the sign sums of the
 // sections about to be fed (DQMC_RED_* indices; sec_b < 0: one section); nothing with it off.  Runs a slice chain unless
 // the cache of the current field holds, so it comes in front of true_greens (the chain overwrites tmp1 / tmp2).
@@ -1801,6 +1815,7 @@ int dqmc_set_pair_directions(dqmc_handle *h, const int32_t *dir_of, int32_t n_di
     }
     dfree(h, &h->dir_ptr);
     CHK(dalloc(h, &h->dir_ptr, (size_t)n_dirs + 1));
+    mom_off(h);  // the phase tables belong to the old directions
     h->n_dirs = n_dirs;
     h->red_valid = false;  // (re)sized: the last reduction is void
     const size_t corr_n = 4 * (size_t)n_dirs + 3 * (size_t)n + 1;
@@ -1818,6 +1833,7 @@ int dqmc_accumulate_correlations(dqmc_handle *h)
     ENTER(h); NEED_PREPARED(h);
     if (!h->n_dirs) return fail(h, DQMC_ERR_STATE, "call dqmc_set_pair_directions first");
     CHK(binner_room(h, DQMC_BIN_CORRELATIONS));
+    CHK(binner_room(h, DQMC_BIN_MOMENTUM_CORRELATIONS));
     CHK(sign_begin(h, DQMC_RED_CORRELATIONS));
     CHK(true_greens(h, h->greens));
     if (h->sign_on) {
@@ -1834,6 +1850,7 @@ int dqmc_accumulate_correlations(dqmc_handle *h)
                                    h->sec[DQMC_RED_CORRELATIONS].acc, h->stream));
     }
     if (h->bin[DQMC_BIN_CORRELATIONS].on) CHK(binner_push_section(h, DQMC_BIN_CORRELATIONS));
+    if (h->bin[DQMC_BIN_MOMENTUM_CORRELATIONS].on) CHK(mom_push(h, DQMC_BIN_MOMENTUM_CORRELATIONS));
     return DQMC_OK;
 }
 // EachLocalQuadByDistance{K}(lattice) (lattice_iterators.jl:264-318) as a target table
@@ -1925,6 +1942,7 @@ int dqmc_export_pairing(dqmc_handle *h, void *device_out) { ENTER(h); return sec
 
 #include "unequal_time.inl"
 #include "binner.inl"
+#include "momentum.inl"
 #include "global_move.inl"
 #include "checkpoint.inl"
 

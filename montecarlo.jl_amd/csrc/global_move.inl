@@ -123,6 +123,9 @@ int dqmc_set_sign_weighting(dqmc_handle *h, int32_t on)
     for (int which = DQMC_BIN_GREENS; which <= DQMC_BIN_TIME_DISPLACED; ++which)
         if (which != DQMC_BIN_USER && h->bin[which].on && h->bin[which].T)
             return fail(h, DQMC_ERR_STATE, "dqmc_set_sign_weighting: a binner has samples: call dqmc_reset_accumulators first");
+    for (int which = DQMC_BIN_MOMENTUM_CORRELATIONS; which < DQMC_BIN_MOMENTUM_END; ++which)
+        if (h->bin[which].on && h->bin[which].T)
+            return fail(h, DQMC_ERR_STATE, "dqmc_set_sign_weighting: a binner has samples: call dqmc_reset_accumulators first");
     h->sign_on = on != 0;
     h->red_valid = false;  // (re)sized: the last reduction is void
     dqmc_handle::Section &sg = h->sec[DQMC_RED_SIGN];
@@ -134,6 +137,9 @@ int dqmc_set_sign_weighting(dqmc_handle *h, int32_t on)
         if (h->sign_on && h->bin[which].on) CHK(binner_alloc(h, binner_sign_of(which), 1, h->bin[which].cap));
         else if (sb.on) binner_free(h, sb);
     }
+    // a momentum sample ends with s_w while weighting is on: its binners are made again, empty, with their capacities
+    for (int which = DQMC_BIN_MOMENTUM_CORRELATIONS; which < DQMC_BIN_MOMENTUM_END; ++which)
+        if (h->bin[which].on) CHK(mom_enable(h, which, h->bin[which].cap));
     return dqmc_synchronize(h);
 }
 int dqmc_get_sign_weighting(dqmc_handle *h, int32_t *on)

@@ -448,6 +448,17 @@ hipError_t launch_binner_push(const BinPush &p, int W, int E, int L, int lmax, d
 // out [8 E + 1]: mean, std_error, std_error_walkers, tau, sum mean_w, sum mean_w^2, sum varN_w(level), sum varN_w(0), W
 hipError_t launch_binner_finish(int W, int E, long T, int level, const double *xs, const double *x2, double *out,
                                 hipStream_t s);
+// the lattice Fourier transform of a segment of every walker's sample (momentum.hip): for w < n_walkers, row < rows,
+// q < n_q:  Y[w y_stride + y_off + row n_q + q] = scale * sum_d X[w x_stride + x_off + row n_dirs + d] tab[d + n_dirs q],
+// d in ascending order.  sw != nullptr: the launch also writes Y[w y_stride + sign_at] = sw[w].
+struct MomentumArgs {
+    const double *X = nullptr, *tab = nullptr, *sw = nullptr;
+    double *Y = nullptr;
+    long x_stride = 0, x_off = 0, y_stride = 0, y_off = 0, sign_at = 0;
+    int rows = 0, n_dirs = 0, n_q = 0;
+    double scale = 1.0;
+};
+hipError_t launch_momentum(const MomentumArgs &a, int n_walkers, hipStream_t s);
 // log|det| and sign of I + B_M ... B_1 per unit (logdet.hip): logabsdet = sum_i log D2[i] with D2 the D of the second
 // udt_AVX_pivot! of calculate_greens_AVX! (stack.jl:376), sign = sign det A2 of the matrix that UDT factors, from an LU
 // with partial pivoting of the copy in A2 (n_units x strideA, destroyed).  One workgroup per unit, fixed summation order.

@@ -11,6 +11,7 @@ const char *const SEC_NAME[N_SEC] = {"greens", "correlations", "pairing", "susce
 const char *const BIN_NAME[N_BIN] = {"greens", "correlations", "pairing", "susceptibilities", "user", "time_displaced",
                                      "sign:greens", "sign:correlations", "sign:pairing", "sign:susceptibilities",
                                      "sign:time_displaced"};
+const char *const MOM_NAME[N_MOM] = {"momentum_correlations", "momentum_susceptibilities", "momentum_time_displaced"};
 
 void put(uint8_t *&p, uint64_t v, int bytes)
 {
@@ -42,6 +43,7 @@ uint64_t fnv1a(const uint8_t *p, size_t n)
 }
 
 enum { HEADER_BYTES = 8 + 4 + 4 + HASH_BYTES + 6 * 4 + 2 * 8 + 2 * N_SEC * 8 + N_BIN * 32 + 6 * 4 + 8 + 8 };
+enum { EXT_FIXED_BYTES = 2 * 4 + N_MOM * 32 };
 
 bool mul(size_t a, size_t b, size_t *out) { return !__builtin_mul_overflow(a, b, out); }
 bool add(size_t a, size_t b, size_t *out) { return !__builtin_add_overflow(a, b, out); }
@@ -100,11 +102,11 @@ bool layout(const Shape &s, Layout *out, std::string *why)
     return true;
 }
 
-void write_header(const Shape &s, uint8_t *out)
+static void write_header_version(const Shape &s, uint32_t version, uint8_t *out)
 {
     uint8_t *p = out;
     put(p, MAGIC, 8);
-    put(p, VERSION, 4);
+    put(p, version, 4);
     put(p, HEADER_BYTES, 4);
     std::memcpy(p, s.source_hash, HASH_BYTES);
     p += HASH_BYTES;
@@ -126,8 +128,13 @@ void write_header(const Shape &s, uint8_t *out)
     put(p, (uint64_t)s.gm_updates, 8);
     put(p, fnv1a(out, (size_t)(p - out)), 8);
 }
+void write_header(const Shape &s, uint8_t *out) { write_header_version(s, VERSION, out); }
+void write_header(const Shape &s, const Momenta &m, uint8_t *out) { write_header_version(s, m.any() ? VERSION_MOMENTA : VERSION, out); }
 
-int validate(const uint8_t *buf, size_t n_bytes, const Shape &h, Shape *blob, std::string *why)
+// validate without its last step, the comparison of n_bytes with the size the header implies (*total).  newest: the
+// highest format version the caller reads
+static int validate_head(const uint8_t *buf, size_t n_bytes, const Shape &h, uint32_t newest, Shape *blob, uint32_t *version_out,
+                         size_t *total, std::string *why)
 {
     if (!buf) return refuse(why, "buffer: NULL");
     if (n_bytes < HEADER_BYTES)
@@ -136,12 +143,13 @@ int validate(const uint8_t *buf, size_t n_bytes, const Shape &h, Shape *blob, st
     const uint8_t *p = buf;
     if (get(p, 8) != MAGIC) return refuse(why, "magic: not a dqmc_state_export blob");
     const uint32_t version = (uint32_t)get(p, 4);
-    if (version != VERSION)
+    if (version < VERSION || version > newest)
         return refuse(why, "version: format version " + std::to_string(version) + ", this library reads version " +
-                               std::to_string(VERSION));
+                               std::to_string(VERSION) + (newest > VERSION ? " and " + std::to_string(newest) : std::string()));
     if (get(p, 4) != HEADER_BYTES) return refuse(why, "header_bytes: not the header size of format version 1");
     const uint8_t *sum_at = buf + HEADER_BYTES - 8;
-    if (get(sum_at, 8) != fnv1a(buf, HEADER_BYTES - 8)) return refuse(why, "checksum: the header is damaged");
+    if (get(sum_at, 8) != fnv1a(buf, HEADER_BYTES - 8))
+        return refuse(why, "checksum: the header is damaged (it claims format version " + std::to_string(version) + ")");
 
     Shape s{};
     std::memcpy(s.source_hash, p, HASH_BYTES);
@@ -203,10 +211,156 @@ int validate(const uint8_t *buf, size_t n_bytes, const Shape &h, Shape *blob, st
     Layout l;
     std::string lw;
     if (!layout(s, &l, &lw)) return refuse(why, lw + ": not a shape a handle can have");
-    if (n_bytes != l.total)
-        return refuse(why, "n_bytes: the buffer has " + std::to_string(n_bytes) + " bytes, the header describes " +
-                               std::to_string(l.total));
     if (blob) *blob = s;
+    *version_out = version;
+    *total = l.total;
+    return 0;
+}
+static int refuse_size(std::string *why, size_t n_bytes, size_t want)
+{
+    return refuse(why, "n_bytes: the buffer has " + std::to_string(n_bytes) + " bytes, the header describes " + std::to_string(want));
+}
+int validate(const uint8_t *buf, size_t n_bytes, const Shape &h, Shape *blob, std::string *why)
+{
+    Shape s{};
+    uint32_t version = 0;
+    size_t total = 0;
+    if (validate_head(buf, n_bytes, h, VERSION, &s, &version, &total, why) != 0) return -1;
+    if (n_bytes != total) return refuse_size(why, n_bytes, total);
+    if (blob) *blob = s;
+    return 0;
+}
+
+bool ext_layout(const Shape &s, const Momenta &m, ExtLayout *out, std::string *why)
+{
+    auto bad = [&](const char *what) {
+        if (why) *why = what;
+        return false;
+    };
+    Layout l;
+    if (!layout(s, &l, why)) return false;
+    ExtLayout e{};
+    e.start = e.total = l.total;
+    if (!m.any()) {
+        if (out) *out = e;
+        return true;
+    }
+    if (m.n_dirs < 1 || m.n_q < 1 || m.n_q > m.n_dirs) return bad("momenta n_q, n_dirs");
+    const size_t W = (size_t)s.n_walkers;
+    size_t off = e.start, skip, tab;
+    bool ok = take(&off, &skip, EXT_FIXED_BYTES, 1) && mul((size_t)m.n_dirs, (size_t)m.n_q, &tab);
+    ok = ok && take(&off, &e.cos_tab, tab, 8) && take(&off, &e.sin_tab, tab, 8);
+    for (int k = 0; k < N_MOM && ok; ++k) {
+        const Shape::Bin &b = m.bin[k];
+        e.bin_xs[k] = e.bin_x2[k] = e.bin_c[k] = off;
+        if (!b.on) continue;
+        if (b.E < 1 || b.L < 1 || b.L > 41) return bad("momentum binner elements / levels");
+        size_t we;
+        ok = mul(W, (size_t)b.E, &we) && mul(we, 8, &we);
+        ok = ok && take(&off, &e.bin_xs[k], (size_t)b.L, we);
+        ok = ok && take(&off, &e.bin_x2[k], (size_t)b.L, we);
+        ok = ok && take(&off, &e.bin_c[k], (size_t)b.L - 1, we);
+    }
+    ok = ok && take(&off, &e.checksum, 1, 8);
+    if (!ok) return bad("blob size overflows");
+    e.total = off;
+    if (out) *out = e;
+    return true;
+}
+
+void write_ext(const Momenta &m, const ExtLayout &e, uint8_t *blob)
+{
+    if (!m.any()) return;
+    uint8_t *p = blob + e.start;
+    put(p, (uint32_t)m.n_q, 4);
+    put(p, (uint32_t)m.n_dirs, 4);
+    for (int k = 0; k < N_MOM; ++k) {
+        const Shape::Bin &b = m.bin[k];
+        put(p, (uint32_t)b.on, 4);
+        put(p, (uint32_t)b.E, 4);
+        put(p, (uint32_t)b.L, 4);
+        put(p, 0, 4);
+        put(p, (uint64_t)b.cap, 8);
+        put(p, (uint64_t)b.T, 8);
+    }
+    const size_t tab = (size_t)m.n_dirs * (size_t)m.n_q;
+    for (size_t i = 0; i < tab; ++i) put(p, bits_of(m.cos_tab[i]), 8);
+    for (size_t i = 0; i < tab; ++i) put(p, bits_of(m.sin_tab[i]), 8);
+}
+
+void seal_ext(const ExtLayout &e, uint8_t *blob)
+{
+    if (e.total == e.start) return;
+    uint8_t *p = blob + e.checksum;
+    put(p, fnv1a(blob + e.start, e.checksum - e.start), 8);
+}
+
+int validate_any(const uint8_t *buf, size_t n_bytes, const Shape &h, const Momenta &hm, Shape *blob, Momenta *mblob,
+                 std::string *why)
+{
+    Shape s{};
+    uint32_t version = 0;
+    size_t total = 0;
+    if (validate_head(buf, n_bytes, h, VERSION_MOMENTA, &s, &version, &total, why) != 0) return -1;
+    Momenta m{};
+    if (version == VERSION) {
+        if (n_bytes != total) return refuse_size(why, n_bytes, total);
+        for (int k = 0; k < N_MOM; ++k)
+            if (hm.bin[k].on)
+                return refuse(why, std::string("binner ") + MOM_NAME[k] + " on: the blob (format version 1) has 0, the handle 1");
+    } else {
+        if (n_bytes < total || n_bytes - total < EXT_FIXED_BYTES) return refuse_size(why, n_bytes, total + EXT_FIXED_BYTES);
+        const uint8_t *p = buf + total;
+        m.n_q = (int32_t)(uint32_t)get(p, 4);
+        m.n_dirs = (int32_t)(uint32_t)get(p, 4);
+        for (int k = 0; k < N_MOM; ++k) {
+            Shape::Bin &b = m.bin[k];
+            b.on = (int32_t)(uint32_t)get(p, 4);
+            b.E = (int32_t)(uint32_t)get(p, 4);
+            b.L = (int32_t)(uint32_t)get(p, 4);
+            (void)get(p, 4);
+            b.cap = (int64_t)get(p, 8);
+            b.T = (int64_t)get(p, 8);
+            if (b.on != 0 && b.on != 1) return refuse(why, std::string("binner ") + MOM_NAME[k] + " on: neither 0 nor 1");
+        }
+        if (!m.any()) return refuse(why, "extension: a format version 2 blob with no momentum binner in it");
+        ExtLayout e;
+        std::string lw;
+        if (!ext_layout(s, m, &e, &lw)) return refuse(why, lw + ": not a shape a handle can have");
+        if (n_bytes != e.total) return refuse_size(why, n_bytes, e.total);
+        const uint8_t *sum_at = buf + e.checksum;
+        if (get(sum_at, 8) != fnv1a(buf + e.start, e.checksum - e.start))
+            return refuse(why, "extension checksum: the extension is damaged");
+#define SAME_M(field, name)                                                                                           \
+    if (!(m.field == hm.field))                                                                                       \
+        return refuse(why, std::string(name) + ": the blob has " + std::to_string(m.field) + ", the handle " +        \
+                               std::to_string(hm.field))
+        SAME_M(n_q, "momenta n_q");
+        SAME_M(n_dirs, "momenta n_dirs");
+        for (int k = 0; k < N_MOM; ++k) {
+            SAME_M(bin[k].on, std::string("binner ") + MOM_NAME[k] + " on");
+            SAME_M(bin[k].E, std::string("binner ") + MOM_NAME[k] + " E");
+            SAME_M(bin[k].L, std::string("binner ") + MOM_NAME[k] + " L");
+            SAME_M(bin[k].cap, std::string("binner ") + MOM_NAME[k] + " cap");
+        }
+#undef SAME_M
+        if (!hm.cos_tab || !hm.sin_tab) return refuse(why, "momenta tables: the handle has none");
+        const size_t tab = (size_t)m.n_dirs * (size_t)m.n_q;
+        const uint8_t *c = buf + e.cos_tab, *sn = buf + e.sin_tab;
+        for (size_t i = 0; i < tab; ++i)
+            if (get(c, 8) != bits_of(hm.cos_tab[i]))
+                return refuse(why, "momenta cos_tab: entry " + std::to_string(i) + " differs from the handle's");
+        for (size_t i = 0; i < tab; ++i)
+            if (get(sn, 8) != bits_of(hm.sin_tab[i]))
+                return refuse(why, "momenta sin_tab: entry " + std::to_string(i) + " differs from the handle's");
+        for (int k = 0; k < N_MOM; ++k) {
+            const Shape::Bin &b = m.bin[k];
+            if (b.T < 0 || b.T > (b.on ? b.cap : 0))
+                return refuse(why, std::string("binner ") + MOM_NAME[k] + " T: " + std::to_string(b.T) + " pushes outside 0 .. capacity");
+        }
+    }
+    if (blob) *blob = s;
+    if (mblob) *mblob = m;
     return 0;
 }
 

@@ -63,6 +63,39 @@ void write_header(const Shape &s, uint8_t *out);
 // state fields' ranges; n_bytes against the size the header implies.  0 and *blob filled, or -1 and *why set.
 int validate(const uint8_t *buf, size_t n_bytes, const Shape &handle, Shape *blob, std::string *why);
 
+// ---- format version 2: the version-1 header (version field 2) and payload, then an extension for the momentum binners,
+// which the 560-byte header has no room for.  A handle with no momentum binner enabled writes version 1 unchanged.
+//   i32 n_q, n_dirs   N_MOM x (i32 on, E, L, pad, i64 cap, T)   cos_tab, sin_tab [n_dirs n_q doubles each]
+//   xs, x2, c of every enabled momentum binner   u64 FNV-1a 64 of every extension byte in front of it
+enum { N_MOM = 3 };  // DQMC_BIN_MOMENTUM_CORRELATIONS, _SUSCEPTIBILITIES, _TIME_DISPLACED
+static const uint32_t VERSION_MOMENTA = 2;
+struct Momenta {
+    int32_t n_q = 0, n_dirs = 0;
+    const double *cos_tab = nullptr, *sin_tab = nullptr;  // n_dirs n_q doubles each, borrowed (nullptr in what validate_any hands back)
+    Shape::Bin bin[N_MOM] = {};
+    bool any() const { return bin[0].on || bin[1].on || bin[2].on; }  // false: the blob is version 1
+};
+// byte offsets from the start of the blob; with !m.any() only `start` and `total` are set, both to the version-1 size
+struct ExtLayout {
+    size_t start, cos_tab, sin_tab;
+    size_t bin_xs[N_MOM], bin_x2[N_MOM], bin_c[N_MOM];
+    size_t checksum, total;
+};
+bool ext_layout(const Shape &s, const Momenta &m, ExtLayout *out, std::string *why = nullptr);
+// write_header with the version the pair (s, m) calls for
+void write_header(const Shape &s, const Momenta &m, uint8_t *out);
+// the extension's fixed fields and tables into blob + e.start (nothing when !m.any())
+void write_ext(const Momenta &m, const ExtLayout &e, uint8_t *blob);
+// the checksum over blob[e.start, e.checksum), once the binner arrays are in place
+void seal_ext(const ExtLayout &e, uint8_t *blob);
+// validate for both versions.  Version 1: as validate, and refused when the handle has a momentum binner enabled.
+// Version 2: the header and payload as above, then the extension: n_bytes holds its fixed fields; its own shape is one a
+// handle can have; n_bytes against the size it implies; its checksum; n_q, n_dirs and every binner's on / E / L / cap
+// against `hm` (the first that differs is named); both tables byte for byte against hm's; the ranges of T.  0 and *blob /
+// *mblob filled (mblob's T are the state to restore), or -1 and *why set.
+int validate_any(const uint8_t *buf, size_t n_bytes, const Shape &handle, const Momenta &hm, Shape *blob, Momenta *mblob,
+                 std::string *why);
+
 // compress / decompress of one walker's field (HubbardModel.jl:56-59): element i of conf (+1 / -1) in bit i % 64 of chunk i / 64
 void pack_conf(const int8_t *conf, size_t n, uint8_t *chunks_le);
 void unpack_conf(const uint8_t *chunks_le, size_t n, int8_t *conf);

@@ -766,12 +766,15 @@ int dqmc_set_time_displaced(dqmc_handle *h, int32_t every, int32_t what)
         HIPCHK(hipStreamSynchronize(h->stream));
         if (h->td.every) h->red_valid = false;
         td_free(h);
+        mom_disable(h, DQMC_BIN_MOMENTUM_TIME_DISPLACED);
         return DQMC_OK;
     }
     if (!h->n_dirs) return fail(h, DQMC_ERR_STATE, "call dqmc_set_pair_directions first");
     if (every < 1 || h->M % every != 0) return fail(h, DQMC_ERR_INVALID, "every must be 0 or a positive divisor of slices");
     if (what < 1 || what > (DQMC_TD_GREENS | DQMC_TD_DENSITY))
         return fail(h, DQMC_ERR_INVALID, "what must be a non-empty mask of DQMC_TD_GREENS | DQMC_TD_DENSITY");
+    HIPCHK(hipStreamSynchronize(h->stream));
+    mom_disable(h, DQMC_BIN_MOMENTUM_TIME_DISPLACED);  // its rows follow the recording: the caller enables it again
     return td_setup(h, every, what);
 }
 int dqmc_time_displaced_size(dqmc_handle *h, size_t *n_doubles) { return sec_size(h, DQMC_RED_TIME_DISPLACED, n_doubles); }
@@ -819,8 +822,10 @@ int dqmc_accumulate_susceptibilities(dqmc_handle *h, int32_t recalculate)
     UTStack *u = h->ut;
     CHK(ut_sus_layout(h));
     CHK(binner_room(h, DQMC_BIN_SUSCEPTIBILITIES));
+    CHK(binner_room(h, DQMC_BIN_MOMENTUM_SUSCEPTIBILITIES));
     const bool record = h->td.every != 0;
     if (record) CHK(binner_room(h, DQMC_BIN_TIME_DISPLACED));
+    if (record) CHK(binner_room(h, DQMC_BIN_MOMENTUM_TIME_DISPLACED));
     const dqmc_handle::Section &sus = h->sec[DQMC_RED_SUSCEPTIBILITIES], &td = h->sec[DQMC_RED_TIME_DISPLACED];
     const long total = sus.bin_E;
     CHK(sign_begin(h, DQMC_RED_SUSCEPTIBILITIES, record ? DQMC_RED_TIME_DISPLACED : -1));
@@ -870,6 +875,8 @@ int dqmc_accumulate_susceptibilities(dqmc_handle *h, int32_t recalculate)
     }
     if (h->bin[DQMC_BIN_SUSCEPTIBILITIES].on) CHK(binner_push_section(h, DQMC_BIN_SUSCEPTIBILITIES));
     if (record && h->bin[DQMC_BIN_TIME_DISPLACED].on) CHK(binner_push_section(h, DQMC_BIN_TIME_DISPLACED));
+    if (h->bin[DQMC_BIN_MOMENTUM_SUSCEPTIBILITIES].on) CHK(mom_push(h, DQMC_BIN_MOMENTUM_SUSCEPTIBILITIES));
+    if (record && h->bin[DQMC_BIN_MOMENTUM_TIME_DISPLACED].on) CHK(mom_push(h, DQMC_BIN_MOMENTUM_TIME_DISPLACED));
     return dqmc_synchronize(h);
 }
 int dqmc_susceptibilities_size(dqmc_handle *h, size_t *n)

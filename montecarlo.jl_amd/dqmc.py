@@ -12,6 +12,7 @@ import numpy as np
 
 from . import _lib, checkpoint as _ckpt
 from ._lib import check, dptr, i64ptr, lib
+from .lattices import _lattice_vectors as _lat_vectors
 from .configurations import CompressedConf, ConfigRecorder
 from .models import rand_conf
 
@@ -244,6 +245,7 @@ class DQMC:
                           checkerboard=checkerboard if isinstance(checkerboard, str) else bool(checkerboard),
                           global_kind=global_kind)
         self._tables, self._td_args, self._bin_caps, self._user_bin = {}, None, {}, None
+        self._dirs, self._mom = None, None  # the directions of set_pair_directions' iterator; (q, cos table, sin table) of set_momenta
         self._gm_set = None       # (rate, kind) of the last set_global_rate
         self._sus_layout = False  # the susceptibility section is laid out (by its first use)
         self._mid_sweep = False  # set by load(): run() finishes the sweep the checkpoint was taken in
@@ -467,6 +469,9 @@ class DQMC:
             self.prepare()
         if binning:  # a resumed run! keeps the binners it has (DQMC.jl:395-411)
             self.enable_binning([m for m in measurements if not self._binning_enabled(m)])
+            if self._mom is not None:  # and, with momenta set, the momentum binner of every section that has one
+                self.enable_binning([k for k in ("momentum_" + m for m in measurements)
+                                     if k in _lib.BIN_MOMENTUM and not self._binning_enabled(k)])
         if self.last_sweep == 0:  # a resumed run! keeps the measurement state (DQMC.jl:395-411)
             self.reset_accumulators()
         total = self.p.thermalization + self.p.sweeps
@@ -548,6 +553,10 @@ class DQMC:
                          global_rate=p.global_rate, sign_weighting=self.sign_weighting()),
             "tables": tables,
             "time_displaced": list(self._td_args) if self._td_args else None,
+            # the wave vectors and both phase tables of set_momenta (the tables as handed to the engine, d fastest); the
+            # momentum binners that are on stand among the sections of "binning"
+            "momenta": None if self._mom is None else {"q": self._mom[0].tolist(), "cos": self._mom[1].tolist(),
+                                                       "sin": self._mom[2].tolist()},
             "binning": {"sections": dict(self._bin_caps), "user": list(self._user_bin) if self._user_bin else None},
             "global": list(self._gm_set) if self._gm_set else None,  # the last set_global_rate: (rate, DQMC_GLOBAL_* kind)
             "susceptibilities_layout": bool(self._sus_layout),
@@ -601,6 +610,10 @@ class DQMC:
                 mc.set_time_displaced(*pre["time_displaced"])
             if pre["global"]:
                 mc.set_global_rate(*pre["global"])
+            if pre.get("momenta"):
+                mo = pre["momenta"]
+                mc._set_momenta(np.array(mo["q"], dtype=np.float64), np.array(mo["cos"], dtype=np.float64),
+                                np.array(mo["sin"], dtype=np.float64))
             mc.prepare()  # (the susceptibility layout and two of the binners need a prepared handle)
             if pre["susceptibilities_layout"]:
                 mc._section_size("susceptibilities")
@@ -907,6 +920,8 @@ class DQMC:
     def _bin(which):
         if which == "time_displaced":  # DQMC_BIN_TIME_DISPLACED, an enum of its own
             return _lib.BIN_TIME_DISPLACED
+        if which in _lib.BIN_MOMENTUM:
+            return _lib.BIN_MOMENTUM[which]
         if which not in _lib.BIN_SECTIONS:
             raise ValueError("unknown binner section %r" % (which,))
         return _lib.BIN_SECTIONS.index(which)
@@ -1005,6 +1020,21 @@ class DQMC:
                 sizes += [(k, B * p["rows"] * nd, (B, p["rows"], nd)) for k in ("Gl0", "G0l")]
             if p["what"] & _lib.TD_DENSITY:
                 sizes += [(k, p["rows"] * nd, (p["rows"], nd)) for k in ("CDC", "SDCx", "SDCy", "SDCz")]
+        elif which in _lib.BIN_MOMENTUM:  # q fastest: C order
+            nq = 0 if self._mom is None else self._mom[0].shape[0]
+            if which == "momentum_correlations":
+                sizes = [(k, nq, None) for k in ("Sc", "Sx", "Sy", "Sz")]
+            elif which == "momentum_susceptibilities":
+                sizes = [(k, nq, None) for k in ("chi_c", "chi_x", "chi_y", "chi_z")]
+            else:
+                p = self.time_displaced_plan()
+                sizes = []
+                if p["what"] & _lib.TD_GREENS:
+                    sizes += [(k, B * p["rows"] * nq, (B, p["rows"], nq)) for k in ("Gl0_C", "Gl0_S", "G0l_C", "G0l_S")]
+                if p["what"] & _lib.TD_DENSITY:
+                    sizes += [(k, p["rows"] * nq, (p["rows"], nq)) for k in ("CDCk", "SDCxk", "SDCyk", "SDCzk")]
+            if self.sign_weighting():
+                sizes.append(("s", 1, None))
         else:
             sizes = [("x", self.binner_size("user")[0], None)]
         out, off = [], 0
@@ -1022,7 +1052,7 @@ class DQMC:
                 v = self._blocks(v)
             elif name == "occupation":
                 v = [v[b * n:(b + 1) * n] for b in range(B)]
-            elif which == "time_displaced":
+            elif which in ("time_displaced", "momentum_time_displaced"):
                 v = v.reshape(shape)
             elif shape is not None:
                 v = v.reshape(shape, order="F")
@@ -1043,6 +1073,8 @@ class DQMC:
         -> PC[dir12, dir1, dir2]; susceptibilities -> CDS, SDSx, SDSy, SDSz, PS, CCS; user -> x.  Every field X comes with
         X_std_error (binning error at `level`, default the reliable level), X_std_error_walkers (the cross-walker
         error, independent of the binning) and X_tau; plus count (samples per walker) and reliable_level."""
+        if which in _lib.BIN_MOMENTUM:
+            return self._binned_momentum(which, level)
         raw = self.binned_raw(which, level)
         res = self._bin_dict(which, raw)
         if which == "time_displaced":
@@ -1078,11 +1110,14 @@ class DQMC:
     def set_pair_directions(self, iterator):
         """hand the EachSitePairByDistance table of the lattice to the device"""
         self._set_pair_directions(iterator.dir_of, iterator.ndirections())
+        self._dirs = np.array(iterator.directions, dtype=np.float64)  # r_d of every direction: set_momenta's tables
 
     def _set_pair_directions(self, dir_of, n_dirs):
         tab = np.asfortranarray(np.asarray(dir_of).astype(np.int32))  # [src, trg] -> dir_of[src + n*trg]
         self._ndirs = int(n_dirs)
         self._c(lib().dqmc_set_pair_directions(self._h, tab.ctypes.data_as(C.POINTER(C.c_int32)), self._ndirs))
+        self._dirs = None
+        self._momenta_dropped()  # (the engine turns momenta off with the old directions)
         self._tables["pair_directions"] = (np.array(tab, dtype=np.int32), self._ndirs)
 
     def accumulate_correlations(self):
@@ -1215,6 +1250,7 @@ class DQMC:
             what = sum(bits[k] for k in set(what))
         self._c(lib().dqmc_set_time_displaced(self._h, int(every), int(what)))
         self._td_args = (int(every), int(what)) if int(every) else None
+        self._binner_dropped("momentum_time_displaced")  # (the engine disables it: enable it again)
 
     def time_displaced_plan(self):
         """-> dict(rows, every, what, fast): fast = the Green's rows take the one-lane-per-direction kernel (all zero
@@ -1243,6 +1279,153 @@ class DQMC:
         for name, v in self._bin_shape("time_displaced", raw[:-1]).items():
             res[name] = v / cnt
         res["count"] = cnt
+        return res
+
+    # ---- momentum-space observables (include/dqmc_hip.h): S(q), chi(q), G(k, tau), n(k)
+    def _binner_dropped(self, which):
+        self._binned = getattr(self, "_binned", set()) - {which}
+        self._bin_caps.pop(which, None)
+
+    def _momenta_dropped(self):
+        self._mom = None
+        for k in _lib.BIN_MOMENTUM:
+            self._binner_dropped(k)
+
+    def set_momenta(self, qs="all", iterator=None):
+        """the wave vectors of the momentum-space observables: "all" (momentum_grid of the lattice), integer labels
+        [n_q, dim] into that grid (an integer array or tuples: (L/2, L/2) is (pi, pi) on a square lattice), or cartesian
+        vectors [n_q, dim] (a float array); None or an empty list turns them off.  The phase tables C[d, q] = cos(q . r_d),
+        S[d, q] = sin(q . r_d) are built from the `directions` of the iterator given to set_pair_directions (on the
+        _set_pair_directions path, which has none, pass the iterator here).  Means need nothing more:
+        structure_factors(), static_susceptibilities(), momentum_time_displaced(); error bars come from the momentum
+        binners: enable_binning(("momentum_correlations", ...)), binned(...).  Disables the momentum binners."""
+        from .lattices import momentum_grid
+        if iterator is not None:
+            self._dirs = np.array(iterator.directions, dtype=np.float64)
+        if qs is None or (not isinstance(qs, str) and len(qs) == 0):
+            self._c(lib().dqmc_set_momenta(self._h, 0, None, None))
+            self._momenta_dropped()
+            return
+        if self._dirs is None:
+            raise _lib.DQMCError(_lib.ERR_STATE, "set_momenta: call set_pair_directions(iterator) first, or pass the iterator")
+        if self._dirs.shape[0] != getattr(self, "_ndirs", 0):
+            raise ValueError("set_momenta: the iterator has %d directions, the engine's table %d"
+                             % (self._dirs.shape[0], getattr(self, "_ndirs", 0)))
+        dim = self._dirs.shape[1]
+        if isinstance(qs, str):
+            if qs != "all":
+                raise ValueError("qs must be 'all', integer labels or cartesian vectors")
+            q = momentum_grid(self.model.l)[0]
+        else:
+            a = np.asarray(qs)
+            if a.ndim == 1:
+                a = a.reshape(1, -1)
+            if a.ndim != 2 or a.shape[1] != dim:
+                raise ValueError("qs must have shape [n_q, %d]" % dim)
+            if np.issubdtype(a.dtype, np.integer):
+                A = np.array(_lat_vectors(self.model.l), dtype=np.float64)
+                q = a.astype(np.float64) @ (2.0 * np.pi * np.linalg.inv(A).T)
+            else:
+                q = a.astype(np.float64)
+        phase = self._dirs @ q.T  # [n_dirs, n_q]
+        self._set_momenta(q, np.cos(phase).reshape(-1, order="F"), np.sin(phase).reshape(-1, order="F"))
+
+    def _set_momenta(self, q, cos_tab, sin_tab):
+        """the engine call: tables [n_dirs x n_q] flat, d fastest"""
+        q = np.ascontiguousarray(q, dtype=np.float64)
+        cos_tab, sin_tab = np.ascontiguousarray(cos_tab, dtype=np.float64), np.ascontiguousarray(sin_tab, dtype=np.float64)
+        nd = getattr(self, "_ndirs", 0)
+        if cos_tab.size != nd * q.shape[0] or sin_tab.size != cos_tab.size:
+            raise ValueError("the phase tables must hold n_dirs x n_q = %d x %d entries" % (nd, q.shape[0]))
+        self._c(lib().dqmc_set_momenta(self._h, q.shape[0], dptr(cos_tab), dptr(sin_tab)))
+        self._momenta_dropped()
+        self._mom = (q, cos_tab, sin_tab)
+
+    def momenta(self):
+        """-> the wave vectors [n_q, dim] of set_momenta (cartesian), or None"""
+        return None if self._mom is None else self._mom[0].copy()
+
+    def momenta_plan(self):
+        """-> dict(n_q, n_dirs, tile_rows, tile_cols) of the engine, all zero when momenta are off"""
+        out = (C.c_int32 * 4)()
+        self._c(lib().dqmc_momenta_plan(self._h, out))
+        return dict(zip(("n_q", "n_dirs", "tile_rows", "tile_cols"), (int(v) for v in out)))
+
+    def _phase_tables(self):
+        if self._mom is None:
+            raise _lib.DQMCError(_lib.ERR_STATE, "call set_momenta first")
+        q, c, s = self._mom
+        return c.reshape((self._ndirs, q.shape[0]), order="F"), s.reshape((self._ndirs, q.shape[0]), order="F")
+
+    def _means(self, which):
+        return self.signed(which) if self.sign_weighting() else getattr(self, which)()
+
+    def structure_factors(self):
+        """-> dict(Sc, Sx, Sy, Sz [n_q], count): sum_d cos(q . r_d) X[d] of the means CDC, SDCx, SDCy, SDCz - a host
+        transform of the accumulated sums (of signed("correlations") with sign weighting on)"""
+        Ct, _ = self._phase_tables()
+        m = self._means("correlations")
+        res = {k: m[src] @ Ct for k, src in (("Sc", "CDC"), ("Sx", "SDCx"), ("Sy", "SDCy"), ("Sz", "SDCz"))}
+        res["count"] = m["count"]
+        return res
+
+    def static_susceptibilities(self):
+        """-> dict(chi_c, chi_x, chi_y, chi_z [n_q], count): the same transform of the means CDS, SDSx, SDSy, SDSz"""
+        Ct, _ = self._phase_tables()
+        m = self._means("susceptibilities")
+        res = {k: m[src] @ Ct for k, src in (("chi_c", "CDS"), ("chi_x", "SDSx"), ("chi_y", "SDSy"), ("chi_z", "SDSz"))}
+        res["count"] = m["count"]
+        return res
+
+    def momentum_time_displaced(self):
+        """-> dict of the transforms of time_displaced(): Gk_l0, Gk_0l (complex [n_blocks, R, n_q]: sum_d e^{-i q . r_d}
+        X[d]) and nk = 1 - Re Gk_l0[:, 0, :] if the Green's rows are recorded, CDCk, SDCxk, SDCyk, SDCzk [R, n_q] (cosine
+        part) if the density rows are; tau, count"""
+        Ct, St = self._phase_tables()
+        m = self._means("time_displaced")
+        res = {"tau": m["tau"], "count": m["count"]}
+        for k, src in (("Gk_l0", "Gl0"), ("Gk_0l", "G0l")):
+            if src in m:
+                res[k] = m[src] @ Ct - 1j * (m[src] @ St)
+        if "Gk_l0" in res:
+            res["nk"] = 1.0 - res["Gk_l0"][:, 0, :].real
+        for src in ("CDC", "SDCx", "SDCy", "SDCz"):
+            if src in m:
+                res[src + "k"] = m[src] @ Ct
+        return res
+
+    def _binned_momentum(self, which, level=None):
+        """binned() of a momentum binner: the keys of structure_factors() / static_susceptibilities() /
+        momentum_time_displaced(), each X with X_std_error, X_std_error_walkers and X_tau; for the complex Gk_l0, Gk_0l the
+        errors and tau of the real and the imaginary part apart (X_std_error_re, X_std_error_im, ...).  With sign weighting
+        on X is <s X> / <s>, X_std_error and X_std_error_walkers both the jackknife of that ratio over the walkers
+        (jackknife_ratio, from level 0 of the sample and of its trailing s: at least two walkers), X_tau that of s X."""
+        raw = self.binned_raw(which, level)
+        if self.sign_weighting():
+            E = self.binner_size(which)[0]
+            lv0 = np.stack([self.binner_level(which, w, 0)[0] for w in range(self.n_walkers)])
+            val, err = jackknife_ratio(lv0[:, :E - 1], lv0[:, E - 1])
+            pad = lambda v: np.concatenate([v, [np.nan]])
+            raw = dict(raw, mean=pad(val), std_error=pad(err), std_error_walkers=pad(err))
+        d = self._bin_dict(which, raw)
+        for k in [k for k in d if k == "s" or k.startswith("s_")]:
+            del d[k]
+        sfx = ("", "_std_error", "_std_error_walkers", "_tau")
+        res = {}
+        if which == "momentum_time_displaced":
+            for k, src in (("Gk_l0", "Gl0"), ("Gk_0l", "G0l")):
+                if src + "_C" in d:
+                    res[k] = d.pop(src + "_C") - 1j * d.pop(src + "_S")
+                    for x in sfx[1:]:
+                        res[k + x + "_re"], res[k + x + "_im"] = d.pop(src + "_C" + x), d.pop(src + "_S" + x)
+            if "Gk_l0" in res:
+                res["nk"] = 1.0 - res["Gk_l0"][:, 0, :].real
+                for x in sfx[1:]:
+                    res["nk" + x] = res["Gk_l0" + x + "_re"][:, 0, :]
+            res["tau"] = self._td_tau()
+        res.update(d)
+        res["count"] = raw["count"]
+        res["reliable_level"] = raw["reliable_level"]
         return res
 
     # ---- current_current_susceptibility (measurements.jl:257-317) over EachLocalQuadBySyncedDistance{K}

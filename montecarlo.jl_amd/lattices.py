@@ -155,6 +155,23 @@ def _lattice_vectors(l):
     return [np.array([float(l.sites)])]
 
 
+def momentum_grid(l):
+    """-> (q [N, dim], labels [N, dim]): the N wave vectors a periodic lattice of N sites allows, cartesian, and their
+    integer labels.  With A_i = _lattice_vectors(l), the vectors the lattice is periodic under, the reciprocal basis is
+    G_j with A_i . G_j = 2 pi delta_ij, and q = sum_j m_j G_j, m_j = 0 .. L_j - 1 (L_j the number of sites along A_j);
+    the first label runs fastest.  Chain, SquareLattice, CubicLattice (D = 3) and TriangularLattice."""
+    A = np.array(_lattice_vectors(l), dtype=np.float64)  # rows A_i
+    if isinstance(l, TriangularLattice):
+        counts = (l.Lx, l.Ly)
+    elif isinstance(l, (SquareLattice, CubicLattice)):
+        counts = (l.L,) * A.shape[0]
+    else:
+        counts = (l.sites,)
+    G = 2.0 * np.pi * np.linalg.inv(A).T  # rows G_j
+    labels = np.array([m[::-1] for m in np.ndindex(*counts[::-1])], dtype=np.int64).reshape(-1, len(counts))
+    return labels.astype(np.float64) @ G, labels
+
+
 def generate_combinations(vs):
     """lattice_iterators.jl:137-143: all periodic images, in the reference's order"""
     out = [np.zeros(len(vs[0]))]
