@@ -538,6 +538,54 @@ enum { DQMC_RED_SIGN = 5 };
 int dqmc_get_reduced(dqmc_handle *h, int32_t which, double *host_out);
 int dqmc_get_reduced_stats(dqmc_handle *h, dqmc_stats *out);
 
+/* ---- thermodynamics ---------------------------------------------------------------------------------------------------
+ * Energy, filling, double occupancy, local moment and the fluctuations behind the compressibility and the uniform spin
+ * susceptibility, as ten scalars per sample.  The reference has no such measurement: its `occupation` is the per-site
+ * vector of the Green's section, and <n_up n_dn>, <N^2>, <Mz^2> are products of Green's elements inside one sample, which
+ * the mean G does not give.  Off by default; a handle that never calls dqmc_set_thermodynamics launches, packs and saves
+ * exactly what it did before this section existed.
+ * Notation: G_s the true equal-time Green's function of block s for one walker's field (dqmc_get_greens; G_ij =
+ * <c_i c+_j>), for the attractive model (one block) G_up = G_dn = G and spin sums count the block twice; T_s the hopping
+ * matrix of block s (mc.s.hopping_matrix, -mu on its diagonal); N = n_sites; n_s,i = 1 - G_s,ii; U_s = +U for the
+ * repulsive model, -U for the attractive one: the interaction is U_s sum_i (n_up,i - 1/2)(n_dn,i - 1/2).
+ *   0 n_up   (1/N) sum_i n_up,i                      1 n_dn   (1/N) sum_i n_dn,i
+ *   2 n      n_up + n_dn                             3 D      (1/N) sum_i n_up,i n_dn,i
+ *   4 m2     n - 2 D  (the local moment <(n_up - n_dn)^2>)
+ *   5 E_kin  (1/N) sum_s sum_{i != j} T_s,ij (-G_s,ji)
+ *   6 E_int  U_s (D - n/2 + 1/4)
+ *   7 E      (1/N) sum_s sum_ij T_s,ij (delta_ij - G_s,ji) + E_int     (the -mu n term is in)
+ *   8 N2     (1/N) [ (sum_s sum_i n_s,i)^2 + sum_s sum_ij (delta_ij - G_s,ji) G_s,ij ]  = <N^2> / N
+ *   9 Mz2    (1/N) [ (sum_i (n_up,i - n_dn,i))^2 + sum_s sum_ij (delta_ij - G_s,ji) G_s,ij ]  = <(sum_i n_up,i - n_dn,i)^2> / N
+ * 8 and 9 use the Wick contraction of cdc_kernel / sdc_z_kernel (measurements.jl:60-74, 180-186) summed over all pairs.
+ * The linear combinations 2, 4, 6, 7 are elements of their own so that a binner gives their error bars without a
+ * covariance.  The host derives kappa = beta (<N2> - N <n>^2) and chi_s = beta <Mz2> / 4.
+ * The section DQMC_RED_THERMODYNAMICS: [10 sums][sum of s][sample count], DQMC_THERMO_ELEMENTS + 2 doubles.  It carries
+ * its own sum of signs, so the DQMC_RED_SIGN section keeps its five entries; the sum of s equals the count while sign
+ * weighting is off, and with it on the ten sums are sums of s_w x_w, a walker whose sign is 0 is left out of all twelve
+ * and counted in dqmc_get_sign_failures.  dqmc_reset_accumulators zeroes it, dqmc_set_sign_weighting refuses while it
+ * holds samples, and dqmc_reduce packs it behind the sums of signs (dqmc_get_reduced(DQMC_RED_THERMODYNAMICS)).
+ * The binner DQMC_BIN_THERMODYNAMICS (dqmc_binner_enable, after dqmc_set_thermodynamics): E = 10, or with sign weighting
+ * on E = 11, the sample being [s_w x_w][s_w] as for the momentum binners, so that the jackknife of <x s> / <s> has its
+ * denominator in the same binner; there is no DQMC_BIN_SIGN + k for it.  Switching sign weighting makes it again, empty,
+ * with its capacity.
+ * A walker's sample is summed in a fixed order without atomics: the same bits in every run and for any n_walkers.
+ * Checkpoint: see "checkpoint and resume", format versions 3 and 4. */
+enum { DQMC_RED_THERMODYNAMICS = 6 };
+enum { DQMC_BIN_THERMODYNAMICS = 14 };  /* = DQMC_BIN_MOMENTUM_END: behind the momentum binners */
+enum { DQMC_THERMO_ELEMENTS = 10 };
+/* The reference has no such measurement.  T: mc.s.hopping_matrix as dqmc_set_current_targets takes it, n_blocks matrices
+ * n x n, column-major; the engine keeps it as a per-row neighbour list.  NULL turns the section off again: its sums and
+ * its binner go.  DQMC_ERR_INVALID for a non-finite entry or a row with more than 64 off-diagonal non-zeros, and the
+ * handle keeps its setting.  A call with a matrix empties the section and drops its binner. */
+int dqmc_set_thermodynamics(dqmc_handle *h, const double *T);
+/* The reference has no such measurement.  One sample per walker from the true G of the current fields, at the place
+ * dqmc_accumulate_greens is called.  DQMC_ERR_STATE before dqmc_prepare or dqmc_set_thermodynamics. */
+int dqmc_accumulate_thermodynamics(dqmc_handle *h);
+/* size / host copy / device copy of the section, as for the other sections (0 doubles while it is off) */
+int dqmc_thermodynamics_size(dqmc_handle *h, size_t *n_doubles);
+int dqmc_get_thermodynamics(dqmc_handle *h, double *host_out);
+int dqmc_export_thermodynamics(dqmc_handle *h, void *device_out);
+
 /* ---- checkpoint and resume ---------------------------------------------------------------------------------------
  * save / load / resume! (FileIO.jl:38-156, DQMC.jl:463-477, 797-924) for the state that lives on the device.  Like the
  * global moves this is a defined extension of the ABI: the reference writes a JLD file from host objects; here the engine
@@ -577,7 +625,17 @@ int dqmc_get_reduced_stats(dqmc_handle *h, dqmc_stats *out);
  * dqmc_state_import takes both versions.  The extension is validated like the header, before the first write: its size,
  * its checksum (which covers the binner arrays too), then n_q, n_dirs and the binner shapes against the importing
  * handle's, then the tables byte for byte against the handle's own; a version-1 blob is refused by a handle with a
- * momentum binner enabled. */
+ * momentum binner enabled.
+ * Format versions 3 and 4: a handle with the thermodynamics section configured (dqmc_set_thermodynamics) writes the
+ * version-1 blob with version field 3, or the version-2 blob with version field 4, followed by one more extension; a
+ * handle without the section writes version 1 or 2 unchanged, byte for byte.
+ *   thermodynamics extension
+ *     u64 n (12), n_red     1 binner (DQMC_BIN_THERMODYNAMICS): i32 on, E, L, pad   i64 capacity, T
+ *     u64 FNV-1a 64 of the bytes of the hopping matrix handed to dqmc_set_thermodynamics     f64 U_s
+ *     the section's n doubles     x_sum, x2_sum, compressor of the binner if enabled
+ *     u64 FNV-1a 64 of all bytes of this extension in front of it
+ * It is validated like the others before the first write; a version 3 / 4 blob is refused by a handle without the
+ * section and a version 1 / 2 blob by a handle with it, the field named ("section thermodynamics n"). */
 /* bytes of the blob of this handle as it is configured now */
 int dqmc_state_size(dqmc_handle *h, size_t *n_bytes);
 /* The blob into host_out (n_bytes = dqmc_state_size).  Only at the measurement point, current_slice == 1 && direction ==

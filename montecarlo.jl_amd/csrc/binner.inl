@@ -5,7 +5,7 @@
 static const int64_t BIN_DEFAULT_CAPACITY = 100000;  // BinningAnalysis' _default_capacity
 
 #define BIN_OK(h, which)                                                                        \
-    if ((which) < DQMC_BIN_GREENS || (which) >= DQMC_BIN_MOMENTUM_END)                          \
+    if ((which) < DQMC_BIN_GREENS || (which) > DQMC_BIN_THERMODYNAMICS)                         \
         return fail((h), DQMC_ERR_INVALID, "binner section out of range");                      \
     if (!(h)->bin[(which)].on) return fail((h), DQMC_ERR_STATE, "this section's binner is not enabled")
 
@@ -18,8 +18,8 @@ static const dqmc_handle::Section &binner_section(dqmc_handle *h, int which)
 // elements of a section as its measurement is configured now (0: not configured)
 static long binner_section_elements(dqmc_handle *h, int which)
 {
-    // (the user binner, the sign binners and the momentum binners have no accumulator section: a change of what they depend
-    // on frees or re-creates them where it is made)
+    // (the user binner, the sign binners and the momentum binners have no accumulator section, and the thermodynamics
+    // binner's length follows sign weighting: a change of what they depend on frees or re-creates them where it is made)
     return which == DQMC_BIN_USER || which >= DQMC_BIN_SIGN ? h->bin[which].E : binner_section(h, which).bin_E;
 }
 // the binner of the signs that go with a measurement section's pushes: DQMC_BIN_SIGN + the section's DQMC_RED_* index
@@ -134,10 +134,12 @@ static int binner_finish_device(dqmc_handle *h, int which, int32_t level)
 }
 
 static int mom_enable(dqmc_handle *h, int which, int64_t capacity);  // momentum.inl
+static int thermo_enable(dqmc_handle *h, int64_t capacity);          // thermo.inl
 int dqmc_binner_enable(dqmc_handle *h, int32_t which, int64_t capacity)
 {
     ENTER(h);
     if (which >= DQMC_BIN_MOMENTUM_CORRELATIONS && which < DQMC_BIN_MOMENTUM_END) return mom_enable(h, which, capacity);
+    if (which == DQMC_BIN_THERMODYNAMICS) return thermo_enable(h, capacity);
     if (which < DQMC_BIN_GREENS || which == DQMC_BIN_USER || which > DQMC_BIN_TIME_DISPLACED)
         return fail(h, DQMC_ERR_INVALID, "dqmc_binner_enable takes a measurement section (dqmc_binner_user_create makes the user "
                                          "binner, the sign binners come with their sections)");

@@ -43,6 +43,18 @@ static void state_momenta(const dqmc_handle *h, dqmc_blob::Momenta *m)
     m->cos_tab = h->mom.cos_h.data(); m->sin_tab = h->mom.sin_h.data();
 }
 
+// the thermodynamics section and its binner: what the extension of a version-3 / 4 blob carries.  With the section off it
+// is empty (t->any() false) and the blob is version 1 / 2.
+static void state_thermo(const dqmc_handle *h, dqmc_blob::Thermo *t)
+{
+    *t = dqmc_blob::Thermo{};
+    if (!h->th.on) return;
+    t->n = h->sec[DQMC_RED_THERMODYNAMICS].n; t->n_red = h->sec[DQMC_RED_THERMODYNAMICS].n_red;
+    const dqmc_handle::Binner &b = h->bin[DQMC_BIN_THERMODYNAMICS];
+    if (b.on) t->bin = {1, b.E, b.L, b.cap, b.T};
+    t->T_hash = h->th.T_hash; t->U_s = h->th.U_s;
+}
+
 // The state dqmc_update_until_measure returns in (and dqmc_sweep when it started there), rebuilt from the HS field alone: dqmc_prepare's init_stack,
 // build_stack and propagate, then the propagates of a down pass with no sweep_spatial in between, which leave the stack
 // slots and mc.s.greens as a down pass that accepted nothing leaves them, at current_slice == 1, direction == +1.
@@ -63,11 +75,13 @@ int dqmc_state_size(dqmc_handle *h, size_t *n_bytes)
     if (!h || !n_bytes) return DQMC_ERR_INVALID;
     dqmc_blob::Shape s;
     dqmc_blob::Momenta m;
-    dqmc_blob::ExtLayout e;
+    dqmc_blob::Thermo th;
+    dqmc_blob::ThermoLayout tl;
     state_shape(h, &s);
     state_momenta(h, &m);
-    if (!dqmc_blob::ext_layout(s, m, &e)) return fail(h, DQMC_ERR_INVALID, "dqmc_state_size: the state does not fit a size_t");
-    *n_bytes = e.total;
+    state_thermo(h, &th);
+    if (!dqmc_blob::thermo_layout(s, m, th, &tl)) return fail(h, DQMC_ERR_INVALID, "dqmc_state_size: the state does not fit a size_t");
+    *n_bytes = tl.total;
     return DQMC_OK;
 }
 
@@ -83,13 +97,16 @@ int dqmc_state_export(dqmc_handle *h, void *host_out, size_t n_bytes)
     dqmc_blob::Layout l;
     dqmc_blob::Momenta m;
     dqmc_blob::ExtLayout e;
+    dqmc_blob::Thermo th;
+    dqmc_blob::ThermoLayout tl;
     state_shape(h, &s);
     state_momenta(h, &m);
-    if (!dqmc_blob::layout(s, &l) || !dqmc_blob::ext_layout(s, m, &e))
+    state_thermo(h, &th);
+    if (!dqmc_blob::layout(s, &l) || !dqmc_blob::ext_layout(s, m, &e) || !dqmc_blob::thermo_layout(s, m, th, &tl))
         return fail(h, DQMC_ERR_INVALID, "dqmc_state_export: the state does not fit a size_t");
-    if (n_bytes != e.total)
+    if (n_bytes != tl.total)
         return fail(h, DQMC_ERR_INVALID, "dqmc_state_export: n_bytes is " + std::to_string(n_bytes) + ", dqmc_state_size reports " +
-                                             std::to_string(e.total));
+                                             std::to_string(tl.total));
     HIPCHK(hipStreamSynchronize(h->stream));
     std::vector<WalkerRng> rg(h->W);
     HIPCHK(hipMemcpy(rg.data(), h->rng, sizeof(WalkerRng) * h->W, hipMemcpyDeviceToHost));
@@ -98,7 +115,7 @@ int dqmc_state_export(dqmc_handle *h, void *host_out, size_t n_bytes)
             return fail(h, DQMC_ERR_STATE, "dqmc_state_export: walker " + std::to_string(w) + " runs on a host-supplied uniform "
                                            "stream (dqmc_set_uniforms), which the blob does not carry");
     uint8_t *out = (uint8_t *)host_out;
-    dqmc_blob::write_header(s, m, out);
+    dqmc_blob::write_header(s, m, th, out);
     {   // only copies from here on: nothing is launched, no buffer of the handle is written
         const size_t sz = (size_t)h->N * h->M, chunk_bytes = dqmc_blob::conf_chunks(h->N, h->M) * 8;
         std::vector<int8_t> conf((size_t)h->W * sz);
@@ -134,6 +151,19 @@ int dqmc_state_export(dqmc_handle *h, void *host_out, size_t n_bytes)
         }
         dqmc_blob::seal_ext(e, out);
     }
+    if (th.any()) {  // format versions 3 / 4: the thermodynamics extension
+        dqmc_blob::write_thermo(th, tl, out);
+        const dqmc_handle::Section &sc = h->sec[DQMC_RED_THERMODYNAMICS];
+        HIPCHK(hipMemcpy(out + tl.sec, sc.acc, sc.n * sizeof(double), hipMemcpyDeviceToHost));
+        const dqmc_handle::Binner &b = h->bin[DQMC_BIN_THERMODYNAMICS];
+        if (b.on) {
+            const size_t we = (size_t)h->W * (size_t)b.E * sizeof(double);
+            HIPCHK(hipMemcpy(out + tl.bin_xs, b.xs, b.L * we, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(out + tl.bin_x2, b.x2, b.L * we, hipMemcpyDeviceToHost));
+            if (b.L > 1) HIPCHK(hipMemcpy(out + tl.bin_c, b.c, (b.L - 1) * we, hipMemcpyDeviceToHost));
+        }
+        dqmc_blob::seal_thermo(tl, out);
+    }
     return DQMC_OK;
 }
 
@@ -144,11 +174,14 @@ int dqmc_state_import(dqmc_handle *h, const void *host_in, size_t n_bytes)
     dqmc_blob::Momenta mine_m, m;
     dqmc_blob::Layout l;
     dqmc_blob::ExtLayout e;
+    dqmc_blob::Thermo mine_t, th;
+    dqmc_blob::ThermoLayout tl;
     std::string why;
     state_shape(h, &mine);
     state_momenta(h, &mine_m);
-    if (dqmc_blob::validate_any((const uint8_t *)host_in, n_bytes, mine, mine_m, &s, &m, &why) != 0 || !dqmc_blob::layout(s, &l, &why) ||
-        !dqmc_blob::ext_layout(s, m, &e, &why))
+    state_thermo(h, &mine_t);
+    if (dqmc_blob::validate_all((const uint8_t *)host_in, n_bytes, mine, mine_m, mine_t, &s, &m, &th, &why) != 0 ||
+        !dqmc_blob::layout(s, &l, &why) || !dqmc_blob::ext_layout(s, m, &e, &why) || !dqmc_blob::thermo_layout(s, m, th, &tl, &why))
         return fail(h, DQMC_ERR_INVALID, "dqmc_state_import: " + why);
     const uint8_t *in = (const uint8_t *)host_in;
     // the one index the payload carries: the site of a walker's latest global move (the next proposal overwrites it before
@@ -203,6 +236,18 @@ int dqmc_state_import(dqmc_handle *h, const void *host_in, size_t n_bytes)
         HIPCHK(hipMemcpy(b.x2, in + e.bin_x2[k], b.L * we, hipMemcpyHostToDevice));
         if (b.L > 1) HIPCHK(hipMemcpy(b.c, in + e.bin_c[k], (b.L - 1) * we, hipMemcpyHostToDevice));
         b.T = m.bin[k].T;
+    }
+    if (th.any()) {  // (format versions 3 / 4; validate_all has made sure the handle has the section, shaped the same)
+        const dqmc_handle::Section &sc = h->sec[DQMC_RED_THERMODYNAMICS];
+        HIPCHK(hipMemcpy(sc.acc, in + tl.sec, sc.n * sizeof(double), hipMemcpyHostToDevice));
+        dqmc_handle::Binner &b = h->bin[DQMC_BIN_THERMODYNAMICS];
+        if (b.on) {
+            const size_t we = (size_t)h->W * (size_t)b.E * sizeof(double);
+            HIPCHK(hipMemcpy(b.xs, in + tl.bin_xs, b.L * we, hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(b.x2, in + tl.bin_x2, b.L * we, hipMemcpyHostToDevice));
+            if (b.L > 1) HIPCHK(hipMemcpy(b.c, in + tl.bin_c, (b.L - 1) * we, hipMemcpyHostToDevice));
+            b.T = th.bin.T;
+        }
     }
     h->gm_updates = s.gm_updates;
     return dqmc_synchronize(h);

@@ -105,7 +105,10 @@ struct dqmc_handle {
         long bin_E = 0;
         int bin_mode = BIN_SRC_PLAIN;
     //   sign             [sum of s per DQMC_RED_* section above], no count; packed only while sign weighting is on
-    } sec[DQMC_RED_SIGN + 1];
+    //   thermodynamics   behind the sign section: acc = [10 sums][sum of s][count], its own sum of signs inside; per_walker
+    //                    [W][11], read with stride 10, or 11 with sign weighting on (the sample then ends with s_w); its
+    //                    binner (DQMC_BIN_THERMODYNAMICS) is sized by hand like a momentum binner (thermo.inl)
+    } sec[DQMC_RED_THERMODYNAMICS + 1];
     // correlation measurements (EachSitePairByDistance tables set by the host)
     int n_dirs = 0;
     int *dir_ptr = nullptr, *pair_src = nullptr, *pair_trg = nullptr;
@@ -144,7 +147,7 @@ struct dqmc_handle {
     size_t red_cap = 0;
     dqmc_stats red_stats{};
     bool red_valid = false;
-    size_t red_sizes[DQMC_RED_SIGN + 1] = {0, 0, 0, 0, 0, 0};  // packed section sizes of the LAST reduction (dqmc_get_reduced checks against these)
+    size_t red_sizes[DQMC_RED_THERMODYNAMICS + 1] = {0, 0, 0, 0, 0, 0, 0};  // packed section sizes of the LAST reduction (dqmc_get_reduced checks against these)
     bool red_td_ok = false;  // the time-displaced and susceptibility sample counts agreed when that reduction was packed
     // logarithmic binners (binner.inl), one per DQMC_BIN_* section: xs, x2 [L][W][E], c [L - 1][W][E], out = finish scratch
     struct Binner {
@@ -152,7 +155,7 @@ struct dqmc_handle {
         int E = 0, L = 0;
         int64_t cap = 0, T = 0;  // capacity and pushes so far: count[level] = T >> level for every element
         double *xs = nullptr, *x2 = nullptr, *c = nullptr, *out = nullptr;
-    } bin[DQMC_BIN_MOMENTUM_END];  // (DQMC_BIN_SIGN + k: the signs pushed with section k = a DQMC_RED_* index; then the momentum binners)
+    } bin[DQMC_BIN_THERMODYNAMICS + 1];  // (DQMC_BIN_SIGN + k: the signs pushed with section k = a DQMC_RED_* index; then the momentum binners and the thermodynamics one)
     // momentum-space observables (momentum.inl, momentum.hip): n_q == 0: off, nothing allocated.  cos_d / sin_d
     // [n_dirs x n_q] on the device, the host copies for the checkpoint; sample[k]: the per-walker momentum sample
     // [W][E] of binner DQMC_BIN_MOMENTUM_CORRELATIONS + k, allocated with the binner
@@ -162,6 +165,16 @@ struct dqmc_handle {
         std::vector<double> cos_h, sin_h;
         double *sample[DQMC_BIN_MOMENTUM_END - DQMC_BIN_MOMENTUM_CORRELATIONS] = {nullptr, nullptr, nullptr};
     } mom;
+    // scalar thermodynamics (thermo.inl, thermo.hip): on == false: off, nothing allocated.  The hopping matrix of
+    // dqmc_set_thermodynamics as a neighbour list: the off-diagonal non-zeros of row i of block b at row_ptr[b n + i] ..
+    // of col / val, the diagonal in diag; T_hash: FNV-1a 64 of the matrix as it was handed in (the checkpoint compares it)
+    struct Thermo {
+        bool on = false;
+        int *row_ptr = nullptr, *col = nullptr;
+        double *val = nullptr, *diag = nullptr;
+        double U_s = 0.0;
+        uint64_t T_hash = 0;
+    } th;
     // time-displaced recording (unequal_time.inl, tdm.hip): every == 0: off, nothing allocated.  The sample (bin_E doubles
     // per walker in the layout of include/dqmc_hip.h) and the sums are sec[DQMC_RED_TIME_DISPLACED]; src_of [n_dirs][n]
     // only with the fast form
@@ -1907,7 +1920,8 @@ int dqmc_reset_accumulators(dqmc_handle *h)
 
 // ---- size / host get / device export of a section's sums (dqmc_handle::Section) --------------------------------------
 static const char *const SEC_NEED[] = {nullptr, "call dqmc_set_pair_directions first", "call dqmc_set_local_targets first",
-                                       "nothing accumulated", "call dqmc_set_time_displaced first", nullptr};
+                                       "nothing accumulated", "call dqmc_set_time_displaced first", nullptr,
+                                       "call dqmc_set_thermodynamics first"};
 static int sec_size(dqmc_handle *h, int which, size_t *n)
 {
     if (!h || !n) return DQMC_ERR_INVALID;
@@ -1944,13 +1958,14 @@ int dqmc_export_pairing(dqmc_handle *h, void *device_out) { ENTER(h); return sec
 #include "binner.inl"
 #include "momentum.inl"
 #include "global_move.inl"
+#include "thermo.inl"
 #include "checkpoint.inl"
 
 // ---------------------------------------------------------------------------
 // Measurement reduction over ranks: every accumulator the handle keeps and the DQMCAnalysis
 // counters, as ONE packed device buffer of doubles [sums | maxima | minima]:
 //   sums   = acc (G, G.^2, occupation, count), correlations, pairing, susceptibilities, time-displaced rows (each if
-//            configured), the sums of signs (with sign weighting on), then prop_local, acc_local, negative_probability {sum, count}, propagation_error {sum, count}
+//            configured), the sums of signs (with sign weighting on), the thermodynamics section (if configured), then prop_local, acc_local, negative_probability {sum, count}, propagation_error {sum, count}
 //   maxima = negative_probability.max, propagation_error.max      minima = the two .min
 // (MagnitudeStats, DQMC.jl:4-47).  dqmc_reduce runs three ncclAllReduce (sum / max / min) on the handle's stream;
 // a host-side collective (MPI from Julia, gloo in the tests) can do the same through export / import.
@@ -1972,7 +1987,7 @@ static int red_pack(dqmc_handle *h)
         h->red_cap = tot;
     }
     size_t off = 0;
-    for (int i = 0; i <= DQMC_RED_SIGN; ++i) {
+    for (int i = 0; i <= DQMC_RED_THERMODYNAMICS; ++i) {
         const dqmc_handle::Section &s = h->sec[i];
         if (s.n_red)
             HIPCHK(hipMemcpyAsync(h->red_buf + off, s.acc, s.n_red * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
@@ -2104,17 +2119,17 @@ int dqmc_reduce_import(dqmc_handle *h, const double *host_in)
 }
 // section `which` of the last reduction: 0 Green's-function sums (dqmc_accumulator_size doubles), 1 correlations,
 // 2 pairing, 3 susceptibilities (sizes as the local getters report), 4 the time-displaced rows: the E packed sums, then
-// the reduced sample count of the susceptibilities (dqmc_time_displaced_size doubles)
+// the reduced sample count of the susceptibilities (dqmc_time_displaced_size doubles), 5 the sums of signs, 6 thermodynamics
 int dqmc_get_reduced(dqmc_handle *h, int32_t which, double *host_out)
 {
     ENTER(h);
-    if (!host_out || which < 0 || which > DQMC_RED_SIGN) return fail(h, DQMC_ERR_INVALID, "dqmc_get_reduced: bad arguments");
+    if (!host_out || which < 0 || which > DQMC_RED_THERMODYNAMICS) return fail(h, DQMC_ERR_INVALID, "dqmc_get_reduced: bad arguments");
     if (!h->red_valid) return fail(h, DQMC_ERR_STATE, "call dqmc_reduce first");
     size_t off = 0;
     for (int i = 0; i < which; ++i) off += h->sec[i].n_red;
     const size_t cnt = h->sec[which].n_red;
     if (cnt == 0) return fail(h, DQMC_ERR_STATE, "dqmc_get_reduced: this accumulator is not configured");
-    for (int i = 0; i <= DQMC_RED_SIGN; ++i)  // (sizes as they are NOW against the sizes that were packed)
+    for (int i = 0; i <= DQMC_RED_THERMODYNAMICS; ++i)  // (sizes as they are NOW against the sizes that were packed)
         if (h->sec[i].n_red != h->red_sizes[i])
             return fail(h, DQMC_ERR_STATE, "accumulators were reconfigured after the last reduction: call dqmc_reduce again");
     if (h->red_cap < red_nsum(h) + 4) return fail(h, DQMC_ERR_STATE, "call dqmc_reduce first");

@@ -112,9 +112,9 @@ int dqmc_set_sign_weighting(dqmc_handle *h, int32_t on)
 {
     ENTER(h);
     HIPCHK(hipStreamSynchronize(h->stream));
-    for (int i = 0; i < DQMC_RED_SIGN; ++i) {  // signed and unsigned sums never mix
+    for (int i = 0; i <= DQMC_RED_THERMODYNAMICS; ++i) {  // signed and unsigned sums never mix
         const dqmc_handle::Section &sc = h->sec[i];
-        if (!sc.n) continue;
+        if (!sc.n || i == DQMC_RED_SIGN) continue;
         double cnt = 0.0;
         HIPCHK(hipMemcpy(&cnt, sc.acc + sc.n - 1, sizeof(double), hipMemcpyDeviceToHost));
         if (cnt != 0.0)
@@ -123,7 +123,7 @@ int dqmc_set_sign_weighting(dqmc_handle *h, int32_t on)
     for (int which = DQMC_BIN_GREENS; which <= DQMC_BIN_TIME_DISPLACED; ++which)
         if (which != DQMC_BIN_USER && h->bin[which].on && h->bin[which].T)
             return fail(h, DQMC_ERR_STATE, "dqmc_set_sign_weighting: a binner has samples: call dqmc_reset_accumulators first");
-    for (int which = DQMC_BIN_MOMENTUM_CORRELATIONS; which < DQMC_BIN_MOMENTUM_END; ++which)
+    for (int which = DQMC_BIN_MOMENTUM_CORRELATIONS; which <= DQMC_BIN_THERMODYNAMICS; ++which)
         if (h->bin[which].on && h->bin[which].T)
             return fail(h, DQMC_ERR_STATE, "dqmc_set_sign_weighting: a binner has samples: call dqmc_reset_accumulators first");
     h->sign_on = on != 0;
@@ -140,6 +140,7 @@ int dqmc_set_sign_weighting(dqmc_handle *h, int32_t on)
     // a momentum sample ends with s_w while weighting is on: its binners are made again, empty, with their capacities
     for (int which = DQMC_BIN_MOMENTUM_CORRELATIONS; which < DQMC_BIN_MOMENTUM_END; ++which)
         if (h->bin[which].on) CHK(mom_enable(h, which, h->bin[which].cap));
+    if (h->bin[DQMC_BIN_THERMODYNAMICS].on) CHK(thermo_enable(h, h->bin[DQMC_BIN_THERMODYNAMICS].cap));  // and so does this one
     return dqmc_synchronize(h);
 }
 int dqmc_get_sign_weighting(dqmc_handle *h, int32_t *on)

@@ -501,6 +501,16 @@ hipError_t launch_correlation_pairs(int n, int nb, int model, int n_walkers, con
 hipError_t launch_pairing_pairs(int n, int nb, int n_walkers, const double *G, long stride_unit, const int *dir_ptr,
                                 const int *pair_src, const int *pair_trg, int n_dirs, int K, const int *trg_of,
                                 double *per_walker, hipStream_t s);
+// scalar thermodynamics (thermo.hip): the ten elements of include/dqmc_hip.h "thermodynamics" per walker from the true G
+// of every unit (G + (w nb + b) stride_unit), written to per_walker[w][per_stride], then the sums into acc
+// [10 sums][sum of signs][count].  The hopping matrix comes as a neighbour list: the off-diagonal non-zeros T_ij of row i
+// of block b at row_ptr[b n + i] .. row_ptr[b n + i + 1] of col / val, the diagonal in tdiag [nb n].  sw: nullptr, or
+// sign.hip's [n_walkers + 2]; then per_walker is rewritten as s_w x, per_walker[w][10] = s_w (per_stride >= 11) and
+// acc[10] is left to launch_sign_prepare.
+constexpr int DQMC_THERMO_ELEMENTS_K = 10;
+hipError_t launch_thermodynamics(int n, int nb, int n_walkers, const double *G, long stride_unit, const int *row_ptr,
+                                 const int *col, const double *val, const double *tdiag, double U_s, double *per_walker,
+                                 long per_stride, const double *sw, double *acc, hipStream_t s);
 // HS field <-> Julia BitArray chunks (compress / decompress, HubbardModel.jl:56-59)
 hipError_t launch_conf_pack(const int8_t *conf, size_t n_elem, unsigned long long *chunks, hipStream_t s);
 hipError_t launch_conf_unpack(const unsigned long long *chunks, size_t n_elem, int8_t *conf, hipStream_t s);

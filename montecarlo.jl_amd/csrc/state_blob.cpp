@@ -44,6 +44,7 @@ uint64_t fnv1a(const uint8_t *p, size_t n)
 
 enum { HEADER_BYTES = 8 + 4 + 4 + HASH_BYTES + 6 * 4 + 2 * 8 + 2 * N_SEC * 8 + N_BIN * 32 + 6 * 4 + 8 + 8 };
 enum { EXT_FIXED_BYTES = 2 * 4 + N_MOM * 32 };
+enum { THERMO_FIXED_BYTES = 2 * 8 + 32 + 8 + 8 };
 
 bool mul(size_t a, size_t b, size_t *out) { return !__builtin_mul_overflow(a, b, out); }
 bool add(size_t a, size_t b, size_t *out) { return !__builtin_add_overflow(a, b, out); }
@@ -63,6 +64,8 @@ int refuse(std::string *why, const std::string &msg)
 }  // namespace
 
 size_t header_bytes() { return HEADER_BYTES; }
+
+uint64_t fnv1a64(const void *bytes, size_t n) { return fnv1a((const uint8_t *)bytes, n); }
 
 size_t conf_chunks(int32_t n_sites, int32_t slices) { return ((size_t)n_sites * (size_t)slices + 63) / 64; }
 
@@ -295,19 +298,25 @@ void seal_ext(const ExtLayout &e, uint8_t *blob)
     put(p, fnv1a(blob + e.start, e.checksum - e.start), 8);
 }
 
-int validate_any(const uint8_t *buf, size_t n_bytes, const Shape &h, const Momenta &hm, Shape *blob, Momenta *mblob,
-                 std::string *why)
+// validate_any for the blob's version-1 / 2 part.  newest: the highest format version the caller reads; with a version
+// above 2 more bytes may follow that part, whose size goes to *end
+static int validate_core(const uint8_t *buf, size_t n_bytes, const Shape &h, const Momenta &hm, uint32_t newest, Shape *blob,
+                         Momenta *mblob, uint32_t *version_out, size_t *end, std::string *why)
 {
     Shape s{};
     uint32_t version = 0;
     size_t total = 0;
-    if (validate_head(buf, n_bytes, h, VERSION_MOMENTA, &s, &version, &total, why) != 0) return -1;
+    if (validate_head(buf, n_bytes, h, newest, &s, &version, &total, why) != 0) return -1;
+    const bool tail = version >= VERSION_THERMO;
+    const char *const fmt = version == VERSION ? "1" : "3";
     Momenta m{};
-    if (version == VERSION) {
-        if (n_bytes != total) return refuse_size(why, n_bytes, total);
+    *version_out = version;
+    *end = total;
+    if (version == VERSION || version == VERSION_THERMO) {
+        if (tail ? n_bytes < total : n_bytes != total) return refuse_size(why, n_bytes, total);
         for (int k = 0; k < N_MOM; ++k)
             if (hm.bin[k].on)
-                return refuse(why, std::string("binner ") + MOM_NAME[k] + " on: the blob (format version 1) has 0, the handle 1");
+                return refuse(why, std::string("binner ") + MOM_NAME[k] + " on: the blob (format version " + fmt + ") has 0, the handle 1");
     } else {
         if (n_bytes < total || n_bytes - total < EXT_FIXED_BYTES) return refuse_size(why, n_bytes, total + EXT_FIXED_BYTES);
         const uint8_t *p = buf + total;
@@ -323,11 +332,12 @@ int validate_any(const uint8_t *buf, size_t n_bytes, const Shape &h, const Momen
             b.T = (int64_t)get(p, 8);
             if (b.on != 0 && b.on != 1) return refuse(why, std::string("binner ") + MOM_NAME[k] + " on: neither 0 nor 1");
         }
-        if (!m.any()) return refuse(why, "extension: a format version 2 blob with no momentum binner in it");
+        if (!m.any()) return refuse(why, "extension: a format version " + std::to_string(version) + " blob with no momentum binner in it");
         ExtLayout e;
         std::string lw;
         if (!ext_layout(s, m, &e, &lw)) return refuse(why, lw + ": not a shape a handle can have");
-        if (n_bytes != e.total) return refuse_size(why, n_bytes, e.total);
+        if (tail ? n_bytes < e.total : n_bytes != e.total) return refuse_size(why, n_bytes, e.total);
+        *end = e.total;
         const uint8_t *sum_at = buf + e.checksum;
         if (get(sum_at, 8) != fnv1a(buf + e.start, e.checksum - e.start))
             return refuse(why, "extension checksum: the extension is damaged");
@@ -361,6 +371,133 @@ int validate_any(const uint8_t *buf, size_t n_bytes, const Shape &h, const Momen
     }
     if (blob) *blob = s;
     if (mblob) *mblob = m;
+    return 0;
+}
+int validate_any(const uint8_t *buf, size_t n_bytes, const Shape &h, const Momenta &hm, Shape *blob, Momenta *mblob,
+                 std::string *why)
+{
+    uint32_t version = 0;
+    size_t end = 0;
+    return validate_core(buf, n_bytes, h, hm, VERSION_MOMENTA, blob, mblob, &version, &end, why);
+}
+
+bool thermo_layout(const Shape &s, const Momenta &m, const Thermo &t, ThermoLayout *out, std::string *why)
+{
+    auto bad = [&](const char *what) {
+        if (why) *why = what;
+        return false;
+    };
+    ExtLayout e;
+    if (!ext_layout(s, m, &e, why)) return false;
+    ThermoLayout l{};
+    l.start = l.total = e.total;
+    if (!t.any()) {
+        if (out) *out = l;
+        return true;
+    }
+    if (t.n > (uint64_t)SIZE_MAX / 8) return bad("section thermodynamics size");
+    const size_t W = (size_t)s.n_walkers;
+    size_t off = l.start, skip;
+    bool ok = take(&off, &skip, THERMO_FIXED_BYTES, 1) && take(&off, &l.sec, (size_t)t.n, 8);
+    l.bin_xs = l.bin_x2 = l.bin_c = off;
+    if (ok && t.bin.on) {
+        if (t.bin.E < 1 || t.bin.L < 1 || t.bin.L > 41) return bad("thermodynamics binner elements / levels");
+        size_t we;
+        ok = mul(W, (size_t)t.bin.E, &we) && mul(we, 8, &we);
+        ok = ok && take(&off, &l.bin_xs, (size_t)t.bin.L, we);
+        ok = ok && take(&off, &l.bin_x2, (size_t)t.bin.L, we);
+        ok = ok && take(&off, &l.bin_c, (size_t)t.bin.L - 1, we);
+    }
+    ok = ok && take(&off, &l.checksum, 1, 8);
+    if (!ok) return bad("blob size overflows");
+    l.total = off;
+    if (out) *out = l;
+    return true;
+}
+
+void write_header(const Shape &s, const Momenta &m, const Thermo &t, uint8_t *out)
+{
+    if (!t.any()) write_header(s, m, out);
+    else write_header_version(s, m.any() ? VERSION_THERMO_MOMENTA : VERSION_THERMO, out);
+}
+
+void write_thermo(const Thermo &t, const ThermoLayout &l, uint8_t *blob)
+{
+    if (!t.any()) return;
+    uint8_t *p = blob + l.start;
+    put(p, t.n, 8);
+    put(p, t.n_red, 8);
+    put(p, (uint32_t)t.bin.on, 4);
+    put(p, (uint32_t)t.bin.E, 4);
+    put(p, (uint32_t)t.bin.L, 4);
+    put(p, 0, 4);
+    put(p, (uint64_t)t.bin.cap, 8);
+    put(p, (uint64_t)t.bin.T, 8);
+    put(p, t.T_hash, 8);
+    put(p, bits_of(t.U_s), 8);
+}
+
+void seal_thermo(const ThermoLayout &l, uint8_t *blob)
+{
+    if (l.total == l.start) return;
+    uint8_t *p = blob + l.checksum;
+    put(p, fnv1a(blob + l.start, l.checksum - l.start), 8);
+}
+
+int validate_all(const uint8_t *buf, size_t n_bytes, const Shape &h, const Momenta &hm, const Thermo &ht, Shape *blob,
+                 Momenta *mblob, Thermo *tblob, std::string *why)
+{
+    Shape s{};
+    Momenta m{};
+    Thermo t{};
+    uint32_t version = 0;
+    size_t end = 0;
+    if (validate_core(buf, n_bytes, h, hm, VERSION_THERMO_MOMENTA, &s, &m, &version, &end, why) != 0) return -1;
+    if (version < VERSION_THERMO) {
+        if (ht.any())
+            return refuse(why, "section thermodynamics n: the blob (format version " + std::to_string(version) + ") has 0, the handle " +
+                                   std::to_string(ht.n));
+    } else {
+        if (n_bytes - end < THERMO_FIXED_BYTES) return refuse_size(why, n_bytes, end + THERMO_FIXED_BYTES);
+        const uint8_t *p = buf + end;
+        t.n = get(p, 8);
+        t.n_red = get(p, 8);
+        t.bin.on = (int32_t)(uint32_t)get(p, 4);
+        t.bin.E = (int32_t)(uint32_t)get(p, 4);
+        t.bin.L = (int32_t)(uint32_t)get(p, 4);
+        (void)get(p, 4);
+        t.bin.cap = (int64_t)get(p, 8);
+        t.bin.T = (int64_t)get(p, 8);
+        t.T_hash = get(p, 8);
+        t.U_s = double_of(get(p, 8));
+        if (t.bin.on != 0 && t.bin.on != 1) return refuse(why, "binner thermodynamics on: neither 0 nor 1");
+        if (!t.any()) return refuse(why, "extension: a format version " + std::to_string(version) + " blob with no thermodynamics section in it");
+        ThermoLayout l;
+        std::string lw;
+        if (!thermo_layout(s, m, t, &l, &lw)) return refuse(why, lw + ": not a shape a handle can have");
+        if (n_bytes != l.total) return refuse_size(why, n_bytes, l.total);
+        const uint8_t *sum_at = buf + l.checksum;
+        if (get(sum_at, 8) != fnv1a(buf + l.start, l.checksum - l.start))
+            return refuse(why, "thermodynamics extension checksum: the extension is damaged");
+#define SAME_T(field, name)                                                                                           \
+    if (!(t.field == ht.field))                                                                                       \
+        return refuse(why, std::string(name) + ": the blob has " + std::to_string(t.field) + ", the handle " +        \
+                               std::to_string(ht.field))
+        SAME_T(n, "section thermodynamics n");
+        SAME_T(n_red, "section thermodynamics n_red");
+        SAME_T(bin.on, "binner thermodynamics on");
+        SAME_T(bin.E, "binner thermodynamics E");
+        SAME_T(bin.L, "binner thermodynamics L");
+        SAME_T(bin.cap, "binner thermodynamics cap");
+#undef SAME_T
+        if (t.T_hash != ht.T_hash) return refuse(why, "thermodynamics hopping matrix: differs from the handle's");
+        if (bits_of(t.U_s) != bits_of(ht.U_s)) return refuse(why, "thermodynamics U_s: differs from the handle's");
+        if (t.bin.T < 0 || t.bin.T > (t.bin.on ? t.bin.cap : 0))
+            return refuse(why, "binner thermodynamics T: " + std::to_string(t.bin.T) + " pushes outside 0 .. capacity");
+    }
+    if (blob) *blob = s;
+    if (mblob) *mblob = m;
+    if (tblob) *tblob = t;
     return 0;
 }
 

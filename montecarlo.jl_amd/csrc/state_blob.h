@@ -96,6 +96,38 @@ void seal_ext(const ExtLayout &e, uint8_t *blob);
 int validate_any(const uint8_t *buf, size_t n_bytes, const Shape &handle, const Momenta &hm, Shape *blob, Momenta *mblob,
                  std::string *why);
 
+// ---- format versions 3 and 4: the version-1 (3) or version-2 (4) blob, its version field apart, then an extension for the
+// thermodynamics section (DQMC_RED_THERMODYNAMICS, DQMC_BIN_THERMODYNAMICS), which the header's tables have no room for.  A
+// handle without the section writes version 1 / 2 unchanged.
+//   u64 n, n_red   i32 on, E, L, pad, i64 cap, T (the binner)   u64 T_hash   f64 U_s
+//   the section's n doubles   xs, x2, c of the binner if enabled   u64 FNV-1a 64 of every extension byte in front of it
+static const uint32_t VERSION_THERMO = 3, VERSION_THERMO_MOMENTA = 4;
+struct Thermo {
+    uint64_t n = 0, n_red = 0;  // doubles of the section / of its part in the reduction; n == 0: off, the blob is version 1 / 2
+    Shape::Bin bin = {};
+    uint64_t T_hash = 0;        // fnv1a64 of the hopping matrix the section was configured with
+    double U_s = 0.0;
+    bool any() const { return n != 0; }
+};
+// byte offsets from the start of the blob; with !t.any() only `start` and `total` are set, both to the size of the version-1 / 2 blob
+struct ThermoLayout {
+    size_t start, sec, bin_xs, bin_x2, bin_c, checksum, total;
+};
+uint64_t fnv1a64(const void *bytes, size_t n);
+bool thermo_layout(const Shape &s, const Momenta &m, const Thermo &t, ThermoLayout *out, std::string *why = nullptr);
+// write_header with the version the triple calls for (t.any(): 3 or 4, else as write_header(s, m, out))
+void write_header(const Shape &s, const Momenta &m, const Thermo &t, uint8_t *out);
+// the extension's fixed fields into blob + l.start (nothing when !t.any()); seal_thermo once the section and the binner
+// arrays are in place
+void write_thermo(const Thermo &t, const ThermoLayout &l, uint8_t *blob);
+void seal_thermo(const ThermoLayout &l, uint8_t *blob);
+// validate_any for all four versions.  Versions 1 and 2: as validate_any, and refused when the handle has the section.
+// Versions 3 and 4: the version-1 / 2 part as there, then this extension: n_bytes holds its fixed fields; its shape is one a
+// handle can have; n_bytes against the size it implies; its checksum; n, n_red, the binner's on / E / L / cap, T_hash and
+// U_s against `ht` (the first that differs is named); the range of T.  0 and *blob / *mblob / *tblob filled, or -1 and *why.
+int validate_all(const uint8_t *buf, size_t n_bytes, const Shape &handle, const Momenta &hm, const Thermo &ht, Shape *blob,
+                 Momenta *mblob, Thermo *tblob, std::string *why);
+
 // compress / decompress of one walker's field (HubbardModel.jl:56-59): element i of conf (+1 / -1) in bit i % 64 of chunk i / 64
 void pack_conf(const int8_t *conf, size_t n, uint8_t *chunks_le);
 void unpack_conf(const uint8_t *chunks_le, size_t n, int8_t *conf);

@@ -248,6 +248,7 @@ class DQMC:
         self._dirs, self._mom = None, None  # the directions of set_pair_directions' iterator; (q, cos table, sin table) of set_momenta
         self._gm_set = None       # (rate, kind) of the last set_global_rate
         self._sus_layout = False  # the susceptibility section is laid out (by its first use)
+        self._thermo = False      # set_thermodynamics is on
         self._mid_sweep = False  # set by load(): run() finishes the sweep the checkpoint was taken in
         if int(global_rate) < 1:
             raise ValueError("global_rate must be at least 1")
@@ -448,7 +449,8 @@ class DQMC:
         "greens" (greens_measurement, occupation), "correlations" (charge/spin density correlations,
         magnetization; needs set_pair_directions), "pairing" (needs set_local_targets) and
         "susceptibilities" (the CombinedGreensIterator measurements) and "time_displaced" (the tau-resolved rows; needs
-        set_time_displaced; shares the one iterator pass with "susceptibilities").  `binning=True` enables the device-side
+        set_time_displaced; shares the one iterator pass with "susceptibilities"), and "thermodynamics" (energy, filling,
+        double occupancy ...; needs set_thermodynamics).  `binning=True` enables the device-side
         LogBinner of every selected measurement before the first sweep (enable_binning; read with binned()).
         `checkpoint=path` saves the run (save()) in every `checkpoint_every`-th sweep and in the last one, thermalization
         included, at the sweep's measurement point behind its measurements: the one place of a sweep where the chain stands
@@ -458,7 +460,7 @@ class DQMC:
         if checkpoint is not None and (checkpoint_every is None or int(checkpoint_every) < 1):
             raise ValueError("run(checkpoint=path) needs checkpoint_every >= 1")
         known = {"greens": lib().dqmc_accumulate_greens, "correlations": lib().dqmc_accumulate_correlations,
-                 "pairing": lib().dqmc_accumulate_pairing}
+                 "pairing": lib().dqmc_accumulate_pairing, "thermodynamics": lib().dqmc_accumulate_thermodynamics}
         for m in measurements:
             if m not in known and m not in ("susceptibilities", "time_displaced"):
                 raise ValueError("unknown measurement %r" % (m,))
@@ -535,14 +537,16 @@ class DQMC:
             raise ValueError("save(): %s on %s is not a model / lattice a checkpoint can name"
                              % (type(m).__name__, type(l).__name__))
         model = {"class": type(m).__name__, "U": m.U, "t": m.t}
-        if m.kind == _lib.ATTRACTIVE:
+        if m.kind == _lib.ATTRACTIVE or m.mu != 0.0:  # (an undoped repulsive model is written as it always was)
             model["mu"] = m.mu
         tables = {}
         for name, entry in self._tables.items():
             tables[name] = {"table": _ckpt.pack_table(entry[0]), "count": entry[1]}
             if name == "current_targets":
                 tables[name]["hopping"] = entry[2]
+        extra = {"thermodynamics": self._thermo} if self._thermo else {}  # (absent while off: the preamble of before)
         return {
+            **extra,
             "format": 1,
             "model": model,
             "lattice": {"class": type(l).__name__, "args": [int(getattr(l, a)) for a in self._LATTICES[type(l).__name__]]},
@@ -614,6 +618,12 @@ class DQMC:
                 mo = pre["momenta"]
                 mc._set_momenta(np.array(mo["q"], dtype=np.float64), np.array(mo["cos"], dtype=np.float64),
                                 np.array(mo["sin"], dtype=np.float64))
+            if pre.get("thermodynamics"):
+                hop = pre["thermodynamics"]
+                if hop is not True:
+                    hop = [np.asarray(hop[b * mc.N * mc.N:(b + 1) * mc.N * mc.N]).reshape((mc.N, mc.N), order="F")
+                           for b in range(mc.nb)]
+                mc.set_thermodynamics(True, hopping=None if hop is True else hop)
             mc.prepare()  # (the susceptibility layout and two of the binners need a prepared handle)
             if pre["susceptibilities_layout"]:
                 mc._section_size("susceptibilities")
@@ -748,6 +758,7 @@ class DQMC:
         return out
 
     _SIGN_ORDER = ("greens", "correlations", "pairing", "susceptibilities", "time_displaced")  # DQMC_RED_* order
+    _NE = len(_lib.THERMO_FIELDS)  # DQMC_THERMO_ELEMENTS: the thermodynamics section is [_NE sums][sum of s][count]
 
     def sign_sums(self, reduced=False):
         """-> {section: sum of s over its samples} (the DQMC_RED_SIGN section; `reduced`: of the last reduction)"""
@@ -755,6 +766,9 @@ class DQMC:
 
     def mean_sign(self, which="greens"):
         """<s> of the samples of one section: its sum of signs over its sample count"""
+        if which == "thermodynamics":  # (the section carries its own sum of signs)
+            raw = self._section(which)
+            return raw[-2] / raw[-1]
         if which not in self._SIGN_ORDER:
             raise ValueError("unknown section %r" % (which,))
         return self.sign_sums()[which] / self._section(which)[-1]
@@ -765,16 +779,18 @@ class DQMC:
         sum of signs instead of its sample count; plus count, sign_sum and mean_sign.  With the section's binner on every
         field X also comes with X_std_error: the jackknife over the walkers of the ratio (jackknife_ratio), from each
         walker's level-0 sums of s x and of s; that needs at least two walkers.  ValueError when the sum of signs is 0."""
-        if which not in self._SIGN_ORDER:
+        if which not in self._SIGN_ORDER + ("thermodynamics",):
             raise ValueError("unknown section %r" % (which,))
         if not self.sign_weighting():
             raise _lib.DQMCError(_lib.ERR_STATE, "signed(): sign weighting is off (set_sign_weighting)")
         raw = self._section(which)
-        cnt, S = raw[-1], self.sign_sums()[which]
+        cnt, S = raw[-1], (raw[-2] if which == "thermodynamics" else self.sign_sums()[which])
         if S == 0:
             raise ValueError("signed(%r): the sum of signs is 0 over %d samples: <O s> / <s> is undefined" % (which, cnt))
         raw = raw.copy()
         raw[-1] = S
+        if which == "thermodynamics":  # (thermodynamics() divides by the sum of signs itself and adds the jackknife errors)
+            return self.thermodynamics()
         if which == "greens":
             res = self.unpack_accumulators(raw)
         elif which == "correlations":
@@ -796,6 +812,9 @@ class DQMC:
     def signed_walker_sums(self, which):
         """-> (sx [n_walkers, E], s [n_walkers]): level 0 of every walker's binners of a section, the sums of s x in the
         section's element order, and of its sign binner, the sums of s"""
+        if which == "thermodynamics":  # one binner: the sample ends with s
+            lv0 = np.stack([self.binner_level(which, w, 0)[0] for w in range(self.n_walkers)])
+            return lv0[:, :self._NE], lv0[:, self._NE]
         bid = _lib.BIN_SIGN + self._SIGN_ORDER.index(which)
         sx = np.stack([self.binner_level(which, w, 0)[0] for w in range(self.n_walkers)])
         sg = np.zeros(self.n_walkers)
@@ -834,7 +853,7 @@ class DQMC:
     def reduced(self, which="greens"):
         """dqmc_get_reduced: the global sums of the last reduction (the handle's own accumulators keep the local sums);
         `which` = greens | correlations | pairing | susceptibilities | time_displaced | sign (the sums of signs, packed
-        only with sign weighting on), layouts as the local getters"""
+        only with sign weighting on) | thermodynamics, layouts as the local getters"""
         return self._section(which, reduced=True)
 
     def reduced_analysis(self):
@@ -878,7 +897,8 @@ class DQMC:
                  "pairing": (2, "dqmc_pairing_size", "dqmc_get_pairing"),
                  "susceptibilities": (3, "dqmc_susceptibilities_size", "dqmc_get_susceptibilities"),
                  "time_displaced": (_lib.RED_TIME_DISPLACED, "dqmc_time_displaced_size", "dqmc_get_time_displaced"),
-                 "sign": (_lib.RED_SIGN, "dqmc_sign_sums_size", "dqmc_get_sign_sums")}
+                 "sign": (_lib.RED_SIGN, "dqmc_sign_sums_size", "dqmc_get_sign_sums"),
+                 "thermodynamics": (_lib.RED_THERMODYNAMICS, "dqmc_thermodynamics_size", "dqmc_get_thermodynamics")}
 
     def _section_size(self, which):
         n = C.c_size_t()
@@ -922,6 +942,8 @@ class DQMC:
             return _lib.BIN_TIME_DISPLACED
         if which in _lib.BIN_MOMENTUM:
             return _lib.BIN_MOMENTUM[which]
+        if which == "thermodynamics":
+            return _lib.BIN_THERMODYNAMICS
         if which not in _lib.BIN_SECTIONS:
             raise ValueError("unknown binner section %r" % (which,))
         return _lib.BIN_SECTIONS.index(which)
@@ -1035,6 +1057,10 @@ class DQMC:
                     sizes += [(k, p["rows"] * nq, (p["rows"], nq)) for k in ("CDCk", "SDCxk", "SDCyk", "SDCzk")]
             if self.sign_weighting():
                 sizes.append(("s", 1, None))
+        elif which == "thermodynamics":
+            sizes = [(k, 1, None) for k in _lib.THERMO_FIELDS]
+            if self.sign_weighting():
+                sizes.append(("s", 1, None))
         else:
             sizes = [("x", self.binner_size("user")[0], None)]
         out, off = [], 0
@@ -1054,6 +1080,8 @@ class DQMC:
                 v = [v[b * n:(b + 1) * n] for b in range(B)]
             elif which in ("time_displaced", "momentum_time_displaced"):
                 v = v.reshape(shape)
+            elif which == "thermodynamics":  # scalars
+                v = v[0]
             elif shape is not None:
                 v = v.reshape(shape, order="F")
             res[name] = v
@@ -1073,7 +1101,7 @@ class DQMC:
         -> PC[dir12, dir1, dir2]; susceptibilities -> CDS, SDSx, SDSy, SDSz, PS, CCS; user -> x.  Every field X comes with
         X_std_error (binning error at `level`, default the reliable level), X_std_error_walkers (the cross-walker
         error, independent of the binning) and X_tau; plus count (samples per walker) and reliable_level."""
-        if which in _lib.BIN_MOMENTUM:
+        if which in _lib.BIN_MOMENTUM or which == "thermodynamics":
             return self._binned_momentum(which, level)
         raw = self.binned_raw(which, level)
         res = self._bin_dict(which, raw)
@@ -1426,6 +1454,65 @@ class DQMC:
         res.update(d)
         res["count"] = raw["count"]
         res["reliable_level"] = raw["reliable_level"]
+        return res
+
+    # ---- scalar thermodynamics (include/dqmc_hip.h "thermodynamics"; the reference has no such measurement)
+    def set_thermodynamics(self, on=True, hopping=None):
+        """configure the thermodynamics section: the model's hopping_matrix() (or `hopping`, one n x n matrix per block)
+        goes to the engine, which keeps it as a neighbour list.  From then on accumulate_thermodynamics() and
+        run(measurements=(..., "thermodynamics")) add one sample per walker of n_up, n_dn, n, D, m2, E_kin, E_int, E, N2,
+        Mz2 (per site; include/dqmc_hip.h).  on=False drops the section.  Either way its sums and its binner go."""
+        self._binner_dropped("thermodynamics")
+        if not on:
+            self._c(lib().dqmc_set_thermodynamics(self._h, None))
+            self._thermo = False
+            return
+        blocks = self.model.hopping_matrix() if hopping is None else hopping
+        if isinstance(blocks, np.ndarray) and blocks.ndim == 2:
+            blocks = [blocks]
+        if len(blocks) != self.nb or any(np.shape(b) != (self.N, self.N) for b in blocks):
+            raise ValueError("hopping must be %d matrices of %d x %d" % (self.nb, self.N, self.N))
+        T = np.ascontiguousarray(np.concatenate([np.asarray(b, dtype=np.float64).reshape(-1, order="F") for b in blocks]))
+        self._c(lib().dqmc_set_thermodynamics(self._h, dptr(T)))
+        # (what a checkpoint writes down: the hopping only where it is not the model's own, as for the current targets)
+        self._thermo = True if hopping is None else [float(x) for x in T]
+
+    def accumulate_thermodynamics(self):
+        self._c(lib().dqmc_accumulate_thermodynamics(self._h))
+
+    def _thermo_derived(self, m):
+        """kappa = beta (<N2> - N <n>^2), chi_s = beta <Mz2> / 4 of means m [..., 10]"""
+        beta = self.p.beta
+        return beta * (m[..., 8] - self.N * m[..., 2] ** 2), beta * m[..., 9] / 4.0
+
+    def thermodynamics(self):
+        """-> dict of the ten means n_up, n_dn, n, D, m2, E_kin, E_int, E, N2, Mz2 (per site), the derived
+        kappa = beta (<N2> - N <n>^2) and chi_s = beta <Mz2> / 4, count, sign_sum and mean_sign.  The sums are divided by
+        the section's sum of signs, which is the sample count while sign weighting is off and makes the means <x s> / <s>
+        while it is on (signed("thermodynamics") returns the same dict).  With the section's binner on and at least two
+        walkers every key X also has X_std_error, the jackknife over the walkers (kappa and chi_s included: they are no
+        linear functions of the sums).  ValueError when the sum of signs is 0."""
+        raw = self._section("thermodynamics")
+        NE = self._NE
+        S, cnt = raw[NE], raw[NE + 1]
+        if S == 0:
+            raise ValueError("thermodynamics(): the sum of signs is 0 over %d samples" % cnt)
+        m = raw[:NE] / S
+        res = dict(zip(_lib.THERMO_FIELDS, m))
+        res["kappa"], res["chi_s"] = self._thermo_derived(m)
+        res.update(count=cnt, sign_sum=S, mean_sign=S / cnt)
+        if self._binning_enabled("thermodynamics") and self.n_walkers >= 2:
+            lv0 = np.stack([self.binner_level("thermodynamics", w, 0)[0] for w in range(self.n_walkers)])
+            T = self.binner_size("thermodynamics")[2]
+            sx, s = lv0[:, :NE], (lv0[:, NE] if self.sign_weighting() else np.full(self.n_walkers, float(T)))
+            W, tot, St = self.n_walkers, sx.sum(axis=0), s.sum()
+            if T and St != 0 and not np.any(St - s == 0):
+                r = (tot[None, :] - sx) / (St - s)[:, None]  # the means with walker w left out
+                k, c = self._thermo_derived(r)
+                full = np.concatenate([r, k[:, None], c[:, None]], axis=1)
+                err = np.sqrt((W - 1) / W * ((full - full.mean(axis=0)) ** 2).sum(axis=0))
+                for name, e in zip(_lib.THERMO_FIELDS + ("kappa", "chi_s"), err):
+                    res[name + "_std_error"] = e
         return res
 
     # ---- current_current_susceptibility (measurements.jl:257-317) over EachLocalQuadBySyncedDistance{K}

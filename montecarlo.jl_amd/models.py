@@ -38,20 +38,23 @@ class HubbardModelAttractive:
 
 
 class HubbardModelRepulsive:
-    """HubbardModelRepulsive.jl:24-41; two spin blocks (BlockDiagonal, :68-69)."""
+    """HubbardModelRepulsive.jl:24-41; two spin blocks (BlockDiagonal, :68-69).  The reference fixes mu at 0; here `mu`
+    dopes the model: -mu on the diagonal of both blocks, as in the attractive model (mu = 0: the reference's matrices)."""
     flv = 2
     kind = 1
 
-    def __init__(self, L=None, dims=None, l=None, U=1.0, t=1.0):
+    def __init__(self, L=None, dims=None, l=None, U=1.0, t=1.0, mu=0.0):
         if U < 0:
             raise ValueError("U must be positive.")
         self.l = l if l is not None else choose_lattice(dims, L)
-        self.U, self.t, self.mu = float(U), float(t), 0.0
+        self.U, self.t, self.mu = float(U), float(t), float(mu)
 
     def hopping_matrix(self):
-        """HubbardModelRepulsive.jl:87-100: BlockDiagonal(T, copy(T))"""
+        """HubbardModelRepulsive.jl:87-100: BlockDiagonal(T, copy(T)), with -mu on the diagonal"""
         N = len(self.l)
         T = np.zeros((N, N))
+        if self.mu != 0.0:
+            T[np.diag_indices(N)] = -self.mu
         for src, trg in self.l.neighbors(True):
             T[trg - 1, src - 1] += -self.t
         return [T, T.copy()]
