@@ -20,7 +20,11 @@ TOL = 1e-10
 
 def lattice(gpu, name):
     return {"2x2": lambda: gpu.SquareLattice(2), "6x6": lambda: gpu.SquareLattice(6), "chain33": lambda: gpu.Chain(33),
-            "16x16": lambda: gpu.SquareLattice(16), "24x24": lambda: gpu.SquareLattice(24)}[name]()
+            "16x16": lambda: gpu.SquareLattice(16), "24x24": lambda: gpu.SquareLattice(24),
+            "tri4": lambda: gpu.TriangularLattice(4), "tri10": lambda: gpu.TriangularLattice(10),
+            "cubic3": lambda: gpu.CubicLattice(3, 3), "cubic5": lambda: gpu.CubicLattice(3, 5),
+            "chain64": lambda: gpu.Chain(64), "chain65": lambda: gpu.Chain(65), "chain128": lambda: gpu.Chain(128),
+            "chain129": lambda: gpu.Chain(129)}[name]()
 
 
 def make(gpu, name, kind, W, seed=77, U=1.0, **kw):
@@ -44,13 +48,24 @@ def one_sample(mc, updates=2):
     return np.stack([mc.binner_level("thermodynamics", w, 0)[0] for w in range(mc.n_walkers)])
 
 
-@pytest.mark.parametrize("W", [1, 3])
-@pytest.mark.parametrize("kind", ["attractive", "repulsive"])
-@pytest.mark.parametrize("name", ["2x2", "6x6", "chain33", "16x16", "24x24"])
+# off-diagonal non-zeros per row of the hopping matrix on the lattices whose neighbour list is not the square lattice's
+NEIGHBOURS = {"tri4": 6, "tri10": 6, "cubic3": 6, "cubic5": 6, "chain64": 2, "chain65": 2, "chain128": 2, "chain129": 2}
+SAMPLE_CASES = [(name, kind, W) for name in ("2x2", "6x6", "chain33", "16x16", "24x24") for kind in ("attractive", "repulsive")
+                for W in (1, 3)]
+SAMPLE_CASES += [(name, kind, W) for name in NEIGHBOURS for kind in ("attractive", "repulsive")
+                 for W in ((1, 3) if name in ("chain65", "tri10") else (1,))]
+
+
+@pytest.mark.parametrize("name,kind,W", SAMPLE_CASES)
 def test_samples_equal_numpy_on_the_same_greens_function(gpu, name, kind, W):
     """n = 4 (below a wavefront), 36 (no multiple of 16, one partial tile), 33 (odd), 256 (4 x 4 full tiles), 576 (9 x 9
-    tiles, more than one per lane stride of the diagonal loop); one and three walkers; both models, doped"""
+    tiles, more than one per lane stride of the diagonal loop); one and three walkers; both models, doped.  The
+    triangular (n = 16, 100) and cubic (n = 27, 125) lattices: six neighbours per row, non-bipartite, and at cubic L = 3
+    the periodic images at distance 1; the exact tile edges n = 64, 65, 128, 129 on chains."""
     mc = make(gpu, name, kind, W)
+    if name in NEIGHBOURS:  # (a degenerate lattice would make the bond sum trivial)
+        for t in mc.model.hopping_matrix():
+            assert np.all(np.count_nonzero(t - np.diag(np.diag(t)), axis=1) == NEIGHBOURS[name]), name
     x = one_sample(mc)
     assert x.shape == (W, NE)
     T = mc.model.hopping_matrix()
