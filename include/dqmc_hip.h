@@ -682,6 +682,18 @@ int dqmc_udt_pivot(int32_t device_id, int32_t n, int32_t batch, double *U, doubl
  * left them: the matrices overwritten by the elimination at n > 64, everything between the units untouched. */
 int dqmc_logdet_matrices(int32_t device_id, int32_t n, int32_t batch, double *A, int64_t strideA, double *D,
                          int64_t strideD, double *logabsdet, int32_t *sign);
+/* Diagnostic (like dqmc_logdet_matrices): impose the per-unit signs that "sign reweighting" works from, sign[w * n_blocks +
+ * b], each -1, 0 or +1.  Real fields give a negative sign only where a search finds one and never a sign of 0; this reaches
+ * the signed sums, and the path of a walker that is left out, at any shape.  The call first brings the cache of the current
+ * field up to date (one slice chain unless it holds: the kept logabsdet stay the true ones) and then overwrites the kept
+ * per-unit signs; the cache still counts as that of the current field.  From then on dqmc_get_sign and every signed
+ * dqmc_accumulate_* see the imposed signs, until something invalidates the cache: any update or sweep, dqmc_set_conf /
+ * dqmc_set_conf_bits, a global move, dqmc_state_import, and dqmc_logdet, which recomputes from scratch.  No other
+ * Monte-Carlo state is changed.  A global move taken while an override is in force would use the imposed signs in its
+ * weight ratio: a test must not do that.  DQMC_ERR_INVALID for a null pointer or a value outside {-1, 0, +1}, DQMC_ERR_STATE
+ * before dqmc_prepare and on the attractive model (sign +1 by construction, no array behind it); a refused call changes
+ * nothing. */
+int dqmc_impose_unit_signs(dqmc_handle *h, const int32_t *sign /* n_walkers * n_blocks */);
 /* rdivp!(A, T, O, pivot) (src/linalg/general.jl:138-166) */
 int dqmc_rdivp(int32_t device_id, int32_t n, int32_t batch, double *A, const double *T,
                const int64_t *pivot);

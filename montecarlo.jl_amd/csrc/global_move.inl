@@ -108,6 +108,23 @@ int dqmc_get_sign(dqmc_handle *h, int32_t *sign)
     }
     return DQMC_OK;
 }
+// Diagnostic: the per-unit signs of the cache replaced by the caller's.  The chain runs first, so that gm_lad[0] holds the
+// true values and the cache counts as current; everything is checked before the first write.
+int dqmc_impose_unit_signs(dqmc_handle *h, const int32_t *sign)
+{
+    ENTER(h);
+    if (!sign) return fail(h, DQMC_ERR_INVALID, "dqmc_impose_unit_signs: null input");
+    if (!h->prepared) return fail(h, DQMC_ERR_STATE, "dqmc_impose_unit_signs: call dqmc_prepare first");
+    if (h->p.model_kind != DQMC_REPULSIVE)
+        return fail(h, DQMC_ERR_STATE, "dqmc_impose_unit_signs: the attractive model's sign is +1 by construction, there is no array");
+    for (int u = 0; u < h->units; ++u)
+        if (sign[u] < -1 || sign[u] > 1) return fail(h, DQMC_ERR_INVALID, "dqmc_impose_unit_signs: a sign must be -1, 0 or +1");
+    CHK(logdet_current(h));
+    CHK(dqmc_synchronize(h));  // (the chain's own signs are written before the caller's)
+    static_assert(sizeof(int) == sizeof(int32_t), "sign buffer");
+    HIPCHK(hipMemcpy(h->gm_sg[0], sign, sizeof(int) * h->units, hipMemcpyHostToDevice));
+    return DQMC_OK;
+}
 int dqmc_set_sign_weighting(dqmc_handle *h, int32_t on)
 {
     ENTER(h);

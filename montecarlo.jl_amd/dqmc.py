@@ -751,6 +751,16 @@ class DQMC:
         self._c(lib().dqmc_get_sign(self._h, sg.ctypes.data_as(C.POINTER(C.c_int32))))
         return sg
 
+    def impose_unit_signs(self, signs):
+        """dqmc_impose_unit_signs (diagnostic): the per-unit signs, an int array [n_walkers, n_blocks] of -1, 0 or +1, in
+        the place of the ones of the current field, for sign() and every signed accumulate_* until the field changes or
+        logdet() recomputes them.  Repulsive model, after prepare().  Take no global move while it is in force."""
+        sg = np.asarray(signs)
+        if not np.issubdtype(sg.dtype, np.integer) or sg.shape != (self.n_walkers, self.nb):
+            raise ValueError("signs must be an int array of shape (n_walkers, n_blocks) = (%d, %d)" % (self.n_walkers, self.nb))
+        sg = np.ascontiguousarray(sg, dtype=np.int32)
+        self._c(lib().dqmc_impose_unit_signs(self._h, sg.ctypes.data_as(C.POINTER(C.c_int32))))
+
     def sign_failures(self):
         """-> int array [n_walkers]: samples left out of the signed sums because the walker's sign came out 0"""
         out = np.zeros(self.n_walkers, dtype=np.int64)
