@@ -242,6 +242,24 @@ def test_calculate_greens_AVX(gpu, O, n):
     print("n = %d: worst rel |G - G_oracle| = %.3g" % (n, worst))
 
 
+@pytest.mark.parametrize("n", [16, 64, 256, 257, 324, 600, 1024])
+def test_calculate_greens_AVX_chain_graded(gpu, O, n):
+    """the sizes of test_calculate_greens_AVX with Dl, Dr = exp(linspace(+20, -20, n)) (greens_ref.graded_udt_inputs at
+    g = 20, the grading that test_gpu_greens_graded.py asks of every size; more than 17 decades on each side of 1)
+    against the reference-rule oracle at TOL.  At n = 256 the device takes the pre-pivoted one-launch UDT.  A direct
+    float64 inverse is no reference at this grading; the extended-precision one is in test_gpu_greens_graded.py."""
+    import greens_ref
+    batch = 2
+    args = greens_ref.graded_udt_inputs(n, 20, 5000 + n, batch)
+    G = gpu.calculate_greens_AVX(*args)
+    worst = 0.0
+    for i in range(batch):
+        assert greens_ref.straddles_one(args[1][i]) and greens_ref.straddles_one(args[4][i])
+        worst = max(worst, relerr(G[i], O.calculate_greens(*greens_ref.unit(args, i))))
+    print("n = %d, g = 20: worst rel |G - G_oracle| = %.3g" % (n, worst))
+    assert worst < TOL
+
+
 @pytest.mark.parametrize("batch", [9, 33])
 def test_rdivp_partial_later_group(gpu, O, batch):
     """n = 256 with units that end inside a later group of eight (trsm_rl_kernel's block map pads them to whole groups):

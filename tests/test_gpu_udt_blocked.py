@@ -30,7 +30,13 @@ def graded_cases(n, rng):
     # trailing part of D is rounding noise in ANY implementation - contracts only, no factor comparison (CONTRACTS_ONLY)
     X[4] = X[4] @ np.diag(np.exp(np.linspace(15, -15, n))) @ rng.standard_normal((n, n)) / n
     X[5] = np.eye(n)[:, rng.permutation(n)] * np.exp(rng.uniform(-3, 3, size=n))[None, :]  # sparse, distinct norms
-    return X
+    # graded the way the matrix of the first UDT of calculate_greens_AVX! is (stack.jl:346-349): a well-conditioned factor
+    # between scale matrices - columns over 80 decades, and rows over 26 decades together with those columns
+    Y = rng.standard_normal((2, n, n)) / 16 + np.eye(n)
+    cols = np.exp(rng.uniform(-92, 92, size=n))
+    Y[0] = Y[0] * cols[None, :]
+    Y[1] = (np.exp(np.linspace(0, -60, n))[:, None] * Y[1]) * cols[None, :]
+    return np.concatenate([X, Y])
 
 
 @pytest.mark.parametrize("apply_pivot", [True, False])
@@ -66,7 +72,7 @@ def test_blocked_udt_contracts(gpu, apply_pivot, batch):
     """test/slice_matrices.jl:202-234: U*Diagonal(D)*T = X (Val(true)); U*D*UpperTriangular(T)*P = X with P[i, pivot[i]] = 1"""
     n = 256
     rng = np.random.default_rng(batch)
-    X = np.concatenate([graded_cases(n, rng) for _ in range((batch + 5) // 6)])[:batch]
+    X = np.concatenate([graded_cases(n, rng) for _ in range((batch + 7) // 8)])[:batch]
     U, D, T, piv = gpu.udt_AVX_pivot(X, apply_pivot)
     for i in range(batch):
         assert relerr(U[i].T @ U[i], np.eye(n)) < 1e-12
