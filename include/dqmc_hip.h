@@ -477,7 +477,8 @@ int dqmc_binner_user_push(dqmc_handle *h, const double *device_samples);
  *                                       Gl0[b][r][.] and G0l[b][r][.]; if DENSITY: [CDC][SDCx][SDCy][SDCz], each R n_q,
  *                                       Cpart only.  E = (4 n_blocks + 4) R n_q with both parts
  * The density-type rows take the cosine only: their Wick expressions are symmetric under i <-> j, so X[d] = X[-d] in
- * every sample and the sine part is rounding noise.  The pairing and current-current sums (ps, ccs) are not transformed.
+ * every sample and the sine part is rounding noise.  The pairing and current-current sums (ps, ccs) have binners of their
+ * own: "pair structure factors and superfluid stiffness" below.
  * Memory per binner: (3 L - 1) n_walkers E doubles, as for every section: a momentum binner over n_q momenta is n_q /
  * n_dirs (Green's rows: 2 n_q / n_dirs) of the real-space one.
  * A momentum binner is pushed on the handle's stream behind the source section's kernels, whether or not the source
@@ -586,6 +587,57 @@ int dqmc_thermodynamics_size(dqmc_handle *h, size_t *n_doubles);
 int dqmc_get_thermodynamics(dqmc_handle *h, double *host_out);
 int dqmc_export_thermodynamics(dqmc_handle *h, void *device_out);
 
+/* ---- pair structure factors and superfluid stiffness: P_c(q), its susceptibility, Lambda_kk(q), the bond kinetic energy ----
+ * The reference measures the pairing sums per (direction, k1, k2) and the current-current sums per (direction, k) only
+ * and leaves the superfluid stiffness as a comment (measurements.jl:223-256).  Like the momentum binners this is a
+ * defined extension, and like them it exists for the ERROR BARS: the means are host transforms of the existing sums
+ * (dqmc.py: pair_structure_factors, pair_susceptibilities, current_response, superfluid_stiffness).
+ * dqmc_set_pair_channels(h, n_ch, F): F is [K*K x n_ch] doubles, kk = k1 + K k2 fastest (element kk + K*K c), K the K of
+ * dqmc_set_local_targets; the engine attaches no meaning to it (dqmc.py: F[kk, c] = f_c[k1] f_c[k2], f_c the weights of
+ * symmetry channel c over the local-target directions).  Needs dqmc_set_local_targets (DQMC_ERR_STATE without it).
+ * n_ch == 0 turns the channels off and frees everything (F is then ignored); 1 <= n_ch <= 8 with F non-NULL turns them
+ * on; anything else returns DQMC_ERR_INVALID and the handle keeps its setting.  A later dqmc_set_local_targets turns them
+ * off.  Every successful call frees the two pairing binners below.
+ * With Cpart / Spart the transforms of dqmc_set_momenta, per-walker samples, q fastest:
+ *   DQMC_BIN_RESPONSE_PAIRING                 fed by dqmc_accumulate_pairing: [P cos: n_ch n_q][P sin: n_ch n_q], the Cpart
+ *                                             and Spart of Z[c][d] = sum_kk F[kk, c] X[d + n_dirs kk], kk ascending, X the
+ *                                             pairing sample.  E = 2 n_ch n_q.  Needs the channels and the momenta
+ *   DQMC_BIN_RESPONSE_PAIRING_SUSCEPTIBILITY  the same of the ps part of the susceptibility sample, times delta_tau as
+ *                                             that section's binner takes it; fed by dqmc_accumulate_susceptibilities.
+ *                                             Needs dqmc_prepare as well
+ *   DQMC_BIN_RESPONSE_CURRENT                 fed by dqmc_accumulate_susceptibilities: [Lambda cos: K_cc n_q][Lambda sin:
+ *                                             K_cc n_q][kbond: K_cc]: the Cpart and Spart of the K_cc rows ccs[. + n_dirs k]
+ *                                             times delta_tau, then the bond kinetic energy of the same sample,
+ *                                               kbond[k] = (1/N) sum_src [trg >= 0] sum_sigma T_sigma[trg, src]
+ *                                                          (delta_{src,trg} - G_sigma[src, trg]),   trg = trg_of[src + n k],
+ *                                             with G the G00 of the pass and trg_of, T those of dqmc_set_current_targets;
+ *                                             the spin sum counts the attractive model's one block twice, as E_kin of
+ *                                             "thermodynamics" does.  E = 2 K_cc n_q + K_cc.  Needs dqmc_set_current_targets,
+ *                                             the momenta and dqmc_prepare
+ * Sign convention of the stiffness (fixed on free fermions, tests/response_ref.py): with k_x = kbond[+x] + kbond[-x]
+ * (negative) and C_xx(q) = the Cpart of the row k = +x as this binner holds it.  The reference's cc_kernel sums <J J> of
+ * J = T c+ c - h.c. without the factor i of the current j = i J, so ccs carries i^2 = -1: C_xx(q) <= 0, and its
+ * longitudinal limit C_xx(q_x -> 0, q_y = 0) tends to +k_x.  The current response of the stiffness formula is
+ * Lambda_xx(q) = -C_xx(q), whose longitudinal limit tends to -k_x > 0:
+ *   rho_s = (-k_x - Lambda_xx(q_x = 0, q_y -> 0)) / 4 = (-k_x + C_xx(q_x = 0, q_y -> 0)) / 4,
+ *   Drude weight = -k_x - Lambda_xx(q_x -> 0, q_y = 0) = -k_x + C_xx(q_x -> 0, q_y = 0).
+ * ccs and this binner's sample stay as cc_kernel gives them; the minus sign is the host's (dqmc.py: superfluid_stiffness).
+ * Everything else is as for the momentum binners: enabled with dqmc_binner_enable (DQMC_ERR_STATE when the momenta or the
+ * source's configuration is missing), pushed on the handle's stream behind the source's kernels whether or not the source's
+ * own binner is on, the room of every binner of a call checked before anything is accumulated, cleared by
+ * dqmc_reset_accumulators, read with dqmc_binner_size, _reliable_level, _get_level, _finish and _export_moments.
+ * dqmc_set_momenta and dqmc_set_pair_directions free all three, dqmc_set_pair_channels and dqmc_set_local_targets the two
+ * pairing ones, dqmc_set_current_targets the current one.  With sign weighting the sources are s_w x already (kbond is
+ * multiplied by s_w here), the sample gains a trailing s_w and dqmc_set_sign_weighting re-creates the binners empty.
+ * Every element is one sum in a fixed order with no atomics: a second pass gives the same bits, and a walker's sample does
+ * not depend on n_walkers.  There is no DQMC_RED_* section: with none of the three binners enabled nothing is launched and
+ * every accumulator, reduction buffer and state blob is byte for byte that of a handle that never called
+ * dqmc_set_pair_channels.  Memory per binner: (3 L - 1) n_walkers E doubles.  Checkpoint: format versions 5 - 8. */
+enum { DQMC_BIN_RESPONSE_PAIRING = 15, DQMC_BIN_RESPONSE_PAIRING_SUSCEPTIBILITY = 16, DQMC_BIN_RESPONSE_CURRENT = 17,
+       DQMC_BIN_RESPONSE_END = 18 };
+int dqmc_set_pair_channels(dqmc_handle *h, int32_t n_ch, const double *F /* [K*K x n_ch], kk fastest */);
+int dqmc_response_plan(dqmc_handle *h, int32_t out[4]);  /* [n_ch, K, K_cc, n_q], zeros where unset */
+
 /* ---- checkpoint and resume ---------------------------------------------------------------------------------------
  * save / load / resume! (FileIO.jl:38-156, DQMC.jl:463-477, 797-924) for the state that lives on the device.  Like the
  * global moves this is a defined extension of the ABI: the reference writes a JLD file from host objects; here the engine
@@ -635,7 +687,17 @@ int dqmc_export_thermodynamics(dqmc_handle *h, void *device_out);
  *     the section's n doubles     x_sum, x2_sum, compressor of the binner if enabled
  *     u64 FNV-1a 64 of all bytes of this extension in front of it
  * It is validated like the others before the first write; a version 3 / 4 blob is refused by a handle without the
- * section and a version 1 / 2 blob by a handle with it, the field named ("section thermodynamics n"). */
+ * section and a version 1 / 2 blob by a handle with it, the field named ("section thermodynamics n").
+ * Format versions 5 - 8: a handle with a response binner enabled (DQMC_BIN_RESPONSE_*) writes the version 1 - 4 blob it
+ * would write without them, its version field raised by 4, followed by a third extension; a handle with none enabled
+ * writes versions 1 - 4 unchanged, byte for byte, whether or not pair channels are set.
+ *   response extension
+ *     i32 n_ch, K, K_cc, pad     3 binners (DQMC_BIN_RESPONSE_PAIRING ..): i32 on, E, L, pad   i64 capacity, T
+ *     F: K K n_ch doubles (none while the channels are off)
+ *     x_sum, x2_sum, compressor of every enabled response binner     u64 FNV-1a 64 of all extension bytes in front of it
+ * It is validated like the others before the first write (the F table byte for byte against the handle's); a version
+ * 5 - 8 blob is refused by a handle with no response binner and a version 1 - 4 blob by a handle with one, the binner
+ * named ("binner response_pairing on"). */
 /* bytes of the blob of this handle as it is configured now */
 int dqmc_state_size(dqmc_handle *h, size_t *n_bytes);
 /* The blob into host_out (n_bytes = dqmc_state_size).  Only at the measurement point, current_slice == 1 && direction ==

@@ -20,6 +20,8 @@ BIN_SIGN, RED_SIGN = 6, 5                      # DQMC_BIN_SIGN (+ a section's DQ
 # DQMC_BIN_MOMENTUM_*: the momentum-space binners, above every other DQMC_BIN_* value
 BIN_MOMENTUM = {"momentum_correlations": 11, "momentum_susceptibilities": 12, "momentum_time_displaced": 13}
 RED_THERMODYNAMICS, BIN_THERMODYNAMICS = 6, 14  # DQMC_RED_THERMODYNAMICS, DQMC_BIN_THERMODYNAMICS
+# DQMC_BIN_RESPONSE_*: the pair-channel and current response binners, behind the thermodynamics one
+BIN_RESPONSE = {"response_pairing": 15, "response_pairing_susceptibility": 16, "response_current": 17}
 # the elements of a thermodynamics sample, in the order of include/dqmc_hip.h (DQMC_THERMO_ELEMENTS of them)
 THERMO_FIELDS = ("n_up", "n_dn", "n", "D", "m2", "E_kin", "E_int", "E", "N2", "Mz2")
 K_FAMILIES = ("gemm", "qr", "trsm", "sweep", "misc", "flush")
@@ -191,6 +193,8 @@ SIGNATURES = {
     "dqmc_binner_user_push": (C.c_int, [_H, C.c_void_p]),
     "dqmc_set_momenta": (C.c_int, [_H, C.c_int32, _dp, _dp]),
     "dqmc_momenta_plan": (C.c_int, [_H, C.POINTER(C.c_int32)]),
+    "dqmc_set_pair_channels": (C.c_int, [_H, C.c_int32, _dp]),
+    "dqmc_response_plan": (C.c_int, [_H, C.POINTER(C.c_int32)]),
     "dqmc_set_thermodynamics": (C.c_int, [_H, _dp]),
     "dqmc_accumulate_thermodynamics": (C.c_int, [_H]),
     "dqmc_thermodynamics_size": (C.c_int, [_H, C.POINTER(C.c_size_t)]),

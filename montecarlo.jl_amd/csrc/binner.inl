@@ -5,7 +5,7 @@
 static const int64_t BIN_DEFAULT_CAPACITY = 100000;  // BinningAnalysis' _default_capacity
 
 #define BIN_OK(h, which)                                                                        \
-    if ((which) < DQMC_BIN_GREENS || (which) > DQMC_BIN_THERMODYNAMICS)                         \
+    if ((which) < DQMC_BIN_GREENS || (which) >= DQMC_BIN_RESPONSE_END)                           \
         return fail((h), DQMC_ERR_INVALID, "binner section out of range");                      \
     if (!(h)->bin[(which)].on) return fail((h), DQMC_ERR_STATE, "this section's binner is not enabled")
 
@@ -135,11 +135,13 @@ static int binner_finish_device(dqmc_handle *h, int which, int32_t level)
 
 static int mom_enable(dqmc_handle *h, int which, int64_t capacity);  // momentum.inl
 static int thermo_enable(dqmc_handle *h, int64_t capacity);          // thermo.inl
+static int resp_enable(dqmc_handle *h, int which, int64_t capacity); // response.inl
 int dqmc_binner_enable(dqmc_handle *h, int32_t which, int64_t capacity)
 {
     ENTER(h);
     if (which >= DQMC_BIN_MOMENTUM_CORRELATIONS && which < DQMC_BIN_MOMENTUM_END) return mom_enable(h, which, capacity);
     if (which == DQMC_BIN_THERMODYNAMICS) return thermo_enable(h, capacity);
+    if (which >= DQMC_BIN_RESPONSE_PAIRING && which < DQMC_BIN_RESPONSE_END) return resp_enable(h, which, capacity);
     if (which < DQMC_BIN_GREENS || which == DQMC_BIN_USER || which > DQMC_BIN_TIME_DISPLACED)
         return fail(h, DQMC_ERR_INVALID, "dqmc_binner_enable takes a measurement section (dqmc_binner_user_create makes the user "
                                          "binner, the sign binners come with their sections)");

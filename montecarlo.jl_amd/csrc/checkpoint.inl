@@ -55,6 +55,21 @@ static void state_thermo(const dqmc_handle *h, dqmc_blob::Thermo *t)
     t->T_hash = h->th.T_hash; t->U_s = h->th.U_s;
 }
 
+// the response binners and what they were made for: what the extension of a version 5 - 8 blob carries.  With none of them
+// enabled it is empty (r->any() false) and the blob is version 1 - 4, channels set or not.
+static_assert(DQMC_BIN_RESPONSE_END - DQMC_BIN_RESPONSE_PAIRING == dqmc_blob::N_RESP, "the response binners: the extension of format versions 5 - 8");
+static void state_response(const dqmc_handle *h, dqmc_blob::Response *r)
+{
+    *r = dqmc_blob::Response{};
+    for (int k = 0; k < dqmc_blob::N_RESP; ++k) {
+        const dqmc_handle::Binner &b = h->bin[DQMC_BIN_RESPONSE_PAIRING + k];
+        if (b.on) r->bin[k] = {1, b.E, b.L, b.cap, b.T};
+    }
+    if (!r->any()) return;
+    r->n_ch = h->rsp.n_ch; r->K = h->rsp.n_ch ? h->K_loc : 0; r->K_cc = h->K_cc;
+    r->F = h->rsp.F_h.data();
+}
+
 // The state dqmc_update_until_measure returns in (and dqmc_sweep when it started there), rebuilt from the HS field alone: dqmc_prepare's init_stack,
 // build_stack and propagate, then the propagates of a down pass with no sweep_spatial in between, which leave the stack
 // slots and mc.s.greens as a down pass that accepted nothing leaves them, at current_slice == 1, direction == +1.
@@ -76,12 +91,14 @@ int dqmc_state_size(dqmc_handle *h, size_t *n_bytes)
     dqmc_blob::Shape s;
     dqmc_blob::Momenta m;
     dqmc_blob::Thermo th;
-    dqmc_blob::ThermoLayout tl;
+    dqmc_blob::Response rs;
+    dqmc_blob::ResponseLayout rl;
     state_shape(h, &s);
     state_momenta(h, &m);
     state_thermo(h, &th);
-    if (!dqmc_blob::thermo_layout(s, m, th, &tl)) return fail(h, DQMC_ERR_INVALID, "dqmc_state_size: the state does not fit a size_t");
-    *n_bytes = tl.total;
+    state_response(h, &rs);
+    if (!dqmc_blob::response_layout(s, m, th, rs, &rl)) return fail(h, DQMC_ERR_INVALID, "dqmc_state_size: the state does not fit a size_t");
+    *n_bytes = rl.total;
     return DQMC_OK;
 }
 
@@ -99,14 +116,18 @@ int dqmc_state_export(dqmc_handle *h, void *host_out, size_t n_bytes)
     dqmc_blob::ExtLayout e;
     dqmc_blob::Thermo th;
     dqmc_blob::ThermoLayout tl;
+    dqmc_blob::Response rs;
+    dqmc_blob::ResponseLayout rl;
     state_shape(h, &s);
     state_momenta(h, &m);
     state_thermo(h, &th);
-    if (!dqmc_blob::layout(s, &l) || !dqmc_blob::ext_layout(s, m, &e) || !dqmc_blob::thermo_layout(s, m, th, &tl))
+    state_response(h, &rs);
+    if (!dqmc_blob::layout(s, &l) || !dqmc_blob::ext_layout(s, m, &e) || !dqmc_blob::thermo_layout(s, m, th, &tl) ||
+        !dqmc_blob::response_layout(s, m, th, rs, &rl))
         return fail(h, DQMC_ERR_INVALID, "dqmc_state_export: the state does not fit a size_t");
-    if (n_bytes != tl.total)
+    if (n_bytes != rl.total)
         return fail(h, DQMC_ERR_INVALID, "dqmc_state_export: n_bytes is " + std::to_string(n_bytes) + ", dqmc_state_size reports " +
-                                             std::to_string(tl.total));
+                                             std::to_string(rl.total));
     HIPCHK(hipStreamSynchronize(h->stream));
     std::vector<WalkerRng> rg(h->W);
     HIPCHK(hipMemcpy(rg.data(), h->rng, sizeof(WalkerRng) * h->W, hipMemcpyDeviceToHost));
@@ -115,7 +136,7 @@ int dqmc_state_export(dqmc_handle *h, void *host_out, size_t n_bytes)
             return fail(h, DQMC_ERR_STATE, "dqmc_state_export: walker " + std::to_string(w) + " runs on a host-supplied uniform "
                                            "stream (dqmc_set_uniforms), which the blob does not carry");
     uint8_t *out = (uint8_t *)host_out;
-    dqmc_blob::write_header(s, m, th, out);
+    dqmc_blob::write_header(s, m, th, rs, out);
     {   // only copies from here on: nothing is launched, no buffer of the handle is written
         const size_t sz = (size_t)h->N * h->M, chunk_bytes = dqmc_blob::conf_chunks(h->N, h->M) * 8;
         std::vector<int8_t> conf((size_t)h->W * sz);
@@ -164,6 +185,18 @@ int dqmc_state_export(dqmc_handle *h, void *host_out, size_t n_bytes)
         }
         dqmc_blob::seal_thermo(tl, out);
     }
+    if (rs.any()) {  // format versions 5 - 8: the response extension
+        dqmc_blob::write_response(rs, rl, out);
+        for (int k = 0; k < dqmc_blob::N_RESP; ++k) {
+            const dqmc_handle::Binner &b = h->bin[DQMC_BIN_RESPONSE_PAIRING + k];
+            if (!b.on) continue;
+            const size_t we = (size_t)h->W * (size_t)b.E * sizeof(double);
+            HIPCHK(hipMemcpy(out + rl.bin_xs[k], b.xs, b.L * we, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(out + rl.bin_x2[k], b.x2, b.L * we, hipMemcpyDeviceToHost));
+            if (b.L > 1) HIPCHK(hipMemcpy(out + rl.bin_c[k], b.c, (b.L - 1) * we, hipMemcpyDeviceToHost));
+        }
+        dqmc_blob::seal_response(rl, out);
+    }
     return DQMC_OK;
 }
 
@@ -176,12 +209,16 @@ int dqmc_state_import(dqmc_handle *h, const void *host_in, size_t n_bytes)
     dqmc_blob::ExtLayout e;
     dqmc_blob::Thermo mine_t, th;
     dqmc_blob::ThermoLayout tl;
+    dqmc_blob::Response mine_r, rs;
+    dqmc_blob::ResponseLayout rl;
     std::string why;
     state_shape(h, &mine);
     state_momenta(h, &mine_m);
     state_thermo(h, &mine_t);
-    if (dqmc_blob::validate_all((const uint8_t *)host_in, n_bytes, mine, mine_m, mine_t, &s, &m, &th, &why) != 0 ||
-        !dqmc_blob::layout(s, &l, &why) || !dqmc_blob::ext_layout(s, m, &e, &why) || !dqmc_blob::thermo_layout(s, m, th, &tl, &why))
+    state_response(h, &mine_r);
+    if (dqmc_blob::validate_full((const uint8_t *)host_in, n_bytes, mine, mine_m, mine_t, mine_r, &s, &m, &th, &rs, &why) != 0 ||
+        !dqmc_blob::layout(s, &l, &why) || !dqmc_blob::ext_layout(s, m, &e, &why) || !dqmc_blob::thermo_layout(s, m, th, &tl, &why) ||
+        !dqmc_blob::response_layout(s, m, th, rs, &rl, &why))
         return fail(h, DQMC_ERR_INVALID, "dqmc_state_import: " + why);
     const uint8_t *in = (const uint8_t *)host_in;
     // the one index the payload carries: the site of a walker's latest global move (the next proposal overwrites it before
@@ -248,6 +285,15 @@ int dqmc_state_import(dqmc_handle *h, const void *host_in, size_t n_bytes)
             if (b.L > 1) HIPCHK(hipMemcpy(b.c, in + tl.bin_c, (b.L - 1) * we, hipMemcpyHostToDevice));
             b.T = th.bin.T;
         }
+    }
+    for (int k = 0; k < dqmc_blob::N_RESP; ++k) {  // (format versions 5 - 8; validate_full has made sure both sides have the same ones)
+        dqmc_handle::Binner &b = h->bin[DQMC_BIN_RESPONSE_PAIRING + k];
+        if (!b.on) continue;
+        const size_t we = (size_t)h->W * (size_t)b.E * sizeof(double);
+        HIPCHK(hipMemcpy(b.xs, in + rl.bin_xs[k], b.L * we, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(b.x2, in + rl.bin_x2[k], b.L * we, hipMemcpyHostToDevice));
+        if (b.L > 1) HIPCHK(hipMemcpy(b.c, in + rl.bin_c[k], (b.L - 1) * we, hipMemcpyHostToDevice));
+        b.T = rs.bin[k].T;
     }
     h->gm_updates = s.gm_updates;
     return dqmc_synchronize(h);

@@ -155,7 +155,7 @@ struct dqmc_handle {
         int E = 0, L = 0;
         int64_t cap = 0, T = 0;  // capacity and pushes so far: count[level] = T >> level for every element
         double *xs = nullptr, *x2 = nullptr, *c = nullptr, *out = nullptr;
-    } bin[DQMC_BIN_THERMODYNAMICS + 1];  // (DQMC_BIN_SIGN + k: the signs pushed with section k = a DQMC_RED_* index; then the momentum binners and the thermodynamics one)
+    } bin[DQMC_BIN_RESPONSE_END];  // (DQMC_BIN_SIGN + k: the signs pushed with section k = a DQMC_RED_* index; then the momentum binners, the thermodynamics one and the response binners)
     // momentum-space observables (momentum.inl, momentum.hip): n_q == 0: off, nothing allocated.  cos_d / sin_d
     // [n_dirs x n_q] on the device, the host copies for the checkpoint; sample[k]: the per-walker momentum sample
     // [W][E] of binner DQMC_BIN_MOMENTUM_CORRELATIONS + k, allocated with the binner
@@ -165,6 +165,15 @@ struct dqmc_handle {
         std::vector<double> cos_h, sin_h;
         double *sample[DQMC_BIN_MOMENTUM_END - DQMC_BIN_MOMENTUM_CORRELATIONS] = {nullptr, nullptr, nullptr};
     } mom;
+    // pair channels and the response binners (response.inl, response.hip): n_ch == 0: channels off.  F_d [K_loc^2 x n_ch]
+    // on the device, F_h the host copy for the checkpoint; Z [W][n_ch][n_dirs]: the contracted pairing sample, allocated
+    // while a pairing response binner is on; sample[k]: [W][E] of binner DQMC_BIN_RESPONSE_PAIRING + k
+    struct Response {
+        int n_ch = 0;
+        double *F_d = nullptr, *Z = nullptr;
+        std::vector<double> F_h;
+        double *sample[DQMC_BIN_RESPONSE_END - DQMC_BIN_RESPONSE_PAIRING] = {nullptr, nullptr, nullptr};
+    } rsp;
     // scalar thermodynamics (thermo.inl, thermo.hip): on == false: off, nothing allocated.  The hopping matrix of
     // dqmc_set_thermodynamics as a neighbour list: the off-diagonal non-zeros of row i of block b at row_ptr[b n + i] ..
     // of col / val, the diagonal in diag; T_hash: FNV-1a 64 of the matrix as it was handed in (the checkpoint compares it)
@@ -1777,6 +1786,11 @@ static int binner_push_section(dqmc_handle *h, int which);
 static int mom_push(dqmc_handle *h, int which);
 static void mom_disable(dqmc_handle *h, int which);
 static void mom_off(dqmc_handle *h);
+// response.inl: the channel contraction / bond kinetic energy, the transform and the push of a response binner;
+// resp_disable drops one binner, resp_channels_off the channel table and the two pairing binners
+static int resp_push(dqmc_handle *h, int which);
+static void resp_disable(dqmc_handle *h, int which);
+static void resp_channels_off(dqmc_handle *h);
 // global_move.inl: with sign weighting on, s_w of the current fields into sign_sw and their sum into the sign sums of the
 // sections about to be fed (DQMC_RED_* indices; sec_b < 0: one section); nothing with it off.  Runs a slice chain unless
 // the cache of the current field holds, so it comes in front of true_greens (the chain overwrites tmp1 / tmp2).
@@ -1876,6 +1890,7 @@ int dqmc_set_local_targets(dqmc_handle *h, const int32_t *trg_of, int32_t K)
     for (size_t i = 0; i < (size_t)n * K; ++i)
         if (trg_of[i] < -1 || trg_of[i] >= n) return fail(h, DQMC_ERR_INVALID, "target index out of range");
     HIPCHK(hipStreamSynchronize(h->stream));
+    resp_channels_off(h);  // the channel table belongs to the old targets
     h->K_loc = K;
     h->red_valid = false;
     dfree(h, &h->trg_of);
@@ -1891,6 +1906,7 @@ int dqmc_accumulate_pairing(dqmc_handle *h)
     ENTER(h); NEED_PREPARED(h);
     if (!h->K_loc) return fail(h, DQMC_ERR_STATE, "call dqmc_set_local_targets first");
     CHK(binner_room(h, DQMC_BIN_PAIRING));
+    CHK(binner_room(h, DQMC_BIN_RESPONSE_PAIRING));
     CHK(sign_begin(h, DQMC_RED_PAIRING));
     CHK(true_greens(h, h->greens));
     if (h->sign_on) {
@@ -1906,6 +1922,7 @@ int dqmc_accumulate_pairing(dqmc_handle *h)
                               h->stream));
     }
     if (h->bin[DQMC_BIN_PAIRING].on) CHK(binner_push_section(h, DQMC_BIN_PAIRING));
+    if (h->bin[DQMC_BIN_RESPONSE_PAIRING].on) CHK(resp_push(h, DQMC_BIN_RESPONSE_PAIRING));
     return DQMC_OK;
 }
 int dqmc_reset_accumulators(dqmc_handle *h)
@@ -1959,6 +1976,7 @@ int dqmc_export_pairing(dqmc_handle *h, void *device_out) { ENTER(h); return sec
 #include "momentum.inl"
 #include "global_move.inl"
 #include "thermo.inl"
+#include "response.inl"
 #include "checkpoint.inl"
 
 // ---------------------------------------------------------------------------

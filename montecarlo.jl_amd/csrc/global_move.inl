@@ -140,7 +140,7 @@ int dqmc_set_sign_weighting(dqmc_handle *h, int32_t on)
     for (int which = DQMC_BIN_GREENS; which <= DQMC_BIN_TIME_DISPLACED; ++which)
         if (which != DQMC_BIN_USER && h->bin[which].on && h->bin[which].T)
             return fail(h, DQMC_ERR_STATE, "dqmc_set_sign_weighting: a binner has samples: call dqmc_reset_accumulators first");
-    for (int which = DQMC_BIN_MOMENTUM_CORRELATIONS; which <= DQMC_BIN_THERMODYNAMICS; ++which)
+    for (int which = DQMC_BIN_MOMENTUM_CORRELATIONS; which < DQMC_BIN_RESPONSE_END; ++which)
         if (h->bin[which].on && h->bin[which].T)
             return fail(h, DQMC_ERR_STATE, "dqmc_set_sign_weighting: a binner has samples: call dqmc_reset_accumulators first");
     h->sign_on = on != 0;
@@ -158,6 +158,8 @@ int dqmc_set_sign_weighting(dqmc_handle *h, int32_t on)
     for (int which = DQMC_BIN_MOMENTUM_CORRELATIONS; which < DQMC_BIN_MOMENTUM_END; ++which)
         if (h->bin[which].on) CHK(mom_enable(h, which, h->bin[which].cap));
     if (h->bin[DQMC_BIN_THERMODYNAMICS].on) CHK(thermo_enable(h, h->bin[DQMC_BIN_THERMODYNAMICS].cap));  // and so does this one
+    for (int which = DQMC_BIN_RESPONSE_PAIRING; which < DQMC_BIN_RESPONSE_END; ++which)  // and the response samples
+        if (h->bin[which].on) CHK(resp_enable(h, which, h->bin[which].cap));
     return dqmc_synchronize(h);
 }
 int dqmc_get_sign_weighting(dqmc_handle *h, int32_t *on)

@@ -511,6 +511,16 @@ constexpr int DQMC_THERMO_ELEMENTS_K = 10;
 hipError_t launch_thermodynamics(int n, int nb, int n_walkers, const double *G, long stride_unit, const int *row_ptr,
                                  const int *col, const double *val, const double *tdiag, double U_s, double *per_walker,
                                  long per_stride, const double *sw, double *acc, hipStream_t s);
+// response.hip: the symmetry-channel contraction of every walker's pairing sample, in front of launch_momentum:
+//   Z[w z_stride + c n_dirs + d] = sum_kk F[kk + KK c] X[w x_stride + x_off + d + n_dirs kk],  kk ascending, c < n_ch <= 8
+hipError_t launch_pair_channels(int n_dirs, int KK, int n_ch, int n_walkers, const double *X, long x_stride, long x_off,
+                                const double *F, double *Z, long z_stride, hipStream_t s);
+// and the bond kinetic energy of the current-target columns from the true G of every unit (G + (w nb + b) stride_unit):
+//   out[w out_stride + out_off + k] = (fac / n) sum_src [trg >= 0] sum_b tts[b n K + src + n k] (delta_{src,trg} - G_b[src + n trg]),
+// trg = trg_of[src + n k], tts = T_b[trg, src] as cc_setup stores it; sw: nullptr, or sign.hip's s_w, then out is s_w x
+hipError_t launch_bond_kinetic(int n, int nb, int K, int n_walkers, double fac, const double *G, long stride_unit,
+                               const int *trg_of, const double *tts, const double *sw, double *out, long out_stride,
+                               long out_off, hipStream_t s);
 // HS field <-> Julia BitArray chunks (compress / decompress, HubbardModel.jl:56-59)
 hipError_t launch_conf_pack(const int8_t *conf, size_t n_elem, unsigned long long *chunks, hipStream_t s);
 hipError_t launch_conf_unpack(const unsigned long long *chunks, size_t n_elem, int8_t *conf, hipStream_t s);

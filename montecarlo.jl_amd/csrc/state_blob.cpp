@@ -12,6 +12,7 @@ const char *const BIN_NAME[N_BIN] = {"greens", "correlations", "pairing", "susce
                                      "sign:greens", "sign:correlations", "sign:pairing", "sign:susceptibilities",
                                      "sign:time_displaced"};
 const char *const MOM_NAME[N_MOM] = {"momentum_correlations", "momentum_susceptibilities", "momentum_time_displaced"};
+const char *const RESP_NAME[N_RESP] = {"response_pairing", "response_pairing_susceptibility", "response_current"};
 
 void put(uint8_t *&p, uint64_t v, int bytes)
 {
@@ -45,6 +46,7 @@ uint64_t fnv1a(const uint8_t *p, size_t n)
 enum { HEADER_BYTES = 8 + 4 + 4 + HASH_BYTES + 6 * 4 + 2 * 8 + 2 * N_SEC * 8 + N_BIN * 32 + 6 * 4 + 8 + 8 };
 enum { EXT_FIXED_BYTES = 2 * 4 + N_MOM * 32 };
 enum { THERMO_FIXED_BYTES = 2 * 8 + 32 + 8 + 8 };
+enum { RESPONSE_FIXED_BYTES = 4 * 4 + N_RESP * 32 };
 
 bool mul(size_t a, size_t b, size_t *out) { return !__builtin_mul_overflow(a, b, out); }
 bool add(size_t a, size_t b, size_t *out) { return !__builtin_add_overflow(a, b, out); }
@@ -307,12 +309,15 @@ static int validate_core(const uint8_t *buf, size_t n_bytes, const Shape &h, con
     uint32_t version = 0;
     size_t total = 0;
     if (validate_head(buf, n_bytes, h, newest, &s, &version, &total, why) != 0) return -1;
-    const bool tail = version >= VERSION_THERMO;
-    const char *const fmt = version == VERSION ? "1" : "3";
+    // (a version above 4 is the version below it by 4 with the response extension behind everything else)
+    const bool more = version > VERSION_THERMO_MOMENTA;
+    const uint32_t base = more ? version - VERSION_RESPONSE_STEP : version;
+    const bool tail = base >= VERSION_THERMO || more;
+    const std::string fmt = std::to_string(version);
     Momenta m{};
     *version_out = version;
     *end = total;
-    if (version == VERSION || version == VERSION_THERMO) {
+    if (base == VERSION || base == VERSION_THERMO) {
         if (tail ? n_bytes < total : n_bytes != total) return refuse_size(why, n_bytes, total);
         for (int k = 0; k < N_MOM; ++k)
             if (hm.bin[k].on)
@@ -444,16 +449,22 @@ void seal_thermo(const ThermoLayout &l, uint8_t *blob)
     put(p, fnv1a(blob + l.start, l.checksum - l.start), 8);
 }
 
-int validate_all(const uint8_t *buf, size_t n_bytes, const Shape &h, const Momenta &hm, const Thermo &ht, Shape *blob,
-                 Momenta *mblob, Thermo *tblob, std::string *why)
+// validate_all for the blob's version 1 - 4 part.  newest: the highest format version the caller reads; with a version
+// above 4 more bytes may follow that part, whose size goes to *end
+static int validate_front(const uint8_t *buf, size_t n_bytes, const Shape &h, const Momenta &hm, const Thermo &ht, uint32_t newest,
+                          Shape *blob, Momenta *mblob, Thermo *tblob, uint32_t *version_out, size_t *end_out, std::string *why)
 {
     Shape s{};
     Momenta m{};
     Thermo t{};
     uint32_t version = 0;
     size_t end = 0;
-    if (validate_core(buf, n_bytes, h, hm, VERSION_THERMO_MOMENTA, &s, &m, &version, &end, why) != 0) return -1;
-    if (version < VERSION_THERMO) {
+    if (validate_core(buf, n_bytes, h, hm, newest, &s, &m, &version, &end, why) != 0) return -1;
+    const bool more = version > VERSION_THERMO_MOMENTA;
+    const uint32_t base = more ? version - VERSION_RESPONSE_STEP : version;
+    *version_out = version;
+    *end_out = end;
+    if (base < VERSION_THERMO) {
         if (ht.any())
             return refuse(why, "section thermodynamics n: the blob (format version " + std::to_string(version) + ") has 0, the handle " +
                                    std::to_string(ht.n));
@@ -475,7 +486,8 @@ int validate_all(const uint8_t *buf, size_t n_bytes, const Shape &h, const Momen
         ThermoLayout l;
         std::string lw;
         if (!thermo_layout(s, m, t, &l, &lw)) return refuse(why, lw + ": not a shape a handle can have");
-        if (n_bytes != l.total) return refuse_size(why, n_bytes, l.total);
+        if (more ? n_bytes < l.total : n_bytes != l.total) return refuse_size(why, n_bytes, l.total);
+        *end_out = l.total;
         const uint8_t *sum_at = buf + l.checksum;
         if (get(sum_at, 8) != fnv1a(buf + l.start, l.checksum - l.start))
             return refuse(why, "thermodynamics extension checksum: the extension is damaged");
@@ -498,6 +510,159 @@ int validate_all(const uint8_t *buf, size_t n_bytes, const Shape &h, const Momen
     if (blob) *blob = s;
     if (mblob) *mblob = m;
     if (tblob) *tblob = t;
+    return 0;
+}
+int validate_all(const uint8_t *buf, size_t n_bytes, const Shape &h, const Momenta &hm, const Thermo &ht, Shape *blob,
+                 Momenta *mblob, Thermo *tblob, std::string *why)
+{
+    uint32_t version = 0;
+    size_t end = 0;
+    return validate_front(buf, n_bytes, h, hm, ht, VERSION_THERMO_MOMENTA, blob, mblob, tblob, &version, &end, why);
+}
+
+bool response_layout(const Shape &s, const Momenta &m, const Thermo &t, const Response &r, ResponseLayout *out, std::string *why)
+{
+    auto bad = [&](const char *what) {
+        if (why) *why = what;
+        return false;
+    };
+    ThermoLayout tl;
+    if (!thermo_layout(s, m, t, &tl, why)) return false;
+    ResponseLayout l{};
+    l.start = l.total = tl.total;
+    if (!r.any()) {
+        if (out) *out = l;
+        return true;
+    }
+    if (r.n_ch < 0 || r.n_ch > 8 || r.K < 0 || r.K_cc < 0 || (r.n_ch > 0 && r.K < 1)) return bad("response n_ch, K, K_cc");
+    const size_t W = (size_t)s.n_walkers;
+    size_t off = l.start, skip, tab;
+    bool ok = take(&off, &skip, RESPONSE_FIXED_BYTES, 1) && mul((size_t)r.K, (size_t)r.K, &tab) && mul(tab, (size_t)r.n_ch, &tab);
+    ok = ok && take(&off, &l.F, tab, 8);
+    for (int k = 0; k < N_RESP && ok; ++k) {
+        const Shape::Bin &b = r.bin[k];
+        l.bin_xs[k] = l.bin_x2[k] = l.bin_c[k] = off;
+        if (!b.on) continue;
+        if (b.E < 1 || b.L < 1 || b.L > 41) return bad("response binner elements / levels");
+        size_t we;
+        ok = mul(W, (size_t)b.E, &we) && mul(we, 8, &we);
+        ok = ok && take(&off, &l.bin_xs[k], (size_t)b.L, we);
+        ok = ok && take(&off, &l.bin_x2[k], (size_t)b.L, we);
+        ok = ok && take(&off, &l.bin_c[k], (size_t)b.L - 1, we);
+    }
+    ok = ok && take(&off, &l.checksum, 1, 8);
+    if (!ok) return bad("blob size overflows");
+    l.total = off;
+    if (out) *out = l;
+    return true;
+}
+
+void write_header(const Shape &s, const Momenta &m, const Thermo &t, const Response &r, uint8_t *out)
+{
+    if (!r.any()) write_header(s, m, t, out);
+    else write_header_version(s, (t.any() ? (m.any() ? VERSION_THERMO_MOMENTA : VERSION_THERMO) : (m.any() ? VERSION_MOMENTA : VERSION)) +
+                                     VERSION_RESPONSE_STEP, out);
+}
+
+void write_response(const Response &r, const ResponseLayout &l, uint8_t *blob)
+{
+    if (!r.any()) return;
+    uint8_t *p = blob + l.start;
+    put(p, (uint32_t)r.n_ch, 4);
+    put(p, (uint32_t)r.K, 4);
+    put(p, (uint32_t)r.K_cc, 4);
+    put(p, 0, 4);
+    for (int k = 0; k < N_RESP; ++k) {
+        const Shape::Bin &b = r.bin[k];
+        put(p, (uint32_t)b.on, 4);
+        put(p, (uint32_t)b.E, 4);
+        put(p, (uint32_t)b.L, 4);
+        put(p, 0, 4);
+        put(p, (uint64_t)b.cap, 8);
+        put(p, (uint64_t)b.T, 8);
+    }
+    const size_t tab = (size_t)r.K * (size_t)r.K * (size_t)r.n_ch;
+    for (size_t i = 0; i < tab; ++i) put(p, bits_of(r.F[i]), 8);
+}
+
+void seal_response(const ResponseLayout &l, uint8_t *blob)
+{
+    if (l.total == l.start) return;
+    uint8_t *p = blob + l.checksum;
+    put(p, fnv1a(blob + l.start, l.checksum - l.start), 8);
+}
+
+int validate_full(const uint8_t *buf, size_t n_bytes, const Shape &h, const Momenta &hm, const Thermo &ht, const Response &hr,
+                  Shape *blob, Momenta *mblob, Thermo *tblob, Response *rblob, std::string *why)
+{
+    Shape s{};
+    Momenta m{};
+    Thermo t{};
+    Response r{};
+    uint32_t version = 0;
+    size_t end = 0;
+    if (validate_front(buf, n_bytes, h, hm, ht, VERSION_THERMO_MOMENTA + VERSION_RESPONSE_STEP, &s, &m, &t, &version, &end, why) != 0)
+        return -1;
+    if (version <= VERSION_THERMO_MOMENTA) {
+        for (int k = 0; k < N_RESP; ++k)
+            if (hr.bin[k].on)
+                return refuse(why, std::string("binner ") + RESP_NAME[k] + " on: the blob (format version " + std::to_string(version) +
+                                       ") has 0, the handle 1");
+    } else {
+        if (n_bytes < end || n_bytes - end < RESPONSE_FIXED_BYTES) return refuse_size(why, n_bytes, end + RESPONSE_FIXED_BYTES);
+        const uint8_t *p = buf + end;
+        r.n_ch = (int32_t)(uint32_t)get(p, 4);
+        r.K = (int32_t)(uint32_t)get(p, 4);
+        r.K_cc = (int32_t)(uint32_t)get(p, 4);
+        (void)get(p, 4);
+        for (int k = 0; k < N_RESP; ++k) {
+            Shape::Bin &b = r.bin[k];
+            b.on = (int32_t)(uint32_t)get(p, 4);
+            b.E = (int32_t)(uint32_t)get(p, 4);
+            b.L = (int32_t)(uint32_t)get(p, 4);
+            (void)get(p, 4);
+            b.cap = (int64_t)get(p, 8);
+            b.T = (int64_t)get(p, 8);
+            if (b.on != 0 && b.on != 1) return refuse(why, std::string("binner ") + RESP_NAME[k] + " on: neither 0 nor 1");
+        }
+        if (!r.any()) return refuse(why, "extension: a format version " + std::to_string(version) + " blob with no response binner in it");
+        ResponseLayout l;
+        std::string lw;
+        if (!response_layout(s, m, t, r, &l, &lw)) return refuse(why, lw + ": not a shape a handle can have");
+        if (n_bytes != l.total) return refuse_size(why, n_bytes, l.total);
+        const uint8_t *sum_at = buf + l.checksum;
+        if (get(sum_at, 8) != fnv1a(buf + l.start, l.checksum - l.start))
+            return refuse(why, "response extension checksum: the extension is damaged");
+#define SAME_R(field, name)                                                                                           \
+    if (!(r.field == hr.field))                                                                                       \
+        return refuse(why, std::string(name) + ": the blob has " + std::to_string(r.field) + ", the handle " +        \
+                               std::to_string(hr.field))
+        for (int k = 0; k < N_RESP; ++k) SAME_R(bin[k].on, std::string("binner ") + RESP_NAME[k] + " on");  // (which binners, first)
+        SAME_R(n_ch, "response n_ch");
+        SAME_R(K, "response K");
+        SAME_R(K_cc, "response K_cc");
+        for (int k = 0; k < N_RESP; ++k) {
+            SAME_R(bin[k].on, std::string("binner ") + RESP_NAME[k] + " on");
+            SAME_R(bin[k].E, std::string("binner ") + RESP_NAME[k] + " E");
+            SAME_R(bin[k].L, std::string("binner ") + RESP_NAME[k] + " L");
+            SAME_R(bin[k].cap, std::string("binner ") + RESP_NAME[k] + " cap");
+        }
+#undef SAME_R
+        const size_t tab = (size_t)r.K * (size_t)r.K * (size_t)r.n_ch;
+        if (tab && !hr.F) return refuse(why, "response F: the handle has none");
+        const uint8_t *f = buf + l.F;
+        for (size_t i = 0; i < tab; ++i)
+            if (get(f, 8) != bits_of(hr.F[i])) return refuse(why, "response F: entry " + std::to_string(i) + " differs from the handle's");
+        for (int k = 0; k < N_RESP; ++k) {
+            const Shape::Bin &b = r.bin[k];
+            if (b.T < 0 || b.T > (b.on ? b.cap : 0))
+                return refuse(why, std::string("binner ") + RESP_NAME[k] + " T: " + std::to_string(b.T) + " pushes outside 0 .. capacity");
+        }
+    }
+    if (blob) *blob = s;
+    if (mblob) *mblob = m;
+    if (tblob) *tblob = t;
+    if (rblob) *rblob = r;
     return 0;
 }
 

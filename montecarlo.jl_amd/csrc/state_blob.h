@@ -128,6 +128,39 @@ void seal_thermo(const ThermoLayout &l, uint8_t *blob);
 int validate_all(const uint8_t *buf, size_t n_bytes, const Shape &handle, const Momenta &hm, const Thermo &ht, Shape *blob,
                  Momenta *mblob, Thermo *tblob, std::string *why);
 
+// ---- format versions 5 - 8: the version 1 - 4 blob, its version field raised by 4, then an extension for the response
+// binners (DQMC_BIN_RESPONSE_*).  A handle with none of them enabled writes versions 1 - 4 unchanged.
+//   i32 n_ch, K, K_cc, pad   N_RESP x (i32 on, E, L, pad, i64 cap, T)   F [K K n_ch doubles]
+//   xs, x2, c of every enabled response binner   u64 FNV-1a 64 of every extension byte in front of it
+enum { N_RESP = 3 };  // DQMC_BIN_RESPONSE_PAIRING, _PAIRING_SUSCEPTIBILITY, _CURRENT
+static const uint32_t VERSION_RESPONSE_STEP = 4;  // version = the version without the binners + 4
+struct Response {
+    int32_t n_ch = 0, K = 0, K_cc = 0;
+    const double *F = nullptr;  // K K n_ch doubles, borrowed (nullptr in what validate_full hands back)
+    Shape::Bin bin[N_RESP] = {};
+    bool any() const { return bin[0].on || bin[1].on || bin[2].on; }  // false: the blob is version 1 - 4
+};
+// byte offsets from the start of the blob; with !r.any() only `start` and `total` are set, both to the version 1 - 4 size
+struct ResponseLayout {
+    size_t start, F;
+    size_t bin_xs[N_RESP], bin_x2[N_RESP], bin_c[N_RESP];
+    size_t checksum, total;
+};
+bool response_layout(const Shape &s, const Momenta &m, const Thermo &t, const Response &r, ResponseLayout *out,
+                     std::string *why = nullptr);
+// write_header with the version the four call for (r.any(): 5 - 8, else as write_header(s, m, t, out))
+void write_header(const Shape &s, const Momenta &m, const Thermo &t, const Response &r, uint8_t *out);
+// the extension's fixed fields and F into blob + l.start (nothing when !r.any()); seal_response once the binner arrays are in place
+void write_response(const Response &r, const ResponseLayout &l, uint8_t *blob);
+void seal_response(const ResponseLayout &l, uint8_t *blob);
+// validate_all for all eight versions.  Versions 1 - 4: as validate_all, and refused when the handle has a response binner
+// enabled.  Versions 5 - 8: the version 1 - 4 part as there, then this extension: n_bytes holds its fixed fields; its shape
+// is one a handle can have; n_bytes against the size it implies; its checksum; n_ch, K, K_cc and every binner's on / E / L /
+// cap against `hr` (the first that differs is named); F byte for byte against hr's; the ranges of T.  0 and *blob / *mblob
+// / *tblob / *rblob filled, or -1 and *why.
+int validate_full(const uint8_t *buf, size_t n_bytes, const Shape &handle, const Momenta &hm, const Thermo &ht,
+                  const Response &hr, Shape *blob, Momenta *mblob, Thermo *tblob, Response *rblob, std::string *why);
+
 // compress / decompress of one walker's field (HubbardModel.jl:56-59): element i of conf (+1 / -1) in bit i % 64 of chunk i / 64
 void pack_conf(const int8_t *conf, size_t n, uint8_t *chunks_le);
 void unpack_conf(const uint8_t *chunks_le, size_t n, int8_t *conf);

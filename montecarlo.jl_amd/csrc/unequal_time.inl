@@ -683,6 +683,8 @@ int dqmc_set_current_targets(dqmc_handle *h, const int32_t *trg_of, int32_t K, c
     if (!trg_of || !T || K < 1 || K > h->n_dirs) return fail(h, DQMC_ERR_INVALID, "bad target table or hopping matrix");
     for (size_t i = 0; i < (size_t)n * K; ++i)
         if (trg_of[i] < -1 || trg_of[i] >= n) return fail(h, DQMC_ERR_INVALID, "target index out of range");
+    HIPCHK(hipStreamSynchronize(h->stream));
+    resp_disable(h, DQMC_BIN_RESPONSE_CURRENT);  // its rows follow the targets: the caller enables it again
     h->cc_trg_h.assign(trg_of, trg_of + (size_t)n * K);
     h->cc_T.assign(T, T + (size_t)h->nb * n * n);
     h->K_cc = K;
@@ -823,6 +825,8 @@ int dqmc_accumulate_susceptibilities(dqmc_handle *h, int32_t recalculate)
     CHK(ut_sus_layout(h));
     CHK(binner_room(h, DQMC_BIN_SUSCEPTIBILITIES));
     CHK(binner_room(h, DQMC_BIN_MOMENTUM_SUSCEPTIBILITIES));
+    CHK(binner_room(h, DQMC_BIN_RESPONSE_PAIRING_SUSCEPTIBILITY));
+    CHK(binner_room(h, DQMC_BIN_RESPONSE_CURRENT));
     const bool record = h->td.every != 0;
     if (record) CHK(binner_room(h, DQMC_BIN_TIME_DISPLACED));
     if (record) CHK(binner_room(h, DQMC_BIN_MOMENTUM_TIME_DISPLACED));
@@ -877,6 +881,8 @@ int dqmc_accumulate_susceptibilities(dqmc_handle *h, int32_t recalculate)
     if (record && h->bin[DQMC_BIN_TIME_DISPLACED].on) CHK(binner_push_section(h, DQMC_BIN_TIME_DISPLACED));
     if (h->bin[DQMC_BIN_MOMENTUM_SUSCEPTIBILITIES].on) CHK(mom_push(h, DQMC_BIN_MOMENTUM_SUSCEPTIBILITIES));
     if (record && h->bin[DQMC_BIN_MOMENTUM_TIME_DISPLACED].on) CHK(mom_push(h, DQMC_BIN_MOMENTUM_TIME_DISPLACED));
+    if (h->bin[DQMC_BIN_RESPONSE_PAIRING_SUSCEPTIBILITY].on) CHK(resp_push(h, DQMC_BIN_RESPONSE_PAIRING_SUSCEPTIBILITY));
+    if (h->bin[DQMC_BIN_RESPONSE_CURRENT].on) CHK(resp_push(h, DQMC_BIN_RESPONSE_CURRENT));
     return dqmc_synchronize(h);
 }
 int dqmc_susceptibilities_size(dqmc_handle *h, size_t *n)

@@ -249,6 +249,7 @@ class DQMC:
         self._gm_set = None       # (rate, kind) of the last set_global_rate
         self._sus_layout = False  # the susceptibility section is laid out (by its first use)
         self._thermo = False      # set_thermodynamics is on
+        self._channels = None     # {name: weights} of set_pair_channels
         self._mid_sweep = False  # set by load(): run() finishes the sweep the checkpoint was taken in
         if int(global_rate) < 1:
             raise ValueError("global_rate must be at least 1")
@@ -545,6 +546,8 @@ class DQMC:
             if name == "current_targets":
                 tables[name]["hopping"] = entry[2]
         extra = {"thermodynamics": self._thermo} if self._thermo else {}  # (absent while off: the preamble of before)
+        if self._channels is not None:  # the names and weights of set_pair_channels (absent while off as well)
+            extra["pair_channels"] = [[k, [float(x) for x in v]] for k, v in self._channels.items()]  # (a list: the order is the engine's)
         return {
             **extra,
             "format": 1,
@@ -602,6 +605,11 @@ class DQMC:
             t = pre["tables"]
             if "pair_directions" in t:
                 mc._set_pair_directions(_ckpt.unpack_table(t["pair_directions"]["table"]), t["pair_directions"]["count"])
+                # the displacements r_d are not in the file: where the saved table is the lattice's own, they are those of
+                # its EachSitePairByDistance (what set_pair_channels("default") and superfluid_stiffness read)
+                it = _lat.EachSitePairByDistance(l)
+                if it.ndirections() == mc._ndirs and np.array_equal(np.asarray(it.dir_of), mc._tables["pair_directions"][0]):
+                    mc._dirs = np.array(it.directions, dtype=np.float64)
             if "local_targets" in t:
                 mc._set_local_targets(_ckpt.unpack_table(t["local_targets"]["table"]), t["local_targets"]["count"])
             if "current_targets" in t:
@@ -624,6 +632,8 @@ class DQMC:
                     hop = [np.asarray(hop[b * mc.N * mc.N:(b + 1) * mc.N * mc.N]).reshape((mc.N, mc.N), order="F")
                            for b in range(mc.nb)]
                 mc.set_thermodynamics(True, hopping=None if hop is True else hop)
+            if pre.get("pair_channels"):
+                mc.set_pair_channels({k: v for k, v in pre["pair_channels"]})
             mc.prepare()  # (the susceptibility layout and two of the binners need a prepared handle)
             if pre["susceptibilities_layout"]:
                 mc._section_size("susceptibilities")
@@ -954,6 +964,8 @@ class DQMC:
             return _lib.BIN_MOMENTUM[which]
         if which == "thermodynamics":
             return _lib.BIN_THERMODYNAMICS
+        if which in _lib.BIN_RESPONSE:
+            return _lib.BIN_RESPONSE[which]
         if which not in _lib.BIN_SECTIONS:
             raise ValueError("unknown binner section %r" % (which,))
         return _lib.BIN_SECTIONS.index(which)
@@ -977,7 +989,7 @@ class DQMC:
             self._c(lib().dqmc_binner_enable(self._h, self._bin(m), cap))
             self._binned = getattr(self, "_binned", set()) | {m}
             self._bin_caps[m] = cap
-            if m == "susceptibilities":  # (its binner lays the section out)
+            if m in ("susceptibilities", "response_pairing_susceptibility", "response_current"):  # (its binner lays the section out)
                 self._sus_layout = True
 
     def _binning_enabled(self, which):
@@ -1113,6 +1125,8 @@ class DQMC:
         error, independent of the binning) and X_tau; plus count (samples per walker) and reliable_level."""
         if which in _lib.BIN_MOMENTUM or which == "thermodynamics":
             return self._binned_momentum(which, level)
+        if which in _lib.BIN_RESPONSE:
+            return self._binned_response(which, level)
         raw = self.binned_raw(which, level)
         res = self._bin_dict(which, raw)
         if which == "time_displaced":
@@ -1186,6 +1200,9 @@ class DQMC:
     def _set_local_targets(self, trg_of, K):
         tab = np.asfortranarray(np.asarray(trg_of).astype(np.int32))  # [src, k] -> trg_of[src + n*k]
         self._K = int(K)
+        self._channels = None  # (the engine turns the pair channels off with the old targets)
+        for k in ("response_pairing", "response_pairing_susceptibility"):
+            self._binner_dropped(k)
         self._c(lib().dqmc_set_local_targets(self._h, tab.ctypes.data_as(C.POINTER(C.c_int32)), self._K))
         self._tables["local_targets"] = (np.array(tab, dtype=np.int32), self._K)
 
@@ -1326,7 +1343,7 @@ class DQMC:
 
     def _momenta_dropped(self):
         self._mom = None
-        for k in _lib.BIN_MOMENTUM:
+        for k in tuple(_lib.BIN_MOMENTUM) + tuple(_lib.BIN_RESPONSE):  # (the response binners use the tables)
             self._binner_dropped(k)
 
     def set_momenta(self, qs="all", iterator=None):
@@ -1466,6 +1483,227 @@ class DQMC:
         res["reliable_level"] = raw["reliable_level"]
         return res
 
+    # ---- pair structure factors and superfluid stiffness (include/dqmc_hip.h; the reference has no such measurement)
+    def set_pair_channels(self, channels="default"):
+        """the symmetry channels of the pair structure factors: a dict name -> weights f[k], k < K, over the directions
+        of set_local_targets (k = 0 is on-site), at most 8 of them; F[kk, c] = f_c[k1] f_c[k2] goes to the engine.
+        "default" (lattices.default_pair_channels): s = e_0 and s* = 1/2 on every nearest neighbour on every lattice (no
+        1/sqrt(z): the square lattice's weights are kept as they are elsewhere), and on a SquareLattice d = +1/2 on the
+        +-x bonds and -1/2 on the +-y bonds, the sign read from the iterator's directions.  None or {} turns the channels
+        off.  Needs set_local_targets(iterator); frees the two pairing response binners."""
+        from .lattices import default_pair_channels
+
+        def dropped():  # (only once the engine has taken the call: a refused one keeps the setting and the binners)
+            for k in ("response_pairing", "response_pairing_susceptibility"):
+                self._binner_dropped(k)
+        if channels is None or (not isinstance(channels, str) and len(channels) == 0):
+            self._c(lib().dqmc_set_pair_channels(self._h, 0, None))
+            dropped()
+            self._channels = None
+            return
+        K = getattr(self, "_K", 0)
+        if not K:
+            raise _lib.DQMCError(_lib.ERR_STATE, "set_pair_channels: call set_local_targets first")
+        if isinstance(channels, str):
+            if channels != "default":
+                raise ValueError("channels must be 'default' or a dict name -> weights")
+            if self._dirs is None:
+                raise _lib.DQMCError(_lib.ERR_STATE, "set_pair_channels('default'): set_local_targets(iterator) first")
+            channels = default_pair_channels(self.model.l, self._dirs, K)
+        if len(channels) > 8:
+            raise ValueError("at most 8 pair channels")
+        ch = {}
+        for name, f in channels.items():
+            f = np.asarray(f, dtype=np.float64)
+            if f.shape != (K,) or not np.all(np.isfinite(f)):
+                raise ValueError("channel %r must hold K = %d finite weights" % (name, K))
+            ch[str(name)] = f
+        F = np.ascontiguousarray(np.concatenate([np.outer(f, f).reshape(-1, order="F") for f in ch.values()]))
+        self._c(lib().dqmc_set_pair_channels(self._h, len(ch), dptr(F)))
+        dropped()
+        self._channels = ch
+
+    def pair_channels(self):
+        """-> {name: weights [K]} of set_pair_channels, or None"""
+        ch = getattr(self, "_channels", None)
+        return None if ch is None else {k: v.copy() for k, v in ch.items()}
+
+    def response_plan(self):
+        """-> dict(n_ch, K, K_cc, n_q) of the engine, zeros where unset"""
+        out = (C.c_int32 * 4)()
+        self._c(lib().dqmc_response_plan(self._h, out))
+        return dict(zip(("n_ch", "K", "K_cc", "n_q"), (int(v) for v in out)))
+
+    def _channel_names(self):
+        ch = getattr(self, "_channels", None)
+        if ch is None:
+            raise _lib.DQMCError(_lib.ERR_STATE, "call set_pair_channels first")
+        return list(ch)
+
+    def _pair_transform(self, X):
+        """X[dir12, k1, k2] -> {name: sum_d e^{-i q . r_d} sum_{k1 k2} f[k1] f[k2] X[d, k1, k2]}"""
+        Ct, St = self._phase_tables()
+        res = {}
+        for name, f in self._channels.items():
+            z = np.einsum("dab,a,b->d", X, f, f)
+            res[name] = z @ Ct - 1j * (z @ St)
+        return res
+
+    def pair_structure_factors(self):
+        """-> {channel: P_c(q) complex [n_q]} and count: the host transform of the pairing mean (of signed("pairing")
+        with sign weighting on), P_c(q) = sum_d e^{-i q . r_d} sum_{k1 k2} f_c[k1] f_c[k2] PC[d, k1, k2]"""
+        self._channel_names()
+        if self.sign_weighting():
+            m = self.signed("pairing")
+            X, cnt = m["PC"], m["count"]
+        else:
+            X, cnt = self.pairing()
+        res = self._pair_transform(X)
+        res["count"] = cnt
+        return res
+
+    def pair_susceptibilities(self):
+        """-> {channel: complex [n_q]} and count: the same transform of the mean PS of susceptibilities()"""
+        self._channel_names()
+        m = self._means("susceptibilities")
+        if "PS" not in m:
+            raise _lib.DQMCError(_lib.ERR_STATE, "the susceptibility section has no pairing part: set_local_targets first")
+        res = self._pair_transform(m["PS"])
+        res["count"] = m["count"]
+        return res
+
+    def _kbond(self, G):
+        """the bond kinetic energy of the current-target columns from Green's blocks G (include/dqmc_hip.h)"""
+        trg, K = self._tables["current_targets"][0], self._Kcc
+        N, fac = self.N, (2.0 if self.nb == 1 else 1.0)
+        out = np.zeros(K)
+        for k in range(K):
+            src = np.nonzero(trg[:, k] >= 0)[0]
+            t = trg[src, k]
+            for b in range(self.nb):
+                T = self._cc_T[b * N * N:(b + 1) * N * N].reshape((N, N), order="F")
+                out[k] += fac * np.sum(T[t, src] * ((src == t) - G[b][src, t])) / N
+        return out
+
+    def current_response(self):
+        """-> dict(Lambda complex [K_cc, n_q], count, and kbond [K_cc] if greens was accumulated): Lambda[k, q] =
+        sum_d e^{-i q . r_d} CCS[d, k] of the mean CCS of susceptibilities() (the engine's sums as they are: see
+        superfluid_stiffness for the sign); kbond is linear in G and comes from the mean G of the greens accumulator."""
+        if not getattr(self, "_Kcc", 0):
+            raise _lib.DQMCError(_lib.ERR_STATE, "call set_current_targets first")
+        Ct, St = self._phase_tables()
+        m = self._means("susceptibilities")
+        ccs = m["CCS"]
+        res = {"Lambda": (ccs.T @ Ct) - 1j * (ccs.T @ St), "count": m["count"]}
+        if self._section("greens")[-1] > 0:
+            res["kbond"] = self._kbond(self._means_greens())
+        return res
+
+    def _means_greens(self):
+        return self.signed("greens")["G"] if self.sign_weighting() else self.unpack_accumulators(self._section("greens"))["G"]
+
+    def _stiffness_indices(self, axis):
+        """(k+, k-, q_L, q_T): the current-target columns along +-axis and the smallest momenta along / across it"""
+        if self._dirs is None or self._mom is None:
+            raise _lib.DQMCError(_lib.ERR_STATE, "superfluid_stiffness: set_current_targets(iterator) and set_momenta first")
+        A = np.array(_lat_vectors(self.model.l), dtype=np.float64)
+        dim = A.shape[0]
+        if not 0 <= axis < dim:
+            raise ValueError("axis must be 0 .. %d" % (dim - 1))
+        a = A[axis] / np.linalg.norm(A[axis])  # (A_i: the vectors the lattice is periodic under, along the bonds)
+        nrm = np.linalg.norm(self._dirs[:self._Kcc], axis=1)
+        par = [k for k in range(self._Kcc) if nrm[k] > 0 and np.isclose(abs(self._dirs[k] @ a), nrm[k])]
+        ks = [k for k in par if np.isclose(nrm[k], min(nrm[j] for j in par))]
+        if len(ks) != 2:
+            raise ValueError("superfluid_stiffness: the current targets do not hold the two bonds along axis %d" % axis)
+        kp, km = (ks if self._dirs[ks[0]] @ a > 0 else ks[::-1])
+        B = 2.0 * np.pi * np.linalg.inv(A).T  # rows B_j with A_i . B_j = 2 pi delta_ij: the smallest momenta
+        qL, qT = B[axis], B[(axis + 1) % dim]
+        q = self._mom[0]
+        idx, missing = [], []
+        for name, want in (("q_L", qL), ("q_T", qT)):
+            hit = [i for i in range(q.shape[0]) if np.allclose(q[i], want, atol=1e-9)]
+            if not hit:
+                missing.append("%s = %s" % (name, np.array2string(want, precision=6)))
+            idx.append(hit[0] if hit else -1)
+        if missing:
+            raise ValueError("superfluid_stiffness: set_momenta's list lacks " + " and ".join(missing))
+        return kp, km, idx[0], idx[1]
+
+    @staticmethod
+    def _stiffness_of(k_axis, lam_L, lam_T):
+        return {"k_axis": k_axis, "Lambda_L": lam_L, "Lambda_T": lam_T, "rho_s": (-k_axis - lam_T) / 4.0,
+                "drude": -k_axis - lam_L}
+
+    def superfluid_stiffness(self, axis=0):
+        """-> dict(k_axis, Lambda_L, Lambda_T, rho_s, drude): k_axis = kbond[+axis] + kbond[-axis]; Lambda_L / Lambda_T =
+        Re Lambda_axis at the smallest momentum along / perpendicular to the axis (both must be in set_momenta's list:
+        ValueError otherwise); rho_s = (-k_axis - Lambda_T) / 4, drude = -k_axis - Lambda_L.  Sign convention: Lambda_axis
+        here is the current-current response whose longitudinal limit tends to -k_axis > 0, i.e. MINUS the cosine
+        transform of the engine's CCS[., k = +axis]: the reference's cc_kernel sums <J J> of J = T c+c - h.c. without the
+        factor i of the current j = i J, so it carries i^2 = -1 (fixed on free fermions: tests/response_ref.py).
+        With the response_current binner on and at least two walkers every key X also has X_std_error: the cross-walker
+        error of the per-walker values formed from level 0 of that binner (jackknife_ratio with sign weighting on)."""
+        kp, km, iL, iT = self._stiffness_indices(axis)
+        cr = self.current_response()
+        if "kbond" not in cr:
+            raise _lib.DQMCError(_lib.ERR_STATE, "superfluid_stiffness: accumulate greens as well (kbond comes from its mean)")
+        lam = -cr["Lambda"][kp].real
+        res = self._stiffness_of(cr["kbond"][kp] + cr["kbond"][km], lam[iL], lam[iT])
+        W = self.n_walkers
+        if self._binning_enabled("response_current") and W >= 2 and self.binner_size("response_current")[2] > 0:
+            E, _, T = self.binner_size("response_current")
+            nq, K = self._mom[0].shape[0], self._Kcc
+            lv0 = np.stack([self.binner_level("response_current", w, 0)[0] for w in range(W)])
+            sel = lambda v: np.stack([v[:, 2 * K * nq + kp] + v[:, 2 * K * nq + km], -v[:, kp * nq + iL], -v[:, kp * nq + iT]], axis=1)
+            if self.sign_weighting():
+                val, err = jackknife_ratio(sel(lv0), lv0[:, E - 1])
+                # (rho_s and drude are linear in the three: their jackknife is that of the combination)
+                comb = np.stack([(-sel(lv0)[:, 0] - sel(lv0)[:, 2]) / 4.0, -sel(lv0)[:, 0] - sel(lv0)[:, 1]], axis=1)
+                _, err2 = jackknife_ratio(comb, lv0[:, E - 1])
+                errs = dict(zip(("k_axis", "Lambda_L", "Lambda_T", "rho_s", "drude"), list(err) + list(err2)))
+            else:
+                x = sel(lv0) / T
+                per = np.stack([x[:, 0], x[:, 1], x[:, 2], (-x[:, 0] - x[:, 2]) / 4.0, -x[:, 0] - x[:, 1]], axis=1)
+                e = np.sqrt(((per - per.mean(axis=0)) ** 2).sum(axis=0) / (W * (W - 1)))
+                errs = dict(zip(("k_axis", "Lambda_L", "Lambda_T", "rho_s", "drude"), e))
+            for k, v in errs.items():
+                res[k + "_std_error"] = v
+        return res
+
+    def _binned_response(self, which, level=None):
+        """binned() of a response binner: response_pairing / response_pairing_susceptibility -> {channel: complex [n_q]};
+        response_current -> Lambda complex [K_cc, n_q] and kbond [K_cc]; every X with X_std_error, X_std_error_walkers,
+        X_tau, those of a complex X split into _re / _im.  With sign weighting as _binned_momentum."""
+        raw = self.binned_raw(which, level)
+        if self.sign_weighting():
+            E = self.binner_size(which)[0]
+            lv0 = np.stack([self.binner_level(which, w, 0)[0] for w in range(self.n_walkers)])
+            val, err = jackknife_ratio(lv0[:, :E - 1], lv0[:, E - 1])
+            pad = lambda v: np.concatenate([v, [np.nan]])
+            raw = dict(raw, mean=pad(val), std_error=pad(err), std_error_walkers=pad(err))
+        nq = self._mom[0].shape[0]
+        if which == "response_current":
+            names, rows = ["Lambda"], self._Kcc
+        else:
+            names, rows = self._channel_names(), 1
+        n = len(names) * rows * nq
+        res = {}
+        for key, x in (("mean", ""), ("std_error", "_std_error"), ("std_error_walkers", "_std_error_walkers"), ("tau", "_tau")):
+            v = raw[key]
+            c, s = v[:n].reshape(len(names), rows, nq), v[n:2 * n].reshape(len(names), rows, nq)
+            for i, name in enumerate(names):
+                ci, si = (c[i], s[i]) if which == "response_current" else (c[i, 0], s[i, 0])
+                if key == "mean":
+                    res[name] = ci - 1j * si
+                else:
+                    res[name + x + "_re"], res[name + x + "_im"] = ci, si
+            if which == "response_current":
+                res["kbond" + x] = v[2 * n:2 * n + self._Kcc]
+        res["count"] = raw["count"]
+        res["reliable_level"] = raw["reliable_level"]
+        return res
+
     # ---- scalar thermodynamics (include/dqmc_hip.h "thermodynamics"; the reference has no such measurement)
     def set_thermodynamics(self, on=True, hopping=None):
         """configure the thermodynamics section: the model's hopping_matrix() (or `hopping`, one n x n matrix per block)
@@ -1544,6 +1782,7 @@ class DQMC:
         tab = np.asfortranarray(np.asarray(trg_of).astype(np.int32))  # [src, k] -> trg_of[src + n*k]
         self._c(lib().dqmc_set_current_targets(self._h, tab.ctypes.data_as(C.POINTER(C.c_int32)), int(K), dptr(self._cc_T)))
         self._Kcc = int(K)
+        self._binner_dropped("response_current")  # (the engine disables it: enable it again)
         # (the hopping goes into a checkpoint only where it is not the model's own)
         self._tables["current_targets"] = (np.array(tab, dtype=np.int32), self._Kcc,
                                            None if hopping is None else [float(x) for x in self._cc_T])

@@ -172,6 +172,27 @@ def momentum_grid(l):
     return labels.astype(np.float64) @ G, labels
 
 
+def default_pair_channels(lattice, directions, K):
+    """-> {name: weights f[k], k < K} over the K shortest directions (`directions[k]` the displacement, k = 0 on-site):
+    s = e_0; s* = 1/2 on every nearest neighbour (the shortest non-zero directions among the K; the same 1/2 on every
+    lattice, no 1/sqrt(z)); on a SquareLattice also d = +1/2 on the bonds along x and -1/2 on those along y."""
+    r = np.asarray(directions, dtype=np.float64)[:K]
+    nrm = np.linalg.norm(r, axis=1)
+    if K < 1 or nrm[0] > 1e-9:
+        raise ValueError("direction 0 must be the on-site one")
+    s = np.zeros(K)
+    s[0] = 1.0
+    res = {"s": s}
+    if K > 1:
+        nn = np.isclose(nrm, nrm[1:].min())
+        res["s*"] = np.where(nn, 0.5, 0.0)
+        if isinstance(lattice, SquareLattice):
+            if nn.sum() != 4:
+                raise ValueError("the d channel needs the four nearest neighbours among the K directions")
+            res["d"] = np.where(nn, np.where(np.abs(r[:, 0]) > np.abs(r[:, 1]), 0.5, -0.5), 0.0)
+    return res
+
+
 def generate_combinations(vs):
     """lattice_iterators.jl:137-143: all periodic images, in the reference's order"""
     out = [np.zeros(len(vs[0]))]
