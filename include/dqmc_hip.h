@@ -638,6 +638,49 @@ enum { DQMC_BIN_RESPONSE_PAIRING = 15, DQMC_BIN_RESPONSE_PAIRING_SUSCEPTIBILITY 
 int dqmc_set_pair_channels(dqmc_handle *h, int32_t n_ch, const double *F /* [K*K x n_ch], kk fastest */);
 int dqmc_response_plan(dqmc_handle *h, int32_t out[4]);  /* [n_ch, K, K_cc, n_q], zeros where unset */
 
+/* ---- entanglement: the second Renyi entropy from walker pairs ------------------------------------------------------
+ * The reference, a single-chain code, has no such measurement: it needs independent Markov chains at the same
+ * parameters, which is what the walker batch is.  Grover's estimator (T. Grover, PRL 111, 130402): for a subsystem
+ * A = (a_0 .. a_{N_A - 1}) of distinct 0-based sites, taken in the order given, and every pair of walkers w < w',
+ *   M_b(w, w') = I - G_A^(w,b) - G_A^(w',b) + 2 G_A^(w,b) G_A^(w',b)                      (N_A x N_A)
+ *   x(w, w')   = prod_b det M_b(w, w')       repulsive model (two blocks: up, down)
+ *   x(w, w')   = (det M_0(w, w'))^2          attractive model (both spin species share the one block)
+ * G_A^(w,b)[i, j] = G^(w,b)[a_i, a_j], G the true equal-time Green's function that dqmc_accumulate_greens sums
+ * (dqmc_get_greens).  One sample is the strictly upper triangle of the W x W matrix x, one matrix per subsystem, element
+ * (w, w') at W w + w'; the lower triangle and the diagonal are 0.  Tr rho_A^2 is the mean of x over pairs and samples,
+ * S_2(A) = -log Tr rho_A^2 (dqmc.py: entanglement_from_pair_sums, with the delete-one-walker jackknife).
+ * det M_b comes from an elimination with partial pivoting in the pivot order of dqmc_logdet's sign (largest magnitude,
+ * lowest row among equals) as sign and sum of log|pivot|; x = sign exp(sum).  Every sum and pivot choice is taken in a
+ * fixed order: x(w, w') depends on the two walkers' G alone, not on W, the other subsystems or the launch shape.  A pair
+ * with a zero or non-finite pivot (or a non-finite x) gives the sample 0 and is counted in `failures`.
+ * Limits: 1 <= N_A <= DQMC_ENT_MAX_SITES (M is eliminated in the LDS of one workgroup), at most DQMC_ENT_MAX_SUBSYSTEMS
+ * subsystems, W >= 2.  Sign weighting: the signed estimator needs s_w s_w' and <s>^2 and is NOT implemented; with sign
+ * weighting on dqmc_accumulate_entanglement returns DQMC_ERR_STATE.  Each handle pairs its own walkers only; there is no
+ * reduction over ranks (purities of ranks combine as count-weighted means on the host).
+ * The sums are NOT a DQMC_RED_* section: dqmc_accumulator_size, dqmc_reduce_size, the packed reduction and the state blob
+ * are those of a handle without the measurement, whether it is on or off, and with it off nothing is allocated or
+ * launched.  The checkpoint carries the sums in the file's preamble (dqmc.py: save / load, dqmc_set_entanglement_sums). */
+enum { DQMC_ENT_MAX_SITES = 128, DQMC_ENT_MAX_SUBSYSTEMS = 64 };
+/* The reference has no such measurement.  Subsystem s is sites[sub_ptr[s] .. sub_ptr[s + 1]), sub_ptr[0] = 0.  n_sub = 0
+ * turns the measurement off and frees everything (the pointers are then ignored).  DQMC_ERR_INVALID for n_sub < 0 or
+ * above DQMC_ENT_MAX_SUBSYSTEMS, an empty list, more than DQMC_ENT_MAX_SITES sites, a duplicate site or a site outside
+ * [0, n_sites): the handle keeps its setting.  DQMC_ERR_STATE for a handle with fewer than two walkers.  A successful
+ * call starts with zero sums. */
+int dqmc_set_entanglement(dqmc_handle *h, int32_t n_sub, const int32_t *sub_ptr /* [n_sub + 1] */, const int32_t *sites);
+/* n_sub W W + 2 doubles: [sums: n_sub x W x W][sample count][failures]; 0 while the measurement is off */
+int dqmc_entanglement_size(dqmc_handle *h, size_t *n_doubles);
+/* The reference has no such measurement.  One sample from the true G of the current fields, at any point where
+ * dqmc_accumulate_greens is allowed.  DQMC_ERR_STATE before dqmc_prepare or dqmc_set_entanglement and with sign
+ * weighting on. */
+int dqmc_accumulate_entanglement(dqmc_handle *h);
+/* the sums, the count and the failures (n = dqmc_entanglement_size); the last sample alone (n = n_sub W W; zeros before
+ * the first one).  dqmc_reset_accumulators zeroes the sums, the count and the failures. */
+int dqmc_get_entanglement(dqmc_handle *h, double *host_out, size_t n);
+int dqmc_get_entanglement_sample(dqmc_handle *h, double *host_out, size_t n);
+/* puts back what dqmc_get_entanglement handed out (the checkpoint's way in); the count and the failures must be
+ * non-negative integers, DQMC_ERR_INVALID otherwise */
+int dqmc_set_entanglement_sums(dqmc_handle *h, const double *host_in, size_t n);
+
 /* ---- checkpoint and resume ---------------------------------------------------------------------------------------
  * save / load / resume! (FileIO.jl:38-156, DQMC.jl:463-477, 797-924) for the state that lives on the device.  Like the
  * global moves this is a defined extension of the ABI: the reference writes a JLD file from host objects; here the engine

@@ -9,14 +9,14 @@ from .configurations import (CompressedConf, ConfigRecorder, Discarder, compress
                              decompress)
 from . import lattices  # noqa: F401
 from .lattices import (Chain, EachLocalQuadByDistance, EachLocalQuadBySyncedDistance, EachSitePairByDistance,  # noqa: F401
-                       CubicLattice, SquareLattice, TriangularLattice, build_checkerboard, momentum_grid)
+                       CubicLattice, SquareLattice, TriangularLattice, build_checkerboard, momentum_grid, strip_subsystem)
 from .models import (HubbardModel, HubbardModelAttractive, HubbardModelRepulsive,  # noqa: F401
                      rand_conf)
 from .sharding import (Communicator, reduce_accumulators, walker_block, walker_range,  # noqa: F401
                        walker_seeds)
 from .dqmc import (DQMC, DQMCParameters, calculate_greens_AVX, device_count,  # noqa: F401
                    checkerboard_exponentials, checkerboard_seqs, checkerboard_slab, checkerboard_tables,
-                   finish_moments, hopping_exponentials, logdet_matrices, mfma_f64_peak, rdivp, triangular_factors,
+                   entanglement_from_pair_sums, finish_moments, hopping_exponentials, logdet_matrices, mfma_f64_peak, rdivp, triangular_factors,
                    udt_AVX_pivot, vmul)
 
 from .mc import MC, IsingModel, IsingTc, greedy_colouring, reciprocal_vectors  # noqa: F401

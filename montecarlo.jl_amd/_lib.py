@@ -24,6 +24,7 @@ RED_THERMODYNAMICS, BIN_THERMODYNAMICS = 6, 14  # DQMC_RED_THERMODYNAMICS, DQMC_
 BIN_RESPONSE = {"response_pairing": 15, "response_pairing_susceptibility": 16, "response_current": 17}
 # the elements of a thermodynamics sample, in the order of include/dqmc_hip.h (DQMC_THERMO_ELEMENTS of them)
 THERMO_FIELDS = ("n_up", "n_dn", "n", "D", "m2", "E_kin", "E_int", "E", "N2", "Mz2")
+ENT_MAX_SITES, ENT_MAX_SUBSYSTEMS = 128, 64  # DQMC_ENT_MAX_SITES, DQMC_ENT_MAX_SUBSYSTEMS
 K_FAMILIES = ("gemm", "qr", "trsm", "sweep", "misc", "flush")
 
 
@@ -200,6 +201,12 @@ SIGNATURES = {
     "dqmc_thermodynamics_size": (C.c_int, [_H, C.POINTER(C.c_size_t)]),
     "dqmc_get_thermodynamics": (C.c_int, [_H, _dp]),
     "dqmc_export_thermodynamics": (C.c_int, [_H, C.c_void_p]),
+    "dqmc_set_entanglement": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "dqmc_entanglement_size": (C.c_int, [_H, C.POINTER(C.c_size_t)]),
+    "dqmc_accumulate_entanglement": (C.c_int, [_H]),
+    "dqmc_get_entanglement": (C.c_int, [_H, _dp, C.c_size_t]),
+    "dqmc_get_entanglement_sample": (C.c_int, [_H, _dp, C.c_size_t]),
+    "dqmc_set_entanglement_sums": (C.c_int, [_H, _dp, C.c_size_t]),
     "dqmc_comm_unique_id": (C.c_int, [C.c_void_p]),
     "dqmc_comm_init": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_H)]),
     "dqmc_comm_destroy": (C.c_int, [_H]),

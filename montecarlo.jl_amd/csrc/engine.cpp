@@ -184,6 +184,20 @@ struct dqmc_handle {
         double U_s = 0.0;
         uint64_t T_hash = 0;
     } th;
+    // Renyi-2 entanglement from walker pairs (entangle.inl, entangle.hip): n_sub == 0: off, nothing allocated.  Not a
+    // section: the sums [n_sub][W][W] and the sample count live here.  sub_ptr / sites: the site lists (host copies
+    // beside them); img: the compact G_A images, subsystem s at img_off[s]; lad / sg [n_sub][pairs][nb]: log|det| and
+    // sign of every pair's M_b; sample: the last sample; fail: pairs whose sample was set to 0
+    struct Entangle {
+        int n_sub = 0;
+        std::vector<int> sub_ptr_h, sites_h;
+        std::vector<long> off_h;
+        int *sub_ptr = nullptr, *sites = nullptr, *sg = nullptr;
+        long *img_off = nullptr;
+        double *img = nullptr, *lad = nullptr, *sample = nullptr, *sums = nullptr;
+        unsigned long long *fail = nullptr;
+        long long count = 0;
+    } ent;
     // time-displaced recording (unequal_time.inl, tdm.hip): every == 0: off, nothing allocated.  The sample (bin_E doubles
     // per walker in the layout of include/dqmc_hip.h) and the sums are sec[DQMC_RED_TIME_DISPLACED]; src_of [n_dirs][n]
     // only with the fast form
@@ -1453,6 +1467,7 @@ int dqmc_create(const dqmc_params *p, dqmc_handle **out)
 
 static void ut_free(dqmc_handle *h);
 static int binner_reset(dqmc_handle *h);
+static int ent_reset(dqmc_handle *h);  // entangle.inl
 int dqmc_destroy(dqmc_handle *h)
 {
     if (!h) return DQMC_OK;
@@ -1932,6 +1947,7 @@ int dqmc_reset_accumulators(dqmc_handle *h)
     for (const auto &s : h->sec)
         if (s.n) HIPCHK(hipMemsetAsync(s.acc, 0, s.n * sizeof(double), h->stream));
     CHK(binner_reset(h));
+    CHK(ent_reset(h));
     return DQMC_OK;
 }
 
@@ -1977,6 +1993,7 @@ int dqmc_export_pairing(dqmc_handle *h, void *device_out) { ENTER(h); return sec
 #include "global_move.inl"
 #include "thermo.inl"
 #include "response.inl"
+#include "entangle.inl"
 #include "checkpoint.inl"
 
 // ---------------------------------------------------------------------------

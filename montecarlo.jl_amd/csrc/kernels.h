@@ -511,6 +511,19 @@ constexpr int DQMC_THERMO_ELEMENTS_K = 10;
 hipError_t launch_thermodynamics(int n, int nb, int n_walkers, const double *G, long stride_unit, const int *row_ptr,
                                  const int *col, const double *val, const double *tdiag, double U_s, double *per_walker,
                                  long per_stride, const double *sw, double *acc, hipStream_t s);
+// entanglement (entangle.hip; include/dqmc_hip.h "entanglement").  launch_entanglement_gather: G_A and its transpose of
+// every (subsystem, unit) from the true G of every unit (G + u stride_unit) into img + img_off[s] + u 2 na^2, sites
+// [sub_ptr[s] .. sub_ptr[s + 1]) of `sites`.  launch_entanglement_pairs, one subsystem: lad / sg [n_pairs][nb] get
+// sum log|pivot| and sign of det M_b of every pair (w < w', w-major), then sample[W w + w'] = x(w, w') and sums += sample;
+// *failures counts the pairs whose sample was set to 0.  entanglement_prepare raises the pair kernel's dynamic LDS limit
+// for the largest subsystem (above 64 sites the image is dynamic: entanglement_lds_bytes).
+constexpr int DQMC_ENT_MAX_SITES_K = 128;
+size_t entanglement_lds_bytes(int na);
+hipError_t entanglement_prepare(int na_max);
+hipError_t launch_entanglement_gather(int n, int n_units, int n_sub, const double *G, long stride_unit, const int *sub_ptr,
+                                      const int *sites, const long *img_off, double *img, hipStream_t s);
+hipError_t launch_entanglement_pairs(int na, int nb, int n_walkers, const double *img, double *lad, int *sg, double *sample,
+                                     double *sums, unsigned long long *failures, hipStream_t s);
 // response.hip: the symmetry-channel contraction of every walker's pairing sample, in front of launch_momentum:
 //   Z[w z_stride + c n_dirs + d] = sum_kk F[kk + KK c] X[w x_stride + x_off + d + n_dirs kk],  kk ascending, c < n_ch <= 8
 hipError_t launch_pair_channels(int n_dirs, int KK, int n_ch, int n_walkers, const double *X, long x_stride, long x_off,

@@ -4,6 +4,7 @@ The object keeps the reference's names (`p`, `a`, `conf`, `propagate`, `sweep_sp
 `update`, `run`, `greens`, `current_slice`, ...) so that parity tests read like the
 reference's tests; every numerical method is a call into libdqmc_hip.so.  One DQMC
 object = `n_walkers` independent Markov chains advancing in lockstep."""
+import base64
 import ctypes as C
 import time
 from dataclasses import dataclass
@@ -250,6 +251,7 @@ class DQMC:
         self._sus_layout = False  # the susceptibility section is laid out (by its first use)
         self._thermo = False      # set_thermodynamics is on
         self._channels = None     # {name: weights} of set_pair_channels
+        self._ent = None          # (names or None, site lists) of set_entanglement
         self._mid_sweep = False  # set by load(): run() finishes the sweep the checkpoint was taken in
         if int(global_rate) < 1:
             raise ValueError("global_rate must be at least 1")
@@ -451,7 +453,8 @@ class DQMC:
         magnetization; needs set_pair_directions), "pairing" (needs set_local_targets) and
         "susceptibilities" (the CombinedGreensIterator measurements) and "time_displaced" (the tau-resolved rows; needs
         set_time_displaced; shares the one iterator pass with "susceptibilities"), and "thermodynamics" (energy, filling,
-        double occupancy ...; needs set_thermodynamics).  `binning=True` enables the device-side
+        double occupancy ...; needs set_thermodynamics) and "entanglement" (the Renyi-2 pair samples; needs
+        set_entanglement; it has no binner: its error bar is the jackknife over walkers of entanglement()).  `binning=True` enables the device-side
         LogBinner of every selected measurement before the first sweep (enable_binning; read with binned()).
         `checkpoint=path` saves the run (save()) in every `checkpoint_every`-th sweep and in the last one, thermalization
         included, at the sweep's measurement point behind its measurements: the one place of a sweep where the chain stands
@@ -461,7 +464,8 @@ class DQMC:
         if checkpoint is not None and (checkpoint_every is None or int(checkpoint_every) < 1):
             raise ValueError("run(checkpoint=path) needs checkpoint_every >= 1")
         known = {"greens": lib().dqmc_accumulate_greens, "correlations": lib().dqmc_accumulate_correlations,
-                 "pairing": lib().dqmc_accumulate_pairing, "thermodynamics": lib().dqmc_accumulate_thermodynamics}
+                 "pairing": lib().dqmc_accumulate_pairing, "thermodynamics": lib().dqmc_accumulate_thermodynamics,
+                 "entanglement": lib().dqmc_accumulate_entanglement}
         for m in measurements:
             if m not in known and m not in ("susceptibilities", "time_displaced"):
                 raise ValueError("unknown measurement %r" % (m,))
@@ -471,7 +475,7 @@ class DQMC:
         if not resumed:  # (a loaded object stands at its measurement point, the stack rebuilt by the import)
             self.prepare()
         if binning:  # a resumed run! keeps the binners it has (DQMC.jl:395-411)
-            self.enable_binning([m for m in measurements if not self._binning_enabled(m)])
+            self.enable_binning([m for m in measurements if m != "entanglement" and not self._binning_enabled(m)])
             if self._mom is not None:  # and, with momenta set, the momentum binner of every section that has one
                 self.enable_binning([k for k in ("momentum_" + m for m in measurements)
                                      if k in _lib.BIN_MOMENTUM and not self._binning_enabled(k)])
@@ -548,6 +552,11 @@ class DQMC:
         extra = {"thermodynamics": self._thermo} if self._thermo else {}  # (absent while off: the preamble of before)
         if self._channels is not None:  # the names and weights of set_pair_channels (absent while off as well)
             extra["pair_channels"] = [[k, [float(x) for x in v]] for k, v in self._channels.items()]  # (a list: the order is the engine's)
+        if self._ent is not None:  # the site lists of set_entanglement and its sums, which no blob section holds (absent while off)
+            raw = self._entanglement_raw()
+            extra["entanglement"] = {"names": self._ent[0], "sites": [list(a) for a in self._ent[1]],
+                                     "count": int(raw[-2]), "failures": int(raw[-1]),
+                                     "sums": base64.b64encode(raw[:-2].astype("<f8").tobytes()).decode("ascii")}
         return {
             **extra,
             "format": 1,
@@ -634,6 +643,9 @@ class DQMC:
                 mc.set_thermodynamics(True, hopping=None if hop is True else hop)
             if pre.get("pair_channels"):
                 mc.set_pair_channels({k: v for k, v in pre["pair_channels"]})
+            ent = pre.get("entanglement")
+            if ent:
+                mc.set_entanglement(ent["sites"] if ent["names"] is None else dict(zip(ent["names"], ent["sites"])))
             mc.prepare()  # (the susceptibility layout and two of the binners need a prepared handle)
             if pre["susceptibilities_layout"]:
                 mc._section_size("susceptibilities")
@@ -642,6 +654,10 @@ class DQMC:
             if pre["binning"]["user"]:
                 mc.user_binner(pre["binning"]["user"][0], pre["binning"]["user"][1] or None)
             mc.set_state(blob)
+            if ent:  # the sums go back bit for bit; the import above does not know them
+                sums = np.frombuffer(base64.b64decode(ent["sums"]), dtype="<f8").astype(np.float64)
+                raw = np.ascontiguousarray(np.concatenate([sums, [float(ent["count"]), float(ent["failures"])]]))
+                mc._c(lib().dqmc_set_entanglement_sums(mc._h, dptr(raw), raw.size))
         except BaseException:
             mc.close()
             raise
@@ -1764,6 +1780,62 @@ class DQMC:
         return res
 
     # ---- current_current_susceptibility (measurements.jl:257-317) over EachLocalQuadBySyncedDistance{K}
+    # ---- Renyi-2 entanglement entropy from walker pairs (include/dqmc_hip.h "entanglement"; the reference has no such measurement)
+    def set_entanglement(self, subsystems):
+        """configure the entanglement measurement: `subsystems` is a list of site sequences (0-based, distinct, taken in
+        the order given, at most 128 sites each and 64 lists; lattices.strip_subsystem makes strips) or a dict name ->
+        sites; None or an empty list turns it off and frees its memory.  From then on accumulate_entanglement() and
+        run(measurements=(..., "entanglement")) add one sample: Grover's x(w, w') of every pair of this object's walkers
+        and every subsystem.  Needs at least two walkers; refused while sign weighting is on (the signed estimator is
+        not implemented).  Multi-rank runs: each rank pairs its own walkers only and there is no reduced("entanglement");
+        the ranks' purities combine as count-weighted means, purity = sum_r count_r purity_r / sum_r count_r, S2 = -log of
+        that."""
+        if not subsystems:
+            self._c(lib().dqmc_set_entanglement(self._h, 0, None, None))
+            self._ent = None
+            return
+        names = None
+        if isinstance(subsystems, dict):
+            names, subsystems = [str(k) for k in subsystems], list(subsystems.values())
+        lists = [[int(a) for a in np.asarray(sub).reshape(-1)] for sub in subsystems]
+        ptr = np.ascontiguousarray(np.concatenate([[0], np.cumsum([len(a) for a in lists])]), dtype=np.int32)
+        flat = np.ascontiguousarray([a for sub in lists for a in sub] or [0], dtype=np.int32)
+        i32 = C.POINTER(C.c_int32)
+        self._c(lib().dqmc_set_entanglement(self._h, len(lists), ptr.ctypes.data_as(i32), flat.ctypes.data_as(i32)))
+        self._ent = (names, lists)
+
+    def accumulate_entanglement(self):
+        self._c(lib().dqmc_accumulate_entanglement(self._h))
+
+    def _entanglement_raw(self):
+        n = C.c_size_t()
+        self._c(lib().dqmc_entanglement_size(self._h, C.byref(n)))
+        out = np.zeros(max(n.value, 1))
+        self._c(lib().dqmc_get_entanglement(self._h, dptr(out), n.value))
+        return out
+
+    def entanglement_sample(self):
+        """the last sample, [n_sub, W, W]: x(w, w') in the strictly upper triangle, 0 elsewhere"""
+        if self._ent is None:
+            raise _lib.DQMCError(_lib.ERR_STATE, "call set_entanglement first")
+        W, ns = self.n_walkers, len(self._ent[1])
+        out = np.zeros(ns * W * W)
+        self._c(lib().dqmc_get_entanglement_sample(self._h, dptr(out), out.size))
+        return out.reshape((ns, W, W))
+
+    def entanglement(self):
+        """-> {"purity": [n_sub], "S2": [n_sub], "S2_std_error": [n_sub] (three walkers and more), "pair_sums":
+        [n_sub, W, W], "count", "failures"} (entanglement_from_pair_sums); "names" with a dict given to
+        set_entanglement.  failures counts the pairs whose sample was set to 0 (a singular or non-finite M)."""
+        raw = self._entanglement_raw()
+        W, ns = self.n_walkers, len(self._ent[1])
+        sums, cnt = raw[:-2].reshape((ns, W, W)), int(raw[-2])
+        res = entanglement_from_pair_sums(sums, cnt) if cnt else {}
+        res.update(pair_sums=sums, count=cnt, failures=int(raw[-1]))
+        if self._ent[0] is not None:
+            res["names"] = list(self._ent[0])
+        return res
+
     def set_current_targets(self, iterator, hopping=None):
         """hand the targets of EachLocalQuadBySyncedDistance{K} and mc.s.hopping_matrix (default: the model's
         hopping_matrix(), one n x n matrix per block) to the device; the pair directions of the same lattice are
@@ -1865,6 +1937,32 @@ def jackknife_ratio(sx, s):
     tot = sx.sum(axis=0)
     r = (tot[None, :] - sx) / (S - s)[:, None]
     return tot / S, np.sqrt((W - 1) / W * ((r - r.mean(axis=0)) ** 2).sum(axis=0))
+
+
+def entanglement_from_pair_sums(pair_sums, count):
+    """Tr rho_A^2 and S2 = -log Tr rho_A^2 from the pair sums of DQMC.entanglement(): pair_sums [n_sub, W, W] (or [W, W])
+    holds sum over `count` samples of x(w, w') in its strictly upper triangle, which alone is read.  purity = sum over
+    pairs / (count W (W - 1) / 2).  With three walkers and more, S2_std_error is the delete-one-walker jackknife of
+    -log(mean): leaving walker w out drops its W - 1 pairs, S2_w = -log of the mean over the other (W - 1)(W - 2) / 2
+    pairs, std_error = sqrt((W - 1) / W sum_w (S2_w - mean S2_w)^2).  A purity <= 0 gives S2 = nan."""
+    ps = np.asarray(pair_sums, dtype=np.float64)
+    single = ps.ndim == 2
+    ps = ps[None] if single else ps
+    W = ps.shape[-1]
+    if ps.ndim != 3 or ps.shape[1] != W or W < 2:
+        raise ValueError("pair_sums must be [n_sub, W, W] with W >= 2")
+    if int(count) < 1:
+        raise ValueError("entanglement_from_pair_sums needs at least one sample")
+    up = np.triu(ps, 1)
+    tot = up.sum(axis=(1, 2))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        purity = tot / (count * W * (W - 1) / 2.0)
+        res = {"purity": purity, "S2": -np.log(purity)}
+        if W >= 3:
+            mine = up.sum(axis=2) + up.sum(axis=1)  # [n_sub, W]: the pairs walker w is part of
+            s2 = -np.log((tot[:, None] - mine) / (count * (W - 1) * (W - 2) / 2.0))
+            res["S2_std_error"] = np.sqrt((W - 1) / W * ((s2 - s2.mean(axis=1, keepdims=True)) ** 2).sum(axis=1))
+    return {k: v[0] for k, v in res.items()} if single else res
 
 
 def finish_moments(buf):

@@ -103,6 +103,20 @@ class TriangularLattice(AbstractLattice):
         self.bonds = bonds
 
 
+def strip_subsystem(lattice, width, axis=0):
+    """The 0-based sites, ascending, whose integer coordinate along `axis` is below `width`: the strip subsystem of an
+    entanglement cut (DQMC.set_entanglement), for SquareLattice, CubicLattice and TriangularLattice, whose `lattice`
+    array carries the coordinates (axis 0 runs fastest in the site index)."""
+    if not isinstance(lattice, (SquareLattice, CubicLattice, TriangularLattice)):
+        raise TypeError("strip_subsystem: SquareLattice, CubicLattice or TriangularLattice, not %s" % type(lattice).__name__)
+    lat = lattice.lattice
+    if not 0 <= int(axis) < lat.ndim:
+        raise ValueError("strip_subsystem: axis %r of a %d-dimensional lattice" % (axis, lat.ndim))
+    if not 1 <= int(width) <= lat.shape[int(axis)]:
+        raise ValueError("strip_subsystem: width %r outside 1 .. %d" % (width, lat.shape[int(axis)]))
+    return np.sort(np.take(lat, np.arange(int(width)), axis=int(axis)).reshape(-1)).astype(np.int64) - 1
+
+
 def build_checkerboard(l):
     """src/flavors/DQMC/abstract.jl:23-54 (used here only to pin the bond tables)."""
     bonds = l.neighbors(False)
