@@ -681,6 +681,46 @@ int dqmc_get_entanglement_sample(dqmc_handle *h, double *host_out, size_t n);
  * non-negative integers, DQMC_ERR_INVALID otherwise */
 int dqmc_set_entanglement_sums(dqmc_handle *h, const double *host_in, size_t n);
 
+/* ---- current response in imaginary time: Lambda(q, tau) ---------------------------------------------------------------
+ * The reference has no such measurement.  DQMC_BIN_RESPONSE_CURRENT holds the current-current sums integrated over all
+ * slices, i.e. Lambda(q, i omega = 0) only.  This opt-in recording keeps the per-slice values that the susceptibility pass
+ * computes anyway, transformed to momentum space, as PER-WALKER sums over calls, so that the host can form
+ * Lambda(q, i omega_m), the Drude weight D / pi = -k_x - Lambda_xx(q = 0, i omega_m -> 0) and the dc-conductivity proxy
+ * (beta^2 / pi) Lambda_xx(q = 0, beta / 2) with delete-one-walker jackknife errors (dqmc.py: current_time_displaced,
+ * current_matsubara, drude_weight, dc_conductivity).
+ * dqmc_set_current_time_displaced(h, every): every == 0 turns the recording off and frees everything (the default);
+ * every >= 1 with slices % every == 0 turns it on with rows r = 0 .. R - 1, R = 1 + slices / every, tau_r = r every
+ * delta_tau; anything else returns DQMC_ERR_INVALID and the handle keeps its setting.  Needs dqmc_set_pair_directions,
+ * dqmc_set_current_targets, dqmc_set_momenta and dqmc_prepare (DQMC_ERR_STATE without them); a later call of any of the
+ * first three turns it off.  Every successful call starts with zero sums; dqmc_reset_accumulators and
+ * dqmc_set_sign_weighting zero them too.  From then on every dqmc_accumulate_susceptibilities pass adds one sample.
+ * Per walker, q fastest, then k, then r (P = 2 R K_cc n_q + K_cc + 3 doubles):
+ *   [C: R x K_cc x n_q][S: R x K_cc x n_q][kbond: K_cc][sum of s_w][samples kept][samples left out]
+ *   C[r][k][q] = sum_d cos(q . r_d) x_r[d + n_dirs k],   S[r][k][q] = sum_d sin(q . r_d) x_r[d + n_dirs k],   d ascending,
+ * with the tables of dqmc_set_momenta and x_r what cc_kernel gives for the packed tuple of slice l = r every, summed over
+ * the quads of a direction and divided by N as ccs is: no delta_tau, the attractive model's factors as in the pass, so
+ * delta_tau sum_{l = 1 .. slices} x_l is the ccs sample.  Row 0 takes (G00, G00 - I, G00, G00), the tau -> 0+ convention
+ * of the time-displaced recording above.  kbond is exactly that of DQMC_BIN_RESPONSE_CURRENT.  With sign weighting every
+ * entry is s_w times the above, a walker with s_w = 0 adds nothing and is counted as left out; with it off the sum of
+ * s_w is the number of samples kept.  The values stay as cc_kernel gives them (C <= 0 on the diagonal); Lambda = -C is
+ * the host's sign, as for the stiffness.
+ * At a recorded slice the ccs kernels write the slice's sums into a zeroed scratch, one kernel (current_tau.hip)
+ * contracts it with both tables and then adds it to the susceptibility sample: that sample, its sums, every binner fed by
+ * them, mc.s.greens, the stacks, the field and the RNG cursors are bit for bit those of a pass without the recording.
+ * Every stored value is one sum in a fixed order with no atomics: a second pass on the same state adds the same bits, and
+ * a walker's sample does not depend on n_walkers.  Not a DQMC_RED_* section, no binner, nothing in the packed reduction
+ * or the state blob: with it off nothing is allocated or launched.  Each handle records its own walkers; ranks combine on
+ * the host (count-weighted).  The checkpoint carries the setting and the sums in the file's preamble (dqmc.py: save /
+ * load, dqmc_set_current_time_displaced_sums). */
+int dqmc_set_current_time_displaced(dqmc_handle *h, int32_t every);
+int dqmc_current_time_displaced_plan(dqmc_handle *h, int32_t out[4]);  /* [R, every, K_cc, n_q], zeros while off */
+/* n_walkers P doubles, walker after walker; 0 while the recording is off */
+int dqmc_current_time_displaced_size(dqmc_handle *h, size_t *n_doubles);
+int dqmc_get_current_time_displaced(dqmc_handle *h, double *host_out);
+/* puts back what dqmc_get_current_time_displaced handed out (the checkpoint's way in); the two sample counts of every
+ * walker must be non-negative integers, DQMC_ERR_INVALID otherwise */
+int dqmc_set_current_time_displaced_sums(dqmc_handle *h, const double *host_in);
+
 /* ---- checkpoint and resume ---------------------------------------------------------------------------------------
  * save / load / resume! (FileIO.jl:38-156, DQMC.jl:463-477, 797-924) for the state that lives on the device.  Like the
  * global moves this is a defined extension of the ABI: the reference writes a JLD file from host objects; here the engine

@@ -14,7 +14,7 @@ from .models import (HubbardModel, HubbardModelAttractive, HubbardModelRepulsive
                      rand_conf)
 from .sharding import (Communicator, reduce_accumulators, walker_block, walker_range,  # noqa: F401
                        walker_seeds)
-from .dqmc import (DQMC, DQMCParameters, calculate_greens_AVX, device_count,  # noqa: F401
+from .dqmc import (DQMC, DQMCParameters, CurrentTauSums, matsubara_trapezoid, calculate_greens_AVX, device_count,  # noqa: F401
                    checkerboard_exponentials, checkerboard_seqs, checkerboard_slab, checkerboard_tables,
                    entanglement_from_pair_sums, finish_moments, hopping_exponentials, logdet_matrices, mfma_f64_peak, rdivp, triangular_factors,
                    udt_AVX_pivot, vmul)

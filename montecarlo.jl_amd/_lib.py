@@ -207,6 +207,11 @@ SIGNATURES = {
     "dqmc_get_entanglement": (C.c_int, [_H, _dp, C.c_size_t]),
     "dqmc_get_entanglement_sample": (C.c_int, [_H, _dp, C.c_size_t]),
     "dqmc_set_entanglement_sums": (C.c_int, [_H, _dp, C.c_size_t]),
+    "dqmc_set_current_time_displaced": (C.c_int, [_H, C.c_int32]),
+    "dqmc_current_time_displaced_plan": (C.c_int, [_H, C.POINTER(C.c_int32)]),
+    "dqmc_current_time_displaced_size": (C.c_int, [_H, C.POINTER(C.c_size_t)]),
+    "dqmc_get_current_time_displaced": (C.c_int, [_H, _dp]),
+    "dqmc_set_current_time_displaced_sums": (C.c_int, [_H, _dp]),
     "dqmc_comm_unique_id": (C.c_int, [C.c_void_p]),
     "dqmc_comm_init": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_H)]),
     "dqmc_comm_destroy": (C.c_int, [_H]),

@@ -198,6 +198,15 @@ struct dqmc_handle {
         unsigned long long *fail = nullptr;
         long long count = 0;
     } ent;
+    // current response in imaginary time (current_tau.inl, current_tau.hip): every == 0: off, nothing allocated.  Not a
+    // section either.  K / n_q: K_cc and the momenta it was set with (the setters of both turn it off); tab
+    // [n_dirs][n_q][2]: cos and sin of dqmc_set_momenta, q fastest; x [W][K][n_dirs]: one slice's own ccs sums; kb
+    // [W][K]: the pass's bond kinetic energies; sums [W][P]: the per-walker sums over calls
+    struct CurrentTau {
+        int every = 0, R = 0, K = 0, n_q = 0;
+        size_t P = 0;
+        double *tab = nullptr, *x = nullptr, *kb = nullptr, *sums = nullptr;
+    } ctd;
     // time-displaced recording (unequal_time.inl, tdm.hip): every == 0: off, nothing allocated.  The sample (bin_E doubles
     // per walker in the layout of include/dqmc_hip.h) and the sums are sec[DQMC_RED_TIME_DISPLACED]; src_of [n_dirs][n]
     // only with the fast form
@@ -1468,6 +1477,11 @@ int dqmc_create(const dqmc_params *p, dqmc_handle **out)
 static void ut_free(dqmc_handle *h);
 static int binner_reset(dqmc_handle *h);
 static int ent_reset(dqmc_handle *h);  // entangle.inl
+static int ctd_reset(dqmc_handle *h);  // current_tau.inl
+static void ctd_off(dqmc_handle *h);   // (the stream must be idle)
+static int ctd_row(dqmc_handle *h, int row, double cc_fac, const double *g0l, const double *gl0, const double *gll,
+                   double *add_to, long add_stride, long add_off);
+static int ctd_finish(dqmc_handle *h, double cc_fac);
 int dqmc_destroy(dqmc_handle *h)
 {
     if (!h) return DQMC_OK;
@@ -1948,6 +1962,7 @@ int dqmc_reset_accumulators(dqmc_handle *h)
         if (s.n) HIPCHK(hipMemsetAsync(s.acc, 0, s.n * sizeof(double), h->stream));
     CHK(binner_reset(h));
     CHK(ent_reset(h));
+    CHK(ctd_reset(h));
     return DQMC_OK;
 }
 
@@ -1994,6 +2009,7 @@ int dqmc_export_pairing(dqmc_handle *h, void *device_out) { ENTER(h); return sec
 #include "thermo.inl"
 #include "response.inl"
 #include "entangle.inl"
+#include "current_tau.inl"
 #include "checkpoint.inl"
 
 // ---------------------------------------------------------------------------

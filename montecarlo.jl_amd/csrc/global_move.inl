@@ -148,6 +148,7 @@ int dqmc_set_sign_weighting(dqmc_handle *h, int32_t on)
     dqmc_handle::Section &sg = h->sec[DQMC_RED_SIGN];
     sg.n_red = h->sign_on ? sg.n : 0;
     HIPCHK(hipMemsetAsync(sg.acc, 0, sg.n * sizeof(double), h->stream));
+    CHK(ctd_reset(h));  // (the imaginary-time current sums: their passes feed the susceptibilities, empty by now)
     for (int which = DQMC_BIN_GREENS; which <= DQMC_BIN_TIME_DISPLACED; ++which) {
         if (which == DQMC_BIN_USER) continue;
         dqmc_handle::Binner &sb = h->bin[binner_sign_of(which)];

@@ -534,6 +534,19 @@ hipError_t launch_pair_channels(int n_dirs, int KK, int n_ch, int n_walkers, con
 hipError_t launch_bond_kinetic(int n, int nb, int K, int n_walkers, double fac, const double *G, long stride_unit,
                                const int *trg_of, const double *tts, const double *sw, double *out, long out_stride,
                                long out_off, hipStream_t s);
+// current_tau.hip: row `r` of the imaginary-time-resolved current-current recording from one slice's own sums
+// x [n_walkers][K][n_dirs] (launch_cc_slice into a zeroed buffer), tab [n_dirs][n_q][2] = (cos, sin) of q . r_d:
+//   sums[w sums_stride + off_c + k n_q + q] += s_w sum_d tab[2 (q + n_q d)]     x[(w K + k) n_dirs + d],  d ascending,
+//   sums[w sums_stride + off_s + k n_q + q] += s_w sum_d tab[2 (q + n_q d) + 1] x[(w K + k) n_dirs + d]
+// (sw == nullptr: s_w = 1; s_w == 0: the walker is left out), and, with add_to != nullptr,
+//   add_to[w add_stride + add_off + k n_dirs + d] += x[(w K + k) n_dirs + d]
+hipError_t launch_current_tau_row(int n_dirs, int n_q, int K, int n_walkers, const double *x, const double *tab,
+                                  const double *sw, double *sums, long sums_stride, long off_c, long off_s,
+                                  double *add_to, long add_stride, long add_off, hipStream_t s);
+// the end of a recorded pass: sums[w sums_stride + tail + .] = [kbond: K][sum of s_w][samples kept][samples left out]
+// take kb [n_walkers][K] (launch_bond_kinetic's, s_w x already), s_w, and one count
+hipError_t launch_current_tau_finish(int K, int n_walkers, const double *kb, const double *sw, double *sums,
+                                     long sums_stride, long tail, hipStream_t s);
 // HS field <-> Julia BitArray chunks (compress / decompress, HubbardModel.jl:56-59)
 hipError_t launch_conf_pack(const int8_t *conf, size_t n_elem, unsigned long long *chunks, hipStream_t s);
 hipError_t launch_conf_unpack(const unsigned long long *chunks, size_t n_elem, int8_t *conf, hipStream_t s);

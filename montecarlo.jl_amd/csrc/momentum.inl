@@ -27,6 +27,7 @@ static void mom_off(dqmc_handle *h)
 {
     for (int which = DQMC_BIN_MOMENTUM_CORRELATIONS; which < DQMC_BIN_MOMENTUM_END; ++which) mom_disable(h, which);
     for (int which = DQMC_BIN_RESPONSE_PAIRING; which < DQMC_BIN_RESPONSE_END; ++which) resp_disable(h, which);  // they use the tables
+    ctd_off(h);  // (and so does the imaginary-time current recording)
     dfree(h, &h->mom.cos_d);
     dfree(h, &h->mom.sin_d);
     h->mom.cos_h.clear();

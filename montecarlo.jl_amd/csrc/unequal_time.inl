@@ -685,6 +685,7 @@ int dqmc_set_current_targets(dqmc_handle *h, const int32_t *trg_of, int32_t K, c
         if (trg_of[i] < -1 || trg_of[i] >= n) return fail(h, DQMC_ERR_INVALID, "target index out of range");
     HIPCHK(hipStreamSynchronize(h->stream));
     resp_disable(h, DQMC_BIN_RESPONSE_CURRENT);  // its rows follow the targets: the caller enables it again
+    ctd_off(h);                                  // and so do those of the imaginary-time recording
     h->cc_trg_h.assign(trg_of, trg_of + (size_t)n * K);
     h->cc_T.assign(T, T + (size_t)h->nb * n * n);
     h->K_cc = K;
@@ -830,6 +831,7 @@ int dqmc_accumulate_susceptibilities(dqmc_handle *h, int32_t recalculate)
     const bool record = h->td.every != 0;
     if (record) CHK(binner_room(h, DQMC_BIN_TIME_DISPLACED));
     if (record) CHK(binner_room(h, DQMC_BIN_MOMENTUM_TIME_DISPLACED));
+    const int crec = h->ctd.every;  // the current response in imaginary time (current_tau.inl); 0: off
     const dqmc_handle::Section &sus = h->sec[DQMC_RED_SUSCEPTIBILITIES], &td = h->sec[DQMC_RED_TIME_DISPLACED];
     const long total = sus.bin_E;
     CHK(sign_begin(h, DQMC_RED_SUSCEPTIBILITIES, record ? DQMC_RED_TIME_DISPLACED : -1));
@@ -847,6 +849,11 @@ int dqmc_accumulate_susceptibilities(dqmc_handle *h, int32_t recalculate)
         Timed t(h, DQMC_K_MISC);
         CHK(td_record(h, 0, 1, u->g00, u->g00, u->g00, u->g00));
     }
+    if (crec) {  // its row 0 the same way; G00 - I goes through out[0], which the iterator's first step overwrites
+        Timed t(h, DQMC_K_MISC);
+        HIPCHK(launch_sub_identity(h->n, h->units, u->out[0], u->g00, h->nn, h->stream));
+        CHK(ctd_row(h, 0, cc_fac, u->out[0], u->g00, u->g00, nullptr, 0, 0));
+    }
     CHK(ut_cgi_begin(h, recalculate));
     for (;;) {
         int l = -1;
@@ -858,10 +865,16 @@ int dqmc_accumulate_susceptibilities(dqmc_handle *h, int32_t recalculate)
         HIPCHK(launch_sus_slice(h->n, h->nb, h->p.model_kind, h->W, u->g00, u->out[0], u->out[1], u->out[2], h->nn,
                                 h->dir_ptr, h->pair_src, h->pair_trg, h->n_dirs, h->K_loc, h->trg_of, sus.per_walker,
                                 total, h->stream));
-        if (h->K_cc)
+        if (crec && l % crec == 0)  // the slice's sums on their own first, then added to the sample: the same bits
+            CHK(ctd_row(h, l / crec, cc_fac, u->out[0], u->out[1], u->out[2], sus.per_walker, total, ut_cc_offset(h)));
+        else if (h->K_cc)
             HIPCHK(launch_cc_slice(h->cc, h->n, h->nb, h->W, cc_fac, cc_fac, u->out[0], u->out[1], u->out[2], h->nn,
                                    h->dir_ptr, h->pair_src, h->pair_trg, h->n_dirs, sus.per_walker, total,
                                    ut_cc_offset(h), h->stream));
+    }
+    if (crec) {
+        Timed t(h, DQMC_K_MISC);
+        CHK(ctd_finish(h, cc_fac));
     }
     if (h->sign_on) {  // the samples become s_w x in place: the binners below read them
         Timed t(h, DQMC_K_MISC);

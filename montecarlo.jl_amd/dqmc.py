@@ -252,6 +252,7 @@ class DQMC:
         self._thermo = False      # set_thermodynamics is on
         self._channels = None     # {name: weights} of set_pair_channels
         self._ent = None          # (names or None, site lists) of set_entanglement
+        self._ctd = 0             # `every` of set_current_time_displaced (0: off)
         self._mid_sweep = False  # set by load(): run() finishes the sweep the checkpoint was taken in
         if int(global_rate) < 1:
             raise ValueError("global_rate must be at least 1")
@@ -557,6 +558,10 @@ class DQMC:
             extra["entanglement"] = {"names": self._ent[0], "sites": [list(a) for a in self._ent[1]],
                                      "count": int(raw[-2]), "failures": int(raw[-1]),
                                      "sums": base64.b64encode(raw[:-2].astype("<f8").tobytes()).decode("ascii")}
+        if self._ctd:  # the setting of set_current_time_displaced and its per-walker sums, which no blob section holds either
+            extra["current_time_displaced"] = {
+                "every": int(self._ctd),
+                "sums": base64.b64encode(self._current_tau_raw().astype("<f8").tobytes()).decode("ascii")}
         return {
             **extra,
             "format": 1,
@@ -647,6 +652,9 @@ class DQMC:
             if ent:
                 mc.set_entanglement(ent["sites"] if ent["names"] is None else dict(zip(ent["names"], ent["sites"])))
             mc.prepare()  # (the susceptibility layout and two of the binners need a prepared handle)
+            ctd = pre.get("current_time_displaced")
+            if ctd:
+                mc.set_current_time_displaced(ctd["every"])
             if pre["susceptibilities_layout"]:
                 mc._section_size("susceptibilities")
             for m, cap in pre["binning"]["sections"].items():
@@ -658,6 +666,11 @@ class DQMC:
                 sums = np.frombuffer(base64.b64decode(ent["sums"]), dtype="<f8").astype(np.float64)
                 raw = np.ascontiguousarray(np.concatenate([sums, [float(ent["count"]), float(ent["failures"])]]))
                 mc._c(lib().dqmc_set_entanglement_sums(mc._h, dptr(raw), raw.size))
+            if ctd:  # and so do these
+                raw = np.ascontiguousarray(np.frombuffer(base64.b64decode(ctd["sums"]), dtype="<f8").astype(np.float64))
+                if raw.size != mc._current_tau_raw().size:
+                    raise _ckpt.CheckpointError("the checkpoint's current_time_displaced sums do not fit its own tables")
+                mc._c(lib().dqmc_set_current_time_displaced_sums(mc._h, dptr(raw)))
         except BaseException:
             mc.close()
             raise
@@ -1359,6 +1372,7 @@ class DQMC:
 
     def _momenta_dropped(self):
         self._mom = None
+        self._ctd = 0  # (the engine turns the imaginary-time current recording off with the tables)
         for k in tuple(_lib.BIN_MOMENTUM) + tuple(_lib.BIN_RESPONSE):  # (the response binners use the tables)
             self._binner_dropped(k)
 
@@ -1836,6 +1850,123 @@ class DQMC:
             res["names"] = list(self._ent[0])
         return res
 
+    # ---- current response in imaginary time (include/dqmc_hip.h "current response in imaginary time"; the reference has no such measurement)
+    def set_current_time_displaced(self, every=1):
+        """record the current-current correlator per imaginary time and momentum inside every
+        accumulate_susceptibilities() / run(measurements=(..., "susceptibilities")) from now on: rows r = 0 .. slices /
+        every at tau_r = r every delta_tau, per walker, for the targets of set_current_targets and the momenta of
+        set_momenta (both needed, and prepare(): ERR_STATE otherwise).  `every` must divide slices (ERR_INVALID, and the
+        setting stays); 0 or None turns it off and frees its memory.  set_pair_directions, set_current_targets and
+        set_momenta turn it off.  Every call starts with zero sums.  Read with current_time_displaced(),
+        current_matsubara(), drude_weight(), dc_conductivity().  Multi-rank runs: each rank records its own walkers and
+        there is no reduced(...) of it; rank results combine count-weighted, X = sum_r count_r X_r / sum_r count_r (with
+        sign weighting: weighted with each rank's sum of signs)."""
+        self._c(lib().dqmc_set_current_time_displaced(self._h, int(every or 0)))
+        self._ctd = int(every or 0)
+
+    def current_time_displaced_plan(self):
+        """-> dict(R, every, K_cc, n_q) of the engine, all zero while the recording is off"""
+        out = (C.c_int32 * 4)()
+        self._c(lib().dqmc_current_time_displaced_plan(self._h, out))
+        return dict(zip(("R", "every", "K_cc", "n_q"), (int(v) for v in out)))
+
+    def _current_tau_raw(self):
+        """the per-walker sums [n_walkers, P] as the engine holds them"""
+        n = C.c_size_t()
+        self._c(lib().dqmc_current_time_displaced_size(self._h, C.byref(n)))
+        out = np.zeros(max(n.value, 1))
+        self._c(lib().dqmc_get_current_time_displaced(self._h, dptr(out)))
+        return out.reshape((self.n_walkers, -1))
+
+    def _current_tau(self):
+        """(CurrentTauSums of the engine's sums, tau [R])"""
+        p = self.current_time_displaced_plan()
+        if not p["every"]:
+            raise _lib.DQMCError(_lib.ERR_STATE, "call set_current_time_displaced first")
+        ct = CurrentTauSums(self._current_tau_raw(), p["R"], p["K_cc"], p["n_q"], could_leave_out=self.sign_weighting())
+        return ct, np.arange(p["R"]) * (p["every"] * self.p.delta_tau)
+
+    def current_time_displaced(self):
+        """-> dict(tau [R], Lambda_cos, Lambda_sin [R, K_cc, n_q], kbond [K_cc], count, left_out): Lambda_cos / Lambda_sin
+        are MINUS the engine's cosine / sine sums (the sign of superfluid_stiffness: Lambda(q, tau) = Lambda_cos - i
+        Lambda_sin >= 0 on the diagonal), means over walkers and calls, <x s> / <s> with sign weighting on; count: samples
+        kept, left_out: samples of walkers whose sign came out 0.  Lambda_cos, Lambda_sin and kbond come with
+        X_std_error, the delete-one-walker jackknife of the ratio (two walkers and more, three with sign weighting on,
+        where a walker can be left out).  ValueError when the sum of signs is 0."""
+        ct, tau = self._current_tau()
+        res = ct.estimate(lambda C_, S_, kb: {"Lambda_cos": -C_, "Lambda_sin": -S_, "kbond": kb})
+        res.update(tau=tau, count=ct.count, left_out=ct.left_out)
+        return res
+
+    def current_matsubara(self, n_max=None):
+        """-> dict(omega [n_max + 1], Lambda complex [n_max + 1, K_cc, n_q], Lambda_std_error_re / _im): the trapezoid
+        rule on the recorded grid, Lambda(q, i omega_m) = every delta_tau sum_r w_r cos(omega_m tau_r) Lambda(q, tau_r),
+        w_0 = w_{R-1} = 1/2, else 1, omega_m = 2 pi m / beta, Lambda(q, tau) = Lambda_cos - i Lambda_sin of
+        current_time_displaced().  n_max <= (R - 1) / 2 (the default).  Errors: the jackknife through the transform."""
+        ct, tau = self._current_tau()
+        top = (ct.R - 1) // 2
+        n_max = top if n_max is None else int(n_max)
+        if not 0 <= n_max <= top:
+            raise ValueError("n_max must be 0 .. (R - 1) / 2 = %d" % top)
+        beta = self.p.slices * self.p.delta_tau
+        omega = 2.0 * np.pi * np.arange(n_max + 1) / beta
+        res = ct.estimate(lambda C_, S_, kb: {"Lambda": matsubara_trapezoid(-C_ + 1j * S_, tau, omega)})
+        res["omega"] = omega
+        return res
+
+    def _axis_bonds(self, axis):
+        """(k+, k-, index of q = 0): the current-target columns along +-axis as superfluid_stiffness takes them"""
+        if self._dirs is None or self._mom is None:
+            raise _lib.DQMCError(_lib.ERR_STATE, "set_current_targets(iterator) and set_momenta first")
+        A = np.array(_lat_vectors(self.model.l), dtype=np.float64)
+        if not 0 <= axis < A.shape[0]:
+            raise ValueError("axis must be 0 .. %d" % (A.shape[0] - 1))
+        a = A[axis] / np.linalg.norm(A[axis])
+        nrm = np.linalg.norm(self._dirs[:self._Kcc], axis=1)
+        par = [k for k in range(self._Kcc) if nrm[k] > 0 and np.isclose(abs(self._dirs[k] @ a), nrm[k])]
+        ks = [k for k in par if np.isclose(nrm[k], min(nrm[j] for j in par))]
+        if len(ks) != 2:
+            raise ValueError("the current targets do not hold the two bonds along axis %d" % axis)
+        kp, km = (ks if self._dirs[ks[0]] @ a > 0 else ks[::-1])
+        q = self._mom[0]
+        hit = [i for i in range(q.shape[0]) if np.allclose(q[i], 0.0, atol=1e-9)]
+        if not hit:
+            raise ValueError("set_momenta's list lacks q = 0")
+        return kp, km, hit[0]
+
+    def drude_weight(self, axis=0, m=(1, 2, 3)):
+        """-> dict(k_axis, omega_m, Lambda_m, D_over_pi_m, each with X_std_error): Scalapino-White-Zhang's D / pi = -k_axis
+        - Lambda_axis,axis(q = 0, i omega_m -> 0) at the Matsubara indices `m` (extrapolate m -> 0), k_axis = kbond[+axis]
+        + kbond[-axis] of the recording's own sums, Lambda_m the real part of current_matsubara() at q = 0 (which must be
+        in set_momenta's list).  This is the limit q -> 0 first; superfluid_stiffness()["drude"] takes omega = 0 first and
+        is fixed to -k_axis by gauge invariance."""
+        kp, km, i0 = self._axis_bonds(axis)
+        ct, tau = self._current_tau()
+        ms = np.atleast_1d(np.asarray(m, dtype=np.int64))
+        if ms.size == 0 or ms.min() < 0 or ms.max() > (ct.R - 1) // 2:
+            raise ValueError("m must lie in 0 .. (R - 1) / 2 = %d" % ((ct.R - 1) // 2))
+        omega = 2.0 * np.pi * ms / (self.p.slices * self.p.delta_tau)
+
+        def f(C_, S_, kb):
+            lam = matsubara_trapezoid(-C_[:, kp, i0], tau, omega)
+            k_axis = kb[kp] + kb[km]
+            return {"k_axis": k_axis, "Lambda_m": lam, "D_over_pi_m": -k_axis - lam}
+        res = ct.estimate(f)
+        res["omega_m"] = omega
+        return res
+
+    def dc_conductivity(self, axis=0):
+        """-> dict(sigma_dc, sigma_dc_std_error, Lambda_half): Trivedi-Randeria's proxy (beta^2 / pi) Lambda_axis,axis(q = 0,
+        tau = beta / 2).  ValueError unless slice slices / 2 is a recorded row."""
+        kp, km, i0 = self._axis_bonds(axis)
+        ct, tau = self._current_tau()
+        M, every = self.p.slices, self.current_time_displaced_plan()["every"]
+        if M % 2 or (M // 2) % every:
+            raise ValueError("dc_conductivity: tau = beta / 2 (slice %g) is not a recorded row (slices = %d, every = %d)"
+                             % (M / 2.0, M, every))
+        r, beta = (M // 2) // every, M * self.p.delta_tau
+        return ct.estimate(lambda C_, S_, kb: {"Lambda_half": -C_[r, kp, i0], "sigma_dc": beta * beta / np.pi * -C_[r, kp, i0]})
+
     def set_current_targets(self, iterator, hopping=None):
         """hand the targets of EachLocalQuadBySyncedDistance{K} and mc.s.hopping_matrix (default: the model's
         hopping_matrix(), one n x n matrix per block) to the device; the pair directions of the same lattice are
@@ -1855,6 +1986,7 @@ class DQMC:
         self._c(lib().dqmc_set_current_targets(self._h, tab.ctypes.data_as(C.POINTER(C.c_int32)), int(K), dptr(self._cc_T)))
         self._Kcc = int(K)
         self._binner_dropped("response_current")  # (the engine disables it: enable it again)
+        self._ctd = 0  # (and turns the imaginary-time current recording off)
         # (the hopping goes into a checkpoint only where it is not the model's own)
         self._tables["current_targets"] = (np.array(tab, dtype=np.int32), self._Kcc,
                                            None if hopping is None else [float(x) for x in self._cc_T])
@@ -1937,6 +2069,66 @@ def jackknife_ratio(sx, s):
     tot = sx.sum(axis=0)
     r = (tot[None, :] - sx) / (S - s)[:, None]
     return tot / S, np.sqrt((W - 1) / W * ((r - r.mean(axis=0)) ** 2).sum(axis=0))
+
+
+def matsubara_trapezoid(x, tau, omega):
+    """sum_r h w_r cos(omega_m tau_r) x[r] over the uniform grid tau [R] (h its spacing, w_0 = w_{R-1} = 1/2, else 1) for
+    every omega_m: x [R, ...] -> [len(omega), ...]"""
+    x, tau, omega = np.asarray(x), np.asarray(tau, dtype=np.float64), np.atleast_1d(np.asarray(omega, dtype=np.float64))
+    if tau.size < 2 or x.shape[0] != tau.size:
+        raise ValueError("matsubara_trapezoid needs at least two rows, one per tau")
+    w = np.ones(tau.size)
+    w[0] = w[-1] = 0.5
+    kern = (tau[1] - tau[0]) * w[None, :] * np.cos(omega[:, None] * tau[None, :])  # [m, r]
+    return np.tensordot(kern, x, axes=(1, 0))
+
+
+class CurrentTauSums:
+    """The per-walker sums of the imaginary-time current recording (include/dqmc_hip.h), [W, P] with P = 2 R K n_q + K + 3:
+    per walker [C: R x K x n_q][S: R x K x n_q][kbond: K][sum of s_w][samples kept][samples left out].  estimate(f) gives
+    f of the ratio estimates (sum over walkers of the sums / sum of signs; without sign weighting the sum of signs is the
+    number of samples) and, through f, the delete-one-walker jackknife error of every entry of its result.
+    `could_leave_out`: a walker's samples can be left out (sign weighting), the jackknife then needs three walkers."""
+
+    def __init__(self, sums, R, K, n_q, could_leave_out=False):
+        sums = np.asarray(sums, dtype=np.float64)
+        self.R, self.K, self.n_q = int(R), int(K), int(n_q)
+        self.E = 2 * self.R * self.K * self.n_q + self.K
+        if sums.ndim != 2 or sums.shape[1] != self.E + 3:
+            raise ValueError("sums must be [n_walkers, 2 R K n_q + K + 3]")
+        self.W = sums.shape[0]
+        self.sx, self.s = sums[:, :self.E], sums[:, self.E]
+        self.count, self.left_out = int(sums[:, self.E + 1].sum()), int(sums[:, self.E + 2].sum())
+        self.min_walkers = 3 if could_leave_out else 2
+
+    def _split(self, v):
+        n = self.R * self.K * self.n_q
+        shape = (self.R, self.K, self.n_q)
+        return v[:n].reshape(shape), v[n:2 * n].reshape(shape), v[2 * n:]
+
+    def estimate(self, f):
+        """f(C [R, K, n_q], S [R, K, n_q], kbond [K]) -> dict of arrays / scalars; -> the dict at the ratio estimate, each
+        real X with X_std_error, each complex X with X_std_error_re / X_std_error_im (where the jackknife has enough
+        walkers).  ValueError when the sum of signs, or one with a walker left out, is 0."""
+        S = self.s.sum()
+        if S == 0:
+            raise ValueError("current_time_displaced: the sum of signs is 0 over %d samples: <O s> / <s> is undefined" % self.count)
+        tot = self.sx.sum(axis=0)
+        res = {k: np.asarray(v) for k, v in f(*self._split(tot / S)).items()}
+        if self.W >= self.min_walkers:
+            if np.any(S - self.s == 0):
+                raise ValueError("the sum of signs is 0 with one walker left out: the ratio is undefined")
+            loo = [f(*self._split((tot - self.sx[w]) / (S - self.s[w]))) for w in range(self.W)]
+            for k in list(res):
+                r = np.stack([np.asarray(l[k]) for l in loo])
+                d = r - r.mean(axis=0)
+                fac = (self.W - 1) / self.W
+                if np.iscomplexobj(r):
+                    res[k + "_std_error_re"] = np.sqrt(fac * (d.real ** 2).sum(axis=0))
+                    res[k + "_std_error_im"] = np.sqrt(fac * (d.imag ** 2).sum(axis=0))
+                else:
+                    res[k + "_std_error"] = np.sqrt(fac * (d ** 2).sum(axis=0))
+        return res
 
 
 def entanglement_from_pair_sums(pair_sums, count):
