@@ -63,7 +63,8 @@ typedef const DQMC_GLOBAL d2v *gcd2p;
 // The same elimination on the four SIMDs of a CU: wave J owns block column J of S and of S' (tiles (I, J), I <= J).
 // In block I0 wave I0 is the PIVOT: it runs the decisions on its diagonal tiles and publishes, per accepted site,
 // the two A operands (x G[:, s], x G[s, :] on the block's rows) through LDS; waves J > I0 apply them to their strip
-// tiles (I0, J), exchange the finished strip rows once per panel and do the k = 4 updates of their later tiles;
+// tiles (I0, J), exchange the finished strip rows once per panel and do the k = 4 updates of their later tiles (the x
+// of the panel's four sites come from sm.xs in one read with the last site's flag);
 // wave (I0 + 2) % 4 also carries the two triangular inverses of the diagonal block.  Each slot of the step ring is
 // written once per launch (no reuse), flags are LDS words with workgroup-scope release / acquire; every wait is
 // bounded (a time-out sets *errflag and lets all waves run through).
@@ -121,14 +122,29 @@ __device__ __forceinline__ double lu4_rcp(double r)
 extern __shared__ __attribute__((aligned(16))) double lu4_lds[];
 #ifdef LU4_STAMPS  // diagnostic build only (tools/lu4_stamps.py): cycle stamps of walker 0 into a buffer of their own
 __device__ long long *lu4_stamp_ptr = nullptr;
-// LU4_STAMPS == 2: only the coarse stamps (index >= 320: phases of a wave), which do not disturb the site loop
+// LU4_STAMPS == 2: only the coarse stamps (index >= 320: phases of a wave), which do not disturb the site loop.
+// The buffer's address is read once per wave (LU4_STAMP_SETUP: null for every walker but 0), not at every stamp: a stamp
+// is then s_memtime and a store from lane 0, without a scalar load of the pointer in front of it.
+#define LU4_STAMP_SETUP()                                                                                        \
+    const unsigned long long lu4_spu = w == 0 ? (unsigned long long)lu4_stamp_ptr : 0ull;                        \
+    DQMC_GLOBAL long long *const lu4_sp = (DQMC_GLOBAL long long *)(                                             \
+        ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(lu4_spu >> 32)) << 32) |             \
+        (unsigned)__builtin_amdgcn_readfirstlane((int)(lu4_spu & 0xffffffffull)))
 #define LU4_STAMP(idx)                                                                       \
     do {                                                                                     \
-        if ((LU4_STAMPS != 2 || (idx) >= 320) && w == 0 && (threadIdx.x & 63) == 0 && lu4_stamp_ptr)            \
-            lu4_stamp_ptr[(idx)] = (long long)__builtin_amdgcn_s_memtime();                  \
+        if ((LU4_STAMPS != 2 || (idx) >= 320) && lu4_sp && (threadIdx.x & 63) == 0)          \
+            lu4_sp[(idx)] = (long long)__builtin_amdgcn_s_memtime();                         \
+    } while (0)
+// the helper's stamps inside a site and at the panel end (index >= 512; only with the stamps of the site loop)
+#define LU4_STAMPF(idx)                                                                      \
+    do {                                                                                     \
+        if (LU4_STAMPS != 2 && lu4_sp && (threadIdx.x & 63) == 0)                            \
+            lu4_sp[(idx)] = (long long)__builtin_amdgcn_s_memtime();                         \
     } while (0)
 #else
+#define LU4_STAMP_SETUP() do { } while (0)
 #define LU4_STAMP(idx) do { } while (0)
+#define LU4_STAMPF(idx) do { } while (0)
 #endif
 #ifdef LU4_STAMPS
 #ifndef FL_STAMP_BID
@@ -155,6 +171,7 @@ __device__ __noinline__ void lu4_wave(int n, const double *__restrict__ Gall, lo
 {
     Lu4Smem<NB> &sm = *reinterpret_cast<Lu4Smem<NB> *>(lu4_lds);
     const int lane = threadIdx.x & 63, g = lane >> 4, ci = lane & 15;
+    LU4_STAMP_SETUP();
     const unsigned long long cbits =
         ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(cbits_v >> 32)) << 32) |
         (unsigned)__builtin_amdgcn_readfirstlane((int)(cbits_v & 0xffffffffull));
@@ -447,12 +464,16 @@ __device__ __noinline__ void lu4_wave(int n, const double *__restrict__ Gall, lo
         // from registers that the MFMAs of site s have not touched yet, so a decision never waits for an MFMA.
         // helper side: flag and payload of the NEXT site are requested before the MFMAs of the current one, so that a
         // helper that is behind (after the prologue, after a panel end) works through the ring at MFMA pace instead of
-        // one LDS round trip per site; a request that came too early (flag not yet set) is repeated by the spin loop
+        // one LDS round trip per site; a request that came too early (flag not yet set) is repeated by the spin loop.
+        // The x of a panel's four sites are only used at the panel end, where lane group g needs the x of site g of the
+        // panel: they ride as ONE read (sm.xs[b][first site of the panel + g]) on the request of the panel's last site
+        // (ks == 3), behind its flag, instead of a read and a select per site.  The pivot stores x before the flag and
+        // writes 0 for a rejected site, so the value is the one the per-site select used to build.
         int pf_v = 0;
         double2 pf_pay[NB];
-        double pf_xh[NB];
+        double pf_x4[NB];
 #pragma unroll
-        for (int b = 0; b < NB; ++b) { pf_pay[b] = make_double2(0.0, 0.0); pf_xh[b] = 0.0; }
+        for (int b = 0; b < NB; ++b) { pf_pay[b] = make_double2(0.0, 0.0); pf_x4[b] = 0.0; }
         double dcur[NB];
         if (PIV) {
 #pragma unroll
@@ -551,16 +572,16 @@ __device__ __noinline__ void lu4_wave(int n, const double *__restrict__ Gall, lo
                     // flag was already set
                     int v = c > 0 ? __builtin_amdgcn_readfirstlane(pf_v) : 0;
                     double2 pay[NB];
-                    double xh[NB];
+                    double x4[NB];
 #pragma unroll
-                    for (int b = 0; b < NB; ++b) { pay[b] = pf_pay[b]; xh[b] = pf_xh[b]; }
+                    for (int b = 0; b < NB; ++b) { pay[b] = pf_pay[b]; x4[b] = pf_x4[b]; }
                     for (int it = 0; v == 0 && it < LU4_SPIN; ++it) {
                         const int vr = __hip_atomic_load(&sm.step[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                         LU4_ORDER();
 #pragma unroll
                         for (int b = 0; b < NB; ++b) {
                             if (c < 15) pay[b] = sm.aST[b][s][lane];
-                            xh[b] = sm.xs[b][s];
+                            if (HLP && ks == 3) x4[b] = sm.xs[b][16 * I0 + 4 * r0 + g];
                         }
                         v = __builtin_amdgcn_readfirstlane(vr);
                         if (v) break;
@@ -576,22 +597,26 @@ __device__ __noinline__ void lu4_wave(int n, const double *__restrict__ Gall, lo
                         v = -1;
                     }
                     if (v > 0) lastflag = v;
+                    if (HLP) LU4_STAMPF(512 + 64 * (J - 1) + s);  // flag seen
                     if (c < 15 && (FULL || s + 1 < nsites)) {  // next site of this block: request it now
                         pf_v = __hip_atomic_load(&sm.step[s + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                         LU4_ORDER();
 #pragma unroll
                         for (int b = 0; b < NB; ++b) {
                             if (c + 1 < 15) pf_pay[b] = sm.aST[b][s + 1][lane];
-                            pf_xh[b] = sm.xs[b][s + 1];
+                            if (HLP && ks == 2) pf_x4[b] = sm.xs[b][16 * I0 + 4 * r0 + g];
                         }
                     }
                     LU4_STAMP(64 * (1 + J) + s);
+                    if (HLP && ks == 3) {
+#pragma unroll
+                        for (int b = 0; b < NB; ++b) xv4[b] = x4[b];
+                    }
                     if (v > 0 && (v & 3) == 2) {
                         panel_acc |= 1u << ks;
 #pragma unroll
                         for (int b = 0; b < NB; ++b) {
                             const double aS = pay[b].x, aT = pay[b].y;
-                            if (HLP) xv4[b] = g == ks ? xh[b] : xv4[b];
                             if (HLP && c < 15) {
                                 S[b][I0] = MFMA(aS, S[b][I0][r0], S[b][I0]);
                                 ST[b][I0] = MFMA(aT, ST[b][I0][r0], ST[b][I0]);
@@ -602,10 +627,20 @@ __device__ __noinline__ void lu4_wave(int n, const double *__restrict__ Gall, lo
                             }
                         }
                     }
+                    if (HLP) LU4_STAMPF(704 + 64 * (J - 1) + s);  // strip MFMAs issued
                 }
             }
             // panel end: the four sites applied to the later tiles of my block column with k = 4 MFMAs
             if (HLP && panel_acc != 0) {
+                LU4_STAMPF(896 + 48 * (J - 1) + 3 * (4 * I0 + r0) + 0);  // panel end entered
+                // a short chunk may end inside a panel, where no site with ks == 3 has brought the x: every panel of
+                // such a chunk reads them here, also one whose last site has already brought them (the same values
+                // again; the short chunk is the split form's last launch of a slice, not the fused path)
+                if (!FULL) {
+                    LU4_ORDER();
+#pragma unroll
+                    for (int b = 0; b < NB; ++b) xv4[b] = sm.xs[b][16 * I0 + 4 * r0 + g];
+                }
                 if (J < 3 && !stored) {  // my finished strip rows for the waves to my right
 #pragma unroll
                     for (int b = 0; b < NB; ++b) {
@@ -620,6 +655,7 @@ __device__ __noinline__ void lu4_wave(int n, const double *__restrict__ Gall, lo
                     S[b][J] = MFMA(xv4[b] * ST[b][I0][r0], S[b][I0][r0], S[b][J]);
                     ST[b][J] = MFMA(xv4[b] * S[b][I0][r0], ST[b][I0][r0], ST[b][J]);
                 }
+                LU4_STAMPF(896 + 48 * (J - 1) + 3 * (4 * I0 + r0) + 1);  // tile (J, J) issued
 #pragma unroll
                 for (int I = I0 + 1; I < J; ++I) {
                     const int ok = lu4_wait(&sm.sflag[lu4_strip_idx(I0, r0, I)], &sm.abort);
@@ -633,6 +669,7 @@ __device__ __noinline__ void lu4_wave(int n, const double *__restrict__ Gall, lo
                         }
                     }
                 }
+                LU4_STAMPF(896 + 48 * (J - 1) + 3 * (4 * I0 + r0) + 2);  // strips of the waves between waited for, all issued
             }
         }
         // block row I0 is final: register images for the flush kernel
@@ -1156,6 +1193,8 @@ hipError_t launch_sweep_fused(int n, int nb, int n_walkers, const double *Gin, d
 }
 
 #ifdef LU4_STAMPS
+// devptr: a device buffer of at least 2048 64-bit words (16 KiB).  The kernels store to it unchecked: LU4_STAMP uses
+// words 0..431, FL_STAMP 480..491, LU4_STAMPF 512..1027 (map in tools/lu4_stamps.py).
 extern "C" int dqmc_debug_lu4_stamps(void *devptr)
 {
     return (int)hipMemcpyToSymbol(HIP_SYMBOL(lu4_stamp_ptr), &devptr, sizeof(void *));

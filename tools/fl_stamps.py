@@ -1,6 +1,6 @@
 """In-kernel timeline of one flush workgroup in the throughput regime (512 units; workgroup FL_STAMP_BID, default 1200 = third
-round): build with `make -C montecarlo.jl_amd/csrc stamps`, run with
-DQMC_HIP_LIB=montecarlo.jl_amd/libdqmc_hip_stamps.so python tools/fl_stamps.py"""
+round): build with `make -C montecarlo.jl_amd/csrc -f diag.mk lu4_stamps` (the same library as tools/lu4_stamps.py), run
+with DQMC_HIP_LIB=montecarlo.jl_amd/libdqmc_hip_lu4stamps.so python tools/fl_stamps.py"""
 import ctypes as C, os, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -8,7 +8,7 @@ import torch
 import __graft_entry__ as g
 gpu = g.load_package()
 L = gpu.lib()
-buf = torch.zeros(512, dtype=torch.int64, device="cuda:0")
+buf = torch.zeros(2048, dtype=torch.int64, device="cuda:0")  # the size dqmc_debug_lu4_stamps asks for: walker 0's waves stamp up to word 1027
 L.dqmc_debug_lu4_stamps.argtypes = [C.c_void_p]
 assert L.dqmc_debug_lu4_stamps(C.c_void_p(buf.data_ptr())) == 0
 mc = gpu.DQMC(gpu.HubbardModelRepulsive(16, 2), beta=1.0, n_walkers=256, seed=3)
