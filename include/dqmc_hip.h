@@ -883,7 +883,7 @@ int dqmc_checkerboard_apply(dqmc_handle *h, int32_t which, int32_t slice, const 
 int dqmc_qr_fallbacks(dqmc_handle *h, int64_t *count);
 /* 1 when slice products and wraps apply eT2 / eTinv2 in factored form (Kronecker products of 16 x 16 factors at n = 256,
  * 8 x 8 factors at n = 512, see dqmc_params; the triangular 16 x 16 lattice's three factors, see
- * dqmc_set_triangular_factors), else 0 */
+ * dqmc_set_triangular_factors; the t-t' square 16 x 16 lattice's four factors, see dqmc_set_square_tp_factors), else 0 */
 int dqmc_kron_hopping(dqmc_handle *h, int32_t *on);
 /* The periodic 16 x 16 TriangularLattice (n_sites = 256, site x + 16 y; hopping along X = x + 1, Y = y + 1 and D = XY,
  * triangular.jl:60-78) in three-factor form.  X, Y and D commute, so exp(-a T) = e^{a mu} f(X) f(Y) f(XY) with
@@ -898,6 +898,23 @@ int dqmc_kron_hopping(dqmc_handle *h, int32_t *on);
  * A handle on a path that does not take them (DQMC_NO_KRON or DQMC_NO_SLAB set, a checkerboard, or a square lattice's
  * Kronecker factors already taken) returns DQMC_OK and keeps its path. */
 int dqmc_set_triangular_factors(dqmc_handle *h, const double *f);
+/* The periodic 16 x 16 SquareLattice with next-nearest-neighbour hopping t' (n_sites = 256, site x + 16 y; hopping t along
+ * X = x + 1 and Y = y + 1, t' along D = XY and A = X Y^-1) in four-factor form.  An extension: the reference's Hubbard
+ * models have nearest-neighbour hopping only.  X, Y, D and A commute, so exp(-a T) = e^{a mu} f_t(X) f_t(Y) f_t'(D) f_t'(A)
+ * with f_s = exp(a s (S + S')) on a 16-ring, and each of eT2 and eTinv2 is E = (Fy (x) Fx) Ed Ea, where Ed applies Fd
+ * along each diagonal x - y = u and Ea applies Fa along each anti-diagonal x + y = w:
+ *   (Ed v)(x, y) = sum_y' Fd[y, y'] v(x - y + y', y')        (Ea v)(x, y) = sum_y' Fa[y, y'] v(x + y - y', y')
+ * f holds, per block, [eT2: Fx Fy Fd Fa][eTinv2: Fx Fy Fd Fa], each a 16 x 16 column-major matrix (2048 doubles per
+ * block); mu is folded into Fx.
+ * The handle checks them against its own eT2 / eTinv2: E[0,0] > 0 and max|E - P| <= 256 DBL_EPSILON max|E| for
+ * P = (Fy (x) Fx) Ed Ea and for the four orders the kernel applies, Fx Ea Ed Fy, Fy Ea Ed Fx, Fy Ed Ea Fx and Fx Ed Ea Fy.
+ * When every block passes, slice products and wraps apply the four factors (ttp.hip; dqmc_kron_hopping reports 1) and, as
+ * on the triangular path, the sweep's last chunk is applied by the stand-alone flush and a wrap is two launches.  Returns
+ * DQMC_ERR_INVALID for factors that fail the check or n_sites != 256, DQMC_ERR_STATE after dqmc_prepare /
+ * dqmc_build_stack / dqmc_replay_greens; in both cases the handle keeps its path and stays usable.  A handle on a path
+ * that does not take them (DQMC_NO_KRON or DQMC_NO_SLAB set, a checkerboard, or Kronecker or triangular factors already
+ * taken) returns DQMC_OK and keeps its path. */
+int dqmc_set_square_tp_factors(dqmc_handle *h, const double *f);
 /* which call sites of udt_AVX_pivot! (UDT.jl:192-306) this handle serves with the one-launch pre-pivoted factorisation:
  * bit 0 add_slice_sequence_left/right (stack.jl:272-311) and other callers, bit 1 / bit 2 the two factorisations of
  * calculate_greens_AVX! (stack.jl:349, :376); 0 = the reference's pivot rule everywhere (n != 256, > 32 units, DQMC_QR_NOBLOCKED) */
@@ -912,7 +929,8 @@ int dqmc_udt_one_launch_sites(dqmc_handle *h, int32_t *mask);
  *           (n_sites <= 256; it runs at the call sites out[3] leaves to it), 0: single-workgroup QR kernels
  *   out[7]  1: site sweep with the fused chunk loop (elimination beside the previous chunk's flush), 0: launch per chunk
  *   out[8], out[9]    workgroups the one-launch factored wrap may use without / with a pending sweep chunk
- *   out[10], out[11]  1: the factored wrap is one launch without / with a pending chunk, 0: two launches (or no factored wrap) */
+ *   out[10], out[11]  1: the factored wrap is one launch without / with a pending chunk, 0: two launches (or no factored wrap;
+ *           always 0 with the triangular lattice's three factors and the t-t' square lattice's four) */
 int dqmc_launch_plan(dqmc_handle *h, int32_t out[12]);
 /* device error word as it stands (0 = no bounded wait inside a kernel has run out); no reference counterpart: the reference
  * has no concurrent workgroups (diagnostic next to DQMCAnalysis, src/flavors/DQMC/DQMC.jl:35-47) */

@@ -16,7 +16,7 @@ from .sharding import (Communicator, reduce_accumulators, walker_block, walker_r
                        walker_seeds)
 from .dqmc import (DQMC, DQMCParameters, CurrentTauSums, matsubara_trapezoid, calculate_greens_AVX, device_count,  # noqa: F401
                    checkerboard_exponentials, checkerboard_seqs, checkerboard_slab, checkerboard_tables,
-                   entanglement_from_pair_sums, finish_moments, hopping_exponentials, logdet_matrices, mfma_f64_peak, rdivp, triangular_factors,
+                   entanglement_from_pair_sums, finish_moments, hopping_exponentials, logdet_matrices, mfma_f64_peak, rdivp, square_tp_factors, triangular_factors,
                    udt_AVX_pivot, vmul)
 
 from .mc import MC, IsingModel, IsingTc, greedy_colouring, reciprocal_vectors  # noqa: F401

@@ -238,6 +238,7 @@ SIGNATURES = {
     "dqmc_qr_fallbacks": (C.c_int, [_H, C.POINTER(C.c_int64)]),
     "dqmc_kron_hopping": (C.c_int, [_H, C.POINTER(C.c_int32)]),
     "dqmc_set_triangular_factors": (C.c_int, [_H, _dp]),
+    "dqmc_set_square_tp_factors": (C.c_int, [_H, _dp]),
     "dqmc_device_errors": (C.c_int, [_H, C.POINTER(C.c_int32)]),
     "dqmc_udt_one_launch_sites": (C.c_int, [_H, C.POINTER(C.c_int32)]),
     "dqmc_launch_plan": (C.c_int, [_H, C.POINTER(C.c_int32)]),

@@ -49,8 +49,11 @@ struct dqmc_handle {
     // kron_f: [eT2, eTinv2, eT2', eTinv2'] x ([Exy image] x nb x 4096, [Ez image] x nb x 256).
     // n == 256 triangular 16 x 16 lattice (dqmc_set_triangular_factors): (Fy (x) Fx) Ed, tri.hip instead of slab.hip.
     // kron_f: [eT2, eTinv2, eT2', eTinv2'] x [x, y, d] x nb x 16 x 16 (ax = Fx, ay = Fy, Fd behind Fy).
+    // n == 256 t-t' square 16 x 16 lattice (dqmc_set_square_tp_factors): (Fy (x) Fx) Ed Ea, ttp.hip instead of slab.hip.
+    // kron_f: [eT2, eTinv2, eT2', eTinv2'] x [x, y, d, a] x nb x 16 x 16 (Fd and Fa behind Fy); tri is set with ttp: what
+    // the triangular path leaves off (the pending-chunk fold, the one-launch wrap) is off here as well.
     // kron_fa / kron_fb: doubles per block of the two operand sets (ax / ay of a KronStep)
-    bool kron = false, tri = false;
+    bool kron = false, tri = false, ttp = false;
     double *kron_f = nullptr;
     int kron_fa = 0, kron_fb = 0;
     int8_t *conf = nullptr;  // W x (N x M)
@@ -529,6 +532,56 @@ static bool tri_factor_ok(const double *E, const double *fx, const double *fy, c
     return std::isfinite(emax) && std::isfinite(rmax) && rmax <= 256.0 * 2.220446049250313e-16 * emax;
 }
 
+// eT2 / eTinv2 of the 16 x 16 periodic square lattice with next-nearest-neighbour hopping (n = 256, site x + 16 y; hopping
+// along X = (1, 0), Y = (0, 1), D = XY and A = X Y^-1) as (Fy (x) Fx) Ed Ea: Ed as above, and Ea applies Fa along the
+// anti-diagonals x + y = const:
+//   (Ea v)(x, y) = sum_y' Fa[y, y'] v(x + y - y', y')
+// The factors come from the host (dqmc_set_square_tp_factors).  The four shifts commute, so every order of the four products
+// is E up to rounding; the gate bounds the claimed form and the four orders the kernel applies (ttp.hip: Fx Ea Ed Fy from a
+// step that starts with y in the registers, Fy Ea Ed Fx from one that starts with x, and, as the transposes of what the
+// transposed factors give in the daggered products and the wraps' right products, Fy Ed Ea Fx and Fx Ed Ea Fy), each by
+// 256 eps max|E|.  Every order is formed by applying its factors to the identity, 16 terms per entry and factor.
+static bool ttp_factor_ok(const double *E, const double *fx, const double *fy, const double *fd, const double *fa)
+{
+    const int n = 256;
+    if (!(E[0] > 0.0)) return false;
+    std::vector<double> M((size_t)n * n), T((size_t)n * n);
+    // M <- Op(F) M, op 0: Fx on x, 1: Fy on y, 2: Ed, 3: Ea
+    auto apply = [&](int op, const double *F) {
+        for (int c = 0; c < n; ++c) {
+            const double *m = M.data() + (size_t)n * c;
+            double *t = T.data() + (size_t)n * c;
+            for (int y = 0; y < 16; ++y)
+                for (int x = 0; x < 16; ++x) {
+                    double acc = 0.0;
+                    for (int k = 0; k < 16; ++k) {
+                        const double f = F[(op == 0 ? x : y) + 16 * k];
+                        const int src = op == 0 ? k + 16 * y : op == 1 ? x + 16 * k : op == 2 ? ((x - y + k) & 15) + 16 * k
+                                                                                               : ((x + y - k) & 15) + 16 * k;
+                        acc += f * m[src];
+                    }
+                    t[x + 16 * y] = acc;
+                }
+        }
+        M.swap(T);
+    };
+    const double *F[4] = {fx, fy, fd, fa};
+    // (the operators are listed right to left: the first one is applied first)
+    static const int orders[5][4] = {{3, 2, 0, 1}, {1, 2, 3, 0}, {0, 2, 3, 1}, {0, 3, 2, 1}, {1, 3, 2, 0}};
+    double emax = 0.0, rmax = 0.0;
+    for (size_t i = 0; i < (size_t)n * n; ++i) emax = std::max(emax, std::fabs(E[i]));
+    for (const auto &ord : orders) {
+        std::fill(M.begin(), M.end(), 0.0);
+        for (int i = 0; i < n; ++i) M[i + (size_t)n * i] = 1.0;
+        for (int k = 0; k < 4; ++k) apply(ord[k], F[ord[k]]);
+        for (size_t i = 0; i < (size_t)n * n; ++i) {
+            const double r = std::fabs(E[i] - M[i]);
+            if (!(r <= rmax)) rmax = r;  // (a NaN is kept)
+        }
+    }
+    return std::isfinite(emax) && std::isfinite(rmax) && rmax <= 256.0 * 2.220446049250313e-16 * emax;
+}
+
 // The kernel-selection and test switches, read from the environment once per handle / stand-alone
 // primitive call: nothing else reads them (the launchers get them from the handle)
 static void read_kernel_switches(dqmc_handle *h)
@@ -878,6 +931,7 @@ static int run_kron(dqmc_handle *h, const KronArgs &a)
     hipEvent_t ea, eb;
     timing_events(h, &ea, &eb);
     if (h->n == 512) HIPCHK(launch_kron3_chain(a, h->stream, ea, eb));
+    else if (h->ttp) HIPCHK(launch_ttp_chain(a, h->stream, ea, eb));
     else if (h->tri) HIPCHK(launch_tri_chain(a, h->stream, ea, eb));
     else HIPCHK(launch_kron_chain(a, h->stream, ea, eb));
     return timing_push(h, ea, eb, DQMC_K_GEMM);
@@ -2241,6 +2295,45 @@ int dqmc_set_triangular_factors(dqmc_handle *h, const double *f)
     h->kron_fa = 256;
     h->kron_fb = 512;  // Fy, then Fd
     h->tri = h->kron = true;
+    return DQMC_OK;
+}
+
+// The t-t' square 16 x 16 lattice's hopping exponentials as four 16 x 16 factors per matrix (include/dqmc_hip.h): checked
+// against the handle's own eT2 / eTinv2 (ttp_factor_ok) before the handle takes them; a failed check leaves it as it was.
+int dqmc_set_square_tp_factors(dqmc_handle *h, const double *f)
+{
+    ENTER(h);
+    if (!f) return fail(h, DQMC_ERR_INVALID, "dqmc_set_square_tp_factors: null factors");
+    if (h->n != 256) return fail(h, DQMC_ERR_INVALID, "dqmc_set_square_tp_factors: n_sites must be 256");
+    if (h->prepared) return fail(h, DQMC_ERR_STATE, "dqmc_set_square_tp_factors: call before dqmc_prepare");
+    if (!h->slab || h->cb.on || h->sw.no_kron || h->kron) return DQMC_OK;  // a path that does not take them: kept
+    const int nb = h->nb;
+    std::vector<double> E((size_t)2 * nb * h->nn);
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(E.data(), h->eT2, sizeof(double) * nb * h->nn, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(E.data() + (size_t)nb * h->nn, h->eTinv2, sizeof(double) * nb * h->nn, hipMemcpyDeviceToHost));
+    // [eT2, eTinv2, eT2', eTinv2'] x [x, y, d, a] x nb x 256
+    std::vector<double> img((size_t)4 * 4 * nb * 256);
+    for (int b = 0; b < nb; ++b)
+        for (int m = 0; m < 2; ++m) {
+            const double *fb = f + (size_t)b * 2048 + (size_t)m * 1024;
+            if (!ttp_factor_ok(E.data() + ((size_t)m * nb + b) * h->nn, fb, fb + 256, fb + 512, fb + 768))
+                return fail(h, DQMC_ERR_INVALID, "dqmc_set_square_tp_factors: the factors do not reproduce eT2 / eTinv2 of block " +
+                                                     std::to_string(b) + " within 256 ulp");
+            for (int k = 0; k < 4; ++k) {
+                double *o = img.data() + (((size_t)m * 4 + k) * nb + b) * 256, *ot = o + (size_t)2 * 4 * nb * 256;
+                for (int j = 0; j < 16; ++j)
+                    for (int i = 0; i < 16; ++i) {
+                        o[i + 16 * j] = fb[256 * k + i + 16 * j];
+                        ot[i + 16 * j] = fb[256 * k + j + 16 * i];
+                    }
+            }
+        }
+    CHK(dalloc(h, &h->kron_f, img.size()));
+    HIPCHK(hipMemcpy(h->kron_f, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice));
+    h->kron_fa = 256;
+    h->kron_fb = 768;  // Fy, then Fd, then Fa
+    h->ttp = h->tri = h->kron = true;
     return DQMC_OK;
 }
 

@@ -135,6 +135,9 @@ hipError_t launch_kron3_chain(const KronArgs &a, hipStream_t s, hipEvent_t start
 // The same chains on the triangular 16 x 16 lattice (n = 256) with A_s = (Fy (x) Fx) Ed (tri.hip): ax = Fx and ay = Fy of
 // block b at + 256 b, and Fd (applied along the diagonals x - y = const) at ay + 256 (nb + b)
 hipError_t launch_tri_chain(const KronArgs &a, hipStream_t s, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
+// The same chains on the t-t' square 16 x 16 lattice (n = 256) with A_s = (Fy (x) Fx) Ed Ea (ttp.hip): ax, ay and Fd as for
+// launch_tri_chain, and Fa (applied along the anti-diagonals x + y = const) at ay + 256 (2 nb + b)
+hipError_t launch_ttp_chain(const KronArgs &a, hipStream_t s, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
 
 // Column-pivoted Householder QR, in place (udt_AVX_pivot! "QR decomposition" loop,
 // src/linalg/UDT.jl:212-246).  On exit A holds R on/above the diagonal and the

@@ -94,6 +94,23 @@ def triangular_factors(model, delta_tau):
     return np.ascontiguousarray(np.tile(per_block, model.flv))
 
 
+def square_tp_factors(model, delta_tau):
+    """The factors dqmc_set_square_tp_factors takes for a model with next-nearest-neighbour hopping tp on SquareLattice(16):
+    per block [eT2: Fx Fy Fd Fa][eTinv2: Fx Fy Fd Fa], each 16 x 16 column-major, such that eT2 = (Fy (x) Fx) Ed(Fd) Ea(Fa)
+    (and eTinv2 alike) in the site order x + 16 y, where Ed applies Fd along the diagonals x - y = const and Ea applies Fa
+    along the anti-diagonals x + y = const.  T = -mu - t (X + X' + Y + Y') - tp (D + D' + A + A') with X, Y, D = XY and
+    A = X Y^-1 commuting shifts, so exp(-dtau T) = e^{dtau mu} f_t(X) f_t(Y) f_tp(D) f_tp(A), f_s = exp(dtau s (S + S')) on a
+    16-ring; mu is folded into Fx.  The engine checks them against the dense exponentials."""
+    L = 16
+    S = np.roll(np.eye(L), 1, axis=0)
+    ring = -model.t * (S + S.T)
+    ex, exi = _ring_exponentials(ring - model.mu * np.eye(L), delta_tau)
+    e1, e1i = _ring_exponentials(ring, delta_tau)
+    ep, epi = _ring_exponentials(-model.tp * (S + S.T), delta_tau)
+    per_block = np.concatenate([m.reshape(-1, order="F") for m in (ex, e1, ep, ep, exi, e1i, epi, epi)])
+    return np.ascontiguousarray(np.tile(per_block, model.flv))
+
+
 def checkerboard_exponentials(T, lattice, delta_tau, return_factors=False):
     """CheckerboardTrue (init_checkerboard_matrices, stack.jl:185-235; slice_matrices.jl:79-222;
     _greens! DQMC.jl:731-750) as the four constant matrices of the dense code path.  The reference
@@ -241,6 +258,8 @@ class DQMC:
                  **kw):
         self.model = model
         self.checkerboard = bool(checkerboard)
+        if getattr(model, "tp", 0.0) != 0.0 and self.checkerboard:
+            raise ValueError("checkerboard: the bond table has no diagonal bonds, so it cannot decompose a model with tp != 0")
         # what save() writes down so that load() can construct and configure the object again
         self._ctor = dict(n_walkers=int(n_walkers), seed=int(seed), first_walker=int(first_walker),
                           checkerboard=checkerboard if isinstance(checkerboard, str) else bool(checkerboard),
@@ -307,6 +326,13 @@ class DQMC:
         if isinstance(l, TriangularLattice) and l.Lx == l.Ly == 16 and not self.checkerboard:
             f = triangular_factors(model, self.p.delta_tau)
             rc = lib().dqmc_set_triangular_factors(self._h, dptr(f))
+            if rc != _ERR_INVALID:
+                self._c(rc)
+        # the t-t' square 16 x 16 lattice: its exponentials in four-factor form (ttp.hip), under the same gate
+        from .lattices import SquareLattice
+        if isinstance(l, SquareLattice) and l.L == 16 and getattr(model, "tp", 0.0) != 0.0 and not self.checkerboard:
+            f = square_tp_factors(model, self.p.delta_tau)
+            rc = lib().dqmc_set_square_tp_factors(self._h, dptr(f))
             if rc != _ERR_INVALID:
                 self._c(rc)
         # rand(DQMC, m, slices) per walker (DQMC.jl:273), then the Metropolis stream
@@ -537,14 +563,30 @@ class DQMC:
     _LATTICES = {"SquareLattice": ("L",), "Chain": ("sites",), "CubicLattice": ("dim", "L"),
                  "TriangularLattice": ("L", "Lx", "Ly")}  # class -> the attributes its constructor takes, in order
 
+    @staticmethod
+    def _model_entry(m):
+        """the "model" entry of a checkpoint preamble: the class and the keywords that construct it again"""
+        model = {"class": type(m).__name__, "U": m.U, "t": m.t}
+        if m.kind == _lib.ATTRACTIVE or m.mu != 0.0:  # (an undoped repulsive model is written as it always was)
+            model["mu"] = m.mu
+        if getattr(m, "tp", 0.0) != 0.0:  # (absent at 0: the preamble of before)
+            model["tp"] = m.tp
+        return model
+
+    @classmethod
+    def _model_from_entry(cls, entry, l):
+        from . import models as _mod
+        mdl = dict(entry)
+        if mdl["class"] not in cls._MODELS:
+            raise _ckpt.CheckpointError("the checkpoint names an unknown model or lattice")
+        return getattr(_mod, mdl.pop("class"))(l=l, **mdl)
+
     def _preamble(self, sweep, mid_sweep):
         m, l, p = self.model, self.model.l, self.p
         if type(m).__name__ not in self._MODELS or type(l).__name__ not in self._LATTICES:
             raise ValueError("save(): %s on %s is not a model / lattice a checkpoint can name"
                              % (type(m).__name__, type(l).__name__))
-        model = {"class": type(m).__name__, "U": m.U, "t": m.t}
-        if m.kind == _lib.ATTRACTIVE or m.mu != 0.0:  # (an undoped repulsive model is written as it always was)
-            model["mu"] = m.mu
+        model = self._model_entry(m)
         tables = {}
         for name, entry in self._tables.items():
             tables[name] = {"table": _ckpt.pack_table(entry[0]), "count": entry[1]}
@@ -604,15 +646,15 @@ class DQMC:
         """load(filename) (FileIO.jl:95-156): an object constructed and configured as the saved one, with its state
         imported (set_state) on device `device_id`.  seed and first_walker are the saved ones, so the files of the ranks of
         a sharded run give back distinct walkers.  last_sweep is the saved one; run() continues behind it."""
-        from . import lattices as _lat, models as _mod
+        from . import lattices as _lat
         pre, blob = _ckpt.read(path)
         if pre.get("format") != 1:
             raise _ckpt.CheckpointError("checkpoint preamble format %r, this package reads format 1" % (pre.get("format"),))
-        lat, mdl = pre["lattice"], dict(pre["model"])
-        if lat["class"] not in cls._LATTICES or mdl["class"] not in cls._MODELS:
+        lat = pre["lattice"]
+        if lat["class"] not in cls._LATTICES or pre["model"]["class"] not in cls._MODELS:
             raise _ckpt.CheckpointError("the checkpoint names an unknown model or lattice")
         l = getattr(_lat, lat["class"])(*lat["args"])
-        model = getattr(_mod, mdl.pop("class"))(l=l, **mdl)
+        model = cls._model_from_entry(pre["model"], l)
         kw = dict(pre["dqmc"])
         mc = cls(model, device_id=device_id, **kw)
         try:
@@ -1674,6 +1716,7 @@ class DQMC:
         factor i of the current j = i J, so it carries i^2 = -1 (fixed on free fermions: tests/response_ref.py).
         With the response_current binner on and at least two walkers every key X also has X_std_error: the cross-walker
         error of the per-walker values formed from level 0 of that binner (jackknife_ratio with sign weighting on)."""
+        self._nearest_neighbour_current("superfluid_stiffness")
         kp, km, iL, iT = self._stiffness_indices(axis)
         cr = self.current_response()
         if "kbond" not in cr:
@@ -1914,6 +1957,16 @@ class DQMC:
         res["omega"] = omega
         return res
 
+    def _nearest_neighbour_current(self, who):
+        """superfluid_stiffness, drude_weight and dc_conductivity take the current along an axis and its kinetic energy from
+        the two nearest-neighbour bonds along it: with tp != 0 the diagonal bonds carry current along both axes as well,
+        and a number without them would be wrong"""
+        if getattr(self.model, "tp", 0.0) != 0.0:
+            raise NotImplementedError("%s: the current along an axis is taken from the nearest-neighbour bonds only; with "
+                                      "tp != 0 the diagonal bonds carry current as well (not implemented).  "
+                                      "current_response() and current_time_displaced() with K = 9 hold the diagonal bonds"
+                                      % who)
+
     def _axis_bonds(self, axis):
         """(k+, k-, index of q = 0): the current-target columns along +-axis as superfluid_stiffness takes them"""
         if self._dirs is None or self._mom is None:
@@ -1940,6 +1993,7 @@ class DQMC:
         + kbond[-axis] of the recording's own sums, Lambda_m the real part of current_matsubara() at q = 0 (which must be
         in set_momenta's list).  This is the limit q -> 0 first; superfluid_stiffness()["drude"] takes omega = 0 first and
         is fixed to -k_axis by gauge invariance."""
+        self._nearest_neighbour_current("drude_weight")
         kp, km, i0 = self._axis_bonds(axis)
         ct, tau = self._current_tau()
         ms = np.atleast_1d(np.asarray(m, dtype=np.int64))
@@ -1958,6 +2012,7 @@ class DQMC:
     def dc_conductivity(self, axis=0):
         """-> dict(sigma_dc, sigma_dc_std_error, Lambda_half): Trivedi-Randeria's proxy (beta^2 / pi) Lambda_axis,axis(q = 0,
         tau = beta / 2).  ValueError unless slice slices / 2 is a recorded row."""
+        self._nearest_neighbour_current("dc_conductivity")
         kp, km, i0 = self._axis_bonds(axis)
         ct, tau = self._current_tau()
         M, every = self.p.slices, self.current_time_displaced_plan()["every"]
@@ -2014,7 +2069,8 @@ class DQMC:
 
     def kron_hopping(self):
         """True when slice products and wraps apply the hopping exponentials in factored form (16 x 16 Kronecker factors
-        at n = 256, 8 x 8 at n = 512, the triangular 16 x 16 lattice's three factors; include/dqmc_hip.h)"""
+        at n = 256, 8 x 8 at n = 512, the triangular 16 x 16 lattice's three factors, the t-t' square 16 x 16 lattice's four;
+        include/dqmc_hip.h)"""
         f = C.c_int32(0)
         self._c(lib().dqmc_kron_hopping(self._h, C.byref(f)))
         return bool(f.value)
@@ -2028,7 +2084,8 @@ class DQMC:
     def launch_plan(self):
         """dqmc_launch_plan: what the handle decided about its co-resident launch forms at creation, as a dict: units,
         units_padded, cus, udt_sites, udt_blocks (0: one-launch UDT not admitted), qr_coop_blocks, qr_coop (1 / 0),
-        sweep_fused (1 / 0), wrap_blocks and wrap_one_launch (each a pair: without / with a pending sweep chunk)"""
+        sweep_fused (1 / 0), wrap_blocks and wrap_one_launch (each a pair: without / with a pending sweep chunk; the wrap
+        is never one launch on the triangular three-factor and the t-t' four-factor paths)"""
         out = (C.c_int32 * 12)()
         self._c(lib().dqmc_launch_plan(self._h, out))
         v = [int(x) for x in out]

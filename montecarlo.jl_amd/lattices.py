@@ -18,7 +18,9 @@ class AbstractLattice:
 
 
 class SquareLattice(AbstractLattice):
-    """SquareLattice(L): neighs rows = up, right, down, left (square.jl:47-60)."""
+    """SquareLattice(L): neighs rows = up, right, down, left (square.jl:47-60).  nnn rows = upright, downright, downleft,
+    upleft: the four next-nearest (diagonal) neighbours, built with the same circshift convention (an extension: the
+    reference's square lattice has no such table)."""
 
     def __init__(self, L):
         self.L = L
@@ -30,6 +32,8 @@ class SquareLattice(AbstractLattice):
         down = np.roll(lat, 1, axis=0)
         left = np.roll(lat, 1, axis=1)
         self.neighs = np.vstack([x.reshape(-1, order="F") for x in (up, right, down, left)]).astype(np.int64)
+        diag = [np.roll(lat, s, axis=(0, 1)) for s in ((-1, -1), (1, -1), (1, 1), (-1, 1))]
+        self.nnn = np.vstack([x.reshape(-1, order="F") for x in diag]).astype(np.int64)
         self.n_bonds = 2 * self.sites
         bonds = np.zeros((self.n_bonds, 3), dtype=np.int64)
         b = 0
@@ -37,6 +41,12 @@ class SquareLattice(AbstractLattice):
             bonds[b] = (src, self.neighs[0, src - 1], 0); b += 1
             bonds[b] = (src, self.neighs[1, src - 1], 0); b += 1
         self.bonds = bonds
+
+    def next_neighbors(self, directed=False):
+        """the diagonal neighbours as neighbors() lists the nearest ones: directed, src-major (src, trg) over the rows of
+        nnn; else every diagonal bond once (src, its upright and its downright neighbour)"""
+        rows = self.nnn if directed else self.nnn[:2]
+        return [(src + 1, int(trg)) for src in range(self.sites) for trg in rows[:, src]]
 
 
 class Chain(AbstractLattice):

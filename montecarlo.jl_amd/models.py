@@ -8,6 +8,21 @@ import numpy as np
 from .lattices import Chain, CubicLattice, SquareLattice
 
 
+def _check_tp(tp, l):
+    """next-nearest-neighbour hopping is defined on the square lattice only"""
+    tp = float(tp)
+    if tp != 0.0 and not isinstance(l, SquareLattice):
+        raise ValueError("tp != 0 needs a SquareLattice, not %s" % type(l).__name__)
+    return tp
+
+
+def _add_tp(T, l, tp):
+    """-tp at T[trg, src] for the four diagonal neighbours of every source (+=, as the nearest neighbours are added: at
+    L = 2 the coinciding diagonals count twice)"""
+    for src, trg in l.next_neighbors(True):
+        T[trg - 1, src - 1] += -tp
+
+
 def choose_lattice(dims, L):
     """HubbardModel.jl:23-31"""
     if dims == 1:
@@ -18,15 +33,17 @@ def choose_lattice(dims, L):
 
 
 class HubbardModelAttractive:
-    """HubbardModelAttractive.jl:26-39; U is stored positive."""
+    """HubbardModelAttractive.jl:26-39; U is stored positive.  `tp` is the next-nearest-neighbour hopping t' of
+    H = -t sum_<ij> - t' sum_<<ij>> - mu sum n + U-term on a SquareLattice (an extension; tp = 0: the reference's matrices)."""
     flv = 1
     kind = 0
 
-    def __init__(self, L=None, dims=None, l=None, U=1.0, t=1.0, mu=0.0):
+    def __init__(self, L=None, dims=None, l=None, U=1.0, t=1.0, mu=0.0, tp=0.0):
         if U < 0:
             raise ValueError("U must be positive.")  # @assert U >= 0.
         self.l = l if l is not None else choose_lattice(dims, L)
         self.U, self.t, self.mu = float(U), float(t), float(mu)
+        self.tp = _check_tp(tp, self.l)
 
     def hopping_matrix(self):
         """HubbardModelAttractive.jl:78-91"""
@@ -34,20 +51,24 @@ class HubbardModelAttractive:
         T = np.diag(np.full(N, -self.mu))
         for src, trg in self.l.neighbors(True):
             T[trg - 1, src - 1] += -self.t
+        if self.tp != 0.0:
+            _add_tp(T, self.l, self.tp)
         return [T]
 
 
 class HubbardModelRepulsive:
     """HubbardModelRepulsive.jl:24-41; two spin blocks (BlockDiagonal, :68-69).  The reference fixes mu at 0; here `mu`
-    dopes the model: -mu on the diagonal of both blocks, as in the attractive model (mu = 0: the reference's matrices)."""
+    dopes the model: -mu on the diagonal of both blocks, as in the attractive model (mu = 0: the reference's matrices).
+    `tp`: the next-nearest-neighbour hopping t' on a SquareLattice, as in the attractive model."""
     flv = 2
     kind = 1
 
-    def __init__(self, L=None, dims=None, l=None, U=1.0, t=1.0, mu=0.0):
+    def __init__(self, L=None, dims=None, l=None, U=1.0, t=1.0, mu=0.0, tp=0.0):
         if U < 0:
             raise ValueError("U must be positive.")
         self.l = l if l is not None else choose_lattice(dims, L)
         self.U, self.t, self.mu = float(U), float(t), float(mu)
+        self.tp = _check_tp(tp, self.l)
 
     def hopping_matrix(self):
         """HubbardModelRepulsive.jl:87-100: BlockDiagonal(T, copy(T)), with -mu on the diagonal"""
@@ -57,6 +78,8 @@ class HubbardModelRepulsive:
             T[np.diag_indices(N)] = -self.mu
         for src, trg in self.l.neighbors(True):
             T[trg - 1, src - 1] += -self.t
+        if self.tp != 0.0:
+            _add_tp(T, self.l, self.tp)
         return [T, T.copy()]
 
 
