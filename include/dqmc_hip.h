@@ -1193,6 +1193,108 @@ typedef struct {
 /* level < 0: the reliable level (the last one with count >= 32, else 0) */
 int dqmc_mc_fss_binner_finish(dqmc_mc_handle *h, int32_t walker, int32_t level, dqmc_mc_fss_binned *out);
 
+/* ---- the SAC flavor: stochastic analytic continuation -----------------------------------------------------------
+ * A(omega) from imaginary-time data by sampling (Sandvik, PRB 57, 10287; Beach, cond-mat/0403055; Shao and Sandvik,
+ * Phys. Rep. 1003), batched over P independent problems (momenta) and R sampling temperatures each (csrc/sac.hip).
+ * The reference has nothing of the kind: like the cluster move and replica exchange this is a defined extension, and
+ * this comment is the definition (tests/sac_ref.py restates it).  fl(.) is one IEEE fp64 rounding; the object file is
+ * compiled with -ffp-contract=off, so no product is fused into a sum.
+ *
+ * A problem p < P has Nt data points g[i], weights w[i] = 1 / sigma_i^2 and a kernel table Kt[j][i], j < Nw, stored
+ * grid-major (the Nt values of one grid point are contiguous).  The host has rotated g and Kt into the eigenbasis of the
+ * covariance; the device never sees a covariance.  The spectrum is Nd delta functions of equal amplitude
+ * a = fl(norm / Nd) at integer grid positions x[d].  Limits: 1 <= Nt <= 256, 1 <= Nd <= 4096, 2 <= Nw <= 65535.
+ *
+ * A chain is (p, r), r < R <= 16, with sampling temperature theta[p][r] > 0.  Its state is x[Nd] (uint16), the residual
+ * res[i] = a sum_d Kt[x_d][i] - g[i], chi2 = sum_i w_i res_i^2 and a move counter m (moves since dqmc_sac_seed).  Its
+ * uniform u(m, t), t in {0, 1}, is Philox4x32-10 made into a uniform as philox4_uniform (csrc/kernels.h) does, with
+ * key = the chain's seed and counter words (low32(m), high32(m), t, 0).  Both uniforms of a move are consumed whatever
+ * the move does, so m alone positions the stream.
+ *
+ * The lane sum L(t) of t[0 .. Nt): p_l = t[l] + t[l + 64] + .. in increasing index for l < 64, entries at and above Nt
+ * being +0.0 (with one entry per lane p_l is that entry); then p_l <- p_l + p_{l xor off} for off = 32, 16, 8, 4, 2, 1;
+ * L = p_0.  In numpy: pad to a multiple of 64, add the rows of the [.][64] image in order, then
+ * while len(p) > 1: h = len(p) // 2; p = p[:h] + p[h:].
+ *
+ * A sweep makes Nd moves, d = 0 .. Nd - 1 in order; move d has counter m and leaves m + 1:
+ *   x' = x_d + (int)floor(fl(u(m, 0) (2 win + 1))) - win, win >= 1 the chain's window.  x' outside [0, Nw): rejected.
+ *   Otherwise D_i = fl(a fl(Kt[x'][i] - Kt[x_d][i])), t_i = fl(fl(w_i D_i) fl(fl(2 res_i) + D_i)), dchi = L(t);
+ *   accept iff dchi <= 0 || u(m, 1) < exp(fl(-dchi / fl(2 theta))) (the exponential only when dchi > 0; the device's exp
+ *   and the host's may differ in the last bit, which decides with probability ~1e-16 per move);
+ *   on accept res_i <- fl(res_i + D_i), chi2 <- fl(chi2 + dchi), x_d <- x'.
+ * prop counts every move, acc the accepted ones, both from the creation of the handle.
+ *
+ * After the sweep with global index i (first_sweep_index, first_sweep_index + 1, ..), in this order:
+ *  - refresh, iff refresh > 0 && i % refresh == 0: S_i = Kt[x_0][i] + Kt[x_1][i] + .. added in increasing d from +0.0,
+ *    res_i = fl(fl(a S_i) - g_i), fresh = L(fl(fl(w_i res_i) res_i)); max_drift = max(max_drift, |chi2 - fresh|), then
+ *    chi2 = fresh.  dqmc_sac_set_problem and dqmc_sac_set_conf build res and chi2 the same way.
+ *  - an exchange round, iff rate > 0 && R >= 2 && i % rate == 0.  The handle keeps a cursor X, the rounds since
+ *    dqmc_sac_set_exchange.  Round X tries the pairs (r, r + 1) of every problem with r = X (mod 2), r + 1 < R:
+ *    q = fl(fl(fl(1 / fl(2 theta_r)) - fl(1 / fl(2 theta_{r+1}))) fl(chi2_r - chi2_{r+1})); the pair swaps iff
+ *    q >= 0 || u < exp(q), u = Philox4x32-10 with the key of slot r and counter words (low32(X), high32(X), 0, 1): a
+ *    domain of its own (the moves have word 3 = 0), formed only when it decides.  As in dqmc_mc_set_exchange theta,
+ *    seed, move counter, window, sums, histogram and counters stay with the slot (p, r); the configuration (x, res,
+ *    chi2) and a replica label (at first r) move.  prop_exchange / acc_exchange of slot r count the tries and swaps of
+ *    the pair (r, r + 1).
+ *  - a measurement, iff i > thermalization: hist[x_d] += 1 for every d (uint64), sum_chi2 += chi2,
+ *    sum_chi2_sq += fl(chi2 chi2), min_chi2 = min(min_chi2, chi2), n_meas += 1.
+ * A chain's results depend on its own problem, ladder and seeds only: not on P, not on the other problems, and not on
+ * how n_sweeps is split over calls of dqmc_sac_sweep.  Errors come from dqmc_sac_last_error. */
+typedef struct dqmc_sac_handle dqmc_sac_handle;
+
+typedef struct {
+    int32_t n_problems;  /* P */
+    int32_t n_tau;       /* Nt */
+    int32_t n_deltas;    /* Nd */
+    int32_t n_omega;     /* Nw */
+    int32_t n_replicas;  /* R */
+    int32_t device_id;
+    int32_t window;      /* every chain's window at first, in 1..2^24 */
+    const double *theta; /* R values every problem's ladder starts with; NULL: 1.0 */
+} dqmc_sac_params;
+
+typedef struct {
+    double chi2;                            /* of the configuration now in the slot */
+    double sum_chi2, sum_chi2_sq, min_chi2; /* over the measurements; min_chi2 = +inf while n_meas == 0 */
+    double max_drift;                       /* largest |running chi2 - rebuilt chi2| a refresh has seen */
+    int64_t n_meas, prop, acc, prop_exchange, acc_exchange;
+    int64_t replica;                        /* label of the configuration now in the slot */
+    uint64_t moves_drawn;                   /* m */
+    uint64_t rounds;                        /* the handle's exchange cursor */
+    int32_t window;
+} dqmc_sac_stats;
+
+/* validates the arguments, then the device (no device: DQMC_ERR_NO_DEVICE), as dqmc_mc_create.  Every chain starts with
+ * x = 0, seed 0, m = 0, label r; the tables are zero until dqmc_sac_set_problem */
+int dqmc_sac_create(const dqmc_sac_params *p, dqmc_sac_handle **out);
+int dqmc_sac_destroy(dqmc_sac_handle *h);
+/* message of the last failing call on this handle (h may be NULL: create errors) */
+const char *dqmc_sac_last_error(const dqmc_sac_handle *h);
+/* g[Nt], w[Nt] (finite, >= 0), Kt[Nw][Nt] and norm > 0 of problem p; rebuilds res and chi2 of its R chains */
+int dqmc_sac_set_problem(dqmc_sac_handle *h, int32_t p, const double *g, const double *w, const double *Kt, double norm);
+/* the R sampling temperatures of problem p, each finite and > 0; they need not be monotone */
+int dqmc_sac_set_theta(dqmc_sac_handle *h, int32_t p, const double *theta);
+/* the chain's stream: key = seed, m = 0 */
+int dqmc_sac_seed(dqmc_sac_handle *h, int32_t p, int32_t r, uint64_t seed);
+/* x[Nd], every entry < Nw; set_conf rebuilds res and chi2 and leaves m, the label and every sum alone */
+int dqmc_sac_set_conf(dqmc_sac_handle *h, int32_t p, int32_t r, const uint16_t *x);
+int dqmc_sac_get_conf(dqmc_sac_handle *h, int32_t p, int32_t r, uint16_t *x);
+/* the chain's window, in 1..2^24 (it may exceed Nw) */
+int dqmc_sac_set_window(dqmc_sac_handle *h, int32_t p, int32_t r, int32_t win);
+/* rate = k > 0: dqmc_sac_sweep runs one round after every sweep whose global index is a multiple of k; 0: none.
+ * Resets the cursor, the labels and the exchange counters */
+int dqmc_sac_set_exchange(dqmc_sac_handle *h, int32_t rate);
+/* n_sweeps sweeps of every chain with global indices first_sweep_index (>= 1) ..; refresh >= 0 (0: never).  Split into
+ * launches of bounded work; complete on return */
+int dqmc_sac_sweep(dqmc_sac_handle *h, int32_t n_sweeps, int64_t first_sweep_index, int64_t thermalization,
+                   int32_t refresh);
+int dqmc_sac_get_stats(dqmc_sac_handle *h, int32_t p, int32_t r, dqmc_sac_stats *out);
+/* hist[Nw] of the slot (p, r) */
+int dqmc_sac_get_histogram(dqmc_sac_handle *h, int32_t p, int32_t r, uint64_t *hist);
+/* clears hist, sum_chi2, sum_chi2_sq, min_chi2 and n_meas of every chain; the chains, prop, acc, the exchange counters
+ * and max_drift stay */
+int dqmc_sac_reset_accumulators(dqmc_sac_handle *h);
+
 /* ---- instrumentation ------------------------------------------------------ */
 /* Per-kernel-family device time accumulated with HIP events on the handle's
  * stream when enabled (off by default; used by bench.py's roofline leg). */

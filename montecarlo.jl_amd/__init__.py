@@ -20,5 +20,7 @@ from .dqmc import (DQMC, DQMCParameters, CurrentTauSums, matsubara_trapezoid, ca
                    udt_AVX_pivot, vmul)
 
 from .mc import MC, IsingModel, IsingTc, greedy_colouring, reciprocal_vectors  # noqa: F401
+from . import sac  # noqa: F401
+from .sac import SAC, boson_symmetric_kernel, fermion_kernel  # noqa: F401
 
 lib()  # fail loudly at import time if the HIP library has not been built

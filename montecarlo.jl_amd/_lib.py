@@ -104,6 +104,19 @@ class McFssBinned(C.Structure):
                 ("n_k", C.c_int32)]
 
 
+class SacParams(C.Structure):
+    _fields_ = [("n_problems", C.c_int32), ("n_tau", C.c_int32), ("n_deltas", C.c_int32), ("n_omega", C.c_int32),
+                ("n_replicas", C.c_int32), ("device_id", C.c_int32), ("window", C.c_int32),
+                ("theta", C.POINTER(C.c_double))]
+
+
+class SacStats(C.Structure):
+    _fields_ = [("chi2", C.c_double), ("sum_chi2", C.c_double), ("sum_chi2_sq", C.c_double), ("min_chi2", C.c_double),
+                ("max_drift", C.c_double), ("n_meas", C.c_int64), ("prop", C.c_int64), ("acc", C.c_int64),
+                ("prop_exchange", C.c_int64), ("acc_exchange", C.c_int64), ("replica", C.c_int64),
+                ("moves_drawn", C.c_uint64), ("rounds", C.c_uint64), ("window", C.c_int32)]
+
+
 _dp = C.POINTER(C.c_double)
 _i64p = C.POINTER(C.c_int64)
 _H = C.c_void_p
@@ -278,6 +291,20 @@ SIGNATURES = {
     "dqmc_mc_get_fss": (C.c_int, [_H, C.c_int32, C.POINTER(McFss)]),
     "dqmc_mc_fss_binner_get_level": (C.c_int, [_H, C.c_int32, C.c_int32, _dp, _dp, _dp, _i64p]),
     "dqmc_mc_fss_binner_finish": (C.c_int, [_H, C.c_int32, C.c_int32, C.POINTER(McFssBinned)]),
+    "dqmc_sac_create": (C.c_int, [C.POINTER(SacParams), C.POINTER(_H)]),
+    "dqmc_sac_destroy": (C.c_int, [_H]),
+    "dqmc_sac_last_error": (C.c_char_p, [_H]),
+    "dqmc_sac_set_problem": (C.c_int, [_H, C.c_int32, _dp, _dp, _dp, C.c_double]),
+    "dqmc_sac_set_theta": (C.c_int, [_H, C.c_int32, _dp]),
+    "dqmc_sac_seed": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_uint64]),
+    "dqmc_sac_set_conf": (C.c_int, [_H, C.c_int32, C.c_int32, C.POINTER(C.c_uint16)]),
+    "dqmc_sac_get_conf": (C.c_int, [_H, C.c_int32, C.c_int32, C.POINTER(C.c_uint16)]),
+    "dqmc_sac_set_window": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32]),
+    "dqmc_sac_set_exchange": (C.c_int, [_H, C.c_int32]),
+    "dqmc_sac_sweep": (C.c_int, [_H, C.c_int32, C.c_int64, C.c_int64, C.c_int32]),
+    "dqmc_sac_get_stats": (C.c_int, [_H, C.c_int32, C.c_int32, C.POINTER(SacStats)]),
+    "dqmc_sac_get_histogram": (C.c_int, [_H, C.c_int32, C.c_int32, C.POINTER(C.c_uint64)]),
+    "dqmc_sac_reset_accumulators": (C.c_int, [_H]),
     "dqmc_timing_enable": (C.c_int, [_H, C.c_int32]),
     "dqmc_timing_get": (C.c_int, [_H, _dp, _i64p]),
     "dqmc_mfma_f64_peak": (C.c_int, [C.c_int32, C.c_int32, _dp]),

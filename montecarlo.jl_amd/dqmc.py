@@ -1521,6 +1521,39 @@ class DQMC:
                 res[src + "k"] = m[src] @ Ct
         return res
 
+    def spectral_function(self, omega, momenta=None, run=None, **sac_args):
+        """A(k, omega) from G(k, tau) by stochastic analytic continuation on the device (sac.SAC; the fermion kernel
+        with this run's beta, norm 1) -> dict(omega [Nw], A, weight [n_blocks, n_k, Nw], chi2, theta [n_blocks, n_k],
+        momenta, sac).  The data are Re Gk_l0 of momentum_time_displaced(), the errors Gk_l0_std_error_re of
+        binned("momentum_time_displaced"): the binner holds no tau-tau' covariances, so the diagonal form of chi2 is
+        used and correlations between time slices are ignored.  `momenta` picks rows of momenta() (default: all); `run`
+        is the keyword dict of SAC.run, the other keywords go to SAC (n_deltas, thetas, seed, ...).  Errors below
+        `error_floor` (default 1e-6) are raised to it.  Needs enable_binning("momentum_time_displaced"); refused with
+        sign weighting on, whose <s G> / <s> errors are not those of a plain mean."""
+        from .sac import SAC, fermion_kernel
+        if self.sign_weighting():
+            raise _lib.DQMCError(_lib.ERR_STATE, "spectral_function: not available with sign weighting on")
+        if not self._binning_enabled("momentum_time_displaced"):
+            raise _lib.DQMCError(_lib.ERR_STATE, 'spectral_function: call enable_binning("momentum_time_displaced") first')
+        floor = float(sac_args.pop("error_floor", 1e-6))
+        b = self.binned("momentum_time_displaced")
+        if "Gk_l0" not in b:
+            raise _lib.DQMCError(_lib.ERR_STATE, "spectral_function: the Green's rows are not recorded (set_time_displaced)")
+        ks = np.arange(b["Gk_l0"].shape[2]) if momenta is None else np.asarray(momenta, dtype=np.int64).reshape(-1)
+        G = self.momentum_time_displaced()["Gk_l0"].real[:, :, ks]   # [n_blocks, R, n_k]
+        err = np.asarray(b["Gk_l0_std_error_re"])[:, :, ks]
+        if not np.all(np.isfinite(err)):
+            raise _lib.DQMCError(_lib.ERR_STATE, "spectral_function: the binner has no error yet (too few samples)")
+        nb, nt, nk = G.shape
+        flat = lambda v: np.ascontiguousarray(np.moveaxis(v, 1, 2).reshape(nb * nk, nt))
+        s = SAC(np.asarray(b["tau"], dtype=np.float64), flat(G), error=np.maximum(flat(err), floor), kernel=fermion_kernel,
+                omega=omega, beta=self.p.beta, device_id=self._device_id, **sac_args)
+        s.run(**(run or {}))
+        sp = s.spectrum()
+        return {"omega": sp["omega"], "A": sp["A"].reshape(nb, nk, -1), "weight": sp["weight"].reshape(nb, nk, -1),
+                "chi2": sp["chi2"].reshape(nb, nk), "theta": sp["theta"].reshape(nb, nk), "momenta": self.momenta()[ks],
+                "sac": s}
+
     def _binned_momentum(self, which, level=None):
         """binned() of a momentum binner: the keys of structure_factors() / static_susceptibilities() /
         momentum_time_displaced(), each X with X_std_error, X_std_error_walkers and X_tau; for the complex Gk_l0, Gk_0l the
