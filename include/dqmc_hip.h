@@ -501,6 +501,55 @@ enum { DQMC_BIN_MOMENTUM_CORRELATIONS = 11, DQMC_BIN_MOMENTUM_SUSCEPTIBILITIES =
 int dqmc_set_momenta(dqmc_handle *h, int32_t n_q, const double *cos_tab, const double *sin_tab);
 int dqmc_momenta_plan(dqmc_handle *h, int32_t out[4]);   /* [n_q, n_dirs, tile rows, tile cols], zeros when off */
 
+/* ---- tau-tau' covariance of G(k, tau) and of the tau-resolved correlations ----------------------------------------
+ * A binner keeps each element's own variance.  An analytic continuation of G(k, tau) needs the covariance between the
+ * time slices of one momentum, which no binner holds: data of one Markov chain are strongly correlated between
+ * neighbouring tau.  The reference has no such measurement; this is a defined extension.
+ * A SERIES is the R values along tau of one (row group, block or channel, q) of the DQMC_BIN_MOMENTUM_TIME_DISPLACED
+ * sample above.  dqmc_set_tau_covariance(h, bin_size, what): `what` is a non-empty mask of DQMC_TD_GREENS (the [Gl0 C]
+ * rows, Re G(k, tau): series b n_q + q, b < n_blocks) and DQMC_TD_DENSITY ([CDC][SDCx][SDCy][SDCz]: series
+ * (channel) n_q + q behind the Green's series, if any), S = (n_blocks [GREENS] + 4 [DENSITY]) n_q series in all; bin_size
+ * >= 1 consecutive samples are averaged into one bin.  bin_size == 0 turns it off and frees everything (the default).
+ * DQMC_ERR_INVALID for bin_size < 0 or a mask that is empty or has other bits; DQMC_ERR_STATE before dqmc_set_momenta or
+ * dqmc_set_time_displaced, for rows the recording does not hold, and with sign weighting on (the sample is then s x, and
+ * the covariance of a ratio is another estimator); the handle keeps its setting.  Whatever frees the momentum
+ * time-displaced binner (dqmc_set_momenta, dqmc_set_pair_directions, dqmc_set_time_displaced) turns it off, and so does
+ * switching sign weighting on.  The momentum binner itself need not be enabled: the accumulator then runs the same
+ * transform into a sample of its own.
+ * State per walker w and series s: the open bin's sum a[R], a shift c[R], S1[R], S2[R][R] (row-major, full), and the
+ * number of closed bins.  Once per dqmc_accumulate_susceptibilities pass, on the handle's stream behind the momentum
+ * binner's push, with x the series of the pass's sample:
+ *     a += x;  and when the pass is the bin_size-th of its bin:
+ *     b = a / bin_size;  c = b if it is the walker's first bin;  d = b - c;  S1 += d;  S2[r][r'] += d[r] d[r'];  a = 0.
+ * The samples of an unfinished bin are part of no result.  The mean of the bins is c + S1 / nb and their scatter matrix
+ * S2 - S1 S1^T / nb (dqmc.py: tau_covariance_from_moments pools walkers and ranks).  The shift is part of the definition:
+ * G(k, tau) is O(1) with errors of 1e-3 and below, so the unshifted sum of products minus the product of means would
+ * cancel six and more digits, and an eigendecomposition that keeps modes down to 1e-10 of the largest would weight that
+ * loss by 1 / lambda.  With the shift the sums hold deviations only.
+ * Every stored value is one accumulator, updated once per closed bin in ascending order with no atomics: the state
+ * depends on the walker's samples only, a second run gives the same bits, and S2 is exactly symmetric (the two products
+ * commute).  csrc/taucov.hip: one workgroup per (walker, series), four series per workgroup for R <= 16; a pass that
+ * closes no bin touches R doubles per series, a closing one streams S2 once (2 R^2 doubles per series).  R <= 2048.
+ * Memory: n_walkers S (R^2 + 3 R) doubles, and the n_walkers E doubles of the sample.  A failed allocation returns the
+ * HIP error and leaves the feature off.  dqmc_tau_covariance_plan: out = [bin_size, S, R, bytes, closed bins], zeros when
+ * off.  dqmc_tau_covariance_get copies the moments to the host: n_bins [n_walkers], shift, S1 [n_walkers][S][R], S2
+ * [n_walkers][S][R][R]; any may be NULL; DQMC_ERR_STATE when off.  dqmc_reset_accumulators clears everything, the open
+ * bin and the shifts included.  The moments are not part of the state blob: a checkpoint of a handle with the
+ * accumulator on would lose them, and the host refuses to write one (dqmc.py: save).  With the accumulator off nothing is
+ * allocated or launched, and every result, reduction buffer and state blob is byte for byte that of a handle that never
+ * called dqmc_set_tau_covariance; with it on every other result still is.
+ * The same kernel on samples of the caller's (an observable of its own), as dqmc_binner_user_create / _push:
+ * dqmc_user_covariance(h, n_series, R, bin_size) (bin_size == 0: off; DQMC_ERR_INVALID for n_series < 1, R < 1,
+ * R > 2048, bin_size < 0), then per sample dqmc_user_covariance_push with a device buffer [n_walkers][n_series][R],
+ * complete when the call is made; the call returns when it has been read.  _plan and _get as above. */
+int dqmc_set_tau_covariance(dqmc_handle *h, int32_t bin_size, int32_t what);
+int dqmc_tau_covariance_plan(dqmc_handle *h, int64_t out[5]);
+int dqmc_tau_covariance_get(dqmc_handle *h, int64_t *n_bins, double *shift, double *S1, double *S2);
+int dqmc_user_covariance(dqmc_handle *h, int64_t n_series, int32_t R, int32_t bin_size);
+int dqmc_user_covariance_push(dqmc_handle *h, const double *device_samples);
+int dqmc_user_covariance_plan(dqmc_handle *h, int64_t out[5]);
+int dqmc_user_covariance_get(dqmc_handle *h, int64_t *n_bins, double *shift, double *S1, double *S2);
+
 /* ---- measurement reduction over ranks -------------------
  * One process (or thread) per GPU; walkers never interact, the only collective is the reduction of the measurement
  * sums every `measure_rate` sweeps (DQMC.jl:429-436).  dqmc_reduce packs EVERY accumulator of the handle (Green's

@@ -15,7 +15,8 @@ from .models import (HubbardModel, HubbardModelAttractive, HubbardModelRepulsive
 from .sharding import (Communicator, reduce_accumulators, walker_block, walker_range,  # noqa: F401
                        walker_seeds)
 from .dqmc import (DQMC, DQMCParameters, CurrentTauSums, matsubara_trapezoid, calculate_greens_AVX, device_count,  # noqa: F401
-                   checkerboard_exponentials, checkerboard_seqs, checkerboard_slab, checkerboard_tables,
+                   check_covariance_bins, checkerboard_exponentials, checkerboard_seqs, checkerboard_slab, checkerboard_tables,
+                   tau_covariance_from_moments,
                    entanglement_from_pair_sums, finish_moments, hopping_exponentials, logdet_matrices, mfma_f64_peak, rdivp, square_tp_factors, triangular_factors,
                    udt_AVX_pivot, vmul)
 

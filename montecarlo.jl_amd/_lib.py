@@ -207,7 +207,14 @@ SIGNATURES = {
     "dqmc_binner_user_push": (C.c_int, [_H, C.c_void_p]),
     "dqmc_set_momenta": (C.c_int, [_H, C.c_int32, _dp, _dp]),
     "dqmc_momenta_plan": (C.c_int, [_H, C.POINTER(C.c_int32)]),
-    "dqmc_set_pair_channels": (C.c_int, [_H, C.c_int32, _dp]),
+    "dqmc_set_tau_covariance": (C.c_int, [_H, C.c_int32, C.c_int32]),
+    "dqmc_tau_covariance_plan": (C.c_int, [_H, _i64p]),
+    "dqmc_tau_covariance_get": (C.c_int, [_H, _i64p, _dp, _dp, _dp]),
+    "dqmc_user_covariance": (C.c_int, [_H, C.c_int64, C.c_int32, C.c_int32]),
+    "dqmc_user_covariance_push": (C.c_int, [_H, C.c_void_p]),
+    "dqmc_user_covariance_plan": (C.c_int, [_H, _i64p]),
+    "dqmc_user_covariance_get": (C.c_int, [_H, _i64p, _dp, _dp, _dp]),
+    "dqmc_set_pair_channels":(C.c_int, [_H, C.c_int32, _dp]),
     "dqmc_response_plan": (C.c_int, [_H, C.POINTER(C.c_int32)]),
     "dqmc_set_thermodynamics": (C.c_int, [_H, _dp]),
     "dqmc_accumulate_thermodynamics": (C.c_int, [_H]),

@@ -218,6 +218,16 @@ struct dqmc_handle {
         bool fast = false;
         int *src_of = nullptr;
     } td;
+    // tau-tau' covariance accumulators (taucov.inl, taucov.hip): bin_size == 0: off, nothing allocated.  Not sections.
+    // tcov follows the momentum time-displaced sample (what: mask of DQMC_TD_*; sample [W][sample_E]: its own copy of that
+    // sample while the momentum binner is off), ucov the caller's samples.  a, c, s1 [W][S][R], s2 [W][S][R][R]; open:
+    // samples in the unfinished bin, nb: closed bins (every walker's: they close together)
+    struct TauCov {
+        int bin_size = 0, what = 0, R = 0;
+        long S = 0, sample_E = 0;
+        int64_t open = 0, nb = 0;
+        double *a = nullptr, *c = nullptr, *s1 = nullptr, *s2 = nullptr, *sample = nullptr;
+    } tcov, ucov;
     // global moves (global_move.inl): per-walker device state, logabsdet / sign per unit of the current field [0] (valid
     // while gm_cache_version == conf_version) and of a proposal [1]; rate / kind of the hook in the update (0 = off)
     GlobalMoveState *gm = nullptr;
@@ -1536,6 +1546,9 @@ static void ctd_off(dqmc_handle *h);   // (the stream must be idle)
 static int ctd_row(dqmc_handle *h, int row, double cc_fac, const double *g0l, const double *gl0, const double *gll,
                    double *add_to, long add_stride, long add_off);
 static int ctd_finish(dqmc_handle *h, double cc_fac);
+static int tcov_reset(dqmc_handle *h);  // taucov.inl
+static void tcov_off(dqmc_handle *h);   // (the stream must be idle)
+static int tcov_push(dqmc_handle *h);   // behind mom_push of DQMC_BIN_MOMENTUM_TIME_DISPLACED
 int dqmc_destroy(dqmc_handle *h)
 {
     if (!h) return DQMC_OK;
@@ -2017,6 +2030,7 @@ int dqmc_reset_accumulators(dqmc_handle *h)
     CHK(binner_reset(h));
     CHK(ent_reset(h));
     CHK(ctd_reset(h));
+    CHK(tcov_reset(h));
     return DQMC_OK;
 }
 
@@ -2059,6 +2073,7 @@ int dqmc_export_pairing(dqmc_handle *h, void *device_out) { ENTER(h); return sec
 #include "unequal_time.inl"
 #include "binner.inl"
 #include "momentum.inl"
+#include "taucov.inl"
 #include "global_move.inl"
 #include "thermo.inl"
 #include "response.inl"

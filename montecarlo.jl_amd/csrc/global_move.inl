@@ -144,6 +144,7 @@ int dqmc_set_sign_weighting(dqmc_handle *h, int32_t on)
         if (h->bin[which].on && h->bin[which].T)
             return fail(h, DQMC_ERR_STATE, "dqmc_set_sign_weighting: a binner has samples: call dqmc_reset_accumulators first");
     h->sign_on = on != 0;
+    if (h->sign_on) tcov_off(h);  // (the covariance of s x is not that of x: dqmc_set_tau_covariance refuses it)
     h->red_valid = false;  // (re)sized: the last reduction is void
     dqmc_handle::Section &sg = h->sec[DQMC_RED_SIGN];
     sg.n_red = h->sign_on ? sg.n : 0;

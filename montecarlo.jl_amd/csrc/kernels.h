@@ -550,6 +550,24 @@ hipError_t launch_current_tau_row(int n_dirs, int n_q, int K, int n_walkers, con
 // take kb [n_walkers][K] (launch_bond_kinetic's, s_w x already), s_w, and one count
 hipError_t launch_current_tau_finish(int K, int n_walkers, const double *kb, const double *sw, double *sums,
                                      long sums_stride, long tail, hipStream_t s);
+// taucov.hip: one push into the tau-tau' covariance state of n_series series of every walker.  Series sl < n_series of
+// this launch is (j, q) = (sl / n_q, sl % n_q); its R values are X[w x_walker + x_off + j j_stride + r r_stride + q] and its
+// state a, c, s1 [n_walkers][S][R], s2 [n_walkers][S][R][R] at series series0 + sl of the S the accumulator holds.
+// a += x; with close != 0: b = a / bin_size, c = b if first, d = b - c, s1 += d, s2[r][r'] += d[r] d[r'], a = 0.
+constexpr int TAUCOV_THREADS = 256;
+constexpr int TAUCOV_MAX_R = 2048;   // a series' d lives in LDS (16 KiB)
+constexpr int TAUCOV_SMALL_R = 16;   // up to here TAUCOV_SMALL_SPB series share a workgroup, one wave each
+constexpr int TAUCOV_SMALL_SPB = 4;
+struct TauCovPush {
+    const double *X = nullptr;
+    long x_walker = 0, x_off = 0, j_stride = 0, r_stride = 0;
+    int n_q = 1, R = 0;
+    long n_series = 0, series0 = 0, S = 0;
+    int close = 0, first = 0;
+    double bin_size = 1.0;
+    double *a = nullptr, *c = nullptr, *s1 = nullptr, *s2 = nullptr;
+};
+hipError_t launch_taucov_push(const TauCovPush &p, int n_walkers, hipStream_t s);
 // HS field <-> Julia BitArray chunks (compress / decompress, HubbardModel.jl:56-59)
 hipError_t launch_conf_pack(const int8_t *conf, size_t n_elem, unsigned long long *chunks, hipStream_t s);
 hipError_t launch_conf_unpack(const unsigned long long *chunks, size_t n_elem, int8_t *conf, hipStream_t s);

@@ -28,6 +28,7 @@ static void mom_off(dqmc_handle *h)
     for (int which = DQMC_BIN_MOMENTUM_CORRELATIONS; which < DQMC_BIN_MOMENTUM_END; ++which) mom_disable(h, which);
     for (int which = DQMC_BIN_RESPONSE_PAIRING; which < DQMC_BIN_RESPONSE_END; ++which) resp_disable(h, which);  // they use the tables
     ctd_off(h);  // (and so does the imaginary-time current recording)
+    tcov_off(h);  // (and the tau-tau' covariance of the momentum sample)
     dfree(h, &h->mom.cos_d);
     dfree(h, &h->mom.sin_d);
     h->mom.cos_h.clear();
@@ -54,21 +55,20 @@ static int mom_enable(dqmc_handle *h, int which, int64_t capacity)
     }
     return DQMC_OK;
 }
-// the transform of every walker's source sample into h->mom.sample, then the push: on the handle's stream, behind the
-// source section's kernels
-static int mom_push(dqmc_handle *h, int which)
+// the transform of every walker's source sample into Y [W][y_stride] (y_stride: the sample's elements, with the trailing
+// s_w while sign weighting is on): on the handle's stream, behind the source section's kernels
+static int mom_fill(dqmc_handle *h, int which, double *Y, long y_stride)
 {
-    const dqmc_handle::Binner &b = h->bin[which];
     const dqmc_handle::Momenta &m = h->mom;
     const int nd = h->n_dirs, nq = m.n_q;
     MomentumArgs a;
-    a.Y = m.sample[mom_index(which)];
-    a.y_stride = b.E;
+    a.Y = Y;
+    a.y_stride = y_stride;
     a.n_dirs = nd;
     a.n_q = nq;
     if (h->sign_on) {  // the first launch also stores s_w behind the sample
         a.sw = h->sign_sw;
-        a.sign_at = b.E - 1;
+        a.sign_at = y_stride - 1;
     }
     {
         Timed t(h, DQMC_K_MISC);
@@ -107,8 +107,15 @@ static int mom_push(dqmc_handle *h, int which)
             if (t.what & DQMC_TD_DENSITY) HIPCHK(seg(m.cos_d, x_off, 4 * t.R, y_off));  // [CDC][SDCx][SDCy][SDCz], R rows each
         }
     }
+    return DQMC_OK;
+}
+// the transform into h->mom.sample, then the push
+static int mom_push(dqmc_handle *h, int which)
+{
+    double *Y = h->mom.sample[mom_index(which)];
+    CHK(mom_fill(h, which, Y, h->bin[which].E));
     BinPush p;
-    p.src = a.Y;
+    p.src = Y;
     return binner_push(h, which, p);
 }
 

@@ -770,6 +770,7 @@ int dqmc_set_time_displaced(dqmc_handle *h, int32_t every, int32_t what)
         if (h->td.every) h->red_valid = false;
         td_free(h);
         mom_disable(h, DQMC_BIN_MOMENTUM_TIME_DISPLACED);
+        tcov_off(h);
         return DQMC_OK;
     }
     if (!h->n_dirs) return fail(h, DQMC_ERR_STATE, "call dqmc_set_pair_directions first");
@@ -778,6 +779,7 @@ int dqmc_set_time_displaced(dqmc_handle *h, int32_t every, int32_t what)
         return fail(h, DQMC_ERR_INVALID, "what must be a non-empty mask of DQMC_TD_GREENS | DQMC_TD_DENSITY");
     HIPCHK(hipStreamSynchronize(h->stream));
     mom_disable(h, DQMC_BIN_MOMENTUM_TIME_DISPLACED);  // its rows follow the recording: the caller enables it again
+    tcov_off(h);                                        // (and so do the series of the tau-tau' covariance)
     return td_setup(h, every, what);
 }
 int dqmc_time_displaced_size(dqmc_handle *h, size_t *n_doubles) { return sec_size(h, DQMC_RED_TIME_DISPLACED, n_doubles); }
@@ -894,6 +896,7 @@ int dqmc_accumulate_susceptibilities(dqmc_handle *h, int32_t recalculate)
     if (record && h->bin[DQMC_BIN_TIME_DISPLACED].on) CHK(binner_push_section(h, DQMC_BIN_TIME_DISPLACED));
     if (h->bin[DQMC_BIN_MOMENTUM_SUSCEPTIBILITIES].on) CHK(mom_push(h, DQMC_BIN_MOMENTUM_SUSCEPTIBILITIES));
     if (record && h->bin[DQMC_BIN_MOMENTUM_TIME_DISPLACED].on) CHK(mom_push(h, DQMC_BIN_MOMENTUM_TIME_DISPLACED));
+    if (record && h->tcov.bin_size) CHK(tcov_push(h));
     if (h->bin[DQMC_BIN_RESPONSE_PAIRING_SUSCEPTIBILITY].on) CHK(resp_push(h, DQMC_BIN_RESPONSE_PAIRING_SUSCEPTIBILITY));
     if (h->bin[DQMC_BIN_RESPONSE_CURRENT].on) CHK(resp_push(h, DQMC_BIN_RESPONSE_CURRENT));
     return dqmc_synchronize(h);

@@ -272,6 +272,8 @@ class DQMC:
         self._channels = None     # {name: weights} of set_pair_channels
         self._ent = None          # (names or None, site lists) of set_entanglement
         self._ctd = 0             # `every` of set_current_time_displaced (0: off)
+        self._tcov = None         # (bin_size, what) of set_tau_covariance
+        self._ucov = None         # (n_series, R, bin_size) of user_covariance
         self._mid_sweep = False  # set by load(): run() finishes the sweep the checkpoint was taken in
         if int(global_rate) < 1:
             raise ValueError("global_rate must be at least 1")
@@ -635,7 +637,12 @@ class DQMC:
         place, so `path` always holds a whole checkpoint.  Only at the measurement point (see state()): run(checkpoint=...)
         calls it there, and so may the caller on an object that load() returned or that went there with
         update_until_measure(); an object whose run() has returned stands at current_slice == slices, direction == -1 and
-        is refused (ERR_STATE).  A ConfigRecorder's configurations are the caller's and are not part of the file."""
+        is refused (ERR_STATE).  A ConfigRecorder's configurations are the caller's and are not part of the file.  The
+        moments of set_tau_covariance / user_covariance are not checkpointed: with either on, save() raises ERR_STATE."""
+        if self._tcov is not None or self._ucov is not None:
+            raise _lib.DQMCError(_lib.ERR_STATE, "save: the tau-tau' covariance moments are not part of a checkpoint: read "
+                                 "them (tau_covariance_moments, user_covariance_result), then turn the accumulators off "
+                                 "with set_tau_covariance(0) / user_covariance(0, 0, 0)")
         blob = self.state()
         # (a loaded object saved again before its run() is still inside the sweep its file was taken in)
         mid = self._mid_sweep if _sweep is None else True
@@ -819,6 +826,8 @@ class DQMC:
         (off: the bare samples, the default).  Refused (ERR_STATE) while a section or a binner holds samples:
         reset_accumulators() first.  Read the results with signed(), mean_sign(), sign_sums()."""
         self._c(lib().dqmc_set_sign_weighting(self._h, int(bool(on))))
+        if on:
+            self._tcov = None  # (the engine turns the tau-tau' covariance off: it is that of the bare samples)
 
     def sign_weighting(self):
         on = C.c_int32()
@@ -1377,6 +1386,7 @@ class DQMC:
         self._c(lib().dqmc_set_time_displaced(self._h, int(every), int(what)))
         self._td_args = (int(every), int(what)) if int(every) else None
         self._binner_dropped("momentum_time_displaced")  # (the engine disables it: enable it again)
+        self._tcov = None  # (and the tau-tau' covariance)
 
     def time_displaced_plan(self):
         """-> dict(rows, every, what, fast): fast = the Green's rows take the one-lane-per-direction kernel (all zero
@@ -1415,6 +1425,7 @@ class DQMC:
     def _momenta_dropped(self):
         self._mom = None
         self._ctd = 0  # (the engine turns the imaginary-time current recording off with the tables)
+        self._tcov = None  # (and the tau-tau' covariance of the momentum sample)
         for k in tuple(_lib.BIN_MOMENTUM) + tuple(_lib.BIN_RESPONSE):  # (the response binners use the tables)
             self._binner_dropped(k)
 
@@ -1521,18 +1532,139 @@ class DQMC:
                 res[src + "k"] = m[src] @ Ct
         return res
 
-    def spectral_function(self, omega, momenta=None, run=None, **sac_args):
+    # ---- tau-tau' covariance (include/dqmc_hip.h "tau-tau' covariance")
+    def set_tau_covariance(self, bin_size, what=("greens", "density")):
+        """from now on every accumulate_susceptibilities pass also feeds the tau-tau' covariance accumulator of the
+        momentum time-displaced sample: per walker, `bin_size` consecutive samples are averaged into a bin, and the
+        shifted first and second moments of the bins are kept over tau for every series - Re Gk_l0 of every (block, q)
+        for "greens", CDCk, SDCxk, SDCyk, SDCzk of every q for "density" (or the DQMC_TD_* mask itself).  bin_size = 0
+        turns it off.  Needs set_momenta and set_time_displaced with these rows; refused with sign weighting on.  Costs
+        n_walkers * S * (R^2 + 3 R) doubles (tau_covariance_plan).  Read with tau_covariance(), tau_covariance_moments()."""
+        if isinstance(what, str):
+            what = (what,)
+        if not isinstance(what, int):
+            bits = {"greens": _lib.TD_GREENS, "density": _lib.TD_DENSITY}
+            for k in what:
+                if k not in bits:
+                    raise ValueError("unknown time-displaced part %r" % (k,))
+            what = sum(bits[k] for k in set(what))
+        self._c(lib().dqmc_set_tau_covariance(self._h, int(bin_size), int(what)))
+        self._tcov = (int(bin_size), int(what)) if int(bin_size) else None
+
+    def tau_covariance_plan(self):
+        """-> dict(bin_size, series, rows, bytes, n_bins) of the engine, all zero when off"""
+        out = (C.c_int64 * 5)()
+        self._c(lib().dqmc_tau_covariance_plan(self._h, out))
+        return dict(zip(("bin_size", "series", "rows", "bytes", "n_bins"), (int(v) for v in out)))
+
+    def _cov_moments(self, plan, get):
+        out = (C.c_int64 * 5)()
+        self._c(plan(self._h, out))
+        bs, S, R = int(out[0]), int(out[1]), int(out[2])
+        W = self.n_walkers
+        nb = np.zeros(W, dtype=np.int64)
+        shift, S1, S2 = np.zeros((W, S, R)), np.zeros((W, S, R)), np.zeros((W, S, R, R))
+        self._c(get(self._h, _lib.i64ptr(nb), dptr(shift), dptr(S1), dptr(S2)))
+        return {"nb": nb, "shift": shift, "S1": S1, "S2": S2, "bin_size": bs}
+
+    def tau_covariance_moments(self):
+        """the raw per-walker moments -> dict(nb [W] closed bins, shift, S1 [W, S, R], S2 [W, S, R, R], bin_size): what a
+        multi-rank run gathers and hands, as a list over its ranks, to tau_covariance_from_moments"""
+        return self._cov_moments(lib().dqmc_tau_covariance_plan, lib().dqmc_tau_covariance_get)
+
+    def tau_covariance(self, moments=None):
+        """-> dict: the mean over the closed bins of every walker and the covariance of that mean (moments: a list of
+        tau_covariance_moments() of several ranks; default this handle's).  Gk_l0_mean [n_blocks, R, n_q] and Gk_l0_cov
+        [n_blocks, n_q, R, R] (of Re Gk_l0) if "greens" is on; CDCk, SDCxk, SDCyk, SDCzk _mean [R, n_q] and _cov
+        [n_q, R, R] if "density" is; tau [R], n_bins, bin_size.  The means are shaped like momentum_time_displaced()."""
+        if self._tcov is None:
+            raise _lib.DQMCError(_lib.ERR_STATE, "tau_covariance: call set_tau_covariance first")
+        pooled = tau_covariance_from_moments([self.tau_covariance_moments()] if moments is None else moments)
+        nq, what = self._mom[0].shape[0], self._tcov[1]
+        mean, cov = pooled["mean"], pooled["cov"]
+        R = mean.shape[1]
+        res, s = {}, 0
+        if what & _lib.TD_GREENS:
+            n = self.nb * nq
+            res["Gk_l0_mean"] = np.moveaxis(mean[s:s + n].reshape(self.nb, nq, R), 1, 2).copy()
+            res["Gk_l0_cov"] = cov[s:s + n].reshape(self.nb, nq, R, R).copy()
+            s += n
+        if what & _lib.TD_DENSITY:
+            for name in ("CDCk", "SDCxk", "SDCyk", "SDCzk"):
+                res[name + "_mean"] = mean[s:s + nq].T.copy()
+                res[name + "_cov"] = cov[s:s + nq].copy()
+                s += nq
+        res.update(tau=self._td_tau(), n_bins=pooled["n_bins"], bin_size=self._tcov[0])
+        return res
+
+    def user_covariance(self, n_series, R, bin_size):
+        """a tau-tau' covariance accumulator over `n_series` series of `R` values per walker that the caller computes on
+        the device (bin_size = 0: off)"""
+        self._c(lib().dqmc_user_covariance(self._h, int(n_series), int(R), int(bin_size)))
+        self._ucov = (int(n_series), int(R), int(bin_size)) if int(bin_size) else None
+
+    def user_covariance_push(self, samples):
+        """push one sample [n_walkers, n_series, R]: a contiguous float64 device tensor (torch) or a device address"""
+        if hasattr(samples, "data_ptr"):
+            if self._ucov is None:
+                raise _lib.DQMCError(_lib.ERR_STATE, "user_covariance_push: call user_covariance first")
+            n = self.n_walkers * self._ucov[0] * self._ucov[1]
+            if str(samples.dtype) != "torch.float64" or not samples.is_contiguous() or not samples.is_cuda \
+                    or samples.numel() != n:
+                raise ValueError("samples must be a contiguous float64 device tensor of n_walkers x %d x %d" % self._ucov[:2])
+            import torch
+            torch.cuda.current_stream(samples.device).synchronize()  # the engine reads it on its own stream
+            samples = samples.data_ptr()
+        self._c(lib().dqmc_user_covariance_push(self._h, C.c_void_p(samples)))
+
+    def user_covariance_result(self):
+        """the raw per-walker moments of the user accumulator, as tau_covariance_moments()"""
+        return self._cov_moments(lib().dqmc_user_covariance_plan, lib().dqmc_user_covariance_get)
+
+    def _sac_covariance_input(self, who, key):
+        """(tau_covariance(), checked) for a continuation with the full covariance"""
+        if self._tcov is None:
+            raise _lib.DQMCError(_lib.ERR_STATE, "%s: covariance=True needs set_tau_covariance" % who)
+        plan = self.tau_covariance_plan()
+        if not plan["n_bins"]:
+            check_covariance_bins(0, plan["rows"], who)
+        tc = self.tau_covariance()
+        if key + "_cov" not in tc:
+            raise _lib.DQMCError(_lib.ERR_STATE, "%s: set_tau_covariance does not hold these rows" % who)
+        return tc
+
+    def spectral_function(self, omega, momenta=None, run=None, covariance=False, **sac_args):
         """A(k, omega) from G(k, tau) by stochastic analytic continuation on the device (sac.SAC; the fermion kernel
         with this run's beta, norm 1) -> dict(omega [Nw], A, weight [n_blocks, n_k, Nw], chi2, theta [n_blocks, n_k],
-        momenta, sac).  The data are Re Gk_l0 of momentum_time_displaced(), the errors Gk_l0_std_error_re of
-        binned("momentum_time_displaced"): the binner holds no tau-tau' covariances, so the diagonal form of chi2 is
-        used and correlations between time slices are ignored.  `momenta` picks rows of momenta() (default: all); `run`
-        is the keyword dict of SAC.run, the other keywords go to SAC (n_deltas, thetas, seed, ...).  Errors below
-        `error_floor` (default 1e-6) are raised to it.  Needs enable_binning("momentum_time_displaced"); refused with
-        sign weighting on, whose <s G> / <s> errors are not those of a plain mean."""
+        momenta, sac).  `momenta` picks rows of momenta() (default: all); `run` is the keyword dict of SAC.run, the
+        other keywords go to SAC (n_deltas, thetas, seed, cut, ...).  Refused with sign weighting on, whose <s G> / <s>
+        errors are not those of a plain mean.
+        covariance=False: the data are Re Gk_l0 of momentum_time_displaced(), the errors Gk_l0_std_error_re of
+        binned("momentum_time_displaced"); the diagonal form of chi2 is used and correlations between time slices are
+        ignored.  Errors below `error_floor` (default 1e-6) are raised to it.  Needs
+        enable_binning("momentum_time_displaced").
+        covariance=True: the data are Gk_l0_mean of tau_covariance(), the mean of the closed bins, and their
+        covariance Gk_l0_cov goes to SAC, which rotates data and kernel into its eigenbasis and drops eigenvalues below
+        `cut` (default 1e-10) of the largest.  Needs set_tau_covariance with "greens" and more bins than time slices
+        (ERR_STATE otherwise: the matrix is singular by construction)."""
         from .sac import SAC, fermion_kernel
         if self.sign_weighting():
             raise _lib.DQMCError(_lib.ERR_STATE, "spectral_function: not available with sign weighting on")
+        if covariance:
+            tc = self._sac_covariance_input("spectral_function", "Gk_l0")
+            G, cov = tc["Gk_l0_mean"], tc["Gk_l0_cov"]
+            check_covariance_bins(tc["n_bins"], G.shape[1], "spectral_function")
+            ks = np.arange(G.shape[2]) if momenta is None else np.asarray(momenta, dtype=np.int64).reshape(-1)
+            G, cov = G[:, :, ks], cov[:, ks]
+            nb, nt, nk = G.shape
+            s = SAC(tc["tau"], np.ascontiguousarray(np.moveaxis(G, 1, 2).reshape(nb * nk, nt)),
+                    covariance=cov.reshape(nb * nk, nt, nt), kernel=fermion_kernel, omega=omega, beta=self.p.beta,
+                    device_id=self._device_id, **sac_args)
+            s.run(**(run or {}))
+            sp = s.spectrum()
+            return {"omega": sp["omega"], "A": sp["A"].reshape(nb, nk, -1), "weight": sp["weight"].reshape(nb, nk, -1),
+                    "chi2": sp["chi2"].reshape(nb, nk), "theta": sp["theta"].reshape(nb, nk),
+                    "momenta": self.momenta()[ks], "n_bins": tc["n_bins"], "sac": s}
         if not self._binning_enabled("momentum_time_displaced"):
             raise _lib.DQMCError(_lib.ERR_STATE, 'spectral_function: call enable_binning("momentum_time_displaced") first')
         floor = float(sac_args.pop("error_floor", 1e-6))
@@ -1553,6 +1685,49 @@ class DQMC:
         return {"omega": sp["omega"], "A": sp["A"].reshape(nb, nk, -1), "weight": sp["weight"].reshape(nb, nk, -1),
                 "chi2": sp["chi2"].reshape(nb, nk), "theta": sp["theta"].reshape(nb, nk), "momenta": self.momenta()[ks],
                 "sac": s}
+
+    def dynamical_structure_factor(self, omega, channel="SDCz", momenta=None, covariance=True, run=None, **sac_args):
+        """S(q, omega) of a density channel ("SDCz", "SDCx", "SDCy", "CDC") from C(q, tau) = <channel>k of
+        tau_covariance() by stochastic analytic continuation with sac.boson_symmetric_kernel on omega >= 0 -> dict(omega,
+        B [n_k, Nw]: the sampled density S(q, omega) (1 + e^{-beta omega}); S = B / (1 + e^{-beta omega}); weight [n_k, Nw]
+        (it sums to C(q, 0)); chi2, theta [n_k]; momenta; left_out; n_bins; sac).  Only the recorded slices with
+        tau <= beta / 2 are used: C(tau) = C(beta - tau), so the upper half carries the same information and would make
+        the covariance singular.  norm = C(q, tau = 0) per momentum; a momentum whose C(q, 0) is not positive (q = 0 of
+        the charge channel at fixed filling) has no spectrum to normalise, is left out and listed (as an index into
+        momenta()) under left_out.  covariance=True hands SAC the covariance of the kept slices and needs more bins than
+        kept slices (ERR_STATE otherwise); covariance=False its diagonal, with errors below `error_floor` (default 1e-6)
+        raised to it.  Needs set_tau_covariance with "density"; `momenta`, `run` and the other keywords as for
+        spectral_function."""
+        from .sac import SAC, boson_symmetric_kernel
+        if channel not in ("SDCz", "SDCx", "SDCy", "CDC"):
+            raise ValueError("channel must be one of SDCz, SDCx, SDCy, CDC")
+        if self.sign_weighting():
+            raise _lib.DQMCError(_lib.ERR_STATE, "dynamical_structure_factor: not available with sign weighting on")
+        floor = float(sac_args.pop("error_floor", 1e-6))
+        tc = self._sac_covariance_input("dynamical_structure_factor", channel + "k")
+        Cq, cov = tc[channel + "k_mean"], tc[channel + "k_cov"]  # [R, n_q], [n_q, R, R]
+        plan = self.time_displaced_plan()
+        keep = np.nonzero(2 * plan["every"] * np.arange(plan["rows"]) <= self.p.slices)[0]  # tau <= beta / 2, in integers
+        if covariance:
+            check_covariance_bins(tc["n_bins"], keep.size, "dynamical_structure_factor")
+        elif tc["n_bins"] < 2:
+            raise _lib.DQMCError(_lib.ERR_STATE, "dynamical_structure_factor: fewer than two closed bins")
+        ks = np.arange(Cq.shape[1]) if momenta is None else np.asarray(momenta, dtype=np.int64).reshape(-1)
+        left_out = np.array([k for k in ks if not Cq[0, k] > 0.0], dtype=np.int64)
+        ks = np.array([k for k in ks if Cq[0, k] > 0.0], dtype=np.int64)
+        if ks.size == 0:
+            raise _lib.DQMCError(_lib.ERR_STATE, "dynamical_structure_factor: no momentum with C(q, 0) > 0")
+        data = np.ascontiguousarray(Cq[keep][:, ks].T)
+        cv = cov[ks][:, keep][:, :, keep]
+        how = {"covariance": cv} if covariance else \
+            {"error": np.maximum(np.sqrt(np.einsum("kii->ki", cv)), floor)}
+        s = SAC(tc["tau"][keep], data, kernel=boson_symmetric_kernel, omega=omega, beta=self.p.beta, norm=Cq[0, ks],
+                device_id=self._device_id, **how, **sac_args)
+        s.run(**(run or {}))
+        sp = s.spectrum()
+        return {"omega": sp["omega"], "B": sp["A"], "S": sp["A"] / (1.0 + np.exp(-self.p.beta * sp["omega"]))[None, :],
+                "weight": sp["weight"], "chi2": sp["chi2"], "theta": sp["theta"], "momenta": self.momenta()[ks],
+                "left_out": left_out, "n_bins": tc["n_bins"], "sac": s}
 
     def _binned_momentum(self, which, level=None):
         """binned() of a momentum binner: the keys of structure_factors() / static_susceptibilities() /
@@ -2245,6 +2420,54 @@ def entanglement_from_pair_sums(pair_sums, count):
             s2 = -np.log((tot[:, None] - mine) / (count * (W - 1) * (W - 2) / 2.0))
             res["S2_std_error"] = np.sqrt((W - 1) / W * ((s2 - s2.mean(axis=1, keepdims=True)) ** 2).sum(axis=1))
     return {k: v[0] for k, v in res.items()} if single else res
+
+
+def check_covariance_bins(n_bins, n_tau, who="spectral_function"):
+    """a covariance of `n_tau` time slices estimated from `n_bins` bins has rank n_bins - 1 at most: it can be inverted
+    only with n_bins > n_tau.  A condition, not a tolerance: ERR_STATE otherwise."""
+    if not int(n_bins) > int(n_tau):
+        raise _lib.DQMCError(_lib.ERR_STATE, "%s: %d closed bins for %d time slices: the covariance is singular by "
+                             "construction; it needs more bins than slices" % (who, int(n_bins), int(n_tau)))
+
+
+def tau_covariance_from_moments(list_of_moments):
+    """Pools the per-walker moments of DQMC.tau_covariance_moments() / user_covariance_result(), one dict per rank (or a
+    single dict): nb [W], shift, S1 [W, S, R], S2 [W, S, R, R].  Per walker the bins have the mean c + S1 / nb and the
+    scatter M2 = S2 - S1 S1^T / nb about it (the sums are of deviations from the shift c, so nothing large cancels);
+    walkers and ranks are chains at the same parameters, so their bins pool into one sample of n_bins = sum nb_w with the
+    pairwise update of Chan, Golub and LeVeque, in float64 and in the order given: n = n_a + n_b, delta = mean_b - mean_a,
+    mean = mean_a + delta n_b / n, M2 = M2_a + M2_b + delta delta^T n_a n_b / n.
+    -> dict(mean [S, R], n_bins, cov [S, R, R] = M2 / (n_bins (n_bins - 1)), the covariance of the mean (nan below two
+    bins), M2 [S, R, R])."""
+    if isinstance(list_of_moments, dict):
+        list_of_moments = [list_of_moments]
+    n, mean, M2 = 0, None, None
+    for m in list_of_moments:
+        nb = np.asarray(m["nb"], dtype=np.int64).reshape(-1)
+        c, S1, S2 = (np.asarray(m[k], dtype=np.float64) for k in ("shift", "S1", "S2"))
+        if S1.ndim != 3 or c.shape != S1.shape or S2.shape != S1.shape + S1.shape[-1:] or nb.size != S1.shape[0]:
+            raise ValueError("moments must hold nb [W], shift and S1 [W, S, R], S2 [W, S, R, R]")
+        if mean is not None and mean.shape != S1.shape[1:]:
+            raise ValueError("the moments of every rank must have the same series and rows")
+        for w in range(nb.size):
+            k = int(nb[w])
+            if k < 1:
+                continue
+            mw = c[w] + S1[w] / k
+            Mw = S2[w] - S1[w][:, :, None] * S1[w][:, None, :] / k
+            if mean is None:
+                n, mean, M2 = k, mw, Mw
+                continue
+            delta = mw - mean
+            tot = n + k
+            mean = mean + delta * (k / tot)
+            M2 = M2 + Mw + delta[:, :, None] * delta[:, None, :] * (n * k / tot)
+            n = tot
+    if mean is None:
+        raise ValueError("tau_covariance_from_moments: no closed bin")
+    with np.errstate(invalid="ignore", divide="ignore"):
+        cov = M2 / (n * (n - 1.0)) if n > 1 else np.full_like(M2, np.nan)
+    return {"mean": mean, "n_bins": n, "cov": cov, "M2": M2}
 
 
 def finish_moments(buf):
