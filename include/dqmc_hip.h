@@ -69,6 +69,10 @@ typedef struct {
      *    Ex = E[0:16, 0:16], Ey = E[0::16, 0::16] / E[0,0].
      *  - n_sites == 512: E = Ez (x) Ey (x) Ex, the periodic 8 x 8 x 8 cubic lattice (site x + 8 y + 64 z), with
      *    Ex = E[0:8, 0:8], Ey = E[0::8, 0::8][0:8, 0:8] / E[0,0], Ez = E[0::64, 0::64] / E[0,0].
+     *  - n_sites == 512, when a block fails that test: E = Ez (x) Ey (x) Ex with a 2 x 2 Ez, the periodic two-layer
+     *    16 x 16 x 2 square lattice with interlayer hopping t_perp (site x + 16 y + 256 z, z the layer), with
+     *    Ex = E[0:16, 0:16], Ey = E[0::16, 0::16][0:16, 0:16] / E[0,0], Ez = E[0::256, 0::256] / E[0,0].  The two-layer
+     *    lattice is factored at L = 16 only; next-nearest-neighbour hopping is not defined on it.
      * When every block passes, slice products and wraps apply the factors instead of the dense matrix
      * (dqmc_kron_hopping reports it); the difference is rounding of the exponential, far inside the 1e-10 tolerance on G.
      * Any other size or hopping keeps the dense products.  The triangular 16 x 16 lattice, which is no Kronecker product,
@@ -931,7 +935,7 @@ int dqmc_checkerboard_apply(dqmc_handle *h, int32_t which, int32_t slice, const 
  * how often that happened.  (The one-launch UDT has no second path: its time-outs fail the call, see dqmc_device_errors.) */
 int dqmc_qr_fallbacks(dqmc_handle *h, int64_t *count);
 /* 1 when slice products and wraps apply eT2 / eTinv2 in factored form (Kronecker products of 16 x 16 factors at n = 256,
- * 8 x 8 factors at n = 512, see dqmc_params; the triangular 16 x 16 lattice's three factors, see
+ * 8 x 8 factors or the two-layer 2 x 2 (x) 16 x 16 (x) 16 x 16 form at n = 512, see dqmc_params; the triangular 16 x 16 lattice's three factors, see
  * dqmc_set_triangular_factors; the t-t' square 16 x 16 lattice's four factors, see dqmc_set_square_tp_factors), else 0 */
 int dqmc_kron_hopping(dqmc_handle *h, int32_t *on);
 /* The periodic 16 x 16 TriangularLattice (n_sites = 256, site x + 16 y; hopping along X = x + 1, Y = y + 1 and D = XY,

@@ -8,7 +8,7 @@ from ._lib import DQMCError, lib  # noqa: F401
 from .configurations import (CompressedConf, ConfigRecorder, Discarder, compress,  # noqa: F401
                              decompress)
 from . import lattices  # noqa: F401
-from .lattices import (Chain, EachLocalQuadByDistance, EachLocalQuadBySyncedDistance, EachSitePairByDistance,  # noqa: F401
+from .lattices import (BilayerSquareLattice, Chain, EachLocalQuadByDistance, EachLocalQuadBySyncedDistance, EachSitePairByDistance,  # noqa: F401
                        CubicLattice, SquareLattice, TriangularLattice, build_checkerboard, momentum_grid, strip_subsystem)
 from .models import (HubbardModel, HubbardModelAttractive, HubbardModelRepulsive,  # noqa: F401
                      rand_conf)

@@ -52,8 +52,11 @@ struct dqmc_handle {
     // n == 256 t-t' square 16 x 16 lattice (dqmc_set_square_tp_factors): (Fy (x) Fx) Ed Ea, ttp.hip instead of slab.hip.
     // kron_f: [eT2, eTinv2, eT2', eTinv2'] x [x, y, d, a] x nb x 16 x 16 (Fd and Fa behind Fy); tri is set with ttp: what
     // the triangular path leaves off (the pending-chunk fold, the one-launch wrap) is off here as well.
+    // n == 512 two-layer 16 x 16 x 2 lattice (bilayer_factor, tried when kron3_factor rejects a block): Ez (x) Ey (x) Ex with
+    // Ex, Ey 16 x 16 and Ez 2 x 2, bilayer.hip instead of the dense GEMMs.
+    // kron_f: [eT2, eTinv2, eT2', eTinv2'] x ([Ex] x nb x 256, [Ey, Ez, padding] x nb x BILAYER_FB).
     // kron_fa / kron_fb: doubles per block of the two operand sets (ax / ay of a KronStep)
-    bool kron = false, tri = false, ttp = false;
+    bool kron = false, tri = false, ttp = false, bilayer = false;
     double *kron_f = nullptr;
     int kron_fa = 0, kron_fb = 0;
     int8_t *conf = nullptr;  // W x (N x M)
@@ -487,6 +490,32 @@ static bool kron3_factor(const double *E, double *fx, double *fy, double *fz)
         for (int r = 0; r < n; ++r) {
             const double e = E[r + (size_t)n * c];
             const double f = fz[(r >> 6) + 8 * (c >> 6)] * fy[((r >> 3) & 7) + 8 * ((c >> 3) & 7)] * fx[(r & 7) + 8 * (c & 7)];
+            emax = std::max(emax, std::fabs(e));
+            rmax = std::max(rmax, std::fabs(e - f));
+        }
+    return std::isfinite(emax) && rmax <= 256.0 * 2.220446049250313e-16 * emax;
+}
+// eT2 / eTinv2 of the periodic two-layer 16 x 16 x 2 square lattice (n = 512, site x + 16 y + 256 z) as Ez (x) Ey (x) Ex:
+// Ex = E[0:16, 0:16], Ey = E[0::16, 0::16][0:16, 0:16] / E[0, 0], Ez = E[0::256, 0::256] / E[0, 0] (2 x 2).  The same
+// acceptance as kron_factor (the bilayer's exponentials measure up to 35 ulp over t_perp = 0.3 .. 3.5); any
+// other hopping keeps the dense path.
+static bool bilayer_factor(const double *E, double *fx, double *fy, double *fz)
+{
+    const int n = 512;
+    const double e00 = E[0];
+    if (!(e00 > 0.0)) return false;
+    for (int j = 0; j < 16; ++j)
+        for (int i = 0; i < 16; ++i) {
+            fx[i + 16 * j] = E[i + (size_t)n * j];
+            fy[i + 16 * j] = E[16 * i + (size_t)n * 16 * j] / e00;
+        }
+    for (int j = 0; j < 2; ++j)
+        for (int i = 0; i < 2; ++i) fz[i + 2 * j] = E[256 * i + (size_t)n * 256 * j] / e00;
+    double emax = 0.0, rmax = 0.0;
+    for (int c = 0; c < n; ++c)
+        for (int r = 0; r < n; ++r) {
+            const double e = E[r + (size_t)n * c];
+            const double f = fz[(r >> 8) + 2 * (c >> 8)] * fy[((r >> 4) & 15) + 16 * ((c >> 4) & 15)] * fx[(r & 15) + 16 * (c & 15)];
             emax = std::max(emax, std::fabs(e));
             rmax = std::max(rmax, std::fabs(e - f));
         }
@@ -940,7 +969,8 @@ static int run_kron(dqmc_handle *h, const KronArgs &a)
 {
     hipEvent_t ea, eb;
     timing_events(h, &ea, &eb);
-    if (h->n == 512) HIPCHK(launch_kron3_chain(a, h->stream, ea, eb));
+    if (h->bilayer) HIPCHK(launch_bilayer_chain(a, h->stream, ea, eb));
+    else if (h->n == 512) HIPCHK(launch_kron3_chain(a, h->stream, ea, eb));
     else if (h->ttp) HIPCHK(launch_ttp_chain(a, h->stream, ea, eb));
     else if (h->tri) HIPCHK(launch_tri_chain(a, h->stream, ea, eb));
     else HIPCHK(launch_kron_chain(a, h->stream, ea, eb));
@@ -1475,6 +1505,35 @@ int dqmc_create(const dqmc_params *p, dqmc_handle **out)
             h->kron = true;
             h->kron_fa = 4096;
             h->kron_fb = 256;
+        }
+    }
+    if (h->n == 512 && !h->sw.no_kron && !h->kron) {
+        // the two-layer form: factors of eT2, eTinv2 and their transposes (Ez' (x) Ey' (x) Ex': same residual, no second check)
+        const size_t per = (size_t)nb * (256 + BILAYER_FB);
+        std::vector<double> f(4 * per, 0.0);
+        double fx[256], fy[256], fz[4];
+        bool ok = true;
+        for (int m = 0; m < 2 && ok; ++m)
+            for (int b = 0; b < nb && ok; ++b) {
+                ok = bilayer_factor((m ? p->eTinv2 : p->eT2) + (size_t)b * h->nn, fx, fy, fz);
+                for (int t = 0; t < 2; ++t) {
+                    double *dx = f.data() + (size_t)(m + 2 * t) * per + (size_t)b * 256;
+                    double *dy = f.data() + (size_t)(m + 2 * t) * per + (size_t)nb * 256 + (size_t)b * BILAYER_FB;
+                    for (int j = 0; j < 16; ++j)
+                        for (int i = 0; i < 16; ++i) {
+                            dx[i + 16 * j] = t ? fx[j + 16 * i] : fx[i + 16 * j];
+                            dy[i + 16 * j] = t ? fy[j + 16 * i] : fy[i + 16 * j];
+                        }
+                    for (int j = 0; j < 2; ++j)
+                        for (int i = 0; i < 2; ++i) dy[256 + i + 2 * j] = t ? fz[j + 2 * i] : fz[i + 2 * j];
+                }
+            }
+        if (ok) {
+            CCHK(dalloc(h, &h->kron_f, f.size()));
+            CHIP(hipMemcpy(h->kron_f, f.data(), f.size() * sizeof(double), hipMemcpyHostToDevice));
+            h->kron = h->bilayer = true;
+            h->kron_fa = 256;
+            h->kron_fb = BILAYER_FB;
         }
     }
     CCHK(dalloc(h, &h->conf, (size_t)h->W * h->N * h->M));

@@ -138,6 +138,10 @@ hipError_t launch_tri_chain(const KronArgs &a, hipStream_t s, hipEvent_t start =
 // The same chains on the t-t' square 16 x 16 lattice (n = 256) with A_s = (Fy (x) Fx) Ed Ea (ttp.hip): ax, ay and Fd as for
 // launch_tri_chain, and Fa (applied along the anti-diagonals x + y = const) at ay + 256 (2 nb + b)
 hipError_t launch_ttp_chain(const KronArgs &a, hipStream_t s, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
+// The same chains on the two-layer square 16 x 16 x 2 lattice (n = 512) with A_s = Ez (x) Ey (x) Ex (bilayer.hip): ax = Ex of
+// block b at + 256 b; ay = Ey of block b at + BILAYER_FB b, with the 2 x 2 Ez (column-major) behind it at + 256
+constexpr int BILAYER_FB = 264;
+hipError_t launch_bilayer_chain(const KronArgs &a, hipStream_t s, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
 
 // Column-pivoted Householder QR, in place (udt_AVX_pivot! "QR decomposition" loop,
 // src/linalg/UDT.jl:212-246).  On exit A holds R on/above the diagonal and the

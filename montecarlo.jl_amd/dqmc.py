@@ -563,7 +563,7 @@ class DQMC:
 
     _MODELS = ("HubbardModelAttractive", "HubbardModelRepulsive")
     _LATTICES = {"SquareLattice": ("L",), "Chain": ("sites",), "CubicLattice": ("dim", "L"),
-                 "TriangularLattice": ("L", "Lx", "Ly")}  # class -> the attributes its constructor takes, in order
+                 "TriangularLattice": ("L", "Lx", "Ly"), "BilayerSquareLattice": ("L",)}  # class -> the attributes its constructor takes, in order
 
     @staticmethod
     def _model_entry(m):
@@ -573,6 +573,8 @@ class DQMC:
             model["mu"] = m.mu
         if getattr(m, "tp", 0.0) != 0.0:  # (absent at 0: the preamble of before)
             model["tp"] = m.tp
+        if getattr(m, "t_perp", None) is not None:  # (a BilayerSquareLattice's model only)
+            model["t_perp"] = m.t_perp
         return model
 
     @classmethod
@@ -1769,7 +1771,8 @@ class DQMC:
         of set_local_targets (k = 0 is on-site), at most 8 of them; F[kk, c] = f_c[k1] f_c[k2] goes to the engine.
         "default" (lattices.default_pair_channels): s = e_0 and s* = 1/2 on every nearest neighbour on every lattice (no
         1/sqrt(z): the square lattice's weights are kept as they are elsewhere), and on a SquareLattice d = +1/2 on the
-        +-x bonds and -1/2 on the +-y bonds, the sign read from the iterator's directions.  None or {} turns the channels
+        +-x bonds and -1/2 on the +-y bonds, the sign read from the iterator's directions; on a BilayerSquareLattice s, s*
+        and d on the in-plane neighbours and s_perp = 1 on the interlayer direction.  None or {} turns the channels
         off.  Needs set_local_targets(iterator); frees the two pairing response binners."""
         from .lattices import default_pair_channels
 
@@ -1890,6 +1893,7 @@ class DQMC:
         dim = A.shape[0]
         if not 0 <= axis < dim:
             raise ValueError("axis must be 0 .. %d" % (dim - 1))
+        self._no_interlayer_current(axis)
         a = A[axis] / np.linalg.norm(A[axis])  # (A_i: the vectors the lattice is periodic under, along the bonds)
         nrm = np.linalg.norm(self._dirs[:self._Kcc], axis=1)
         par = [k for k in range(self._Kcc) if nrm[k] > 0 and np.isclose(abs(self._dirs[k] @ a), nrm[k])]
@@ -2175,6 +2179,13 @@ class DQMC:
                                       "current_response() and current_time_displaced() with K = 9 hold the diagonal bonds"
                                       % who)
 
+    def _no_interlayer_current(self, axis):
+        """a BilayerSquareLattice has one interlayer direction, its own inverse: there is no +- pair of bonds along z to
+        take a current from, and no smallest momentum along it"""
+        from .lattices import BilayerSquareLattice
+        if isinstance(self.model.l, BilayerSquareLattice) and axis == 2:
+            raise ValueError("axis 2 of a BilayerSquareLattice: the interlayer current response is not implemented (axis 0 or 1)")
+
     def _axis_bonds(self, axis):
         """(k+, k-, index of q = 0): the current-target columns along +-axis as superfluid_stiffness takes them"""
         if self._dirs is None or self._mom is None:
@@ -2182,6 +2193,7 @@ class DQMC:
         A = np.array(_lat_vectors(self.model.l), dtype=np.float64)
         if not 0 <= axis < A.shape[0]:
             raise ValueError("axis must be 0 .. %d" % (A.shape[0] - 1))
+        self._no_interlayer_current(axis)
         a = A[axis] / np.linalg.norm(A[axis])
         nrm = np.linalg.norm(self._dirs[:self._Kcc], axis=1)
         par = [k for k in range(self._Kcc) if nrm[k] > 0 and np.isclose(abs(self._dirs[k] @ a), nrm[k])]
@@ -2277,8 +2289,8 @@ class DQMC:
 
     def kron_hopping(self):
         """True when slice products and wraps apply the hopping exponentials in factored form (16 x 16 Kronecker factors
-        at n = 256, 8 x 8 at n = 512, the triangular 16 x 16 lattice's three factors, the t-t' square 16 x 16 lattice's four;
-        include/dqmc_hip.h)"""
+        at n = 256, 8 x 8 at n = 512, the triangular 16 x 16 lattice's three factors, the t-t' square 16 x 16 lattice's four,
+        the 16 x 16 x 2 bilayer's 2 x 2 (x) 16 x 16 (x) 16 x 16; include/dqmc_hip.h)"""
         f = C.c_int32(0)
         self._c(lib().dqmc_kron_hopping(self._h, C.byref(f)))
         return bool(f.value)

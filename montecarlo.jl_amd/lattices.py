@@ -113,12 +113,41 @@ class TriangularLattice(AbstractLattice):
         self.bonds = bonds
 
 
+class BilayerSquareLattice(AbstractLattice):
+    """BilayerSquareLattice(L): two periodic L x L square layers, site 1 + x + L y + L^2 z (z = 0, 1 the layer; column-major
+    reshape of 1:2 L^2 to (L, L, 2)).  neighs rows = up, right, down, left inside the layer (the SquareLattice circshift
+    convention, per layer), then perp: the same (x, y) in the other layer.  The bonds table lists up and right for every
+    source and perp for the sources of layer 0, so every physical bond stands once (5 L^2; at L = 2 the periodic in-plane
+    bonds count twice, as on SquareLattice(2)).  On the torus Z_L x Z_L x Z_2 it is a Bravais lattice with the layer swap
+    as its z translation: one target per direction, as many directions as sites.  An extension: the reference has no such
+    lattice.  Not a SquareLattice: no nnn table, no t'."""
+
+    def __init__(self, L):
+        self.L = L
+        self.sites = 2 * L * L
+        lat = np.arange(1, self.sites + 1).reshape((L, L, 2), order="F")
+        self.lattice = lat
+        rows = [np.roll(lat, -1, axis=0), np.roll(lat, -1, axis=1), np.roll(lat, 1, axis=0), np.roll(lat, 1, axis=1),
+                lat[:, :, ::-1]]
+        self.neighs = np.vstack([x.reshape(-1, order="F") for x in rows]).astype(np.int64)
+        self.n_bonds = 5 * L * L
+        bonds = np.zeros((self.n_bonds, 3), dtype=np.int64)
+        b = 0
+        for src in lat.reshape(-1, order="F"):
+            bonds[b] = (src, self.neighs[0, src - 1], 0); b += 1
+            bonds[b] = (src, self.neighs[1, src - 1], 0); b += 1
+            if src <= L * L:
+                bonds[b] = (src, self.neighs[4, src - 1], 0); b += 1
+        self.bonds = bonds
+
+
 def strip_subsystem(lattice, width, axis=0):
     """The 0-based sites, ascending, whose integer coordinate along `axis` is below `width`: the strip subsystem of an
-    entanglement cut (DQMC.set_entanglement), for SquareLattice, CubicLattice and TriangularLattice, whose `lattice`
-    array carries the coordinates (axis 0 runs fastest in the site index)."""
-    if not isinstance(lattice, (SquareLattice, CubicLattice, TriangularLattice)):
-        raise TypeError("strip_subsystem: SquareLattice, CubicLattice or TriangularLattice, not %s" % type(lattice).__name__)
+    entanglement cut (DQMC.set_entanglement), for SquareLattice, CubicLattice, TriangularLattice and BilayerSquareLattice,
+    whose `lattice` array carries the coordinates (axis 0 runs fastest in the site index)."""
+    if not isinstance(lattice, (SquareLattice, CubicLattice, TriangularLattice, BilayerSquareLattice)):
+        raise TypeError("strip_subsystem: SquareLattice, CubicLattice, TriangularLattice or BilayerSquareLattice, not %s"
+                        % type(lattice).__name__)
     lat = lattice.lattice
     if not 0 <= int(axis) < lat.ndim:
         raise ValueError("strip_subsystem: axis %r of a %d-dimensional lattice" % (axis, lat.ndim))
@@ -165,6 +194,8 @@ def _positions(l):
     if isinstance(l, CubicLattice):
         _check_cubic(l)
         return [np.array([i + 1.0, j + 1.0, k + 1.0]) for k in range(l.L) for j in range(l.L) for i in range(l.L)]
+    if isinstance(l, BilayerSquareLattice):
+        return [np.array([i + 1.0, j + 1.0, k + 1.0]) for k in range(2) for j in range(l.L) for i in range(l.L)]
     return [np.array([i + 1.0]) for i in range(l.sites)]
 
 
@@ -176,6 +207,8 @@ def _lattice_vectors(l):
     if isinstance(l, CubicLattice):
         _check_cubic(l)
         return [np.array([float(l.L), 0.0, 0.0]), np.array([0.0, float(l.L), 0.0]), np.array([0.0, 0.0, float(l.L)])]
+    if isinstance(l, BilayerSquareLattice):  # the layer swap is the z translation: period 2
+        return [np.array([float(l.L), 0.0, 0.0]), np.array([0.0, float(l.L), 0.0]), np.array([0.0, 0.0, 2.0])]
     return [np.array([float(l.sites)])]
 
 
@@ -183,10 +216,13 @@ def momentum_grid(l):
     """-> (q [N, dim], labels [N, dim]): the N wave vectors a periodic lattice of N sites allows, cartesian, and their
     integer labels.  With A_i = _lattice_vectors(l), the vectors the lattice is periodic under, the reciprocal basis is
     G_j with A_i . G_j = 2 pi delta_ij, and q = sum_j m_j G_j, m_j = 0 .. L_j - 1 (L_j the number of sites along A_j);
-    the first label runs fastest.  Chain, SquareLattice, CubicLattice (D = 3) and TriangularLattice."""
+    the first label runs fastest.  Chain, SquareLattice, CubicLattice (D = 3), TriangularLattice and BilayerSquareLattice
+    (counts (L, L, 2): q_z = 0 and pi are the bonding and antibonding combinations of the layers)."""
     A = np.array(_lattice_vectors(l), dtype=np.float64)  # rows A_i
     if isinstance(l, TriangularLattice):
         counts = (l.Lx, l.Ly)
+    elif isinstance(l, BilayerSquareLattice):
+        counts = (l.L, l.L, 2)
     elif isinstance(l, (SquareLattice, CubicLattice)):
         counts = (l.L,) * A.shape[0]
     else:
@@ -199,7 +235,10 @@ def momentum_grid(l):
 def default_pair_channels(lattice, directions, K):
     """-> {name: weights f[k], k < K} over the K shortest directions (`directions[k]` the displacement, k = 0 on-site):
     s = e_0; s* = 1/2 on every nearest neighbour (the shortest non-zero directions among the K; the same 1/2 on every
-    lattice, no 1/sqrt(z)); on a SquareLattice also d = +1/2 on the bonds along x and -1/2 on those along y."""
+    lattice, no 1/sqrt(z)); on a SquareLattice also d = +1/2 on the bonds along x and -1/2 on those along y.  On a
+    BilayerSquareLattice the five nearest neighbours all have length 1 and are told apart by their z component: s* and d
+    take the four in-plane ones, and s_perp = 1 on the interlayer direction, which is its own inverse on the two-layer torus
+    (the 1 stands for the 1/2 + 1/2 of a +- pair)."""
     r = np.asarray(directions, dtype=np.float64)[:K]
     nrm = np.linalg.norm(r, axis=1)
     if K < 1 or nrm[0] > 1e-9:
@@ -207,6 +246,16 @@ def default_pair_channels(lattice, directions, K):
     s = np.zeros(K)
     s[0] = 1.0
     res = {"s": s}
+    if isinstance(lattice, BilayerSquareLattice):
+        nn = np.isclose(nrm, 1.0)
+        perp = nn & (np.abs(r[:, 2]) > 0.5)
+        inplane = nn & ~perp
+        if inplane.sum() != 4 or perp.sum() != 1:
+            raise ValueError("the bilayer channels need the four in-plane nearest neighbours and the interlayer one among the K directions")
+        res["s*"] = np.where(inplane, 0.5, 0.0)
+        res["d"] = np.where(inplane, np.where(np.abs(r[:, 0]) > np.abs(r[:, 1]), 0.5, -0.5), 0.0)
+        res["s_perp"] = np.where(perp, 1.0, 0.0)
+        return res
     if K > 1:
         nn = np.isclose(nrm, nrm[1:].min())
         res["s*"] = np.where(nn, 0.5, 0.0)

@@ -5,7 +5,7 @@ performance-critical methods (interaction_matrix_exp!, propose_local,
 accept_local!) live on the device behind dqmc_sweep_spatial / dqmc_propagate."""
 import numpy as np
 
-from .lattices import Chain, CubicLattice, SquareLattice
+from .lattices import BilayerSquareLattice, Chain, CubicLattice, SquareLattice
 
 
 def _check_tp(tp, l):
@@ -14,6 +14,26 @@ def _check_tp(tp, l):
     if tp != 0.0 and not isinstance(l, SquareLattice):
         raise ValueError("tp != 0 needs a SquareLattice, not %s" % type(l).__name__)
     return tp
+
+
+def _check_t_perp(t_perp, t, l):
+    """the interlayer hopping of a BilayerSquareLattice (None: t); no other lattice has one"""
+    if isinstance(l, BilayerSquareLattice):
+        return float(t) if t_perp is None else float(t_perp)
+    if t_perp is not None:
+        raise ValueError("t_perp needs a BilayerSquareLattice, not %s" % type(l).__name__)
+    return None
+
+
+def _add_hopping(T, l, t, t_perp):
+    """-t at T[trg, src] for every directed nearest-neighbour pair (+=: coinciding neighbours count twice); on a
+    BilayerSquareLattice -t_perp on the perp row of neighs (the fifth target of every source)"""
+    if t_perp is None:
+        for src, trg in l.neighbors(True):
+            T[trg - 1, src - 1] += -t
+        return
+    for k, (src, trg) in enumerate(l.neighbors(True)):
+        T[trg - 1, src - 1] += -(t_perp if k % 5 == 4 else t)
 
 
 def _add_tp(T, l, tp):
@@ -34,23 +54,24 @@ def choose_lattice(dims, L):
 
 class HubbardModelAttractive:
     """HubbardModelAttractive.jl:26-39; U is stored positive.  `tp` is the next-nearest-neighbour hopping t' of
-    H = -t sum_<ij> - t' sum_<<ij>> - mu sum n + U-term on a SquareLattice (an extension; tp = 0: the reference's matrices)."""
+    H = -t sum_<ij> - t' sum_<<ij>> - mu sum n + U-term on a SquareLattice (an extension; tp = 0: the reference's matrices).
+    `t_perp` is the interlayer hopping of a BilayerSquareLattice (None there: t; any value on another lattice: ValueError)."""
     flv = 1
     kind = 0
 
-    def __init__(self, L=None, dims=None, l=None, U=1.0, t=1.0, mu=0.0, tp=0.0):
+    def __init__(self, L=None, dims=None, l=None, U=1.0, t=1.0, mu=0.0, tp=0.0, t_perp=None):
         if U < 0:
             raise ValueError("U must be positive.")  # @assert U >= 0.
         self.l = l if l is not None else choose_lattice(dims, L)
         self.U, self.t, self.mu = float(U), float(t), float(mu)
         self.tp = _check_tp(tp, self.l)
+        self.t_perp = _check_t_perp(t_perp, self.t, self.l)
 
     def hopping_matrix(self):
         """HubbardModelAttractive.jl:78-91"""
         N = len(self.l)
         T = np.diag(np.full(N, -self.mu))
-        for src, trg in self.l.neighbors(True):
-            T[trg - 1, src - 1] += -self.t
+        _add_hopping(T, self.l, self.t, self.t_perp)
         if self.tp != 0.0:
             _add_tp(T, self.l, self.tp)
         return [T]
@@ -59,16 +80,18 @@ class HubbardModelAttractive:
 class HubbardModelRepulsive:
     """HubbardModelRepulsive.jl:24-41; two spin blocks (BlockDiagonal, :68-69).  The reference fixes mu at 0; here `mu`
     dopes the model: -mu on the diagonal of both blocks, as in the attractive model (mu = 0: the reference's matrices).
-    `tp`: the next-nearest-neighbour hopping t' on a SquareLattice, as in the attractive model."""
+    `tp`: the next-nearest-neighbour hopping t' on a SquareLattice, `t_perp`: the interlayer hopping of a
+    BilayerSquareLattice, both as in the attractive model."""
     flv = 2
     kind = 1
 
-    def __init__(self, L=None, dims=None, l=None, U=1.0, t=1.0, mu=0.0, tp=0.0):
+    def __init__(self, L=None, dims=None, l=None, U=1.0, t=1.0, mu=0.0, tp=0.0, t_perp=None):
         if U < 0:
             raise ValueError("U must be positive.")
         self.l = l if l is not None else choose_lattice(dims, L)
         self.U, self.t, self.mu = float(U), float(t), float(mu)
         self.tp = _check_tp(tp, self.l)
+        self.t_perp = _check_t_perp(t_perp, self.t, self.l)
 
     def hopping_matrix(self):
         """HubbardModelRepulsive.jl:87-100: BlockDiagonal(T, copy(T)), with -mu on the diagonal"""
@@ -76,8 +99,7 @@ class HubbardModelRepulsive:
         T = np.zeros((N, N))
         if self.mu != 0.0:
             T[np.diag_indices(N)] = -self.mu
-        for src, trg in self.l.neighbors(True):
-            T[trg - 1, src - 1] += -self.t
+        _add_hopping(T, self.l, self.t, self.t_perp)
         if self.tp != 0.0:
             _add_tp(T, self.l, self.tp)
         return [T, T.copy()]
