@@ -372,11 +372,16 @@ int dqmc_current_targets_plan(dqmc_handle *h, int32_t out[8]);
  * susceptibility layout: divided by N, no delta_tau.  The accumulator has the same layout, holds the sum of the samples
  * over walkers and calls, and ends with [samples]; dqmc_reset_accumulators clears it.
  * Every value is stored from a sum in a fixed order (no atomics): two passes on the same state give the same bits and a
- * walker's sample does not depend on the other walkers.  The Green's rows take one of two kernels (csrc/tdm.hip):
+ * walker's sample does not depend on the other walkers.  The Green's rows take one of three kernels (csrc/tdm.hip):
  * where n_dirs == n_sites and every source and every target meets each direction exactly once (translation-invariant
  * tables) a lane owns a direction and walks the columns through a table src_of[d + n_dirs j] built here from dir_of, so
- * that a wave reads within one column; every other table, or any table under DQMC_TDM_GENERAL=1 (read at dqmc_create),
- * takes the pair lists.  dqmc_time_displaced_plan: out = [rows R, every, what, fast (1 / 0)], all zero when off.
+ * that a wave reads within one column (fast = 1); where that test fails but every source and every target still meets
+ * a direction at most once and n_dirs <= 2 n_sites (a lattice with a two-site basis: the honeycomb has 3 n / 2
+ * directions, n or n / 2 pairs each) the same walk runs over a src_of with -1 where a column has no source in a direction
+ * (fast = 2, the injective form); every other table, or any table under DQMC_TDM_GENERAL=1 (read at dqmc_create), takes
+ * the pair lists (fast = 0).  The three differ in summation order only.  The division is by N = n_sites in all of them,
+ * whatever the pair count of a direction.  dqmc_time_displaced_plan: out = [rows R, every, what, fast (2 / 1 / 0)], all
+ * zero when off.
  * With recording off nothing is allocated or launched and every result is bit for bit that of a handle without it; with
  * recording on the pass leaves the susceptibility accumulators, mc.s.greens, the stacks, the HS field and the RNG
  * cursors bit for bit as without. */

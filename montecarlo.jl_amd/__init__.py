@@ -9,7 +9,8 @@ from .configurations import (CompressedConf, ConfigRecorder, Discarder, compress
                              decompress)
 from . import lattices  # noqa: F401
 from .lattices import (BilayerSquareLattice, Chain, EachLocalQuadByDistance, EachLocalQuadBySyncedDistance, EachSitePairByDistance,  # noqa: F401
-                       CubicLattice, SquareLattice, TriangularLattice, build_checkerboard, momentum_grid, strip_subsystem)
+                       CubicLattice, HoneycombLattice, SquareLattice, TriangularLattice, build_checkerboard, momentum_grid,
+                       strip_subsystem, sublattice_sign)
 from .models import (HubbardModel, HubbardModelAttractive, HubbardModelRepulsive,  # noqa: F401
                      rand_conf)
 from .sharding import (Communicator, reduce_accumulators, walker_block, walker_range,  # noqa: F401

@@ -219,6 +219,7 @@ struct dqmc_handle {
     struct TimeDisplaced {
         int every = 0, what = 0, R = 0;
         bool fast = false;
+        bool inj = false;  // the injective form (tdm_greens_inj_kernel): src_of has holes and n_dirs rows per column
         int *src_of = nullptr;
     } td;
     // tau-tau' covariance accumulators (taucov.inl, taucov.hip): bin_size == 0: off, nothing allocated.  Not sections.

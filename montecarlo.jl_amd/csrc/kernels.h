@@ -431,6 +431,12 @@ hipError_t launch_tdm_greens(bool fast, int n, int nb, int n_walkers, int R, int
                              const double *Gl0, const double *G0l, long stride_unit, const int *src_of,
                              const int *dir_ptr, const int *pair_src, const int *pair_trg, int n_dirs,
                              double *per_walker, long per_stride, hipStream_t s);
+// the injective form of the Green's rows: src_of[d + n_dirs j] with -1 where column j has no source in direction d (every
+// source and every target meets a direction at most once, n_dirs <= 2 n; chosen by the host where the fast form's Latin
+// square test fails); rows of n_dirs entries
+hipError_t launch_tdm_greens_inj(int n, int n_dirs, int nb, int n_walkers, int R, int row, int minus_identity,
+                                 const double *Gl0, const double *G0l, long stride_unit, const int *src_of,
+                                 double *per_walker, long per_stride, hipStream_t s);
 // density rows: the per-slice values of sus_pairs_kernel at offset + (q R + row) n_dirs + d, q = CDC, SDCx, SDCy, SDCz
 hipError_t launch_tdm_density(int n, int nb, int model, int n_walkers, int R, int row, int minus_identity,
                               const double *G00, const double *G0l, const double *Gl0, const double *Gll,

@@ -15,6 +15,8 @@
 // with dir_of[i, j] = d, and tdm_greens_fast_kernel gives each lane one direction d and lets it walk the columns j in
 // order: at every step a wave reads src_of[., j] contiguously and 64 elements of the one column j, 8 n contiguous bytes.
 // A workgroup is 64 directions x 4 column quarters (one wave per quarter); the four partial sums are added in order.
+// A table that is no Latin square but still injective (every source and every target meets a direction at most once,
+// n_dirs <= 2 n: the two-sublattice lattices) takes tdm_greens_inj_kernel, the same walk over a src_of with holes.
 // Every other table takes tdm_greens_pairs_kernel, one workgroup per (direction, matrix, walker) with a tree reduction.
 #include "kernels.h"
 
@@ -48,6 +50,40 @@ __global__ __launch_bounds__(TDM_DIRS *TDM_SEGS) void tdm_greens_fast_kernel(
         double t = part[0][lane];
         for (int q = 1; q < TDM_SEGS; ++q) t += part[q][lane];
         per_walker[(long)w * per_stride + ((long)(m * nb + b) * R + row) * n + d] = t / (double)n;
+    }
+}
+
+// The injective form: the table of a lattice with a basis (honeycomb: n_dirs = 3 n / 2) is no Latin square, but every
+// source and every target still meets a direction at most once, so src_of[d + n_dirs j] is well defined with holes (-1)
+// where column j has no source in direction d.  The walk is that of the fast form, one lane per direction over the columns
+// in order, a hole skipped; n_dirs <= 2 n bounds the table.  grid (ceil(n_dirs / 64), 2 nb, walkers), blockIdx.y as above;
+// the rows have n_dirs entries, as the pair-list kernel writes them.
+__global__ __launch_bounds__(TDM_DIRS *TDM_SEGS) void tdm_greens_inj_kernel(
+    int n, int n_dirs, int nb, int R, int row, int minus_identity, const double *__restrict__ Gl0,
+    const double *__restrict__ G0l, long stride_unit, const int *__restrict__ src_of, double *__restrict__ per_walker,
+    long per_stride)
+{
+    __shared__ double part[TDM_SEGS][TDM_DIRS];
+    const int lane = threadIdx.x & (TDM_DIRS - 1), seg = threadIdx.x / TDM_DIRS;
+    const int d = blockIdx.x * TDM_DIRS + lane, m = blockIdx.y / nb, b = blockIdx.y % nb, w = blockIdx.z;
+    const double *G = (m == 0 ? Gl0 : G0l) + (long)(w * nb + b) * stride_unit;
+    const bool sub = m == 1 && minus_identity;
+    const int len = (n + TDM_SEGS - 1) / TDM_SEGS, j0 = seg * len, j1 = min(n, j0 + len);
+    double s = 0.0;
+    if (d < n_dirs)
+        for (int j = j0; j < j1; ++j) {
+            const int i = src_of[d + (long)n_dirs * j];
+            if (i < 0) continue;
+            double v = G[i + (long)n * j];
+            if (sub && i == j) v -= 1.0;
+            s += v;
+        }
+    part[seg][lane] = s;
+    __syncthreads();
+    if (seg == 0 && d < n_dirs) {
+        double t = part[0][lane];
+        for (int q = 1; q < TDM_SEGS; ++q) t += part[q][lane];
+        per_walker[(long)w * per_stride + ((long)(m * nb + b) * R + row) * n_dirs + d] = t / (double)n;
     }
 }
 
@@ -135,6 +171,15 @@ hipError_t launch_tdm_greens(bool fast, int n, int nb, int n_walkers, int R, int
         hipLaunchKernelGGL(tdm_greens_pairs_kernel, dim3(n_dirs, 2 * nb, n_walkers), dim3(256), 0, s, n, nb, R, row,
                            minus_identity, Gl0, G0l, stride_unit, dir_ptr, pair_src, pair_trg, n_dirs, per_walker,
                            per_stride);
+    return hipGetLastError();
+}
+hipError_t launch_tdm_greens_inj(int n, int n_dirs, int nb, int n_walkers, int R, int row, int minus_identity,
+                                 const double *Gl0, const double *G0l, long stride_unit, const int *src_of,
+                                 double *per_walker, long per_stride, hipStream_t s)
+{
+    hipLaunchKernelGGL(tdm_greens_inj_kernel, dim3((n_dirs + TDM_DIRS - 1) / TDM_DIRS, 2 * nb, n_walkers),
+                       dim3(TDM_DIRS * TDM_SEGS), 0, s, n, n_dirs, nb, R, row, minus_identity, Gl0, G0l, stride_unit,
+                       src_of, per_walker, per_stride);
     return hipGetLastError();
 }
 hipError_t launch_tdm_density(int n, int nb, int model, int n_walkers, int R, int row, int minus_identity,

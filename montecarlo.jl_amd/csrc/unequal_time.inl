@@ -758,8 +758,33 @@ static int td_setup(dqmc_handle *h, int every, int what)
             HIPCHK(hipMemcpy(t.src_of, src_of.data(), sizeof(int) * nd * n, hipMemcpyHostToDevice));
         }
     }
+    // injective form: the Latin square test failed, but every source and every target still meets a direction at most
+    // once and n_dirs <= 2 n (a lattice with a two-site basis: 3 n / 2 directions): src_of with holes
+    bool inj = !fast && (what & DQMC_TD_GREENS) && !h->sw.tdm_general && nd != n && nd <= 2 * n;
+    if (inj) {
+        std::vector<int> ptr(nd + 1), src((size_t)n * n), dst((size_t)n * n);
+        HIPCHK(hipMemcpy(ptr.data(), h->dir_ptr, sizeof(int) * (nd + 1), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(src.data(), h->pair_src, sizeof(int) * n * n, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(dst.data(), h->pair_trg, sizeof(int) * n * n, hipMemcpyDeviceToHost));
+        std::vector<int> src_of((size_t)nd * n, -1);
+        std::vector<char> seen((size_t)n * nd, 0);
+        for (int d = 0; d < nd && inj; ++d)
+            for (int q = ptr[d]; q < ptr[d + 1]; ++q) {
+                const int i = src[q], j = dst[q];
+                if (i < 0 || i >= n || j < 0 || j >= n || seen[(size_t)i * nd + d] || src_of[d + (size_t)nd * j] >= 0) {
+                    inj = false;
+                    break;
+                }
+                seen[(size_t)i * nd + d] = 1;
+                src_of[d + (size_t)nd * j] = i;
+            }
+        if (inj) {
+            CHK(dalloc(h, &t.src_of, (size_t)nd * n));
+            HIPCHK(hipMemcpy(t.src_of, src_of.data(), sizeof(int) * nd * n, hipMemcpyHostToDevice));
+        }
+    }
     HIPCHK(hipStreamSynchronize(h->stream));
-    t.every = every; t.what = what; t.R = R; t.fast = fast;
+    t.every = every; t.what = what; t.R = R; t.fast = fast; t.inj = inj;
     return 0;
 }
 int dqmc_set_time_displaced(dqmc_handle *h, int32_t every, int32_t what)
@@ -799,7 +824,7 @@ int dqmc_time_displaced_plan(dqmc_handle *h, int32_t out[4])
 {
     if (!h || !out) return DQMC_ERR_INVALID;
     const dqmc_handle::TimeDisplaced &t = h->td;
-    out[0] = t.R; out[1] = t.every; out[2] = t.what; out[3] = t.every && t.fast ? 1 : 0;
+    out[0] = t.R; out[1] = t.every; out[2] = t.what; out[3] = !t.every ? 0 : (t.fast ? 1 : (t.inj ? 2 : 0));
     return DQMC_OK;
 }
 // row `row` of every walker's sample from one packed tuple (Timed by the caller)
@@ -809,7 +834,10 @@ static int td_record(dqmc_handle *h, int row, int minus_identity, const double *
     const dqmc_handle::TimeDisplaced &t = h->td;
     const dqmc_handle::Section &sc = h->sec[DQMC_RED_TIME_DISPLACED];
     const long off_density = (t.what & DQMC_TD_GREENS) ? 2L * h->nb * t.R * h->n_dirs : 0;
-    if (t.what & DQMC_TD_GREENS)
+    if ((t.what & DQMC_TD_GREENS) && t.inj)
+        HIPCHK(launch_tdm_greens_inj(h->n, h->n_dirs, h->nb, h->W, t.R, row, minus_identity, gl0, g0l, h->nn, t.src_of,
+                                     sc.per_walker, sc.bin_E, h->stream));
+    else if (t.what & DQMC_TD_GREENS)
         HIPCHK(launch_tdm_greens(t.fast, h->n, h->nb, h->W, t.R, row, minus_identity, gl0, g0l, h->nn, t.src_of,
                                  h->dir_ptr, h->pair_src, h->pair_trg, h->n_dirs, sc.per_walker, sc.bin_E, h->stream));
     if (t.what & DQMC_TD_DENSITY)

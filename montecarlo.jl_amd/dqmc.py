@@ -563,7 +563,7 @@ class DQMC:
 
     _MODELS = ("HubbardModelAttractive", "HubbardModelRepulsive")
     _LATTICES = {"SquareLattice": ("L",), "Chain": ("sites",), "CubicLattice": ("dim", "L"),
-                 "TriangularLattice": ("L", "Lx", "Ly"), "BilayerSquareLattice": ("L",)}  # class -> the attributes its constructor takes, in order
+                 "TriangularLattice": ("L", "Lx", "Ly"), "BilayerSquareLattice": ("L",), "HoneycombLattice": ("L",)}  # class -> the attributes its constructor takes, in order
 
     @staticmethod
     def _model_entry(m):
@@ -1391,8 +1391,10 @@ class DQMC:
         self._tcov = None  # (and the tau-tau' covariance)
 
     def time_displaced_plan(self):
-        """-> dict(rows, every, what, fast): fast = the Green's rows take the one-lane-per-direction kernel (all zero
-        when recording is off)"""
+        """-> dict(rows, every, what, fast): fast = 1: the Green's rows take the one-lane-per-direction kernel of a Latin
+        square table (the Bravais lattices); 2: its injective form over a table with holes (every source and every target
+        meets a direction at most once, n_dirs <= 2 n: HoneycombLattice); 0: the pair lists (all zero when recording is
+        off)"""
         out = (C.c_int32 * 4)()
         self._c(lib().dqmc_time_displaced_plan(self._h, out))
         return dict(zip(("rows", "every", "what", "fast"), (int(v) for v in out)))
@@ -1520,7 +1522,18 @@ class DQMC:
     def momentum_time_displaced(self):
         """-> dict of the transforms of time_displaced(): Gk_l0, Gk_0l (complex [n_blocks, R, n_q]: sum_d e^{-i q . r_d}
         X[d]) and nk = 1 - Re Gk_l0[:, 0, :] if the Green's rows are recorded, CDCk, SDCxk, SDCyk, SDCzk [R, n_q] (cosine
-        part) if the density rows are; tau, count"""
+        part) if the density rows are; tau, count.
+
+        On a lattice with a basis (HoneycombLattice) Gk_l0 and Gk_0l are the sublattice trace G_AA(k) + G_BB(k), formed
+        from the same-sublattice directions only, and Gk_l0_AB / Gk_0l_AB the complex off-diagonal part G_AB(k), formed
+        from the A -> B directions only (source on A; the B -> A directions hold its conjugate partner G_BA).
+        Normalisation: the device divides every direction's sum by n = 2 L^2, but a honeycomb direction class has one
+        pair per cell, n / 2 of them, so the host multiplies by 2: G_ab(k) = (1 / L^2) sum over the cells of both sites
+        e^{-i k . (r_i - r_j)} G[i, j], i on a, j on b, with the true site positions.  nk = 2 - Re tr G(k) at tau = 0 is
+        the occupation of both bands together.  The density transforms CDCk .. are the full sums over all directions,
+        sum_d cos(q . r_d) X[d] = (1 / n) sum_ij, as on every lattice."""
+        if self._basis_classes() is not None:
+            return self._momentum_time_displaced_basis()
         Ct, St = self._phase_tables()
         m = self._means("time_displaced")
         res = {"tau": m["tau"], "count": m["count"]}
@@ -1533,6 +1546,79 @@ class DQMC:
             if src in m:
                 res[src + "k"] = m[src] @ Ct
         return res
+
+    # ---- lattices with a basis: direction classes, sublattice-resolved G(k), staggered (q = 0, signed) transforms
+    def _basis_classes(self):
+        """None on a lattice without a `sublattice` array; else [n_dirs] of 0 (same sublattice), 1 (source on sublattice
+        0, target on 1: A -> B) or 2 (B -> A), read off the table of set_pair_directions"""
+        sub = getattr(self.model.l, "sublattice", None)
+        if sub is None or "pair_directions" not in self._tables:
+            return None
+        dir_of, nd = self._tables["pair_directions"]
+        sub = np.asarray(sub)
+        kind = np.where(sub[:, None] == sub[None, :], 0, np.where(sub[:, None] == 0, 1, 2))  # [src, trg]
+        cls = np.full(nd, -1, dtype=np.int64)
+        cls[np.asarray(dir_of).reshape(-1)] = kind.reshape(-1)
+        if (cls < 0).any() or not np.array_equal(cls[np.asarray(dir_of)], kind):
+            raise ValueError("the direction table mixes sublattice classes in one direction")
+        return cls
+
+    def _momentum_time_displaced_basis(self):
+        cls = self._basis_classes()
+        Ct, St = self._phase_tables()
+        m = self._means("time_displaced")
+        res = {"tau": m["tau"], "count": m["count"]}
+        same, ab = (cls == 0).astype(np.float64), (cls == 1).astype(np.float64)
+        for k, src in (("Gk_l0", "Gl0"), ("Gk_0l", "G0l")):
+            if src in m:
+                res[k] = 2.0 * ((m[src] * same) @ Ct - 1j * ((m[src] * same) @ St))
+                res[k + "_AB"] = 2.0 * ((m[src] * ab) @ Ct - 1j * ((m[src] * ab) @ St))
+        if "Gk_l0" in res:
+            res["nk"] = 2.0 - res["Gk_l0"][:, 0, :].real
+        for src in ("CDC", "SDCx", "SDCy", "SDCz"):
+            if src in m:
+                res[src + "k"] = m[src] @ Ct
+        return res
+
+    def sublattice_signs(self):
+        """-> [n_dirs] of +1 (same-sublattice direction) / -1 (inter-sublattice): lattices.sublattice_sign of the table of
+        set_pair_directions"""
+        cls = self._basis_classes()
+        if cls is None:
+            raise _lib.DQMCError(_lib.ERR_STATE, "sublattice_signs: a lattice with a sublattice array (HoneycombLattice) "
+                                 "and set_pair_directions first")
+        return np.where(cls == 0, 1.0, -1.0)
+
+    def staggered_structure_factors(self):
+        """-> dict(Sc, Sx, Sy, Sz, count): the q = 0 transform with the sublattice signs, sum_d sign_d X[d] of the means
+        CDC, SDCx, SDCy, SDCz = (1 / n) sum_ij (+1 same sublattice, -1 else) <O_i O_j>: the antiferromagnetic S_AF of the
+        four channels (the device's direction sums are divided by n = 2 L^2 whatever the pair count of a direction, so
+        this is the sum over all pairs over n; on the honeycomb an inter-sublattice direction holds n / 2 pairs and a
+        per-pair mean would carry a factor 2).  A host transform of the accumulated sums; for error bars hand the
+        signs to the momentum binner: set_staggered_momentum(), then binned("momentum_correlations")."""
+        sg = self.sublattice_signs()
+        m = self._means("correlations")
+        res = {k: float(m[src] @ sg) for k, src in (("Sc", "CDC"), ("Sx", "SDCx"), ("Sy", "SDCy"), ("Sz", "SDCz"))}
+        res["count"] = m["count"]
+        return res
+
+    def staggered_static_susceptibilities(self):
+        """-> dict(chi_c, chi_x, chi_y, chi_z, count): the same signed q = 0 transform of the means CDS, SDSx, SDSy, SDSz:
+        the antiferromagnetic chi_AF of the four channels (normalised as staggered_structure_factors)"""
+        sg = self.sublattice_signs()
+        m = self._means("susceptibilities")
+        res = {k: float(m[src] @ sg) for k, src in (("chi_c", "CDS"), ("chi_x", "SDSx"), ("chi_y", "SDSy"), ("chi_z", "SDSz"))}
+        res["count"] = m["count"]
+        return res
+
+    def set_staggered_momentum(self):
+        """hand the engine one table in the place of set_momenta's: cos = the sublattice signs, sin = 0 (the interface
+        takes any tables with n_q <= n_dirs), labelled q = 0.  The momentum binners then carry S_AF / chi_AF with error
+        bars: structure_factors() and static_susceptibilities() return them as their one "momentum".  Replaces the
+        tables of set_momenta (and disables the momentum binners, as set_momenta does)."""
+        sg = self.sublattice_signs()
+        dim = len(_lat_vectors(self.model.l)[0])
+        self._set_momenta(np.zeros((1, dim)), sg, np.zeros_like(sg))
 
     # ---- tau-tau' covariance (include/dqmc_hip.h "tau-tau' covariance")
     def set_tau_covariance(self, bin_size, what=("greens", "density")):
@@ -2173,6 +2259,11 @@ class DQMC:
         """superfluid_stiffness, drude_weight and dc_conductivity take the current along an axis and its kinetic energy from
         the two nearest-neighbour bonds along it: with tp != 0 the diagonal bonds carry current along both axes as well,
         and a number without them would be wrong"""
+        from .lattices import HoneycombLattice
+        if isinstance(self.model.l, HoneycombLattice):
+            raise NotImplementedError("%s: a HoneycombLattice has no +- pair of bonds along a cartesian axis (the inverse of "
+                                      "an A -> B bond starts on the other sublattice); current_response() with K = 7 holds "
+                                      "the six bond directions" % who)
         if getattr(self.model, "tp", 0.0) != 0.0:
             raise NotImplementedError("%s: the current along an axis is taken from the nearest-neighbour bonds only; with "
                                       "tp != 0 the diagonal bonds carry current as well (not implemented).  "

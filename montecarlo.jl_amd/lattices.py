@@ -141,10 +141,62 @@ class BilayerSquareLattice(AbstractLattice):
         self.bonds = bonds
 
 
+class HoneycombLattice(AbstractLattice):
+    """HoneycombLattice(L): L x L periodic cells of two sites, 2 L^2 sites.  Geometry of the reference's positions
+    (honeycomb.jl:130-135): v1 = (sqrt(3)/2, -1/2), v2 = (sqrt(3)/2, 1/2), the B site of a cell at (1/sqrt(3), 0) from
+    its A site.  Site order as that comprehension lists them: the sublattice o runs fastest, then y, then x, so site
+    1 + o + 2 (y + L x) sits at o b + x v1 + y v2 (x, y = 0 .. L - 1, o = 0: A, 1: B).  neighs has 3 rows: for an A site of
+    cell R the B sites of cells R, R - v1 and R - v2 (periodic); for a B site the three inverse steps, the A sites of R,
+    R + v1 and R + v2.  bonds lists the three rows of every A source: every physical bond once, 3 L^2 rows.  At L = 1 the
+    three neighbours of a site coincide and count three times in the hopping matrix (T[0, 1] = -3 t), as the periodic
+    bonds of SquareLattice(2) count twice.  `sublattice` is 0 on A and 1 on B, isAsite its negation; `lattice` [x, y, o]
+    holds the site of a cell coordinate.  An extension: the reference's honeycomb.jl is commented out and keeps other
+    tables.  A lattice with a basis: 3 L^2 directions (EachSitePairByDistance), not one per site."""
+
+    def __init__(self, L):
+        self.L = L
+        self.sites = 2 * L * L
+        lat = np.zeros((L, L, 2), dtype=np.int64)
+        for x in range(L):
+            for y in range(L):
+                for o in range(2):
+                    lat[x, y, o] = 1 + o + 2 * (y + L * x)
+        self.lattice = lat
+        self.sublattice = np.array([i % 2 for i in range(self.sites)], dtype=np.int64)
+        self.isAsite = self.sublattice == 0
+        neighs = np.zeros((3, self.sites), dtype=np.int64)
+        for x in range(L):
+            for y in range(L):
+                a, b = lat[x, y, 0] - 1, lat[x, y, 1] - 1
+                neighs[:, a] = (lat[x, y, 1], lat[(x - 1) % L, y, 1], lat[x, (y - 1) % L, 1])
+                neighs[:, b] = (lat[x, y, 0], lat[(x + 1) % L, y, 0], lat[x, (y + 1) % L, 0])
+        self.neighs = neighs
+        self.n_bonds = 3 * L * L
+        bonds = np.zeros((self.n_bonds, 3), dtype=np.int64)
+        b = 0
+        for src in range(1, self.sites + 1, 2):  # the A sites, ascending
+            for trg in neighs[:, src - 1]:
+                bonds[b] = (src, trg, 0); b += 1
+        self.bonds = bonds
+
+
+HONEYCOMB_V1 = np.array([0.8660254037844386, -0.5])
+HONEYCOMB_V2 = np.array([0.8660254037844386, 0.5])
+HONEYCOMB_B = np.array([0.5773502691896258, 0.0])
+
+
 def strip_subsystem(lattice, width, axis=0):
     """The 0-based sites, ascending, whose integer coordinate along `axis` is below `width`: the strip subsystem of an
     entanglement cut (DQMC.set_entanglement), for SquareLattice, CubicLattice, TriangularLattice and BilayerSquareLattice,
-    whose `lattice` array carries the coordinates (axis 0 runs fastest in the site index)."""
+    whose `lattice` array carries the coordinates (axis 0 runs fastest in the site index).  On a HoneycombLattice the
+    coordinates are the cell coordinates (x, y) along v1 and v2 (axis 0 or 1): both sublattice sites of a cell belong to
+    the strip."""
+    if isinstance(lattice, HoneycombLattice):
+        if int(axis) not in (0, 1):
+            raise ValueError("strip_subsystem: axis %r of a HoneycombLattice (0 or 1: the cell coordinates)" % (axis,))
+        if not 1 <= int(width) <= lattice.L:
+            raise ValueError("strip_subsystem: width %r outside 1 .. %d" % (width, lattice.L))
+        return np.sort(np.take(lattice.lattice, np.arange(int(width)), axis=int(axis)).reshape(-1)).astype(np.int64) - 1
     if not isinstance(lattice, (SquareLattice, CubicLattice, TriangularLattice, BilayerSquareLattice)):
         raise TypeError("strip_subsystem: SquareLattice, CubicLattice, TriangularLattice or BilayerSquareLattice, not %s"
                         % type(lattice).__name__)
@@ -196,6 +248,8 @@ def _positions(l):
         return [np.array([i + 1.0, j + 1.0, k + 1.0]) for k in range(l.L) for j in range(l.L) for i in range(l.L)]
     if isinstance(l, BilayerSquareLattice):
         return [np.array([i + 1.0, j + 1.0, k + 1.0]) for k in range(2) for j in range(l.L) for i in range(l.L)]
+    if isinstance(l, HoneycombLattice):  # honeycomb.jl:130-135
+        return [o * HONEYCOMB_B + HONEYCOMB_V1 * x + HONEYCOMB_V2 * y for x in range(l.L) for y in range(l.L) for o in range(2)]
     return [np.array([i + 1.0]) for i in range(l.sites)]
 
 
@@ -209,6 +263,8 @@ def _lattice_vectors(l):
         return [np.array([float(l.L), 0.0, 0.0]), np.array([0.0, float(l.L), 0.0]), np.array([0.0, 0.0, float(l.L)])]
     if isinstance(l, BilayerSquareLattice):  # the layer swap is the z translation: period 2
         return [np.array([float(l.L), 0.0, 0.0]), np.array([0.0, float(l.L), 0.0]), np.array([0.0, 0.0, 2.0])]
+    if isinstance(l, HoneycombLattice):
+        return [HONEYCOMB_V1 * l.L, HONEYCOMB_V2 * l.L]
     return [np.array([float(l.sites)])]
 
 
@@ -217,12 +273,15 @@ def momentum_grid(l):
     integer labels.  With A_i = _lattice_vectors(l), the vectors the lattice is periodic under, the reciprocal basis is
     G_j with A_i . G_j = 2 pi delta_ij, and q = sum_j m_j G_j, m_j = 0 .. L_j - 1 (L_j the number of sites along A_j);
     the first label runs fastest.  Chain, SquareLattice, CubicLattice (D = 3), TriangularLattice and BilayerSquareLattice
-    (counts (L, L, 2): q_z = 0 and pi are the bonding and antibonding combinations of the layers)."""
+    (counts (L, L, 2): q_z = 0 and pi are the bonding and antibonding combinations of the layers); on a HoneycombLattice
+    the L^2 cell momenta (counts (L, L), A = L v1, L v2), N = sites / 2."""
     A = np.array(_lattice_vectors(l), dtype=np.float64)  # rows A_i
     if isinstance(l, TriangularLattice):
         counts = (l.Lx, l.Ly)
     elif isinstance(l, BilayerSquareLattice):
         counts = (l.L, l.L, 2)
+    elif isinstance(l, HoneycombLattice):  # the L^2 cell momenta: the two sublattice sites share them
+        counts = (l.L, l.L)
     elif isinstance(l, (SquareLattice, CubicLattice)):
         counts = (l.L,) * A.shape[0]
     else:
@@ -238,7 +297,9 @@ def default_pair_channels(lattice, directions, K):
     lattice, no 1/sqrt(z)); on a SquareLattice also d = +1/2 on the bonds along x and -1/2 on those along y.  On a
     BilayerSquareLattice the five nearest neighbours all have length 1 and are told apart by their z component: s* and d
     take the four in-plane ones, and s_perp = 1 on the interlayer direction, which is its own inverse on the two-layer torus
-    (the 1 stands for the 1/2 + 1/2 of a +- pair)."""
+    (the 1 stands for the 1/2 + 1/2 of a +- pair).  On a HoneycombLattice with K = 7 the six shortest non-zero directions
+    are the three A -> B and the three B -> A bonds: s* is 1/2 on all six, so every site sees weight 1/2 on each of its
+    three bonds (its other three directions have no target); s and s* only."""
     r = np.asarray(directions, dtype=np.float64)[:K]
     nrm = np.linalg.norm(r, axis=1)
     if K < 1 or nrm[0] > 1e-9:
@@ -329,6 +390,38 @@ class EachSitePairByDistance:
                 yield d + 1, s, t
 
 
+def _default_K(lattice):
+    """the default K of the quad iterators: on-site plus one direction per neighbour row.  On a HoneycombLattice the
+    three A -> B and the three B -> A nearest directions are distinct, so K = 1 + 2 * 3: every source then has its three
+    neighbours among its targets (and no target in the other three directions: trg_of == -1 there)."""
+    if isinstance(lattice, HoneycombLattice):
+        return 1 + 2 * lattice.neighs.shape[0]
+    return 1 + lattice.neighs.shape[0]
+
+
+def sublattice_sign(iterator, lattice):
+    """-> [n_dirs] of +1.0 / -1.0 over the directions of an EachSitePairByDistance (or anything with dir_of and
+    ndirections()): +1 where a direction joins sites of the same sublattice, -1 where it joins A and B.  The q = 0
+    transform with these signs is the staggered (antiferromagnetic) one.  Needs a lattice with a `sublattice` array
+    (HoneycombLattice); a direction that mixed both kinds of pair would be an error of the table."""
+    sub = getattr(lattice, "sublattice", None)
+    if sub is None:
+        raise TypeError("sublattice_sign: %s has no sublattice array" % type(lattice).__name__)
+    sub = np.asarray(sub)
+    dir_of = np.asarray(iterator.dir_of)
+    nd = int(iterator.ndirections())
+    pair_sign = np.where(sub[:, None] == sub[None, :], 1.0, -1.0)
+    sign = np.zeros(nd)
+    for s in (1.0, -1.0):
+        hit = np.unique(dir_of[pair_sign == s])
+        if np.any(sign[hit] != 0.0):
+            raise ValueError("sublattice_sign: a direction joins both kinds of pair")
+        sign[hit] = s
+    if np.any(sign == 0.0):
+        raise ValueError("sublattice_sign: a direction without pairs")
+    return sign
+
+
 class EachLocalQuadByDistance:
     """EachLocalQuadByDistance{K}(lattice) (src/lattices/lattice_iterators.jl:258-353): quadruples
     (src1, trg1, src2, trg2) where trg_k is reached from src_k in one of the K shortest directions,
@@ -341,7 +434,7 @@ class EachLocalQuadByDistance:
         self.pairs_by_dir = pairs if pairs is not None else EachSitePairByDistance(lattice)
         n = len(lattice)
         if K is None:  # pairing(): K = 1 + length(neighbors(lattice, 1)) (measurements.jl:199-204)
-            K = 1 + lattice.neighs.shape[0]
+            K = _default_K(lattice)
         if K > self.pairs_by_dir.ndirections():
             raise ValueError("K exceeds the number of directions of the lattice")
         self.K = K
@@ -390,7 +483,7 @@ class EachLocalQuadBySyncedDistance:
         self.pairs_by_dir = pairs if pairs is not None else EachSitePairByDistance(lattice)
         n = len(lattice)
         if K is None:  # current_current_susceptibility(): K = 1 + length(neighbors(lattice, 1)) (measurements.jl:257-263)
-            K = 1 + lattice.neighs.shape[0]
+            K = _default_K(lattice)
         if K > self.pairs_by_dir.ndirections():
             raise ValueError("K exceeds the number of directions of the lattice")
         self.K = K
