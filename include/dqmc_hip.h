@@ -67,6 +67,10 @@ typedef struct {
      * is unset; the test is max|E - product of the factors| <= 256 DBL_EPSILON max|E| with E[0,0] > 0.
      *  - n_sites == 256 (dense slab path): E = Ey (x) Ex, the periodic 16 x 16 square lattice (site x + 16 y), with
      *    Ex = E[0:16, 0:16], Ey = E[0::16, 0::16] / E[0,0].
+     *  - n_sites == 256, when a block fails that test: E = Ey (x) Ex with unequal factors, the periodic 32 x 8
+     *    rectangular lattice (site x + 32 y), with Ex = E[0:32, 0:32], Ey = E[0::32, 0::32][0:8, 0:8] / E[0,0].  That
+     *    orientation only: 8 x 32 and 64 x 4 keep the dense path.  Wraps are two launches and the sweep's last chunk is
+     *    applied by a flush of its own, as on the triangular path.
      *  - n_sites == 512: E = Ez (x) Ey (x) Ex, the periodic 8 x 8 x 8 cubic lattice (site x + 8 y + 64 z), with
      *    Ex = E[0:8, 0:8], Ey = E[0::8, 0::8][0:8, 0:8] / E[0,0], Ez = E[0::64, 0::64] / E[0,0].
      *  - n_sites == 512, when a block fails that test: E = Ez (x) Ey (x) Ex with a 2 x 2 Ez, the periodic two-layer
@@ -939,8 +943,8 @@ int dqmc_checkerboard_apply(dqmc_handle *h, int32_t which, int32_t slice, const 
  * the guarded single-workgroup kernel launched behind it redoes the factorisation, so results stay valid.  This counter reports
  * how often that happened.  (The one-launch UDT has no second path: its time-outs fail the call, see dqmc_device_errors.) */
 int dqmc_qr_fallbacks(dqmc_handle *h, int64_t *count);
-/* 1 when slice products and wraps apply eT2 / eTinv2 in factored form (Kronecker products of 16 x 16 factors at n = 256,
- * 8 x 8 factors or the two-layer 2 x 2 (x) 16 x 16 (x) 16 x 16 form at n = 512, see dqmc_params; the triangular 16 x 16 lattice's three factors, see
+/* 1 when slice products and wraps apply eT2 / eTinv2 in factored form (Kronecker products of 16 x 16 factors or of an 8 x 8 and a
+ * 32 x 32 factor at n = 256, 8 x 8 factors or the two-layer 2 x 2 (x) 16 x 16 (x) 16 x 16 form at n = 512, see dqmc_params; the triangular 16 x 16 lattice's three factors, see
  * dqmc_set_triangular_factors; the t-t' square 16 x 16 lattice's four factors, see dqmc_set_square_tp_factors), else 0 */
 int dqmc_kron_hopping(dqmc_handle *h, int32_t *on);
 /* The periodic 16 x 16 TriangularLattice (n_sites = 256, site x + 16 y; hopping along X = x + 1, Y = y + 1 and D = XY,

@@ -9,7 +9,8 @@ from .configurations import (CompressedConf, ConfigRecorder, Discarder, compress
                              decompress)
 from . import lattices  # noqa: F401
 from .lattices import (BilayerSquareLattice, Chain, EachLocalQuadByDistance, EachLocalQuadBySyncedDistance, EachSitePairByDistance,  # noqa: F401
-                       CubicLattice, HoneycombLattice, SquareLattice, TriangularLattice, build_checkerboard, momentum_grid,
+                       CubicLattice, HoneycombLattice, RectangularLattice, SquareLattice, TriangularLattice, build_checkerboard,
+                       momentum_grid,
                        strip_subsystem, sublattice_sign)
 from .models import (HubbardModel, HubbardModelAttractive, HubbardModelRepulsive,  # noqa: F401
                      rand_conf)

@@ -55,8 +55,11 @@ struct dqmc_handle {
     // n == 512 two-layer 16 x 16 x 2 lattice (bilayer_factor, tried when kron3_factor rejects a block): Ez (x) Ey (x) Ex with
     // Ex, Ey 16 x 16 and Ez 2 x 2, bilayer.hip instead of the dense GEMMs.
     // kron_f: [eT2, eTinv2, eT2', eTinv2'] x ([Ex] x nb x 256, [Ey, Ez, padding] x nb x BILAYER_FB).
+    // n == 256 rectangular 32 x 8 lattice (rect_factor, tried when kron_factor rejects a block): Ey (x) Ex with Ex 32 x 32 and
+    // Ey 8 x 8, rect.hip instead of slab.hip; like tri, without the pending-chunk fold and the one-launch wrap.
+    // kron_f: [eT2, eTinv2, eT2', eTinv2'] x ([Ex] x nb x 1024, [Ey] x nb x 64).
     // kron_fa / kron_fb: doubles per block of the two operand sets (ax / ay of a KronStep)
-    bool kron = false, tri = false, ttp = false, bilayer = false;
+    bool kron = false, tri = false, ttp = false, bilayer = false, rect = false;
     double *kron_f = nullptr;
     int kron_fa = 0, kron_fb = 0;
     int8_t *conf = nullptr;  // W x (N x M)
@@ -522,6 +525,27 @@ static bool bilayer_factor(const double *E, double *fx, double *fy, double *fz)
         }
     return std::isfinite(emax) && rmax <= 256.0 * 2.220446049250313e-16 * emax;
 }
+// eT2 / eTinv2 of the periodic 32 x 8 rectangular lattice (n = 256, site x + 32 y) as Ey (x) Ex with unequal factors:
+// Ex = E[0:32, 0:32], Ey = E[0::32, 0::32][0:8, 0:8] / E[0, 0].  The same acceptance as kron_factor (the lattice's
+// exponentials measure up to 16 ulp); 8 x 32, 64 x 4 and any other hopping keep the dense slab path.
+static bool rect_factor(const double *E, double *fx, double *fy)
+{
+    const int n = 256;
+    const double e00 = E[0];
+    if (!(e00 > 0.0)) return false;
+    for (int j = 0; j < 32; ++j)
+        for (int i = 0; i < 32; ++i) fx[i + 32 * j] = E[i + (size_t)n * j];
+    for (int j = 0; j < 8; ++j)
+        for (int i = 0; i < 8; ++i) fy[i + 8 * j] = E[32 * i + (size_t)n * 32 * j] / e00;
+    double emax = 0.0, rmax = 0.0;
+    for (int c = 0; c < n; ++c)
+        for (int r = 0; r < n; ++r) {
+            const double e = E[r + (size_t)n * c];
+            emax = std::max(emax, std::fabs(e));
+            rmax = std::max(rmax, std::fabs(e - fy[(r >> 5) + 8 * (c >> 5)] * fx[(r & 31) + 32 * (c & 31)]));
+        }
+    return std::isfinite(emax) && rmax <= 256.0 * 2.220446049250313e-16 * emax;
+}
 // The operand images kron3.hip reads (see there) of A = Ez (x) Exy, Exy = Ey (x) Ex; tr: of A' = Ez' (x) Exy'
 static void kron3_images(const double *fx, const double *fy, const double *fz, bool tr, double *img_xy, double *img_z)
 {
@@ -700,7 +724,7 @@ static int alloc_qr_workspace(dqmc_handle *h)
 // another handle, stream or process on the device: that case is what the bounded poll and the error bit are for.
 static int alloc_wrap_handoff(dqmc_handle *h)
 {
-    if (!h->kron || h->n != 256 || h->sw.wrap_two_launch) return 0;
+    if (!h->kron || h->n != 256 || h->rect || h->sw.wrap_two_launch) return 0;
     hipDeviceProp_t prop;
     HIPCHK(hipGetDeviceProperties(&prop, h->p.device_id));
     h->cus = prop.multiProcessorCount;
@@ -711,7 +735,7 @@ static int alloc_wrap_handoff(dqmc_handle *h)
 // whether wrap_greens_kron takes the one-launch form, with / without a pending chunk
 static bool wrap_one_launch(const dqmc_handle *h, bool pending)
 {
-    return h->wrap_cnt && h->n == 256 && !h->tri && kron_wrap_grid(h->units) <= h->wrap_blocks[pending ? 1 : 0];
+    return h->wrap_cnt && h->n == 256 && !h->tri && !h->rect && kron_wrap_grid(h->units) <= h->wrap_blocks[pending ? 1 : 0];
 }
 static int check_qr_workspace(dqmc_handle *h)
 {
@@ -927,8 +951,9 @@ static bool oop_wrap(const dqmc_handle *h) { return (h->slab || h->kron) && !h->
 // replaces is cheaper
 static bool fold_wrap_flush(const dqmc_handle *h)
 {
-    // (not on the triangular path: tri.hip has no pending-chunk form; the stand-alone flush applies the last chunk)
-    return use_kron(h) && h->n == 256 && !h->tri && h->sweep_fused && !h->sw.no_wrap_flush;
+    // (not on the triangular and rectangular paths: tri.hip and rect.hip have no pending-chunk form; the stand-alone flush
+    // applies the last chunk)
+    return use_kron(h) && h->n == 256 && !h->tri && !h->rect && h->sweep_fused && !h->sw.no_wrap_flush;
 }
 // greens as the reference has it: a pending last chunk is applied by the stand-alone flush (out of place through
 // greens_alt, which is free between two sweep_spatial calls)
@@ -974,6 +999,7 @@ static int run_kron(dqmc_handle *h, const KronArgs &a)
     else if (h->n == 512) HIPCHK(launch_kron3_chain(a, h->stream, ea, eb));
     else if (h->ttp) HIPCHK(launch_ttp_chain(a, h->stream, ea, eb));
     else if (h->tri) HIPCHK(launch_tri_chain(a, h->stream, ea, eb));
+    else if (h->rect) HIPCHK(launch_rect_chain(a, h->stream, ea, eb));
     else HIPCHK(launch_kron_chain(a, h->stream, ea, eb));
     return timing_push(h, ea, eb, DQMC_K_GEMM);
 }
@@ -1079,7 +1105,7 @@ static int wrap_greens_kron(dqmc_handle *h, const double *src, double *dst, int 
     KronArgs a = kron_base(h, src, h->bufB);
     a.transpose_out = 1;
     if (h->pf.G) {  // the sweep's last chunk is applied to the columns of src as the first launch loads them
-        if (h->pf.G != src || h->n != 256 || h->tri) return fail(h, DQMC_ERR_STATE, "wrap of another matrix with a sweep update pending");
+        if (h->pf.G != src || h->n != 256 || h->tri || h->rect) return fail(h, DQMC_ERR_STATE, "wrap of another matrix with a sweep update pending");
         a.pf_img = h->pf.img; a.pf_img_su = (long)sweep_lu_image_doubles(); a.pf_site0 = h->pf.site0;
         h->pf = dqmc_handle::PendingFlush{};
     }
@@ -1484,6 +1510,32 @@ int dqmc_create(const dqmc_params *p, dqmc_handle **out)
             CHIP(hipMemcpy(h->kron_f, f.data(), f.size() * sizeof(double), hipMemcpyHostToDevice));
             h->kron = true;
             h->kron_fa = h->kron_fb = 256;
+        }
+    }
+    if (h->slab && !h->sw.no_kron && !h->kron) {
+        // the 32 x 8 form: factors of eT2, eTinv2 and their transposes (Ey' (x) Ex': same residual, no second check)
+        const size_t per = (size_t)nb * (1024 + 64);
+        std::vector<double> f(4 * per);
+        double fx[1024], fy[64];
+        bool ok = true;
+        for (int m = 0; m < 2 && ok; ++m)
+            for (int b = 0; b < nb && ok; ++b) {
+                ok = rect_factor((m ? p->eTinv2 : p->eT2) + (size_t)b * h->nn, fx, fy);
+                for (int t = 0; t < 2; ++t) {
+                    double *dx = f.data() + (size_t)(m + 2 * t) * per + (size_t)b * 1024;
+                    double *dy = f.data() + (size_t)(m + 2 * t) * per + (size_t)nb * 1024 + (size_t)b * 64;
+                    for (int j = 0; j < 32; ++j)
+                        for (int i = 0; i < 32; ++i) dx[i + 32 * j] = t ? fx[j + 32 * i] : fx[i + 32 * j];
+                    for (int j = 0; j < 8; ++j)
+                        for (int i = 0; i < 8; ++i) dy[i + 8 * j] = t ? fy[j + 8 * i] : fy[i + 8 * j];
+                }
+            }
+        if (ok) {
+            CCHK(dalloc(h, &h->kron_f, f.size()));
+            CHIP(hipMemcpy(h->kron_f, f.data(), f.size() * sizeof(double), hipMemcpyHostToDevice));
+            h->kron = h->rect = true;
+            h->kron_fa = 1024;
+            h->kron_fb = 64;
         }
     }
     if (h->n == 512 && !h->sw.no_kron) {

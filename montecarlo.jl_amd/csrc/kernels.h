@@ -142,6 +142,9 @@ hipError_t launch_ttp_chain(const KronArgs &a, hipStream_t s, hipEvent_t start =
 // block b at + 256 b; ay = Ey of block b at + BILAYER_FB b, with the 2 x 2 Ez (column-major) behind it at + 256
 constexpr int BILAYER_FB = 264;
 hipError_t launch_bilayer_chain(const KronArgs &a, hipStream_t s, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
+// The same chains on the rectangular 32 x 8 lattice (n = 256, site x + 32 y) with A_s = Ey (x) Ex of unequal factors
+// (rect.hip): ax = Ex (32 x 32, column-major) of block b at + 1024 b, ay = Ey (8 x 8) of block b at + 64 b
+hipError_t launch_rect_chain(const KronArgs &a, hipStream_t s, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
 
 // Column-pivoted Householder QR, in place (udt_AVX_pivot! "QR decomposition" loop,
 // src/linalg/UDT.jl:212-246).  On exit A holds R on/above the diagonal and the

@@ -564,6 +564,13 @@ class DQMC:
     _MODELS = ("HubbardModelAttractive", "HubbardModelRepulsive")
     _LATTICES = {"SquareLattice": ("L",), "Chain": ("sites",), "CubicLattice": ("dim", "L"),
                  "TriangularLattice": ("L", "Lx", "Ly"), "BilayerSquareLattice": ("L",), "HoneycombLattice": ("L",)}  # class -> the attributes its constructor takes, in order
+    # the lattices added since: a table of their own, because tests/test_honeycomb_tables.py pins the one above entry by entry
+    _LATTICES_MORE = {"RectangularLattice": ("Lx", "Ly")}
+
+    @classmethod
+    def _lattice_args(cls, name):
+        """the constructor attributes of a lattice class a checkpoint can name, None for any other"""
+        return cls._LATTICES.get(name, cls._LATTICES_MORE.get(name))
 
     @staticmethod
     def _model_entry(m):
@@ -587,7 +594,7 @@ class DQMC:
 
     def _preamble(self, sweep, mid_sweep):
         m, l, p = self.model, self.model.l, self.p
-        if type(m).__name__ not in self._MODELS or type(l).__name__ not in self._LATTICES:
+        if type(m).__name__ not in self._MODELS or self._lattice_args(type(l).__name__) is None:
             raise ValueError("save(): %s on %s is not a model / lattice a checkpoint can name"
                              % (type(m).__name__, type(l).__name__))
         model = self._model_entry(m)
@@ -612,7 +619,7 @@ class DQMC:
             **extra,
             "format": 1,
             "model": model,
-            "lattice": {"class": type(l).__name__, "args": [int(getattr(l, a)) for a in self._LATTICES[type(l).__name__]]},
+            "lattice": {"class": type(l).__name__, "args": [int(getattr(l, a)) for a in self._lattice_args(type(l).__name__)]},
             "dqmc": dict(self._ctor, beta=p.beta, delta_tau=p.delta_tau, slices=p.slices, safe_mult=p.safe_mult,
                          thermalization=p.thermalization, sweeps=p.sweeps, measure_rate=p.measure_rate,
                          check_sign_problem=bool(p.check_sign_problem),
@@ -660,7 +667,7 @@ class DQMC:
         if pre.get("format") != 1:
             raise _ckpt.CheckpointError("checkpoint preamble format %r, this package reads format 1" % (pre.get("format"),))
         lat = pre["lattice"]
-        if lat["class"] not in cls._LATTICES or pre["model"]["class"] not in cls._MODELS:
+        if cls._lattice_args(lat["class"]) is None or pre["model"]["class"] not in cls._MODELS:
             raise _ckpt.CheckpointError("the checkpoint names an unknown model or lattice")
         l = getattr(_lat, lat["class"])(*lat["args"])
         model = cls._model_from_entry(pre["model"], l)
@@ -2381,7 +2388,8 @@ class DQMC:
     def kron_hopping(self):
         """True when slice products and wraps apply the hopping exponentials in factored form (16 x 16 Kronecker factors
         at n = 256, 8 x 8 at n = 512, the triangular 16 x 16 lattice's three factors, the t-t' square 16 x 16 lattice's four,
-        the 16 x 16 x 2 bilayer's 2 x 2 (x) 16 x 16 (x) 16 x 16; include/dqmc_hip.h)"""
+        the 16 x 16 x 2 bilayer's 2 x 2 (x) 16 x 16 (x) 16 x 16, the 32 x 8 rectangular lattice's 8 x 8 (x) 32 x 32;
+        include/dqmc_hip.h)"""
         f = C.c_int32(0)
         self._c(lib().dqmc_kron_hopping(self._h, C.byref(f)))
         return bool(f.value)

@@ -49,6 +49,37 @@ class SquareLattice(AbstractLattice):
         return [(src + 1, int(trg)) for src in range(self.sites) for trg in rows[:, src]]
 
 
+class RectangularLattice(AbstractLattice):
+    """RectangularLattice(Lx, Ly): the periodic Lx x Ly square-net torus, site 1 + x + Lx y (x fastest; column-major reshape
+    of 1:Lx*Ly to (Lx, Ly)).  neighs rows = up (x + 1), right (y + 1), down, left; nnn rows = upright, downright, downleft,
+    upleft; bonds = up and right of every source (2 Lx Ly rows; along an axis of length 2 the coinciding neighbours stand
+    twice): SquareLattice's circshift convention throughout, and RectangularLattice(L, L) has SquareLattice(L)'s tables.
+    An extension: the reference has no such lattice.  Not a SquareLattice: it has no single L, so no `isinstance(l,
+    SquareLattice)` branch takes it by accident."""
+
+    def __init__(self, Lx, Ly):
+        Lx, Ly = int(Lx), int(Ly)
+        if Lx < 2 or Ly < 2:
+            raise ValueError("RectangularLattice: Lx and Ly must be at least 2 (Lx = %d, Ly = %d)" % (Lx, Ly))
+        self.Lx, self.Ly = Lx, Ly
+        self.sites = Lx * Ly
+        lat = np.arange(1, self.sites + 1).reshape((Lx, Ly), order="F")
+        self.lattice = lat
+        near = [np.roll(lat, -1, axis=0), np.roll(lat, -1, axis=1), np.roll(lat, 1, axis=0), np.roll(lat, 1, axis=1)]
+        self.neighs = np.vstack([x.reshape(-1, order="F") for x in near]).astype(np.int64)
+        diag = [np.roll(lat, s, axis=(0, 1)) for s in ((-1, -1), (1, -1), (1, 1), (-1, 1))]
+        self.nnn = np.vstack([x.reshape(-1, order="F") for x in diag]).astype(np.int64)
+        self.n_bonds = 2 * self.sites
+        bonds = np.zeros((self.n_bonds, 3), dtype=np.int64)
+        b = 0
+        for src in lat.reshape(-1, order="F"):
+            bonds[b] = (src, self.neighs[0, src - 1], 0); b += 1
+            bonds[b] = (src, self.neighs[1, src - 1], 0); b += 1
+        self.bonds = bonds
+
+    next_neighbors = SquareLattice.next_neighbors
+
+
 class Chain(AbstractLattice):
     """Chain(nsites): neighs rows = right, left (chain.jl:36-41)."""
 
@@ -187,8 +218,8 @@ HONEYCOMB_B = np.array([0.5773502691896258, 0.0])
 
 def strip_subsystem(lattice, width, axis=0):
     """The 0-based sites, ascending, whose integer coordinate along `axis` is below `width`: the strip subsystem of an
-    entanglement cut (DQMC.set_entanglement), for SquareLattice, CubicLattice, TriangularLattice and BilayerSquareLattice,
-    whose `lattice` array carries the coordinates (axis 0 runs fastest in the site index).  On a HoneycombLattice the
+    entanglement cut (DQMC.set_entanglement), for SquareLattice, RectangularLattice, CubicLattice, TriangularLattice and
+    BilayerSquareLattice, whose `lattice` array carries the coordinates (axis 0 runs fastest in the site index).  On a HoneycombLattice the
     coordinates are the cell coordinates (x, y) along v1 and v2 (axis 0 or 1): both sublattice sites of a cell belong to
     the strip."""
     if isinstance(lattice, HoneycombLattice):
@@ -197,9 +228,9 @@ def strip_subsystem(lattice, width, axis=0):
         if not 1 <= int(width) <= lattice.L:
             raise ValueError("strip_subsystem: width %r outside 1 .. %d" % (width, lattice.L))
         return np.sort(np.take(lattice.lattice, np.arange(int(width)), axis=int(axis)).reshape(-1)).astype(np.int64) - 1
-    if not isinstance(lattice, (SquareLattice, CubicLattice, TriangularLattice, BilayerSquareLattice)):
-        raise TypeError("strip_subsystem: SquareLattice, CubicLattice, TriangularLattice or BilayerSquareLattice, not %s"
-                        % type(lattice).__name__)
+    if not isinstance(lattice, (SquareLattice, RectangularLattice, CubicLattice, TriangularLattice, BilayerSquareLattice)):
+        raise TypeError("strip_subsystem: SquareLattice, RectangularLattice, CubicLattice, TriangularLattice or "
+                        "BilayerSquareLattice, not %s" % type(lattice).__name__)
     lat = lattice.lattice
     if not 0 <= int(axis) < lat.ndim:
         raise ValueError("strip_subsystem: axis %r of a %d-dimensional lattice" % (axis, lat.ndim))
@@ -243,6 +274,8 @@ def _positions(l):
         return [a1 * (i + 1) + a2 * (j + 1) for j in range(l.Ly) for i in range(l.Lx)]
     if isinstance(l, SquareLattice):
         return [np.array([i + 1.0, j + 1.0]) for j in range(l.L) for i in range(l.L)]
+    if isinstance(l, RectangularLattice):
+        return [np.array([i + 1.0, j + 1.0]) for j in range(l.Ly) for i in range(l.Lx)]
     if isinstance(l, CubicLattice):
         _check_cubic(l)
         return [np.array([i + 1.0, j + 1.0, k + 1.0]) for k in range(l.L) for j in range(l.L) for i in range(l.L)]
@@ -258,6 +291,8 @@ def _lattice_vectors(l):
         return [np.array([0.5, 0.8660254037844386]) * l.Lx, np.array([float(l.Ly), 0.0])]
     if isinstance(l, SquareLattice):
         return [np.array([float(l.L), 0.0]), np.array([0.0, float(l.L)])]
+    if isinstance(l, RectangularLattice):
+        return [np.array([float(l.Lx), 0.0]), np.array([0.0, float(l.Ly)])]
     if isinstance(l, CubicLattice):
         _check_cubic(l)
         return [np.array([float(l.L), 0.0, 0.0]), np.array([0.0, float(l.L), 0.0]), np.array([0.0, 0.0, float(l.L)])]
@@ -272,11 +307,11 @@ def momentum_grid(l):
     """-> (q [N, dim], labels [N, dim]): the N wave vectors a periodic lattice of N sites allows, cartesian, and their
     integer labels.  With A_i = _lattice_vectors(l), the vectors the lattice is periodic under, the reciprocal basis is
     G_j with A_i . G_j = 2 pi delta_ij, and q = sum_j m_j G_j, m_j = 0 .. L_j - 1 (L_j the number of sites along A_j);
-    the first label runs fastest.  Chain, SquareLattice, CubicLattice (D = 3), TriangularLattice and BilayerSquareLattice
-    (counts (L, L, 2): q_z = 0 and pi are the bonding and antibonding combinations of the layers); on a HoneycombLattice
+    the first label runs fastest.  Chain, SquareLattice, RectangularLattice (counts (Lx, Ly)), CubicLattice (D = 3),
+    TriangularLattice and BilayerSquareLattice (counts (L, L, 2): q_z = 0 and pi are the bonding and antibonding combinations of the layers); on a HoneycombLattice
     the L^2 cell momenta (counts (L, L), A = L v1, L v2), N = sites / 2."""
     A = np.array(_lattice_vectors(l), dtype=np.float64)  # rows A_i
-    if isinstance(l, TriangularLattice):
+    if isinstance(l, (TriangularLattice, RectangularLattice)):
         counts = (l.Lx, l.Ly)
     elif isinstance(l, BilayerSquareLattice):
         counts = (l.L, l.L, 2)
@@ -294,7 +329,7 @@ def momentum_grid(l):
 def default_pair_channels(lattice, directions, K):
     """-> {name: weights f[k], k < K} over the K shortest directions (`directions[k]` the displacement, k = 0 on-site):
     s = e_0; s* = 1/2 on every nearest neighbour (the shortest non-zero directions among the K; the same 1/2 on every
-    lattice, no 1/sqrt(z)); on a SquareLattice also d = +1/2 on the bonds along x and -1/2 on those along y.  On a
+    lattice, no 1/sqrt(z)); on a SquareLattice or RectangularLattice also d = +1/2 on the bonds along x and -1/2 on those along y.  On a
     BilayerSquareLattice the five nearest neighbours all have length 1 and are told apart by their z component: s* and d
     take the four in-plane ones, and s_perp = 1 on the interlayer direction, which is its own inverse on the two-layer torus
     (the 1 stands for the 1/2 + 1/2 of a +- pair).  On a HoneycombLattice with K = 7 the six shortest non-zero directions
@@ -320,7 +355,7 @@ def default_pair_channels(lattice, directions, K):
     if K > 1:
         nn = np.isclose(nrm, nrm[1:].min())
         res["s*"] = np.where(nn, 0.5, 0.0)
-        if isinstance(lattice, SquareLattice):
+        if isinstance(lattice, (SquareLattice, RectangularLattice)):
             if nn.sum() != 4:
                 raise ValueError("the d channel needs the four nearest neighbours among the K directions")
             res["d"] = np.where(nn, np.where(np.abs(r[:, 0]) > np.abs(r[:, 1]), 0.5, -0.5), 0.0)

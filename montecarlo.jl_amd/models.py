@@ -5,14 +5,14 @@ performance-critical methods (interaction_matrix_exp!, propose_local,
 accept_local!) live on the device behind dqmc_sweep_spatial / dqmc_propagate."""
 import numpy as np
 
-from .lattices import BilayerSquareLattice, Chain, CubicLattice, SquareLattice
+from .lattices import BilayerSquareLattice, Chain, CubicLattice, RectangularLattice, SquareLattice
 
 
 def _check_tp(tp, l):
-    """next-nearest-neighbour hopping is defined on the square lattice only"""
+    """next-nearest-neighbour hopping is defined on the square and rectangular lattices only (the ones with an nnn table)"""
     tp = float(tp)
-    if tp != 0.0 and not isinstance(l, SquareLattice):
-        raise ValueError("tp != 0 needs a SquareLattice, not %s" % type(l).__name__)
+    if tp != 0.0 and not isinstance(l, (SquareLattice, RectangularLattice)):
+        raise ValueError("tp != 0 needs a SquareLattice or RectangularLattice, not %s" % type(l).__name__)
     return tp
 
 
