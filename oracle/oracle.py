@@ -248,11 +248,17 @@ class OracleDQMC:
         if hopping is None:
             hopping = hopping_square(L, t, mu if self.model == ATTRACTIVE else 0.0)
         self.T = hopping
-        # exps: the four constant matrices handed over explicitly (e.g. the checkerboard group products)
-        eT, eTinv, eT2, eTinv2 = [F(e) for e in exps] if exps is not None else hopping_exponentials(self.T, delta_tau)
-        self.eT, self.eTinv, self.eT2, self.eTinv2 = eT, eTinv, eT2, eTinv2
-        rep = lambda a: F(np.concatenate([a.reshape(-1, order="F")] * self.nb))
-        self._c = [rep(eT), rep(eTinv), rep(eT2), rep(eTinv2)]
+        # exps: the four constant matrices handed over explicitly (e.g. the checkerboard group products), replicated over
+        # the blocks; or a list of nb such four-tuples, one per block (self.eT .. self.eTinv2 are then block 0's)
+        if exps is not None and np.ndim(exps[0][0]) == 2:
+            if len(exps) != self.nb or any(len(e) != 4 for e in exps):
+                raise ValueError("exps: one (eT, eTinv, eT2, eTinv2) per block, %d blocks" % self.nb)
+            per_block = [[F(m) for m in e] for e in exps]
+        else:
+            per_block = [[F(e) for e in exps] if exps is not None else hopping_exponentials(self.T, delta_tau)] * self.nb
+        self.eT, self.eTinv, self.eT2, self.eTinv2 = per_block[0]
+        cat = lambda k: F(np.concatenate([e[k].reshape(-1, order="F") for e in per_block]))
+        self._c = [cat(0), cat(1), cat(2), cat(3)]
         self.h = lib().orc_create(self.N, self.model, self.slices, safe_mult, delta_tau, U,
                                   *[_dp(a) for a in self._c], int(check_propagation_error),
                                   int(check_sign_problem))

@@ -206,7 +206,8 @@ def test_multiplied_out_checkerboard_at_32x8_matches_oracle(gpu, O):
     """checkerboard=True at n = 256 hands the engine the bond groups multiplied out, and never tells it of a checkerboard.
     On this lattice those products are Kronecker products Ey (x) Ex themselves, so the gate, which reads the matrices,
     accepts them (observed: kron_hopping() True); what is asserted is the result: a prepare within TOL of the oracle given
-    the same products."""
+    the same products.  These products are not symmetric, which no exponential of the lattice's own hopping is; the chains,
+    wraps and sweeps of rect.hip on non-symmetric factors, in both spin blocks, are in test_gpu_factored_generic.py."""
     mc = gpu.DQMC(_model(gpu, "attractive", 32, 8), beta=1.0, n_walkers=1, seed=9, checkerboard=True)
     print("checkerboard=True at 32 x 8: kron_hopping() = %r" % mc.kron_hopping())
     _prepare_matches_oracle(O, mc, "attractive", (mc.hopping_matrix_exp[0], mc.hopping_matrix_exp_inv[0],
