@@ -2,7 +2,7 @@
 // factored form (n = 512 = 16 x 16 x 2).
 //
 // On the periodic 16 x 16 x 2 BilayerSquareLattice (site i = x + 16 y + 256 z, z the layer) every hopping exponential is,
-// up to rounding, a Kronecker product A = Ez (x) Ey (x) Ex with Ex, Ey 16 x 16 and Ez 2 x 2 (engine.cpp: bilayer_factor
+// up to rounding, a Kronecker product A = Ez (x) Ey (x) Ex with Ex, Ey 16 x 16 and Ez 2 x 2 (hopping_forms.h: kron_split
 // checks it at handle creation).  A column v of 512 entries is two planes V_z[x][y] = v[x + 16 y + 256 z], and
 //   (A v)_z = sum_z' Ez[z][z'] vec(Ex V_z' Ey^T):
 // the two 16-contractions of kron.hip on each plane, 16 v_mfma_f64_16x16x4_f64 per column instead of the 256 of the dense
@@ -21,13 +21,9 @@
 // the same lanes, so the layer factor needs no data movement; it commutes with the in-plane factors and is applied right
 // behind the step's first scaling.  A workgroup (4 waves, 8 columns) owns its columns through all steps; the result is
 // staged in LDS and stored as whole 64-byte runs, as is or transposed.
-#include "kernels.h"
-#include <hip/hip_ext.h>
+#include "factored_common.h"
 
 namespace dqmc {
-
-typedef double d4b __attribute__((ext_vector_type(4)));
-#define BL_MFMA(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 0)
 
 constexpr int BL_N = 512;
 constexpr int BL_P = 256;                         // sites of a plane
@@ -46,11 +42,6 @@ constexpr int BL_LDS_S = BL_N * BL_SLD + (BL_N / 16) * BL_SPAD;
 constexpr int BL_LDS = BL_LDS_T > BL_LDS_S ? BL_LDS_T : BL_LDS_S;  // 41 472 bytes: three workgroups per CU
 static_assert(BL_LDS >= BL_COLS * BL_N, "the untransposed staging image [column][entry] reuses the LDS");
 
-__device__ __forceinline__ double bl_conf(int8_t c, int sign, bool bn, double epl, double eml)
-{
-    return (((c > 0) == (sign > 0)) != bn) ? epl : eml;
-}
-
 __global__ __launch_bounds__(256) void bilayer_chain_kernel(KronArgs a)
 {
     __shared__ __attribute__((aligned(16))) double lds[BL_LDS];
@@ -65,7 +56,7 @@ __global__ __launch_bounds__(256) void bilayer_chain_kernel(KronArgs a)
     const double *x0u = a.X0 + (long)unit * a.x_su;
 
     // X_0: tile t = 2 h + z is plane z of column cp + h, parity (y, x): register r = entries ci + 16 (g + 4 r) of the plane
-    d4b v[BL_NT];
+    d4 v[BL_NT];
     {
         const double *x0 = x0u + (long)BL_N * cp + ci + 16 * g;
 #pragma unroll
@@ -118,7 +109,7 @@ __global__ __launch_bounds__(256) void bilayer_chain_kernel(KronArgs a)
             for (int z = 0; z < 2; ++z)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const double f = bl_conf(cur.cpre[z][r], st.pre_sign, bn, a.epl, a.eml);
+                    const double f = fk_conf(cur.cpre[z][r], st.pre_sign, bn, a.epl, a.eml);
                     v[z][r] *= f;
                     v[2 + z][r] *= f;
                 }
@@ -126,16 +117,16 @@ __global__ __launch_bounds__(256) void bilayer_chain_kernel(KronArgs a)
         // the layer factor: (V_0, V_1) <- (Ez00 V_0 + Ez01 V_1, Ez10 V_0 + Ez11 V_1), column by column
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-            const d4b p0 = v[2 * h], p1 = v[2 * h + 1];
+            const d4 p0 = v[2 * h], p1 = v[2 * h + 1];
             v[2 * h] = cur.ez[0] * p0 + cur.ez[2] * p1;
             v[2 * h + 1] = cur.ez[1] * p0 + cur.ez[3] * p1;
         }
         // P = Fa V  ->  tile[a][b]
 #pragma unroll
         for (int t = 0; t < BL_NT; ++t) {
-            d4b p = (d4b){0.0, 0.0, 0.0, 0.0};
+            d4 p = (d4){0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-            for (int q = 0; q < 4; ++q) p = BL_MFMA(cur.av[q], v[t][q], p);
+            for (int q = 0; q < 4; ++q) p = FK_MFMA(cur.av[q], v[t][q], p);
 #pragma unroll
             for (int r = 0; r < 4; ++r) tile[t * 16 * BL_TLD + (g + 4 * r) * BL_TLD + ci] = p[r];
         }
@@ -144,9 +135,9 @@ __global__ __launch_bounds__(256) void bilayer_chain_kernel(KronArgs a)
         // Q = Fb P^T: B operand of k-block q is P[a = ci][b = 4 q + g]; the result has b in the registers, a on the lanes
 #pragma unroll
         for (int t = 0; t < BL_NT; ++t) {
-            d4b q4 = (d4b){0.0, 0.0, 0.0, 0.0};
+            d4 q4 = (d4){0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-            for (int q = 0; q < 4; ++q) q4 = BL_MFMA(cur.bv[q], tile[t * 16 * BL_TLD + ci * BL_TLD + 4 * q + g], q4);
+            for (int q = 0; q < 4; ++q) q4 = FK_MFMA(cur.bv[q], tile[t * 16 * BL_TLD + ci * BL_TLD + 4 * q + g], q4);
             v[t] = q4;
         }
         __syncthreads();  // (the next step's tile writes, or the staging image, reuse the LDS)
@@ -155,7 +146,7 @@ __global__ __launch_bounds__(256) void bilayer_chain_kernel(KronArgs a)
             for (int z = 0; z < 2; ++z)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const double f = bl_conf(cur.cpost[z][r], st.post_sign, bn, a.epl, a.eml);
+                    const double f = fk_conf(cur.cpost[z][r], st.post_sign, bn, a.epl, a.eml);
                     v[z][r] *= f;
                     v[2 + z][r] *= f;
                 }
@@ -175,31 +166,14 @@ __global__ __launch_bounds__(256) void bilayer_chain_kernel(KronArgs a)
         }
     }
     __syncthreads();
-    double *o = a.out + (long)unit * a.out_su;
-    if (a.transpose_out) {  // out[c][e] = X[e][c]: row e of the image is 8 consecutive doubles at c0 + 512 e
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const int e2 = 2 * (tid + 256 * k), e = e2 >> 3, cl = e2 & 7;
-            *reinterpret_cast<double2 *>(o + c0 + (long)BL_N * e + cl) =
-                *reinterpret_cast<const double2 *>(lds + e * BL_SLD + (e >> 4) * BL_SPAD + cl);
-        }
-    } else {  // columns c0 .. c0 + 7 are 4096 consecutive doubles
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const int e2 = 2 * (tid + 256 * k);
-            *reinterpret_cast<double2 *>(o + (long)BL_N * c0 + e2) = *reinterpret_cast<const double2 *>(lds + e2);
-        }
-    }
+    fk_store_image<BL_N, BL_COLS, BL_SLD, BL_SPAD>(a.out + (long)unit * a.out_su, lds, a, c0, tid);
 }
 
 hipError_t launch_bilayer_chain(const KronArgs &a, hipStream_t s, hipEvent_t start, hipEvent_t stop)
 {
     if (a.nsteps < 1 || a.nsteps > SLAB_MAX_STEPS || a.nb < 1 || a.nb > 2 || a.n_units < 1) return hipErrorInvalidValue;
     if (a.x_su < (long)BL_N * BL_N || a.out_su < (long)BL_N * BL_N || a.pf_img) return hipErrorInvalidValue;
-    const dim3 grid(a.n_units * (BL_N / BL_COLS)), block(256);
-    if (start) hipExtLaunchKernelGGL(bilayer_chain_kernel, grid, block, 0, s, start, stop, 0, a);
-    else hipLaunchKernelGGL(bilayer_chain_kernel, grid, block, 0, s, a);
-    return hipGetLastError();
+    return fk_launch(bilayer_chain_kernel, dim3(a.n_units * (BL_N / BL_COLS)), a, s, start, stop);
 }
 
 }  // namespace dqmc

@@ -16,11 +16,13 @@
 #include <vector>
 
 #include "../../include/dqmc_hip.h"
+#include "hopping_forms.h"
 #include "kernels.h"
 #include "state_blob.h"
 #include <rccl/rccl.h>
 
 using namespace dqmc;
+static_assert(HOP_BILAYER_FB == BILAYER_FB, "the table and bilayer.hip agree on the block behind ay");
 
 struct dqmc_comm {
     ncclComm_t comm = nullptr;
@@ -43,25 +45,10 @@ struct dqmc_handle {
     double *eT = nullptr, *eTinv = nullptr, *eT2 = nullptr, *eTinv2 = nullptr;
     double *eT2T = nullptr;  // transposed copy of eT2: A operand of the daggered slice products in slab.hip
     bool slab = false;       // n == 256 dense path: slice chains and wraps as slab-resident launches
-    // n == 256 hopping exponentials that are Kronecker products Ey (x) Ex of 16 x 16 factors (kron_factor): slice chains
-    // and wraps take kron.hip instead of slab.hip.  kron_f: [eT2, eTinv2, eT2', eTinv2'] x [x, y] x nb x 16 x 16.
-    // n == 512 ones that are Ez (x) Ey (x) Ex of 8 x 8 factors (kron3_factor): kron3.hip instead of the dense GEMMs.
-    // kron_f: [eT2, eTinv2, eT2', eTinv2'] x ([Exy image] x nb x 4096, [Ez image] x nb x 256).
-    // n == 256 triangular 16 x 16 lattice (dqmc_set_triangular_factors): (Fy (x) Fx) Ed, tri.hip instead of slab.hip.
-    // kron_f: [eT2, eTinv2, eT2', eTinv2'] x [x, y, d] x nb x 16 x 16 (ax = Fx, ay = Fy, Fd behind Fy).
-    // n == 256 t-t' square 16 x 16 lattice (dqmc_set_square_tp_factors): (Fy (x) Fx) Ed Ea, ttp.hip instead of slab.hip.
-    // kron_f: [eT2, eTinv2, eT2', eTinv2'] x [x, y, d, a] x nb x 16 x 16 (Fd and Fa behind Fy); tri is set with ttp: what
-    // the triangular path leaves off (the pending-chunk fold, the one-launch wrap) is off here as well.
-    // n == 512 two-layer 16 x 16 x 2 lattice (bilayer_factor, tried when kron3_factor rejects a block): Ez (x) Ey (x) Ex with
-    // Ex, Ey 16 x 16 and Ez 2 x 2, bilayer.hip instead of the dense GEMMs.
-    // kron_f: [eT2, eTinv2, eT2', eTinv2'] x ([Ex] x nb x 256, [Ey, Ez, padding] x nb x BILAYER_FB).
-    // n == 256 rectangular 32 x 8 lattice (rect_factor, tried when kron_factor rejects a block): Ey (x) Ex with Ex 32 x 32 and
-    // Ey 8 x 8, rect.hip instead of slab.hip; like tri, without the pending-chunk fold and the one-launch wrap.
-    // kron_f: [eT2, eTinv2, eT2', eTinv2'] x ([Ex] x nb x 1024, [Ey] x nb x 64).
-    // kron_fa / kron_fb: doubles per block of the two operand sets (ax / ay of a KronStep)
-    bool kron = false, tri = false, ttp = false, bilayer = false, rect = false;
+    // the factored form of the hopping exponentials, if they have one (hopping_forms.h: the table, the operand layouts),
+    // and the device image of its factors: slice chains and wraps then take the form's kernel instead of slab.hip / the GEMMs
+    HopForm form = HopForm::None;
     double *kron_f = nullptr;
-    int kron_fa = 0, kron_fb = 0;
     int8_t *conf = nullptr;  // W x (N x M)
     // stack (slot-major): u/t: (K+1) x units x n^2 ; d: (K+1) x units x n
     double *u_stack = nullptr, *t_stack = nullptr, *d_stack = nullptr;
@@ -450,202 +437,6 @@ static int set_ones(dqmc_handle *h, double *d)
     return 0;
 }
 
-// eT2 / eTinv2 of the 16 x 16 periodic square lattice (n = 256, site x + 16 y) as Ey (x) Ex: Ex = E[0:16, 0:16] (the
-// y = y' = 0 block), Ey = E[0::16, 0::16] / E[0, 0].  Accepted when max|E - Ey (x) Ex| <= 256 eps max|E| (the exponentials
-// of the lattice's Kronecker-sum hopping matrix measure 16-28 ulp); any other hopping keeps the dense slab path.
-static bool kron_factor(const double *E, double *fx, double *fy)
-{
-    const int n = 256;
-    const double e00 = E[0];
-    if (!(e00 > 0.0)) return false;
-    for (int j = 0; j < 16; ++j)
-        for (int i = 0; i < 16; ++i) {
-            fx[i + 16 * j] = E[i + (size_t)n * j];
-            fy[i + 16 * j] = E[16 * i + (size_t)n * 16 * j] / e00;
-        }
-    double emax = 0.0, rmax = 0.0;
-    for (int y2 = 0; y2 < 16; ++y2)
-        for (int x2 = 0; x2 < 16; ++x2)
-            for (int y = 0; y < 16; ++y)
-                for (int x = 0; x < 16; ++x) {
-                    const double e = E[(x + 16 * y) + (size_t)n * (x2 + 16 * y2)];
-                    emax = std::max(emax, std::fabs(e));
-                    rmax = std::max(rmax, std::fabs(e - fy[y + 16 * y2] * fx[x + 16 * x2]));
-                }
-    return std::isfinite(emax) && rmax <= 256.0 * 2.220446049250313e-16 * emax;
-}
-
-// eT2 / eTinv2 of the 8 x 8 x 8 periodic cubic lattice (n = 512, site x + 8 y + 64 z) as Ez (x) Ey (x) Ex:
-// Ex = E[0:8, 0:8], Ey = E[0::8, 0::8][0:8, 0:8] / E[0, 0], Ez = E[0::64, 0::64] / E[0, 0].  The same acceptance as
-// kron_factor (the cubic lattice's exponentials measure 18-39 ulp); any other hopping keeps the dense path.
-static bool kron3_factor(const double *E, double *fx, double *fy, double *fz)
-{
-    const int n = 512;
-    const double e00 = E[0];
-    if (!(e00 > 0.0)) return false;
-    for (int j = 0; j < 8; ++j)
-        for (int i = 0; i < 8; ++i) {
-            fx[i + 8 * j] = E[i + (size_t)n * j];
-            fy[i + 8 * j] = E[8 * i + (size_t)n * 8 * j] / e00;
-            fz[i + 8 * j] = E[64 * i + (size_t)n * 64 * j] / e00;
-        }
-    double emax = 0.0, rmax = 0.0;
-    for (int c = 0; c < n; ++c)
-        for (int r = 0; r < n; ++r) {
-            const double e = E[r + (size_t)n * c];
-            const double f = fz[(r >> 6) + 8 * (c >> 6)] * fy[((r >> 3) & 7) + 8 * ((c >> 3) & 7)] * fx[(r & 7) + 8 * (c & 7)];
-            emax = std::max(emax, std::fabs(e));
-            rmax = std::max(rmax, std::fabs(e - f));
-        }
-    return std::isfinite(emax) && rmax <= 256.0 * 2.220446049250313e-16 * emax;
-}
-// eT2 / eTinv2 of the periodic two-layer 16 x 16 x 2 square lattice (n = 512, site x + 16 y + 256 z) as Ez (x) Ey (x) Ex:
-// Ex = E[0:16, 0:16], Ey = E[0::16, 0::16][0:16, 0:16] / E[0, 0], Ez = E[0::256, 0::256] / E[0, 0] (2 x 2).  The same
-// acceptance as kron_factor (the bilayer's exponentials measure up to 35 ulp over t_perp = 0.3 .. 3.5); any
-// other hopping keeps the dense path.
-static bool bilayer_factor(const double *E, double *fx, double *fy, double *fz)
-{
-    const int n = 512;
-    const double e00 = E[0];
-    if (!(e00 > 0.0)) return false;
-    for (int j = 0; j < 16; ++j)
-        for (int i = 0; i < 16; ++i) {
-            fx[i + 16 * j] = E[i + (size_t)n * j];
-            fy[i + 16 * j] = E[16 * i + (size_t)n * 16 * j] / e00;
-        }
-    for (int j = 0; j < 2; ++j)
-        for (int i = 0; i < 2; ++i) fz[i + 2 * j] = E[256 * i + (size_t)n * 256 * j] / e00;
-    double emax = 0.0, rmax = 0.0;
-    for (int c = 0; c < n; ++c)
-        for (int r = 0; r < n; ++r) {
-            const double e = E[r + (size_t)n * c];
-            const double f = fz[(r >> 8) + 2 * (c >> 8)] * fy[((r >> 4) & 15) + 16 * ((c >> 4) & 15)] * fx[(r & 15) + 16 * (c & 15)];
-            emax = std::max(emax, std::fabs(e));
-            rmax = std::max(rmax, std::fabs(e - f));
-        }
-    return std::isfinite(emax) && rmax <= 256.0 * 2.220446049250313e-16 * emax;
-}
-// eT2 / eTinv2 of the periodic 32 x 8 rectangular lattice (n = 256, site x + 32 y) as Ey (x) Ex with unequal factors:
-// Ex = E[0:32, 0:32], Ey = E[0::32, 0::32][0:8, 0:8] / E[0, 0].  The same acceptance as kron_factor (the lattice's
-// exponentials measure up to 16 ulp); 8 x 32, 64 x 4 and any other hopping keep the dense slab path.
-static bool rect_factor(const double *E, double *fx, double *fy)
-{
-    const int n = 256;
-    const double e00 = E[0];
-    if (!(e00 > 0.0)) return false;
-    for (int j = 0; j < 32; ++j)
-        for (int i = 0; i < 32; ++i) fx[i + 32 * j] = E[i + (size_t)n * j];
-    for (int j = 0; j < 8; ++j)
-        for (int i = 0; i < 8; ++i) fy[i + 8 * j] = E[32 * i + (size_t)n * 32 * j] / e00;
-    double emax = 0.0, rmax = 0.0;
-    for (int c = 0; c < n; ++c)
-        for (int r = 0; r < n; ++r) {
-            const double e = E[r + (size_t)n * c];
-            emax = std::max(emax, std::fabs(e));
-            rmax = std::max(rmax, std::fabs(e - fy[(r >> 5) + 8 * (c >> 5)] * fx[(r & 31) + 32 * (c & 31)]));
-        }
-    return std::isfinite(emax) && rmax <= 256.0 * 2.220446049250313e-16 * emax;
-}
-// The operand images kron3.hip reads (see there) of A = Ez (x) Exy, Exy = Ey (x) Ex; tr: of A' = Ez' (x) Exy'
-static void kron3_images(const double *fx, const double *fy, const double *fz, bool tr, double *img_xy, double *img_z)
-{
-    auto exy = [&](int r, int c) {
-        if (tr) std::swap(r, c);
-        return fy[(r >> 3) + 8 * (c >> 3)] * fx[(r & 7) + 8 * (c & 7)];
-    };
-    auto ez = [&](int r, int c) { return tr ? fz[c + 8 * r] : fz[r + 8 * c]; };
-    for (int mp = 0; mp < 4; ++mp)
-        for (int m = 0; m < 4; ++m)
-            for (int r = 0; r < 4; ++r)
-                for (int lane = 0; lane < 64; ++lane)
-                    img_xy[((mp * 4 + m) * 4 + r) * 64 + lane] = exy(16 * mp + (lane & 15), 16 * m + 4 * r + (lane >> 4));
-    for (int q = 0; q < 4; ++q)
-        for (int lane = 0; lane < 64; ++lane) {
-            const int row = lane & 15, k = 4 * q + (lane >> 4);
-            img_z[q * 64 + lane] = (row >> 3) == (k >> 3) ? ez(row & 7, k & 7) : 0.0;
-        }
-}
-
-// eT2 / eTinv2 of the 16 x 16 periodic triangular lattice (n = 256, site x + 16 y; hopping along X = (1, 0), Y = (0, 1) and
-// D = XY) as (Fy (x) Fx) Ed, where Ed applies Fd along the diagonals x - y = const:
-//   (Ed v)(x, y) = sum_y' Fd[y, y'] v(x - y + y', y')
-// The factors come from the host (dqmc_set_triangular_factors).  X, Y and D commute, so every order of the three products is
-// E up to rounding; the gate bounds the claimed form and the two orders the kernel applies (tri.hip: Fx Ed Fy from a step
-// that starts with y in the registers, Fy Ed Fx from one that starts with x), each by 256 eps max|E|.  Their transposes
-// (the daggered products and the wraps' right products) have the same residuals.
-static bool tri_factor_ok(const double *E, const double *fx, const double *fy, const double *fd)
-{
-    const int n = 256;
-    if (!(E[0] > 0.0)) return false;
-    auto F = [](const double *f, int r, int c) { return f[(r & 15) + 16 * (c & 15)]; };
-    double emax = 0.0, rmax = 0.0;
-    for (int y2 = 0; y2 < 16; ++y2)
-        for (int x2 = 0; x2 < 16; ++x2)
-            for (int y = 0; y < 16; ++y)
-                for (int x = 0; x < 16; ++x) {
-                    const double e = E[(x + 16 * y) + (size_t)n * (x2 + 16 * y2)];
-                    double claim = 0.0, xdy = 0.0, ydx = 0.0;
-                    for (int k = 0; k < 16; ++k) {
-                        claim += F(fy, y, k) * F(fx, x, x2 - y2 + k) * F(fd, k, y2);   // (Fy (x) Fx) Ed
-                        xdy += F(fx, x, x2 + y - k) * F(fd, y, k) * F(fy, k, y2);      // Fx Ed Fy
-                        ydx += F(fy, y, k) * F(fd, k, y2) * F(fx, x - k + y2, x2);     // Fy Ed Fx
-                    }
-                    emax = std::max(emax, std::fabs(e));
-                    rmax = std::max(rmax, std::max(std::fabs(e - claim), std::max(std::fabs(e - xdy), std::fabs(e - ydx))));
-                }
-    return std::isfinite(emax) && std::isfinite(rmax) && rmax <= 256.0 * 2.220446049250313e-16 * emax;
-}
-
-// eT2 / eTinv2 of the 16 x 16 periodic square lattice with next-nearest-neighbour hopping (n = 256, site x + 16 y; hopping
-// along X = (1, 0), Y = (0, 1), D = XY and A = X Y^-1) as (Fy (x) Fx) Ed Ea: Ed as above, and Ea applies Fa along the
-// anti-diagonals x + y = const:
-//   (Ea v)(x, y) = sum_y' Fa[y, y'] v(x + y - y', y')
-// The factors come from the host (dqmc_set_square_tp_factors).  The four shifts commute, so every order of the four products
-// is E up to rounding; the gate bounds the claimed form and the four orders the kernel applies (ttp.hip: Fx Ea Ed Fy from a
-// step that starts with y in the registers, Fy Ea Ed Fx from one that starts with x, and, as the transposes of what the
-// transposed factors give in the daggered products and the wraps' right products, Fy Ed Ea Fx and Fx Ed Ea Fy), each by
-// 256 eps max|E|.  Every order is formed by applying its factors to the identity, 16 terms per entry and factor.
-static bool ttp_factor_ok(const double *E, const double *fx, const double *fy, const double *fd, const double *fa)
-{
-    const int n = 256;
-    if (!(E[0] > 0.0)) return false;
-    std::vector<double> M((size_t)n * n), T((size_t)n * n);
-    // M <- Op(F) M, op 0: Fx on x, 1: Fy on y, 2: Ed, 3: Ea
-    auto apply = [&](int op, const double *F) {
-        for (int c = 0; c < n; ++c) {
-            const double *m = M.data() + (size_t)n * c;
-            double *t = T.data() + (size_t)n * c;
-            for (int y = 0; y < 16; ++y)
-                for (int x = 0; x < 16; ++x) {
-                    double acc = 0.0;
-                    for (int k = 0; k < 16; ++k) {
-                        const double f = F[(op == 0 ? x : y) + 16 * k];
-                        const int src = op == 0 ? k + 16 * y : op == 1 ? x + 16 * k : op == 2 ? ((x - y + k) & 15) + 16 * k
-                                                                                               : ((x + y - k) & 15) + 16 * k;
-                        acc += f * m[src];
-                    }
-                    t[x + 16 * y] = acc;
-                }
-        }
-        M.swap(T);
-    };
-    const double *F[4] = {fx, fy, fd, fa};
-    // (the operators are listed right to left: the first one is applied first)
-    static const int orders[5][4] = {{3, 2, 0, 1}, {1, 2, 3, 0}, {0, 2, 3, 1}, {0, 3, 2, 1}, {1, 3, 2, 0}};
-    double emax = 0.0, rmax = 0.0;
-    for (size_t i = 0; i < (size_t)n * n; ++i) emax = std::max(emax, std::fabs(E[i]));
-    for (const auto &ord : orders) {
-        std::fill(M.begin(), M.end(), 0.0);
-        for (int i = 0; i < n; ++i) M[i + (size_t)n * i] = 1.0;
-        for (int k = 0; k < 4; ++k) apply(ord[k], F[ord[k]]);
-        for (size_t i = 0; i < (size_t)n * n; ++i) {
-            const double r = std::fabs(E[i] - M[i]);
-            if (!(r <= rmax)) rmax = r;  // (a NaN is kept)
-        }
-    }
-    return std::isfinite(emax) && std::isfinite(rmax) && rmax <= 256.0 * 2.220446049250313e-16 * emax;
-}
-
 // The kernel-selection and test switches, read from the environment once per handle / stand-alone
 // primitive call: nothing else reads them (the launchers get them from the handle)
 static void read_kernel_switches(dqmc_handle *h)
@@ -724,7 +515,7 @@ static int alloc_qr_workspace(dqmc_handle *h)
 // another handle, stream or process on the device: that case is what the bounded poll and the error bit are for.
 static int alloc_wrap_handoff(dqmc_handle *h)
 {
-    if (!h->kron || h->n != 256 || h->rect || h->sw.wrap_two_launch) return 0;
+    if (!hop_row(h->form).one_launch_wrap || h->sw.wrap_two_launch) return 0;
     hipDeviceProp_t prop;
     HIPCHK(hipGetDeviceProperties(&prop, h->p.device_id));
     h->cus = prop.multiProcessorCount;
@@ -735,7 +526,7 @@ static int alloc_wrap_handoff(dqmc_handle *h)
 // whether wrap_greens_kron takes the one-launch form, with / without a pending chunk
 static bool wrap_one_launch(const dqmc_handle *h, bool pending)
 {
-    return h->wrap_cnt && h->n == 256 && !h->tri && !h->rect && kron_wrap_grid(h->units) <= h->wrap_blocks[pending ? 1 : 0];
+    return h->wrap_cnt && hop_row(h->form).one_launch_wrap && kron_wrap_grid(h->units) <= h->wrap_blocks[pending ? 1 : 0];
 }
 static int check_qr_workspace(dqmc_handle *h)
 {
@@ -942,18 +733,17 @@ static int run_slab(dqmc_handle *h, const SlabArgs &a)
 
 // ---- the same with Kronecker-factored hopping exponentials (kron.hip) -------------
 enum { KF_ET2 = 0, KF_ETINV2 = 1, KF_ET2T = 2, KF_ETINV2T = 3 };
-static bool use_kron(const dqmc_handle *h) { return h->kron && !h->cb.on; }
+static bool use_kron(const dqmc_handle *h) { return h->form != HopForm::None && !h->cb.on; }
 // wraps out of place (wrap_greens_slab): the n = 256 slab path and every factored path
-static bool oop_wrap(const dqmc_handle *h) { return (h->slab || h->kron) && !h->cb.on; }
+static bool oop_wrap(const dqmc_handle *h) { return (h->slab || h->form != HopForm::None) && !h->cb.on; }
 // the last chunk of sweep_spatial goes into the first launch of the next wrap (kron.hip) instead of a flush of its own.
 // Only with the fused chunk loop (few units: one round of workgroups): every one of the 16 workgroups of a unit reads all of
 // C (128 KB) and the image, so the folded launch grows with the units, and at 512 units (config 4) the multi-pass flush it
 // replaces is cheaper
 static bool fold_wrap_flush(const dqmc_handle *h)
 {
-    // (not on the triangular and rectangular paths: tri.hip and rect.hip have no pending-chunk form; the stand-alone flush
-    // applies the last chunk)
-    return use_kron(h) && h->n == 256 && !h->tri && !h->rect && h->sweep_fused && !h->sw.no_wrap_flush;
+    // (a form without a pending-chunk kernel: the stand-alone flush applies the last chunk)
+    return use_kron(h) && hop_row(h->form).pending_chunk && h->sweep_fused && !h->sw.no_wrap_flush;
 }
 // greens as the reference has it: a pending last chunk is applied by the stand-alone flush (out of place through
 // greens_alt, which is free between two sweep_spatial calls)
@@ -987,20 +777,19 @@ static KronStep &kron_step(dqmc_handle *h, KronArgs &a, int which)
 {
     KronStep &st = a.st[a.nsteps++];
     st = KronStep{};
-    st.ax = h->kron_f + (size_t)which * h->nb * (h->kron_fa + h->kron_fb);
-    st.ay = st.ax + (size_t)h->nb * h->kron_fa;
+    const HopFormRow &row = hop_row(h->form);
+    st.ax = h->kron_f + (size_t)which * h->nb * (row.fa + row.fb);
+    st.ay = st.ax + (size_t)h->nb * row.fa;
     return st;
 }
+// the chain launcher of every form, in the order of HopForm (None: run_kron is not reached without a form)
+static hipError_t (*const KRON_LAUNCHERS[])(const KronArgs &, hipStream_t, hipEvent_t, hipEvent_t) = {
+    nullptr, launch_kron_chain, launch_rect_chain, launch_kron3_chain, launch_bilayer_chain, launch_tri_chain, launch_ttp_chain};
 static int run_kron(dqmc_handle *h, const KronArgs &a)
 {
     hipEvent_t ea, eb;
     timing_events(h, &ea, &eb);
-    if (h->bilayer) HIPCHK(launch_bilayer_chain(a, h->stream, ea, eb));
-    else if (h->n == 512) HIPCHK(launch_kron3_chain(a, h->stream, ea, eb));
-    else if (h->ttp) HIPCHK(launch_ttp_chain(a, h->stream, ea, eb));
-    else if (h->tri) HIPCHK(launch_tri_chain(a, h->stream, ea, eb));
-    else if (h->rect) HIPCHK(launch_rect_chain(a, h->stream, ea, eb));
-    else HIPCHK(launch_kron_chain(a, h->stream, ea, eb));
+    HIPCHK(KRON_LAUNCHERS[(int)h->form](a, h->stream, ea, eb));
     return timing_push(h, ea, eb, DQMC_K_GEMM);
 }
 
@@ -1097,7 +886,7 @@ static int add_slice_sequence_right(dqmc_handle *h, int idx) { return add_slice_
 // product becomes a left product with the transposed factors:
 //   +1:  P = eT2 (eV G)           -> bufB = P'        dst = (eTinv2' (eV^-1 P'))'  = P eV^-1 eTinv2
 //   -1:  P = eV^-1 (eTinv2 G)     -> bufB = P'        dst = (eV (eT2' P'))'        = P eT2 eV
-// At n = 256 on the square lattice both run in one launch with a hand-off per unit (kron_wrap_kernel) when its whole grid is
+// On a form with the one-launch wrap (hopping_forms.h) both run in one launch with a hand-off per unit (kron_wrap_kernel) when its whole grid is
 // co-resident by the occupancy API (alloc_wrap_handoff); otherwise, and under DQMC_WRAP_TWO_LAUNCH, as two launches.
 static int wrap_greens_kron(dqmc_handle *h, const double *src, double *dst, int curr_slice, int direction)
 {
@@ -1105,7 +894,7 @@ static int wrap_greens_kron(dqmc_handle *h, const double *src, double *dst, int 
     KronArgs a = kron_base(h, src, h->bufB);
     a.transpose_out = 1;
     if (h->pf.G) {  // the sweep's last chunk is applied to the columns of src as the first launch loads them
-        if (h->pf.G != src || h->n != 256 || h->tri || h->rect) return fail(h, DQMC_ERR_STATE, "wrap of another matrix with a sweep update pending");
+        if (h->pf.G != src || !hop_row(h->form).pending_chunk) return fail(h, DQMC_ERR_STATE, "wrap of another matrix with a sweep update pending");
         a.pf_img = h->pf.img; a.pf_img_su = (long)sweep_lu_image_doubles(); a.pf_site0 = h->pf.site0;
         h->pf = dqmc_handle::PendingFlush{};
     }
@@ -1490,103 +1279,16 @@ int dqmc_create(const dqmc_params *p, dqmc_handle **out)
         CHIP(hipMemcpy(h->eT2T, tr.data(), cn * sizeof(double), hipMemcpyHostToDevice));
         h->slab = true;
     }
-    if (h->slab && !h->sw.no_kron) {
-        // factors of eT2, eTinv2 and their transposes ((Ey (x) Ex)' = Ey' (x) Ex': same residual, no second check)
-        std::vector<double> f((size_t)4 * 2 * nb * 256);
-        bool ok = true;
-        for (int m = 0; m < 2 && ok; ++m)
-            for (int b = 0; b < nb && ok; ++b) {
-                double *fx = f.data() + ((size_t)m * 2 * nb + b) * 256, *fy = fx + (size_t)nb * 256;
-                double *tx = f.data() + ((size_t)(m + 2) * 2 * nb + b) * 256, *ty = tx + (size_t)nb * 256;
-                ok = kron_factor((m ? p->eTinv2 : p->eT2) + (size_t)b * h->nn, fx, fy);
-                for (int j = 0; j < 16; ++j)
-                    for (int i = 0; i < 16; ++i) {
-                        tx[i + 16 * j] = fx[j + 16 * i];
-                        ty[i + 16 * j] = fy[j + 16 * i];
-                    }
-            }
-        if (ok) {
-            CCHK(dalloc(h, &h->kron_f, f.size()));
-            CHIP(hipMemcpy(h->kron_f, f.data(), f.size() * sizeof(double), hipMemcpyHostToDevice));
-            h->kron = true;
-            h->kron_fa = h->kron_fb = 256;
-        }
-    }
-    if (h->slab && !h->sw.no_kron && !h->kron) {
-        // the 32 x 8 form: factors of eT2, eTinv2 and their transposes (Ey' (x) Ex': same residual, no second check)
-        const size_t per = (size_t)nb * (1024 + 64);
-        std::vector<double> f(4 * per);
-        double fx[1024], fy[64];
-        bool ok = true;
-        for (int m = 0; m < 2 && ok; ++m)
-            for (int b = 0; b < nb && ok; ++b) {
-                ok = rect_factor((m ? p->eTinv2 : p->eT2) + (size_t)b * h->nn, fx, fy);
-                for (int t = 0; t < 2; ++t) {
-                    double *dx = f.data() + (size_t)(m + 2 * t) * per + (size_t)b * 1024;
-                    double *dy = f.data() + (size_t)(m + 2 * t) * per + (size_t)nb * 1024 + (size_t)b * 64;
-                    for (int j = 0; j < 32; ++j)
-                        for (int i = 0; i < 32; ++i) dx[i + 32 * j] = t ? fx[j + 32 * i] : fx[i + 32 * j];
-                    for (int j = 0; j < 8; ++j)
-                        for (int i = 0; i < 8; ++i) dy[i + 8 * j] = t ? fy[j + 8 * i] : fy[i + 8 * j];
-                }
-            }
-        if (ok) {
-            CCHK(dalloc(h, &h->kron_f, f.size()));
-            CHIP(hipMemcpy(h->kron_f, f.data(), f.size() * sizeof(double), hipMemcpyHostToDevice));
-            h->kron = h->rect = true;
-            h->kron_fa = 1024;
-            h->kron_fb = 64;
-        }
-    }
-    if (h->n == 512 && !h->sw.no_kron) {
-        // operand images of eT2, eTinv2 and their transposes (Ez' (x) Ey' (x) Ex': same residual, no second check)
-        const size_t per = (size_t)nb * (4096 + 256);
-        std::vector<double> f(4 * per);
-        double fx[64], fy[64], fz[64];
-        bool ok = true;
-        for (int m = 0; m < 2 && ok; ++m)
-            for (int b = 0; b < nb && ok; ++b) {
-                ok = kron3_factor((m ? p->eTinv2 : p->eT2) + (size_t)b * h->nn, fx, fy, fz);
-                for (int t = 0; t < 2; ++t) {
-                    double *xy = f.data() + (size_t)(m + 2 * t) * per + (size_t)b * 4096;
-                    kron3_images(fx, fy, fz, t == 1, xy, f.data() + (size_t)(m + 2 * t) * per + (size_t)nb * 4096 + (size_t)b * 256);
-                }
-            }
-        if (ok) {
-            CCHK(dalloc(h, &h->kron_f, f.size()));
-            CHIP(hipMemcpy(h->kron_f, f.data(), f.size() * sizeof(double), hipMemcpyHostToDevice));
-            h->kron = true;
-            h->kron_fa = 4096;
-            h->kron_fb = 256;
-        }
-    }
-    if (h->n == 512 && !h->sw.no_kron && !h->kron) {
-        // the two-layer form: factors of eT2, eTinv2 and their transposes (Ez' (x) Ey' (x) Ex': same residual, no second check)
-        const size_t per = (size_t)nb * (256 + BILAYER_FB);
-        std::vector<double> f(4 * per, 0.0);
-        double fx[256], fy[256], fz[4];
-        bool ok = true;
-        for (int m = 0; m < 2 && ok; ++m)
-            for (int b = 0; b < nb && ok; ++b) {
-                ok = bilayer_factor((m ? p->eTinv2 : p->eT2) + (size_t)b * h->nn, fx, fy, fz);
-                for (int t = 0; t < 2; ++t) {
-                    double *dx = f.data() + (size_t)(m + 2 * t) * per + (size_t)b * 256;
-                    double *dy = f.data() + (size_t)(m + 2 * t) * per + (size_t)nb * 256 + (size_t)b * BILAYER_FB;
-                    for (int j = 0; j < 16; ++j)
-                        for (int i = 0; i < 16; ++i) {
-                            dx[i + 16 * j] = t ? fx[j + 16 * i] : fx[i + 16 * j];
-                            dy[i + 16 * j] = t ? fy[j + 16 * i] : fy[i + 16 * j];
-                        }
-                    for (int j = 0; j < 2; ++j)
-                        for (int i = 0; i < 2; ++i) dy[256 + i + 2 * j] = t ? fz[j + 2 * i] : fz[i + 2 * j];
-                }
-            }
-        if (ok) {
-            CCHK(dalloc(h, &h->kron_f, f.size()));
-            CHIP(hipMemcpy(h->kron_f, f.data(), f.size() * sizeof(double), hipMemcpyHostToDevice));
-            h->kron = h->bilayer = true;
-            h->kron_fa = 256;
-            h->kron_fb = BILAYER_FB;
+    if (!h->sw.no_kron && (h->slab || h->n != 256)) {
+        // the gate forms of this size in the table's order: the first one that takes every block of eT2 and eTinv2 (at
+        // n = 256 the factored launches stand in for the slab path's: none without it)
+        std::vector<double> img;
+        for (HopForm f : {HopForm::Square16, HopForm::Rect32x8, HopForm::Cubic8, HopForm::Bilayer16}) {
+            if (hop_row(f).n != h->n || !build_hop_image(f, nb, p->eT2, p->eTinv2, nullptr, img)) continue;
+            CCHK(dalloc(h, &h->kron_f, img.size()));
+            CHIP(hipMemcpy(h->kron_f, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice));
+            h->form = f;
+            break;
         }
     }
     CCHK(dalloc(h, &h->conf, (size_t)h->W * h->N * h->M));
@@ -2386,83 +2088,31 @@ int dqmc_get_reduced_stats(dqmc_handle *h, dqmc_stats *out)
 }
 
 
-// The triangular 16 x 16 lattice's hopping exponentials as three 16 x 16 factors per matrix (include/dqmc_hip.h): checked
-// against the handle's own eT2 / eTinv2 (tri_factor_ok) before the handle takes them; a failed check leaves it as it was.
-int dqmc_set_triangular_factors(dqmc_handle *h, const double *f)
+// Factors from the host (include/dqmc_hip.h): the triangular 16 x 16 lattice's hopping exponentials as three 16 x 16 factors
+// per matrix, the t-t' square lattice's as four.  They are checked against the handle's own eT2 / eTinv2 (tri_factor_ok,
+// ttp_factor_ok) before the handle takes them; a failed check leaves it as it was.
+static int set_host_factors(dqmc_handle *h, const double *f, HopForm form, const std::string &name)
 {
     ENTER(h);
-    if (!f) return fail(h, DQMC_ERR_INVALID, "dqmc_set_triangular_factors: null factors");
-    if (h->n != 256) return fail(h, DQMC_ERR_INVALID, "dqmc_set_triangular_factors: n_sites must be 256");
-    if (h->prepared) return fail(h, DQMC_ERR_STATE, "dqmc_set_triangular_factors: call before dqmc_prepare");
-    if (!h->slab || h->cb.on || h->sw.no_kron || h->kron) return DQMC_OK;  // a path that does not take them: kept
+    if (!f) return fail(h, DQMC_ERR_INVALID, name + ": null factors");
+    if (h->n != 256) return fail(h, DQMC_ERR_INVALID, name + ": n_sites must be 256");
+    if (h->prepared) return fail(h, DQMC_ERR_STATE, name + ": call before dqmc_prepare");
+    if (!h->slab || h->cb.on || h->sw.no_kron || h->form != HopForm::None) return DQMC_OK;  // a path that does not take them: kept
     const int nb = h->nb;
-    std::vector<double> E((size_t)2 * nb * h->nn);
+    std::vector<double> E((size_t)2 * nb * h->nn), img;
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipMemcpy(E.data(), h->eT2, sizeof(double) * nb * h->nn, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(E.data() + (size_t)nb * h->nn, h->eTinv2, sizeof(double) * nb * h->nn, hipMemcpyDeviceToHost));
-    // [eT2, eTinv2, eT2', eTinv2'] x [x, y, d] x nb x 256
-    std::vector<double> img((size_t)4 * 3 * nb * 256);
-    for (int b = 0; b < nb; ++b)
-        for (int m = 0; m < 2; ++m) {
-            const double *fb = f + (size_t)b * 1536 + (size_t)m * 768;
-            if (!tri_factor_ok(E.data() + ((size_t)m * nb + b) * h->nn, fb, fb + 256, fb + 512))
-                return fail(h, DQMC_ERR_INVALID, "dqmc_set_triangular_factors: the factors do not reproduce eT2 / eTinv2 of block " +
-                                                     std::to_string(b) + " within 256 ulp");
-            for (int k = 0; k < 3; ++k) {
-                double *o = img.data() + (((size_t)m * 3 + k) * nb + b) * 256, *ot = o + (size_t)2 * 3 * nb * 256;
-                for (int j = 0; j < 16; ++j)
-                    for (int i = 0; i < 16; ++i) {
-                        o[i + 16 * j] = fb[256 * k + i + 16 * j];
-                        ot[i + 16 * j] = fb[256 * k + j + 16 * i];
-                    }
-            }
-        }
+    int b = 0;
+    if (!build_hop_image(form, nb, E.data(), E.data() + (size_t)nb * h->nn, f, img, &b))
+        return fail(h, DQMC_ERR_INVALID, name + ": the factors do not reproduce eT2 / eTinv2 of block " + std::to_string(b) + " within 256 ulp");
     CHK(dalloc(h, &h->kron_f, img.size()));
     HIPCHK(hipMemcpy(h->kron_f, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice));
-    h->kron_fa = 256;
-    h->kron_fb = 512;  // Fy, then Fd
-    h->tri = h->kron = true;
+    h->form = form;
     return DQMC_OK;
 }
-
-// The t-t' square 16 x 16 lattice's hopping exponentials as four 16 x 16 factors per matrix (include/dqmc_hip.h): checked
-// against the handle's own eT2 / eTinv2 (ttp_factor_ok) before the handle takes them; a failed check leaves it as it was.
-int dqmc_set_square_tp_factors(dqmc_handle *h, const double *f)
-{
-    ENTER(h);
-    if (!f) return fail(h, DQMC_ERR_INVALID, "dqmc_set_square_tp_factors: null factors");
-    if (h->n != 256) return fail(h, DQMC_ERR_INVALID, "dqmc_set_square_tp_factors: n_sites must be 256");
-    if (h->prepared) return fail(h, DQMC_ERR_STATE, "dqmc_set_square_tp_factors: call before dqmc_prepare");
-    if (!h->slab || h->cb.on || h->sw.no_kron || h->kron) return DQMC_OK;  // a path that does not take them: kept
-    const int nb = h->nb;
-    std::vector<double> E((size_t)2 * nb * h->nn);
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(E.data(), h->eT2, sizeof(double) * nb * h->nn, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(E.data() + (size_t)nb * h->nn, h->eTinv2, sizeof(double) * nb * h->nn, hipMemcpyDeviceToHost));
-    // [eT2, eTinv2, eT2', eTinv2'] x [x, y, d, a] x nb x 256
-    std::vector<double> img((size_t)4 * 4 * nb * 256);
-    for (int b = 0; b < nb; ++b)
-        for (int m = 0; m < 2; ++m) {
-            const double *fb = f + (size_t)b * 2048 + (size_t)m * 1024;
-            if (!ttp_factor_ok(E.data() + ((size_t)m * nb + b) * h->nn, fb, fb + 256, fb + 512, fb + 768))
-                return fail(h, DQMC_ERR_INVALID, "dqmc_set_square_tp_factors: the factors do not reproduce eT2 / eTinv2 of block " +
-                                                     std::to_string(b) + " within 256 ulp");
-            for (int k = 0; k < 4; ++k) {
-                double *o = img.data() + (((size_t)m * 4 + k) * nb + b) * 256, *ot = o + (size_t)2 * 4 * nb * 256;
-                for (int j = 0; j < 16; ++j)
-                    for (int i = 0; i < 16; ++i) {
-                        o[i + 16 * j] = fb[256 * k + i + 16 * j];
-                        ot[i + 16 * j] = fb[256 * k + j + 16 * i];
-                    }
-            }
-        }
-    CHK(dalloc(h, &h->kron_f, img.size()));
-    HIPCHK(hipMemcpy(h->kron_f, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice));
-    h->kron_fa = 256;
-    h->kron_fb = 768;  // Fy, then Fd, then Fa
-    h->ttp = h->tri = h->kron = true;
-    return DQMC_OK;
-}
+int dqmc_set_triangular_factors(dqmc_handle *h, const double *f) { return set_host_factors(h, f, HopForm::Tri16, "dqmc_set_triangular_factors"); }
+int dqmc_set_square_tp_factors(dqmc_handle *h, const double *f) { return set_host_factors(h, f, HopForm::Ttp16, "dqmc_set_square_tp_factors"); }
 
 // CheckerboardTrue with the bond-group factors kept sparse on the device (stack.jl:185-235): `n_mats` factors in ELL
 // form (vals / cols [n_mats][n][kmax], 0-based columns, padding val 0), the diagonal exp(-+dtau mu) per block and

@@ -94,9 +94,10 @@ struct SlabArgs {
     double epl, eml;
 };
 hipError_t launch_slab_chain(const SlabArgs &a, hipStream_t s, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
-// The same chains with Kronecker-factored A_s = ay (x) ax (kron.hip, n = 256 = 16 x 16 sites; kron3.hip, n = 512)
+// The same chains with A_s in one of the factored forms of hopping_forms.h, each with a kernel of its own (below); the
+// form's operand layout behind ax / ay is described once, at the table there
 struct KronStep {
-    const double *ax, *ay;               // 16 x 16 factors, column-major, block b at + 256 b
+    const double *ax, *ay;               // the two operand sets of A_s, all blocks (HopFormRow: fa / fb doubles per block)
     const int8_t *pre_conf; int pre_sign;    // conf pointers already offset to the slice; null = no scaling
     const int8_t *post_conf; int post_sign;
 };
@@ -109,7 +110,7 @@ struct KronArgs {
     int transpose_out;                   // store the result transposed
     long conf_stride;                    // per walker
     double epl, eml;
-    // pending rank-64 update of X_0 (n = 256 only): the last chunk of a sweep, eliminated but not yet applied to G.  When
+    // pending rank-64 update of X_0 (launch_kron_chain / launch_kron_wrap only): the last chunk of a sweep, eliminated but not yet applied to G.  When
     // pf_img is set, X_0 is first replaced by X_0 + (X_0[:, c] - E) X Y X_0[c, :] (c = pf_site0 .. + 63, the chunk's image
     // at pf_img + unit * pf_img_su): what sweep_flush_lu_kernel would have written (kron.hip).  Null: no update.
     const double *pf_img; long pf_img_su;

@@ -1,7 +1,7 @@
 // kron.hip — slice-matrix chains and wraps with the hopping exponential applied in Kronecker-factored form (n = 256).
 //
 // On the periodic 16 x 16 SquareLattice (site i = x + 16 y) every hopping exponential is, up to rounding, a Kronecker
-// product A = Ay (x) Ax of two 16 x 16 matrices (engine.cpp: kron_factor checks it at handle creation).  A column v of
+// product A = Ay (x) Ax of two 16 x 16 matrices (hopping_forms.h: kron_split checks it at handle creation).  A column v of
 // 256 entries, read as the 16 x 16 matrix V[x][y] = v[x + 16 y], then gives (A v) = vec(Ax V Ay^T): two 16-contractions,
 // 8 v_mfma_f64_16x16x4_f64 per column instead of the 64 of the dense product.
 //
@@ -27,13 +27,9 @@
 //   XV_J = X_J Q_J (R0_J + sum_{K<J} L_JK XV_K),   R^_J = PT_J (XV_J + X_J sum_{K>J} Uu_JK R^_K)
 // (blocks of 16 sites, image tiles as in kernels.h, each taken as the A operand of its own matrix), then 256 x 64 x 16 of
 // MFMA with C read from G.  R0 is register (site0 / 64) of the X_0 tiles already loaded.
-#include "kernels.h"
-#include <hip/hip_ext.h>
+#include "factored_common.h"
 
 namespace dqmc {
-
-typedef double d4k __attribute__((ext_vector_type(4)));
-#define KR_MFMA(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 0)
 
 constexpr int KR_N = 256;
 constexpr int KR_NC = 4;                 // columns per wave
@@ -56,12 +52,6 @@ typedef const KR_GLOBAL double *kr_gcdp;
 typedef double kr_d2 __attribute__((ext_vector_type(2)));
 typedef const KR_GLOBAL kr_d2 *kr_gcd2p;
 typedef unsigned kr_u4 __attribute__((ext_vector_type(4)));
-
-// exp(sign lambda conf[i]) of block blk (vs_conf() of engine.cpp, slab_conf_val() of slab.hip)
-__device__ __forceinline__ double kr_conf(int8_t c, int sign, bool bn, double epl, double eml)
-{
-    return (((c > 0) == (sign > 0)) != bn) ? epl : eml;
-}
 
 #ifdef KR_STAMPS  // diagnostic build only (tools/kr_stamps.py): per workgroup of the pending-chunk launch, cycle stamps of wave 0
                   // (inside kr_chain only of the chain that applies the chunk: the second chain of kron_wrap_kernel stamps nothing)
@@ -86,7 +76,7 @@ extern "C" int dqmc_debug_kr_stamps(void *devptr)
 #endif
 // X_0 (the column tiles v of this workgroup's 16 columns) += C R^ for the pending chunk (file header)
 template <bool PF>
-__device__ __forceinline__ void kr_apply_pending(const KronArgs &a, int unit, int c0, d4k (&v)[KR_NC], double *lds)
+__device__ __forceinline__ void kr_apply_pending(const KronArgs &a, int unit, int c0, d4 (&v)[KR_NC], double *lds)
 {
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 4, ci = lane & 15;
     const int site0 = a.pf_site0;
@@ -140,17 +130,17 @@ __device__ __forceinline__ void kr_apply_pending(const KronArgs &a, int unit, in
     // TIMING PROBE, WRONG VALUES (diagnostic build with KR_STAMPS only): what the solves would cost as two
     // block-triangular products on prebuilt inverse blocks, with image tiles standing in for the blocks nothing builds yet.
     // Wave w forms block row w of each product (independent accumulators), the intermediate and R^ go through LDS.
-    d4k rh[4];
+    d4 rh[4];
     {
         double *lw = lr + KR_COLS * KR_PF_RLD, *lh = lr;  // behind R0 (free up to KR_LDS_PF); over R0, dead after the first product
         static_assert(KR_PF_R0 + 2 * KR_COLS * KR_PF_RLD <= KR_LDS_PF, "probe LDS");
-        d4k pa[4];
+        d4 pa[4];
 #pragma unroll
         for (int J = 0; J < 4; ++J) {
-            pa[J] = (d4k){0.0, 0.0, 0.0, 0.0};
+            pa[J] = (d4){0.0, 0.0, 0.0, 0.0};
             if (J <= w)
 #pragma unroll
-                for (int q = 0; q < 4; ++q) pa[J] = KR_MFMA(A(TL + J, q), lr[ci * KR_PF_RLD + 16 * J + 4 * q + g], pa[J]);
+                for (int q = 0; q < 4; ++q) pa[J] = FK_MFMA(A(TL + J, q), lr[ci * KR_PF_RLD + 16 * J + 4 * q + g], pa[J]);
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r)
@@ -158,10 +148,10 @@ __device__ __forceinline__ void kr_apply_pending(const KronArgs &a, int unit, in
         __syncthreads();
 #pragma unroll
         for (int J = 0; J < 4; ++J) {
-            pa[J] = (d4k){0.0, 0.0, 0.0, 0.0};
+            pa[J] = (d4){0.0, 0.0, 0.0, 0.0};
             if (J >= w)
 #pragma unroll
-                for (int q = 0; q < 4; ++q) pa[J] = KR_MFMA(A(TU + J, q), lw[ci * KR_PF_RLD + 16 * J + 4 * q + g], pa[J]);
+                for (int q = 0; q < 4; ++q) pa[J] = FK_MFMA(A(TU + J, q), lw[ci * KR_PF_RLD + 16 * J + 4 * q + g], pa[J]);
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) lh[ci * KR_PF_RLD + 16 * w + 4 * r + g] = pa[0][r] + pa[1][r] + pa[2][r] + pa[3][r];
@@ -172,42 +162,42 @@ __device__ __forceinline__ void kr_apply_pending(const KronArgs &a, int unit, in
             for (int q = 0; q < 4; ++q) rh[J][q] = lh[ci * KR_PF_RLD + 16 * J + 4 * q + g];
     }
 #else
-    d4k xv[4], rh[4];
+    d4 xv[4], rh[4];
 #pragma unroll
     for (int J = 0; J < 4; ++J) {
-        d4k acc;
+        d4 acc;
 #pragma unroll
         for (int r = 0; r < 4; ++r) acc[r] = lr[ci * KR_PF_RLD + 16 * J + 4 * r + g];
 #pragma unroll
         for (int K = 0; K < J; ++K)
 #pragma unroll
-            for (int q = 0; q < 4; ++q) acc = KR_MFMA(A(TL + lu_pair(K, J), q), xv[K][q], acc);
-        d4k z = (d4k){0.0, 0.0, 0.0, 0.0};
+            for (int q = 0; q < 4; ++q) acc = FK_MFMA(A(TL + lu_pair(K, J), q), xv[K][q], acc);
+        d4 z = (d4){0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-        for (int q = 0; q < 4; ++q) z = KR_MFMA(A(TQ + J, q), acc[q], z);
+        for (int q = 0; q < 4; ++q) z = FK_MFMA(A(TQ + J, q), acc[q], z);
 #pragma unroll
         for (int r = 0; r < 4; ++r) xv[J][r] = z[r] * xr(J, r);
     }
 #pragma unroll
     for (int J = 3; J >= 0; --J) {
-        d4k acc = (d4k){0.0, 0.0, 0.0, 0.0};
+        d4 acc = (d4){0.0, 0.0, 0.0, 0.0};
 #pragma unroll
         for (int K = J + 1; K < 4; ++K)
 #pragma unroll
-            for (int q = 0; q < 4; ++q) acc = KR_MFMA(A(TU + lu_pair(J, K), q), rh[K][q], acc);
+            for (int q = 0; q < 4; ++q) acc = FK_MFMA(A(TU + lu_pair(J, K), q), rh[K][q], acc);
 #pragma unroll
         for (int r = 0; r < 4; ++r) acc[r] = xv[J][r] + xr(J, r) * acc[r];
-        d4k o = (d4k){0.0, 0.0, 0.0, 0.0};
+        d4 o = (d4){0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-        for (int q = 0; q < 4; ++q) o = KR_MFMA(A(TP + J, q), acc[q], o);
+        for (int q = 0; q < 4; ++q) o = FK_MFMA(A(TP + J, q), acc[q], o);
         rh[J] = o;
     }
 #endif
     KR_STAMP(3);
     // tile mm of D holds D[16 (4 w + mm) + 4 r + g][j = ci]
-    d4k dm[4];
+    d4 dm[4];
 #pragma unroll
-    for (int mm = 0; mm < 4; ++mm) dm[mm] = (d4k){0.0, 0.0, 0.0, 0.0};
+    for (int mm = 0; mm < 4; ++mm) dm[mm] = (d4){0.0, 0.0, 0.0, 0.0};
 #pragma unroll
     for (int J = 0; J < 4; ++J) {
         if (J < 3) fetch(J + 1, ca[(J + 1) & 1]);
@@ -218,7 +208,7 @@ __device__ __forceinline__ void kr_apply_pending(const KronArgs &a, int unit, in
             for (int mm = 0; mm < 4; ++mm) {
                 const int i = 16 * (4 * w + mm) + ci, s = 16 * J + 4 * q + g;
                 const double c = ca[J & 1][mm][q] - (i == site0 + s ? 1.0 : 0.0);
-                dm[mm] = KR_MFMA(c, rh[J][q], dm[mm]);
+                dm[mm] = FK_MFMA(c, rh[J][q], dm[mm]);
             }
         __builtin_amdgcn_sched_barrier(0);
     }
@@ -251,7 +241,7 @@ __device__ __forceinline__ void kr_chain(const KronArgs &a, const KronStep *step
     double *tile = lds + w * (KR_NC * 16 * KR_TLD);
 
     // X_0: column c0 + KR_NC w + t, parity (y, x): register r = entries ci + 16 (g + 4 r), 64 consecutive doubles
-    d4k v[KR_NC];
+    d4 v[KR_NC];
     {
         const double *x0 = x0u + (long)KR_N * (c0 + KR_NC * w) + ci + 16 * g;
 #pragma unroll
@@ -303,7 +293,7 @@ __device__ __forceinline__ void kr_chain(const KronArgs &a, const KronStep *step
         if (st.pre_conf) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const double f = kr_conf(cur.cpre[r], st.pre_sign, bn, a.epl, a.eml);
+                const double f = fk_conf(cur.cpre[r], st.pre_sign, bn, a.epl, a.eml);
 #pragma unroll
                 for (int t = 0; t < KR_NC; ++t) v[t][r] *= f;
             }
@@ -311,9 +301,9 @@ __device__ __forceinline__ void kr_chain(const KronArgs &a, const KronStep *step
         // P = Fa V  ->  tile[a][b]
 #pragma unroll
         for (int t = 0; t < KR_NC; ++t) {
-            d4k p = (d4k){0.0, 0.0, 0.0, 0.0};
+            d4 p = (d4){0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-            for (int q = 0; q < 4; ++q) p = KR_MFMA(cur.av[q], v[t][q], p);
+            for (int q = 0; q < 4; ++q) p = FK_MFMA(cur.av[q], v[t][q], p);
 #pragma unroll
             for (int r = 0; r < 4; ++r) tile[t * 16 * KR_TLD + (g + 4 * r) * KR_TLD + ci] = p[r];
         }
@@ -322,16 +312,16 @@ __device__ __forceinline__ void kr_chain(const KronArgs &a, const KronStep *step
         // Q = Fb P^T: B operand of k-block q is P[a = ci][b = 4 q + g]; the result has b in the registers, a on the lanes
 #pragma unroll
         for (int t = 0; t < KR_NC; ++t) {
-            d4k q4 = (d4k){0.0, 0.0, 0.0, 0.0};
+            d4 q4 = (d4){0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-            for (int q = 0; q < 4; ++q) q4 = KR_MFMA(cur.bv[q], tile[t * 16 * KR_TLD + ci * KR_TLD + 4 * q + g], q4);
+            for (int q = 0; q < 4; ++q) q4 = FK_MFMA(cur.bv[q], tile[t * 16 * KR_TLD + ci * KR_TLD + 4 * q + g], q4);
             v[t] = q4;
         }
         __syncthreads();  // (the next step's tile writes, or the staging image, reuse the LDS)
         if (st.post_conf) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const double f = kr_conf(cur.cpost[r], st.post_sign, bn, a.epl, a.eml);
+                const double f = fk_conf(cur.cpost[r], st.post_sign, bn, a.epl, a.eml);
 #pragma unroll
                 for (int t = 0; t < KR_NC; ++t) v[t][r] *= f;
             }
@@ -360,18 +350,8 @@ __device__ __forceinline__ void kr_chain(const KronArgs &a, const KronStep *step
             __builtin_amdgcn_raw_buffer_store_b128(*reinterpret_cast<const kr_u4 *>(lds + i * KR_SLD + cl), rs,
                                                    (c0 + KR_N * i + cl) * (int)sizeof(double), 0, 16 /* sc1 */);
         }
-    } else if (a.transpose_out) {  // out[c][i] = X[i][c]: row i of the image is 16 consecutive doubles at c0 + 256 i
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const int e = 2 * (tid + 256 * k), i = e >> 4, cl = e & 15;
-            *reinterpret_cast<double2 *>(o + c0 + (long)KR_N * i + cl) = *reinterpret_cast<const double2 *>(lds + i * KR_SLD + cl);
-        }
-    } else {  // columns c0 .. c0 + 15 are 4096 consecutive doubles
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const int e = 2 * (tid + 256 * k);
-            *reinterpret_cast<double2 *>(o + (long)KR_N * c0 + e) = *reinterpret_cast<const double2 *>(lds + e);
-        }
+    } else {
+        fk_store_image<KR_N, KR_COLS, KR_SLD, 0>(o, lds, a, c0, tid);
     }
 }
 
@@ -465,15 +445,7 @@ hipError_t launch_kron_wrap(const KronArgs &a, hipStream_t s, hipEvent_t start, 
     if (a.x_su < KR_N * KR_N || a.out_su < KR_N * KR_N) return hipErrorInvalidValue;
     if (a.pf_img && (a.pf_site0 < 0 || a.pf_site0 % 64 != 0 || a.pf_site0 + 64 > KR_N || a.pf_img_su < LU_STRIDE))
         return hipErrorInvalidValue;
-    const dim3 gridx(kron_wrap_grid(a.n_units)), block(256);
-    if (a.pf_img) {
-        if (start) hipExtLaunchKernelGGL(kron_wrap_kernel<true>, gridx, block, 0, s, start, stop, 0, a);
-        else hipLaunchKernelGGL(kron_wrap_kernel<true>, gridx, block, 0, s, a);
-    } else {
-        if (start) hipExtLaunchKernelGGL(kron_wrap_kernel<false>, gridx, block, 0, s, start, stop, 0, a);
-        else hipLaunchKernelGGL(kron_wrap_kernel<false>, gridx, block, 0, s, a);
-    }
-    return hipGetLastError();
+    return fk_launch(a.pf_img ? kron_wrap_kernel<true> : kron_wrap_kernel<false>, dim3(kron_wrap_grid(a.n_units)), a, s, start, stop);
 }
 
 hipError_t launch_kron_chain(const KronArgs &a, hipStream_t s, hipEvent_t start, hipEvent_t stop)
@@ -481,16 +453,9 @@ hipError_t launch_kron_chain(const KronArgs &a, hipStream_t s, hipEvent_t start,
     if (a.nsteps < 1 || a.nsteps > SLAB_MAX_STEPS || a.nb < 1 || a.nb > 2) return hipErrorInvalidValue;
     if (a.pf_img && (a.pf_site0 < 0 || a.pf_site0 % 64 != 0 || a.pf_site0 + 64 > KR_N || a.pf_img_su < LU_STRIDE))
         return hipErrorInvalidValue;
-    const dim3 grid(a.n_units * (KR_N / KR_COLS)), block(256);
-    if (a.pf_img) {
-        const dim3 gridx((a.n_units + 7) / 8 * 8 * (KR_N / KR_COLS));  // whole groups of eight units (XCD placement)
-        if (start) hipExtLaunchKernelGGL(kron_chain_kernel<true>, gridx, block, 0, s, start, stop, 0, a);
-        else hipLaunchKernelGGL(kron_chain_kernel<true>, gridx, block, 0, s, a);
-    } else {
-        if (start) hipExtLaunchKernelGGL(kron_chain_kernel<false>, grid, block, 0, s, start, stop, 0, a);
-        else hipLaunchKernelGGL(kron_chain_kernel<false>, grid, block, 0, s, a);
-    }
-    return hipGetLastError();
+    // the pending-chunk form: whole groups of eight units (XCD placement)
+    if (a.pf_img) return fk_launch(kron_chain_kernel<true>, dim3((a.n_units + 7) / 8 * 8 * (KR_N / KR_COLS)), a, s, start, stop);
+    return fk_launch(kron_chain_kernel<false>, dim3(a.n_units * (KR_N / KR_COLS)), a, s, start, stop);
 }
 
 }  // namespace dqmc

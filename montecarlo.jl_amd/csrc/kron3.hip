@@ -1,7 +1,7 @@
 // kron3.hip — slice-matrix chains and wraps with the hopping exponential applied in three-factor Kronecker form (n = 512).
 //
 // On the periodic 8 x 8 x 8 CubicLattice (site i = x + 8 y + 64 z) every hopping exponential is, up to rounding, a
-// Kronecker product A = Ez (x) Ey (x) Ex of three 8 x 8 matrices (engine.cpp: kron3_factor checks it at handle creation).
+// Kronecker product A = Ez (x) Ey (x) Ex of three 8 x 8 matrices (hopping_forms.h: kron_split checks it at handle creation).
 // The kernel groups it as A = Ez (x) Exy with Exy = Ey (x) Ex (64 x 64, multiplied out on the host).  A column v of 512
 // entries, read as the 64 x 8 matrix V[i][z] = v[i + 64 z] (i = x + 8 y), then gives (A v) = vec(Exy V Ez^T): a
 // 64-contraction and an 8-contraction, 40 v_mfma_f64_16x16x4_f64 per column instead of the 256 of the dense product
@@ -25,13 +25,9 @@
 // transpose and the state alternates: a step starts in Z when it is even (the first load reads 128 consecutive bytes per
 // 16 lanes) and in I when it is odd.  A workgroup (4 waves, 8 columns) owns its columns through all steps; the result is
 // staged in LDS and stored as whole lines, as is or transposed.
-#include "kernels.h"
-#include <hip/hip_ext.h>
+#include "factored_common.h"
 
 namespace dqmc {
-
-typedef double d4x __attribute__((ext_vector_type(4)));
-#define K3_MFMA(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 0)
 
 constexpr int K3_N = 512;
 constexpr int K3_WAVES = 4;
@@ -42,11 +38,6 @@ constexpr int K3_XY = 4096;                      // Exy operand image
 constexpr int K3_EZ = 256;                       // I2 (x) Ez operand image
 constexpr int K3_LDS = K3_XY + K3_WAVES * K3_T;  // 66 KB: two workgroups per CU
 static_assert(K3_LDS >= K3_COLS * K3_N, "the staging image of the result reuses the LDS");
-
-__device__ __forceinline__ double k3_conf(int8_t c, int sign, bool bn, double epl, double eml)
-{
-    return (((c > 0) == (sign > 0)) != bn) ? epl : eml;
-}
 
 __global__ __launch_bounds__(256) void kron3_chain_kernel(KronArgs a)
 {
@@ -65,7 +56,7 @@ __global__ __launch_bounds__(256) void kron3_chain_kernel(KronArgs a)
     auto hcol = [&](int st, int r) { return st ? ci >> 3 : r >> 1; };
 
     // X_0 in state Z: for one (m, r) the 64 lanes read 4 runs of 16 consecutive doubles
-    d4x v[4];
+    d4 v[4];
     {
         const double *x0 = a.X0 + (long)unit * a.x_su + (long)K3_N * cp;
 #pragma unroll
@@ -99,29 +90,29 @@ __global__ __launch_bounds__(256) void kron3_chain_kernel(KronArgs a)
 #pragma unroll
         for (int m = 0; m < 4; ++m)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) v[m][r] *= k3_conf(cb[4 * m + r], sign, bn, a.epl, a.eml);
+            for (int r = 0; r < 4; ++r) v[m][r] *= fk_conf(cb[4 * m + r], sign, bn, a.epl, a.eml);
     };
     // state Z -> Z: W <- (I2 (x) Ez) W, tile by tile
     auto contract_z = [&](const Ops &o) {
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
-            d4x q4 = (d4x){0.0, 0.0, 0.0, 0.0};
+            d4 q4 = (d4){0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-            for (int q = 0; q < 4; ++q) q4 = K3_MFMA(o.ez[q], v[m][q], q4);
+            for (int q = 0; q < 4; ++q) q4 = FK_MFMA(o.ez[q], v[m][q], q4);
             v[m] = q4;
         }
     };
     // state I -> I: W <- Exy W, k-step (m, r) is register r of tile m
     auto contract_i = [&]() {
-        d4x p[4];
+        d4 p[4];
 #pragma unroll
-        for (int mp = 0; mp < 4; ++mp) p[mp] = (d4x){0.0, 0.0, 0.0, 0.0};
+        for (int mp = 0; mp < 4; ++mp) p[mp] = (d4){0.0, 0.0, 0.0, 0.0};
 #pragma unroll
         for (int m = 0; m < 4; ++m)
 #pragma unroll
             for (int r = 0; r < 4; ++r)
 #pragma unroll
-                for (int mp = 0; mp < 4; ++mp) p[mp] = K3_MFMA(exy[((mp * 4 + m) * 4 + r) * 64 + lane], v[m][r], p[mp]);
+                for (int mp = 0; mp < 4; ++mp) p[mp] = FK_MFMA(exy[((mp * 4 + m) * 4 + r) * 64 + lane], v[m][r], p[mp]);
 #pragma unroll
         for (int m = 0; m < 4; ++m) v[m] = p[m];
     };
@@ -190,29 +181,13 @@ __global__ __launch_bounds__(256) void kron3_chain_kernel(KronArgs a)
             lds[a.transpose_out ? e * K3_COLS + cl : cl * K3_N + e] = val;
         }
     __syncthreads();
-    double *o = a.out + (long)unit * a.out_su;
-    if (a.transpose_out) {  // out[c][e] = X[e][c]: row e of the image is 8 consecutive doubles at c0 + 512 e
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const int e2 = 2 * (tid + 256 * k), e = e2 >> 3, cl = e2 & 7;
-            *reinterpret_cast<double2 *>(o + c0 + (long)K3_N * e + cl) = *reinterpret_cast<const double2 *>(lds + e2);
-        }
-    } else {  // columns c0 .. c0 + 7 are 4096 consecutive doubles
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const int e2 = 2 * (tid + 256 * k);
-            *reinterpret_cast<double2 *>(o + (long)K3_N * c0 + e2) = *reinterpret_cast<const double2 *>(lds + e2);
-        }
-    }
+    fk_store_image<K3_N, K3_COLS, K3_COLS, 0>(a.out + (long)unit * a.out_su, lds, a, c0, tid);
 }
 
 hipError_t launch_kron3_chain(const KronArgs &a, hipStream_t s, hipEvent_t start, hipEvent_t stop)
 {
     if (a.nsteps < 1 || a.nsteps > SLAB_MAX_STEPS || a.nb < 1 || a.nb > 2) return hipErrorInvalidValue;
-    const dim3 grid(a.n_units * (K3_N / K3_COLS)), block(256);
-    if (start) hipExtLaunchKernelGGL(kron3_chain_kernel, grid, block, 0, s, start, stop, 0, a);
-    else hipLaunchKernelGGL(kron3_chain_kernel, grid, block, 0, s, a);
-    return hipGetLastError();
+    return fk_launch(kron3_chain_kernel, dim3(a.n_units * (K3_N / K3_COLS)), a, s, start, stop);
 }
 
 }  // namespace dqmc

@@ -2,7 +2,7 @@
 // factored form (n = 256 = 32 x 8).
 //
 // On the periodic RectangularLattice(32, 8) (site i = x + 32 y) every hopping exponential is, up to rounding, a Kronecker
-// product A = Ey (x) Ex with Ex 32 x 32 and Ey 8 x 8 (engine.cpp: rect_factor checks it at handle creation).  A column v of
+// product A = Ey (x) Ex with Ex 32 x 32 and Ey 8 x 8 (hopping_forms.h: kron_split checks it at handle creation).  A column v of
 // 256 entries is a plane V[y][x] = v[x + 32 y], and A v = vec(Ey V Ex^T): one 8-contraction along y and one 32-contraction
 // along x instead of the dense 256-contraction.
 //
@@ -27,13 +27,9 @@
 // index (R's read, C's write) then put two lanes on every bank pair, the minimum for 64 eight-byte lanes; the other two
 // (R's write, C's read) put up to four.  A workgroup (4 waves, 8 columns) owns its columns through all steps; the result is
 // staged in LDS and stored as whole 64-byte runs, as is or transposed.
-#include "kernels.h"
-#include <hip/hip_ext.h>
+#include "factored_common.h"
 
 namespace dqmc {
-
-typedef double d4r __attribute__((ext_vector_type(4)));
-#define RC_MFMA(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 0)
 
 constexpr int RC_N = 256;
 constexpr int RC_LX = 32, RC_LY = 8;
@@ -47,11 +43,6 @@ constexpr int RC_LDS_S = RC_N * RC_SLD + (RC_N / 16) * RC_SPAD;
 constexpr int RC_LDS = RC_LDS_T > RC_LDS_S ? RC_LDS_T : RC_LDS_S;  // 20 736 bytes
 static_assert(RC_LDS >= RC_COLS * RC_N, "the untransposed staging image [column][entry] reuses the LDS");
 static_assert(RC_LX * RC_LY == RC_N && 2 * RC_LY == 16 && RC_LX == 32, "two columns of 8 rows fill a 16-row tile; x spans two tiles");
-
-__device__ __forceinline__ double rc_conf(int8_t c, int sign, bool bn, double epl, double eml)
-{
-    return (((c > 0) == (sign > 0)) != bn) ? epl : eml;
-}
 
 __global__ __launch_bounds__(256) void rect_chain_kernel(KronArgs a)
 {
@@ -73,7 +64,7 @@ __global__ __launch_bounds__(256) void rect_chain_kernel(KronArgs a)
     auto col = [&](int par, int r) { return par ? ci >> 3 : r >> 1; };
 
     // X_0 in layout R
-    d4r v[2];
+    d4 v[2];
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -126,15 +117,15 @@ __global__ __launch_bounds__(256) void rect_chain_kernel(KronArgs a)
 #pragma unroll
             for (int t = 0; t < 2; ++t)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) v[t][r] *= rc_conf(cur.cpre[t][r], st.pre_sign, bn, a.epl, a.eml);
+                for (int r = 0; r < 4; ++r) v[t][r] *= fk_conf(cur.cpre[t][r], st.pre_sign, bn, a.epl, a.eml);
         }
         if (!par) {
             // P = Dy Z  ->  tile[(h, y)][x]
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
-                d4r p = (d4r){0.0, 0.0, 0.0, 0.0};
+                d4 p = (d4){0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-                for (int q = 0; q < 4; ++q) p = RC_MFMA(cur.dy[q], v[t][q], p);
+                for (int q = 0; q < 4; ++q) p = FK_MFMA(cur.dy[q], v[t][q], p);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) tile[(g + 4 * r) * RC_TLD + 16 * t + ci] = p[r];
             }
@@ -142,9 +133,9 @@ __global__ __launch_bounds__(256) void rect_chain_kernel(KronArgs a)
             // P^T = Ex Z^T  ->  tile[(h, y)][x]: the B operand of k-block q = 4 t' + q' is register q' of tile t'
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
-                d4r p = (d4r){0.0, 0.0, 0.0, 0.0};
+                d4 p = (d4){0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-                for (int q = 0; q < 8; ++q) p = RC_MFMA(cur.ex[t][q], v[q >> 2][q & 3], p);
+                for (int q = 0; q < 8; ++q) p = FK_MFMA(cur.ex[t][q], v[q >> 2][q & 3], p);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) tile[ci * RC_TLD + 16 * t + g + 4 * r] = p[r];
             }
@@ -155,18 +146,18 @@ __global__ __launch_bounds__(256) void rect_chain_kernel(KronArgs a)
             // Q^T = Ex P^T: B operand of k-block q is P[(h, y) = ci][x = 4 q + g]  ->  layout C
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
-                d4r q4 = (d4r){0.0, 0.0, 0.0, 0.0};
+                d4 q4 = (d4){0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-                for (int q = 0; q < 8; ++q) q4 = RC_MFMA(cur.ex[t][q], tile[ci * RC_TLD + 4 * q + g], q4);
+                for (int q = 0; q < 8; ++q) q4 = FK_MFMA(cur.ex[t][q], tile[ci * RC_TLD + 4 * q + g], q4);
                 v[t] = q4;
             }
         } else {
             // Q = Dy P: B operand of k-block q is P[(h, y) = 4 q + g][x = 16 t + ci]  ->  layout R
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
-                d4r q4 = (d4r){0.0, 0.0, 0.0, 0.0};
+                d4 q4 = (d4){0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-                for (int q = 0; q < 4; ++q) q4 = RC_MFMA(cur.dy[q], tile[(4 * q + g) * RC_TLD + 16 * t + ci], q4);
+                for (int q = 0; q < 4; ++q) q4 = FK_MFMA(cur.dy[q], tile[(4 * q + g) * RC_TLD + 16 * t + ci], q4);
                 v[t] = q4;
             }
         }
@@ -175,7 +166,7 @@ __global__ __launch_bounds__(256) void rect_chain_kernel(KronArgs a)
 #pragma unroll
             for (int t = 0; t < 2; ++t)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) v[t][r] *= rc_conf(cur.cpost[t][r], st.post_sign, bn, a.epl, a.eml);
+                for (int r = 0; r < 4; ++r) v[t][r] *= fk_conf(cur.cpost[t][r], st.post_sign, bn, a.epl, a.eml);
         }
         cur = nxt;
     }
@@ -190,31 +181,14 @@ __global__ __launch_bounds__(256) void rect_chain_kernel(KronArgs a)
             lds[a.transpose_out ? e * RC_SLD + (e >> 4) * RC_SPAD + cl : cl * RC_N + e] = val;
         }
     __syncthreads();
-    double *o = a.out + (long)unit * a.out_su;
-    if (a.transpose_out) {  // out[c][e] = X[e][c]: row e of the image is 8 consecutive doubles at c0 + 256 e
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int e2 = 2 * (tid + 256 * k), e = e2 >> 3, cl = e2 & 7;
-            *reinterpret_cast<double2 *>(o + c0 + (long)RC_N * e + cl) =
-                *reinterpret_cast<const double2 *>(lds + e * RC_SLD + (e >> 4) * RC_SPAD + cl);
-        }
-    } else {  // columns c0 .. c0 + 7 are 2048 consecutive doubles
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int e2 = 2 * (tid + 256 * k);
-            *reinterpret_cast<double2 *>(o + (long)RC_N * c0 + e2) = *reinterpret_cast<const double2 *>(lds + e2);
-        }
-    }
+    fk_store_image<RC_N, RC_COLS, RC_SLD, RC_SPAD>(a.out + (long)unit * a.out_su, lds, a, c0, tid);
 }
 
 hipError_t launch_rect_chain(const KronArgs &a, hipStream_t s, hipEvent_t start, hipEvent_t stop)
 {
     if (a.nsteps < 1 || a.nsteps > SLAB_MAX_STEPS || a.nb < 1 || a.nb > 2 || a.n_units < 1) return hipErrorInvalidValue;
     if (a.x_su < (long)RC_N * RC_N || a.out_su < (long)RC_N * RC_N || a.pf_img) return hipErrorInvalidValue;
-    const dim3 grid(a.n_units * (RC_N / RC_COLS)), block(256);
-    if (start) hipExtLaunchKernelGGL(rect_chain_kernel, grid, block, 0, s, start, stop, 0, a);
-    else hipLaunchKernelGGL(rect_chain_kernel, grid, block, 0, s, a);
-    return hipGetLastError();
+    return fk_launch(rect_chain_kernel, dim3(a.n_units * (RC_N / RC_COLS)), a, s, start, stop);
 }
 
 }  // namespace dqmc

@@ -27,13 +27,9 @@
 // doubles.  The two passes use separate tile regions, so a step needs two barriers.  Columns are independent: a
 // workgroup (4 waves x TR_NC columns) owns 16 consecutive columns through all steps, and nothing crosses workgroups.  The
 // result is staged in LDS and stored as whole 128-byte lines, as is or transposed.
-#include "kernels.h"
-#include <hip/hip_ext.h>
+#include "factored_common.h"
 
 namespace dqmc {
-
-typedef double d4t __attribute__((ext_vector_type(4)));
-#define TR_MFMA(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 0)
 
 constexpr int TR_N = 256;
 constexpr int TR_NC = 4;                         // columns per wave
@@ -44,12 +40,6 @@ constexpr int TR_REGION = 4 * TR_NC * TR_TILE;   // the tiles of the four waves 
 constexpr int TR_SLD = 18;                       // row stride of the transposed staging image (doubles; even: 16-byte reads)
 constexpr int TR_LDS = 2 * TR_REGION;            // 69 632 bytes: two workgroups per CU
 static_assert(TR_LDS >= TR_N * TR_SLD && TR_LDS >= TR_COLS * TR_N, "the staging image of the result reuses the tiles");
-
-// exp(sign lambda conf[i]) of block blk (vs_conf() of engine.cpp, kr_conf() of kron.hip)
-__device__ __forceinline__ double tr_conf(int8_t c, int sign, bool bn, double epl, double eml)
-{
-    return (((c > 0) == (sign > 0)) != bn) ? epl : eml;
-}
 
 __global__ __launch_bounds__(256) void tri_chain_kernel(KronArgs a)
 {
@@ -63,7 +53,7 @@ __global__ __launch_bounds__(256) void tri_chain_kernel(KronArgs a)
     double *t1 = lds + w * (TR_NC * TR_TILE), *t2 = t1 + TR_REGION;
 
     // X_0: column c0 + TR_NC w + t in state A: register r = entries ci + 16 (g + 4 r), 64 consecutive doubles
-    d4t v[TR_NC];
+    d4 v[TR_NC];
     {
         const double *x0 = a.X0 + (long)a.x_su * unit + (long)TR_N * (c0 + TR_NC * w) + ci + 16 * g;
 #pragma unroll
@@ -103,9 +93,9 @@ __global__ __launch_bounds__(256) void tri_chain_kernel(KronArgs a)
     auto product_to = [&](const double (&fv)[4], double *tl) {
 #pragma unroll
         for (int t = 0; t < TR_NC; ++t) {
-            d4t p = (d4t){0.0, 0.0, 0.0, 0.0};
+            d4 p = (d4){0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-            for (int q = 0; q < 4; ++q) p = TR_MFMA(fv[q], v[t][q], p);
+            for (int q = 0; q < 4; ++q) p = FK_MFMA(fv[q], v[t][q], p);
 #pragma unroll
             for (int r = 0; r < 4; ++r) tl[t * TR_TILE + (g + 4 * r) * TR_TLD + ci] = p[r];
         }
@@ -125,7 +115,7 @@ __global__ __launch_bounds__(256) void tri_chain_kernel(KronArgs a)
         if (st.pre_conf) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const double f = tr_conf(cur.cpre[r], st.pre_sign, bn, a.epl, a.eml);
+                const double f = fk_conf(cur.cpre[r], st.pre_sign, bn, a.epl, a.eml);
 #pragma unroll
                 for (int t = 0; t < TR_NC; ++t) v[t][r] *= f;
             }
@@ -156,15 +146,15 @@ __global__ __launch_bounds__(256) void tri_chain_kernel(KronArgs a)
         // Fx (state B) or Fy (state A), in registers
 #pragma unroll
         for (int t = 0; t < TR_NC; ++t) {
-            d4t q4 = (d4t){0.0, 0.0, 0.0, 0.0};
+            d4 q4 = (d4){0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-            for (int q = 0; q < 4; ++q) q4 = TR_MFMA(cur.f3[q], v[t][q], q4);
+            for (int q = 0; q < 4; ++q) q4 = FK_MFMA(cur.f3[q], v[t][q], q4);
             v[t] = q4;
         }
         if (st.post_conf) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const double f = tr_conf(cur.cpost[r], st.post_sign, bn, a.epl, a.eml);
+                const double f = fk_conf(cur.cpost[r], st.post_sign, bn, a.epl, a.eml);
 #pragma unroll
                 for (int t = 0; t < TR_NC; ++t) v[t][r] *= f;
             }
@@ -184,29 +174,13 @@ __global__ __launch_bounds__(256) void tri_chain_kernel(KronArgs a)
         }
     }
     __syncthreads();
-    double *o = a.out + (long)unit * a.out_su;
-    if (a.transpose_out) {  // out[c][i] = X[i][c]: row i of the image is 16 consecutive doubles at c0 + 256 i
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const int e = 2 * (tid + 256 * k), i = e >> 4, cl = e & 15;
-            *reinterpret_cast<double2 *>(o + c0 + (long)TR_N * i + cl) = *reinterpret_cast<const double2 *>(lds + i * TR_SLD + cl);
-        }
-    } else {  // columns c0 .. c0 + 15 are 4096 consecutive doubles
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const int e = 2 * (tid + 256 * k);
-            *reinterpret_cast<double2 *>(o + (long)TR_N * c0 + e) = *reinterpret_cast<const double2 *>(lds + e);
-        }
-    }
+    fk_store_image<TR_N, TR_COLS, TR_SLD, 0>(a.out + (long)unit * a.out_su, lds, a, c0, tid);
 }
 
 hipError_t launch_tri_chain(const KronArgs &a, hipStream_t s, hipEvent_t start, hipEvent_t stop)
 {
     if (a.nsteps < 1 || a.nsteps > SLAB_MAX_STEPS || a.nb < 1 || a.nb > 2 || a.pf_img) return hipErrorInvalidValue;
-    const dim3 grid(a.n_units * (TR_N / TR_COLS)), block(256);
-    if (start) hipExtLaunchKernelGGL(tri_chain_kernel, grid, block, 0, s, start, stop, 0, a);
-    else hipLaunchKernelGGL(tri_chain_kernel, grid, block, 0, s, a);
-    return hipGetLastError();
+    return fk_launch(tri_chain_kernel, dim3(a.n_units * (TR_N / TR_COLS)), a, s, start, stop);
 }
 
 }  // namespace dqmc

@@ -30,13 +30,9 @@
 // second pass's barrier.  Columns are independent: a workgroup (4 waves x TP_NC columns) owns 16 consecutive columns
 // through all steps, and nothing crosses workgroups.  The result is staged in LDS and stored as whole 128-byte lines, as
 // is or transposed.
-#include "kernels.h"
-#include <hip/hip_ext.h>
+#include "factored_common.h"
 
 namespace dqmc {
-
-typedef double d4t __attribute__((ext_vector_type(4)));
-#define TP_MFMA(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 0)
 
 constexpr int TP_N = 256;
 constexpr int TP_NC = 4;                         // columns per wave
@@ -47,12 +43,6 @@ constexpr int TP_REGION = 4 * TP_NC * TP_TILE;   // the tiles of the four waves 
 constexpr int TP_SLD = 18;                       // row stride of the transposed staging image (doubles; even: 16-byte reads)
 constexpr int TP_LDS = 2 * TP_REGION;            // 69 632 bytes: two workgroups per CU
 static_assert(TP_LDS >= TP_N * TP_SLD && TP_LDS >= TP_COLS * TP_N, "the staging image of the result reuses the tiles");
-
-// exp(sign lambda conf[i]) of block blk (vs_conf() of engine.cpp, kr_conf() of kron.hip, tr_conf() of tri.hip)
-__device__ __forceinline__ double tp_conf(int8_t c, int sign, bool bn, double epl, double eml)
-{
-    return (((c > 0) == (sign > 0)) != bn) ? epl : eml;
-}
 
 __global__ __launch_bounds__(256) void ttp_chain_kernel(KronArgs a)
 {
@@ -66,7 +56,7 @@ __global__ __launch_bounds__(256) void ttp_chain_kernel(KronArgs a)
     double *t1 = lds + w * (TP_NC * TP_TILE), *t2 = t1 + TP_REGION;
 
     // X_0: column c0 + TP_NC w + t in state A: register r = entries ci + 16 (g + 4 r), 64 consecutive doubles
-    d4t v[TP_NC];
+    d4 v[TP_NC];
     {
         const double *x0 = a.X0 + (long)a.x_su * unit + (long)TP_N * (c0 + TP_NC * w) + ci + 16 * g;
 #pragma unroll
@@ -108,9 +98,9 @@ __global__ __launch_bounds__(256) void ttp_chain_kernel(KronArgs a)
     auto product_to = [&](const double (&fv)[4], double *tl) {
 #pragma unroll
         for (int t = 0; t < TP_NC; ++t) {
-            d4t p = (d4t){0.0, 0.0, 0.0, 0.0};
+            d4 p = (d4){0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-            for (int q = 0; q < 4; ++q) p = TP_MFMA(fv[q], v[t][q], p);
+            for (int q = 0; q < 4; ++q) p = FK_MFMA(fv[q], v[t][q], p);
 #pragma unroll
             for (int r = 0; r < 4; ++r) tl[t * TP_TILE + (g + 4 * r) * TP_TLD + ci] = p[r];
         }
@@ -130,7 +120,7 @@ __global__ __launch_bounds__(256) void ttp_chain_kernel(KronArgs a)
         if (st.pre_conf) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const double f = tp_conf(cur.cpre[r], st.pre_sign, bn, a.epl, a.eml);
+                const double f = fk_conf(cur.cpre[r], st.pre_sign, bn, a.epl, a.eml);
 #pragma unroll
                 for (int t = 0; t < TP_NC; ++t) v[t][r] *= f;
             }
@@ -172,15 +162,15 @@ __global__ __launch_bounds__(256) void ttp_chain_kernel(KronArgs a)
         // Fx (state B) or Fy (state A), in registers
 #pragma unroll
         for (int t = 0; t < TP_NC; ++t) {
-            d4t q4 = (d4t){0.0, 0.0, 0.0, 0.0};
+            d4 q4 = (d4){0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-            for (int q = 0; q < 4; ++q) q4 = TP_MFMA(cur.f4[q], v[t][q], q4);
+            for (int q = 0; q < 4; ++q) q4 = FK_MFMA(cur.f4[q], v[t][q], q4);
             v[t] = q4;
         }
         if (st.post_conf) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const double f = tp_conf(cur.cpost[r], st.post_sign, bn, a.epl, a.eml);
+                const double f = fk_conf(cur.cpost[r], st.post_sign, bn, a.epl, a.eml);
 #pragma unroll
                 for (int t = 0; t < TP_NC; ++t) v[t][r] *= f;
             }
@@ -201,29 +191,13 @@ __global__ __launch_bounds__(256) void ttp_chain_kernel(KronArgs a)
         }
     }
     __syncthreads();
-    double *o = a.out + (long)unit * a.out_su;
-    if (a.transpose_out) {  // out[c][i] = X[i][c]: row i of the image is 16 consecutive doubles at c0 + 256 i
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const int e = 2 * (tid + 256 * k), i = e >> 4, cl = e & 15;
-            *reinterpret_cast<double2 *>(o + c0 + (long)TP_N * i + cl) = *reinterpret_cast<const double2 *>(lds + i * TP_SLD + cl);
-        }
-    } else {  // columns c0 .. c0 + 15 are 4096 consecutive doubles
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const int e = 2 * (tid + 256 * k);
-            *reinterpret_cast<double2 *>(o + (long)TP_N * c0 + e) = *reinterpret_cast<const double2 *>(lds + e);
-        }
-    }
+    fk_store_image<TP_N, TP_COLS, TP_SLD, 0>(a.out + (long)unit * a.out_su, lds, a, c0, tid);
 }
 
 hipError_t launch_ttp_chain(const KronArgs &a, hipStream_t s, hipEvent_t start, hipEvent_t stop)
 {
     if (a.nsteps < 1 || a.nsteps > SLAB_MAX_STEPS || a.nb < 1 || a.nb > 2 || a.pf_img) return hipErrorInvalidValue;
-    const dim3 grid(a.n_units * (TP_N / TP_COLS)), block(256);
-    if (start) hipExtLaunchKernelGGL(ttp_chain_kernel, grid, block, 0, s, start, stop, 0, a);
-    else hipLaunchKernelGGL(ttp_chain_kernel, grid, block, 0, s, a);
-    return hipGetLastError();
+    return fk_launch(ttp_chain_kernel, dim3(a.n_units * (TP_N / TP_COLS)), a, s, start, stop);
 }
 
 }  // namespace dqmc

@@ -1,7 +1,7 @@
 """BilayerSquareLattice(L) on the host: the tables against a brute-force construction from coordinates, the direction
 folding on the torus Z_L x Z_L x Z_2, the quad iterators, the momentum grid with q_z = 0 / pi, the models' t_perp, the
 pair channels, and the factored form Ez (x) Ey (x) Ex of the hopping exponentials at 16 x 16 x 2 that bilayer.hip applies
-(the gate is bilayer_factor in engine.cpp, restated here in numpy, and the kernel's step order, restated lane by lane: no
+(the gate is kron_split in hopping_forms.h, restated here in numpy, and the kernel's step order, restated lane by lane: no
 GPU is needed)."""
 import itertools
 

@@ -1,5 +1,5 @@
 """The three-factor Kronecker form of the hopping exponentials that the n = 512 slice products use (kron3.hip; the gate is
-kron3_factor in engine.cpp, restated here in numpy, so no GPU is needed).  On the periodic 8 x 8 x 8 cubic lattice
+kron_split in hopping_forms.h (kron3_factor before the form table), restated here in numpy, so no GPU is needed).  On the periodic 8 x 8 x 8 cubic lattice
 (site x + 8 y + 64 z) T is a Kronecker sum, so eT2 and eTinv2 are Ez (x) Ey (x) Ex up to rounding."""
 import numpy as np
 import pytest

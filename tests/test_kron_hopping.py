@@ -1,5 +1,5 @@
 """The Kronecker form of the hopping exponentials that the n = 256 slice products use (kron.hip; the gate is
-kron_factor in engine.cpp, restated here in numpy, so no GPU is needed).  On the periodic 16 x 16 square lattice
+kron_split in hopping_forms.h (kron_factor before the form table), restated here in numpy, so no GPU is needed).  On the periodic 16 x 16 square lattice
 (site x + 16 y) T is a Kronecker sum, so eT2 and eTinv2 are Ey (x) Ex up to rounding."""
 import numpy as np
 import pytest

@@ -1,7 +1,7 @@
 """RectangularLattice(Lx, Ly) on the host: the tables against a construction from coordinates and against SquareLattice(L)
 at Lx = Ly = L, the hopping matrix as a Kronecker sum (with mu and t'), the iterators, the momentum grid, the pair channels,
-the errors, and the factored form Ey (x) Ex of unequal factors at 32 x 8 that rect.hip applies (the gate is rect_factor in
-engine.cpp, restated here in numpy, and the kernel's two step forms and staging addresses, restated lane by lane: no GPU is
+the errors, and the factored form Ey (x) Ex of unequal factors at 32 x 8 that rect.hip applies (the gate is kron_split in
+hopping_forms.h, restated here in numpy, and the kernel's two step forms and staging addresses, restated lane by lane: no GPU is
 needed)."""
 import itertools
 

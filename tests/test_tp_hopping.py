@@ -1,6 +1,6 @@
 """Next-nearest-neighbour hopping t' on the square lattice, host side: the hopping matrix, the lattices and decompositions
 that refuse it, the four-factor form of the 16 x 16 lattice's hopping exponentials that the n = 256 slice products use
-(ttp.hip) with the residual the engine's gate (ttp_factor_ok in engine.cpp, restated here in numpy) bounds, a
+(ttp.hip) with the residual the engine's gate (ttp_factor_ok in hopping_forms.h, restated here in numpy) bounds, a
 register-level replay of the kernel's step order, the checkpoint's model entry and the helpers that refuse tp != 0.
 No GPU is needed."""
 import os
@@ -288,13 +288,13 @@ def test_each_pass_lands_in_its_state():
 
 
 def conf_scale(c, sign, bn, epl, eml):
-    """tp_conf() of ttp.hip"""
+    """fk_conf() of factored_common.h"""
     return np.where(((c > 0) == (sign > 0)) != bn, epl, eml)
 
 
 def chain(X0, nb, blk, ax, ay, steps, conf, epl, eml):
     """the kernel's step loop on one column of block blk: the operands of step s from the buffers ax / ay as request()
-    indexes them (block b at + 256 b, Fd at ay + 256 (nb + b), Fa at ay + 256 (2 nb + b)), the scalings as tp_conf()"""
+    indexes them (block b at + 256 b, Fd at ay + 256 (nb + b), Fa at ay + 256 (2 nb + b)), the scalings as fk_conf()"""
     mat = lambda buf, off: buf[off:off + 256].reshape(16, 16, order="F")
     v = load(X0)
     for s, (pre, post) in enumerate(steps):

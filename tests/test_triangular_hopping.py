@@ -1,5 +1,5 @@
 """The three-factor form of the triangular 16 x 16 lattice's hopping exponentials that the n = 256 slice products use
-(tri.hip): the factors triangular_factors() builds, the residual the engine's gate (tri_factor_ok in engine.cpp, restated
+(tri.hip): the factors triangular_factors() builds, the residual the engine's gate (tri_factor_ok in hopping_forms.h, restated
 here in numpy) bounds, and a register-level replay of the kernel's step order.  No GPU is needed."""
 import numpy as np
 import pytest
