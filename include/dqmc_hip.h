@@ -1255,6 +1255,124 @@ typedef struct {
 /* level < 0: the reliable level (the last one with count >= 32, else 0) */
 int dqmc_mc_fss_binner_finish(dqmc_mc_handle *h, int32_t walker, int32_t level, dqmc_mc_fss_binned *out);
 
+/* ---- the classical MC flavor with q-state models: Potts and clock ------------------------------------------------
+ * The reference's MC flavor is a plugin surface (energy, propose_local, accept_local!) with the IsingModel as its one
+ * model; the q-state models, their update and their order parameter are a defined extension, and this comment is the
+ * definition (tests/qstate_ref.py restates it).  A handle family of its own (csrc/qstate.hip): nothing of dqmc_mc_*
+ * takes part.  fl(.) is one IEEE fp64 rounding; the object file is compiled with -ffp-contract=off, so no product is
+ * fused into a sum.
+ *
+ * Model.  Site variable s_i in {0 .. q - 1}, 2 <= q <= 64, and a pair-energy table e[d] over d = (s_i - s_j) mod q with
+ * e[d] = e[(q - d) mod q]: E = -J sum_bonds e[(s_i - s_j) mod q] over the undirected bonds table.  Potts: e[d] = delta_{d,0};
+ * clock: e[d] = cos(2 pi d / q).  The host passes three fixed-point tables, e_q30[d] = llround(J e[d] 2^30) (int64,
+ * |e_q30| <= 2^32, symmetric), c_q30[s] = llround(cos(2 pi s / q) 2^30) and s_q30[s] = llround(sin(2 pi s / q) 2^30)
+ * (int32, magnitude <= 2^30).  A walker's energy is the exact int64 E_int = -sum_bonds e_q30[d] (|E_int| <= 2^16 2^32)
+ * and its order parameter the exact int64 pair (Mx, My) = sum_i (c_q30[s_i], s_q30[s_i]) (magnitude <= 2^44); integer
+ * sums are exact in any order, so the device's reductions and a numpy int64 sum agree.  For q = 2, My = 0.
+ *
+ * Uniforms.  P(key; c0, c1, c2, c3) is Philox4x32-10 with key = the walker's seed; its output words (o0, o1, o2, o3) give
+ * two uniforms by the conversion of philox4_uniform (csrc/kernels.h): u1 = (((o0 >> 5) << 26) | (o1 >> 6)) 2^-53 and
+ * u2 = (((o2 >> 5) << 26) | (o3 >> 6)) 2^-53.  Domain word c2 = 4: the sweep, P(key; i, low32(s), 4, high32(s)) for site
+ * i (0-based) in the walker's sweep s, the number of sweeps the walker has run since dqmc_qs_seed.  Domain word c2 = 5:
+ * the initial configuration, P(key; i, low32(r), 5, high32(r)), r = the dqmc_qs_rand_conf calls the walker has had since
+ * dqmc_qs_seed; site i takes min(q - 1, (int)fl(u1 q)), u2 is not used.  (Words 0..3 are the Ising flavor's domains.)
+ *
+ * Sweep.  One workgroup per walker; the sites as bytes and the walker's weight table in LDS.  A colouring gives every
+ * site a colour in [0, C), C <= 16, such that no site shares its colour with any entry of its neighs column (a repeated
+ * neighbour is fine and counts twice, as on SquareLattice(2); a site that lists itself cannot be coloured).  A sweep
+ * visits the colours 0 .. C - 1 in order; within a colour every site is decided from the configuration as it stood
+ * when the colour began.  For site i with state s, one call P gives (u1, u2):
+ *   proposal    t = (s + 1 + min(q - 2, (int)fl(u1 (q - 1)))) mod q: uniform over the other states, the flip for q = 2
+ *   for k = 0 .. z - 1, j = neighs[k, i]: a_k = (s - s_j) mod q, b_k = (t - s_j) mod q
+ *   dE_int      = sum_k (e_q30[a_k] - e_q30[b_k]) in int64: exactly the change of E_int
+ *   p           = 1.0, then p = fl(p w[a_k][b_k]) for k = 0 .. z - 1 in order, with the walker's table
+ *                 w[a][b] = exp(fl(-beta fl((double)(e_q30[a] - e_q30[b]) 2^-30))), q^2 doubles from the host's libm
+ *                 (dqmc_qs_set_beta); no exp on the device, only exactly rounded products
+ *   accept iff  dE_int <= 0 || u2 < p
+ * Both uniforms are formed for every site, whatever it decides: the sweep cursor alone positions the stream.  The sites
+ * of a colour share no bond, so the outcome is one configuration whatever order the device takes them in and dE_int is
+ * additive within a colour: a host restatement reproduces every sweep bit for bit.  prop_local += n_sites per sweep,
+ * acc_local counts the accepted sites.  The proposal is symmetric and each single-site kernel accepts with
+ * min(1, p(s -> t)); p(s -> t) p(t -> s) = 1 and p = exp(-beta dE) hold up to the rounding of z factors and z - 1
+ * products, about z ulp of p (|p exp(beta dE) - 1| <= (2 z - 1) 2^-53 to first order, plus libm's error per factor):
+ * that relative error of the acceptance probability is the size of the deviation from exact detailed balance.  A
+ * colour pass is a product of commuting single-site Metropolis kernels, so the sweep leaves the Boltzmann weight of
+ * E_int 2^-30 invariant to that accuracy.
+ *
+ * Measurement.  After the sweep with global index i (first_sweep_index, first_sweep_index + 1, ..) iff
+ * i > thermalization && i % measure_rate == 0 (the rule of dqmc_mc_sweep), inside the kernel, in this order of operations:
+ *   e = (double)E_int 2^-30, x = (double)Mx 2^-30, y = (double)My 2^-30 (exact: conversions below 2^53, powers of two)
+ *   m2 = fl(fl(x x) + fl(y y))
+ *   sum_E += e, sum_E2 += fl(e e), sum_M2 += m2, sum_M4 += fl(m2 m2), sum_absM += sqrt(m2), n_meas += 1
+ * each sum one rounding per measurement, in the order of the measurements.  numpy reproduces all of them bit for bit
+ * except sum_absM where the device's fp64 sqrt is not the correctly rounded one: that sum is compared at 1e-13 relative.
+ * While fewer than series_capacity measurements are recorded, (E_int, Mx, My) is appended to the walker's series.
+ * U4 = 1 - <M^4> / (2 <M^2>^2) is the Binder cumulant of a two-component order parameter (0 in the disordered phase).
+ * The results do not depend on how a run is split into calls of dqmc_qs_sweep.
+ * Limits: n_sites <= 16384, 1 <= z <= 8, 2 <= q <= 64, n_colours <= 16.  Errors come from dqmc_qs_last_error. */
+typedef struct dqmc_qs_handle dqmc_qs_handle;
+
+typedef struct {
+    int32_t n_sites;         /* length(lattice) */
+    int32_t z;               /* neighbours per site: size(l.neighs, 1) */
+    int32_t q;               /* states per site */
+    int32_t n_walkers;       /* independent chains batched on this device */
+    int32_t device_id;
+    int32_t n_bonds;         /* size(l.bonds, 1) */
+    int32_t series_capacity; /* per-walker measurements recorded as a series (0 = none) */
+    int32_t n_colours;       /* C */
+    const int64_t *neighs;   /* l.neighs: z x n_sites, column-major, 1-based */
+    const int64_t *bonds;    /* l.bonds[:, 1:2]: n_bonds x 2, column-major, 1-based */
+    const int64_t *e_q30;    /* [q] */
+    const int32_t *c_q30;    /* [q] */
+    const int32_t *s_q30;    /* [q] */
+    const int32_t *colour;   /* [n_sites], each in [0, n_colours) */
+} dqmc_qs_params;
+
+typedef struct {
+    int64_t energy_q30, mx_q30, my_q30;  /* E_int, Mx, My of the configuration now in the slot */
+    double sum_E, sum_E2, sum_absM, sum_M2, sum_M4;
+    int64_t n_meas;                      /* measurements summed since the last dqmc_qs_reset_accumulators */
+    int64_t prop_local, acc_local;
+    uint64_t sweeps_drawn, confs_drawn;  /* the cursors s and r */
+    int64_t n_series;                    /* measurements recorded in the series, <= series_capacity */
+    int32_t n_colours;
+} dqmc_qs_stats;
+
+/* Everything is validated on the host before the device is touched; DQMC_ERR_INVALID names the offender: q outside
+ * 2..64, n_sites above 16384, z outside 1..8, an index out of range, e_q30[d] != e_q30[(q - d) mod q] or an entry above
+ * 2^32 in magnitude, a c_q30 / s_q30 entry above 2^30 in magnitude, and the colouring as dqmc_qs_set_colouring.  Then
+ * the device (none: DQMC_ERR_NO_DEVICE).  Every walker starts with seed 0, beta 0 (w = 1) and all sites in state 0. */
+int dqmc_qs_create(const dqmc_qs_params *p, dqmc_qs_handle **out);
+int dqmc_qs_destroy(dqmc_qs_handle *h);
+/* message of the last failing call on this handle (h may be NULL: create errors) */
+const char *dqmc_qs_last_error(const dqmc_qs_handle *h);
+/* the walker's stream: key = seed, both cursors at 0 (the configuration stays) */
+int dqmc_qs_seed(dqmc_qs_handle *h, int32_t walker, uint64_t seed);
+/* beta finite and >= 0: builds the walker's table w on the host */
+int dqmc_qs_set_beta(dqmc_qs_handle *h, int32_t walker, double beta);
+/* the initial configuration at the walker's cursor r (walker < 0: every walker), then E_int, Mx, My from scratch */
+int dqmc_qs_rand_conf(dqmc_qs_handle *h, int32_t walker);
+/* the states in site order, each < q (else DQMC_ERR_INVALID, nothing changed); set_conf recomputes E_int, Mx and My and
+ * leaves the cursors alone */
+int dqmc_qs_set_conf(dqmc_qs_handle *h, int32_t walker, const uint8_t *conf);
+int dqmc_qs_get_conf(dqmc_qs_handle *h, int32_t walker, uint8_t *conf);
+/* another colouring from now on (copied): colour[i] in [0, n_colours), 1 <= n_colours <= 16.  Validated on the host
+ * before the device is touched: DQMC_ERR_INVALID names the offending site or pair of sites, and the handle stays as it
+ * was.  Between sweeps at any time; configurations, sums and cursors stay. */
+int dqmc_qs_set_colouring(dqmc_qs_handle *h, const int32_t *colour, int32_t n_colours);
+/* n_sweeps sweeps of every walker with the measurement rule above.  Split into launches of bounded work; complete on
+ * return. */
+int dqmc_qs_sweep(dqmc_qs_handle *h, int32_t n_sweeps, int64_t first_sweep_index, int64_t thermalization,
+                  int32_t measure_rate);
+int dqmc_qs_get_stats(dqmc_qs_handle *h, int32_t walker, dqmc_qs_stats *out);
+/* the recorded (E_int, Mx, My), n_series entries each; any buffer may be NULL */
+int dqmc_qs_get_series(dqmc_qs_handle *h, int32_t walker, int64_t *energy_q30, int64_t *mx_q30, int64_t *my_q30,
+                       int64_t *n_recorded);
+/* clear the measurement sums and series of every walker (prop_local, acc_local and the cursors stay) */
+int dqmc_qs_reset_accumulators(dqmc_qs_handle *h);
+int dqmc_qs_synchronize(dqmc_qs_handle *h);
+
 /* ---- the SAC flavor: stochastic analytic continuation -----------------------------------------------------------
  * A(omega) from imaginary-time data by sampling (Sandvik, PRB 57, 10287; Beach, cond-mat/0403055; Shao and Sandvik,
  * Phys. Rep. 1003), batched over P independent problems (momenta) and R sampling temperatures each (csrc/sac.hip).

@@ -23,6 +23,8 @@ from .dqmc import (DQMC, DQMCParameters, CurrentTauSums, matsubara_trapezoid, ca
                    udt_AVX_pivot, vmul)
 
 from .mc import MC, IsingModel, IsingTc, greedy_colouring, reciprocal_vectors  # noqa: F401
+from . import qstate  # noqa: F401
+from .qstate import ClockModel, PottsModel, QStateMC, QStateModel, qstate_tables  # noqa: F401
 from . import sac  # noqa: F401
 from .sac import SAC, boson_symmetric_kernel, fermion_kernel  # noqa: F401
 

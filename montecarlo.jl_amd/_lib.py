@@ -104,6 +104,22 @@ class McFssBinned(C.Structure):
                 ("n_k", C.c_int32)]
 
 
+class QsParams(C.Structure):
+    _fields_ = [("n_sites", C.c_int32), ("z", C.c_int32), ("q", C.c_int32), ("n_walkers", C.c_int32),
+                ("device_id", C.c_int32), ("n_bonds", C.c_int32), ("series_capacity", C.c_int32),
+                ("n_colours", C.c_int32), ("neighs", C.POINTER(C.c_int64)), ("bonds", C.POINTER(C.c_int64)),
+                ("e_q30", C.POINTER(C.c_int64)), ("c_q30", C.POINTER(C.c_int32)), ("s_q30", C.POINTER(C.c_int32)),
+                ("colour", C.POINTER(C.c_int32))]
+
+
+class QsStats(C.Structure):
+    _fields_ = [("energy_q30", C.c_int64), ("mx_q30", C.c_int64), ("my_q30", C.c_int64), ("sum_E", C.c_double),
+                ("sum_E2", C.c_double), ("sum_absM", C.c_double), ("sum_M2", C.c_double), ("sum_M4", C.c_double),
+                ("n_meas", C.c_int64), ("prop_local", C.c_int64), ("acc_local", C.c_int64),
+                ("sweeps_drawn", C.c_uint64), ("confs_drawn", C.c_uint64), ("n_series", C.c_int64),
+                ("n_colours", C.c_int32)]
+
+
 class SacParams(C.Structure):
     _fields_ = [("n_problems", C.c_int32), ("n_tau", C.c_int32), ("n_deltas", C.c_int32), ("n_omega", C.c_int32),
                 ("n_replicas", C.c_int32), ("device_id", C.c_int32), ("window", C.c_int32),
@@ -298,6 +314,20 @@ SIGNATURES = {
     "dqmc_mc_get_fss": (C.c_int, [_H, C.c_int32, C.POINTER(McFss)]),
     "dqmc_mc_fss_binner_get_level": (C.c_int, [_H, C.c_int32, C.c_int32, _dp, _dp, _dp, _i64p]),
     "dqmc_mc_fss_binner_finish": (C.c_int, [_H, C.c_int32, C.c_int32, C.POINTER(McFssBinned)]),
+    "dqmc_qs_create": (C.c_int, [C.POINTER(QsParams), C.POINTER(_H)]),
+    "dqmc_qs_destroy": (C.c_int, [_H]),
+    "dqmc_qs_last_error": (C.c_char_p, [_H]),
+    "dqmc_qs_seed": (C.c_int, [_H, C.c_int32, C.c_uint64]),
+    "dqmc_qs_set_beta": (C.c_int, [_H, C.c_int32, C.c_double]),
+    "dqmc_qs_rand_conf": (C.c_int, [_H, C.c_int32]),
+    "dqmc_qs_set_conf": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_uint8)]),
+    "dqmc_qs_get_conf": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_uint8)]),
+    "dqmc_qs_set_colouring": (C.c_int, [_H, C.POINTER(C.c_int32), C.c_int32]),
+    "dqmc_qs_sweep": (C.c_int, [_H, C.c_int32, C.c_int64, C.c_int64, C.c_int32]),
+    "dqmc_qs_get_stats": (C.c_int, [_H, C.c_int32, C.POINTER(QsStats)]),
+    "dqmc_qs_get_series": (C.c_int, [_H, C.c_int32, _i64p, _i64p, _i64p, _i64p]),
+    "dqmc_qs_reset_accumulators": (C.c_int, [_H]),
+    "dqmc_qs_synchronize": (C.c_int, [_H]),
     "dqmc_sac_create": (C.c_int, [C.POINTER(SacParams), C.POINTER(_H)]),
     "dqmc_sac_destroy": (C.c_int, [_H]),
     "dqmc_sac_last_error": (C.c_char_p, [_H]),

@@ -1,0 +1,736 @@
+// qstate.hip - the classical MC flavor with q-state models (Potts, clock) behind dqmc_qs_* (include/dqmc_hip.h, "the
+// classical MC flavor with q-state models": that comment is the definition, this file follows it).  A handle family of its
+// own; nothing here is shared with ising.hip but the Philox rounds of kernels.h.
+//
+// One workgroup sweeps one walker, colour class by colour class, as the Ising checkerboard path does (ising_cb.inl).  The
+// walker's sites are bytes in LDS, its weight table w[q][q] (fp64), e_q30 and the (cos, sin) pairs lie beside them:
+// 8 q^2 + 16 q + 32 + N bytes, 50 KiB at q = 64 and N = 16384, about 1 KiB for a 32 x 32 three-state Potts model.  The host
+// passes the sites sorted by colour and their padded neighbour rows in that order, read-only and shared by all walkers.
+// The sites of a class share no bond: a lane's byte store touches no byte another lane of the class reads.  One barrier
+// ends a class.
+//
+// dE_int, dMx, dMy (int64) and the accepted sites add up in registers and are reduced over the workgroup only where they
+// are needed: at a measurement and at the end of the launch.  Lane 0 keeps the walker's fp64 sums in registers for the
+// whole launch and adds every measurement in the header's order of operations (compiled with -ffp-contract=off).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/dqmc_hip.h"
+#include "kernels.h"
+
+namespace dqmc_qs {
+
+constexpr int MAX_SITES = 16384;
+constexpr int MAX_Z = 8;
+constexpr int MAX_Q = 64;
+constexpr int MAX_COLOURS = 16;
+constexpr int WAVE = 64;
+constexpr int THREADS = 256;
+constexpr unsigned int DOMAIN_SWEEP = 4u, DOMAIN_CONF = 5u;
+constexpr double Q30_INV = 1.0 / 1073741824.0;
+// The work bound of a launch, in the terms of the Ising checkerboard path (ising.hip, CB_LAUNCH_BUDGET): a sweep counts as
+// N + 512 site visits, 512 walkers' workgroups run side by side, and a launch runs at most
+// QS_LAUNCH_BUDGET / ((N + 512) max(1, W / 512)) sweeps, one at least.  A q-state site draws two uniforms and reads z table
+// entries, so the budget is half the Ising one.
+constexpr double QS_LAUNCH_BUDGET = 524288.0;
+constexpr double QS_SWEEP_OVERHEAD = 512.0;
+constexpr double QS_RESIDENT_WALKERS = 512.0;
+
+struct DevState {
+    int N, Nw, W, q, z, cap, n_bonds;  // Nw: 4-byte words of a walker's configuration (N bytes, padded with zeros)
+    unsigned int *conf;                // [W][Nw]
+    double *wt;                        // [W][q q]
+    unsigned long long *key, *cursor;  // [W]
+    long long *E, *Mx, *My;            // [W]
+    double *sE, *sE2, *sM, *sM2, *sM4;
+    long long *n_meas, *prop, *acc, *n_series;
+    long long *ser;                    // [W][cap][3]
+};
+
+// Philox4x32-10 as kernels.h philox4_uniform, with both uniforms of the output: (o0, o1) -> u1, (o2, o3) -> u2
+__device__ __forceinline__ void philox4_two(unsigned long long seed, unsigned int c0, unsigned int c1, unsigned int c2,
+                                            unsigned int c3, double &u1, double &u2)
+{
+    unsigned int k0 = (unsigned int)seed, k1 = (unsigned int)(seed >> 32);
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0;
+        const unsigned long long p1 = (unsigned long long)0xCD9E8D57u * c2;
+        const unsigned int n0 = (unsigned int)(p1 >> 32) ^ c1 ^ k0;
+        const unsigned int n1 = (unsigned int)p1;
+        const unsigned int n2 = (unsigned int)(p0 >> 32) ^ c3 ^ k1;
+        const unsigned int n3 = (unsigned int)p0;
+        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    u1 = (double)(((unsigned long long)(c0 >> 5) << 26) | (c1 >> 6)) * (1.0 / 9007199254740992.0);
+    u2 = (double)(((unsigned long long)(c2 >> 5) << 26) | (c3 >> 6)) * (1.0 / 9007199254740992.0);
+}
+
+__device__ __forceinline__ long long wave_sum(long long v)
+{
+#pragma unroll
+    for (int o = WAVE / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+__device__ __forceinline__ int mod_q(int d, int q) { return d < 0 ? d + q : d; }  // d in (-q, q)
+
+static inline size_t sweep_lds_bytes(int q, int Nw) { return (size_t)8 * q * q + (size_t)16 * q + 32 + (size_t)4 * Nw; }
+
+__global__ __launch_bounds__(THREADS) void qs_sweep_kernel(DevState s, const int *__restrict__ site,
+                                                           const int4 *__restrict__ rows, const int *__restrict__ off,
+                                                           const long long *__restrict__ e_q30,
+                                                           const int2 *__restrict__ cs_q30, int C, int n_sweeps,
+                                                           long long first_sweep, long long thermalization,
+                                                           int measure_rate)
+{
+    extern __shared__ __align__(16) unsigned char lds[];
+    const int tid = threadIdx.x, nt = blockDim.x, w = blockIdx.x;
+    const int N = s.N, Nw = s.Nw, q = s.q, z = s.z;
+    double *wt = (double *)lds;                                // [q][q]
+    long long *et = (long long *)(wt + q * q);                 // [q]
+    int2 *cs = (int2 *)(et + q);                               // [q]
+    unsigned long long *red = (unsigned long long *)(cs + q);  // E_int, Mx, My, accepted sites of the launch
+    unsigned char *st = (unsigned char *)(red + 4);            // [4 Nw]
+    {
+        unsigned int *stw = (unsigned int *)st;
+        const unsigned int *src = s.conf + (size_t)w * Nw;
+        for (int j = tid; j < Nw; j += nt) stw[j] = src[j];
+        const double *wsrc = s.wt + (size_t)w * q * q;
+        for (int j = tid; j < q * q; j += nt) wt[j] = wsrc[j];
+        for (int j = tid; j < q; j += nt) {
+            et[j] = e_q30[j];
+            cs[j] = cs_q30[j];
+        }
+        if (tid == 0) {
+            red[0] = (unsigned long long)s.E[w];
+            red[1] = (unsigned long long)s.Mx[w];
+            red[2] = (unsigned long long)s.My[w];
+            red[3] = 0ull;
+        }
+    }
+    const unsigned long long key = s.key[w];
+    unsigned long long sc = s.cursor[w];
+    // lane 0 carries the walker's sums through the launch
+    double sE = 0.0, sE2 = 0.0, sM = 0.0, sM2 = 0.0, sM4 = 0.0;
+    long long n_meas = 0, n_series = 0;
+    if (tid == 0) {
+        sE = s.sE[w];
+        sE2 = s.sE2[w];
+        sM = s.sM[w];
+        sM2 = s.sM2[w];
+        sM4 = s.sM4[w];
+        n_meas = s.n_meas[w];
+        n_series = s.n_series[w];
+    }
+    // the next measured sweep at or behind first_sweep: one division per launch, none per sweep
+    const long long g0 = first_sweep > thermalization + 1 ? first_sweep : thermalization + 1;
+    long long next = (g0 + measure_rate - 1) / measure_rate * measure_rate;
+    long long dE = 0, dMx = 0, dMy = 0;
+    int acc = 0;
+    const double qm1 = (double)(q - 1);
+    __syncthreads();
+
+    for (int sw = 0; sw < n_sweeps; ++sw, ++sc) {
+        const unsigned int c1 = (unsigned int)sc, c3 = (unsigned int)(sc >> 32);
+        for (int c = 0; c < C; ++c) {
+            const int e1 = off[c + 1];
+            for (int e = off[c] + tid; e < e1; e += nt) {
+                const int i = site[e];
+                const int4 r0 = rows[2 * e], r1 = rows[2 * e + 1];
+                const int row[MAX_Z] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w};
+                const int so = st[i];
+                double u1, u2;
+                philox4_two(key, (unsigned int)i, c1, DOMAIN_SWEEP, c3, u1, u2);
+                int t = so + 1 + min(q - 2, (int)(u1 * qm1));
+                t = t >= q ? t - q : t;
+                long long d = 0;
+                double p = 1.0;
+#pragma unroll
+                for (int k = 0; k < MAX_Z; ++k)
+                    if (k < z) {
+                        const int sj = st[row[k]];
+                        const int a = mod_q(so - sj, q), b = mod_q(t - sj, q);
+                        d += et[a] - et[b];
+                        p = p * wt[a * q + b];
+                    }
+                if (d <= 0 || u2 < p) {
+                    st[i] = (unsigned char)t;
+                    const int2 co = cs[so], cn = cs[t];
+                    dE += d;
+                    dMx += (long long)cn.x - co.x;  // (up to 2^31 in magnitude: not an int)
+                    dMy += (long long)cn.y - co.y;
+                    ++acc;
+                }
+            }
+            __syncthreads();
+        }
+        const long long g = first_sweep + sw;  // global 1-based sweep index
+        if (g != next) continue;               // (uniform)
+        next += measure_rate;
+        const long long e = wave_sum(dE), mx = wave_sum(dMx), my = wave_sum(dMy);
+        dE = dMx = dMy = 0;
+        if ((tid & (WAVE - 1)) == 0) {
+            atomicAdd(&red[0], (unsigned long long)e);
+            atomicAdd(&red[1], (unsigned long long)mx);
+            atomicAdd(&red[2], (unsigned long long)my);
+        }
+        __syncthreads();  // (the next write of red[0..2] lies behind the next sweep's barriers)
+        if (tid == 0) {
+            const long long E = (long long)red[0], Mx = (long long)red[1], My = (long long)red[2];
+            const double ev = (double)E * Q30_INV, x = (double)Mx * Q30_INV, y = (double)My * Q30_INV;
+            const double m2 = x * x + y * y;
+            sE = sE + ev;
+            sE2 = sE2 + ev * ev;
+            sM2 = sM2 + m2;
+            sM4 = sM4 + m2 * m2;
+            sM = sM + sqrt(m2);
+            n_meas += 1;
+            if (n_series < s.cap) {
+                long long *rec = s.ser + ((size_t)w * s.cap + (size_t)n_series) * 3;
+                rec[0] = E;
+                rec[1] = Mx;
+                rec[2] = My;
+                n_series += 1;
+            }
+        }
+    }
+
+    __syncthreads();
+    {
+        const long long e = wave_sum(dE), mx = wave_sum(dMx), my = wave_sum(dMy), n = wave_sum((long long)acc);
+        if ((tid & (WAVE - 1)) == 0) {
+            atomicAdd(&red[0], (unsigned long long)e);
+            atomicAdd(&red[1], (unsigned long long)mx);
+            atomicAdd(&red[2], (unsigned long long)my);
+            atomicAdd(&red[3], (unsigned long long)n);
+        }
+    }
+    __syncthreads();
+    {
+        const unsigned int *stw = (const unsigned int *)st;
+        unsigned int *dst = s.conf + (size_t)w * Nw;
+        for (int j = tid; j < Nw; j += nt) dst[j] = stw[j];
+    }
+    if (tid == 0) {
+        const long long prop = s.prop[w], accd = s.acc[w];  // requested together
+        s.E[w] = (long long)red[0];
+        s.Mx[w] = (long long)red[1];
+        s.My[w] = (long long)red[2];
+        s.prop[w] = prop + (long long)n_sweeps * N;
+        s.acc[w] = accd + (long long)red[3];
+        s.cursor[w] = sc;
+        s.sE[w] = sE;
+        s.sE2[w] = sE2;
+        s.sM[w] = sM;
+        s.sM2[w] = sM2;
+        s.sM4[w] = sM4;
+        s.n_meas[w] = n_meas;
+        s.n_series[w] = n_series;
+    }
+}
+
+// the initial configuration of one walker (walker >= 0) or of every walker: site i takes min(q - 1, (int)fl(u1 q)) with
+// u1 of P(key; i, low32(r), 5, high32(r)), r = the walker's conf cursor (held on the host)
+__global__ __launch_bounds__(THREADS) void qs_rand_conf_kernel(DevState s, const unsigned long long *__restrict__ confs,
+                                                               int walker)
+{
+    const int w = walker >= 0 ? walker : (int)blockIdx.x;
+    if (w >= s.W) return;
+    const unsigned long long key = s.key[w], r = confs[w];
+    unsigned char *dst = (unsigned char *)(s.conf + (size_t)w * s.Nw);
+    const double qd = (double)s.q;
+    for (int i = threadIdx.x; i < s.N; i += blockDim.x) {
+        double u1, u2;
+        philox4_two(key, (unsigned int)i, (unsigned int)r, DOMAIN_CONF, (unsigned int)(r >> 32), u1, u2);
+        dst[i] = (unsigned char)min(s.q - 1, (int)(u1 * qd));
+    }
+}
+
+// E_int, Mx, My of one walker (walker >= 0) or of every walker from the configuration in device memory
+__global__ __launch_bounds__(THREADS) void qs_observables_kernel(DevState s, const int *__restrict__ bonds,
+                                                                 const long long *__restrict__ e_q30,
+                                                                 const int2 *__restrict__ cs_q30, int walker)
+{
+    __shared__ unsigned long long red[3];
+    const int w = walker >= 0 ? walker : (int)blockIdx.x;
+    if (w >= s.W) return;  // (uniform)
+    const int tid = threadIdx.x, q = s.q;
+    if (tid < 3) red[tid] = 0ull;
+    __syncthreads();
+    const unsigned char *st = (const unsigned char *)(s.conf + (size_t)w * s.Nw);
+    long long E = 0, Mx = 0, My = 0;
+    for (int b = tid; b < s.n_bonds; b += blockDim.x) E -= e_q30[mod_q((int)st[bonds[2 * b]] - (int)st[bonds[2 * b + 1]], q)];
+    for (int i = tid; i < s.N; i += blockDim.x) {
+        const int2 c = cs_q30[st[i]];
+        Mx += c.x;
+        My += c.y;
+    }
+    E = wave_sum(E);
+    Mx = wave_sum(Mx);
+    My = wave_sum(My);
+    if ((tid & (WAVE - 1)) == 0) {
+        atomicAdd(&red[0], (unsigned long long)E);
+        atomicAdd(&red[1], (unsigned long long)Mx);
+        atomicAdd(&red[2], (unsigned long long)My);
+    }
+    __syncthreads();
+    if (tid == 0) {
+        s.E[w] = (long long)red[0];
+        s.Mx[w] = (long long)red[1];
+        s.My[w] = (long long)red[2];
+    }
+}
+
+}  // namespace dqmc_qs
+
+using namespace dqmc_qs;
+
+struct dqmc_qs_handle {
+    int N = 0, z = 0, q = 0, W = 0, Nw = 0, cap = 0, n_bonds = 0, device = 0;
+    int C = 0, threads = THREADS;
+    std::vector<int> nbr_h;             // [N][z] 0-based
+    std::vector<long long> e_h;         // [q]
+    std::vector<unsigned long long> confs_h;  // [W]: the conf cursor r of every walker
+    hipStream_t stream = nullptr;
+    DevState d{};
+    int *site = nullptr, *rows = nullptr, *off = nullptr, *bonds = nullptr;  // [N], [N][8], [17], [n_bonds][2]
+    long long *e_q30 = nullptr;         // [q]
+    int2 *cs_q30 = nullptr;             // [q]
+    unsigned long long *confs = nullptr;  // [W], the device image of confs_h for qs_rand_conf_kernel
+    std::vector<void *> allocs;
+    std::string err;
+};
+
+static thread_local std::string g_qs_create_error;
+
+static int qs_fail(dqmc_qs_handle *h, int code, const std::string &msg)
+{
+    if (h) h->err = msg;
+    else g_qs_create_error = msg;
+    return code;
+}
+
+#define QCHK(expr)                                                                                               \
+    do {                                                                                                         \
+        hipError_t e_ = (expr);                                                                                  \
+        if (e_ != hipSuccess) return qs_fail(h, DQMC_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
+template <typename T>
+static int qs_alloc(dqmc_qs_handle *h, T **p, size_t count)
+{
+    void *m = nullptr;
+    QCHK(hipMalloc(&m, (count ? count : 1) * sizeof(T)));
+    h->allocs.push_back(m);
+    QCHK(hipMemsetAsync(m, 0, (count ? count : 1) * sizeof(T), h->stream));
+    *p = (T *)m;
+    return 0;
+}
+
+static int qs_walker(dqmc_qs_handle *h, int32_t w, const char *fn)
+{
+    if (!h) return qs_fail(nullptr, DQMC_ERR_INVALID, std::string(fn) + ": null handle");
+    if (w < 0 || w >= h->W) return qs_fail(h, DQMC_ERR_INVALID, std::string(fn) + ": walker out of range");
+    return 0;
+}
+
+template <typename T>
+static int qs_put(dqmc_qs_handle *h, T *base, int w, T v)
+{
+    QCHK(hipMemcpyAsync(base + w, &v, sizeof(T), hipMemcpyHostToDevice, h->stream));
+    QCHK(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+template <typename T>
+static int qs_get(dqmc_qs_handle *h, const T *base, int w, T *v)
+{
+    QCHK(hipMemcpyAsync(v, base + w, sizeof(T), hipMemcpyDeviceToHost, h->stream));
+    QCHK(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+// the colour-sorted tables of a colouring, validated against the neighbour table (h may be NULL while creating: the
+// message then goes where dqmc_qs_last_error(NULL) finds it)
+static int qs_colour_tables(dqmc_qs_handle *err_to, const char *fn, const std::vector<int> &nbr, int N, int z,
+                            const int32_t *colour, int nc, std::vector<int> &site, std::vector<int> &rows,
+                            std::vector<int> &off, int *largest)
+{
+    const std::string f(fn);
+    if (!colour) return qs_fail(err_to, DQMC_ERR_INVALID, f + ": null colouring");
+    if (nc < 1 || nc > MAX_COLOURS) return qs_fail(err_to, DQMC_ERR_INVALID, f + ": n_colours must be in 1..16");
+    for (int i = 0; i < N; ++i)
+        if (colour[i] < 0 || colour[i] >= nc)
+            return qs_fail(err_to, DQMC_ERR_INVALID,
+                           f + ": the colour of site " + std::to_string(i) + " is out of range 0..n_colours-1");
+    for (int i = 0; i < N; ++i)
+        for (int k = 0; k < z; ++k) {
+            const int j = nbr[(size_t)i * z + k];
+            if (j == i)
+                return qs_fail(err_to, DQMC_ERR_INVALID,
+                               f + ": site " + std::to_string(i) + " lists itself as a neighbour (0-based): no colouring");
+            if (colour[j] == colour[i])
+                return qs_fail(err_to, DQMC_ERR_INVALID, f + ": the neighbours " + std::to_string(i) + " and " +
+                                                             std::to_string(j) + " (0-based sites) share colour " +
+                                                             std::to_string(colour[i]));
+        }
+    off.assign((size_t)MAX_COLOURS + 1, 0);
+    site.assign((size_t)N, 0);
+    rows.assign((size_t)N * MAX_Z, 0);
+    for (int i = 0; i < N; ++i) off[(size_t)colour[i] + 1] += 1;
+    *largest = 0;
+    for (int c = 0; c < MAX_COLOURS; ++c) {
+        *largest = std::max(*largest, off[(size_t)c + 1]);
+        off[(size_t)c + 1] += off[c];
+    }
+    std::vector<int> fill(off.begin(), off.end() - 1);
+    for (int i = 0; i < N; ++i) {
+        const int e = fill[colour[i]]++;
+        site[e] = i;
+        for (int k = 0; k < z; ++k) rows[(size_t)e * MAX_Z + k] = nbr[(size_t)i * z + k];
+    }
+    return 0;
+}
+
+static int qs_put_colouring(dqmc_qs_handle *h, const std::vector<int> &site, const std::vector<int> &rows,
+                            const std::vector<int> &off, int nc, int largest)
+{
+    QCHK(hipSetDevice(h->device));
+    QCHK(hipStreamSynchronize(h->stream));
+    QCHK(hipMemcpyAsync(h->site, site.data(), site.size() * 4, hipMemcpyHostToDevice, h->stream));
+    QCHK(hipMemcpyAsync(h->rows, rows.data(), rows.size() * 4, hipMemcpyHostToDevice, h->stream));
+    QCHK(hipMemcpyAsync(h->off, off.data(), off.size() * 4, hipMemcpyHostToDevice, h->stream));
+    QCHK(hipStreamSynchronize(h->stream));  // (the vectors are the caller's: copied before it returns)
+    h->C = nc;
+    h->threads = std::min(THREADS, std::max(WAVE, (largest + WAVE - 1) / WAVE * WAVE));
+    return 0;
+}
+
+static int qs_launch_observables(dqmc_qs_handle *h, int walker)
+{
+    hipLaunchKernelGGL(qs_observables_kernel, dim3(walker >= 0 ? 1 : h->W), dim3(THREADS), 0, h->stream, h->d,
+                       (const int *)h->bonds, (const long long *)h->e_q30, (const int2 *)h->cs_q30, walker);
+    QCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" {
+
+const char *dqmc_qs_last_error(const dqmc_qs_handle *h) { return h ? h->err.c_str() : g_qs_create_error.c_str(); }
+
+int dqmc_qs_create(const dqmc_qs_params *p, dqmc_qs_handle **out)
+{
+    const std::string f = "dqmc_qs_create";
+    if (!p || !out) return qs_fail(nullptr, DQMC_ERR_INVALID, f + ": null argument");
+    *out = nullptr;
+    if (p->q < 2 || p->q > MAX_Q)
+        return qs_fail(nullptr, DQMC_ERR_INVALID, f + ": q = " + std::to_string(p->q) + " is outside 2..64");
+    if (p->n_sites < 1 || p->n_walkers < 1)
+        return qs_fail(nullptr, DQMC_ERR_INVALID, f + ": n_sites and n_walkers must be >= 1");
+    if (p->n_sites > MAX_SITES)
+        return qs_fail(nullptr, DQMC_ERR_INVALID, f + ": n_sites = " + std::to_string(p->n_sites) +
+                                                      " exceeds 16384 (the walker's sites must fit in LDS)");
+    if (p->z < 1 || p->z > MAX_Z)
+        return qs_fail(nullptr, DQMC_ERR_INVALID,
+                       f + ": z = " + std::to_string(p->z) + " is outside 1..8 (neighbours per site)");
+    if (p->n_bonds < 0 || p->series_capacity < 0)
+        return qs_fail(nullptr, DQMC_ERR_INVALID, f + ": n_bonds and series_capacity must be >= 0");
+    if (!p->neighs || (p->n_bonds > 0 && !p->bonds))
+        return qs_fail(nullptr, DQMC_ERR_INVALID, f + ": neighbour or bonds table missing");
+    if (!p->e_q30 || !p->c_q30 || !p->s_q30)
+        return qs_fail(nullptr, DQMC_ERR_INVALID, f + ": e_q30, c_q30 or s_q30 missing");
+    const int N = p->n_sites, z = p->z, nb = p->n_bonds, q = p->q;
+    for (long i = 0; i < (long)z * N; ++i)
+        if (p->neighs[i] < 1 || p->neighs[i] > N)
+            return qs_fail(nullptr, DQMC_ERR_INVALID, f + ": neighbour index out of range 1..n_sites");
+    for (long i = 0; i < 2L * nb; ++i)
+        if (p->bonds[i] < 1 || p->bonds[i] > N)
+            return qs_fail(nullptr, DQMC_ERR_INVALID, f + ": bond index out of range 1..n_sites");
+    for (int d = 0; d < q; ++d) {
+        if (p->e_q30[d] != p->e_q30[(q - d) % q])
+            return qs_fail(nullptr, DQMC_ERR_INVALID, f + ": e_q30[" + std::to_string(d) + "] != e_q30[" +
+                                                          std::to_string((q - d) % q) + "]: the table is not symmetric");
+        if (p->e_q30[d] > (1LL << 32) || p->e_q30[d] < -(1LL << 32))
+            return qs_fail(nullptr, DQMC_ERR_INVALID, f + ": e_q30[" + std::to_string(d) + "] exceeds 2^32 in magnitude");
+        if (p->c_q30[d] > (1 << 30) || p->c_q30[d] < -(1 << 30) || p->s_q30[d] > (1 << 30) || p->s_q30[d] < -(1 << 30))
+            return qs_fail(nullptr, DQMC_ERR_INVALID,
+                           f + ": c_q30 / s_q30 entry " + std::to_string(d) + " exceeds 2^30 in magnitude");
+    }
+    std::vector<int> nbr((size_t)N * z);
+    for (size_t i = 0; i < nbr.size(); ++i) nbr[i] = (int)p->neighs[i] - 1;
+    std::vector<int> site, rows, off;
+    int largest = 0;
+    if (int rc = qs_colour_tables(nullptr, "dqmc_qs_create", nbr, N, z, p->colour, p->n_colours, site, rows, off, &largest))
+        return rc;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+        return qs_fail(nullptr, DQMC_ERR_NO_DEVICE, f + ": no HIP device visible");
+    if (p->device_id < 0 || p->device_id >= ndev)
+        return qs_fail(nullptr, DQMC_ERR_INVALID, f + ": device_id out of range");
+
+    dqmc_qs_handle *h = new dqmc_qs_handle();
+    h->N = N;
+    h->z = z;
+    h->q = q;
+    h->W = p->n_walkers;
+    h->Nw = (N + 3) / 4;
+    h->cap = p->series_capacity;
+    h->n_bonds = nb;
+    h->device = p->device_id;
+    h->nbr_h = nbr;
+    h->e_h.assign(p->e_q30, p->e_q30 + q);
+    h->confs_h.assign((size_t)h->W, 0ull);
+    std::vector<int> bonds_h((size_t)2 * nb);
+    for (int b = 0; b < nb; ++b) {  // n_bonds x 2 column-major -> pairs
+        bonds_h[2 * b] = (int)p->bonds[b] - 1;
+        bonds_h[2 * b + 1] = (int)p->bonds[nb + b] - 1;
+    }
+    std::vector<int2> cs_h((size_t)q);
+    for (int d = 0; d < q; ++d) cs_h[d] = make_int2(p->c_q30[d], p->s_q30[d]);
+    auto bail = [&](int rc) {
+        g_qs_create_error = h->err;
+        dqmc_qs_destroy(h);
+        return rc;
+    };
+    if (hipSetDevice(h->device) != hipSuccess || hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess)
+        return bail(qs_fail(h, DQMC_ERR_HIP, f + ": cannot open the device"));
+    DevState &d = h->d;
+    d.N = N;
+    d.Nw = h->Nw;
+    d.W = h->W;
+    d.q = q;
+    d.z = z;
+    d.cap = h->cap;
+    d.n_bonds = nb;
+    const size_t W = h->W;
+    int rc = 0;
+    if ((rc = qs_alloc(h, &d.conf, (size_t)h->Nw * W)) || (rc = qs_alloc(h, &d.wt, (size_t)q * q * W)) ||
+        (rc = qs_alloc(h, &d.key, W)) || (rc = qs_alloc(h, &d.cursor, W)) || (rc = qs_alloc(h, &d.E, W)) ||
+        (rc = qs_alloc(h, &d.Mx, W)) || (rc = qs_alloc(h, &d.My, W)) || (rc = qs_alloc(h, &d.sE, W)) ||
+        (rc = qs_alloc(h, &d.sE2, W)) || (rc = qs_alloc(h, &d.sM, W)) || (rc = qs_alloc(h, &d.sM2, W)) ||
+        (rc = qs_alloc(h, &d.sM4, W)) || (rc = qs_alloc(h, &d.n_meas, W)) || (rc = qs_alloc(h, &d.prop, W)) ||
+        (rc = qs_alloc(h, &d.acc, W)) || (rc = qs_alloc(h, &d.n_series, W)) ||
+        (rc = qs_alloc(h, &d.ser, (size_t)3 * h->cap * W)) || (rc = qs_alloc(h, &h->site, (size_t)N)) ||
+        (rc = qs_alloc(h, &h->rows, (size_t)N * MAX_Z)) || (rc = qs_alloc(h, &h->off, (size_t)MAX_COLOURS + 1)) ||
+        (rc = qs_alloc(h, &h->bonds, bonds_h.size())) || (rc = qs_alloc(h, &h->e_q30, (size_t)q)) ||
+        (rc = qs_alloc(h, &h->cs_q30, (size_t)q)) || (rc = qs_alloc(h, &h->confs, W)))
+        return bail(rc);
+    std::vector<double> ones((size_t)q * q * W, 1.0);  // beta = 0
+    if (hipMemcpyAsync(d.wt, ones.data(), ones.size() * 8, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
+        (nb && hipMemcpyAsync(h->bonds, bonds_h.data(), bonds_h.size() * 4, hipMemcpyHostToDevice, h->stream) !=
+                   hipSuccess) ||
+        hipMemcpyAsync(h->e_q30, h->e_h.data(), (size_t)q * 8, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
+        hipMemcpyAsync(h->cs_q30, cs_h.data(), (size_t)q * 8, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
+        hipStreamSynchronize(h->stream) != hipSuccess)
+        return bail(qs_fail(h, DQMC_ERR_HIP, f + ": table upload failed"));
+    if ((rc = qs_put_colouring(h, site, rows, off, p->n_colours, largest))) return bail(rc);
+    if ((rc = qs_launch_observables(h, -1))) return bail(rc);  // all sites in state 0
+    if (hipStreamSynchronize(h->stream) != hipSuccess)
+        return bail(qs_fail(h, DQMC_ERR_HIP, f + ": device initialisation failed"));
+    *out = h;
+    return DQMC_OK;
+}
+
+int dqmc_qs_destroy(dqmc_qs_handle *h)
+{
+    if (!h) return DQMC_OK;
+    if (h->stream) {
+        (void)hipSetDevice(h->device);
+        (void)hipStreamSynchronize(h->stream);
+    }
+    for (void *p : h->allocs) (void)hipFree(p);
+    if (h->stream) (void)hipStreamDestroy(h->stream);
+    delete h;
+    return DQMC_OK;
+}
+
+int dqmc_qs_seed(dqmc_qs_handle *h, int32_t walker, uint64_t seed)
+{
+    if (int rc = qs_walker(h, walker, "dqmc_qs_seed")) return rc;
+    QCHK(hipSetDevice(h->device));
+    if (int rc = qs_put<unsigned long long>(h, h->d.key, walker, seed)) return rc;
+    h->confs_h[walker] = 0ull;
+    return qs_put<unsigned long long>(h, h->d.cursor, walker, 0ull);
+}
+
+int dqmc_qs_set_beta(dqmc_qs_handle *h, int32_t walker, double beta)
+{
+    if (int rc = qs_walker(h, walker, "dqmc_qs_set_beta")) return rc;
+    if (!std::isfinite(beta) || beta < 0.0)
+        return qs_fail(h, DQMC_ERR_INVALID, "dqmc_qs_set_beta: beta must be finite and >= 0");
+    const int q = h->q;
+    std::vector<double> wt((size_t)q * q);
+    for (int a = 0; a < q; ++a)
+        for (int b = 0; b < q; ++b) {
+            const double x = (double)(h->e_h[a] - h->e_h[b]) * Q30_INV;  // exact
+            const double y = -beta * x;                                   // one rounding
+            wt[(size_t)a * q + b] = exp(y);
+        }
+    QCHK(hipSetDevice(h->device));
+    QCHK(hipMemcpyAsync(h->d.wt + (size_t)walker * q * q, wt.data(), wt.size() * 8, hipMemcpyHostToDevice, h->stream));
+    QCHK(hipStreamSynchronize(h->stream));
+    return DQMC_OK;
+}
+
+int dqmc_qs_rand_conf(dqmc_qs_handle *h, int32_t walker)
+{
+    if (!h) return qs_fail(nullptr, DQMC_ERR_INVALID, "dqmc_qs_rand_conf: null handle");
+    if (walker >= h->W) return qs_fail(h, DQMC_ERR_INVALID, "dqmc_qs_rand_conf: walker out of range");
+    QCHK(hipSetDevice(h->device));
+    QCHK(hipMemcpyAsync(h->confs, h->confs_h.data(), (size_t)h->W * 8, hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(qs_rand_conf_kernel, dim3(walker >= 0 ? 1 : h->W), dim3(THREADS), 0, h->stream, h->d,
+                       (const unsigned long long *)h->confs, (int)walker);
+    QCHK(hipGetLastError());
+    if (int rc = qs_launch_observables(h, walker)) return rc;
+    QCHK(hipStreamSynchronize(h->stream));
+    for (int w = 0; w < h->W; ++w)
+        if (walker < 0 || w == walker) h->confs_h[w] += 1;
+    return DQMC_OK;
+}
+
+int dqmc_qs_set_conf(dqmc_qs_handle *h, int32_t walker, const uint8_t *conf)
+{
+    if (int rc = qs_walker(h, walker, "dqmc_qs_set_conf")) return rc;
+    if (!conf) return qs_fail(h, DQMC_ERR_INVALID, "dqmc_qs_set_conf: null conf");
+    std::vector<unsigned int> words((size_t)h->Nw, 0u);
+    for (int i = 0; i < h->N; ++i) {
+        if (conf[i] >= h->q)
+            return qs_fail(h, DQMC_ERR_INVALID, "dqmc_qs_set_conf: the state of site " + std::to_string(i) +
+                                                    " (0-based) is not below q");
+        words[i >> 2] |= (unsigned int)conf[i] << (8 * (i & 3));
+    }
+    QCHK(hipSetDevice(h->device));
+    QCHK(hipMemcpyAsync(h->d.conf + (size_t)walker * h->Nw, words.data(), words.size() * 4, hipMemcpyHostToDevice,
+                        h->stream));
+    if (int rc = qs_launch_observables(h, walker)) return rc;
+    QCHK(hipStreamSynchronize(h->stream));
+    return DQMC_OK;
+}
+
+int dqmc_qs_get_conf(dqmc_qs_handle *h, int32_t walker, uint8_t *conf)
+{
+    if (int rc = qs_walker(h, walker, "dqmc_qs_get_conf")) return rc;
+    if (!conf) return qs_fail(h, DQMC_ERR_INVALID, "dqmc_qs_get_conf: null conf");
+    std::vector<unsigned int> words((size_t)h->Nw, 0u);
+    QCHK(hipSetDevice(h->device));
+    QCHK(hipMemcpyAsync(words.data(), h->d.conf + (size_t)walker * h->Nw, words.size() * 4, hipMemcpyDeviceToHost,
+                        h->stream));
+    QCHK(hipStreamSynchronize(h->stream));
+    for (int i = 0; i < h->N; ++i) conf[i] = (uint8_t)(words[i >> 2] >> (8 * (i & 3)));
+    return DQMC_OK;
+}
+
+int dqmc_qs_set_colouring(dqmc_qs_handle *h, const int32_t *colour, int32_t n_colours)
+{
+    if (!h) return qs_fail(nullptr, DQMC_ERR_INVALID, "dqmc_qs_set_colouring: null handle");
+    std::vector<int> site, rows, off;
+    int largest = 0;
+    if (int rc = qs_colour_tables(h, "dqmc_qs_set_colouring", h->nbr_h, h->N, h->z, colour, n_colours, site, rows, off,
+                                  &largest))
+        return rc;
+    return qs_put_colouring(h, site, rows, off, n_colours, largest);
+}
+
+int dqmc_qs_sweep(dqmc_qs_handle *h, int32_t n_sweeps, int64_t first_sweep_index, int64_t thermalization,
+                  int32_t measure_rate)
+{
+    if (!h) return qs_fail(nullptr, DQMC_ERR_INVALID, "dqmc_qs_sweep: null handle");
+    if (n_sweeps < 0 || measure_rate < 1 || first_sweep_index < 1)
+        return qs_fail(h, DQMC_ERR_INVALID, "dqmc_qs_sweep: n_sweeps >= 0, first_sweep_index >= 1, measure_rate >= 1");
+    QCHK(hipSetDevice(h->device));
+    const double per_sweep = ((double)h->N + QS_SWEEP_OVERHEAD) * std::max(1.0, (double)h->W / QS_RESIDENT_WALKERS);
+    const int chunk = (int)std::max(1.0, std::min((double)n_sweeps, std::floor(QS_LAUNCH_BUDGET / per_sweep)));
+    const size_t lds = sweep_lds_bytes(h->q, h->Nw);
+    for (int done = 0; done < n_sweeps;) {
+        const int n = std::min(chunk, n_sweeps - done);
+        hipLaunchKernelGGL(qs_sweep_kernel, dim3(h->W), dim3(h->threads), lds, h->stream, h->d, (const int *)h->site,
+                           (const int4 *)h->rows, (const int *)h->off, (const long long *)h->e_q30,
+                           (const int2 *)h->cs_q30, h->C, n, (long long)(first_sweep_index + done),
+                           (long long)thermalization, (int)measure_rate);
+        QCHK(hipGetLastError());
+        done += n;
+    }
+    QCHK(hipStreamSynchronize(h->stream));
+    return DQMC_OK;
+}
+
+int dqmc_qs_get_stats(dqmc_qs_handle *h, int32_t walker, dqmc_qs_stats *out)
+{
+    if (int rc = qs_walker(h, walker, "dqmc_qs_get_stats")) return rc;
+    if (!out) return qs_fail(h, DQMC_ERR_INVALID, "dqmc_qs_get_stats: null out");
+    QCHK(hipSetDevice(h->device));
+    const DevState &d = h->d;
+    long long E = 0, Mx = 0, My = 0, n_meas = 0, prop = 0, acc = 0, n_series = 0;
+    unsigned long long cursor = 0;
+    int rc = 0;
+    if ((rc = qs_get(h, d.E, walker, &E)) || (rc = qs_get(h, d.Mx, walker, &Mx)) || (rc = qs_get(h, d.My, walker, &My)) ||
+        (rc = qs_get(h, d.sE, walker, &out->sum_E)) || (rc = qs_get(h, d.sE2, walker, &out->sum_E2)) ||
+        (rc = qs_get(h, d.sM, walker, &out->sum_absM)) || (rc = qs_get(h, d.sM2, walker, &out->sum_M2)) ||
+        (rc = qs_get(h, d.sM4, walker, &out->sum_M4)) || (rc = qs_get(h, d.n_meas, walker, &n_meas)) ||
+        (rc = qs_get(h, d.prop, walker, &prop)) || (rc = qs_get(h, d.acc, walker, &acc)) ||
+        (rc = qs_get(h, d.n_series, walker, &n_series)) || (rc = qs_get(h, d.cursor, walker, &cursor)))
+        return rc;
+    out->energy_q30 = E;
+    out->mx_q30 = Mx;
+    out->my_q30 = My;
+    out->n_meas = n_meas;
+    out->prop_local = prop;
+    out->acc_local = acc;
+    out->sweeps_drawn = cursor;
+    out->confs_drawn = h->confs_h[walker];
+    out->n_series = n_series;
+    out->n_colours = h->C;
+    return DQMC_OK;
+}
+
+int dqmc_qs_get_series(dqmc_qs_handle *h, int32_t walker, int64_t *energy_q30, int64_t *mx_q30, int64_t *my_q30,
+                       int64_t *n_recorded)
+{
+    if (int rc = qs_walker(h, walker, "dqmc_qs_get_series")) return rc;
+    QCHK(hipSetDevice(h->device));
+    long long n = 0;
+    if (int rc = qs_get(h, h->d.n_series, walker, &n)) return rc;
+    if (n_recorded) *n_recorded = n;
+    if (n > 0 && (energy_q30 || mx_q30 || my_q30)) {
+        std::vector<long long> rec((size_t)3 * n);
+        QCHK(hipMemcpyAsync(rec.data(), h->d.ser + (size_t)walker * h->cap * 3, rec.size() * 8, hipMemcpyDeviceToHost,
+                            h->stream));
+        QCHK(hipStreamSynchronize(h->stream));
+        for (long long k = 0; k < n; ++k) {
+            if (energy_q30) energy_q30[k] = rec[3 * k];
+            if (mx_q30) mx_q30[k] = rec[3 * k + 1];
+            if (my_q30) my_q30[k] = rec[3 * k + 2];
+        }
+    }
+    return DQMC_OK;
+}
+
+int dqmc_qs_reset_accumulators(dqmc_qs_handle *h)
+{
+    if (!h) return qs_fail(nullptr, DQMC_ERR_INVALID, "dqmc_qs_reset_accumulators: null handle");
+    QCHK(hipSetDevice(h->device));
+    const DevState &d = h->d;
+    const size_t W = h->W;
+    for (double *p : {d.sE, d.sE2, d.sM, d.sM2, d.sM4}) QCHK(hipMemsetAsync(p, 0, W * 8, h->stream));
+    for (long long *p : {d.n_meas, d.n_series}) QCHK(hipMemsetAsync(p, 0, W * 8, h->stream));
+    QCHK(hipStreamSynchronize(h->stream));
+    return DQMC_OK;
+}
+
+int dqmc_qs_synchronize(dqmc_qs_handle *h)
+{
+    if (!h) return qs_fail(nullptr, DQMC_ERR_INVALID, "dqmc_qs_synchronize: null handle");
+    QCHK(hipSetDevice(h->device));
+    QCHK(hipStreamSynchronize(h->stream));
+    return DQMC_OK;
+}
+
+}  // extern "C"

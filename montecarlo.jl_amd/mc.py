@@ -64,6 +64,12 @@ def reciprocal_vectors(l):
     return (2.0 * np.pi * np.linalg.inv(A.T)).T.copy()
 
 
+def _llround(x):
+    """half away from zero, as C's llround; int64"""
+    x = np.asarray(x, dtype=np.float64)
+    return (np.sign(x) * np.floor(np.abs(x) + 0.5)).astype(np.int64)
+
+
 def q30_tables(l, k_vectors):
     """(cos_q30, sin_q30, k): int32 [n_k][N] with llround(cos(k . r_i) 2^30) and the sine likewise, r_i =
     lattices._positions(l) in the site order of mc.conf (include/dqmc_hip.h, "finite-size-scaling observables")"""
@@ -73,10 +79,8 @@ def q30_tables(l, k_vectors):
         raise ValueError("FSS: at most 8 wave vectors")
     ph = k @ r.T
 
-    def llround(x):  # half away from zero, as C's llround
-        return (np.sign(x) * np.floor(np.abs(x) + 0.5)).astype(np.int64).astype(np.int32)
-    return (np.ascontiguousarray(llround(np.cos(ph) * 2.0 ** 30)),
-            np.ascontiguousarray(llround(np.sin(ph) * 2.0 ** 30)), k)
+    return (np.ascontiguousarray(_llround(np.cos(ph) * 2.0 ** 30).astype(np.int32)),
+            np.ascontiguousarray(_llround(np.sin(ph) * 2.0 ** 30).astype(np.int32)), k)
 
 
 def greedy_colouring(l):
@@ -148,7 +152,16 @@ class MC:
     `update="checkerboard"` sweeps every walker with a whole workgroup, colour class by colour class (set_update;
     `colouring=None`: greedy_colouring(lattice)): another Markov chain than the reference's sequential sweep(mc), with
     the same stationary distribution, on a Philox domain of its own, and much faster per sweep where the walkers are
-    few and the lattice is large.  `update="sequential"` (the default) is the reference's sweep."""
+    few and the lattice is large.  `update="sequential"` (the default) is the reference's sweep.
+
+    With a q-state model (qstate.PottsModel, ClockModel, QStateModel) MC(...) returns a qstate.QStateMC: the engine of
+    dqmc_qs_* with its own kernels.  With an IsingModel nothing changes."""
+
+    def __new__(cls, model, *args, **kwargs):
+        if cls is MC and getattr(model, "is_qstate", False):
+            from .qstate import QStateMC
+            return QStateMC(model, *args, **kwargs)  # (not an MC: __init__ below does not run)
+        return super().__new__(cls)
 
     def __init__(self, model, beta=None, T=None, n_walkers=1, seed=123, first_walker=0, thermalization=0, sweeps=1000,
                  measure_rate=1, print_rate=1000, global_moves=False, global_rate=5, device_id=0, series_capacity=0,

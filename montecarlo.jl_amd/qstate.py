@@ -1,0 +1,324 @@
+"""q-state models for the classical MC flavor: Potts and clock (include/dqmc_hip.h, "the classical MC flavor with q-state
+models"; csrc/qstate.hip).  The reference's MC flavor is a plugin surface (energy, propose_local, accept_local!) whose one
+model is the IsingModel; these models, their checkerboard update and their two-component order parameter are a defined
+extension.  The host holds the model, the fixed-point tables, the colouring and the loop control; every site update and
+every measurement runs on the device, one workgroup per walker.
+
+Walker w draws from the Philox4x32-10 streams keyed by `seed + first_walker + w`, as the Ising walkers do, on domains of
+its own."""
+import ctypes as C
+import math
+import time
+
+import numpy as np
+
+from ._lib import DQMCError, ERR_INVALID, QsParams, QsStats, lib
+from .mc import _choose_lattice, _llround, greedy_colouring
+
+Q_MAX = 64
+Q30 = 2.0 ** 30
+
+
+def qstate_tables(q, pair_energy, J=1.0):
+    """(e_q30 int64 [q], c_q30 int32 [q], s_q30 int32 [q]): llround(J e[d] 2^30), symmetric by construction (d <= q / 2
+    computed, the rest mirrored), and llround(cos(2 pi s / q) 2^30) with the sine likewise"""
+    e = np.asarray(pair_energy, dtype=np.float64)
+    e_q30 = np.zeros(q, dtype=np.int64)
+    for d in range(q // 2 + 1):
+        e_q30[d] = e_q30[(q - d) % q] = _llround(J * e[d] * Q30)
+    ang = 2.0 * np.pi * np.arange(q) / q
+    return (e_q30, np.ascontiguousarray(_llround(np.cos(ang) * Q30).astype(np.int32)),
+            np.ascontiguousarray(_llround(np.sin(ang) * Q30).astype(np.int32)))
+
+
+class QStateModel:
+    """QStateModel(q, pair_energy; dims, L | l, J): s_i in {0 .. q - 1}, 2 <= q <= 64, and
+    E = -J sum_bonds e[(s_i - s_j) mod q] over the lattice's undirected bonds table, with the length-q table
+    e = pair_energy, e[d] == e[(q - d) % q].  Any project lattice may be given as `l`."""
+    is_qstate = True
+
+    def __init__(self, q, pair_energy, dims=None, L=None, l=None, J=1.0):
+        if int(q) != q or not 2 <= q <= Q_MAX:
+            raise ValueError("QStateModel: q must be an integer in 2..%d, got %r" % (Q_MAX, q))
+        q = int(q)
+        e = np.array(pair_energy, dtype=np.float64).reshape(-1)
+        if e.size != q or not np.all(np.isfinite(e)):
+            raise ValueError("QStateModel: pair_energy must hold q = %d finite values" % q)
+        for d in range(q):
+            if e[d] != e[(q - d) % q]:
+                raise ValueError("QStateModel: pair_energy[%d] != pair_energy[%d]: the table must be symmetric, "
+                                 "e[d] == e[(q - d) %% q]" % (d, (q - d) % q))
+        if not math.isfinite(J) or np.max(np.abs(J * e)) > 4.0:
+            raise ValueError("QStateModel: |J e[d]| must be finite and at most 4")
+        if l is None:
+            if dims is None or L is None:
+                raise ValueError("QStateModel needs dims and L, or a lattice l")
+            l = _choose_lattice(dims, L)
+        self.q, self.pair_energy, self.J = q, e, float(J)
+        self.l = l
+        self.L = L if L is not None else getattr(l, "L", len(l))
+        self.dims = dims if dims is not None else getattr(l, "dim", 2 if hasattr(l, "lattice") else 1)
+        self.e_q30, self.c_q30, self.s_q30 = qstate_tables(q, e, self.J)
+
+    def __len__(self):
+        return len(self.l)
+
+    def _conf(self, conf):
+        c = np.asarray(conf).reshape(-1, order="F").astype(np.int64)
+        if c.size != len(self.l) or np.any(c < 0) or np.any(c >= self.q):
+            raise ValueError("conf must hold %d states in 0..%d" % (len(self.l), self.q - 1))
+        return c
+
+    def energy_q30(self, conf):
+        """E_int = -sum_bonds e_q30[(s_i - s_j) mod q]: the device's exact integer energy"""
+        c = self._conf(conf)
+        b = np.asarray(self.l.bonds, dtype=np.int64)[:, :2] - 1
+        return -int(np.sum(self.e_q30[(c[b[:, 0]] - c[b[:, 1]]) % self.q]))
+
+    def energy(self, conf):
+        """energy(mc, m, conf): -J sum over the undirected bonds table of e[(s_i - s_j) mod q]"""
+        c = self._conf(conf)
+        b = np.asarray(self.l.bonds, dtype=np.int64)[:, :2] - 1
+        return float(-self.J * np.sum(self.pair_energy[(c[b[:, 0]] - c[b[:, 1]]) % self.q]))
+
+    def propose_local(self, i, t, conf):
+        """propose_local(mc, m, i, conf) for the proposal s_i -> t: delta_E = J sum_{j in neighs[:, i]} (e[(s_i - s_j) mod q]
+        - e[(t - s_j) mod q]), a repeated neighbour counted twice; i 1-based"""
+        c = self._conf(conf)
+        sj = c[np.asarray(self.l.neighs, dtype=np.int64)[:, i - 1] - 1]
+        e = self.pair_energy
+        return float(self.J * np.sum(e[(c[i - 1] - sj) % self.q] - e[(int(t) - sj) % self.q]))
+
+    def order_parameter_q30(self, conf):
+        """(Mx, My) = sum_i (c_q30[s_i], s_q30[s_i]) as exact integers"""
+        c = self._conf(conf)
+        return int(self.c_q30[c].astype(np.int64).sum()), int(self.s_q30[c].astype(np.int64).sum())
+
+
+class PottsModel(QStateModel):
+    """PottsModel(q; dims, L | l, J): e[d] = delta_{d,0}, E = -J sum_bonds delta(s_i, s_j)"""
+
+    def __init__(self, q, dims=None, L=None, l=None, J=1.0):
+        e = np.zeros(max(int(q), 1) if int(q) == q else 1)
+        e[0] = 1.0
+        super().__init__(q, e, dims=dims, L=L, l=l, J=J)
+
+
+class ClockModel(QStateModel):
+    """ClockModel(q; dims, L | l, J): e[d] = cos(2 pi d / q), E = -J sum_bonds cos(theta_i - theta_j) with
+    theta = 2 pi s / q (d <= q / 2 computed, the rest mirrored: exactly symmetric)"""
+
+    def __init__(self, q, dims=None, L=None, l=None, J=1.0):
+        n = max(int(q), 1) if int(q) == q else 1
+        e = np.zeros(n)
+        for d in range(n // 2 + 1):
+            e[d] = e[(n - d) % n] = math.cos(2.0 * math.pi * d / n)
+        super().__init__(q, e, dims=dims, L=L, l=l, J=J)
+
+
+_ISING_ONLY = "MC with a q-state model: %s is implemented for the IsingModel only (the q-state engine has local " \
+              "checkerboard sweeps; cluster moves, replica exchange, the device binner, FSS and the sequential sweep " \
+              "are out of scope)"
+
+
+class QStateMC:
+    """What MC(model; beta | T, ...) returns for a q-state model: `n_walkers` chains, one workgroup each, swept colour
+    class by colour class (`colouring=None`: greedy_colouring(lattice)) under the rule of include/dqmc_hip.h.  `beta`
+    may be a sequence of n_walkers values.  The Ising-only options (cluster_moves, n_replicas, exchange_rate, fss,
+    binning, update="sequential") raise NotImplementedError."""
+
+    def __init__(self, model, beta=None, T=None, n_walkers=1, seed=123, first_walker=0, thermalization=0, sweeps=1000,
+                 measure_rate=1, print_rate=1000, global_moves=False, global_rate=5, device_id=0, series_capacity=0,
+                 cluster_moves=False, binning=False, binning_capacity=None, n_replicas=0, exchange_rate=0,
+                 fss=False, update=None, colouring=None):
+        for name, on in (("global_moves", global_moves), ("cluster_moves", cluster_moves), ("binning", binning),
+                         ("n_replicas", n_replicas), ("exchange_rate", exchange_rate),
+                         ("fss", fss is not False and fss is not None),
+                         ('update="%s"' % update, update not in (None, "checkerboard"))):
+            if on:
+                raise NotImplementedError(_ISING_ONLY % name)
+        if (beta is None) == (T is None):
+            raise ValueError("MC needs exactly one of beta and T")
+        if T is not None:
+            beta = (1.0 / np.asarray(T, dtype=float)) if np.ndim(T) else 1.0 / float(T)
+        betas = np.broadcast_to(np.asarray(beta, dtype=float), (n_walkers,)).copy()
+        if not np.all(np.isfinite(betas)) or np.any(betas < 0):
+            raise ValueError("beta must be finite and >= 0")
+        if measure_rate < 1:
+            raise ValueError("measure_rate must be >= 1")
+        self.model = model
+        self.N = len(model.l)
+        self.q = model.q
+        self.n_walkers = n_walkers
+        self.betas = betas
+        self.beta = float(betas[0]) if np.all(betas == betas[0]) else betas
+        self.seeds = [seed + first_walker + w for w in range(n_walkers)]
+        self.thermalization, self.sweeps, self.measure_rate = thermalization, sweeps, measure_rate
+        self.print_rate = print_rate
+        self.last_sweep = 0
+        self.series_capacity = series_capacity
+        self.update = "checkerboard"
+        self._neighs = np.asfortranarray(np.asarray(model.l.neighs, dtype=np.int64))
+        self._bonds = np.asfortranarray(np.asarray(model.l.bonds, dtype=np.int64)[:, :2])
+        col, n_col = self._colouring(colouring)
+        self._tables = [np.ascontiguousarray(model.e_q30, dtype=np.int64), np.ascontiguousarray(model.c_q30, dtype=np.int32),
+                        np.ascontiguousarray(model.s_q30, dtype=np.int32)]
+        i32, i64 = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+        p = QsParams(n_sites=self.N, z=self._neighs.shape[0], q=self.q, n_walkers=n_walkers, device_id=device_id,
+                     n_bonds=self._bonds.shape[0], series_capacity=series_capacity, n_colours=n_col,
+                     neighs=self._neighs.ctypes.data_as(i64), bonds=self._bonds.ctypes.data_as(i64),
+                     e_q30=self._tables[0].ctypes.data_as(i64), c_q30=self._tables[1].ctypes.data_as(i32),
+                     s_q30=self._tables[2].ctypes.data_as(i32), colour=col.ctypes.data_as(i32))
+        h = C.c_void_p()
+        self._h = None
+        rc = lib().dqmc_qs_create(C.byref(p), C.byref(h))
+        if rc != 0:
+            msg = lib().dqmc_qs_last_error(None)
+            raise DQMCError(rc, msg.decode() if msg else "")
+        self._h = h
+        self.colouring = col
+        for w in range(n_walkers):
+            self._c(lib().dqmc_qs_seed(self._h, w, self.seeds[w]))
+            self._c(lib().dqmc_qs_set_beta(self._h, w, float(betas[w])))
+        self._c(lib().dqmc_qs_rand_conf(self._h, -1))
+
+    def _colouring(self, colouring):
+        col = greedy_colouring(self.model.l) if colouring is None else colouring
+        col = np.ascontiguousarray(np.asarray(col).reshape(-1), dtype=np.int32)
+        if col.size != self.N:
+            raise DQMCError(ERR_INVALID, "colouring: expected %d colours" % self.N)
+        return col, (int(col.max()) + 1 if col.size else 0)
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            lib().dqmc_qs_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _c(self, rc):
+        if rc != 0:
+            msg = lib().dqmc_qs_last_error(self._h)
+            raise DQMCError(rc, msg.decode() if msg else "")
+
+    # ---- state
+    def seed(self, walker, seed):
+        """key the walker's streams with `seed`, both cursors at 0 (the configuration stays)"""
+        self._c(lib().dqmc_qs_seed(self._h, walker, seed))
+        self.seeds[walker] = seed
+
+    def set_beta(self, walker, beta):
+        self._c(lib().dqmc_qs_set_beta(self._h, walker, float(beta)))
+        self.betas[walker] = float(beta)
+
+    def rand_conf(self, walker=-1):
+        self._c(lib().dqmc_qs_rand_conf(self._h, walker))
+
+    def conf(self, walker=0):
+        out = np.zeros(self.N, dtype=np.uint8)
+        self._c(lib().dqmc_qs_get_conf(self._h, walker, out.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return out
+
+    def set_conf(self, walker, conf):
+        c = np.asarray(conf).reshape(-1, order="F")
+        if c.size != self.N:
+            raise DQMCError(ERR_INVALID, "set_conf: expected %d states" % self.N)
+        if np.any(c < 0) or np.any(c >= self.q):
+            raise DQMCError(ERR_INVALID, "set_conf: the states must lie in 0..%d" % (self.q - 1))
+        c = np.ascontiguousarray(c, dtype=np.uint8)
+        self._c(lib().dqmc_qs_set_conf(self._h, walker, c.ctypes.data_as(C.POINTER(C.c_uint8))))
+
+    def set_colouring(self, colouring=None):
+        """dqmc_qs_set_colouring: another colouring from now on (None: greedy_colouring(lattice)); a colouring that is
+        refused leaves the handle as it was"""
+        col, n_col = self._colouring(colouring)
+        self._c(lib().dqmc_qs_set_colouring(self._h, col.ctypes.data_as(C.POINTER(C.c_int32)), n_col))
+        self.colouring = col
+
+    def stats(self, walker=0):
+        st = QsStats()
+        self._c(lib().dqmc_qs_get_stats(self._h, walker, C.byref(st)))
+        return st
+
+    def energy(self, walker=0):
+        """the walker's energy, tracked on the device as an exact integer in units of 2^-30"""
+        return self.stats(walker).energy_q30 / Q30
+
+    def order_parameter(self, walker=0):
+        """(Mx, My) = sum_i (cos, sin)(2 pi s_i / q) from the device's exact integers"""
+        st = self.stats(walker)
+        return st.mx_q30 / Q30, st.my_q30 / Q30
+
+    # ---- the loop
+    def sweep(self, n=1):
+        """n sweeps with run!'s measurement rule, continuing from last_sweep"""
+        if n > 0:
+            self._c(lib().dqmc_qs_sweep(self._h, n, self.last_sweep + 1, self.thermalization, self.measure_rate))
+            self.last_sweep += n
+
+    def run(self, verbose=False, sweeps=None, thermalization=None):
+        """run!(mc) for every walker, resuming after last_sweep"""
+        if sweeps is not None:
+            self.sweeps = sweeps
+        if thermalization is not None:
+            self.thermalization = thermalization
+        total = self.thermalization + self.sweeps
+        t0 = time.time()
+        while self.last_sweep < total:
+            stop = total
+            if verbose and self.print_rate:
+                stop = min(total, (self.last_sweep // self.print_rate + 1) * self.print_rate)
+            self.sweep(stop - self.last_sweep)
+            i = self.last_sweep
+            if verbose and self.print_rate and i % self.print_rate == 0:
+                st = self.stats(0)
+                print("\t%d\n\t\tsweep dur: %.3fs\n\t\tacc rate (local) : %.1f%%" %
+                      (i, (time.time() - t0) / self.print_rate, 100.0 * st.acc_local / max(st.prop_local, 1)))
+                t0 = time.time()
+        return True
+
+    def reset_accumulators(self):
+        self._c(lib().dqmc_qs_reset_accumulators(self._h))
+
+    def synchronize(self):
+        self._c(lib().dqmc_qs_synchronize(self._h))
+
+    # ---- results
+    def analysis(self, walker=0):
+        """MCAnalysis (MC.jl:1-11) of one walker"""
+        st = self.stats(walker)
+        return {"acc_rate": st.acc_local / st.prop_local if st.prop_local else 0.0, "prop_local": int(st.prop_local),
+                "acc_local": int(st.acc_local)}
+
+    def measurements(self, walker=0):
+        """{"Energy": {E, E2, e, C}, "Magn": {M, M2, M4, m, chi, U4}, "n_meas"}: means over the walker's measurements,
+        in units of J-scaled energy and of unit vectors (the 2^30 of the device's integers removed).  M = <|M|> with
+        |M| = sqrt(Mx^2 + My^2), m = M / N, C = beta^2 / N (<E2> - <E>^2), chi = beta N (<m^2> - <m>^2) =
+        beta / N (<M2> - <M>^2), and U4 = 1 - <M4> / (2 <M2>^2), the Binder cumulant of a two-component order parameter
+        (0 in the disordered phase, 1/2 in the ordered one).  For q = 2, My = 0."""
+        st = self.stats(walker)
+        n = st.n_meas
+        if n == 0:
+            raise DQMCError(ERR_INVALID, "measurements: no measurement has been taken")
+        beta, invN = float(self.betas[walker]), 1.0 / self.N
+        E, E2, M, M2, M4 = st.sum_E / n, st.sum_E2 / n, st.sum_absM / n, st.sum_M2 / n, st.sum_M4 / n
+        with np.errstate(invalid="ignore", divide="ignore"):
+            U4 = float(1.0 - np.float64(M4) / (2.0 * np.float64(M2) * np.float64(M2)))
+        return {"Magn": {"M": M, "M2": M2, "M4": M4, "m": M * invN, "chi": beta * invN * (M2 - M * M), "U4": U4},
+                "Energy": {"E": E, "E2": E2, "e": E * invN, "C": beta * beta * invN * (E2 - E * E)},
+                "n_meas": int(n)}
+
+    def series(self, walker=0):
+        """per-measurement (E_int, Mx, My) of the walker as recorded, exact int64 in units of 2^-30 (at most
+        series_capacity entries)"""
+        cap = max(self.series_capacity, 1)
+        e, mx, my = (np.zeros(cap, dtype=np.int64) for _ in range(3))
+        n = C.c_int64()
+        p = C.POINTER(C.c_int64)
+        self._c(lib().dqmc_qs_get_series(self._h, walker, e.ctypes.data_as(p), mx.ctypes.data_as(p), my.ctypes.data_as(p),
+                                         C.byref(n)))
+        return e[:n.value].copy(), mx[:n.value].copy(), my[:n.value].copy()
