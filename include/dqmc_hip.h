@@ -1309,6 +1309,37 @@ int dqmc_mc_fss_binner_finish(dqmc_mc_handle *h, int32_t walker, int32_t level, 
  * While fewer than series_capacity measurements are recorded, (E_int, Mx, My) is appended to the walker's series.
  * U4 = 1 - <M^4> / (2 <M^2>^2) is the Binder cumulant of a two-component order parameter (0 in the disordered phase).
  * The results do not depend on how a run is split into calls of dqmc_qs_sweep.
+ *
+ * Cluster move (dqmc_qs_set_cluster_rate, dqmc_qs_cluster_move).  A cluster move in Wolff's embedding: for a symmetric
+ * table the reflection s -> (r - s) mod q maps the difference d of a bond to -d when both ends are reflected, so it is a
+ * symmetry of every bond; reflecting one end takes the bond from difference a to difference b at the cost
+ * e[a] - e[b].  For Potts models this is the Wolff move (clusters of equal states, bond probability 1 - exp(-beta J)),
+ * for clock models Wolff's reflection restricted to the q lattice axes.  Domain word c2 = 6; m is the walker's move
+ * cursor, the cluster moves since dqmc_qs_seed (which sets it to 0): P(key; t, low32(m), 6, high32(m)) gives (u1, u2).
+ * The sweep and configuration streams are not touched.
+ *   seed        t = 0: i0 = min(N - 1, (int)fl(u1 N)), N = n_sites
+ *   reflection  r = (2 s_i0 + 1 + min(q - 2, (int)fl(u2 (q - 1)))) mod q: uniform over the q - 1 reflections that move
+ *               the seed's state, the flip for q = 2
+ *   slot (i, k) the directed slot of site i (0-based) and k < z uses t = 1 + 8 i + k and u1 only.  With j = neighs[k, i]
+ *               and the states as they stood before the move: a = (s_i - s_j) mod q, b = (r - s_i - s_j) mod q; the slot
+ *               is active iff e_q30[a] > e_q30[b] && u1 < fl(1.0 - w[a][b]), with the walker's table w
+ *   cluster     C = the sites reachable from i0 through active slots (i0 itself at least).  The set does not depend on
+ *               the order in which slots are examined; a slot is drawn only where it is needed, and the stream is
+ *               addressed by (m, i, k), not by position
+ *   move        s_i <- (r - s_i) mod q for every i in C
+ *   dE_int      = sum_{i in C} sum_k [neighs[k, i] not in C] (e_q30[a] - e_q30[b]) in int64: bonds inside C do not
+ *               change by the symmetry of e, a repeated neighbour counts twice as in the local rule, and on
+ *               TriangularLattice the running E stays "bonds energy of the start plus neighbour differences"
+ *   dMx, dMy    = sum_{i in C} (c_q30, s_q30)[new] - (c_q30, s_q30)[old]: integers, exact in any order
+ *   counters    prop_global += 1, acc_global += (|C| > 1), sum_cluster_size += |C|, moves_drawn = m + 1
+ * The move is never rejected.  With p = fl(1 - w[a][b]) = 1 - exp(-beta (e[a] - e[b])) up to the rounding of one table
+ * entry and one subtraction, the probability of growing C and not growing it across its boundary differs between a
+ * configuration and its image by the factor exp(-beta dE) to about one ulp per boundary slot: detailed balance for the
+ * Boltzmann weight of E_int 2^-30, to the accuracy the sweep has.  With cluster rate k > 0 the sweep with global index
+ * i runs one move per walker iff i % k == 0, in the order sweep i, its move, its measurement; rate 0 (the default)
+ * leaves every stream, sum and launch as without the feature.  The results do not depend on how a run is split into
+ * calls of dqmc_qs_sweep, nor on the number of walkers in the handle.
+ *
  * Limits: n_sites <= 16384, 1 <= z <= 8, 2 <= q <= 64, n_colours <= 16.  Errors come from dqmc_qs_last_error. */
 typedef struct dqmc_qs_handle dqmc_qs_handle;
 
@@ -1347,7 +1378,7 @@ int dqmc_qs_create(const dqmc_qs_params *p, dqmc_qs_handle **out);
 int dqmc_qs_destroy(dqmc_qs_handle *h);
 /* message of the last failing call on this handle (h may be NULL: create errors) */
 const char *dqmc_qs_last_error(const dqmc_qs_handle *h);
-/* the walker's stream: key = seed, both cursors at 0 (the configuration stays) */
+/* the walker's stream: key = seed, the cursors s, r and m at 0 (the configuration stays) */
 int dqmc_qs_seed(dqmc_qs_handle *h, int32_t walker, uint64_t seed);
 /* beta finite and >= 0: builds the walker's table w on the host */
 int dqmc_qs_set_beta(dqmc_qs_handle *h, int32_t walker, double beta);
@@ -1372,6 +1403,21 @@ int dqmc_qs_get_series(dqmc_qs_handle *h, int32_t walker, int64_t *energy_q30, i
 /* clear the measurement sums and series of every walker (prop_local, acc_local and the cursors stay) */
 int dqmc_qs_reset_accumulators(dqmc_qs_handle *h);
 int dqmc_qs_synchronize(dqmc_qs_handle *h);
+
+typedef struct {
+    int64_t prop_global, acc_global; /* cluster moves made, and those with |C| > 1 */
+    int64_t sum_cluster_size;        /* sum of |C| over the moves */
+    uint64_t moves_drawn;            /* the move cursor m */
+} dqmc_qs_cluster_stats;
+/* one cluster move per walker behind every sweep whose global index is a multiple of rate, before its measurement;
+ * rate >= 0 (else DQMC_ERR_INVALID), 0 = none (the default).  The first rate > 0 reserves the larger LDS of the sweep
+ * kernel with moves (DQMC_ERR_HIP and a message if the device refuses it; the rate then stays as it was). */
+int dqmc_qs_set_cluster_rate(dqmc_qs_handle *h, int32_t rate);
+/* one cluster move of the walker by hand, or of every walker (walker < 0), at its cursor m; E_int, Mx and My follow, no
+ * measurement is taken.  Works at any rate. */
+int dqmc_qs_cluster_move(dqmc_qs_handle *h, int32_t walker);
+/* (dqmc_qs_seed puts moves_drawn back to 0; dqmc_qs_reset_accumulators leaves all four alone, as it leaves prop_local) */
+int dqmc_qs_get_cluster_stats(dqmc_qs_handle *h, int32_t walker, dqmc_qs_cluster_stats *out);
 
 /* ---- the SAC flavor: stochastic analytic continuation -----------------------------------------------------------
  * A(omega) from imaginary-time data by sampling (Sandvik, PRB 57, 10287; Beach, cond-mat/0403055; Shao and Sandvik,

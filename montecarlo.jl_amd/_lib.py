@@ -120,6 +120,11 @@ class QsStats(C.Structure):
                 ("n_colours", C.c_int32)]
 
 
+class QsClusterStats(C.Structure):
+    _fields_ = [("prop_global", C.c_int64), ("acc_global", C.c_int64), ("sum_cluster_size", C.c_int64),
+                ("moves_drawn", C.c_uint64)]
+
+
 class SacParams(C.Structure):
     _fields_ = [("n_problems", C.c_int32), ("n_tau", C.c_int32), ("n_deltas", C.c_int32), ("n_omega", C.c_int32),
                 ("n_replicas", C.c_int32), ("device_id", C.c_int32), ("window", C.c_int32),
@@ -328,6 +333,9 @@ SIGNATURES = {
     "dqmc_qs_get_series": (C.c_int, [_H, C.c_int32, _i64p, _i64p, _i64p, _i64p]),
     "dqmc_qs_reset_accumulators": (C.c_int, [_H]),
     "dqmc_qs_synchronize": (C.c_int, [_H]),
+    "dqmc_qs_set_cluster_rate": (C.c_int, [_H, C.c_int32]),
+    "dqmc_qs_cluster_move": (C.c_int, [_H, C.c_int32]),
+    "dqmc_qs_get_cluster_stats": (C.c_int, [_H, C.c_int32, C.POINTER(QsClusterStats)]),
     "dqmc_sac_create": (C.c_int, [C.POINTER(SacParams), C.POINTER(_H)]),
     "dqmc_sac_destroy": (C.c_int, [_H]),
     "dqmc_sac_last_error": (C.c_char_p, [_H]),

@@ -12,6 +12,16 @@
 // dE_int, dMx, dMy (int64) and the accepted sites add up in registers and are reduced over the workgroup only where they
 // are needed: at a measurement and at the end of the launch.  Lane 0 keeps the walker's fp64 sums in registers for the
 // whole launch and adds every measurement in the header's order of operations (compiled with -ffp-contract=off).
+//
+// The cluster move (the header's "Cluster move") runs inside the sweep kernel's CLUSTER instantiation, on the bytes already
+// in LDS, behind the colour passes of a sweep whose index is a multiple of the rate and before its measurement.  Beside the
+// sites it keeps a cluster bitset (ceil(N / 32) words), one append-only queue of N 16-bit site indices and a few counters:
+// 4 ceil(N / 32) + 2 N + 32 bytes more, 83 KiB in all at q = 64 and N = 16384, reserved for that instantiation alone.  A
+// site enters the queue exactly once, by the old value of an LDS atomicOr on its bit, so the N entries hold all levels of
+// the breadth-first growth as consecutive ranges.  The slots of a level are spread over the workgroup, one barrier ends a
+// level, and the next level's range is read from LDS behind it.  One pass over the queue then adds the boundary terms to
+// the lane's dE, dMx, dMy (the sweep's own registers) and writes the reflected bytes.  The host launches the instantiation
+// without moves whenever the rate is 0.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -31,7 +41,7 @@ constexpr int MAX_Q = 64;
 constexpr int MAX_COLOURS = 16;
 constexpr int WAVE = 64;
 constexpr int THREADS = 256;
-constexpr unsigned int DOMAIN_SWEEP = 4u, DOMAIN_CONF = 5u;
+constexpr unsigned int DOMAIN_SWEEP = 4u, DOMAIN_CONF = 5u, DOMAIN_CLUSTER = 6u;
 constexpr double Q30_INV = 1.0 / 1073741824.0;
 // The work bound of a launch, in the terms of the Ising checkerboard path (ising.hip, CB_LAUNCH_BUDGET): a sweep counts as
 // N + 512 site visits, 512 walkers' workgroups run side by side, and a launch runs at most
@@ -50,6 +60,14 @@ struct DevState {
     double *sE, *sE2, *sM, *sM2, *sM4;
     long long *n_meas, *prop, *acc, *n_series;
     long long *ser;                    // [W][cap][3]
+};
+
+// what the cluster move adds to a handle: the site-ordered neighbour rows and the per-walker global counters
+struct ClusterArgs {
+    const int *nbr;                     // [N][8]: neighs[k, i] at 8 i + k, 0-based (shared by all walkers)
+    long long *prop, *acc, *sum_size;   // [W]
+    unsigned long long *cursor;         // [W]: the move cursor m
+    int rate;
 };
 
 // Philox4x32-10 as kernels.h philox4_uniform, with both uniforms of the output: (o0, o1) -> u1, (o2, o3) -> u2
@@ -83,13 +101,104 @@ __device__ __forceinline__ long long wave_sum(long long v)
 __device__ __forceinline__ int mod_q(int d, int q) { return d < 0 ? d + q : d; }  // d in (-q, q)
 
 static inline size_t sweep_lds_bytes(int q, int Nw) { return (size_t)8 * q * q + (size_t)16 * q + 32 + (size_t)4 * Nw; }
+// counters (8 words), bitset, queue: what the cluster move keeps behind the sites
+static inline size_t cluster_lds_bytes(int N) { return (size_t)32 + (size_t)4 * ((N + 31) / 32) + (size_t)2 * N; }
 
+// One cluster move of the workgroup's walker at move cursor m, on the sites st[] in LDS (the header's "Cluster move").
+// All lanes call it behind a barrier (st[] is at rest) and leave it behind one (st[] holds the reflected cluster).  The
+// lane's share of dE_int, dMx, dMy is added to dE, dMx, dMy; |C| is returned to every lane.  scratch: 8 counter words, the
+// bitset and the queue, in this order.  Any blockDim.x that is a multiple of the wave.
+__device__ __forceinline__ int qs_cluster_move_lds(unsigned char *st, const double *wt, const long long *et, const int2 *cs,
+                                                   unsigned int *scratch, const int *__restrict__ nbr, int N, int q, int z,
+                                                   unsigned long long key, unsigned long long m, long long &dE,
+                                                   long long &dMx, long long &dMy)
+{
+    const int tid = threadIdx.x, nt = blockDim.x;
+    unsigned int *cnt = scratch;                   // [3] used: sites appended by a level, in rotation
+    unsigned int *bits = scratch + 8;              // [ceil(N / 32)]
+    unsigned short *queue = (unsigned short *)(bits + (N + 31) / 32);  // [N]
+    const unsigned int m_lo = (unsigned int)m, m_hi = (unsigned int)(m >> 32);
+    int i0, r;
+    {  // every lane forms the seed and the reflection itself (uniform)
+        double u1, u2;
+        philox4_two(key, 0u, m_lo, DOMAIN_CLUSTER, m_hi, u1, u2);
+        i0 = min(N - 1, (int)(u1 * (double)N));
+        r = (2 * (int)st[i0] + 1 + min(q - 2, (int)(u2 * (double)(q - 1)))) % q;
+    }
+    for (int j = tid; j < (N + 31) / 32; j += nt) bits[j] = j == (i0 >> 5) ? 1u << (i0 & 31) : 0u;
+    if (tid == 0) {
+        queue[0] = (unsigned short)i0;
+        cnt[0] = 0u;
+        cnt[1] = 0u;
+        cnt[2] = 0u;
+    }
+    __syncthreads();
+    // level by level: queue[lo .. hi) is the last level, its slots append the next one behind hi.  A level counts its
+    // sites in cnt[lev]; the counter of the next level is cleared here, two barriers behind its last reader.
+    int lo = 0, hi = 1, lev = 0;
+    while (lo < hi) {  // (uniform: hi comes from LDS behind the barrier)
+        const int nxt = lev == 2 ? 0 : lev + 1;
+        if (tid == 0) cnt[nxt] = 0u;
+        const int n_slots = (hi - lo) * z;
+        for (int x = tid; x < n_slots; x += nt) {
+            const int e = x / z, k = x - e * z;
+            const int i = queue[lo + e];
+            const int j = nbr[8 * i + k];
+            const int si = st[i], sj = st[j];
+            const int a = mod_q(si - sj, q);
+            int b = r - si - sj;  // in (-2 q, q)
+            b = b < 0 ? b + q : b;
+            b = b < 0 ? b + q : b;
+            const unsigned int bit = 1u << (j & 31);
+            if (et[a] > et[b] && !(bits[j >> 5] & bit)) {
+                double u1, u2;
+                philox4_two(key, (unsigned int)(1 + 8 * i + k), m_lo, DOMAIN_CLUSTER, m_hi, u1, u2);
+                if (u1 < 1.0 - wt[a * q + b]) {
+                    if (!(atomicOr(&bits[j >> 5], bit) & bit)) queue[hi + (int)atomicAdd(&cnt[lev], 1u)] = (unsigned short)j;
+                }
+            }
+        }
+        __syncthreads();
+        lo = hi;
+        hi += (int)cnt[lev];
+        lev = nxt;
+    }
+    // one lane per cluster site.  st[j] is read only for j outside C, and those bytes do not change: no barrier between
+    // the reads and the writes.
+    for (int x = tid; x < hi; x += nt) {
+        const int i = queue[x];
+        const int si = st[i];
+        long long d = 0;
+        for (int k = 0; k < z; ++k) {
+            const int j = nbr[8 * i + k];
+            if (bits[j >> 5] >> (j & 31) & 1u) continue;
+            const int sj = st[j];
+            const int a = mod_q(si - sj, q);
+            int b = r - si - sj;
+            b = b < 0 ? b + q : b;
+            b = b < 0 ? b + q : b;
+            d += et[a] - et[b];
+        }
+        const int sn = mod_q(r - si, q);
+        const int2 co = cs[si], cn = cs[sn];
+        dE += d;
+        dMx += (long long)cn.x - co.x;
+        dMy += (long long)cn.y - co.y;
+        st[i] = (unsigned char)sn;
+    }
+    __syncthreads();
+    return hi;
+}
+
+// CLUSTER = false is the sweep without moves (ca is not read); CLUSTER = true runs the walker's cluster move behind the
+// colour passes of every sweep whose global index is a multiple of ca.rate (> 0)
+template <bool CLUSTER>
 __global__ __launch_bounds__(THREADS) void qs_sweep_kernel(DevState s, const int *__restrict__ site,
                                                            const int4 *__restrict__ rows, const int *__restrict__ off,
                                                            const long long *__restrict__ e_q30,
                                                            const int2 *__restrict__ cs_q30, int C, int n_sweeps,
                                                            long long first_sweep, long long thermalization,
-                                                           int measure_rate)
+                                                           int measure_rate, ClusterArgs ca)
 {
     extern __shared__ __align__(16) unsigned char lds[];
     const int tid = threadIdx.x, nt = blockDim.x, w = blockIdx.x;
@@ -136,6 +245,13 @@ __global__ __launch_bounds__(THREADS) void qs_sweep_kernel(DevState s, const int
     long long dE = 0, dMx = 0, dMy = 0;
     int acc = 0;
     const double qm1 = (double)(q - 1);
+    // (CLUSTER) the move cursor in every lane, the next sweep with a move, and lane 0's global counters
+    unsigned long long mc = 0ull;
+    long long next_move = 0, g_prop = 0, g_acc = 0, g_size = 0;
+    if constexpr (CLUSTER) {
+        mc = ca.cursor[w];
+        next_move = (first_sweep + ca.rate - 1) / ca.rate * ca.rate;
+    }
     __syncthreads();
 
     for (int sw = 0; sw < n_sweeps; ++sw, ++sc) {
@@ -173,6 +289,17 @@ __global__ __launch_bounds__(THREADS) void qs_sweep_kernel(DevState s, const int
             __syncthreads();
         }
         const long long g = first_sweep + sw;  // global 1-based sweep index
+        if constexpr (CLUSTER) {
+            if (g == next_move) {  // (uniform)
+                next_move += ca.rate;
+                const int size = qs_cluster_move_lds(st, wt, et, cs, (unsigned int *)(st + 4 * Nw), ca.nbr, N, q, z, key, mc,
+                                                     dE, dMx, dMy);
+                ++mc;
+                g_prop += 1;
+                g_acc += size > 1;
+                g_size += size;
+            }
+        }
         if (g != next) continue;               // (uniform)
         next += measure_rate;
         const long long e = wave_sum(dE), mx = wave_sum(dMx), my = wave_sum(dMy);
@@ -234,6 +361,69 @@ __global__ __launch_bounds__(THREADS) void qs_sweep_kernel(DevState s, const int
         s.sM4[w] = sM4;
         s.n_meas[w] = n_meas;
         s.n_series[w] = n_series;
+        if constexpr (CLUSTER) {
+            ca.prop[w] += g_prop;
+            ca.acc[w] += g_acc;
+            ca.sum_size[w] += g_size;
+            ca.cursor[w] = mc;
+        }
+    }
+}
+
+// dqmc_qs_cluster_move: one move of one walker (walker >= 0) or of every walker, with the sweep kernel's LDS layout
+__global__ __launch_bounds__(THREADS) void qs_cluster_move_kernel(DevState s, const long long *__restrict__ e_q30,
+                                                                  const int2 *__restrict__ cs_q30, ClusterArgs ca,
+                                                                  int walker)
+{
+    extern __shared__ __align__(16) unsigned char lds[];
+    const int w = walker >= 0 ? walker : (int)blockIdx.x;
+    if (w >= s.W) return;  // (uniform)
+    const int tid = threadIdx.x, nt = blockDim.x;
+    const int N = s.N, Nw = s.Nw, q = s.q, z = s.z;
+    double *wt = (double *)lds;
+    long long *et = (long long *)(wt + q * q);
+    int2 *cs = (int2 *)(et + q);
+    unsigned long long *red = (unsigned long long *)(cs + q);
+    unsigned char *st = (unsigned char *)(red + 4);
+    {
+        unsigned int *stw = (unsigned int *)st;
+        const unsigned int *src = s.conf + (size_t)w * Nw;
+        for (int j = tid; j < Nw; j += nt) stw[j] = src[j];
+        const double *wsrc = s.wt + (size_t)w * q * q;
+        for (int j = tid; j < q * q; j += nt) wt[j] = wsrc[j];
+        for (int j = tid; j < q; j += nt) {
+            et[j] = e_q30[j];
+            cs[j] = cs_q30[j];
+        }
+        if (tid < 3) red[tid] = 0ull;
+    }
+    const unsigned long long m = ca.cursor[w];
+    __syncthreads();
+    long long dE = 0, dMx = 0, dMy = 0;
+    const int size = qs_cluster_move_lds(st, wt, et, cs, (unsigned int *)(st + 4 * Nw), ca.nbr, N, q, z, s.key[w], m, dE, dMx,
+                                         dMy);
+    {
+        const long long e = wave_sum(dE), mx = wave_sum(dMx), my = wave_sum(dMy);
+        if ((tid & (WAVE - 1)) == 0) {
+            atomicAdd(&red[0], (unsigned long long)e);
+            atomicAdd(&red[1], (unsigned long long)mx);
+            atomicAdd(&red[2], (unsigned long long)my);
+        }
+    }
+    __syncthreads();
+    {
+        const unsigned int *stw = (const unsigned int *)st;
+        unsigned int *dst = s.conf + (size_t)w * Nw;
+        for (int j = tid; j < Nw; j += nt) dst[j] = stw[j];
+    }
+    if (tid == 0) {
+        s.E[w] += (long long)red[0];
+        s.Mx[w] += (long long)red[1];
+        s.My[w] += (long long)red[2];
+        ca.prop[w] += 1;
+        ca.acc[w] += size > 1;
+        ca.sum_size[w] += size;
+        ca.cursor[w] = m + 1;
     }
 }
 
@@ -305,6 +495,9 @@ struct dqmc_qs_handle {
     long long *e_q30 = nullptr;         // [q]
     int2 *cs_q30 = nullptr;             // [q]
     unsigned long long *confs = nullptr;  // [W], the device image of confs_h for qs_rand_conf_kernel
+    ClusterArgs ca{};                   // rate 0: no moves inside dqmc_qs_sweep
+    int *nbr_site = nullptr;            // [N][8], what ca.nbr points to
+    bool cluster_lds_reserved = false;  // the kernels with a move may ask for more than 64 KiB of dynamic LDS
     std::vector<void *> allocs;
     std::string err;
 };
@@ -411,6 +604,25 @@ static int qs_put_colouring(dqmc_qs_handle *h, const std::vector<int> &site, con
     QCHK(hipStreamSynchronize(h->stream));  // (the vectors are the caller's: copied before it returns)
     h->C = nc;
     h->threads = std::min(THREADS, std::max(WAVE, (largest + WAVE - 1) / WAVE * WAVE));
+    return 0;
+}
+
+// the dynamic LDS of the kernels with a cluster move, 83 KiB at q = 64 and N = 16384: above the 64 KiB a kernel gets
+// without asking, below the 160 KiB of a CU.  Reserved once per handle, for those kernels only, and always at the
+// engine's limits: the attribute belongs to the kernel, not to the handle, and a smaller handle must not lower it.
+static int qs_reserve_cluster_lds(dqmc_qs_handle *h, const char *fn)
+{
+    if (h->cluster_lds_reserved) return 0;
+    const size_t lds = sweep_lds_bytes(MAX_Q, MAX_SITES / 4) + cluster_lds_bytes(MAX_SITES);
+    if (hipFuncSetAttribute((const void *)qs_sweep_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
+            hipSuccess ||
+        hipFuncSetAttribute((const void *)qs_cluster_move_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
+            hipSuccess) {
+        (void)hipGetLastError();
+        return qs_fail(h, DQMC_ERR_HIP, std::string(fn) + ": cannot reserve " + std::to_string(lds) +
+                                            " bytes of LDS for the cluster-move kernels");
+    }
+    h->cluster_lds_reserved = true;
     return 0;
 }
 
@@ -521,10 +733,19 @@ int dqmc_qs_create(const dqmc_qs_params *p, dqmc_qs_handle **out)
         (rc = qs_alloc(h, &d.ser, (size_t)3 * h->cap * W)) || (rc = qs_alloc(h, &h->site, (size_t)N)) ||
         (rc = qs_alloc(h, &h->rows, (size_t)N * MAX_Z)) || (rc = qs_alloc(h, &h->off, (size_t)MAX_COLOURS + 1)) ||
         (rc = qs_alloc(h, &h->bonds, bonds_h.size())) || (rc = qs_alloc(h, &h->e_q30, (size_t)q)) ||
-        (rc = qs_alloc(h, &h->cs_q30, (size_t)q)) || (rc = qs_alloc(h, &h->confs, W)))
+        (rc = qs_alloc(h, &h->cs_q30, (size_t)q)) || (rc = qs_alloc(h, &h->confs, W)) ||
+        (rc = qs_alloc(h, &h->nbr_site, (size_t)N * MAX_Z)) || (rc = qs_alloc(h, &h->ca.prop, W)) ||
+        (rc = qs_alloc(h, &h->ca.acc, W)) || (rc = qs_alloc(h, &h->ca.sum_size, W)) ||
+        (rc = qs_alloc(h, &h->ca.cursor, W)))
         return bail(rc);
+    h->ca.nbr = h->nbr_site;
+    h->ca.rate = 0;
+    std::vector<int> nbr_site((size_t)N * MAX_Z, 0);
+    for (int i = 0; i < N; ++i)
+        for (int k = 0; k < z; ++k) nbr_site[(size_t)i * MAX_Z + k] = nbr[(size_t)i * z + k];
     std::vector<double> ones((size_t)q * q * W, 1.0);  // beta = 0
     if (hipMemcpyAsync(d.wt, ones.data(), ones.size() * 8, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
+        hipMemcpyAsync(h->nbr_site, nbr_site.data(), nbr_site.size() * 4, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
         (nb && hipMemcpyAsync(h->bonds, bonds_h.data(), bonds_h.size() * 4, hipMemcpyHostToDevice, h->stream) !=
                    hipSuccess) ||
         hipMemcpyAsync(h->e_q30, h->e_h.data(), (size_t)q * 8, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
@@ -558,6 +779,7 @@ int dqmc_qs_seed(dqmc_qs_handle *h, int32_t walker, uint64_t seed)
     QCHK(hipSetDevice(h->device));
     if (int rc = qs_put<unsigned long long>(h, h->d.key, walker, seed)) return rc;
     h->confs_h[walker] = 0ull;
+    if (int rc = qs_put<unsigned long long>(h, h->ca.cursor, walker, 0ull)) return rc;
     return qs_put<unsigned long long>(h, h->d.cursor, walker, 0ull);
 }
 
@@ -651,10 +873,16 @@ int dqmc_qs_sweep(dqmc_qs_handle *h, int32_t n_sweeps, int64_t first_sweep_index
     const size_t lds = sweep_lds_bytes(h->q, h->Nw);
     for (int done = 0; done < n_sweeps;) {
         const int n = std::min(chunk, n_sweeps - done);
-        hipLaunchKernelGGL(qs_sweep_kernel, dim3(h->W), dim3(h->threads), lds, h->stream, h->d, (const int *)h->site,
-                           (const int4 *)h->rows, (const int *)h->off, (const long long *)h->e_q30,
-                           (const int2 *)h->cs_q30, h->C, n, (long long)(first_sweep_index + done),
-                           (long long)thermalization, (int)measure_rate);
+        if (h->ca.rate > 0)
+            hipLaunchKernelGGL(qs_sweep_kernel<true>, dim3(h->W), dim3(h->threads), lds + cluster_lds_bytes(h->N), h->stream,
+                               h->d, (const int *)h->site, (const int4 *)h->rows, (const int *)h->off,
+                               (const long long *)h->e_q30, (const int2 *)h->cs_q30, h->C, n,
+                               (long long)(first_sweep_index + done), (long long)thermalization, (int)measure_rate, h->ca);
+        else
+            hipLaunchKernelGGL(qs_sweep_kernel<false>, dim3(h->W), dim3(h->threads), lds, h->stream, h->d,
+                               (const int *)h->site, (const int4 *)h->rows, (const int *)h->off,
+                               (const long long *)h->e_q30, (const int2 *)h->cs_q30, h->C, n,
+                               (long long)(first_sweep_index + done), (long long)thermalization, (int)measure_rate, h->ca);
         QCHK(hipGetLastError());
         done += n;
     }
@@ -722,6 +950,50 @@ int dqmc_qs_reset_accumulators(dqmc_qs_handle *h)
     for (double *p : {d.sE, d.sE2, d.sM, d.sM2, d.sM4}) QCHK(hipMemsetAsync(p, 0, W * 8, h->stream));
     for (long long *p : {d.n_meas, d.n_series}) QCHK(hipMemsetAsync(p, 0, W * 8, h->stream));
     QCHK(hipStreamSynchronize(h->stream));
+    return DQMC_OK;
+}
+
+int dqmc_qs_set_cluster_rate(dqmc_qs_handle *h, int32_t rate)
+{
+    if (!h) return qs_fail(nullptr, DQMC_ERR_INVALID, "dqmc_qs_set_cluster_rate: null handle");
+    if (rate < 0) return qs_fail(h, DQMC_ERR_INVALID, "dqmc_qs_set_cluster_rate: rate must be >= 0");
+    if (rate > 0) {
+        QCHK(hipSetDevice(h->device));
+        if (int rc = qs_reserve_cluster_lds(h, "dqmc_qs_set_cluster_rate")) return rc;
+    }
+    h->ca.rate = rate;
+    return DQMC_OK;
+}
+
+int dqmc_qs_cluster_move(dqmc_qs_handle *h, int32_t walker)
+{
+    if (!h) return qs_fail(nullptr, DQMC_ERR_INVALID, "dqmc_qs_cluster_move: null handle");
+    if (walker >= h->W) return qs_fail(h, DQMC_ERR_INVALID, "dqmc_qs_cluster_move: walker out of range");
+    QCHK(hipSetDevice(h->device));
+    if (int rc = qs_reserve_cluster_lds(h, "dqmc_qs_cluster_move")) return rc;
+    const size_t lds = sweep_lds_bytes(h->q, h->Nw) + cluster_lds_bytes(h->N);
+    hipLaunchKernelGGL(qs_cluster_move_kernel, dim3(walker >= 0 ? 1 : h->W), dim3(h->threads), lds, h->stream, h->d,
+                       (const long long *)h->e_q30, (const int2 *)h->cs_q30, h->ca, (int)walker);
+    QCHK(hipGetLastError());
+    QCHK(hipStreamSynchronize(h->stream));
+    return DQMC_OK;
+}
+
+int dqmc_qs_get_cluster_stats(dqmc_qs_handle *h, int32_t walker, dqmc_qs_cluster_stats *out)
+{
+    if (int rc = qs_walker(h, walker, "dqmc_qs_get_cluster_stats")) return rc;
+    if (!out) return qs_fail(h, DQMC_ERR_INVALID, "dqmc_qs_get_cluster_stats: null out");
+    QCHK(hipSetDevice(h->device));
+    long long prop = 0, acc = 0, size = 0;
+    unsigned long long m = 0;
+    int rc = 0;
+    if ((rc = qs_get(h, h->ca.prop, walker, &prop)) || (rc = qs_get(h, h->ca.acc, walker, &acc)) ||
+        (rc = qs_get(h, h->ca.sum_size, walker, &size)) || (rc = qs_get(h, h->ca.cursor, walker, &m)))
+        return rc;
+    out->prop_global = prop;
+    out->acc_global = acc;
+    out->sum_cluster_size = size;
+    out->moves_drawn = m;
     return DQMC_OK;
 }
 

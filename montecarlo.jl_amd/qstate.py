@@ -12,7 +12,7 @@ import time
 
 import numpy as np
 
-from ._lib import DQMCError, ERR_INVALID, QsParams, QsStats, lib
+from ._lib import DQMCError, ERR_INVALID, QsClusterStats, QsParams, QsStats, lib
 from .mc import _choose_lattice, _llround, greedy_colouring
 
 Q_MAX = 64
@@ -117,20 +117,23 @@ class ClockModel(QStateModel):
 
 
 _ISING_ONLY = "MC with a q-state model: %s is implemented for the IsingModel only (the q-state engine has local " \
-              "checkerboard sweeps; cluster moves, replica exchange, the device binner, FSS and the sequential sweep " \
-              "are out of scope)"
+              "checkerboard sweeps and its own reflection cluster moves, cluster_rate=k; replica exchange, the device " \
+              "binner, FSS and the sequential sweep are out of scope)"
 
 
 class QStateMC:
     """What MC(model; beta | T, ...) returns for a q-state model: `n_walkers` chains, one workgroup each, swept colour
     class by colour class (`colouring=None`: greedy_colouring(lattice)) under the rule of include/dqmc_hip.h.  `beta`
-    may be a sequence of n_walkers values.  The Ising-only options (cluster_moves, n_replicas, exchange_rate, fss,
-    binning, update="sequential") raise NotImplementedError."""
+    may be a sequence of n_walkers values.  `cluster_rate=k > 0` runs one reflection cluster move per walker behind every
+    sweep whose index is a multiple of k, before its measurement (the header's "Cluster move": the Wolff move for Potts
+    models, Wolff's reflection along the q lattice axes for clock models); 0, the default, runs none.  The Ising-only
+    options (cluster_moves, global_moves, n_replicas, exchange_rate, fss, binning, update="sequential") raise
+    NotImplementedError."""
 
     def __init__(self, model, beta=None, T=None, n_walkers=1, seed=123, first_walker=0, thermalization=0, sweeps=1000,
                  measure_rate=1, print_rate=1000, global_moves=False, global_rate=5, device_id=0, series_capacity=0,
                  cluster_moves=False, binning=False, binning_capacity=None, n_replicas=0, exchange_rate=0,
-                 fss=False, update=None, colouring=None):
+                 fss=False, update=None, colouring=None, cluster_rate=0):
         for name, on in (("global_moves", global_moves), ("cluster_moves", cluster_moves), ("binning", binning),
                          ("n_replicas", n_replicas), ("exchange_rate", exchange_rate),
                          ("fss", fss is not False and fss is not None),
@@ -146,6 +149,7 @@ class QStateMC:
             raise ValueError("beta must be finite and >= 0")
         if measure_rate < 1:
             raise ValueError("measure_rate must be >= 1")
+        cluster_rate = self._cluster_rate(cluster_rate)
         self.model = model
         self.N = len(model.l)
         self.q = model.q
@@ -181,6 +185,15 @@ class QStateMC:
             self._c(lib().dqmc_qs_seed(self._h, w, self.seeds[w]))
             self._c(lib().dqmc_qs_set_beta(self._h, w, float(betas[w])))
         self._c(lib().dqmc_qs_rand_conf(self._h, -1))
+        self.cluster_rate = 0
+        if cluster_rate:
+            self.set_cluster_rate(cluster_rate)
+
+    @staticmethod
+    def _cluster_rate(k):
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 0:
+            raise ValueError("cluster_rate must be an integer >= 0, got %r" % (k,))
+        return int(k)
 
     def _colouring(self, colouring):
         col = greedy_colouring(self.model.l) if colouring is None else colouring
@@ -239,6 +252,23 @@ class QStateMC:
         self._c(lib().dqmc_qs_set_colouring(self._h, col.ctypes.data_as(C.POINTER(C.c_int32)), n_col))
         self.colouring = col
 
+    def set_cluster_rate(self, k):
+        """dqmc_qs_set_cluster_rate: from now on one cluster move per walker behind every sweep whose index is a multiple
+        of k, before its measurement; 0 = none"""
+        k = self._cluster_rate(k)
+        self._c(lib().dqmc_qs_set_cluster_rate(self._h, k))
+        self.cluster_rate = k
+
+    def cluster_move(self, walker=-1):
+        """one cluster move of the walker by hand, or of every walker (-1); no measurement is taken"""
+        self._c(lib().dqmc_qs_cluster_move(self._h, walker))
+
+    def cluster_stats(self, walker=0):
+        """prop_global, acc_global (moves with |C| > 1), sum_cluster_size and moves_drawn (the move cursor)"""
+        st = QsClusterStats()
+        self._c(lib().dqmc_qs_get_cluster_stats(self._h, walker, C.byref(st)))
+        return st
+
     def stats(self, walker=0):
         st = QsStats()
         self._c(lib().dqmc_qs_get_stats(self._h, walker, C.byref(st)))
@@ -290,9 +320,9 @@ class QStateMC:
     # ---- results
     def analysis(self, walker=0):
         """MCAnalysis (MC.jl:1-11) of one walker"""
-        st = self.stats(walker)
+        st, cl = self.stats(walker), self.cluster_stats(walker)
         return {"acc_rate": st.acc_local / st.prop_local if st.prop_local else 0.0, "prop_local": int(st.prop_local),
-                "acc_local": int(st.acc_local)}
+                "acc_local": int(st.acc_local), "prop_global": int(cl.prop_global), "acc_global": int(cl.acc_global)}
 
     def measurements(self, walker=0):
         """{"Energy": {E, E2, e, C}, "Magn": {M, M2, M4, m, chi, U4}, "n_meas"}: means over the walker's measurements,

@@ -2,12 +2,14 @@
 """Site updates per second of the q-state (Potts, clock) engine on the device, beside the numpy restatement of
 tests/qstate_ref.py on one host core and, for q = 2, beside the Ising checkerboard kernel at the same size.
 
-    python tools/time_qstate.py [--out FILE.json] [--quick]
+    python tools/time_qstate.py [--out FILE.json] [--quick] [--cluster-rate K]
 
 Cases: Potts q = 3, clock q = 8 and Potts q = 2 on SquareLattice(L), L = 32 and 128, with 64 and 1024 walkers, at
 beta = 1.0, every tenth sweep measured.  A device time is the host clock around sweep() calls that end in a device
 synchronise, after a warm-up of the same shape; the best of three windows is reported.  The restatement runs 8 walkers
-(its time per site update does not depend on the count beyond that) for a few sweeps.  Prints one JSON line per case."""
+(its time per site update does not depend on the count beyond that) for a few sweeps.  With --cluster-rate K > 0 the device
+runs one cluster move per walker behind every K-th sweep (the sweeps then cost more than their site updates; the
+restatement column stays the local sweep's).  Prints one JSON line per case."""
 import argparse
 import json
 import os
@@ -36,6 +38,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--quick", action="store_true", help="small sweep counts (a rehearsal, not a measurement)")
+    ap.add_argument("--cluster-rate", type=int, default=0, help="a cluster move behind every K-th sweep (0: none)")
     args = ap.parse_args()
     g = entry.load_package()
     if g.device_count() < 1:
@@ -59,12 +62,15 @@ def main():
                 target = 5e7 * W if not args.quick else 2e6  # site updates per window: a few tenths of a second
                 sweeps = max(10, int(target / (N * W)) // 10 * 10)
                 model = g.PottsModel(q, l=l) if kind == "potts" else g.ClockModel(q, l=l)
-                mc = g.MC(model, beta=beta, n_walkers=W, seed=1, measure_rate=rate)
+                extra = {"cluster_rate": args.cluster_rate} if args.cluster_rate else {}
+                mc = g.MC(model, beta=beta, n_walkers=W, seed=1, measure_rate=rate, **extra)
                 dt = timed(mc, sweeps)
                 acc = mc.analysis(0)["acc_rate"]
                 mc.close()
                 r = {"model": kind, "q": q, "L": L, "walkers": W, "sweeps": sweeps, "seconds": dt,
                      "site_updates_per_s": N * W * sweeps / dt, "acc_rate": acc, "host_site_updates_per_s": host_rate}
+                if args.cluster_rate:
+                    r["cluster_rate"] = args.cluster_rate
                 if q == 2:  # the yardstick: the Ising checkerboard kernel at the same L and walker count
                     im = g.MC(g.IsingModel(l=l), beta=beta / 2.0, n_walkers=W, seed=1, measure_rate=rate,
                               update="checkerboard")  # (the same physics: J_potts = 2 J_ising)
