@@ -69,6 +69,7 @@
 
 #include "../../include/dqmc_hip.h"
 #include "kernels.h"
+#include "mc_host.h"
 
 namespace dqmc_mc {
 
@@ -458,9 +459,11 @@ constexpr double CB_RESIDENT_WALKERS = 512.0;
 }  // namespace dqmc_mc
 
 using namespace dqmc_mc;
+static_assert(MAX_Z == mc_tables::ROW && CB_MAX_COLOURS == mc_tables::MAX_COLOURS && WAVE == mc_tables::WAVE,
+              "the kernels read the tables mc_tables.h lays out");
 
-struct dqmc_mc_handle {
-    int N = 0, z = 0, W = 0, nw = 0, cap = 0, n_bonds = 0, device = 0;
+struct dqmc_mc_handle : mc_handle_base {
+    int N = 0, z = 0, nw = 0, cap = 0, n_bonds = 0;
     int global_rate = 0;       // mc.p.global_rate when global moves are on, 0 = off
     struct Tempering {         // replica exchange (dqmc_mc_set_exchange); R = 0: no ladders
         int R = 0, rate = 0, J = 0;
@@ -473,25 +476,19 @@ struct dqmc_mc_handle {
     std::vector<double> beta_h;  // [W], as dqmc_mc_set_beta got them
     std::vector<int> nbr_h;    // [N][z] 0-based
     std::vector<int> bonds_h;  // [n_bonds][2] 0-based
-    hipStream_t stream = nullptr;
     DevState d{};
-    std::vector<void *> allocs;
-    std::string err;
-    struct Binner {  // ising_bin_push: count[level] = T >> level for every walker, so no count lives on the device
+    struct Binner : mc_bin_section {  // ising_bin_push: elements [E, E2, |M|, M2], pairs (E, E2) and (|M|, M2)
         bool on = false;
-        int L = 0;
-        int64_t cap = 0, T = 0;
-        double *xs = nullptr, *x2 = nullptr, *xy = nullptr, *c = nullptr;  // [L][4][W], [L][4][W], [L][2][W], [L - 1][4][W]
+        int64_t cap = 0;
     } bin;
     struct Fss {  // dqmc_mc_set_fss; n_k = -1: off
         int n_k = -1;
         int *cq = nullptr, *sq = nullptr;         // [n_k][32 nw]: rows padded with zeros to whole spin words
         double *sM4 = nullptr, *sS = nullptr;     // [W], [8][W] (allocated when FSS is first switched on)
         long long *n_meas = nullptr;              // [W]
-        // the FSS section of the binner (there iff bin.on && n_k >= 0; L and cap are bin's): [L][2 + n_k][W] twice,
-        // [L][1 + n_k][W], [L - 1][1 + n_k][2][W]; T = its pushes
-        double *xs = nullptr, *x2 = nullptr, *xy = nullptr, *c = nullptr;
-        int64_t T = 0;
+        // the FSS section of the binner (there iff bin.on && n_k >= 0; its levels and capacity are bin's): elements
+        // [M2, M4, S_0 ..], pairs (M2, M4), (M2, S_k), a compressor value per member of a pair
+        mc_bin_section bin;
     } fss;
     struct Update {  // dqmc_mc_set_update
         int kind = DQMC_MC_UPDATE_SEQUENTIAL, C = 0, threads = CB_THREADS;
@@ -499,56 +496,6 @@ struct dqmc_mc_handle {
         unsigned long long *cursor = nullptr;                  // [W], allocated with the handle (dqmc_mc_seed zeroes it)
     } upd;
 };
-
-static thread_local std::string g_mc_create_error;
-
-static int mc_fail(dqmc_mc_handle *h, int code, const std::string &msg)
-{
-    if (h) h->err = msg;
-    else g_mc_create_error = msg;
-    return code;
-}
-
-#define MCHK(expr)                                                                          \
-    do {                                                                                    \
-        hipError_t e_ = (expr);                                                             \
-        if (e_ != hipSuccess) return mc_fail(h, DQMC_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-template <typename T>
-static int mc_alloc(dqmc_mc_handle *h, T **p, size_t count)
-{
-    void *q = nullptr;
-    MCHK(hipMalloc(&q, (count ? count : 1) * sizeof(T)));
-    h->allocs.push_back(q);
-    MCHK(hipMemsetAsync(q, 0, (count ? count : 1) * sizeof(T), h->stream));
-    *p = (T *)q;
-    return 0;
-}
-
-static int mc_walker(dqmc_mc_handle *h, int32_t w, const char *fn)
-{
-    if (!h) return mc_fail(nullptr, DQMC_ERR_INVALID, std::string(fn) + ": null handle");
-    if (w < 0 || w >= h->W) return mc_fail(h, DQMC_ERR_INVALID, std::string(fn) + ": walker out of range");
-    return 0;
-}
-
-// one element of a [row][W] device array
-template <typename T>
-static int mc_put(dqmc_mc_handle *h, T *base, int row, int w, T v)
-{
-    MCHK(hipMemcpyAsync(base + (size_t)row * h->W + w, &v, sizeof(T), hipMemcpyHostToDevice, h->stream));
-    MCHK(hipStreamSynchronize(h->stream));
-    return 0;
-}
-
-template <typename T>
-static int mc_get(dqmc_mc_handle *h, const T *base, int row, int w, T *v)
-{
-    MCHK(hipMemcpyAsync(v, base + (size_t)row * h->W + w, sizeof(T), hipMemcpyDeviceToHost, h->stream));
-    MCHK(hipStreamSynchronize(h->stream));
-    return 0;
-}
 
 static int mc_launch_observables(dqmc_mc_handle *h, int walker)
 {
@@ -604,19 +551,12 @@ static int mc_put_pair_table(dqmc_mc_handle *h, int a)
 
 static const int64_t MC_BIN_DEFAULT_CAPACITY = 100000;  // BinningAnalysis' _default_capacity
 
-static void mc_bin_free(dqmc_mc_handle *h)
+static void mc_bin_free(dqmc_mc_handle *h)  // both sections; the binner is off afterwards
 {
-    dqmc_mc_handle::Binner &b = h->bin;
-    for (double **p : {&b.xs, &b.x2, &b.xy, &b.c}) {
-        if (!*p) continue;
-        for (size_t i = 0; i < h->allocs.size(); ++i)
-            if (h->allocs[i] == (void *)*p) {
-                h->allocs.erase(h->allocs.begin() + i);
-                break;
-            }
-        (void)hipFree(*p);
-    }
-    b = dqmc_mc_handle::Binner{};
+    h->fss.bin.free(h);
+    h->bin.free(h);
+    h->bin.on = false;
+    h->bin.cap = 0;
 }
 
 // the push of the measurement ising_wolff_kernel has just taken
@@ -624,8 +564,7 @@ static int mc_launch_bin_push(dqmc_mc_handle *h)
 {
     dqmc_mc_handle::Binner &b = h->bin;
     int lmax = 0;
-    while ((b.T >> lmax) & 1) ++lmax;
-    if (lmax >= b.L) return mc_fail(h, DQMC_ERR_STATE, "dqmc_mc_sweep: binner capacity exhausted");
+    if (int rc = b.next_lmax(h, "dqmc_mc_sweep", &lmax)) return rc;
     hipLaunchKernelGGL(ising_bin_push_kernel, dim3((h->W + WAVE - 1) / WAVE), dim3(WAVE), 0, h->stream,
                        (const int *)h->d.E, (const int *)h->d.M, h->W, lmax, b.L - 1, b.xs, b.x2, b.xy, b.c);
     MCHK(hipGetLastError());
@@ -633,80 +572,20 @@ static int mc_launch_bin_push(dqmc_mc_handle *h)
     return 0;
 }
 
-// measurements of run! (MC.jl:262-283) among the sweeps first..last: i > thermalization && i % rate == 0
-static int64_t mc_measurements_in(int64_t first, int64_t last, int64_t thermalization, int64_t rate)
-{
-    const int64_t lo = std::max<int64_t>(first - 1, thermalization);  // (first >= 1)
-    return last > lo ? last / rate - lo / rate : 0;
-}
-
 #define MC_BIN_OK(h, fn)                                                                              \
     if (!(h)) return mc_fail(nullptr, DQMC_ERR_INVALID, std::string(fn) + ": null handle");          \
     if (!(h)->bin.on) return mc_fail((h), DQMC_ERR_STATE, std::string(fn) + ": the binner is not enabled")
 
-// x_sum, x2_sum (4 each) and xy_sum (2) of one level of one walker
-static int mc_bin_level(dqmc_mc_handle *h, int walker, int level, double *xs, double *x2, double *xy)
-{
-    const dqmc_mc_handle::Binner &b = h->bin;
-    const size_t W = h->W, pitch = W * sizeof(double);
-    MCHK(hipSetDevice(h->device));
-    if (xs)
-        MCHK(hipMemcpy2DAsync(xs, 8, b.xs + (size_t)level * 4 * W + walker, pitch, 8, 4, hipMemcpyDeviceToHost, h->stream));
-    if (x2)
-        MCHK(hipMemcpy2DAsync(x2, 8, b.x2 + (size_t)level * 4 * W + walker, pitch, 8, 4, hipMemcpyDeviceToHost, h->stream));
-    if (xy)
-        MCHK(hipMemcpy2DAsync(xy, 8, b.xy + (size_t)level * 2 * W + walker, pitch, 8, 2, hipMemcpyDeviceToHost, h->stream));
-    MCHK(hipStreamSynchronize(h->stream));
-    return 0;
-}
-
-static int mc_bin_reliable(const dqmc_mc_handle::Binner &b)  // the last level with count >= 32, else 0
-{
-    int lv = 0;
-    for (int l = 0; l < b.L; ++l)
-        if ((b.T >> l) >= 32) lv = l;
-    return lv;
-}
-
 // ---- finite-size-scaling observables
 constexpr int MAX_K = 8;
-
-static void mc_release(dqmc_mc_handle *h, void *p)  // hipFree of one of the handle's allocations
-{
-    if (!p) return;
-    for (size_t i = 0; i < h->allocs.size(); ++i)
-        if (h->allocs[i] == p) {
-            h->allocs.erase(h->allocs.begin() + i);
-            break;
-        }
-    (void)hipFree(p);
-}
-
-static void mc_fss_bin_free(dqmc_mc_handle *h)
-{
-    dqmc_mc_handle::Fss &f = h->fss;
-    for (double **p : {&f.xs, &f.x2, &f.xy, &f.c}) {
-        mc_release(h, *p);
-        *p = nullptr;
-    }
-    f.T = 0;
-}
 
 // the FSS section for the binner as it stands (nothing unless both are on)
 static int mc_fss_bin_alloc(dqmc_mc_handle *h)
 {
     dqmc_mc_handle::Fss &f = h->fss;
-    mc_fss_bin_free(h);
+    f.bin.free(h);
     if (!h->bin.on || f.n_k < 0) return 0;
-    const size_t W = h->W, L = h->bin.L, ne = 2 + f.n_k, np = 1 + f.n_k;
-    int rc = 0;
-    if ((rc = mc_alloc(h, &f.xs, L * ne * W)) || (rc = mc_alloc(h, &f.x2, L * ne * W)) ||
-        (rc = mc_alloc(h, &f.xy, L * np * W)) || (rc = mc_alloc(h, &f.c, (L - 1) * np * 2 * W))) {
-        const std::string msg = h->err;
-        mc_fss_bin_free(h);
-        h->err = msg;
-    }
-    return rc;
+    return f.bin.alloc(h, 2 + f.n_k, 1 + f.n_k, 2 * (1 + f.n_k), h->bin.L);
 }
 
 static int mc_fss_clear(dqmc_mc_handle *h)  // the sums and the section's state
@@ -718,15 +597,7 @@ static int mc_fss_clear(dqmc_mc_handle *h)  // the sums and the section's state
         MCHK(hipMemsetAsync(f.sS, 0, (size_t)MAX_K * W * 8, h->stream));
         MCHK(hipMemsetAsync(f.n_meas, 0, W * 8, h->stream));
     }
-    if (f.xs) {
-        const size_t L = h->bin.L, ne = 2 + f.n_k, np = 1 + f.n_k;
-        MCHK(hipMemsetAsync(f.xs, 0, L * ne * W * 8, h->stream));
-        MCHK(hipMemsetAsync(f.x2, 0, L * ne * W * 8, h->stream));
-        MCHK(hipMemsetAsync(f.xy, 0, L * np * W * 8, h->stream));
-        if (L > 1) MCHK(hipMemsetAsync(f.c, 0, (L - 1) * np * 2 * W * 8, h->stream));
-    }
-    f.T = 0;
-    return 0;
+    return f.bin.clear(h);
 }
 
 // the FSS measurement of the sweep whose last kernel has just been launched (and its push).  The 1 + n_k pairs run side
@@ -740,16 +611,13 @@ static int mc_launch_fss(dqmc_mc_handle *h)
     a.sM4 = f.sM4;
     a.sS = f.sS;
     a.n_meas = f.n_meas;
-    if (f.xs) {
-        int lmax = 0;
-        while ((f.T >> lmax) & 1) ++lmax;
-        if (lmax >= h->bin.L) return mc_fail(h, DQMC_ERR_STATE, "dqmc_mc_sweep: binner capacity exhausted");
-        a.bxs = f.xs;
-        a.bx2 = f.x2;
-        a.bxy = f.xy;
-        a.bc = f.c;
-        a.lmax = lmax;
-        a.top = h->bin.L - 1;
+    if (f.bin.xs) {
+        if (int rc = f.bin.next_lmax(h, "dqmc_mc_sweep", &a.lmax)) return rc;
+        a.bxs = f.bin.xs;
+        a.bx2 = f.bin.x2;
+        a.bxy = f.bin.xy;
+        a.bc = f.bin.c;
+        a.top = f.bin.L - 1;
     }
     const int pairs = 1 + f.n_k;
     const double per_pair = (double)h->N * std::max((double)h->W, BUDGET_WALKERS);
@@ -759,33 +627,17 @@ static int mc_launch_fss(dqmc_mc_handle *h)
                            h->stream, h->d, a, (const int4 *)f.cq, (const int4 *)f.sq, y0);
         MCHK(hipGetLastError());
     }
-    if (f.xs) f.T += 1;
+    if (f.bin.xs) f.bin.T += 1;
     return 0;
 }
 
 #define MC_FSS_BIN_OK(h, fn)                                                                          \
     MC_BIN_OK(h, fn);                                                                                 \
-    if (!(h)->fss.xs) return mc_fail((h), DQMC_ERR_STATE, std::string(fn) + ": FSS is off (dqmc_mc_set_fss first)")
-
-// x_sum, x2_sum (2 + n_k each) and xy_sum (1 + n_k) of one level of one walker of the FSS section
-static int mc_fss_bin_level(dqmc_mc_handle *h, int walker, int level, double *xs, double *x2, double *xy)
-{
-    const dqmc_mc_handle::Fss &f = h->fss;
-    const size_t W = h->W, pitch = W * sizeof(double), ne = 2 + f.n_k, np = 1 + f.n_k;
-    MCHK(hipSetDevice(h->device));
-    if (xs)
-        MCHK(hipMemcpy2DAsync(xs, 8, f.xs + (size_t)level * ne * W + walker, pitch, 8, ne, hipMemcpyDeviceToHost, h->stream));
-    if (x2)
-        MCHK(hipMemcpy2DAsync(x2, 8, f.x2 + (size_t)level * ne * W + walker, pitch, 8, ne, hipMemcpyDeviceToHost, h->stream));
-    if (xy)
-        MCHK(hipMemcpy2DAsync(xy, 8, f.xy + (size_t)level * np * W + walker, pitch, 8, np, hipMemcpyDeviceToHost, h->stream));
-    MCHK(hipStreamSynchronize(h->stream));
-    return 0;
-}
+    if (!(h)->fss.bin.xs) return mc_fail((h), DQMC_ERR_STATE, std::string(fn) + ": FSS is off (dqmc_mc_set_fss first)")
 
 extern "C" {
 
-const char *dqmc_mc_last_error(const dqmc_mc_handle *h) { return h ? h->err.c_str() : g_mc_create_error.c_str(); }
+const char *dqmc_mc_last_error(const dqmc_mc_handle *h) { return mc_last_error(h); }
 
 int dqmc_mc_create(const dqmc_mc_params *p, dqmc_mc_handle **out)
 {
@@ -798,22 +650,12 @@ int dqmc_mc_create(const dqmc_mc_params *p, dqmc_mc_handle **out)
                        "dqmc_mc_create: n_sites exceeds 16384 (the walker's spins must fit in LDS)");
     if (p->z < 1 || p->z > MAX_Z)
         return mc_fail(nullptr, DQMC_ERR_INVALID, "dqmc_mc_create: z must be in 1..8 (neighbours per site)");
-    if (p->n_bonds < 0 || p->series_capacity < 0)
-        return mc_fail(nullptr, DQMC_ERR_INVALID, "dqmc_mc_create: n_bonds and series_capacity must be >= 0");
-    if (!p->neighs || (p->n_bonds > 0 && !p->bonds))
-        return mc_fail(nullptr, DQMC_ERR_INVALID, "dqmc_mc_create: neighbour or bonds table missing");
     const int N = p->n_sites, z = p->z, nb = p->n_bonds;
-    for (long i = 0; i < (long)z * N; ++i)
-        if (p->neighs[i] < 1 || p->neighs[i] > N)
-            return mc_fail(nullptr, DQMC_ERR_INVALID, "dqmc_mc_create: neighbour index out of range 1..n_sites");
-    for (long i = 0; i < 2L * nb; ++i)
-        if (p->bonds[i] < 1 || p->bonds[i] > N)
-            return mc_fail(nullptr, DQMC_ERR_INVALID, "dqmc_mc_create: bond index out of range 1..n_sites");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return mc_fail(nullptr, DQMC_ERR_NO_DEVICE, "dqmc_mc_create: no HIP device visible");
-    if (p->device_id < 0 || p->device_id >= ndev)
-        return mc_fail(nullptr, DQMC_ERR_INVALID, "dqmc_mc_create: device_id out of range");
+    std::vector<int> nbr_h, bonds_h;
+    std::string msg;
+    if (!mc_tables::lattice_tables("dqmc_mc_create", N, z, nb, p->series_capacity, p->neighs, p->bonds, nbr_h, bonds_h, &msg))
+        return mc_fail(nullptr, DQMC_ERR_INVALID, msg);
+    if (int rc = mc_check_device("dqmc_mc_create", p->device_id)) return rc;
 
     dqmc_mc_handle *h = new dqmc_mc_handle();
     h->N = N;
@@ -824,24 +666,11 @@ int dqmc_mc_create(const dqmc_mc_params *p, dqmc_mc_handle **out)
     h->n_bonds = nb;
     h->device = p->device_id;
     h->beta_h.assign((size_t)p->n_walkers, 0.0);
-    h->nbr_h.resize((size_t)N * z);
-    for (int i = 0; i < N; ++i)
-        for (int k = 0; k < z; ++k) h->nbr_h[(size_t)i * z + k] = (int)p->neighs[(size_t)i * z + k] - 1;
-    h->bonds_h.resize((size_t)2 * nb);
-    for (int b = 0; b < nb; ++b) {  // Julia's n_bonds x 2 column-major -> pairs
-        h->bonds_h[2 * b] = (int)p->bonds[b] - 1;
-        h->bonds_h[2 * b + 1] = (int)p->bonds[nb + b] - 1;
-    }
-    auto bail = [&](int rc) {
-        g_mc_create_error = h->err;
-        dqmc_mc_destroy(h);
-        return rc;
-    };
-    if (hipSetDevice(h->device) != hipSuccess || hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess)
-        return bail(mc_fail(h, DQMC_ERR_HIP, "dqmc_mc_create: cannot open the device"));
-    std::vector<int> nbr_pad((size_t)(N + 1) * MAX_Z, 0);
-    for (int i = 0; i < N; ++i)
-        for (int k = 0; k < z; ++k) nbr_pad[(size_t)i * MAX_Z + k] = h->nbr_h[(size_t)i * z + k];
+    h->nbr_h = nbr_h;
+    h->bonds_h = bonds_h;
+    auto bail = [&](int rc) { return mc_bail(h, rc); };
+    if (int rc = mc_open(h, "dqmc_mc_create")) return bail(rc);
+    const std::vector<int> nbr_pad = mc_tables::padded_rows(h->nbr_h, N, z, N + 1);  // (row N: read ahead, unused)
     DevState &d = h->d;
     d.N = N;
     d.W = h->W;
@@ -887,18 +716,7 @@ int dqmc_mc_create(const dqmc_mc_params *p, dqmc_mc_handle **out)
     return DQMC_OK;
 }
 
-int dqmc_mc_destroy(dqmc_mc_handle *h)
-{
-    if (!h) return DQMC_OK;
-    if (h->stream) {
-        (void)hipSetDevice(h->device);
-        (void)hipStreamSynchronize(h->stream);
-    }
-    for (void *p : h->allocs) (void)hipFree(p);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
-    return DQMC_OK;
-}
+int dqmc_mc_destroy(dqmc_mc_handle *h) { return mc_destroy(h); }
 
 int dqmc_mc_set_beta(dqmc_mc_handle *h, int32_t walker, double beta)
 {
@@ -999,12 +817,12 @@ int dqmc_mc_sweep(dqmc_mc_handle *h, int32_t n_sweeps, int64_t first_sweep_index
     if (n_sweeps < 0 || measure_rate < 1 || first_sweep_index < 1)
         return mc_fail(h, DQMC_ERR_INVALID, "dqmc_mc_sweep: n_sweeps >= 0, first_sweep_index >= 1, measure_rate >= 1");
     dqmc_mc_handle::Binner &b = h->bin;
-    if (b.on && b.T + mc_measurements_in(first_sweep_index, first_sweep_index + n_sweeps - 1, thermalization,
-                                          measure_rate) > b.cap)  // the reference: OverflowError of push!
+    const int64_t n_meas = mc_tables::measurements_in(first_sweep_index, first_sweep_index + n_sweeps - 1, thermalization,
+                                                      measure_rate);
+    if (b.on && b.T + n_meas > b.cap)  // the reference: OverflowError of push!
         return mc_fail(h, DQMC_ERR_STATE, "dqmc_mc_sweep: the measurements of this call would pass the binner's capacity");
     dqmc_mc_handle::Fss &fs = h->fss;
-    if (fs.xs && fs.T + mc_measurements_in(first_sweep_index, first_sweep_index + n_sweeps - 1, thermalization,
-                                            measure_rate) > b.cap)
+    if (fs.bin.xs && fs.bin.T + n_meas > b.cap)
         return mc_fail(h, DQMC_ERR_STATE,
                        "dqmc_mc_sweep: the measurements of this call would pass the capacity of the binner's FSS section");
     MCHK(hipSetDevice(h->device));
@@ -1066,7 +884,7 @@ int dqmc_mc_sweep(dqmc_mc_handle *h, int32_t n_sweeps, int64_t first_sweep_index
             MC_CASE(1) MC_CASE(2) MC_CASE(3) MC_CASE(4) MC_CASE(5) MC_CASE(6) MC_CASE(7) MC_CASE(8)
 #undef MC_CASE
         }
-        if (b.on) b.T += mc_measurements_in(first, last, thermalization, measure_rate) - (deferred ? 1 : 0);
+        if (b.on) b.T += mc_tables::measurements_in(first, last, thermalization, measure_rate) - (deferred ? 1 : 0);
         MCHK(hipGetLastError());
         if (fused) t.cursor += (uint64_t)(last / k - (first - 1) / k - (round ? 1 : 0));  // the rounds the launch ran
         if (move)
@@ -1271,14 +1089,7 @@ int dqmc_mc_reset_accumulators(dqmc_mc_handle *h)
     MCHK(hipMemsetAsync(h->d.sM2, 0, W * 8, h->stream));
     MCHK(hipMemsetAsync(h->d.n_meas, 0, W * 8, h->stream));
     MCHK(hipMemsetAsync(h->d.n_series, 0, W * 8, h->stream));
-    dqmc_mc_handle::Binner &b = h->bin;
-    if (b.on) {
-        MCHK(hipMemsetAsync(b.xs, 0, (size_t)b.L * 4 * W * 8, h->stream));
-        MCHK(hipMemsetAsync(b.x2, 0, (size_t)b.L * 4 * W * 8, h->stream));
-        MCHK(hipMemsetAsync(b.xy, 0, (size_t)b.L * 2 * W * 8, h->stream));
-        if (b.L > 1) MCHK(hipMemsetAsync(b.c, 0, (size_t)(b.L - 1) * 4 * W * 8, h->stream));
-        b.T = 0;
-    }
+    if (int rc = h->bin.clear(h)) return rc;
     if (int rc = mc_fss_clear(h)) return rc;
     MCHK(hipStreamSynchronize(h->stream));
     return DQMC_OK;
@@ -1294,17 +1105,7 @@ int dqmc_mc_binner_enable(dqmc_mc_handle *h, int64_t capacity)
     MCHK(hipStreamSynchronize(h->stream));
     mc_bin_free(h);
     dqmc_mc_handle::Binner &b = h->bin;
-    int L = 1;  // ceil(log2(capacity + 1))
-    while (((int64_t)1 << L) < capacity + 1) ++L;
-    const size_t W = h->W;
-    int rc = 0;
-    if ((rc = mc_alloc(h, &b.xs, (size_t)L * 4 * W)) || (rc = mc_alloc(h, &b.x2, (size_t)L * 4 * W)) ||
-        (rc = mc_alloc(h, &b.xy, (size_t)L * 2 * W)) || (rc = mc_alloc(h, &b.c, (size_t)(L - 1) * 4 * W))) {
-        const std::string msg = h->err;
-        mc_bin_free(h);
-        h->err = msg;
-        return rc;
-    }
+    if (int rc = b.alloc(h, 4, 2, 4, mc_tables::bin_levels(capacity))) return rc;
     const void *kernels[] = {(const void *)ising_sweep_binned_kernel<1>, (const void *)ising_sweep_binned_kernel<2>,
                              (const void *)ising_sweep_binned_kernel<3>, (const void *)ising_sweep_binned_kernel<4>,
                              (const void *)ising_sweep_binned_kernel<5>, (const void *)ising_sweep_binned_kernel<6>,
@@ -1317,13 +1118,9 @@ int dqmc_mc_binner_enable(dqmc_mc_handle *h, int64_t capacity)
         }
     MCHK(hipStreamSynchronize(h->stream));
     b.on = true;
-    b.L = L;
     b.cap = capacity;
-    b.T = 0;
     if (int rc = mc_fss_bin_alloc(h)) {  // the FSS section, when FSS is on
-        const std::string msg = h->err;
         mc_bin_free(h);
-        h->err = msg;
         return rc;
     }
     MCHK(hipStreamSynchronize(h->stream));
@@ -1342,7 +1139,7 @@ int dqmc_mc_binner_reliable_level(dqmc_mc_handle *h, int32_t *level)
 {
     MC_BIN_OK(h, "dqmc_mc_binner_reliable_level");
     if (!level) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_mc_binner_reliable_level: null level");
-    *level = mc_bin_reliable(h->bin);
+    *level = mc_tables::bin_reliable(h->bin.T, h->bin.L);
     return DQMC_OK;
 }
 
@@ -1351,17 +1148,7 @@ int dqmc_mc_binner_get_level(dqmc_mc_handle *h, int32_t walker, int32_t level, d
 {
     MC_BIN_OK(h, "dqmc_mc_binner_get_level");
     if (int rc = mc_walker(h, walker, "dqmc_mc_binner_get_level")) return rc;
-    if (level < 0 || level >= h->bin.L) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_mc_binner_get_level: level out of range");
-    if (int rc = mc_bin_level(h, walker, level, x_sum, x2_sum, xy_sum)) return rc;
-    if (count) *count = h->bin.T >> level;
-    return DQMC_OK;
-}
-
-// varN and covN of the header: (q/(n - 1) - a b/(n (n - 1)))/n, NaN below two samples (varN: a = b, q = x2_sum)
-static double mc_bin_covN(double a, double b, double q, double n)
-{
-    if (n < 2.0) return std::nan("");
-    return (q / (n - 1.0) - a * b / (n * (n - 1.0))) / n;
+    return h->bin.level_sums(h, "dqmc_mc_binner_get_level", walker, level, x_sum, x2_sum, xy_sum, count);
 }
 
 int dqmc_mc_binner_finish(dqmc_mc_handle *h, int32_t walker, int32_t level, dqmc_mc_binned *out)
@@ -1369,23 +1156,8 @@ int dqmc_mc_binner_finish(dqmc_mc_handle *h, int32_t walker, int32_t level, dqmc
     MC_BIN_OK(h, "dqmc_mc_binner_finish");
     if (int rc = mc_walker(h, walker, "dqmc_mc_binner_finish")) return rc;
     if (!out) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_mc_binner_finish: null out");
-    const dqmc_mc_handle::Binner &b = h->bin;
-    if (level >= b.L) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_mc_binner_finish: level out of range");
-    if (level < 0) level = mc_bin_reliable(b);
-    double xs0[4], x20[4], xs[4], x2[4], xy[2];
-    if (int rc = mc_bin_level(h, walker, 0, xs0, x20, nullptr)) return rc;
-    if (int rc = mc_bin_level(h, walker, level, xs, x2, xy)) return rc;
-    const double n0 = (double)b.T, nl = (double)(b.T >> level);
-    for (int k = 0; k < 4; ++k) {
-        out->mean[k] = xs0[k] / n0;
-        out->varN[k] = mc_bin_covN(xs[k], xs[k], x2[k], nl);
-        out->varN0[k] = mc_bin_covN(xs0[k], xs0[k], x20[k], n0);
-        out->tau[k] = 0.5 * (out->varN[k] / out->varN0[k] - 1.0);
-    }
-    for (int q = 0; q < 2; ++q) out->covN[q] = mc_bin_covN(xs[2 * q], xs[2 * q + 1], xy[q], nl);
-    out->count = b.T >> level;
-    out->level = level;
-    return DQMC_OK;
+    return h->bin.finish(h, "dqmc_mc_binner_finish", walker, level, false, out->mean, out->varN, out->varN0, out->tau,
+                         out->covN, &out->count, &out->level);
 }
 
 int dqmc_mc_set_fss(dqmc_mc_handle *h, int32_t n_k, const int32_t *cos_q30, const int32_t *sin_q30)
@@ -1400,10 +1172,9 @@ int dqmc_mc_set_fss(dqmc_mc_handle *h, int32_t n_k, const int32_t *cos_q30, cons
     MCHK(hipSetDevice(h->device));
     MCHK(hipStreamSynchronize(h->stream));
     dqmc_mc_handle::Fss &f = h->fss;
-    mc_fss_bin_free(h);
+    f.bin.free(h);
     mc_release(h, f.cq);
     mc_release(h, f.sq);
-    f.cq = f.sq = nullptr;
     f.n_k = -1;
     if (n_k >= 0) {
         const size_t W = h->W, pitch = (size_t)32 * h->nw, n = (size_t)n_k * pitch;
@@ -1450,11 +1221,7 @@ int dqmc_mc_fss_binner_get_level(dqmc_mc_handle *h, int32_t walker, int32_t leve
 {
     MC_FSS_BIN_OK(h, "dqmc_mc_fss_binner_get_level");
     if (int rc = mc_walker(h, walker, "dqmc_mc_fss_binner_get_level")) return rc;
-    if (level < 0 || level >= h->bin.L)
-        return mc_fail(h, DQMC_ERR_INVALID, "dqmc_mc_fss_binner_get_level: level out of range");
-    if (int rc = mc_fss_bin_level(h, walker, level, x_sum, x2_sum, xy_sum)) return rc;
-    if (count) *count = h->fss.T >> level;
-    return DQMC_OK;
+    return h->fss.bin.level_sums(h, "dqmc_mc_fss_binner_get_level", walker, level, x_sum, x2_sum, xy_sum, count);
 }
 
 int dqmc_mc_fss_binner_finish(dqmc_mc_handle *h, int32_t walker, int32_t level, dqmc_mc_fss_binned *out)
@@ -1462,29 +1229,12 @@ int dqmc_mc_fss_binner_finish(dqmc_mc_handle *h, int32_t walker, int32_t level, 
     MC_FSS_BIN_OK(h, "dqmc_mc_fss_binner_finish");
     if (int rc = mc_walker(h, walker, "dqmc_mc_fss_binner_finish")) return rc;
     if (!out) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_mc_fss_binner_finish: null out");
-    const dqmc_mc_handle::Fss &f = h->fss;
-    const int L = h->bin.L, ne = 2 + f.n_k;
-    if (level >= L) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_mc_fss_binner_finish: level out of range");
-    if (level < 0) {  // the existing rule: the last level with count >= 32, else 0
-        level = 0;
-        for (int l = 0; l < L; ++l)
-            if ((f.T >> l) >= 32) level = l;
-    }
-    double xs0[2 + MAX_K], x20[2 + MAX_K], xs[2 + MAX_K], x2[2 + MAX_K], xy[1 + MAX_K];
-    if (int rc = mc_fss_bin_level(h, walker, 0, xs0, x20, nullptr)) return rc;
-    if (int rc = mc_fss_bin_level(h, walker, level, xs, x2, xy)) return rc;
-    *out = dqmc_mc_fss_binned{};
-    const double n0 = (double)f.T, nl = (double)(f.T >> level);
-    for (int k = 0; k < ne; ++k) {
-        out->mean[k] = xs0[k] / n0;
-        out->varN[k] = mc_bin_covN(xs[k], xs[k], x2[k], nl);
-        out->varN0[k] = mc_bin_covN(xs0[k], xs0[k], x20[k], n0);
-        out->tau[k] = 0.5 * (out->varN[k] / out->varN0[k] - 1.0);
-    }
-    for (int q = 0; q + 1 < ne; ++q) out->covN[q] = mc_bin_covN(xs[0], xs[1 + q], xy[q], nl);
-    out->count = f.T >> level;
-    out->level = level;
-    out->n_k = f.n_k;
+    dqmc_mc_fss_binned r{};  // (entries past the section's elements stay 0)
+    if (int rc = h->fss.bin.finish(h, "dqmc_mc_fss_binner_finish", walker, level, true, r.mean, r.varN, r.varN0, r.tau,
+                                   r.covN, &r.count, &r.level))
+        return rc;
+    r.n_k = h->fss.n_k;
+    *out = r;
     return DQMC_OK;
 }
 
@@ -1497,57 +1247,26 @@ int dqmc_mc_set_update(dqmc_mc_handle *h, int32_t kind, const int32_t *colour, i
     }
     if (kind != DQMC_MC_UPDATE_CHECKERBOARD)
         return mc_fail(h, DQMC_ERR_INVALID, "dqmc_mc_set_update: kind must be 0 (sequential) or 1 (checkerboard)");
-    if (!colour) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_mc_set_update: null colouring");
-    if (n_colours < 1 || n_colours > CB_MAX_COLOURS)
-        return mc_fail(h, DQMC_ERR_INVALID, "dqmc_mc_set_update: n_colours must be in 1..16");
-    const int N = h->N, z = h->z, nc = n_colours;
-    for (int i = 0; i < N; ++i)
-        if (colour[i] < 0 || colour[i] >= nc)
-            return mc_fail(h, DQMC_ERR_INVALID,
-                           "dqmc_mc_set_update: the colour of site " + std::to_string(i) + " is out of range 0..n_colours-1");
-    for (int i = 0; i < N; ++i)
-        for (int k = 0; k < z; ++k) {
-            const int j = h->nbr_h[(size_t)i * z + k];
-            if (j == i)
-                return mc_fail(h, DQMC_ERR_INVALID, "dqmc_mc_set_update: site " + std::to_string(i) +
-                                                        " lists itself as a neighbour (0-based): no checkerboard sweep");
-            if (colour[j] == colour[i])
-                return mc_fail(h, DQMC_ERR_INVALID, "dqmc_mc_set_update: the neighbours " + std::to_string(i) + " and " +
-                                                        std::to_string(j) + " (0-based sites) share colour " +
-                                                        std::to_string(colour[i]));
-        }
-    // the sites sorted by colour (site order within a class), the class offsets, and the padded rows in that order
-    std::vector<int> off((size_t)nc + 1, 0), site((size_t)N), rows((size_t)N * MAX_Z, 0);
-    for (int i = 0; i < N; ++i) off[(size_t)colour[i] + 1] += 1;
-    int largest = 0;
-    for (int c = 0; c < nc; ++c) {
-        largest = std::max(largest, off[(size_t)c + 1]);
-        off[(size_t)c + 1] += off[c];
-    }
-    std::vector<int> fill(off.begin(), off.end() - 1);
-    for (int i = 0; i < N; ++i) {
-        const int e = fill[colour[i]]++;
-        site[e] = i;
-        for (int k = 0; k < z; ++k) rows[(size_t)e * MAX_Z + k] = h->nbr_h[(size_t)i * z + k];
-    }
+    mc_tables::Colouring t;  // the class offsets end at n_colours: [n_colours + 1]
+    std::string msg;
+    if (!mc_tables::colour_tables("dqmc_mc_set_update", h->nbr_h, h->N, h->z, colour, n_colours, n_colours + 1, CB_THREADS,
+                                  t, &msg))
+        return mc_fail(h, DQMC_ERR_INVALID, msg);
     MCHK(hipSetDevice(h->device));
     MCHK(hipStreamSynchronize(h->stream));
     dqmc_mc_handle::Update &u = h->upd;
-    for (int **p : {&u.site, &u.rows, &u.off}) {
-        mc_release(h, *p);
-        *p = nullptr;
-    }
+    for (int **p : {&u.site, &u.rows, &u.off}) mc_release(h, *p);
     u.kind = DQMC_MC_UPDATE_SEQUENTIAL;  // (until the new tables are in place)
     int rc = 0;
-    if ((rc = mc_alloc(h, &u.site, site.size())) || (rc = mc_alloc(h, &u.rows, rows.size())) ||
-        (rc = mc_alloc(h, &u.off, off.size())))
+    if ((rc = mc_alloc(h, &u.site, t.site.size())) || (rc = mc_alloc(h, &u.rows, t.rows.size())) ||
+        (rc = mc_alloc(h, &u.off, t.off.size())))
         return rc;
-    MCHK(hipMemcpyAsync(u.site, site.data(), site.size() * 4, hipMemcpyHostToDevice, h->stream));
-    MCHK(hipMemcpyAsync(u.rows, rows.data(), rows.size() * 4, hipMemcpyHostToDevice, h->stream));
-    MCHK(hipMemcpyAsync(u.off, off.data(), off.size() * 4, hipMemcpyHostToDevice, h->stream));
+    MCHK(hipMemcpyAsync(u.site, t.site.data(), t.site.size() * 4, hipMemcpyHostToDevice, h->stream));
+    MCHK(hipMemcpyAsync(u.rows, t.rows.data(), t.rows.size() * 4, hipMemcpyHostToDevice, h->stream));
+    MCHK(hipMemcpyAsync(u.off, t.off.data(), t.off.size() * 4, hipMemcpyHostToDevice, h->stream));
     MCHK(hipStreamSynchronize(h->stream));  // (the vectors are this call's: copied before it returns)
-    u.C = nc;
-    u.threads = std::min(CB_THREADS, std::max(WAVE, (largest + WAVE - 1) / WAVE * WAVE));
+    u.C = n_colours;
+    u.threads = t.threads;
     u.kind = DQMC_MC_UPDATE_CHECKERBOARD;
     return DQMC_OK;
 }

@@ -1,0 +1,148 @@
+// mc_tables.h — what the two engines of the classical MC flavor (ising.hip, qstate.hip) work out on the host before
+// anything reaches the device: the lattice tables of a create, the colour-sorted tables of a checkerboard sweep, and the
+// arithmetic of the logarithmic binner.  Plain C++17, no device runtime: mc_host.h includes it, and
+// tests/mc_tables_check.cpp builds it alone under the host sanitizers.  A refusal returns false with the message in *err,
+// prefixed with the name of the ABI function the caller passes as fn.
+#pragma once
+
+#include <algorithm>
+#include <cmath>
+#include <cstddef>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+namespace mc_tables {
+
+constexpr int ROW = 8;           // a site's neighbour row on the device: z <= 8 entries padded with zeros to 8
+constexpr int MAX_COLOURS = 16;
+constexpr int WAVE = 64;
+
+// The tables of dqmc_mc_params / dqmc_qs_params (1-based, neighs [N][z] with z fastest, bonds n_bonds x 2 column-major)
+// as the engines keep them: nbr [N][z] and pairs [n_bonds][2], 0-based.  N and z are the caller's to check against its
+// own limits first.
+inline bool lattice_tables(const std::string &fn, int N, int z, int n_bonds, long series_capacity, const int64_t *neighs,
+                           const int64_t *bonds, std::vector<int> &nbr, std::vector<int> &pairs, std::string *err)
+{
+    if (n_bonds < 0 || series_capacity < 0) return *err = fn + ": n_bonds and series_capacity must be >= 0", false;
+    if (!neighs || (n_bonds > 0 && !bonds)) return *err = fn + ": neighbour or bonds table missing", false;
+    for (long i = 0; i < (long)z * N; ++i)
+        if (neighs[i] < 1 || neighs[i] > N) return *err = fn + ": neighbour index out of range 1..n_sites", false;
+    for (long i = 0; i < 2L * n_bonds; ++i)
+        if (bonds[i] < 1 || bonds[i] > N) return *err = fn + ": bond index out of range 1..n_sites", false;
+    nbr.resize((size_t)N * z);
+    for (size_t i = 0; i < nbr.size(); ++i) nbr[i] = (int)neighs[i] - 1;
+    pairs.resize((size_t)2 * n_bonds);
+    for (int b = 0; b < n_bonds; ++b) {
+        pairs[2 * b] = (int)bonds[b] - 1;
+        pairs[2 * b + 1] = (int)bonds[n_bonds + b] - 1;
+    }
+    return true;
+}
+
+// nbr [N][z] as n_rows >= N rows of ROW entries, zeros behind a row's z and in the rows past N
+inline std::vector<int> padded_rows(const std::vector<int> &nbr, int N, int z, int n_rows)
+{
+    std::vector<int> rows((size_t)n_rows * ROW, 0);
+    for (int i = 0; i < N; ++i)
+        for (int k = 0; k < z; ++k) rows[(size_t)i * ROW + k] = nbr[(size_t)i * z + k];
+    return rows;
+}
+
+// A colouring (colour[i] in [0, n_colours), n_colours <= 16, no site sharing its colour with a neighbour) as the tables a
+// checkerboard sweep reads: the sites sorted by colour, site order within a class; their padded neighbour rows in that
+// order; the class offsets, n_off >= n_colours + 1 entries (the classes past n_colours are empty); the largest class, and
+// the workgroup size that gives each of its sites a lane: whole waves, max_threads at most.
+struct Colouring {
+    std::vector<int> site, rows, off;  // [N], [N][ROW], [n_off]
+    int largest = 0, threads = 0;
+};
+inline bool colour_tables(const std::string &fn, const std::vector<int> &nbr, int N, int z, const int32_t *colour,
+                          int n_colours, int n_off, int max_threads, Colouring &out, std::string *err)
+{
+    if (!colour) return *err = fn + ": null colouring", false;
+    if (n_colours < 1 || n_colours > MAX_COLOURS) return *err = fn + ": n_colours must be in 1..16", false;
+    for (int i = 0; i < N; ++i)
+        if (colour[i] < 0 || colour[i] >= n_colours)
+            return *err = fn + ": the colour of site " + std::to_string(i) + " is out of range 0..n_colours-1", false;
+    for (int i = 0; i < N; ++i)
+        for (int k = 0; k < z; ++k) {
+            const int j = nbr[(size_t)i * z + k];
+            if (j == i)
+                return *err = fn + ": site " + std::to_string(i) + " lists itself as a neighbour (0-based): no colouring",
+                       false;
+            if (colour[j] == colour[i])
+                return *err = fn + ": the neighbours " + std::to_string(i) + " and " + std::to_string(j) +
+                              " (0-based sites) share colour " + std::to_string(colour[i]),
+                       false;
+        }
+    out.off.assign((size_t)n_off, 0);
+    out.site.assign((size_t)N, 0);
+    out.rows.assign((size_t)N * ROW, 0);
+    for (int i = 0; i < N; ++i) out.off[(size_t)colour[i] + 1] += 1;
+    out.largest = 0;
+    for (int c = 0; c + 1 < n_off; ++c) {
+        out.largest = std::max(out.largest, out.off[(size_t)c + 1]);
+        out.off[(size_t)c + 1] += out.off[c];
+    }
+    std::vector<int> fill(out.off.begin(), out.off.end() - 1);
+    for (int i = 0; i < N; ++i) {
+        const int e = fill[colour[i]]++;
+        out.site[e] = i;
+        for (int k = 0; k < z; ++k) out.rows[(size_t)e * ROW + k] = nbr[(size_t)i * z + k];
+    }
+    out.threads = std::min(max_threads, std::max(WAVE, (out.largest + WAVE - 1) / WAVE * WAVE));
+    return true;
+}
+
+// measurements of run! (MC.jl:262-283) among the sweeps first..last: i > thermalization && i % rate == 0
+inline int64_t measurements_in(int64_t first, int64_t last, int64_t thermalization, int64_t rate)
+{
+    const int64_t lo = std::max<int64_t>(first - 1, thermalization);  // (first >= 1)
+    return last > lo ? last / rate - lo / rate : 0;
+}
+
+// ---- the logarithmic binner (include/dqmc_hip.h, "error bars of the MC flavor"): count[level] = T >> level after T pushes
+inline int bin_levels(int64_t capacity)  // ceil(log2(capacity + 1)), one at least
+{
+    int L = 1;
+    while (((int64_t)1 << L) < capacity + 1) ++L;
+    return L;
+}
+inline int bin_lmax(int64_t T)  // the level that keeps push T + 1: the trailing 1-bits of T (>= the levels: no room left)
+{
+    int lmax = 0;
+    while ((T >> lmax) & 1) ++lmax;
+    return lmax;
+}
+inline int bin_reliable(int64_t T, int L)  // the last level with count >= 32, else 0
+{
+    int lv = 0;
+    for (int l = 0; l < L; ++l)
+        if ((T >> l) >= 32) lv = l;
+    return lv;
+}
+// varN and covN of the header: (q/(n - 1) - a b/(n (n - 1)))/n, NaN below two samples (varN: a = b, q = x2_sum)
+inline double bin_covN(double a, double b, double q, double n)
+{
+    if (n < 2.0) return std::nan("");
+    return (q / (n - 1.0) - a * b / (n * (n - 1.0))) / n;
+}
+// mean, varN, varN0 and tau of n_elem elements and covN of n_pairs pairs from the sums of level 0 (xs0, x20) and of
+// `level` (xs, x2, xy) after T pushes.  Pair p is the elements (2 p, 2 p + 1), or (0, 1 + p) with pairs_from_first.
+inline void bin_finish(int n_elem, int n_pairs, bool pairs_from_first, int64_t T, int level, const double *xs0,
+                       const double *x20, const double *xs, const double *x2, const double *xy, double *mean,
+                       double *varN, double *varN0, double *tau, double *covN)
+{
+    const double n0 = (double)T, nl = (double)(T >> level);
+    for (int k = 0; k < n_elem; ++k) {
+        mean[k] = xs0[k] / n0;
+        varN[k] = bin_covN(xs[k], xs[k], x2[k], nl);
+        varN0[k] = bin_covN(xs0[k], xs0[k], x20[k], n0);
+        tau[k] = 0.5 * (varN[k] / varN0[k] - 1.0);
+    }
+    for (int p = 0; p < n_pairs; ++p)
+        covN[p] = pairs_from_first ? bin_covN(xs[0], xs[1 + p], xy[p], nl) : bin_covN(xs[2 * p], xs[2 * p + 1], xy[p], nl);
+}
+
+}  // namespace mc_tables

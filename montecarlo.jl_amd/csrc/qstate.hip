@@ -1,6 +1,7 @@
 // qstate.hip - the classical MC flavor with q-state models (Potts, clock) behind dqmc_qs_* (include/dqmc_hip.h, "the
 // classical MC flavor with q-state models": that comment is the definition, this file follows it).  A handle family of its
-// own; nothing here is shared with ising.hip but the Philox rounds of kernels.h.
+// own with its own kernels and DevState; the host layer under it is the one under ising.hip: mc_host.h (the handle base,
+// errors, device memory, single-value moves, create and destroy) and mc_tables.h (the lattice and colouring tables).
 //
 // One workgroup sweeps one walker, colour class by colour class, as the Ising checkerboard path does (ising_cb.inl).  The
 // walker's sites are bytes in LDS, its weight table w[q][q] (fp64), e_q30 and the (cos, sin) pairs lie beside them:
@@ -32,6 +33,7 @@
 
 #include "../../include/dqmc_hip.h"
 #include "kernels.h"
+#include "mc_host.h"
 
 namespace dqmc_qs {
 
@@ -483,13 +485,15 @@ __global__ __launch_bounds__(THREADS) void qs_observables_kernel(DevState s, con
 
 using namespace dqmc_qs;
 
-struct dqmc_qs_handle {
-    int N = 0, z = 0, q = 0, W = 0, Nw = 0, cap = 0, n_bonds = 0, device = 0;
+static_assert(MAX_Z == mc_tables::ROW && MAX_COLOURS == mc_tables::MAX_COLOURS && WAVE == mc_tables::WAVE,
+              "the kernels read the tables mc_tables.h lays out");
+
+struct dqmc_qs_handle : mc_handle_base {
+    int N = 0, z = 0, q = 0, Nw = 0, cap = 0, n_bonds = 0;
     int C = 0, threads = THREADS;
     std::vector<int> nbr_h;             // [N][z] 0-based
     std::vector<long long> e_h;         // [q]
     std::vector<unsigned long long> confs_h;  // [W]: the conf cursor r of every walker
-    hipStream_t stream = nullptr;
     DevState d{};
     int *site = nullptr, *rows = nullptr, *off = nullptr, *bonds = nullptr;  // [N], [N][8], [17], [n_bonds][2]
     long long *e_q30 = nullptr;         // [q]
@@ -498,112 +502,19 @@ struct dqmc_qs_handle {
     ClusterArgs ca{};                   // rate 0: no moves inside dqmc_qs_sweep
     int *nbr_site = nullptr;            // [N][8], what ca.nbr points to
     bool cluster_lds_reserved = false;  // the kernels with a move may ask for more than 64 KiB of dynamic LDS
-    std::vector<void *> allocs;
-    std::string err;
 };
 
-static thread_local std::string g_qs_create_error;
-
-static int qs_fail(dqmc_qs_handle *h, int code, const std::string &msg)
+// a validated colouring's tables into the handle's fixed-size arrays (off: all 17 entries, the empty classes at N)
+static int qs_put_colouring(dqmc_qs_handle *h, const mc_tables::Colouring &t, int nc)
 {
-    if (h) h->err = msg;
-    else g_qs_create_error = msg;
-    return code;
-}
-
-#define QCHK(expr)                                                                                               \
-    do {                                                                                                         \
-        hipError_t e_ = (expr);                                                                                  \
-        if (e_ != hipSuccess) return qs_fail(h, DQMC_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-template <typename T>
-static int qs_alloc(dqmc_qs_handle *h, T **p, size_t count)
-{
-    void *m = nullptr;
-    QCHK(hipMalloc(&m, (count ? count : 1) * sizeof(T)));
-    h->allocs.push_back(m);
-    QCHK(hipMemsetAsync(m, 0, (count ? count : 1) * sizeof(T), h->stream));
-    *p = (T *)m;
-    return 0;
-}
-
-static int qs_walker(dqmc_qs_handle *h, int32_t w, const char *fn)
-{
-    if (!h) return qs_fail(nullptr, DQMC_ERR_INVALID, std::string(fn) + ": null handle");
-    if (w < 0 || w >= h->W) return qs_fail(h, DQMC_ERR_INVALID, std::string(fn) + ": walker out of range");
-    return 0;
-}
-
-template <typename T>
-static int qs_put(dqmc_qs_handle *h, T *base, int w, T v)
-{
-    QCHK(hipMemcpyAsync(base + w, &v, sizeof(T), hipMemcpyHostToDevice, h->stream));
-    QCHK(hipStreamSynchronize(h->stream));
-    return 0;
-}
-
-template <typename T>
-static int qs_get(dqmc_qs_handle *h, const T *base, int w, T *v)
-{
-    QCHK(hipMemcpyAsync(v, base + w, sizeof(T), hipMemcpyDeviceToHost, h->stream));
-    QCHK(hipStreamSynchronize(h->stream));
-    return 0;
-}
-
-// the colour-sorted tables of a colouring, validated against the neighbour table (h may be NULL while creating: the
-// message then goes where dqmc_qs_last_error(NULL) finds it)
-static int qs_colour_tables(dqmc_qs_handle *err_to, const char *fn, const std::vector<int> &nbr, int N, int z,
-                            const int32_t *colour, int nc, std::vector<int> &site, std::vector<int> &rows,
-                            std::vector<int> &off, int *largest)
-{
-    const std::string f(fn);
-    if (!colour) return qs_fail(err_to, DQMC_ERR_INVALID, f + ": null colouring");
-    if (nc < 1 || nc > MAX_COLOURS) return qs_fail(err_to, DQMC_ERR_INVALID, f + ": n_colours must be in 1..16");
-    for (int i = 0; i < N; ++i)
-        if (colour[i] < 0 || colour[i] >= nc)
-            return qs_fail(err_to, DQMC_ERR_INVALID,
-                           f + ": the colour of site " + std::to_string(i) + " is out of range 0..n_colours-1");
-    for (int i = 0; i < N; ++i)
-        for (int k = 0; k < z; ++k) {
-            const int j = nbr[(size_t)i * z + k];
-            if (j == i)
-                return qs_fail(err_to, DQMC_ERR_INVALID,
-                               f + ": site " + std::to_string(i) + " lists itself as a neighbour (0-based): no colouring");
-            if (colour[j] == colour[i])
-                return qs_fail(err_to, DQMC_ERR_INVALID, f + ": the neighbours " + std::to_string(i) + " and " +
-                                                             std::to_string(j) + " (0-based sites) share colour " +
-                                                             std::to_string(colour[i]));
-        }
-    off.assign((size_t)MAX_COLOURS + 1, 0);
-    site.assign((size_t)N, 0);
-    rows.assign((size_t)N * MAX_Z, 0);
-    for (int i = 0; i < N; ++i) off[(size_t)colour[i] + 1] += 1;
-    *largest = 0;
-    for (int c = 0; c < MAX_COLOURS; ++c) {
-        *largest = std::max(*largest, off[(size_t)c + 1]);
-        off[(size_t)c + 1] += off[c];
-    }
-    std::vector<int> fill(off.begin(), off.end() - 1);
-    for (int i = 0; i < N; ++i) {
-        const int e = fill[colour[i]]++;
-        site[e] = i;
-        for (int k = 0; k < z; ++k) rows[(size_t)e * MAX_Z + k] = nbr[(size_t)i * z + k];
-    }
-    return 0;
-}
-
-static int qs_put_colouring(dqmc_qs_handle *h, const std::vector<int> &site, const std::vector<int> &rows,
-                            const std::vector<int> &off, int nc, int largest)
-{
-    QCHK(hipSetDevice(h->device));
-    QCHK(hipStreamSynchronize(h->stream));
-    QCHK(hipMemcpyAsync(h->site, site.data(), site.size() * 4, hipMemcpyHostToDevice, h->stream));
-    QCHK(hipMemcpyAsync(h->rows, rows.data(), rows.size() * 4, hipMemcpyHostToDevice, h->stream));
-    QCHK(hipMemcpyAsync(h->off, off.data(), off.size() * 4, hipMemcpyHostToDevice, h->stream));
-    QCHK(hipStreamSynchronize(h->stream));  // (the vectors are the caller's: copied before it returns)
+    MCHK(hipSetDevice(h->device));
+    MCHK(hipStreamSynchronize(h->stream));
+    MCHK(hipMemcpyAsync(h->site, t.site.data(), t.site.size() * 4, hipMemcpyHostToDevice, h->stream));
+    MCHK(hipMemcpyAsync(h->rows, t.rows.data(), t.rows.size() * 4, hipMemcpyHostToDevice, h->stream));
+    MCHK(hipMemcpyAsync(h->off, t.off.data(), t.off.size() * 4, hipMemcpyHostToDevice, h->stream));
+    MCHK(hipStreamSynchronize(h->stream));  // (the vectors are the caller's: copied before it returns)
     h->C = nc;
-    h->threads = std::min(THREADS, std::max(WAVE, (largest + WAVE - 1) / WAVE * WAVE));
+    h->threads = t.threads;
     return 0;
 }
 
@@ -619,7 +530,7 @@ static int qs_reserve_cluster_lds(dqmc_qs_handle *h, const char *fn)
         hipFuncSetAttribute((const void *)qs_cluster_move_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
             hipSuccess) {
         (void)hipGetLastError();
-        return qs_fail(h, DQMC_ERR_HIP, std::string(fn) + ": cannot reserve " + std::to_string(lds) +
+        return mc_fail(h, DQMC_ERR_HIP, std::string(fn) + ": cannot reserve " + std::to_string(lds) +
                                             " bytes of LDS for the cluster-move kernels");
     }
     h->cluster_lds_reserved = true;
@@ -630,63 +541,50 @@ static int qs_launch_observables(dqmc_qs_handle *h, int walker)
 {
     hipLaunchKernelGGL(qs_observables_kernel, dim3(walker >= 0 ? 1 : h->W), dim3(THREADS), 0, h->stream, h->d,
                        (const int *)h->bonds, (const long long *)h->e_q30, (const int2 *)h->cs_q30, walker);
-    QCHK(hipGetLastError());
+    MCHK(hipGetLastError());
     return 0;
 }
 
 extern "C" {
 
-const char *dqmc_qs_last_error(const dqmc_qs_handle *h) { return h ? h->err.c_str() : g_qs_create_error.c_str(); }
+const char *dqmc_qs_last_error(const dqmc_qs_handle *h) { return mc_last_error(h); }
 
 int dqmc_qs_create(const dqmc_qs_params *p, dqmc_qs_handle **out)
 {
     const std::string f = "dqmc_qs_create";
-    if (!p || !out) return qs_fail(nullptr, DQMC_ERR_INVALID, f + ": null argument");
+    if (!p || !out) return mc_fail(nullptr, DQMC_ERR_INVALID, f + ": null argument");
     *out = nullptr;
     if (p->q < 2 || p->q > MAX_Q)
-        return qs_fail(nullptr, DQMC_ERR_INVALID, f + ": q = " + std::to_string(p->q) + " is outside 2..64");
+        return mc_fail(nullptr, DQMC_ERR_INVALID, f + ": q = " + std::to_string(p->q) + " is outside 2..64");
     if (p->n_sites < 1 || p->n_walkers < 1)
-        return qs_fail(nullptr, DQMC_ERR_INVALID, f + ": n_sites and n_walkers must be >= 1");
+        return mc_fail(nullptr, DQMC_ERR_INVALID, f + ": n_sites and n_walkers must be >= 1");
     if (p->n_sites > MAX_SITES)
-        return qs_fail(nullptr, DQMC_ERR_INVALID, f + ": n_sites = " + std::to_string(p->n_sites) +
+        return mc_fail(nullptr, DQMC_ERR_INVALID, f + ": n_sites = " + std::to_string(p->n_sites) +
                                                       " exceeds 16384 (the walker's sites must fit in LDS)");
     if (p->z < 1 || p->z > MAX_Z)
-        return qs_fail(nullptr, DQMC_ERR_INVALID,
+        return mc_fail(nullptr, DQMC_ERR_INVALID,
                        f + ": z = " + std::to_string(p->z) + " is outside 1..8 (neighbours per site)");
-    if (p->n_bonds < 0 || p->series_capacity < 0)
-        return qs_fail(nullptr, DQMC_ERR_INVALID, f + ": n_bonds and series_capacity must be >= 0");
-    if (!p->neighs || (p->n_bonds > 0 && !p->bonds))
-        return qs_fail(nullptr, DQMC_ERR_INVALID, f + ": neighbour or bonds table missing");
     if (!p->e_q30 || !p->c_q30 || !p->s_q30)
-        return qs_fail(nullptr, DQMC_ERR_INVALID, f + ": e_q30, c_q30 or s_q30 missing");
+        return mc_fail(nullptr, DQMC_ERR_INVALID, f + ": e_q30, c_q30 or s_q30 missing");
     const int N = p->n_sites, z = p->z, nb = p->n_bonds, q = p->q;
-    for (long i = 0; i < (long)z * N; ++i)
-        if (p->neighs[i] < 1 || p->neighs[i] > N)
-            return qs_fail(nullptr, DQMC_ERR_INVALID, f + ": neighbour index out of range 1..n_sites");
-    for (long i = 0; i < 2L * nb; ++i)
-        if (p->bonds[i] < 1 || p->bonds[i] > N)
-            return qs_fail(nullptr, DQMC_ERR_INVALID, f + ": bond index out of range 1..n_sites");
+    std::vector<int> nbr, bonds_h;
+    std::string msg;
+    if (!mc_tables::lattice_tables(f, N, z, nb, p->series_capacity, p->neighs, p->bonds, nbr, bonds_h, &msg))
+        return mc_fail(nullptr, DQMC_ERR_INVALID, msg);
     for (int d = 0; d < q; ++d) {
         if (p->e_q30[d] != p->e_q30[(q - d) % q])
-            return qs_fail(nullptr, DQMC_ERR_INVALID, f + ": e_q30[" + std::to_string(d) + "] != e_q30[" +
+            return mc_fail(nullptr, DQMC_ERR_INVALID, f + ": e_q30[" + std::to_string(d) + "] != e_q30[" +
                                                           std::to_string((q - d) % q) + "]: the table is not symmetric");
         if (p->e_q30[d] > (1LL << 32) || p->e_q30[d] < -(1LL << 32))
-            return qs_fail(nullptr, DQMC_ERR_INVALID, f + ": e_q30[" + std::to_string(d) + "] exceeds 2^32 in magnitude");
+            return mc_fail(nullptr, DQMC_ERR_INVALID, f + ": e_q30[" + std::to_string(d) + "] exceeds 2^32 in magnitude");
         if (p->c_q30[d] > (1 << 30) || p->c_q30[d] < -(1 << 30) || p->s_q30[d] > (1 << 30) || p->s_q30[d] < -(1 << 30))
-            return qs_fail(nullptr, DQMC_ERR_INVALID,
+            return mc_fail(nullptr, DQMC_ERR_INVALID,
                            f + ": c_q30 / s_q30 entry " + std::to_string(d) + " exceeds 2^30 in magnitude");
     }
-    std::vector<int> nbr((size_t)N * z);
-    for (size_t i = 0; i < nbr.size(); ++i) nbr[i] = (int)p->neighs[i] - 1;
-    std::vector<int> site, rows, off;
-    int largest = 0;
-    if (int rc = qs_colour_tables(nullptr, "dqmc_qs_create", nbr, N, z, p->colour, p->n_colours, site, rows, off, &largest))
-        return rc;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return qs_fail(nullptr, DQMC_ERR_NO_DEVICE, f + ": no HIP device visible");
-    if (p->device_id < 0 || p->device_id >= ndev)
-        return qs_fail(nullptr, DQMC_ERR_INVALID, f + ": device_id out of range");
+    mc_tables::Colouring colouring;
+    if (!mc_tables::colour_tables(f, nbr, N, z, p->colour, p->n_colours, MAX_COLOURS + 1, THREADS, colouring, &msg))
+        return mc_fail(nullptr, DQMC_ERR_INVALID, msg);
+    if (int rc = mc_check_device(f, p->device_id)) return rc;
 
     dqmc_qs_handle *h = new dqmc_qs_handle();
     h->N = N;
@@ -700,20 +598,10 @@ int dqmc_qs_create(const dqmc_qs_params *p, dqmc_qs_handle **out)
     h->nbr_h = nbr;
     h->e_h.assign(p->e_q30, p->e_q30 + q);
     h->confs_h.assign((size_t)h->W, 0ull);
-    std::vector<int> bonds_h((size_t)2 * nb);
-    for (int b = 0; b < nb; ++b) {  // n_bonds x 2 column-major -> pairs
-        bonds_h[2 * b] = (int)p->bonds[b] - 1;
-        bonds_h[2 * b + 1] = (int)p->bonds[nb + b] - 1;
-    }
     std::vector<int2> cs_h((size_t)q);
     for (int d = 0; d < q; ++d) cs_h[d] = make_int2(p->c_q30[d], p->s_q30[d]);
-    auto bail = [&](int rc) {
-        g_qs_create_error = h->err;
-        dqmc_qs_destroy(h);
-        return rc;
-    };
-    if (hipSetDevice(h->device) != hipSuccess || hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess)
-        return bail(qs_fail(h, DQMC_ERR_HIP, f + ": cannot open the device"));
+    auto bail = [&](int rc) { return mc_bail(h, rc); };
+    if (int rc = mc_open(h, f)) return bail(rc);
     DevState &d = h->d;
     d.N = N;
     d.Nw = h->Nw;
@@ -724,25 +612,23 @@ int dqmc_qs_create(const dqmc_qs_params *p, dqmc_qs_handle **out)
     d.n_bonds = nb;
     const size_t W = h->W;
     int rc = 0;
-    if ((rc = qs_alloc(h, &d.conf, (size_t)h->Nw * W)) || (rc = qs_alloc(h, &d.wt, (size_t)q * q * W)) ||
-        (rc = qs_alloc(h, &d.key, W)) || (rc = qs_alloc(h, &d.cursor, W)) || (rc = qs_alloc(h, &d.E, W)) ||
-        (rc = qs_alloc(h, &d.Mx, W)) || (rc = qs_alloc(h, &d.My, W)) || (rc = qs_alloc(h, &d.sE, W)) ||
-        (rc = qs_alloc(h, &d.sE2, W)) || (rc = qs_alloc(h, &d.sM, W)) || (rc = qs_alloc(h, &d.sM2, W)) ||
-        (rc = qs_alloc(h, &d.sM4, W)) || (rc = qs_alloc(h, &d.n_meas, W)) || (rc = qs_alloc(h, &d.prop, W)) ||
-        (rc = qs_alloc(h, &d.acc, W)) || (rc = qs_alloc(h, &d.n_series, W)) ||
-        (rc = qs_alloc(h, &d.ser, (size_t)3 * h->cap * W)) || (rc = qs_alloc(h, &h->site, (size_t)N)) ||
-        (rc = qs_alloc(h, &h->rows, (size_t)N * MAX_Z)) || (rc = qs_alloc(h, &h->off, (size_t)MAX_COLOURS + 1)) ||
-        (rc = qs_alloc(h, &h->bonds, bonds_h.size())) || (rc = qs_alloc(h, &h->e_q30, (size_t)q)) ||
-        (rc = qs_alloc(h, &h->cs_q30, (size_t)q)) || (rc = qs_alloc(h, &h->confs, W)) ||
-        (rc = qs_alloc(h, &h->nbr_site, (size_t)N * MAX_Z)) || (rc = qs_alloc(h, &h->ca.prop, W)) ||
-        (rc = qs_alloc(h, &h->ca.acc, W)) || (rc = qs_alloc(h, &h->ca.sum_size, W)) ||
-        (rc = qs_alloc(h, &h->ca.cursor, W)))
+    if ((rc = mc_alloc(h, &d.conf, (size_t)h->Nw * W)) || (rc = mc_alloc(h, &d.wt, (size_t)q * q * W)) ||
+        (rc = mc_alloc(h, &d.key, W)) || (rc = mc_alloc(h, &d.cursor, W)) || (rc = mc_alloc(h, &d.E, W)) ||
+        (rc = mc_alloc(h, &d.Mx, W)) || (rc = mc_alloc(h, &d.My, W)) || (rc = mc_alloc(h, &d.sE, W)) ||
+        (rc = mc_alloc(h, &d.sE2, W)) || (rc = mc_alloc(h, &d.sM, W)) || (rc = mc_alloc(h, &d.sM2, W)) ||
+        (rc = mc_alloc(h, &d.sM4, W)) || (rc = mc_alloc(h, &d.n_meas, W)) || (rc = mc_alloc(h, &d.prop, W)) ||
+        (rc = mc_alloc(h, &d.acc, W)) || (rc = mc_alloc(h, &d.n_series, W)) ||
+        (rc = mc_alloc(h, &d.ser, (size_t)3 * h->cap * W)) || (rc = mc_alloc(h, &h->site, (size_t)N)) ||
+        (rc = mc_alloc(h, &h->rows, (size_t)N * MAX_Z)) || (rc = mc_alloc(h, &h->off, (size_t)MAX_COLOURS + 1)) ||
+        (rc = mc_alloc(h, &h->bonds, bonds_h.size())) || (rc = mc_alloc(h, &h->e_q30, (size_t)q)) ||
+        (rc = mc_alloc(h, &h->cs_q30, (size_t)q)) || (rc = mc_alloc(h, &h->confs, W)) ||
+        (rc = mc_alloc(h, &h->nbr_site, (size_t)N * MAX_Z)) || (rc = mc_alloc(h, &h->ca.prop, W)) ||
+        (rc = mc_alloc(h, &h->ca.acc, W)) || (rc = mc_alloc(h, &h->ca.sum_size, W)) ||
+        (rc = mc_alloc(h, &h->ca.cursor, W)))
         return bail(rc);
     h->ca.nbr = h->nbr_site;
     h->ca.rate = 0;
-    std::vector<int> nbr_site((size_t)N * MAX_Z, 0);
-    for (int i = 0; i < N; ++i)
-        for (int k = 0; k < z; ++k) nbr_site[(size_t)i * MAX_Z + k] = nbr[(size_t)i * z + k];
+    const std::vector<int> nbr_site = mc_tables::padded_rows(nbr, N, z, N);
     std::vector<double> ones((size_t)q * q * W, 1.0);  // beta = 0
     if (hipMemcpyAsync(d.wt, ones.data(), ones.size() * 8, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
         hipMemcpyAsync(h->nbr_site, nbr_site.data(), nbr_site.size() * 4, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
@@ -751,43 +637,32 @@ int dqmc_qs_create(const dqmc_qs_params *p, dqmc_qs_handle **out)
         hipMemcpyAsync(h->e_q30, h->e_h.data(), (size_t)q * 8, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
         hipMemcpyAsync(h->cs_q30, cs_h.data(), (size_t)q * 8, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
         hipStreamSynchronize(h->stream) != hipSuccess)
-        return bail(qs_fail(h, DQMC_ERR_HIP, f + ": table upload failed"));
-    if ((rc = qs_put_colouring(h, site, rows, off, p->n_colours, largest))) return bail(rc);
+        return bail(mc_fail(h, DQMC_ERR_HIP, f + ": table upload failed"));
+    if ((rc = qs_put_colouring(h, colouring, p->n_colours))) return bail(rc);
     if ((rc = qs_launch_observables(h, -1))) return bail(rc);  // all sites in state 0
     if (hipStreamSynchronize(h->stream) != hipSuccess)
-        return bail(qs_fail(h, DQMC_ERR_HIP, f + ": device initialisation failed"));
+        return bail(mc_fail(h, DQMC_ERR_HIP, f + ": device initialisation failed"));
     *out = h;
     return DQMC_OK;
 }
 
-int dqmc_qs_destroy(dqmc_qs_handle *h)
-{
-    if (!h) return DQMC_OK;
-    if (h->stream) {
-        (void)hipSetDevice(h->device);
-        (void)hipStreamSynchronize(h->stream);
-    }
-    for (void *p : h->allocs) (void)hipFree(p);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
-    return DQMC_OK;
-}
+int dqmc_qs_destroy(dqmc_qs_handle *h) { return mc_destroy(h); }
 
 int dqmc_qs_seed(dqmc_qs_handle *h, int32_t walker, uint64_t seed)
 {
-    if (int rc = qs_walker(h, walker, "dqmc_qs_seed")) return rc;
-    QCHK(hipSetDevice(h->device));
-    if (int rc = qs_put<unsigned long long>(h, h->d.key, walker, seed)) return rc;
+    if (int rc = mc_walker(h, walker, "dqmc_qs_seed")) return rc;
+    MCHK(hipSetDevice(h->device));
+    if (int rc = mc_put<unsigned long long>(h, h->d.key, 0, walker, seed)) return rc;
     h->confs_h[walker] = 0ull;
-    if (int rc = qs_put<unsigned long long>(h, h->ca.cursor, walker, 0ull)) return rc;
-    return qs_put<unsigned long long>(h, h->d.cursor, walker, 0ull);
+    if (int rc = mc_put<unsigned long long>(h, h->ca.cursor, 0, walker, 0ull)) return rc;
+    return mc_put<unsigned long long>(h, h->d.cursor, 0, walker, 0ull);
 }
 
 int dqmc_qs_set_beta(dqmc_qs_handle *h, int32_t walker, double beta)
 {
-    if (int rc = qs_walker(h, walker, "dqmc_qs_set_beta")) return rc;
+    if (int rc = mc_walker(h, walker, "dqmc_qs_set_beta")) return rc;
     if (!std::isfinite(beta) || beta < 0.0)
-        return qs_fail(h, DQMC_ERR_INVALID, "dqmc_qs_set_beta: beta must be finite and >= 0");
+        return mc_fail(h, DQMC_ERR_INVALID, "dqmc_qs_set_beta: beta must be finite and >= 0");
     const int q = h->q;
     std::vector<double> wt((size_t)q * q);
     for (int a = 0; a < q; ++a)
@@ -796,23 +671,23 @@ int dqmc_qs_set_beta(dqmc_qs_handle *h, int32_t walker, double beta)
             const double y = -beta * x;                                   // one rounding
             wt[(size_t)a * q + b] = exp(y);
         }
-    QCHK(hipSetDevice(h->device));
-    QCHK(hipMemcpyAsync(h->d.wt + (size_t)walker * q * q, wt.data(), wt.size() * 8, hipMemcpyHostToDevice, h->stream));
-    QCHK(hipStreamSynchronize(h->stream));
+    MCHK(hipSetDevice(h->device));
+    MCHK(hipMemcpyAsync(h->d.wt + (size_t)walker * q * q, wt.data(), wt.size() * 8, hipMemcpyHostToDevice, h->stream));
+    MCHK(hipStreamSynchronize(h->stream));
     return DQMC_OK;
 }
 
 int dqmc_qs_rand_conf(dqmc_qs_handle *h, int32_t walker)
 {
-    if (!h) return qs_fail(nullptr, DQMC_ERR_INVALID, "dqmc_qs_rand_conf: null handle");
-    if (walker >= h->W) return qs_fail(h, DQMC_ERR_INVALID, "dqmc_qs_rand_conf: walker out of range");
-    QCHK(hipSetDevice(h->device));
-    QCHK(hipMemcpyAsync(h->confs, h->confs_h.data(), (size_t)h->W * 8, hipMemcpyHostToDevice, h->stream));
+    if (!h) return mc_fail(nullptr, DQMC_ERR_INVALID, "dqmc_qs_rand_conf: null handle");
+    if (walker >= h->W) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_qs_rand_conf: walker out of range");
+    MCHK(hipSetDevice(h->device));
+    MCHK(hipMemcpyAsync(h->confs, h->confs_h.data(), (size_t)h->W * 8, hipMemcpyHostToDevice, h->stream));
     hipLaunchKernelGGL(qs_rand_conf_kernel, dim3(walker >= 0 ? 1 : h->W), dim3(THREADS), 0, h->stream, h->d,
                        (const unsigned long long *)h->confs, (int)walker);
-    QCHK(hipGetLastError());
+    MCHK(hipGetLastError());
     if (int rc = qs_launch_observables(h, walker)) return rc;
-    QCHK(hipStreamSynchronize(h->stream));
+    MCHK(hipStreamSynchronize(h->stream));
     for (int w = 0; w < h->W; ++w)
         if (walker < 0 || w == walker) h->confs_h[w] += 1;
     return DQMC_OK;
@@ -820,54 +695,54 @@ int dqmc_qs_rand_conf(dqmc_qs_handle *h, int32_t walker)
 
 int dqmc_qs_set_conf(dqmc_qs_handle *h, int32_t walker, const uint8_t *conf)
 {
-    if (int rc = qs_walker(h, walker, "dqmc_qs_set_conf")) return rc;
-    if (!conf) return qs_fail(h, DQMC_ERR_INVALID, "dqmc_qs_set_conf: null conf");
+    if (int rc = mc_walker(h, walker, "dqmc_qs_set_conf")) return rc;
+    if (!conf) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_qs_set_conf: null conf");
     std::vector<unsigned int> words((size_t)h->Nw, 0u);
     for (int i = 0; i < h->N; ++i) {
         if (conf[i] >= h->q)
-            return qs_fail(h, DQMC_ERR_INVALID, "dqmc_qs_set_conf: the state of site " + std::to_string(i) +
+            return mc_fail(h, DQMC_ERR_INVALID, "dqmc_qs_set_conf: the state of site " + std::to_string(i) +
                                                     " (0-based) is not below q");
         words[i >> 2] |= (unsigned int)conf[i] << (8 * (i & 3));
     }
-    QCHK(hipSetDevice(h->device));
-    QCHK(hipMemcpyAsync(h->d.conf + (size_t)walker * h->Nw, words.data(), words.size() * 4, hipMemcpyHostToDevice,
+    MCHK(hipSetDevice(h->device));
+    MCHK(hipMemcpyAsync(h->d.conf + (size_t)walker * h->Nw, words.data(), words.size() * 4, hipMemcpyHostToDevice,
                         h->stream));
     if (int rc = qs_launch_observables(h, walker)) return rc;
-    QCHK(hipStreamSynchronize(h->stream));
+    MCHK(hipStreamSynchronize(h->stream));
     return DQMC_OK;
 }
 
 int dqmc_qs_get_conf(dqmc_qs_handle *h, int32_t walker, uint8_t *conf)
 {
-    if (int rc = qs_walker(h, walker, "dqmc_qs_get_conf")) return rc;
-    if (!conf) return qs_fail(h, DQMC_ERR_INVALID, "dqmc_qs_get_conf: null conf");
+    if (int rc = mc_walker(h, walker, "dqmc_qs_get_conf")) return rc;
+    if (!conf) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_qs_get_conf: null conf");
     std::vector<unsigned int> words((size_t)h->Nw, 0u);
-    QCHK(hipSetDevice(h->device));
-    QCHK(hipMemcpyAsync(words.data(), h->d.conf + (size_t)walker * h->Nw, words.size() * 4, hipMemcpyDeviceToHost,
+    MCHK(hipSetDevice(h->device));
+    MCHK(hipMemcpyAsync(words.data(), h->d.conf + (size_t)walker * h->Nw, words.size() * 4, hipMemcpyDeviceToHost,
                         h->stream));
-    QCHK(hipStreamSynchronize(h->stream));
+    MCHK(hipStreamSynchronize(h->stream));
     for (int i = 0; i < h->N; ++i) conf[i] = (uint8_t)(words[i >> 2] >> (8 * (i & 3)));
     return DQMC_OK;
 }
 
 int dqmc_qs_set_colouring(dqmc_qs_handle *h, const int32_t *colour, int32_t n_colours)
 {
-    if (!h) return qs_fail(nullptr, DQMC_ERR_INVALID, "dqmc_qs_set_colouring: null handle");
-    std::vector<int> site, rows, off;
-    int largest = 0;
-    if (int rc = qs_colour_tables(h, "dqmc_qs_set_colouring", h->nbr_h, h->N, h->z, colour, n_colours, site, rows, off,
-                                  &largest))
-        return rc;
-    return qs_put_colouring(h, site, rows, off, n_colours, largest);
+    if (!h) return mc_fail(nullptr, DQMC_ERR_INVALID, "dqmc_qs_set_colouring: null handle");
+    mc_tables::Colouring t;
+    std::string msg;
+    if (!mc_tables::colour_tables("dqmc_qs_set_colouring", h->nbr_h, h->N, h->z, colour, n_colours, MAX_COLOURS + 1, THREADS, t,
+                                  &msg))
+        return mc_fail(h, DQMC_ERR_INVALID, msg);
+    return qs_put_colouring(h, t, n_colours);
 }
 
 int dqmc_qs_sweep(dqmc_qs_handle *h, int32_t n_sweeps, int64_t first_sweep_index, int64_t thermalization,
                   int32_t measure_rate)
 {
-    if (!h) return qs_fail(nullptr, DQMC_ERR_INVALID, "dqmc_qs_sweep: null handle");
+    if (!h) return mc_fail(nullptr, DQMC_ERR_INVALID, "dqmc_qs_sweep: null handle");
     if (n_sweeps < 0 || measure_rate < 1 || first_sweep_index < 1)
-        return qs_fail(h, DQMC_ERR_INVALID, "dqmc_qs_sweep: n_sweeps >= 0, first_sweep_index >= 1, measure_rate >= 1");
-    QCHK(hipSetDevice(h->device));
+        return mc_fail(h, DQMC_ERR_INVALID, "dqmc_qs_sweep: n_sweeps >= 0, first_sweep_index >= 1, measure_rate >= 1");
+    MCHK(hipSetDevice(h->device));
     const double per_sweep = ((double)h->N + QS_SWEEP_OVERHEAD) * std::max(1.0, (double)h->W / QS_RESIDENT_WALKERS);
     const int chunk = (int)std::max(1.0, std::min((double)n_sweeps, std::floor(QS_LAUNCH_BUDGET / per_sweep)));
     const size_t lds = sweep_lds_bytes(h->q, h->Nw);
@@ -883,28 +758,28 @@ int dqmc_qs_sweep(dqmc_qs_handle *h, int32_t n_sweeps, int64_t first_sweep_index
                                (const int *)h->site, (const int4 *)h->rows, (const int *)h->off,
                                (const long long *)h->e_q30, (const int2 *)h->cs_q30, h->C, n,
                                (long long)(first_sweep_index + done), (long long)thermalization, (int)measure_rate, h->ca);
-        QCHK(hipGetLastError());
+        MCHK(hipGetLastError());
         done += n;
     }
-    QCHK(hipStreamSynchronize(h->stream));
+    MCHK(hipStreamSynchronize(h->stream));
     return DQMC_OK;
 }
 
 int dqmc_qs_get_stats(dqmc_qs_handle *h, int32_t walker, dqmc_qs_stats *out)
 {
-    if (int rc = qs_walker(h, walker, "dqmc_qs_get_stats")) return rc;
-    if (!out) return qs_fail(h, DQMC_ERR_INVALID, "dqmc_qs_get_stats: null out");
-    QCHK(hipSetDevice(h->device));
+    if (int rc = mc_walker(h, walker, "dqmc_qs_get_stats")) return rc;
+    if (!out) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_qs_get_stats: null out");
+    MCHK(hipSetDevice(h->device));
     const DevState &d = h->d;
     long long E = 0, Mx = 0, My = 0, n_meas = 0, prop = 0, acc = 0, n_series = 0;
     unsigned long long cursor = 0;
     int rc = 0;
-    if ((rc = qs_get(h, d.E, walker, &E)) || (rc = qs_get(h, d.Mx, walker, &Mx)) || (rc = qs_get(h, d.My, walker, &My)) ||
-        (rc = qs_get(h, d.sE, walker, &out->sum_E)) || (rc = qs_get(h, d.sE2, walker, &out->sum_E2)) ||
-        (rc = qs_get(h, d.sM, walker, &out->sum_absM)) || (rc = qs_get(h, d.sM2, walker, &out->sum_M2)) ||
-        (rc = qs_get(h, d.sM4, walker, &out->sum_M4)) || (rc = qs_get(h, d.n_meas, walker, &n_meas)) ||
-        (rc = qs_get(h, d.prop, walker, &prop)) || (rc = qs_get(h, d.acc, walker, &acc)) ||
-        (rc = qs_get(h, d.n_series, walker, &n_series)) || (rc = qs_get(h, d.cursor, walker, &cursor)))
+    if ((rc = mc_get(h, d.E, 0, walker, &E)) || (rc = mc_get(h, d.Mx, 0, walker, &Mx)) || (rc = mc_get(h, d.My, 0, walker, &My)) ||
+        (rc = mc_get(h, d.sE, 0, walker, &out->sum_E)) || (rc = mc_get(h, d.sE2, 0, walker, &out->sum_E2)) ||
+        (rc = mc_get(h, d.sM, 0, walker, &out->sum_absM)) || (rc = mc_get(h, d.sM2, 0, walker, &out->sum_M2)) ||
+        (rc = mc_get(h, d.sM4, 0, walker, &out->sum_M4)) || (rc = mc_get(h, d.n_meas, 0, walker, &n_meas)) ||
+        (rc = mc_get(h, d.prop, 0, walker, &prop)) || (rc = mc_get(h, d.acc, 0, walker, &acc)) ||
+        (rc = mc_get(h, d.n_series, 0, walker, &n_series)) || (rc = mc_get(h, d.cursor, 0, walker, &cursor)))
         return rc;
     out->energy_q30 = E;
     out->mx_q30 = Mx;
@@ -922,16 +797,16 @@ int dqmc_qs_get_stats(dqmc_qs_handle *h, int32_t walker, dqmc_qs_stats *out)
 int dqmc_qs_get_series(dqmc_qs_handle *h, int32_t walker, int64_t *energy_q30, int64_t *mx_q30, int64_t *my_q30,
                        int64_t *n_recorded)
 {
-    if (int rc = qs_walker(h, walker, "dqmc_qs_get_series")) return rc;
-    QCHK(hipSetDevice(h->device));
+    if (int rc = mc_walker(h, walker, "dqmc_qs_get_series")) return rc;
+    MCHK(hipSetDevice(h->device));
     long long n = 0;
-    if (int rc = qs_get(h, h->d.n_series, walker, &n)) return rc;
+    if (int rc = mc_get(h, h->d.n_series, 0, walker, &n)) return rc;
     if (n_recorded) *n_recorded = n;
     if (n > 0 && (energy_q30 || mx_q30 || my_q30)) {
         std::vector<long long> rec((size_t)3 * n);
-        QCHK(hipMemcpyAsync(rec.data(), h->d.ser + (size_t)walker * h->cap * 3, rec.size() * 8, hipMemcpyDeviceToHost,
+        MCHK(hipMemcpyAsync(rec.data(), h->d.ser + (size_t)walker * h->cap * 3, rec.size() * 8, hipMemcpyDeviceToHost,
                             h->stream));
-        QCHK(hipStreamSynchronize(h->stream));
+        MCHK(hipStreamSynchronize(h->stream));
         for (long long k = 0; k < n; ++k) {
             if (energy_q30) energy_q30[k] = rec[3 * k];
             if (mx_q30) mx_q30[k] = rec[3 * k + 1];
@@ -943,22 +818,22 @@ int dqmc_qs_get_series(dqmc_qs_handle *h, int32_t walker, int64_t *energy_q30, i
 
 int dqmc_qs_reset_accumulators(dqmc_qs_handle *h)
 {
-    if (!h) return qs_fail(nullptr, DQMC_ERR_INVALID, "dqmc_qs_reset_accumulators: null handle");
-    QCHK(hipSetDevice(h->device));
+    if (!h) return mc_fail(nullptr, DQMC_ERR_INVALID, "dqmc_qs_reset_accumulators: null handle");
+    MCHK(hipSetDevice(h->device));
     const DevState &d = h->d;
     const size_t W = h->W;
-    for (double *p : {d.sE, d.sE2, d.sM, d.sM2, d.sM4}) QCHK(hipMemsetAsync(p, 0, W * 8, h->stream));
-    for (long long *p : {d.n_meas, d.n_series}) QCHK(hipMemsetAsync(p, 0, W * 8, h->stream));
-    QCHK(hipStreamSynchronize(h->stream));
+    for (double *p : {d.sE, d.sE2, d.sM, d.sM2, d.sM4}) MCHK(hipMemsetAsync(p, 0, W * 8, h->stream));
+    for (long long *p : {d.n_meas, d.n_series}) MCHK(hipMemsetAsync(p, 0, W * 8, h->stream));
+    MCHK(hipStreamSynchronize(h->stream));
     return DQMC_OK;
 }
 
 int dqmc_qs_set_cluster_rate(dqmc_qs_handle *h, int32_t rate)
 {
-    if (!h) return qs_fail(nullptr, DQMC_ERR_INVALID, "dqmc_qs_set_cluster_rate: null handle");
-    if (rate < 0) return qs_fail(h, DQMC_ERR_INVALID, "dqmc_qs_set_cluster_rate: rate must be >= 0");
+    if (!h) return mc_fail(nullptr, DQMC_ERR_INVALID, "dqmc_qs_set_cluster_rate: null handle");
+    if (rate < 0) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_qs_set_cluster_rate: rate must be >= 0");
     if (rate > 0) {
-        QCHK(hipSetDevice(h->device));
+        MCHK(hipSetDevice(h->device));
         if (int rc = qs_reserve_cluster_lds(h, "dqmc_qs_set_cluster_rate")) return rc;
     }
     h->ca.rate = rate;
@@ -967,28 +842,28 @@ int dqmc_qs_set_cluster_rate(dqmc_qs_handle *h, int32_t rate)
 
 int dqmc_qs_cluster_move(dqmc_qs_handle *h, int32_t walker)
 {
-    if (!h) return qs_fail(nullptr, DQMC_ERR_INVALID, "dqmc_qs_cluster_move: null handle");
-    if (walker >= h->W) return qs_fail(h, DQMC_ERR_INVALID, "dqmc_qs_cluster_move: walker out of range");
-    QCHK(hipSetDevice(h->device));
+    if (!h) return mc_fail(nullptr, DQMC_ERR_INVALID, "dqmc_qs_cluster_move: null handle");
+    if (walker >= h->W) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_qs_cluster_move: walker out of range");
+    MCHK(hipSetDevice(h->device));
     if (int rc = qs_reserve_cluster_lds(h, "dqmc_qs_cluster_move")) return rc;
     const size_t lds = sweep_lds_bytes(h->q, h->Nw) + cluster_lds_bytes(h->N);
     hipLaunchKernelGGL(qs_cluster_move_kernel, dim3(walker >= 0 ? 1 : h->W), dim3(h->threads), lds, h->stream, h->d,
                        (const long long *)h->e_q30, (const int2 *)h->cs_q30, h->ca, (int)walker);
-    QCHK(hipGetLastError());
-    QCHK(hipStreamSynchronize(h->stream));
+    MCHK(hipGetLastError());
+    MCHK(hipStreamSynchronize(h->stream));
     return DQMC_OK;
 }
 
 int dqmc_qs_get_cluster_stats(dqmc_qs_handle *h, int32_t walker, dqmc_qs_cluster_stats *out)
 {
-    if (int rc = qs_walker(h, walker, "dqmc_qs_get_cluster_stats")) return rc;
-    if (!out) return qs_fail(h, DQMC_ERR_INVALID, "dqmc_qs_get_cluster_stats: null out");
-    QCHK(hipSetDevice(h->device));
+    if (int rc = mc_walker(h, walker, "dqmc_qs_get_cluster_stats")) return rc;
+    if (!out) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_qs_get_cluster_stats: null out");
+    MCHK(hipSetDevice(h->device));
     long long prop = 0, acc = 0, size = 0;
     unsigned long long m = 0;
     int rc = 0;
-    if ((rc = qs_get(h, h->ca.prop, walker, &prop)) || (rc = qs_get(h, h->ca.acc, walker, &acc)) ||
-        (rc = qs_get(h, h->ca.sum_size, walker, &size)) || (rc = qs_get(h, h->ca.cursor, walker, &m)))
+    if ((rc = mc_get(h, h->ca.prop, 0, walker, &prop)) || (rc = mc_get(h, h->ca.acc, 0, walker, &acc)) ||
+        (rc = mc_get(h, h->ca.sum_size, 0, walker, &size)) || (rc = mc_get(h, h->ca.cursor, 0, walker, &m)))
         return rc;
     out->prop_global = prop;
     out->acc_global = acc;
@@ -999,9 +874,9 @@ int dqmc_qs_get_cluster_stats(dqmc_qs_handle *h, int32_t walker, dqmc_qs_cluster
 
 int dqmc_qs_synchronize(dqmc_qs_handle *h)
 {
-    if (!h) return qs_fail(nullptr, DQMC_ERR_INVALID, "dqmc_qs_synchronize: null handle");
-    QCHK(hipSetDevice(h->device));
-    QCHK(hipStreamSynchronize(h->stream));
+    if (!h) return mc_fail(nullptr, DQMC_ERR_INVALID, "dqmc_qs_synchronize: null handle");
+    MCHK(hipSetDevice(h->device));
+    MCHK(hipStreamSynchronize(h->stream));
     return DQMC_OK;
 }
 

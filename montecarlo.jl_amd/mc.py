@@ -123,7 +123,146 @@ def _delta_var(grad, vx, vy, cov):
     return max(var, 0.0) if var == var else var
 
 
-class MC:
+class _MCBase:
+    """What MC and qstate.QStateMC share: the handle of one engine's ABI family (`_abi`: "dqmc_mc_" / "dqmc_qs_", whose
+    create, destroy, last_error, seed, set_beta, rand_conf, sweep, reset_accumulators and synchronize have one shape),
+    the temperatures, the colouring argument and the run! loop.  A subclass has stats(walker) with acc_local and
+    prop_local."""
+    _abi = None
+
+    def _call(self, name, *args):
+        self._c(getattr(lib(), self._abi + name)(self._h, *args))
+
+    @staticmethod
+    def _resolve_beta(beta, T):
+        if (beta is None) == (T is None):
+            raise ValueError("MC needs exactly one of beta and T")
+        if T is not None:
+            beta = (1.0 / np.asarray(T, dtype=float)) if np.ndim(T) else 1.0 / float(T)
+        return np.asarray(beta, dtype=float)
+
+    def _init_common(self, model, beta, n_walkers, seed, first_walker, thermalization, sweeps, measure_rate, print_rate,
+                     series_capacity):
+        betas = np.broadcast_to(beta, (n_walkers,)).copy()
+        if not np.all(np.isfinite(betas)) or np.any(betas < 0):
+            raise ValueError("beta must be finite and >= 0")
+        if measure_rate < 1:
+            raise ValueError("measure_rate must be >= 1")
+        self.model = model
+        self.N = len(model.l)
+        self.n_walkers = n_walkers
+        self.betas = betas
+        self.beta = float(betas[0]) if np.all(betas == betas[0]) else betas
+        self.seeds = [seed + first_walker + w for w in range(n_walkers)]
+        self.thermalization, self.sweeps, self.measure_rate = thermalization, sweeps, measure_rate
+        self.print_rate = print_rate
+        self.last_sweep = 0
+        self.series_capacity = series_capacity
+        self._neighs = np.asfortranarray(np.asarray(model.l.neighs, dtype=np.int64))
+        self._bonds = np.asfortranarray(np.asarray(model.l.bonds, dtype=np.int64)[:, :2])
+
+    def _create(self, params):
+        """the handle for `params`, every walker seeded, at its beta and with a random configuration (init!, MC.jl:61,74)"""
+        h = C.c_void_p()
+        self._h = None
+        rc = getattr(lib(), self._abi + "create")(C.byref(params), C.byref(h))
+        if rc != 0:
+            msg = getattr(lib(), self._abi + "last_error")(None)
+            raise DQMCError(rc, msg.decode() if msg else "")
+        self._h = h
+        for w in range(self.n_walkers):
+            self._call("seed", w, self.seeds[w])
+            self._call("set_beta", w, float(self.betas[w]))
+        self._call("rand_conf", -1)
+
+    def _colours(self, colouring, what):
+        """(int32 [N], n_colours) of a colouring argument; None: greedy_colouring(lattice)"""
+        col = greedy_colouring(self.model.l) if colouring is None else colouring
+        col = np.ascontiguousarray(np.asarray(col).reshape(-1), dtype=np.int32)
+        if col.size != self.N:
+            raise DQMCError(ERR_INVALID, "%s: expected %d colours" % (what, self.N))
+        return col, (int(col.max()) + 1 if col.size else 0)
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            getattr(lib(), self._abi + "destroy")(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _c(self, rc):
+        if rc != 0:
+            msg = getattr(lib(), self._abi + "last_error")(self._h)
+            raise DQMCError(rc, msg.decode() if msg else "")
+
+    # ---- state
+    def seed(self, walker, seed):
+        """key the walker's streams with `seed`, every cursor at 0 (the configuration stays)"""
+        self._call("seed", walker, seed)
+        self.seeds[walker] = seed
+
+    def set_beta(self, walker, beta):
+        self._call("set_beta", walker, float(beta))
+        self.betas[walker] = float(beta)
+
+    def rand_conf(self, walker=-1):
+        self._call("rand_conf", walker)
+
+    def reset_accumulators(self):
+        self._call("reset_accumulators")
+
+    def synchronize(self):
+        self._call("synchronize")
+
+    # ---- the loop
+    def sweep(self, n=1):
+        """n x sweep(mc) with run!'s measurement rule, continuing from last_sweep"""
+        if n > 0:
+            self._call("sweep", n, self.last_sweep + 1, self.thermalization, self.measure_rate)
+            self.last_sweep += n
+
+    def _print_mark(self):
+        """run(verbose=True): what _print_more needs from before the first print window"""
+        return None
+
+    def _print_more(self, mark):
+        """run(verbose=True): the lines behind the local acceptance rate; returns the next window's mark"""
+        return mark
+
+    def _run(self, verbose, recorder, sweeps, thermalization):
+        if sweeps is not None:
+            self.sweeps = sweeps
+        if thermalization is not None:
+            self.thermalization = thermalization
+        total = self.thermalization + self.sweeps
+        t0 = time.time()
+        mark = self._print_mark() if verbose else None
+        while self.last_sweep < total:
+            stop = total
+            if recorder is not None and getattr(recorder, "rate", None):
+                nxt = max(self.last_sweep + 1, self.thermalization + 1)
+                r = recorder.rate
+                stop = min(total, ((nxt + r - 1) // r) * r)
+            elif verbose and self.print_rate:
+                stop = min(total, (self.last_sweep // self.print_rate + 1) * self.print_rate)
+            self.sweep(stop - self.last_sweep)
+            i = self.last_sweep
+            if recorder is not None and i > self.thermalization:
+                recorder.push(self, i)
+            if verbose and self.print_rate and i % self.print_rate == 0:
+                st = self.stats(0)
+                print("\t%d\n\t\tsweep dur: %.3fs\n\t\tacc rate (local) : %.1f%%" %
+                      (i, (time.time() - t0) / self.print_rate, 100.0 * st.acc_local / max(st.prop_local, 1)))
+                t0 = time.time()
+                mark = self._print_more(mark)
+        return True
+
+
+class MC(_MCBase):
     """MC(model; beta | T, ...) (MC.jl:16-80) for `n_walkers` chains.  `beta` may be a sequence of n_walkers values
     (one temperature per walker).
 
@@ -156,6 +295,7 @@ class MC:
 
     With a q-state model (qstate.PottsModel, ClockModel, QStateModel) MC(...) returns a qstate.QStateMC: the engine of
     dqmc_qs_* with its own kernels.  With an IsingModel nothing changes."""
+    _abi = "dqmc_mc_"
 
     def __new__(cls, model, *args, **kwargs):
         if cls is MC and getattr(model, "is_qstate", False):
@@ -174,48 +314,20 @@ class MC:
                 "MC(cluster_moves=True, global_rate=...) runs the cluster move on a stream of its own")
         if cluster_moves and (int(global_rate) != global_rate or global_rate < 1):
             raise ValueError("MC(cluster_moves=True): global_rate must be an integer >= 1")
-        if (beta is None) == (T is None):
-            raise ValueError("MC needs exactly one of beta and T")
-        if T is not None:
-            beta = (1.0 / np.asarray(T, dtype=float)) if np.ndim(T) else 1.0 / float(T)
+        beta = self._resolve_beta(beta, T)
         if int(n_replicas) != n_replicas or int(exchange_rate) != exchange_rate:
             raise ValueError("MC: n_replicas and exchange_rate must be integers")
-        beta = np.asarray(beta, dtype=float)
         if n_replicas >= 2 and beta.ndim == 1 and len(beta) == n_replicas and n_walkers % n_replicas == 0:
             beta = np.tile(beta, n_walkers // n_replicas)  # one ladder's temperatures, the same in every ladder
-        betas = np.broadcast_to(beta, (n_walkers,)).copy()
-        if not np.all(np.isfinite(betas)) or np.any(betas < 0):
-            raise ValueError("beta must be finite and >= 0")
-        if measure_rate < 1:
-            raise ValueError("measure_rate must be >= 1")
-        self.model = model
-        self.N = len(model.l)
-        self.n_walkers = n_walkers
-        self.betas = betas
-        self.beta = float(betas[0]) if np.all(betas == betas[0]) else betas
-        self.seeds = [seed + first_walker + w for w in range(n_walkers)]
-        self.thermalization, self.sweeps, self.measure_rate = thermalization, sweeps, measure_rate
-        self.print_rate, self.global_moves, self.global_rate = print_rate, global_moves, global_rate
+        self._init_common(model, beta, n_walkers, seed, first_walker, thermalization, sweeps, measure_rate, print_rate,
+                          series_capacity)
+        self.global_moves, self.global_rate = global_moves, global_rate
         self.cluster_moves = bool(cluster_moves)
         self.n_replicas, self.exchange_rate = int(n_replicas), int(exchange_rate)
-        self.last_sweep = 0
-        self.series_capacity = series_capacity
-        self._neighs = np.asfortranarray(np.asarray(model.l.neighs, dtype=np.int64))
-        self._bonds = np.asfortranarray(np.asarray(model.l.bonds, dtype=np.int64)[:, :2])
-        p = McParams(n_sites=self.N, z=self._neighs.shape[0], n_walkers=n_walkers, device_id=device_id,
-                     n_bonds=self._bonds.shape[0], series_capacity=series_capacity,
-                     neighs=self._neighs.ctypes.data_as(C.POINTER(C.c_int64)),
-                     bonds=self._bonds.ctypes.data_as(C.POINTER(C.c_int64)))
-        h = C.c_void_p()
-        rc = lib().dqmc_mc_create(C.byref(p), C.byref(h))
-        if rc != 0:
-            msg = lib().dqmc_mc_last_error(None)
-            raise DQMCError(rc, msg.decode() if msg else "")
-        self._h = h
-        for w in range(n_walkers):
-            self._c(lib().dqmc_mc_seed(self._h, w, self.seeds[w]))
-            self._c(lib().dqmc_mc_set_beta(self._h, w, float(betas[w])))
-        self._c(lib().dqmc_mc_rand_conf(self._h, -1))  # mc.conf = rand(MC, m); init! (MC.jl:61,74)
+        self._create(McParams(n_sites=self.N, z=self._neighs.shape[0], n_walkers=n_walkers, device_id=device_id,
+                              n_bonds=self._bonds.shape[0], series_capacity=series_capacity,
+                              neighs=self._neighs.ctypes.data_as(C.POINTER(C.c_int64)),
+                              bonds=self._bonds.ctypes.data_as(C.POINTER(C.c_int64))))
         if self.cluster_moves:
             self._c(lib().dqmc_mc_set_global_rate(self._h, int(global_rate)))
         if self.n_replicas or self.exchange_rate:
@@ -229,35 +341,7 @@ class MC:
         if binning:
             self.enable_binning(binning_capacity)
 
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            lib().dqmc_mc_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _c(self, rc):
-        if rc != 0:
-            msg = lib().dqmc_mc_last_error(self._h)
-            raise DQMCError(rc, msg.decode() if msg else "")
-
     # ---- state
-    def seed(self, walker, seed):
-        """key the walker's stream with `seed`, cursor at draw 0 (the configuration stays)"""
-        self._c(lib().dqmc_mc_seed(self._h, walker, seed))
-        self.seeds[walker] = seed
-
-    def set_beta(self, walker, beta):
-        self._c(lib().dqmc_mc_set_beta(self._h, walker, float(beta)))
-        self.betas[walker] = float(beta)
-
-    def rand_conf(self, walker=-1):
-        self._c(lib().dqmc_mc_rand_conf(self._h, walker))
-
     def conf(self, walker=0):
         out = np.zeros(self.N, dtype=np.int8)
         self._c(lib().dqmc_mc_get_conf(self._h, walker, out.ctypes.data_as(C.c_void_p)))
@@ -288,48 +372,25 @@ class MC:
         return int(self.stats(walker).uniforms_used)
 
     # ---- the loop
-    def sweep(self, n=1):
-        """n x sweep(mc) with run!'s measurement rule, continuing from last_sweep"""
-        if n > 0:
-            self._c(lib().dqmc_mc_sweep(self._h, n, self.last_sweep + 1, self.thermalization, self.measure_rate))
-            self.last_sweep += n
-
     def run(self, verbose=False, recorder=None, sweeps=None, thermalization=None):
         """run!(mc) (MC.jl:190-315) for every walker, resuming after last_sweep; a recorder gets
         push(mc, i) after each sweep i > thermalization (of walker 0, ConfigRecorder keeps every rate-th)"""
-        if sweeps is not None:
-            self.sweeps = sweeps
-        if thermalization is not None:
-            self.thermalization = thermalization
-        total = self.thermalization + self.sweeps
-        t0 = time.time()
-        if verbose and self.cluster_moves:
-            g = self.global_stats(0)
-            g0 = (g.acc_global, g.prop_global)
-        while self.last_sweep < total:
-            stop = total
-            if recorder is not None and getattr(recorder, "rate", None):
-                nxt = max(self.last_sweep + 1, self.thermalization + 1)
-                r = recorder.rate
-                stop = min(total, ((nxt + r - 1) // r) * r)
-            elif verbose and self.print_rate:
-                stop = min(total, (self.last_sweep // self.print_rate + 1) * self.print_rate)
-            self.sweep(stop - self.last_sweep)
-            i = self.last_sweep
-            if recorder is not None and i > self.thermalization:
-                recorder.push(self, i)
-            if verbose and self.print_rate and i % self.print_rate == 0:
-                st = self.stats(0)
-                print("\t%d\n\t\tsweep dur: %.3fs\n\t\tacc rate (local) : %.1f%%" %
-                      (i, (time.time() - t0) / self.print_rate, 100.0 * st.acc_local / max(st.prop_local, 1)))
-                t0 = time.time()
-                if self.cluster_moves:  # MC.jl:265-271: this print window, then overall
-                    g = self.global_stats(0)
-                    print("\t\tacc rate (global): %.1f%%\n\t\tacc rate (global, overall): %.1f%%" %
-                          (100.0 * (g.acc_global - g0[0]) / max(g.prop_global - g0[1], 1),
-                           100.0 * g.acc_global / max(g.prop_global, 1)))
-                    g0 = (g.acc_global, g.prop_global)
-        return True
+        return self._run(verbose, recorder, sweeps, thermalization)
+
+    def _print_mark(self):
+        if not self.cluster_moves:
+            return None
+        g = self.global_stats(0)
+        return g.acc_global, g.prop_global
+
+    def _print_more(self, mark):
+        if not self.cluster_moves:
+            return mark
+        g = self.global_stats(0)  # MC.jl:265-271: this print window, then overall
+        print("\t\tacc rate (global): %.1f%%\n\t\tacc rate (global, overall): %.1f%%" %
+              (100.0 * (g.acc_global - mark[0]) / max(g.prop_global - mark[1], 1),
+               100.0 * g.acc_global / max(g.prop_global, 1)))
+        return g.acc_global, g.prop_global
 
     def global_move(self, walker=-1):
         """global_move(mc, m, conf) (IsingModel.jl:104-140): one Wolff cluster move of one walker (walker < 0: every
@@ -381,11 +442,7 @@ class MC:
         if kind == "sequential":
             self._c(lib().dqmc_mc_set_update(self._h, 0, None, 0))
         else:
-            col = greedy_colouring(self.model.l) if colouring is None else colouring
-            col = np.ascontiguousarray(np.asarray(col).reshape(-1), dtype=np.int32)
-            if col.size != self.N:
-                raise DQMCError(ERR_INVALID, "set_update: expected %d colours" % self.N)
-            n = int(col.max()) + 1 if col.size else 0
+            col, n = self._colours(colouring, "set_update")
             self._c(lib().dqmc_mc_set_update(self._h, 1, col.ctypes.data_as(C.POINTER(C.c_int32)), n))
         self.update = kind
 
@@ -394,12 +451,6 @@ class MC:
         st = McUpdateStats()
         self._c(lib().dqmc_mc_get_update(self._h, walker, C.byref(st)))
         return st
-
-    def reset_accumulators(self):
-        self._c(lib().dqmc_mc_reset_accumulators(self._h))
-
-    def synchronize(self):
-        self._c(lib().dqmc_mc_synchronize(self._h))
 
     # ---- results
     def analysis(self, walker=0):

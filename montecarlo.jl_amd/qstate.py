@@ -8,12 +8,11 @@ Walker w draws from the Philox4x32-10 streams keyed by `seed + first_walker + w`
 its own."""
 import ctypes as C
 import math
-import time
 
 import numpy as np
 
 from ._lib import DQMCError, ERR_INVALID, QsClusterStats, QsParams, QsStats, lib
-from .mc import _choose_lattice, _llround, greedy_colouring
+from .mc import _MCBase, _choose_lattice, _llround
 
 Q_MAX = 64
 Q30 = 2.0 ** 30
@@ -121,7 +120,7 @@ _ISING_ONLY = "MC with a q-state model: %s is implemented for the IsingModel onl
               "binner, FSS and the sequential sweep are out of scope)"
 
 
-class QStateMC:
+class QStateMC(_MCBase):
     """What MC(model; beta | T, ...) returns for a q-state model: `n_walkers` chains, one workgroup each, swept colour
     class by colour class (`colouring=None`: greedy_colouring(lattice)) under the rule of include/dqmc_hip.h.  `beta`
     may be a sequence of n_walkers values.  `cluster_rate=k > 0` runs one reflection cluster move per walker behind every
@@ -129,6 +128,7 @@ class QStateMC:
     models, Wolff's reflection along the q lattice axes for clock models); 0, the default, runs none.  The Ising-only
     options (cluster_moves, global_moves, n_replicas, exchange_rate, fss, binning, update="sequential") raise
     NotImplementedError."""
+    _abi = "dqmc_qs_"
 
     def __init__(self, model, beta=None, T=None, n_walkers=1, seed=123, first_walker=0, thermalization=0, sweeps=1000,
                  measure_rate=1, print_rate=1000, global_moves=False, global_rate=5, device_id=0, series_capacity=0,
@@ -140,51 +140,21 @@ class QStateMC:
                          ('update="%s"' % update, update not in (None, "checkerboard"))):
             if on:
                 raise NotImplementedError(_ISING_ONLY % name)
-        if (beta is None) == (T is None):
-            raise ValueError("MC needs exactly one of beta and T")
-        if T is not None:
-            beta = (1.0 / np.asarray(T, dtype=float)) if np.ndim(T) else 1.0 / float(T)
-        betas = np.broadcast_to(np.asarray(beta, dtype=float), (n_walkers,)).copy()
-        if not np.all(np.isfinite(betas)) or np.any(betas < 0):
-            raise ValueError("beta must be finite and >= 0")
-        if measure_rate < 1:
-            raise ValueError("measure_rate must be >= 1")
+        self._init_common(model, self._resolve_beta(beta, T), n_walkers, seed, first_walker, thermalization, sweeps,
+                          measure_rate, print_rate, series_capacity)
         cluster_rate = self._cluster_rate(cluster_rate)
-        self.model = model
-        self.N = len(model.l)
         self.q = model.q
-        self.n_walkers = n_walkers
-        self.betas = betas
-        self.beta = float(betas[0]) if np.all(betas == betas[0]) else betas
-        self.seeds = [seed + first_walker + w for w in range(n_walkers)]
-        self.thermalization, self.sweeps, self.measure_rate = thermalization, sweeps, measure_rate
-        self.print_rate = print_rate
-        self.last_sweep = 0
-        self.series_capacity = series_capacity
         self.update = "checkerboard"
-        self._neighs = np.asfortranarray(np.asarray(model.l.neighs, dtype=np.int64))
-        self._bonds = np.asfortranarray(np.asarray(model.l.bonds, dtype=np.int64)[:, :2])
         col, n_col = self._colouring(colouring)
         self._tables = [np.ascontiguousarray(model.e_q30, dtype=np.int64), np.ascontiguousarray(model.c_q30, dtype=np.int32),
                         np.ascontiguousarray(model.s_q30, dtype=np.int32)]
         i32, i64 = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
-        p = QsParams(n_sites=self.N, z=self._neighs.shape[0], q=self.q, n_walkers=n_walkers, device_id=device_id,
-                     n_bonds=self._bonds.shape[0], series_capacity=series_capacity, n_colours=n_col,
-                     neighs=self._neighs.ctypes.data_as(i64), bonds=self._bonds.ctypes.data_as(i64),
-                     e_q30=self._tables[0].ctypes.data_as(i64), c_q30=self._tables[1].ctypes.data_as(i32),
-                     s_q30=self._tables[2].ctypes.data_as(i32), colour=col.ctypes.data_as(i32))
-        h = C.c_void_p()
-        self._h = None
-        rc = lib().dqmc_qs_create(C.byref(p), C.byref(h))
-        if rc != 0:
-            msg = lib().dqmc_qs_last_error(None)
-            raise DQMCError(rc, msg.decode() if msg else "")
-        self._h = h
+        self._create(QsParams(n_sites=self.N, z=self._neighs.shape[0], q=self.q, n_walkers=n_walkers, device_id=device_id,
+                              n_bonds=self._bonds.shape[0], series_capacity=series_capacity, n_colours=n_col,
+                              neighs=self._neighs.ctypes.data_as(i64), bonds=self._bonds.ctypes.data_as(i64),
+                              e_q30=self._tables[0].ctypes.data_as(i64), c_q30=self._tables[1].ctypes.data_as(i32),
+                              s_q30=self._tables[2].ctypes.data_as(i32), colour=col.ctypes.data_as(i32)))
         self.colouring = col
-        for w in range(n_walkers):
-            self._c(lib().dqmc_qs_seed(self._h, w, self.seeds[w]))
-            self._c(lib().dqmc_qs_set_beta(self._h, w, float(betas[w])))
-        self._c(lib().dqmc_qs_rand_conf(self._h, -1))
         self.cluster_rate = 0
         if cluster_rate:
             self.set_cluster_rate(cluster_rate)
@@ -196,41 +166,9 @@ class QStateMC:
         return int(k)
 
     def _colouring(self, colouring):
-        col = greedy_colouring(self.model.l) if colouring is None else colouring
-        col = np.ascontiguousarray(np.asarray(col).reshape(-1), dtype=np.int32)
-        if col.size != self.N:
-            raise DQMCError(ERR_INVALID, "colouring: expected %d colours" % self.N)
-        return col, (int(col.max()) + 1 if col.size else 0)
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            lib().dqmc_qs_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _c(self, rc):
-        if rc != 0:
-            msg = lib().dqmc_qs_last_error(self._h)
-            raise DQMCError(rc, msg.decode() if msg else "")
+        return self._colours(colouring, "colouring")
 
     # ---- state
-    def seed(self, walker, seed):
-        """key the walker's streams with `seed`, both cursors at 0 (the configuration stays)"""
-        self._c(lib().dqmc_qs_seed(self._h, walker, seed))
-        self.seeds[walker] = seed
-
-    def set_beta(self, walker, beta):
-        self._c(lib().dqmc_qs_set_beta(self._h, walker, float(beta)))
-        self.betas[walker] = float(beta)
-
-    def rand_conf(self, walker=-1):
-        self._c(lib().dqmc_qs_rand_conf(self._h, walker))
-
     def conf(self, walker=0):
         out = np.zeros(self.N, dtype=np.uint8)
         self._c(lib().dqmc_qs_get_conf(self._h, walker, out.ctypes.data_as(C.POINTER(C.c_uint8))))
@@ -284,38 +222,9 @@ class QStateMC:
         return st.mx_q30 / Q30, st.my_q30 / Q30
 
     # ---- the loop
-    def sweep(self, n=1):
-        """n sweeps with run!'s measurement rule, continuing from last_sweep"""
-        if n > 0:
-            self._c(lib().dqmc_qs_sweep(self._h, n, self.last_sweep + 1, self.thermalization, self.measure_rate))
-            self.last_sweep += n
-
     def run(self, verbose=False, sweeps=None, thermalization=None):
         """run!(mc) for every walker, resuming after last_sweep"""
-        if sweeps is not None:
-            self.sweeps = sweeps
-        if thermalization is not None:
-            self.thermalization = thermalization
-        total = self.thermalization + self.sweeps
-        t0 = time.time()
-        while self.last_sweep < total:
-            stop = total
-            if verbose and self.print_rate:
-                stop = min(total, (self.last_sweep // self.print_rate + 1) * self.print_rate)
-            self.sweep(stop - self.last_sweep)
-            i = self.last_sweep
-            if verbose and self.print_rate and i % self.print_rate == 0:
-                st = self.stats(0)
-                print("\t%d\n\t\tsweep dur: %.3fs\n\t\tacc rate (local) : %.1f%%" %
-                      (i, (time.time() - t0) / self.print_rate, 100.0 * st.acc_local / max(st.prop_local, 1)))
-                t0 = time.time()
-        return True
-
-    def reset_accumulators(self):
-        self._c(lib().dqmc_qs_reset_accumulators(self._h))
-
-    def synchronize(self):
-        self._c(lib().dqmc_qs_synchronize(self._h))
+        return self._run(verbose, None, sweeps, thermalization)
 
     # ---- results
     def analysis(self, walker=0):
