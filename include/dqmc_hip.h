@@ -1340,6 +1340,47 @@ int dqmc_mc_fss_binner_finish(dqmc_mc_handle *h, int32_t walker, int32_t level, 
  * leaves every stream, sum and launch as without the feature.  The results do not depend on how a run is split into
  * calls of dqmc_qs_sweep, nor on the number of walkers in the handle.
  *
+ * Replica exchange (dqmc_qs_set_exchange, dqmc_qs_exchange).  As dqmc_mc_set_exchange: the walkers form n_walkers / R
+ * ladders of R consecutive slots.  Slot w keeps what belongs to its temperature: beta and its table w[q][q], the key, the
+ * sweep cursor s, the move cursor m and the conf cursor r, the sums, the series, the binner and every counter.  An
+ * accepted exchange of the pair (a, b = a + 1) swaps the configurations (the Nw = ceil(N / 4) words), E_int, Mx, My and a
+ * replica label, which starts as the slot's index within its ladder.  The handle keeps an exchange cursor x, the rounds
+ * since dqmc_qs_set_exchange; round x tries the pairs with ladder-local i = x (mod 2), i + 1 < R.
+ *   d           = E_a - E_b, an exact int64 in units of 2^-30
+ *   db          = beta_a - beta_b in fp64 on the host; the betas need not be monotone
+ *   swap if     db == 0, d == 0, or db and d have the same sign
+ *   otherwise   p = 1.0, then p = fl(p t[j]) for every set bit j of |d| in ascending order, with the per-pair table
+ *               t[j] = exp(-fl(|db| 2^(j - 30))), j < J, from the host's libm (the scaling by a power of two is exact, so
+ *               exp sees one rounded argument; no exp on the device).  J is the smallest integer with
+ *               2^J > 2 n_bonds max_d |e_q30[d]| >= |d|: 50 at the create-time limits (2^16 bonds, |e_q30| <= 2^32); a
+ *               handle whose J would exceed 62 is refused (DQMC_ERR_INVALID).  dqmc_qs_set_beta rebuilds the tables of
+ *               the at most two pairs a slot belongs to.
+ *   swap iff    u < p, u = u1 of P(key_a; 0, low32(x), 7, high32(x)): domain word c2 = 7, a fourth q-state domain (4 the
+ *               sweep, 5 the configuration, 6 the cluster move).  No other cursor moves.
+ *   counters    per slot a: prop_exchange / acc_exchange count the tries and swaps of the pair (a, a + 1); the last slot
+ *               of a ladder stays 0
+ * Every decision can be reproduced bit for bit.  p differs from exp(db d) by the error of libm and one rounding per
+ * factor and one per product: at most about 2 J ulp, |p exp(-db d) - 1| <= 2 J 2^-53 to first order with a correctly
+ * rounded exp.  That relative error of the acceptance probability is the size of the deviation from exact detailed
+ * balance (a chain that used p for both directions of every pair would be exact; the rule is symmetric in a and b).
+ *
+ * Order inside a sweep.  The sweep with global index i runs, in this order: its colour passes; its cluster move iff
+ * cluster rate > 0 && i % cluster rate == 0; its exchange round iff exchange rate k > 0 && R >= 2 && i % k == 0; its
+ * measurement by the rule above, of every slot, on the configuration the slot then holds.  The measurement of a sweep
+ * with a round is taken by the exchange kernel.  Results do not depend on how a run is split into dqmc_qs_sweep calls.
+ *
+ * Binner (dqmc_qs_binner_enable).  One logarithmic binner per walker under the contract of "error bars" above, pushed
+ * wherever a measurement is taken, behind the sums and the series record.  Six elements [E, E2, |M|, M2, M2, M4] with
+ * the values the sums use: e, fl(e e), sqrt(m2), m2, m2, fl(m2 m2); M2 is kept twice so that pair p is the elements
+ * (2 p, 2 p + 1): (E, E2), (|M|, M2), (M2, M4), whose cross sums xy_sum[3] take the product of the pair's two level-l
+ * values wherever x2_sum[l] takes the squares.  L = ceil(log2(capacity + 1)) levels, a one-value compressor per element
+ * below the top level, device layout [level][element][walker]; all walkers measure at the same sweeps, so the push
+ * count T and count[l] = T >> l are host integers, and the level a push stops at is the number of trailing 1-bits of T.
+ * varN, covN, tau and the reliable level are those of dqmc_mc_binned.  A dqmc_qs_sweep whose measurements would pass
+ * the capacity returns DQMC_ERR_STATE and nothing has run.  dqmc_qs_reset_accumulators clears the binner and its count.
+ * The sums, series and chains are exactly those of a handle without a binner.  The elements with a square root (|M|,
+ * and the cross sum of (|M|, M2)) inherit the device's sqrt and compare at 1e-13 relative, all others bit for bit.
+ *
  * Limits: n_sites <= 16384, 1 <= z <= 8, 2 <= q <= 64, n_colours <= 16.  Errors come from dqmc_qs_last_error. */
 typedef struct dqmc_qs_handle dqmc_qs_handle;
 
@@ -1418,6 +1459,43 @@ int dqmc_qs_set_cluster_rate(dqmc_qs_handle *h, int32_t rate);
 int dqmc_qs_cluster_move(dqmc_qs_handle *h, int32_t walker);
 /* (dqmc_qs_seed puts moves_drawn back to 0; dqmc_qs_reset_accumulators leaves all four alone, as it leaves prop_local) */
 int dqmc_qs_get_cluster_stats(dqmc_qs_handle *h, int32_t walker, dqmc_qs_cluster_stats *out);
+
+/* n_replicas = R >= 2 defines the ladders (n_walkers % R != 0: DQMC_ERR_INVALID; so is a handle whose J would exceed
+ * 62); 0 or 1: none.  rate = k > 0: from now on dqmc_qs_sweep runs one round after every sweep whose global index is a
+ * multiple of k, in the order of "Order inside a sweep"; rate 0 (or no ladders): dqmc_qs_sweep runs none and behaves as
+ * on a handle that never had exchange (with R >= 2 dqmc_qs_exchange still works).  Resets the cursor, the labels and the
+ * exchange counters. */
+int dqmc_qs_set_exchange(dqmc_qs_handle *h, int32_t n_replicas, int32_t rate);
+/* one round at the cursor by hand (a launch of its own); it takes no measurement.  Without ladders: DQMC_ERR_STATE */
+int dqmc_qs_exchange(dqmc_qs_handle *h);
+/* the exchange counters of the pair (walker, walker + 1), the label of the replica now in the slot, and the cursor */
+typedef struct {
+    int64_t prop_exchange, acc_exchange;
+    int64_t replica;
+    uint64_t rounds;
+} dqmc_qs_exchange_stats;
+int dqmc_qs_get_exchange_stats(dqmc_qs_handle *h, int32_t walker, dqmc_qs_exchange_stats *out);
+/* a binner per walker for `capacity` measurements (0 = 100000, at most 2^40); enabling again starts anew */
+int dqmc_qs_binner_enable(dqmc_qs_handle *h, int64_t capacity);
+/* levels and pushes so far; either may be NULL.  This and the calls below: DQMC_ERR_STATE without a binner */
+int dqmc_qs_binner_size(dqmc_qs_handle *h, int32_t *n_levels, int64_t *n_pushed);
+/* the last level with count >= 32, else 0 */
+int dqmc_qs_binner_reliable_level(dqmc_qs_handle *h, int32_t *level);
+/* the sums of one level of one walker in element order [E, E2, |M|, M2, M2, M4] / pair order [(E, E2), (|M|, M2),
+ * (M2, M4)] and the level's count; any output may be NULL */
+int dqmc_qs_binner_get_level(dqmc_qs_handle *h, int32_t walker, int32_t level,
+                             double x_sum[6], double x2_sum[6], double xy_sum[3], int64_t *count);
+typedef struct {
+    double mean[6];   /* x_sum[0] / count[0] */
+    double varN[6];   /* at `level`; std_error = sqrt(max(varN, 0)) */
+    double varN0[6];  /* at level 0 */
+    double tau[6];    /* (varN / varN0 - 1) / 2 */
+    double covN[3];   /* at `level`, pairs (E, E2), (|M|, M2) and (M2, M4) */
+    int64_t count;    /* count[level] */
+    int32_t level;    /* the level used */
+} dqmc_qs_binned;
+/* level < 0: the reliable level */
+int dqmc_qs_binner_finish(dqmc_qs_handle *h, int32_t walker, int32_t level, dqmc_qs_binned *out);
 
 /* ---- the SAC flavor: stochastic analytic continuation -----------------------------------------------------------
  * A(omega) from imaginary-time data by sampling (Sandvik, PRB 57, 10287; Beach, cond-mat/0403055; Shao and Sandvik,

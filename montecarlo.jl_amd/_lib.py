@@ -125,6 +125,16 @@ class QsClusterStats(C.Structure):
                 ("moves_drawn", C.c_uint64)]
 
 
+class QsExchangeStats(C.Structure):
+    _fields_ = [("prop_exchange", C.c_int64), ("acc_exchange", C.c_int64), ("replica", C.c_int64),
+                ("rounds", C.c_uint64)]
+
+
+class QsBinned(C.Structure):
+    _fields_ = [("mean", C.c_double * 6), ("varN", C.c_double * 6), ("varN0", C.c_double * 6), ("tau", C.c_double * 6),
+                ("covN", C.c_double * 3), ("count", C.c_int64), ("level", C.c_int32)]
+
+
 class SacParams(C.Structure):
     _fields_ = [("n_problems", C.c_int32), ("n_tau", C.c_int32), ("n_deltas", C.c_int32), ("n_omega", C.c_int32),
                 ("n_replicas", C.c_int32), ("device_id", C.c_int32), ("window", C.c_int32),
@@ -336,6 +346,14 @@ SIGNATURES = {
     "dqmc_qs_set_cluster_rate": (C.c_int, [_H, C.c_int32]),
     "dqmc_qs_cluster_move": (C.c_int, [_H, C.c_int32]),
     "dqmc_qs_get_cluster_stats": (C.c_int, [_H, C.c_int32, C.POINTER(QsClusterStats)]),
+    "dqmc_qs_set_exchange": (C.c_int, [_H, C.c_int32, C.c_int32]),
+    "dqmc_qs_exchange": (C.c_int, [_H]),
+    "dqmc_qs_get_exchange_stats": (C.c_int, [_H, C.c_int32, C.POINTER(QsExchangeStats)]),
+    "dqmc_qs_binner_enable": (C.c_int, [_H, C.c_int64]),
+    "dqmc_qs_binner_size": (C.c_int, [_H, C.POINTER(C.c_int32), _i64p]),
+    "dqmc_qs_binner_reliable_level": (C.c_int, [_H, C.POINTER(C.c_int32)]),
+    "dqmc_qs_binner_get_level": (C.c_int, [_H, C.c_int32, C.c_int32, _dp, _dp, _dp, _i64p]),
+    "dqmc_qs_binner_finish": (C.c_int, [_H, C.c_int32, C.c_int32, C.POINTER(QsBinned)]),
     "dqmc_sac_create": (C.c_int, [C.POINTER(SacParams), C.POINTER(_H)]),
     "dqmc_sac_destroy": (C.c_int, [_H]),
     "dqmc_sac_last_error": (C.c_char_p, [_H]),

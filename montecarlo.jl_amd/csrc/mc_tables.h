@@ -1,7 +1,8 @@
 // mc_tables.h — what the two engines of the classical MC flavor (ising.hip, qstate.hip) work out on the host before
-// anything reaches the device: the lattice tables of a create, the colour-sorted tables of a checkerboard sweep, and the
-// arithmetic of the logarithmic binner.  Plain C++17, no device runtime: mc_host.h includes it, and
-// tests/mc_tables_check.cpp builds it alone under the host sanitizers.  A refusal returns false with the message in *err,
+// anything reaches the device: the lattice tables of a create, the colour-sorted tables of a checkerboard sweep, the
+// arithmetic of the logarithmic binner, and the q-state engine's replica exchange (the pair tables, the product rule, the
+// cut of a sweep call into launches).  Plain C++17, no device runtime: mc_host.h includes it, and
+// tests/mc_tables_check.cpp and tests/qs_exchange_check.cpp build it alone under the host sanitizers.  A refusal returns false with the message in *err,
 // prefixed with the name of the ABI function the caller passes as fn.
 #pragma once
 
@@ -143,6 +144,67 @@ inline void bin_finish(int n_elem, int n_pairs, bool pairs_from_first, int64_t T
     }
     for (int p = 0; p < n_pairs; ++p)
         covN[p] = pairs_from_first ? bin_covN(xs[0], xs[1 + p], xy[p], nl) : bin_covN(xs[2 * p], xs[2 * p + 1], xy[p], nl);
+}
+
+// ---- replica exchange of the q-state engine (include/dqmc_hip.h, "Replica exchange" of the q-state section)
+// J, the entries of a pair's table: the smallest integer with 2^J > 2 n_bonds max_d |e_q30[d]| >= |E_a - E_b|
+inline int qs_exchange_bits(int64_t n_bonds, const int64_t *e_q30, int q)
+{
+    unsigned __int128 bound = 0;
+    for (int d = 0; d < q; ++d) {
+        const unsigned __int128 a = (unsigned __int128)(e_q30[d] < 0 ? -e_q30[d] : e_q30[d]);
+        bound = std::max(bound, a);
+    }
+    bound = bound * (unsigned __int128)(2 * n_bonds);
+    int J = 0;
+    while (J < 127 && ((unsigned __int128)1 << J) <= bound) ++J;
+    return J;
+}
+// the pair's table for db = beta_a - beta_b: t[j] = exp(-(|db| 2^(j - 30))), the scaling exact, one libm call per entry
+inline void qs_exchange_table(double db, int J, double *t)
+{
+    for (int j = 0; j < J; ++j) t[j] = std::exp(-std::ldexp(std::fabs(db), j - 30));
+}
+// p = 1.0, then p = p * t[j] for every set bit j of |d| in ascending order (|d| < 2^J)
+inline double qs_exchange_product(const double *t, int J, uint64_t abs_d)
+{
+    double p = 1.0;
+    for (int j = 0; j < J; ++j)
+        if ((abs_d >> j) & 1) p = p * t[j];
+    return p;
+}
+// does the pair swap?  d = E_a - E_b, sgn = the sign of db; u is looked at only where the product decides
+inline bool qs_exchange_swaps(int sgn, int64_t d, const double *t, int J, double u)
+{
+    if (sgn == 0 || d == 0 || (d > 0) == (sgn > 0)) return true;
+    return u < qs_exchange_product(t, J, d < 0 ? (uint64_t)0 - (uint64_t)d : (uint64_t)d);
+}
+// One dqmc_qs_sweep(n, first, thermalization, rate) call as launches of the sweep kernel.  A launch ends at every sweep
+// with an exchange round (global index a multiple of k; k = 0: no rounds) and at the work bound of `chunk` sweeps,
+// whichever comes first.  defer_last: the launch's last sweep has a round and is measured, so its measurement is the
+// exchange kernel's.  T_at_start: the binner's push count when the launch starts, T0 at the first.
+struct SweepLaunch {
+    int n_sweeps;
+    int64_t first;
+    bool defer_last;
+    int64_t T_at_start;
+};
+inline std::vector<SweepLaunch> qs_sweep_cut(int n, int64_t first, int64_t thermalization, int64_t rate, int64_t k,
+                                             int chunk, int64_t T0)
+{
+    std::vector<SweepLaunch> out;
+    int64_t T = T0;
+    for (int done = 0; done < n;) {
+        const int64_t f = first + done;
+        int64_t m = std::min<int64_t>(std::max(chunk, 1), n - done);
+        if (k > 0) m = std::min<int64_t>(m, k - (f - 1) % k);
+        const int64_t last = f + m - 1;
+        const bool round = k > 0 && last % k == 0;
+        out.push_back(SweepLaunch{(int)m, f, round && last > thermalization && last % rate == 0, T});
+        T += measurements_in(f, last, thermalization, rate);
+        done += (int)m;
+    }
+    return out;
 }
 
 }  // namespace mc_tables

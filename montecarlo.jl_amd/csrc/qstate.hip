@@ -43,7 +43,8 @@ constexpr int MAX_Q = 64;
 constexpr int MAX_COLOURS = 16;
 constexpr int WAVE = 64;
 constexpr int THREADS = 256;
-constexpr unsigned int DOMAIN_SWEEP = 4u, DOMAIN_CONF = 5u, DOMAIN_CLUSTER = 6u;
+constexpr unsigned int DOMAIN_SWEEP = 4u, DOMAIN_CONF = 5u, DOMAIN_CLUSTER = 6u, DOMAIN_EXCHANGE = 7u;
+constexpr int MAX_XJ = 62;  // entries of an exchange pair's table at most: |E_a - E_b| < 2^J as an int64
 constexpr double Q30_INV = 1.0 / 1073741824.0;
 // The work bound of a launch, in the terms of the Ising checkerboard path (ising.hip, CB_LAUNCH_BUDGET): a sweep counts as
 // N + 512 site visits, 512 walkers' workgroups run side by side, and a launch runs at most
@@ -192,184 +193,165 @@ __device__ __forceinline__ int qs_cluster_move_lds(unsigned char *st, const doub
     return hi;
 }
 
-// CLUSTER = false is the sweep without moves (ca is not read); CLUSTER = true runs the walker's cluster move behind the
-// colour passes of every sweep whose global index is a multiple of ca.rate (> 0)
-template <bool CLUSTER>
-__global__ __launch_bounds__(THREADS) void qs_sweep_kernel(DevState s, const int *__restrict__ site,
-                                                           const int4 *__restrict__ rows, const int *__restrict__ off,
-                                                           const long long *__restrict__ e_q30,
-                                                           const int2 *__restrict__ cs_q30, int C, int n_sweeps,
-                                                           long long first_sweep, long long thermalization,
-                                                           int measure_rate, ClusterArgs ca)
+// the walker's binner (the header's "Binner"): a kernel argument of its own, so that DevState keeps its layout.
+// xs == nullptr: no binner
+struct BinArgs {
+    double *xs, *x2, *xy, *c;  // [L][6][W], [L][6][W], [L][3][W], [L - 1][6][W]
+    int top;                   // L - 1, the level without a compressor
+    long long T;               // the pushes the binner stands at when the launch starts
+};
+
+// replica exchange (the header's "Replica exchange"): a kernel argument of its own
+struct ExchangeArgs {
+    int R, J;                      // ladder length, entries of a pair's table
+    unsigned long long x;          // the exchange cursor of this round
+    const double *__restrict__ t;  // [J][W], column a: t[j] = exp(-|beta_a - beta_{a+1}| 2^(j - 30)) of the pair (a, a + 1)
+    const int *__restrict__ sgn;   // [W], the sign of beta_a - beta_{a+1}
+    int *replica;                  // [W], the label of the configuration in the slot
+    long long *prop, *acc;         // [W], tries and swaps of the pair (a, a + 1)
+};
+
+// One push of walker w at push count T: elements [E, E2, |M|, M2, M2, M4], pairs (2 p, 2 p + 1), state
+// [level][element][walker].  lmax = the trailing 1-bits of T, the same for every walker: the levels below it complete a
+// pair with their compressor and carry the average upwards, level lmax keeps the value (the top level has no
+// compressor).  A level's values are requested together and then written; levels above lmax are not touched.
+__device__ __forceinline__ void qs_bin_push(const BinArgs &ba, int W, int w, long long T, double e, double am, double m2,
+                                            double m4)
 {
-    extern __shared__ __align__(16) unsigned char lds[];
-    const int tid = threadIdx.x, nt = blockDim.x, w = blockIdx.x;
-    const int N = s.N, Nw = s.Nw, q = s.q, z = s.z;
-    double *wt = (double *)lds;                                // [q][q]
-    long long *et = (long long *)(wt + q * q);                 // [q]
-    int2 *cs = (int2 *)(et + q);                               // [q]
-    unsigned long long *red = (unsigned long long *)(cs + q);  // E_int, Mx, My, accepted sites of the launch
-    unsigned char *st = (unsigned char *)(red + 4);            // [4 Nw]
-    {
-        unsigned int *stw = (unsigned int *)st;
-        const unsigned int *src = s.conf + (size_t)w * Nw;
-        for (int j = tid; j < Nw; j += nt) stw[j] = src[j];
-        const double *wsrc = s.wt + (size_t)w * q * q;
-        for (int j = tid; j < q * q; j += nt) wt[j] = wsrc[j];
-        for (int j = tid; j < q; j += nt) {
-            et[j] = e_q30[j];
-            cs[j] = cs_q30[j];
-        }
-        if (tid == 0) {
-            red[0] = (unsigned long long)s.E[w];
-            red[1] = (unsigned long long)s.Mx[w];
-            red[2] = (unsigned long long)s.My[w];
-            red[3] = 0ull;
-        }
-    }
-    const unsigned long long key = s.key[w];
-    unsigned long long sc = s.cursor[w];
-    // lane 0 carries the walker's sums through the launch
-    double sE = 0.0, sE2 = 0.0, sM = 0.0, sM2 = 0.0, sM4 = 0.0;
-    long long n_meas = 0, n_series = 0;
-    if (tid == 0) {
-        sE = s.sE[w];
-        sE2 = s.sE2[w];
-        sM = s.sM[w];
-        sM2 = s.sM2[w];
-        sM4 = s.sM4[w];
-        n_meas = s.n_meas[w];
-        n_series = s.n_series[w];
-    }
-    // the next measured sweep at or behind first_sweep: one division per launch, none per sweep
-    const long long g0 = first_sweep > thermalization + 1 ? first_sweep : thermalization + 1;
-    long long next = (g0 + measure_rate - 1) / measure_rate * measure_rate;
-    long long dE = 0, dMx = 0, dMy = 0;
-    int acc = 0;
-    const double qm1 = (double)(q - 1);
-    // (CLUSTER) the move cursor in every lane, the next sweep with a move, and lane 0's global counters
-    unsigned long long mc = 0ull;
-    long long next_move = 0, g_prop = 0, g_acc = 0, g_size = 0;
-    if constexpr (CLUSTER) {
-        mc = ca.cursor[w];
-        next_move = (first_sweep + ca.rate - 1) / ca.rate * ca.rate;
-    }
-    __syncthreads();
-
-    for (int sw = 0; sw < n_sweeps; ++sw, ++sc) {
-        const unsigned int c1 = (unsigned int)sc, c3 = (unsigned int)(sc >> 32);
-        for (int c = 0; c < C; ++c) {
-            const int e1 = off[c + 1];
-            for (int e = off[c] + tid; e < e1; e += nt) {
-                const int i = site[e];
-                const int4 r0 = rows[2 * e], r1 = rows[2 * e + 1];
-                const int row[MAX_Z] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w};
-                const int so = st[i];
-                double u1, u2;
-                philox4_two(key, (unsigned int)i, c1, DOMAIN_SWEEP, c3, u1, u2);
-                int t = so + 1 + min(q - 2, (int)(u1 * qm1));
-                t = t >= q ? t - q : t;
-                long long d = 0;
-                double p = 1.0;
+    double x[6] = {e, e * e, am, m2, m2, m4};
+    const int lmax = min(ba.top, (int)__builtin_ctzll(~(unsigned long long)T));  // (T < capacity < 2^(top + 1))
+    const size_t sW = (size_t)W;
+    size_t a6 = (size_t)w, a3 = (size_t)w;
+    for (int l = 0; l <= lmax; ++l, a6 += 6 * sW, a3 += 3 * sW) {
+        const bool carry = l < lmax;
+        double s1[6], s2[6], cc[6], pr[3];
 #pragma unroll
-                for (int k = 0; k < MAX_Z; ++k)
-                    if (k < z) {
-                        const int sj = st[row[k]];
-                        const int a = mod_q(so - sj, q), b = mod_q(t - sj, q);
-                        d += et[a] - et[b];
-                        p = p * wt[a * q + b];
-                    }
-                if (d <= 0 || u2 < p) {
-                    st[i] = (unsigned char)t;
-                    const int2 co = cs[so], cn = cs[t];
-                    dE += d;
-                    dMx += (long long)cn.x - co.x;  // (up to 2^31 in magnitude: not an int)
-                    dMy += (long long)cn.y - co.y;
-                    ++acc;
-                }
-            }
-            __syncthreads();
+        for (int k = 0; k < 6; ++k) {
+            s1[k] = ba.xs[a6 + k * sW];
+            s2[k] = ba.x2[a6 + k * sW];
+            cc[k] = carry ? ba.c[a6 + k * sW] : 0.0;
         }
-        const long long g = first_sweep + sw;  // global 1-based sweep index
-        if constexpr (CLUSTER) {
-            if (g == next_move) {  // (uniform)
-                next_move += ca.rate;
-                const int size = qs_cluster_move_lds(st, wt, et, cs, (unsigned int *)(st + 4 * Nw), ca.nbr, N, q, z, key, mc,
-                                                     dE, dMx, dMy);
-                ++mc;
-                g_prop += 1;
-                g_acc += size > 1;
-                g_size += size;
-            }
+#pragma unroll
+        for (int p = 0; p < 3; ++p) pr[p] = ba.xy[a3 + p * sW];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+            ba.xs[a6 + k * sW] = s1[k] + x[k];
+            ba.x2[a6 + k * sW] = s2[k] + x[k] * x[k];
+            if (!carry && l < ba.top) ba.c[a6 + k * sW] = x[k];
         }
-        if (g != next) continue;               // (uniform)
-        next += measure_rate;
-        const long long e = wave_sum(dE), mx = wave_sum(dMx), my = wave_sum(dMy);
-        dE = dMx = dMy = 0;
-        if ((tid & (WAVE - 1)) == 0) {
-            atomicAdd(&red[0], (unsigned long long)e);
-            atomicAdd(&red[1], (unsigned long long)mx);
-            atomicAdd(&red[2], (unsigned long long)my);
-        }
-        __syncthreads();  // (the next write of red[0..2] lies behind the next sweep's barriers)
-        if (tid == 0) {
-            const long long E = (long long)red[0], Mx = (long long)red[1], My = (long long)red[2];
-            const double ev = (double)E * Q30_INV, x = (double)Mx * Q30_INV, y = (double)My * Q30_INV;
-            const double m2 = x * x + y * y;
-            sE = sE + ev;
-            sE2 = sE2 + ev * ev;
-            sM2 = sM2 + m2;
-            sM4 = sM4 + m2 * m2;
-            sM = sM + sqrt(m2);
-            n_meas += 1;
-            if (n_series < s.cap) {
-                long long *rec = s.ser + ((size_t)w * s.cap + (size_t)n_series) * 3;
-                rec[0] = E;
-                rec[1] = Mx;
-                rec[2] = My;
-                n_series += 1;
-            }
-        }
+#pragma unroll
+        for (int p = 0; p < 3; ++p) ba.xy[a3 + p * sW] = pr[p] + x[2 * p] * x[2 * p + 1];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) x[k] = 0.5 * (cc[k] + x[k]);
     }
+}
 
-    __syncthreads();
-    {
-        const long long e = wave_sum(dE), mx = wave_sum(dMx), my = wave_sum(dMy), n = wave_sum((long long)acc);
-        if ((tid & (WAVE - 1)) == 0) {
-            atomicAdd(&red[0], (unsigned long long)e);
-            atomicAdd(&red[1], (unsigned long long)mx);
-            atomicAdd(&red[2], (unsigned long long)my);
-            atomicAdd(&red[3], (unsigned long long)n);
+// the sweep kernel: the two forms of a handle without binner and rounds, then the forms with BIN and DEFER
+#define QS_SWEEP_MODES 0
+#include "qs_sweep.inl"
+#undef QS_SWEEP_MODES
+#define QS_SWEEP_MODES 1
+#include "qs_sweep.inl"
+#undef QS_SWEEP_MODES
+
+// does the pair (a, a + 1) swap in round x.x?  Every lane of the workgroup forms the same answer.
+__device__ __forceinline__ bool qs_exchange_decide(const ExchangeArgs &x, int W, int a, unsigned long long key_a, int sgn,
+                                                   long long Ea, long long Eb)
+{
+    const long long d = Ea - Eb;
+    if (sgn == 0 || d == 0 || (d > 0) == (sgn > 0)) return true;
+    const unsigned long long ad = d < 0 ? 0ull - (unsigned long long)d : (unsigned long long)d;
+    double p = 1.0;
+    for (int j = 0; j < x.J; ++j)  // (|d| < 2^J: no bit at or above J is set)
+        if ((ad >> j) & 1ull) p = p * x.t[(size_t)j * W + a];
+    double u1, u2;
+    philox4_two(key_a, 0u, (unsigned int)x.x, DOMAIN_EXCHANGE, (unsigned int)(x.x >> 32), u1, u2);
+    return u1 < p;
+}
+
+// the measurement of slot w on (E, Mx, My) outside the sweep kernel, by one lane: the sums in the header's order of
+// operations, the series record, the binner push
+__device__ __forceinline__ void qs_measure_slot(const DevState &s, const BinArgs &ba, int w, long long E, long long Mx,
+                                                long long My)
+{
+    const double sE = s.sE[w], sE2 = s.sE2[w], sM = s.sM[w], sM2 = s.sM2[w], sM4 = s.sM4[w];  // requested together
+    const long long n_meas = s.n_meas[w], n_series = s.n_series[w];
+    const double ev = (double)E * Q30_INV, x = (double)Mx * Q30_INV, y = (double)My * Q30_INV;
+    const double m2 = x * x + y * y;
+    const double am = sqrt(m2);
+    s.sE[w] = sE + ev;
+    s.sE2[w] = sE2 + ev * ev;
+    s.sM2[w] = sM2 + m2;
+    s.sM4[w] = sM4 + m2 * m2;
+    s.sM[w] = sM + am;
+    s.n_meas[w] = n_meas + 1;
+    if (n_series < s.cap) {
+        long long *rec = s.ser + ((size_t)w * s.cap + (size_t)n_series) * 3;
+        rec[0] = E;
+        rec[1] = Mx;
+        rec[2] = My;
+        s.n_series[w] = n_series + 1;
+    }
+    if (ba.xs) qs_bin_push(ba, s.W, w, ba.T, ev, am, m2, m2 * m2);
+}
+
+// One exchange round (x.x) on the state in device memory, one workgroup per slot that has something to do: the lower
+// slot a of each tried pair, which also acts for b = a + 1, and with measure != 0 every slot without a pair in this
+// round.  Per ladder these are n_lo = (R - par) / 2 pairs (par = x mod 2) and R - 2 n_lo single slots: slot 0 when par
+// is 1, slot R - 1 when R - par is odd; the grid is (W / R) (n_lo + (measure ? R - 2 n_lo : 0)) workgroups.  Every lane
+// reads what the decision needs and forms it; behind a barrier the rows of Nw words change places, each word of both
+// rows in registers before either is written, and lane 0 writes E_int, Mx, My, the labels and the counters.  measure:
+// lane 0 then takes the measurement of the sweep this round ends, for both slots of a pair and for a single slot.
+__global__ __launch_bounds__(THREADS) void qs_exchange_kernel(DevState s, ExchangeArgs x, BinArgs ba, int measure)
+{
+    const int tid = threadIdx.x, nt = blockDim.x;
+    const int par = (int)(x.x & 1ull), n_lo = (x.R - par) / 2, n_un = x.R - 2 * n_lo;
+    const int per = n_lo + (measure ? n_un : 0);
+    const int ladder = (int)blockIdx.x / per, j = (int)blockIdx.x - ladder * per;
+    const bool active = j < n_lo;
+    const int il = active ? par + 2 * j : (par && j == n_lo ? 0 : x.R - 1);
+    const int a = ladder * x.R + il;
+    if (a + (active ? 1 : 0) >= s.W) return;  // (uniform; the host's grid never gets here)
+    long long E = s.E[a], Mx = s.Mx[a], My = s.My[a];
+    if (active) {  // (uniform)
+        const int b = a + 1;
+        long long Eb = s.E[b], Mxb = s.Mx[b], Myb = s.My[b];
+        const int ra = x.replica[a], rb = x.replica[b], sgn = x.sgn[a];
+        const unsigned long long key = s.key[a];
+        const long long prop = x.prop[a], acc = x.acc[a];
+        const bool swap = qs_exchange_decide(x, s.W, a, key, sgn, E, Eb);
+        __syncthreads();  // every lane has read what lane 0 is about to overwrite
+        if (swap) {
+            unsigned int *ca = s.conf + (size_t)a * s.Nw, *cb = s.conf + (size_t)b * s.Nw;
+            for (int k = tid; k < s.Nw; k += nt) {
+                const unsigned int va = ca[k], vb = cb[k];
+                ca[k] = vb;
+                cb[k] = va;
+            }
+            long long t = E;
+            E = Eb, Eb = t;
+            t = Mx;
+            Mx = Mxb, Mxb = t;
+            t = My;
+            My = Myb, Myb = t;
+        }
+        if (tid == 0) {
+            x.prop[a] = prop + 1;
+            if (swap) {
+                x.acc[a] = acc + 1;
+                s.E[a] = E;
+                s.Mx[a] = Mx;
+                s.My[a] = My;
+                s.E[b] = Eb;
+                s.Mx[b] = Mxb;
+                s.My[b] = Myb;
+                x.replica[a] = rb;
+                x.replica[b] = ra;
+            }
+            if (measure) qs_measure_slot(s, ba, b, Eb, Mxb, Myb);
         }
     }
-    __syncthreads();
-    {
-        const unsigned int *stw = (const unsigned int *)st;
-        unsigned int *dst = s.conf + (size_t)w * Nw;
-        for (int j = tid; j < Nw; j += nt) dst[j] = stw[j];
-    }
-    if (tid == 0) {
-        const long long prop = s.prop[w], accd = s.acc[w];  // requested together
-        s.E[w] = (long long)red[0];
-        s.Mx[w] = (long long)red[1];
-        s.My[w] = (long long)red[2];
-        s.prop[w] = prop + (long long)n_sweeps * N;
-        s.acc[w] = accd + (long long)red[3];
-        s.cursor[w] = sc;
-        s.sE[w] = sE;
-        s.sE2[w] = sE2;
-        s.sM[w] = sM;
-        s.sM2[w] = sM2;
-        s.sM4[w] = sM4;
-        s.n_meas[w] = n_meas;
-        s.n_series[w] = n_series;
-        if constexpr (CLUSTER) {
-            ca.prop[w] += g_prop;
-            ca.acc[w] += g_acc;
-            ca.sum_size[w] += g_size;
-            ca.cursor[w] = mc;
-        }
-    }
+    if (measure && tid == 0) qs_measure_slot(s, ba, a, E, Mx, My);
 }
 
 // dqmc_qs_cluster_move: one move of one walker (walker >= 0) or of every walker, with the sweep kernel's LDS layout
@@ -502,7 +484,64 @@ struct dqmc_qs_handle : mc_handle_base {
     ClusterArgs ca{};                   // rate 0: no moves inside dqmc_qs_sweep
     int *nbr_site = nullptr;            // [N][8], what ca.nbr points to
     bool cluster_lds_reserved = false;  // the kernels with a move may ask for more than 64 KiB of dynamic LDS
+    struct Tempering {                  // replica exchange (dqmc_qs_set_exchange); R = 0: no ladders
+        int R = 0, rate = 0, J = 0;
+        uint64_t cursor = 0;            // rounds since dqmc_qs_set_exchange
+        double *t = nullptr;            // [J][W]
+        int *sgn = nullptr, *replica = nullptr;
+        long long *prop = nullptr, *acc = nullptr;
+    } xch;
+    std::vector<double> beta_h;         // [W], as dqmc_qs_set_beta got them (0 at first)
+    struct Binner : mc_bin_section {    // qs_bin_push: elements [E, E2, |M|, M2, M2, M4], pairs (2 p, 2 p + 1)
+        bool on = false;
+        int64_t cap = 0;
+    } bin;
 };
+
+static const int64_t QS_BIN_DEFAULT_CAPACITY = 100000;  // as dqmc_mc_binner_enable
+
+// the binner as the kernels see it at push count T (xs == nullptr: off)
+static BinArgs qs_bin_arg(const dqmc_qs_handle *h, int64_t T)
+{
+    const dqmc_qs_handle::Binner &b = h->bin;
+    if (!b.on) return BinArgs{nullptr, nullptr, nullptr, nullptr, 0, 0};
+    return BinArgs{b.xs, b.x2, b.xy, b.c, b.L - 1, (long long)T};
+}
+
+// One round at the handle's cursor, which it advances.  measure: the round ends a measured sweep, and T is the binner's
+// push count at that measurement.
+static int qs_launch_exchange(dqmc_qs_handle *h, int measure, int64_t T)
+{
+    dqmc_qs_handle::Tempering &t = h->xch;
+    const int par = (int)(t.cursor & 1), n_lo = (t.R - par) / 2, per = n_lo + (measure ? t.R - 2 * n_lo : 0);
+    if (per > 0) {  // (R = 2 at an odd cursor, no measurement: nothing to do)
+        const ExchangeArgs xa{t.R, t.J, (unsigned long long)t.cursor, t.t, t.sgn, t.replica, t.prop, t.acc};
+        hipLaunchKernelGGL(qs_exchange_kernel, dim3((h->W / t.R) * per), dim3(THREADS), 0, h->stream, h->d, xa,
+                           qs_bin_arg(h, T), measure);
+        MCHK(hipGetLastError());
+    }
+    t.cursor += 1;
+    return 0;
+}
+
+// the table of the pair (a, a + 1) and the sign of beta_a - beta_{a+1}
+static void qs_pair_table(const dqmc_qs_handle *h, int a, double *t, int *sgn)
+{
+    const double db = h->beta_h[a] - h->beta_h[a + 1];
+    *sgn = db > 0.0 ? 1 : (db < 0.0 ? -1 : 0);
+    mc_tables::qs_exchange_table(db, h->xch.J, t);
+}
+
+static int qs_put_pair_table(dqmc_qs_handle *h, int a)
+{
+    double t[MAX_XJ];
+    int sgn = 0;
+    qs_pair_table(h, a, t, &sgn);
+    if (h->xch.J > 0)
+        MCHK(hipMemcpy2DAsync(h->xch.t + a, (size_t)h->W * sizeof(double), t, sizeof(double), sizeof(double), h->xch.J,
+                              hipMemcpyHostToDevice, h->stream));
+    return mc_put<int>(h, h->xch.sgn, 0, a, sgn);
+}
 
 // a validated colouring's tables into the handle's fixed-size arrays (off: all 17 entries, the empty classes at N)
 static int qs_put_colouring(dqmc_qs_handle *h, const mc_tables::Colouring &t, int nc)
@@ -525,14 +564,16 @@ static int qs_reserve_cluster_lds(dqmc_qs_handle *h, const char *fn)
 {
     if (h->cluster_lds_reserved) return 0;
     const size_t lds = sweep_lds_bytes(MAX_Q, MAX_SITES / 4) + cluster_lds_bytes(MAX_SITES);
-    if (hipFuncSetAttribute((const void *)qs_sweep_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
-            hipSuccess ||
-        hipFuncSetAttribute((const void *)qs_cluster_move_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
-            hipSuccess) {
-        (void)hipGetLastError();
-        return mc_fail(h, DQMC_ERR_HIP, std::string(fn) + ": cannot reserve " + std::to_string(lds) +
-                                            " bytes of LDS for the cluster-move kernels");
-    }
+    const void *kernels[] = {(const void *)qs_sweep_kernel<true>, (const void *)qs_cluster_move_kernel,
+                             (const void *)qs_sweep_kernel<true, true, false>,
+                             (const void *)qs_sweep_kernel<true, false, true>,
+                             (const void *)qs_sweep_kernel<true, true, true>};
+    for (const void *k : kernels)
+        if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+            (void)hipGetLastError();
+            return mc_fail(h, DQMC_ERR_HIP, std::string(fn) + ": cannot reserve " + std::to_string(lds) +
+                                                " bytes of LDS for the cluster-move kernels");
+        }
     h->cluster_lds_reserved = true;
     return 0;
 }
@@ -598,6 +639,7 @@ int dqmc_qs_create(const dqmc_qs_params *p, dqmc_qs_handle **out)
     h->nbr_h = nbr;
     h->e_h.assign(p->e_q30, p->e_q30 + q);
     h->confs_h.assign((size_t)h->W, 0ull);
+    h->beta_h.assign((size_t)h->W, 0.0);
     std::vector<int2> cs_h((size_t)q);
     for (int d = 0; d < q; ++d) cs_h[d] = make_int2(p->c_q30[d], p->s_q30[d]);
     auto bail = [&](int rc) { return mc_bail(h, rc); };
@@ -674,6 +716,12 @@ int dqmc_qs_set_beta(dqmc_qs_handle *h, int32_t walker, double beta)
     MCHK(hipSetDevice(h->device));
     MCHK(hipMemcpyAsync(h->d.wt + (size_t)walker * q * q, wt.data(), wt.size() * 8, hipMemcpyHostToDevice, h->stream));
     MCHK(hipStreamSynchronize(h->stream));
+    h->beta_h[walker] = beta;
+    const int R = h->xch.R;  // the exchange tables of the at most two pairs this slot belongs to
+    if (R >= 2 && walker % R > 0)
+        if (int rc = qs_put_pair_table(h, walker - 1)) return rc;
+    if (R >= 2 && walker % R + 1 < R)
+        if (int rc = qs_put_pair_table(h, walker)) return rc;
     return DQMC_OK;
 }
 
@@ -742,25 +790,47 @@ int dqmc_qs_sweep(dqmc_qs_handle *h, int32_t n_sweeps, int64_t first_sweep_index
     if (!h) return mc_fail(nullptr, DQMC_ERR_INVALID, "dqmc_qs_sweep: null handle");
     if (n_sweeps < 0 || measure_rate < 1 || first_sweep_index < 1)
         return mc_fail(h, DQMC_ERR_INVALID, "dqmc_qs_sweep: n_sweeps >= 0, first_sweep_index >= 1, measure_rate >= 1");
+    dqmc_qs_handle::Binner &b = h->bin;
+    const int64_t n_meas = mc_tables::measurements_in(first_sweep_index, first_sweep_index + n_sweeps - 1, thermalization,
+                                                      measure_rate);
+    if (b.on && b.T + n_meas > b.cap)
+        return mc_fail(h, DQMC_ERR_STATE, "dqmc_qs_sweep: the measurements of this call would pass the binner's capacity");
     MCHK(hipSetDevice(h->device));
     const double per_sweep = ((double)h->N + QS_SWEEP_OVERHEAD) * std::max(1.0, (double)h->W / QS_RESIDENT_WALKERS);
     const int chunk = (int)std::max(1.0, std::min((double)n_sweeps, std::floor(QS_LAUNCH_BUDGET / per_sweep)));
-    const size_t lds = sweep_lds_bytes(h->q, h->Nw);
-    for (int done = 0; done < n_sweeps;) {
-        const int n = std::min(chunk, n_sweeps - done);
-        if (h->ca.rate > 0)
-            hipLaunchKernelGGL(qs_sweep_kernel<true>, dim3(h->W), dim3(h->threads), lds + cluster_lds_bytes(h->N), h->stream,
-                               h->d, (const int *)h->site, (const int4 *)h->rows, (const int *)h->off,
-                               (const long long *)h->e_q30, (const int2 *)h->cs_q30, h->C, n,
-                               (long long)(first_sweep_index + done), (long long)thermalization, (int)measure_rate, h->ca);
-        else
-            hipLaunchKernelGGL(qs_sweep_kernel<false>, dim3(h->W), dim3(h->threads), lds, h->stream, h->d,
-                               (const int *)h->site, (const int4 *)h->rows, (const int *)h->off,
-                               (const long long *)h->e_q30, (const int2 *)h->cs_q30, h->C, n,
-                               (long long)(first_sweep_index + done), (long long)thermalization, (int)measure_rate, h->ca);
+    const bool cluster = h->ca.rate > 0;
+    const size_t lds = sweep_lds_bytes(h->q, h->Nw) + (cluster ? cluster_lds_bytes(h->N) : 0);
+    const int k = h->xch.R >= 2 ? h->xch.rate : 0;  // an exchange round after every k-th sweep
+    for (const mc_tables::SweepLaunch &l : mc_tables::qs_sweep_cut(n_sweeps, first_sweep_index, thermalization,
+                                                                   measure_rate, k, chunk, b.T)) {
+        const long long last = l.first + l.n_sweeps - 1;
+        const BinArgs ba = qs_bin_arg(h, l.T_at_start);
+#define QS_SWEEP(...)                                                                                                  \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(qs_sweep_kernel<__VA_ARGS__>), dim3(h->W), dim3(h->threads), lds, h->stream, h->d,                \
+                       (const int *)h->site, (const int4 *)h->rows, (const int *)h->off, (const long long *)h->e_q30,      \
+                       (const int2 *)h->cs_q30, h->C, l.n_sweeps, (long long)l.first, (long long)thermalization,           \
+                       (int)measure_rate, h->ca
+        // binner off and no measurement handed to a round: the forms of a handle that has neither feature
+        if (!b.on && !l.defer_last) {
+            if (cluster) QS_SWEEP(true));
+            else QS_SWEEP(false));
+        } else if (cluster) {
+            if (b.on && l.defer_last) QS_SWEEP(true, true, true), ba);
+            else if (b.on) QS_SWEEP(true, true, false), ba);
+            else QS_SWEEP(true, false, true), ba);
+        } else {
+            if (b.on && l.defer_last) QS_SWEEP(false, true, true), ba);
+            else if (b.on) QS_SWEEP(false, true, false), ba);
+            else QS_SWEEP(false, false, true), ba);
+        }
+#undef QS_SWEEP
         MCHK(hipGetLastError());
-        done += n;
+        if (k > 0 && last % k == 0) {  // the round of sweep `last`, with that sweep's measurement if it has one
+            const int64_t T = l.T_at_start + mc_tables::measurements_in(l.first, last, thermalization, measure_rate) - 1;
+            if (int rc = qs_launch_exchange(h, l.defer_last ? 1 : 0, l.defer_last ? T : 0)) return rc;
+        }
     }
+    if (b.on) b.T += n_meas;
     MCHK(hipStreamSynchronize(h->stream));
     return DQMC_OK;
 }
@@ -824,8 +894,141 @@ int dqmc_qs_reset_accumulators(dqmc_qs_handle *h)
     const size_t W = h->W;
     for (double *p : {d.sE, d.sE2, d.sM, d.sM2, d.sM4}) MCHK(hipMemsetAsync(p, 0, W * 8, h->stream));
     for (long long *p : {d.n_meas, d.n_series}) MCHK(hipMemsetAsync(p, 0, W * 8, h->stream));
+    if (int rc = h->bin.clear(h)) return rc;
     MCHK(hipStreamSynchronize(h->stream));
     return DQMC_OK;
+}
+
+int dqmc_qs_set_exchange(dqmc_qs_handle *h, int32_t n_replicas, int32_t rate)
+{
+    if (!h) return mc_fail(nullptr, DQMC_ERR_INVALID, "dqmc_qs_set_exchange: null handle");
+    if (n_replicas < 0 || rate < 0)
+        return mc_fail(h, DQMC_ERR_INVALID, "dqmc_qs_set_exchange: n_replicas and rate must be >= 0 (0 = off)");
+    const int R = n_replicas >= 2 ? n_replicas : 0;
+    if (R && h->W % R != 0)
+        return mc_fail(h, DQMC_ERR_INVALID, "dqmc_qs_set_exchange: n_walkers must be a multiple of n_replicas");
+    const std::vector<int64_t> e(h->e_h.begin(), h->e_h.end());
+    const int J = mc_tables::qs_exchange_bits(h->n_bonds, e.data(), h->q);
+    if (R && J > MAX_XJ)
+        return mc_fail(h, DQMC_ERR_INVALID, "dqmc_qs_set_exchange: an energy difference needs " + std::to_string(J) +
+                                                " bits, above the 62 a pair's table has");
+    MCHK(hipSetDevice(h->device));
+    dqmc_qs_handle::Tempering &t = h->xch;
+    const size_t W = h->W;
+    if (R && !t.sgn) {
+        int rc = 0;
+        if ((rc = mc_alloc(h, &t.t, (size_t)J * W)) || (rc = mc_alloc(h, &t.sgn, W)) || (rc = mc_alloc(h, &t.replica, W)) ||
+            (rc = mc_alloc(h, &t.prop, W)) || (rc = mc_alloc(h, &t.acc, W)))
+            return rc;
+    }
+    t.R = R;
+    t.rate = rate;
+    t.cursor = 0;
+    t.J = J;
+    if (t.sgn) {
+        MCHK(hipMemsetAsync(t.prop, 0, W * 8, h->stream));
+        MCHK(hipMemsetAsync(t.acc, 0, W * 8, h->stream));
+        std::vector<int> label(W, 0), sgn(W, 0);
+        std::vector<double> tab((size_t)std::max(J, 1) * W, 0.0);
+        for (size_t w = 0; R && w < W; ++w) {
+            label[w] = (int)(w % R);
+            if (w % R + 1 == (size_t)R) continue;  // the last slot of a ladder has no pair of its own
+            double col[MAX_XJ];
+            qs_pair_table(h, (int)w, col, &sgn[w]);
+            for (int j = 0; j < J; ++j) tab[(size_t)j * W + w] = col[j];
+        }
+        MCHK(hipMemcpyAsync(t.replica, label.data(), W * 4, hipMemcpyHostToDevice, h->stream));
+        MCHK(hipMemcpyAsync(t.sgn, sgn.data(), W * 4, hipMemcpyHostToDevice, h->stream));
+        if (J > 0) MCHK(hipMemcpyAsync(t.t, tab.data(), (size_t)J * W * 8, hipMemcpyHostToDevice, h->stream));
+    }
+    MCHK(hipStreamSynchronize(h->stream));
+    return DQMC_OK;
+}
+
+int dqmc_qs_exchange(dqmc_qs_handle *h)
+{
+    if (!h) return mc_fail(nullptr, DQMC_ERR_INVALID, "dqmc_qs_exchange: null handle");
+    if (h->xch.R < 2)
+        return mc_fail(h, DQMC_ERR_STATE, "dqmc_qs_exchange: no ladders (dqmc_qs_set_exchange with n_replicas >= 2 first)");
+    MCHK(hipSetDevice(h->device));
+    if (int rc = qs_launch_exchange(h, 0, 0)) return rc;
+    MCHK(hipStreamSynchronize(h->stream));
+    return DQMC_OK;
+}
+
+int dqmc_qs_get_exchange_stats(dqmc_qs_handle *h, int32_t walker, dqmc_qs_exchange_stats *out)
+{
+    if (int rc = mc_walker(h, walker, "dqmc_qs_get_exchange_stats")) return rc;
+    if (!out) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_qs_get_exchange_stats: null out");
+    MCHK(hipSetDevice(h->device));
+    const dqmc_qs_handle::Tempering &t = h->xch;
+    long long prop = 0, acc = 0;
+    int label = 0;
+    int rc = 0;
+    if (t.sgn && ((rc = mc_get(h, t.prop, 0, walker, &prop)) || (rc = mc_get(h, t.acc, 0, walker, &acc)) ||
+                  (rc = mc_get(h, t.replica, 0, walker, &label))))
+        return rc;
+    out->prop_exchange = prop;
+    out->acc_exchange = acc;
+    out->replica = label;
+    out->rounds = t.cursor;
+    return DQMC_OK;
+}
+
+// (in a function whose handle is `h`)
+#define QS_BIN_OK(h, fn)                                                                   \
+    if (!(h)) return mc_fail(nullptr, DQMC_ERR_INVALID, std::string(fn) + ": null handle"); \
+    if (!(h)->bin.on) return mc_fail((h), DQMC_ERR_STATE, std::string(fn) + ": the binner is not enabled")
+
+int dqmc_qs_binner_enable(dqmc_qs_handle *h, int64_t capacity)
+{
+    if (!h) return mc_fail(nullptr, DQMC_ERR_INVALID, "dqmc_qs_binner_enable: null handle");
+    if (capacity < 0) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_qs_binner_enable: capacity must be positive (0 selects 100000)");
+    if (capacity == 0) capacity = QS_BIN_DEFAULT_CAPACITY;
+    if (capacity > ((int64_t)1 << 40)) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_qs_binner_enable: capacity above 2^40");
+    MCHK(hipSetDevice(h->device));
+    MCHK(hipStreamSynchronize(h->stream));
+    dqmc_qs_handle::Binner &b = h->bin;
+    b.on = false;
+    b.cap = 0;
+    if (int rc = b.alloc(h, 6, 3, 6, mc_tables::bin_levels(capacity))) return rc;
+    MCHK(hipStreamSynchronize(h->stream));
+    b.on = true;
+    b.cap = capacity;
+    return DQMC_OK;
+}
+
+int dqmc_qs_binner_size(dqmc_qs_handle *h, int32_t *n_levels, int64_t *n_pushed)
+{
+    QS_BIN_OK(h, "dqmc_qs_binner_size");
+    if (n_levels) *n_levels = h->bin.L;
+    if (n_pushed) *n_pushed = h->bin.T;
+    return DQMC_OK;
+}
+
+int dqmc_qs_binner_reliable_level(dqmc_qs_handle *h, int32_t *level)
+{
+    QS_BIN_OK(h, "dqmc_qs_binner_reliable_level");
+    if (!level) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_qs_binner_reliable_level: null level");
+    *level = mc_tables::bin_reliable(h->bin.T, h->bin.L);
+    return DQMC_OK;
+}
+
+int dqmc_qs_binner_get_level(dqmc_qs_handle *h, int32_t walker, int32_t level, double x_sum[6], double x2_sum[6],
+                             double xy_sum[3], int64_t *count)
+{
+    QS_BIN_OK(h, "dqmc_qs_binner_get_level");
+    if (int rc = mc_walker(h, walker, "dqmc_qs_binner_get_level")) return rc;
+    return h->bin.level_sums(h, "dqmc_qs_binner_get_level", walker, level, x_sum, x2_sum, xy_sum, count);
+}
+
+int dqmc_qs_binner_finish(dqmc_qs_handle *h, int32_t walker, int32_t level, dqmc_qs_binned *out)
+{
+    QS_BIN_OK(h, "dqmc_qs_binner_finish");
+    if (int rc = mc_walker(h, walker, "dqmc_qs_binner_finish")) return rc;
+    if (!out) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_qs_binner_finish: null out");
+    return h->bin.finish(h, "dqmc_qs_binner_finish", walker, level, false, out->mean, out->varN, out->varN0, out->tau,
+                         out->covN, &out->count, &out->level);
 }
 
 int dqmc_qs_set_cluster_rate(dqmc_qs_handle *h, int32_t rate)

@@ -11,8 +11,8 @@ import math
 
 import numpy as np
 
-from ._lib import DQMCError, ERR_INVALID, QsClusterStats, QsParams, QsStats, lib
-from .mc import _MCBase, _choose_lattice, _llround
+from ._lib import DQMCError, ERR_INVALID, QsBinned, QsClusterStats, QsExchangeStats, QsParams, QsStats, lib
+from .mc import _MCBase, _choose_lattice, _delta_var, _llround
 
 Q_MAX = 64
 Q30 = 2.0 ** 30
@@ -116,8 +116,9 @@ class ClockModel(QStateModel):
 
 
 _ISING_ONLY = "MC with a q-state model: %s is implemented for the IsingModel only (the q-state engine has local " \
-              "checkerboard sweeps and its own reflection cluster moves, cluster_rate=k; replica exchange, the device " \
-              "binner, FSS and the sequential sweep are out of scope)"
+              "checkerboard sweeps and keywords of its own: cluster_rate=k for its reflection cluster moves, " \
+              "tempering=(R, k) for replica exchange and binner=True | capacity for the device binner; FSS, " \
+              "checkpointing and the sequential sweep are out of scope)"
 
 
 class QStateMC(_MCBase):
@@ -125,23 +126,37 @@ class QStateMC(_MCBase):
     class by colour class (`colouring=None`: greedy_colouring(lattice)) under the rule of include/dqmc_hip.h.  `beta`
     may be a sequence of n_walkers values.  `cluster_rate=k > 0` runs one reflection cluster move per walker behind every
     sweep whose index is a multiple of k, before its measurement (the header's "Cluster move": the Wolff move for Potts
-    models, Wolff's reflection along the q lattice axes for clock models); 0, the default, runs none.  The Ising-only
-    options (cluster_moves, global_moves, n_replicas, exchange_rate, fss, binning, update="sequential") raise
-    NotImplementedError."""
+    models, Wolff's reflection along the q lattice axes for clock models); 0, the default, runs none.
+
+    `tempering=(R, k)` makes every R consecutive walkers a ladder for replica exchange (the header's "Replica exchange";
+    n_walkers a multiple of R) and runs one round behind every k-th sweep: after its cluster move, before its
+    measurement.  A `beta` or `T` sequence of R values is tiled over the ladders.  Walker w stays at beta_w with its
+    streams, sums, series and binner; an accepted exchange swaps the configurations (states, E_int, Mx, My and the
+    replica label) of two neighbouring walkers, so measurements(w), series(w), binned(w) and exchange_stats(w) remain
+    "at beta_w".  `binner=True | capacity` gives every walker a logarithmic binner over [E, E2, |M|, M2, M2, M4], pushed
+    on the device where the measurement is taken (enable_binning); binned() answers mean, std_error and tau.
+
+    The Ising-only options (cluster_moves, global_moves, n_replicas, exchange_rate, fss, binning, update="sequential")
+    raise NotImplementedError."""
     _abi = "dqmc_qs_"
 
     def __init__(self, model, beta=None, T=None, n_walkers=1, seed=123, first_walker=0, thermalization=0, sweeps=1000,
                  measure_rate=1, print_rate=1000, global_moves=False, global_rate=5, device_id=0, series_capacity=0,
                  cluster_moves=False, binning=False, binning_capacity=None, n_replicas=0, exchange_rate=0,
-                 fss=False, update=None, colouring=None, cluster_rate=0):
+                 fss=False, update=None, colouring=None, cluster_rate=0, tempering=None, binner=False):
         for name, on in (("global_moves", global_moves), ("cluster_moves", cluster_moves), ("binning", binning),
                          ("n_replicas", n_replicas), ("exchange_rate", exchange_rate),
                          ("fss", fss is not False and fss is not None),
                          ('update="%s"' % update, update not in (None, "checkerboard"))):
             if on:
                 raise NotImplementedError(_ISING_ONLY % name)
-        self._init_common(model, self._resolve_beta(beta, T), n_walkers, seed, first_walker, thermalization, sweeps,
-                          measure_rate, print_rate, series_capacity)
+        beta = self._resolve_beta(beta, T)
+        R, k = self._tempering(tempering, n_walkers)
+        capacity = self._binner_capacity(binner)
+        if R >= 2 and beta.ndim == 1 and len(beta) == R:
+            beta = np.tile(beta, n_walkers // R)  # one ladder's temperatures, the same in every ladder
+        self._init_common(model, beta, n_walkers, seed, first_walker, thermalization, sweeps, measure_rate, print_rate,
+                          series_capacity)
         cluster_rate = self._cluster_rate(cluster_rate)
         self.q = model.q
         self.update = "checkerboard"
@@ -158,6 +173,38 @@ class QStateMC(_MCBase):
         self.cluster_rate = 0
         if cluster_rate:
             self.set_cluster_rate(cluster_rate)
+        self.n_replicas, self.exchange_rate = 0, 0
+        if R or k:
+            self.set_exchange(R, k)
+        if capacity is not False:
+            self.enable_binning(capacity)
+
+    @staticmethod
+    def _tempering(tempering, n_walkers):
+        """(R, k) of tempering=(R, k); None: (0, 0)"""
+        if tempering is None:
+            return 0, 0
+        try:
+            R, k = tempering
+        except (TypeError, ValueError):
+            raise ValueError("tempering must be a pair (n_replicas, rate), got %r" % (tempering,))
+        for v in (R, k):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
+                raise ValueError("tempering=(n_replicas, rate): integers >= 0, got %r" % (tempering,))
+        if R >= 2 and n_walkers % R != 0:
+            raise ValueError("tempering: n_walkers = %d is not a multiple of n_replicas = %d" % (n_walkers, R))
+        return int(R), int(k)
+
+    @staticmethod
+    def _binner_capacity(binner):
+        """False: no binner; None: the default capacity; else the capacity"""
+        if binner is False or binner is None:
+            return False
+        if binner is True:
+            return None
+        if not isinstance(binner, (int, np.integer)) or binner < 1:
+            raise ValueError("binner must be True, False or a capacity >= 1, got %r" % (binner,))
+        return int(binner)
 
     @staticmethod
     def _cluster_rate(k):
@@ -206,6 +253,119 @@ class QStateMC(_MCBase):
         st = QsClusterStats()
         self._c(lib().dqmc_qs_get_cluster_stats(self._h, walker, C.byref(st)))
         return st
+
+    # ---- replica exchange
+    def set_exchange(self, n_replicas, rate):
+        """dqmc_qs_set_exchange: ladders of n_replicas consecutive walkers (0 or 1: none), a round after every rate-th
+        sweep, behind its cluster move and before its measurement (0: none); resets the exchange cursor, the replica
+        labels and the exchange counters"""
+        self._c(lib().dqmc_qs_set_exchange(self._h, int(n_replicas), int(rate)))
+        self.n_replicas, self.exchange_rate = int(n_replicas), int(rate)
+
+    def exchange(self):
+        """one exchange round by hand (dqmc_qs_exchange), counted in the exchange stats, no measurement"""
+        self._c(lib().dqmc_qs_exchange(self._h))
+
+    def exchange_stats(self, walker=0):
+        """prop_exchange and acc_exchange of the pair (walker, walker + 1), the label `replica` of the configuration
+        now in the slot, and `rounds` (the exchange cursor)"""
+        st = QsExchangeStats()
+        self._c(lib().dqmc_qs_get_exchange_stats(self._h, walker, C.byref(st)))
+        return st
+
+    def replicas(self):
+        """the replica labels of all slots: replicas()[w] is the ladder-local index of the slot in which the
+        configuration now in slot w started"""
+        return np.array([self.exchange_stats(w).replica for w in range(self.n_walkers)], dtype=np.int64)
+
+    # ---- error bars
+    def enable_binning(self, capacity=None):
+        """a logarithmic binner per walker over [E, E2, |M|, M2, M2, M4] (capacity None: 100000 measurements), pushed
+        on the device where the measurement is taken; enabling again starts anew.  A sweep() whose measurements would
+        pass the capacity raises before anything runs."""
+        self._c(lib().dqmc_qs_binner_enable(self._h, 0 if capacity is None else int(capacity)))
+
+    def binner_size(self):
+        """(levels, pushes so far)"""
+        L, T = C.c_int32(), C.c_int64()
+        self._c(lib().dqmc_qs_binner_size(self._h, C.byref(L), C.byref(T)))
+        return L.value, T.value
+
+    def binner_reliable_level(self):
+        lv = C.c_int32()
+        self._c(lib().dqmc_qs_binner_reliable_level(self._h, C.byref(lv)))
+        return lv.value
+
+    def binner_level(self, walker, level):
+        """(x_sum[6], x2_sum[6], xy_sum[3], count) of one level of one walker: elements [E, E2, |M|, M2, M2, M4], pairs
+        (E, E2), (|M|, M2) and (M2, M4)"""
+        xs, x2, xy, n = np.zeros(6), np.zeros(6), np.zeros(3), C.c_int64()
+        dp = C.POINTER(C.c_double)
+        self._c(lib().dqmc_qs_binner_get_level(self._h, walker, level, xs.ctypes.data_as(dp), x2.ctypes.data_as(dp),
+                                               xy.ctypes.data_as(dp), C.byref(n)))
+        return xs, x2, xy, n.value
+
+    def binner_finish(self, walker=0, level=None):
+        """dqmc_qs_binned of one walker at `level` (None: the reliable level)"""
+        out = QsBinned()
+        self._c(lib().dqmc_qs_binner_finish(self._h, walker, -1 if level is None else int(level), C.byref(out)))
+        return out
+
+    def _binned_walker(self, walker, level):
+        """per observable (mean, variance of the mean at `level`, the same at level 0 or None) of one walker"""
+        b = self.binner_finish(walker, level)
+        beta, invN = float(self.betas[walker]), 1.0 / self.N
+        E, E2, M, M2, M2b, M4 = b.mean
+        v, v0 = b.varN, b.varN0
+
+        def fluct(scale, x, x2, vx, vx2, cov):  # scale (<x2> - <x>^2): gradient (-2 x, 1) with respect to (x, x2)
+            return scale * (x2 - x * x), scale * scale * _delta_var((-2.0 * x, 1.0), vx, vx2, cov), None
+
+        with np.errstate(invalid="ignore", divide="ignore"):
+            m2, m4 = np.float64(M2b), np.float64(M4)
+            U4 = float(1.0 - m4 / (2.0 * m2 * m2))
+            gU = (float(m4 / (m2 * m2 * m2)), float(-1.0 / (2.0 * m2 * m2)))
+        obs = {"E": (E, v[0], v0[0]), "E2": (E2, v[1], v0[1]), "e": (E * invN, v[0] * invN * invN, v0[0] * invN * invN),
+               "C": fluct(beta * beta * invN, E, E2, v[0], v[1], b.covN[0]),
+               "M": (M, v[2], v0[2]), "M2": (M2, v[3], v0[3]), "M4": (M4, v[5], v0[5]),
+               "m": (M * invN, v[2] * invN * invN, v0[2] * invN * invN),
+               "chi": fluct(beta * invN, M, M2, v[2], v[3], b.covN[1]),
+               "U4": (U4, _delta_var(gU, v[4], v[5], b.covN[2]), None)}
+        return obs, int(b.count), int(b.level)
+
+    def binned(self, walker=0, level=None, walkers=None):
+        """mean, std_error and tau from the device binner at `level` (None: the reliable one): {"Energy": {E, E2, e, C},
+        "Magn": {M, M2, M4, m, chi, U4}, "count", "level"}, each observable {mean, std_error, tau}.  C, chi and
+        U4 = 1 - <M4> / (2 <M2>^2) get their error by the delta method on the binned covariances of (E, E2), (|M|, M2)
+        and (M2, M4); their tau is NaN (they are no time series).  `walkers=[...]` pools chains of equal beta as
+        MC.binned does: mean = sum_w mean_w / W, std_error = sqrt(sum_w var_w) / W (C, chi and U4 formed per walker
+        first), tau from the summed variances, plus std_error_walkers = sqrt(sum_w (mean_w - mean)^2 / (W (W - 1))).
+        Under replica exchange the values are those of the slot: "at beta_w"."""
+        pooled = walkers is not None
+        ws = [int(w) for w in walkers] if pooled else [walker]
+        if not ws:
+            raise ValueError("binned: no walker given")
+        if any(self.betas[w] != self.betas[ws[0]] for w in ws):
+            raise ValueError("binned: the pooled walkers must share one beta")
+        per = [self._binned_walker(w, level) for w in ws]
+        W = float(len(ws))
+        out = {"Energy": {}, "Magn": {}, "count": per[0][1], "level": per[0][2]}
+        for group, names in (("Energy", ("E", "E2", "e", "C")), ("Magn", ("M", "M2", "M4", "m", "chi", "U4"))):
+            for k in names:
+                means = np.array([p[0][k][0] for p in per])
+                vl = float(np.sum([p[0][k][1] for p in per]))
+                mean = float(means.sum() / W)
+                o = {"mean": mean, "std_error": (math.sqrt(max(vl, 0.0)) if vl == vl else vl) / W, "tau": float("nan")}
+                if per[0][0][k][2] is not None:
+                    with np.errstate(invalid="ignore", divide="ignore"):
+                        o["tau"] = float(0.5 * (np.float64(vl) / np.sum([p[0][k][2] for p in per]) - 1.0))
+                if pooled:
+                    o["std_error_walkers"] = (math.sqrt(float(((means - mean) ** 2).sum()) / (W * (W - 1.0)))
+                                              if W >= 2 else float("nan"))
+                out[group][k] = o
+        if pooled:
+            out["n_walkers"] = len(ws)
+        return out
 
     def stats(self, walker=0):
         st = QsStats()
