@@ -1298,6 +1298,16 @@ int dqmc_mc_fss_binner_finish(dqmc_mc_handle *h, int32_t walker, int32_t level, 
  * that relative error of the acceptance probability is the size of the deviation from exact detailed balance.  A
  * colour pass is a product of commuting single-site Metropolis kernels, so the sweep leaves the Boltzmann weight of
  * E_int 2^-30 invariant to that accuracy.
+ * Domain of beta.  The decision u2 < p is consulted exactly where dE_int > 0, so a partial product that left the finite
+ * range would corrupt it: inf times a later factor accepts an uphill move whose true p is small, 0 or NaN rejects one
+ * whose true p is moderate.  Every partial product is the exponential of a sum of at most z exponents, each within
+ * beta range of zero, range = (max_d e_q30[d] - min_d e_q30[d]) 2^-30 (exact in fp64).  dqmc_qs_set_beta therefore
+ * accepts beta iff fl(fl(beta z) range) <= 700: then every partial product lies in [e^-700, e^700], finite, non-zero
+ * and normal (e^-700 = 1e-304 > DBL_MIN, e^700 < DBL_MAX), and the rounding of at most 8 factors cannot move it across
+ * either edge.  A beta outside is refused with DQMC_ERR_INVALID; the message names beta, z, the range and the bound,
+ * and the walker's beta, table and exchange tables stay as they were.  (|J e| = 4 of both signs and z = 8: beta <= 10.9;
+ * Potts with J = 1 on a square lattice: beta <= 175.)  The exchange tables need no such guard: their products have
+ * factors <= 1 only and can do no worse than underflow monotonically to 0, a correct "reject".
  *
  * Measurement.  After the sweep with global index i (first_sweep_index, first_sweep_index + 1, ..) iff
  * i > thermalization && i % measure_rate == 0 (the rule of dqmc_mc_sweep), inside the kernel, in this order of operations:

@@ -1,6 +1,6 @@
 // mc_tables.h — what the two engines of the classical MC flavor (ising.hip, qstate.hip) work out on the host before
 // anything reaches the device: the lattice tables of a create, the colour-sorted tables of a checkerboard sweep, the
-// arithmetic of the logarithmic binner, and the q-state engine's replica exchange (the pair tables, the product rule, the
+// arithmetic of the logarithmic binner, the beta domain of the q-state sweep, and the q-state engine's replica exchange (the pair tables, the product rule, the
 // cut of a sweep call into launches).  Plain C++17, no device runtime: mc_host.h includes it, and
 // tests/mc_tables_check.cpp and tests/qs_exchange_check.cpp build it alone under the host sanitizers.  A refusal returns false with the message in *err,
 // prefixed with the name of the ABI function the caller passes as fn.
@@ -10,6 +10,7 @@
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
+#include <cstdio>
 #include <string>
 #include <vector>
 
@@ -144,6 +145,33 @@ inline void bin_finish(int n_elem, int n_pairs, bool pairs_from_first, int64_t T
     }
     for (int p = 0; p < n_pairs; ++p)
         covN[p] = pairs_from_first ? bin_covN(xs[0], xs[1 + p], xy[p], nl) : bin_covN(xs[2 * p], xs[2 * p + 1], xy[p], nl);
+}
+
+// ---- the finite domain of the q-state sweep's acceptance product (include/dqmc_hip.h, "Sweep" of the q-state section)
+// Every partial product of p = fl(p w[a_k][b_k]), k < z, is the exponential of a sum of at most z exponents, each within
+// beta range of zero, range = (max_d e_q30[d] - min_d e_q30[d]) 2^-30 (exact in fp64: the difference is below 2^34).
+// With beta z range <= 700 all of them lie in [e^-700, e^700]: finite, non-zero and normal, with room for the rounding
+// of 8 factors.  The comparison is fl(fl(beta z) range) <= 700.
+constexpr double QS_BETA_DOMAIN = 700.0;
+inline double qs_table_range(const int64_t *e_q30, int q)
+{
+    int64_t lo = e_q30[0], hi = e_q30[0];
+    for (int d = 1; d < q; ++d) {
+        lo = std::min(lo, e_q30[d]);
+        hi = std::max(hi, e_q30[d]);
+    }
+    return (double)(hi - lo) * (1.0 / 1073741824.0);
+}
+inline bool qs_beta_in_domain(const std::string &fn, double beta, int z, const int64_t *e_q30, int q, std::string *err)
+{
+    const double range = qs_table_range(e_q30, q);
+    if (beta * (double)z * range <= QS_BETA_DOMAIN) return true;
+    char buf[256];
+    std::snprintf(buf, sizeof buf,
+                  ": beta = %.17g with z = %d and a table range of %.17g gives beta z range = %.17g, above the bound of "
+                  "%g under which every partial acceptance product is finite and non-zero",
+                  beta, z, range, beta * (double)z * range, QS_BETA_DOMAIN);
+    return *err = fn + buf, false;
 }
 
 // ---- replica exchange of the q-state engine (include/dqmc_hip.h, "Replica exchange" of the q-state section)

@@ -706,6 +706,12 @@ int dqmc_qs_set_beta(dqmc_qs_handle *h, int32_t walker, double beta)
     if (!std::isfinite(beta) || beta < 0.0)
         return mc_fail(h, DQMC_ERR_INVALID, "dqmc_qs_set_beta: beta must be finite and >= 0");
     const int q = h->q;
+    {  // the domain in which no partial acceptance product overflows or vanishes; a refusal changes nothing
+        const std::vector<int64_t> e(h->e_h.begin(), h->e_h.end());
+        std::string msg;
+        if (!mc_tables::qs_beta_in_domain("dqmc_qs_set_beta", beta, h->z, e.data(), q, &msg))
+            return mc_fail(h, DQMC_ERR_INVALID, msg);
+    }
     std::vector<double> wt((size_t)q * q);
     for (int a = 0; a < q; ++a)
         for (int b = 0; b < q; ++b) {

@@ -128,6 +128,12 @@ class QStateMC(_MCBase):
     sweep whose index is a multiple of k, before its measurement (the header's "Cluster move": the Wolff move for Potts
     models, Wolff's reflection along the q lattice axes for clock models); 0, the default, runs none.
 
+    The domain of beta: a site's acceptance is a product of z table entries exp(-beta (e[a] - e[b])), each partial
+    product the exponential of at most z exponents within beta * range of zero, range = max(J e) - min(J e) of the
+    fixed-point table.  With beta * z * range <= 700 every partial product stays in [e^-700, e^700], finite and
+    non-zero; beyond it one could become inf or 0 and decide an uphill move wrongly, so MC(...) and set_beta raise
+    DQMCError (ERR_INVALID) there and leave the walker as it was.
+
     `tempering=(R, k)` makes every R consecutive walkers a ladder for replica exchange (the header's "Replica exchange";
     n_walkers a multiple of R) and runs one round behind every k-th sweep: after its cluster move, before its
     measurement.  A `beta` or `T` sequence of R values is tiled over the ladders.  Walker w stays at beta_w with its

@@ -1,5 +1,5 @@
 // The host arithmetic of the q-state engine's replica exchange (csrc/mc_tables.h: J, a pair's table, the product rule,
-// the cut of a dqmc_qs_sweep call into launches) on its own: built by tests/test_qs_exchange_host.py with
+// the cut of a dqmc_qs_sweep call into launches) and the beta domain of its sweep (qs_beta_in_domain) on their own: built by tests/test_qs_exchange_host.py with
 // g++ -fsanitize=address,undefined and run as a child process on the CPU.  The program only prints its inputs and what
 // the header makes of them (doubles as hex floats); the pytest side restates every line in numpy and compares.
 #include <cinttypes>
@@ -22,6 +22,9 @@ int main()
         {7, {0, 0, 0}},
         {1, {1, 0}},
         {2147483647, {4294967296, 0}},                                   // beyond what a table can hold
+        // |e_q30| = 2^32 on the bond counts of CubicLattice(4, 3) and BilayerSquareLattice(4): clock q = 7 with J = 4
+        {324, {4294967296, 2677868308, -955720134, -3869631822, -3869631822, -955720134, 2677868308}},
+        {80, {-4294967296, 0, 0}},                                       // Potts q = 3 with J = -4
     };
     for (const auto &c : bits) {
         std::printf("bits %" PRId64 " %d :", c.first, qs_exchange_bits(c.first, c.second.data(), (int)c.second.size()));
@@ -44,6 +47,35 @@ int main()
         for (int64_t d : {(int64_t)0, (int64_t)1073741824, (int64_t)-1073741824, (int64_t)5, (int64_t)-5})
             for (double u : {0.0, 0.5, 0.9499, 0.9999999})
                 std::printf("swaps %a %" PRId64 " %a %d\n", db, d, u, qs_exchange_swaps(sgn, d, t.data(), J, u) ? 1 : 0);
+    }
+    // the finite domain of the sweep's acceptance product: z, the table, then (beta, verdict) for the doubles around
+    // 700 / (z range), nine steps of one ulp, and the message of the first refusal
+    const std::vector<std::pair<int, std::vector<int64_t>>> domains = {
+        {4, {1073741824, 536870912, -536870912, -1073741824, -536870912, 536870912}},  // clock q = 6: range 2
+        {8, {4294967296, -4294967296, -4294967296}},                                    // |J e| = 4 of both signs: range 8
+        {8, {4294967296, 2677868308, -955720134, -3869631822, -3869631822, -955720134, 2677868308}},  // clock q = 7, J = 4
+        {5, {-1073741824, 0, 0}},                                                       // Potts q = 3, J = -1, z = 5
+    };
+    for (const auto &c : domains) {
+        const int q = (int)c.second.size();
+        const double range = qs_table_range(c.second.data(), q);
+        std::printf("domain %d %a :", c.first, range);
+        for (int64_t e : c.second) std::printf(" %" PRId64, e);
+        std::printf("\n");
+        double beta = QS_BETA_DOMAIN / ((double)c.first * range);
+        for (int i = 0; i < 4; ++i) beta = std::nextafter(beta, 0.0);
+        std::string first;
+        for (int i = 0; i < 9; ++i, beta = std::nextafter(beta, 1.0e300)) {
+            std::string err;
+            const bool ok = qs_beta_in_domain("fn", beta, c.first, c.second.data(), q, &err);
+            if (!ok && first.empty()) first = err;
+            std::printf("verdict %d %a %d\n", c.first, beta, ok ? 1 : 0);
+        }
+        std::printf("refusal %s\n", first.c_str());
+        for (double b : {0.0, 1.0, 50.0, 1.0e300}) {
+            std::string err;
+            std::printf("verdict %d %a %d\n", c.first, b, qs_beta_in_domain("fn", b, c.first, c.second.data(), q, &err) ? 1 : 0);
+        }
     }
     // the launch cut: n, first, thermalization, rate, k, chunk, T0
     const int64_t cuts[][7] = {

@@ -35,6 +35,7 @@ class ClusterWalkers(ref.Walkers):
         self.acc_global = np.zeros(W, dtype=np.int64)
         self.sum_cluster_size = np.zeros(W, dtype=np.int64)
         self.max_cluster_size = np.zeros(W, dtype=np.int64)  # (not a counter of the engine: for the tests' own use)
+        self.n_partial = np.zeros(W, dtype=np.int64)  # (likewise: the moves with 1 < |C| < N)
         self.last_dE = np.zeros(W, dtype=np.int64)  # dE_int of every walker's last move
         self.last = None                            # the last call's walkers, cluster masks, reflections and states before
 
@@ -83,6 +84,7 @@ class ClusterWalkers(ref.Walkers):
         self.acc_global[ws] += size > 1
         self.sum_cluster_size[ws] += size
         self.max_cluster_size[ws] = np.maximum(self.max_cluster_size[ws], size)
+        self.n_partial[ws] += (size > 1) & (size < N)
         self.m[ws] = m + np.uint64(1)
 
     def run(self, first, n, thermalization, measure_rate, cluster_rate=0):

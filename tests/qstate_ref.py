@@ -10,6 +10,7 @@ include/dqmc_hip.h ("the classical MC flavor with q-state models") and independe
               p = 1.0 then p = p * w[a_k][b_k] for k = 0 .. z - 1, accept iff dE_int <= 0 or u2 < p
   w           w[a][b] = exp(-beta ((e_q30[a] - e_q30[b]) 2^-30)) by the host's libm (math.exp: the C library's exp, as
               the product's host code calls it; numpy's own exp may differ in the last bit)
+  domain      beta is accepted iff beta z range <= 700, range = (max e_q30 - min e_q30) 2^-30: every partial p is finite
   measure     e = E_int 2^-30, x = Mx 2^-30, y = My 2^-30, m2 = x x + y y; sum_E += e, sum_E2 += e e, sum_M2 += m2,
               sum_M4 += m2 m2, sum_absM += sqrt(m2), one rounding each, in the order of the measurements
 
@@ -61,6 +62,27 @@ def weights(e_q30, beta):
         for b in range(q):
             w[a, b] = math.exp(-float(beta) * (float(int(e_q30[a]) - int(e_q30[b])) / Q30))
     return w
+
+
+BETA_DOMAIN = 700.0
+
+
+def beta_in_domain(beta, z, e_q30):
+    """the header's domain of the acceptance product: fl(fl(beta z) range) <= 700 with the exact
+    range = (max e_q30 - min e_q30) 2^-30.  Inside it every partial product of z table entries is finite and non-zero."""
+    rng = float(int(max(e_q30)) - int(min(e_q30))) / Q30
+    return float(beta) * float(z) * rng <= BETA_DOMAIN
+
+
+def domain_edge(z, e_q30):
+    """(the largest beta inside the domain, the smallest outside)"""
+    rng = float(int(max(e_q30)) - int(min(e_q30))) / Q30
+    b = BETA_DOMAIN / (float(z) * rng)
+    while beta_in_domain(b, z, e_q30):
+        b = math.nextafter(b, math.inf)
+    while not beta_in_domain(b, z, e_q30):
+        b = math.nextafter(b, 0.0)
+    return b, math.nextafter(b, math.inf)
 
 
 def philox_two(keys, c0, c1, c2, c3):
@@ -138,6 +160,7 @@ class Walkers:
         self.r = np.zeros(self.W, dtype=np.uint64)
         self.prop_local = np.zeros(self.W, dtype=np.int64)
         self.acc_local = np.zeros(self.W, dtype=np.int64)
+        self.max_acc_dE = np.zeros(self.W, dtype=np.int64)  # (no counter of the engine: the largest accepted |dE_int|)
         self.reset_accumulators()
         if rand:
             self.rand_conf()
@@ -200,6 +223,7 @@ class Walkers:
             self.My += np.where(accept, self.s_q30[t] - self.s_q30[so], 0).sum(axis=1)
             c[:, idx] = np.where(accept, t, so)
             self.acc_local += accept.sum(axis=1)
+            self.max_acc_dE = np.maximum(self.max_acc_dE, np.where(accept, np.abs(dE), 0).max(axis=1))
         self.prop_local += self.N
         self.s = self.s + np.uint64(1)
 

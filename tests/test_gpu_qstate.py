@@ -71,6 +71,24 @@ def test_parity_on_the_shapes_where_the_kernel_can_go_wrong(gpu, shape):
     mc.close()
 
 
+def test_a_coupling_other_than_one(gpu):
+    """clock q = 6 on TriangularLattice(6) with J = 0.5: the table is llround(J e 2^30), and at twice the beta of the
+    J = 1 shape the chain accepts as often"""
+    l = gpu.TriangularLattice(6)
+    W, seed, cap, n, J = 3, 700, 20, 8, 0.5
+    betas = 0.8 * np.array([0.8, 1.0, 1.25])
+    mc = gpu.MC(_model(gpu, "clock", 6, l, J=J), beta=betas, n_walkers=W, seed=seed, series_capacity=cap)
+    wk = ref.Walkers(l, 6, _table("clock", 6), betas, [seed + w for w in range(W)], J=J, series_capacity=cap)
+    assert wk.e_q30.tolist() == [2 ** 29, 2 ** 28, -2 ** 28, -2 ** 29, -2 ** 28, 2 ** 28]
+    _check(mc, wk, "J = 0.5, initial")
+    mc.sweep(n)
+    wk.run(1, n, 0, 1)
+    _check(mc, wk, "J = 0.5")
+    st = mc.stats(1)
+    assert st.n_meas == n and 0.3 < st.acc_local / st.prop_local < 0.7
+    mc.close()
+
+
 def test_the_site_ceiling(gpu):
     """N = 16384, the LDS limit: one walker, two sweeps"""
     l = gpu.SquareLattice(128)
