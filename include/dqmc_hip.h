@@ -1391,6 +1391,45 @@ int dqmc_mc_fss_binner_finish(dqmc_mc_handle *h, int32_t walker, int32_t level, 
  * The sums, series and chains are exactly those of a handle without a binner.  The elements with a square root (|M|,
  * and the cross sum of (|M|, M2)) inherit the device's sqrt and compare at 1e-13 relative, all others bit for bit.
  *
+ * Scaling (dqmc_qs_set_scaling).  The structure factor of the two-component order parameter m_i = (cos theta_i,
+ * sin theta_i), theta = 2 pi s / q: S(k) = (|sum_i cos theta_i e^{i k . r_i}|^2 + |sum_i sin theta_i e^{i k . r_i}|^2) / N =
+ * sum_ij m_i . m_j cos(k . (r_i - r_j)) / N, the transform of the correlation function, at up to 8 wave vectors, for the
+ * second-moment correlation length xi = sqrt(S(0)/S(k) - 1)/(2 sin(|k|/2)), S(0) = <M2>/N (tests/qstate_scaling_ref.py
+ * restates this part).
+ *   phase tables  the host passes n_k wave vectors, 1 <= n_k <= 8, as int32 cos_q30[n_k][N] and sin_q30[n_k][N], site
+ *                 order as dqmc_qs_get_conf: cos_q30[k][i] = llround(cos(k . r_i) 2^30) and the sine likewise, magnitude
+ *                 <= 2^30 (the tables of dqmc_mc_set_fss).
+ *   exact part    per measurement, walker and k, for every state t < q: Ac[t] = sum_{i: s_i = t} cos_q30[k][i] and
+ *                 As[t] = sum_{i: s_i = t} sin_q30[k][i] in int64 (|.| <= 2^14 2^30 = 2^44: exact in any order), over the N
+ *                 sites only: the zero bytes that pad a walker's last configuration word are no sites of state 0.
+ *   fp64 part     u[t] A[t] can reach 2^74 and has no exact integer home, so the contraction over t is fp64 in a fixed
+ *                 order.  For (u, A) = (c_q30, Ac), (c_q30, As), (s_q30, Ac), (s_q30, As) in this order:
+ *                 F = +0.0; for t = 0 .. q - 1: F = fl(F + fl((double)u[t] (double)A[t])) (both conversions exact), giving
+ *                 F1 .. F4.  S_k = fl(fl(fl(fl(fl(F1 F1) + fl(F2 F2)) + fl(F3 F3)) + fl(F4 F4)) inv) with
+ *                 inv = 1.0 / ((double)N 2^120) from the host (N 2^120 is exact: one rounding).  numpy reproduces S_k and
+ *                 its running sum bit for bit.  F1 + i F2 and F3 + i F4 are the transforms of the two components; the
+ *                 complex number sum_i e^{i theta_i} e^{i k . r_i} = (F1 - F4) + i (F2 + F3) is another quantity, whose
+ *                 square differs from S_k N by 2 (F2 F3 - F1 F4): zero on average, not per configuration.  For q = 2,
+ *                 s_q30 = 0 and F3 = F4 = 0 exactly.  At
+ *                 k = 0 (cos_q30 = 2^30, sin_q30 = 0) S_k N equals m2 of "Measurement" up to rounding, in the units of
+ *                 sum_M2.  The table entries are off by at most 2^-31 each: |S_k - S(k)| <~ 2^-29 N.
+ *   when          exactly where the sweep's measurement is taken by the rule of "Measurement", on the configuration E
+ *                 and M are taken from: by "Order inside a sweep" after the cluster move and the exchange round.  Under
+ *                 replica exchange the value belongs to the slot ("at beta_w").
+ *   sums          per walker sum_S[8] (each += S_k, one rounding per measurement, in the order of the measurements) and
+ *                 an n_meas of its own: the feature may be switched on mid-run.  dqmc_qs_reset_accumulators clears them.
+ *   binner        with the binner enabled, a second section over the elements [M2, S_0 .. S_{n_k - 1}] under the level /
+ *                 compressor scheme of the first: M2 is the m2 the first section gets, cross sums xy_sum[n_k] of the pairs
+ *                 (M2, S_k), device layout [level][element][walker], a push count of its own.  The six-element section,
+ *                 its getters and its pushes are as they are without the feature.  dqmc_qs_set_scaling with a binner
+ *                 enabled restarts the binner with every section empty and its capacity kept; the capacity check of
+ *                 dqmc_qs_sweep covers both sections.  No element has a square root: all compare bit for bit.
+ * The measurement is a kernel of its own (csrc/qs_scaling.inl) that dqmc_qs_sweep launches behind every measured sweep,
+ * behind the exchange kernel where that sweep has a round, on the configuration in device memory; with the feature on,
+ * a launch of the sweep kernel additionally ends at every measured sweep (mc_tables.h, qs_scaling_cut).  The chains, the
+ * sums, the series, the draws and the first binner section are those of a handle without the feature, and with
+ * n_k = 0 (the default) so is every launch.  Results do not depend on how a run is split into dqmc_qs_sweep calls.
+ *
  * Limits: n_sites <= 16384, 1 <= z <= 8, 2 <= q <= 64, n_colours <= 16.  Errors come from dqmc_qs_last_error. */
 typedef struct dqmc_qs_handle dqmc_qs_handle;
 
@@ -1506,6 +1545,36 @@ typedef struct {
 } dqmc_qs_binned;
 /* level < 0: the reliable level */
 int dqmc_qs_binner_finish(dqmc_qs_handle *h, int32_t walker, int32_t level, dqmc_qs_binned *out);
+
+/* "Scaling" above.  n_k in 1..8: the measurement on with these tables (copied); n_k = 0: off (the default; the tables
+ * are not looked at).  Resets the scaling sums; if the binner is enabled it starts anew with every section empty and
+ * its capacity kept.  DQMC_ERR_INVALID for n_k outside 0..8, a NULL table with n_k > 0 (these two are checked before the
+ * handle), or an entry above 2^30 in magnitude; the handle then stays as it was. */
+int dqmc_qs_set_scaling(dqmc_qs_handle *h, int32_t n_k, const int32_t *cos_q30 /* [n_k][n_sites] */,
+                        const int32_t *sin_q30 /* [n_k][n_sites] */);
+typedef struct {
+    int64_t n_meas;    /* scaling measurements summed since dqmc_qs_set_scaling / dqmc_qs_reset_accumulators */
+    int32_t n_k;       /* 0: the measurement is off (then everything else is 0) */
+    double sum_S[8];   /* entries at and above n_k are 0 */
+} dqmc_qs_scaling;
+int dqmc_qs_get_scaling(dqmc_qs_handle *h, int32_t walker, dqmc_qs_scaling *out);
+/* the sums of one level of one walker of the scaling section: x_sum and x2_sum hold 1 + n_k elements [M2, S_0 ..],
+ * xy_sum n_k pairs [(M2, S_0) ..]; any output may be NULL.  DQMC_ERR_STATE without a binner or with the measurement off. */
+int dqmc_qs_scaling_binner_get_level(dqmc_qs_handle *h, int32_t walker, int32_t level, double *x_sum, double *x2_sum,
+                                     double *xy_sum, int64_t *count);
+/* as dqmc_qs_binned, for the scaling section: entries at and above 1 + n_k (covN: n_k) are 0 */
+typedef struct {
+    double mean[9];    /* [M2, S_0 ..] */
+    double varN[9];    /* at `level` */
+    double varN0[9];   /* at level 0 */
+    double tau[9];
+    double covN[8];    /* at `level`, pairs (M2, S_0) .. */
+    int64_t count;
+    int32_t level;
+    int32_t n_k;
+} dqmc_qs_scaling_binned;
+/* level < 0: the reliable level (the last one with count >= 32, else 0) */
+int dqmc_qs_scaling_binner_finish(dqmc_qs_handle *h, int32_t walker, int32_t level, dqmc_qs_scaling_binned *out);
 
 /* ---- the SAC flavor: stochastic analytic continuation -----------------------------------------------------------
  * A(omega) from imaginary-time data by sampling (Sandvik, PRB 57, 10287; Beach, cond-mat/0403055; Shao and Sandvik,

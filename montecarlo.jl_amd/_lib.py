@@ -135,6 +135,15 @@ class QsBinned(C.Structure):
                 ("covN", C.c_double * 3), ("count", C.c_int64), ("level", C.c_int32)]
 
 
+class QsScaling(C.Structure):
+    _fields_ = [("n_meas", C.c_int64), ("n_k", C.c_int32), ("sum_S", C.c_double * 8)]
+
+
+class QsScalingBinned(C.Structure):
+    _fields_ = [("mean", C.c_double * 9), ("varN", C.c_double * 9), ("varN0", C.c_double * 9), ("tau", C.c_double * 9),
+                ("covN", C.c_double * 8), ("count", C.c_int64), ("level", C.c_int32), ("n_k", C.c_int32)]
+
+
 class SacParams(C.Structure):
     _fields_ = [("n_problems", C.c_int32), ("n_tau", C.c_int32), ("n_deltas", C.c_int32), ("n_omega", C.c_int32),
                 ("n_replicas", C.c_int32), ("device_id", C.c_int32), ("window", C.c_int32),
@@ -354,6 +363,10 @@ SIGNATURES = {
     "dqmc_qs_binner_reliable_level": (C.c_int, [_H, C.POINTER(C.c_int32)]),
     "dqmc_qs_binner_get_level": (C.c_int, [_H, C.c_int32, C.c_int32, _dp, _dp, _dp, _i64p]),
     "dqmc_qs_binner_finish": (C.c_int, [_H, C.c_int32, C.c_int32, C.POINTER(QsBinned)]),
+    "dqmc_qs_set_scaling": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "dqmc_qs_get_scaling": (C.c_int, [_H, C.c_int32, C.POINTER(QsScaling)]),
+    "dqmc_qs_scaling_binner_get_level": (C.c_int, [_H, C.c_int32, C.c_int32, _dp, _dp, _dp, _i64p]),
+    "dqmc_qs_scaling_binner_finish": (C.c_int, [_H, C.c_int32, C.c_int32, C.POINTER(QsScalingBinned)]),
     "dqmc_sac_create": (C.c_int, [C.POINTER(SacParams), C.POINTER(_H)]),
     "dqmc_sac_destroy": (C.c_int, [_H]),
     "dqmc_sac_last_error": (C.c_char_p, [_H]),

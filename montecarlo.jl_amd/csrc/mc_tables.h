@@ -217,8 +217,9 @@ struct SweepLaunch {
     bool defer_last;
     int64_t T_at_start;
 };
-inline std::vector<SweepLaunch> qs_sweep_cut(int n, int64_t first, int64_t thermalization, int64_t rate, int64_t k,
-                                             int chunk, int64_t T0)
+// (at_measured: a launch also ends at every measured sweep - the cut of qs_scaling_cut below)
+inline std::vector<SweepLaunch> qs_cut_launches(int n, int64_t first, int64_t thermalization, int64_t rate, int64_t k,
+                                                int chunk, int64_t T0, bool at_measured)
 {
     std::vector<SweepLaunch> out;
     int64_t T = T0;
@@ -226,6 +227,10 @@ inline std::vector<SweepLaunch> qs_sweep_cut(int n, int64_t first, int64_t therm
         const int64_t f = first + done;
         int64_t m = std::min<int64_t>(std::max(chunk, 1), n - done);
         if (k > 0) m = std::min<int64_t>(m, k - (f - 1) % k);
+        if (at_measured) {  // the first measured sweep at or behind f: the smallest multiple of rate above thermalization
+            const int64_t g0 = std::max<int64_t>(f, thermalization + 1);
+            m = std::min<int64_t>(m, (g0 + rate - 1) / rate * rate - f + 1);
+        }
         const int64_t last = f + m - 1;
         const bool round = k > 0 && last % k == 0;
         out.push_back(SweepLaunch{(int)m, f, round && last > thermalization && last % rate == 0, T});
@@ -233,6 +238,20 @@ inline std::vector<SweepLaunch> qs_sweep_cut(int n, int64_t first, int64_t therm
         done += (int)m;
     }
     return out;
+}
+inline std::vector<SweepLaunch> qs_sweep_cut(int n, int64_t first, int64_t thermalization, int64_t rate, int64_t k,
+                                             int chunk, int64_t T0)
+{
+    return qs_cut_launches(n, first, thermalization, rate, k, chunk, T0, false);
+}
+// The same call with the scaling measurement on (include/dqmc_hip.h, "Scaling" of the q-state section): a launch
+// additionally ends at every measured sweep, so that the measured configuration lies in device memory when the
+// measurement kernel runs behind the launch (and behind its round).  A launch then holds at most one measured sweep,
+// its last.  Rounds, defer_last and T_at_start follow the rule above; the launches still add up to the n sweeps.
+inline std::vector<SweepLaunch> qs_scaling_cut(int n, int64_t first, int64_t thermalization, int64_t rate, int64_t k,
+                                               int chunk, int64_t T0)
+{
+    return qs_cut_launches(n, first, thermalization, rate, k, chunk, T0, true);
 }
 
 }  // namespace mc_tables

@@ -23,6 +23,9 @@
 // level, and the next level's range is read from LDS behind it.  One pass over the queue then adds the boundary terms to
 // the lane's dE, dMx, dMy (the sweep's own registers) and writes the reflected bytes.  The host launches the instantiation
 // without moves whenever the rate is 0.
+//
+// The scaling measurement (the header's "Scaling": the structure factor of the order parameter at up to 8 wave vectors) is
+// a kernel of its own behind every measured sweep, qs_scaling.inl; the kernels above are what they are without it.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -354,6 +357,9 @@ __global__ __launch_bounds__(THREADS) void qs_exchange_kernel(DevState s, Exchan
     if (measure && tid == 0) qs_measure_slot(s, ba, a, E, Mx, My);
 }
 
+// the scaling measurement: ScalingArgs, qs_scaling_bin_push, qs_scaling_kernel
+#include "qs_scaling.inl"
+
 // dqmc_qs_cluster_move: one move of one walker (walker >= 0) or of every walker, with the sweep kernel's LDS layout
 __global__ __launch_bounds__(THREADS) void qs_cluster_move_kernel(DevState s, const long long *__restrict__ e_q30,
                                                                   const int2 *__restrict__ cs_q30, ClusterArgs ca,
@@ -496,6 +502,15 @@ struct dqmc_qs_handle : mc_handle_base {
         bool on = false;
         int64_t cap = 0;
     } bin;
+    struct Scaling {                    // dqmc_qs_set_scaling; n_k = 0: off
+        int n_k = 0;
+        int *cq = nullptr, *sq = nullptr;      // [n_k][4 Nw]: rows padded with zeros to whole configuration words
+        double *sS = nullptr;                  // [8][W] (allocated when the feature is first switched on)
+        long long *n_meas = nullptr;           // [W]
+        // the scaling section of the binner (there iff bin.on && n_k > 0; its levels and capacity are bin's): elements
+        // [M2, S_0 ..], pairs (M2, S_k), a compressor value per member of a pair
+        mc_bin_section bin;
+    } sc;
 };
 
 static const int64_t QS_BIN_DEFAULT_CAPACITY = 100000;  // as dqmc_mc_binner_enable
@@ -583,6 +598,59 @@ static int qs_launch_observables(dqmc_qs_handle *h, int walker)
     hipLaunchKernelGGL(qs_observables_kernel, dim3(walker >= 0 ? 1 : h->W), dim3(THREADS), 0, h->stream, h->d,
                        (const int *)h->bonds, (const long long *)h->e_q30, (const int2 *)h->cs_q30, walker);
     MCHK(hipGetLastError());
+    return 0;
+}
+
+static void qs_bin_free(dqmc_qs_handle *h)  // both sections; the binner is off afterwards
+{
+    h->sc.bin.free(h);
+    h->bin.free(h);
+    h->bin.on = false;
+    h->bin.cap = 0;
+}
+
+// the scaling section for the binner as it stands (nothing unless both are on)
+static int qs_scaling_bin_alloc(dqmc_qs_handle *h)
+{
+    dqmc_qs_handle::Scaling &f = h->sc;
+    f.bin.free(h);
+    if (!h->bin.on || f.n_k < 1) return 0;
+    return f.bin.alloc(h, 1 + f.n_k, f.n_k, 2 * f.n_k, h->bin.L);
+}
+
+static int qs_scaling_clear(dqmc_qs_handle *h)  // the sums and the section's state
+{
+    dqmc_qs_handle::Scaling &f = h->sc;
+    const size_t W = h->W;
+    if (f.sS) {
+        MCHK(hipMemsetAsync(f.sS, 0, (size_t)SC_MAX_K * W * 8, h->stream));
+        MCHK(hipMemsetAsync(f.n_meas, 0, W * 8, h->stream));
+    }
+    return f.bin.clear(h);
+}
+
+// the scaling measurement of the sweep whose last kernel has just been launched, and its push
+static int qs_launch_scaling(dqmc_qs_handle *h)
+{
+    dqmc_qs_handle::Scaling &f = h->sc;
+    ScalingArgs a{};
+    a.n_k = f.n_k;
+    a.shift = scaling_shift(h->q);
+    a.inv = 1.0 / std::ldexp((double)h->N, 120);  // N 2^120 is exact, one rounding
+    a.sS = f.sS;
+    a.n_meas = f.n_meas;
+    if (f.bin.xs) {
+        if (int rc = f.bin.next_lmax(h, "dqmc_qs_sweep", &a.lmax)) return rc;
+        a.bxs = f.bin.xs;
+        a.bx2 = f.bin.x2;
+        a.bxy = f.bin.xy;
+        a.bc = f.bin.c;
+        a.top = f.bin.L - 1;
+    }
+    hipLaunchKernelGGL(qs_scaling_kernel, dim3(h->W), dim3(THREADS), scaling_lds_bytes(f.n_k), h->stream, h->d, a,
+                       (const int4 *)f.cq, (const int4 *)f.sq, (const int2 *)h->cs_q30);
+    MCHK(hipGetLastError());
+    if (f.bin.xs) f.bin.T += 1;
     return 0;
 }
 
@@ -801,14 +869,21 @@ int dqmc_qs_sweep(dqmc_qs_handle *h, int32_t n_sweeps, int64_t first_sweep_index
                                                       measure_rate);
     if (b.on && b.T + n_meas > b.cap)
         return mc_fail(h, DQMC_ERR_STATE, "dqmc_qs_sweep: the measurements of this call would pass the binner's capacity");
+    dqmc_qs_handle::Scaling &sc = h->sc;
+    if (sc.bin.xs && sc.bin.T + n_meas > b.cap)
+        return mc_fail(h, DQMC_ERR_STATE, "dqmc_qs_sweep: the measurements of this call would pass the capacity of the "
+                                          "binner's scaling section");
     MCHK(hipSetDevice(h->device));
     const double per_sweep = ((double)h->N + QS_SWEEP_OVERHEAD) * std::max(1.0, (double)h->W / QS_RESIDENT_WALKERS);
     const int chunk = (int)std::max(1.0, std::min((double)n_sweeps, std::floor(QS_LAUNCH_BUDGET / per_sweep)));
     const bool cluster = h->ca.rate > 0;
     const size_t lds = sweep_lds_bytes(h->q, h->Nw) + (cluster ? cluster_lds_bytes(h->N) : 0);
     const int k = h->xch.R >= 2 ? h->xch.rate : 0;  // an exchange round after every k-th sweep
-    for (const mc_tables::SweepLaunch &l : mc_tables::qs_sweep_cut(n_sweeps, first_sweep_index, thermalization,
-                                                                   measure_rate, k, chunk, b.T)) {
+    // scaling on: a launch also ends at every measured sweep, and the measurement kernel runs behind it
+    const std::vector<mc_tables::SweepLaunch> launches =
+        sc.n_k > 0 ? mc_tables::qs_scaling_cut(n_sweeps, first_sweep_index, thermalization, measure_rate, k, chunk, b.T)
+                   : mc_tables::qs_sweep_cut(n_sweeps, first_sweep_index, thermalization, measure_rate, k, chunk, b.T);
+    for (const mc_tables::SweepLaunch &l : launches) {
         const long long last = l.first + l.n_sweeps - 1;
         const BinArgs ba = qs_bin_arg(h, l.T_at_start);
 #define QS_SWEEP(...)                                                                                                  \
@@ -835,6 +910,8 @@ int dqmc_qs_sweep(dqmc_qs_handle *h, int32_t n_sweeps, int64_t first_sweep_index
             const int64_t T = l.T_at_start + mc_tables::measurements_in(l.first, last, thermalization, measure_rate) - 1;
             if (int rc = qs_launch_exchange(h, l.defer_last ? 1 : 0, l.defer_last ? T : 0)) return rc;
         }
+        if (sc.n_k > 0 && last > thermalization && last % measure_rate == 0)
+            if (int rc = qs_launch_scaling(h)) return rc;
     }
     if (b.on) b.T += n_meas;
     MCHK(hipStreamSynchronize(h->stream));
@@ -901,6 +978,7 @@ int dqmc_qs_reset_accumulators(dqmc_qs_handle *h)
     for (double *p : {d.sE, d.sE2, d.sM, d.sM2, d.sM4}) MCHK(hipMemsetAsync(p, 0, W * 8, h->stream));
     for (long long *p : {d.n_meas, d.n_series}) MCHK(hipMemsetAsync(p, 0, W * 8, h->stream));
     if (int rc = h->bin.clear(h)) return rc;
+    if (int rc = qs_scaling_clear(h)) return rc;
     MCHK(hipStreamSynchronize(h->stream));
     return DQMC_OK;
 }
@@ -994,13 +1072,17 @@ int dqmc_qs_binner_enable(dqmc_qs_handle *h, int64_t capacity)
     if (capacity > ((int64_t)1 << 40)) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_qs_binner_enable: capacity above 2^40");
     MCHK(hipSetDevice(h->device));
     MCHK(hipStreamSynchronize(h->stream));
+    qs_bin_free(h);
     dqmc_qs_handle::Binner &b = h->bin;
-    b.on = false;
-    b.cap = 0;
     if (int rc = b.alloc(h, 6, 3, 6, mc_tables::bin_levels(capacity))) return rc;
     MCHK(hipStreamSynchronize(h->stream));
     b.on = true;
     b.cap = capacity;
+    if (int rc = qs_scaling_bin_alloc(h)) {  // the scaling section, when the feature is on
+        qs_bin_free(h);
+        return rc;
+    }
+    MCHK(hipStreamSynchronize(h->stream));
     return DQMC_OK;
 }
 
@@ -1035,6 +1117,83 @@ int dqmc_qs_binner_finish(dqmc_qs_handle *h, int32_t walker, int32_t level, dqmc
     if (!out) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_qs_binner_finish: null out");
     return h->bin.finish(h, "dqmc_qs_binner_finish", walker, level, false, out->mean, out->varN, out->varN0, out->tau,
                          out->covN, &out->count, &out->level);
+}
+
+#define QS_SCALING_BIN_OK(h, fn)                                                                      \
+    QS_BIN_OK(h, fn);                                                                                 \
+    if (!(h)->sc.bin.xs)                                                                              \
+    return mc_fail((h), DQMC_ERR_STATE, std::string(fn) + ": the scaling measurement is off (dqmc_qs_set_scaling first)")
+
+int dqmc_qs_set_scaling(dqmc_qs_handle *h, int32_t n_k, const int32_t *cos_q30, const int32_t *sin_q30)
+{
+    if (n_k < 0 || n_k > SC_MAX_K) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_qs_set_scaling: n_k must be in 0..8 (0 = off)");
+    if (n_k > 0 && (!cos_q30 || !sin_q30)) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_qs_set_scaling: null phase table");
+    if (!h) return mc_fail(nullptr, DQMC_ERR_INVALID, "dqmc_qs_set_scaling: null handle");
+    for (long i = 0; i < (long)n_k * h->N; ++i)
+        if (std::abs((long)cos_q30[i]) > (1L << 30) || std::abs((long)sin_q30[i]) > (1L << 30))
+            return mc_fail(h, DQMC_ERR_INVALID, "dqmc_qs_set_scaling: table entry above 2^30 in magnitude");
+    MCHK(hipSetDevice(h->device));
+    MCHK(hipStreamSynchronize(h->stream));
+    dqmc_qs_handle::Scaling &f = h->sc;
+    f.bin.free(h);
+    mc_release(h, f.cq);
+    mc_release(h, f.sq);
+    f.n_k = 0;
+    if (n_k > 0) {
+        const size_t W = h->W, pitch = (size_t)4 * h->Nw, n = (size_t)n_k * pitch;
+        int rc = 0;
+        if (!f.sS && ((rc = mc_alloc(h, &f.sS, (size_t)SC_MAX_K * W)) || (rc = mc_alloc(h, &f.n_meas, W)))) return rc;
+        if ((rc = mc_alloc(h, &f.cq, n)) || (rc = mc_alloc(h, &f.sq, n))) return rc;  // (mc_alloc zeroes the padding)
+        MCHK(hipMemcpy2DAsync(f.cq, pitch * 4, cos_q30, (size_t)h->N * 4, (size_t)h->N * 4, n_k, hipMemcpyHostToDevice,
+                              h->stream));
+        MCHK(hipMemcpy2DAsync(f.sq, pitch * 4, sin_q30, (size_t)h->N * 4, (size_t)h->N * 4, n_k, hipMemcpyHostToDevice,
+                              h->stream));
+        MCHK(hipStreamSynchronize(h->stream));  // (the tables are the caller's: copied before this returns)
+        f.n_k = n_k;
+    }
+    if (int rc = qs_scaling_clear(h)) return rc;
+    MCHK(hipStreamSynchronize(h->stream));
+    if (h->bin.on) return dqmc_qs_binner_enable(h, h->bin.cap);  // every section empty, the capacity kept
+    return DQMC_OK;
+}
+
+int dqmc_qs_get_scaling(dqmc_qs_handle *h, int32_t walker, dqmc_qs_scaling *out)
+{
+    if (int rc = mc_walker(h, walker, "dqmc_qs_get_scaling")) return rc;
+    if (!out) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_qs_get_scaling: null out");
+    const dqmc_qs_handle::Scaling &f = h->sc;
+    *out = dqmc_qs_scaling{};
+    if (f.n_k < 1) return DQMC_OK;
+    MCHK(hipSetDevice(h->device));
+    long long n = 0;
+    if (int rc = mc_get(h, f.n_meas, 0, walker, &n)) return rc;
+    for (int k = 0; k < f.n_k; ++k)
+        if (int rc = mc_get(h, f.sS, k, walker, &out->sum_S[k])) return rc;
+    out->n_meas = n;
+    out->n_k = f.n_k;
+    return DQMC_OK;
+}
+
+int dqmc_qs_scaling_binner_get_level(dqmc_qs_handle *h, int32_t walker, int32_t level, double *x_sum, double *x2_sum,
+                                     double *xy_sum, int64_t *count)
+{
+    QS_SCALING_BIN_OK(h, "dqmc_qs_scaling_binner_get_level");
+    if (int rc = mc_walker(h, walker, "dqmc_qs_scaling_binner_get_level")) return rc;
+    return h->sc.bin.level_sums(h, "dqmc_qs_scaling_binner_get_level", walker, level, x_sum, x2_sum, xy_sum, count);
+}
+
+int dqmc_qs_scaling_binner_finish(dqmc_qs_handle *h, int32_t walker, int32_t level, dqmc_qs_scaling_binned *out)
+{
+    QS_SCALING_BIN_OK(h, "dqmc_qs_scaling_binner_finish");
+    if (int rc = mc_walker(h, walker, "dqmc_qs_scaling_binner_finish")) return rc;
+    if (!out) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_qs_scaling_binner_finish: null out");
+    dqmc_qs_scaling_binned r{};  // (entries past the section's elements stay 0)
+    if (int rc = h->sc.bin.finish(h, "dqmc_qs_scaling_binner_finish", walker, level, true, r.mean, r.varN, r.varN0, r.tau,
+                                  r.covN, &r.count, &r.level))
+        return rc;
+    r.n_k = h->sc.n_k;
+    *out = r;
+    return DQMC_OK;
 }
 
 int dqmc_qs_set_cluster_rate(dqmc_qs_handle *h, int32_t rate)

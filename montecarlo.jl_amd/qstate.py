@@ -11,8 +11,9 @@ import math
 
 import numpy as np
 
-from ._lib import DQMCError, ERR_INVALID, QsBinned, QsClusterStats, QsExchangeStats, QsParams, QsStats, lib
-from .mc import _MCBase, _choose_lattice, _delta_var, _llround
+from ._lib import (DQMCError, ERR_INVALID, ERR_STATE, QsBinned, QsClusterStats, QsExchangeStats, QsParams, QsScaling,
+                   QsScalingBinned, QsStats, lib)
+from .mc import _MCBase, _choose_lattice, _delta_var, _llround, _xi, q30_tables, reciprocal_vectors
 
 Q_MAX = 64
 Q30 = 2.0 ** 30
@@ -117,8 +118,8 @@ class ClockModel(QStateModel):
 
 _ISING_ONLY = "MC with a q-state model: %s is implemented for the IsingModel only (the q-state engine has local " \
               "checkerboard sweeps and keywords of its own: cluster_rate=k for its reflection cluster moves, " \
-              "tempering=(R, k) for replica exchange and binner=True | capacity for the device binner; FSS, " \
-              "checkpointing and the sequential sweep are out of scope)"
+              "tempering=(R, k) for replica exchange, binner=True | capacity for the device binner and " \
+              "scaling=True | [k vectors] for S(k) and xi; checkpointing and the sequential sweep are out of scope)"
 
 
 class QStateMC(_MCBase):
@@ -142,6 +143,12 @@ class QStateMC(_MCBase):
     "at beta_w".  `binner=True | capacity` gives every walker a logarithmic binner over [E, E2, |M|, M2, M2, M4], pushed
     on the device where the measurement is taken (enable_binning); binned() answers mean, std_error and tau.
 
+    `scaling=True` (or a list of at most 8 wave vectors; True: reciprocal_vectors(lattice)) also measures the structure
+    factor S(k) of the two-component order parameter wherever E and M are measured (the header's "Scaling", set_scaling):
+    `scaling()` gives S and the second-moment correlation length xi_k = sqrt(S(0)/S(k) - 1) / (2 sin(|k|/2)) with
+    S(0) = <M2>/N, whose xi/L crossings locate the transitions, and with a binner `binned_scaling()` gives their error
+    bars.  The chains, the sums and binned() are those of a handle without it.
+
     The Ising-only options (cluster_moves, global_moves, n_replicas, exchange_rate, fss, binning, update="sequential")
     raise NotImplementedError."""
     _abi = "dqmc_qs_"
@@ -149,7 +156,7 @@ class QStateMC(_MCBase):
     def __init__(self, model, beta=None, T=None, n_walkers=1, seed=123, first_walker=0, thermalization=0, sweeps=1000,
                  measure_rate=1, print_rate=1000, global_moves=False, global_rate=5, device_id=0, series_capacity=0,
                  cluster_moves=False, binning=False, binning_capacity=None, n_replicas=0, exchange_rate=0,
-                 fss=False, update=None, colouring=None, cluster_rate=0, tempering=None, binner=False):
+                 fss=False, update=None, colouring=None, cluster_rate=0, tempering=None, binner=False, scaling=False):
         for name, on in (("global_moves", global_moves), ("cluster_moves", cluster_moves), ("binning", binning),
                          ("n_replicas", n_replicas), ("exchange_rate", exchange_rate),
                          ("fss", fss is not False and fss is not None),
@@ -159,6 +166,7 @@ class QStateMC(_MCBase):
         beta = self._resolve_beta(beta, T)
         R, k = self._tempering(tempering, n_walkers)
         capacity = self._binner_capacity(binner)
+        tables = self._scaling_tables(model.l, scaling)  # (refused before the device is touched)
         if R >= 2 and beta.ndim == 1 and len(beta) == R:
             beta = np.tile(beta, n_walkers // R)  # one ladder's temperatures, the same in every ladder
         self._init_common(model, beta, n_walkers, seed, first_walker, thermalization, sweeps, measure_rate, print_rate,
@@ -182,6 +190,9 @@ class QStateMC(_MCBase):
         self.n_replicas, self.exchange_rate = 0, 0
         if R or k:
             self.set_exchange(R, k)
+        self.k_vectors = None
+        if tables is not None:
+            self._put_scaling(tables)
         if capacity is not False:
             self.enable_binning(capacity)
 
@@ -369,6 +380,132 @@ class QStateMC(_MCBase):
                     o["std_error_walkers"] = (math.sqrt(float(((means - mean) ** 2).sum()) / (W * (W - 1.0)))
                                               if W >= 2 else float("nan"))
                 out[group][k] = o
+        if pooled:
+            out["n_walkers"] = len(ws)
+        return out
+
+    # ---- finite-size scaling
+    def set_scaling(self, k_vectors=True):
+        """dqmc_qs_set_scaling: from now on every measurement also takes S(k) at the given wave vectors (True:
+        reciprocal_vectors(lattice), the smallest ones, one per lattice dimension; else 1 to 8 vectors of the lattice's
+        dimension; None or False: off).  Resets the scaling sums and, if a binner is on, restarts it with every section
+        empty and its capacity kept."""
+        self._put_scaling(self._scaling_tables(self.model.l, k_vectors))
+
+    @staticmethod
+    def _scaling_tables(l, k_vectors):
+        """(cos_q30, sin_q30, k) of a scaling argument, None for None or False; ValueError unless 1 to 8 vectors"""
+        if k_vectors is None or k_vectors is False:
+            return None
+        ks = reciprocal_vectors(l) if k_vectors is True else k_vectors
+        if not 1 <= len(ks) <= 8:
+            raise ValueError("scaling: 1 to 8 wave vectors, got %d" % len(ks))
+        return q30_tables(l, ks)
+
+    def _put_scaling(self, tables):
+        if tables is None:
+            self._c(lib().dqmc_qs_set_scaling(self._h, 0, None, None))
+            self.k_vectors = None
+            return
+        cq, sq, k = tables
+        i32 = C.POINTER(C.c_int32)
+        self._c(lib().dqmc_qs_set_scaling(self._h, len(k), cq.ctypes.data_as(i32), sq.ctypes.data_as(i32)))
+        self.k_vectors = k
+
+    def scaling_sums(self, walker=0):
+        """dqmc_qs_scaling of one walker: n_meas, n_k (0: off), sum_S[8]"""
+        out = QsScaling()
+        self._c(lib().dqmc_qs_get_scaling(self._h, walker, C.byref(out)))
+        return out
+
+    def _knorm(self, k):
+        return float(np.linalg.norm(self.k_vectors[k]))
+
+    def scaling(self, walker=0):
+        """the plain means of one walker: S (one per wave vector), M2, k and the second-moment correlation length
+        xi_k = sqrt(S(0)/S_k - 1) / (2 sin(|k|/2)) with S(0) = <M2>/N (NaN where S(0) < S_k), xi_over_L where the lattice
+        has an L.  <M2> is the one of measurements(): the two counts must agree (after switching the measurement on
+        mid-run, reset_accumulators() first)."""
+        f, st = self.scaling_sums(walker), self.stats(walker)
+        if f.n_k < 1:
+            raise DQMCError(ERR_STATE, "scaling: the measurement is off (MC(scaling=True) or set_scaling)")
+        if f.n_meas == 0:
+            raise DQMCError(ERR_INVALID, "scaling: no measurement has been taken")
+        if f.n_meas != st.n_meas:
+            raise DQMCError(ERR_STATE, "scaling: %d scaling measurements but %d of M2 (the measurement was switched on "
+                                       "mid-run: reset_accumulators() first)" % (f.n_meas, st.n_meas))
+        n = float(f.n_meas)
+        M2 = st.sum_M2 / n
+        S = np.array([f.sum_S[k] / n for k in range(f.n_k)])
+        xi = np.array([_xi(M2, S[k], self.N, self._knorm(k))[0] for k in range(f.n_k)])
+        out = {"S": S, "xi": xi, "M2": M2, "k": self.k_vectors.copy(), "n_meas": int(f.n_meas)}
+        L = getattr(self.model.l, "L", None)
+        if L is not None:
+            out["xi_over_L"] = xi / float(L)
+        return out
+
+    def scaling_binner_level(self, walker, level):
+        """(x_sum[1 + n_k], x2_sum[1 + n_k], xy_sum[n_k], count) of one level of one walker of the binner's scaling
+        section: elements [M2, S_0 ..], pairs (M2, S_0) .."""
+        nk = 0 if self.k_vectors is None else len(self.k_vectors)
+        xs, x2, xy, n = np.zeros(1 + nk), np.zeros(1 + nk), np.zeros(max(nk, 1)), C.c_int64()
+        dp = C.POINTER(C.c_double)
+        self._c(lib().dqmc_qs_scaling_binner_get_level(self._h, walker, level, xs.ctypes.data_as(dp),
+                                                       x2.ctypes.data_as(dp), xy.ctypes.data_as(dp), C.byref(n)))
+        return xs, x2, xy[:nk], n.value
+
+    def scaling_binner_finish(self, walker=0, level=None):
+        """dqmc_qs_scaling_binned of one walker at `level` (None: the reliable level)"""
+        out = QsScalingBinned()
+        self._c(lib().dqmc_qs_scaling_binner_finish(self._h, walker, -1 if level is None else int(level), C.byref(out)))
+        return out
+
+    def _binned_scaling_walker(self, walker, level):
+        """{name: (mean, variance of the mean at `level`, the same at level 0 or None)} of one walker; S, xi as lists"""
+        b = self.scaling_binner_finish(walker, level)
+        M2 = b.mean[0]
+        obs = {"M2": (M2, b.varN[0], b.varN0[0]), "S": [], "xi": []}
+        for k in range(b.n_k):
+            S = b.mean[1 + k]
+            xi, g = _xi(M2, S, self.N, self._knorm(k))
+            obs["S"].append((S, b.varN[1 + k], b.varN0[1 + k]))
+            obs["xi"].append((xi, _delta_var(g, b.varN[0], b.varN[1 + k], b.covN[k]), None))
+        return obs, int(b.count), int(b.level)
+
+    def binned_scaling(self, walker=0, level=None, walkers=None):
+        """mean, std_error and tau of M2 and each S_k from the binner's scaling section at `level` (None: the reliable
+        one), and mean and std_error of each xi_k (xi_over_L where the lattice has an L) by the delta method on the binned
+        covariance of (M2, S_k): {"M2": {...}, "S", "xi": [{...} per k], "count", "level"}.  `walkers=[...]` pools chains
+        of equal beta under the rules of binned(): xi is formed per walker first, std_error = sqrt(sum_w var_w) / W,
+        plus std_error_walkers."""
+        pooled = walkers is not None
+        ws = [int(w) for w in walkers] if pooled else [walker]
+        if not ws:
+            raise ValueError("binned_scaling: no walker given")
+        if any(self.betas[w] != self.betas[ws[0]] for w in ws):
+            raise ValueError("binned_scaling: the pooled walkers must share one beta")
+        per = [self._binned_scaling_walker(w, level) for w in ws]
+        W = float(len(ws))
+
+        def pool(entries):
+            means = np.array([e[0] for e in entries])
+            vl = float(np.sum([e[1] for e in entries]))
+            mean = float(means.sum() / W)
+            o = {"mean": mean, "std_error": (math.sqrt(max(vl, 0.0)) if vl == vl else vl) / W}
+            if entries[0][2] is not None:
+                with np.errstate(invalid="ignore", divide="ignore"):
+                    o["tau"] = float(0.5 * (np.float64(vl) / np.sum([e[2] for e in entries]) - 1.0))
+            if pooled:
+                o["std_error_walkers"] = (math.sqrt(float(((means - mean) ** 2).sum()) / (W * (W - 1.0)))
+                                          if W >= 2 else float("nan"))
+            return o
+
+        out = {"count": per[0][1], "level": per[0][2], "M2": pool([p[0]["M2"] for p in per])}
+        for name in ("S", "xi"):
+            out[name] = [pool([p[0][name][k] for p in per]) for k in range(len(per[0][0][name]))]
+        L = getattr(self.model.l, "L", None)
+        if L is not None:
+            out["xi_over_L"] = [{key: v / float(L) for key, v in o.items()} for o in out["xi"]]
         if pooled:
             out["n_walkers"] = len(ws)
         return out
