@@ -1430,6 +1430,44 @@ int dqmc_mc_fss_binner_finish(dqmc_mc_handle *h, int32_t walker, int32_t level, 
  * sums, the series, the draws and the first binner section are those of a handle without the feature, and with
  * n_k = 0 (the default) so is every launch.  Results do not depend on how a run is split into dqmc_qs_sweep calls.
  *
+ * Stiffness (dqmc_qs_set_stiffness).  The helicity modulus (spin stiffness) of a model whose pair energy is a function
+ * e(theta_i - theta_j) of an angle theta = 2 pi s / q.  Under a uniform twist phi along the unit vector e_mu the bond
+ * (i, j) gets the energy -J e(theta_i - theta_j - phi x_b), x_b = e_mu . (r_j - r_i) at minimum image, and
+ *   Upsilon_mu = (1/N) d^2F/dphi^2 at phi = 0 = (<T_mu> - beta <J_mu^2>) / N,
+ *   T_mu = sum_b x_b^2 d2[(s_i - s_j) mod q],  J_mu = sum_b x_b d1[(s_i - s_j) mod q],
+ * d1 the first and d2 the second derivative of the pair energy with respect to the angle (clock model:
+ * d1[d] = J sin(2 pi d / q), d2[d] = J cos(2 pi d / q)).  Z(phi) is a smooth function of phi even with discrete spins, so
+ * the formula is an identity of the q^N-state sum (tests/qstate_stiffness_ref.py restates this part and checks it by
+ * enumeration).
+ *   twist tables  int64 d1_q30[q] and d2_q30[q] = llround(. 2^30), magnitude <= 2^32; d1 exactly antisymmetric,
+ *                 d1[(q - d) % q] == -d1[d] (so d1[0] = 0, and d1[q/2] = 0 for even q), d2 exactly symmetric: both computed
+ *                 for d <= q / 2 and mirrored, as e_q30.
+ *   slot classes  a directed slot is a pair (i, k), k < z, with j = neighs[k, i].  The host passes int8 slot_class, z x
+ *                 n_sites in the layout of neighs: -1 (the slot is not counted) or a class c < n_c <= 8.  A class is a bond
+ *                 displacement vector; the host counts every undirected neighbour pair once, in the orientation whose
+ *                 displacement is the class vector.  The engine validates ranges only: which slots are counted is the
+ *                 host's definition.
+ *   exact part    per measurement, walker and class, int64: I_c = sum_{(i, k) of class c} d1_q30[(s_i - s_j) mod q] and
+ *                 K_c likewise with d2_q30 (|.| <= 2^17 2^32 = 2^49: exact in any order).  The padding bytes of a
+ *                 walker's last configuration word are no sites.
+ *   fp64 part     for each direction mu < n_dir <= 4 with the host's projections double x[n_dir][n_c], in this order and
+ *                 with no product fused into a sum: G = +0.0, for c = 0 .. n_c - 1: G = fl(G + fl(x[mu][c] (double)I_c));
+ *                 F = +0.0, for c = 0 .. n_c - 1: F = fl(F + fl(fl(x[mu][c] x[mu][c]) (double)K_c)); J_mu = fl(G 2^-30),
+ *                 T_mu = fl(F 2^-30), J2_mu = fl(J_mu J_mu).  numpy reproduces all three bit for bit.
+ *   when          exactly where E and M are measured, on that configuration: after the cluster move and the exchange
+ *                 round ("at beta_w" under replica exchange).  If scaling is on as well, the scaling kernel runs first.
+ *   sums          per walker sum_T[4], sum_J[4], sum_J2[4], one rounding each per measurement in measurement order, and
+ *                 an n_meas of its own (the feature may be switched on mid-run).  dqmc_qs_reset_accumulators clears them.
+ *                 I_c and K_c of the last sample stay readable (dqmc_qs_get_stiffness_sample).
+ *   binner        with the binner enabled, a third section over the 2 n_dir elements [T_0, J2_0, T_1, J2_1, ..] under the
+ *                 level / compressor scheme of the first: pair p is the elements (2 p, 2 p + 1) with one cross sum
+ *                 xy_sum[p], device layout [level][element][walker], a push count of its own.  dqmc_qs_set_stiffness with
+ *                 a binner enabled restarts the binner with every section empty and its capacity kept; the capacity check
+ *                 of dqmc_qs_sweep covers every section.  No element has a square root: all compare bit for bit.
+ * The measurement is a kernel of its own (csrc/qs_stiffness.inl) behind every measured sweep, under the launch cut of
+ * "Scaling" (one cut, two trailing kernels with both features on).  The chains, the sums, the series, the draws and the
+ * other binner sections are those of a handle without the feature, and with n_dir = 0 (the default) so is every launch.
+ *
  * Limits: n_sites <= 16384, 1 <= z <= 8, 2 <= q <= 64, n_colours <= 16.  Errors come from dqmc_qs_last_error. */
 typedef struct dqmc_qs_handle dqmc_qs_handle;
 
@@ -1575,6 +1613,46 @@ typedef struct {
 } dqmc_qs_scaling_binned;
 /* level < 0: the reliable level (the last one with count >= 32, else 0) */
 int dqmc_qs_scaling_binner_finish(dqmc_qs_handle *h, int32_t walker, int32_t level, dqmc_qs_scaling_binned *out);
+
+/* "Stiffness" above.  n_dir in 1..4: the measurement on with these tables (copied); n_dir = 0: off (the default; nothing
+ * else is looked at).  Resets the stiffness sums; if the binner is enabled it starts anew with every section empty and
+ * its capacity kept.  Everything is checked before the device is touched: DQMC_ERR_INVALID for n_dir outside 0..4,
+ * n_classes outside 1..8, a NULL table, a class outside -1..n_classes-1, a d1_q30 that is not antisymmetric or a d2_q30
+ * that is not symmetric, an entry of either above 2^32 in magnitude, or an x that is not finite; the handle then stays
+ * as it was. */
+int dqmc_qs_set_stiffness(dqmc_qs_handle *h, int32_t n_dir, int32_t n_classes,
+                          const int8_t *slot_class /* z x n_sites, column-major as neighs */,
+                          const int64_t *d1_q30 /* [q] */, const int64_t *d2_q30 /* [q] */,
+                          const double *x /* [n_dir][n_classes] */);
+typedef struct {
+    int64_t n_meas;     /* stiffness measurements summed since dqmc_qs_set_stiffness / dqmc_qs_reset_accumulators */
+    int32_t n_dir;      /* 0: the measurement is off (then everything else is 0) */
+    double sum_T[4];    /* entries at and above n_dir are 0 */
+    double sum_J[4];
+    double sum_J2[4];
+} dqmc_qs_stiffness;
+int dqmc_qs_get_stiffness(dqmc_qs_handle *h, int32_t walker, dqmc_qs_stiffness *out);
+/* I_c and K_c of the walker's last measurement (entries at and above n_classes, and everything with the measurement
+ * off or before the first measurement, are 0) */
+int dqmc_qs_get_stiffness_sample(dqmc_qs_handle *h, int32_t walker, int64_t I[8], int64_t K[8]);
+/* the sums of one level of one walker of the stiffness section: x_sum and x2_sum hold 2 n_dir elements
+ * [T_0, J2_0, T_1, J2_1 ..], xy_sum n_dir pairs [(T_0, J2_0) ..]; any output may be NULL.  DQMC_ERR_STATE without a
+ * binner or with the measurement off. */
+int dqmc_qs_stiffness_binner_get_level(dqmc_qs_handle *h, int32_t walker, int32_t level, double *x_sum, double *x2_sum,
+                                       double *xy_sum, int64_t *count);
+/* as dqmc_qs_binned, for the stiffness section: entries at and above 2 n_dir (covN: n_dir) are 0 */
+typedef struct {
+    double mean[8];    /* [T_0, J2_0, T_1, J2_1 ..] */
+    double varN[8];    /* at `level` */
+    double varN0[8];   /* at level 0 */
+    double tau[8];
+    double covN[4];    /* at `level`, pairs (T_mu, J2_mu) */
+    int64_t count;
+    int32_t level;
+    int32_t n_dir;
+} dqmc_qs_stiffness_binned;
+/* level < 0: the reliable level (the last one with count >= 32, else 0) */
+int dqmc_qs_stiffness_binner_finish(dqmc_qs_handle *h, int32_t walker, int32_t level, dqmc_qs_stiffness_binned *out);
 
 /* ---- the SAC flavor: stochastic analytic continuation -----------------------------------------------------------
  * A(omega) from imaginary-time data by sampling (Sandvik, PRB 57, 10287; Beach, cond-mat/0403055; Shao and Sandvik,

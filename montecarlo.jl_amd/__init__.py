@@ -10,7 +10,7 @@ from .configurations import (CompressedConf, ConfigRecorder, Discarder, compress
 from . import lattices  # noqa: F401
 from .lattices import (BilayerSquareLattice, Chain, EachLocalQuadByDistance, EachLocalQuadBySyncedDistance, EachSitePairByDistance,  # noqa: F401
                        CubicLattice, HoneycombLattice, RectangularLattice, SquareLattice, TriangularLattice, build_checkerboard,
-                       momentum_grid,
+                       bond_classes, momentum_grid,
                        strip_subsystem, sublattice_sign)
 from .models import (HubbardModel, HubbardModelAttractive, HubbardModelRepulsive,  # noqa: F401
                      rand_conf)
@@ -24,7 +24,7 @@ from .dqmc import (DQMC, DQMCParameters, CurrentTauSums, matsubara_trapezoid, ca
 
 from .mc import MC, IsingModel, IsingTc, greedy_colouring, reciprocal_vectors  # noqa: F401
 from . import qstate  # noqa: F401
-from .qstate import ClockModel, PottsModel, QStateMC, QStateModel, qstate_tables  # noqa: F401
+from .qstate import ClockModel, PottsModel, QStateMC, QStateModel, qstate_tables, twist_tables  # noqa: F401
 from . import sac  # noqa: F401
 from .sac import SAC, boson_symmetric_kernel, fermion_kernel  # noqa: F401
 

@@ -144,6 +144,16 @@ class QsScalingBinned(C.Structure):
                 ("covN", C.c_double * 8), ("count", C.c_int64), ("level", C.c_int32), ("n_k", C.c_int32)]
 
 
+class QsStiffness(C.Structure):
+    _fields_ = [("n_meas", C.c_int64), ("n_dir", C.c_int32), ("sum_T", C.c_double * 4), ("sum_J", C.c_double * 4),
+                ("sum_J2", C.c_double * 4)]
+
+
+class QsStiffnessBinned(C.Structure):
+    _fields_ = [("mean", C.c_double * 8), ("varN", C.c_double * 8), ("varN0", C.c_double * 8), ("tau", C.c_double * 8),
+                ("covN", C.c_double * 4), ("count", C.c_int64), ("level", C.c_int32), ("n_dir", C.c_int32)]
+
+
 class SacParams(C.Structure):
     _fields_ = [("n_problems", C.c_int32), ("n_tau", C.c_int32), ("n_deltas", C.c_int32), ("n_omega", C.c_int32),
                 ("n_replicas", C.c_int32), ("device_id", C.c_int32), ("window", C.c_int32),
@@ -367,6 +377,11 @@ SIGNATURES = {
     "dqmc_qs_get_scaling": (C.c_int, [_H, C.c_int32, C.POINTER(QsScaling)]),
     "dqmc_qs_scaling_binner_get_level": (C.c_int, [_H, C.c_int32, C.c_int32, _dp, _dp, _dp, _i64p]),
     "dqmc_qs_scaling_binner_finish": (C.c_int, [_H, C.c_int32, C.c_int32, C.POINTER(QsScalingBinned)]),
+    "dqmc_qs_set_stiffness": (C.c_int, [_H, C.c_int32, C.c_int32, C.POINTER(C.c_int8), _i64p, _i64p, _dp]),
+    "dqmc_qs_get_stiffness": (C.c_int, [_H, C.c_int32, C.POINTER(QsStiffness)]),
+    "dqmc_qs_get_stiffness_sample": (C.c_int, [_H, C.c_int32, _i64p, _i64p]),
+    "dqmc_qs_stiffness_binner_get_level": (C.c_int, [_H, C.c_int32, C.c_int32, _dp, _dp, _dp, _i64p]),
+    "dqmc_qs_stiffness_binner_finish": (C.c_int, [_H, C.c_int32, C.c_int32, C.POINTER(QsStiffnessBinned)]),
     "dqmc_sac_create": (C.c_int, [C.POINTER(SacParams), C.POINTER(_H)]),
     "dqmc_sac_destroy": (C.c_int, [_H]),
     "dqmc_sac_last_error": (C.c_char_p, [_H]),

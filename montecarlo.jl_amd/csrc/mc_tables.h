@@ -254,4 +254,36 @@ inline std::vector<SweepLaunch> qs_scaling_cut(int n, int64_t first, int64_t the
     return qs_cut_launches(n, first, thermalization, rate, k, chunk, T0, true);
 }
 
+// The arguments of dqmc_qs_set_stiffness with n_dir > 0 (include/dqmc_hip.h, "Stiffness" of the q-state section), checked
+// on the host before the device is touched: the counts, the range of every slot class (which slots are counted is the
+// caller's definition), d1 exactly antisymmetric and d2 exactly symmetric with magnitudes <= 2^32, x finite.
+inline bool qs_stiffness_check(const std::string &fn, int N, int z, int q, int n_dir, int n_classes, const int8_t *slot_class,
+                               const int64_t *d1, const int64_t *d2, const double *x, std::string *err)
+{
+    if (n_dir < 1 || n_dir > 4) return *err = fn + ": n_dir must be in 0..4 (0 = off)", false;
+    if (n_classes < 1 || n_classes > 8) return *err = fn + ": n_classes must be in 1..8", false;
+    if (!slot_class || !d1 || !d2 || !x) return *err = fn + ": slot_class, d1_q30, d2_q30 or x missing", false;
+    for (long i = 0; i < (long)z * N; ++i)
+        if (slot_class[i] < -1 || slot_class[i] >= n_classes)
+            return *err = fn + ": the class of slot " + std::to_string(i % z) + " of site " + std::to_string(i / z) +
+                          " (0-based) is outside -1.." + std::to_string(n_classes - 1),
+                   false;
+    const int64_t top = (int64_t)1 << 32;
+    for (int d = 0; d < q; ++d) {
+        if (d1[d] > top || d1[d] < -top || d2[d] > top || d2[d] < -top)
+            return *err = fn + ": d1_q30 / d2_q30 entry " + std::to_string(d) + " exceeds 2^32 in magnitude", false;
+        if (d1[d] != -d1[(q - d) % q])
+            return *err = fn + ": d1_q30[" + std::to_string(d) + "] != -d1_q30[" + std::to_string((q - d) % q) +
+                          "]: the table is not antisymmetric",
+                   false;
+        if (d2[d] != d2[(q - d) % q])
+            return *err = fn + ": d2_q30[" + std::to_string(d) + "] != d2_q30[" + std::to_string((q - d) % q) +
+                          "]: the table is not symmetric",
+                   false;
+    }
+    for (int i = 0; i < n_dir * n_classes; ++i)
+        if (!std::isfinite(x[i])) return *err = fn + ": x[" + std::to_string(i) + "] is not finite", false;
+    return true;
+}
+
 }  // namespace mc_tables

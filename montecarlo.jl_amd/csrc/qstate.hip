@@ -25,7 +25,8 @@
 // without moves whenever the rate is 0.
 //
 // The scaling measurement (the header's "Scaling": the structure factor of the order parameter at up to 8 wave vectors) is
-// a kernel of its own behind every measured sweep, qs_scaling.inl; the kernels above are what they are without it.
+// a kernel of its own behind every measured sweep, qs_scaling.inl; the kernels above are what they are without it.  So is
+// the stiffness measurement (the header's "Stiffness": the helicity modulus from per-class bond sums), qs_stiffness.inl.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -360,6 +361,9 @@ __global__ __launch_bounds__(THREADS) void qs_exchange_kernel(DevState s, Exchan
 // the scaling measurement: ScalingArgs, qs_scaling_bin_push, qs_scaling_kernel
 #include "qs_scaling.inl"
 
+// the stiffness measurement: StiffnessArgs, qs_stiffness_bin_push, qs_stiffness_kernel
+#include "qs_stiffness.inl"
+
 // dqmc_qs_cluster_move: one move of one walker (walker >= 0) or of every walker, with the sweep kernel's LDS layout
 __global__ __launch_bounds__(THREADS) void qs_cluster_move_kernel(DevState s, const long long *__restrict__ e_q30,
                                                                   const int2 *__restrict__ cs_q30, ClusterArgs ca,
@@ -511,6 +515,18 @@ struct dqmc_qs_handle : mc_handle_base {
         // [M2, S_0 ..], pairs (M2, S_k), a compressor value per member of a pair
         mc_bin_section bin;
     } sc;
+    struct Stiffness {                  // dqmc_qs_set_stiffness; n_dir = 0: off
+        int n_dir = 0, n_c = 0;
+        double x[ST_MAX_DIR][ST_MAX_CLASSES] = {};
+        signed char *cls = nullptr;            // [N][8]: the slot classes in the order of nbr_site, -1 behind z
+        long long *d1 = nullptr, *d2 = nullptr;  // [q]
+        double *sT = nullptr, *sJ = nullptr, *sJ2 = nullptr;  // [4][W] (allocated when the feature is first switched on)
+        long long *n_meas = nullptr;           // [W]
+        long long *sI = nullptr, *sK = nullptr;  // [8][W]: the last sample
+        // the stiffness section of the binner (there iff bin.on && n_dir > 0; its levels and capacity are bin's):
+        // elements [T_0, J2_0, T_1, J2_1 ..], pairs (2 p, 2 p + 1)
+        mc_bin_section bin;
+    } st;
 };
 
 static const int64_t QS_BIN_DEFAULT_CAPACITY = 100000;  // as dqmc_mc_binner_enable
@@ -601,8 +617,9 @@ static int qs_launch_observables(dqmc_qs_handle *h, int walker)
     return 0;
 }
 
-static void qs_bin_free(dqmc_qs_handle *h)  // both sections; the binner is off afterwards
+static void qs_bin_free(dqmc_qs_handle *h)  // every section; the binner is off afterwards
 {
+    h->st.bin.free(h);
     h->sc.bin.free(h);
     h->bin.free(h);
     h->bin.on = false;
@@ -649,6 +666,56 @@ static int qs_launch_scaling(dqmc_qs_handle *h)
     }
     hipLaunchKernelGGL(qs_scaling_kernel, dim3(h->W), dim3(THREADS), scaling_lds_bytes(f.n_k), h->stream, h->d, a,
                        (const int4 *)f.cq, (const int4 *)f.sq, (const int2 *)h->cs_q30);
+    MCHK(hipGetLastError());
+    if (f.bin.xs) f.bin.T += 1;
+    return 0;
+}
+
+// the stiffness section for the binner as it stands (nothing unless both are on)
+static int qs_stiffness_bin_alloc(dqmc_qs_handle *h)
+{
+    dqmc_qs_handle::Stiffness &f = h->st;
+    f.bin.free(h);
+    if (!h->bin.on || f.n_dir < 1) return 0;
+    return f.bin.alloc(h, 2 * f.n_dir, f.n_dir, 2 * f.n_dir, h->bin.L);
+}
+
+static int qs_stiffness_clear(dqmc_qs_handle *h)  // the sums, the last sample and the section's state
+{
+    dqmc_qs_handle::Stiffness &f = h->st;
+    const size_t W = h->W;
+    if (f.sT) {
+        for (double *p : {f.sT, f.sJ, f.sJ2}) MCHK(hipMemsetAsync(p, 0, (size_t)ST_MAX_DIR * W * 8, h->stream));
+        for (long long *p : {f.sI, f.sK}) MCHK(hipMemsetAsync(p, 0, (size_t)ST_MAX_CLASSES * W * 8, h->stream));
+        MCHK(hipMemsetAsync(f.n_meas, 0, W * 8, h->stream));
+    }
+    return f.bin.clear(h);
+}
+
+// the stiffness measurement of the sweep whose last kernel has just been launched, and its push
+static int qs_launch_stiffness(dqmc_qs_handle *h)
+{
+    dqmc_qs_handle::Stiffness &f = h->st;
+    StiffnessArgs a{};
+    a.n_dir = f.n_dir;
+    a.n_c = f.n_c;
+    std::memcpy(a.x, f.x, sizeof(a.x));
+    a.sT = f.sT;
+    a.sJ = f.sJ;
+    a.sJ2 = f.sJ2;
+    a.n_meas = f.n_meas;
+    a.sI = f.sI;
+    a.sK = f.sK;
+    if (f.bin.xs) {
+        if (int rc = f.bin.next_lmax(h, "dqmc_qs_sweep", &a.lmax)) return rc;
+        a.bxs = f.bin.xs;
+        a.bx2 = f.bin.x2;
+        a.bxy = f.bin.xy;
+        a.bc = f.bin.c;
+        a.top = f.bin.L - 1;
+    }
+    hipLaunchKernelGGL(qs_stiffness_kernel, dim3(h->W), dim3(THREADS), stiffness_lds_bytes(h->q, h->Nw), h->stream, h->d, a,
+                       (const int4 *)h->nbr_site, (const int2 *)f.cls, (const long long *)f.d1, (const long long *)f.d2);
     MCHK(hipGetLastError());
     if (f.bin.xs) f.bin.T += 1;
     return 0;
@@ -873,15 +940,19 @@ int dqmc_qs_sweep(dqmc_qs_handle *h, int32_t n_sweeps, int64_t first_sweep_index
     if (sc.bin.xs && sc.bin.T + n_meas > b.cap)
         return mc_fail(h, DQMC_ERR_STATE, "dqmc_qs_sweep: the measurements of this call would pass the capacity of the "
                                           "binner's scaling section");
+    dqmc_qs_handle::Stiffness &sf = h->st;
+    if (sf.bin.xs && sf.bin.T + n_meas > b.cap)
+        return mc_fail(h, DQMC_ERR_STATE, "dqmc_qs_sweep: the measurements of this call would pass the capacity of the "
+                                          "binner's stiffness section");
     MCHK(hipSetDevice(h->device));
     const double per_sweep = ((double)h->N + QS_SWEEP_OVERHEAD) * std::max(1.0, (double)h->W / QS_RESIDENT_WALKERS);
     const int chunk = (int)std::max(1.0, std::min((double)n_sweeps, std::floor(QS_LAUNCH_BUDGET / per_sweep)));
     const bool cluster = h->ca.rate > 0;
     const size_t lds = sweep_lds_bytes(h->q, h->Nw) + (cluster ? cluster_lds_bytes(h->N) : 0);
     const int k = h->xch.R >= 2 ? h->xch.rate : 0;  // an exchange round after every k-th sweep
-    // scaling on: a launch also ends at every measured sweep, and the measurement kernel runs behind it
+    // scaling or stiffness on: a launch also ends at every measured sweep, and the measurement kernels run behind it
     const std::vector<mc_tables::SweepLaunch> launches =
-        sc.n_k > 0 ? mc_tables::qs_scaling_cut(n_sweeps, first_sweep_index, thermalization, measure_rate, k, chunk, b.T)
+        sc.n_k > 0 || sf.n_dir > 0 ? mc_tables::qs_scaling_cut(n_sweeps, first_sweep_index, thermalization, measure_rate, k, chunk, b.T)
                    : mc_tables::qs_sweep_cut(n_sweeps, first_sweep_index, thermalization, measure_rate, k, chunk, b.T);
     for (const mc_tables::SweepLaunch &l : launches) {
         const long long last = l.first + l.n_sweeps - 1;
@@ -912,6 +983,8 @@ int dqmc_qs_sweep(dqmc_qs_handle *h, int32_t n_sweeps, int64_t first_sweep_index
         }
         if (sc.n_k > 0 && last > thermalization && last % measure_rate == 0)
             if (int rc = qs_launch_scaling(h)) return rc;
+        if (sf.n_dir > 0 && last > thermalization && last % measure_rate == 0)
+            if (int rc = qs_launch_stiffness(h)) return rc;
     }
     if (b.on) b.T += n_meas;
     MCHK(hipStreamSynchronize(h->stream));
@@ -979,6 +1052,7 @@ int dqmc_qs_reset_accumulators(dqmc_qs_handle *h)
     for (long long *p : {d.n_meas, d.n_series}) MCHK(hipMemsetAsync(p, 0, W * 8, h->stream));
     if (int rc = h->bin.clear(h)) return rc;
     if (int rc = qs_scaling_clear(h)) return rc;
+    if (int rc = qs_stiffness_clear(h)) return rc;
     MCHK(hipStreamSynchronize(h->stream));
     return DQMC_OK;
 }
@@ -1079,6 +1153,10 @@ int dqmc_qs_binner_enable(dqmc_qs_handle *h, int64_t capacity)
     b.on = true;
     b.cap = capacity;
     if (int rc = qs_scaling_bin_alloc(h)) {  // the scaling section, when the feature is on
+        qs_bin_free(h);
+        return rc;
+    }
+    if (int rc = qs_stiffness_bin_alloc(h)) {  // the stiffness section, when the feature is on
         qs_bin_free(h);
         return rc;
     }
@@ -1192,6 +1270,117 @@ int dqmc_qs_scaling_binner_finish(dqmc_qs_handle *h, int32_t walker, int32_t lev
                                   r.covN, &r.count, &r.level))
         return rc;
     r.n_k = h->sc.n_k;
+    *out = r;
+    return DQMC_OK;
+}
+
+#define QS_STIFFNESS_BIN_OK(h, fn)                                                                    \
+    QS_BIN_OK(h, fn);                                                                                 \
+    if (!(h)->st.bin.xs)                                                                              \
+    return mc_fail((h), DQMC_ERR_STATE, std::string(fn) + ": the stiffness measurement is off (dqmc_qs_set_stiffness first)")
+
+int dqmc_qs_set_stiffness(dqmc_qs_handle *h, int32_t n_dir, int32_t n_classes, const int8_t *slot_class,
+                          const int64_t *d1_q30, const int64_t *d2_q30, const double *x)
+{
+    if (!h) return mc_fail(nullptr, DQMC_ERR_INVALID, "dqmc_qs_set_stiffness: null handle");
+    const int N = h->N, z = h->z, q = h->q;
+    if (n_dir != 0) {  // everything before the device is touched; a refusal leaves the handle as it was
+        std::string msg;
+        if (!mc_tables::qs_stiffness_check("dqmc_qs_set_stiffness", N, z, q, n_dir, n_classes, slot_class, d1_q30, d2_q30, x,
+                                           &msg))
+            return mc_fail(h, DQMC_ERR_INVALID, msg);
+    }
+    MCHK(hipSetDevice(h->device));
+    MCHK(hipStreamSynchronize(h->stream));
+    dqmc_qs_handle::Stiffness &f = h->st;
+    f.bin.free(h);
+    f.n_dir = 0;
+    f.n_c = 0;
+    if (n_dir > 0) {
+        const size_t W = h->W;
+        int rc = 0;
+        if (!f.sT && ((rc = mc_alloc(h, &f.sT, (size_t)ST_MAX_DIR * W)) || (rc = mc_alloc(h, &f.sJ, (size_t)ST_MAX_DIR * W)) ||
+                      (rc = mc_alloc(h, &f.sJ2, (size_t)ST_MAX_DIR * W)) || (rc = mc_alloc(h, &f.n_meas, W)) ||
+                      (rc = mc_alloc(h, &f.sI, (size_t)ST_MAX_CLASSES * W)) ||
+                      (rc = mc_alloc(h, &f.sK, (size_t)ST_MAX_CLASSES * W)) || (rc = mc_alloc(h, &f.cls, (size_t)N * MAX_Z)) ||
+                      (rc = mc_alloc(h, &f.d1, (size_t)q)) || (rc = mc_alloc(h, &f.d2, (size_t)q))))
+            return rc;
+        std::vector<signed char> cls((size_t)N * MAX_Z, (signed char)-1);  // the rows of nbr_site: slot k of site i at 8 i + k
+        for (int i = 0; i < N; ++i)
+            for (int k = 0; k < z; ++k) cls[(size_t)i * MAX_Z + k] = (signed char)slot_class[(size_t)i * z + k];
+        MCHK(hipMemcpyAsync(f.cls, cls.data(), cls.size(), hipMemcpyHostToDevice, h->stream));
+        MCHK(hipMemcpyAsync(f.d1, d1_q30, (size_t)q * 8, hipMemcpyHostToDevice, h->stream));
+        MCHK(hipMemcpyAsync(f.d2, d2_q30, (size_t)q * 8, hipMemcpyHostToDevice, h->stream));
+        MCHK(hipStreamSynchronize(h->stream));  // (the tables are the caller's: copied before this returns)
+        std::memset(f.x, 0, sizeof(f.x));
+        for (int m = 0; m < n_dir; ++m)
+            for (int c = 0; c < n_classes; ++c) f.x[m][c] = x[(size_t)m * n_classes + c];
+        f.n_dir = n_dir;
+        f.n_c = n_classes;
+    }
+    if (int rc = qs_stiffness_clear(h)) return rc;
+    MCHK(hipStreamSynchronize(h->stream));
+    if (h->bin.on) return dqmc_qs_binner_enable(h, h->bin.cap);  // every section empty, the capacity kept
+    return DQMC_OK;
+}
+
+int dqmc_qs_get_stiffness(dqmc_qs_handle *h, int32_t walker, dqmc_qs_stiffness *out)
+{
+    if (int rc = mc_walker(h, walker, "dqmc_qs_get_stiffness")) return rc;
+    if (!out) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_qs_get_stiffness: null out");
+    const dqmc_qs_handle::Stiffness &f = h->st;
+    *out = dqmc_qs_stiffness{};
+    if (f.n_dir < 1) return DQMC_OK;
+    MCHK(hipSetDevice(h->device));
+    long long n = 0;
+    if (int rc = mc_get(h, f.n_meas, 0, walker, &n)) return rc;
+    for (int m = 0; m < f.n_dir; ++m) {
+        int rc = 0;
+        if ((rc = mc_get(h, f.sT, m, walker, &out->sum_T[m])) || (rc = mc_get(h, f.sJ, m, walker, &out->sum_J[m])) ||
+            (rc = mc_get(h, f.sJ2, m, walker, &out->sum_J2[m])))
+            return rc;
+    }
+    out->n_meas = n;
+    out->n_dir = f.n_dir;
+    return DQMC_OK;
+}
+
+int dqmc_qs_get_stiffness_sample(dqmc_qs_handle *h, int32_t walker, int64_t I[8], int64_t K[8])
+{
+    if (int rc = mc_walker(h, walker, "dqmc_qs_get_stiffness_sample")) return rc;
+    if (!I || !K) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_qs_get_stiffness_sample: null output");
+    const dqmc_qs_handle::Stiffness &f = h->st;
+    for (int c = 0; c < ST_MAX_CLASSES; ++c) I[c] = K[c] = 0;
+    if (f.n_dir < 1) return DQMC_OK;
+    MCHK(hipSetDevice(h->device));
+    for (int c = 0; c < f.n_c; ++c) {
+        long long a = 0, b = 0;
+        int rc = 0;
+        if ((rc = mc_get(h, f.sI, c, walker, &a)) || (rc = mc_get(h, f.sK, c, walker, &b))) return rc;
+        I[c] = a;
+        K[c] = b;
+    }
+    return DQMC_OK;
+}
+
+int dqmc_qs_stiffness_binner_get_level(dqmc_qs_handle *h, int32_t walker, int32_t level, double *x_sum, double *x2_sum,
+                                       double *xy_sum, int64_t *count)
+{
+    QS_STIFFNESS_BIN_OK(h, "dqmc_qs_stiffness_binner_get_level");
+    if (int rc = mc_walker(h, walker, "dqmc_qs_stiffness_binner_get_level")) return rc;
+    return h->st.bin.level_sums(h, "dqmc_qs_stiffness_binner_get_level", walker, level, x_sum, x2_sum, xy_sum, count);
+}
+
+int dqmc_qs_stiffness_binner_finish(dqmc_qs_handle *h, int32_t walker, int32_t level, dqmc_qs_stiffness_binned *out)
+{
+    QS_STIFFNESS_BIN_OK(h, "dqmc_qs_stiffness_binner_finish");
+    if (int rc = mc_walker(h, walker, "dqmc_qs_stiffness_binner_finish")) return rc;
+    if (!out) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_qs_stiffness_binner_finish: null out");
+    dqmc_qs_stiffness_binned r{};  // (entries past the section's elements stay 0)
+    if (int rc = h->st.bin.finish(h, "dqmc_qs_stiffness_binner_finish", walker, level, false, r.mean, r.varN, r.varN0, r.tau,
+                                  r.covN, &r.count, &r.level))
+        return rc;
+    r.n_dir = h->st.n_dir;
     *out = r;
     return DQMC_OK;
 }

@@ -303,6 +303,94 @@ def _lattice_vectors(l):
     return [np.array([float(l.sites)])]
 
 
+def _slot_displacements(l, eps=1e-9):
+    """-> images[k][i]: the minimum-image displacements r_j - r_i of the directed slot (i, k), j = neighs[k, i], as a list
+    of vectors: one, or several of equal length where the lattice has a period of 2 along the bond (both +v and -v are
+    minimum images).  The first entry is the image nearest to the unwrapped difference of the positions, so that of the
+    two slots of such a pair one points each way.  From the lattice's own row semantics: _positions and _lattice_vectors;
+    a CubicLattice with D != 3 has neither, and its rows are +e_d (d < D) and -e_d by construction."""
+    nb = np.asarray(l.neighs, dtype=np.int64) - 1
+    z, N = nb.shape
+    if isinstance(l, CubicLattice) and l.dim != 3:
+        D = l.dim
+        out = []
+        for k in range(z):
+            v = np.zeros(D)
+            v[k % D] = 1.0 if k < D else -1.0
+            out.append([[v.copy(), -v] if l.L == 2 else [v.copy()] for _ in range(N)])
+        return out
+    pos = np.array(_positions(l), dtype=np.float64)
+    wrap = np.array(generate_combinations(_lattice_vectors(l)), dtype=np.float64)
+    out = []
+    for k in range(z):
+        raw = pos[nb[k]] - pos                              # [N][dim]
+        cand = raw[None, :, :] + wrap[:, None, :]           # [images][N][dim]
+        norms = np.linalg.norm(cand, axis=2)
+        tied = norms <= norms.min(axis=0)[None, :] + eps
+        row = []
+        for i in range(N):
+            c = cand[tied[:, i], i]
+            if len(c) > 1:  # nearest to the unwrapped difference first (stable), duplicates dropped
+                c = c[np.argsort(np.linalg.norm(c - raw[i], axis=1), kind="stable")]
+                uniq = []
+                for v in c:
+                    if not any(np.linalg.norm(v - u) <= eps for u in uniq):
+                        uniq.append(v)
+                c = uniq
+            row.append(list(c))
+        out.append(row)
+    return out
+
+
+def bond_classes(l, directions=True, eps=1e-9):
+    """-> (slot_class int8 [z, N], class vectors [n_c, dim], x [n_dir, n_c]): the bond displacement classes of a lattice
+    for the helicity modulus (include/dqmc_hip.h, "Stiffness" of the q-state section; QStateMC.set_stiffness).
+
+    A directed slot is (i, k) with j = neighs[k, i]; its displacement is r_j - r_i at minimum image.  A class is a
+    displacement vector in its canonical orientation of +-v, the one whose first non-zero component is positive; a slot
+    is counted (slot_class >= 0) iff its displacement is the canonical one, so that every undirected neighbour pair is
+    counted once; the other slots hold -1.  Classes are numbered in the order they first appear, rows of neighs first.
+    `directions`: 1 to 4 unit vectors of the lattice's dimension, or True for its cartesian axes (at most 4; on a
+    BilayerSquareLattice the two in-plane axes: the layer index has period 2 and carries no twist);
+    x[mu][c] = directions[mu] . v_c.  Where the lattice has a period of 2 along a bond, +v and -v are both minimum
+    images: fine while every requested direction sees the same projection, a ValueError otherwise (SquareLattice(2)
+    along x).  TriangularLattice: the rows of neighs only, not the two-step bonds of ext_neighs."""
+    images = _slot_displacements(l, eps)
+    z, N = len(images), len(images[0])
+    dim = len(images[0][0][0])
+    if directions is True:
+        n_axes = 2 if isinstance(l, BilayerSquareLattice) else min(dim, 4)
+        dirs = np.eye(dim)[:n_axes]
+    else:
+        dirs = np.array(directions, dtype=np.float64)
+        if dirs.ndim != 2 or dirs.shape[1] != dim or not 1 <= dirs.shape[0] <= 4:
+            raise ValueError("bond_classes: 1 to 4 direction vectors of dimension %d, got an array of shape %r"
+                             % (dim, dirs.shape))
+        if not np.all(np.isfinite(dirs)) or np.any(np.abs(np.linalg.norm(dirs, axis=1) - 1.0) > 1e-9):
+            raise ValueError("bond_classes: the directions must be finite unit vectors")
+    slot_class = -np.ones((z, N), dtype=np.int8)
+    vectors = []
+    for k in range(z):
+        for i in range(N):
+            v = images[k][i][0]
+            lead = next((c for c in v if abs(c) > eps), 0.0)
+            if lead <= 0.0:
+                continue  # the reverse slot is the counted one
+            for other in images[k][i][1:]:
+                if np.any(np.abs(dirs @ (other - v)) > eps):
+                    raise ValueError("bond_classes: the displacement of the bond (%d, %d) (1-based) is ambiguous along a "
+                                     "requested direction: the lattice has a period of 2 there" % (i + 1, l.neighs[k, i]))
+            c = next((n for n, u in enumerate(vectors) if np.linalg.norm(u - v) <= eps), None)
+            if c is None:
+                vectors.append(np.array(v, dtype=np.float64))
+                c = len(vectors) - 1
+            slot_class[k, i] = c
+    if not 1 <= len(vectors) <= 8:
+        raise ValueError("bond_classes: %d displacement classes (the engine takes 1 to 8)" % len(vectors))
+    vectors = np.array(vectors, dtype=np.float64)
+    return slot_class, vectors, np.ascontiguousarray(dirs @ vectors.T)
+
+
 def momentum_grid(l):
     """-> (q [N, dim], labels [N, dim]): the N wave vectors a periodic lattice of N sites allows, cartesian, and their
     integer labels.  With A_i = _lattice_vectors(l), the vectors the lattice is periodic under, the reciprocal basis is

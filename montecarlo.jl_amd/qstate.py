@@ -12,7 +12,8 @@ import math
 import numpy as np
 
 from ._lib import (DQMCError, ERR_INVALID, ERR_STATE, QsBinned, QsClusterStats, QsExchangeStats, QsParams, QsScaling,
-                   QsScalingBinned, QsStats, lib)
+                   QsScalingBinned, QsStats, QsStiffness, QsStiffnessBinned, lib)
+from .lattices import bond_classes
 from .mc import _MCBase, _choose_lattice, _delta_var, _llround, _xi, q30_tables, reciprocal_vectors
 
 Q_MAX = 64
@@ -31,13 +32,29 @@ def qstate_tables(q, pair_energy, J=1.0):
             np.ascontiguousarray(_llround(np.sin(ang) * Q30).astype(np.int32)))
 
 
+def twist_tables(q, d1, d2, J=1.0):
+    """(d1_q30, d2_q30) int64 [q]: llround(J d[k] 2^30) for k <= q / 2, the rest mirrored: d1 exactly antisymmetric
+    (d1_q30[0] = 0, and d1_q30[q / 2] = 0 for even q), d2 exactly symmetric"""
+    d1, d2 = np.asarray(d1, dtype=np.float64), np.asarray(d2, dtype=np.float64)
+    a, b = np.zeros(q, dtype=np.int64), np.zeros(q, dtype=np.int64)
+    for k in range(q // 2 + 1):
+        v = int(_llround(J * d1[k] * Q30))
+        a[k] = v
+        a[(q - k) % q] = -v if (q - k) % q != k else 0
+        b[k] = b[(q - k) % q] = _llround(J * d2[k] * Q30)
+    return a, b
+
+
 class QStateModel:
-    """QStateModel(q, pair_energy; dims, L | l, J): s_i in {0 .. q - 1}, 2 <= q <= 64, and
+    """QStateModel(q, pair_energy; dims, L | l, J, twist): s_i in {0 .. q - 1}, 2 <= q <= 64, and
     E = -J sum_bonds e[(s_i - s_j) mod q] over the lattice's undirected bonds table, with the length-q table
-    e = pair_energy, e[d] == e[(q - d) % q].  Any project lattice may be given as `l`."""
+    e = pair_energy, e[d] == e[(q - d) % q].  Any project lattice may be given as `l`.  `twist=(d1, d2)`: the first and
+    second derivative of the pair energy with respect to the angle 2 pi d / q as length-q tables, d1[d] == -d1[(q - d) % q]
+    and d2[d] == d2[(q - d) % q], |J d| <= 4: what the helicity modulus needs (MC(..., stiffness=True)); None for a
+    model whose pair energy is no function of an angle."""
     is_qstate = True
 
-    def __init__(self, q, pair_energy, dims=None, L=None, l=None, J=1.0):
+    def __init__(self, q, pair_energy, dims=None, L=None, l=None, J=1.0, twist=None):
         if int(q) != q or not 2 <= q <= Q_MAX:
             raise ValueError("QStateModel: q must be an integer in 2..%d, got %r" % (Q_MAX, q))
         q = int(q)
@@ -59,6 +76,25 @@ class QStateModel:
         self.L = L if L is not None else getattr(l, "L", len(l))
         self.dims = dims if dims is not None else getattr(l, "dim", 2 if hasattr(l, "lattice") else 1)
         self.e_q30, self.c_q30, self.s_q30 = qstate_tables(q, e, self.J)
+        self.twist, self.twist_q30 = None, None
+        if twist is not None:
+            try:
+                d1, d2 = (np.array(t, dtype=np.float64).reshape(-1) for t in twist)
+            except (TypeError, ValueError):
+                raise ValueError("QStateModel: twist must be a pair (d1, d2) of length-q tables")
+            if d1.size != q or d2.size != q or not (np.all(np.isfinite(d1)) and np.all(np.isfinite(d2))):
+                raise ValueError("QStateModel: twist=(d1, d2) must hold q = %d finite values each" % q)
+            for d in range(q):
+                if d1[d] != -d1[(q - d) % q]:
+                    raise ValueError("QStateModel: twist d1[%d] != -d1[%d]: the first derivative must be antisymmetric, "
+                                     "d1[d] == -d1[(q - d) %% q]" % (d, (q - d) % q))
+                if d2[d] != d2[(q - d) % q]:
+                    raise ValueError("QStateModel: twist d2[%d] != d2[%d]: the second derivative must be symmetric, "
+                                     "d2[d] == d2[(q - d) %% q]" % (d, (q - d) % q))
+            if max(np.max(np.abs(J * d1)), np.max(np.abs(J * d2))) > 4.0:
+                raise ValueError("QStateModel: |J d1[d]| and |J d2[d]| of twist must be at most 4")
+            self.twist = (d1 + 0.0, d2)  # (+ 0.0: no -0.0 entries)
+            self.twist_q30 = twist_tables(q, d1, d2, self.J)
 
     def __len__(self):
         return len(self.l)
@@ -106,20 +142,25 @@ class PottsModel(QStateModel):
 
 class ClockModel(QStateModel):
     """ClockModel(q; dims, L | l, J): e[d] = cos(2 pi d / q), E = -J sum_bonds cos(theta_i - theta_j) with
-    theta = 2 pi s / q (d <= q / 2 computed, the rest mirrored: exactly symmetric)"""
+    theta = 2 pi s / q (d <= q / 2 computed, the rest mirrored: exactly symmetric).  Its twist tables are
+    d1[d] = sin(2 pi d / q), mirrored with the opposite sign (0 at d = 0 and d = q / 2), and d2 = e."""
 
     def __init__(self, q, dims=None, L=None, l=None, J=1.0):
         n = max(int(q), 1) if int(q) == q else 1
-        e = np.zeros(n)
+        e, d1 = np.zeros(n), np.zeros(n)
         for d in range(n // 2 + 1):
             e[d] = e[(n - d) % n] = math.cos(2.0 * math.pi * d / n)
-        super().__init__(q, e, dims=dims, L=L, l=l, J=J)
+            if (n - d) % n != d:
+                d1[d] = math.sin(2.0 * math.pi * d / n)
+                d1[(n - d) % n] = -d1[d]
+        super().__init__(q, e, dims=dims, L=L, l=l, J=J, twist=(d1, e))
 
 
 _ISING_ONLY = "MC with a q-state model: %s is implemented for the IsingModel only (the q-state engine has local " \
               "checkerboard sweeps and keywords of its own: cluster_rate=k for its reflection cluster moves, " \
-              "tempering=(R, k) for replica exchange, binner=True | capacity for the device binner and " \
-              "scaling=True | [k vectors] for S(k) and xi; checkpointing and the sequential sweep are out of scope)"
+              "tempering=(R, k) for replica exchange, binner=True | capacity for the device binner, " \
+              "scaling=True | [k vectors] for S(k) and xi and stiffness=True | [unit vectors] for the helicity " \
+              "modulus; checkpointing and the sequential sweep are out of scope)"
 
 
 class QStateMC(_MCBase):
@@ -149,6 +190,12 @@ class QStateMC(_MCBase):
     S(0) = <M2>/N, whose xi/L crossings locate the transitions, and with a binner `binned_scaling()` gives their error
     bars.  The chains, the sums and binned() are those of a handle without it.
 
+    `stiffness=True` (or a list of at most 4 unit vectors; True: the lattice's cartesian axes) also measures the helicity
+    modulus Upsilon_mu = (<T_mu> - beta <J_mu^2>) / N along each direction wherever E and M are measured (the header's
+    "Stiffness", set_stiffness), for a model with twist tables (ClockModel, or QStateModel(..., twist=(d1, d2))):
+    `stiffness()` gives the plain means, and with a binner `binned_stiffness()` gives the error bars.  The chains, the
+    sums and the other binner sections are those of a handle without it.
+
     The Ising-only options (cluster_moves, global_moves, n_replicas, exchange_rate, fss, binning, update="sequential")
     raise NotImplementedError."""
     _abi = "dqmc_qs_"
@@ -156,7 +203,8 @@ class QStateMC(_MCBase):
     def __init__(self, model, beta=None, T=None, n_walkers=1, seed=123, first_walker=0, thermalization=0, sweeps=1000,
                  measure_rate=1, print_rate=1000, global_moves=False, global_rate=5, device_id=0, series_capacity=0,
                  cluster_moves=False, binning=False, binning_capacity=None, n_replicas=0, exchange_rate=0,
-                 fss=False, update=None, colouring=None, cluster_rate=0, tempering=None, binner=False, scaling=False):
+                 fss=False, update=None, colouring=None, cluster_rate=0, tempering=None, binner=False, scaling=False,
+                 stiffness=False):
         for name, on in (("global_moves", global_moves), ("cluster_moves", cluster_moves), ("binning", binning),
                          ("n_replicas", n_replicas), ("exchange_rate", exchange_rate),
                          ("fss", fss is not False and fss is not None),
@@ -167,6 +215,7 @@ class QStateMC(_MCBase):
         R, k = self._tempering(tempering, n_walkers)
         capacity = self._binner_capacity(binner)
         tables = self._scaling_tables(model.l, scaling)  # (refused before the device is touched)
+        twist = self._stiffness_tables(model, stiffness)  # (likewise)
         if R >= 2 and beta.ndim == 1 and len(beta) == R:
             beta = np.tile(beta, n_walkers // R)  # one ladder's temperatures, the same in every ladder
         self._init_common(model, beta, n_walkers, seed, first_walker, thermalization, sweeps, measure_rate, print_rate,
@@ -193,6 +242,9 @@ class QStateMC(_MCBase):
         self.k_vectors = None
         if tables is not None:
             self._put_scaling(tables)
+        self.stiffness_directions, self.bond_vectors = None, None
+        if twist is not None:
+            self._put_stiffness(twist)
         if capacity is not False:
             self.enable_binning(capacity)
 
@@ -506,6 +558,133 @@ class QStateMC(_MCBase):
         L = getattr(self.model.l, "L", None)
         if L is not None:
             out["xi_over_L"] = [{key: v / float(L) for key, v in o.items()} for o in out["xi"]]
+        if pooled:
+            out["n_walkers"] = len(ws)
+        return out
+
+    # ---- helicity modulus
+    def set_stiffness(self, directions=True):
+        """dqmc_qs_set_stiffness: from now on every measurement also takes T_mu and J_mu of the helicity modulus along the
+        given unit vectors (True: the lattice's cartesian axes, lattices.bond_classes; else 1 to 4 vectors of the
+        lattice's dimension; None or False: off).  Resets the stiffness sums and, if a binner is on, restarts it with
+        every section empty and its capacity kept.  ValueError for a model without twist tables."""
+        self._put_stiffness(self._stiffness_tables(self.model, directions))
+
+    @staticmethod
+    def _stiffness_tables(model, directions):
+        """(slot_class, class vectors, x, directions, d1_q30, d2_q30) of a stiffness argument, None for None or False"""
+        if directions is None or directions is False:
+            return None
+        if getattr(model, "twist_q30", None) is None:
+            raise ValueError("stiffness: the model has no twist tables: its pair energy is no function of an angle "
+                             "(PottsModel); give QStateModel(..., twist=(d1, d2)) the derivatives of the pair energy")
+        slot_class, vectors, x = bond_classes(model.l, directions)
+        dirs = np.eye(vectors.shape[1])[:x.shape[0]] if directions is True else np.array(directions, dtype=np.float64)
+        d1, d2 = model.twist_q30
+        return (np.asfortranarray(slot_class, dtype=np.int8), vectors, np.ascontiguousarray(x, dtype=np.float64), dirs,
+                np.ascontiguousarray(d1, dtype=np.int64), np.ascontiguousarray(d2, dtype=np.int64))
+
+    def _put_stiffness(self, tables):
+        if tables is None:
+            self._c(lib().dqmc_qs_set_stiffness(self._h, 0, 0, None, None, None, None))
+            self.stiffness_directions, self.bond_vectors = None, None
+            return
+        slot_class, vectors, x, dirs, d1, d2 = tables
+        i64, dp = C.POINTER(C.c_int64), C.POINTER(C.c_double)
+        self._c(lib().dqmc_qs_set_stiffness(self._h, x.shape[0], x.shape[1], slot_class.ctypes.data_as(C.POINTER(C.c_int8)),
+                                            d1.ctypes.data_as(i64), d2.ctypes.data_as(i64), x.ctypes.data_as(dp)))
+        self.stiffness_directions, self.bond_vectors = dirs, vectors
+
+    def _n_dir(self):
+        return 0 if self.stiffness_directions is None else len(self.stiffness_directions)
+
+    def stiffness_sums(self, walker=0):
+        """dqmc_qs_stiffness of one walker: n_meas, n_dir (0: off), sum_T[4], sum_J[4], sum_J2[4]"""
+        out = QsStiffness()
+        self._c(lib().dqmc_qs_get_stiffness(self._h, walker, C.byref(out)))
+        return out
+
+    def stiffness_sample(self, walker=0):
+        """(I[n_c], K[n_c]) of the walker's last measurement: the exact int64 class sums of d1_q30 and d2_q30"""
+        I, K = np.zeros(8, dtype=np.int64), np.zeros(8, dtype=np.int64)
+        p = C.POINTER(C.c_int64)
+        self._c(lib().dqmc_qs_get_stiffness_sample(self._h, walker, I.ctypes.data_as(p), K.ctypes.data_as(p)))
+        n_c = 0 if self.bond_vectors is None else len(self.bond_vectors)
+        return I[:n_c].copy(), K[:n_c].copy()
+
+    def stiffness(self, walker=0):
+        """the plain means of one walker: Upsilon_mu = (<T_mu> - beta <J_mu^2>) / N per direction, with T, J, J2 (the
+        means of T_mu, J_mu and J_mu^2), the directions and n_meas"""
+        f = self.stiffness_sums(walker)
+        if f.n_dir < 1:
+            raise DQMCError(ERR_STATE, "stiffness: the measurement is off (MC(stiffness=True) or set_stiffness)")
+        if f.n_meas == 0:
+            raise DQMCError(ERR_INVALID, "stiffness: no measurement has been taken")
+        n, beta = float(f.n_meas), float(self.betas[walker])
+        T, J, J2 = (np.array(s[:f.n_dir]) / n for s in (f.sum_T, f.sum_J, f.sum_J2))
+        return {"Upsilon": (T - beta * J2) / self.N, "T": T, "J": J, "J2": J2,
+                "directions": self.stiffness_directions.copy(), "n_meas": int(f.n_meas)}
+
+    def stiffness_binner_level(self, walker, level):
+        """(x_sum[2 n_dir], x2_sum[2 n_dir], xy_sum[n_dir], count) of one level of one walker of the binner's stiffness
+        section: elements [T_0, J2_0, T_1, J2_1 ..], pairs (T_mu, J2_mu)"""
+        nd = self._n_dir()
+        xs, x2, xy, n = np.zeros(max(2 * nd, 1)), np.zeros(max(2 * nd, 1)), np.zeros(max(nd, 1)), C.c_int64()
+        dp = C.POINTER(C.c_double)
+        self._c(lib().dqmc_qs_stiffness_binner_get_level(self._h, walker, level, xs.ctypes.data_as(dp),
+                                                         x2.ctypes.data_as(dp), xy.ctypes.data_as(dp), C.byref(n)))
+        return xs[:2 * nd], x2[:2 * nd], xy[:nd], n.value
+
+    def stiffness_binner_finish(self, walker=0, level=None):
+        """dqmc_qs_stiffness_binned of one walker at `level` (None: the reliable level)"""
+        out = QsStiffnessBinned()
+        self._c(lib().dqmc_qs_stiffness_binner_finish(self._h, walker, -1 if level is None else int(level), C.byref(out)))
+        return out
+
+    def _binned_stiffness_walker(self, walker, level):
+        """{name: [(mean, variance of the mean at `level`, the same at level 0 or None) per direction]} of one walker"""
+        b = self.stiffness_binner_finish(walker, level)
+        beta, invN = float(self.betas[walker]), 1.0 / self.N
+        obs = {"T": [], "J2": [], "Upsilon": []}
+        for m in range(b.n_dir):
+            T, J2 = b.mean[2 * m], b.mean[2 * m + 1]
+            obs["T"].append((T, b.varN[2 * m], b.varN0[2 * m]))
+            obs["J2"].append((J2, b.varN[2 * m + 1], b.varN0[2 * m + 1]))
+            obs["Upsilon"].append(((T - beta * J2) * invN,
+                                   _delta_var((invN, -beta * invN), b.varN[2 * m], b.varN[2 * m + 1], b.covN[m]), None))
+        return obs, int(b.count), int(b.level)
+
+    def binned_stiffness(self, walker=0, level=None, walkers=None):
+        """mean, std_error and tau of T_mu and J2_mu from the binner's stiffness section at `level` (None: the reliable
+        one), and mean and std_error of Upsilon_mu = (<T_mu> - beta <J2_mu>) / N by the delta method with the gradient
+        (1 / N, -beta / N) on the binned covariance of (T_mu, J2_mu): {"T", "J2", "Upsilon": [{...} per direction],
+        "count", "level"}.  `walkers=[...]` pools chains of equal beta under the rules of binned_scaling(): Upsilon is
+        formed per walker first, std_error = sqrt(sum_w var_w) / W, plus std_error_walkers."""
+        pooled = walkers is not None
+        ws = [int(w) for w in walkers] if pooled else [walker]
+        if not ws:
+            raise ValueError("binned_stiffness: no walker given")
+        if any(self.betas[w] != self.betas[ws[0]] for w in ws):
+            raise ValueError("binned_stiffness: the pooled walkers must share one beta")
+        per = [self._binned_stiffness_walker(w, level) for w in ws]
+        W = float(len(ws))
+
+        def pool(entries):
+            means = np.array([e[0] for e in entries])
+            vl = float(np.sum([e[1] for e in entries]))
+            mean = float(means.sum() / W)
+            o = {"mean": mean, "std_error": (math.sqrt(max(vl, 0.0)) if vl == vl else vl) / W}
+            if entries[0][2] is not None:
+                with np.errstate(invalid="ignore", divide="ignore"):
+                    o["tau"] = float(0.5 * (np.float64(vl) / np.sum([e[2] for e in entries]) - 1.0))
+            if pooled:
+                o["std_error_walkers"] = (math.sqrt(float(((means - mean) ** 2).sum()) / (W * (W - 1.0)))
+                                          if W >= 2 else float("nan"))
+            return o
+
+        out = {"count": per[0][1], "level": per[0][2]}
+        for name in ("T", "J2", "Upsilon"):
+            out[name] = [pool([p[0][name][m] for p in per]) for m in range(len(per[0][0][name]))]
         if pooled:
             out["n_walkers"] = len(ws)
         return out
