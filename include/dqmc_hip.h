@@ -1654,6 +1654,55 @@ typedef struct {
 /* level < 0: the reliable level (the last one with count >= 32, else 0) */
 int dqmc_qs_stiffness_binner_finish(dqmc_qs_handle *h, int32_t walker, int32_t level, dqmc_qs_stiffness_binned *out);
 
+/* ---- checkpoint and resume of the classical MC flavor ---------------------------------------------------------------
+ * save / load (FileIO.jl covers the MC flavor as well as DQMC) for the state of a dqmc_mc_handle or a dqmc_qs_handle.  As
+ * for DQMC ("checkpoint and resume") the engine hands out and takes back one blob and the file around it is the host's
+ * (mc.py: save / load).  Every piece of chain state lives in global memory between launches, every decision is integer or
+ * exact, and the results do not depend on how a run is cut into sweep calls, so a handle that imported a blob continues
+ * BYTE FOR BYTE as the exporting one would have: there is no "measurement point", a handle may be exported between any two
+ * calls, and nothing is rebuilt.  The format (csrc/mc_blob.h) is one of its own; the DQMC blob is untouched by it.
+ * The blob is little-endian with fixed-width fields; doubles are IEEE bit patterns.
+ *   header
+ *     u64 magic "DQMCMCS1"   u32 format version (1)   u32 header bytes
+ *     char[16] dqmc_build_source_hash of the exporting library, zero padded (carried, never checked)
+ *     the configuration: i32 engine kind (0 Ising, 1 q-state), n_sites, z, q (0: Ising), n_walkers, series_capacity,
+ *       n_bonds, update kind, n_colours (0 while sequential), cluster / global rate, exchange n_replicas, exchange rate,
+ *       n_k of FSS (-1 = off) / scaling (0 = off), stiffness n_dir, n_classes
+ *       3 binner sections (main, FSS / scaling, stiffness): i32 on   i64 capacity   i32 L, n_elem, n_pairs, n_comp
+ *       u64 FNV-1a 64 of: the neighbour table, the bonds table, e_q30, (c_q30, s_q30), the twist tables (d1_q30, d2_q30),
+ *       the colouring, the per-walker betas, the k-vector phase tables, the stiffness slot classes and projections; each as
+ *       the handle got it, 0 where it has none
+ *     u32 records   u32 0   per record: u32 tag, u32 element bytes, u64 elements, u64 byte offset in the blob
+ *   payload: the records' arrays in the order of the table, each 8-byte aligned
+ *     the configurations (Ising: the bit-packed u32 words [ceil(n_sites / 32)][W]; q-state: byte states [W][4 ceil(n_sites / 4)])
+ *     per walker: the Philox key; the cursors (sweep or draw, conf, cluster or Wolff move, checkerboard sweeps_drawn); the
+ *     running E, M (Ising) or E_int, Mx, My (q-state); the sums of E, E2, |M|, M2 (q-state: M4) and n_meas; prop / acc of
+ *     the local and of the cluster moves and sum_cluster_size; n_series and the series
+ *     with ladders: the replica labels and per-pair prop / acc
+ *     with FSS / scaling: sum_M4 (Ising), sum_S and their n_meas;  with stiffness: sum_T, sum_J, sum_J2, their n_meas and
+ *     the last sample I, K
+ *     xs, x2, xy, c of every binner section that is on
+ *     u64 x 4: T of the three binner sections, the exchange cursor
+ *   u64 FNV-1a 64 of every byte in front of it
+ * The running energy is restored, not recomputed.  Tables that follow from the configuration (the acceptance weights of
+ * beta, the exchange pair tables and signs, the colour-sorted site tables) are not in the blob: the handle has them.
+ * Import checks, in this order and before its first write: the buffer holds a header; magic; version; the size the header
+ * implies against n_bytes; the checksum; every configuration field against the handle (the first that differs is named
+ * under *_last_error); the ranges of the state (every T <= capacity, n_series <= series_capacity, q-state bytes < q with zero
+ * padding behind site n_sites, Ising padding bits zero, the replica labels a permutation within each ladder).  A refused
+ * import returns DQMC_ERR_INVALID and leaves the handle exactly as it was: an export before and after gives the same
+ * bytes.  Resuming on another walker count or with changed tables is refused by these checks.
+ * dqmc_*_state_size: the bytes of the blob the handle would export now.  dqmc_*_state_export: synchronizes the handle's
+ * stream and copies into `host_out` (n_bytes must be the size, else DQMC_ERR_INVALID); it changes nothing.
+ * dqmc_*_state_import: validates on the host, copies to the device and sets the host-side state (the binner sections' T,
+ * the exchange cursor, the q-state conf cursors).  A null handle: DQMC_ERR_INVALID. */
+int dqmc_mc_state_size(dqmc_mc_handle *h, size_t *n_bytes);
+int dqmc_mc_state_export(dqmc_mc_handle *h, void *host_out, size_t n_bytes);
+int dqmc_mc_state_import(dqmc_mc_handle *h, const void *host_in, size_t n_bytes);
+int dqmc_qs_state_size(dqmc_qs_handle *h, size_t *n_bytes);
+int dqmc_qs_state_export(dqmc_qs_handle *h, void *host_out, size_t n_bytes);
+int dqmc_qs_state_import(dqmc_qs_handle *h, const void *host_in, size_t n_bytes);
+
 /* ---- the SAC flavor: stochastic analytic continuation -----------------------------------------------------------
  * A(omega) from imaginary-time data by sampling (Sandvik, PRB 57, 10287; Beach, cond-mat/0403055; Shao and Sandvik,
  * Phys. Rep. 1003), batched over P independent problems (momenta) and R sampling temperatures each (csrc/sac.hip).

@@ -348,6 +348,12 @@ SIGNATURES = {
     "dqmc_mc_get_fss": (C.c_int, [_H, C.c_int32, C.POINTER(McFss)]),
     "dqmc_mc_fss_binner_get_level": (C.c_int, [_H, C.c_int32, C.c_int32, _dp, _dp, _dp, _i64p]),
     "dqmc_mc_fss_binner_finish": (C.c_int, [_H, C.c_int32, C.c_int32, C.POINTER(McFssBinned)]),
+    "dqmc_mc_state_size": (C.c_int, [_H, C.POINTER(C.c_size_t)]),
+    "dqmc_mc_state_export": (C.c_int, [_H, C.c_void_p, C.c_size_t]),
+    "dqmc_mc_state_import": (C.c_int, [_H, C.c_void_p, C.c_size_t]),
+    "dqmc_qs_state_size": (C.c_int, [_H, C.POINTER(C.c_size_t)]),
+    "dqmc_qs_state_export": (C.c_int, [_H, C.c_void_p, C.c_size_t]),
+    "dqmc_qs_state_import": (C.c_int, [_H, C.c_void_p, C.c_size_t]),
     "dqmc_qs_create": (C.c_int, [C.POINTER(QsParams), C.POINTER(_H)]),
     "dqmc_qs_destroy": (C.c_int, [_H]),
     "dqmc_qs_last_error": (C.c_char_p, [_H]),

@@ -489,11 +489,13 @@ struct dqmc_mc_handle : mc_handle_base {
         // the FSS section of the binner (there iff bin.on && n_k >= 0; its levels and capacity are bin's): elements
         // [M2, M4, S_0 ..], pairs (M2, M4), (M2, S_k), a compressor value per member of a pair
         mc_bin_section bin;
+        uint64_t hash = 0;  // of the two phase tables as dqmc_mc_set_fss got them (the checkpoint blob's header)
     } fss;
     struct Update {  // dqmc_mc_set_update
         int kind = DQMC_MC_UPDATE_SEQUENTIAL, C = 0, threads = CB_THREADS;
         int *site = nullptr, *rows = nullptr, *off = nullptr;  // [N], [N][8], [C + 1]: the colour-sorted tables
         unsigned long long *cursor = nullptr;                  // [W], allocated with the handle (dqmc_mc_seed zeroes it)
+        uint64_t hash = 0;  // of the colouring as dqmc_mc_set_update got it (the checkpoint blob's header)
     } upd;
 };
 
@@ -1191,6 +1193,7 @@ int dqmc_mc_set_fss(dqmc_mc_handle *h, int32_t n_k, const int32_t *cos_q30, cons
         }
         MCHK(hipStreamSynchronize(h->stream));  // (the tables are the caller's: copied before this returns)
         f.n_k = n_k;
+        f.hash = mc_blob::hash_pair(mc_hash(cos_q30, n_k ? (size_t)n_k * h->N : 0), mc_hash(sin_q30, n_k ? (size_t)n_k * h->N : 0));
     }
     if (int rc = mc_fss_clear(h)) return rc;
     MCHK(hipStreamSynchronize(h->stream));
@@ -1267,6 +1270,7 @@ int dqmc_mc_set_update(dqmc_mc_handle *h, int32_t kind, const int32_t *colour, i
     MCHK(hipStreamSynchronize(h->stream));  // (the vectors are this call's: copied before it returns)
     u.C = n_colours;
     u.threads = t.threads;
+    u.hash = mc_hash(colour, (size_t)h->N);
     u.kind = DQMC_MC_UPDATE_CHECKERBOARD;
     return DQMC_OK;
 }
@@ -1293,3 +1297,6 @@ int dqmc_mc_synchronize(dqmc_mc_handle *h)
 }
 
 }  // extern "C"
+
+// checkpoint and resume: dqmc_mc_state_size, _export, _import
+#include "ising_state.inl"

@@ -7,10 +7,12 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cstring>
 #include <string>
 #include <vector>
 
 #include "../../include/dqmc_hip.h"
+#include "mc_blob.h"
 #include "mc_tables.h"
 
 struct mc_handle_base {
@@ -19,6 +21,18 @@ struct mc_handle_base {
     std::vector<void *> allocs;
     std::string err;
 };
+
+// FNV-1a 64 of a table, as the checkpoint blob's header carries it (mc_blob.h)
+template <typename T>
+static uint64_t mc_hash(const T *p, size_t count)
+{
+    return dqmc_blob::fnv1a64(p, count * sizeof(T));
+}
+template <typename T>
+static uint64_t mc_hash(const std::vector<T> &v)
+{
+    return mc_hash(v.data(), v.size());
+}
 
 static thread_local std::string g_mc_null_error;  // what *_last_error(NULL) answers: create errors, null handles
 

@@ -502,6 +502,8 @@ struct dqmc_qs_handle : mc_handle_base {
         long long *prop = nullptr, *acc = nullptr;
     } xch;
     std::vector<double> beta_h;         // [W], as dqmc_qs_set_beta got them (0 at first)
+    // FNV-1a 64 of the tables as the handle got them (the checkpoint blob's header): bonds, (c_q30, s_q30), the colouring
+    uint64_t hash_bonds = 0, hash_order = 0, hash_colour = 0;
     struct Binner : mc_bin_section {    // qs_bin_push: elements [E, E2, |M|, M2, M2, M4], pairs (2 p, 2 p + 1)
         bool on = false;
         int64_t cap = 0;
@@ -514,6 +516,7 @@ struct dqmc_qs_handle : mc_handle_base {
         // the scaling section of the binner (there iff bin.on && n_k > 0; its levels and capacity are bin's): elements
         // [M2, S_0 ..], pairs (M2, S_k), a compressor value per member of a pair
         mc_bin_section bin;
+        uint64_t hash = 0;                     // of the two phase tables as dqmc_qs_set_scaling got them
     } sc;
     struct Stiffness {                  // dqmc_qs_set_stiffness; n_dir = 0: off
         int n_dir = 0, n_c = 0;
@@ -526,6 +529,7 @@ struct dqmc_qs_handle : mc_handle_base {
         // the stiffness section of the binner (there iff bin.on && n_dir > 0; its levels and capacity are bin's):
         // elements [T_0, J2_0, T_1, J2_1 ..], pairs (2 p, 2 p + 1)
         mc_bin_section bin;
+        uint64_t hash_twist = 0, hash = 0;     // of (d1_q30, d2_q30) and of (slot_class, x) as dqmc_qs_set_stiffness got them
     } st;
 };
 
@@ -775,6 +779,9 @@ int dqmc_qs_create(const dqmc_qs_params *p, dqmc_qs_handle **out)
     h->e_h.assign(p->e_q30, p->e_q30 + q);
     h->confs_h.assign((size_t)h->W, 0ull);
     h->beta_h.assign((size_t)h->W, 0.0);
+    h->hash_bonds = mc_hash(bonds_h);
+    h->hash_order = mc_blob::hash_pair(mc_hash(p->c_q30, (size_t)q), mc_hash(p->s_q30, (size_t)q));
+    h->hash_colour = mc_hash(p->colour, (size_t)N);
     std::vector<int2> cs_h((size_t)q);
     for (int d = 0; d < q; ++d) cs_h[d] = make_int2(p->c_q30[d], p->s_q30[d]);
     auto bail = [&](int rc) { return mc_bail(h, rc); };
@@ -922,7 +929,9 @@ int dqmc_qs_set_colouring(dqmc_qs_handle *h, const int32_t *colour, int32_t n_co
     if (!mc_tables::colour_tables("dqmc_qs_set_colouring", h->nbr_h, h->N, h->z, colour, n_colours, MAX_COLOURS + 1, THREADS, t,
                                   &msg))
         return mc_fail(h, DQMC_ERR_INVALID, msg);
-    return qs_put_colouring(h, t, n_colours);
+    if (int rc = qs_put_colouring(h, t, n_colours)) return rc;
+    h->hash_colour = mc_hash(colour, (size_t)h->N);
+    return DQMC_OK;
 }
 
 int dqmc_qs_sweep(dqmc_qs_handle *h, int32_t n_sweeps, int64_t first_sweep_index, int64_t thermalization,
@@ -1228,6 +1237,7 @@ int dqmc_qs_set_scaling(dqmc_qs_handle *h, int32_t n_k, const int32_t *cos_q30, 
                               h->stream));
         MCHK(hipStreamSynchronize(h->stream));  // (the tables are the caller's: copied before this returns)
         f.n_k = n_k;
+        f.hash = mc_blob::hash_pair(mc_hash(cos_q30, (size_t)n_k * h->N), mc_hash(sin_q30, (size_t)n_k * h->N));
     }
     if (int rc = qs_scaling_clear(h)) return rc;
     MCHK(hipStreamSynchronize(h->stream));
@@ -1317,6 +1327,8 @@ int dqmc_qs_set_stiffness(dqmc_qs_handle *h, int32_t n_dir, int32_t n_classes, c
             for (int c = 0; c < n_classes; ++c) f.x[m][c] = x[(size_t)m * n_classes + c];
         f.n_dir = n_dir;
         f.n_c = n_classes;
+        f.hash_twist = mc_blob::hash_pair(mc_hash(d1_q30, (size_t)q), mc_hash(d2_q30, (size_t)q));
+        f.hash = mc_blob::hash_pair(mc_hash(slot_class, (size_t)N * z), mc_hash(x, (size_t)n_dir * n_classes));
     }
     if (int rc = qs_stiffness_clear(h)) return rc;
     MCHK(hipStreamSynchronize(h->stream));
@@ -1438,3 +1450,6 @@ int dqmc_qs_synchronize(dqmc_qs_handle *h)
 }
 
 }  // extern "C"
+
+// checkpoint and resume: dqmc_qs_state_size, _export, _import
+#include "qs_state.inl"

@@ -664,6 +664,9 @@ class DQMC:
         a sharded run give back distinct walkers.  last_sweep is the saved one; run() continues behind it."""
         from . import lattices as _lat
         pre, blob = _ckpt.read(path)
+        if pre.get("flavor", "dqmc") != "dqmc":  # a file of the classical flavor (MC.save, QStateMC.save)
+            raise _ckpt.CheckpointError("the checkpoint holds a run of flavor %r, DQMC.load reads flavor 'dqmc'"
+                                        % (pre["flavor"],))
         if pre.get("format") != 1:
             raise _ckpt.CheckpointError("checkpoint preamble format %r, this package reads format 1" % (pre.get("format"),))
         lat = pre["lattice"]

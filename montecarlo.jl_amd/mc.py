@@ -12,6 +12,7 @@ import time
 
 import numpy as np
 
+from . import checkpoint as _ckpt
 from ._lib import (DQMCError, ERR_INVALID, ERR_STATE, MC_UPDATE_KINDS, McBinned, McExchangeStats, McFss, McFssBinned,
                    McGlobalStats, McParams, McStats, McUpdateStats, lib)
 from .configurations import CompressedConf
@@ -154,6 +155,8 @@ class _MCBase:
         self.betas = betas
         self.beta = float(betas[0]) if np.all(betas == betas[0]) else betas
         self.seeds = [seed + first_walker + w for w in range(n_walkers)]
+        self._seed0, self._first_walker = seed, first_walker  # (what a checkpoint's preamble writes down)
+        self._binning = None  # the capacity enable_binning was last given (0: the default); None: no binner
         self.thermalization, self.sweeps, self.measure_rate = thermalization, sweeps, measure_rate
         self.print_rate = print_rate
         self.last_sweep = 0
@@ -233,7 +236,105 @@ class _MCBase:
         """run(verbose=True): the lines behind the local acceptance rate; returns the next window's mark"""
         return mark
 
-    def _run(self, verbose, recorder, sweeps, thermalization):
+    # ---- checkpoint and resume (include/dqmc_hip.h "checkpoint and resume of the classical MC flavor"; the file:
+    # checkpoint.py, the container of DQMC.save with a "flavor" key in the preamble)
+    _flavor = None  # "mc_ising" / "mc_qstate"
+
+    def state_size(self):
+        n = C.c_size_t()
+        self._call("state_size", C.byref(n))
+        return n.value
+
+    def state(self):
+        """dqmc_*_state_export: the engine's state as a numpy.uint8 array - configurations, Philox keys, every cursor, the
+        running energy and magnetization, the sums, counters, series, replica labels and every binner level.  Between any
+        two calls; the chains are left exactly as they were."""
+        buf = np.empty(self.state_size(), dtype=np.uint8)
+        self._call("state_export", buf.ctypes.data, buf.size)
+        return buf
+
+    def set_state(self, blob):
+        """dqmc_*_state_import into this object, which must be configured as the exporting one was (walkers, lattice,
+        model tables, betas, colouring, update, cluster and exchange settings, binner, FSS / scaling, stiffness):
+        ERR_INVALID naming the first field that differs otherwise, and the object stays as it was.  Afterwards the chains
+        continue bit for bit as the exporting object's would have."""
+        blob = np.ascontiguousarray(blob, dtype=np.uint8).reshape(-1)
+        self._call("state_import", blob.ctypes.data, blob.size)
+
+    @staticmethod
+    def _lattice_entry(l):
+        from .dqmc import DQMC
+        args = DQMC._lattice_args(type(l).__name__)
+        if args is None:
+            raise ValueError("save(): %s is not a lattice a checkpoint can name" % type(l).__name__)
+        return {"class": type(l).__name__, "args": [int(getattr(l, a)) for a in args]}
+
+    @staticmethod
+    def _lattice_from_entry(entry):
+        from . import lattices as _lat
+        from .dqmc import DQMC
+        if DQMC._lattice_args(entry["class"]) is None:
+            raise _ckpt.CheckpointError("the checkpoint names an unknown lattice")
+        return getattr(_lat, entry["class"])(*entry["args"])
+
+    def _preamble(self):
+        """everything load() needs to build and configure the object again; `mc` holds the constructor's keywords"""
+        return {"format": 1, "flavor": self._flavor, "model": self._model_entry(self.model),
+                "lattice": self._lattice_entry(self.model.l),
+                "mc": dict(self._settings(), beta=[float(b) for b in self.betas], n_walkers=int(self.n_walkers),
+                           seed=int(self._seed0), first_walker=int(self._first_walker),
+                           thermalization=int(self.thermalization), sweeps=int(self.sweeps),
+                           measure_rate=int(self.measure_rate), print_rate=int(self.print_rate),
+                           series_capacity=int(self.series_capacity)),
+                "seeds": [int(s) for s in self.seeds], "last_sweep": int(self.last_sweep)}
+
+    def save(self, path):
+        """save(filename, mc) (FileIO.jl) for what lives on the device: one file (checkpoint.py) with a JSON preamble -
+        flavor, model, lattice, the constructor's keywords as they stand now, the seeds and the run loop's last sweep - and
+        the blob of state().  Written to a temporary file in the same directory and moved into place, so `path` always
+        holds a whole checkpoint.  Between any two sweep() calls: the classical flavor has no measurement point."""
+        _ckpt.write(path, self._preamble(), self.state())
+
+    @classmethod
+    def check_flavor(cls, pre):
+        """CheckpointError naming the flavor found unless the preamble is one of this class"""
+        found = pre.get("flavor", "dqmc")
+        if found != cls._flavor:
+            raise _ckpt.CheckpointError("the checkpoint holds a run of flavor %r, %s.load reads flavor %r"
+                                        % (found, cls.__name__, cls._flavor))
+        if pre.get("format") != 1:
+            raise _ckpt.CheckpointError("checkpoint preamble format %r, this package reads format 1" % (pre.get("format"),))
+
+    @classmethod
+    def load(cls, path, device_id=0):
+        """load(filename): an object constructed and configured as the saved one - the settings applied in the order the
+        constructor applies them - with its state imported (set_state, whose configuration check guards the
+        reconstruction) on device `device_id`.  seed and first_walker are the saved ones, so the files of the ranks of a
+        sharded run give back distinct walkers.  last_sweep is the saved one; run() continues behind it."""
+        pre, blob = _ckpt.read(path)
+        cls.check_flavor(pre)
+        model = cls._model_from_entry(pre["model"], cls._lattice_from_entry(pre["lattice"]))
+        kw = dict(pre["mc"])
+        kw["beta"] = np.array(kw["beta"], dtype=np.float64)
+        mc = cls(model, device_id=device_id, **cls._keywords(kw))
+        try:
+            mc.set_state(blob)
+        except BaseException:
+            mc.close()
+            raise
+        mc.seeds = [int(s) for s in pre["seeds"]]
+        mc.last_sweep = int(pre["last_sweep"])
+        return mc
+
+    @staticmethod
+    def _keywords(kw):
+        """the constructor's keywords from the "mc" entry of a preamble (JSON lists back to what the constructor takes)"""
+        return kw
+
+    def _run(self, verbose, recorder, sweeps, thermalization, checkpoint=None, checkpoint_every=None):
+        if checkpoint is not None and (checkpoint_every is None or int(checkpoint_every) < 1):
+            raise ValueError("run(checkpoint=path) needs checkpoint_every >= 1")
+        every = int(checkpoint_every) if checkpoint is not None else 0
         if sweeps is not None:
             self.sweeps = sweeps
         if thermalization is not None:
@@ -249,6 +350,8 @@ class _MCBase:
                 stop = min(total, ((nxt + r - 1) // r) * r)
             elif verbose and self.print_rate:
                 stop = min(total, (self.last_sweep // self.print_rate + 1) * self.print_rate)
+            if every:  # a sweep call also ends at every multiple of checkpoint_every: the results do not depend on the cuts
+                stop = min(stop, (self.last_sweep // every + 1) * every)
             self.sweep(stop - self.last_sweep)
             i = self.last_sweep
             if recorder is not None and i > self.thermalization:
@@ -259,6 +362,8 @@ class _MCBase:
                       (i, (time.time() - t0) / self.print_rate, 100.0 * st.acc_local / max(st.prop_local, 1)))
                 t0 = time.time()
                 mark = self._print_more(mark)
+            if every and (i % every == 0 or i == total):
+                self.save(checkpoint)
         return True
 
 
@@ -296,6 +401,7 @@ class MC(_MCBase):
     With a q-state model (qstate.PottsModel, ClockModel, QStateModel) MC(...) returns a qstate.QStateMC: the engine of
     dqmc_qs_* with its own kernels.  With an IsingModel nothing changes."""
     _abi = "dqmc_mc_"
+    _flavor = "mc_ising"
 
     def __new__(cls, model, *args, **kwargs):
         if cls is MC and getattr(model, "is_qstate", False):
@@ -332,7 +438,7 @@ class MC(_MCBase):
             self._c(lib().dqmc_mc_set_global_rate(self._h, int(global_rate)))
         if self.n_replicas or self.exchange_rate:
             self.set_exchange(self.n_replicas, self.exchange_rate)
-        self.update = "sequential"
+        self.update, self.colouring = "sequential", None
         if update != "sequential" or colouring is not None:
             self.set_update(update, colouring)
         self.k_vectors = None
@@ -372,10 +478,33 @@ class MC(_MCBase):
         return int(self.stats(walker).uniforms_used)
 
     # ---- the loop
-    def run(self, verbose=False, recorder=None, sweeps=None, thermalization=None):
+    def run(self, verbose=False, recorder=None, sweeps=None, thermalization=None, checkpoint=None, checkpoint_every=None):
         """run!(mc) (MC.jl:190-315) for every walker, resuming after last_sweep; a recorder gets
-        push(mc, i) after each sweep i > thermalization (of walker 0, ConfigRecorder keeps every rate-th)"""
-        return self._run(verbose, recorder, sweeps, thermalization)
+        push(mc, i) after each sweep i > thermalization (of walker 0, ConfigRecorder keeps every rate-th).
+        `checkpoint=path` saves the run (save()) after every sweep whose index is a multiple of `checkpoint_every` and
+        after the last one; the sweep calls are cut there, which changes no bit of the results.  A ConfigRecorder's
+        configurations are the caller's and are not part of the file."""
+        return self._run(verbose, recorder, sweeps, thermalization, checkpoint, checkpoint_every)
+
+    # ---- checkpoint and resume (state, set_state, save, load: _MCBase)
+    @staticmethod
+    def _model_entry(m):
+        if type(m) is not IsingModel:
+            raise ValueError("save(): %s is not a model a checkpoint can name" % type(m).__name__)
+        return {"class": "IsingModel", "dims": int(m.dims), "L": int(m.L)}
+
+    @staticmethod
+    def _model_from_entry(entry, l):
+        if entry.get("class") != "IsingModel":
+            raise _ckpt.CheckpointError("the checkpoint names an unknown model")
+        return IsingModel(dims=entry["dims"], L=entry["L"], l=l)
+
+    def _settings(self):
+        return {"cluster_moves": bool(self.cluster_moves), "global_rate": int(self.global_rate),
+                "n_replicas": int(self.n_replicas), "exchange_rate": int(self.exchange_rate), "update": self.update,
+                "colouring": None if self.colouring is None else [int(c) for c in self.colouring],
+                "fss": False if self.k_vectors is None else np.asarray(self.k_vectors, dtype=np.float64).tolist(),
+                "binning": self._binning is not None, "binning_capacity": self._binning or None}
 
     def _print_mark(self):
         if not self.cluster_moves:
@@ -441,9 +570,11 @@ class MC(_MCBase):
             raise ValueError("set_update: kind must be one of %s" % (MC_UPDATE_KINDS,))
         if kind == "sequential":
             self._c(lib().dqmc_mc_set_update(self._h, 0, None, 0))
+            self.colouring = None
         else:
             col, n = self._colours(colouring, "set_update")
             self._c(lib().dqmc_mc_set_update(self._h, 1, col.ctypes.data_as(C.POINTER(C.c_int32)), n))
+            self.colouring = col
         self.update = kind
 
     def update_stats(self, walker=0):
@@ -483,6 +614,7 @@ class MC(_MCBase):
         """a LogBinner per walker over [E, E2, |M|, M2] (capacity None: 100000 measurements); enabling again starts
         anew.  A sweep() whose measurements would pass the capacity raises before anything runs."""
         self._c(lib().dqmc_mc_binner_enable(self._h, 0 if capacity is None else int(capacity)))
+        self._binning = 0 if capacity is None else int(capacity)
 
     def binner_size(self):
         """(levels, pushes so far)"""

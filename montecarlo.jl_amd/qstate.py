@@ -11,6 +11,7 @@ import math
 
 import numpy as np
 
+from . import checkpoint as _ckpt
 from ._lib import (DQMCError, ERR_INVALID, ERR_STATE, QsBinned, QsClusterStats, QsExchangeStats, QsParams, QsScaling,
                    QsScalingBinned, QsStats, QsStiffness, QsStiffnessBinned, lib)
 from .lattices import bond_classes
@@ -160,7 +161,7 @@ _ISING_ONLY = "MC with a q-state model: %s is implemented for the IsingModel onl
               "checkerboard sweeps and keywords of its own: cluster_rate=k for its reflection cluster moves, " \
               "tempering=(R, k) for replica exchange, binner=True | capacity for the device binner, " \
               "scaling=True | [k vectors] for S(k) and xi and stiffness=True | [unit vectors] for the helicity " \
-              "modulus; checkpointing and the sequential sweep are out of scope)"
+              "modulus; the sequential sweep is out of scope)"
 
 
 class QStateMC(_MCBase):
@@ -199,6 +200,7 @@ class QStateMC(_MCBase):
     The Ising-only options (cluster_moves, global_moves, n_replicas, exchange_rate, fss, binning, update="sequential")
     raise NotImplementedError."""
     _abi = "dqmc_qs_"
+    _flavor = "mc_qstate"
 
     def __init__(self, model, beta=None, T=None, n_walkers=1, seed=123, first_walker=0, thermalization=0, sweeps=1000,
                  measure_rate=1, print_rate=1000, global_moves=False, global_rate=5, device_id=0, series_capacity=0,
@@ -353,6 +355,7 @@ class QStateMC(_MCBase):
         on the device where the measurement is taken; enabling again starts anew.  A sweep() whose measurements would
         pass the capacity raises before anything runs."""
         self._c(lib().dqmc_qs_binner_enable(self._h, 0 if capacity is None else int(capacity)))
+        self._binning = 0 if capacity is None else int(capacity)
 
     def binner_size(self):
         """(levels, pushes so far)"""
@@ -704,9 +707,49 @@ class QStateMC(_MCBase):
         return st.mx_q30 / Q30, st.my_q30 / Q30
 
     # ---- the loop
-    def run(self, verbose=False, sweeps=None, thermalization=None):
-        """run!(mc) for every walker, resuming after last_sweep"""
-        return self._run(verbose, None, sweeps, thermalization)
+    def run(self, verbose=False, sweeps=None, thermalization=None, checkpoint=None, checkpoint_every=None):
+        """run!(mc) for every walker, resuming after last_sweep.  `checkpoint=path` saves the run (save()) after every
+        sweep whose index is a multiple of `checkpoint_every` and after the last one; the sweep calls are cut there, which
+        changes no bit of the results."""
+        return self._run(verbose, None, sweeps, thermalization, checkpoint, checkpoint_every)
+
+    # ---- checkpoint and resume (state, set_state, save, load: _MCBase)
+    @staticmethod
+    def _model_entry(m):
+        """the "model" entry of a checkpoint preamble.  JSON floats give back the same doubles, so pair_energy, J and
+        twist construct the same fixed-point tables again."""
+        if not isinstance(m, QStateModel):
+            raise ValueError("save(): %s is not a model a checkpoint can name" % type(m).__name__)
+        name = type(m).__name__ if type(m) in (PottsModel, ClockModel) else "QStateModel"
+        return {"class": name, "q": int(m.q), "J": float(m.J), "pair_energy": [float(x) for x in m.pair_energy],
+                "twist": None if m.twist is None else [[float(x) for x in t] for t in m.twist],
+                "dims": int(m.dims), "L": int(m.L)}
+
+    @staticmethod
+    def _model_from_entry(entry, l):
+        kw = dict(dims=entry["dims"], L=entry["L"], l=l, J=entry["J"])
+        if entry.get("class") == "PottsModel":
+            return PottsModel(entry["q"], **kw)
+        if entry.get("class") == "ClockModel":
+            return ClockModel(entry["q"], **kw)
+        if entry.get("class") != "QStateModel":
+            raise _ckpt.CheckpointError("the checkpoint names an unknown model")
+        return QStateModel(entry["q"], entry["pair_energy"], twist=entry["twist"], **kw)
+
+    def _settings(self):
+        R, k = int(self.n_replicas), int(self.exchange_rate)
+        return {"colouring": [int(c) for c in self.colouring], "cluster_rate": int(self.cluster_rate),
+                "tempering": [R, k] if R or k else None,
+                "binner": False if self._binning is None else (self._binning or True),
+                "scaling": False if self.k_vectors is None else np.asarray(self.k_vectors, dtype=np.float64).tolist(),
+                "stiffness": False if self.stiffness_directions is None
+                else np.asarray(self.stiffness_directions, dtype=np.float64).tolist()}
+
+    @staticmethod
+    def _keywords(kw):
+        if kw.get("tempering") is not None:
+            kw["tempering"] = tuple(kw["tempering"])
+        return kw
 
     # ---- results
     def analysis(self, walker=0):
