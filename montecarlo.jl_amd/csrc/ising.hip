@@ -61,6 +61,7 @@
 // the sequential kernels, their launches and their results are untouched while the mode is off.
 #include <hip/hip_runtime.h>
 
+#include <array>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -69,6 +70,7 @@
 
 #include "../../include/dqmc_hip.h"
 #include "kernels.h"
+#include "mc_bin_device.h"
 #include "mc_host.h"
 
 namespace dqmc_mc {
@@ -440,7 +442,7 @@ __global__ __launch_bounds__(WAVE) void ising_exchange_kernel(DevState s, Exchan
     if (measure) ising_measure_slot(s, w, E, M);
 }
 
-// the finite-size-scaling measurement: FssArg, ising_fss_bin_push, ising_fss_kernel
+// the finite-size-scaling measurement: FssArg, ising_fss_kernel
 #include "ising_fss.inl"
 
 // the checkerboard sweep, one workgroup per walker: CbArg, ising_cb_kernel
@@ -497,6 +499,8 @@ struct dqmc_mc_handle : mc_handle_base {
         unsigned long long *cursor = nullptr;                  // [W], allocated with the handle (dqmc_mc_seed zeroes it)
         uint64_t hash = 0;  // of the colouring as dqmc_mc_set_update got it (the checkpoint blob's header)
     } upd;
+    // every binner section, at its index in the checkpoint blob (mc_blob.h: SEC_MAIN, SEC_SCALING)
+    std::array<mc_bin_section *, 2> sections() { return {&bin, &fss.bin}; }
 };
 
 static int mc_launch_observables(dqmc_mc_handle *h, int walker)
@@ -551,16 +555,6 @@ static int mc_put_pair_table(dqmc_mc_handle *h, int a)
     return mc_put<int>(h, h->xch.sgn, 0, a, sgn);
 }
 
-static const int64_t MC_BIN_DEFAULT_CAPACITY = 100000;  // BinningAnalysis' _default_capacity
-
-static void mc_bin_free(dqmc_mc_handle *h)  // both sections; the binner is off afterwards
-{
-    h->fss.bin.free(h);
-    h->bin.free(h);
-    h->bin.on = false;
-    h->bin.cap = 0;
-}
-
 // the push of the measurement ising_wolff_kernel has just taken
 static int mc_launch_bin_push(dqmc_mc_handle *h)
 {
@@ -574,23 +568,18 @@ static int mc_launch_bin_push(dqmc_mc_handle *h)
     return 0;
 }
 
-#define MC_BIN_OK(h, fn)                                                                              \
-    if (!(h)) return mc_fail(nullptr, DQMC_ERR_INVALID, std::string(fn) + ": null handle");          \
-    if (!(h)->bin.on) return mc_fail((h), DQMC_ERR_STATE, std::string(fn) + ": the binner is not enabled")
-
 // ---- finite-size-scaling observables
 constexpr int MAX_K = 8;
 
-// the FSS section for the binner as it stands (nothing unless both are on)
-static int mc_fss_bin_alloc(dqmc_mc_handle *h)
+// every section the handle's features call for, at L levels each: the one place that knows their shapes
+static int mc_bin_alloc(dqmc_mc_handle *h, int L)
 {
-    dqmc_mc_handle::Fss &f = h->fss;
-    f.bin.free(h);
-    if (!h->bin.on || f.n_k < 0) return 0;
-    return f.bin.alloc(h, 2 + f.n_k, 1 + f.n_k, 2 * (1 + f.n_k), h->bin.L);
+    const int n_k = h->fss.n_k;
+    if (int rc = h->bin.alloc(h, 4, 2, 4, L)) return rc;
+    return n_k < 0 ? 0 : h->fss.bin.alloc(h, 2 + n_k, 1 + n_k, 2 * (1 + n_k), L);
 }
 
-static int mc_fss_clear(dqmc_mc_handle *h)  // the sums and the section's state
+static int mc_fss_clear(dqmc_mc_handle *h)  // the sums (the section: mc_bin_clear)
 {
     dqmc_mc_handle::Fss &f = h->fss;
     const size_t W = h->W;
@@ -599,7 +588,7 @@ static int mc_fss_clear(dqmc_mc_handle *h)  // the sums and the section's state
         MCHK(hipMemsetAsync(f.sS, 0, (size_t)MAX_K * W * 8, h->stream));
         MCHK(hipMemsetAsync(f.n_meas, 0, W * 8, h->stream));
     }
-    return f.bin.clear(h);
+    return 0;
 }
 
 // the FSS measurement of the sweep whose last kernel has just been launched (and its push).  The 1 + n_k pairs run side
@@ -613,14 +602,7 @@ static int mc_launch_fss(dqmc_mc_handle *h)
     a.sM4 = f.sM4;
     a.sS = f.sS;
     a.n_meas = f.n_meas;
-    if (f.bin.xs) {
-        if (int rc = f.bin.next_lmax(h, "dqmc_mc_sweep", &a.lmax)) return rc;
-        a.bxs = f.bin.xs;
-        a.bx2 = f.bin.x2;
-        a.bxy = f.bin.xy;
-        a.bc = f.bin.c;
-        a.top = f.bin.L - 1;
-    }
+    if (int rc = f.bin.push_arg(h, "dqmc_mc_sweep", &a.bin)) return rc;
     const int pairs = 1 + f.n_k;
     const double per_pair = (double)h->N * std::max((double)h->W, BUDGET_WALKERS);
     const int chunk = (int)std::max(1.0, std::min((double)pairs, std::floor(LAUNCH_BUDGET / per_pair)));
@@ -629,13 +611,11 @@ static int mc_launch_fss(dqmc_mc_handle *h)
                            h->stream, h->d, a, (const int4 *)f.cq, (const int4 *)f.sq, y0);
         MCHK(hipGetLastError());
     }
-    if (f.bin.xs) f.bin.T += 1;
+    f.bin.pushed();
     return 0;
 }
 
-#define MC_FSS_BIN_OK(h, fn)                                                                          \
-    MC_BIN_OK(h, fn);                                                                                 \
-    if (!(h)->fss.bin.xs) return mc_fail((h), DQMC_ERR_STATE, std::string(fn) + ": FSS is off (dqmc_mc_set_fss first)")
+static const char *const MC_FSS_OFF = ": FSS is off (dqmc_mc_set_fss first)";
 
 extern "C" {
 
@@ -969,12 +949,8 @@ int dqmc_mc_get_global_stats(dqmc_mc_handle *h, int32_t walker, dqmc_mc_global_s
 
 int dqmc_mc_set_exchange(dqmc_mc_handle *h, int32_t n_replicas, int32_t rate)
 {
-    if (!h) return mc_fail(nullptr, DQMC_ERR_INVALID, "dqmc_mc_set_exchange: null handle");
-    if (n_replicas < 0 || rate < 0)
-        return mc_fail(h, DQMC_ERR_INVALID, "dqmc_mc_set_exchange: n_replicas and rate must be >= 0 (0 = off)");
-    const int R = n_replicas >= 2 ? n_replicas : 0;
-    if (R && h->W % R != 0)
-        return mc_fail(h, DQMC_ERR_INVALID, "dqmc_mc_set_exchange: n_walkers must be a multiple of n_replicas");
+    int R = 0;
+    if (int rc = mc_exchange_ladders(h, "dqmc_mc_set_exchange", n_replicas, rate, &R)) return rc;
     MCHK(hipSetDevice(h->device));
     dqmc_mc_handle::Tempering &t = h->xch;
     const size_t W = h->W;
@@ -1037,21 +1013,7 @@ int dqmc_mc_exchange(dqmc_mc_handle *h)
 
 int dqmc_mc_get_exchange_stats(dqmc_mc_handle *h, int32_t walker, dqmc_mc_exchange_stats *out)
 {
-    if (int rc = mc_walker(h, walker, "dqmc_mc_get_exchange_stats")) return rc;
-    if (!out) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_mc_get_exchange_stats: null out");
-    MCHK(hipSetDevice(h->device));
-    const dqmc_mc_handle::Tempering &t = h->xch;
-    long long prop = 0, acc = 0;
-    int label = 0;
-    int rc = 0;
-    if (t.q && ((rc = mc_get(h, t.prop, 0, walker, &prop)) || (rc = mc_get(h, t.acc, 0, walker, &acc)) ||
-                (rc = mc_get(h, t.replica, 0, walker, &label))))
-        return rc;
-    out->prop_exchange = prop;
-    out->acc_exchange = acc;
-    out->replica = label;
-    out->rounds = t.cursor;
-    return DQMC_OK;
+    return mc_get_exchange_stats(h, "dqmc_mc_get_exchange_stats", walker, out);
 }
 
 int dqmc_mc_exchange_fused(dqmc_mc_handle *h, int32_t *fused)
@@ -1091,23 +1053,22 @@ int dqmc_mc_reset_accumulators(dqmc_mc_handle *h)
     MCHK(hipMemsetAsync(h->d.sM2, 0, W * 8, h->stream));
     MCHK(hipMemsetAsync(h->d.n_meas, 0, W * 8, h->stream));
     MCHK(hipMemsetAsync(h->d.n_series, 0, W * 8, h->stream));
-    if (int rc = h->bin.clear(h)) return rc;
     if (int rc = mc_fss_clear(h)) return rc;
+    if (int rc = mc_bin_clear(h)) return rc;
     MCHK(hipStreamSynchronize(h->stream));
     return DQMC_OK;
 }
 
 int dqmc_mc_binner_enable(dqmc_mc_handle *h, int64_t capacity)
 {
-    if (!h) return mc_fail(nullptr, DQMC_ERR_INVALID, "dqmc_mc_binner_enable: null handle");
-    if (capacity < 0) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_mc_binner_enable: capacity must be positive (0 selects 100000)");
-    if (capacity == 0) capacity = MC_BIN_DEFAULT_CAPACITY;
-    if (capacity > ((int64_t)1 << 40)) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_mc_binner_enable: capacity above 2^40");
+    if (int rc = mc_binner_capacity(h, "dqmc_mc_binner_enable", &capacity)) return rc;
     MCHK(hipSetDevice(h->device));
     MCHK(hipStreamSynchronize(h->stream));
     mc_bin_free(h);
-    dqmc_mc_handle::Binner &b = h->bin;
-    if (int rc = b.alloc(h, 4, 2, 4, mc_tables::bin_levels(capacity))) return rc;
+    if (int rc = mc_bin_alloc(h, mc_tables::bin_levels(capacity))) {  // the FSS section too, when FSS is on
+        mc_bin_free(h);
+        return rc;
+    }
     const void *kernels[] = {(const void *)ising_sweep_binned_kernel<1>, (const void *)ising_sweep_binned_kernel<2>,
                              (const void *)ising_sweep_binned_kernel<3>, (const void *)ising_sweep_binned_kernel<4>,
                              (const void *)ising_sweep_binned_kernel<5>, (const void *)ising_sweep_binned_kernel<6>,
@@ -1119,47 +1080,31 @@ int dqmc_mc_binner_enable(dqmc_mc_handle *h, int64_t capacity)
             return mc_fail(h, DQMC_ERR_HIP, "dqmc_mc_binner_enable: cannot reserve LDS for the spins");
         }
     MCHK(hipStreamSynchronize(h->stream));
-    b.on = true;
-    b.cap = capacity;
-    if (int rc = mc_fss_bin_alloc(h)) {  // the FSS section, when FSS is on
-        mc_bin_free(h);
-        return rc;
-    }
-    MCHK(hipStreamSynchronize(h->stream));
+    h->bin.on = true;
+    h->bin.cap = capacity;
     return DQMC_OK;
 }
 
 int dqmc_mc_binner_size(dqmc_mc_handle *h, int32_t *n_levels, int64_t *n_pushed)
 {
-    MC_BIN_OK(h, "dqmc_mc_binner_size");
-    if (n_levels) *n_levels = h->bin.L;
-    if (n_pushed) *n_pushed = h->bin.T;
-    return DQMC_OK;
+    return mc_binner_size(h, "dqmc_mc_binner_size", n_levels, n_pushed);
 }
 
 int dqmc_mc_binner_reliable_level(dqmc_mc_handle *h, int32_t *level)
 {
-    MC_BIN_OK(h, "dqmc_mc_binner_reliable_level");
-    if (!level) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_mc_binner_reliable_level: null level");
-    *level = mc_tables::bin_reliable(h->bin.T, h->bin.L);
-    return DQMC_OK;
+    return mc_binner_reliable_level(h, "dqmc_mc_binner_reliable_level", level);
 }
 
 int dqmc_mc_binner_get_level(dqmc_mc_handle *h, int32_t walker, int32_t level, double x_sum[4], double x2_sum[4],
                              double xy_sum[2], int64_t *count)
 {
-    MC_BIN_OK(h, "dqmc_mc_binner_get_level");
-    if (int rc = mc_walker(h, walker, "dqmc_mc_binner_get_level")) return rc;
-    return h->bin.level_sums(h, "dqmc_mc_binner_get_level", walker, level, x_sum, x2_sum, xy_sum, count);
+    return mc_binner_get_level(h, "dqmc_mc_binner_get_level", mc_blob::SEC_MAIN, nullptr, walker, level, x_sum, x2_sum, xy_sum,
+                               count);
 }
 
 int dqmc_mc_binner_finish(dqmc_mc_handle *h, int32_t walker, int32_t level, dqmc_mc_binned *out)
 {
-    MC_BIN_OK(h, "dqmc_mc_binner_finish");
-    if (int rc = mc_walker(h, walker, "dqmc_mc_binner_finish")) return rc;
-    if (!out) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_mc_binner_finish: null out");
-    return h->bin.finish(h, "dqmc_mc_binner_finish", walker, level, false, out->mean, out->varN, out->varN0, out->tau,
-                         out->covN, &out->count, &out->level);
+    return mc_binner_finish(h, "dqmc_mc_binner_finish", mc_blob::SEC_MAIN, nullptr, false, walker, level, out);
 }
 
 int dqmc_mc_set_fss(dqmc_mc_handle *h, int32_t n_k, const int32_t *cos_q30, const int32_t *sin_q30)
@@ -1222,22 +1167,15 @@ int dqmc_mc_get_fss(dqmc_mc_handle *h, int32_t walker, dqmc_mc_fss *out)
 int dqmc_mc_fss_binner_get_level(dqmc_mc_handle *h, int32_t walker, int32_t level, double *x_sum, double *x2_sum,
                                  double *xy_sum, int64_t *count)
 {
-    MC_FSS_BIN_OK(h, "dqmc_mc_fss_binner_get_level");
-    if (int rc = mc_walker(h, walker, "dqmc_mc_fss_binner_get_level")) return rc;
-    return h->fss.bin.level_sums(h, "dqmc_mc_fss_binner_get_level", walker, level, x_sum, x2_sum, xy_sum, count);
+    return mc_binner_get_level(h, "dqmc_mc_fss_binner_get_level", mc_blob::SEC_SCALING, MC_FSS_OFF, walker, level, x_sum,
+                               x2_sum, xy_sum, count);
 }
 
 int dqmc_mc_fss_binner_finish(dqmc_mc_handle *h, int32_t walker, int32_t level, dqmc_mc_fss_binned *out)
 {
-    MC_FSS_BIN_OK(h, "dqmc_mc_fss_binner_finish");
-    if (int rc = mc_walker(h, walker, "dqmc_mc_fss_binner_finish")) return rc;
-    if (!out) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_mc_fss_binner_finish: null out");
-    dqmc_mc_fss_binned r{};  // (entries past the section's elements stay 0)
-    if (int rc = h->fss.bin.finish(h, "dqmc_mc_fss_binner_finish", walker, level, true, r.mean, r.varN, r.varN0, r.tau,
-                                   r.covN, &r.count, &r.level))
+    if (int rc = mc_binner_finish(h, "dqmc_mc_fss_binner_finish", mc_blob::SEC_SCALING, MC_FSS_OFF, true, walker, level, out))
         return rc;
-    r.n_k = h->fss.n_k;
-    *out = r;
+    out->n_k = h->fss.n_k;
     return DQMC_OK;
 }
 

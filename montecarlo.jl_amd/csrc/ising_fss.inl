@@ -10,10 +10,9 @@
 //
 // One lane per walker, one wave per workgroup, and blockIdx.y = the pair the workgroup serves: pair 0 is (M2, M4),
 // pair y >= 1 is (M2, S_{y-1}).  The pairs of a walker share nothing they write: each has its own sum, its own
-// elements of the binner and - so that no workgroup reads what another one writes - its own copy of M2's compressor
-// (the copies hold the same values; pair 0 alone adds M2 to x_sum and x2_sum).  All lanes of a wave visit the same
-// site of the same table row, so the row is read with scalar loads; the walker's spin words come from conf[word][W],
-// coalesced.  Results leave through ordinary vector stores.
+// elements of the binner and its own copy of M2's compressor (mc_bin_push_shared, mc_bin_device.h).  All lanes of a
+// wave visit the same site of the same table row, so the row is read with scalar loads; the walker's spin words come
+// from conf[word][W], coalesced.  Results leave through ordinary vector stores.
 
 // kernel argument of the FSS measurement; the tables are arguments of their own (read-only, not aliased)
 struct FssArg {
@@ -21,44 +20,9 @@ struct FssArg {
     double inv;                     // 1 / (N 2^60)
     double *sM4, *sS;               // [W], [8][W]
     long long *n_meas;              // [W]
-    double *bxs, *bx2, *bxy, *bc;   // the FSS section of the binner (bxs == nullptr: binner off):
-                                    // [L][2 + n_k][W], the same, [L][1 + n_k][W], [L - 1][1 + n_k][2][W]
-    int lmax, top;                  // trailing 1-bits of the push count (capped at top), the last level
+    mc_bin_arg bin;                 // the FSS section of the binner: [L][2 + n_k][W], the same, [L][1 + n_k][W],
+                                    // [L - 1][1 + n_k][2][W]
 };
-
-// the push of pair y with the values (a, b) = (M2, element 1 + y), as ising_bin_push does for its four elements
-__device__ __forceinline__ void ising_fss_bin_push(const FssArg &f, int W, int w, int y, double a, double b)
-{
-    const size_t sW = (size_t)W, ne = (size_t)(2 + f.n_k), np = (size_t)(1 + f.n_k);
-    size_t ie = (size_t)(1 + y) * sW + w, i0 = (size_t)w, ip = (size_t)y * sW + w, ic = (size_t)y * 2 * sW + w;
-    for (int l = 0;; ++l, ie += ne * sW, i0 += ne * sW, ip += np * sW, ic += 2 * np * sW) {
-        const bool last = l == f.lmax;
-        const double s1 = f.bxs[ie], s2 = f.bx2[ie], p = f.bxy[ip];  // a level's values are requested together
-        double ca = 0.0, cb = 0.0, t1 = 0.0, t2 = 0.0;
-        if (!last) {
-            ca = f.bc[ic];
-            cb = f.bc[ic + sW];
-        }
-        if (y == 0) {
-            t1 = f.bxs[i0];
-            t2 = f.bx2[i0];
-        }
-        f.bxs[ie] = s1 + b;
-        f.bx2[ie] = s2 + b * b;
-        f.bxy[ip] = p + a * b;
-        if (y == 0) {
-            f.bxs[i0] = t1 + a;
-            f.bx2[i0] = t2 + a * a;
-        }
-        if (last) break;
-        a = 0.5 * (ca + a);
-        b = 0.5 * (cb + b);
-    }
-    if (f.lmax < f.top) {  // (the top level has no compressor)
-        f.bc[ic] = a;
-        f.bc[ic + sW] = b;
-    }
-}
 
 // The tables arrive padded: [n_k][32 nw] with zeros behind site N - 1 (dqmc_mc_set_fss), so that every spin word has its
 // 32 entries, 128-byte aligned, and a row is read in whole int4s.  With m = 0 for an up spin and -1 for a down spin,
@@ -108,5 +72,5 @@ __global__ __launch_bounds__(WAVE) void ising_fss_kernel(DevState s, FssArg f, c
         const double sum = f.sS[at(y - 1, W, w)];
         f.sS[at(y - 1, W, w)] = sum + v;
     }
-    if (f.bxs) ising_fss_bin_push(f, W, w, y, m2, v);
+    if (f.bin.xs) mc_bin_push_shared(f.bin, (size_t)(2 + f.n_k), (size_t)(1 + f.n_k), W, w, y, m2, v);
 }

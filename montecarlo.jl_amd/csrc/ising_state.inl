@@ -2,7 +2,7 @@
 // flavor"): what mc_state.inl needs to know about a dqmc_mc_handle.  Included by ising.hip behind the handle.  No kernel.
 #include "mc_state.inl"
 
-static void mc_state_config(const dqmc_mc_handle *h, mc_blob::Config *c)
+static void mc_state_config(dqmc_mc_handle *h, mc_blob::Config *c)
 {
     const bool cb = h->upd.kind == DQMC_MC_UPDATE_CHECKERBOARD;
     c->kind = mc_blob::KIND_ISING;
@@ -18,9 +18,6 @@ static void mc_state_config(const dqmc_mc_handle *h, mc_blob::Config *c)
     c->exchange_R = h->xch.R;
     c->exchange_rate = h->xch.rate;
     c->n_k = h->fss.n_k;
-    if (h->bin.on) c->bin[mc_blob::SEC_MAIN] = {1, h->bin.L, h->bin.n_elem, h->bin.n_pairs, h->bin.n_comp, h->bin.cap};
-    if (h->fss.bin.xs)
-        c->bin[mc_blob::SEC_SCALING] = {1, h->fss.bin.L, h->fss.bin.n_elem, h->fss.bin.n_pairs, h->fss.bin.n_comp, h->bin.cap};
     c->hash_neighs = mc_hash(h->nbr_h);
     c->hash_bonds = mc_hash(h->bonds_h);
     c->hash_colouring = cb ? h->upd.hash : 0;
@@ -59,31 +56,10 @@ static mc_state_slot mc_state_slot_of(dqmc_mc_handle *h, uint32_t tag)
     case mc_blob::TAG_K_SUM_M4: p = h->fss.sM4; break;
     case mc_blob::TAG_K_SUM_S: p = h->fss.sS; break;
     case mc_blob::TAG_K_N_MEAS: p = h->fss.n_meas; break;
-    default:
-        if (tag >= mc_blob::TAG_BIN && tag < mc_blob::TAG_BIN + 8) {
-            const mc_bin_section &b = tag < mc_blob::TAG_BIN + 4 ? (const mc_bin_section &)h->bin : h->fss.bin;
-            double *const a[4] = {b.xs, b.x2, b.xy, b.c};
-            p = a[(tag - mc_blob::TAG_BIN) & 3];
-        }
     }
     mc_state_slot s;
     s.dev = p;
     return s;
-}
-
-static void mc_state_host_get(const dqmc_mc_handle *h, uint64_t v[mc_blob::HOST_WORDS])
-{
-    v[mc_blob::SEC_MAIN] = (uint64_t)h->bin.T;
-    v[mc_blob::SEC_SCALING] = (uint64_t)h->fss.bin.T;
-    v[mc_blob::SEC_STIFFNESS] = 0;
-    v[mc_blob::N_SEC] = h->xch.cursor;
-}
-
-static void mc_state_host_set(dqmc_mc_handle *h, const uint64_t v[mc_blob::HOST_WORDS])
-{
-    h->bin.T = (int64_t)v[mc_blob::SEC_MAIN];
-    h->fss.bin.T = (int64_t)v[mc_blob::SEC_SCALING];
-    h->xch.cursor = v[mc_blob::N_SEC];
 }
 
 extern "C" {

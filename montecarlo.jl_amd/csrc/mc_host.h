@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/dqmc_hip.h"
+#include "mc_bin_device.h"
 #include "mc_blob.h"
 #include "mc_tables.h"
 
@@ -199,6 +200,20 @@ struct mc_bin_section {
         if (*lmax >= L) return mc_fail(h, DQMC_ERR_STATE, std::string(fn) + ": binner capacity exhausted");
         return 0;
     }
+    // the section as the kernel of the next push sees it (out->xs == nullptr: the section is not there), and that push done
+    int push_arg(mc_handle_base *h, const char *fn, mc_bin_arg *out) const
+    {
+        *out = mc_bin_arg{};
+        if (!xs) return 0;
+        int lmax = 0;
+        if (int rc = next_lmax(h, fn, &lmax)) return rc;
+        *out = mc_bin_arg{xs, x2, xy, c, lmax, L - 1};
+        return 0;
+    }
+    void pushed()
+    {
+        if (xs) T += 1;
+    }
     // the bodies of the *_binner_get_level and *_binner_finish calls (level < 0 in finish: the reliable level)
     int level_sums(mc_handle_base *h, const char *fn, int walker, int level, double *oxs, double *ox2, double *oxy,
                    int64_t *count) const
@@ -224,3 +239,127 @@ struct mc_bin_section {
         return 0;
     }
 };
+
+// ---- the binner of a handle H: h->bin is the main section with `on` and `cap` (the capacity, shared by all sections),
+// and h->sections() lists every section once, in the order of the checkpoint blob's SEC_* (mc_blob.h).  A new section is
+// added to that list and to the engine's *_bin_alloc; everything below, and the checkpoint (mc_state.inl), follows.
+static const int64_t MC_BIN_DEFAULT_CAPACITY = 100000;  // BinningAnalysis' _default_capacity
+
+// (in a function whose handle is `h`)
+#define MC_BIN_OK(h, fn)                                                                     \
+    if (!(h)) return mc_fail(nullptr, DQMC_ERR_INVALID, std::string(fn) + ": null handle"); \
+    if (!(h)->bin.on) return mc_fail((h), DQMC_ERR_STATE, std::string(fn) + ": the binner is not enabled")
+
+template <typename H>
+static void mc_bin_free(H *h)  // every section; the binner is off afterwards
+{
+    for (mc_bin_section *s : h->sections()) s->free(h);
+    h->bin.on = false;
+    h->bin.cap = 0;
+}
+
+template <typename H>
+static int mc_bin_clear(H *h)
+{
+    for (mc_bin_section *s : h->sections())
+        if (int rc = s->clear(h)) return rc;
+    return 0;
+}
+
+// the head of *_binner_enable: the capacity as it will be used (0 selects the default)
+template <typename H>
+static int mc_binner_capacity(H *h, const char *fn, int64_t *capacity)
+{
+    if (!h) return mc_fail(nullptr, DQMC_ERR_INVALID, std::string(fn) + ": null handle");
+    if (*capacity < 0) return mc_fail(h, DQMC_ERR_INVALID, std::string(fn) + ": capacity must be positive (0 selects 100000)");
+    if (*capacity == 0) *capacity = MC_BIN_DEFAULT_CAPACITY;
+    if (*capacity > ((int64_t)1 << 40)) return mc_fail(h, DQMC_ERR_INVALID, std::string(fn) + ": capacity above 2^40");
+    return 0;
+}
+
+template <typename H>
+static int mc_binner_size(H *h, const char *fn, int32_t *n_levels, int64_t *n_pushed)
+{
+    MC_BIN_OK(h, fn);
+    if (n_levels) *n_levels = h->bin.L;
+    if (n_pushed) *n_pushed = h->bin.T;
+    return DQMC_OK;
+}
+
+template <typename H>
+static int mc_binner_reliable_level(H *h, const char *fn, int32_t *level)
+{
+    MC_BIN_OK(h, fn);
+    if (!level) return mc_fail(h, DQMC_ERR_INVALID, std::string(fn) + ": null level");
+    *level = mc_tables::bin_reliable(h->bin.T, h->bin.L);
+    return DQMC_OK;
+}
+
+// section `sec` of an enabled binner for a call about `walker`; off: what follows "fn" when the section is not there
+// (nullptr for the main section, which is there whenever the binner is)
+template <typename H>
+static int mc_binner_section(H *h, const char *fn, int sec, const char *off, int32_t walker, const mc_bin_section **s)
+{
+    MC_BIN_OK(h, fn);
+    *s = h->sections()[sec];
+    if (off && !(*s)->xs) return mc_fail(h, DQMC_ERR_STATE, std::string(fn) + off);
+    return mc_walker(h, walker, fn);
+}
+
+template <typename H>
+static int mc_binner_get_level(H *h, const char *fn, int sec, const char *off, int32_t walker, int32_t level, double *x_sum,
+                               double *x2_sum, double *xy_sum, int64_t *count)
+{
+    const mc_bin_section *s = nullptr;
+    if (int rc = mc_binner_section(h, fn, sec, off, walker, &s)) return rc;
+    return s->level_sums(h, fn, walker, level, x_sum, x2_sum, xy_sum, count);
+}
+
+// Out: one of the dqmc_*_binned structs.  pairs_from_first: pair k = (element 0, element 1 + k), else (2 k, 2 k + 1)
+template <typename H, typename Out>
+static int mc_binner_finish(H *h, const char *fn, int sec, const char *off, bool pairs_from_first, int32_t walker,
+                            int32_t level, Out *out)
+{
+    const mc_bin_section *s = nullptr;
+    if (int rc = mc_binner_section(h, fn, sec, off, walker, &s)) return rc;
+    if (!out) return mc_fail(h, DQMC_ERR_INVALID, std::string(fn) + ": null out");
+    Out r{};  // (entries past the section's elements stay 0)
+    if (int rc = s->finish(h, fn, walker, level, pairs_from_first, r.mean, r.varN, r.varN0, r.tau, r.covN, &r.count, &r.level))
+        return rc;
+    *out = r;
+    return DQMC_OK;
+}
+
+// ---- replica exchange: what has one shape in both engines (h->xch: R, rate, cursor, sgn, replica, prop, acc; the pair
+// tables and the kernels are the engine's)
+template <typename H>
+static int mc_exchange_ladders(H *h, const char *fn, int32_t n_replicas, int32_t rate, int *R)
+{
+    if (!h) return mc_fail(nullptr, DQMC_ERR_INVALID, std::string(fn) + ": null handle");
+    if (n_replicas < 0 || rate < 0)
+        return mc_fail(h, DQMC_ERR_INVALID, std::string(fn) + ": n_replicas and rate must be >= 0 (0 = off)");
+    *R = n_replicas >= 2 ? n_replicas : 0;
+    if (*R && h->W % *R != 0)
+        return mc_fail(h, DQMC_ERR_INVALID, std::string(fn) + ": n_walkers must be a multiple of n_replicas");
+    return 0;
+}
+
+template <typename H, typename Out>
+static int mc_get_exchange_stats(H *h, const char *fn, int32_t walker, Out *out)
+{
+    if (int rc = mc_walker(h, walker, fn)) return rc;
+    if (!out) return mc_fail(h, DQMC_ERR_INVALID, std::string(fn) + ": null out");
+    MCHK(hipSetDevice(h->device));
+    const auto &t = h->xch;
+    long long prop = 0, acc = 0;
+    int label = 0;
+    int rc = 0;
+    if (t.sgn && ((rc = mc_get(h, t.prop, 0, walker, &prop)) || (rc = mc_get(h, t.acc, 0, walker, &acc)) ||
+                  (rc = mc_get(h, t.replica, 0, walker, &label))))
+        return rc;
+    out->prop_exchange = prop;
+    out->acc_exchange = acc;
+    out->replica = label;
+    out->rounds = t.cursor;
+    return DQMC_OK;
+}

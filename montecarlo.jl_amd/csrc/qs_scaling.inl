@@ -29,9 +29,8 @@ struct ScalingArgs {
     double inv;                     // 1 / (N 2^120)
     double *sS;                     // [8][W]
     long long *n_meas;              // [W]
-    double *bxs, *bx2, *bxy, *bc;   // the scaling section of the binner (bxs == nullptr: binner off):
-                                    // [L][1 + n_k][W], the same, [L][n_k][W], [L - 1][n_k][2][W]
-    int lmax, top;                  // trailing 1-bits of the push count (capped at top), the last level
+    mc_bin_arg bin;                 // the scaling section of the binner: [L][1 + n_k][W], the same, [L][n_k][W],
+                                    // [L - 1][n_k][2][W]
 };
 
 static inline size_t scaling_lds_bytes(int n_k) { return (size_t)n_k * 2 * SC_SLOTS * sizeof(unsigned long long); }
@@ -40,43 +39,6 @@ static inline int scaling_shift(int q)  // the largest s with q 2^s <= SC_SLOTS 
     int s = 0;
     while ((q << (s + 1)) <= SC_SLOTS) ++s;
     return s;
-}
-
-// The push of pair k with the values (a, b) = (M2, S_k): elements [M2, S_0 ..], pair k = (element 0, element 1 + k),
-// state [level][element][walker].  The pairs of a walker share nothing they write: each has its own element, its own
-// cross sum and its own copy of M2's compressor (the copies hold the same values; pair 0 alone adds M2 to x_sum and
-// x2_sum), as the FSS section of the Ising binner has it (ising_fss.inl).
-__device__ __forceinline__ void qs_scaling_bin_push(const ScalingArgs &f, int W, int w, int k, double a, double b)
-{
-    const size_t sW = (size_t)W, ne = (size_t)(1 + f.n_k), np = (size_t)f.n_k;
-    size_t ie = (size_t)(1 + k) * sW + w, i0 = (size_t)w, ip = (size_t)k * sW + w, ic = (size_t)k * 2 * sW + w;
-    for (int l = 0;; ++l, ie += ne * sW, i0 += ne * sW, ip += np * sW, ic += 2 * np * sW) {
-        const bool last = l == f.lmax;
-        const double s1 = f.bxs[ie], s2 = f.bx2[ie], p = f.bxy[ip];  // a level's values are requested together
-        double ca = 0.0, cb = 0.0, t1 = 0.0, t2 = 0.0;
-        if (!last) {
-            ca = f.bc[ic];
-            cb = f.bc[ic + sW];
-        }
-        if (k == 0) {
-            t1 = f.bxs[i0];
-            t2 = f.bx2[i0];
-        }
-        f.bxs[ie] = s1 + b;
-        f.bx2[ie] = s2 + b * b;
-        f.bxy[ip] = p + a * b;
-        if (k == 0) {
-            f.bxs[i0] = t1 + a;
-            f.bx2[i0] = t2 + a * a;
-        }
-        if (last) break;
-        a = 0.5 * (ca + a);
-        b = 0.5 * (cb + b);
-    }
-    if (f.lmax < f.top) {  // (the top level has no compressor)
-        f.bc[ic] = a;
-        f.bc[ic + sW] = b;
-    }
 }
 
 // blockDim.x == THREADS, dynamic LDS scaling_lds_bytes(n_k); 1 <= n_k <= 8 and every state below q (the host's to keep)
@@ -143,9 +105,9 @@ __global__ __launch_bounds__(THREADS) void qs_scaling_kernel(DevState s, Scaling
             const long long n = f.n_meas[w];
             f.n_meas[w] = n + 1;
         }
-        if (f.bxs) {  // m2 as qs_measure_slot and the sweep kernel form it: the value the first section gets
+        if (f.bin.xs) {  // elements [M2, S_0 ..], pair k = (M2, S_k); m2 as qs_measure_slot and the sweep kernel form it
             const double x = (double)s.Mx[w] * Q30_INV, y = (double)s.My[w] * Q30_INV;
-            qs_scaling_bin_push(f, W, w, k, x * x + y * y, v);
+            mc_bin_push_shared(f.bin, (size_t)(1 + f.n_k), (size_t)f.n_k, W, w, k, x * x + y * y, v);
         }
     }
 }

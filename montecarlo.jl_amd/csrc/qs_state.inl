@@ -2,7 +2,7 @@
 // flavor"): what mc_state.inl needs to know about a dqmc_qs_handle.  Included by qstate.hip behind the handle.  No kernel.
 #include "mc_state.inl"
 
-static void mc_state_config(const dqmc_qs_handle *h, mc_blob::Config *c)
+static void mc_state_config(dqmc_qs_handle *h, mc_blob::Config *c)
 {
     c->kind = mc_blob::KIND_QSTATE;
     c->n_sites = h->N;
@@ -19,10 +19,6 @@ static void mc_state_config(const dqmc_qs_handle *h, mc_blob::Config *c)
     c->n_k = h->sc.n_k;
     c->n_dir = h->st.n_dir;
     c->n_classes = h->st.n_c;
-    const mc_bin_section *sec[mc_blob::N_SEC] = {h->bin.on ? &h->bin : nullptr, h->sc.bin.xs ? &h->sc.bin : nullptr,
-                                                 h->st.bin.xs ? &h->st.bin : nullptr};
-    for (int s = 0; s < mc_blob::N_SEC; ++s)
-        if (sec[s]) c->bin[s] = {1, sec[s]->L, sec[s]->n_elem, sec[s]->n_pairs, sec[s]->n_comp, h->bin.cap};
     c->hash_neighs = mc_hash(h->nbr_h);
     c->hash_bonds = h->hash_bonds;
     c->hash_energy = mc_hash(h->e_h);
@@ -72,33 +68,9 @@ static mc_state_slot mc_state_slot_of(dqmc_qs_handle *h, uint32_t tag)
     case mc_blob::TAG_ST_N_MEAS: p = h->st.n_meas; break;
     case mc_blob::TAG_ST_LAST_I: p = h->st.sI; break;
     case mc_blob::TAG_ST_LAST_K: p = h->st.sK; break;
-    default:
-        if (tag >= mc_blob::TAG_BIN && tag < mc_blob::TAG_BIN + 4 * mc_blob::N_SEC) {
-            const int sec = (int)(tag - mc_blob::TAG_BIN) / 4;
-            const mc_bin_section &b = sec == mc_blob::SEC_MAIN ? (const mc_bin_section &)h->bin
-                                                               : (sec == mc_blob::SEC_SCALING ? h->sc.bin : h->st.bin);
-            double *const a[4] = {b.xs, b.x2, b.xy, b.c};
-            p = a[(tag - mc_blob::TAG_BIN) & 3];
-        }
     }
     s.dev = p;
     return s;
-}
-
-static void mc_state_host_get(const dqmc_qs_handle *h, uint64_t v[mc_blob::HOST_WORDS])
-{
-    v[mc_blob::SEC_MAIN] = (uint64_t)h->bin.T;
-    v[mc_blob::SEC_SCALING] = (uint64_t)h->sc.bin.T;
-    v[mc_blob::SEC_STIFFNESS] = (uint64_t)h->st.bin.T;
-    v[mc_blob::N_SEC] = h->xch.cursor;
-}
-
-static void mc_state_host_set(dqmc_qs_handle *h, const uint64_t v[mc_blob::HOST_WORDS])
-{
-    h->bin.T = (int64_t)v[mc_blob::SEC_MAIN];
-    h->sc.bin.T = (int64_t)v[mc_blob::SEC_SCALING];
-    h->st.bin.T = (int64_t)v[mc_blob::SEC_STIFFNESS];
-    h->xch.cursor = v[mc_blob::N_SEC];
 }
 
 extern "C" {

@@ -27,9 +27,8 @@ struct StiffnessArgs {
     double *sT, *sJ, *sJ2;                 // [4][W]
     long long *n_meas;                     // [W]
     long long *sI, *sK;                    // [8][W]: the class sums of the last sample
-    double *bxs, *bx2, *bxy, *bc;          // the stiffness section of the binner (bxs == nullptr: binner off):
-                                           // [L][2 n_dir][W], the same, [L][n_dir][W], [L - 1][2 n_dir][W]
-    int lmax, top;                         // trailing 1-bits of the push count (capped at top), the last level
+    mc_bin_arg bin;                        // the stiffness section of the binner: [L][2 n_dir][W], the same,
+                                           // [L][n_dir][W], [L - 1][2 n_dir][W]
 };
 
 // d1 and d2 (q int64 each), 4 x 16 wave partials, 16 totals, the configuration words: 18 KiB at q = 64 and N = 16384
@@ -40,31 +39,31 @@ static inline size_t stiffness_lds_bytes(int q, int Nw)
 
 // The push of pair p with the values (a, b) = (T_p, J2_p): elements [T_0, J2_0, T_1, J2_1 ..], pair p = (2 p, 2 p + 1),
 // state [level][element][walker].  The pairs of a walker share nothing: each lane has its two elements, its cross sum
-// and its two compressor values.  The level scheme is qs_scaling_bin_push's.
-__device__ __forceinline__ void qs_stiffness_bin_push(const StiffnessArgs &f, int W, int w, int p, double a, double b)
+// and its two compressor values.  The level scheme is mc_bin_push_shared's (mc_bin_device.h).
+__device__ __forceinline__ void qs_stiffness_bin_push(const mc_bin_arg &f, int n_dir, int W, int w, int p, double a, double b)
 {
-    const size_t sW = (size_t)W, ne = (size_t)(2 * f.n_dir), np = (size_t)f.n_dir;
+    const size_t sW = (size_t)W, ne = (size_t)(2 * n_dir), np = (size_t)n_dir;
     size_t ie = (size_t)(2 * p) * sW + w, ip = (size_t)p * sW + w;
     for (int l = 0;; ++l, ie += ne * sW, ip += np * sW) {
         const bool last = l == f.lmax;
-        const double a1 = f.bxs[ie], b1 = f.bxs[ie + sW], a2 = f.bx2[ie], b2 = f.bx2[ie + sW], pr = f.bxy[ip];
+        const double a1 = f.xs[ie], b1 = f.xs[ie + sW], a2 = f.x2[ie], b2 = f.x2[ie + sW], pr = f.xy[ip];
         double ca = 0.0, cb = 0.0;
         if (!last) {
-            ca = f.bc[ie];
-            cb = f.bc[ie + sW];
+            ca = f.c[ie];
+            cb = f.c[ie + sW];
         }
-        f.bxs[ie] = a1 + a;
-        f.bxs[ie + sW] = b1 + b;
-        f.bx2[ie] = a2 + a * a;
-        f.bx2[ie + sW] = b2 + b * b;
-        f.bxy[ip] = pr + a * b;
+        f.xs[ie] = a1 + a;
+        f.xs[ie + sW] = b1 + b;
+        f.x2[ie] = a2 + a * a;
+        f.x2[ie + sW] = b2 + b * b;
+        f.xy[ip] = pr + a * b;
         if (last) break;
         a = 0.5 * (ca + a);
         b = 0.5 * (cb + b);
     }
     if (f.lmax < f.top) {  // (the top level has no compressor; the compressor's [level][element][walker] is the sums')
-        f.bc[ie] = a;
-        f.bc[ie + sW] = b;
+        f.c[ie] = a;
+        f.c[ie + sW] = b;
     }
 }
 
@@ -166,6 +165,6 @@ __global__ __launch_bounds__(THREADS) void qs_stiffness_kernel(DevState s, Stiff
             const long long n = f.n_meas[w];
             f.n_meas[w] = n + 1;
         }
-        if (f.bxs) qs_stiffness_bin_push(f, W, w, mu, Tv, J2);
+        if (f.bin.xs) qs_stiffness_bin_push(f.bin, f.n_dir, W, w, mu, Tv, J2);
     }
 }

@@ -30,6 +30,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -37,6 +38,7 @@
 
 #include "../../include/dqmc_hip.h"
 #include "kernels.h"
+#include "mc_bin_device.h"
 #include "mc_host.h"
 
 namespace dqmc_qs {
@@ -358,7 +360,7 @@ __global__ __launch_bounds__(THREADS) void qs_exchange_kernel(DevState s, Exchan
     if (measure && tid == 0) qs_measure_slot(s, ba, a, E, Mx, My);
 }
 
-// the scaling measurement: ScalingArgs, qs_scaling_bin_push, qs_scaling_kernel
+// the scaling measurement: ScalingArgs, qs_scaling_kernel
 #include "qs_scaling.inl"
 
 // the stiffness measurement: StiffnessArgs, qs_stiffness_bin_push, qs_stiffness_kernel
@@ -531,9 +533,9 @@ struct dqmc_qs_handle : mc_handle_base {
         mc_bin_section bin;
         uint64_t hash_twist = 0, hash = 0;     // of (d1_q30, d2_q30) and of (slot_class, x) as dqmc_qs_set_stiffness got them
     } st;
+    // every binner section, at its index in the checkpoint blob (mc_blob.h: SEC_MAIN, SEC_SCALING, SEC_STIFFNESS)
+    std::array<mc_bin_section *, 3> sections() { return {&bin, &sc.bin, &st.bin}; }
 };
-
-static const int64_t QS_BIN_DEFAULT_CAPACITY = 100000;  // as dqmc_mc_binner_enable
 
 // the binner as the kernels see it at push count T (xs == nullptr: off)
 static BinArgs qs_bin_arg(const dqmc_qs_handle *h, int64_t T)
@@ -621,25 +623,17 @@ static int qs_launch_observables(dqmc_qs_handle *h, int walker)
     return 0;
 }
 
-static void qs_bin_free(dqmc_qs_handle *h)  // every section; the binner is off afterwards
+// every section the handle's features call for, at L levels each: the one place that knows their shapes
+static int qs_bin_alloc(dqmc_qs_handle *h, int L)
 {
-    h->st.bin.free(h);
-    h->sc.bin.free(h);
-    h->bin.free(h);
-    h->bin.on = false;
-    h->bin.cap = 0;
+    const int n_k = h->sc.n_k, n_dir = h->st.n_dir;
+    if (int rc = h->bin.alloc(h, 6, 3, 6, L)) return rc;
+    if (n_k > 0)
+        if (int rc = h->sc.bin.alloc(h, 1 + n_k, n_k, 2 * n_k, L)) return rc;
+    return n_dir > 0 ? h->st.bin.alloc(h, 2 * n_dir, n_dir, 2 * n_dir, L) : 0;
 }
 
-// the scaling section for the binner as it stands (nothing unless both are on)
-static int qs_scaling_bin_alloc(dqmc_qs_handle *h)
-{
-    dqmc_qs_handle::Scaling &f = h->sc;
-    f.bin.free(h);
-    if (!h->bin.on || f.n_k < 1) return 0;
-    return f.bin.alloc(h, 1 + f.n_k, f.n_k, 2 * f.n_k, h->bin.L);
-}
-
-static int qs_scaling_clear(dqmc_qs_handle *h)  // the sums and the section's state
+static int qs_scaling_clear(dqmc_qs_handle *h)  // the sums (the section: mc_bin_clear)
 {
     dqmc_qs_handle::Scaling &f = h->sc;
     const size_t W = h->W;
@@ -647,7 +641,7 @@ static int qs_scaling_clear(dqmc_qs_handle *h)  // the sums and the section's st
         MCHK(hipMemsetAsync(f.sS, 0, (size_t)SC_MAX_K * W * 8, h->stream));
         MCHK(hipMemsetAsync(f.n_meas, 0, W * 8, h->stream));
     }
-    return f.bin.clear(h);
+    return 0;
 }
 
 // the scaling measurement of the sweep whose last kernel has just been launched, and its push
@@ -660,31 +654,15 @@ static int qs_launch_scaling(dqmc_qs_handle *h)
     a.inv = 1.0 / std::ldexp((double)h->N, 120);  // N 2^120 is exact, one rounding
     a.sS = f.sS;
     a.n_meas = f.n_meas;
-    if (f.bin.xs) {
-        if (int rc = f.bin.next_lmax(h, "dqmc_qs_sweep", &a.lmax)) return rc;
-        a.bxs = f.bin.xs;
-        a.bx2 = f.bin.x2;
-        a.bxy = f.bin.xy;
-        a.bc = f.bin.c;
-        a.top = f.bin.L - 1;
-    }
+    if (int rc = f.bin.push_arg(h, "dqmc_qs_sweep", &a.bin)) return rc;
     hipLaunchKernelGGL(qs_scaling_kernel, dim3(h->W), dim3(THREADS), scaling_lds_bytes(f.n_k), h->stream, h->d, a,
                        (const int4 *)f.cq, (const int4 *)f.sq, (const int2 *)h->cs_q30);
     MCHK(hipGetLastError());
-    if (f.bin.xs) f.bin.T += 1;
+    f.bin.pushed();
     return 0;
 }
 
-// the stiffness section for the binner as it stands (nothing unless both are on)
-static int qs_stiffness_bin_alloc(dqmc_qs_handle *h)
-{
-    dqmc_qs_handle::Stiffness &f = h->st;
-    f.bin.free(h);
-    if (!h->bin.on || f.n_dir < 1) return 0;
-    return f.bin.alloc(h, 2 * f.n_dir, f.n_dir, 2 * f.n_dir, h->bin.L);
-}
-
-static int qs_stiffness_clear(dqmc_qs_handle *h)  // the sums, the last sample and the section's state
+static int qs_stiffness_clear(dqmc_qs_handle *h)  // the sums and the last sample (the section: mc_bin_clear)
 {
     dqmc_qs_handle::Stiffness &f = h->st;
     const size_t W = h->W;
@@ -693,7 +671,7 @@ static int qs_stiffness_clear(dqmc_qs_handle *h)  // the sums, the last sample a
         for (long long *p : {f.sI, f.sK}) MCHK(hipMemsetAsync(p, 0, (size_t)ST_MAX_CLASSES * W * 8, h->stream));
         MCHK(hipMemsetAsync(f.n_meas, 0, W * 8, h->stream));
     }
-    return f.bin.clear(h);
+    return 0;
 }
 
 // the stiffness measurement of the sweep whose last kernel has just been launched, and its push
@@ -710,18 +688,11 @@ static int qs_launch_stiffness(dqmc_qs_handle *h)
     a.n_meas = f.n_meas;
     a.sI = f.sI;
     a.sK = f.sK;
-    if (f.bin.xs) {
-        if (int rc = f.bin.next_lmax(h, "dqmc_qs_sweep", &a.lmax)) return rc;
-        a.bxs = f.bin.xs;
-        a.bx2 = f.bin.x2;
-        a.bxy = f.bin.xy;
-        a.bc = f.bin.c;
-        a.top = f.bin.L - 1;
-    }
+    if (int rc = f.bin.push_arg(h, "dqmc_qs_sweep", &a.bin)) return rc;
     hipLaunchKernelGGL(qs_stiffness_kernel, dim3(h->W), dim3(THREADS), stiffness_lds_bytes(h->q, h->Nw), h->stream, h->d, a,
                        (const int4 *)h->nbr_site, (const int2 *)f.cls, (const long long *)f.d1, (const long long *)f.d2);
     MCHK(hipGetLastError());
-    if (f.bin.xs) f.bin.T += 1;
+    f.bin.pushed();
     return 0;
 }
 
@@ -1059,21 +1030,17 @@ int dqmc_qs_reset_accumulators(dqmc_qs_handle *h)
     const size_t W = h->W;
     for (double *p : {d.sE, d.sE2, d.sM, d.sM2, d.sM4}) MCHK(hipMemsetAsync(p, 0, W * 8, h->stream));
     for (long long *p : {d.n_meas, d.n_series}) MCHK(hipMemsetAsync(p, 0, W * 8, h->stream));
-    if (int rc = h->bin.clear(h)) return rc;
     if (int rc = qs_scaling_clear(h)) return rc;
     if (int rc = qs_stiffness_clear(h)) return rc;
+    if (int rc = mc_bin_clear(h)) return rc;
     MCHK(hipStreamSynchronize(h->stream));
     return DQMC_OK;
 }
 
 int dqmc_qs_set_exchange(dqmc_qs_handle *h, int32_t n_replicas, int32_t rate)
 {
-    if (!h) return mc_fail(nullptr, DQMC_ERR_INVALID, "dqmc_qs_set_exchange: null handle");
-    if (n_replicas < 0 || rate < 0)
-        return mc_fail(h, DQMC_ERR_INVALID, "dqmc_qs_set_exchange: n_replicas and rate must be >= 0 (0 = off)");
-    const int R = n_replicas >= 2 ? n_replicas : 0;
-    if (R && h->W % R != 0)
-        return mc_fail(h, DQMC_ERR_INVALID, "dqmc_qs_set_exchange: n_walkers must be a multiple of n_replicas");
+    int R = 0;
+    if (int rc = mc_exchange_ladders(h, "dqmc_qs_set_exchange", n_replicas, rate, &R)) return rc;
     const std::vector<int64_t> e(h->e_h.begin(), h->e_h.end());
     const int J = mc_tables::qs_exchange_bits(h->n_bonds, e.data(), h->q);
     if (R && J > MAX_XJ)
@@ -1125,91 +1092,49 @@ int dqmc_qs_exchange(dqmc_qs_handle *h)
 
 int dqmc_qs_get_exchange_stats(dqmc_qs_handle *h, int32_t walker, dqmc_qs_exchange_stats *out)
 {
-    if (int rc = mc_walker(h, walker, "dqmc_qs_get_exchange_stats")) return rc;
-    if (!out) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_qs_get_exchange_stats: null out");
-    MCHK(hipSetDevice(h->device));
-    const dqmc_qs_handle::Tempering &t = h->xch;
-    long long prop = 0, acc = 0;
-    int label = 0;
-    int rc = 0;
-    if (t.sgn && ((rc = mc_get(h, t.prop, 0, walker, &prop)) || (rc = mc_get(h, t.acc, 0, walker, &acc)) ||
-                  (rc = mc_get(h, t.replica, 0, walker, &label))))
-        return rc;
-    out->prop_exchange = prop;
-    out->acc_exchange = acc;
-    out->replica = label;
-    out->rounds = t.cursor;
-    return DQMC_OK;
+    return mc_get_exchange_stats(h, "dqmc_qs_get_exchange_stats", walker, out);
 }
-
-// (in a function whose handle is `h`)
-#define QS_BIN_OK(h, fn)                                                                   \
-    if (!(h)) return mc_fail(nullptr, DQMC_ERR_INVALID, std::string(fn) + ": null handle"); \
-    if (!(h)->bin.on) return mc_fail((h), DQMC_ERR_STATE, std::string(fn) + ": the binner is not enabled")
 
 int dqmc_qs_binner_enable(dqmc_qs_handle *h, int64_t capacity)
 {
-    if (!h) return mc_fail(nullptr, DQMC_ERR_INVALID, "dqmc_qs_binner_enable: null handle");
-    if (capacity < 0) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_qs_binner_enable: capacity must be positive (0 selects 100000)");
-    if (capacity == 0) capacity = QS_BIN_DEFAULT_CAPACITY;
-    if (capacity > ((int64_t)1 << 40)) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_qs_binner_enable: capacity above 2^40");
+    if (int rc = mc_binner_capacity(h, "dqmc_qs_binner_enable", &capacity)) return rc;
     MCHK(hipSetDevice(h->device));
     MCHK(hipStreamSynchronize(h->stream));
-    qs_bin_free(h);
-    dqmc_qs_handle::Binner &b = h->bin;
-    if (int rc = b.alloc(h, 6, 3, 6, mc_tables::bin_levels(capacity))) return rc;
-    MCHK(hipStreamSynchronize(h->stream));
-    b.on = true;
-    b.cap = capacity;
-    if (int rc = qs_scaling_bin_alloc(h)) {  // the scaling section, when the feature is on
-        qs_bin_free(h);
-        return rc;
-    }
-    if (int rc = qs_stiffness_bin_alloc(h)) {  // the stiffness section, when the feature is on
-        qs_bin_free(h);
+    mc_bin_free(h);
+    if (int rc = qs_bin_alloc(h, mc_tables::bin_levels(capacity))) {  // with the sections of the features that are on
+        mc_bin_free(h);
         return rc;
     }
     MCHK(hipStreamSynchronize(h->stream));
+    h->bin.on = true;
+    h->bin.cap = capacity;
     return DQMC_OK;
 }
 
 int dqmc_qs_binner_size(dqmc_qs_handle *h, int32_t *n_levels, int64_t *n_pushed)
 {
-    QS_BIN_OK(h, "dqmc_qs_binner_size");
-    if (n_levels) *n_levels = h->bin.L;
-    if (n_pushed) *n_pushed = h->bin.T;
-    return DQMC_OK;
+    return mc_binner_size(h, "dqmc_qs_binner_size", n_levels, n_pushed);
 }
 
 int dqmc_qs_binner_reliable_level(dqmc_qs_handle *h, int32_t *level)
 {
-    QS_BIN_OK(h, "dqmc_qs_binner_reliable_level");
-    if (!level) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_qs_binner_reliable_level: null level");
-    *level = mc_tables::bin_reliable(h->bin.T, h->bin.L);
-    return DQMC_OK;
+    return mc_binner_reliable_level(h, "dqmc_qs_binner_reliable_level", level);
 }
 
 int dqmc_qs_binner_get_level(dqmc_qs_handle *h, int32_t walker, int32_t level, double x_sum[6], double x2_sum[6],
                              double xy_sum[3], int64_t *count)
 {
-    QS_BIN_OK(h, "dqmc_qs_binner_get_level");
-    if (int rc = mc_walker(h, walker, "dqmc_qs_binner_get_level")) return rc;
-    return h->bin.level_sums(h, "dqmc_qs_binner_get_level", walker, level, x_sum, x2_sum, xy_sum, count);
+    return mc_binner_get_level(h, "dqmc_qs_binner_get_level", mc_blob::SEC_MAIN, nullptr, walker, level, x_sum, x2_sum, xy_sum,
+                               count);
 }
 
 int dqmc_qs_binner_finish(dqmc_qs_handle *h, int32_t walker, int32_t level, dqmc_qs_binned *out)
 {
-    QS_BIN_OK(h, "dqmc_qs_binner_finish");
-    if (int rc = mc_walker(h, walker, "dqmc_qs_binner_finish")) return rc;
-    if (!out) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_qs_binner_finish: null out");
-    return h->bin.finish(h, "dqmc_qs_binner_finish", walker, level, false, out->mean, out->varN, out->varN0, out->tau,
-                         out->covN, &out->count, &out->level);
+    return mc_binner_finish(h, "dqmc_qs_binner_finish", mc_blob::SEC_MAIN, nullptr, false, walker, level, out);
 }
 
-#define QS_SCALING_BIN_OK(h, fn)                                                                      \
-    QS_BIN_OK(h, fn);                                                                                 \
-    if (!(h)->sc.bin.xs)                                                                              \
-    return mc_fail((h), DQMC_ERR_STATE, std::string(fn) + ": the scaling measurement is off (dqmc_qs_set_scaling first)")
+static const char *const QS_SCALING_OFF = ": the scaling measurement is off (dqmc_qs_set_scaling first)";
+static const char *const QS_STIFFNESS_OFF = ": the stiffness measurement is off (dqmc_qs_set_stiffness first)";
 
 int dqmc_qs_set_scaling(dqmc_qs_handle *h, int32_t n_k, const int32_t *cos_q30, const int32_t *sin_q30)
 {
@@ -1265,29 +1190,18 @@ int dqmc_qs_get_scaling(dqmc_qs_handle *h, int32_t walker, dqmc_qs_scaling *out)
 int dqmc_qs_scaling_binner_get_level(dqmc_qs_handle *h, int32_t walker, int32_t level, double *x_sum, double *x2_sum,
                                      double *xy_sum, int64_t *count)
 {
-    QS_SCALING_BIN_OK(h, "dqmc_qs_scaling_binner_get_level");
-    if (int rc = mc_walker(h, walker, "dqmc_qs_scaling_binner_get_level")) return rc;
-    return h->sc.bin.level_sums(h, "dqmc_qs_scaling_binner_get_level", walker, level, x_sum, x2_sum, xy_sum, count);
+    return mc_binner_get_level(h, "dqmc_qs_scaling_binner_get_level", mc_blob::SEC_SCALING, QS_SCALING_OFF, walker, level,
+                               x_sum, x2_sum, xy_sum, count);
 }
 
 int dqmc_qs_scaling_binner_finish(dqmc_qs_handle *h, int32_t walker, int32_t level, dqmc_qs_scaling_binned *out)
 {
-    QS_SCALING_BIN_OK(h, "dqmc_qs_scaling_binner_finish");
-    if (int rc = mc_walker(h, walker, "dqmc_qs_scaling_binner_finish")) return rc;
-    if (!out) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_qs_scaling_binner_finish: null out");
-    dqmc_qs_scaling_binned r{};  // (entries past the section's elements stay 0)
-    if (int rc = h->sc.bin.finish(h, "dqmc_qs_scaling_binner_finish", walker, level, true, r.mean, r.varN, r.varN0, r.tau,
-                                  r.covN, &r.count, &r.level))
+    if (int rc = mc_binner_finish(h, "dqmc_qs_scaling_binner_finish", mc_blob::SEC_SCALING, QS_SCALING_OFF, true, walker, level,
+                                  out))
         return rc;
-    r.n_k = h->sc.n_k;
-    *out = r;
+    out->n_k = h->sc.n_k;
     return DQMC_OK;
 }
-
-#define QS_STIFFNESS_BIN_OK(h, fn)                                                                    \
-    QS_BIN_OK(h, fn);                                                                                 \
-    if (!(h)->st.bin.xs)                                                                              \
-    return mc_fail((h), DQMC_ERR_STATE, std::string(fn) + ": the stiffness measurement is off (dqmc_qs_set_stiffness first)")
 
 int dqmc_qs_set_stiffness(dqmc_qs_handle *h, int32_t n_dir, int32_t n_classes, const int8_t *slot_class,
                           const int64_t *d1_q30, const int64_t *d2_q30, const double *x)
@@ -1378,22 +1292,16 @@ int dqmc_qs_get_stiffness_sample(dqmc_qs_handle *h, int32_t walker, int64_t I[8]
 int dqmc_qs_stiffness_binner_get_level(dqmc_qs_handle *h, int32_t walker, int32_t level, double *x_sum, double *x2_sum,
                                        double *xy_sum, int64_t *count)
 {
-    QS_STIFFNESS_BIN_OK(h, "dqmc_qs_stiffness_binner_get_level");
-    if (int rc = mc_walker(h, walker, "dqmc_qs_stiffness_binner_get_level")) return rc;
-    return h->st.bin.level_sums(h, "dqmc_qs_stiffness_binner_get_level", walker, level, x_sum, x2_sum, xy_sum, count);
+    return mc_binner_get_level(h, "dqmc_qs_stiffness_binner_get_level", mc_blob::SEC_STIFFNESS, QS_STIFFNESS_OFF, walker, level,
+                               x_sum, x2_sum, xy_sum, count);
 }
 
 int dqmc_qs_stiffness_binner_finish(dqmc_qs_handle *h, int32_t walker, int32_t level, dqmc_qs_stiffness_binned *out)
 {
-    QS_STIFFNESS_BIN_OK(h, "dqmc_qs_stiffness_binner_finish");
-    if (int rc = mc_walker(h, walker, "dqmc_qs_stiffness_binner_finish")) return rc;
-    if (!out) return mc_fail(h, DQMC_ERR_INVALID, "dqmc_qs_stiffness_binner_finish: null out");
-    dqmc_qs_stiffness_binned r{};  // (entries past the section's elements stay 0)
-    if (int rc = h->st.bin.finish(h, "dqmc_qs_stiffness_binner_finish", walker, level, false, r.mean, r.varN, r.varN0, r.tau,
-                                  r.covN, &r.count, &r.level))
+    if (int rc = mc_binner_finish(h, "dqmc_qs_stiffness_binner_finish", mc_blob::SEC_STIFFNESS, QS_STIFFNESS_OFF, false, walker,
+                                  level, out))
         return rc;
-    r.n_dir = h->st.n_dir;
-    *out = r;
+    out->n_dir = h->st.n_dir;
     return DQMC_OK;
 }
 

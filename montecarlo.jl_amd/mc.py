@@ -124,12 +124,58 @@ def _delta_var(grad, vx, vy, cov):
     return max(var, 0.0) if var == var else var
 
 
+def pool_walkers(method, betas, walker, walkers, per_walker, derived_tau=None):
+    """The binned results of one walker, or of several chains of equal beta pooled (MC.binned's docstring has the
+    formulas).  `walkers` None: the single `walker`, not pooled.  per_walker(w) gives (obs, count, level) of walker w,
+    obs = {name: entry or [entry, ..]} with entry = (mean, variance of the mean at `level`, the same at level 0, or None
+    for a derived observable, which is no time series); it is asked only once the walkers have passed the checks, which
+    raise ValueError under the calling `method`'s name.  Returns {name: pooled or [pooled, ..], "count", "level"} (count
+    and level of the first walker; they are the same for all), pooled = {mean, std_error, tau}, where a derived
+    observable gets tau = derived_tau, or no tau key for derived_tau None; pooling adds std_error_walkers (NaN for one
+    walker) to every entry and n_walkers to the result.  Needs no handle."""
+    pooled = walkers is not None
+    ws = [int(w) for w in walkers] if pooled else [walker]
+    if not ws:
+        raise ValueError("%s: no walker given" % method)
+    if any(betas[w] != betas[ws[0]] for w in ws):
+        raise ValueError("%s: the pooled walkers must share one beta" % method)
+    per = [per_walker(w) for w in ws]
+    W = float(len(ws))
+
+    def pool(entries):
+        means = np.array([e[0] for e in entries])
+        vl = float(np.sum([e[1] for e in entries]))
+        mean = float(means.sum() / W)
+        o = {"mean": mean, "std_error": (math.sqrt(max(vl, 0.0)) if vl == vl else vl) / W}
+        if entries[0][2] is not None:
+            with np.errstate(invalid="ignore", divide="ignore"):
+                o["tau"] = float(0.5 * (np.float64(vl) / np.sum([e[2] for e in entries]) - 1.0))
+        elif derived_tau is not None:
+            o["tau"] = derived_tau
+        if pooled:
+            o["std_error_walkers"] = (math.sqrt(float(((means - mean) ** 2).sum()) / (W * (W - 1.0)))
+                                      if W >= 2 else float("nan"))
+        return o
+
+    out = {"count": per[0][1], "level": per[0][2]}
+    for name, first in per[0][0].items():
+        if isinstance(first, list):
+            out[name] = [pool([p[0][name][k] for p in per]) for k in range(len(first))]
+        else:
+            out[name] = pool([p[0][name] for p in per])
+    if pooled:
+        out["n_walkers"] = len(ws)
+    return out
+
+
 class _MCBase:
     """What MC and qstate.QStateMC share: the handle of one engine's ABI family (`_abi`: "dqmc_mc_" / "dqmc_qs_", whose
-    create, destroy, last_error, seed, set_beta, rand_conf, sweep, reset_accumulators and synchronize have one shape),
-    the temperatures, the colouring argument and the run! loop.  A subclass has stats(walker) with acc_local and
-    prop_local."""
+    create, destroy, last_error, seed, set_beta, rand_conf, sweep, reset_accumulators, synchronize, the exchange calls
+    and the binner calls have one shape), the temperatures, the colouring argument, replica exchange, the binner's
+    sections and the run! loop.  A subclass has stats(walker) with acc_local and prop_local, and names the ctypes
+    struct of its exchange stats (`_ExchangeStats`)."""
     _abi = None
+    _ExchangeStats = None
 
     def _call(self, name, *args):
         self._c(getattr(lib(), self._abi + name)(self._h, *args))
@@ -220,6 +266,65 @@ class _MCBase:
 
     def synchronize(self):
         self._call("synchronize")
+
+    # ---- replica exchange
+    def set_exchange(self, n_replicas, rate):
+        """dqmc_*_set_exchange: ladders of n_replicas consecutive walkers (0 or 1: none), a round after every rate-th
+        sweep (0: none; the q-state engine runs it behind its cluster move and before its measurement); resets the
+        exchange cursor, the replica labels and the exchange counters"""
+        self._call("set_exchange", int(n_replicas), int(rate))
+        self.n_replicas, self.exchange_rate = int(n_replicas), int(rate)
+
+    def exchange(self):
+        """one exchange round by hand (dqmc_*_exchange), counted in the exchange stats, no measurement"""
+        self._call("exchange")
+
+    def exchange_stats(self, walker=0):
+        """prop_exchange and acc_exchange of the pair (walker, walker + 1), the label `replica` of the configuration
+        now in the slot, and `rounds` (the exchange cursor)"""
+        st = self._ExchangeStats()
+        self._call("get_exchange_stats", walker, C.byref(st))
+        return st
+
+    def replicas(self):
+        """the replica labels of all slots: replicas()[w] is the ladder-local index of the slot in which the
+        configuration now in slot w started"""
+        return np.array([self.exchange_stats(w).replica for w in range(self.n_walkers)], dtype=np.int64)
+
+    # ---- the binner: the main section and, with the `prefix` of their calls ("fss_", "scaling_", "stiffness_"), the
+    # sections of the measurements that have one
+    def enable_binning(self, capacity=None):
+        """a logarithmic binner (LogBinner) per walker over the engine's main elements - MC: [E, E2, |M|, M2], QStateMC:
+        [E, E2, |M|, M2, M2, M4] - (capacity None: 100000 measurements), pushed on the device where the measurement is
+        taken; enabling again starts anew.  A sweep() whose measurements would pass the capacity raises before
+        anything runs."""
+        self._call("binner_enable", 0 if capacity is None else int(capacity))
+        self._binning = 0 if capacity is None else int(capacity)
+
+    def binner_size(self):
+        """(levels, pushes so far)"""
+        L, T = C.c_int32(), C.c_int64()
+        self._call("binner_size", C.byref(L), C.byref(T))
+        return L.value, T.value
+
+    def binner_reliable_level(self):
+        lv = C.c_int32()
+        self._call("binner_reliable_level", C.byref(lv))
+        return lv.value
+
+    def _section_level(self, prefix, n_elem, n_pairs, walker, level):
+        """(x_sum[n_elem], x2_sum[n_elem], xy_sum[n_pairs], count) of one level of one walker of a section"""
+        xs, x2, xy, n = np.zeros(max(n_elem, 1)), np.zeros(max(n_elem, 1)), np.zeros(max(n_pairs, 1)), C.c_int64()
+        dp = C.POINTER(C.c_double)
+        self._call(prefix + "binner_get_level", walker, level, xs.ctypes.data_as(dp), x2.ctypes.data_as(dp),
+                   xy.ctypes.data_as(dp), C.byref(n))
+        return xs[:n_elem], x2[:n_elem], xy[:n_pairs], n.value
+
+    def _section_finish(self, prefix, Struct, walker, level):
+        """the section's dqmc_*_binned (`Struct`) of one walker at `level` (None: the reliable level)"""
+        out = Struct()
+        self._call(prefix + "binner_finish", walker, -1 if level is None else int(level), C.byref(out))
+        return out
 
     # ---- the loop
     def sweep(self, n=1):
@@ -402,6 +507,7 @@ class MC(_MCBase):
     dqmc_qs_* with its own kernels.  With an IsingModel nothing changes."""
     _abi = "dqmc_mc_"
     _flavor = "mc_ising"
+    _ExchangeStats = McExchangeStats
 
     def __new__(cls, model, *args, **kwargs):
         if cls is MC and getattr(model, "is_qstate", False):
@@ -532,34 +638,12 @@ class MC(_MCBase):
         self._c(lib().dqmc_mc_get_global_stats(self._h, walker, C.byref(st)))
         return st
 
-    # ---- replica exchange
-    def set_exchange(self, n_replicas, rate):
-        """dqmc_mc_set_exchange: ladders of n_replicas consecutive walkers (0 or 1: none), a round after every rate-th
-        sweep (0: none); resets the exchange cursor, the replica labels and the exchange counters"""
-        self._c(lib().dqmc_mc_set_exchange(self._h, int(n_replicas), int(rate)))
-        self.n_replicas, self.exchange_rate = int(n_replicas), int(rate)
-
-    def exchange(self):
-        """one exchange round by hand (dqmc_mc_exchange), counted in the exchange stats, no measurement"""
-        self._c(lib().dqmc_mc_exchange(self._h))
-
-    def exchange_stats(self, walker=0):
-        """prop_exchange and acc_exchange of the pair (walker, walker + 1), the label `replica` of the configuration
-        now in the slot, and `rounds` (the exchange cursor)"""
-        st = McExchangeStats()
-        self._c(lib().dqmc_mc_get_exchange_stats(self._h, walker, C.byref(st)))
-        return st
-
+    # ---- replica exchange (set_exchange, exchange, exchange_stats, replicas: _MCBase)
     def exchange_fused(self):
         """True: sweep() runs its exchange rounds inside the sweep kernel (64 % n_replicas == 0)"""
         f = C.c_int32()
         self._c(lib().dqmc_mc_exchange_fused(self._h, C.byref(f)))
         return bool(f.value)
-
-    def replicas(self):
-        """the replica labels of all slots: replicas()[w] is the ladder-local index of the slot in which the
-        configuration now in slot w started"""
-        return np.array([self.exchange_stats(w).replica for w in range(self.n_walkers)], dtype=np.int64)
 
     # ---- the local update
     def set_update(self, kind, colouring=None):
@@ -609,38 +693,15 @@ class MC(_MCBase):
                 "Energy": {"E": E, "E2": E2, "e": E * invN, "C": beta * beta * invN * (E2 - E * E)},
                 "n_meas": int(n)}
 
-    # ---- error bars
-    def enable_binning(self, capacity=None):
-        """a LogBinner per walker over [E, E2, |M|, M2] (capacity None: 100000 measurements); enabling again starts
-        anew.  A sweep() whose measurements would pass the capacity raises before anything runs."""
-        self._c(lib().dqmc_mc_binner_enable(self._h, 0 if capacity is None else int(capacity)))
-        self._binning = 0 if capacity is None else int(capacity)
-
-    def binner_size(self):
-        """(levels, pushes so far)"""
-        L, T = C.c_int32(), C.c_int64()
-        self._c(lib().dqmc_mc_binner_size(self._h, C.byref(L), C.byref(T)))
-        return L.value, T.value
-
-    def binner_reliable_level(self):
-        lv = C.c_int32()
-        self._c(lib().dqmc_mc_binner_reliable_level(self._h, C.byref(lv)))
-        return lv.value
-
+    # ---- error bars (enable_binning, binner_size, binner_reliable_level: _MCBase)
     def binner_level(self, walker, level):
         """(x_sum[4], x2_sum[4], xy_sum[2], count) of one level of one walker: elements [E, E2, |M|, M2], pairs
         (E, E2) and (|M|, M2)"""
-        xs, x2, xy, n = np.zeros(4), np.zeros(4), np.zeros(2), C.c_int64()
-        dp = C.POINTER(C.c_double)
-        self._c(lib().dqmc_mc_binner_get_level(self._h, walker, level, xs.ctypes.data_as(dp), x2.ctypes.data_as(dp),
-                                               xy.ctypes.data_as(dp), C.byref(n)))
-        return xs, x2, xy, n.value
+        return self._section_level("", 4, 2, walker, level)
 
     def binner_finish(self, walker=0, level=None):
         """dqmc_mc_binned of one walker at `level` (None: the reliable level)"""
-        out = McBinned()
-        self._c(lib().dqmc_mc_binner_finish(self._h, walker, -1 if level is None else int(level), C.byref(out)))
-        return out
+        return self._section_finish("", McBinned, walker, level)
 
     def _binned_walker(self, walker, level):
         """per observable (mean, variance of the mean at `level`, the same at level 0 or None) of one walker"""
@@ -669,31 +730,10 @@ class MC(_MCBase):
         have no tau.  `walkers=[...]` pools chains of equal beta: mean = sum_w mean_w / W, std_error =
         sqrt(sum_w var_w) / W (C and chi formed per walker first), tau from the summed variances, plus
         std_error_walkers = sqrt(sum_w (mean_w - mean)^2 / (W (W - 1))), which needs no binning."""
-        pooled = walkers is not None
-        ws = [int(w) for w in walkers] if pooled else [walker]
-        if not ws:
-            raise ValueError("binned: no walker given")
-        if any(self.betas[w] != self.betas[ws[0]] for w in ws):
-            raise ValueError("binned: the pooled walkers must share one beta")
-        per = [self._binned_walker(w, level) for w in ws]
-        count, lv = per[0][1], per[0][2]
-        W = float(len(ws))
-        out = {"Energy": {}, "Magn": {}, "count": count, "level": lv}
-        for group, names in (("Energy", ("E", "E2", "e", "C")), ("Magn", ("M", "M2", "m", "chi"))):
-            for k in names:
-                means = np.array([p[0][k][0] for p in per])
-                vl = float(np.sum([p[0][k][1] for p in per]))
-                mean = float(means.sum() / W)
-                o = {"mean": mean, "std_error": (math.sqrt(max(vl, 0.0)) if vl == vl else vl) / W}
-                if per[0][0][k][2] is not None:
-                    with np.errstate(invalid="ignore", divide="ignore"):
-                        o["tau"] = float(0.5 * (np.float64(vl) / np.sum([p[0][k][2] for p in per]) - 1.0))
-                if pooled:
-                    o["std_error_walkers"] = (math.sqrt(float(((means - mean) ** 2).sum()) / (W * (W - 1.0)))
-                                              if W >= 2 else float("nan"))
-                out[group][k] = o
-        if pooled:
-            out["n_walkers"] = len(ws)
+        p = pool_walkers("binned", self.betas, walker, walkers, lambda w: self._binned_walker(w, level))
+        out = {"Energy": {k: p.pop(k) for k in ("E", "E2", "e", "C")},
+               "Magn": {k: p.pop(k) for k in ("M", "M2", "m", "chi")}}
+        out.update(p)
         return out
 
     # ---- finite-size scaling
@@ -750,17 +790,11 @@ class MC(_MCBase):
         """(x_sum[2 + n_k], x2_sum[2 + n_k], xy_sum[1 + n_k], count) of one level of one walker of the binner's FSS
         section: elements [M2, M4, S_0 ..], pairs (M2, M4), (M2, S_0) .."""
         nk = 0 if self.k_vectors is None else len(self.k_vectors)
-        xs, x2, xy, n = np.zeros(2 + nk), np.zeros(2 + nk), np.zeros(1 + nk), C.c_int64()
-        dp = C.POINTER(C.c_double)
-        self._c(lib().dqmc_mc_fss_binner_get_level(self._h, walker, level, xs.ctypes.data_as(dp), x2.ctypes.data_as(dp),
-                                                   xy.ctypes.data_as(dp), C.byref(n)))
-        return xs, x2, xy, n.value
+        return self._section_level("fss_", 2 + nk, 1 + nk, walker, level)
 
     def fss_binner_finish(self, walker=0, level=None):
         """dqmc_mc_fss_binned of one walker at `level` (None: the reliable level)"""
-        out = McFssBinned()
-        self._c(lib().dqmc_mc_fss_binner_finish(self._h, walker, -1 if level is None else int(level), C.byref(out)))
-        return out
+        return self._section_finish("fss_", McFssBinned, walker, level)
 
     def _binned_fss_walker(self, walker, level):
         """{name: (mean, variance of the mean at `level`, the same at level 0 or None)} of one walker; S, xi as lists"""
@@ -783,38 +817,10 @@ class MC(_MCBase):
         the binned covariances of (M2, M4) and (M2, S_k): {"M2", "M4", "U4": {...}, "S", "xi": [{...} per k], "count",
         "level"}.  `walkers=[...]` pools chains of equal beta under the rules of binned(): U4 and xi are formed per
         walker first, std_error = sqrt(sum_w var_w) / W, plus std_error_walkers."""
-        pooled = walkers is not None
-        ws = [int(w) for w in walkers] if pooled else [walker]
-        if not ws:
-            raise ValueError("binned_fss: no walker given")
-        if any(self.betas[w] != self.betas[ws[0]] for w in ws):
-            raise ValueError("binned_fss: the pooled walkers must share one beta")
-        per = [self._binned_fss_walker(w, level) for w in ws]
-        W = float(len(ws))
-
-        def pool(entries):
-            means = np.array([e[0] for e in entries])
-            vl = float(np.sum([e[1] for e in entries]))
-            mean = float(means.sum() / W)
-            o = {"mean": mean, "std_error": (math.sqrt(max(vl, 0.0)) if vl == vl else vl) / W}
-            if entries[0][2] is not None:
-                with np.errstate(invalid="ignore", divide="ignore"):
-                    o["tau"] = float(0.5 * (np.float64(vl) / np.sum([e[2] for e in entries]) - 1.0))
-            if pooled:
-                o["std_error_walkers"] = (math.sqrt(float(((means - mean) ** 2).sum()) / (W * (W - 1.0)))
-                                          if W >= 2 else float("nan"))
-            return o
-
-        out = {"count": per[0][1], "level": per[0][2]}
-        for name in ("M2", "M4", "U4"):
-            out[name] = pool([p[0][name] for p in per])
-        for name in ("S", "xi"):
-            out[name] = [pool([p[0][name][k] for p in per]) for k in range(len(per[0][0][name]))]
+        out = pool_walkers("binned_fss", self.betas, walker, walkers, lambda w: self._binned_fss_walker(w, level))
         L = getattr(self.model.l, "L", None)
         if L is not None:
             out["xi_over_L"] = [{key: v / float(L) for key, v in o.items()} for o in out["xi"]]
-        if pooled:
-            out["n_walkers"] = len(ws)
         return out
 
     def series(self, walker=0):

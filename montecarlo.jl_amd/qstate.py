@@ -15,7 +15,7 @@ from . import checkpoint as _ckpt
 from ._lib import (DQMCError, ERR_INVALID, ERR_STATE, QsBinned, QsClusterStats, QsExchangeStats, QsParams, QsScaling,
                    QsScalingBinned, QsStats, QsStiffness, QsStiffnessBinned, lib)
 from .lattices import bond_classes
-from .mc import _MCBase, _choose_lattice, _delta_var, _llround, _xi, q30_tables, reciprocal_vectors
+from .mc import _MCBase, _choose_lattice, _delta_var, _llround, _xi, pool_walkers, q30_tables, reciprocal_vectors
 
 Q_MAX = 64
 Q30 = 2.0 ** 30
@@ -201,6 +201,7 @@ class QStateMC(_MCBase):
     raise NotImplementedError."""
     _abi = "dqmc_qs_"
     _flavor = "mc_qstate"
+    _ExchangeStats = QsExchangeStats
 
     def __init__(self, model, beta=None, T=None, n_walkers=1, seed=123, first_walker=0, thermalization=0, sweeps=1000,
                  measure_rate=1, print_rate=1000, global_moves=False, global_rate=5, device_id=0, series_capacity=0,
@@ -325,63 +326,16 @@ class QStateMC(_MCBase):
         self._c(lib().dqmc_qs_get_cluster_stats(self._h, walker, C.byref(st)))
         return st
 
-    # ---- replica exchange
-    def set_exchange(self, n_replicas, rate):
-        """dqmc_qs_set_exchange: ladders of n_replicas consecutive walkers (0 or 1: none), a round after every rate-th
-        sweep, behind its cluster move and before its measurement (0: none); resets the exchange cursor, the replica
-        labels and the exchange counters"""
-        self._c(lib().dqmc_qs_set_exchange(self._h, int(n_replicas), int(rate)))
-        self.n_replicas, self.exchange_rate = int(n_replicas), int(rate)
-
-    def exchange(self):
-        """one exchange round by hand (dqmc_qs_exchange), counted in the exchange stats, no measurement"""
-        self._c(lib().dqmc_qs_exchange(self._h))
-
-    def exchange_stats(self, walker=0):
-        """prop_exchange and acc_exchange of the pair (walker, walker + 1), the label `replica` of the configuration
-        now in the slot, and `rounds` (the exchange cursor)"""
-        st = QsExchangeStats()
-        self._c(lib().dqmc_qs_get_exchange_stats(self._h, walker, C.byref(st)))
-        return st
-
-    def replicas(self):
-        """the replica labels of all slots: replicas()[w] is the ladder-local index of the slot in which the
-        configuration now in slot w started"""
-        return np.array([self.exchange_stats(w).replica for w in range(self.n_walkers)], dtype=np.int64)
-
-    # ---- error bars
-    def enable_binning(self, capacity=None):
-        """a logarithmic binner per walker over [E, E2, |M|, M2, M2, M4] (capacity None: 100000 measurements), pushed
-        on the device where the measurement is taken; enabling again starts anew.  A sweep() whose measurements would
-        pass the capacity raises before anything runs."""
-        self._c(lib().dqmc_qs_binner_enable(self._h, 0 if capacity is None else int(capacity)))
-        self._binning = 0 if capacity is None else int(capacity)
-
-    def binner_size(self):
-        """(levels, pushes so far)"""
-        L, T = C.c_int32(), C.c_int64()
-        self._c(lib().dqmc_qs_binner_size(self._h, C.byref(L), C.byref(T)))
-        return L.value, T.value
-
-    def binner_reliable_level(self):
-        lv = C.c_int32()
-        self._c(lib().dqmc_qs_binner_reliable_level(self._h, C.byref(lv)))
-        return lv.value
-
+    # ---- replica exchange: set_exchange, exchange, exchange_stats, replicas (_MCBase)
+    # ---- error bars (enable_binning, binner_size, binner_reliable_level: _MCBase)
     def binner_level(self, walker, level):
         """(x_sum[6], x2_sum[6], xy_sum[3], count) of one level of one walker: elements [E, E2, |M|, M2, M2, M4], pairs
         (E, E2), (|M|, M2) and (M2, M4)"""
-        xs, x2, xy, n = np.zeros(6), np.zeros(6), np.zeros(3), C.c_int64()
-        dp = C.POINTER(C.c_double)
-        self._c(lib().dqmc_qs_binner_get_level(self._h, walker, level, xs.ctypes.data_as(dp), x2.ctypes.data_as(dp),
-                                               xy.ctypes.data_as(dp), C.byref(n)))
-        return xs, x2, xy, n.value
+        return self._section_level("", 6, 3, walker, level)
 
     def binner_finish(self, walker=0, level=None):
         """dqmc_qs_binned of one walker at `level` (None: the reliable level)"""
-        out = QsBinned()
-        self._c(lib().dqmc_qs_binner_finish(self._h, walker, -1 if level is None else int(level), C.byref(out)))
-        return out
+        return self._section_finish("", QsBinned, walker, level)
 
     def _binned_walker(self, walker, level):
         """per observable (mean, variance of the mean at `level`, the same at level 0 or None) of one walker"""
@@ -413,30 +367,11 @@ class QStateMC(_MCBase):
         MC.binned does: mean = sum_w mean_w / W, std_error = sqrt(sum_w var_w) / W (C, chi and U4 formed per walker
         first), tau from the summed variances, plus std_error_walkers = sqrt(sum_w (mean_w - mean)^2 / (W (W - 1))).
         Under replica exchange the values are those of the slot: "at beta_w"."""
-        pooled = walkers is not None
-        ws = [int(w) for w in walkers] if pooled else [walker]
-        if not ws:
-            raise ValueError("binned: no walker given")
-        if any(self.betas[w] != self.betas[ws[0]] for w in ws):
-            raise ValueError("binned: the pooled walkers must share one beta")
-        per = [self._binned_walker(w, level) for w in ws]
-        W = float(len(ws))
-        out = {"Energy": {}, "Magn": {}, "count": per[0][1], "level": per[0][2]}
-        for group, names in (("Energy", ("E", "E2", "e", "C")), ("Magn", ("M", "M2", "M4", "m", "chi", "U4"))):
-            for k in names:
-                means = np.array([p[0][k][0] for p in per])
-                vl = float(np.sum([p[0][k][1] for p in per]))
-                mean = float(means.sum() / W)
-                o = {"mean": mean, "std_error": (math.sqrt(max(vl, 0.0)) if vl == vl else vl) / W, "tau": float("nan")}
-                if per[0][0][k][2] is not None:
-                    with np.errstate(invalid="ignore", divide="ignore"):
-                        o["tau"] = float(0.5 * (np.float64(vl) / np.sum([p[0][k][2] for p in per]) - 1.0))
-                if pooled:
-                    o["std_error_walkers"] = (math.sqrt(float(((means - mean) ** 2).sum()) / (W * (W - 1.0)))
-                                              if W >= 2 else float("nan"))
-                out[group][k] = o
-        if pooled:
-            out["n_walkers"] = len(ws)
+        p = pool_walkers("binned", self.betas, walker, walkers, lambda w: self._binned_walker(w, level),
+                         derived_tau=float("nan"))
+        out = {"Energy": {k: p.pop(k) for k in ("E", "E2", "e", "C")},
+               "Magn": {k: p.pop(k) for k in ("M", "M2", "M4", "m", "chi", "U4")}}
+        out.update(p)
         return out
 
     # ---- finite-size scaling
@@ -503,17 +438,11 @@ class QStateMC(_MCBase):
         """(x_sum[1 + n_k], x2_sum[1 + n_k], xy_sum[n_k], count) of one level of one walker of the binner's scaling
         section: elements [M2, S_0 ..], pairs (M2, S_0) .."""
         nk = 0 if self.k_vectors is None else len(self.k_vectors)
-        xs, x2, xy, n = np.zeros(1 + nk), np.zeros(1 + nk), np.zeros(max(nk, 1)), C.c_int64()
-        dp = C.POINTER(C.c_double)
-        self._c(lib().dqmc_qs_scaling_binner_get_level(self._h, walker, level, xs.ctypes.data_as(dp),
-                                                       x2.ctypes.data_as(dp), xy.ctypes.data_as(dp), C.byref(n)))
-        return xs, x2, xy[:nk], n.value
+        return self._section_level("scaling_", 1 + nk, nk, walker, level)
 
     def scaling_binner_finish(self, walker=0, level=None):
         """dqmc_qs_scaling_binned of one walker at `level` (None: the reliable level)"""
-        out = QsScalingBinned()
-        self._c(lib().dqmc_qs_scaling_binner_finish(self._h, walker, -1 if level is None else int(level), C.byref(out)))
-        return out
+        return self._section_finish("scaling_", QsScalingBinned, walker, level)
 
     def _binned_scaling_walker(self, walker, level):
         """{name: (mean, variance of the mean at `level`, the same at level 0 or None)} of one walker; S, xi as lists"""
@@ -533,36 +462,10 @@ class QStateMC(_MCBase):
         covariance of (M2, S_k): {"M2": {...}, "S", "xi": [{...} per k], "count", "level"}.  `walkers=[...]` pools chains
         of equal beta under the rules of binned(): xi is formed per walker first, std_error = sqrt(sum_w var_w) / W,
         plus std_error_walkers."""
-        pooled = walkers is not None
-        ws = [int(w) for w in walkers] if pooled else [walker]
-        if not ws:
-            raise ValueError("binned_scaling: no walker given")
-        if any(self.betas[w] != self.betas[ws[0]] for w in ws):
-            raise ValueError("binned_scaling: the pooled walkers must share one beta")
-        per = [self._binned_scaling_walker(w, level) for w in ws]
-        W = float(len(ws))
-
-        def pool(entries):
-            means = np.array([e[0] for e in entries])
-            vl = float(np.sum([e[1] for e in entries]))
-            mean = float(means.sum() / W)
-            o = {"mean": mean, "std_error": (math.sqrt(max(vl, 0.0)) if vl == vl else vl) / W}
-            if entries[0][2] is not None:
-                with np.errstate(invalid="ignore", divide="ignore"):
-                    o["tau"] = float(0.5 * (np.float64(vl) / np.sum([e[2] for e in entries]) - 1.0))
-            if pooled:
-                o["std_error_walkers"] = (math.sqrt(float(((means - mean) ** 2).sum()) / (W * (W - 1.0)))
-                                          if W >= 2 else float("nan"))
-            return o
-
-        out = {"count": per[0][1], "level": per[0][2], "M2": pool([p[0]["M2"] for p in per])}
-        for name in ("S", "xi"):
-            out[name] = [pool([p[0][name][k] for p in per]) for k in range(len(per[0][0][name]))]
+        out = pool_walkers("binned_scaling", self.betas, walker, walkers, lambda w: self._binned_scaling_walker(w, level))
         L = getattr(self.model.l, "L", None)
         if L is not None:
             out["xi_over_L"] = [{key: v / float(L) for key, v in o.items()} for o in out["xi"]]
-        if pooled:
-            out["n_walkers"] = len(ws)
         return out
 
     # ---- helicity modulus
@@ -632,17 +535,11 @@ class QStateMC(_MCBase):
         """(x_sum[2 n_dir], x2_sum[2 n_dir], xy_sum[n_dir], count) of one level of one walker of the binner's stiffness
         section: elements [T_0, J2_0, T_1, J2_1 ..], pairs (T_mu, J2_mu)"""
         nd = self._n_dir()
-        xs, x2, xy, n = np.zeros(max(2 * nd, 1)), np.zeros(max(2 * nd, 1)), np.zeros(max(nd, 1)), C.c_int64()
-        dp = C.POINTER(C.c_double)
-        self._c(lib().dqmc_qs_stiffness_binner_get_level(self._h, walker, level, xs.ctypes.data_as(dp),
-                                                         x2.ctypes.data_as(dp), xy.ctypes.data_as(dp), C.byref(n)))
-        return xs[:2 * nd], x2[:2 * nd], xy[:nd], n.value
+        return self._section_level("stiffness_", 2 * nd, nd, walker, level)
 
     def stiffness_binner_finish(self, walker=0, level=None):
         """dqmc_qs_stiffness_binned of one walker at `level` (None: the reliable level)"""
-        out = QsStiffnessBinned()
-        self._c(lib().dqmc_qs_stiffness_binner_finish(self._h, walker, -1 if level is None else int(level), C.byref(out)))
-        return out
+        return self._section_finish("stiffness_", QsStiffnessBinned, walker, level)
 
     def _binned_stiffness_walker(self, walker, level):
         """{name: [(mean, variance of the mean at `level`, the same at level 0 or None) per direction]} of one walker"""
@@ -663,34 +560,8 @@ class QStateMC(_MCBase):
         (1 / N, -beta / N) on the binned covariance of (T_mu, J2_mu): {"T", "J2", "Upsilon": [{...} per direction],
         "count", "level"}.  `walkers=[...]` pools chains of equal beta under the rules of binned_scaling(): Upsilon is
         formed per walker first, std_error = sqrt(sum_w var_w) / W, plus std_error_walkers."""
-        pooled = walkers is not None
-        ws = [int(w) for w in walkers] if pooled else [walker]
-        if not ws:
-            raise ValueError("binned_stiffness: no walker given")
-        if any(self.betas[w] != self.betas[ws[0]] for w in ws):
-            raise ValueError("binned_stiffness: the pooled walkers must share one beta")
-        per = [self._binned_stiffness_walker(w, level) for w in ws]
-        W = float(len(ws))
-
-        def pool(entries):
-            means = np.array([e[0] for e in entries])
-            vl = float(np.sum([e[1] for e in entries]))
-            mean = float(means.sum() / W)
-            o = {"mean": mean, "std_error": (math.sqrt(max(vl, 0.0)) if vl == vl else vl) / W}
-            if entries[0][2] is not None:
-                with np.errstate(invalid="ignore", divide="ignore"):
-                    o["tau"] = float(0.5 * (np.float64(vl) / np.sum([e[2] for e in entries]) - 1.0))
-            if pooled:
-                o["std_error_walkers"] = (math.sqrt(float(((means - mean) ** 2).sum()) / (W * (W - 1.0)))
-                                          if W >= 2 else float("nan"))
-            return o
-
-        out = {"count": per[0][1], "level": per[0][2]}
-        for name in ("T", "J2", "Upsilon"):
-            out[name] = [pool([p[0][name][m] for p in per]) for m in range(len(per[0][0][name]))]
-        if pooled:
-            out["n_walkers"] = len(ws)
-        return out
+        return pool_walkers("binned_stiffness", self.betas, walker, walkers,
+                            lambda w: self._binned_stiffness_walker(w, level))
 
     def stats(self, walker=0):
         st = QsStats()
